@@ -21,6 +21,9 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
                 40 % target names) and ``roofline.classes`` the per-class split (ms, TF/s per step).
   cpu_baseline  the CPU oracle (port of the reference's math, ATen CPU ops) on a bounded sample, all host cores this
                 process may use, median of 5 runs after 2 warm-ups
+
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0) as DIR/<name>.npy (``dump_outputs``); weights and
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -118,6 +121,45 @@ def cpu_baseline(sd, H, W, quality, budget_s=24.0):
                       f"torch CPU fp32, {cores} threads"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out, out_dir, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write every tensor of a ``forward_single_quality`` result as ``out_dir/<name>.npy`` (nested keys joined with "_",
+    e.g. ``likelihoods_y``): float64 tensors stay float64, all others become float32.  The files share ``budget_bytes``
+    equally; a tensor larger than its share is written as a fixed sample, the flattened elements at sorted positions
+    drawn by a generator seeded with DUMP_SAMPLE_SEED (the positions depend only on the tensor's size, so every run and
+    build samples the same ones).  Returns {name: (shape written, full shape)}."""
+    import numpy as np
+    tensors = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k, w in v.items():
+                walk(f"{prefix}_{k}" if prefix else k, w)
+        elif torch.is_tensor(v):
+            tensors[prefix] = v
+
+    walk("", out)
+    os.makedirs(out_dir, exist_ok=True)
+    share = (budget_bytes - 4096 * len(tensors)) // max(len(tensors), 1)        # 4 KB per file for the .npy header
+    written = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:cap].sort().values
+            a = t.reshape(-1)[idx.to(t.device)]
+        else:
+            a = t
+        a = a.cpu().contiguous().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (tuple(a.shape), tuple(t.shape))
+    return written
+
+
 def self_launch(argv, n: int, script: str = None) -> int:
     """``python bench.py --gpus N`` with no launcher around it: start N ranks as CHILD processes (one per GPU)
     through torch.distributed.run — nothing in this parent has touched the GPU — relay their output and
@@ -191,7 +233,12 @@ def main():
                          "REM fine-tune steps on this GPU's share of the batch)")
     ap.add_argument("--dry", action="store_true",
                     help="rehearse rank setup / sharding / aggregation without touching a GPU (CPU test of the N>1 entry)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all (larger tensors as a fixed seeded sample)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], a.gpus))
@@ -256,6 +303,10 @@ def main():
     dt = sharding.max_over_ranks(dt, red_dev)                 # slowest rank (RCCL all-reduce MAX)
     ms_step = dt / a.steps * 1e3
     mp_s = sharding.whole_job_megapixels_per_s(B, H, W, a.steps, world, dt)
+    if rank == 0 and a.dump_outputs:
+        # before anything below reruns the plan: `out` holds views of the plan's buffers (clone=False)
+        dumped = dump_outputs(out, a.dump_outputs)
+        print(f"[bench] dumped {len(dumped)} arrays of the last timed step to {a.dump_outputs}", file=sys.stderr, flush=True)
 
     # ---- roofline of the dominant kernel, measured live with HIP events (eager replay, same plan)
     roof = None

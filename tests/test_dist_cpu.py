@@ -152,6 +152,37 @@ def test_bench_entry_launches_its_own_ranks():
     assert abs(rec["value"] - 2 * 32 * 65536 * 4 / 1e6 / (rec["ms_per_step"] * 4e-3)) / rec["value"] < 1e-3
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: one .npy per tensor of the result (nested keys joined), float32 / float64 only, the
+    whole set inside the byte budget, small tensors whole, large ones as the same seeded sample in every run."""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(1)
+    out = {"x_hat": torch.rand(2, 3, 64, 64, generator=g),
+           "likelihoods": {"y": torch.rand(2, 8, 16, 16, generator=g).permute(0, 2, 3, 1).permute(0, 3, 1, 2),
+                           "z": torch.rand(2, 4, 2, 2, generator=g)},
+           "log2_likelihood_sum": torch.rand(2, 2, dtype=torch.float64, generator=g),
+           "mask": torch.rand(2, 8, 4, 4, generator=g) > 0.5, "mu_prog": []}
+    budget = 64 << 10
+    w1 = bench.dump_outputs(out, str(tmp_path / "a"), budget_bytes=budget)
+    w2 = bench.dump_outputs(out, str(tmp_path / "b"), budget_bytes=budget)
+    names = {"x_hat", "likelihoods_y", "likelihoods_z", "log2_likelihood_sum", "mask"}
+    assert set(w1) == names and w1 == w2
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == (np.float64 if n == "log2_likelihood_sum" else np.float32) and np.array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "likelihoods_z.npy"), out["likelihoods"]["z"].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "mask.npy"), out["mask"].float().numpy())
+    xs = np.load(tmp_path / "a" / "x_hat.npy")                    # 24576 elements, share ~2 K: a sample of the flat tensor
+    assert xs.ndim == 1 and 0 < xs.size < out["x_hat"].numel() and np.isin(xs, out["x_hat"].numpy().ravel()).all()
+
+
 def test_bucket_partition_layout():
     """The first-stage gradient buffer is cut into buckets in the order the backward finishes the parameters: disjoint
     cover, every bucket but the last at least the target size, ready steps monotone and closing with the plan."""
