@@ -730,36 +730,10 @@ def lower_rem_blocks(plan: Plan, mods: Sequence[Ly.LatentRateReduction], y_cks: 
 # =============================================================================
 # REM fine-tune: taped forward + backward lowering            (train.py:223-226, training/step.py:56-95)
 # =============================================================================
-class TrainPacks:
-    """Persistent packed weights of the TRAINED convolutions (forward form and data-gradient form), refreshed
-    in place at the head of every step: the optimiser changes the parameters between steps while the plan's
-    pre-marshalled launches keep their pointers."""
-
-    def __init__(self, convs: Sequence[Ly.Conv2d], need_dgrad: Sequence[Ly.Conv2d]):
-        self.convs = list(convs)
-        self.f = {id(c): ops.pack_conv(c.weight, c.bias, 1) for c in self.convs}
-        self.d = {id(c): ops.pack_conv_dgrad(c.weight) for c in need_dgrad}
-        self._dg = list(need_dgrad)
-
-    def fwd(self, c) -> ops.Packed:
-        return self.f[id(c)]
-
-    def dgrad(self, c) -> ops.Packed:
-        return self.d[id(c)]
-
-    def record_refresh(self, plan: Plan):
-        def refresh():
-            with ops.pack_batch():               # one grouped launch per 32 repacks instead of one launch each
-                for c in self.convs:
-                    ops.repack_conv(c.weight, c.bias, self.f[id(c)])
-                for c in self._dg:
-                    ops.repack_conv(c.weight, None, self.d[id(c)], dgrad=True)
-        plan.call(refresh, f"repack {len(self.convs)}+{len(self._dg)} trained convs")
-
-
 def rem_trained_convs(mods: Sequence[Ly.LatentRateReduction]):
-    """(all convs, convs whose data gradient is needed) of K REM blocks.  The first ResidualBlock of each of the
-    three input branches feeds from frozen tensors, so its conv1 / skip need no data gradient."""
+    """(all convs, convs whose data gradient is needed) of K REM blocks: the arguments of gs_train.TransformPacks.  The
+    first ResidualBlock of each of the three input branches feeds from frozen tensors, so its conv1 / skip need no data
+    gradient."""
     allc, dg = [], []
     for m in mods:
         for name in ("enc_base_rep", "enc_progressive_entropy_params", "enc_base_entropy_params", "enc"):
@@ -772,23 +746,23 @@ def rem_trained_convs(mods: Sequence[Ly.LatentRateReduction]):
     return allc, dg
 
 
-def _rb_forward_taped(plan: Plan, blocks, ins, packs: TrainPacks):
+def _rb_forward_taped(plan: Plan, blocks, ins, packs: "gs_train.TransformPacks"):
     """ResidualBlock forward keeping what the backward needs: h1a = LeakyReLU(conv1 x), o2 = LeakyReLU(conv2 h1a)
     (the sign of a LeakyReLU's output is the sign of its input), out = o2 + skip(x)."""
     h = [plan.buf(i[0].B, i[0].H, i[0].W, b.conv1.out_channels) for b, i in zip(blocks, ins)]
-    probs = [ops.conv_problem(packs.fwd(b.conv1), i, o, L.ACT_LEAKY) for b, i, o in zip(blocks, ins, h)]
+    probs = [ops.conv_problem(packs.f[id(b.conv1)], i, o, L.ACT_LEAKY) for b, i, o in zip(blocks, ins, h)]
     idn = []
     for b, i in zip(blocks, ins):
         if b.skip is not None:
             sv = plan.buf(i[0].B, i[0].H, i[0].W, b.skip.out_channels)
-            probs.append(ops.conv_problem(packs.fwd(b.skip), i, sv))
+            probs.append(ops.conv_problem(packs.f[id(b.skip)], i, sv))
             idn.append(sv)
         else:
             assert len(i) == 1
             idn.append(i[0])
     plan.conv(probs)
     o2 = [plan.buf(v.B, v.H, v.W, b.conv2.out_channels) for b, v in zip(blocks, h)]
-    plan.conv([ops.conv_problem(packs.fwd(b.conv2), [hv], o, L.ACT_LEAKY) for b, hv, o in zip(blocks, h, o2)])
+    plan.conv([ops.conv_problem(packs.f[id(b.conv2)], [hv], o, L.ACT_LEAKY) for b, hv, o in zip(blocks, h, o2)])
     outs = [plan.buf(v.B, v.H, v.W, v.C) for v in o2]
     for a, b_, o in zip(o2, idn, outs):
         plan.call(lambda a=a, b_=b_, o=o: ops.add(b_, a, o), "rb residual add")     # same order as post + act(.)
@@ -796,7 +770,7 @@ def _rb_forward_taped(plan: Plan, blocks, ins, packs: TrainPacks):
     return outs, recs
 
 
-def lower_rem_blocks_train(plan: Plan, mods, y_cks, ep_bases, ep_progs, atts, outs, packs: TrainPacks) -> dict:
+def lower_rem_blocks_train(plan: Plan, mods, y_cks, ep_bases, ep_progs, atts, outs, packs: "gs_train.TransformPacks") -> dict:
     """Forward of K REM blocks (same arithmetic as :func:`lower_rem_blocks`) recording a tape."""
     K = len(mods)
     m0 = mods[0]
@@ -825,7 +799,7 @@ def lower_rem_blocks_train(plan: Plan, mods, y_cks, ep_bases, ep_progs, atts, ou
     return tape
 
 
-def _rb_backward(plan: Plan, recs, d_outs, need_dx: bool, packs: TrainPacks, grads: Dict[int, torch.Tensor]):
+def _rb_backward(plan: Plan, recs, d_outs, need_dx: bool, packs: "gs_train.TransformPacks", grads: Dict[int, torch.Tensor]):
     """Backward of K ResidualBlocks in lockstep.  ``grads[id(param)]`` are the gradient buffers (parameter
     layout).  Returns dL/dx per block (one View over the concatenated input channels) or None."""
     g = lambda p: grads[id(p)]
@@ -837,7 +811,7 @@ def _rb_backward(plan: Plan, recs, d_outs, need_dx: bool, packs: TrainPacks, gra
         wg += ops.wgrad_problems([r["h1a"]], t, g(b.conv2.weight), g(b.conv2.bias))
     plan.wgrad(wg)
     dh1a = [plan.buf(r["h1a"].B, r["h1a"].H, r["h1a"].W, r["h1a"].C) for r in recs]
-    plan.conv([ops.conv_problem(packs.dgrad(r["block"].conv2), [t], o) for r, t, o in zip(recs, dh2, dh1a)])
+    plan.conv([ops.conv_problem(packs.d[id(r["block"].conv2)], [t], o) for r, t, o in zip(recs, dh2, dh1a)])
     dh1 = [plan.buf(v.B, v.H, v.W, v.C) for v in dh1a]
     wg = []
     for r, a, t, do in zip(recs, dh1a, dh1, d_outs):
@@ -855,16 +829,16 @@ def _rb_backward(plan: Plan, recs, d_outs, need_dx: bool, packs: TrainPacks, gra
     sk = [(r, do) for r, do in zip(recs, d_outs) if r["block"].skip is not None]
     if sk:
         tmp = {id(r): plan.buf(r["o2"].B, r["o2"].H, r["o2"].W, c) for (r, _), c in zip(sk, [sum(v.C for v in r["x"]) for r, _ in sk])}
-        plan.conv([ops.conv_problem(packs.dgrad(r["block"].skip), [do], tmp[id(r)]) for r, do in sk])
+        plan.conv([ops.conv_problem(packs.d[id(r["block"].skip)], [do], tmp[id(r)]) for r, do in sk])
     for r, do in zip(recs, d_outs):
         via.append(tmp[id(r)] if r["block"].skip is not None else do)
-    plan.conv([ops.conv_problem(packs.dgrad(r["block"].conv1), [t], o, post=p_)
+    plan.conv([ops.conv_problem(packs.d[id(r["block"].conv1)], [t], o, post=p_)
                for r, t, o, p_ in zip(recs, dh1, dx, via)])
     return dx
 
 
 def lower_rem_backward(plan: Plan, tape: dict, mods, d_mu: Sequence[View], d_sigma: Sequence[View], atts: Sequence[View],
-                       packs: TrainPacks, grads: Dict[int, torch.Tensor]):
+                       packs: "gs_train.TransformPacks", grads: Dict[int, torch.Tensor]):
     """dL/d(REM parameters) from dL/d(mu', sigma') of K slices: res = identity + ret * att  (rem.py:139-141),
     so d ret = d res * att; nothing upstream of the REM inputs is trainable (train.py:223-226)."""
     K = tape["K"]

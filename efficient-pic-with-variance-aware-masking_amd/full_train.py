@@ -31,121 +31,13 @@ from . import engine as E
 from . import gs_train as G
 from . import layers as Ly
 from . import ops
+from .gs_train import lower_stacks_backward, lower_stacks_train
 from .ops import View
 
 BUCKET_BYTES = 25 * 1024 * 1024
 WGRAD_BRANCH = 7                # stream branch of the backward plan's weight-gradient launches
 WGRAD_SIDE_DEFAULT = "3"
 GS_BASE_BRANCH = 1              # the base decoder beside the progressive slice chain (forward and backward)
-
-
-# ============================================================================= generic conv stacks with a tape
-def _layer_out(m, v: View):
-    if isinstance(m, Ly.SubpelConv):
-        return 2 * v.H, 2 * v.W, m.out_ch
-    if m.stride == 2:
-        return v.H // 2, v.W // 2, m.out_channels
-    return v.H, v.W, m.out_channels
-
-
-def lower_stacks_train(plan: E.Plan, stacks: Sequence[nn.Sequential], inputs: Sequence[Sequence[View]],
-                       outs: Sequence[Optional[View]], packs: Sequence[G.TransformPacks]) -> List[dict]:
-    """K structurally identical conv stacks (conv / subpel layers with GELU between, no activation after the last:
-    models/pic.py:83-164, builder.py:72-135) in lockstep, keeping every layer's input segments and pre-activation.
-    The last layer writes ``outs[k]`` when given.  A trained stack runs its first layer whole (the eval plans hoist the
-    hyperprior part, engine.lower_stack_heads: same sum, different association — fp32 rounding apart)."""
-    K = len(stacks)
-    lay = [E.conv_layers(s) for s in stacks]
-    depth = len(lay[0])
-    assert all(len(l) == depth for l in lay)
-    cur: List[List[View]] = [list(i) for i in inputs]
-    tapes = [dict(stack=stacks[k], x=[], z=[], out=None) for k in range(K)]
-    for d in range(depth):
-        probs, zs, nxt = [], [], []
-        last = d == depth - 1
-        for k in range(K):
-            m, act = lay[k][d]
-            assert act == (L.ACT_NONE if last else L.ACT_GELU)
-            v0 = cur[k][0]
-            Ho, Wo, Co = _layer_out(m, v0)
-            z = outs[k] if (last and outs[k] is not None) else plan.buf(v0.B, Ho, Wo, Co)
-            if last:
-                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], z))
-            else:                       # GELU in the epilogue (as the eval plans), pre-activation kept as the second output
-                # the activation is read by the next layer's convolution and by that layer's weight gradient only: where
-                # both take bf16x3 planes it is written as planes (one split, by the producer), as in the eval stacks
-                nm = lay[k][d + 1][0]
-                p3 = Co % 8 == 0 and isinstance(m, Ly.Conv2d) and isinstance(nm, Ly.Conv2d) and nm.kernel_size == 3 and \
-                    nm.stride == 1 and ops.train_tape_planes(Ho, Wo) and v0.B * Ho * Wo <= E.P3_MAX_PIXELS
-                a = plan.buf3(v0.B, Ho, Wo, Co) if p3 else plan.buf(v0.B, Ho, Wo, Co)
-                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], a, L.ACT_GELU, preact=z))
-                nxt.append([a])
-            tapes[k]["x"].append(list(cur[k]))
-            tapes[k]["z"].append(z)
-            zs.append(z)
-        plan.conv(probs)
-        if not last:
-            cur = nxt
-        else:
-            for k in range(K):
-                tapes[k]["out"] = zs[k]
-    return tapes
-
-
-def lower_stacks_backward(bw: E.Plan, tapes: Sequence[dict], d_outs: Sequence[View], packs: Sequence[G.TransformPacks],
-                          grads, need_dx: bool = True) -> Optional[List[View]]:
-    """Backward of :func:`lower_stacks_train`: weight / bias gradients of every layer (``grads[id(param)]``) and, with
-    ``need_dx``, dL/d(first layer's concatenated input) per stack — one fresh [B,H,W,C_in] buffer each, whose channel
-    ranges the caller adds into the accumulators of the segments."""
-    K = len(tapes)
-    lay = [E.conv_layers(t["stack"]) for t in tapes]
-    depth = len(lay[0])
-    dz = list(d_outs)
-    for d in range(depth - 1, -1, -1):
-        ms = [lay[k][d][0] for k in range(K)]
-        m0 = ms[0]
-        g_conv = dz                                              # gradient at the convolution's own output grid
-        if isinstance(m0, Ly.SubpelConv):                        # PixelShuffle backward
-            g_conv = []
-            for k in range(K):
-                x0 = tapes[k]["x"][d][0]
-                u = bw.buf(x0.B, x0.H, x0.W, 4 * dz[k].C)
-                bw.call(lambda s=dz[k], u=u: ops.ps2_unshuffle(s, u), "pixel un-shuffle")
-                g_conv.append(u)
-        wg = []
-        for k in range(K):
-            c = ms[k][0] if isinstance(ms[k], Ly.SubpelConv) else ms[k]
-            wg += ops.wgrad_problems(tapes[k]["x"][d], g_conv[k], grads[id(c.weight)], grads[id(c.bias)], stride=c.stride)
-        bw.wgrad(wg)
-        if d == 0 and not need_dx:
-            return None
-        gz = (lambda k: tapes[k]["z"][d - 1]) if d > 0 else (lambda k: None)     # pre-activation of the GELU in front of layer d
-        if not isinstance(m0, Ly.SubpelConv) and m0.stride == 2:
-            if m0.kernel_size == 5:                              # transposed convolution: four phase problems per stack
-                das, probs = [], []
-                for k in range(K):
-                    x0 = tapes[k]["x"][d][0]
-                    assert len(tapes[k]["x"][d]) == 1
-                    o = bw.buf(x0.B, x0.H, x0.W, x0.C)
-                    probs += [ops.conv_problem(p_, [g_conv[k]], o, gelu_z=gz(k)) for p_ in packs[k].d[id(ms[k])]]
-                    das.append(o)
-                bw.conv(probs)
-            else:                                                # k3 s2: zero insertion + stride-1 data-gradient problem
-                ups = []
-                for k in range(K):
-                    x0 = tapes[k]["x"][d][0]
-                    u = bw.buf(x0.B, x0.H, x0.W, g_conv[k].C)
-                    bw.call(lambda s=g_conv[k], u=u: ops.upsample2_zero(s, u), "zero insertion")
-                    ups.append(u)
-                das = [bw.buf(u.B, u.H, u.W, sum(v.C for v in tapes[k]["x"][d])) for k, u in enumerate(ups)]
-                bw.conv([ops.conv_problem(packs[k].d[id(ms[k])], [ups[k]], das[k], gelu_z=gz(k)) for k in range(K)])
-        else:
-            das = [bw.buf(g_conv[k].B, g_conv[k].H, g_conv[k].W, sum(v.C for v in tapes[k]["x"][d])) for k in range(K)]
-            bw.conv([ops.conv_problem(packs[k].d[id(ms[k])], [g_conv[k]], das[k], gelu_z=gz(k)) for k in range(K)])
-        if d == 0:
-            return das
-        dz = das                          # the data-gradient launches applied gelu'(z) of the GELU in front of the layer
-    return None
 
 
 # ============================================================================= analysis transform with a tape
@@ -415,12 +307,7 @@ class FullTrainPlan:
             add(e)
         self.params = order
         self.trainable_ids = trainable_ids
-        offs, tot = [], 0
-        for p in order:
-            offs.append(tot)
-            tot += (p.numel() + 3) // 4 * 4
-        self.flat = torch.zeros(tot, **f32)
-        self.views = [self.flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, order)]
+        self.flat, self.views, offs = G.flat_grads(order, dev)
         self.offsets = offs
         grads = {id(p): g for p, g in zip(order, self.views)}
 
@@ -497,7 +384,7 @@ class FullTrainPlan:
                 ps = list(gs_base.parameters())
                 pos = {id(p_): i for i, p_ in enumerate(order)}
                 lo_ = offs[pos[id(ps[0])]]
-                hi_ = offs[pos[id(ps[-1])]] + (ps[-1].numel() + 3) // 4 * 4
+                hi_ = (offs + [self.flat.numel()])[pos[id(ps[-1])] + 1]
                 tmp = torch.zeros(hi_ - lo_, **f32)
                 bw.keep.append(tmp)
                 g0 = dict(grads)
@@ -666,7 +553,7 @@ class FullTrainPlan:
         # ------------------------------------------------------------------ buckets
         from .sharding import bucket_partition
         self.bucket_bounds, self.bucket_ready = bucket_partition(offs, [p.numel() for p in order],
-                                                                 [self.param_done[id(p)] for p in order], tot, len(bw.steps),
+                                                                 [self.param_done[id(p)] for p in order], self.flat.numel(), len(bw.steps),
                                                                  BUCKET_BYTES)
 
     # ------------------------------------------------------------------------------------------- execution

@@ -1,5 +1,8 @@
-"""Training-mode lowering of a synthesis transform (first schedule: ``--training_type refine_gs``,
-reference train.py:150-157,216-218 — everything frozen except ``g_s[1]``; loss = DistortionLoss, training/loss.py:126-187).
+"""Taped training pieces shared by every training plan: weight packs refreshed in place, taped conv stacks and
+their backward, the flat gradient buffer, and the taped synthesis transform of ``--training_type refine_gs`` (reference
+train.py:150-157,216-218 — everything frozen except ``g_s[1]``; loss = DistortionLoss, training/loss.py:126-187).  The
+REM fine-tune (models._FsqPlan with ``train=True``), refine_gs with or without ``--lrp`` (models._FsqPlan with
+``train_gs``) and the first-stage plan (full_train.FullTrainPlan) all build on them.
 
 Forward: the same kernels as the eval lowering (engine.lower_g_s), but every tensor the backward needs is kept ("tape"):
 pre-activations of the GELUs, the pre-sigmoid gate operand, the IGDN norm pool, qkv.  Activations that the eval path
@@ -32,15 +35,19 @@ _BETA_BOUND = (1e-6 + 2.0 ** -36) ** 0.5         # NonNegativeParametrizer(minim
 
 
 class TransformPacks:
-    """Forward and data-gradient packed weights of every layer of ONE transform stack, re-packed IN PLACE at the head of
-    every step (the optimiser changes the parameters between steps; plans and graphs keep their pointers)."""
+    """Forward and data-gradient packed weights of every layer of ``mods`` (one module or a sequence of them), re-packed IN
+    PLACE at the head of every step (the optimiser changes the parameters between steps; plans and graphs keep their
+    pointers).  ``dgrad``: the stride-1 convolutions that need a data-gradient pack (default: all of them); the others get
+    a forward pack only and no data-gradient repack."""
 
-    def __init__(self, stack: nn.Module):
+    def __init__(self, mods, dgrad: Optional[Sequence[nn.Module]] = None):
         self.f: Dict[int, object] = {}
         self.d: Dict[int, ops.Packed] = {}
         self._refresh = []
         self.keep = []
-        self._walk(stack)
+        self._dgrad = None if dgrad is None else {id(c) for c in dgrad}
+        for mod in ([mods] if isinstance(mods, nn.Module) else mods):
+            self._walk(mod)
 
     def _walk(self, mod):
         if isinstance(mod, Ly.SubpelConv):             # conv3x3 + PixelShuffle(2): a leaf (its inner Conv2d packs phase-major)
@@ -124,14 +131,16 @@ class TransformPacks:
 
     def _add_conv(self, c):
         n, cin, k = c.out_channels, c.in_channels, c.kernel_size
-        f = ops.pack_conv(c.weight, c.bias, 1)
-        d = ops.pack_conv_dgrad(c.weight)
-        self.f[id(c)], self.d[id(c)] = f, d
+        f = self.f[id(c)] = ops.pack_conv(c.weight, c.bias, 1)
+        d = None
+        if self._dgrad is None or id(c) in self._dgrad:
+            d = self.d[id(c)] = ops.pack_conv_dgrad(c.weight)
 
         def refresh():
             ops.repack_weights(c.weight, f.w, L.PACK_CONV, 0, k, k, cin, n)
             ops.repack_bias(c.bias, f.b, L.PACK_CONV, n)
-            ops.repack_weights(c.weight, d.w, L.PACK_CONV_DGRAD, 0, k, k, n, cin)
+            if d is not None:
+                ops.repack_weights(c.weight, d.w, L.PACK_CONV_DGRAD, 0, k, k, n, cin)
         self._refresh.append(refresh)
 
     def _add_linear(self, l):
@@ -192,6 +201,126 @@ class TransformPacks:
                 for fn in fns:
                     fn()
         plan.call(run, f"repack {len(fns)} trained layers")
+
+
+def flat_grads(params: Sequence[torch.Tensor], device):
+    """ONE zero-filled fp32 buffer for the gradients of ``params`` in order, every tensor starting 16-byte aligned:
+    (buffer, per-parameter views, offsets in floats)."""
+    offs, tot = [], 0
+    for p in params:
+        offs.append(tot)
+        tot += (p.numel() + 3) // 4 * 4
+    flat = torch.zeros(tot, dtype=torch.float32, device=device)
+    return flat, [flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)], offs
+
+
+# ============================================================================= generic conv stacks with a tape
+def _layer_out(m, v: View):
+    if isinstance(m, Ly.SubpelConv):
+        return 2 * v.H, 2 * v.W, m.out_ch
+    if m.stride == 2:
+        return v.H // 2, v.W // 2, m.out_channels
+    return v.H, v.W, m.out_channels
+
+
+def lower_stacks_train(plan: E.Plan, stacks: Sequence[nn.Sequential], inputs: Sequence[Sequence[View]],
+                       outs: Sequence[Optional[View]], packs: Sequence[TransformPacks]) -> List[dict]:
+    """K structurally identical conv stacks (conv / subpel layers with GELU between, no activation after the last:
+    models/pic.py:83-164, builder.py:72-135) in lockstep, keeping every layer's input segments and pre-activation.
+    The last layer writes ``outs[k]`` when given.  A trained stack runs its first layer whole (the eval plans hoist the
+    hyperprior part, engine.lower_stack_heads: same sum, different association — fp32 rounding apart)."""
+    K = len(stacks)
+    lay = [E.conv_layers(s) for s in stacks]
+    depth = len(lay[0])
+    assert all(len(l) == depth for l in lay)
+    cur: List[List[View]] = [list(i) for i in inputs]
+    tapes = [dict(stack=stacks[k], x=[], z=[], out=None) for k in range(K)]
+    for d in range(depth):
+        probs, zs, nxt = [], [], []
+        last = d == depth - 1
+        for k in range(K):
+            m, act = lay[k][d]
+            assert act == (L.ACT_NONE if last else L.ACT_GELU)
+            v0 = cur[k][0]
+            Ho, Wo, Co = _layer_out(m, v0)
+            z = outs[k] if (last and outs[k] is not None) else plan.buf(v0.B, Ho, Wo, Co)
+            if last:
+                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], z))
+            else:                       # GELU in the epilogue (as the eval plans), pre-activation kept as the second output
+                # the activation is read by the next layer's convolution and by that layer's weight gradient only: where
+                # both take bf16x3 planes it is written as planes (one split, by the producer), as in the eval stacks
+                nm = lay[k][d + 1][0]
+                p3 = Co % 8 == 0 and isinstance(m, Ly.Conv2d) and isinstance(nm, Ly.Conv2d) and nm.kernel_size == 3 and \
+                    nm.stride == 1 and ops.train_tape_planes(Ho, Wo) and v0.B * Ho * Wo <= E.P3_MAX_PIXELS
+                a = plan.buf3(v0.B, Ho, Wo, Co) if p3 else plan.buf(v0.B, Ho, Wo, Co)
+                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], a, L.ACT_GELU, preact=z))
+                nxt.append([a])
+            tapes[k]["x"].append(list(cur[k]))
+            tapes[k]["z"].append(z)
+            zs.append(z)
+        plan.conv(probs)
+        if not last:
+            cur = nxt
+        else:
+            for k in range(K):
+                tapes[k]["out"] = zs[k]
+    return tapes
+
+
+def lower_stacks_backward(bw: E.Plan, tapes: Sequence[dict], d_outs: Sequence[View], packs: Sequence[TransformPacks],
+                          grads, need_dx: bool = True) -> Optional[List[View]]:
+    """Backward of :func:`lower_stacks_train`: weight / bias gradients of every layer (``grads[id(param)]``) and, with
+    ``need_dx``, dL/d(first layer's concatenated input) per stack — one fresh [B,H,W,C_in] buffer each, whose channel
+    ranges the caller adds into the accumulators of the segments."""
+    K = len(tapes)
+    lay = [E.conv_layers(t["stack"]) for t in tapes]
+    depth = len(lay[0])
+    dz = list(d_outs)
+    for d in range(depth - 1, -1, -1):
+        ms = [lay[k][d][0] for k in range(K)]
+        m0 = ms[0]
+        g_conv = dz                                              # gradient at the convolution's own output grid
+        if isinstance(m0, Ly.SubpelConv):                        # PixelShuffle backward
+            g_conv = []
+            for k in range(K):
+                x0 = tapes[k]["x"][d][0]
+                u = bw.buf(x0.B, x0.H, x0.W, 4 * dz[k].C)
+                bw.call(lambda s=dz[k], u=u: ops.ps2_unshuffle(s, u), "pixel un-shuffle")
+                g_conv.append(u)
+        wg = []
+        for k in range(K):
+            c = ms[k][0] if isinstance(ms[k], Ly.SubpelConv) else ms[k]
+            wg += ops.wgrad_problems(tapes[k]["x"][d], g_conv[k], grads[id(c.weight)], grads[id(c.bias)], stride=c.stride)
+        bw.wgrad(wg)
+        if d == 0 and not need_dx:
+            return None
+        gz = (lambda k: tapes[k]["z"][d - 1]) if d > 0 else (lambda k: None)     # pre-activation of the GELU in front of layer d
+        if not isinstance(m0, Ly.SubpelConv) and m0.stride == 2:
+            if m0.kernel_size == 5:                              # transposed convolution: four phase problems per stack
+                das, probs = [], []
+                for k in range(K):
+                    x0 = tapes[k]["x"][d][0]
+                    assert len(tapes[k]["x"][d]) == 1
+                    o = bw.buf(x0.B, x0.H, x0.W, x0.C)
+                    probs += [ops.conv_problem(p_, [g_conv[k]], o, gelu_z=gz(k)) for p_ in packs[k].d[id(ms[k])]]
+                    das.append(o)
+                bw.conv(probs)
+            else:                                                # k3 s2: zero insertion + stride-1 data-gradient problem
+                ups = []
+                for k in range(K):
+                    x0 = tapes[k]["x"][d][0]
+                    u = bw.buf(x0.B, x0.H, x0.W, g_conv[k].C)
+                    bw.call(lambda s=g_conv[k], u=u: ops.upsample2_zero(s, u), "zero insertion")
+                    ups.append(u)
+                das = [bw.buf(u.B, u.H, u.W, sum(v.C for v in tapes[k]["x"][d])) for k, u in enumerate(ups)]
+                bw.conv([ops.conv_problem(packs[k].d[id(ms[k])], [ups[k]], das[k], gelu_z=gz(k)) for k in range(K)])
+        else:
+            das = [bw.buf(g_conv[k].B, g_conv[k].H, g_conv[k].W, sum(v.C for v in tapes[k]["x"][d])) for k in range(K)]
+            bw.conv([ops.conv_problem(packs[k].d[id(ms[k])], [g_conv[k]], das[k], gelu_z=gz(k)) for k in range(K)])
+        if d == 0:
+            return das
+        dz = das                          # the data-gradient launches applied gelu'(z) of the GELU in front of the layer
+    return None
 
 
 # ============================================================================= forward (taped)
@@ -414,71 +543,3 @@ def lower_g_s_backward(bw: E.Plan, tape: list, x_hat: torch.Tensor, g_xhat: torc
             d = _attention_block_bwd(bw, pk, r, d, grads, need_dx=(not first) or need_input_grad)
     bw.flush_wgrad()
     return d
-
-
-# ============================================================================= latent-residual-prediction stacks (--lrp)
-def lower_lrp_stacks_train(plan: E.Plan, stacks: Sequence[nn.Sequential], inputs: Sequence[Sequence[View]],
-                           rqs: Sequence[View], bases: Sequence[View], outs: Sequence[View],
-                           packs: Sequence[TransformPacks]) -> List[dict]:
-    """K progressive LRP stacks in lockstep with a tape (pic.py:635-641: y_hat_j = rq_j + 0.5 tanh(stack_j(cat(supports,
-    rq_j))) + base_j).  Same kernels as the eval lowering, but every layer writes its pre-activation and the GELU / the
-    0.5 tanh tail are element-wise launches with the epilogue's formulas.  The eval plan computes the hyperprior part of
-    the first layer ahead of the slice loop (engine.lower_stack_heads: same sum, different association); a TRAINED stack
-    runs its first layer whole, so its forward agrees with the eval plan to fp32 rounding, not bit for bit."""
-    K = len(stacks)
-    lay = [E.conv_layers(s) for s in stacks]
-    depth = len(lay[0])
-    cur: List[List[View]] = [list(i) for i in inputs]
-    tapes = [dict(stack=stacks[k], x=[], z=[]) for k in range(K)]
-    for d in range(depth):
-        zs = []
-        probs = []
-        nxt: List[List[View]] = []
-        for k in range(K):
-            m, act = lay[k][d]
-            assert isinstance(m, Ly.Conv2d) and m.stride == 1 and act == (L.ACT_NONE if d == depth - 1 else L.ACT_GELU)
-            v0 = cur[k][0]
-            z = plan.buf(v0.B, v0.H, v0.W, m.out_channels)
-            if d < depth - 1:           # GELU in the epilogue, pre-activation kept as the second output
-                # (as planes where the next layer's convolution and weight gradient both read planes: full_train.lower_stacks_train)
-                p3 = m.out_channels % 8 == 0 and ops.train_tape_planes(v0.H, v0.W) and v0.B * v0.H * v0.W <= E.P3_MAX_PIXELS
-                a = plan.buf3(v0.B, v0.H, v0.W, m.out_channels) if p3 else plan.buf(v0.B, v0.H, v0.W, m.out_channels)
-                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], a, L.ACT_GELU, preact=z))
-                nxt.append([a])
-            else:
-                probs.append(ops.conv_problem(packs[k].f[id(m)], cur[k], z))
-            tapes[k]["x"].append(list(cur[k]))
-            tapes[k]["z"].append(z)
-            zs.append(z)
-        plan.conv(probs)
-        if d < depth - 1:
-            cur = nxt
-        else:
-            for z, rq, yb, o in zip(zs, rqs, bases, outs):
-                plan.call(lambda z=z, rq=rq, yb=yb, o=o: ops.ew(L.EW_HTANH_FWD, [z, rq, yb], [o]), "lrp tail")
-    return tapes
-
-
-def lower_lrp_stacks_backward(bw: E.Plan, tapes: Sequence[dict], d_outs: Sequence[View], packs: Sequence[TransformPacks], grads):
-    """dL/d(parameters of the LRP stacks) from dL/dy_hat_j.  The stacks' inputs (hyperprior means, supports, rq_j) have no
-    trainable producer in this schedule, so the first layer needs no data gradient."""
-    K = len(tapes)
-    lay = [E.conv_layers(t["stack"]) for t in tapes]
-    depth = len(lay[0])
-    dz = []
-    for t, dy in zip(tapes, d_outs):
-        z = t["z"][-1]
-        o = bw.buf(z.B, z.H, z.W, z.C)
-        bw.call(lambda z=z, dy=dy, o=o: ops.ew(L.EW_HTANH_BWD, [z, dy], [o]), "lrp tail bwd")
-        dz.append(o)
-    for d in range(depth - 1, -1, -1):
-        wg = []
-        for k in range(K):
-            m = lay[k][d][0]
-            wg += ops.wgrad_problems(tapes[k]["x"][d], dz[k], grads[id(m.weight)], grads[id(m.bias)])
-        bw.wgrad(wg)
-        if d == 0:
-            break
-        das = [bw.buf(t["z"][d - 1].B, t["z"][d - 1].H, t["z"][d - 1].W, t["z"][d - 1].C) for t in tapes]
-        bw.conv([ops.conv_problem(packs[k].d[id(lay[k][d][0])], [dz[k]], das[k], gelu_z=tapes[k]["z"][d - 1]) for k in range(K)])
-        dz = das                          # the launch applied gelu'(z) of the GELU in front of the layer

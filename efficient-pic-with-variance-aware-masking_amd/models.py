@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import engine as E
+from . import gs_train as G
 from . import layers as Ly
 from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, get_scale_table
@@ -369,7 +370,7 @@ class VarianceMaskingPIC(CompressionModel):
         plan = self._plan(x.detach(), base_only=(quality == 0), train=bool(training), train_gs=train_gs, train_lrp=train_lrp)
         out = plan.execute(x.detach(), pr, None, self.use_graph, clone, noise=noise)
         if train_gs:
-            out["x_hat"] = _GsTrainFn.apply(plan, out["x_hat"], self.use_graph, *plan.gs_params)
+            out["x_hat"] = _FsqTrainFn.apply(plan, out["x_hat"], self.use_graph, *plan.train_params)
         return out
 
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
@@ -650,8 +651,8 @@ class VarianceMaskingPICREM(VarianceMaskingPIC):
         plan = self._plan(x.detach(), base_only=(quality == 0), rem_idx=rem_idx, train=True, own_ck=own)
         out = plan.execute(x.detach(), pr, checkpoint_ref if (rem_idx is not None and not own) else None, self.use_graph,
                            True, noise=noise, ck_pr=ck_pr if own else None)
-        if rem_idx is not None and torch.is_grad_enabled() and any(p.requires_grad for p in plan.rem_params):
-            out["likelihoods"]["y"] = _RemTrainFn.apply(plan, out["likelihoods"]["y"], self.use_graph, *plan.rem_params)
+        if rem_idx is not None and torch.is_grad_enabled() and any(p.requires_grad for p in plan.train_params):
+            out["likelihoods"]["y"] = _FsqTrainFn.apply(plan, out["likelihoods"]["y"], self.use_graph, *plan.train_params)
         return out
 
     def apply_latent_enhancement(self, current_index, quality, quality_bar, y_b_hat, mu_scale_base, mu_scale_enh,
@@ -757,42 +758,29 @@ def _version_sig(mod: nn.Module):
     return tuple(p._version for p in mod.parameters())
 
 
-class _RemTrainFn(torch.autograd.Function):
-    """likelihoods["y"] of the training-mode REM forward as a differentiable function of the REM parameters
-    (the only trainable ones under ``--training_type rems``, train.py:223-226)."""
+def _check_tape(ctx):
+    """The tape lives in the plan's buffers: it belongs to ONE execute() of the plan."""
+    if ctx.plan.generation != ctx.generation:
+        raise RuntimeError(
+            "the training plan for this shape ran again before this backward(): its tape (activations, noise, "
+            "mask) now belongs to the later forward.  Call loss.backward() before the next training forward of "
+            "the same shape (gradient accumulation: backward after every forward).")
+
+
+class _FsqTrainFn(torch.autograd.Function):
+    """One output of a training-mode _FsqPlan as a differentiable function of the parameters the plan trains:
+    likelihoods["y"] under ``--training_type rems`` (the REM parameters, train.py:223-226), x_hat under ``refine_gs``
+    (the synthesis transform's, with ``--lrp`` the progressive LRP stacks' as well, train.py:216-218)."""
 
     @staticmethod
-    def forward(ctx, plan, lik_y, use_graph, *params):
-        ctx.plan, ctx.use_graph = plan, use_graph
-        ctx.generation = plan.generation      # the tape lives in the plan's buffers: it belongs to ONE execute()
-        return lik_y.clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.plan.generation != ctx.generation:
-            raise RuntimeError(
-                "the training plan for this shape ran again before this backward(): its tape (activations, noise, "
-                "mask) now belongs to the later forward.  Call loss.backward() before the next training forward of "
-                "the same shape (gradient accumulation: backward after every forward).")
-        grads = ctx.plan.backward(g, ctx.use_graph)
-        return (None, None, None) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[3:]))
-
-
-class _GsTrainFn(torch.autograd.Function):
-    """x_hat of the training-mode forward as a differentiable function of the synthesis transform's parameters (the only
-    trainable ones under ``--training_type refine_gs``, train.py:216-218)."""
-
-    @staticmethod
-    def forward(ctx, plan, x_hat, use_graph, *params):
+    def forward(ctx, plan, out, use_graph, *params):
         ctx.plan, ctx.use_graph, ctx.generation = plan, use_graph, plan.generation
-        return x_hat.clone()
+        return out.clone()
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.plan.generation != ctx.generation:
-            raise RuntimeError("the training plan for this shape ran again before this backward(): its tape now belongs to "
-                               "the later forward — call loss.backward() before the next training forward of this shape")
-        grads = ctx.plan.backward_gs(g.contiguous(), ctx.use_graph)
+        _check_tape(ctx)
+        grads = ctx.plan._backward(g, ctx.use_graph)
         return (None, None, None) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[3:]))
 
 
@@ -808,9 +796,7 @@ class _FullTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xhat, g_lik, g_z):
-        if ctx.plan.generation != ctx.generation:
-            raise RuntimeError("the training plan for this shape ran again before this backward(): its tape now belongs to "
-                               "the later forward — call loss.backward() before the next training forward of this shape")
+        _check_tape(ctx)
         plan = ctx.plan
         plan.backward(g_xhat, g_lik, g_z, ctx.use_graph, ctx.reducer)
         need = ctx.needs_input_grad[6:]
@@ -834,7 +820,8 @@ class _FsqPlan:
         self.base_only, self.rem_idx = base_only, rem_idx
         self.symbols = symbols
         self.train = train          # additive-noise likelihoods (+ taped REM and a backward plan when rem_idx is set)
-        self.bwd = None
+        self.bwd = None             # backward plan of a training plan (REM fine-tune or refine_gs): see _backward
+        self._bwd_graph = None
         self.generation = 0         # bumped by every execute(): which forward the training tape belongs to
         self.pr = 0.0
         self.graphs: Dict[float, ops.Graph] = {}
@@ -1015,8 +1002,8 @@ class _FsqPlan:
                       [sl(att, j) for j in range(ns)],
                       [([sl(mu_f, j)] if mu_std else []) + [sl(std_f, j)] for j in range(ns)])
             if train:
-                self.rem_params = [p for mod in mods for p in mod.parameters()]
-                self.packs = E.TrainPacks(*E.rem_trained_convs(mods))
+                self.train_params = [p for mod in mods for p in mod.parameters()]
+                self.packs = G.TransformPacks(*E.rem_trained_convs(mods))
                 self.packs.record_refresh(plan)
                 tape = E.lower_rem_blocks_train(plan, mods, *rem_io, self.packs)
             else:
@@ -1038,17 +1025,12 @@ class _FsqPlan:
             if rem_idx is not None:
                 # ---- backward plan: dL/dlik (progressive half) -> (dmu', dsigma') -> REM parameters
                 bw = self.bwd = E.Plan(device)
-                self.glik = bw.buf(B, h, w, d)
+                glik = bw.buf(B, h, w, d)
+                self._bwd_in = lambda g: glik.buf.copy_(g[:, d:].permute(0, 2, 3, 1))       # dL/dlikelihoods["y"], NCHW
                 dmu, dsg = bw.buf(B, h, w, d), bw.buf(B, h, w, d)
                 self.dmu, self.dsg, self.rem_io, self.rem_tape = dmu, dsg, rem_io, tape     # kept for teacher-forced gradient checks
-                flat = torch.zeros(sum(p.numel() for p in self.rem_params), **f32)
-                self.gflat, self.gviews, off = flat, [], 0
-                for p in self.rem_params:
-                    self.gviews.append(flat[off:off + p.numel()].view(p.shape))
-                    off += p.numel()
-                grads = {id(p): g for p, g in zip(self.rem_params, self.gviews)}
-                bw.keep += [flat, self.gviews]
-                bw.call(lambda: ops.gauss_train(yr, mu_f, std_f, nz, y2=y0, mask=self.mask, grad_lik=self.glik,
+                grads = self._grad_buffer()
+                bw.call(lambda: ops.gauss_train(yr, mu_f, std_f, nz, y2=y0, mask=self.mask, grad_lik=glik,
                                                 dmu=dmu, dsigma=dsg), "likelihood backward")
                 E.lower_rem_backward(bw, tape, mods, [sl(dmu, j) for j in range(ns)], [sl(dsg, j) for j in range(ns)],
                                      rem_io[3], self.packs, grads)
@@ -1056,15 +1038,16 @@ class _FsqPlan:
             plan.call(lambda: ops.build_indexes(std_f, table, mask=self.mask, out=self.idx.window(d, d)))
         lrp = None
         if train_lrp:
-            from . import gs_train as G
+            # y_hat_j = rq_j + 0.5 tanh(stack_j(cat(supports, rq_j))) + base_j  (pic.py:635-641); a TRAINED stack runs its
+            # first layer whole (the eval plan hoists the hyperprior part: same sum, different association)
             stacks = [m.lrp_transforms_prog[j] for j in range(ns)]
             lpk = [G.TransformPacks(st) for st in stacks]
             for pk_ in lpk:
                 pk_.record_refresh(plan)
             mh1 = means_h.window(d, d)
-            tapes = G.lower_lrp_stacks_train(plan, stacks, [[mh1] + msups[j] + [sl(rq, j)] for j in range(ns)],
-                                             [sl(rq, j) for j in range(ns)], [sl(yb, j) for j in range(ns)],
-                                             [sl(yp, j) for j in range(ns)], lpk)
+            tapes = G.lower_stacks_train(plan, stacks, [[mh1] + msups[j] + [sl(rq, j)] for j in range(ns)], [None] * ns, lpk)
+            for j in range(ns):
+                plan.call(lambda j=j: ops.ew(L.EW_HTANH_FWD, [tapes[j]["out"], sl(rq, j), sl(yb, j)], [sl(yp, j)]), "lrp tail")
             lrp = dict(tapes=tapes, packs=lpk, params=[p for st in stacks for p in st.parameters()])
         else:
             E.lower_stacks(plan, [m.lrp_transforms_prog[j] for j in range(ns)], [msups[j] + [sl(rq, j)] for j in range(ns)],
@@ -1082,46 +1065,52 @@ class _FsqPlan:
     def _lower_g_s_train(self, plan, dec, y_in, lrp=None):
         """refine_gs: taped synthesis transform + its backward plan (gs_train.py); ``lrp`` = the taped progressive LRP
         stacks when they train too (refine_gs --lrp): their gradients come from dL/dy_hat, the input gradient of g_s."""
-        from . import gs_train as G
-        dev = self.x_in.device
-        self.gs_params = list(dec.parameters()) + (lrp["params"] if lrp else [])
+        self.train_params = list(dec.parameters()) + (lrp["params"] if lrp else [])
         self.gs_packs = G.TransformPacks(dec)
         self.gs_packs.record_refresh(plan)
         tape = G.lower_g_s_train(plan, dec, y_in, self.x_hat, self.gs_packs)
-        bw = self.gs_bwd = E.Plan(dev)
+        bw = self.bwd = E.Plan(self.x_in.device)
         self.g_xhat = torch.zeros_like(self.x_hat)
-        offs, tot = [], 0
-        for p in self.gs_params:                       # every gradient view 16-byte aligned inside one flat bucket
-            offs.append(tot)
-            tot += (p.numel() + 3) // 4 * 4
-        self.gs_flat = torch.zeros(tot, dtype=torch.float32, device=dev)
-        self.gs_views = [self.gs_flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.gs_params)]
-        grads = {id(p): g for p, g in zip(self.gs_params, self.gs_views)}
-        bw.keep += [self.g_xhat, self.gs_flat, self.gs_views]
+        self._bwd_in = self.g_xhat.copy_                                  # dL/dx_hat
+        grads = self._grad_buffer()
+        bw.keep.append(self.g_xhat)
         d_y = G.lower_g_s_backward(bw, tape, self.x_hat, self.g_xhat, self.gs_packs, grads, need_input_grad=lrp is not None)
         if lrp is not None:
             self.lrp_tapes, self.d_yhat = lrp["tapes"], d_y                    # kept for teacher-forced gradient checks
-            G.lower_lrp_stacks_backward(bw, lrp["tapes"], [d_y.window(32 * j, 32) for j in range(len(lrp["tapes"]))],
-                                        lrp["packs"], grads)
+            dz = []
+            for j, t in enumerate(lrp["tapes"]):
+                z, dy = t["out"], d_y.window(32 * j, 32)
+                o = bw.buf(z.B, z.H, z.W, z.C)
+                bw.call(lambda z=z, dy=dy, o=o: ops.ew(L.EW_HTANH_BWD, [z, dy], [o]), "lrp tail bwd")
+                dz.append(o)
+            # the stacks' inputs (hyperprior means, supports, rq_j) have no trainable producer in this schedule
+            G.lower_stacks_backward(bw, lrp["tapes"], dz, lrp["packs"], grads, need_dx=False)
 
-    def backward_gs(self, grad_x_hat: torch.Tensor, use_graph: bool):
-        """dL/d(parameters of the trained synthesis transform) for dL/dx_hat; fresh tensors in ``gs_params`` order."""
+    def _grad_buffer(self) -> Dict[int, torch.Tensor]:
+        """The backward plan's flat gradient buffer over ``train_params``: {id(param): its view}."""
+        self.gflat, views, self.goffs = G.flat_grads(self.train_params, self.x_in.device)
+        self.bwd.keep += [self.gflat, views]
+        return {id(p): g for p, g in zip(self.train_params, views)}
+
+    def _backward(self, grad: torch.Tensor, use_graph: bool) -> List[torch.Tensor]:
+        """Run the backward plan for the incoming gradient (dL/dlikelihoods["y"] of the REM fine-tune, dL/dx_hat of
+        refine_gs), capturing its graph at the first graph run; returns fresh tensors in ``train_params`` order."""
         cur = torch.cuda.current_stream(self.x_in.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            self.g_xhat.copy_(grad_x_hat)
+            self._bwd_in(grad)
             if use_graph:
-                if getattr(self, "_gs_bwd_graph", None) is None:
-                    self.gs_bwd.run()
+                if self._bwd_graph is None:
+                    self.bwd.run()
                     self.stream.synchronize()
-                    self._gs_bwd_graph = ops.Graph()
-                    self._gs_bwd_graph.capture(self.gs_bwd.run)
-                self._gs_bwd_graph.launch()
+                    self._bwd_graph = ops.Graph()
+                    self._bwd_graph.capture(self.bwd.run)
+                self._bwd_graph.launch()
             else:
-                self.gs_bwd.run()
-            out = [v.clone() for v in self.gs_views]
+                self.bwd.run()
+            flat = self.gflat.clone()
         cur.wait_stream(self.stream)
-        return out
+        return [flat[o:o + p.numel()].view(p.shape) for o, p in zip(self.goffs, self.train_params)]
 
     def _lower_prog_sequential(self, plan, heads, means_h, scales_h, hyper_done, supports, y_top, y_sub, yb, yp, ls_y,
                                table, symbols):
@@ -1168,12 +1157,11 @@ class _FsqPlan:
     # -------------------------------------------------------------------------------------------
     def close(self):
         """Give up the executable graphs of this plan (ops.Graph.close: destroyed at the next safe point)."""
-        for g in list(self.graphs.values()) + [getattr(self, "_bwd_graph", None), getattr(self, "_gs_bwd_graph", None),
-                                               getattr(self.plan, "_graph", None)]:
+        for g in list(self.graphs.values()) + [self._bwd_graph, getattr(self.plan, "_graph", None)]:
             if g is not None:
                 g.close()
         self.graphs.clear()
-        self._bwd_graph = self._gs_bwd_graph = None
+        self._bwd_graph = None
 
     def set_noise(self, noise=None):
         """Training: U(-.5,.5) for the likelihood proxies; ``noise`` = {"y": NCHW, "z": NCHW} injects fixed draws
@@ -1184,43 +1172,14 @@ class _FsqPlan:
             else:
                 v.buf.uniform_(-0.5, 0.5)
 
-    def backward(self, grad_lik_y: torch.Tensor, use_graph: bool):
-        """dL/d(REM parameters) for dL/dlikelihoods["y"] (NCHW); returns fresh tensors in ``rem_params`` order."""
-        d = self.m.division_dimension[0]
-        cur = torch.cuda.current_stream(self.x_in.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.glik.buf.copy_(grad_lik_y[:, d:].permute(0, 2, 3, 1))
-            if use_graph:
-                if getattr(self, "_bwd_graph", None) is None:
-                    self.bwd.run()
-                    self.stream.synchronize()
-                    self._bwd_graph = ops.Graph()
-                    self._bwd_graph.capture(self.bwd.run)
-                self._bwd_graph.launch()
-            else:
-                self.bwd.run()
-            flat = self.gflat.clone()
-        cur.wait_stream(self.stream)
-        out, off = [], 0
-        for p in self.rem_params:
-            out.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        return out
-
     def execute(self, x, pr, checkpoint_ref, use_graph, clone, noise=None, ck_pr=None):
         """Run the plan on the model's own HIP stream (hipGraph capture is not allowed on the
         legacy default stream), ordered after / before the caller's current stream."""
         self.pr = float(pr)
         self.generation += 1
         self.ck_pr = float(ck_pr) if ck_pr is not None else 0.0
-        if self.train_gs:
-            sig = tuple(p.data_ptr() for p in self.gs_params)
-            if getattr(self, "_gs_ptr_sig", sig) != sig:       # parameter storage replaced: captured pointers are stale
-                self.close()
-            self._gs_ptr_sig = sig
-        if self.train and self.rem_idx is not None:
-            sig = tuple(p.data_ptr() for p in self.rem_params)
+        if self.bwd is not None:
+            sig = tuple(p.data_ptr() for p in self.train_params)
             if getattr(self, "_ptr_sig", sig) != sig:          # parameter storage replaced: captured pointers are stale
                 self.close()
             self._ptr_sig = sig

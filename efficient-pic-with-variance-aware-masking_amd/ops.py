@@ -250,20 +250,6 @@ def _pack_job(src: torch.Tensor, dst: torch.Tensor, bias: bool, mode: int, phase
     return True
 
 
-def repack_conv(conv_weight: torch.Tensor, conv_bias: Optional[torch.Tensor], pk: "Packed", dgrad: bool = False):
-    """Refresh ``pk`` IN PLACE from the (trained) parameters: plans keep pointing at the same packed buffers
-    while the optimiser updates the weights between steps."""
-    lib = L.load()
-    assert conv_weight.is_cuda and conv_weight.is_contiguous() and conv_weight.dtype == torch.float32
-    mode = L.PACK_CONV_DGRAD if dgrad else L.PACK_CONV
-    if not _pack_job(conv_weight, pk.w, False, mode, 0, pk.kh, pk.kw, pk.cin, pk.n):
-        L.check(lib.vam_pack_conv_weights(conv_weight.data_ptr(), pk.w.data_ptr(), mode, 0, pk.kh, pk.kw, pk.cin, pk.n,
-                                          stream_ptr()), "vam_pack_conv_weights")
-    if not dgrad and conv_bias is not None:
-        if not _pack_job(conv_bias, pk.b, True, L.PACK_CONV, 0, 0, 0, 0, pk.n):
-            L.check(lib.vam_pack_bias(conv_bias.data_ptr(), pk.b.data_ptr(), L.PACK_CONV, pk.n, stream_ptr()), "vam_pack_bias")
-
-
 def pack_bias(src: torch.Tensor, mode: int, n: int) -> torch.Tensor:
     lib = L.load()
     src = src.detach().to(dtype=torch.float32).contiguous()

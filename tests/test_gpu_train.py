@@ -142,10 +142,11 @@ def test_module_level_training_forwards_are_differentiable():
     assert float((out - zg).abs().max()) <= 0.5 and lik.requires_grad and tuple(lik.shape) == tuple(zg.shape)
 
 
-def test_rem_blocks_backward_teacher_forced():
-    """Taped REM forward + backward lowering (engine.lower_rem_blocks_train / lower_rem_backward) on IDENTICAL
-    inputs against autograd over the oracle's rem_block: outputs 1e-5, every parameter gradient 2e-5 of its max."""
-    from vampic import engine as E, layers as Ly
+def test_rem_blocks_backward_teacher_forced_shared_packs():
+    """Taped REM forward + backward lowering (engine.lower_rem_blocks_train / lower_rem_backward, weights packed by the
+    shared gs_train.TransformPacks) on IDENTICAL inputs against autograd over the oracle's rem_block: outputs 1e-5,
+    every parameter gradient 2e-5 of its max."""
+    from vampic import engine as E, gs_train as G, layers as Ly
     K, N, B, H, W = 2, 32, 2, 8, 8
     mods = [Ly.LatentRateReduction(N, True, "middle") for _ in range(K)]
     sds = []
@@ -163,7 +164,7 @@ def test_rem_blocks_backward_teacher_forced():
     dres = [synth.normal((B, 2 * N, H, W), 60 + k) for k in range(K)]
     vb, vp, va, vd = [V(t) for t in epb], [V(t) for t in epp], [V(t) for t in att], [V(t) for t in dres]
     outs = [ops.new_view(B, H, W, 2 * N) for _ in range(K)]
-    packs = E.TrainPacks(*E.rem_trained_convs(mods))
+    packs = G.TransformPacks(*E.rem_trained_convs(mods))
     packs.record_refresh(plan)
     tape = E.lower_rem_blocks_train(plan, mods, [V(t) for t in yck], [[v.window(0, N), v.window(N, N)] for v in vb],
                                     [[v.window(0, N), v.window(N, N)] for v in vp], va,
@@ -208,7 +209,7 @@ def test_rem_train_step_matches_reference_gradients(train_model, use_graph):
     rule at sigma = 0.11, LeakyReLU's sign) that an fp32-order difference can flip for single elements, so they are
     bounded in aggregate: all sampled gradient entries together within 1e-3 of their joint norm, each tensor within
     3e-2 of its own norm.  The backward machinery itself is held to 2e-5 by
-    test_rem_blocks_backward_teacher_forced and test_conv_backward_matches_autograd."""
+    test_rem_blocks_backward_teacher_forced_shared_packs and test_conv_backward_matches_autograd."""
     m, _ = train_model
     m.use_graph = use_graph
     gold = np.load(os.path.join(GOLD, "rem_train_step.npz"))
