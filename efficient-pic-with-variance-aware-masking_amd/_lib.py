@@ -38,6 +38,7 @@ class VamSeg(C.Structure):
 
 VAM_MAX_WGRAD_GROUP = 16
 VAM_MAX_EW_GROUP = 8
+VAM_MAX_MASK_LEVELS = 8         # include/vampic.h: levels of one vam_variance_mask_levels launch
 VAM_MAX_TAIL_GROUP = 8
 
 
@@ -137,6 +138,8 @@ _SIGNATURES = {
     "vam_attn_mfma": (C.c_int, []),
     "vam_variance_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                     C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_variance_mask_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_gauss_tail": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_void_p, C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_build_indexes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_eb_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p]),
@@ -159,6 +162,10 @@ _SIGNATURES = {
     "vam_leaky_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_mul": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_gauss_train": (C.c_int, [C.c_void_p, C.c_int] * 10 + [C.c_long, C.c_int, C.c_void_p]),
+    "vam_gauss_levels_fwd": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_long, C.c_void_p, C.c_int, C.c_long] + [C.c_void_p, C.c_int, C.c_long] * 2
+                             + [C.c_int, C.c_long, C.c_int, C.c_void_p]),
+    "vam_gauss_levels_bwd": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_long] + [C.c_void_p, C.c_int, C.c_long] * 3 + [C.c_void_p, C.c_int] * 4
+                             + [C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_train_elementwise": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
     "vam_train_axpy_group": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vam_stack_tail_group": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

@@ -306,7 +306,8 @@ def first_train_setup(model):
 def first_train_step(model, criterion, batch: torch.Tensor, optimizer, list_quality: Sequence[float] = (0, 10),
                      clip_max_norm: float = 1.0, noise=None, aux_optimizer=None) -> dict:
     """One optimisation step of the first-stage schedule on this rank's shard (training/step.py:56-99 with
-    ``sampling_training=False``): ``out = model(d, quality=[0, 10])``, criterion, backward, clip, step.  On a multi-GPU
+    ``sampling_training=False``): ``out = model(d, quality=list_quality)`` — [0, 10] by default, or any [0, q1, ..., qL]
+    with one lambda per level in the criterion (training/loss.py:17-66) —, criterion, backward, clip, step.  On a multi-GPU
     job the gradients are averaged over the ranks DURING ``backward()``: the plan's flat gradient buffer is cut into
     ~25 MB buckets in the order the backward finishes them, and each bucket's all-reduce (RCCL) is issued on a
     communication stream as soon as its last weight gradient has been enqueued (sharding.BucketReducer); the clip runs

@@ -106,25 +106,42 @@ def lower_g_a_backward(bw: E.Plan, tape: list, d_y: View, pk: G.TransformPacks, 
 # ============================================================================= the plan
 class FullTrainPlan:
     """Training forward + backward for one (B, H, W, mode).  ``mode`` = "multi": ``forward(x, [0, q])`` — both decoders,
-    no clamp, likelihoods y / y_prog / z;  "single": ``forward_single_quality(x, q)`` — one decoder, clamp."""
+    no clamp, likelihoods y / y_prog / z;  "single": ``forward_single_quality(x, q)`` — one decoder, clamp;  "levels":
+    ``forward(x, [0, q1, ..., qL])`` with ``n_levels`` = L >= 2 (all_scalable only).
 
-    def __init__(self, m, B: int, H: int, W: int, mode: str, base_only: bool, device, trainable_ids: Optional[set] = None):
-        assert mode in ("multi", "single") and not (mode == "multi" and base_only)
+    Levels: the reference builds mu_total / std_total once, outside its quality loop, and slices them by absolute
+    position (pic.py:264-270,380-478), so with all_scalable every level's progressive (mu, sigma) equal level 1's.  The
+    front end, the base slices, the base decoder and the progressive (mu, sigma) chain therefore run ONCE; only the
+    per-level tail (mask, quantisation, likelihood, LRP stacks, merge, g_s[1]) depends on the quality, and it runs
+    batched along the image axis as L * B images (level k = images k*B .. (k+1)*B-1).  In the backward the level tail's
+    gradients w.r.t. the shared (mu, sigma) and supports are summed over the levels — what the extra evaluations of the
+    same stacks at the same inputs contribute in the reference's graph."""
+
+    def __init__(self, m, B: int, H: int, W: int, mode: str, base_only: bool, device, trainable_ids: Optional[set] = None,
+                 n_levels: int = 1):
+        assert mode in ("multi", "single", "levels") and not (mode != "single" and base_only)
         delta, mu_rep, scal = bool(m.delta_encode), bool(m.total_mu_rep), bool(m.all_scalable)
+        levels = mode == "levels"
+        NL = self.n_levels = int(n_levels) if levels else 1
+        assert not levels or (NL >= 2 and scal), "levels mode: L >= 2 quality levels, all_scalable"
         me, md, mh = bool(m.multiple_encoder), bool(m.multiple_decoder), bool(m.multiple_hyperprior)
         self.m, self.B, self.H, self.W, self.mode, self.base_only = m, B, H, W, mode, base_only
         self.device = torch.device(device)
         self.pr = 10.0
+        self.prs = (10.0,) * NL
         self.generation = 0
         self.stream = None
-        self.fwd_graphs: Dict[float, ops.Graph] = {}
+        self.fwd_graphs: Dict[object, ops.Graph] = {}
         self.bwd_graphs: Dict[tuple, List[ops.Graph]] = {}
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         h, w, d, ns, C = H // 16, W // 16, m.division_dimension[0], m.ns0, m.dim_chunk
         sl = lambda v, i, n=1: v.window(i * C, n * C)
         nh = 1 if base_only else 2
-        multi = mode == "multi"
+        nl = nh + NL - 1                                         # d-channel blocks of noise_y / lik: base, then one per level
+        LB = NL * B                                              # images of the level-batched progressive tail
+        self.d = d
+        multi = mode in ("multi", "levels")
         clamp = not multi
         self.clamp = clamp
         dec_base = multi or base_only
@@ -159,7 +176,7 @@ class FullTrainPlan:
             self.pk[id(mod)].record_refresh(P)
         P.branch(0)
         self.x_in = torch.empty((B, 3, H, W), **f32)
-        n_rec = (1 if dec_base else 0) + (1 if dec_prog else 0)
+        n_rec = (1 if dec_base else 0) + (NL if dec_prog else 0)
         self.x_hat = torch.empty((n_rec, B, 3, H, W), **f32)
         P.keep += [self.x_in, self.x_hat]
         x_s2d = P.buf(B, H // 2, W // 2, 16)
@@ -171,7 +188,7 @@ class FullTrainPlan:
         z = self.z = P.buf(B, h // 4, w // 4, m.N)
         self.t_ha = lower_stacks_train(P, [m.h_a], [[y]], [z], [pk(m.h_a)])
         self.z_hat, self.z_lik, self.noise_z = (P.buf(B, h // 4, w // 4, m.N) for _ in range(3))
-        self.noise_y = P.buf(B, h, w, nh * d)
+        self.noise_y = P.buf(B, h, w, nl * d)
         eb = m.entropy_bottleneck
         self.eb_names = ["_matrix0", "_bias0", "_factor0", "_matrix1", "_bias1", "_factor1", "_matrix2", "_bias2", "_factor2",
                          "_matrix3", "_bias3", "_factor3", "_matrix4", "_bias4", "quantiles"]
@@ -194,7 +211,7 @@ class FullTrainPlan:
         yq, yb = P.buf(B, h, w, d), P.buf(B, h, w, d)
         self.y_base, self.yq = yb, yq
         self.mu_b, self.std_b = P.buf(B, h, w, d), P.buf(B, h, w, d)
-        self.lik = P.buf(B, h, w, nh * d)
+        self.lik = P.buf(B, h, w, nl * d)
         zero32 = P.buf(B, h, w, C, zero=True)
         junk = P.buf(B, h, w, d)
         self.base_groups = [[i] for i in range(min(ns, m.max_support_slices))] + \
@@ -235,9 +252,9 @@ class FullTrainPlan:
             sp = m.support_progressive_slices
             y_top, y_sub = y.window(d, d), (y.window(0, d) if delta else None)      # pic.py:397-398: r = y_top - y_base under delta_encode
             self.t_chain = []
-            self.mask = P.buf(B, h, w, d)
-            rq = self.rq = P.buf(B, h, w, d)
-            yp = self.y_prog = P.buf(B, h, w, d)
+            self.mask = P.buf(LB, h, w, d)                       # levels: level k's mask / rq / y_prog are images k*B ..
+            rq = self.rq = P.buf(LB, h, w, d)
+            yp = self.y_prog = P.buf(LB, h, w, d)
             nz_p = self.noise_y.window(d, d)
             lst = [m.lrp_transforms_prog[j] for j in range(ns)]
             # all_scalable (pic.py:400-401): the supports of slice j are mu_total / std_total of the slices before it, so the
@@ -261,17 +278,21 @@ class FullTrainPlan:
                     (tl,) = lower_stacks_train(P, [lst[j]], [ms + [sl(rq, j)]], [None], [pk(lst[j])])
                     self.t_lrp_p.append(tl)
                     P.call(lambda j=j, tl=tl: ops.ew(L.EW_HTANH_FWD, [tl["out"], sl(rq, j), sl(yb, j)], [sl(yp, j)]), "lrp tail (prog)")
-            if scal:
+            if levels:
+                self._lower_levels_tail(P, m, pk, ns, C, mh1, yb, mu_tot, y_top, y_sub, gs_prog, clamp)
+            elif scal:
                 P.call(lambda: ops.variance_mask(self.std_p, self.pr, self.mask, n_slice=ns), "variance mask")   # pic.py:430
                 P.call(lambda: ops.gauss_tail(y_top, self.mu_p, self.std_p, y2=y_sub, mask=self.mask, yhat=rq, lik=junk), "quantise (prog)")
-            P.call(lambda: ops.gauss_train(y_top, self.mu_p, self.std_p, nz_p, y2=y_sub, mask=self.mask, lik=self.lik.window(d, d)),
-                   "noise likelihood (prog)")
-            if scal:
+            if not levels:
+                P.call(lambda: ops.gauss_train(y_top, self.mu_p, self.std_p, nz_p, y2=y_sub, mask=self.mask, lik=self.lik.window(d, d)),
+                       "noise likelihood (prog)")
+            if scal and not levels:
                 self.t_lrp_p = lower_stacks_train(P, lst, [self.t_chain[j]["msup"] + [sl(rq, j)] for j in range(ns)], [None] * ns,
                                                   [pk(s) for s in lst])
                 for j in range(ns):
                     P.call(lambda j=j: ops.ew(L.EW_HTANH_FWD, [self.t_lrp_p[j]["out"], sl(rq, j), sl(yb, j)], [sl(yp, j)]), "lrp tail (prog)")
-            self.t_gs1 = G.lower_g_s_train(P, gs_prog, yp, self.x_hat[n_rec - 1], pk(gs_prog), clamp=clamp)
+            if not levels:
+                self.t_gs1 = G.lower_g_s_train(P, gs_prog, yp, self.x_hat[n_rec - 1], pk(gs_prog), clamp=clamp)
 
         # ------------------------------------------------------------------ parameters and the flat gradient buffer
         # order = the order in which the backward FINISHES them (so that buckets complete front to back)
@@ -331,7 +352,7 @@ class FullTrainPlan:
                 bw.wgrad_branch = keep_
         bw.keep += [self.flat, self.views]
         self.g_xhat = torch.zeros_like(self.x_hat)
-        self.glik = bw.buf(B, h, w, nh * d, zero=True)
+        self.glik = bw.buf(B, h, w, nl * d, zero=True)
         self.glik_z = bw.buf(B, h // 4, w // 4, m.N, zero=True)
         bw.keep.append(self.g_xhat)
         D_y = bw.buf(B, h, w, 2 * d, zero=True)
@@ -398,7 +419,11 @@ class FullTrainPlan:
         d_yb0 = None
         if dec_prog:
             g1 = self.g_xhat[n_rec - 1]
-            d_yp = transform_bwd(G.lower_g_s_backward, bw, self.t_gs1, self.x_hat[n_rec - 1], g1, pk(gs_prog), grads, need_input_grad=True, clamp=clamp)
+            if levels:              # the L reconstructions are one [L * B] batch of g_s[1] (contiguous in x_hat[1:])
+                d_yp = transform_bwd(G.lower_g_s_backward, bw, self.t_gs1, self.x_hat[1:].view(LB, 3, H, W),
+                                     self.g_xhat[1:].view(LB, 3, H, W), pk(gs_prog), grads, need_input_grad=True, clamp=clamp)
+            else:
+                d_yp = transform_bwd(G.lower_g_s_backward, bw, self.t_gs1, self.x_hat[n_rec - 1], g1, pk(gs_prog), grads, need_input_grad=True, clamp=clamp)
             if not shared_dec:
                 done(gs_prog)
             if overlap:                             # the base decoder's backward beside the progressive chain's (see the forward)
@@ -407,7 +432,52 @@ class FullTrainPlan:
                 bw.wait(ev)
                 d_yb0 = gs_base_bwd()
                 bw.branch(0)
-            if scal:
+            def chain_bwd(G_mu, dsg_l):
+                for j in range(ns - 1, -1, -1):
+                    rec = self.t_chain[j]
+                    s_ = rec["s"]
+                    acc_many([(sl(G_mu, j), sl(D_mutot, j), 1.0)] +                      # mu_total_j = mu_j + y_hat_base_j
+                             ([(sl(D_yb, j), sl(D_mutot, j), 1.0)] if mu_rep else []) +
+                             [(sl(dsg_l, j), sl(D_stdp, j), 1.0)], "supports' gradients of slice j")
+                    st = [m.cc_mean_transforms_prog[j], m.cc_scale_transforms_prog[j]]
+                    dxm, dxs_ = lower_stacks_backward(bw, rec["t"], [sl(G_mu, j), sl(dsg_l, j)], [pk(s) for s in st], grads)
+                    done(st[0])
+                    done(st[1])
+                    scatter(dxm, [(D_mh.window(d, d), d), (sl(D_yb, j), C)] + ([(sl(D_mutot, j - s_, s_), C * s_)] if s_ else []))
+                    scatter(dxs_, [(D_sh.window(d, d), d), (sl(D_yb, j), C)] + ([(sl(D_stdp, j - s_, s_), C * s_)] if s_ else []))
+            if levels:
+                # the level tail on L * B images: its supports' gradients land in level-batched accumulators first and are
+                # summed over the levels (level order) before the shared chain's backward reads them
+                DL_mh, DL_yb, DL_mt = (bw.buf(LB, h, w, d, zero=True) for _ in range(3))
+                bw.call(lambda: [ops.memset_zero(a.buf) for a in (DL_mh, DL_yb, DL_mt)], "clear the level accumulators")
+                acc(DL_yb, d_yp)                                                      # merge: y_hat = r_hat + y_hat_base (pic.py:451)
+                dzl = []
+                for j in range(ns):
+                    zt = self.t_lrp_p[j]["out"]
+                    o = bw.buf(zt.B, zt.H, zt.W, zt.C)
+                    bw.call(lambda j=j, zt=zt, o=o: ops.ew(L.EW_HTANH_BWD, [zt, sl(d_yp, j)], [o]), "lrp tail bwd")
+                    dzl.append(o)
+                lst = [m.lrp_transforms_prog[j] for j in range(ns)]
+                dxs = lower_stacks_backward(bw, self.t_lrp_p, dzl, [pk(s) for s in lst], grads)   # weight gradients: all levels
+                for s in lst:
+                    done(s)
+                d_rq = bw.buf(LB, h, w, d)
+                for j in range(ns):
+                    s_ = self.t_chain[j]["s"]
+                    scatter(dxs[j], [(DL_mh, d), (sl(DL_yb, j), C)] + ([(sl(DL_mt, j - s_, s_), C * s_)] if s_ else []) + [(None, C)])
+                    bw.call(lambda j=j, dx=dxs[j]: ops.ew(L.EW_AXPY, [sl(d_yp, j), dx.window(dx.C - C, C)], [sl(d_rq, j)], coef=1.0), "d rq")
+                for k in range(NL):
+                    img = lambda v, k=k: View(v.buf[k * B:(k + 1) * B], v.c0, v.C)
+                    acc_many([(D_mh.window(d, d), img(DL_mh), 1.0), (D_yb, img(DL_yb), 1.0), (D_mutot, img(DL_mt), 1.0)],
+                             "levels' sum of the supports' gradients")
+                # likelihood + straight-through rounding of every level, summed into the shared (mu, sigma): one launch
+                G_mu, dsg_l = bw.buf(B, h, w, d), bw.buf(B, h, w, d)
+                bw.call(lambda: ops.gauss_levels_bwd(y_top, self.mu_p, self.std_p, self.mask, self.noise_y.window(d, d),
+                                                     self.glik.window(d, d), d_rq, G_mu, dsg_l, D_y.window(d, d), NL, y2=y_sub,
+                                                     dy_sub=D_y.window(0, d) if delta else None, noise_ls=d, glik_ls=d),
+                        "likelihood + straight-through rounding backward (levels)")
+                chain_bwd(G_mu, dsg_l)
+            elif scal:
                 acc(D_yb, d_yp)                                                       # merge: y_hat = r_hat + y_hat_base (pic.py:451)
                 dzl = []
                 for j in range(ns):
@@ -435,18 +505,7 @@ class FullTrainPlan:
                 acc(D_y.window(d, d), d_r)
                 if delta:
                     acc(D_y.window(0, d), d_r, -1.0)                                      # delta_encode: r = y_top - y_sub
-                for j in range(ns - 1, -1, -1):
-                    rec = self.t_chain[j]
-                    s_ = rec["s"]
-                    acc_many([(sl(G_mu, j), sl(D_mutot, j), 1.0)] +                      # mu_total_j = mu_j + y_hat_base_j
-                             ([(sl(D_yb, j), sl(D_mutot, j), 1.0)] if mu_rep else []) +
-                             [(sl(dsg_l, j), sl(D_stdp, j), 1.0)], "supports' gradients of slice j")
-                    st = [m.cc_mean_transforms_prog[j], m.cc_scale_transforms_prog[j]]
-                    dxm, dxs_ = lower_stacks_backward(bw, rec["t"], [sl(G_mu, j), sl(dsg_l, j)], [pk(s) for s in st], grads)
-                    done(st[0])
-                    done(st[1])
-                    scatter(dxm, [(D_mh.window(d, d), d), (sl(D_yb, j), C)] + ([(sl(D_mutot, j - s_, s_), C * s_)] if s_ else []))
-                    scatter(dxs_, [(D_sh.window(d, d), d), (sl(D_yb, j), C)] + ([(sl(D_stdp, j - s_, s_), C * s_)] if s_ else []))
+                chain_bwd(G_mu, dsg_l)
             else:
                 # all_scalable off: slice j's stacks and LRP read the DECODED slices before it, so dL/dy_hat_j collects the
                 # input gradients of the later slices before slice j's own backward runs (d_yp is accumulated in place:
@@ -556,6 +615,39 @@ class FullTrainPlan:
                                                                  [self.param_done[id(p)] for p in order], self.flat.numel(), len(bw.steps),
                                                                  BUCKET_BYTES)
 
+    def _lower_levels_tail(self, P: E.Plan, m, pk, ns: int, C: int, mh1: View, yb: View, mu_tot: View, y_top: View,
+                           y_sub: Optional[View], gs_prog, clamp: bool):
+        """The per-level part of ``forward(x, [0, q1, ..., qL])`` (pic.py:425-466 once per level) on L * B images: the L
+        masks in one launch, quantisation + noisy likelihood of every level in one launch, the ten LRP stacks and g_s[1]
+        once over the level batch.  Their supports (hyperprior half, y_hat_base, mu_total) are the same for every level
+        and are replicated into level-batched buffers."""
+        B, NL, d = self.B, self.n_levels, self.d
+        LB = NL * B
+        h, w = yb.H, yb.W
+        sl = lambda v, i, n=1: v.window(i * C, n * C)
+        reps = [(src, P.buf(LB, h, w, d)) for src in (mh1, yb, mu_tot)]
+
+        def replicate():
+            for src, dst in reps:
+                dst.buf.view(NL, B, h, w, d).copy_(src.buf[..., src.c0:src.c0 + src.C].unsqueeze(0))
+        P.call(lambda: ops.variance_mask_levels(self.std_p, self.prs, self.mask, n_slice=ns), "variance masks (levels)")
+        P.call(lambda: ops.gauss_levels_fwd(y_top, self.mu_p, self.std_p, self.mask, self.noise_y.window(d, d), self.rq,
+                                            self.lik.window(d, d), NL, y2=y_sub, noise_ls=d, lik_ls=d),
+               "quantise + noise likelihood (levels)")
+        P.call(replicate, "supports per level")
+        mh_l, yb_l, mt_l = (dst for _, dst in reps)
+        sp = m.support_progressive_slices
+        lst = [m.lrp_transforms_prog[j] for j in range(ns)]
+        ins = []
+        for j in range(ns):
+            s_ = min(sp, j)
+            ins.append([mh_l, sl(yb_l, j)] + ([sl(mt_l, j - s_, s_)] if s_ else []) + [sl(self.rq, j)])
+        self.t_lrp_p = lower_stacks_train(P, lst, ins, [None] * ns, [pk(s) for s in lst])
+        for j in range(ns):
+            P.call(lambda j=j: ops.ew(L.EW_HTANH_FWD, [self.t_lrp_p[j]["out"], sl(self.rq, j), sl(yb_l, j)], [sl(self.y_prog, j)]),
+                   "lrp tail (levels)")
+        self.t_gs1 = G.lower_g_s_train(P, gs_prog, self.y_prog, self.x_hat[1:].view(LB, 3, self.H, self.W), pk(gs_prog), clamp=clamp)
+
     # ------------------------------------------------------------------------------------------- execution
     def _own_stream(self):
         if self.stream is None:
@@ -569,15 +661,28 @@ class FullTrainPlan:
         self.bwd_graphs.clear()
 
     def set_noise(self, noise=None):
+        """noise = {"y": NCHW, "z": NCHW} or None (fresh U(-.5, .5) draws).  Levels: "y" holds the base block and one
+        block per level ([B, d * (L+1)], the reference's draw order), or [B, 2d] — one progressive block for every level."""
         for key, v in (("y", self.noise_y), ("z", self.noise_z)):
             if noise is not None and key in noise:
                 src = noise[key].to(v.buf.device)
+                if key == "y" and self.mode == "levels" and src.shape[1] == 2 * self.d:
+                    src = torch.cat([src[:, :self.d]] + [src[:, self.d:]] * self.n_levels, 1)
+                if src.shape[1] < v.C:
+                    raise ValueError(f"noise[{key!r}] has {src.shape[1]} channels, the plan needs {v.C}")
                 v.buf.copy_(src[:, :v.C].permute(0, 2, 3, 1))
             else:
                 v.buf.uniform_(-0.5, 0.5)
 
-    def execute(self, x: torch.Tensor, pr: float, use_graph: bool, noise=None) -> dict:
-        self.pr = float(pr)
+    def execute(self, x: torch.Tensor, pr, use_graph: bool, noise=None) -> dict:
+        """``pr``: the mask's quality (a float), or in levels mode one per level (the forward graph is kept per value)."""
+        if self.mode == "levels":
+            self.prs = tuple(float(p_) for p_ in pr)
+            assert len(self.prs) == self.n_levels
+            gkey = self.prs
+        else:
+            self.pr = float(pr)
+            gkey = self.pr
         self.generation += 1
         sig = tuple(p.data_ptr() for p in self.params)
         if getattr(self, "_ptr_sig", sig) != sig:          # parameter storage replaced: captured pointers are stale
@@ -591,13 +696,13 @@ class FullTrainPlan:
             self.x_in.copy_(x)
             self.set_noise(noise)
             if use_graph:
-                g = self.fwd_graphs.get(self.pr)
+                g = self.fwd_graphs.get(gkey)
                 if g is None:
                     self.plan.run()
                     st.synchronize()
                     g = ops.Graph()
                     g.capture(self.plan.run)
-                    self.fwd_graphs[self.pr] = g
+                    self.fwd_graphs[gkey] = g
                 g.launch()
             else:
                 self.plan.run()

@@ -375,9 +375,12 @@ class VarianceMaskingPIC(CompressionModel):
 
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),
-        stacked as the reference stacks them.  ``training=True`` evaluates the likelihoods with additive uniform noise
-        (values only, see :meth:`forward_single_quality`); the same noise tensors serve every quality, as one
-        ``uniform_`` draw per slice would in a single reference pass."""
+        stacked as the reference stacks them.  ``training=True`` evaluates the likelihoods with additive uniform noise;
+        without trainable parameters the values only (see :meth:`forward_single_quality`), and the same noise tensors
+        serve every quality.  With trainable parameters (first-stage training) the result is differentiable for any list
+        [0, q1, ..., qL] with q_k > 0: x_hat [L+1, B, 3, H, W], likelihoods {"y": base, "y_prog": [L, B, 2d, h, w] (each
+        level's block holds the base likelihoods again), "z"}; ``noise["y"]`` is then [B, d * (L+1), h, w] (base, then
+        one block per level, the reference's draw order) or [B, 2d, h, w] (one progressive block shared by the levels)."""
         qs = self.define_quality(quality)
         if training and torch.is_grad_enabled() and self._trainable_outside_rem():
             return self._forward_full_train(x, qs, mask_pol, noise, single=False)
@@ -405,9 +408,16 @@ class VarianceMaskingPIC(CompressionModel):
         mask_pol = self.mask_policy if mask_pol is None else mask_pol
         if mask_pol not in ("point-based-std", "two-levels"):
             raise NotImplementedError()
-        if not single and (len(qs) != 2 or qs[0] != 0 or qs[1] == 0):
-            raise NotImplementedError("training forward with gradients: quality lists [0, q] (train.py:147: [0, 10]); "
-                                      f"got {qs}")
+        n_lv = 0 if single else len(qs) - 1
+        if not single and (n_lv < 1 or qs[0] != 0 or any(not q_ > 0 for q_ in qs[1:])):
+            raise NotImplementedError("training forward with gradients: quality lists [0, q1, ..., qL] with every q_k > 0 "
+                                      f"(train.py:147: [0, 10]); got {qs}")
+        if n_lv > 1 and not self.all_scalable:
+            raise NotImplementedError("training forward with gradients over several quality levels is built for all_scalable=True "
+                                      "(README config): the levels then share the progressive (mu, sigma) chain")
+        if n_lv > L.VAM_MAX_MASK_LEVELS:
+            raise NotImplementedError(f"training forward with gradients: at most {L.VAM_MAX_MASK_LEVELS} quality levels per step "
+                                      f"(one vam_variance_mask_levels launch); got {n_lv}")
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
@@ -415,16 +425,21 @@ class VarianceMaskingPIC(CompressionModel):
         nb = _max_images_per_plan(x)
         if x.shape[0] > nb:
             raise NotImplementedError(f"training with gradients: at most {nb} images of {x.shape[2]}x{x.shape[3]} per step")
+        if n_lv > 1 and n_lv * x.shape[0] > nb:
+            raise NotImplementedError(f"training with gradients over {n_lv} quality levels: the level tail runs as levels x images "
+                                      f"= {n_lv * x.shape[0]} images of {x.shape[2]}x{x.shape[3]} in one plan, at most {nb}")
         B, C_, H, W = x.shape
         if C_ != 3 or H % 64 or W % 64:
             raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
         base_only = single and q == 0
-        key = ("full_train", B, H, W, "single" if single else "multi", base_only, str(x.device))
+        mode = "single" if single else ("multi" if n_lv == 1 else "levels")
+        key = ("full_train", B, H, W, mode, base_only, str(x.device)) + ((n_lv,) if mode == "levels" else ())
         plan = self._plans.get(key)
         if plan is None:
-            plan = FullTrainPlan(self, B, H, W, "single" if single else "multi", base_only, x.device)
+            plan = FullTrainPlan(self, B, H, W, mode, base_only, x.device, n_levels=max(n_lv, 1))
             self._plans[key] = plan
-        pr = 10 if (mask_pol == "two-levels" and q != 0) else q
+        mpr = lambda q_: 10 if (mask_pol == "two-levels" and q_ != 0) else q_
+        pr = [mpr(q_) for q_ in qs[1:]] if mode == "levels" else mpr(q)
         raw = plan.execute(x.detach(), pr, self.use_graph, noise=noise)
         x_hat, lik, z_lik = _FullTrainFn.apply(plan, self.use_graph, getattr(self, "grad_reducer", None), raw["x_hat"], raw["lik"],
                                                raw["z_lik"], *plan.params)
@@ -436,6 +451,15 @@ class VarianceMaskingPIC(CompressionModel):
             if not base_only:
                 out.update({"mu": raw["mu"], "std": raw["std"], "mask": raw["mask"]})
             return out
+        if mode == "levels":
+            # lik = [base | level 1 | ... | level L] channel blocks; each level's y_prog entry repeats the base block
+            # (pic.py:471-472): autograd sums the base's L+1 appearances
+            lik_b = lik[:, :d]
+            y_prog_lik = torch.stack([torch.cat([lik_b, lik[:, k * d:(k + 1) * d]], 1) for k in range(1, n_lv + 1)], 0)
+            yps = list(raw["y_prog"].split(B, 0))
+            return {"x_hat": x_hat, "likelihoods": {"y": lik_b, "y_prog": y_prog_lik, "z": z_lik},   # pic.py:480-491
+                    "y_hat": [raw["y_base"]] + yps, "y_base": raw["y_base"], "y_prog": yps[-1],
+                    "mu_base": raw["mu_base"], "std_base": raw["std_base"], "mu_prog": raw["mu"], "std_prog": raw["std"]}
         return {"x_hat": x_hat, "likelihoods": {"y": lik[:, :d], "y_prog": lik.unsqueeze(0), "z": z_lik},   # pic.py:389-390,471-472,486-491
                 "y_hat": [raw["y_base"], raw["y_prog"]], "y_base": raw["y_base"], "y_prog": raw["y_prog"],
                 "mu_base": raw["mu_base"], "std_base": raw["std_base"], "mu_prog": raw["mu"], "std_prog": raw["std"]}

@@ -491,6 +491,27 @@ def variance_mask(sigma: View, pr: float, mask: View, n_slice: int = 1, slice_C:
                                        thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_mask")
 
 
+
+def variance_mask_levels(sigma: View, prs: Sequence[float], mask: View, n_slice: int = 1, level_stride: Optional[int] = None,
+                         thr: Optional[torch.Tensor] = None):
+    """The masks of several qualities in one launch: level l's mask is ``mask`` shifted by l * ``level_stride`` floats
+    (default: the next ``sigma.B`` images, i.e. ``mask`` holds [L * B, H, W, ld]); ``thr`` [L, B * n_slice].  Bit-identical
+    to one :func:`variance_mask` per level."""
+    slice_C = sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
+    prs = [float(p_) for p_ in prs]
+    nl = len(prs)
+    hw = sigma.H * sigma.W
+    if level_stride is None:
+        assert mask.B == nl * sigma.B, (mask.B, nl, sigma.B)
+        level_stride = sigma.B * hw * mask.ld
+    assert thr is None or thr.numel() >= nl * sigma.B * n_slice
+    arr = (C.c_double * max(nl, 1))(*prs)
+    L.check(L.load().vam_variance_mask_levels(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, arr, nl,
+                                              mask.ptr, mask.ld, hw * mask.ld, slice_C, level_stride,
+                                              thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_mask_levels")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""
@@ -656,6 +677,44 @@ def gauss_train(y: View, mu: View, sigma: View, noise: View, *, y2: Optional[Vie
     def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
     L.check(L.load().vam_gauss_train(*p(y), *p(y2), *p(mu), *p(sigma), *p(mask), *p(noise), *p(grad_lik), *p(lik),
                                      *p(dmu), *p(dsigma), y.n_pix, y.C, stream_ptr()), "vam_gauss_train")
+
+
+
+def _level_arg(v: View, n: int, ref: View, ls: Optional[int]):
+    """(ptr, ld, level stride in floats) of a per-level operand: default stride = the next ``ref.B`` images of ``v``."""
+    assert v.C == ref.C and v.H == ref.H and v.W == ref.W
+    if ls is None:
+        assert v.B == n * ref.B, (v.B, n, ref.B)
+        ls = ref.B * ref.H * ref.W * v.ld
+    else:
+        assert v.B == ref.B
+    return v.ptr, v.ld, ls
+
+
+def gauss_levels_fwd(y: View, mu: View, sigma: View, mask: View, noise: View, rq: View, lik: View, n_levels: int, *,
+                     y2: Optional[View] = None, noise_ls: Optional[int] = None, lik_ls: Optional[int] = None):
+    """Progressive tail of ``n_levels`` quality levels over one (y, y2, mu, sigma) window (csrc/train.hip): per level
+    rq = round(r - mu) * m + mu and the noisy likelihood.  ``mask`` / ``rq`` hold the levels as consecutive image blocks
+    ([L * B, H, W, ld]); ``noise`` / ``lik`` likewise, or — with ``noise_ls`` / ``lik_ls`` — windows of one [B, ...]
+    buffer whose level l starts ``l * ls`` floats further (e.g. consecutive channel blocks)."""
+    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
+    L.check(L.load().vam_gauss_levels_fwd(*p(y), *p(y2), *p(mu), *p(sigma), *_level_arg(mask, n_levels, y, None),
+                                          *_level_arg(noise, n_levels, y, noise_ls), *_level_arg(rq, n_levels, y, None),
+                                          *_level_arg(lik, n_levels, y, lik_ls), n_levels, y.n_pix, y.C, stream_ptr()),
+            "vam_gauss_levels_fwd")
+
+
+def gauss_levels_bwd(y: View, mu: View, sigma: View, mask: View, noise: View, grad_lik: View, d_rq: View, gmu: View,
+                     dsigma: View, dy_top: View, n_levels: int, *, y2: Optional[View] = None, dy_sub: Optional[View] = None,
+                     noise_ls: Optional[int] = None, glik_ls: Optional[int] = None):
+    """Backward of :func:`gauss_levels_fwd` with the straight-through rounding under each level's mask: writes
+    gmu = sum_l (d_rq_l * (1 - m_l) + dmu_l) and dsigma = sum_l dsigma_l, and adds sum_l d_r_l into ``dy_top`` (and its
+    negative into ``dy_sub``) in place — level by level, as the unfused launches would."""
+    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
+    L.check(L.load().vam_gauss_levels_bwd(*p(y), *p(y2), *p(mu), *p(sigma), *_level_arg(mask, n_levels, y, None),
+                                          *_level_arg(noise, n_levels, y, noise_ls), *_level_arg(grad_lik, n_levels, y, glik_ls),
+                                          *_level_arg(d_rq, n_levels, y, None), *p(gmu), *p(dsigma), *p(dy_top), *p(dy_sub),
+                                          n_levels, y.n_pix, y.C, stream_ptr()), "vam_gauss_levels_bwd")
 
 
 # ---- transform backward pieces (csrc/train_gs.hip)

@@ -263,6 +263,15 @@ int vam_variance_mask(const float* sigma, int ld, long batch_stride, long slice_
                       int n_batch, int n_slice, int n_pix, int C, double pr,
                       float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
                       float* thr_out, void* stream);
+/* The masks of n_levels qualities prs[0..n_levels-1] in ONE launch (training forward with quality lists
+ * [0, q1, ..., qL], pic.py:425-430 once per level): each segment is loaded once and both order statistics are selected
+ * per level.  Level l's mask is written at mask_out + l*mask_level_stride (float 0/1, the layout of vam_variance_mask),
+ * its thresholds at thr_out[l*n_batch*n_slice + s].  Bit-identical to n_levels vam_variance_mask calls. */
+#define VAM_MAX_MASK_LEVELS 8
+int vam_variance_mask_levels(const float* sigma, int ld, long batch_stride, long slice_stride,
+                             int n_batch, int n_slice, int n_pix, int C, const double* prs, int n_levels,
+                             float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
+                             long mask_level_stride, float* thr_out, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
@@ -378,6 +387,25 @@ int vam_gauss_train(const float* y, int ld_y, const float* y2, int ld_y2, const 
                     const float* sigma, int ld_sigma, const float* mask, int ld_mask, const float* noise, int ld_noise,
                     const float* grad_lik, int ld_glik, float* lik, int ld_lik, float* dmu, int ld_dmu,
                     float* dsigma, int ld_dsigma, long n_pix, int C, void* stream);
+/* The progressive tail of n_levels quality levels over ONE (y, y2, mu, sigma) window (training forward with quality lists
+ * [0, q1, ..., qL]: every level shares the progressive (mu, sigma) chain, pic.py:380-478).  Level l's mask, noise, lik and
+ * rq live at their base pointer + l * <name>_ls floats, with their own pixel stride.
+ *   forward:  rq_l = round(r - mu) * m_l + mu (r = y - y2) and lik_l = vam_gauss_train's forward with m_l, noise_l —
+ *             bit-identical to vam_gauss_tail (yhat) + vam_gauss_train (lik) per level.
+ *   backward: for l = 0 .. n_levels-1 in order, vam_gauss_train's backward (grad_lik_l) -> (dmu_l, dsg_l) and the
+ *             straight-through rounding under m_l of d_rq_l: d_r = d_rq*m + (-1)*dmu_l, g = d_rq*(1-m) + dmu_l;
+ *             gmu = (0 + g_0) + g_1 ..., dsigma = (0 + dsg_0) + dsg_1 ..., dy_top += d_r (in place) and, when dy_sub is
+ *             not NULL, dy_sub += (-1)*d_r — bit-identical to that sequence of vam_gauss_train, VAM_EW_MASK_SPLIT and
+ *             VAM_EW_AXPY launches. */
+int vam_gauss_levels_fwd(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls,
+                         const float* noise, int ld_noise, long noise_ls, float* rq, int ld_rq, long rq_ls,
+                         float* lik, int ld_lik, long lik_ls, int n_levels, long n_pix, int C, void* stream);
+int vam_gauss_levels_bwd(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls,
+                         const float* noise, int ld_noise, long noise_ls, const float* grad_lik, int ld_glik, long glik_ls,
+                         const float* d_rq, int ld_drq, long drq_ls, float* gmu, int ld_gmu, float* dsigma, int ld_dsigma,
+                         float* dy_top, int ld_dyt, float* dy_sub, int ld_dys, int n_levels, long n_pix, int C, void* stream);
 
 /* ------------------------------------------------------------------ transform backward (refine_gs) */
 /* Element-wise derivatives of the synthesis / analysis transforms (csrc/train_gs.hip).  Every tensor is a channel
