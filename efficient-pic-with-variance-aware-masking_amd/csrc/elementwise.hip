@@ -98,6 +98,18 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ src, int ld, float
 }
 
 // ------------------------------------------------------------------ Gaussian slice tail
+// pic.py:625-629, one element under mask value m: the likelihood is taken at round((r-mu)*m) with scale sigma*m, and
+// yhat = round(r-mu)*m + mu (q = round(r-mu)).  Shared by gauss_tail_kernel and gauss_levels_eval_kernel.
+__device__ __forceinline__ void masked_tail(float d, float q, float mu, float sg, float m, float& yh, float& absv, float& s,
+                                            int& sym) {
+  float in = d * m;
+  float rq = rintf(in);
+  absv = fabsf(rq);
+  s = sg * m;
+  yh = q * m + mu;
+  sym = (int)rq;
+}
+
 struct TailArgs {
   const float *y, *y2, *mu, *sigma, *mask;
   float *yhat, *lik;
@@ -134,13 +146,7 @@ __global__ void gauss_tail_kernel(const TailArgs a) {
       float q = rintf(d);                         // torch.round = half-to-even
       float absv, s;
       if (a.mask) {
-        // pic.py:625-629: lik on round((r-mu)*m) with scale sigma*m ; yhat = round(r-mu)*m + mu
-        float in = d * mk[k];
-        float rq = rintf(in);
-        absv = fabsf(rq);
-        s = sv[k] * mk[k];
-        yh[k] = q * mk[k] + mv[k];
-        sy[k] = (int)rq;
+        masked_tail(d, q, mv[k], sv[k], mk[k], yh[k], absv, s, sy[k]);
       } else {
         // pic.py:545-546 + entropy_models.py:140-149,623-630: |(round(y-mu)+mu) - mu|
         float o = q + mv[k];
@@ -156,6 +162,60 @@ __global__ void gauss_tail_kernel(const TailArgs a) {
     if (a.lik) *reinterpret_cast<float4*>(a.lik + p * a.ld_lik + c) = make_float4(lk[0], lk[1], lk[2], lk[3]);
     if (a.sym) *reinterpret_cast<int4*>(a.sym + p * a.ld_sym + c) = make_int4(sy[0], sy[1], sy[2], sy[3]);
     if (a.log2sum) wave_accumulate(lsum, (int)(p / a.pix_per_item), a.log2sum);
+  }
+}
+
+// The progressive tail of n_levels masks over one shared (y, y2, mu, sigma) window (vam_gauss_levels_eval): the shared
+// operands are loaded once per element, level l's mask once; per level the element math of gauss_tail_kernel's masked
+// branch, and level l's per-image log2 sum goes to log2sum[l * n_items + item].  Level l's arrays sit at base + l * ls.
+struct TailLevelsArgs {
+  const float *y, *y2, *mu, *sigma, *mask;
+  float *yhat, *lik;
+  int32_t* sym;
+  double* log2sum;
+  int ld_y, ld_y2, ld_mu, ld_sigma, ld_mask, ld_yhat, ld_lik, ld_sym;
+  long ls_mask, ls_yhat, ls_lik, ls_sym;
+  int pix_per_item, n_items, n_levels, C4;
+  long n_vec;
+};
+
+__global__ void gauss_levels_eval_kernel(const TailLevelsArgs a) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_vec; i += (long)gridDim.x * blockDim.x) {
+    long p = i / a.C4;
+    int c = (int)(i - p * a.C4) * 4;
+    float4 y = *reinterpret_cast<const float4*>(a.y + p * a.ld_y + c);
+    if (a.y2) {
+      float4 y2 = *reinterpret_cast<const float4*>(a.y2 + p * a.ld_y2 + c);
+      y.x -= y2.x; y.y -= y2.y; y.z -= y2.z; y.w -= y2.w;            // pic.py:583-584
+    }
+    float4 mu = *reinterpret_cast<const float4*>(a.mu + p * a.ld_mu + c);
+    float4 sg = *reinterpret_cast<const float4*>(a.sigma + p * a.ld_sigma + c);
+    float yv[4] = {y.x, y.y, y.z, y.w}, mv[4] = {mu.x, mu.y, mu.z, mu.w}, sv[4] = {sg.x, sg.y, sg.z, sg.w};
+    float dv[4], qv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dv[k] = yv[k] - mv[k];
+      qv[k] = rintf(dv[k]);                       // torch.round = half-to-even
+    }
+    const int item = (int)(p / a.pix_per_item);
+    for (int lv = 0; lv < a.n_levels; ++lv) {
+      float4 m = *reinterpret_cast<const float4*>(a.mask + lv * a.ls_mask + p * a.ld_mask + c);
+      float mk[4] = {m.x, m.y, m.z, m.w};
+      float yh[4], lk[4];
+      int sy[4];
+      double lsum = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float absv, s;
+        masked_tail(dv[k], qv[k], mv[k], sv[k], mk[k], yh[k], absv, s, sy[k]);
+        lk[k] = gauss_lik(absv, s);
+        lsum += log2((double)lk[k]);
+      }
+      if (a.yhat) *reinterpret_cast<float4*>(a.yhat + lv * a.ls_yhat + p * a.ld_yhat + c) = make_float4(yh[0], yh[1], yh[2], yh[3]);
+      if (a.lik) *reinterpret_cast<float4*>(a.lik + lv * a.ls_lik + p * a.ld_lik + c) = make_float4(lk[0], lk[1], lk[2], lk[3]);
+      if (a.sym) *reinterpret_cast<int4*>(a.sym + lv * a.ls_sym + p * a.ld_sym + c) = make_int4(sy[0], sy[1], sy[2], sy[3]);
+      if (a.log2sum) wave_accumulate(lsum, lv * a.n_items + item, a.log2sum);
+    }
   }
 }
 
@@ -430,6 +490,33 @@ int vam_gauss_tail(const float* y, int ld_y, const float* y2, int ld_y2, const f
   ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, 4.0 * (double)n_pix * C * (nin + nout));
   hipLaunchKernelGGL(gauss_tail_kernel, dim3(stream_grid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("gauss_tail_kernel");
+}
+
+int vam_gauss_levels_eval(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                          const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls, float* yhat,
+                          int ld_yhat, long yhat_ls, float* lik, int ld_lik, long lik_ls, int32_t* sym, int ld_sym,
+                          long sym_ls, double* log2sum, int pix_per_item, int n_levels, long n_pix, int C, void* stream) {
+  VAM_REQUIRE(y && mu && sigma && mask && n_levels > 0 && n_pix > 0 && C > 0 && C % 4 == 0,
+              "vam_gauss_levels_eval: need y, mu, sigma, mask, n_levels > 0 and C %% 4 == 0");
+  VAM_REQUIRE(!log2sum || (pix_per_item > 0 && n_pix % pix_per_item == 0), "vam_gauss_levels_eval: pix_per_item");
+  VAM_REQUIRE(n_pix / (pix_per_item > 0 ? pix_per_item : 1) * (long)n_levels < (1L << 31), "vam_gauss_levels_eval: too many items");
+  VAM_REQUIRE(al16(y) && al16(mu) && al16(sigma) && al16(y2) && al16(mask) && al16(yhat) && al16(lik) && al16(sym), "vam_gauss_levels_eval: 16-byte alignment");
+  VAM_REQUIRE(ld_y % 4 == 0 && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && ld_mask % 4 == 0 && mask_ls % 4 == 0 && (!y2 || ld_y2 % 4 == 0) &&
+              (!yhat || (ld_yhat % 4 == 0 && yhat_ls % 4 == 0)) && (!lik || (ld_lik % 4 == 0 && lik_ls % 4 == 0)) &&
+              (!sym || (ld_sym % 4 == 0 && sym_ls % 4 == 0)), "vam_gauss_levels_eval: strides must be multiples of 4");
+  TailLevelsArgs a;
+  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.mask = mask; a.yhat = yhat; a.lik = lik; a.sym = sym;
+  a.log2sum = log2sum;
+  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma; a.ld_mask = ld_mask;
+  a.ld_yhat = ld_yhat; a.ld_lik = ld_lik; a.ld_sym = ld_sym;
+  a.ls_mask = mask_ls; a.ls_yhat = yhat_ls; a.ls_lik = lik_ls; a.ls_sym = sym_ls;
+  a.pix_per_item = pix_per_item > 0 ? pix_per_item : 1;
+  a.n_items = (int)(n_pix / a.pix_per_item);
+  a.n_levels = n_levels; a.C4 = C / 4; a.n_vec = n_pix * (C / 4);
+  int nin = 3 + (y2 ? 1 : 0) + n_levels, nout = n_levels * ((yhat ? 1 : 0) + (lik ? 1 : 0) + (sym ? 1 : 0));
+  ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, 4.0 * (double)n_pix * C * (nin + nout));
+  hipLaunchKernelGGL(gauss_levels_eval_kernel, dim3(stream_grid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("gauss_levels_eval_kernel");
 }
 
 int vam_build_indexes(const float* sigma, int ld_sigma, const float* mask, int ld_mask, const float* table,

@@ -70,6 +70,41 @@ __global__ void avgpool2_kernel(const float* __restrict__ x, float* __restrict__
   }
 }
 
+// Per (level, image) sums of squared differences of a rate sweep's reconstructions (vam_sqdiff_sum_levels): x is
+// [B, n] (n = 3 H W floats per image), xhat holds the levels as consecutive image blocks [L * B, n].  Block row
+// blockIdx.y = image b; each thread reads its x elements once and keeps one fp64 partial per level in registers, then
+// one wave-reduced atomic per (wave, level) into out[l * B + b].  Same per-element arithmetic as vam_sqdiff_sum
+// (fp32 difference, fp64 square and sum).
+constexpr int SQD_MAX_LEVELS = 16;
+
+__global__ __launch_bounds__(256) void sqdiff_levels_kernel(const float* __restrict__ x, const float* __restrict__ xhat, long n,
+                                                            int B, int n_levels, double* __restrict__ out) {
+  const int b = blockIdx.y;
+  const float* xb = x + (long)b * n;
+  double acc[SQD_MAX_LEVELS];
+#pragma unroll
+  for (int l = 0; l < SQD_MAX_LEVELS; ++l) acc[l] = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = xb[i];
+#pragma unroll
+    for (int l = 0; l < SQD_MAX_LEVELS; ++l) {
+      if (l < n_levels) {
+        float d = xv - xhat[((long)l * B + b) * n + i];
+        acc[l] += (double)d * (double)d;
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < SQD_MAX_LEVELS; ++l) {
+    if (l < n_levels) {
+      double s = acc[l];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+      if ((threadIdx.x & 63) == 0) atomicAdd(out + (long)l * B + b, s);
+    }
+  }
+}
+
 }  // namespace vam
 
 using namespace vam;
@@ -96,6 +131,24 @@ int vam_avgpool2(const float* x, float* out, int planes, int H, int W, int pad_h
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(avgpool2_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, out, H, W, Ho, Wo, pad_h, pad_w, total);
   return check_launch("avgpool2_kernel");
+}
+
+int vam_sqdiff_sum_levels(const float* x, const float* xhat, int B, long n, int n_levels, double* out, void* stream) {
+  // out[l * B + b] += sum_i (x[b, i] - xhat[l * B + b, i])^2 ; groups of SQD_MAX_LEVELS levels per launch
+  VAM_REQUIRE(x && xhat && out && B > 0 && B <= 65535 && n > 0 && n_levels > 0, "vam_sqdiff_sum_levels: bad arguments");
+  long per_img = (n + 255) / 256;
+  unsigned gx = (unsigned)(per_img < 1 ? 1 : per_img);
+  long cap = (2048 + B - 1) / B;                           // about 2048 blocks in all
+  if (gx > (unsigned)(cap < 1 ? 1 : cap)) gx = (unsigned)(cap < 1 ? 1 : cap);
+  for (int l0 = 0; l0 < n_levels; l0 += SQD_MAX_LEVELS) {
+    int nl = n_levels - l0 < SQD_MAX_LEVELS ? n_levels - l0 : SQD_MAX_LEVELS;
+    ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, 4.0 * (double)B * n * (1 + nl));
+    hipLaunchKernelGGL(sqdiff_levels_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x, xhat + (long)l0 * B * n, n, B,
+                       nl, out + (long)l0 * B);
+    int rc = check_launch("sqdiff_levels_kernel");
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 }  // extern "C"

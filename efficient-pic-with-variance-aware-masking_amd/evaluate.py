@@ -1,7 +1,8 @@
 """Evaluation drivers and metric helpers (inference half): the counterparts of
 ``test_epoch`` / ``compress_with_ac`` (reference training/step.py:206-243,259-358) and of
 ``compute_psnr`` / ``compute_padding`` (utility/functions.py:172-174,191-219) on top of the HIP model.
-Rates come from the in-kernel ``log2`` accumulators (a13), squared errors from ``vam_sqdiff_sum``.
+Rates come from the in-kernel ``log2`` accumulators (a13), squared errors from ``vam_sqdiff_sum`` (``vam_sqdiff_sum_levels``
+per level and image for a rate sweep, :func:`rd_sweep`).
 """
 from __future__ import annotations
 
@@ -48,6 +49,58 @@ def estimated_bpp(out: dict, num_pixels: int) -> float:
     return -out["log2_likelihood_sum"].sum().item() / num_pixels
 
 
+def _sweeps(model) -> bool:
+    """Does ``model`` evaluate a quality list in one sweep (VarianceMaskingPIC.forward_qualities)?"""
+    f = getattr(model, "_sweep_eligible", None)
+    return bool(f is not None and f())
+
+
+def _rd_sums(model, x: torch.Tensor, qualities: Sequence[float], mask_pol: str = "point-based-std"):
+    """Per (quality, image) float64 device tensors [L, B]: the sum of log2 likelihoods (y and z) and the sum of squared
+    errors of the reconstruction.  No host synchronisation."""
+    dev = next(model.parameters()).device
+    x = x.to(dev).contiguous()
+    nq, B = len(qualities), x.shape[0]
+    ls = torch.zeros((nq, B), dtype=torch.float64, device=dev)
+    sq = torch.zeros((nq, B), dtype=torch.float64, device=dev)
+    if not _sweeps(model):
+        for k, q in enumerate(qualities):
+            out = model.forward_single_quality(x, q, mask_pol, training=False)
+            ls[k] = out["log2_likelihood_sum"].sum(0)
+            ops.sqdiff_sum_levels(x, out["x_hat"].contiguous(), sq[k:k + 1])
+        return ls, sq
+
+    def emit(i0, i1, sw, t, ks):
+        fp, xb = sw.fp, x[i0:i1]
+        if t is None:                      # the base reconstruction, once for every 0 of the list
+            acc = torch.zeros((1, i1 - i0), dtype=torch.float64, device=dev)
+            ops.sqdiff_sum_levels(xb, fp.x_hat, acc)
+            tot = fp.log2sum.sum(0)
+            for k in ks:
+                sq[k, i0:i1] = acc[0]
+                ls[k, i0:i1] = tot
+            return
+        acc = torch.zeros((len(ks), i1 - i0), dtype=torch.float64, device=dev)
+        ops.sqdiff_sum_levels(xb, t.x_hat, acc)                    # every level of the group in one launch
+        tot = (fp.log2sum[0].unsqueeze(0) + t.log2sum) + fp.log2sum[1].unsqueeze(0)
+        for g, k in enumerate(ks):
+            sq[k, i0:i1] = acc[g]
+            ls[k, i0:i1] = tot[g]
+    model._sweep(x, list(qualities), mask_pol, emit)
+    return ls, sq
+
+
+def rd_sweep(model, x: torch.Tensor, qualities: Sequence[float]):
+    """Rate and distortion of every image of ``x`` at every quality: (bpp, psnr), float64 [L, B] host tensors, with the
+    definitions of :func:`estimated_bpp` and :func:`compute_psnr` applied to each image on its own.  Eligible models run
+    one sweep (forward_qualities' plan); the host synchronises once, at the end."""
+    with torch.no_grad():
+        ls, sq = _rd_sums(model, x, qualities)
+        hw = x.shape[2] * x.shape[3]
+        vals = torch.stack([ls, sq]).cpu()
+    return -vals[0] / hw, -10.0 * torch.log10(vals[1] / (x[0].numel()))
+
+
 def _checkpoint_for(model, x, p):
     """training/step.py:13-29 extract_quality_ref + ExtractChekpointRepr (REM models only)."""
     levels = getattr(model, "check_levels", None)
@@ -61,9 +114,17 @@ def test_epoch(batches: Iterable[torch.Tensor], model, pr_list: Sequence[float],
     """training/step.py:206-243: likelihood-estimated (bpp, PSNR) averaged over the batches, per quality."""
     bpp = [[] for _ in pr_list]
     psnr = [[] for _ in pr_list]
+    sweep = not rems and _sweeps(model)
     with torch.no_grad():
         for d in batches:
             n_pix = d.shape[0] * d.shape[2] * d.shape[3]
+            if sweep:                      # one front end for the whole list; the same formulas over the batch's sums
+                ls, sq = _rd_sums(model, d, pr_list)
+                vals = torch.stack([ls.sum(1), sq.sum(1)]).cpu()
+                for j in range(len(pr_list)):
+                    bpp[j].append(-float(vals[0, j]) / n_pix)
+                    psnr[j].append(-10.0 * math.log10(float(vals[1, j]) / d.numel()))
+                continue
             for j, p in enumerate(pr_list):
                 ck = _checkpoint_for(model, d, p) if rems else None
                 out = model.forward_single_quality(d, quality=p, training=False, **({"checkpoint_ref": ck} if rems else {}))
@@ -116,11 +177,15 @@ def valid_epoch(epoch: int, test_dataloader: Iterable[torch.Tensor], criterion, 
     device = next(model.parameters()).device
     tot = {"loss": 0.0, "bpp": 0.0, "mse": 0.0, "psnr": 0.0}
     n = 0
+    sweep = not rems and _sweeps(model)
     with torch.no_grad():
         for d in test_dataloader:
             d = d.to(device)
-            for p in pr_list:
-                if rems is None:
+            outs = model.forward_qualities(d, list(pr_list), mask_pol="point-based-std") if sweep else None
+            for j, p in enumerate(pr_list):
+                if sweep:
+                    out = outs[j]
+                elif rems is None:
                     out = model.forward_single_quality(d, quality=p, training=False)
                 else:
                     q_ref = extract_quality_ref(p, rems)

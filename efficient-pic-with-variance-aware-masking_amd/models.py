@@ -373,6 +373,96 @@ class VarianceMaskingPIC(CompressionModel):
             out["x_hat"] = _FsqTrainFn.apply(plan, out["x_hat"], self.use_graph, *plan.train_params)
         return out
 
+    # ---- rate sweep: many qualities from one front end
+    def _sweep_eligible(self) -> bool:
+        """With all_scalable no quality reaches the front end (g_a, hyperprior, base slices, progressive (mu, sigma)
+        chain): the sweep computes it once.  REM models (a per-quality REM refines (mu, sigma)), all_scalable=False (the
+        chain reads the decoded slices of each quality), bf16 storage and VAMPIC_CONV=f16x2 (their bits depend on how the
+        launches are batched) run one forward_single_quality per quality instead."""
+        return (self.all_scalable and not isinstance(self, VarianceMaskingPICREM) and getattr(self, "storage", "fp32") == "fp32"
+                and not ops.f16x2_mode())
+
+    def _sweep_plan(self, x) -> "_SweepPlan":
+        B, C_, H, W = x.shape
+        if C_ != 3 or H % 64 or W % 64:
+            raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
+        key = ("sweep", B, H, W, str(x.device))
+        wsig = self._weights_sig()
+        p = self._plans.get(key)
+        if p is not None and p.wsig != wsig:            # a parameter was edited in place since the plan packed it
+            self._plans.pop(key).close()
+            p = None
+        if p is None:
+            p = _SweepPlan(self, B, H, W, x.device)
+            p.wsig = wsig
+            self._plans[key] = p
+        return p
+
+    def _sweep(self, x, qualities, mask_pol, emit):
+        """Run the sweep over ``qualities`` and hand each result to ``emit(i0, i1, sweep_plan, tail, ks)`` while its buffers
+        hold it (the next group overwrites them): images i0..i1 of x; ``tail`` None = the base reconstruction (the entries
+        ks of ``qualities`` equal to 0), else a _SweepTail whose level g is quality ``qualities[ks[g]]``.  ``emit`` runs on
+        the caller's stream, ordered after the group and before the next one."""
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if mask_pol not in ("point-based-std", "two-levels"):
+            raise NotImplementedError()
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        lv = [k for k, q in enumerate(qualities) if q != 0]
+        zeros = [k for k, q in enumerate(qualities) if q == 0]
+        mpr = lambda q: 10 if (mask_pol == "two-levels" and q != 0) else q   # channel_mask.py:152-153
+        B, _, H, W = x.shape
+        for i0, i1, groups in sweep_groups(len(lv), B, H, W):
+            xb = x[i0:i1].detach()
+            sw = self._sweep_plan(xb)
+            sw.front(xb, self.use_graph)
+            if zeros:
+                sw.base(self.use_graph)
+                emit(i0, i1, sw, None, zeros)
+            for l0, l1 in groups:
+                ks = lv[l0:l1]
+                t = sw.tail([float(mpr(qualities[k])) for k in ks], self.use_graph)
+                emit(i0, i1, sw, t, ks)
+
+    def forward_qualities(self, x, qualities, mask_pol=None):
+        """One ``forward_single_quality(x, q, mask_pol, training=False)`` result dict per quality of the list, in list
+        order (same keys, shapes and — log2_likelihood_sum up to its float64 summation order — bits; cloned tensors).
+        Eligible models (:meth:`_sweep_eligible`) run the front end once for the whole list and the per-quality tail
+        batched over the levels; the others loop."""
+        qualities = list(qualities)
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if not self._sweep_eligible():
+            return [self.forward_single_quality(x, q, mask_pol, training=False) for q in qualities]
+        parts: List[list] = [[] for _ in qualities]
+        d = self.division_dimension[0]
+
+        def emit(i0, i1, sw, t, ks):
+            fp = sw.fp
+            nchw = lambda v: v.torch_nchw().clone()
+            for g, k in enumerate(ks):
+                if t is None:                                           # pic.py:558: the base reconstruction
+                    yh = nchw(fp.y_base)
+                    parts[k].append({"x_hat": fp.x_hat.clone(),
+                                     "likelihoods": {"y": nchw(fp.lik.window(0, d)), "z": nchw(fp.z_lik)},
+                                     "log2_likelihood_sum": fp.log2sum.clone(),
+                                     "y_hat": yh, "y_base": yh, "y_prog": yh, "mu": nchw(fp.mu_b), "std": nchw(fp.std_b),
+                                     "mu_base": nchw(fp.mu_b), "std_base": nchw(fp.std_b), "mu_prog": [], "std_prog": []})
+                    continue
+                ls = fp.log2sum.clone()
+                ls[0] += t.log2sum[g]
+                yh = nchw(t.level(t.y_prog, g))
+                parts[k].append({"x_hat": t.x_hat[g * t.B:(g + 1) * t.B].clone(),
+                                 "likelihoods": {"y": torch.cat([fp.lik.window(0, d).torch_nchw(),
+                                                                 t.level(t.lik, g).torch_nchw()], 1),
+                                                 "z": nchw(fp.z_lik)},
+                                 "log2_likelihood_sum": ls,
+                                 "y_hat": yh, "y_base": nchw(fp.y_base), "y_prog": yh, "mu_base": nchw(fp.mu_b),
+                                 "mu": nchw(fp.mu_p), "std_base": nchw(fp.std_b), "std": nchw(fp.std_p),
+                                 "mask": nchw(t.level(t.mask, g))})
+        self._sweep(x, qualities, mask_pol, emit)
+        return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
+
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),
         stacked as the reference stacks them.  ``training=True`` evaluates the likelihoods with additive uniform noise;
@@ -384,11 +474,14 @@ class VarianceMaskingPIC(CompressionModel):
         qs = self.define_quality(quality)
         if training and torch.is_grad_enabled() and self._trainable_outside_rem():
             return self._forward_full_train(x, qs, mask_pol, noise, single=False)
-        base = self.forward_single_quality(x, 0, mask_pol, training, noise=noise)
+        sweep = None
+        if not training and self._sweep_eligible():
+            sweep = self.forward_qualities(x, [0] + list(qs[1:]), mask_pol)       # one front end for the whole list
+        base = sweep[0] if sweep else self.forward_single_quality(x, 0, mask_pol, training, noise=noise)
         x_hats, y_prog, y_hat_total = [base["x_hat"].unsqueeze(0)], [], [base["y_hat"]]
         out = None
-        for q in qs[1:]:
-            out = self.forward_single_quality(x, q, mask_pol, training, noise=noise)
+        for i, q in enumerate(qs[1:]):
+            out = sweep[i + 1] if sweep else self.forward_single_quality(x, q, mask_pol, training, noise=noise)
             x_hats.append(out["x_hat"].unsqueeze(0))
             y_prog.append(out["likelihoods"]["y"].unsqueeze(0))
             y_hat_total.append(out["y_hat"])
@@ -836,7 +929,8 @@ class _FsqPlan:
     """``forward_single_quality`` for one (B,H,W) lowered to libvampic launches."""
 
     def __init__(self, m: VarianceMaskingPIC, B, H, W, base_only, rem_idx, device, symbols=False, train=False,
-                 own_ck=False, train_gs=False, train_lrp=False):
+                 own_ck=False, train_gs=False, train_lrp=False, sweep=False):
+        assert not sweep or (m.all_scalable and not base_only and rem_idx is None and not (symbols or train))
         self.m, self.B, self.H, self.W = m, B, H, W
         self.train_gs = train_gs    # the synthesis transform in use is being trained (refine_gs): taped g_s + backward plan
         self.train_lrp = train_lrp  # ... and the progressive LRP stacks with it (refine_gs --lrp)
@@ -1001,6 +1095,12 @@ class _FsqPlan:
         chain_done = plan.record()
         plan.branch(0)
         plan.wait(chain_done)
+        if sweep:
+            # rate sweep (_SweepPlan): everything up to here does not depend on the quality; the per-level tail and the
+            # base reconstruction are plans of their own over these buffers
+            self.mu_f, self.std_f = self.mu_p, self.std_p
+            self.sweep_parts = dict(heads=heads, yb=yb, mu_tot=mu_tot, y_top=y_top, y_sub=y_sub, g_s=g_s)
+            return
 
         mu_f, std_f = self.mu_p, self.std_p
         if rem_idx is not None:                                                       # rem_pic.py:363-377
@@ -1250,6 +1350,151 @@ class _FsqPlan:
                         "mu": nchw(self.mu_f), "std_base": nchw(self.std_b), "std": nchw(self.std_f),
                         "mask": nchw(self.mask)})
         return out
+
+
+def sweep_groups(n_levels: int, B: int, H: int, W: int) -> List[tuple]:
+    """How a rate sweep over ``n_levels`` qualities (q != 0) of B images of HxW runs: [(i0, i1, [(l0, l1), ...]), ...].
+    Images are split into sub-batches of at most one plan's worth (``_max_images_per_plan``), as forward_single_quality
+    splits them; the levels of a sub-batch of b images run in groups of at most min(VAM_MAX_MASK_LEVELS, nb // b) levels,
+    so that a group's level batch (levels * b images) fits one plan and its masks one vam_variance_mask_levels launch."""
+    nb = max(1, MAX_PLAN_PIXELS // (H * W))
+    out = []
+    for i0 in range(0, B, nb):
+        b = min(nb, B - i0)
+        g = max(1, min(L.VAM_MAX_MASK_LEVELS, nb // b))
+        out.append((i0, i0 + b, [(l0, min(l0 + g, n_levels)) for l0 in range(0, n_levels, g)]))
+    return out
+
+
+def _launch(plan: E.Plan, graphs: Optional[dict], key, stream, use_graph: bool, prep=None):
+    """Run ``plan`` on ``stream`` ordered after / before the caller's stream (as _FsqPlan.execute does), replaying the
+    hipGraph kept in ``graphs[key]`` (captured at its first use; more than 32 kept: all retired)."""
+    cur = torch.cuda.current_stream(plan.device)
+    stream.wait_stream(cur)
+    with torch.cuda.stream(stream):
+        if prep is not None:
+            prep()
+        if use_graph:
+            g = graphs.get(key)
+            if g is None:
+                plan.run()                           # warm-up: every code object loaded before capture
+                stream.synchronize()
+                g = ops.Graph()
+                g.capture(plan.run)
+                if len(graphs) > 32:
+                    for g_ in graphs.values():
+                        g_.close()
+                    graphs.clear()
+                graphs[key] = g
+            g.launch()
+        else:
+            plan.run()
+    cur.wait_stream(stream)
+
+
+class _SweepTail:
+    """The per-level part of a rate sweep for ``n_levels`` qualities over the shared buffers of a _SweepPlan's front end
+    (pic.py:621-651 once per level), run as n_levels * B images: level k is images k*B .. (k+1)*B-1 of every buffer here.
+    The masks are one vam_variance_mask_levels launch, quantisation and likelihood one vam_gauss_levels_eval launch; the
+    ten LRP stacks and g_s[1] run once over the level batch.  The stacks' shared inputs — the stack heads (bias + the
+    hyperprior part of the first layer, computed once at B images: the eval plan's association of that sum), y_hat_base
+    and mu_total — are replicated per level."""
+
+    def __init__(self, fp: "_FsqPlan", n_levels: int):
+        m, B, H, W = fp.m, fp.B, fp.H, fp.W
+        assert 1 <= n_levels <= L.VAM_MAX_MASK_LEVELS
+        NL, LB = n_levels, n_levels * B
+        h, w, d, ns, C = H // 16, W // 16, m.division_dimension[0], m.ns0, m.dim_chunk
+        dev = fp.x_in.device
+        self.n_levels, self.B = NL, B
+        self.prs = (0.0,) * NL
+        self.graphs: Dict[tuple, ops.Graph] = {}
+        P = self.plan = E.Plan(dev)
+        sl = lambda v, i, n=1: v.window(i * C, n * C)
+        parts = fp.sweep_parts
+        self.log2sum = torch.zeros((NL, B), dtype=torch.float64, device=dev)      # level k's progressive log2 sums per image
+        self.x_hat = torch.empty((LB, 3, H, W), dtype=torch.float32, device=dev)
+        P.keep += [self.log2sum, self.x_hat]
+        P.call(lambda: ops.memset_zero(self.log2sum))
+        self.mask, self.rq, self.lik, self.y_prog = (P.buf(LB, h, w, d) for _ in range(4))
+        stacks = [m.lrp_transforms_prog[j] for j in range(ns)]
+        heads = parts["heads"]
+        reps = [(heads[id(st)][0], P.buf(LB, h, w, heads[id(st)][0].C)) for st in stacks]
+        reps += [(parts["yb"], P.buf(LB, h, w, d)), (parts["mu_tot"], P.buf(LB, h, w, d))]
+
+        def replicate():
+            for src, dst in reps:
+                dst.buf.view(NL, B, h, w, dst.ld).copy_(src.buf[..., src.c0:src.c0 + src.C].unsqueeze(0))
+        P.set_class("lrp_prog")
+        P.call(lambda: ops.variance_mask_levels(fp.std_p, self.prs, self.mask, n_slice=ns), "variance masks (sweep)")   # :621-622
+        P.call(lambda: ops.gauss_levels_eval(parts["y_top"], fp.mu_p, fp.std_p, self.mask, NL, y2=parts["y_sub"], yhat=self.rq,
+                                             lik=self.lik, log2sum=self.log2sum), "quantise + likelihood (sweep)")   # :625-629
+        P.call(replicate, "supports per level")
+        heads_l = {id(st): (dst, False) for st, (_, dst) in zip(stacks, reps)}
+        yb_l, mt_l = reps[ns][1], reps[ns + 1][1]
+        sp = m.support_progressive_slices
+        ins = []
+        for j in range(ns):
+            s_ = min(sp, j)
+            ins.append([sl(yb_l, j)] + ([sl(mt_l, j - s_, s_)] if s_ else []) + [sl(self.rq, j)])
+        E.lower_stacks(P, stacks, ins, [sl(self.y_prog, j) for j in range(ns)],
+                       [dict(act=L.ACT_HALF_TANH, post=sl(self.rq, j), post2=sl(yb_l, j)) for j in range(ns)], heads=heads_l)   # :635-641
+        P.set_class("g_s")
+        E.lower_g_s(P, [parts["g_s"]], [self.y_prog], [self.x_hat])
+
+    def level(self, v: ops.View, k: int) -> ops.View:
+        return ops.View(v.buf[k * self.B:(k + 1) * self.B], v.c0, v.C)
+
+    def close(self):
+        for g in self.graphs.values():
+            g.close()
+        self.graphs.clear()
+
+
+class _SweepPlan:
+    """``forward_qualities`` for one (B, H, W) (all_scalable, fp32 storage): the quality-independent
+    front end (g_a, hyperprior, base slices, progressive (mu, sigma) chain, stack heads — an _FsqPlan in sweep mode) runs
+    once, g_s[0] on y_hat_base only when 0 is asked for, and the per-level tail once per group of levels (_SweepTail,
+    one plan per group size, one hipGraph per tuple of mask qualities)."""
+
+    def __init__(self, m: VarianceMaskingPIC, B, H, W, device):
+        self.m, self.B, self.H, self.W = m, B, H, W
+        self.device = torch.device(device)
+        self.fp = _FsqPlan(m, B, H, W, False, None, device, sweep=True)
+        self.p_base = E.Plan(device)
+        self.p_base.set_class("g_s")
+        E.lower_g_s(self.p_base, [m.g_s[0] if m.multiple_decoder else m.g_s], [self.fp.y_base], [self.fp.x_hat])
+        self.tails: Dict[int, _SweepTail] = {}
+        self.graphs: Dict[tuple, ops.Graph] = {}         # ("front",) and ("base",)
+        self.stream = None
+
+    def _stream(self):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+        return self.stream
+
+    def front(self, x, use_graph: bool):
+        ops.drain_graveyard()
+        _launch(self.fp.plan, self.graphs, ("front",), self._stream(), use_graph, prep=lambda: self.fp.x_in.copy_(x))
+
+    def base(self, use_graph: bool):
+        _launch(self.p_base, self.graphs, ("base",), self._stream(), use_graph)
+
+    def tail(self, prs: Sequence[float], use_graph: bool) -> _SweepTail:
+        t = self.tails.get(len(prs))
+        if t is None:
+            t = self.tails[len(prs)] = _SweepTail(self.fp, len(prs))
+        t.prs = tuple(float(p_) for p_ in prs)
+        _launch(t.plan, t.graphs, t.prs, self._stream(), use_graph)
+        return t
+
+    def close(self):
+        self.fp.close()
+        for g in self.graphs.values():
+            g.close()
+        self.graphs.clear()
+        for t in self.tails.values():
+            t.close()
 
 
 class _DecPlan:

@@ -547,6 +547,26 @@ def gauss_tail(y: View, mu: View, sigma: View, *, y2: Optional[View] = None, mas
                                     stream_ptr()), "vam_gauss_tail")
 
 
+def gauss_levels_eval(y: View, mu: View, sigma: View, mask: View, n_levels: int, *, y2: Optional[View] = None,
+                      yhat: Optional[View] = None, lik: Optional[View] = None, sym: Optional[IView] = None,
+                      log2sum: Optional[torch.Tensor] = None):
+    """Evaluation tail of ``n_levels`` masks over one (y, y2, mu, sigma) window (rate sweep): per level the masked branch
+    of :func:`gauss_tail`, bit for bit.  ``mask`` / ``yhat`` / ``lik`` / ``sym`` hold the levels as consecutive image
+    blocks ([L * B, H, W, ld], level l = images l*B ..); ``log2sum`` [L, B] float64 receives level l's per-image sums."""
+    B = y.B
+    def lv(v):
+        if v is None:
+            return None, 0, 0
+        nb, ld = v.buf.shape[0], v.buf.shape[3]
+        assert nb == n_levels * B and tuple(v.buf.shape[1:3]) == (y.H, y.W) and v.C == y.C, (nb, n_levels, B, v.C, y.C)
+        return v.ptr, ld, B * y.H * y.W * ld
+    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
+    assert log2sum is None or (log2sum.dtype == torch.float64 and log2sum.is_contiguous() and log2sum.numel() == n_levels * B)
+    L.check(L.load().vam_gauss_levels_eval(*p(y), *p(y2), *p(mu), *p(sigma), *lv(mask), *lv(yhat), *lv(lik), *lv(sym),
+                                           log2sum.data_ptr() if log2sum is not None else None, y.H * y.W, n_levels,
+                                           y.n_pix, y.C, stream_ptr()), "vam_gauss_levels_eval")
+
+
 def build_indexes(sigma: View, table: torch.Tensor, mask: Optional[View] = None, out: Optional[IView] = None) -> torch.Tensor:
     if out is None:
         out = new_iview(sigma.B, sigma.H, sigma.W, sigma.C, sigma.buf.device)
@@ -859,6 +879,18 @@ def memset_zero(t: torch.Tensor):
 def sqdiff_sum(a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor):
     assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
     L.check(L.load().vam_sqdiff_sum(a.data_ptr(), b.data_ptr(), a.numel(), acc.data_ptr(), stream_ptr()), "vam_sqdiff_sum")
+
+
+def sqdiff_sum_levels(x: torch.Tensor, x_hat: torch.Tensor, acc: torch.Tensor):
+    """acc[l, b] += sum((x[b] - x_hat[l * B + b])^2) in float64: x [B, ...], x_hat [L * B, ...] (level-major), acc [L, B]."""
+    B = x.shape[0]
+    n = x[0].numel()
+    nl = x_hat.shape[0] // B
+    assert x.is_contiguous() and x_hat.is_contiguous() and x.dtype == x_hat.dtype == torch.float32
+    assert x_hat.shape[0] == nl * B and x_hat[0].numel() == n and x.device == x_hat.device
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == nl * B
+    L.check(L.load().vam_sqdiff_sum_levels(x.data_ptr(), x_hat.data_ptr(), B, n, nl, acc.data_ptr(), stream_ptr()),
+            "vam_sqdiff_sum_levels")
 
 
 # --------------------------------------------------------------------------- graphs / profiling

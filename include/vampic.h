@@ -289,6 +289,19 @@ int vam_gauss_tail(const float* y, int ld_y, const float* y2, int ld_y2,
                    float* yhat, int ld_yhat, float* lik, int ld_lik,
                    int32_t* sym, int ld_sym, double* log2sum, int pix_per_item,
                    long n_pix, int C, void* stream);
+/* Rate sweep (VarianceMaskingPIC.forward_qualities): the evaluation tail of n_levels masks over ONE
+ * shared (y, y2, mu, sigma) window.  With all_scalable every quality shares the progressive (mu, sigma) chain, so only
+ * the mask differs between levels.  y, y2, mu and sigma are loaded once per element; level l's mask, yhat, lik and sym
+ * live at their base pointer + l * <name>_ls floats (ints), each with its own pixel stride.  Per level the prog branch
+ * of vam_gauss_tail: yhat_l = round(r-mu)*m_l + mu, lik_l = L(|round((r-mu)*m_l)|, sigma*m_l), sym_l = round((r-mu)*m_l)
+ * — bit-identical to vam_gauss_tail called once per level.  log2sum (may be NULL): level l's per-item sum of log2(lik_l)
+ * is accumulated at log2sum[l * (n_pix / pix_per_item) + item] (fp64 atomics, cleared by the caller).  yhat, lik and sym
+ * may be NULL. */
+int vam_gauss_levels_eval(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                          const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls,
+                          float* yhat, int ld_yhat, long yhat_ls, float* lik, int ld_lik, long lik_ls,
+                          int32_t* sym, int ld_sym, long sym_ls, double* log2sum, int pix_per_item, int n_levels,
+                          long n_pix, int C, void* stream);
 
 /* GaussianConditional.build_indexes (entropy_models.py:654-659): idx = 63 - #{i<63: max(s,.11) <= T_i}
  * table: 64 floats (device). mask (may be NULL) multiplies sigma first (pic.py:809). */
@@ -325,6 +338,10 @@ int vam_add(const float* a, int ld_a, const float* b, int ld_b, float* out, int 
 int vam_memset_zero(void* ptr, size_t bytes, void* stream);
 /* sum((a-b)^2) accumulated in double into acc[0] (PSNR, utility/functions.py:172-174) */
 int vam_sqdiff_sum(const float* a, const float* b, long n, double* acc, void* stream);
+/* Rate sweep distortion: x [B, n] and xhat [n_levels * B, n] (level l = images l*B .. l*B+B-1, n = 3*H*W floats per image);
+ * out[l * B + b] += sum_i (x[b, i] - xhat[l*B + b, i])^2 in double (the arithmetic of vam_sqdiff_sum).  x is read once per
+ * element for up to 16 levels (one launch per 16 levels).  out is cleared by the caller. */
+int vam_sqdiff_sum_levels(const float* x, const float* xhat, int B, long n, int n_levels, double* out, void* stream);
 
 /* ------------------------------------------------------------------ MS-SSIM pieces (utility/functions.py:176-177) */
 /* One SSIM level over `planes` contiguous HxW planes (NCHW): 11-tap Gaussian window `win11` applied to x, y, x^2, y^2, xy
