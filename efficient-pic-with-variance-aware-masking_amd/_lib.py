@@ -40,6 +40,15 @@ VAM_MAX_WGRAD_GROUP = 16
 VAM_MAX_EW_GROUP = 8
 VAM_MAX_MASK_LEVELS = 8         # include/vampic.h: levels of one vam_variance_mask_levels launch
 VAM_MAX_TAIL_GROUP = 8
+VAM_MAX_LAYER_LEVELS = 32       # include/vampic.h: qualities of one vam_variance_layers launch
+VAM_RANS_MAX_THREADS = 16       # include/vampic.h: host threads of one vam_rans_*_streams call
+LAYER_NONE = 0xFF               # vam_variance_layers: the element is in no layer
+
+
+class VamRansStream(C.Structure):
+    _fields_ = [("symbols", C.c_void_p), ("symbols_out", C.c_void_p), ("indexes", C.c_void_p), ("layer", C.c_void_p),
+                ("n", C.c_long), ("sel", C.c_int), ("pad_", C.c_int), ("bytes", C.c_void_p), ("capacity", C.c_long),
+                ("n_bytes", C.c_long)]
 
 
 class VamWgrad(C.Structure):
@@ -140,6 +149,10 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_variance_mask_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_variance_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_gauss_levels_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_void_p]),
     "vam_gauss_tail": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_void_p, C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_gauss_levels_eval": (C.c_int, [C.c_void_p, C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_long] * 4
                               + [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p]),
@@ -182,6 +195,10 @@ _SIGNATURES = {
     "vam_pmf_to_quantized_cdf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vam_rans_encode": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long]),
     "vam_rans_decode": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_rans_encode_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int]),
+    "vam_rans_decode_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int]),
     "vam_graph_begin": (C.c_int, [C.c_void_p]),
     "vam_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "vam_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

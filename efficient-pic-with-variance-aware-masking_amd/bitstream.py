@@ -4,7 +4,9 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -63,3 +65,59 @@ def decode(stream: bytes, indexes: np.ndarray, t: Tables) -> np.ndarray:
                                      t.sizes.ctypes.data, t.offsets.ctypes.data, t.cdf.shape[0], out.ctypes.data),
             "vam_rans_decode")
     return out
+
+
+def coder_threads(requested: Optional[int] = None) -> int:
+    """Host threads for the stream coder: at most L.VAM_RANS_MAX_THREADS and the CPUs this process may run on."""
+    n = min(L.VAM_RANS_MAX_THREADS, len(os.sched_getaffinity(0)))
+    return max(1, n if requested is None else min(int(requested), n))
+
+
+def _i32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+
+def _layer(a) -> Optional[np.ndarray]:
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+
+
+def encode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> List[bytes]:
+    """Many independent streams in one vam_rans_encode_streams call.  ``jobs``: (symbols, indexes) or (symbols, indexes,
+    layer, sel) per stream; with a layer array only the elements with layer == sel are coded (the others as 0 / table 0).
+    Each stream's bytes equal :func:`encode`'s on the same (masked) inputs.  ``threads`` is passed on as given (the library
+    clamps it to L.VAM_RANS_MAX_THREADS); None = :func:`coder_threads`."""
+    keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
+    caps = []
+    for j in jobs:
+        s, i = _i32(j[0]), _i32(j[1])
+        ly = _layer(j[2]) if len(j) > 2 else None
+        assert s.size == i.size and (ly is None or ly.size == s.size)
+        caps.append(8 * s.size + 64)
+        keep.append((s, i, ly))
+    out = np.empty(sum(caps), dtype=np.uint8)
+    off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    for k, (j, (s, i, ly)) in enumerate(zip(jobs, keep)):
+        arr[k] = L.VamRansStream(s.ctypes.data, None, i.ctypes.data, ly.ctypes.data if ly is not None else None, s.size,
+                                 int(j[3]) if ly is not None else 0, 0, out.ctypes.data + int(off[k]), caps[k], 0)
+    L.check(L.load().vam_rans_encode_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                             t.offsets.ctypes.data, t.cdf.shape[0],
+                                             coder_threads() if threads is None else int(threads)), "vam_rans_encode_streams")
+    return [out[int(off[k]):int(off[k]) + arr[k].n_bytes].tobytes() for k in range(len(jobs))]
+
+
+def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> None:
+    """Decode many streams in one vam_rans_decode_streams call.  ``jobs``: (stream bytes, indexes, out) or (stream bytes,
+    indexes, out, layer, sel); ``out`` is a writable C-contiguous int32 array of the indexes' size.  With a layer array only
+    out[layer == sel] is written, so the layers of a container can fill one array."""
+    keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
+    for k, j in enumerate(jobs):
+        src = np.frombuffer(j[0], dtype=np.uint8)
+        i, o = _i32(j[1]), j[2]
+        ly = _layer(j[3]) if len(j) > 3 else None
+        assert o.dtype == np.int32 and o.flags.c_contiguous and o.size == i.size and (ly is None or ly.size == i.size)
+        keep.append((src, i, ly))
+        arr[k] = L.VamRansStream(None, o.ctypes.data, i.ctypes.data, ly.ctypes.data if ly is not None else None, i.size,
+                                 int(j[4]) if ly is not None else 0, 0, src.ctypes.data, src.size, src.size)
+    L.check(L.load().vam_rans_decode_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                             t.offsets.ctypes.data, t.cdf.shape[0],
+                                             coder_threads() if threads is None else int(threads)), "vam_rans_decode_streams")

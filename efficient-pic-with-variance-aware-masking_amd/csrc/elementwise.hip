@@ -219,6 +219,42 @@ __global__ void gauss_levels_eval_kernel(const TailLevelsArgs a) {
   }
 }
 
+// The decoder's side of the levels tail (vam_gauss_levels_decode): q = float(sym) is the decoded round(r - mu) and level l's
+// mask is (layer <= k_l); yhat_l through masked_tail's expression q * m + mu, so it equals gauss_levels_eval_kernel's.
+struct DecodeLevelsArgs {
+  const int32_t* sym;
+  const uint8_t* layer;
+  const float* mu;
+  float* yhat;
+  int ld_sym, ld_layer, ld_mu, ld_yhat;
+  long ls_yhat;
+  int ks[VAM_MAX_MASK_LEVELS];
+  int n_levels, C4;
+  long n_vec;
+};
+
+__global__ void gauss_levels_decode_kernel(const DecodeLevelsArgs a) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_vec; i += (long)gridDim.x * blockDim.x) {
+    long p = i / a.C4;
+    int c = (int)(i - p * a.C4) * 4;
+    int4 sy = *reinterpret_cast<const int4*>(a.sym + p * a.ld_sym + c);
+    unsigned ly = *reinterpret_cast<const unsigned*>(a.layer + p * a.ld_layer + c);
+    float4 mu = *reinterpret_cast<const float4*>(a.mu + p * a.ld_mu + c);
+    float qv[4] = {(float)sy.x, (float)sy.y, (float)sy.z, (float)sy.w}, mv[4] = {mu.x, mu.y, mu.z, mu.w};
+    int lv4[4] = {(int)(ly & 255u), (int)((ly >> 8) & 255u), (int)((ly >> 16) & 255u), (int)(ly >> 24)};
+    for (int lv = 0; lv < a.n_levels; ++lv) {
+      const int k = a.ks[lv];
+      float yh[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float m = lv4[e] <= k ? 1.f : 0.f;
+        yh[e] = qv[e] * m + mv[e];
+      }
+      *reinterpret_cast<float4*>(a.yhat + lv * a.ls_yhat + p * a.ld_yhat + c) = make_float4(yh[0], yh[1], yh[2], yh[3]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ build_indexes
 __global__ void build_indexes_kernel(const float* __restrict__ sigma, int ld_sigma, const float* __restrict__ mask,
                                      int ld_mask, const float* __restrict__ table, int n_table,
@@ -517,6 +553,25 @@ int vam_gauss_levels_eval(const float* y, int ld_y, const float* y2, int ld_y2, 
   ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, 4.0 * (double)n_pix * C * (nin + nout));
   hipLaunchKernelGGL(gauss_levels_eval_kernel, dim3(stream_grid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("gauss_levels_eval_kernel");
+}
+
+int vam_gauss_levels_decode(const int32_t* sym, int ld_sym, const uint8_t* layer, int ld_layer, const float* mu, int ld_mu,
+                            const int* ks, int n_levels, float* yhat, int ld_yhat, long yhat_ls, long n_pix, int C,
+                            void* stream) {
+  VAM_REQUIRE(sym && layer && mu && ks && yhat && n_pix > 0 && C > 0 && C % 4 == 0, "vam_gauss_levels_decode: bad arguments");
+  VAM_REQUIRE(n_levels >= 1 && n_levels <= VAM_MAX_MASK_LEVELS, "vam_gauss_levels_decode: 1..%d levels, got %d",
+              VAM_MAX_MASK_LEVELS, n_levels);
+  VAM_REQUIRE(al16(sym) && al16(mu) && al16(yhat) && (((uintptr_t)layer) & 3) == 0, "vam_gauss_levels_decode: alignment");
+  VAM_REQUIRE(ld_sym % 4 == 0 && ld_layer % 4 == 0 && ld_mu % 4 == 0 && ld_yhat % 4 == 0 && yhat_ls % 4 == 0,
+              "vam_gauss_levels_decode: strides must be multiples of 4");
+  DecodeLevelsArgs a;
+  a.sym = sym; a.layer = layer; a.mu = mu; a.yhat = yhat;
+  a.ld_sym = ld_sym; a.ld_layer = ld_layer; a.ld_mu = ld_mu; a.ld_yhat = ld_yhat; a.ls_yhat = yhat_ls;
+  for (int l = 0; l < VAM_MAX_MASK_LEVELS; ++l) a.ks[l] = l < n_levels ? ks[l] : -1;
+  a.n_levels = n_levels; a.C4 = C / 4; a.n_vec = n_pix * (C / 4);
+  ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, (double)n_pix * C * (9.0 + 4.0 * n_levels));
+  hipLaunchKernelGGL(gauss_levels_decode_kernel, dim3(stream_grid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("gauss_levels_decode_kernel");
 }
 
 int vam_build_indexes(const float* sigma, int ld_sigma, const float* mask, int ld_mask, const float* table,

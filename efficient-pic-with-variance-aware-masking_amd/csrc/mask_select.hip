@@ -182,27 +182,31 @@ __global__ __launch_bounds__(1024) void variance_mask_kernel(const MaskArgs a) {
   }
 }
 
-// vam_variance_mask_levels: the same selection for several qualities over one load of the segment
+// vam_variance_mask_levels: the same selection for several qualities over one load of the segment;
+// vam_variance_layers: the same selections, then one pass that assigns each element its container layer
 struct MaskLevelsArgs {
   const float* sigma;
   float* mask;
   float* thr;
+  uint8_t* layer;                    // LAYERS: layer ids instead of masks
   long batch_stride, slice_stride, mask_batch_stride, mask_slice_stride, mask_level_stride;
   int ld, ld_mask, n_slice, n_pix, C4;
   int n_levels, any_select;          // any_select: some level needs the order statistics
   // per level (vam_variance_mask: one level)
-  int k_lo[VAM_MAX_MASK_LEVELS], k_hi[VAM_MAX_MASK_LEVELS];
-  float w[VAM_MAX_MASK_LEVELS];
-  int mode[VAM_MAX_MASK_LEVELS];     // 0 = quantile, 1 = all zero (pr == 0), 2 = all one (pr >= 10)
+  int k_lo[VAM_MAX_LAYER_LEVELS], k_hi[VAM_MAX_LAYER_LEVELS];
+  float w[VAM_MAX_LAYER_LEVELS];
+  int mode[VAM_MAX_LAYER_LEVELS];    // 0 = quantile, 1 = all zero (pr == 0), 2 = all one (pr >= 10)
 };
 
 // MAXV = float4 per thread kept in registers (0 = stream from memory every pass).  The segment is loaded once; each level
-// then runs its own selection on the same registers and writes its own mask.
-template <int MAXV>
+// then runs its own selection on the same registers and writes its own mask.  LAYERS: the levels' thresholds stay in
+// LDS, and one last pass writes layer = the first level whose mask holds the element (mask_* name the layer array).
+template <int MAXV, bool LAYERS>
 __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLevelsArgs a) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sh_prefix, sh_k, sh_cnt, sh_min;
   __shared__ int sh_nan;
+  __shared__ float sh_thr[LAYERS ? VAM_MAX_LAYER_LEVELS : 1];
 
   const int seg = blockIdx.x;
   const int segs = gridDim.x;
@@ -257,7 +261,8 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
     float* thr_out = a.thr ? a.thr + (long)lv * segs : nullptr;
     if (a.mode[lv] != 0) {
       const float v = a.mode[lv] == 2 ? 1.f : 0.f;
-      for (int i = tid; i < nvec; i += 1024) *reinterpret_cast<float4*>(out_ptr(dst, i)) = make_float4(v, v, v, v);
+      if (!LAYERS)
+        for (int i = tid; i < nvec; i += 1024) *reinterpret_cast<float4*>(out_ptr(dst, i)) = make_float4(v, v, v, v);
       if (tid == 0 && thr_out) thr_out[seg] = a.mode[lv] == 2 ? -INFINITY : INFINITY;
       continue;
     }
@@ -330,6 +335,10 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
     float thr = (w < 0.5f) ? __builtin_fmaf(w, d, lo_v) : __builtin_fmaf(w - 1.0f, d, hi_v);
     if (sh_nan) thr = __uint_as_float(0x7FC00000u);
     if (tid == 0 && thr_out) thr_out[seg] = thr;
+    if (LAYERS) {
+      if (tid == 0) sh_thr[lv] = thr;
+      continue;
+    }
 
     if (MAXV > 0) {
 #pragma unroll
@@ -348,6 +357,32 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
                                                                    v.z >= thr ? 1.f : 0.f, v.w >= thr ? 1.f : 0.f);
       }
     }
+  }
+  if (!LAYERS) return;
+
+  // ---- layer assignment: layer <= k  <=>  mask_k == 1 (the masks of a non-decreasing quality list are nested)
+  __syncthreads();
+  uint8_t* const ldst = a.layer + b * a.mask_batch_stride + j * a.mask_slice_stride;
+  auto layer_of = [&](float x) -> unsigned {
+    for (int lv = 0; lv < a.n_levels; ++lv) {
+      const int md = a.mode[lv];
+      if (md == 2 || (md == 0 && x >= sh_thr[lv])) return (unsigned)lv;
+    }
+    return 0xFFu;
+  };
+  auto put = [&](int i, float4 v) {
+    int p = i / a.C4;
+    const unsigned word = layer_of(v.x) | (layer_of(v.y) << 8) | (layer_of(v.z) << 16) | (layer_of(v.w) << 24);
+    *reinterpret_cast<unsigned*>(ldst + (long)p * a.ld_mask + (i - p * a.C4) * 4) = word;
+  };
+  if (MAXV > 0) {
+#pragma unroll
+    for (int r = 0; r < MAXV; ++r) {
+      int i = tid + r * 1024;
+      if (i < nvec) put(i, reg[r]);
+    }
+  } else {
+    for (int i = tid; i < nvec; i += 1024) put(i, *reinterpret_cast<const float4*>(vec_ptr(i)));
   }
 }
 
@@ -426,19 +461,26 @@ static int mask_level_params(MaskLevelsArgs& a, int lv, double pr, long n) {
   return 0;
 }
 
+// layer_out != NULL: vam_variance_layers (mask_* then describe the uint8 layer array)
 static int mask_launch(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice, int n_pix,
-                       int C, const double* prs, int n_levels, float* mask_out, int ld_mask, long mask_batch_stride,
-                       long mask_slice_stride, long mask_level_stride, float* thr_out, void* stream) {
-  VAM_REQUIRE(sigma && mask_out && n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "vam_variance_mask: bad arguments");
+                       int C, const double* prs, int n_levels, float* mask_out, uint8_t* layer_out, int ld_mask,
+                       long mask_batch_stride, long mask_slice_stride, long mask_level_stride, float* thr_out, void* stream) {
+  const bool layers = layer_out != nullptr;
+  VAM_REQUIRE(sigma && (mask_out || layers) && n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "vam_variance_mask: bad arguments");
   VAM_REQUIRE(C % 4 == 0 && ld % 4 == 0 && ld_mask % 4 == 0 && batch_stride % 4 == 0 && slice_stride % 4 == 0 && mask_batch_stride % 4 == 0 && mask_slice_stride % 4 == 0 && mask_level_stride % 4 == 0, "vam_variance_mask: C and strides must be multiples of 4");
-  VAM_REQUIRE((((uintptr_t)sigma) & 15) == 0 && (((uintptr_t)mask_out) & 15) == 0, "vam_variance_mask: 16-byte alignment");
+  VAM_REQUIRE((((uintptr_t)sigma) & 15) == 0 && (((uintptr_t)mask_out) & 15) == 0 && (((uintptr_t)layer_out) & 3) == 0,
+              "vam_variance_mask: 16-byte alignment (layers: 4-byte)");
   VAM_REQUIRE(ld >= C && ld_mask >= C, "vam_variance_mask: pixel stride < C");
-  VAM_REQUIRE(prs && n_levels >= 1 && n_levels <= VAM_MAX_MASK_LEVELS, "vam_variance_mask_levels: 1..%d levels, got %d", VAM_MAX_MASK_LEVELS, n_levels);
+  const int max_levels = layers ? VAM_MAX_LAYER_LEVELS : VAM_MAX_MASK_LEVELS;
+  VAM_REQUIRE(prs && n_levels >= 1 && n_levels <= max_levels, "%s: 1..%d levels, got %d",
+              layers ? "vam_variance_layers" : "vam_variance_mask_levels", max_levels, n_levels);
+  for (int lv = 1; layers && lv < n_levels; ++lv)
+    VAM_REQUIRE(prs[lv] >= prs[lv - 1], "vam_variance_layers: qualities must be non-decreasing (prs[%d] < prs[%d])", lv, lv - 1);
   const long n = (long)n_pix * C;
   // torch.quantile rejects inputs above 16M elements (ATen Sorting.cpp); so do we
   VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
   MaskLevelsArgs a;
-  a.sigma = sigma; a.mask = mask_out; a.thr = thr_out;
+  a.sigma = sigma; a.mask = mask_out; a.thr = thr_out; a.layer = layer_out;
   a.batch_stride = batch_stride; a.slice_stride = slice_stride;
   a.mask_batch_stride = mask_batch_stride; a.mask_slice_stride = mask_slice_stride; a.mask_level_stride = mask_level_stride;
   a.ld = ld; a.ld_mask = ld_mask; a.n_slice = n_slice; a.n_pix = n_pix; a.C4 = C / 4;
@@ -452,13 +494,22 @@ static int mask_launch(const float* sigma, int ld, long batch_stride, long slice
   const int segs = n_batch * n_slice;
   const int nvec = n_pix * (C / 4);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(VAM_FAM_MASK, s, 0, (4.0 + 4.0 * n_levels) * (double)n * segs);
+  ProfScope ps(VAM_FAM_MASK, s, 0, (layers ? 5.0 : 4.0 + 4.0 * n_levels) * (double)n * segs);
+  if (layers) {
+    if (nvec <= 4 * 1024)
+      hipLaunchKernelGGL((variance_mask_levels_kernel<4, true>), dim3(segs), dim3(1024), 0, s, a);
+    else if (nvec <= 16 * 1024)
+      hipLaunchKernelGGL((variance_mask_levels_kernel<16, true>), dim3(segs), dim3(1024), 0, s, a);
+    else
+      hipLaunchKernelGGL((variance_mask_levels_kernel<0, true>), dim3(segs), dim3(1024), 0, s, a);
+    return check_launch("variance_layers_kernel");
+  }
   if (nvec <= 4 * 1024)
-    hipLaunchKernelGGL((variance_mask_levels_kernel<4>), dim3(segs), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL((variance_mask_levels_kernel<4, false>), dim3(segs), dim3(1024), 0, s, a);
   else if (nvec <= 16 * 1024)
-    hipLaunchKernelGGL((variance_mask_levels_kernel<16>), dim3(segs), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL((variance_mask_levels_kernel<16, false>), dim3(segs), dim3(1024), 0, s, a);
   else
-    hipLaunchKernelGGL((variance_mask_levels_kernel<0>), dim3(segs), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL((variance_mask_levels_kernel<0, false>), dim3(segs), dim3(1024), 0, s, a);
   return check_launch("variance_mask_levels_kernel");
 }
 
@@ -466,6 +517,14 @@ extern "C" int vam_variance_mask_levels(const float* sigma, int ld, long batch_s
                                         int n_slice, int n_pix, int C, const double* prs, int n_levels, float* mask_out,
                                         int ld_mask, long mask_batch_stride, long mask_slice_stride, long mask_level_stride,
                                         float* thr_out, void* stream) {
-  return mask_launch(sigma, ld, batch_stride, slice_stride, n_batch, n_slice, n_pix, C, prs, n_levels, mask_out, ld_mask,
-                     mask_batch_stride, mask_slice_stride, mask_level_stride, thr_out, stream);
+  return mask_launch(sigma, ld, batch_stride, slice_stride, n_batch, n_slice, n_pix, C, prs, n_levels, mask_out, nullptr,
+                     ld_mask, mask_batch_stride, mask_slice_stride, mask_level_stride, thr_out, stream);
+}
+
+extern "C" int vam_variance_layers(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice,
+                                   int n_pix, int C, const double* prs, int n_levels, uint8_t* layer_out, int ld_layer,
+                                   long layer_batch_stride, long layer_slice_stride, float* thr_out, void* stream) {
+  VAM_REQUIRE(layer_out, "vam_variance_layers: layer_out is NULL");
+  return mask_launch(sigma, ld, batch_stride, slice_stride, n_batch, n_slice, n_pix, C, prs, n_levels, nullptr, layer_out,
+                     ld_layer, layer_batch_stride, layer_slice_stride, 0, thr_out, stream);
 }

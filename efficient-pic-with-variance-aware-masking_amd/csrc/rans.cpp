@@ -11,9 +11,13 @@
 //
 // Host code by nature (bit-serial, one stream per image and slice); it runs beside the GPU path,
 // exactly where the reference runs it (SURVEY §1 "sits beside the path").
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
 #include <vector>
 #include "../../include/vampic.h"
 
@@ -111,8 +115,14 @@ int vam_pmf_to_quantized_cdf(const float* pmf, int n, int precision, int32_t* cd
   return VAM_OK;
 }
 
-long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
-                     const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap) {
+}  // extern "C"
+
+namespace {
+
+// One stream.  layer != NULL: element i is coded as symbol 0 with table 0 unless layer[i] == sel (the reference's
+// `r_sym * delta`, `idx * delta`, src/test/functions_encode.py:190-192, without building the masked copies).
+long encode_one(const int32_t* symbols, const int32_t* indexes, const uint8_t* layer, int sel, long n, const int32_t* cdfs,
+                int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap) {
   if (!symbols || !indexes || !cdfs || !cdf_sizes || !offsets || !out || n < 0 || n_cdfs < 1) {
     set_error("vam_rans_encode: bad arguments");
     return VAM_EINVAL;
@@ -120,7 +130,8 @@ long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, con
   std::vector<Sym> syms;
   syms.reserve((size_t)n + 16);
   for (long i = 0; i < n; ++i) {
-    const int ci = indexes[i];
+    const bool keep = !layer || layer[i] == sel;
+    const int ci = keep ? indexes[i] : 0;
     if (ci < 0 || ci >= n_cdfs) {
       set_error("vam_rans_encode: index %d out of range at %ld", ci, i);
       return VAM_EINVAL;
@@ -131,7 +142,7 @@ long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, con
       set_error("vam_rans_encode: cdf size %d invalid for table %d", cdf_sizes[ci], ci);
       return VAM_EINVAL;
     }
-    int32_t value = symbols[i] - offsets[ci];
+    int32_t value = (keep ? symbols[i] : 0) - offsets[ci];
     uint32_t raw = 0;
     if (value < 0) {
       raw = (uint32_t)(-2 * (int64_t)value - 1);
@@ -143,7 +154,7 @@ long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, con
     syms.push_back({(uint16_t)cdf[value], (uint16_t)(cdf[value + 1] - cdf[value]), false});
     if (value == max_value) {                      // bypass mode: Golomb-like count + raw 4-bit chunks
       int n_bypass = 0;
-      while ((raw >> (n_bypass * kBypassBits)) != 0) ++n_bypass;
+      while (n_bypass < 32 / kBypassBits && (raw >> (n_bypass * kBypassBits)) != 0) ++n_bypass;   // no shift by 32
       int32_t val = n_bypass;
       while (val >= (int32_t)kMaxBypass) {
         syms.push_back({(uint16_t)kMaxBypass, (uint16_t)(kMaxBypass + 1), true});
@@ -181,8 +192,11 @@ long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, con
   return nbytes;
 }
 
-int vam_rans_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
-                    int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out) {
+// One stream.  layer != NULL: element i is decoded with table 0 unless layer[i] == sel, and only the elements with
+// layer[i] == sel are written to out (the layers of a container fill one symbol array).
+int decode_one(const uint8_t* in, long n_bytes, const int32_t* indexes, const uint8_t* layer, int sel, long n,
+               const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs,
+               int32_t* out) {
   if (!in || !indexes || !cdfs || !cdf_sizes || !offsets || !out || n < 0 || n_bytes < 8 || (n_bytes & 3)) {
     set_error("vam_rans_decode: bad arguments (stream of %ld bytes)", n_bytes);
     return VAM_EINVAL;
@@ -195,7 +209,8 @@ int vam_rans_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, lon
   p += 2;
   bool ok = true;
   for (long i = 0; i < n; ++i) {
-    const int ci = indexes[i];
+    const bool keep = !layer || layer[i] == sel;
+    const int ci = keep ? indexes[i] : 0;
     if (ci < 0 || ci >= n_cdfs) {
       set_error("vam_rans_decode: index %d out of range at %ld", ci, i);
       return VAM_EINVAL;
@@ -227,13 +242,86 @@ int vam_rans_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, lon
       else value += max_value;
     }
     if (!ok) break;
-    out[i] = value + offsets[ci];
+    if (keep) out[i] = value + offsets[ci];
   }
   if (!ok) {
     set_error("vam_rans_decode: bitstream truncated");
     return VAM_EINVAL;
   }
   return VAM_OK;
+}
+
+// Runs job(i) for i in [0, n_jobs) on min(n_threads, n_jobs) threads (the caller's thread included).  Jobs write
+// disjoint memory.  The first failure (lowest job index) becomes this thread's vam_last_error.
+template <class F>
+int run_jobs(int n_jobs, int n_threads, const char* what, F&& job) {
+  if (n_jobs < 0 || n_threads < 1) {
+    set_error("%s: bad arguments (%d streams, %d threads)", what, n_jobs, n_threads);
+    return VAM_EINVAL;
+  }
+  const int nt = std::min(std::min(n_threads, VAM_RANS_MAX_THREADS), std::max(n_jobs, 1));
+  std::atomic<int> next{0};
+  std::mutex mu;
+  int bad = -1;
+  std::string msg;
+  auto worker = [&]() {
+    for (int i = next++; i < n_jobs; i = next++) {
+      if (job(i) >= 0) continue;
+      std::lock_guard<std::mutex> g(mu);
+      if (bad < 0 || i < bad) { bad = i; msg = vam_last_error(); }
+    }
+  };
+  std::vector<std::thread> pool;
+  pool.reserve(nt - 1);
+  for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
+  worker();
+  for (auto& t : pool) t.join();
+  if (bad >= 0) {
+    set_error("%s: stream %d: %s", what, bad, msg.c_str());
+    return VAM_EINVAL;
+  }
+  return VAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long vam_rans_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                     const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap) {
+  return encode_one(symbols, indexes, nullptr, 0, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out, out_cap);
+}
+
+int vam_rans_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
+                    int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out) {
+  return decode_one(in, n_bytes, indexes, nullptr, 0, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out);
+}
+
+int vam_rans_encode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs, int cdf_stride,
+                            const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int n_threads) {
+  if (n_streams > 0 && !streams) {
+    set_error("vam_rans_encode_streams: bad arguments");
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, "vam_rans_encode_streams", [&](int i) -> long {
+    vam_rans_stream& s = streams[i];
+    s.n_bytes = encode_one(s.symbols, s.indexes, s.layer, s.sel, s.n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                           s.bytes, s.capacity);
+    return s.n_bytes;
+  });
+}
+
+int vam_rans_decode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs, int cdf_stride,
+                            const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int n_threads) {
+  if (n_streams > 0 && !streams) {
+    set_error("vam_rans_decode_streams: bad arguments");
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, "vam_rans_decode_streams", [&](int i) -> long {
+    const vam_rans_stream& s = streams[i];
+    return decode_one(s.bytes, s.n_bytes, s.indexes, s.layer, s.sel, s.n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                      s.symbols_out);
+  });
 }
 
 }  // extern "C"

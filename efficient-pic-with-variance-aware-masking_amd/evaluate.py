@@ -168,6 +168,51 @@ def compress_with_ac(model, images: Iterable[torch.Tensor], pr_list: Sequence[fl
     return avg(bpp), avg(psnr), avg(t_enc), avg(t_dec)
 
 
+def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float]):
+    """The demo's progressive printout (reference demo.py with src/test/functions_encode.py / functions_decode.py) for a
+    list of images on the batched container (progressive.encode_batch / ProgressiveDecoder): images of one shape are
+    padded as :func:`compress_with_ac` pads them and coded as one batch; every level 0..len(q_list) is decoded.  Returns
+    one dict per level: q (0 for the base), bpp (8 * the container's bytes up to the level / pixels of the ORIGINAL image),
+    psnr (of the cropped decode), enc_s and dec_s (seconds per image: the encode once, the decode of that level), each
+    the mean over the images, plus the per-image "bpp_all" / "psnr_all"."""
+    from . import progressive as P
+    images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
+    nl = len(q_list) + 1
+    rows = [{"q": 0.0 if k == 0 else float(q_list[k - 1]), "bpp_all": [None] * len(images), "psnr_all": [None] * len(images),
+             "enc_s": 0.0, "dec_s": 0.0} for k in range(nl)]
+    by_shape = {}
+    for i, x in enumerate(images):
+        by_shape.setdefault(tuple(x.shape[1:]), []).append(i)
+    with torch.no_grad():
+        for ids in by_shape.values():
+            xs = torch.cat([images[i] for i in ids], 0)
+            xp, unpad = pad_image(xs)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            containers, _ = P.encode_batch(model, xp, q_list)
+            t1 = time.perf_counter()
+            dec = P.ProgressiveDecoder(model, containers)
+            for k in range(nl):
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                out = dec.decode(k)
+                torch.cuda.synchronize()
+                t3 = time.perf_counter()
+                x_hat = torch.nn.functional.pad(out["x_hat"], unpad)
+                rows[k]["enc_s"] += (t1 - t0)
+                rows[k]["dec_s"] += (t3 - t2) if k else (t3 - t1)       # level 0 includes the base decode
+                for n, (i, c) in enumerate(zip(ids, containers)):
+                    x = images[i]
+                    rows[k]["bpp_all"][i] = P.bits_up_to(c, k) / (x.shape[0] * x.shape[2] * x.shape[3])
+                    rows[k]["psnr_all"][i] = compute_psnr(x, x_hat[n:n + 1])
+    for r in rows:
+        r["bpp"] = sum(r["bpp_all"]) / len(images)
+        r["psnr"] = sum(r["psnr_all"]) / len(images)
+        r["enc_s"] /= len(images)
+        r["dec_s"] /= len(images)
+    return rows
+
+
 def valid_epoch(epoch: int, test_dataloader: Iterable[torch.Tensor], criterion, model, pr_list: Sequence[float] = (0.05,),
                 rems: Optional[Sequence[float]] = None):
     """training/step.py:136-202 (without wandb): mean criterion loss over batches x qualities — what drives the

@@ -635,6 +635,21 @@ class VarianceMaskingPIC(CompressionModel):
         pr = 10 if (mask_pol == "two-levels" and quality != 0) else quality
         return {"x_hat": dp.decode(strings, pr, checkpoint_rep if rem_idx is not None else None)}
 
+    def _prog_dec_plan(self, B, hz, wz, q_list) -> "_ProgDecPlan":
+        """The plans of progressive.ProgressiveDecoder for one (B, z-shape, quality list), cached beside decompress's."""
+        dev = self.entropy_bottleneck.quantiles.device
+        key = ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev))
+        wsig = self._weights_sig()
+        dp = self._dec_plans.get(key)
+        if dp is not None and dp.wsig != wsig:            # a weight was edited in place since the plan packed it
+            self._dec_plans.pop(key).close()
+            dp = None
+        if dp is None:
+            dp = _ProgDecPlan(self, B, hz, wz, q_list, dev)
+            dp.wsig = wsig
+            self._dec_plans[key] = dp
+        return dp
+
 
 class VarianceMaskingPICREM(VarianceMaskingPIC):
     """models/rem_pic.py:8-818."""
@@ -1099,7 +1114,8 @@ class _FsqPlan:
             # rate sweep (_SweepPlan): everything up to here does not depend on the quality; the per-level tail and the
             # base reconstruction are plans of their own over these buffers
             self.mu_f, self.std_f = self.mu_p, self.std_p
-            self.sweep_parts = dict(heads=heads, yb=yb, mu_tot=mu_tot, y_top=y_top, y_sub=y_sub, g_s=g_s)
+            self.sweep_parts = dict(heads=heads, yb=yb, mu=self.mu_p, std=self.std_p, mu_tot=mu_tot, y_top=y_top, y_sub=y_sub,
+                                    g_s=g_s)
             return
 
         mu_f, std_f = self.mu_p, self.std_p
@@ -1398,25 +1414,32 @@ class _SweepTail:
     The masks are one vam_variance_mask_levels launch, quantisation and likelihood one vam_gauss_levels_eval launch; the
     ten LRP stacks and g_s[1] run once over the level batch.  The stacks' shared inputs — the stack heads (bias + the
     hyperprior part of the first layer, computed once at B images: the eval plan's association of that sum), y_hat_base
-    and mu_total — are replicated per level."""
+    and mu_total — are replicated per level.
 
-    def __init__(self, fp: "_FsqPlan", n_levels: int):
-        m, B, H, W = fp.m, fp.B, fp.H, fp.W
+    ``decode``: the quantised latents come from decoded symbols instead (_ProgDecPlan): one vam_gauss_levels_decode launch
+    over the plan's symbols and container layer ids, with the container-layer cut-offs ``ks`` in place of the qualities
+    (level g keeps the elements of layers <= ks[g]); no masks and no likelihoods.  The rest of the tail is the same."""
+
+    def __init__(self, fp, n_levels: int, decode: bool = False):
+        m, parts = fp.m, fp.sweep_parts
+        yb0 = parts["yb"]
+        B, h, w = yb0.B, yb0.H, yb0.W
+        H, W = 16 * h, 16 * w
         assert 1 <= n_levels <= L.VAM_MAX_MASK_LEVELS
         NL, LB = n_levels, n_levels * B
-        h, w, d, ns, C = H // 16, W // 16, m.division_dimension[0], m.ns0, m.dim_chunk
-        dev = fp.x_in.device
+        d, ns, C = m.division_dimension[0], m.ns0, m.dim_chunk
+        dev = yb0.buf.device
         self.n_levels, self.B = NL, B
-        self.prs = (0.0,) * NL
+        self.prs = (0.0,) * NL            # eval: the mask qualities of the levels
+        self.ks = (0,) * NL               # decode: the container-layer cut-offs of the levels
         self.graphs: Dict[tuple, ops.Graph] = {}
         P = self.plan = E.Plan(dev)
         sl = lambda v, i, n=1: v.window(i * C, n * C)
-        parts = fp.sweep_parts
         self.log2sum = torch.zeros((NL, B), dtype=torch.float64, device=dev)      # level k's progressive log2 sums per image
         self.x_hat = torch.empty((LB, 3, H, W), dtype=torch.float32, device=dev)
         P.keep += [self.log2sum, self.x_hat]
-        P.call(lambda: ops.memset_zero(self.log2sum))
-        self.mask, self.rq, self.lik, self.y_prog = (P.buf(LB, h, w, d) for _ in range(4))
+        self.rq, self.y_prog = P.buf(LB, h, w, d), P.buf(LB, h, w, d)
+        self.mask = self.lik = None
         stacks = [m.lrp_transforms_prog[j] for j in range(ns)]
         heads = parts["heads"]
         reps = [(heads[id(st)][0], P.buf(LB, h, w, heads[id(st)][0].C)) for st in stacks]
@@ -1426,9 +1449,15 @@ class _SweepTail:
             for src, dst in reps:
                 dst.buf.view(NL, B, h, w, dst.ld).copy_(src.buf[..., src.c0:src.c0 + src.C].unsqueeze(0))
         P.set_class("lrp_prog")
-        P.call(lambda: ops.variance_mask_levels(fp.std_p, self.prs, self.mask, n_slice=ns), "variance masks (sweep)")   # :621-622
-        P.call(lambda: ops.gauss_levels_eval(parts["y_top"], fp.mu_p, fp.std_p, self.mask, NL, y2=parts["y_sub"], yhat=self.rq,
-                                             lik=self.lik, log2sum=self.log2sum), "quantise + likelihood (sweep)")   # :625-629
+        if decode:                                  # functions_decode.py:186-207: the decoded layers <= k, + mu
+            P.call(lambda: ops.gauss_levels_decode(parts["sym"], parts["layer"], parts["mu"], self.ks, self.rq),
+                   "dequantise levels (decode)")
+        else:
+            self.mask, self.lik = P.buf(LB, h, w, d), P.buf(LB, h, w, d)
+            P.call(lambda: ops.memset_zero(self.log2sum))
+            P.call(lambda: ops.variance_mask_levels(parts["std"], self.prs, self.mask, n_slice=ns), "variance masks (sweep)")   # :621-622
+            P.call(lambda: ops.gauss_levels_eval(parts["y_top"], parts["mu"], parts["std"], self.mask, NL, y2=parts["y_sub"],
+                                                 yhat=self.rq, lik=self.lik, log2sum=self.log2sum), "quantise + likelihood (sweep)")   # :625-629
         P.call(replicate, "supports per level")
         heads_l = {id(st): (dst, False) for st, (_, dst) in zip(stacks, reps)}
         yb_l, mt_l = reps[ns][1], reps[ns + 1][1]
@@ -1503,7 +1532,9 @@ class _DecPlan:
     kernel's K order is canonical, so mu / sigma / masks / indexes are bit-identical to the
     encoder's although the launches are grouped differently."""
 
-    def __init__(self, m: VarianceMaskingPIC, B, hz, wz, base_only, rem_idx, device):
+    def __init__(self, m: VarianceMaskingPIC, B, hz, wz, base_only, rem_idx, device, prog_chain: bool = False):
+        """``prog_chain``: stop after the base slices (hyper-synthesis of both halves and every stack head included) and
+        keep g_s[0] on y_hat_base in ``p_syn``; _ProgDecPlan lowers the progressive part itself."""
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
         self.device = torch.device(device)
         self.pr = 0.0
@@ -1545,7 +1576,8 @@ class _DecPlan:
                            [dict(act=L.ACT_HALF_TANH, post=sl(yq, i))], heads=heads)
             self.p_base.append((Pa, Pb))
         self.p_syn = E.Plan(device)
-        if base_only:
+        self.heads, self.yb = heads, yb
+        if base_only or prog_chain:
             E.lower_g_s(self.p_syn, [m.g_s[0] if m.multiple_decoder else m.g_s], [yb], [self.x_hat])
             return
         # ---- progressive slices
@@ -1594,6 +1626,20 @@ class _DecPlan:
             out[b] = dec.reshape(C, h, w).transpose(1, 2, 0)
         sym_view.buf[..., sym_view.c0:sym_view.c0 + C].copy_(torch.from_numpy(out).to(self.device))
 
+    def _decode_base(self, y_strings, z_strings, tg, te):
+        """z (host decode) -> hyper-synthesis -> base slices, each slice's symbols decoded on the host; on self.stream."""
+        from . import bitstream as bs
+        m, C = self.m, self.m.dim_chunk
+        zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
+        zs = np.stack([bs.decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
+                       for b in range(self.B)])
+        self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
+        self.p_hyper.run()
+        for i, (Pa, Pb) in enumerate(self.p_base):
+            Pa.run()
+            self._decode_slice(y_strings[i], self.idx_b.window(i * C, C), self.sym_b.window(i * C, C), tg, C)
+            Pb.run()
+
     def decode(self, strings, pr, checkpoint_rep):
         from . import bitstream as bs
         m = self.m
@@ -1612,15 +1658,7 @@ class _DecPlan:
             if checkpoint_rep is not None:
                 ck = ops.from_nchw(checkpoint_rep.to(self.device))
                 self.ck.buf.copy_(ck.buf[..., ck.c0:ck.c0 + ck.C])
-            zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
-            zs = np.stack([bs.decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
-                           for b in range(self.B)])
-            self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
-            self.p_hyper.run()
-            for i, (Pa, Pb) in enumerate(self.p_base):
-                Pa.run()
-                self._decode_slice(y_strings[i], self.idx_b.window(i * C, C), self.sym_b.window(i * C, C), tg, C)
-                Pb.run()
+            self._decode_base(y_strings, z_strings, tg, te)
             if not self.base_only:
                 for j, (Pa, Pb) in enumerate(self.p_prog):
                     Pa.run()
@@ -1629,6 +1667,80 @@ class _DecPlan:
             self.p_syn.run()
         cur.wait_stream(self.stream)
         return self.x_hat.clone()
+
+
+class _ProgDecPlan(_DecPlan):
+    """progressive.ProgressiveDecoder for one (B, z-shape, quality list) (all_scalable): _DecPlan's z,
+    hyper-synthesis and base slices with their host round trips, then the progressive (mu, sigma) chain with no mask and
+    no host round trip — with all_scalable it reads only y_hat_base and its own history (pic.py:586-612) —, the container
+    layer id of every element (vam_variance_layers on the chain's sigma) and the unmasked table indexes
+    (src/test/utils.py:35-54, functions_decode.py:186-203).  ``sweep_parts`` feeds _SweepTail in decode mode: level g is
+    the decoded symbols of the layers <= ks[g], + mu, then the LRP stacks and g_s[1]; ``p_syn`` is level 0 (g_s[0])."""
+
+    def __init__(self, m: VarianceMaskingPIC, B, hz, wz, q_list, device):
+        super().__init__(m, B, hz, wz, False, None, device, prog_chain=True)
+        h, w, d, C, ns = self.h, self.w, m.division_dimension[0], m.dim_chunk, m.ns0
+        sl = lambda v, i, n=1: v.window(i * C, n * C)
+        self.q_list = tuple(float(q) for q in q_list)
+        nv = lambda: ops.new_view(B, h, w, d, device)
+        mu_p, std_p = nv(), nv()
+        mu_tot = nv() if m.total_mu_rep else mu_p                                    # pic.py:601
+        yb, heads, sp = self.yb, self.heads, m.support_progressive_slices
+        P = self.p_chain = E.Plan(device)
+        for j in range(ns):                                                           # pic.py:586-612 with all_scalable
+            s_ = min(sp, j)
+            ms = [sl(yb, j)] + ([sl(mu_tot, j - s_, s_)] if s_ else [])
+            ss = [sl(yb, j)] + ([sl(std_p, j - s_, s_)] if s_ else [])
+            E.lower_stacks(P, [m.cc_mean_transforms_prog[j], m.cc_scale_transforms_prog[j]], [ms, ss], [sl(mu_p, j), sl(std_p, j)],
+                           heads=heads)
+            if m.total_mu_rep:
+                P.call(lambda j=j: ops.add(sl(mu_p, j), sl(yb, j), sl(mu_tot, j)))
+        self.layer = torch.empty((B, h, w, d), dtype=torch.uint8, device=device)
+        self.idx_l, self.sym = ops.new_iview(B, h, w, d, device), ops.new_iview(B, h, w, d, device)
+        P.keep += [mu_p.buf, std_p.buf, mu_tot.buf, self.layer, self.idx_l.buf, self.sym.buf]
+        table = m.gaussian_conditional.scale_table
+        P.call(lambda: ops.variance_layers(std_p, self.q_list, self.layer, n_slice=ns), "container layers")
+        P.call(lambda: ops.build_indexes(std_p, table, out=self.idx_l))                # functions_decode.py:179-180
+        self.sweep_parts = dict(heads=heads, yb=yb, mu=mu_p, std=std_p, mu_tot=mu_tot, sym=self.sym, layer=self.layer,
+                                g_s=m.g_s[1] if m.multiple_decoder else m.g_s)
+        self.tails: Dict[int, _SweepTail] = {}
+        self.graphs: Dict[tuple, ops.Graph] = {}
+        self.owner = None                   # the ProgressiveDecoder whose base and chain the buffers hold
+
+    def _stream(self):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+        return self.stream
+
+    def front(self, y_strings, z_strings):
+        """Base slices (host round trips) and the progressive chain, layer ids and indexes of every image."""
+        from . import bitstream as bs
+        ops.drain_graveyard()
+        tg, te = bs.Tables.of(self.m.gaussian_conditional), bs.Tables.of(self.m.entropy_bottleneck)
+        cur = torch.cuda.current_stream(self.device)
+        self._stream().wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self._decode_base(y_strings, z_strings, tg, te)
+            self.p_chain.run()
+        cur.wait_stream(self.stream)
+
+    def base(self, use_graph: bool):
+        _launch(self.p_syn, self.graphs, ("base",), self._stream(), use_graph)
+
+    def tail(self, ks: Sequence[int], use_graph: bool) -> _SweepTail:
+        t = self.tails.get(len(ks))
+        if t is None:
+            t = self.tails[len(ks)] = _SweepTail(self, len(ks), decode=True)
+        t.ks = tuple(int(k) for k in ks)
+        _launch(t.plan, t.graphs, t.ks, self._stream(), use_graph)
+        return t
+
+    def close(self):
+        for g in self.graphs.values():
+            g.close()
+        self.graphs.clear()
+        for t in self.tails.values():
+            t.close()
 
 
 models = {"pic": VarianceMaskingPIC, "rem": VarianceMaskingPICREM}

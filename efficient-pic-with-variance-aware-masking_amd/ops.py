@@ -512,6 +512,24 @@ def variance_mask_levels(sigma: View, prs: Sequence[float], mask: View, n_slice:
                                               thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_mask_levels")
 
 
+def variance_layers(sigma: View, prs: Sequence[float], layer: torch.Tensor, n_slice: int = 1,
+                    thr: Optional[torch.Tensor] = None):
+    """Container layer of every element for the non-decreasing quality list ``prs`` (up to L.VAM_MAX_LAYER_LEVELS, one
+    launch): ``layer`` uint8 [B, H, W, sigma.C] gets the first k with ``variance_mask(sigma, prs[k])`` == 1 (L.LAYER_NONE if
+    none); ``thr`` [L, B * n_slice] the thresholds as :func:`variance_mask_levels` writes them."""
+    slice_C = sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
+    prs = [float(p_) for p_ in prs]
+    nl = len(prs)
+    hw = sigma.H * sigma.W
+    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= nl * sigma.B * n_slice)
+    arr = (C.c_double * max(nl, 1))(*prs)
+    L.check(L.load().vam_variance_layers(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, arr, nl,
+                                         layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
+                                         thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_layers")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""
@@ -565,6 +583,17 @@ def gauss_levels_eval(y: View, mu: View, sigma: View, mask: View, n_levels: int,
     L.check(L.load().vam_gauss_levels_eval(*p(y), *p(y2), *p(mu), *p(sigma), *lv(mask), *lv(yhat), *lv(lik), *lv(sym),
                                            log2sum.data_ptr() if log2sum is not None else None, y.H * y.W, n_levels,
                                            y.n_pix, y.C, stream_ptr()), "vam_gauss_levels_eval")
+
+
+def gauss_levels_decode(sym: "IView", layer: torch.Tensor, mu: View, ks: Sequence[int], yhat: View):
+    """Decoder side of :func:`gauss_levels_eval`: level l's quantised latents float(sym) * (layer <= ks[l]) + mu, written as
+    ``yhat``'s consecutive image blocks ([L * B, H, W, ld], level l = images l*B ..).  ``layer`` uint8 [B, H, W, mu.C]."""
+    B, nl = mu.B, len(ks)
+    assert yhat.buf.shape[0] == nl * B and tuple(yhat.buf.shape[1:3]) == (mu.H, mu.W) and yhat.C == mu.C == sym.C
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (B, mu.H, mu.W, mu.C)
+    arr = (C.c_int * max(nl, 1))(*[int(k) for k in ks])
+    L.check(L.load().vam_gauss_levels_decode(sym.ptr, sym.ld, layer.data_ptr(), mu.C, mu.ptr, mu.ld, arr, nl, yhat.ptr, yhat.ld,
+                                             B * mu.H * mu.W * yhat.ld, mu.n_pix, mu.C, stream_ptr()), "vam_gauss_levels_decode")
 
 
 def build_indexes(sigma: View, table: torch.Tensor, mask: Optional[View] = None, out: Optional[IView] = None) -> torch.Tensor:

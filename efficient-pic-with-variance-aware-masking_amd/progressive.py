@@ -11,13 +11,19 @@ Model variants: like the reference's harness this one follows ``multiple_encoder
 ``multiple_decoder`` (functions_decode.py:107,224), ``multiple_hyperprior`` (test/utils.py:20-31) and any
 ``support_progressive_slices``; and like it, it is defined for ``delta_encode=True`` (functions_encode.py:113-114
 names the residual only there) and ``all_scalable=True`` (the parameter chain of test/utils.py:35-54 never sees a mask).
+
+:func:`encode_batch` and :class:`ProgressiveDecoder` write and read the same container for a batch of images on the fused
+plans: with all_scalable the layers differ only in which elements they carry, so one front end and one
+set of symbols serve every layer, and a decoded level equals ``forward_single_quality(x, q_k)`` bit for bit.
 """
 from __future__ import annotations
 
+import math
 import os
 import pickle
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 Q_LIST = [0.002, 0.05, 0.5, 0.75, 1, 1.5, 2, 2.5, 3, 4, 5, 5.5, 6, 6.6]     # functions_encode.py:11
@@ -186,3 +192,191 @@ def decode(model, bitstreams, q_ind=0, res_base=None, index_hat_slice=None, mean
         x_hat = _synthesis(model, 1)(y_prog)
     return {"x_hat": x_hat, "z_data": z_data, "entropy_data": entropy_data, "y_hat_base": y_hat_base, "y_prog": y_prog,
             "res_base": res_base}
+
+
+# ---------------------------------------------------------------- batched container on the fused plans
+_EAGER = "the eager harness (progressive.encode / progressive.decode)"
+
+
+def check_q_list(q_list: Sequence[float]) -> List[float]:
+    """A container's quality list: 1..VAM_MAX_LAYER_LEVELS qualities >= 0, non-decreasing (the variance masks are then
+    nested, so each element belongs to exactly one layer)."""
+    from . import _lib as L
+    qs = [float(q) for q in q_list]
+    if not 1 <= len(qs) <= L.VAM_MAX_LAYER_LEVELS:
+        raise ValueError(f"q_list: 1..{L.VAM_MAX_LAYER_LEVELS} qualities, got {len(qs)}")
+    if any(not (q >= 0.0) or math.isinf(q) for q in qs):
+        raise ValueError(f"q_list: qualities must be finite and >= 0, got {qs}")
+    if any(b < a for a, b in zip(qs, qs[1:])):
+        raise ValueError(f"q_list must be non-decreasing (each layer adds the elements of the next quality), got {qs}")
+    return qs
+
+
+def container_bits(c) -> list:
+    """[bits_z, bits_base, bits_per_layer] of one image's container (what :func:`encode` returns beside it)."""
+    return [8.0 * sum(len(s) for s in c["z"]), 8.0 * sum(len(s[0]) for s in c["base"]),
+            [8.0 * sum(len(s) for s in layer) for layer in c["progressive"]]]
+
+
+def bits_up_to(c, k: int) -> float:
+    """Bits a decoder reads for level k of container c: z, the base and layers 1..k (level 0 = the base)."""
+    if not 0 <= k <= len(c["progressive"]):
+        raise ValueError(f"level {k} outside 0..{len(c['progressive'])}")
+    bz, bb, bl = container_bits(c)
+    return bz + bb + sum(bl[:k])
+
+
+def _check_batched(model):
+    """What the plan-backed container needs beyond the eager one (_check_variant)."""
+    from . import ops
+    from .models import VarianceMaskingPICREM
+    if isinstance(model, VarianceMaskingPICREM):
+        raise NotImplementedError("batched progressive containers: REM models refine sigma with the checkpoints, so the layers "
+                                  f"depend on them; use {_EAGER} with rems=True")
+    if not (model.delta_encode and getattr(model, "all_scalable", True)):
+        raise NotImplementedError("batched progressive containers are defined for delta_encode=True and all_scalable=True, as "
+                                  f"the container itself (src/test/functions_encode.py:113-114); {_EAGER} refuses them too")
+    if getattr(model, "storage", "fp32") != "fp32" or ops.f16x2_mode():
+        raise NotImplementedError("batched progressive containers run in fp32 storage and the default bf16x3 arithmetic "
+                                  "(encoder and decoder must agree bit for bit): not with bf16 storage or VAMPIC_CONV=f16x2; "
+                                  f"use {_EAGER}")
+
+
+def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
+    """:func:`encode` for a batch x [B,3,H,W] (H, W multiples of 64, as for ``compress``) on the fused plans: the
+    ``compress(x, 10)`` plan (symbols round(r - mu), unmasked indexes), then vam_variance_layers on its sigma assigns every
+    element its layer.  The symbols, indexes, layer ids and z symbols go to the host once; z, the base slices and the
+    layers are coded by the threaded stream coder.  Returns (containers, bits): per image the container of :func:`encode`
+    and [bits_z, bits_base, bits_per_layer]."""
+    from . import _lib as L
+    from . import bitstream as bs
+    from . import ops
+    _check_variant(model)
+    _check_batched(model)
+    qs = check_q_list(q_list)
+    m = model
+    B, _, H, W = x.shape
+    d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
+    with torch.no_grad():
+        L.require_gpu()
+        m._check_config()
+        plan = m._plan(x, base_only=False, symbols=True)
+        if plan.idx is None:
+            raise ValueError("empty scale table: call model.update() before encode_batch()")
+        plan.execute(x, 10.0, None, m.use_graph, False)
+        layer = torch.empty((B, H // 16, W // 16, d), dtype=torch.uint8, device=x.device)
+        ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)              # functions_encode.py:168-196's delta masks
+        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        sym, idx, lay, zs = nchw(plan.sym.buf), nchw(plan.idx.buf), nchw(layer), nchw(plan.z_sym.buf)
+    tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
+    zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
+    z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te)
+    sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
+    jobs = [(sl(sym, b, i), sl(idx, b, i)) for i in range(ns) for b in range(B)]
+    jobs += [(sl(sym, b, ns + j), sl(idx, b, ns + j), sl(lay, b, j), k) for k in range(len(qs)) for j in range(ns) for b in range(B)]
+    y_str = bs.encode_streams(jobs, tg)
+    base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
+    prog = [[y_str[(ns + k * ns + j) * B:(ns + k * ns + j + 1) * B] for j in range(ns)] for k in range(len(qs))]
+    containers, bits = [], []
+    for b in range(B):
+        c = {"q_list": list(q_list), "shape": (H // 64, W // 64), "z": [z_str[b]], "base": [[base[i][b]] for i in range(ns)],
+             "progressive": [[prog[k][j][b] for j in range(ns)] for k in range(len(qs))]}
+        containers.append(c)
+        bits.append(container_bits(c))
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+        for b, c in enumerate(containers):
+            with open(os.path.join(save_path, "bits.pkl" if B == 1 else f"bits_{b}.pkl"), "wb") as f:
+                pickle.dump(c, f)
+    return containers, bits
+
+
+class ProgressiveDecoder:
+    """Decodes the levels of a batch of containers (all of one shape and quality list) on the fused plans.  Level 0 is
+    the base, level k (1 <= k <= len(q_list)) quality q_list[k-1]; each equals ``forward_single_quality(x, q)`` bit for bit.
+    The base slices and the progressive (mu, sigma) chain run once; a layer's streams are entropy-decoded only the first
+    time a level needs them (:attr:`layers_decoded`)."""
+
+    def __init__(self, model, containers):
+        _check_variant(model)
+        _check_batched(model)
+        cs = list(containers)
+        if not cs:
+            raise ValueError("ProgressiveDecoder: no containers")
+        shape, q0 = tuple(cs[0]["shape"]), [float(q) for q in cs[0]["q_list"]]
+        for c in cs[1:]:
+            if tuple(c["shape"]) != shape or [float(q) for q in c["q_list"]] != q0:
+                raise ValueError("ProgressiveDecoder: every container must have the same shape and q_list, got "
+                                 f"{shape} / {q0} and {tuple(c['shape'])} / {list(c['q_list'])}; decode them separately")
+        self.q_list = check_q_list(q0)
+        self.m, self.containers, self.B = model, cs, len(cs)
+        from . import _lib as L
+        from .models import sweep_groups
+        L.require_gpu()
+        model._check_config()
+        hz, wz = int(shape[0]), int(shape[1])
+        self.H, self.W = 64 * hz, 64 * wz
+        if len(sweep_groups(1, self.B, self.H, self.W)) > 1:
+            raise NotImplementedError(f"ProgressiveDecoder: {self.B} images of {self.H}x{self.W} exceed one plan; decode "
+                                      "the containers in smaller batches")
+        self.dp = model._prog_dec_plan(self.B, hz, wz, self.q_list)
+        d, ns, C = model.division_dimension[0], model.ns0, model.dim_chunk
+        self._front()
+        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        self.idx, self.layer = nchw(self.dp.idx_l.buf), nchw(self.dp.layer)
+        self.sym = np.zeros(self.idx.shape, dtype=np.int32)          # [B, d, h, w]: the layers decoded so far
+        self.layers_decoded = 0
+
+    def _front(self):
+        cs, ns = self.containers, self.m.ns0
+        self.dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
+        self.dp.owner = self
+
+    def _need(self, k: int):
+        """Entropy-decode layers up to k and hand the symbols to the plans."""
+        from . import bitstream as bs
+        if not 0 <= k <= len(self.q_list):
+            raise ValueError(f"level {k} outside 0..{len(self.q_list)}")
+        if self.dp.owner is not self:                    # another decoder ran on the same plans since
+            self._front()
+        C, ns = self.m.dim_chunk, self.m.ns0
+        if k > self.layers_decoded:
+            sl = lambda a, b, j: a[b, j * C:(j + 1) * C]
+            jobs = [(c["progressive"][kk][j], sl(self.idx, b, j), sl(self.sym, b, j), sl(self.layer, b, j), kk)
+                    for kk in range(self.layers_decoded, k) for j in range(ns) for b, c in enumerate(self.containers)]
+            bs.decode_streams(jobs, bs.Tables.of(self.m.gaussian_conditional))
+            self.layers_decoded = k
+        self.dp.sym.buf.copy_(torch.from_numpy(self.sym).to(self.dp.device).permute(0, 2, 3, 1))
+
+    def decode_levels(self, ks: Sequence[int]) -> List[dict]:
+        """{"x_hat", "y_hat"} of the batch for every level of ``ks``, the levels > 0 through the batched tail."""
+        from .models import sweep_groups
+        ks = [int(k) for k in ks]
+        if not ks or min(ks) < 0:
+            raise ValueError(f"levels must be >= 0, got {ks}")
+        with torch.no_grad():
+            self._need(max(ks))
+            out: List[Optional[dict]] = [None] * len(ks)
+            dp, use_graph = self.dp, self.m.use_graph
+            if 0 in ks:
+                dp.base(use_graph)
+                for g, k in enumerate(ks):
+                    if k == 0:
+                        out[g] = {"x_hat": dp.x_hat.clone(), "y_hat": dp.yb.torch_nchw().clone()}
+            lv = [g for g, k in enumerate(ks) if k > 0]
+            for _, _, groups in sweep_groups(len(lv), self.B, self.H, self.W):
+                for l0, l1 in groups:
+                    gs = lv[l0:l1]
+                    t = dp.tail([ks[g] - 1 for g in gs], use_graph)         # level k keeps the layers 0..k-1
+                    for i, g in enumerate(gs):
+                        out[g] = {"x_hat": t.x_hat[i * self.B:(i + 1) * self.B].clone(),
+                                  "y_hat": t.level(t.y_prog, i).torch_nchw().clone()}
+        return out
+
+    def decode(self, k: int) -> dict:
+        """{"x_hat", "y_hat"} of level k for the batch (0 = base, k = quality q_list[k-1])."""
+        return self.decode_levels([k])[0]
+
+    def bits(self, k: int) -> List[float]:
+        """Each image's bits up to level k."""
+        return [bits_up_to(c, k) for c in self.containers]

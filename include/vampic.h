@@ -272,6 +272,17 @@ int vam_variance_mask_levels(const float* sigma, int ld, long batch_stride, long
                              int n_batch, int n_slice, int n_pix, int C, const double* prs, int n_levels,
                              float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
                              long mask_level_stride, float* thr_out, void* stream);
+/* Progressive container layers (progressive.encode_batch / ProgressiveDecoder): for a non-decreasing list of
+ * n_levels <= VAM_MAX_LAYER_LEVELS qualities, layer_out[e] = the first k with vam_variance_mask(sigma, prs[k])[e] == 1,
+ * 0xFF when there is none, so that  layer[e] <= k  <=>  mask_k[e] == 1  (the masks are nested in q).  One uint8 per
+ * element in the layout of vam_variance_mask's mask (pixel stride ld_layer, strides in elements); level k's thresholds
+ * at thr_out[k*n_batch*n_slice + s] as vam_variance_mask_levels writes them.  One launch: each segment is loaded once,
+ * the thresholds are selected level by level with vam_variance_mask_levels' code, and the layer ids are assigned in one
+ * pass over the segment. */
+#define VAM_MAX_LAYER_LEVELS 32
+int vam_variance_layers(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice,
+                        int n_pix, int C, const double* prs, int n_levels, uint8_t* layer_out, int ld_layer,
+                        long layer_batch_stride, long layer_slice_stride, float* thr_out, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
@@ -302,6 +313,13 @@ int vam_gauss_levels_eval(const float* y, int ld_y, const float* y2, int ld_y2, 
                           float* yhat, int ld_yhat, long yhat_ls, float* lik, int ld_lik, long lik_ls,
                           int32_t* sym, int ld_sym, long sym_ls, double* log2sum, int pix_per_item, int n_levels,
                           long n_pix, int C, void* stream);
+/* The decoder's counterpart (ProgressiveDecoder): from the int32 symbols decoded so far and the layer ids of
+ * vam_variance_layers, level l's quantised latents yhat_l = float(sym) * m_l + mu with m_l = (layer <= k_l), through
+ * masked_tail's expression; k_l = ks[l] (n_levels <= VAM_MAX_MASK_LEVELS cut-offs).  yhat_l lives at yhat + l * yhat_ls,
+ * the eval kernel's layout.  Fed the q = 10 symbols round(r - mu), bit-identical to vam_gauss_levels_eval's yhat. */
+int vam_gauss_levels_decode(const int32_t* sym, int ld_sym, const uint8_t* layer, int ld_layer, const float* mu, int ld_mu,
+                            const int* ks, int n_levels, float* yhat, int ld_yhat, long yhat_ls, long n_pix, int C,
+                            void* stream);
 
 /* GaussianConditional.build_indexes (entropy_models.py:654-659): idx = 63 - #{i<63: max(s,.11) <= T_i}
  * table: 64 floats (device). mask (may be NULL) multiplies sigma first (pic.py:809). */
@@ -518,6 +536,29 @@ long vam_rans_encode(const int32_t* symbols_host, const int32_t* indexes_host, l
 int vam_rans_decode(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n,
                     const int32_t* cdfs_host, int cdf_stride, const int32_t* cdf_sizes_host,
                     const int32_t* offsets_host, int n_cdfs, int32_t* symbols_out_host);
+/* Many independent streams in one call (progressive containers: z, the base slices and every layer of a batch of
+ * images), coded on min(n_threads, VAM_RANS_MAX_THREADS, n_streams) host threads.  Each stream's bytes equal
+ * vam_rans_encode's on the same inputs, whatever the thread count.  layer != NULL selects one container layer: element i
+ * is coded as symbol 0 with table 0 unless layer[i] == sel (the reference's r_sym * delta, idx * delta), and decoding
+ * writes symbols_out[i] only where layer[i] == sel, so the layers of a container fill one symbol array.  On error the
+ * first failing stream (lowest index) is reported. */
+#define VAM_RANS_MAX_THREADS 16
+typedef struct vam_rans_stream {
+  const int32_t* symbols;     /* encode: n symbols */
+  int32_t* symbols_out;       /* decode: n symbols */
+  const int32_t* indexes;     /* n table indexes */
+  const uint8_t* layer;       /* NULL, or n layer ids (0xFF = in no layer) */
+  long n;
+  int sel;                    /* the layer this stream carries */
+  int pad_;
+  uint8_t* bytes;             /* encode: output buffer of `capacity` bytes; decode: the stream */
+  long capacity;
+  long n_bytes;               /* encode: bytes written (set by the call); decode: stream length */
+} vam_rans_stream;
+int vam_rans_encode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
+                            const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int n_threads);
+int vam_rans_decode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
+                            const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int n_threads);
 
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
