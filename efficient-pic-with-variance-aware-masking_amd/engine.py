@@ -2,7 +2,7 @@
 
 A :class:`Plan` owns every NHWC buffer it needs (allocated while the plan is built,
 never while it runs) and a flat list of pre-marshalled C-ABI calls.  ``run()`` replays
-them on the current HIP stream; ``graph()`` captures the replay once into a hipGraph so
+them on the current HIP stream; a :class:`Runner` captures the replay once into a hipGraph so
 a steady-state step is a single ``hipGraphLaunch``.
 
 Lowering rules (reference lines in brackets)
@@ -35,7 +35,6 @@ class Plan:
         self.device = torch.device(device)
         self.steps: List[Callable[[], None]] = []
         self.keep: List[object] = []          # buffers / ctypes arrays referenced by the steps
-        self._graph: Optional[ops.Graph] = None
         self.flops = 0.0
         self.meta: List[dict] = []            # one entry per step: what it is and its algorithmic FLOP
         self.branch_of: List[int] = []        # stream branch of each step (0 = the caller's stream)
@@ -418,14 +417,86 @@ class Plan:
         finally:
             torch.cuda.set_stream(main)
 
-    def graph_run(self):
-        if self._graph is None:
-            self.run()                       # warm every kernel (lazy code-object load) before capture
-            torch.cuda.current_stream().synchronize()
-            g = ops.Graph()
-            g.capture(self.run)
-            self._graph = g
-        self._graph.launch()
+
+class Runner:
+    """How every plan executes: on a private HIP stream (hipGraph capture is not allowed on the legacy default stream),
+    ordered after and before the caller's stream, replaying the hipGraphs it keeps per key.
+
+    ``cap``: when a new capture finds more than ``cap`` graphs kept, all of them are closed (ops.Graph.close: retired at
+    the next drain); None keeps every graph.  A runner that never enters :meth:`on_stream` only keeps graphs, replayed on
+    whichever runner's stream is current (the tails of a sweep count their own graphs against their own cap)."""
+
+    def __init__(self, device, cap: Optional[int] = None):
+        self.device = torch.device(device)
+        self.cap = cap
+        self.stream: Optional["torch.cuda.Stream"] = None
+        self.graphs: Dict[object, List[ops.Graph]] = {}
+        self._ptr_sig: Optional[tuple] = None
+
+    @contextlib.contextmanager
+    def on_stream(self):
+        """The body runs on the private stream, which first waits for the caller's stream; the caller's stream then
+        waits for it.  Dropped graphs are drained here, outside any capture."""
+        ops.drain_graveyard()
+        cur = torch.cuda.current_stream(self.device)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            yield self.stream
+        cur.wait_stream(self.stream)
+
+    def replay(self, key, fn: Callable[[], None], use_graph: bool):
+        """``fn`` on the current stream; with ``use_graph`` the graph of ``key``, captured at its first use."""
+        if use_graph:
+            self._captured(key, fn, [fn])[0].launch()
+        else:
+            fn()
+
+    def replay_segments(self, key, run_range: Callable[[int, int], None], cuts: Sequence[int], use_graph: bool,
+                        after: Callable[[int], None]):
+        """``run_range(a, b)`` over the segments [cuts[k], cuts[k+1]) in order, ``after(b)`` behind each one; with
+        ``use_graph`` one graph per segment.  The warm-up before the captures runs the WHOLE range once: later segments
+        accumulate into buffers that only the first one clears, so one warm-up per segment would accumulate twice."""
+        segs = list(zip(cuts[:-1], cuts[1:]))
+        graphs = self._captured(key, lambda: run_range(cuts[0], cuts[-1]),
+                                [lambda a=a, b=b: run_range(a, b) for a, b in segs]) if use_graph else None
+        for k, (a, b) in enumerate(segs):
+            if use_graph:
+                graphs[k].launch()
+            else:
+                run_range(a, b)
+            after(b)
+
+    def _captured(self, key, warm: Callable[[], None], parts: Sequence[Callable[[], None]]) -> List[ops.Graph]:
+        graphs = self.graphs.get(key)
+        if graphs is None:
+            warm()                                   # every code object loaded before the capture
+            torch.cuda.current_stream(self.device).synchronize()
+            graphs = []
+            for fn in parts:
+                g = ops.Graph()
+                g.capture(fn)
+                graphs.append(g)
+            if self.cap is not None and len(self.graphs) > self.cap:
+                self.close()
+            self.graphs[key] = graphs
+        return graphs
+
+    def stale(self, params: Sequence[torch.Tensor]) -> bool:
+        """True when the storage of a trained parameter moved since the last call: the captured pointers are stale and
+        the caller closes every graph of the plan."""
+        sig = tuple(p.data_ptr() for p in params)
+        moved = self._ptr_sig is not None and self._ptr_sig != sig
+        self._ptr_sig = sig
+        return moved
+
+    def close(self):
+        """Give up every graph (ops.Graph.close: retired at the next drain)."""
+        for graphs in self.graphs.values():
+            for g in graphs:
+                g.close()
+        self.graphs.clear()
 
 
 # =============================================================================

@@ -115,7 +115,10 @@ class FullTrainPlan:
     per-level tail (mask, quantisation, likelihood, LRP stacks, merge, g_s[1]) depends on the quality, and it runs
     batched along the image axis as L * B images (level k = images k*B .. (k+1)*B-1).  In the backward the level tail's
     gradients w.r.t. the shared (mu, sigma) and supports are summed over the levels — what the extra evaluations of the
-    same stacks at the same inputs contribute in the reference's graph."""
+    same stacks at the same inputs contribute in the reference's graph.
+
+    Both plans run on the private stream of one engine.Runner: a forward hipGraph per quality (tuple of qualities), a
+    list of segment graphs per tuple of bucket cuts for the backward."""
 
     def __init__(self, m, B: int, H: int, W: int, mode: str, base_only: bool, device, trainable_ids: Optional[set] = None,
                  n_levels: int = 1):
@@ -130,9 +133,7 @@ class FullTrainPlan:
         self.pr = 10.0
         self.prs = (10.0,) * NL
         self.generation = 0
-        self.stream = None
-        self.fwd_graphs: Dict[object, ops.Graph] = {}
-        self.bwd_graphs: Dict[tuple, List[ops.Graph]] = {}
+        self.runner = E.Runner(device)            # no cap: training graphs are never retired
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         h, w, d, ns, C = H // 16, W // 16, m.division_dimension[0], m.ns0, m.dim_chunk
@@ -649,16 +650,8 @@ class FullTrainPlan:
         self.t_gs1 = G.lower_g_s_train(P, gs_prog, self.y_prog, self.x_hat[1:].view(LB, 3, self.H, self.W), pk(gs_prog), clamp=clamp)
 
     # ------------------------------------------------------------------------------------------- execution
-    def _own_stream(self):
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.device)
-        return self.stream
-
     def close(self):
-        for g in list(self.fwd_graphs.values()) + [g for gs in self.bwd_graphs.values() for g in gs]:
-            g.close()
-        self.fwd_graphs.clear()
-        self.bwd_graphs.clear()
+        self.runner.close()
 
     def set_noise(self, noise=None):
         """noise = {"y": NCHW, "z": NCHW} or None (fresh U(-.5, .5) draws).  Levels: "y" holds the base block and one
@@ -684,29 +677,12 @@ class FullTrainPlan:
             self.pr = float(pr)
             gkey = self.pr
         self.generation += 1
-        sig = tuple(p.data_ptr() for p in self.params)
-        if getattr(self, "_ptr_sig", sig) != sig:          # parameter storage replaced: captured pointers are stale
+        if self.runner.stale(self.params):          # parameter storage replaced: captured pointers are stale
             self.close()
-        self._ptr_sig = sig
-        ops.drain_graveyard()
-        cur = torch.cuda.current_stream(self.device)
-        st = self._own_stream()
-        st.wait_stream(cur)
-        with torch.cuda.stream(st):
+        with self.runner.on_stream():
             self.x_in.copy_(x)
             self.set_noise(noise)
-            if use_graph:
-                g = self.fwd_graphs.get(gkey)
-                if g is None:
-                    self.plan.run()
-                    st.synchronize()
-                    g = ops.Graph()
-                    g.capture(self.plan.run)
-                    self.fwd_graphs[gkey] = g
-                g.launch()
-            else:
-                self.plan.run()
-        cur.wait_stream(st)
+            self.runner.replay(gkey, self.plan.run, use_graph)
         d = self.m.division_dimension[0]
         nchw = lambda v: v.torch_nchw().clone()
         out = {"x_hat": self.x_hat.clone(), "lik": nchw(self.lik), "z_lik": nchw(self.z_lik), "y_base": nchw(self.y_base),
@@ -720,10 +696,7 @@ class FullTrainPlan:
         """Run the backward plan for dL/dx_hat [n_rec,B,3,H,W], dL/dlik [B, n*d, h, w] (NCHW) and dL/dlik_z; returns the
         parameter gradients (views of the flat buffer, ``self.params`` order).  ``reducer`` (sharding.BucketReducer):
         called with (bucket index, flat slice, stream) as each bucket becomes final."""
-        cur = torch.cuda.current_stream(self.device)
-        st = self._own_stream()
-        st.wait_stream(cur)
-        with torch.cuda.stream(st):
+        with self.runner.on_stream() as st:
             if g_xhat is None:
                 self.g_xhat.zero_()
             else:
@@ -733,34 +706,17 @@ class FullTrainPlan:
                     buf.buf.zero_()
                 else:
                     buf.buf.copy_(g.permute(0, 2, 3, 1))
-            cuts = [0] + (list(self.bucket_ready) if reducer is not None else [len(self.bwd.steps)])
-            cuts = sorted(set(cuts))
-            key = tuple(cuts)
-            graphs = self.bwd_graphs.get(key) if use_graph else None
-            if use_graph and graphs is None:
-                self._run_bwd_segment(0, len(self.bwd.steps))                      # warm-up (code objects loaded before capture)
-                st.synchronize()
-                graphs = []
-                for a, b in zip(cuts[:-1], cuts[1:]):
-                    g = ops.Graph()
-                    g.capture(lambda a=a, b=b: self._run_bwd_segment(a, b))
-                    graphs.append(g)
-                self.bwd_graphs[key] = graphs
+            cuts = sorted(set([0] + (list(self.bucket_ready) if reducer is not None else [len(self.bwd.steps)])))
             nb = 0
-            for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
-                if use_graph:
-                    graphs[k].launch()
-                else:
-                    self._run_bwd_segment(a, b)
-                if reducer is not None:
-                    while nb < len(self.bucket_ready) and self.bucket_ready[nb] <= b:
-                        lo, hi = self.bucket_bounds[nb]
-                        reducer(nb, self.flat[lo:hi], st)
-                        nb += 1
+
+            def hand_out(b: int):                   # the buckets that are final once the steps before b have run
+                nonlocal nb
+                while reducer is not None and nb < len(self.bucket_ready) and self.bucket_ready[nb] <= b:
+                    lo, hi = self.bucket_bounds[nb]
+                    reducer(nb, self.flat[lo:hi], st)
+                    nb += 1
+            # (run_range joins the weight-gradient branch at the end: a segment ends where a bucket is final)
+            self.runner.replay_segments(("backward", tuple(cuts)), self.bwd.run_range, cuts, use_graph, hand_out)
             if reducer is not None:
                 reducer.finish(st)
-        cur.wait_stream(st)
         return self.views
-
-    def _run_bwd_segment(self, a: int, b: int):
-        self.bwd.run_range(a, b)        # (joins the weight-gradient branch at the end: a segment ends where a bucket is final)

@@ -208,9 +208,7 @@ class VarianceMaskingPIC(CompressionModel):
         whenever the garbage collector finds the plans' reference cycles) and destroyed at the next plan entry point,
         after their last replay has finished."""
         for p in list(self._plans.values()) + list(self._dec_plans.values()):
-            close = getattr(p, "close", None)
-            if close is not None:
-                close()
+            p.close()
         self._plans.clear()
         self._dec_plans.clear()
 
@@ -276,11 +274,30 @@ class VarianceMaskingPIC(CompressionModel):
         if self.support_progressive_slices < 0:
             raise ValueError("support_progressive_slices must be >= 0")
 
+    def _mask_policy(self, mask_pol):
+        """``mask_pol``, or the model's for None: the plans implement point-based-std and two-levels."""
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if mask_pol not in ("point-based-std", "two-levels"):
+            raise NotImplementedError()
+        return mask_pol
+
+    def _cached_plan(self, plans: dict, key, build, wsig=None, rem_idx: Optional[int] = None):
+        """The plan under ``key`` in ``plans``; ``build()`` makes it when there is none or the kept one is stale: built
+        under another ``wsig`` (a packed weight was edited in place: param.data.copy_, nn.init, optimizer step), or REM
+        ``rem_idx`` changed since the plan packed it (``rem_sig``).  None compares nothing.  A replaced plan is closed."""
+        p = plans.get(key)
+        if p is not None and ((wsig is not None and p.wsig != wsig) or
+                              (rem_idx is not None and p.rem_sig != _version_sig(self.post_latent[rem_idx]))):
+            plans.pop(key).close()
+            p = None
+        if p is None:
+            p = plans[key] = build()
+            p.wsig = wsig
+        return p
+
     def _plan(self, x, base_only: bool, rem_idx: Optional[int] = None, symbols: bool = False,
               train: bool = False, own_ck: bool = False, train_gs: bool = False, train_lrp: bool = False) -> "_FsqPlan":
-        B, C_, H, W = x.shape
-        if C_ != 3 or H % 64 or W % 64:
-            raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
+        B, H, W = _check_input(x)
         key = (B, H, W, base_only, rem_idx, str(x.device)) + ((True,) if symbols else ()) + (("train",) if train else ()) + \
             (("own_ck",) if own_ck else ()) + (("train_gs",) if train_gs else ()) + (("train_lrp",) if train_lrp else ()) + \
             (("bf16",) if getattr(self, "storage", "fp32") == "bf16" else ())
@@ -288,23 +305,13 @@ class VarianceMaskingPIC(CompressionModel):
             raise NotImplementedError("bf16 storage is an inference configuration (forward_single_quality): training and "
                                       "the bitstream path run in fp32")
         if ops.f16x2_mode() and (train or symbols):
-            raise NotImplementedError("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-forward configuration: its results depend, in the last bits, on the power-of-two scale of each launch (batch composition, plan structure), so the bitstream path (encoder and decoder must agree bit for bit) and training run in the default bf16x3 arithmetic")
-        p = self._plans.get(key)
-        if p is not None and rem_idx is not None and not train and p.rem_sig != _version_sig(self.post_latent[rem_idx]):
-            p = None                # the REM was fine-tuned since this plan packed its weights
+            raise NotImplementedError(F16X2_REFUSAL)
+        # training plans re-pack what they train every step: wsig leaves those modules out, a training REM plan its REM
         trained = ([self._decoder_in_use(base_only)] if train_gs else []) + ([self.lrp_transforms_prog] if train_lrp else [])
-        wsig = self._weights_sig(trained)
-        if p is not None and p.wsig != wsig:
-            p = None                # a parameter was edited in place (param.data.copy_, nn.init, optimizer step)
-        if p is None:
-            old = self._plans.pop(key, None)
-            if old is not None:
-                old.close()
-            p = _FsqPlan(self, B, H, W, base_only, rem_idx, x.device, symbols=symbols, train=train, own_ck=own_ck,
-                         train_gs=train_gs, train_lrp=train_lrp)
-            p.wsig = wsig
-            self._plans[key] = p
-        return p
+        return self._cached_plan(self._plans, key,
+                                 lambda: _FsqPlan(self, B, H, W, base_only, rem_idx, x.device, symbols=symbols, train=train,
+                                                  own_ck=own_ck, train_gs=train_gs, train_lrp=train_lrp),
+                                 self._weights_sig(trained), None if train else rem_idx)
 
     def _decoder_in_use(self, base_only: bool):
         return (self.g_s[0 if base_only else 1] if self.multiple_decoder else self.g_s)
@@ -350,15 +357,11 @@ class VarianceMaskingPIC(CompressionModel):
                 # train.py:219-222): the complete training plan (full_train.py)
                 return self._forward_full_train(x, [quality], mask_pol, noise, single=True)
             train_gs, train_lrp = True, bool(n_lrp)
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
-        pr = quality
-        if mask_pol == "two-levels" and quality != 0:
-            pr = 10                                   # channel_mask.py:152-153: all ones unless pr == 0
+        pr = _mask_quality(mask_pol, quality)
         nb = _max_images_per_plan(x)
         if train_gs and x.shape[0] > nb:                # one tape per plan: sub-batches would overwrite each other's
             raise NotImplementedError(f"training with gradients: at most {nb} images of {x.shape[2]}x{x.shape[3]} per step "
@@ -383,35 +386,21 @@ class VarianceMaskingPIC(CompressionModel):
                 and not ops.f16x2_mode())
 
     def _sweep_plan(self, x) -> "_SweepPlan":
-        B, C_, H, W = x.shape
-        if C_ != 3 or H % 64 or W % 64:
-            raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
-        key = ("sweep", B, H, W, str(x.device))
-        wsig = self._weights_sig()
-        p = self._plans.get(key)
-        if p is not None and p.wsig != wsig:            # a parameter was edited in place since the plan packed it
-            self._plans.pop(key).close()
-            p = None
-        if p is None:
-            p = _SweepPlan(self, B, H, W, x.device)
-            p.wsig = wsig
-            self._plans[key] = p
-        return p
+        B, H, W = _check_input(x)
+        return self._cached_plan(self._plans, ("sweep", B, H, W, str(x.device)), lambda: _SweepPlan(self, B, H, W, x.device),
+                                 self._weights_sig())
 
     def _sweep(self, x, qualities, mask_pol, emit):
         """Run the sweep over ``qualities`` and hand each result to ``emit(i0, i1, sweep_plan, tail, ks)`` while its buffers
         hold it (the next group overwrites them): images i0..i1 of x; ``tail`` None = the base reconstruction (the entries
         ks of ``qualities`` equal to 0), else a _SweepTail whose level g is quality ``qualities[ks[g]]``.  ``emit`` runs on
         the caller's stream, ordered after the group and before the next one."""
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
         lv = [k for k, q in enumerate(qualities) if q != 0]
         zeros = [k for k, q in enumerate(qualities) if q == 0]
-        mpr = lambda q: 10 if (mask_pol == "two-levels" and q != 0) else q   # channel_mask.py:152-153
         B, _, H, W = x.shape
         for i0, i1, groups in sweep_groups(len(lv), B, H, W):
             xb = x[i0:i1].detach()
@@ -422,7 +411,7 @@ class VarianceMaskingPIC(CompressionModel):
                 emit(i0, i1, sw, None, zeros)
             for l0, l1 in groups:
                 ks = lv[l0:l1]
-                t = sw.tail([float(mpr(qualities[k])) for k in ks], self.use_graph)
+                t = sw.tail([float(_mask_quality(mask_pol, qualities[k])) for k in ks], self.use_graph)
                 emit(i0, i1, sw, t, ks)
 
     def forward_qualities(self, x, qualities, mask_pol=None):
@@ -497,10 +486,8 @@ class VarianceMaskingPIC(CompressionModel):
         ``single`` = False: ``forward(x, [0, q])`` (pic.py:301-491); True: ``forward_single_quality(x, q)`` (:497-666)."""
         from .full_train import FullTrainPlan
         if ops.f16x2_mode():
-            raise NotImplementedError("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-forward configuration: its results depend, in the last bits, on the power-of-two scale of each launch (batch composition, plan structure), so the bitstream path (encoder and decoder must agree bit for bit) and training run in the default bf16x3 arithmetic")
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+            raise NotImplementedError(F16X2_REFUSAL)
+        mask_pol = self._mask_policy(mask_pol)
         n_lv = 0 if single else len(qs) - 1
         if not single and (n_lv < 1 or qs[0] != 0 or any(not q_ > 0 for q_ in qs[1:])):
             raise NotImplementedError("training forward with gradients: quality lists [0, q1, ..., qL] with every q_k > 0 "
@@ -521,18 +508,14 @@ class VarianceMaskingPIC(CompressionModel):
         if n_lv > 1 and n_lv * x.shape[0] > nb:
             raise NotImplementedError(f"training with gradients over {n_lv} quality levels: the level tail runs as levels x images "
                                       f"= {n_lv * x.shape[0]} images of {x.shape[2]}x{x.shape[3]} in one plan, at most {nb}")
-        B, C_, H, W = x.shape
-        if C_ != 3 or H % 64 or W % 64:
-            raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
+        B, H, W = _check_input(x)
         base_only = single and q == 0
         mode = "single" if single else ("multi" if n_lv == 1 else "levels")
         key = ("full_train", B, H, W, mode, base_only, str(x.device)) + ((n_lv,) if mode == "levels" else ())
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = FullTrainPlan(self, B, H, W, mode, base_only, x.device, n_levels=max(n_lv, 1))
-            self._plans[key] = plan
-        mpr = lambda q_: 10 if (mask_pol == "two-levels" and q_ != 0) else q_
-        pr = [mpr(q_) for q_ in qs[1:]] if mode == "levels" else mpr(q)
+        # no staleness check: the plan re-packs every module it reads at each step (the REMs are not on its path)
+        plan = self._cached_plan(self._plans, key, lambda: FullTrainPlan(self, B, H, W, mode, base_only, x.device,
+                                                                         n_levels=max(n_lv, 1)))
+        pr = [_mask_quality(mask_pol, q_) for q_ in qs[1:]] if mode == "levels" else _mask_quality(mask_pol, q)
         raw = plan.execute(x.detach(), pr, self.use_graph, noise=noise)
         x_hat, lik, z_lik = _FullTrainFn.apply(plan, self.use_graph, getattr(self, "grad_reducer", None), raw["x_hat"], raw["lik"],
                                                raw["z_lik"], *plan.params)
@@ -565,15 +548,13 @@ class VarianceMaskingPIC(CompressionModel):
         """One rANS stream per (slice, image) for y and per image for z.  The latents, entropy
         parameters, masks, symbols and table indexes come from the fused HIP plan; only the
         bit-serial coder runs on the host (as in the reference, entropy_models.py:231-239)."""
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
         base_only = quality <= 0
         rem_idx = None if base_only else self._rem_choice(quality, checkpoint_rep)
-        pr = 10 if (mask_pol == "two-levels" and quality != 0) else quality
+        pr = _mask_quality(mask_pol, quality)
         plan = self._plan(x, base_only=base_only, rem_idx=rem_idx, symbols=True)
         out = plan.execute(x, pr, checkpoint_rep if rem_idx is not None else None, self.use_graph, True)
         B, C = plan.B, self.dim_chunk
@@ -608,9 +589,7 @@ class VarianceMaskingPIC(CompressionModel):
     def decompress(self, strings, shape, quality, mask_pol=None, checkpoint_rep=None):
         """models/pic.py:838-967: z -> hyper-synthesis -> slice by slice (entropy parameters on the
         GPU, rANS decode on the host, LRP on the GPU) -> g_s."""
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         L.require_gpu()
         self._check_config()
         dev = self.entropy_bottleneck.quantiles.device
@@ -618,37 +597,19 @@ class VarianceMaskingPIC(CompressionModel):
         hz, wz = int(shape[0]), int(shape[1])
         base_only = quality == 0
         rem_idx = None if base_only else self._rem_choice(quality, checkpoint_rep)
-        key = (B, hz, wz, base_only, rem_idx, str(dev))
-        dp = self._dec_plans.get(key)
-        if dp is not None and rem_idx is not None and dp.rem_sig != _version_sig(self.post_latent[rem_idx]):
-            dp = None               # REM fine-tuned since the plan packed its weights
-        wsig = self._weights_sig()
-        if dp is not None and dp.wsig != wsig:
-            dp = None               # a weight was edited in place since the plan packed it
-        if dp is None:
+
+        def build():
             if ops.f16x2_mode():
-                raise NotImplementedError("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-forward configuration: its results depend, in the last bits, on the power-of-two scale of each launch (batch composition, plan structure), so the bitstream path (encoder and decoder must agree bit for bit) and training run in the default bf16x3 arithmetic")
-            dp = _DecPlan(self, B, hz, wz, base_only, rem_idx, dev)
-            dp.wsig = wsig
-            dp.rem_sig = _version_sig(self.post_latent[rem_idx]) if rem_idx is not None else None
-            self._dec_plans[key] = dp
-        pr = 10 if (mask_pol == "two-levels" and quality != 0) else quality
-        return {"x_hat": dp.decode(strings, pr, checkpoint_rep if rem_idx is not None else None)}
+                raise NotImplementedError(F16X2_REFUSAL)
+            return _DecPlan(self, B, hz, wz, base_only, rem_idx, dev)
+        dp = self._cached_plan(self._dec_plans, (B, hz, wz, base_only, rem_idx, str(dev)), build, self._weights_sig(), rem_idx)
+        return {"x_hat": dp.decode(strings, _mask_quality(mask_pol, quality), checkpoint_rep if rem_idx is not None else None)}
 
     def _prog_dec_plan(self, B, hz, wz, q_list) -> "_ProgDecPlan":
         """The plans of progressive.ProgressiveDecoder for one (B, z-shape, quality list), cached beside decompress's."""
         dev = self.entropy_bottleneck.quantiles.device
-        key = ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev))
-        wsig = self._weights_sig()
-        dp = self._dec_plans.get(key)
-        if dp is not None and dp.wsig != wsig:            # a weight was edited in place since the plan packed it
-            self._dec_plans.pop(key).close()
-            dp = None
-        if dp is None:
-            dp = _ProgDecPlan(self, B, hz, wz, q_list, dev)
-            dp.wsig = wsig
-            self._dec_plans[key] = dp
-        return dp
+        return self._cached_plan(self._dec_plans, ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev)),
+                                 lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev), self._weights_sig())
 
 
 class VarianceMaskingPICREM(VarianceMaskingPIC):
@@ -730,9 +691,7 @@ class VarianceMaskingPICREM(VarianceMaskingPIC):
         additive-noise likelihoods, autograd-connected to the ``post_latent`` parameters only."""
         if training:
             return self._forward_train(x, mask_pol, quality, checkpoint_ref, noise)
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
@@ -742,7 +701,7 @@ class VarianceMaskingPICREM(VarianceMaskingPIC):
                                               None if checkpoint_ref is None else checkpoint_ref[i:i + nb], True)
                                  for i in range(0, x.shape[0], nb)])
         rem_idx = self._rem_choice(quality, checkpoint_ref) if quality != 0 else None
-        pr = 10 if (mask_pol == "two-levels" and quality != 0) else quality
+        pr = _mask_quality(mask_pol, quality)
         plan = self._plan(x, base_only=(quality == 0), rem_idx=rem_idx)
         return plan.execute(x, pr, checkpoint_ref if rem_idx is not None else None, self.use_graph, clone)
 
@@ -767,19 +726,17 @@ class VarianceMaskingPICREM(VarianceMaskingPIC):
         if loose:
             raise NotImplementedError("training-mode forward is built for --training_type rems only (call freeze_all(); "
                                       f"unfreeze_rems()); trainable non-REM parameters: {loose[:3]}...")
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if mask_pol not in ("point-based-std", "two-levels"):
-            raise NotImplementedError()
+        mask_pol = self._mask_policy(mask_pol)
         L.require_gpu()
         self._check_config()
         own = isinstance(checkpoint_ref, str)
         if checkpoint_ref is not None and not own:
             checkpoint_ref = checkpoint_ref.detach()
         rem_idx = self._rem_choice(quality, checkpoint_ref) if quality != 0 else None
-        pr = 10 if (mask_pol == "two-levels" and quality != 0) else quality
+        pr = _mask_quality(mask_pol, quality)
         own = own and rem_idx is not None
-        if own and mask_pol == "two-levels":
-            ck_pr = 10 if ck_pr != 0 else 0
+        if own:
+            ck_pr = _mask_quality(mask_pol, ck_pr)
         plan = self._plan(x.detach(), base_only=(quality == 0), rem_idx=rem_idx, train=True, own_ck=own)
         out = plan.execute(x.detach(), pr, checkpoint_ref if (rem_idx is not None and not own) else None, self.use_graph,
                            True, noise=noise, ck_pr=ck_pr if own else None)
@@ -829,6 +786,24 @@ MAX_PLAN_PIXELS = int((2 ** 31 - 2 ** 20) // (192 * 4) * 4)
 
 def _max_images_per_plan(x) -> int:
     return max(1, MAX_PLAN_PIXELS // (x.shape[2] * x.shape[3]))
+
+
+def _check_input(x):
+    """(B, H, W) of an image batch the plans accept."""
+    B, C_, H, W = x.shape
+    if C_ != 3 or H % 64 or W % 64:
+        raise ValueError(f"expected [B,3,H,W] with H,W multiples of 64 (reference pads to 64), got {tuple(x.shape)}")
+    return B, H, W
+
+
+def _mask_quality(mask_pol, q):
+    """The quality the variance mask is computed at (channel_mask.py:152-153: two-levels is all ones unless pr == 0)."""
+    return 10 if (mask_pol == "two-levels" and q != 0) else q
+
+
+F16X2_REFUSAL = ("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-forward configuration: its results depend, in "
+                 "the last bits, on the power-of-two scale of each launch (batch composition, plan structure), so the "
+                 "bitstream path (encoder and decoder must agree bit for bit) and training run in the default bf16x3 arithmetic")
 
 
 def _cat_outputs(outs):
@@ -954,11 +929,10 @@ class _FsqPlan:
         self.symbols = symbols
         self.train = train          # additive-noise likelihoods (+ taped REM and a backward plan when rem_idx is set)
         self.bwd = None             # backward plan of a training plan (REM fine-tune or refine_gs): see _backward
-        self._bwd_graph = None
         self.generation = 0         # bumped by every execute(): which forward the training tape belongs to
         self.pr = 0.0
-        self.graphs: Dict[float, ops.Graph] = {}
-        self.stream = None
+        self.runner = E.Runner(device, cap=32)      # forward graphs per (pr, ck_pr)
+        self.bwd_runner = E.Runner(device)          # the backward's graph (no cap), replayed on self.runner's stream
         plan = self.plan = E.Plan(device)
         h, w = H // 16, W // 16
         d = m.division_dimension[0]
@@ -1235,21 +1209,10 @@ class _FsqPlan:
     def _backward(self, grad: torch.Tensor, use_graph: bool) -> List[torch.Tensor]:
         """Run the backward plan for the incoming gradient (dL/dlikelihoods["y"] of the REM fine-tune, dL/dx_hat of
         refine_gs), capturing its graph at the first graph run; returns fresh tensors in ``train_params`` order."""
-        cur = torch.cuda.current_stream(self.x_in.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self.runner.on_stream():
             self._bwd_in(grad)
-            if use_graph:
-                if self._bwd_graph is None:
-                    self.bwd.run()
-                    self.stream.synchronize()
-                    self._bwd_graph = ops.Graph()
-                    self._bwd_graph.capture(self.bwd.run)
-                self._bwd_graph.launch()
-            else:
-                self.bwd.run()
+            self.bwd_runner.replay("backward", self.bwd.run, use_graph)
             flat = self.gflat.clone()
-        cur.wait_stream(self.stream)
         return [flat[o:o + p.numel()].view(p.shape) for o, p in zip(self.goffs, self.train_params)]
 
     def _lower_prog_sequential(self, plan, heads, means_h, scales_h, hyper_done, supports, y_top, y_sub, yb, yp, ls_y,
@@ -1297,11 +1260,8 @@ class _FsqPlan:
     # -------------------------------------------------------------------------------------------
     def close(self):
         """Give up the executable graphs of this plan (ops.Graph.close: destroyed at the next safe point)."""
-        for g in list(self.graphs.values()) + [self._bwd_graph, getattr(self.plan, "_graph", None)]:
-            if g is not None:
-                g.close()
-        self.graphs.clear()
-        self._bwd_graph = None
+        self.runner.close()
+        self.bwd_runner.close()
 
     def set_noise(self, noise=None):
         """Training: U(-.5,.5) for the likelihood proxies; ``noise`` = {"y": NCHW, "z": NCHW} injects fixed draws
@@ -1313,44 +1273,20 @@ class _FsqPlan:
                 v.buf.uniform_(-0.5, 0.5)
 
     def execute(self, x, pr, checkpoint_ref, use_graph, clone, noise=None, ck_pr=None):
-        """Run the plan on the model's own HIP stream (hipGraph capture is not allowed on the
-        legacy default stream), ordered after / before the caller's current stream."""
+        """Run the plan on its runner's stream, ordered after / before the caller's current stream."""
         self.pr = float(pr)
         self.generation += 1
         self.ck_pr = float(ck_pr) if ck_pr is not None else 0.0
-        if self.bwd is not None:
-            sig = tuple(p.data_ptr() for p in self.train_params)
-            if getattr(self, "_ptr_sig", sig) != sig:          # parameter storage replaced: captured pointers are stale
-                self.close()
-            self._ptr_sig = sig
-        ops.drain_graveyard()                          # dropped plans' graphs: destroyed here, outside any capture
-        cur = torch.cuda.current_stream(self.x_in.device)
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.x_in.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        if self.bwd is not None and self.runner.stale(self.train_params):
+            self.close()                               # parameter storage replaced: captured pointers are stale
+        with self.runner.on_stream():
             self.x_in.copy_(x)
             if self.train:
                 self.set_noise(noise)
             if checkpoint_ref is not None:
                 ck = ops.from_nchw(checkpoint_ref.to(self.x_in.device))
                 self.ck.buf.copy_(ck.buf[..., ck.c0:ck.c0 + ck.C])
-            if use_graph:
-                g = self.graphs.get((self.pr, self.ck_pr))
-                if g is None:
-                    self.plan.run()                      # warm-up: every code object loaded before capture
-                    self.stream.synchronize()
-                    g = ops.Graph()
-                    g.capture(self.plan.run)
-                    if len(self.graphs) > 32:
-                        for g_ in self.graphs.values():
-                            g_.close()
-                        self.graphs.clear()
-                    self.graphs[(self.pr, self.ck_pr)] = g
-                g.launch()
-            else:
-                self.plan.run()
-        cur.wait_stream(self.stream)
+            self.runner.replay((self.pr, self.ck_pr), self.plan.run, use_graph)
         fin = (lambda t: t.clone()) if clone else (lambda t: t)
         nchw = lambda v: fin(v.torch_nchw())
         out = {"x_hat": fin(self.x_hat),
@@ -1382,32 +1318,6 @@ def sweep_groups(n_levels: int, B: int, H: int, W: int) -> List[tuple]:
     return out
 
 
-def _launch(plan: E.Plan, graphs: Optional[dict], key, stream, use_graph: bool, prep=None):
-    """Run ``plan`` on ``stream`` ordered after / before the caller's stream (as _FsqPlan.execute does), replaying the
-    hipGraph kept in ``graphs[key]`` (captured at its first use; more than 32 kept: all retired)."""
-    cur = torch.cuda.current_stream(plan.device)
-    stream.wait_stream(cur)
-    with torch.cuda.stream(stream):
-        if prep is not None:
-            prep()
-        if use_graph:
-            g = graphs.get(key)
-            if g is None:
-                plan.run()                           # warm-up: every code object loaded before capture
-                stream.synchronize()
-                g = ops.Graph()
-                g.capture(plan.run)
-                if len(graphs) > 32:
-                    for g_ in graphs.values():
-                        g_.close()
-                    graphs.clear()
-                graphs[key] = g
-            g.launch()
-        else:
-            plan.run()
-    cur.wait_stream(stream)
-
-
 class _SweepTail:
     """The per-level part of a rate sweep for ``n_levels`` qualities over the shared buffers of a _SweepPlan's front end
     (pic.py:621-651 once per level), run as n_levels * B images: level k is images k*B .. (k+1)*B-1 of every buffer here.
@@ -1432,7 +1342,7 @@ class _SweepTail:
         self.n_levels, self.B = NL, B
         self.prs = (0.0,) * NL            # eval: the mask qualities of the levels
         self.ks = (0,) * NL               # decode: the container-layer cut-offs of the levels
-        self.graphs: Dict[tuple, ops.Graph] = {}
+        self.runner = E.Runner(dev, cap=32)     # one graph per tuple of levels, replayed on the owner's stream
         P = self.plan = E.Plan(dev)
         sl = lambda v, i, n=1: v.window(i * C, n * C)
         self.log2sum = torch.zeros((NL, B), dtype=torch.float64, device=dev)      # level k's progressive log2 sums per image
@@ -1475,9 +1385,7 @@ class _SweepTail:
         return ops.View(v.buf[k * self.B:(k + 1) * self.B], v.c0, v.C)
 
     def close(self):
-        for g in self.graphs.values():
-            g.close()
-        self.graphs.clear()
+        self.runner.close()
 
 
 class _SweepPlan:
@@ -1488,40 +1396,34 @@ class _SweepPlan:
 
     def __init__(self, m: VarianceMaskingPIC, B, H, W, device):
         self.m, self.B, self.H, self.W = m, B, H, W
-        self.device = torch.device(device)
         self.fp = _FsqPlan(m, B, H, W, False, None, device, sweep=True)
         self.p_base = E.Plan(device)
         self.p_base.set_class("g_s")
         E.lower_g_s(self.p_base, [m.g_s[0] if m.multiple_decoder else m.g_s], [self.fp.y_base], [self.fp.x_hat])
         self.tails: Dict[int, _SweepTail] = {}
-        self.graphs: Dict[tuple, ops.Graph] = {}         # ("front",) and ("base",)
-        self.stream = None
-
-    def _stream(self):
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.device)
-        return self.stream
+        self.runner = E.Runner(device, cap=32)           # ("front",) and ("base",); the tails run on its stream
 
     def front(self, x, use_graph: bool):
-        ops.drain_graveyard()
-        _launch(self.fp.plan, self.graphs, ("front",), self._stream(), use_graph, prep=lambda: self.fp.x_in.copy_(x))
+        with self.runner.on_stream():
+            self.fp.x_in.copy_(x)
+            self.runner.replay(("front",), self.fp.plan.run, use_graph)
 
     def base(self, use_graph: bool):
-        _launch(self.p_base, self.graphs, ("base",), self._stream(), use_graph)
+        with self.runner.on_stream():
+            self.runner.replay(("base",), self.p_base.run, use_graph)
 
     def tail(self, prs: Sequence[float], use_graph: bool) -> _SweepTail:
         t = self.tails.get(len(prs))
         if t is None:
             t = self.tails[len(prs)] = _SweepTail(self.fp, len(prs))
         t.prs = tuple(float(p_) for p_ in prs)
-        _launch(t.plan, t.graphs, t.prs, self._stream(), use_graph)
+        with self.runner.on_stream():
+            t.runner.replay(t.prs, t.plan.run, use_graph)
         return t
 
     def close(self):
         self.fp.close()
-        for g in self.graphs.values():
-            g.close()
-        self.graphs.clear()
+        self.runner.close()
         for t in self.tails.values():
             t.close()
 
@@ -1536,9 +1438,10 @@ class _DecPlan:
         """``prog_chain``: stop after the base slices (hyper-synthesis of both halves and every stack head included) and
         keep g_s[0] on y_hat_base in ``p_syn``; _ProgDecPlan lowers the progressive part itself."""
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
+        self.rem_sig = _version_sig(m.post_latent[rem_idx]) if rem_idx is not None else None
         self.device = torch.device(device)
         self.pr = 0.0
-        self.stream = None
+        self.runner = E.Runner(device, cap=32)           # stream ordering; _ProgDecPlan's ("base",) graph
         h, w = hz * 4, wz * 4
         self.h, self.w, self.hz, self.wz = h, w, hz, wz
         d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
@@ -1618,7 +1521,7 @@ class _DecPlan:
         """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window)."""
         from . import bitstream as bs
         B, h, w = self.B, idx_view.buf.shape[1], idx_view.buf.shape[2]
-        self.stream.synchronize()
+        self.runner.stream.synchronize()
         idx = idx_view.buf[..., idx_view.c0:idx_view.c0 + C].cpu().numpy()          # [B,h,w,C]
         out = np.empty((B, h, w, C), dtype=np.int32)
         for b in range(B):
@@ -1627,7 +1530,8 @@ class _DecPlan:
         sym_view.buf[..., sym_view.c0:sym_view.c0 + C].copy_(torch.from_numpy(out).to(self.device))
 
     def _decode_base(self, y_strings, z_strings, tg, te):
-        """z (host decode) -> hyper-synthesis -> base slices, each slice's symbols decoded on the host; on self.stream."""
+        """z (host decode) -> hyper-synthesis -> base slices, each slice's symbols decoded on the host; on the runner's
+        stream."""
         from . import bitstream as bs
         m, C = self.m, self.m.dim_chunk
         zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
@@ -1649,12 +1553,8 @@ class _DecPlan:
         if len(y_strings) < n_need or len(z_strings) != self.B:
             raise ValueError(f"expected {n_need} slice streams x {self.B} images, got {len(y_strings)} x {len(z_strings)}")
         tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
-        cur = torch.cuda.current_stream(self.device)
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.device)
-        self.stream.wait_stream(cur)
         C = m.dim_chunk
-        with torch.cuda.stream(self.stream):
+        with self.runner.on_stream():
             if checkpoint_rep is not None:
                 ck = ops.from_nchw(checkpoint_rep.to(self.device))
                 self.ck.buf.copy_(ck.buf[..., ck.c0:ck.c0 + ck.C])
@@ -1665,8 +1565,10 @@ class _DecPlan:
                     self._decode_slice(y_strings[m.ns0 + j], self.idx_p.window(j * C, C), self.sym_p.window(j * C, C), tg, C)
                     Pb.run()
             self.p_syn.run()
-        cur.wait_stream(self.stream)
         return self.x_hat.clone()
+
+    def close(self):
+        self.runner.close()
 
 
 class _ProgDecPlan(_DecPlan):
@@ -1704,41 +1606,31 @@ class _ProgDecPlan(_DecPlan):
         self.sweep_parts = dict(heads=heads, yb=yb, mu=mu_p, std=std_p, mu_tot=mu_tot, sym=self.sym, layer=self.layer,
                                 g_s=m.g_s[1] if m.multiple_decoder else m.g_s)
         self.tails: Dict[int, _SweepTail] = {}
-        self.graphs: Dict[tuple, ops.Graph] = {}
         self.owner = None                   # the ProgressiveDecoder whose base and chain the buffers hold
-
-    def _stream(self):
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.device)
-        return self.stream
 
     def front(self, y_strings, z_strings):
         """Base slices (host round trips) and the progressive chain, layer ids and indexes of every image."""
         from . import bitstream as bs
-        ops.drain_graveyard()
         tg, te = bs.Tables.of(self.m.gaussian_conditional), bs.Tables.of(self.m.entropy_bottleneck)
-        cur = torch.cuda.current_stream(self.device)
-        self._stream().wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self.runner.on_stream():
             self._decode_base(y_strings, z_strings, tg, te)
             self.p_chain.run()
-        cur.wait_stream(self.stream)
 
     def base(self, use_graph: bool):
-        _launch(self.p_syn, self.graphs, ("base",), self._stream(), use_graph)
+        with self.runner.on_stream():
+            self.runner.replay(("base",), self.p_syn.run, use_graph)
 
     def tail(self, ks: Sequence[int], use_graph: bool) -> _SweepTail:
         t = self.tails.get(len(ks))
         if t is None:
             t = self.tails[len(ks)] = _SweepTail(self, len(ks), decode=True)
         t.ks = tuple(int(k) for k in ks)
-        _launch(t.plan, t.graphs, t.ks, self._stream(), use_graph)
+        with self.runner.on_stream():
+            t.runner.replay(t.ks, t.plan.run, use_graph)
         return t
 
     def close(self):
-        for g in self.graphs.values():
-            g.close()
-        self.graphs.clear()
+        super().close()
         for t in self.tails.values():
             t.close()
 

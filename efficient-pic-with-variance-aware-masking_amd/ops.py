@@ -931,8 +931,8 @@ class Graph:
     """hipGraph capture of a sequence of libvampic launches on the current stream.
 
     Lifetime.  A dropped graph (``close()`` or garbage collection) only parks its handle: no HIP call from ``__del__``,
-    which can run inside another plan's capture.  :func:`drain_graveyard` — called by the plans at their entry points,
-    never during a capture — synchronises the stream each parked handle was last launched on and then RETIRES it: the
+    which can run inside another plan's capture.  :func:`drain_graveyard` — called by ``engine.Runner`` at every entry of
+    a plan, never during a capture — synchronises the stream each parked handle was last launched on and then RETIRES it: the
     handle is kept for the life of the process and ``hipGraphExecDestroy`` is not called.
 
     Why not destroyed (round 3, demonstrated; ROCm 7.2 / gfx950).  The host segfault of round 2 (``hipGraphLaunch``

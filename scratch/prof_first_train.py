@@ -16,7 +16,7 @@ out = net(x, quality=[0, 10], training=True)
 crit(out, x)["loss"].backward()
 plan = [p for k, p in net._plans.items() if k[0] == "full_train"][0]
 for name, pl in (("forward", plan.plan), ("backward", plan.bwd)):
-    with torch.cuda.stream(plan.stream):
+    with torch.cuda.stream(plan.runner.stream):
         prof = pl.profile(2)
     print(name, "total", round(sum(p["ms"] for p in prof), 2), "ms, steps", len(prof))
     agg = collections.OrderedDict()

@@ -11,7 +11,7 @@ net = net.cuda().train(); net.freeze_all(); net.unfreeze_rems(); net.use_graph =
 x = vampic.synth.synth_image(16, 256, 256, seed=1).cuda()
 out = net.forward_finetune(x, 2.5)
 plan = [p for k, p in net._plans.items() if "train" in k][0]
-with torch.cuda.stream(plan.stream):
+with torch.cuda.stream(plan.runner.stream):
     prof = plan.plan.profile(3)
 tot = sum(p["ms"] for p in prof)
 print("total", tot, "steps", len(prof))
@@ -21,7 +21,7 @@ for p in prof:
     a = agg.setdefault(k, [0, 0.0]); a[0] += 1; a[1] += p["ms"]
 for k, (n, ms) in sorted(agg.items(), key=lambda t: -t[1][1])[:40]:
     print(f"{ms:8.3f} ms  x{n:3d}  {k}")
-with torch.cuda.stream(plan.stream):
+with torch.cuda.stream(plan.runner.stream):
     prof = plan.bwd.profile(3)
 print("bwd total", sum(p["ms"] for p in prof), len(prof))
 agg = collections.OrderedDict()
