@@ -156,6 +156,7 @@ _SIGNATURES = {
     "vam_gauss_tail": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_void_p, C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_gauss_levels_eval": (C.c_int, [C.c_void_p, C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_long] * 4
                               + [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p]),
+    "vam_gauss_layer_bits": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_build_indexes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_eb_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p]),
     "vam_eb_aux_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -255,6 +255,73 @@ __global__ void gauss_levels_decode_kernel(const DecodeLevelsArgs a) {
   }
 }
 
+// The rate-only tail (vam_gauss_layer_bits): the in-mask likelihood of every element — masked_tail /
+// gauss_lik with m = 1, the float gauss_levels_eval_kernel gets for an element inside a mask — binned by the element's
+// container layer.  A workgroup's pixels belong to one item; its four waves keep one row of n_levels + 1 fp64 bins (and
+// counts) each in LDS, filled with LDS atomics, and the workgroup flushes one global fp64 atomic per non-empty bin.
+struct LayerBitsArgs {
+  const float *y, *y2, *mu, *sigma;
+  const uint8_t* layer;
+  double* bits;
+  long long* count;
+  int ld_y, ld_y2, ld_mu, ld_sigma, ld_layer;
+  int n_levels, C4, blocks_per_item;
+  long vec_per_item;     // pix_per_item * C4
+};
+
+constexpr int LAYER_BINS = VAM_MAX_LAYER_LEVELS + 1;
+
+__global__ __launch_bounds__(256) void gauss_layer_bits_kernel(const LayerBitsArgs a) {
+  __shared__ double sh_bits[4][LAYER_BINS];
+  __shared__ unsigned sh_cnt[4][LAYER_BINS];
+  const int nb = a.n_levels + 1;                           // slot n_levels: layer == 0xFF
+  const int item = blockIdx.x / a.blocks_per_item, blk = blockIdx.x - item * a.blocks_per_item;
+  const int wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < 4 * LAYER_BINS; i += 256) {
+    (&sh_bits[0][0])[i] = 0.0;
+    (&sh_cnt[0][0])[i] = 0u;
+  }
+  __syncthreads();
+  const long v0 = (long)item * a.vec_per_item;
+  for (long j = (long)blk * 256 + threadIdx.x; j < a.vec_per_item; j += (long)a.blocks_per_item * 256) {
+    const long i = v0 + j;
+    long p = i / a.C4;
+    int c = (int)(i - p * a.C4) * 4;
+    float4 y = *reinterpret_cast<const float4*>(a.y + p * a.ld_y + c);
+    if (a.y2) {
+      float4 y2 = *reinterpret_cast<const float4*>(a.y2 + p * a.ld_y2 + c);
+      y.x -= y2.x; y.y -= y2.y; y.z -= y2.z; y.w -= y2.w;            // pic.py:583-584
+    }
+    float4 mu = *reinterpret_cast<const float4*>(a.mu + p * a.ld_mu + c);
+    float4 sg = *reinterpret_cast<const float4*>(a.sigma + p * a.ld_sigma + c);
+    unsigned ly = *reinterpret_cast<const unsigned*>(a.layer + p * a.ld_layer + c);
+    float yv[4] = {y.x, y.y, y.z, y.w}, mv[4] = {mu.x, mu.y, mu.z, mu.w}, sv[4] = {sg.x, sg.y, sg.z, sg.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float d = yv[k] - mv[k];
+      float q = rintf(d);                         // torch.round = half-to-even
+      float yh, absv, s;
+      int sy;
+      masked_tail(d, q, mv[k], sv[k], 1.f, yh, absv, s, sy);
+      const float lk = gauss_lik(absv, s);
+      const int l = (int)((ly >> (8 * k)) & 255u);
+      const int bin = l < a.n_levels ? l : a.n_levels;     // 0xFF (and any id beyond the list) -> the last slot
+      __hip_atomic_fetch_add(&sh_bits[wave][bin], log2((double)lk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&sh_cnt[wave][bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < nb) {
+    const unsigned n = sh_cnt[0][t] + sh_cnt[1][t] + sh_cnt[2][t] + sh_cnt[3][t];
+    if (n) {
+      const double v = (sh_bits[0][t] + sh_bits[1][t]) + (sh_bits[2][t] + sh_bits[3][t]);
+      atomicAdd(a.bits + (long)item * nb + t, v);
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.count) + (long)item * nb + t, (unsigned long long)n);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ build_indexes
 __global__ void build_indexes_kernel(const float* __restrict__ sigma, int ld_sigma, const float* __restrict__ mask,
                                      int ld_mask, const float* __restrict__ table, int n_table,
@@ -572,6 +639,37 @@ int vam_gauss_levels_decode(const int32_t* sym, int ld_sym, const uint8_t* layer
   ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, (double)n_pix * C * (9.0 + 4.0 * n_levels));
   hipLaunchKernelGGL(gauss_levels_decode_kernel, dim3(stream_grid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("gauss_levels_decode_kernel");
+}
+
+int vam_gauss_layer_bits(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const uint8_t* layer, int ld_layer, int n_levels,
+                         double* bits, long long* count, int pix_per_item, long n_pix, int C, void* stream) {
+  VAM_REQUIRE(y && mu && sigma && layer && bits && count, "vam_gauss_layer_bits: y, mu, sigma, layer, bits and count must not be NULL");
+  VAM_REQUIRE(n_pix > 0 && C > 0 && C % 4 == 0, "vam_gauss_layer_bits: need n_pix > 0 and C %% 4 == 0");
+  VAM_REQUIRE(n_levels >= 1 && n_levels <= VAM_MAX_LAYER_LEVELS, "vam_gauss_layer_bits: 1..%d levels, got %d",
+              VAM_MAX_LAYER_LEVELS, n_levels);
+  VAM_REQUIRE(pix_per_item > 0 && n_pix % pix_per_item == 0, "vam_gauss_layer_bits: pix_per_item must divide n_pix");
+  VAM_REQUIRE((long)pix_per_item * C < (1L << 31) && n_pix / pix_per_item < (1L << 24), "vam_gauss_layer_bits: item too large");
+  VAM_REQUIRE(al16(y) && al16(mu) && al16(sigma) && al16(y2) && (((uintptr_t)layer) & 3) == 0 && (((uintptr_t)bits) & 7) == 0 &&
+              (((uintptr_t)count) & 7) == 0, "vam_gauss_layer_bits: alignment");
+  VAM_REQUIRE(ld_y % 4 == 0 && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && ld_layer % 4 == 0 && (!y2 || ld_y2 % 4 == 0) &&
+              ld_y >= C && ld_mu >= C && ld_sigma >= C && ld_layer >= C && (!y2 || ld_y2 >= C),
+              "vam_gauss_layer_bits: pixel strides must be multiples of 4 and >= C");
+  LayerBitsArgs a;
+  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.layer = layer; a.bits = bits; a.count = count;
+  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma; a.ld_layer = ld_layer;
+  a.n_levels = n_levels; a.C4 = C / 4;
+  a.vec_per_item = (long)pix_per_item * (C / 4);
+  const long n_items = n_pix / pix_per_item;
+  // a workgroup stays inside one item; about two float4 per lane, and no more than ~2048 workgroups in all
+  long per_item = cdiv(a.vec_per_item, 512L);
+  const long room = n_items >= 2048 ? 1 : 2048 / n_items;
+  if (per_item > room) per_item = room;
+  if (per_item < 1) per_item = 1;
+  a.blocks_per_item = (int)per_item;
+  ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, (double)n_pix * C * (y2 ? 17.0 : 13.0));
+  hipLaunchKernelGGL(gauss_layer_bits_kernel, dim3((unsigned)(n_items * per_item)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("gauss_layer_bits_kernel");
 }
 
 int vam_build_indexes(const float* sigma, int ld_sigma, const float* mask, int ld_mask, const float* table,

@@ -101,6 +101,30 @@ def rd_sweep(model, x: torch.Tensor, qualities: Sequence[float]):
     return -vals[0] / hw, -10.0 * torch.log10(vals[1] / (x[0].numel()))
 
 
+def rate_curve(model, x: torch.Tensor, qualities: Sequence[float]):
+    """Estimated bpp of every image of ``x`` at every quality, float64 [L, B] on the host, without reconstructing anything
+    (VarianceMaskingPIC.rate_curve): equal to :func:`rd_sweep`'s bpp."""
+    dev = next(model.parameters()).device
+    return model.rate_curve(x.to(dev).contiguous(), qualities)["bpp"].cpu()
+
+
+def rd_at_rates(model, x: torch.Tensor, target_bpps):
+    """Rate and distortion at target rates: the qualities are resolved once for the batch (VarianceMaskingPIC.
+    qualities_for_bpp: per image the largest quality whose estimated rate fits each target), then every image is
+    evaluated at its own qualities (:func:`rd_sweep` per image: they differ between images).  ``target_bpps``: T floats or
+    a [T, B] tensor.  Returns (bpp, psnr, quality, reached), [T, B] host tensors; where ``reached`` is False (even the
+    base exceeds the budget) the row holds the base (quality 0)."""
+    dev = next(model.parameters()).device
+    x = x.to(dev).contiguous()
+    sol = model.qualities_for_bpp(x, target_bpps)
+    q = sol["quality"]
+    bpp, psnr = torch.zeros_like(q), torch.zeros_like(q)
+    for b in range(x.shape[0]):
+        r, p_ = rd_sweep(model, x[b:b + 1], q[:, b].tolist())
+        bpp[:, b], psnr[:, b] = r[:, 0], p_[:, 0]
+    return bpp, psnr, q, sol["reached"]
+
+
 def _checkpoint_for(model, x, p):
     """training/step.py:13-29 extract_quality_ref + ExtractChekpointRepr (REM models only)."""
     levels = getattr(model, "check_levels", None)

@@ -452,6 +452,109 @@ class VarianceMaskingPIC(CompressionModel):
         self._sweep(x, qualities, mask_pol, emit)
         return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
 
+    # ---- rate control: the rate of many qualities without the per-quality tail (DESIGN section 9h)
+    _REM_RATE_REFUSAL = ("rate control on REM models: the rate at a quality q needs the checkpoint representation of q's "
+                         "check level (the REM refines (mu, sigma) per level), so neither one front end nor one layer pass "
+                         "gives the curve; call forward_single_quality(x, q, checkpoint_ref=...) per quality")
+
+    def _rate_loop(self, x, qualities, mask_pol) -> torch.Tensor:
+        """[len(qualities), 2, B] from one forward_single_quality per quality (models that are not _sweep_eligible)."""
+        if not len(qualities):
+            return torch.zeros((0, 2, x.shape[0]), dtype=torch.float64, device=x.device)
+        return torch.stack([self.forward_single_quality(x, q, mask_pol, training=False)["log2_likelihood_sum"] for q in qualities])
+
+    def _rate_result(self, ls: torch.Tensor, x) -> Dict[str, torch.Tensor]:
+        return {"log2_likelihood_sum": ls, "bpp": -ls.sum(1) / float(x.shape[2] * x.shape[3])}
+
+    def rate_curve(self, x, qualities, mask_pol=None):
+        """The estimated rate of every image of ``x`` at every quality of the list (any order, repeats allowed, any count):
+        {"log2_likelihood_sum": float64 [len(qualities), 2, B] (rows y and z, what forward_single_quality returns per
+        quality, to its float64 summation order), "bpp": float64 [len(qualities), B] = -(y + z) / (H * W)}.  Eligible models
+        (:meth:`_sweep_eligible`) run the front end once per sub-batch and, per group of up to VAM_MAX_LAYER_LEVELS distinct
+        qualities, one vam_variance_layers and one vam_gauss_layer_bits launch: no masks, no LRP stacks, no g_s.  The
+        others loop over forward_single_quality; REM models are refused."""
+        qualities = [float(q) for q in qualities]
+        if isinstance(self, VarianceMaskingPICREM):
+            raise NotImplementedError(self._REM_RATE_REFUSAL)
+        mask_pol = self._mask_policy(mask_pol)
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        if not self._sweep_eligible():
+            with torch.no_grad():
+                return self._rate_result(self._rate_loop(x, qualities, mask_pol), x)
+        prs = [float(_mask_quality(mask_pol, q)) for q in qualities]
+        levels = sorted({p_ for p_ in prs if p_ != 0})
+        col = {p_: j for j, p_ in enumerate(levels)}
+        B, _, H, W = x.shape
+        out = torch.zeros((len(prs), 2, B), dtype=torch.float64, device=x.device)
+        idx = torch.tensor([col[p_] for p_ in prs if p_ != 0], dtype=torch.long, device=x.device)
+        rows = torch.tensor([k for k, p_ in enumerate(prs) if p_ != 0], dtype=torch.long, device=x.device)
+        with torch.no_grad():
+            for i0, i1, _ in sweep_groups(0, B, H, W):
+                xb = x[i0:i1].detach()
+                sw = self._sweep_plan(xb)
+                sw.front(xb, self.use_graph)
+                out[:, :, i0:i1] = sw.fp.log2sum                       # q == 0: the base-only sums (the sweep's zeros branch)
+                prog = [sw.rate(levels[l0:l0 + L.VAM_MAX_LAYER_LEVELS], self.use_graph)
+                        for l0 in range(0, len(levels), L.VAM_MAX_LAYER_LEVELS)]
+                if prog:
+                    out[rows, 0, i0:i1] += torch.cat(prog, 1).t()[idx]
+        return self._rate_result(out, x)
+
+    def qualities_for_bpp(self, x, target_bpp, q_tol=1e-3, mask_pol=None):
+        """The largest quality whose estimated rate fits a budget, per image: ``target_bpp`` a float, T floats or a [T, B]
+        tensor (per-image budgets).  Returns {"quality": float64 [T, B], "bpp": float64 [T, B] (the estimated bpp at that
+        quality), "reached": bool [T, B]} on the host, with, per image b and target t:  bpp_b(q*) <= t;  q* = 10 or
+        bpp_b(min(10, q* + q_tol)) > t;  and q* = 0 with reached = False when even the base exceeds the budget.
+        Eligible models run the front end once per sub-batch and refine a bracket per (target, image) on grids of
+        RATE_GRID points (:func:`rate_search`): a pass is vam_variance_layers + vam_gauss_layer_bits on the buffers the
+        front end left in place and one host synchronisation.  The others bisect over forward_single_quality."""
+        if isinstance(self, VarianceMaskingPICREM):
+            raise NotImplementedError(self._REM_RATE_REFUSAL)
+        mask_pol = self._mask_policy(mask_pol)
+        if mask_pol != "point-based-std":
+            raise ValueError(f"qualities_for_bpp searches the point-based-std curve; the {mask_pol!r} curve has two values "
+                             "(q == 0 and q != 0): read them from rate_curve(x, [0, 10])")
+        if not q_tol > 0:
+            raise ValueError(f"q_tol must be > 0, got {q_tol}")
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        B, _, H, W = x.shape
+        tg = torch.as_tensor(target_bpp, dtype=torch.float64).cpu().numpy()
+        if tg.ndim == 0:
+            tg = tg.reshape(1)
+        if tg.ndim == 1:
+            tg = np.repeat(tg[:, None], B, axis=1)
+        if tg.ndim != 2 or tg.shape[1] != B:
+            raise ValueError(f"target_bpp: a float, T floats or a [T, {B}] tensor, got shape {tuple(tg.shape)}")
+        hw = float(H * W)
+        quality, bpp, reached = (np.zeros(tg.shape), np.zeros(tg.shape), np.zeros(tg.shape, dtype=bool))
+        with torch.no_grad():
+            if not self._sweep_eligible():
+                def curve(q, need):                        # one forward_single_quality per (image, quality) asked for
+                    out = np.zeros(q.shape)
+                    for b in range(B):
+                        qs = np.unique(q[:, b][need[:, b]])
+                        if qs.size:
+                            ls = self._rate_loop(x[b:b + 1], qs.tolist(), mask_pol)
+                            val = dict(zip(qs.tolist(), (-ls.sum(1)[:, 0] / hw).tolist()))
+                            out[:, b][need[:, b]] = [val[v] for v in q[:, b][need[:, b]].tolist()]
+                    return out
+                bpp0 = (-self._rate_loop(x, [0.0], mask_pol)[0].sum(0) / hw).cpu().numpy()
+                quality, bpp, reached = rate_search(curve, bpp0, tg, q_tol, n_grid=2)
+            else:
+                for i0, i1, _ in sweep_groups(0, B, H, W):
+                    xb = x[i0:i1].detach()
+                    sw = self._sweep_plan(xb)
+                    sw.front(xb, self.use_graph)
+                    base = sw.fp.log2sum.clone()                      # [2, b]: y (base slices) and z
+                    bpp0 = (-base.sum(0) / hw).cpu().numpy()
+                    curve = lambda q, need, sw=sw, base=base: sw.rate_points(q, need, base, self.use_graph) / -hw
+                    quality[:, i0:i1], bpp[:, i0:i1], reached[:, i0:i1] = rate_search(curve, bpp0, tg[:, i0:i1], q_tol)
+        return {"quality": torch.from_numpy(quality), "bpp": torch.from_numpy(bpp), "reached": torch.from_numpy(reached)}
+
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),
         stacked as the reference stacks them.  ``training=True`` evaluates the likelihoods with additive uniform noise;
@@ -1318,6 +1421,121 @@ def sweep_groups(n_levels: int, B: int, H: int, W: int) -> List[tuple]:
     return out
 
 
+RATE_GRID = 32          # grid points of one refinement pass of qualities_for_bpp (= VAM_MAX_LAYER_LEVELS: one launch)
+
+
+def rate_search_passes(q_tol: float, n_grid: int = RATE_GRID) -> int:
+    """Passes after which a bracket that starts as [0, 10] and shrinks by ``n_grid`` per pass is no wider than q_tol."""
+    n, w = 0, 10.0
+    while w > q_tol:
+        w /= n_grid
+        n += 1
+    return n
+
+
+def rate_search_grid(lo, hi, n_grid: int = RATE_GRID):
+    """[..., n_grid] ascending points that split each bracket (lo, hi] evenly; the last one is hi itself."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    f = np.arange(1, n_grid + 1, dtype=np.float64) / n_grid
+    g = lo[..., None] + (hi - lo)[..., None] * f
+    g[..., -1] = hi
+    return g
+
+
+def rate_search_step(grid_q, grid_bpp, targets):
+    """One refinement of the bracket arithmetic of qualities_for_bpp, on host arrays: ``grid_q`` [..., G] ascending
+    qualities whose FIRST point is the bracket's lower end, ``grid_bpp`` [..., G] the (non-decreasing) rate there,
+    ``targets`` [...].  Returns (lo, bpp_lo, hi, bpp_hi, reached): lo = the largest grid point whose rate is within the
+    target (reached False, and lo = the first point, when not even that one is), hi = the grid point after lo (lo itself
+    when lo is the last one: the budget covers the whole grid)."""
+    q, r = np.asarray(grid_q, dtype=np.float64), np.asarray(grid_bpp, dtype=np.float64)
+    t = np.asarray(targets, dtype=np.float64)
+    ok = r <= t[..., None]
+    G = q.shape[-1]
+    # the LAST point within budget (a non-decreasing curve makes `ok` a prefix; taking the last keeps bpp(lo) <= t anyway)
+    last = G - 1 - np.argmax(ok[..., ::-1], axis=-1)
+    reached = ok.any(axis=-1)
+    i_lo = np.where(reached, last, 0)
+    i_hi = np.minimum(i_lo + 1, G - 1)
+    i_hi = np.where(reached, i_hi, 0)
+    take = lambda a, i: np.take_along_axis(a, i[..., None], axis=-1)[..., 0]
+    return take(q, i_lo), take(r, i_lo), take(q, i_hi), take(r, i_hi), reached
+
+
+def rate_search(curve, bpp0, targets, q_tol: float, n_grid: int = RATE_GRID):
+    """Successive refinement for qualities_for_bpp on host arrays, no model and no GPU of its own.  ``curve(q, need)``
+    returns the rate at the qualities q [T, B, n] (entries outside ``need`` [T, B, n] are not read), non-decreasing in q
+    per image; ``bpp0`` [B] the rate at q = 0; ``targets`` [T, B].  Pass 1 evaluates n_grid points of (0, 10]; later passes
+    the n_grid - 1 interior points of each (target, image)'s bracket (both ends are known), so the bracket shrinks by
+    n_grid per pass and rate_search_passes(q_tol, n_grid) passes end it.  Returns (quality, bpp, reached), each [T, B]."""
+    t = np.asarray(targets, dtype=np.float64)
+    T, B = t.shape
+    lo = np.zeros((T, B))
+    r_lo = np.broadcast_to(np.asarray(bpp0, dtype=np.float64), (T, B)).copy()
+    hi, r_hi = np.full((T, B), 10.0), np.full((T, B), np.inf)
+    reached = r_lo <= t
+    active = reached.copy()                                    # brackets still open
+    for p in range(rate_search_passes(q_tol, n_grid)):
+        if not active.any():
+            break
+        pts = rate_search_grid(lo, hi, n_grid)                 # [T, B, n]; from pass 2 on the last point (hi) is known
+        need = np.broadcast_to(active[..., None], pts.shape).copy()
+        if p > 0:
+            need[..., -1] = False
+        r = np.where(need, curve(pts, need), r_hi[..., None])
+        gq = np.concatenate([lo[..., None], pts], axis=-1)
+        gr = np.concatenate([r_lo[..., None], r], axis=-1)
+        n_lo, n_rlo, n_hi, n_rhi, _ = rate_search_step(gq, gr, t)
+        lo, r_lo = np.where(active, n_lo, lo), np.where(active, n_rlo, r_lo)
+        hi, r_hi = np.where(active, n_hi, hi), np.where(active, n_rhi, r_hi)
+        active &= hi > lo                                      # lo == hi: the budget covers q = 10
+    return np.where(reached, lo, 0.0), r_lo, reached
+
+
+class _RateTail:
+    """The rate-only tail of a _SweepPlan's front end for ``n_levels`` sorted distinct qualities > 0: one
+    vam_variance_layers launch on the progressive sigma gives every element the first level whose mask holds it, one
+    vam_gauss_layer_bits launch bins the in-mask log2 likelihoods by that level.  No masks, no replicated supports, no LRP
+    stacks, no g_s.  ``acc`` [2, B, n_levels + 1]: the float64 sums and (as int64) the counts."""
+
+    def __init__(self, fp, n_levels: int):
+        m, parts = fp.m, fp.sweep_parts
+        sg = parts["std"]
+        assert 1 <= n_levels <= L.VAM_MAX_LAYER_LEVELS
+        dev = sg.buf.device
+        self.parts, self.ns, self.n_levels, self.B = parts, m.ns0, n_levels, sg.B
+        self.prs = (0.0,) * n_levels
+        self.outside = ops.log2_lik_outside(dev)         # log2 L(0, 0) (outside any capture: it synchronises)
+        self.runner = E.Runner(dev, cap=32)              # one graph per tuple of qualities, replayed on the owner's stream
+        self.layer = torch.empty((sg.B, sg.H, sg.W, sg.C), dtype=torch.uint8, device=dev)
+        self.acc = torch.zeros((2, sg.B, n_levels + 1), dtype=torch.float64, device=dev)
+        P = self.plan = E.Plan(dev)
+        P.keep += [self.layer, self.acc]
+        P.set_class("lrp_prog")
+        P.call(lambda: ops.memset_zero(self.acc))
+        P.call(lambda: self.launch(self.prs, self.acc), "layers + layer bits (rate)")
+
+    def launch(self, prs: Sequence[float], acc: torch.Tensor, b: Optional[int] = None):
+        """The two kernels for the whole sub-batch, or (``b``) for image b alone with its own qualities; ``acc`` cleared."""
+        img = (lambda v: v) if b is None else (lambda v: ops.View(v.buf[b:b + 1], v.c0, v.C))
+        pa = self.parts
+        layer = self.layer if b is None else self.layer[b:b + 1]
+        ops.variance_layers(img(pa["std"]), prs, layer, n_slice=self.ns)                      # pic.py:621-622, all levels
+        ops.gauss_layer_bits(img(pa["y_top"]), img(pa["mu"]), img(pa["std"]), layer, len(prs), acc[0], acc[1].view(torch.int64),
+                             y2=None if pa["y_sub"] is None else img(pa["y_sub"]))
+
+    def level_sums(self, acc: torch.Tensor, n_levels: int) -> torch.Tensor:
+        """[..., n_levels] progressive log2 sums from ``acc`` [2, ..., >= n_levels + 1]: level k holds the elements of layers
+        <= k at their in-mask likelihood and every other element at log2 L(0, 0)."""
+        bits, count = acc[0][..., :n_levels + 1], acc[1].view(torch.int64)[..., :n_levels + 1]
+        n = count.sum(-1, keepdim=True)
+        inside = count[..., :n_levels].cumsum(-1)
+        return bits[..., :n_levels].cumsum(-1) + (n - inside).double() * self.outside
+
+    def close(self):
+        self.runner.close()
+
+
 class _SweepTail:
     """The per-level part of a rate sweep for ``n_levels`` qualities over the shared buffers of a _SweepPlan's front end
     (pic.py:621-651 once per level), run as n_levels * B images: level k is images k*B .. (k+1)*B-1 of every buffer here.
@@ -1401,6 +1619,7 @@ class _SweepPlan:
         self.p_base.set_class("g_s")
         E.lower_g_s(self.p_base, [m.g_s[0] if m.multiple_decoder else m.g_s], [self.fp.y_base], [self.fp.x_hat])
         self.tails: Dict[int, _SweepTail] = {}
+        self.rate_tails: Dict[int, _RateTail] = {}
         self.runner = E.Runner(device, cap=32)           # ("front",) and ("base",); the tails run on its stream
 
     def front(self, x, use_graph: bool):
@@ -1421,10 +1640,66 @@ class _SweepPlan:
             t.runner.replay(t.prs, t.plan.run, use_graph)
         return t
 
+    def _rate_tail(self, n_levels: int) -> _RateTail:
+        t = self.rate_tails.get(n_levels)
+        if t is None:
+            t = self.rate_tails[n_levels] = _RateTail(self.fp, n_levels)
+        return t
+
+    def rate(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
+        """[B, len(prs)] float64: the progressive log2 sums at the sorted distinct qualities ``prs`` (> 0), one plan per
+        list length and one hipGraph per list, as the sweep's tails."""
+        t = self._rate_tail(len(prs))
+        t.prs = tuple(float(p_) for p_ in prs)
+        with self.runner.on_stream():
+            t.runner.replay(t.prs, t.plan.run, use_graph)
+        return t.level_sums(t.acc, len(prs))
+
+    def rate_points(self, q, need, base: torch.Tensor, use_graph: bool):
+        """qualities_for_bpp's curve: the total log2 sums (y + z) at the qualities q [T, B, n] (> 0) wanted by ``need``, as
+        a host array of q's shape; one host synchronisation.  Every image has its own points: when all images ask for the
+        same ones (the first pass) the batched tail runs, else the two kernels run per image (n_batch = 1 at the image's
+        offset) with the image's sorted distinct points, VAM_MAX_LAYER_LEVELS at a time, eagerly: the points of a pass are
+        never asked for again, so a graph of them would only be captured and dropped."""
+        T, B, _ = q.shape
+        G = L.VAM_MAX_LAYER_LEVELS
+        pts, inv = [], []
+        for b in range(B):
+            u, iv = np.unique(q[:, b][need[:, b]], return_inverse=True)
+            pts.append(u)
+            inv.append(iv)
+        out = np.zeros(q.shape)
+        tot = base.sum(0)                                                  # [B]
+        if all(u.size == pts[0].size and np.array_equal(u, pts[0]) for u in pts):
+            if not pts[0].size:
+                return out
+            sums = torch.cat([self.rate(pts[0][l0:l0 + G].tolist(), use_graph) for l0 in range(0, pts[0].size, G)], 1)
+            vals = (sums + tot[:, None]).cpu().numpy()                     # [B, n_points]
+            for b in range(B):
+                out[:, b][need[:, b]] = vals[b][inv[b]]
+            return out
+        jobs = [(b, l0, min(G, pts[b].size - l0)) for b in range(B) for l0 in range(0, pts[b].size, G)]
+        if not jobs:
+            return out
+        t = self._rate_tail(G)
+        acc = torch.zeros((2, len(jobs), G + 1), dtype=torch.float64, device=base.device)     # a row per launch; unused slots stay 0
+        with self.runner.on_stream():
+            for j, (b, l0, n) in enumerate(jobs):
+                t.launch(pts[b][l0:l0 + n].tolist(), acc[:, j], b)
+        # a launch of n < G levels leaves its no-layer count in slot n: it only reaches the levels >= n, which are not read
+        sums = t.level_sums(acc, G) + tot[[b for b, _, _ in jobs]][:, None]
+        host = sums.cpu().numpy()                                          # [jobs, G]
+        vals = [np.zeros(u.size) for u in pts]
+        for j, (b, l0, n) in enumerate(jobs):
+            vals[b][l0:l0 + n] = host[j, :n]
+        for b in range(B):
+            out[:, b][need[:, b]] = vals[b][inv[b]]
+        return out
+
     def close(self):
         self.fp.close()
         self.runner.close()
-        for t in self.tails.values():
+        for t in list(self.tails.values()) + list(self.rate_tails.values()):
             t.close()
 
 

@@ -596,6 +596,47 @@ def gauss_levels_decode(sym: "IView", layer: torch.Tensor, mu: View, ks: Sequenc
                                              B * mu.H * mu.W * yhat.ld, mu.n_pix, mu.C, stream_ptr()), "vam_gauss_levels_decode")
 
 
+def gauss_layer_bits(y: View, mu: View, sigma: View, layer: torch.Tensor, n_levels: int, bits: torch.Tensor,
+                     count: torch.Tensor, *, y2: Optional[View] = None, ld_layer: Optional[int] = None):
+    """Rate-only tail (rate control): per image the fp64 sum of log2 of the IN-mask likelihood — the float
+    :func:`gauss_levels_eval` gets for an element inside a mask — and the element count, binned by the layer ids of
+    :func:`variance_layers`: ``bits`` float64 / ``count`` int64 [B, n_levels + 1], slot ``n_levels`` for L.LAYER_NONE.
+    Both accumulate: clear them first (:func:`memset_zero`); one image may use the head of a longer row.  ``layer`` uint8 with pixel stride ``ld_layer`` (default:
+    contiguous [B, H, W, y.C])."""
+    B = y.B
+    if ld_layer is None:
+        assert layer.is_contiguous() and tuple(layer.shape) == (B, y.H, y.W, y.C)
+        ld_layer = y.C
+    assert layer.dtype == torch.uint8 and mu.C == sigma.C == y.C and (y2 is None or y2.C == y.C)
+    for t, dt in ((bits, torch.float64), (count, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous(), (t.dtype, tuple(t.shape))
+        assert t.numel() == B * (n_levels + 1) or (B == 1 and t.numel() > n_levels), (tuple(t.shape), B, n_levels)
+    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
+    L.check(L.load().vam_gauss_layer_bits(*p(y), *p(y2), *p(mu), *p(sigma), layer.data_ptr(), ld_layer, n_levels,
+                                          bits.data_ptr(), count.data_ptr(), y.H * y.W, y.n_pix, y.C, stream_ptr()),
+            "vam_gauss_layer_bits")
+
+
+_LOG2_LIK_OUTSIDE: dict = {}
+
+
+def log2_lik_outside(device) -> float:
+    """log2 L(0, 0): what an element outside the variance mask contributes to the log2-likelihood sum at every quality
+    (masked_tail with m = 0 gives |v| = 0 and sigma = 0; the 0.11 bound applies).  Taken once per process and device from
+    :func:`gauss_layer_bits` itself on one such element, so it is the device's own double."""
+    device = torch.device(device)
+    key = (device.type, device.index)
+    if key not in _LOG2_LIK_OUTSIDE:
+        z = new_view(1, 1, 1, 4, device, zero=True)
+        layer = torch.tensor([0, L.LAYER_NONE, L.LAYER_NONE, L.LAYER_NONE], dtype=torch.uint8, device=device).view(1, 1, 1, 4)
+        bits = torch.zeros((1, 2), dtype=torch.float64, device=device)
+        count = torch.zeros((1, 2), dtype=torch.int64, device=device)
+        gauss_layer_bits(z, z, z, layer, 1, bits, count)
+        assert count.tolist() == [[1, 3]]
+        _LOG2_LIK_OUTSIDE[key] = float(bits[0, 0])
+    return _LOG2_LIK_OUTSIDE[key]
+
+
 def build_indexes(sigma: View, table: torch.Tensor, mask: Optional[View] = None, out: Optional[IView] = None) -> torch.Tensor:
     if out is None:
         out = new_iview(sigma.B, sigma.H, sigma.W, sigma.C, sigma.buf.device)

@@ -212,6 +212,20 @@ def check_q_list(q_list: Sequence[float]) -> List[float]:
     return qs
 
 
+def q_list_for_bpps(model, x, target_bpps: Sequence[float]) -> List[float]:
+    """The quality list of a container of ONE image whose level k lands at the k-th target: per target the largest
+    quality whose estimated rate fits it (VarianceMaskingPIC.qualities_for_bpp), sorted and de-duplicated, as
+    :func:`encode_batch` / :class:`ProgressiveDecoder` accept it.  Targets below the base rate are dropped (the base is
+    level 0 of every container); the rates are the likelihood estimate, not coded bytes."""
+    if x.shape[0] != 1:
+        raise ValueError(f"q_list_for_bpps resolves one image's list (the qualities differ between images), got a batch of {x.shape[0]}")
+    sol = model.qualities_for_bpp(x, [float(t) for t in target_bpps])
+    qs = sorted({float(q) for q, ok in zip(sol["quality"][:, 0].tolist(), sol["reached"][:, 0].tolist()) if ok})
+    if not qs:
+        raise ValueError(f"no target of {list(target_bpps)} reaches the base rate of this image")
+    return check_q_list(qs)
+
+
 def container_bits(c) -> list:
     """[bits_z, bits_base, bits_per_layer] of one image's container (what :func:`encode` returns beside it)."""
     return [8.0 * sum(len(s) for s in c["z"]), 8.0 * sum(len(s[0]) for s in c["base"]),

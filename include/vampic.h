@@ -321,6 +321,23 @@ int vam_gauss_levels_decode(const int32_t* sym, int ld_sym, const uint8_t* layer
                             const int* ks, int n_levels, float* yhat, int ld_yhat, long yhat_ls, long n_pix, int C,
                             void* stream);
 
+/* Rate control (VarianceMaskingPIC.rate_curve / qualities_for_bpp): the rate of up to
+ * VAM_MAX_LAYER_LEVELS qualities from ONE pass over the progressive windows vam_gauss_levels_eval reads, with the layer
+ * ids of vam_variance_layers in place of masks.  Per element lk = L(|round(r-mu)|, sigma), r = y - y2: masked_tail /
+ * gauss_lik with m = 1, the float vam_gauss_levels_eval gets for an element INSIDE a mask, bit for bit.  Per item
+ * (pix_per_item consecutive pixels; it must divide n_pix):
+ *   bits [item * (n_levels+1) + k] += sum of log2((double)lk) over the item's elements with layer == k   (fp64)
+ *   count[item * (n_levels+1) + k] += the number of such elements
+ * for k < n_levels; slot n_levels takes layer == 0xFF (and any id >= n_levels).  Both ACCUMULATE (fp64 / 64-bit atomics)
+ * and are cleared by the caller, as log2sum is.  An element outside a mask contributes the constant log2 L(0, 0) at
+ * every quality, so the list's level k sums to  sum_{j<=k} bits_j + (n - sum_{j<=k} count_j) * log2 L(0, 0);  the
+ * constant is what this call writes to bits[0] for one element with y = mu = sigma = 0 and layer 0.  Each tensor is
+ * read once, nothing else is written; no float32 accumulation.  layer: one uint8 per element, pixel stride ld_layer
+ * (a multiple of 4, 4-byte aligned); y, y2 (may be NULL), mu, sigma as in vam_gauss_levels_eval. */
+int vam_gauss_layer_bits(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const uint8_t* layer, int ld_layer, int n_levels,
+                         double* bits, long long* count, int pix_per_item, long n_pix, int C, void* stream);
+
 /* GaussianConditional.build_indexes (entropy_models.py:654-659): idx = 63 - #{i<63: max(s,.11) <= T_i}
  * table: 64 floats (device). mask (may be NULL) multiplies sigma first (pic.py:809). */
 int vam_build_indexes(const float* sigma, int ld_sigma, const float* mask, int ld_mask,
