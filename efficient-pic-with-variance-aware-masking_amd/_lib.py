@@ -51,6 +51,18 @@ class VamRansStream(C.Structure):
                 ("n_bytes", C.c_long)]
 
 
+class VamLayerParams(C.Structure):
+    """vam_layer_params: one image's record of the device table of vam_variance_layers_per_image."""
+    _fields_ = [("n_levels", C.c_int32), ("any_select", C.c_int32), ("k_lo", C.c_int32 * VAM_MAX_LAYER_LEVELS),
+                ("k_hi", C.c_int32 * VAM_MAX_LAYER_LEVELS), ("w", C.c_float * VAM_MAX_LAYER_LEVELS),
+                ("mode", C.c_int32 * VAM_MAX_LAYER_LEVELS)]
+
+
+class VamCoderTables(C.Structure):
+    """vam_coder_tables: the coder's tables on the device (bitstream.DeviceTables)."""
+    _fields_ = [("cost", C.c_void_p), ("sizes", C.c_void_p), ("offsets", C.c_void_p), ("n_cdfs", C.c_int32), ("stride", C.c_int32)]
+
+
 class VamWgrad(C.Structure):
     _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
                 ("ld_x", C.c_int), ("ld_dy", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -151,6 +163,15 @@ _SIGNATURES = {
                                            C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_variance_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_layer_params_size": (C.c_size_t, []),
+    "vam_variance_layer_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vam_variance_layers_per_image": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_coded_layer_bits": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_int, C.c_void_p, C.c_int, C.POINTER(VamCoderTables), C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
+    "vam_coded_symbol_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.POINTER(VamCoderTables), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int,
+                                        C.c_void_p]),
     "vam_gauss_levels_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_void_p]),
     "vam_gauss_tail": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_void_p, C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
@@ -237,6 +258,8 @@ def load():
         fn.argtypes = args
     if lib.vam_conv_struct_size() != C.sizeof(VamConv):
         raise VamError(f"ABI mismatch: sizeof(vam_conv) is {lib.vam_conv_struct_size()} in libvampic.so, {C.sizeof(VamConv)} in the binding")
+    if lib.vam_layer_params_size() != C.sizeof(VamLayerParams):
+        raise VamError(f"ABI mismatch: sizeof(vam_layer_params) is {lib.vam_layer_params_size()} in libvampic.so, {C.sizeof(VamLayerParams)} in the binding")
     if lib.vam_resunit_struct_size() != C.sizeof(VamResunit):
         raise VamError(f"ABI mismatch: sizeof(vam_resunit) is {lib.vam_resunit_struct_size()} in libvampic.so, {C.sizeof(VamResunit)} in the binding")
     _lib = lib

@@ -121,3 +121,109 @@ def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = No
     L.check(L.load().vam_rans_decode_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
                                              t.offsets.ctypes.data, t.cdf.shape[0],
                                              coder_threads() if threads is None else int(threads)), "vam_rans_decode_streams")
+
+
+# ---------------------------------------------------------------- coded-size pricing
+LOG2E = 1.4426950408889634
+MAX_BYPASS = 8            # raw nibbles of one out-of-range value (a 32-bit raw value; csrc/rans.cpp)
+
+
+def cost_table(t: Tables) -> np.ndarray:
+    """float64 [n, stride]: what the coder charges for entry v of table i, 16 - log2(cdf[i][v+1] - cdf[i][v]) bits, for
+    v <= sizes[i] - 2 (entry sizes[i] - 2 is the escape); 0 beyond.  Tables the coder itself would refuse are refused."""
+    cdf = t.cdf.astype(np.int64)
+    n, stride = cdf.shape
+    mx = t.sizes.astype(np.int64) - 2
+    if (mx < 0).any() or (mx + 1 >= stride).any():
+        raise ValueError(f"cdf sizes {t.sizes.tolist()} invalid for tables of stride {stride}")
+    used = np.arange(stride - 1)[None, :] <= mx[:, None]
+    freq = np.where(used, cdf[:, 1:] - cdf[:, :-1], 1)
+    if (freq <= 0).any():
+        raise ValueError("zero-frequency symbol (cdf table not normalised)")
+    out = np.zeros((n, stride), dtype=np.float64)
+    out[:, :-1] = np.where(used, 16.0 - np.log2(freq.astype(np.float64)), 0.0)
+    return out
+
+
+def price(symbols, indexes, t: Tables, layer=None, sel: int = 0, cost: Optional[np.ndarray] = None) -> np.ndarray:
+    """The exact price in bits of every element of a stream as :func:`encode` / :func:`encode_streams` code it (with a
+    ``layer`` array: symbol 0 in table 0 where layer != sel), float64 of the symbols' shape: the table entry's
+    16 - log2(freq), and for a value outside the table the escape entry plus 4 * (1 + n_bypass) bits (one count nibble and
+    n_bypass <= 8 raw nibbles).  The host statement of what vam_coded_layer_bits computes on the device."""
+    s = np.asarray(symbols).astype(np.int64)
+    i = np.broadcast_to(np.asarray(indexes), s.shape).astype(np.int64)
+    if layer is not None:
+        keep = np.asarray(layer) == sel
+        s, i = np.where(keep, s, 0), np.where(keep, i, 0)
+    if i.size and (i.min() < 0 or i.max() >= t.cdf.shape[0]):
+        raise ValueError("index out of range")
+    cost = cost_table(t) if cost is None else cost
+    mx = t.sizes.astype(np.int64)[i] - 2
+    v = s - t.offsets.astype(np.int64)[i]
+    inside = (v >= 0) & (v < mx)
+    raw = np.where(v < 0, -2 * v - 1, 2 * (v - mx)) & 0xFFFFFFFF
+    nb = np.zeros(s.shape, dtype=np.int64)
+    for k in range(MAX_BYPASS):
+        nb += (raw >> (4 * k)) != 0
+    return np.where(inside, cost[i, np.where(inside, v, 0)], cost[i, mx] + 4.0 * (1 + nb))
+
+
+def stream_words(bits, n_symbols):
+    """(lo, hi) bounds of the number W of 32-bit words a stream flushes before its final state, from its exact table cost
+    ``bits`` (S) and its number of symbols n.  The coder's state obeys 32 W + log2(x_final) = 31 + S + e with log2(x_final)
+    in [31, 63), so W = floor((S + e) / 32).  Every symbol put maps x to floor(x / f) * 2^16 + x % f + start with
+    floor(x / f) >= 2^15 (renormalisation included: floor(floor(u) / f) = floor(u / f)), so it moves log2 x by
+    16 - log2 f up to log2(1 + 2^-15); a bypass nibble shifts a state >= 2^27 by four bits: up to log2(1 + 2^-27), at most
+    9 nibbles per symbol.  Hence |e| <= n * log2(e) * (2^-15 + 9 * 2^-27); the float64 rounding of S itself gets
+    S * 2^-36 + 2^-30 on top.  lo == hi unless S is that close to a multiple of 32."""
+    S = np.asarray(bits, dtype=np.float64)
+    n = np.asarray(n_symbols, dtype=np.float64)
+    e = n * LOG2E * (2.0 ** -15 + 9.0 * 2.0 ** -27) + S * 2.0 ** -36 + 2.0 ** -30
+    lo = np.floor((S - e) / 32.0).astype(np.int64)
+    hi = np.floor((S + e) / 32.0).astype(np.int64)
+    return np.maximum(lo, 0), np.maximum(hi, 0)
+
+
+def stream_bytes(bits, n_symbols):
+    """(lo, hi) bounds of a stream's length in bytes: 8 (the final 64-bit state) + 4 W (:func:`stream_words`).  The two
+    are equal or 4 apart for streams of up to about 3e5 symbols."""
+    lo, hi = stream_words(bits, n_symbols)
+    return 8 + 4 * lo, 8 + 4 * hi
+
+
+@dataclass
+class DeviceTables:
+    """The device-side companion of :class:`Tables` for the pricing kernels: the float64 cost table (16 - log2(freq), built
+    once on the host from the int32 CDFs), sizes and offsets, and the constants an element outside the variance mask costs:
+    ``zero_cost[i]`` = the price of symbol 0 under table i (a container layer codes 0 in table 0, compress(x, q) codes 0
+    at the index build_indexes gives sigma = 0)."""
+    host: Tables
+    cost: torch.Tensor        # float64 [n, stride]
+    sizes: torch.Tensor       # int32 [n]
+    offsets: torch.Tensor     # int32 [n]
+    zero_cost: np.ndarray     # float64 [n]
+    struct: "L.VamCoderTables"
+    key: tuple = ()           # the generation key of ``host`` and the device
+
+    def __deepcopy__(self, memo):
+        return None           # device pointers of THIS model: a copied model builds its own at its first use
+
+    @staticmethod
+    def of(model, device) -> "DeviceTables":
+        t = Tables.of(model)
+        key = (model._tables_key, str(torch.device(device)))
+        d = getattr(model, "_device_tables", None)
+        if d is None or d.key != key:
+            c = cost_table(t)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            d = DeviceTables(t, dev(c), dev(t.sizes), dev(t.offsets),
+                             price(np.zeros(t.cdf.shape[0], dtype=np.int64), np.arange(t.cdf.shape[0]), t, cost=c), None, key)
+            d.struct = L.VamCoderTables(d.cost.data_ptr(), d.sizes.data_ptr(), d.offsets.data_ptr(), t.cdf.shape[0], t.cdf.shape[1])
+            object.__setattr__(model, "_device_tables", d)
+        return d
+
+
+def sigma0_index(scale_table) -> int:
+    """The table index build_indexes gives sigma = 0 (the 0.11 bound applies), in float32 as the kernel compares."""
+    tb = np.asarray(torch.as_tensor(scale_table).detach().cpu().numpy(), dtype=np.float32)
+    return int(tb.size - 1 - np.count_nonzero(np.float32(0.11) <= tb[:-1]))

@@ -323,6 +323,15 @@ __global__ __launch_bounds__(256) void gauss_layer_bits_kernel(const LayerBitsAr
 }
 
 // ------------------------------------------------------------------ build_indexes
+// entropy_models.py:654-659 for one scale: n_table - 1 - #{t < n_table - 1: max(s, .11) <= T_t}.  Shared by
+// build_indexes_kernel and the pricing kernel (coded_bits_kernel), which must name the same table.
+__device__ __forceinline__ int scale_index(float s, const float* tbl, int n_table) {
+  float v = fmaxf(s, 0.11f);
+  int cnt = 0;
+  for (int t = 0; t < n_table - 1; ++t) cnt += (v <= tbl[t]) ? 1 : 0;   // entropy_models.py:657-658
+  return n_table - 1 - cnt;
+}
+
 __global__ void build_indexes_kernel(const float* __restrict__ sigma, int ld_sigma, const float* __restrict__ mask,
                                      int ld_mask, const float* __restrict__ table, int n_table,
                                      int32_t* __restrict__ idx, int ld_idx, long n_vec, int C4) {
@@ -340,13 +349,117 @@ __global__ void build_indexes_kernel(const float* __restrict__ sigma, int ld_sig
     }
     int r[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = fmaxf(s[k], 0.11f);
-      int cnt = 0;
-      for (int t = 0; t < n_table - 1; ++t) cnt += (v <= tbl[t]) ? 1 : 0;   // entropy_models.py:657-658
-      r[k] = n_table - 1 - cnt;
-    }
+    for (int k = 0; k < 4; ++k) r[k] = scale_index(s[k], tbl, n_table);
     *reinterpret_cast<int4*>(idx + p * ld_idx + c) = make_int4(r[0], r[1], r[2], r[3]);
+  }
+}
+
+// ------------------------------------------------------------------ coded-size pricing
+// What encode_one (csrc/rans.cpp) charges for `symbol` under table t: 16 - log2(freq) of the entry it codes, and for a
+// value outside the table the escape entry plus one count nibble and n_bypass <= 8 raw nibbles (enc_put_bits).
+struct CoderTables {
+  const double* cost;
+  const int32_t *sizes, *offsets;
+  int n_cdfs, stride;
+};
+
+__device__ __forceinline__ double symbol_cost(int symbol, int t, const CoderTables& T) {
+  if (t < 0 || t >= T.n_cdfs) return __longlong_as_double(0x7FF8000000000000LL);
+  int max_value = T.sizes[t] - 2;
+  max_value = max_value < 0 ? 0 : (max_value >= T.stride ? T.stride - 1 : max_value);   // the host builder rejects such tables
+  long long value = (long long)symbol - (long long)T.offsets[t];
+  const double* row = T.cost + (long)t * T.stride;
+  if (value >= 0 && value < max_value) return row[value];
+  const unsigned raw = value < 0 ? (unsigned)(-2 * value - 1) : (unsigned)(2 * (value - max_value));
+  int n_bypass = 0;
+  while (n_bypass < 8 && (raw >> (n_bypass * 4)) != 0u) ++n_bypass;
+  return row[max_value] + 4.0 * (double)(1 + n_bypass);
+}
+
+struct CodedBitsArgs {
+  const float *y, *y2, *mu, *sigma, *scale_table;
+  const int32_t *sym, *idx;
+  const uint8_t* layer;
+  double* bits;
+  long long* count;
+  CoderTables T;
+  int ld_y, ld_y2, ld_mu, ld_sigma, ld_sym, ld_idx, ld_layer, idx_base, n_table;
+  int n_levels, S4, n_slices, blocks_per_stream, pix_per_item;
+  long vec_per_stream;   // pix_per_item * S4
+};
+
+// One workgroup stays inside one stream (item, slice of 4 * S4 channels); bins as in gauss_layer_bits_kernel: a row of
+// n_levels + 1 fp64 sums and counts per wave in LDS, one global atomic per non-empty bin.  SYMS: the (symbol, index) pair
+// is read; else it is derived from (y, y2, mu, sigma) with masked_tail (m = 1) and scale_index.
+template <bool SYMS>
+__global__ __launch_bounds__(256) void coded_bits_kernel(const CodedBitsArgs a) {
+  __shared__ double sh_bits[4][LAYER_BINS];
+  __shared__ unsigned sh_cnt[4][LAYER_BINS];
+  __shared__ float tbl[256];
+  const int nb = a.n_levels + 1;                           // slot n_levels: layer == 0xFF
+  const int stream = blockIdx.x / a.blocks_per_stream, blk = blockIdx.x - stream * a.blocks_per_stream;
+  const int item = stream / a.n_slices, slice = stream - item * a.n_slices;
+  const int wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < 4 * LAYER_BINS; i += 256) {
+    (&sh_bits[0][0])[i] = 0.0;
+    (&sh_cnt[0][0])[i] = 0u;
+  }
+  if (!SYMS)
+    for (int i = threadIdx.x; i < a.n_table; i += 256) tbl[i] = a.scale_table[i];
+  __syncthreads();
+  const long p0 = (long)item * a.pix_per_item;
+  const int c0 = slice * a.S4 * 4;
+  for (long j = (long)blk * 256 + threadIdx.x; j < a.vec_per_stream; j += (long)a.blocks_per_stream * 256) {
+    const long pp = j / a.S4;
+    const long p = p0 + pp;
+    const int c = c0 + (int)(j - pp * a.S4) * 4;
+    int sy[4], ix[4];
+    if (SYMS) {
+      const int4 s4 = *reinterpret_cast<const int4*>(a.sym + p * a.ld_sym + c);
+      sy[0] = s4.x; sy[1] = s4.y; sy[2] = s4.z; sy[3] = s4.w;
+      if (a.idx) {
+        const int4 i4 = *reinterpret_cast<const int4*>(a.idx + p * a.ld_idx + c);
+        ix[0] = i4.x; ix[1] = i4.y; ix[2] = i4.z; ix[3] = i4.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ix[k] = a.idx_base + c + k;
+      }
+    } else {
+      float4 y = *reinterpret_cast<const float4*>(a.y + p * a.ld_y + c);
+      if (a.y2) {
+        float4 y2 = *reinterpret_cast<const float4*>(a.y2 + p * a.ld_y2 + c);
+        y.x -= y2.x; y.y -= y2.y; y.z -= y2.z; y.w -= y2.w;            // pic.py:583-584
+      }
+      float4 mu = *reinterpret_cast<const float4*>(a.mu + p * a.ld_mu + c);
+      float4 sg = *reinterpret_cast<const float4*>(a.sigma + p * a.ld_sigma + c);
+      float yv[4] = {y.x, y.y, y.z, y.w}, mv[4] = {mu.x, mu.y, mu.z, mu.w}, sv[4] = {sg.x, sg.y, sg.z, sg.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float d = yv[k] - mv[k];
+        float q = rintf(d);                         // torch.round = half-to-even
+        float yh, absv, s;
+        masked_tail(d, q, mv[k], sv[k], 1.f, yh, absv, s, sy[k]);
+        ix[k] = scale_index(s, tbl, a.n_table);
+      }
+    }
+    const unsigned ly = a.layer ? *reinterpret_cast<const unsigned*>(a.layer + p * a.ld_layer + c) : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int l = (int)((ly >> (8 * k)) & 255u);
+      const int bin = l < a.n_levels ? l : a.n_levels;     // 0xFF (and any id beyond the list) -> the last slot
+      __hip_atomic_fetch_add(&sh_bits[wave][bin], symbol_cost(sy[k], ix[k], a.T), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&sh_cnt[wave][bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < nb) {
+    const unsigned n = sh_cnt[0][t] + sh_cnt[1][t] + sh_cnt[2][t] + sh_cnt[3][t];
+    if (n) {
+      const double v = (sh_bits[0][t] + sh_bits[1][t]) + (sh_bits[2][t] + sh_bits[3][t]);
+      atomicAdd(a.bits + (long)stream * nb + t, v);
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.count) + (long)stream * nb + t, (unsigned long long)n);
+    }
   }
 }
 
@@ -682,6 +795,71 @@ int vam_build_indexes(const float* sigma, int ld_sigma, const float* mask, int l
   hipLaunchKernelGGL(build_indexes_kernel, dim3(stream_grid(n_vec, 256)), dim3(256), 0, (hipStream_t)stream, sigma,
                      ld_sigma, mask, ld_mask, table, n_table, idx, ld_idx, n_vec, C / 4);
   return check_launch("build_indexes_kernel");
+}
+
+static int coded_bits_launch(CodedBitsArgs& a, const char* who, const vam_coder_tables* tables, const uint8_t* layer,
+                             int ld_layer, int n_levels, int chans_per_stream, double* bits, long long* count,
+                             int pix_per_item, long n_pix, int C, bool syms, double bytes_per_elem, void* stream) {
+  VAM_REQUIRE(tables && tables->cost && tables->sizes && tables->offsets && bits && count, "%s: tables, bits and count must not be NULL", who);
+  VAM_REQUIRE(tables->n_cdfs >= 1 && tables->stride >= 2, "%s: %d tables of stride %d", who, tables->n_cdfs, tables->stride);
+  VAM_REQUIRE(n_pix > 0 && C > 0 && C % 4 == 0, "%s: need n_pix > 0 and C %% 4 == 0", who);
+  VAM_REQUIRE(chans_per_stream > 0 && chans_per_stream % 4 == 0 && C % chans_per_stream == 0,
+              "%s: chans_per_stream %d must be a multiple of 4 that divides C = %d", who, chans_per_stream, C);
+  VAM_REQUIRE(n_levels >= 1 && n_levels <= VAM_MAX_LAYER_LEVELS, "%s: 1..%d levels, got %d", who, VAM_MAX_LAYER_LEVELS, n_levels);
+  VAM_REQUIRE(pix_per_item > 0 && n_pix % pix_per_item == 0, "%s: pix_per_item must divide n_pix", who);
+  VAM_REQUIRE((long)pix_per_item * C < (1L << 31) && n_pix / pix_per_item * (C / chans_per_stream) < (1L << 20), "%s: item too large", who);
+  VAM_REQUIRE((((uintptr_t)layer) & 3) == 0 && (((uintptr_t)bits) & 7) == 0 && (((uintptr_t)count) & 7) == 0 &&
+              (((uintptr_t)tables->cost) & 7) == 0 && (!layer || (ld_layer % 4 == 0 && ld_layer >= C)), "%s: alignment / layer stride", who);
+  a.layer = layer; a.ld_layer = ld_layer; a.bits = bits; a.count = count;
+  a.T.cost = tables->cost; a.T.sizes = tables->sizes; a.T.offsets = tables->offsets;
+  a.T.n_cdfs = tables->n_cdfs; a.T.stride = tables->stride;
+  a.n_levels = n_levels; a.S4 = chans_per_stream / 4; a.n_slices = C / chans_per_stream; a.pix_per_item = pix_per_item;
+  a.vec_per_stream = (long)pix_per_item * a.S4;
+  const long n_streams = n_pix / pix_per_item * a.n_slices;
+  // a workgroup stays inside one stream; about two vectors per lane, and no more than ~2048 workgroups in all
+  long per = cdiv(a.vec_per_stream, 512L);
+  const long room = n_streams >= 2048 ? 1 : 2048 / n_streams;
+  if (per > room) per = room;
+  if (per < 1) per = 1;
+  a.blocks_per_stream = (int)per;
+  ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, (double)n_pix * C * bytes_per_elem);
+  if (syms)
+    hipLaunchKernelGGL(coded_bits_kernel<true>, dim3((unsigned)(n_streams * per)), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(coded_bits_kernel<false>, dim3((unsigned)(n_streams * per)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("coded_bits_kernel");
+}
+
+int vam_coded_layer_bits(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const uint8_t* layer, int ld_layer, int n_levels,
+                         const float* scale_table, int n_table, const vam_coder_tables* tables, int chans_per_stream,
+                         double* bits, long long* count, int pix_per_item, long n_pix, int C, void* stream) {
+  VAM_REQUIRE(y && mu && sigma && scale_table, "vam_coded_layer_bits: y, mu, sigma and scale_table must not be NULL");
+  VAM_REQUIRE(n_table >= 2 && n_table <= 256 && tables && n_table <= tables->n_cdfs,
+              "vam_coded_layer_bits: scale table of %d entries (2..256, at most one per coder table)", n_table);
+  VAM_REQUIRE(al16(y) && al16(mu) && al16(sigma) && al16(y2), "vam_coded_layer_bits: 16-byte alignment");
+  VAM_REQUIRE(ld_y % 4 == 0 && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && (!y2 || ld_y2 % 4 == 0) && ld_y >= C && ld_mu >= C &&
+              ld_sigma >= C && (!y2 || ld_y2 >= C), "vam_coded_layer_bits: pixel strides must be multiples of 4 and >= C");
+  CodedBitsArgs a = {};
+  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.scale_table = scale_table; a.n_table = n_table;
+  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma;
+  return coded_bits_launch(a, "vam_coded_layer_bits", tables, layer, ld_layer, n_levels, chans_per_stream, bits, count,
+                           pix_per_item, n_pix, C, false, (y2 ? 16.0 : 12.0) + (layer ? 1.0 : 0.0), stream);
+}
+
+int vam_coded_symbol_bits(const int32_t* sym, int ld_sym, const int32_t* idx, int ld_idx, int idx_base,
+                          const uint8_t* layer, int ld_layer, int n_levels, const vam_coder_tables* tables,
+                          int chans_per_stream, double* bits, long long* count, int pix_per_item, long n_pix, int C,
+                          void* stream) {
+  VAM_REQUIRE(sym && al16(sym) && al16(idx), "vam_coded_symbol_bits: sym must not be NULL; 16-byte alignment");
+  VAM_REQUIRE(ld_sym % 4 == 0 && ld_sym >= C && (!idx || (ld_idx % 4 == 0 && ld_idx >= C)),
+              "vam_coded_symbol_bits: pixel strides must be multiples of 4 and >= C");
+  VAM_REQUIRE(idx || (tables && idx_base >= 0 && (long)idx_base + C <= tables->n_cdfs),
+              "vam_coded_symbol_bits: without idx the channels idx_base .. idx_base + C must name tables");
+  CodedBitsArgs a = {};
+  a.sym = sym; a.idx = idx; a.ld_sym = ld_sym; a.ld_idx = ld_idx; a.idx_base = idx_base;
+  return coded_bits_launch(a, "vam_coded_symbol_bits", tables, layer, ld_layer, n_levels, chans_per_stream, bits, count,
+                           pix_per_item, n_pix, C, true, (idx ? 8.0 : 4.0) + (layer ? 1.0 : 0.0), stream);
 }
 
 int vam_eb_forward(const float* z, int ld_z, const float* params, int C, float* zhat, int ld_zhat, float* lik,

@@ -13,6 +13,7 @@
 // traffic is the algorithmic 4 B read + 4 B written per element.  Histograms live in LDS.
 #include "common.h"
 #include <cmath>
+#include <cstring>
 
 namespace vam {
 
@@ -198,11 +199,46 @@ struct MaskLevelsArgs {
   int mode[VAM_MAX_LAYER_LEVELS];    // 0 = quantile, 1 = all zero (pr == 0), 2 = all one (pr >= 10)
 };
 
+// vam_variance_layers_per_image: the strides of MaskLevelsArgs, and the per-level fields from a device table with one
+// record per image (a list of 32 qualities per image does not fit the kernel arguments of a batch)
+struct MaskImageArgs {
+  const float* sigma;
+  float* thr;
+  uint8_t* layer;
+  const vam_layer_params* table;
+  long batch_stride, slice_stride, mask_batch_stride, mask_slice_stride;
+  int ld, ld_mask, n_slice, n_pix, C4;
+};
+
+// the per-level fields of the two argument kinds of variance_mask_levels_kernel
+__device__ __forceinline__ int lv_count(const MaskLevelsArgs& a, int) { return a.n_levels; }
+__device__ __forceinline__ int lv_any_select(const MaskLevelsArgs& a, int) { return a.any_select; }
+__device__ __forceinline__ int lv_mode(const MaskLevelsArgs& a, int, int lv) { return a.mode[lv]; }
+__device__ __forceinline__ int lv_k_lo(const MaskLevelsArgs& a, int, int lv) { return a.k_lo[lv]; }
+__device__ __forceinline__ int lv_k_hi(const MaskLevelsArgs& a, int, int lv) { return a.k_hi[lv]; }
+__device__ __forceinline__ float lv_w(const MaskLevelsArgs& a, int, int lv) { return a.w[lv]; }
+__device__ __forceinline__ float* lv_mask(const MaskLevelsArgs& a) { return a.mask; }
+__device__ __forceinline__ long lv_stride(const MaskLevelsArgs& a) { return a.mask_level_stride; }
+__device__ __forceinline__ int lv_count(const MaskImageArgs& a, int b) {
+  const int n = a.table[b].n_levels;                      // the host validates the table; a bad record selects nothing
+  return n < 0 || n > VAM_MAX_LAYER_LEVELS ? 0 : n;
+}
+__device__ __forceinline__ int lv_any_select(const MaskImageArgs& a, int b) { return a.table[b].any_select; }
+__device__ __forceinline__ int lv_mode(const MaskImageArgs& a, int b, int lv) { return a.table[b].mode[lv]; }
+__device__ __forceinline__ int lv_k_lo(const MaskImageArgs& a, int b, int lv) { return a.table[b].k_lo[lv]; }
+__device__ __forceinline__ int lv_k_hi(const MaskImageArgs& a, int b, int lv) { return a.table[b].k_hi[lv]; }
+__device__ __forceinline__ float lv_w(const MaskImageArgs& a, int b, int lv) { return a.table[b].w[lv]; }
+__device__ __forceinline__ float* lv_mask(const MaskImageArgs&) { return nullptr; }
+__device__ __forceinline__ long lv_stride(const MaskImageArgs&) { return 0L; }
+
 // MAXV = float4 per thread kept in registers (0 = stream from memory every pass).  The segment is loaded once; each level
 // then runs its own selection on the same registers and writes its own mask.  LAYERS: the levels' thresholds stay in
 // LDS, and one last pass writes layer = the first level whose mask holds the element (mask_* name the layer array).
-template <int MAXV, bool LAYERS>
-__global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLevelsArgs a) {
+// Args: MaskLevelsArgs (one quality list in the kernel arguments) or MaskImageArgs (vam_variance_layers_per_image: image
+// b's record of a device table); the per-level fields are read through the lv_* accessors above, so the first kind
+// compiles to the accesses it always made.
+template <int MAXV, bool LAYERS, class Args = MaskLevelsArgs>
+__global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const Args a) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sh_prefix, sh_k, sh_cnt, sh_min;
   __shared__ int sh_nan;
@@ -212,7 +248,7 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
   const int segs = gridDim.x;
   const int b = seg / a.n_slice, j = seg - b * a.n_slice;
   const float* src = a.sigma + b * a.batch_stride + j * a.slice_stride;
-  float* const dst0 = a.mask + b * a.mask_batch_stride + j * a.mask_slice_stride;
+  float* const dst0 = lv_mask(a) + b * a.mask_batch_stride + j * a.mask_slice_stride;
   const int nvec = a.n_pix * a.C4;
   const int tid = threadIdx.x;
 
@@ -248,7 +284,7 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
     }
   };
 
-  if (a.any_select) {
+  if (lv_any_select(a, b)) {
     if (tid == 0) sh_nan = 0;
     __syncthreads();
     int nan = 0;
@@ -256,18 +292,18 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
     if (nan) atomicOr(&sh_nan, 1);
   }
 
-  for (int lv = 0; lv < a.n_levels; ++lv) {
-    float* dst = dst0 + lv * a.mask_level_stride;
+  for (int lv = 0; lv < lv_count(a, b); ++lv) {
+    float* dst = dst0 + lv * lv_stride(a);
     float* thr_out = a.thr ? a.thr + (long)lv * segs : nullptr;
-    if (a.mode[lv] != 0) {
-      const float v = a.mode[lv] == 2 ? 1.f : 0.f;
+    if (lv_mode(a, b, lv) != 0) {
+      const float v = lv_mode(a, b, lv) == 2 ? 1.f : 0.f;
       if (!LAYERS)
         for (int i = tid; i < nvec; i += 1024) *reinterpret_cast<float4*>(out_ptr(dst, i)) = make_float4(v, v, v, v);
-      if (tid == 0 && thr_out) thr_out[seg] = a.mode[lv] == 2 ? -INFINITY : INFINITY;
+      if (tid == 0 && thr_out) thr_out[seg] = lv_mode(a, b, lv) == 2 ? -INFINITY : INFINITY;
       continue;
     }
-    const int k_lo = a.k_lo[lv], k_hi = a.k_hi[lv];
-    const float w = a.w[lv];
+    const int k_lo = lv_k_lo(a, b, lv), k_hi = lv_k_hi(a, b, lv);
+    const float w = lv_w(a, b, lv);
     __syncthreads();              // the previous level's readers of sh_prefix / sh_cnt / sh_min are done
 
     // ---- radix select of rank k_lo (ascending, 0-based)
@@ -364,8 +400,8 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const MaskLe
   __syncthreads();
   uint8_t* const ldst = a.layer + b * a.mask_batch_stride + j * a.mask_slice_stride;
   auto layer_of = [&](float x) -> unsigned {
-    for (int lv = 0; lv < a.n_levels; ++lv) {
-      const int md = a.mode[lv];
+    for (int lv = 0; lv < lv_count(a, b); ++lv) {
+      const int md = lv_mode(a, b, lv);
       if (md == 2 || (md == 0 && x >= sh_thr[lv])) return (unsigned)lv;
     }
     return 0xFFu;
@@ -527,4 +563,62 @@ extern "C" int vam_variance_layers(const float* sigma, int ld, long batch_stride
   VAM_REQUIRE(layer_out, "vam_variance_layers: layer_out is NULL");
   return mask_launch(sigma, ld, batch_stride, slice_stride, n_batch, n_slice, n_pix, C, prs, n_levels, nullptr, layer_out,
                      ld_layer, layer_batch_stride, layer_slice_stride, 0, thr_out, stream);
+}
+
+extern "C" size_t vam_layer_params_size(void) { return sizeof(vam_layer_params); }
+
+extern "C" int vam_variance_layer_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix,
+                                         int C, vam_layer_params* table_host) {
+  VAM_REQUIRE(prs && n_levels && table_host && n_batch > 0 && levels_stride >= 1 && n_pix > 0 && C > 0,
+              "vam_variance_layer_params: bad arguments");
+  const long n = (long)n_pix * C;
+  VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
+  MaskLevelsArgs a;                              // mask_level_params' own arithmetic, one image at a time
+  for (int b = 0; b < n_batch; ++b) {
+    const int nl = n_levels[b];
+    const double* p = prs + (long)b * levels_stride;
+    VAM_REQUIRE(nl >= 1 && nl <= VAM_MAX_LAYER_LEVELS && nl <= levels_stride, "vam_variance_layers_per_image: image %d: 1..%d levels, got %d",
+                b, VAM_MAX_LAYER_LEVELS, nl);
+    vam_layer_params& t = table_host[b];
+    std::memset(&t, 0, sizeof(t));
+    t.n_levels = nl;
+    for (int lv = 0; lv < nl; ++lv) {
+      VAM_REQUIRE(lv == 0 || p[lv] >= p[lv - 1], "vam_variance_layers_per_image: image %d: qualities must be non-decreasing (prs[%d] < prs[%d])",
+                  b, lv, lv - 1);
+      const int rc = mask_level_params(a, lv, p[lv], n);
+      if (rc) return rc;
+      t.k_lo[lv] = a.k_lo[lv]; t.k_hi[lv] = a.k_hi[lv]; t.w[lv] = a.w[lv]; t.mode[lv] = a.mode[lv];
+      t.any_select |= a.mode[lv] == 0;
+    }
+  }
+  return VAM_OK;
+}
+
+extern "C" int vam_variance_layers_per_image(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch,
+                                             int n_slice, int n_pix, int C, const vam_layer_params* table_dev,
+                                             uint8_t* layer_out, int ld_layer, long layer_batch_stride,
+                                             long layer_slice_stride, float* thr_out, void* stream) {
+  VAM_REQUIRE(sigma && table_dev && layer_out && n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "vam_variance_layers_per_image: bad arguments");
+  VAM_REQUIRE(C % 4 == 0 && ld % 4 == 0 && ld_layer % 4 == 0 && batch_stride % 4 == 0 && slice_stride % 4 == 0 && layer_batch_stride % 4 == 0 && layer_slice_stride % 4 == 0, "vam_variance_layers_per_image: C and strides must be multiples of 4");
+  VAM_REQUIRE((((uintptr_t)sigma) & 15) == 0 && (((uintptr_t)layer_out) & 3) == 0 && (((uintptr_t)table_dev) & 3) == 0,
+              "vam_variance_layers_per_image: 16-byte alignment (layers, table: 4-byte)");
+  VAM_REQUIRE(ld >= C && ld_layer >= C, "vam_variance_layers_per_image: pixel stride < C");
+  const long n = (long)n_pix * C;
+  VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
+  MaskImageArgs a;
+  a.sigma = sigma; a.thr = thr_out; a.layer = layer_out; a.table = table_dev;
+  a.batch_stride = batch_stride; a.slice_stride = slice_stride;
+  a.mask_batch_stride = layer_batch_stride; a.mask_slice_stride = layer_slice_stride;
+  a.ld = ld; a.ld_mask = ld_layer; a.n_slice = n_slice; a.n_pix = n_pix; a.C4 = C / 4;
+  const int segs = n_batch * n_slice;
+  const int nvec = n_pix * (C / 4);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(VAM_FAM_MASK, s, 0, 5.0 * (double)n * segs);
+  if (nvec <= 4 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<4, true, MaskImageArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else if (nvec <= 16 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<16, true, MaskImageArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else
+    hipLaunchKernelGGL((variance_mask_levels_kernel<0, true, MaskImageArgs>), dim3(segs), dim3(1024), 0, s, a);
+  return check_launch("variance_layers_per_image_kernel");
 }

@@ -125,6 +125,22 @@ def rd_at_rates(model, x: torch.Tensor, target_bpps):
     return bpp, psnr, q, sol["reached"]
 
 
+def rd_at_sizes(model, x: torch.Tensor, target_bytes):
+    """Coded size and distortion at byte budgets, the analogue of :func:`rd_at_rates`: the qualities are resolved once for
+    the batch (VarianceMaskingPIC.qualities_for_bytes: per image the largest quality whose compress strings are guaranteed
+    to fit each budget), then every image is evaluated at its own qualities.  ``target_bytes``: T numbers or a [T, B]
+    tensor.  Returns (bytes, psnr, quality, reached), [T, B] host tensors: ``bytes`` the guaranteed upper size at that
+    quality; where ``reached`` is False (even the base exceeds the budget) the row holds the base (quality 0)."""
+    dev = next(model.parameters()).device
+    x = x.to(dev).contiguous()
+    sol = model.qualities_for_bytes(x, target_bytes)
+    q = sol["quality"]
+    psnr = torch.zeros_like(q)
+    for b in range(x.shape[0]):
+        psnr[:, b] = rd_sweep(model, x[b:b + 1], q[:, b].tolist())[1][:, 0]
+    return sol["bytes"], psnr, q, sol["reached"]
+
+
 def _checkpoint_for(model, x, p):
     """training/step.py:13-29 extract_quality_ref + ExtractChekpointRepr (REM models only)."""
     levels = getattr(model, "check_levels", None)

@@ -555,6 +555,121 @@ class VarianceMaskingPIC(CompressionModel):
                     quality[:, i0:i1], bpp[:, i0:i1], reached[:, i0:i1] = rate_search(curve, bpp0, tg[:, i0:i1], q_tol)
         return {"quality": torch.from_numpy(quality), "bpp": torch.from_numpy(bpp), "reached": torch.from_numpy(reached)}
 
+    # ---- coded-size control: the bytes of compress(x, q) without masks, tails or the coder
+    _REM_SIZE_REFUSAL = ("coded-size control on REM models: the symbols and indexes at a quality q depend on the checkpoint "
+                         "representation of q's check level (the REM refines (mu, sigma) per level), so neither one front end "
+                         "nor one layer pass prices them; call compress(x, q, checkpoint_rep=...) per quality")
+
+    def _compress_size(self, xb, q, mask_pol):
+        """(bytes, table cost in bits) of the strings of the real ``compress(xb, q)`` for ONE image, the cost priced on the
+        host from that plan's own symbol and index buffers (models that are not _sweep_eligible)."""
+        from . import bitstream as bs
+        out = self.compress(xb, q, mask_pol)
+        nbytes = sum(len(s_) for part in out["strings"][0] for s_ in part) + sum(len(s_) for s_ in out["strings"][1])
+        plan = self._plan(xb, base_only=q <= 0, rem_idx=None, symbols=True)
+        tg, te = bs.Tables.of(self.gaussian_conditional), bs.Tables.of(self.entropy_bottleneck)
+        zs = plan.z_sym.buf.cpu().numpy()
+        bits = bs.price(plan.sym.buf.cpu().numpy(), plan.idx.buf.cpu().numpy(), tg).sum() + \
+            bs.price(zs, np.arange(self.N)[None, None, None, :], te).sum()
+        return nbytes, float(bits)
+
+    def _size_prepare(self, x, mask_pol, what):
+        if isinstance(self, VarianceMaskingPICREM):
+            raise NotImplementedError(self._REM_SIZE_REFUSAL)
+        mask_pol = self._mask_policy(mask_pol)
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        if self.gaussian_conditional.scale_table.numel() == 0:
+            raise ValueError(f"empty scale table: call model.update() before {what}()")
+        return mask_pol
+
+    def coded_size_curve(self, x, qualities, mask_pol=None):
+        """The size of the strings of ``compress(x[b:b+1], q)`` — z, the base slices and, for q > 0, the progressive slices —
+        for every image at every quality of the list (any order, repeats allowed, any count), without running it:
+        {"bytes_lo", "bytes_hi": int64 [len(qualities), B] with bytes_lo <= actual <= bytes_hi guaranteed (each stream
+        is one of at most two lengths, 4 bytes apart), "bits": float64 [len(qualities), B] the exact table cost}.  Eligible
+        models (:meth:`_sweep_eligible`) run the front end once per sub-batch, price z and the base slices once, and per
+        group of up to VAM_MAX_LAYER_LEVELS distinct qualities run one vam_variance_layers and one vam_coded_layer_bits
+        launch.  The others loop over the real compress (bytes_lo == bytes_hi == the actual size); REM models are refused."""
+        qualities = [float(q) for q in qualities]
+        mask_pol = self._size_prepare(x, mask_pol, "coded_size_curve")
+        B, _, H, W = x.shape
+        lo, hi = np.zeros((len(qualities), B), dtype=np.int64), np.zeros((len(qualities), B), dtype=np.int64)
+        bits = np.zeros((len(qualities), B))
+        with torch.no_grad():
+            if not self._sweep_eligible():
+                for b in range(B):
+                    seen: Dict[float, tuple] = {}
+                    for k, q in enumerate(qualities):
+                        if q not in seen:
+                            seen[q] = self._compress_size(x[b:b + 1], q, mask_pol)
+                        lo[k, b] = hi[k, b] = seen[q][0]
+                        bits[k, b] = seen[q][1]
+            else:
+                prs = [float(_mask_quality(mask_pol, q)) for q in qualities]
+                levels = sorted({p_ for p_ in prs if p_ != 0})
+                col = {p_: j for j, p_ in enumerate(levels)}
+                G = L.VAM_MAX_LAYER_LEVELS
+                for i0, i1, _ in sweep_groups(0, B, H, W):
+                    xb = x[i0:i1].detach()
+                    sw = self._sweep_plan(xb)
+                    sw.front(xb, self.use_graph)
+                    sz = sw.size_front(self.use_graph)
+                    prog = [sw.size(levels[l0:l0 + G], self.use_graph) for l0 in range(0, len(levels), G)]
+                    base = sz.base_sizes()                                  # (lo, hi, bits), each [b]
+                    pl = sz.level_sizes(prog, [min(G, len(levels) - l0) for l0 in range(0, len(levels), G)])   # each [b, n_levels]
+                    for k, p_ in enumerate(prs):
+                        for dst, b0, pv in zip((lo, hi, bits), base, pl):
+                            dst[k, i0:i1] = b0 if p_ == 0 else b0 + pv[:, col[p_]]
+        return {"bytes_lo": torch.from_numpy(lo), "bytes_hi": torch.from_numpy(hi), "bits": torch.from_numpy(bits)}
+
+    def qualities_for_bytes(self, x, target_bytes, q_tol=1e-3, mask_pol=None):
+        """The largest quality whose coded size fits a byte budget, per image: ``target_bytes`` a number, T numbers or a
+        [T, B] tensor.  Returns {"quality": float64 [T, B], "bytes": float64 [T, B] (bytes_hi of coded_size_curve at that
+        quality), "reached": bool [T, B]} on the host, with, per image b and target t: the strings of the real
+        compress(x[b:b+1], q*) weigh <= t;  q* = 10 or bytes_hi(min(10, q* + q_tol)) > t (for a bytes_hi that does not
+        decrease in q);  q* = 0 with reached = False when even the base exceeds t.  :func:`rate_search` over bytes_hi:
+        one front end per sub-batch; the first pass is the batched size tail, every later pass one
+        vam_variance_layers_per_image and one vam_coded_layer_bits launch for the sub-batch and one synchronisation."""
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if not isinstance(self, VarianceMaskingPICREM) and self._mask_policy(mask_pol) != "point-based-std":
+            raise ValueError(f"qualities_for_bytes searches the point-based-std curve; the {mask_pol!r} curve has two values "
+                             "(q == 0 and q != 0): read them from coded_size_curve(x, [0, 10])")
+        mask_pol = self._size_prepare(x, mask_pol, "qualities_for_bytes")
+        if not q_tol > 0:
+            raise ValueError(f"q_tol must be > 0, got {q_tol}")
+        B, _, H, W = x.shape
+        tg = torch.as_tensor(target_bytes, dtype=torch.float64).cpu().numpy()
+        if tg.ndim == 0:
+            tg = tg.reshape(1)
+        if tg.ndim == 1:
+            tg = np.repeat(tg[:, None], B, axis=1)
+        if tg.ndim != 2 or tg.shape[1] != B:
+            raise ValueError(f"target_bytes: a number, T numbers or a [T, {B}] tensor, got shape {tuple(tg.shape)}")
+        quality, size, reached = (np.zeros(tg.shape), np.zeros(tg.shape), np.zeros(tg.shape, dtype=bool))
+        with torch.no_grad():
+            if not self._sweep_eligible():
+                def curve(q, need):                        # one real compress per (image, quality) asked for
+                    out = np.zeros(q.shape)
+                    for b in range(B):
+                        qs = np.unique(q[:, b][need[:, b]])
+                        val = {v: self._compress_size(x[b:b + 1], v, mask_pol)[0] for v in qs.tolist()}
+                        out[:, b][need[:, b]] = [val[v] for v in q[:, b][need[:, b]].tolist()]
+                    return out
+                size0 = np.array([self._compress_size(x[b:b + 1], 0.0, mask_pol)[0] for b in range(B)], dtype=np.float64)
+                quality, size, reached = rate_search(curve, size0, tg, q_tol, n_grid=2)
+            else:
+                for i0, i1, _ in sweep_groups(0, B, H, W):
+                    xb = x[i0:i1].detach()
+                    sw = self._sweep_plan(xb)
+                    sw.front(xb, self.use_graph)
+                    sz = sw.size_front(self.use_graph)
+                    size0 = sz.base_sizes()[1].astype(np.float64)
+                    curve = lambda q, need, sw=sw: sw.size_points(q, need, self.use_graph)
+                    quality[:, i0:i1], size[:, i0:i1], reached[:, i0:i1] = rate_search(curve, size0, tg[:, i0:i1], q_tol)
+        return {"quality": torch.from_numpy(quality), "bytes": torch.from_numpy(size), "reached": torch.from_numpy(reached)}
+
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),
         stacked as the reference stacks them.  ``training=True`` evaluates the likelihoods with additive uniform noise;
@@ -1069,7 +1184,8 @@ class _FsqPlan:
         E.lower_stacks(plan, [m.h_a], [[y]], [z])
         self.z_hat = plan.buf(B, h // 4, w // 4, m.N)
         self.z_lik = plan.buf(B, h // 4, w // 4, m.N)
-        self.z_sym = ops.new_iview(B, h // 4, w // 4, m.N, device) if symbols else None
+        # the entropy coder's z symbols (compress) — kept in sweep mode too: coded_size_curve prices them
+        self.z_sym = ops.new_iview(B, h // 4, w // 4, m.N, device) if symbols or sweep else None
         plan.keep.append(self.z_sym)
         self.noise_z = plan.buf(B, h // 4, w // 4, m.N) if train else None
         self.noise_y = plan.buf(B, h, w, d if base_only else 2 * d) if train else None
@@ -1536,6 +1652,138 @@ class _RateTail:
         self.runner.close()
 
 
+class _SizeTail:
+    """The coded-size tail of a _SweepPlan's front end, beside _RateTail.  Once per front end
+    (``front``): z (vam_coded_symbol_bits on the front end's z symbols) and the base slices (vam_coded_layer_bits with no
+    layer ids) are priced per stream.  Per list of n sorted distinct qualities > 0 (``levels``): one zero-fill, one
+    vam_variance_layers on the progressive sigma and one vam_coded_layer_bits, which bins the exact price of every
+    element's (symbol, index) pair by (image, slice, layer).  No masks, no LRP stacks, no g_s, no coder.  The bins go to
+    the host once; the stream lengths are host arithmetic (bitstream.stream_bytes)."""
+
+    def __init__(self, fp):
+        m, parts = fp.m, fp.sweep_parts
+        sg = parts["std"]
+        dev = sg.buf.device
+        self.fp, self.m, self.parts, self.ns, self.B, self.dev = fp, m, parts, m.ns0, sg.B, dev
+        self.C = m.dim_chunk
+        self.n_y = self.C * sg.H * sg.W                              # symbols of one y stream
+        self.n_z = m.N * fp.z_sym.buf.shape[1] * fp.z_sym.buf.shape[2]
+        self.runner = E.Runner(dev, cap=32)              # ("front",) and one graph per tuple of qualities
+        self.layer = torch.empty((sg.B, sg.H, sg.W, sg.C), dtype=torch.uint8, device=dev)
+        # z: [B, 1, 2] sums and counts, then the base slices: [B, ns, 2] sums and counts, one buffer and one zero-fill
+        B, ns = sg.B, self.ns
+        self.acc0 = torch.zeros((4 * B + 4 * B * ns,), dtype=torch.float64, device=dev)
+        a = self.acc0
+        self.z_bits, self.z_cnt = a[:2 * B].view(B, 1, 2), a[2 * B:4 * B].view(torch.int64).view(B, 1, 2)
+        self.b_bits = a[4 * B:4 * B + 2 * B * ns].view(B, ns, 2)
+        self.b_cnt = a[4 * B + 2 * B * ns:].view(torch.int64).view(B, ns, 2)
+        d = m.division_dimension[0]
+        P = self.front_plan = E.Plan(dev)
+        P.keep += [self.acc0, self.layer]
+        P.set_class("lrp_prog")
+        P.call(lambda: ops.memset_zero(self.acc0))
+        P.call(lambda: ops.coded_symbol_bits(fp.z_sym, None, None, 1, self.te, m.N, self.z_bits, self.z_cnt), "z prices (size)")
+        P.call(lambda: ops.coded_layer_bits(fp.y.window(0, d), fp.mu_b, fp.std_b, None, 1, self.table, self.tg, self.C,
+                                            self.b_bits, self.b_cnt), "base prices (size)")
+        self.tails: Dict[int, tuple] = {}                # n_levels -> (plan, acc)
+        self.prs: tuple = ()
+        self.tg = self.te = None
+        self._base = None
+
+    def refresh(self):
+        """The coder's tables on the device (built on the host and copied: outside any capture).  Graphs captured with
+        replaced tables are given up."""
+        from . import bitstream as bs
+        m = self.m
+        tg = bs.DeviceTables.of(m.gaussian_conditional, self.dev)
+        te = bs.DeviceTables.of(m.entropy_bottleneck, self.dev)
+        if tg is not self.tg or te is not self.te:
+            self.runner.close()
+            self.tg, self.te = tg, te
+            self.table = m.gaussian_conditional.scale_table.detach().to(self.dev, torch.float32).contiguous()
+            self.c_out = float(tg.zero_cost[bs.sigma0_index(self.table)])      # compress: symbol 0 at build_indexes(0)
+            self.c_out_layer = float(tg.zero_cost[0])                           # a container layer: symbol 0 in table 0
+
+    def front(self, use_graph: bool):
+        """Price z and the base slices of the front end that has just run (on the owner's stream)."""
+        self.refresh()
+        self.runner.replay(("front",), self.front_plan.run, use_graph)
+        self._base = None
+
+    def _tail(self, n_levels: int):
+        t = self.tails.get(n_levels)
+        if t is None:
+            assert 1 <= n_levels <= L.VAM_MAX_LAYER_LEVELS
+            acc = torch.zeros((2, self.B, self.ns, n_levels + 1), dtype=torch.float64, device=self.dev)
+            P = E.Plan(self.dev)
+            P.keep += [acc]
+            P.set_class("lrp_prog")
+            P.call(lambda: ops.memset_zero(acc))
+            P.call(lambda: self.launch(self.prs, acc), "layers + coded layer bits (size)")
+            t = self.tails[n_levels] = (P, acc)
+        return t
+
+    def launch(self, prs, acc: torch.Tensor, per_image: bool = False):
+        """The two kernels for the whole sub-batch: one quality list for all images, or (``per_image``) one per image;
+        ``acc`` [2, B, ns, n + 1] cleared."""
+        pa = self.parts
+        if per_image:
+            ops.variance_layers_per_image(pa["std"], prs, self.layer, n_slice=self.ns)
+        else:
+            ops.variance_layers(pa["std"], prs, self.layer, n_slice=self.ns)                  # pic.py:621-622, all levels
+        ops.coded_layer_bits(pa["y_top"], pa["mu"], pa["std"], self.layer, acc.shape[-1] - 1, self.table, self.tg, self.C,
+                             acc[0], acc[1].view(torch.int64), y2=pa["y_sub"])
+
+    def levels(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
+        """A clone of the bins [2, B, ns, len(prs) + 1] of the sorted distinct qualities ``prs`` (> 0); one plan per list
+        length and one hipGraph per list, as the rate tails."""
+        P, acc = self._tail(len(prs))
+        self.prs = tuple(float(p_) for p_ in prs)
+        self.runner.replay(self.prs, P.run, use_graph)
+        return acc.clone()
+
+    # ---- host arithmetic on the bins
+    def base_sizes(self):
+        """(bytes_lo, bytes_hi, bits), each [B]: z and the base slices, the strings of compress(x, 0).  Synchronises."""
+        from . import bitstream as bs
+        if self._base is None:
+            a = self.acc0.cpu()
+            B, ns = self.B, self.ns
+            zb = a[:2 * B].view(B, 1, 2).numpy()[:, :, 0]
+            bb = a[4 * B:4 * B + 2 * B * ns].view(B, ns, 2).numpy()[:, :, 0]
+            zl, zh = bs.stream_bytes(zb, self.n_z)
+            bl, bh = bs.stream_bytes(bb, self.n_y)
+            self._base = (zl.sum(1) + bl.sum(1), zh.sum(1) + bh.sum(1), zb.sum(1) + bb.sum(1))
+            self._parts = ((zl.sum(1), zh.sum(1)), (bl.sum(1), bh.sum(1)))
+        return self._base
+
+    def stream_bits(self, acc: np.ndarray, n_levels, c_out: float, cumulative: bool = True) -> np.ndarray:
+        """[..., ns, n_levels] table cost of each progressive stream from host bins ``acc`` [2 (sums, counts as float64
+        bit patterns), ..., ns, >= n_levels + 1].  ``cumulative``: compress at level k, the elements of layers <= k at their
+        price and every other element at ``c_out``; else container layer k alone."""
+        bits, count = acc[0][..., :n_levels], acc[1].view(np.int64)[..., :n_levels]
+        if cumulative:
+            bits, count = np.cumsum(bits, -1), np.cumsum(count, -1)
+        return bits + (self.n_y - count).astype(np.float64) * c_out
+
+    def level_sizes(self, accs: Sequence[torch.Tensor], ns_levels: Sequence[int]):
+        """(bytes_lo, bytes_hi, bits), each [B, total levels]: the progressive strings of compress at every level of the
+        groups' bins (what :meth:`levels` returned).  One host synchronisation."""
+        from . import bitstream as bs
+        lo, hi, bits = [], [], []
+        for acc, n in zip([a.cpu().numpy() for a in accs], ns_levels):
+            S = self.stream_bits(acc, n, self.c_out)                    # [B, ns, n]
+            l, h = bs.stream_bytes(S, self.n_y)
+            lo.append(l.sum(1)); hi.append(h.sum(1)); bits.append(S.sum(1))
+        if not lo:
+            z = np.zeros((self.B, 0))
+            return z.astype(np.int64), z.astype(np.int64), z
+        return np.concatenate(lo, 1), np.concatenate(hi, 1), np.concatenate(bits, 1)
+
+    def close(self):
+        self.runner.close()
+
+
 class _SweepTail:
     """The per-level part of a rate sweep for ``n_levels`` qualities over the shared buffers of a _SweepPlan's front end
     (pic.py:621-651 once per level), run as n_levels * B images: level k is images k*B .. (k+1)*B-1 of every buffer here.
@@ -1620,6 +1868,7 @@ class _SweepPlan:
         E.lower_g_s(self.p_base, [m.g_s[0] if m.multiple_decoder else m.g_s], [self.fp.y_base], [self.fp.x_hat])
         self.tails: Dict[int, _SweepTail] = {}
         self.rate_tails: Dict[int, _RateTail] = {}
+        self.size_tail: Optional[_SizeTail] = None
         self.runner = E.Runner(device, cap=32)           # ("front",) and ("base",); the tails run on its stream
 
     def front(self, x, use_graph: bool):
@@ -1654,6 +1903,73 @@ class _SweepPlan:
         with self.runner.on_stream():
             t.runner.replay(t.prs, t.plan.run, use_graph)
         return t.level_sums(t.acc, len(prs))
+
+    # ---- coded sizes
+    def size_front(self, use_graph: bool) -> _SizeTail:
+        """Price z and the base slices of the front end that has just run; the plan's size tail."""
+        if self.size_tail is None:
+            self.size_tail = _SizeTail(self.fp)
+        with self.runner.on_stream():
+            self.size_tail.front(use_graph)
+        return self.size_tail
+
+    def size(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
+        """The bins [2, B, ns, len(prs) + 1] of the sorted distinct qualities ``prs`` (> 0) (after :meth:`size_front`)."""
+        with self.runner.on_stream():
+            return self.size_tail.levels(prs, use_graph)
+
+    def size_eager(self, prs: Sequence[float]) -> np.ndarray:
+        """Host bins [2, B, ns, len(prs) + 1] of a non-decreasing list that is asked for once (no graph); synchronises."""
+        st = self.size_tail
+        acc = torch.zeros((2, self.B, st.ns, len(prs) + 1), dtype=torch.float64, device=st.dev)
+        with self.runner.on_stream():
+            st.launch([float(p_) for p_ in prs], acc)
+        return acc.cpu().numpy()
+
+    def size_points(self, q, need, use_graph: bool):
+        """qualities_for_bytes' curve: bytes_hi of compress at the qualities q [T, B, n] (> 0) wanted by ``need``, as a host
+        array of q's shape; one host synchronisation.  When all images ask for the same points (the first pass) the batched
+        tail runs (and its graph); else every image has its own sorted distinct points and, VAM_MAX_LAYER_LEVELS at a
+        time, ONE vam_variance_layers_per_image and one vam_coded_layer_bits launch serve the whole sub-batch, eagerly (the
+        points of a pass are never asked for again)."""
+        T, B, _ = q.shape
+        G = L.VAM_MAX_LAYER_LEVELS
+        st = self.size_tail
+        pts, inv = [], []
+        for b in range(B):
+            u, iv = np.unique(q[:, b][need[:, b]], return_inverse=True)
+            pts.append(u)
+            inv.append(iv)
+        out = np.zeros(q.shape)
+        base_hi = st.base_sizes()[1]
+        most = max(u.size for u in pts)
+        if not most:
+            return out
+        if all(u.size == pts[0].size and np.array_equal(u, pts[0]) for u in pts):
+            chunks = [(l0, min(G, most - l0)) for l0 in range(0, most, G)]
+            accs = [self.size(pts[0][l0:l0 + n].tolist(), use_graph) for l0, n in chunks]
+            hi = st.level_sizes(accs, [n for _, n in chunks])[1]             # [B, n_points]
+            for b in range(B):
+                out[:, b][need[:, b]] = (base_hi[b] + hi[b])[inv[b]]
+            return out
+        from . import bitstream as bs
+        accs = []
+        with self.runner.on_stream():
+            for l0 in range(0, most, G):
+                acc = torch.zeros((2, B, st.ns, G + 1), dtype=torch.float64, device=st.dev)
+                # an image with no point left in this chunk gets the list [0]: no element in any layer, its row is not read
+                st.launch([u[l0:l0 + G].tolist() or [0.0] for u in pts], acc, per_image=True)
+                accs.append(acc)
+        host = [a.cpu().numpy() for a in accs]
+        for b in range(B):
+            vals = np.zeros(pts[b].size)
+            for c, l0 in enumerate(range(0, pts[b].size, G)):
+                n = min(G, pts[b].size - l0)
+                # a list of n < G levels leaves its no-layer elements in slot G: only the first n slots are read
+                S = st.stream_bits(host[c][:, b], n, st.c_out)            # [ns, n]
+                vals[l0:l0 + n] = bs.stream_bytes(S, st.n_y)[1].sum(0)
+            out[:, b][need[:, b]] = (base_hi[b] + vals)[inv[b]]
+        return out
 
     def rate_points(self, q, need, base: torch.Tensor, use_graph: bool):
         """qualities_for_bpp's curve: the total log2 sums (y + z) at the qualities q [T, B, n] (> 0) wanted by ``need``, as
@@ -1699,7 +2015,7 @@ class _SweepPlan:
     def close(self):
         self.fp.close()
         self.runner.close()
-        for t in list(self.tails.values()) + list(self.rate_tails.values()):
+        for t in list(self.tails.values()) + list(self.rate_tails.values()) + ([self.size_tail] if self.size_tail else []):
             t.close()
 
 

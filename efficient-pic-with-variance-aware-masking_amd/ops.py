@@ -11,6 +11,7 @@ import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -530,6 +531,31 @@ def variance_layers(sigma: View, prs: Sequence[float], layer: torch.Tensor, n_sl
                                          thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_layers")
 
 
+def variance_layers_per_image(sigma: View, prs: Sequence[Sequence[float]], layer: torch.Tensor, n_slice: int = 1,
+                              thr: Optional[torch.Tensor] = None):
+    """:func:`variance_layers` with one non-decreasing quality list per image (``prs[b]``, 1..L.VAM_MAX_LAYER_LEVELS entries,
+    the lengths may differ) in ONE launch: image b's layer ids equal ``variance_layers`` on image b alone with ``prs[b]``,
+    byte for byte; ``thr`` [max length, B * n_slice] gets level k of image b at [k, b * n_slice + j] for k < len(prs[b]).
+    The per-image ranks and weights are host arithmetic (vam_variance_layer_params); their table is copied to the device
+    here, so this call cannot be captured into a graph."""
+    slice_C = sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C and len(prs) == sigma.B
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
+    lists = [[float(p_) for p_ in row] for row in prs]
+    width = max([len(r) for r in lists] + [1])
+    hw = sigma.H * sigma.W
+    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= width * sigma.B * n_slice)
+    flat = (C.c_double * (width * sigma.B))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
+    nl = (C.c_int * sigma.B)(*[len(r) for r in lists])
+    table = np.zeros(sigma.B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
+    L.check(L.load().vam_variance_layer_params(flat, nl, sigma.B, width, hw, slice_C, table.ctypes.data), "vam_variance_layer_params")
+    dev = torch.from_numpy(table).to(sigma.buf.device)
+    L.check(L.load().vam_variance_layers_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
+                                                   dev.data_ptr(), layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
+                                                   thr.data_ptr() if thr is not None else None, stream_ptr()),
+            "vam_variance_layers_per_image")        # `dev` returns to the allocator of this same stream
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""
@@ -635,6 +661,44 @@ def log2_lik_outside(device) -> float:
         assert count.tolist() == [[1, 3]]
         _LOG2_LIK_OUTSIDE[key] = float(bits[0, 0])
     return _LOG2_LIK_OUTSIDE[key]
+
+
+def _coded_bins(bits: torch.Tensor, count: torch.Tensor, n_streams: int, n_levels: int):
+    for t, dt in ((bits, torch.float64), (count, torch.int64)):
+        assert t.dtype == dt and t.is_contiguous() and t.numel() == n_streams * (n_levels + 1), (t.dtype, tuple(t.shape), n_streams, n_levels)
+
+
+def coded_layer_bits(y: View, mu: View, sigma: View, layer: Optional[torch.Tensor], n_levels: int, scale_table: torch.Tensor,
+                     tables, chans_per_stream: int, bits: torch.Tensor, count: torch.Tensor, *, y2: Optional[View] = None):
+    """Coded-size tail: per stream (image, slice of ``chans_per_stream`` channels) the exact price in bits
+    the range coder charges for the pair (round(r - mu), build_indexes(sigma)) of every element, and the element count,
+    binned by the layer ids of :func:`variance_layers` (``layer`` None: all in layer 0): ``bits`` float64 / ``count`` int64
+    [B, y.C // chans_per_stream, n_levels + 1], slot ``n_levels`` for L.LAYER_NONE.  Both accumulate: clear them first.
+    ``tables``: a bitstream.DeviceTables of the gaussian conditional."""
+    B = y.B
+    assert mu.C == sigma.C == y.C and (y2 is None or y2.C == y.C)
+    assert layer is None or (layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (B, y.H, y.W, y.C))
+    assert scale_table.dtype == torch.float32 and scale_table.is_contiguous() and scale_table.device == y.buf.device
+    _coded_bins(bits, count, B * (y.C // max(chans_per_stream, 1)), n_levels)
+    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
+    L.check(L.load().vam_coded_layer_bits(*p(y), *p(y2), *p(mu), *p(sigma), layer.data_ptr() if layer is not None else None, y.C,
+                                          n_levels, scale_table.data_ptr(), scale_table.numel(), C.byref(tables.struct),
+                                          chans_per_stream, bits.data_ptr(), count.data_ptr(), y.H * y.W, y.n_pix, y.C,
+                                          stream_ptr()), "vam_coded_layer_bits")
+
+
+def coded_symbol_bits(sym: IView, idx: Optional[IView], layer: Optional[torch.Tensor], n_levels: int, tables,
+                      chans_per_stream: int, bits: torch.Tensor, count: torch.Tensor, *, idx_base: int = 0):
+    """The symbol-input form of :func:`coded_layer_bits`: int32 symbols with int32 table indexes (``idx`` None: index =
+    ``idx_base`` + channel, the entropy bottleneck's per-channel tables)."""
+    B, H, W = sym.buf.shape[:3]
+    assert idx is None or (idx.C == sym.C and tuple(idx.buf.shape[:3]) == (B, H, W))
+    assert layer is None or (layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (B, H, W, sym.C))
+    _coded_bins(bits, count, B * (sym.C // max(chans_per_stream, 1)), n_levels)
+    L.check(L.load().vam_coded_symbol_bits(sym.ptr, sym.ld, idx.ptr if idx is not None else None, idx.ld if idx is not None else 0,
+                                           idx_base, layer.data_ptr() if layer is not None else None, sym.C, n_levels,
+                                           C.byref(tables.struct), chans_per_stream, bits.data_ptr(), count.data_ptr(), H * W,
+                                           B * H * W, sym.C, stream_ptr()), "vam_coded_symbol_bits")
 
 
 def build_indexes(sigma: View, table: torch.Tensor, mask: Optional[View] = None, out: Optional[IView] = None) -> torch.Tensor:

@@ -226,6 +226,120 @@ def q_list_for_bpps(model, x, target_bpps: Sequence[float]) -> List[float]:
     return check_q_list(qs)
 
 
+def container_sizes(model, x, q_list: Sequence[float] = Q_LIST) -> List[dict]:
+    """What the containers of ``encode_batch(model, x, q_list)`` weigh, without encoding: per image
+    {"z": [lo, hi], "base": [lo, hi], "progressive": [[lo, hi] per layer]} in bytes, with lo <= actual <= hi guaranteed
+    for every group of streams.  One front end per sub-batch, one vam_variance_layers and one vam_coded_layer_bits
+    launch; a layer's stream costs its elements' exact table prices plus the price of symbol 0 in table 0 for every other
+    element.  The refusals are encode_batch's."""
+    from . import _lib as L
+    from . import bitstream as bs
+    from .models import sweep_groups
+    _check_variant(model)
+    _check_batched(model)
+    qs = check_q_list(q_list)
+    m = model
+    B, _, H, W = x.shape
+    out: List[dict] = []
+    with torch.no_grad():
+        L.require_gpu()
+        m._check_config()
+        if m.gaussian_conditional.scale_table.numel() == 0:
+            raise ValueError("empty scale table: call model.update() before container_sizes()")
+        for i0, i1, _ in sweep_groups(0, B, H, W):
+            xb = x[i0:i1].detach()
+            sw = m._sweep_plan(xb)
+            sw.front(xb, m.use_graph)
+            st = sw.size_front(m.use_graph)
+            acc = sw.size(qs, m.use_graph).cpu().numpy()
+            st.base_sizes()
+            (zl, zh), (bl, bh) = st._parts
+            S = st.stream_bits(acc, len(qs), st.c_out_layer, cumulative=False)        # [b, ns, L]
+            lo, hi = bs.stream_bytes(S, st.n_y)
+            lo, hi = lo.sum(1), hi.sum(1)
+            for b in range(i1 - i0):
+                out.append({"z": [int(zl[b]), int(zh[b])], "base": [int(bl[b]), int(bh[b])],
+                            "progressive": [[int(lo[b, k]), int(hi[b, k])] for k in range(len(qs))]})
+    return out
+
+
+def solve_q_list_for_bytes(layer_hi, fixed_hi: float, target_bytes: Sequence[float], q_tol: float = 1e-3, n_grid: int = 31):
+    """The level-by-level arithmetic of :func:`q_list_for_bytes` on host numbers, no model and no GPU of its own.
+    ``layer_hi(q_prev, qs)`` returns the upper size in bytes of ONE container layer that adds the elements between the
+    masks of q_prev and of each q of ``qs`` (ascending, every q >= q_prev; q == q_prev is the empty layer, which still
+    pays its stream overheads), non-decreasing in q; ``fixed_hi`` the upper size of z and the base.  The targets are taken
+    in ascending order; level k gets the largest quality q_k in [q_{k-1}, 10] with
+    fixed_hi + sum_{j<=k} layer_hi(q_{j-1}, q_j) <= target_k, found by successive refinement on grids of ``n_grid`` points
+    (the bracket shrinks by n_grid per pass, as rate_search's).  A target that does not even admit the empty layer (or lies
+    below the base) is dropped, and so is every target after the mask is full (q = 10).  Returns (qualities, the targets
+    kept, the upper size up to each level)."""
+    from .models import rate_search_grid, rate_search_passes, rate_search_step
+    qs, kept, sizes = [], [], []
+    q_prev, used = 0.0, float(fixed_hi)
+    for t in sorted(float(t_) for t_ in target_bytes):
+        if q_prev >= 10.0:
+            break
+        budget = t - used
+        lo, r_lo = q_prev, float(np.asarray(layer_hi(q_prev, np.array([q_prev])), dtype=np.float64)[0])
+        if t < fixed_hi or r_lo > budget:
+            continue
+        hi = 10.0
+        for _ in range(rate_search_passes(q_tol, n_grid)):
+            if not hi > lo:
+                break
+            pts = rate_search_grid(np.float64(lo), np.float64(hi), n_grid)               # ascending, the last one is hi
+            r = np.asarray(layer_hi(q_prev, pts), dtype=np.float64)
+            gq, gr = np.concatenate([[lo], pts]), np.concatenate([[r_lo], r])
+            n_lo, n_rlo, n_hi, _, _ = rate_search_step(gq, gr, np.float64(budget))
+            lo, r_lo, hi = float(n_lo), float(n_rlo), float(n_hi)
+        used += r_lo
+        q_prev = lo
+        qs.append(lo)
+        kept.append(t)
+        sizes.append(used)
+    return qs, kept, sizes
+
+
+def q_list_for_bytes(model, x, target_bytes: Sequence[float], q_tol: float = 1e-3, return_targets: bool = False):
+    """The quality list of a container of ONE image whose level k is guaranteed to fit the k-th byte budget:
+    ``bits_up_to(c, k) / 8 <= target_k`` for the container c of ``encode_batch(model, x, q_list)``, with the largest such
+    quality level by level (:func:`solve_q_list_for_bytes`): a layer's size depends on the previous cut, and every layer
+    adds its own stream overheads.  Targets below the base (z + base slices) are dropped.  One front end; every
+    refinement pass is one vam_variance_layers and one vam_coded_layer_bits launch.  ``return_targets``: also the targets
+    kept, one per level."""
+    from . import _lib as L
+    from . import bitstream as bs
+    if x.shape[0] != 1:
+        raise ValueError(f"q_list_for_bytes resolves one image's list (the qualities differ between images), got a batch of {x.shape[0]}")
+    _check_variant(model)
+    _check_batched(model)
+    m = model
+    with torch.no_grad():
+        L.require_gpu()
+        m._check_config()
+        if m.gaussian_conditional.scale_table.numel() == 0:
+            raise ValueError("empty scale table: call model.update() before q_list_for_bytes()")
+        xb = x.detach()
+        sw = m._sweep_plan(xb)
+        sw.front(xb, m.use_graph)
+        st = sw.size_front(m.use_graph)
+        fixed_hi = float(st.base_sizes()[1][0])
+
+        def layer_hi(q_prev, qs_):
+            # slot 0 takes the elements the previous levels already carry; the layer up to qs_[i] is slots 1..i+1
+            qs_ = [float(q) for q in np.asarray(qs_).reshape(-1)]
+            acc = sw.size_eager([float(q_prev)] + qs_)[:, 0]                      # [2, ns, n + 2]
+            S = st.stream_bits(acc[..., 1:], len(qs_), st.c_out_layer)            # cumulative over slots 1..
+            return bs.stream_bytes(S, st.n_y)[1].sum(0)
+
+        qs, kept, _ = solve_q_list_for_bytes(layer_hi, fixed_hi, target_bytes, q_tol,
+                                             n_grid=min(31, L.VAM_MAX_LAYER_LEVELS - 1))
+    if not qs:
+        raise ValueError(f"no target of {list(target_bytes)} reaches the base size of this image ({fixed_hi:.0f} bytes and one layer)")
+    qs = check_q_list(qs)
+    return (qs, kept) if return_targets else qs
+
+
 def container_bits(c) -> list:
     """[bits_z, bits_base, bits_per_layer] of one image's container (what :func:`encode` returns beside it)."""
     return [8.0 * sum(len(s) for s in c["z"]), 8.0 * sum(len(s[0]) for s in c["base"]),

@@ -283,6 +283,28 @@ int vam_variance_mask_levels(const float* sigma, int ld, long batch_stride, long
 int vam_variance_layers(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice,
                         int n_pix, int C, const double* prs, int n_levels, uint8_t* layer_out, int ld_layer,
                         long layer_batch_stride, long layer_slice_stride, float* thr_out, void* stream);
+/* vam_variance_layers with a quality list PER IMAGE (the later passes of VarianceMaskingPIC.qualities_for_bytes, DESIGN
+ * section 9i: every image refines its own bracket).  vam_variance_layer_params is the host arithmetic of one segment size:
+ * for image b it turns the non-decreasing list prs[b * levels_stride .. + n_levels[b]) (1 <= n_levels[b] <=
+ * VAM_MAX_LAYER_LEVELS) into the rank / weight / mode of every level, what vam_variance_layers computes for its one list,
+ * and writes n_batch records of vam_layer_params to table_host.  The caller copies the table to the device (outside any
+ * graph capture) and hands it to vam_variance_layers_per_image, which runs the same kernel code with image b's record:
+ * the layer ids of image b equal vam_variance_layers on image b alone with prs[b], byte for byte, and its thresholds
+ * land at thr_out[k * n_batch * n_slice + b * n_slice + j] for k < n_levels[b] (rows beyond are left alone).  A record
+ * whose n_levels is outside 1..VAM_MAX_LAYER_LEVELS makes the kernel skip that image (ids 0xFF). */
+typedef struct vam_layer_params {
+  int32_t n_levels, any_select;
+  int32_t k_lo[VAM_MAX_LAYER_LEVELS], k_hi[VAM_MAX_LAYER_LEVELS];
+  float w[VAM_MAX_LAYER_LEVELS];
+  int32_t mode[VAM_MAX_LAYER_LEVELS];
+} vam_layer_params;
+size_t vam_layer_params_size(void);
+int vam_variance_layer_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix, int C,
+                              vam_layer_params* table_host);
+int vam_variance_layers_per_image(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch,
+                                  int n_slice, int n_pix, int C, const vam_layer_params* table_dev, uint8_t* layer_out,
+                                  int ld_layer, long layer_batch_stride, long layer_slice_stride, float* thr_out,
+                                  void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
@@ -337,6 +359,36 @@ int vam_gauss_levels_decode(const int32_t* sym, int ld_sym, const uint8_t* layer
 int vam_gauss_layer_bits(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
                          const float* sigma, int ld_sigma, const uint8_t* layer, int ld_layer, int n_levels,
                          double* bits, long long* count, int pix_per_item, long n_pix, int C, void* stream);
+
+/* Coded-size control (VarianceMaskingPIC.coded_size_curve / qualities_for_bytes, progressive.container_sizes; DESIGN
+ * section 9i): what the range coder of csrc/rans.cpp charges for every element, binned like vam_gauss_layer_bits but per
+ * STREAM.  The coder's tables on the device: cost[t * stride + v] = 16 - log2(cdf[t][v+1] - cdf[t][v]) in float64 for
+ * v <= sizes[t] - 2 (entry sizes[t] - 2 is the escape), built once on the host from the int32 CDFs (bitstream.py). */
+typedef struct vam_coder_tables {
+  const double* cost;       /* device [n_cdfs][stride] */
+  const int32_t* sizes;     /* device [n_cdfs]: cdf lengths, as the coder takes them */
+  const int32_t* offsets;   /* device [n_cdfs] */
+  int32_t n_cdfs, stride;
+} vam_coder_tables;
+/* Per element of the windows vam_gauss_layer_bits reads: the symbol round(r - mu) (masked_tail with m = 1) and the table
+ * index of sigma (the arithmetic of vam_build_indexes on scale_table[n_table], n_table <= n_cdfs) — bit for bit the pair
+ * compress / encode_batch hand to the coder for an element inside the mask — and that pair's exact price in bits:
+ * cost[index][v] for v = symbol - offset inside the table, else the escape entry plus 4 * (1 + n_bypass) with n_bypass
+ * <= 8 raw nibbles (enc_put_bits).  A stream is chans_per_stream consecutive channels of one item (it divides C):
+ *   bits [(item * (C / chans_per_stream) + slice) * (n_levels+1) + k] += the prices of the elements with layer == k (fp64)
+ *   count[ same ] += their number
+ * slot n_levels takes 0xFF (and any id >= n_levels); layer == NULL: every element is layer 0.  Both ACCUMULATE and are
+ * cleared by the caller.  No float32 accumulation.  An index outside [0, n_cdfs) prices as NaN. */
+int vam_coded_layer_bits(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
+                         const float* sigma, int ld_sigma, const uint8_t* layer, int ld_layer, int n_levels,
+                         const float* scale_table, int n_table, const vam_coder_tables* tables, int chans_per_stream,
+                         double* bits, long long* count, int pix_per_item, long n_pix, int C, void* stream);
+/* The symbol-input form: int32 symbols with int32 table indexes (idx == NULL: index = idx_base + channel, the entropy
+ * bottleneck's per-channel tables), same bins.  Prices z, and the slices of a symbols-mode plan. */
+int vam_coded_symbol_bits(const int32_t* sym, int ld_sym, const int32_t* idx, int ld_idx, int idx_base,
+                          const uint8_t* layer, int ld_layer, int n_levels, const vam_coder_tables* tables,
+                          int chans_per_stream, double* bits, long long* count, int pix_per_item, long n_pix, int C,
+                          void* stream);
 
 /* GaussianConditional.build_indexes (entropy_models.py:654-659): idx = 63 - #{i<63: max(s,.11) <= T_i}
  * table: 64 floats (device). mask (may be NULL) multiplies sigma first (pic.py:809). */
