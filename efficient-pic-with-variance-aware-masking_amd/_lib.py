@@ -167,6 +167,9 @@ _SIGNATURES = {
     "vam_variance_layer_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vam_variance_layers_per_image": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_variance_mask_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vam_variance_masks_per_image": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_coded_layer_bits": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_int, C.c_void_p, C.c_int, C.POINTER(VamCoderTables), C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_coded_symbol_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

@@ -210,7 +210,15 @@ struct MaskImageArgs {
   int ld, ld_mask, n_slice, n_pix, C4;
 };
 
-// the per-level fields of the two argument kinds of variance_mask_levels_kernel
+// vam_variance_masks_per_image: MaskImageArgs' table, and the float masks of MaskLevelsArgs in place of layer ids (layer
+// stays NULL: the kernel's LAYERS = false instantiations never read it).  max_levels = the levels `mask` and `thr` hold.
+struct MaskImageMaskArgs : MaskImageArgs {
+  float* mask;
+  long mask_level_stride;
+  int max_levels;
+};
+
+// the per-level fields of the three argument kinds of variance_mask_levels_kernel
 __device__ __forceinline__ int lv_count(const MaskLevelsArgs& a, int) { return a.n_levels; }
 __device__ __forceinline__ int lv_any_select(const MaskLevelsArgs& a, int) { return a.any_select; }
 __device__ __forceinline__ int lv_mode(const MaskLevelsArgs& a, int, int lv) { return a.mode[lv]; }
@@ -230,13 +238,20 @@ __device__ __forceinline__ int lv_k_hi(const MaskImageArgs& a, int b, int lv) { 
 __device__ __forceinline__ float lv_w(const MaskImageArgs& a, int b, int lv) { return a.table[b].w[lv]; }
 __device__ __forceinline__ float* lv_mask(const MaskImageArgs&) { return nullptr; }
 __device__ __forceinline__ long lv_stride(const MaskImageArgs&) { return 0L; }
+// the other fields of a MaskImageMaskArgs are its base's: image b's record
+__device__ __forceinline__ int lv_count(const MaskImageMaskArgs& a, int b) {
+  const int n = a.table[b].n_levels;                      // a record beyond what the buffers hold writes nothing
+  return n < 0 || n > a.max_levels ? 0 : n;
+}
+__device__ __forceinline__ float* lv_mask(const MaskImageMaskArgs& a) { return a.mask; }
+__device__ __forceinline__ long lv_stride(const MaskImageMaskArgs& a) { return a.mask_level_stride; }
 
 // MAXV = float4 per thread kept in registers (0 = stream from memory every pass).  The segment is loaded once; each level
 // then runs its own selection on the same registers and writes its own mask.  LAYERS: the levels' thresholds stay in
 // LDS, and one last pass writes layer = the first level whose mask holds the element (mask_* name the layer array).
 // Args: MaskLevelsArgs (one quality list in the kernel arguments) or MaskImageArgs (vam_variance_layers_per_image: image
-// b's record of a device table); the per-level fields are read through the lv_* accessors above, so the first kind
-// compiles to the accesses it always made.
+// b's record of a device table) or MaskImageMaskArgs (vam_variance_masks_per_image: that record, float masks per level);
+// the per-level fields are read through the lv_* accessors above, so the first kind compiles to the accesses it always made.
 template <int MAXV, bool LAYERS, class Args = MaskLevelsArgs>
 __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const Args a) {
   __shared__ unsigned hist[256];
@@ -567,24 +582,23 @@ extern "C" int vam_variance_layers(const float* sigma, int ld, long batch_stride
 
 extern "C" size_t vam_layer_params_size(void) { return sizeof(vam_layer_params); }
 
-extern "C" int vam_variance_layer_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix,
-                                         int C, vam_layer_params* table_host) {
-  VAM_REQUIRE(prs && n_levels && table_host && n_batch > 0 && levels_stride >= 1 && n_pix > 0 && C > 0,
-              "vam_variance_layer_params: bad arguments");
+// the records of vam_variance_layers_per_image (sorted: non-decreasing lists of up to VAM_MAX_LAYER_LEVELS) and of
+// vam_variance_masks_per_image (any order, up to VAM_MAX_MASK_LEVELS): mask_level_params' own arithmetic, one image at a time
+static int image_params(const char* what, const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix, int C,
+                        vam_layer_params* table_host, int max_levels, bool sorted) {
   const long n = (long)n_pix * C;
   VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
-  MaskLevelsArgs a;                              // mask_level_params' own arithmetic, one image at a time
+  MaskLevelsArgs a;
   for (int b = 0; b < n_batch; ++b) {
     const int nl = n_levels[b];
     const double* p = prs + (long)b * levels_stride;
-    VAM_REQUIRE(nl >= 1 && nl <= VAM_MAX_LAYER_LEVELS && nl <= levels_stride, "vam_variance_layers_per_image: image %d: 1..%d levels, got %d",
-                b, VAM_MAX_LAYER_LEVELS, nl);
+    VAM_REQUIRE(nl >= 1 && nl <= max_levels && nl <= levels_stride, "%s: image %d: 1..%d levels, got %d", what, b, max_levels, nl);
     vam_layer_params& t = table_host[b];
     std::memset(&t, 0, sizeof(t));
     t.n_levels = nl;
     for (int lv = 0; lv < nl; ++lv) {
-      VAM_REQUIRE(lv == 0 || p[lv] >= p[lv - 1], "vam_variance_layers_per_image: image %d: qualities must be non-decreasing (prs[%d] < prs[%d])",
-                  b, lv, lv - 1);
+      VAM_REQUIRE(!sorted || lv == 0 || p[lv] >= p[lv - 1], "%s: image %d: qualities must be non-decreasing (prs[%d] < prs[%d])",
+                  what, b, lv, lv - 1);
       const int rc = mask_level_params(a, lv, p[lv], n);
       if (rc) return rc;
       t.k_lo[lv] = a.k_lo[lv]; t.k_hi[lv] = a.k_hi[lv]; t.w[lv] = a.w[lv]; t.mode[lv] = a.mode[lv];
@@ -592,6 +606,22 @@ extern "C" int vam_variance_layer_params(const double* prs, const int* n_levels,
     }
   }
   return VAM_OK;
+}
+
+extern "C" int vam_variance_layer_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix,
+                                         int C, vam_layer_params* table_host) {
+  VAM_REQUIRE(prs && n_levels && table_host && n_batch > 0 && levels_stride >= 1 && n_pix > 0 && C > 0,
+              "vam_variance_layer_params: bad arguments");
+  return image_params("vam_variance_layers_per_image", prs, n_levels, n_batch, levels_stride, n_pix, C, table_host,
+                      VAM_MAX_LAYER_LEVELS, true);
+}
+
+extern "C" int vam_variance_mask_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix,
+                                        int C, vam_layer_params* table_host) {
+  VAM_REQUIRE(prs && n_levels && table_host && n_batch > 0 && levels_stride >= 1 && n_pix > 0 && C > 0,
+              "vam_variance_mask_params: bad arguments");
+  return image_params("vam_variance_masks_per_image", prs, n_levels, n_batch, levels_stride, n_pix, C, table_host,
+                      VAM_MAX_MASK_LEVELS, false);
 }
 
 extern "C" int vam_variance_layers_per_image(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch,
@@ -621,4 +651,36 @@ extern "C" int vam_variance_layers_per_image(const float* sigma, int ld, long ba
   else
     hipLaunchKernelGGL((variance_mask_levels_kernel<0, true, MaskImageArgs>), dim3(segs), dim3(1024), 0, s, a);
   return check_launch("variance_layers_per_image_kernel");
+}
+
+extern "C" int vam_variance_masks_per_image(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch,
+                                            int n_slice, int n_pix, int C, const vam_layer_params* table_dev, int max_levels,
+                                            float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
+                                            long mask_level_stride, float* thr_out, void* stream) {
+  VAM_REQUIRE(sigma && table_dev && mask_out && n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "vam_variance_masks_per_image: bad arguments");
+  VAM_REQUIRE(max_levels >= 1 && max_levels <= VAM_MAX_MASK_LEVELS, "vam_variance_masks_per_image: 1..%d levels, got %d",
+              VAM_MAX_MASK_LEVELS, max_levels);
+  VAM_REQUIRE(C % 4 == 0 && ld % 4 == 0 && ld_mask % 4 == 0 && batch_stride % 4 == 0 && slice_stride % 4 == 0 && mask_batch_stride % 4 == 0 && mask_slice_stride % 4 == 0 && mask_level_stride % 4 == 0, "vam_variance_masks_per_image: C and strides must be multiples of 4");
+  VAM_REQUIRE((((uintptr_t)sigma) & 15) == 0 && (((uintptr_t)mask_out) & 15) == 0 && (((uintptr_t)table_dev) & 3) == 0,
+              "vam_variance_masks_per_image: 16-byte alignment (table: 4-byte)");
+  VAM_REQUIRE(ld >= C && ld_mask >= C, "vam_variance_masks_per_image: pixel stride < C");
+  const long n = (long)n_pix * C;
+  VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
+  MaskImageMaskArgs a;
+  a.sigma = sigma; a.thr = thr_out; a.layer = nullptr; a.table = table_dev;
+  a.batch_stride = batch_stride; a.slice_stride = slice_stride;
+  a.mask_batch_stride = mask_batch_stride; a.mask_slice_stride = mask_slice_stride;
+  a.ld = ld; a.ld_mask = ld_mask; a.n_slice = n_slice; a.n_pix = n_pix; a.C4 = C / 4;
+  a.mask = mask_out; a.mask_level_stride = mask_level_stride; a.max_levels = max_levels;
+  const int segs = n_batch * n_slice;
+  const int nvec = n_pix * (C / 4);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(VAM_FAM_MASK, s, 0, (4.0 + 4.0 * max_levels) * (double)n * segs);
+  if (nvec <= 4 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<4, false, MaskImageMaskArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else if (nvec <= 16 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<16, false, MaskImageMaskArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else
+    hipLaunchKernelGGL((variance_mask_levels_kernel<0, false, MaskImageMaskArgs>), dim3(segs), dim3(1024), 0, s, a);
+  return check_launch("variance_masks_per_image_kernel");
 }

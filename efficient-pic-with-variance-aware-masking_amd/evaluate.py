@@ -108,37 +108,86 @@ def rate_curve(model, x: torch.Tensor, qualities: Sequence[float]):
     return model.rate_curve(x.to(dev).contiguous(), qualities)["bpp"].cpu()
 
 
+def _rd_sums_per_image(model, x: torch.Tensor, Q: torch.Tensor, mask_pol: str = "point-based-std"):
+    """:func:`_rd_sums` with image b of row t at quality Q[t][b] (host float64 [T, B]), on the per-image sweep: one front
+    end per sub-batch, the base once for the entries equal to 0, the per-image tails for the others.  No host
+    synchronisation."""
+    dev = next(model.parameters()).device
+    T, B = Q.shape
+    ls = torch.zeros((T, B), dtype=torch.float64, device=dev)
+    sq = torch.zeros((T, B), dtype=torch.float64, device=dev)
+    is0 = (Q == 0).to(dev)
+
+    def emit(i0, i1, sw, t, ks):
+        fp, xb = sw.fp, x[i0:i1]
+        n = 1 if t is None else len(ks)
+        acc = torch.zeros((n, i1 - i0), dtype=torch.float64, device=dev)
+        ops.sqdiff_sum_levels(xb, fp.x_hat if t is None else t.x_hat, acc)
+        if t is None:
+            tot = fp.log2sum.sum(0).unsqueeze(0)
+        else:
+            tot = (fp.log2sum[0].unsqueeze(0) + t.log2sum) + fp.log2sum[1].unsqueeze(0)
+        for g, k in enumerate(ks):
+            take = is0[k, i0:i1] if t is None else ~is0[k, i0:i1]
+            g_ = 0 if t is None else g
+            sq[k, i0:i1] = torch.where(take, acc[g_], sq[k, i0:i1])
+            ls[k, i0:i1] = torch.where(take, tot[g_], ls[k, i0:i1])
+    model._sweep(x, Q.tolist(), mask_pol, emit, per_image=True)
+    return ls, sq
+
+
+def rd_at_qualities(model, x: torch.Tensor, Q):
+    """Rate and distortion of image b at quality Q[t][b]: (bpp, psnr), float64 [T, B] host tensors (``Q``: [T, B], or B
+    values for T = 1; zeros and positives may mix freely), equal to :func:`rd_sweep` on each image alone with its column
+    of Q up to the float64 summation order.  Eligible models run the per-image sweep (VarianceMaskingPIC.
+    forward_qualities_per_image's plans) and synchronise once; the others loop over the images."""
+    dev = next(model.parameters()).device
+    x = x.to(dev).contiguous()
+    Q = torch.as_tensor(Q, dtype=torch.float64).cpu()
+    if Q.dim() == 1:
+        Q = Q.unsqueeze(0)
+    if Q.dim() != 2 or Q.shape[1] != x.shape[0]:
+        raise ValueError(f"Q is [T, {x.shape[0]}] (or one row of {x.shape[0]}), got shape {tuple(Q.shape)}")
+    if not bool((Q >= 0).all()):
+        raise ValueError("qualities must be >= 0 (and not NaN)")
+    if not _sweeps(model):
+        bpp, psnr = torch.zeros_like(Q), torch.zeros_like(Q)
+        for b in range(x.shape[0]):
+            r, p_ = rd_sweep(model, x[b:b + 1], Q[:, b].tolist())
+            bpp[:, b], psnr[:, b] = r[:, 0], p_[:, 0]
+        return bpp, psnr
+    with torch.no_grad():
+        ls, sq = _rd_sums_per_image(model, x, Q)
+        hw = x.shape[2] * x.shape[3]
+        vals = torch.stack([ls, sq]).cpu()
+    return -vals[0] / hw, -10.0 * torch.log10(vals[1] / (x[0].numel()))
+
+
 def rd_at_rates(model, x: torch.Tensor, target_bpps):
     """Rate and distortion at target rates: the qualities are resolved once for the batch (VarianceMaskingPIC.
     qualities_for_bpp: per image the largest quality whose estimated rate fits each target), then every image is
-    evaluated at its own qualities (:func:`rd_sweep` per image: they differ between images).  ``target_bpps``: T floats or
+    evaluated at its own qualities in the same batch (:func:`rd_at_qualities`).  ``target_bpps``: T floats or
     a [T, B] tensor.  Returns (bpp, psnr, quality, reached), [T, B] host tensors; where ``reached`` is False (even the
     base exceeds the budget) the row holds the base (quality 0)."""
     dev = next(model.parameters()).device
     x = x.to(dev).contiguous()
     sol = model.qualities_for_bpp(x, target_bpps)
     q = sol["quality"]
-    bpp, psnr = torch.zeros_like(q), torch.zeros_like(q)
-    for b in range(x.shape[0]):
-        r, p_ = rd_sweep(model, x[b:b + 1], q[:, b].tolist())
-        bpp[:, b], psnr[:, b] = r[:, 0], p_[:, 0]
+    bpp, psnr = rd_at_qualities(model, x, q)
     return bpp, psnr, q, sol["reached"]
 
 
 def rd_at_sizes(model, x: torch.Tensor, target_bytes):
     """Coded size and distortion at byte budgets, the analogue of :func:`rd_at_rates`: the qualities are resolved once for
     the batch (VarianceMaskingPIC.qualities_for_bytes: per image the largest quality whose compress strings are guaranteed
-    to fit each budget), then every image is evaluated at its own qualities.  ``target_bytes``: T numbers or a [T, B]
+    to fit each budget), then every image is evaluated at its own qualities in the same batch.  ``target_bytes``: T numbers or a [T, B]
     tensor.  Returns (bytes, psnr, quality, reached), [T, B] host tensors: ``bytes`` the guaranteed upper size at that
     quality; where ``reached`` is False (even the base exceeds the budget) the row holds the base (quality 0)."""
     dev = next(model.parameters()).device
     x = x.to(dev).contiguous()
     sol = model.qualities_for_bytes(x, target_bytes)
     q = sol["quality"]
-    psnr = torch.zeros_like(q)
-    for b in range(x.shape[0]):
-        psnr[:, b] = rd_sweep(model, x[b:b + 1], q[:, b].tolist())[1][:, 0]
-    return sol["bytes"], psnr, q, sol["reached"]
+    return sol["bytes"], rd_at_qualities(model, x, q)[1], q, sol["reached"]
 
 
 def _checkpoint_for(model, x, p):

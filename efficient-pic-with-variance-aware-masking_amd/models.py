@@ -296,11 +296,12 @@ class VarianceMaskingPIC(CompressionModel):
         return p
 
     def _plan(self, x, base_only: bool, rem_idx: Optional[int] = None, symbols: bool = False,
-              train: bool = False, own_ck: bool = False, train_gs: bool = False, train_lrp: bool = False) -> "_FsqPlan":
+              train: bool = False, own_ck: bool = False, train_gs: bool = False, train_lrp: bool = False,
+              per_image: bool = False) -> "_FsqPlan":
         B, H, W = _check_input(x)
         key = (B, H, W, base_only, rem_idx, str(x.device)) + ((True,) if symbols else ()) + (("train",) if train else ()) + \
             (("own_ck",) if own_ck else ()) + (("train_gs",) if train_gs else ()) + (("train_lrp",) if train_lrp else ()) + \
-            (("bf16",) if getattr(self, "storage", "fp32") == "bf16" else ())
+            (("bf16",) if getattr(self, "storage", "fp32") == "bf16" else ()) + (("per_image",) if per_image else ())
         if getattr(self, "storage", "fp32") == "bf16" and (train or symbols):
             raise NotImplementedError("bf16 storage is an inference configuration (forward_single_quality): training and "
                                       "the bitstream path run in fp32")
@@ -310,7 +311,7 @@ class VarianceMaskingPIC(CompressionModel):
         trained = ([self._decoder_in_use(base_only)] if train_gs else []) + ([self.lrp_transforms_prog] if train_lrp else [])
         return self._cached_plan(self._plans, key,
                                  lambda: _FsqPlan(self, B, H, W, base_only, rem_idx, x.device, symbols=symbols, train=train,
-                                                  own_ck=own_ck, train_gs=train_gs, train_lrp=train_lrp),
+                                                  own_ck=own_ck, train_gs=train_gs, train_lrp=train_lrp, per_image=per_image),
                                  self._weights_sig(trained), None if train else rem_idx)
 
     def _decoder_in_use(self, base_only: bool):
@@ -390,17 +391,24 @@ class VarianceMaskingPIC(CompressionModel):
         return self._cached_plan(self._plans, ("sweep", B, H, W, str(x.device)), lambda: _SweepPlan(self, B, H, W, x.device),
                                  self._weights_sig())
 
-    def _sweep(self, x, qualities, mask_pol, emit):
+    def _sweep(self, x, qualities, mask_pol, emit, per_image: bool = False):
         """Run the sweep over ``qualities`` and hand each result to ``emit(i0, i1, sweep_plan, tail, ks)`` while its buffers
         hold it (the next group overwrites them): images i0..i1 of x; ``tail`` None = the base reconstruction (the entries
         ks of ``qualities`` equal to 0), else a _SweepTail whose level g is quality ``qualities[ks[g]]``.  ``emit`` runs on
-        the caller's stream, ordered after the group and before the next one."""
+        the caller's stream, ordered after the group and before the next one.  ``per_image``: every entry of ``qualities``
+        is a row of B qualities, one per image; the base is emitted for the rows that hold a 0 anywhere, a tail level for
+        the rows that hold a positive quality anywhere (a 0 inside such a row masks everything out: the caller takes that
+        image from the base)."""
         mask_pol = self._mask_policy(mask_pol)
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
-        lv = [k for k, q in enumerate(qualities) if q != 0]
-        zeros = [k for k, q in enumerate(qualities) if q == 0]
+        if per_image:
+            lv = [k for k, row in enumerate(qualities) if any(q != 0 for q in row)]
+            zeros = [k for k, row in enumerate(qualities) if any(q == 0 for q in row)]
+        else:
+            lv = [k for k, q in enumerate(qualities) if q != 0]
+            zeros = [k for k, q in enumerate(qualities) if q == 0]
         B, _, H, W = x.shape
         for i0, i1, groups in sweep_groups(len(lv), B, H, W):
             xb = x[i0:i1].detach()
@@ -411,7 +419,11 @@ class VarianceMaskingPIC(CompressionModel):
                 emit(i0, i1, sw, None, zeros)
             for l0, l1 in groups:
                 ks = lv[l0:l1]
-                t = sw.tail([float(_mask_quality(mask_pol, qualities[k])) for k in ks], self.use_graph)
+                if per_image:
+                    t = sw.tail_per_image([[float(_mask_quality(mask_pol, q)) for q in qualities[k][i0:i1]] for k in ks],
+                                          self.use_graph)
+                else:
+                    t = sw.tail([float(_mask_quality(mask_pol, qualities[k])) for k in ks], self.use_graph)
                 emit(i0, i1, sw, t, ks)
 
     def forward_qualities(self, x, qualities, mask_pol=None):
@@ -424,6 +436,11 @@ class VarianceMaskingPIC(CompressionModel):
         if not self._sweep_eligible():
             return [self.forward_single_quality(x, q, mask_pol, training=False) for q in qualities]
         parts: List[list] = [[] for _ in qualities]
+        self._sweep(x, qualities, mask_pol, self._sweep_dicts(parts))
+        return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
+
+    def _sweep_dicts(self, parts: List[list]):
+        """An ``emit`` for :meth:`_sweep` that appends to ``parts[k]`` the result dict of entry k for each sub-batch."""
         d = self.division_dimension[0]
 
         def emit(i0, i1, sw, t, ks):
@@ -449,8 +466,202 @@ class VarianceMaskingPIC(CompressionModel):
                                  "y_hat": yh, "y_base": nchw(fp.y_base), "y_prog": yh, "mu_base": nchw(fp.mu_b),
                                  "mu": nchw(fp.mu_p), "std_base": nchw(fp.std_b), "std": nchw(fp.std_p),
                                  "mask": nchw(t.level(t.mask, g))})
-        self._sweep(x, qualities, mask_pol, emit)
+        return emit
+
+    # ---- per-image qualities in one batch
+    def _batch_shareable(self) -> bool:
+        """Can images at different qualities share one plan?  REM models (a per-quality REM and checkpoint), bf16 storage
+        and VAMPIC_CONV=f16x2 (their bits depend on how the launches are batched) loop over single images instead."""
+        return (not isinstance(self, VarianceMaskingPICREM) and getattr(self, "storage", "fp32") == "fp32"
+                and not ops.f16x2_mode())
+
+    @staticmethod
+    def _quality_vector(x, qualities, what, allow_zero: bool) -> List[float]:
+        qs = [float(q) for q in (qualities.tolist() if torch.is_tensor(qualities) else list(qualities))]
+        if len(qs) != x.shape[0]:
+            raise ValueError(f"{what}: one quality per image, got {len(qs)} for a batch of {x.shape[0]}")
+        bad = [q for q in qs if not q >= 0]
+        if bad:
+            raise ValueError(f"{what}: qualities must be >= 0 (and not NaN), got {bad[0]}")
+        zero = [b for b, q in enumerate(qs) if q == 0]
+        if zero and not allow_zero:
+            raise ValueError(f"{what}: quality 0 runs the base plan (other transforms): split the batch, e.g. "
+                             f"forward_single_quality(x[zero], 0) for zero = {zero} and {what} for the rest")
+        return qs
+
+    def forward_per_image(self, x, qualities, mask_pol=None):
+        """``forward_single_quality(x[b:b+1], qualities[b], mask_pol, training=False)`` for every image of the batch in ONE
+        plan run: the same dict, image b's tensors bit-identical (log2_likelihood_sum up to its float64 summation order).
+        ``qualities``: B numbers > 0.  The variance masks read each image's quality from a device table, so the plan keeps
+        one hipGraph whatever the qualities.  Models that cannot share a batch (:meth:`_batch_shareable`) loop."""
+        qs = self._quality_vector(x, qualities, "forward_per_image", allow_zero=False)
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if not self._batch_shareable():
+            return _cat_outputs([self.forward_single_quality(x[b:b + 1], q, mask_pol, training=False) for b, q in enumerate(qs)])
+        mask_pol = self._mask_policy(mask_pol)
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        nb = _max_images_per_plan(x)
+        outs = []
+        for i in range(0, x.shape[0], nb):
+            xb = x[i:i + nb].detach()
+            plan = self._plan(xb, base_only=False, per_image=True)
+            outs.append(plan.execute_per_image(xb, [float(_mask_quality(mask_pol, q)) for q in qs[i:i + nb]], self.use_graph, True))
+        return outs[0] if len(outs) == 1 else _cat_outputs(outs)
+
+    @staticmethod
+    def _quality_rows(x, Q, what) -> List[List[float]]:
+        Qt = torch.as_tensor(Q, dtype=torch.float64).cpu()
+        if Qt.dim() == 1:
+            Qt = Qt.unsqueeze(0)
+        if Qt.dim() != 2 or Qt.shape[1] != x.shape[0]:
+            raise ValueError(f"{what}: Q is [T, {x.shape[0]}] (or one row of {x.shape[0]}), got shape {tuple(Qt.shape)}")
+        if not bool((Qt >= 0).all()):
+            raise ValueError(f"{what}: qualities must be >= 0 (and not NaN)")
+        return Qt.tolist()
+
+    def forward_qualities_per_image(self, x, Q, mask_pol=None):
+        """One result dict per row of ``Q`` [T, B] (a [B] vector: T = 1), shaped like :meth:`forward_qualities`' results, with
+        image b of row t at quality Q[t][b].  A row is all zero (the base dict) or all positive.  Eligible models
+        (:meth:`_sweep_eligible`) run one front end per sub-batch and the per-image tails in sweep_groups' groups; the
+        others run :meth:`forward_per_image` per positive row."""
+        rows = self._quality_rows(x, Q, "forward_qualities_per_image")
+        for t, row in enumerate(rows):
+            if any(q == 0 for q in row) and any(q != 0 for q in row):
+                raise ValueError(f"forward_qualities_per_image: row {t} mixes quality 0 (the base plan) with positive "
+                                 "qualities; a row is all zero or all positive")
+        mask_pol = self.mask_policy if mask_pol is None else mask_pol
+        if not self._sweep_eligible():
+            return [self.forward_single_quality(x, 0, mask_pol, training=False) if row[0] == 0 else
+                    self.forward_per_image(x, row, mask_pol) for row in rows]
+        parts: List[list] = [[] for _ in rows]
+        self._sweep(x, rows, mask_pol, self._sweep_dicts(parts), per_image=True)
         return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
+
+    def compress_per_image(self, x, qualities, mask_pol=None):
+        """``compress(x[b:b+1], qualities[b], mask_pol)`` for every image, as a list of B dicts {"strings", "shape",
+        "quality"} whose strings and shape are exactly that call's.  The images at quality 0 run the base symbols plan as
+        one sub-batch, the others the per-image symbols plan (one graph whatever the qualities); all streams are coded by
+        the threaded stream coder (bitstream.encode_streams).  Models that cannot share a batch loop over compress."""
+        from . import bitstream as bs
+        qs = self._quality_vector(x, qualities, "compress_per_image", allow_zero=True)
+        if not self._batch_shareable():
+            items = []
+            for b, q in enumerate(qs):
+                out = self.compress(x[b:b + 1], q, mask_pol)
+                items.append({"strings": out["strings"], "shape": out["shape"], "quality": q})
+            return items
+        mask_pol = self._mask_policy(mask_pol)
+        Ly._no_autograd(x)
+        L.require_gpu()
+        self._check_config()
+        if self.gaussian_conditional.scale_table.numel() == 0:
+            raise ValueError("empty scale table: call model.update() before compress()")
+        tg, te = bs.Tables.of(self.gaussian_conditional), bs.Tables.of(self.entropy_bottleneck)
+        C, nb = self.dim_chunk, _max_images_per_plan(x)
+        y_jobs, z_jobs, where = [], [], []                  # where: (image, number of y streams) per image, in job order
+        with torch.no_grad():
+            for base_only, ids in ((True, [b for b, q in enumerate(qs) if q == 0]), (False, [b for b, q in enumerate(qs) if q != 0])):
+                for i in range(0, len(ids), nb):
+                    sub = ids[i:i + nb]
+                    xb = x[sub].detach().contiguous()
+                    plan = self._plan(xb, base_only=base_only, symbols=True, per_image=not base_only)
+                    if base_only:
+                        plan.execute(xb, 0.0, None, self.use_graph, False)
+                    else:
+                        plan.execute_per_image(xb, [float(_mask_quality(mask_pol, qs[b])) for b in sub], self.use_graph, False)
+                    sym = plan.sym.buf.cpu().numpy()           # [b,h,w,C_lat] int32 (synchronises)
+                    idx = plan.idx.buf.cpu().numpy()
+                    zs = plan.z_sym.buf.cpu().numpy()
+                    zi = np.broadcast_to(np.arange(self.N, dtype=np.int32)[:, None, None], (self.N,) + zs.shape[1:3])
+                    n_sl = self.ns0 if base_only else self.ns1
+                    for k, b in enumerate(sub):                 # stream order: [C, h, w] per image, as compress flattens
+                        for s_ in range(n_sl):
+                            ch = slice(s_ * C, (s_ + 1) * C)
+                            y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
+                        z_jobs.append((zs[k].transpose(2, 0, 1), zi))
+                        where.append((b, n_sl))
+        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+        items: List[Optional[dict]] = [None] * len(qs)
+        shape = (x.shape[2] // 64, x.shape[3] // 64)
+        o = 0
+        for k, (b, n_sl) in enumerate(where):
+            items[b] = {"strings": [[[s_] for s_ in ys[o:o + n_sl]], [zstr[k]]], "shape": shape, "quality": qs[b]}
+            o += n_sl
+        return items
+
+    def decompress_per_image(self, items, mask_pol=None):
+        """{"x_hat": [B, 3, H, W]} from the list :meth:`compress_per_image` returns (same ``shape`` everywhere), in order:
+        image b is what ``decompress(strings_b, shape, quality_b)`` returns.  Zeros and positives are sub-batched as in
+        :meth:`compress_per_image`; the per-slice masks of the positives read each image's quality from a device table."""
+        items = list(items)
+        if not items:
+            raise ValueError("decompress_per_image: no items")
+        shape = tuple(int(v) for v in items[0]["shape"])
+        if any(tuple(int(v) for v in it["shape"]) != shape for it in items):
+            raise ValueError("decompress_per_image: all items must have the same shape; decode other shapes in a call of their own")
+        qs = [float(it["quality"]) for it in items]
+        if any(not q >= 0 for q in qs):
+            raise ValueError("decompress_per_image: qualities must be >= 0 (and not NaN)")
+        if not self._batch_shareable():
+            return {"x_hat": torch.cat([self.decompress(it["strings"], shape, q, mask_pol)["x_hat"] for it, q in zip(items, qs)], 0)}
+        mask_pol = self._mask_policy(mask_pol)
+        L.require_gpu()
+        self._check_config()
+        dev = self.entropy_bottleneck.quantiles.device
+        hz, wz = shape
+        nb = max(1, MAX_PLAN_PIXELS // (hz * wz * 64 * 64))
+        x_hat = torch.empty((len(items), 3, hz * 64, wz * 64), dtype=torch.float32, device=dev)
+        for base_only, ids in ((True, [b for b, q in enumerate(qs) if q == 0]), (False, [b for b, q in enumerate(qs) if q != 0])):
+            n_sl = self.ns0 if base_only else self.ns1
+            for i in range(0, len(ids), nb):
+                sub = ids[i:i + nb]
+                for b in sub:
+                    if len(items[b]["strings"][0]) < n_sl or len(items[b]["strings"][1]) != 1:
+                        raise ValueError(f"decompress_per_image: item {b}: expected {n_sl} slice streams and one z stream of one image")
+                strings = [[[items[b]["strings"][0][s_][0] for b in sub] for s_ in range(n_sl)], [items[b]["strings"][1][0] for b in sub]]
+                if base_only:
+                    x_hat[sub] = self.decompress(strings, shape, 0, mask_pol)["x_hat"]
+                    continue
+
+                def build(B=len(sub)):
+                    if ops.f16x2_mode():
+                        raise NotImplementedError(F16X2_REFUSAL)
+                    return _DecPlan(self, B, hz, wz, False, None, dev, per_image=True)
+                dp = self._cached_plan(self._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image"), build, self._weights_sig())
+                x_hat[sub] = dp.decode(strings, [float(_mask_quality(mask_pol, qs[b])) for b in sub], None)
+        return {"x_hat": x_hat}
+
+    def _per_image_budget(self, x, target, what) -> torch.Tensor:
+        """[1, B] float64 budgets from a scalar or B values."""
+        t = torch.as_tensor(target, dtype=torch.float64).cpu().reshape(-1)
+        B = x.shape[0]
+        if t.numel() == 1:
+            t = t.repeat(B)
+        if t.numel() != B:
+            raise ValueError(f"{what}: one budget, or one per image ({B}), got {t.numel()}")
+        return t.reshape(1, B)
+
+    def compress_to_bytes(self, x, target_bytes, q_tol=1e-3, mask_pol=None):
+        """Compress every image to its own byte budget (``target_bytes``: a number or B numbers): :meth:`qualities_for_bytes`,
+        then :meth:`compress_per_image` at those qualities.  Returns {"items": that list, "quality": float64 [B], "reached":
+        bool [B], "bytes_hi": float64 [B] (the guaranteed upper size)}.  Where ``reached``, the item's strings weigh at most
+        the budget (they are the strings of compress(x[b:b+1], q_b): the guarantee of qualities_for_bytes); elsewhere the
+        item is the base (quality 0)."""
+        sol = self.qualities_for_bytes(x, self._per_image_budget(x, target_bytes, "compress_to_bytes"), q_tol, mask_pol)
+        q = sol["quality"][0]
+        return {"items": self.compress_per_image(x, q.tolist(), mask_pol), "quality": q, "reached": sol["reached"][0],
+                "bytes_hi": sol["bytes"][0]}
+
+    def compress_to_bpp(self, x, target_bpp, q_tol=1e-3, mask_pol=None):
+        """Compress every image to its own estimated-rate budget (``target_bpp``: a number or B numbers):
+        :meth:`qualities_for_bpp`, then :meth:`compress_per_image`.  Returns {"items", "quality" [B], "reached" [B], "bpp" [B]
+        (the estimated bpp at that quality; the coded size is not bounded by it)}."""
+        sol = self.qualities_for_bpp(x, self._per_image_budget(x, target_bpp, "compress_to_bpp"), q_tol, mask_pol)
+        q = sol["quality"][0]
+        return {"items": self.compress_per_image(x, q.tolist(), mask_pol), "quality": q, "reached": sol["reached"][0],
+                "bpp": sol["bpp"][0]}
 
     # ---- rate control: the rate of many qualities without the per-quality tail (DESIGN section 9h)
     _REM_RATE_REFUSAL = ("rate control on REM models: the rate at a quality q needs the checkpoint representation of q's "
@@ -1024,6 +1235,12 @@ F16X2_REFUSAL = ("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-for
                  "bitstream path (encoder and decoder must agree bit for bit) and training run in the default bf16x3 arithmetic")
 
 
+def _mask_table_buffer(B: int, device) -> torch.Tensor:
+    """A plan's device table for ops.variance_masks_per_image: one record per image, refilled before each replay."""
+    import ctypes
+    return torch.zeros((B * ctypes.sizeof(L.VamLayerParams),), dtype=torch.uint8, device=device)
+
+
 def _cat_outputs(outs):
     """Concatenate per-sub-batch result dicts along the batch dimension (every image is an independent unit)."""
     def cat(vals):
@@ -1137,8 +1354,12 @@ class _FsqPlan:
     """``forward_single_quality`` for one (B,H,W) lowered to libvampic launches."""
 
     def __init__(self, m: VarianceMaskingPIC, B, H, W, base_only, rem_idx, device, symbols=False, train=False,
-                 own_ck=False, train_gs=False, train_lrp=False, sweep=False):
+                 own_ck=False, train_gs=False, train_lrp=False, sweep=False, per_image=False):
         assert not sweep or (m.all_scalable and not base_only and rem_idx is None and not (symbols or train))
+        # per_image: the variance masks read each image's quality from a device table (DESIGN section 9j)
+        assert not per_image or not (sweep or base_only or train or own_ck or rem_idx is not None)
+        self.per_image = per_image
+        self.qtable = _mask_table_buffer(B, device) if per_image else None
         self.m, self.B, self.H, self.W = m, B, H, W
         self.train_gs = train_gs    # the synthesis transform in use is being trained (refine_gs): taped g_s + backward plan
         self.train_lrp = train_lrp  # ... and the progressive LRP stacks with it (refine_gs --lrp)
@@ -1325,7 +1546,7 @@ class _FsqPlan:
                                [msups[j] + [sl(rq_ck, j)] for j in range(ns)], [sl(self.ck, j) for j in range(ns)],
                                [dict(act=L.ACT_HALF_TANH, post=sl(rq_ck, j), post2=sl(yb, j)) for j in range(ns)], heads=heads)
             att = self.att = plan.buf(B, h, w, d)
-            plan.call(lambda: ops.variance_mask(self.std_p, self.pr, att, n_slice=ns))
+            plan.call(lambda: self._vmask(self.std_p, att, ns))
             std_f = plan.buf(B, h, w, d)
             mu_f = plan.buf(B, h, w, d) if mu_std else self.mu_p      # without mu_std only sigma is refined (rem_pic.py:214-218)
             mods = [m.post_latent[rem_idx][j] for j in range(ns)]
@@ -1347,7 +1568,7 @@ class _FsqPlan:
         self.mask = plan.buf(B, h, w, d)
         self.thr = torch.empty((B * ns,), **f32)
         plan.keep.append(self.thr)
-        plan.call(lambda: ops.variance_mask(std_f, self.pr, self.mask, n_slice=ns, thr=self.thr))   # pic.py:621-622
+        plan.call(lambda: self._vmask(std_f, self.mask, ns, self.thr))                              # pic.py:621-622
         rq = plan.buf(B, h, w, d)
         plan.call(lambda: ops.gauss_tail(y_top, mu_f, std_f, y2=y_sub, mask=self.mask, yhat=rq,
                                          lik=self.lik.window(d, d), log2sum=ls_y,
@@ -1463,11 +1684,11 @@ class _FsqPlan:
             E.lower_stacks(plan, [m.cc_mean_transforms_prog[j], m.cc_scale_transforms_prog[j]], [ms, ss],
                            [sl(self.mu_p, j), sl(self.std_p, j)], heads=heads)
             if rem_idx is not None:                                                   # rem_pic.py:363-377
-                plan.call(lambda j=j: ops.variance_mask(sl(self.std_p, j), self.pr, sl(att, j), n_slice=1))
+                plan.call(lambda j=j: self._vmask(sl(self.std_p, j), sl(att, j), 1))
                 E.lower_rem_blocks(plan, [m.post_latent[rem_idx][j]], [sl(self.ck, j)], [[sl(self.mu_b, j), sl(self.std_b, j)]],
                                    [([sl(self.mu_p, j)] if mu_std else []) + [sl(self.std_p, j)]], [sl(att, j)],
                                    [([sl(mu_f, j)] if mu_std else []) + [sl(std_f, j)]])
-            plan.call(lambda j=j: ops.variance_mask(sl(std_f, j), self.pr, sl(self.mask, j), n_slice=1))          # pic.py:621-622
+            plan.call(lambda j=j: self._vmask(sl(std_f, j), sl(self.mask, j), 1))                                 # pic.py:621-622
             plan.call(lambda j=j: ops.gauss_tail(sl(y_top, j), sl(mu_f, j), sl(std_f, j), y2=sl(y_sub, j) if y_sub is not None else None,
                                                  mask=sl(self.mask, j), yhat=sl(rq, j), lik=sl(self.lik, ns + j), log2sum=ls_y,
                                                  sym=sl(self.sym, ns + j) if symbols else None))                  # pic.py:625-629
@@ -1475,6 +1696,14 @@ class _FsqPlan:
                 plan.call(lambda j=j: ops.build_indexes(sl(std_f, j), table, mask=sl(self.mask, j), out=sl(self.idx, ns + j)))
             E.lower_stacks(plan, [m.lrp_transforms_prog[j]], [ms + [sl(rq, j)]], [sl(yp, j)],
                            [dict(act=L.ACT_HALF_TANH, post=sl(rq, j), post2=sl(yb, j))], heads=heads)              # pic.py:635-641
+
+    def _vmask(self, sigma, mask, n_slice, thr=None):
+        """The variance mask at this execute's quality: the scalar ``pr``, or (per_image plans) each image's own, read from
+        the plan's device table — one level, the same segments, so the same bits per image."""
+        if self.per_image:
+            ops.variance_masks_per_image(sigma, self.qtable, mask, n_slice=n_slice, thr=thr)
+        else:
+            ops.variance_mask(sigma, self.pr, mask, n_slice=n_slice, thr=thr)
 
     # -------------------------------------------------------------------------------------------
     def close(self):
@@ -1506,6 +1735,22 @@ class _FsqPlan:
                 ck = ops.from_nchw(checkpoint_ref.to(self.x_in.device))
                 self.ck.buf.copy_(ck.buf[..., ck.c0:ck.c0 + ck.C])
             self.runner.replay((self.pr, self.ck_pr), self.plan.run, use_graph)
+        return self._outputs(clone)
+
+    def execute_per_image(self, x, prs: Sequence[float], use_graph, clone=True):
+        """:meth:`execute` of a per_image plan with image b at mask quality ``prs[b]`` (> 0).  The table is refilled on the
+        runner's stream before the replay, outside the capture; the qualities are inputs of the plan's ONE graph."""
+        assert self.per_image and len(prs) == self.B
+        self.generation += 1
+        h, w = self.H // 16, self.W // 16
+        table = ops.mask_table([[p_] for p_ in prs], h * w, self.m.dim_chunk)
+        with self.runner.on_stream():
+            self.x_in.copy_(x)
+            self.qtable.copy_(torch.from_numpy(table))
+            self.runner.replay(("per_image",), self.plan.run, use_graph)
+        return self._outputs(clone)
+
+    def _outputs(self, clone):
         fin = (lambda t: t.clone()) if clone else (lambda t: t)
         nchw = lambda v: fin(v.torch_nchw())
         out = {"x_hat": fin(self.x_hat),
@@ -1796,7 +2041,10 @@ class _SweepTail:
     over the plan's symbols and container layer ids, with the container-layer cut-offs ``ks`` in place of the qualities
     (level g keeps the elements of layers <= ks[g]); no masks and no likelihoods.  The rest of the tail is the same."""
 
-    def __init__(self, fp, n_levels: int, decode: bool = False):
+    def __init__(self, fp, n_levels: int, decode: bool = False, per_image: bool = False):
+        """``per_image``: level g of image b is masked at that image's own quality, read from ``qtable`` (which
+        _SweepPlan.tail_per_image refills before each replay); the rest of the tail is the same."""
+        assert not (decode and per_image)
         m, parts = fp.m, fp.sweep_parts
         yb0 = parts["yb"]
         B, h, w = yb0.B, yb0.H, yb0.W
@@ -1809,7 +2057,9 @@ class _SweepTail:
         self.prs = (0.0,) * NL            # eval: the mask qualities of the levels
         self.ks = (0,) * NL               # decode: the container-layer cut-offs of the levels
         self.runner = E.Runner(dev, cap=32)     # one graph per tuple of levels, replayed on the owner's stream
+        self.qtable = _mask_table_buffer(B, dev) if per_image else None
         P = self.plan = E.Plan(dev)
+        P.keep.append(self.qtable)
         sl = lambda v, i, n=1: v.window(i * C, n * C)
         self.log2sum = torch.zeros((NL, B), dtype=torch.float64, device=dev)      # level k's progressive log2 sums per image
         self.x_hat = torch.empty((LB, 3, H, W), dtype=torch.float32, device=dev)
@@ -1831,7 +2081,11 @@ class _SweepTail:
         else:
             self.mask, self.lik = P.buf(LB, h, w, d), P.buf(LB, h, w, d)
             P.call(lambda: ops.memset_zero(self.log2sum))
-            P.call(lambda: ops.variance_mask_levels(parts["std"], self.prs, self.mask, n_slice=ns), "variance masks (sweep)")   # :621-622
+            if per_image:
+                P.call(lambda: ops.variance_masks_per_image(parts["std"], self.qtable, self.mask, n_slice=ns),
+                       "variance masks per image (sweep)")
+            else:
+                P.call(lambda: ops.variance_mask_levels(parts["std"], self.prs, self.mask, n_slice=ns), "variance masks (sweep)")   # :621-622
             P.call(lambda: ops.gauss_levels_eval(parts["y_top"], parts["mu"], parts["std"], self.mask, NL, y2=parts["y_sub"],
                                                  yhat=self.rq, lik=self.lik, log2sum=self.log2sum), "quantise + likelihood (sweep)")   # :625-629
         P.call(replicate, "supports per level")
@@ -1867,6 +2121,7 @@ class _SweepPlan:
         self.p_base.set_class("g_s")
         E.lower_g_s(self.p_base, [m.g_s[0] if m.multiple_decoder else m.g_s], [self.fp.y_base], [self.fp.x_hat])
         self.tails: Dict[int, _SweepTail] = {}
+        self.pi_tails: Dict[int, _SweepTail] = {}        # per-image qualities: one plan AND one graph per group size
         self.rate_tails: Dict[int, _RateTail] = {}
         self.size_tail: Optional[_SizeTail] = None
         self.runner = E.Runner(device, cap=32)           # ("front",) and ("base",); the tails run on its stream
@@ -1887,6 +2142,20 @@ class _SweepPlan:
         t.prs = tuple(float(p_) for p_ in prs)
         with self.runner.on_stream():
             t.runner.replay(t.prs, t.plan.run, use_graph)
+        return t
+
+    def tail_per_image(self, Q_group: Sequence[Sequence[float]], use_graph: bool) -> _SweepTail:
+        """:meth:`tail` with level g of image b at mask quality ``Q_group[g][b]``."""
+        n = len(Q_group)
+        assert all(len(row) == self.B for row in Q_group)
+        t = self.pi_tails.get(n)
+        if t is None:
+            t = self.pi_tails[n] = _SweepTail(self.fp, n, per_image=True)
+        sg = self.fp.sweep_parts["std"]
+        table = ops.mask_table([[float(Q_group[g][b]) for g in range(n)] for b in range(self.B)], sg.H * sg.W, self.m.dim_chunk)
+        with self.runner.on_stream():
+            t.qtable.copy_(torch.from_numpy(table))
+            t.runner.replay(("per_image",), t.plan.run, use_graph)
         return t
 
     def _rate_tail(self, n_levels: int) -> _RateTail:
@@ -2015,7 +2284,8 @@ class _SweepPlan:
     def close(self):
         self.fp.close()
         self.runner.close()
-        for t in list(self.tails.values()) + list(self.rate_tails.values()) + ([self.size_tail] if self.size_tail else []):
+        for t in list(self.tails.values()) + list(self.pi_tails.values()) + list(self.rate_tails.values()) + \
+                ([self.size_tail] if self.size_tail else []):
             t.close()
 
 
@@ -2025,10 +2295,15 @@ class _DecPlan:
     kernel's K order is canonical, so mu / sigma / masks / indexes are bit-identical to the
     encoder's although the launches are grouped differently."""
 
-    def __init__(self, m: VarianceMaskingPIC, B, hz, wz, base_only, rem_idx, device, prog_chain: bool = False):
+    def __init__(self, m: VarianceMaskingPIC, B, hz, wz, base_only, rem_idx, device, prog_chain: bool = False,
+                 per_image: bool = False):
         """``prog_chain``: stop after the base slices (hyper-synthesis of both halves and every stack head included) and
-        keep g_s[0] on y_hat_base in ``p_syn``; _ProgDecPlan lowers the progressive part itself."""
+        keep g_s[0] on y_hat_base in ``p_syn``; _ProgDecPlan lowers the progressive part itself.  ``per_image``: the
+        per-slice masks read each image's quality from ``qtable`` (decode_per_image refills it)."""
+        assert not per_image or not (base_only or prog_chain or rem_idx is not None)
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
+        self.per_image = per_image
+        self.qtable = _mask_table_buffer(B, device) if per_image else None
         self.rem_sig = _version_sig(m.post_latent[rem_idx]) if rem_idx is not None else None
         self.device = torch.device(device)
         self.pr = 0.0
@@ -2096,17 +2371,24 @@ class _DecPlan:
             if m.total_mu_rep:
                 Pa.call(lambda j=j: ops.add(sl(mu_p, j), sl(yb, j), sl(mu_tot, j)))
             if rem_idx is not None:
-                Pa.call(lambda j=j: ops.variance_mask(sl(std_p, j), self.pr, sl(att, j), n_slice=1))
+                Pa.call(lambda j=j: self._vmask(sl(std_p, j), sl(att, j)))
                 E.lower_rem_blocks(Pa, [m.post_latent[rem_idx][j]], [sl(self.ck, j)], [[sl(mu_b, j), sl(std_b, j)]],
                                    [([sl(mu_p, j)] if mu_std else []) + [sl(std_p, j)]], [sl(att, j)],
                                    [([sl(mu_f, j)] if mu_std else []) + [sl(std_f, j)]])
-            Pa.call(lambda j=j: ops.variance_mask(sl(std_f, j), self.pr, sl(mask, j), n_slice=1))       # pic.py:942
+            Pa.call(lambda j=j: self._vmask(sl(std_f, j), sl(mask, j)))                                 # pic.py:942
             Pa.call(lambda j=j: ops.build_indexes(sl(std_f, j), table, mask=sl(mask, j), out=sl(self.idx_p, j)))  # :945
             Pb.call(lambda j=j: ops.dequantize(sl(self.sym_p, j), sl(mu_f, j), sl(rq, j)))               # :948
             E.lower_stacks(Pb, [m.lrp_transforms_prog[j]], [ms + [sl(rq, j)]], [sl(yp, j)],
                            [dict(act=L.ACT_HALF_TANH, post=sl(rq, j), post2=sl(yb, j))], heads=heads)
             self.p_prog.append((Pa, Pb))
         E.lower_g_s(self.p_syn, [m.g_s[1] if m.multiple_decoder else m.g_s], [yp], [self.x_hat])
+
+    def _vmask(self, sigma, mask):
+        """One slice's mask at this decode's quality: the scalar ``pr``, or (per_image) each image's own from the table."""
+        if self.per_image:
+            ops.variance_masks_per_image(sigma, self.qtable, mask, n_slice=1)
+        else:
+            ops.variance_mask(sigma, self.pr, mask, n_slice=1)
 
     def _decode_slice(self, strings, idx_view: ops.IView, sym_view: ops.IView, tables, C):
         """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window)."""
@@ -2136,9 +2418,16 @@ class _DecPlan:
             Pb.run()
 
     def decode(self, strings, pr, checkpoint_rep):
+        """``pr``: the mask quality, or (per_image plans) one per image."""
         from . import bitstream as bs
         m = self.m
-        self.pr = float(pr)
+        if self.per_image:
+            assert len(pr) == self.B
+            table = ops.mask_table([[float(p_)] for p_ in pr], self.h * self.w, m.dim_chunk)
+            with self.runner.on_stream():
+                self.qtable.copy_(torch.from_numpy(table))
+        else:
+            self.pr = float(pr)
         y_strings, z_strings = strings[0], strings[1]
         n_need = m.ns0 if self.base_only else m.ns1
         if len(y_strings) < n_need or len(z_strings) != self.B:

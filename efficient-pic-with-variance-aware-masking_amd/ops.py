@@ -556,6 +556,48 @@ def variance_layers_per_image(sigma: View, prs: Sequence[Sequence[float]], layer
             "vam_variance_layers_per_image")        # `dev` returns to the allocator of this same stream
 
 
+def mask_table(prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int) -> np.ndarray:
+    """The host bytes (uint8, one L.VamLayerParams record per image) of the table :func:`variance_masks_per_image` reads:
+    image b's qualities ``prs_per_image[b]`` (1..L.VAM_MAX_MASK_LEVELS, any order, repeats allowed) for segments of
+    ``n_pix`` pixels x ``C_`` channels.  Host arithmetic only (vam_variance_mask_params)."""
+    lists = [[float(p_) for p_ in row] for row in prs_per_image]
+    B = len(lists)
+    width = max([len(r) for r in lists] + [1])
+    flat = (C.c_double * (width * max(B, 1)))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
+    nl = (C.c_int * max(B, 1))(*[len(r) for r in lists])
+    table = np.zeros(B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
+    L.check(L.load().vam_variance_mask_params(flat, nl, B, width, n_pix, C_, table.ctypes.data), "vam_variance_mask_params")
+    return table
+
+
+def variance_masks_per_image(sigma: View, table_dev: torch.Tensor, mask: View, n_slice: int = 1,
+                             level_stride: Optional[int] = None, thr: Optional[torch.Tensor] = None,
+                             max_levels: Optional[int] = None):
+    """:func:`variance_mask_levels` with image b's quality list read from record b of ``table_dev`` (the bytes of
+    :func:`mask_table` on the device), so the call can be captured and the captured graph serves every table content.
+    Level l's mask is ``mask`` shifted by l * ``level_stride`` floats (default: ``mask`` holds [L * B, H, W, ld] and the
+    table may hold up to L = mask.B // sigma.B levels per image; with an explicit stride ``max_levels`` says how many
+    the buffers hold); ``thr`` [L, B * n_slice].  Bit-identical per (image, level) to :func:`variance_mask` on that image."""
+    slice_C = sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
+    hw = sigma.H * sigma.W
+    if level_stride is None:
+        assert mask.B % sigma.B == 0 and mask.B >= sigma.B, (mask.B, sigma.B)
+        max_levels = mask.B // sigma.B if max_levels is None else max_levels
+        assert max_levels * sigma.B <= mask.B
+        level_stride = sigma.B * hw * mask.ld
+    assert max_levels is not None and 1 <= max_levels <= L.VAM_MAX_MASK_LEVELS, max_levels
+    # the last element the kernel may write lies inside the mask's buffer
+    assert level_stride >= 0 and mask.c0 + (max_levels - 1) * level_stride + (sigma.B * hw - 1) * mask.ld + mask.C <= mask.buf.numel()
+    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
+        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
+    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= max_levels * sigma.B * n_slice)
+    L.check(L.load().vam_variance_masks_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
+                                                  table_dev.data_ptr(), max_levels, mask.ptr, mask.ld, hw * mask.ld, slice_C,
+                                                  level_stride, thr.data_ptr() if thr is not None else None, stream_ptr()),
+            "vam_variance_masks_per_image")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

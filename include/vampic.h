@@ -305,6 +305,19 @@ int vam_variance_layers_per_image(const float* sigma, int ld, long batch_stride,
                                   int n_slice, int n_pix, int C, const vam_layer_params* table_dev, uint8_t* layer_out,
                                   int ld_layer, long layer_batch_stride, long layer_slice_stride, float* thr_out,
                                   void* stream);
+/* vam_variance_mask_levels with a quality list PER IMAGE, read from a device table (one captured graph then serves every
+ * quality vector: the qualities are graph inputs).  vam_variance_mask_params is vam_variance_layer_params
+ * for these lists: 1 <= n_levels[b] <= VAM_MAX_MASK_LEVELS qualities per image, in any order, repeats allowed.  The kernel
+ * writes level l of image b at mask_out + l*mask_level_stride + b*mask_batch_stride + j*mask_slice_stride (float 0/1) and
+ * its threshold at thr_out[l*n_batch*n_slice + b*n_slice + j], for l < n_levels[b]; rows beyond an image's count are left
+ * alone.  max_levels = the levels mask_out and thr_out hold (1..VAM_MAX_MASK_LEVELS): a record with more writes nothing.
+ * Mask and threshold of every (b, l) equal vam_variance_mask on image b alone with that quality, bit for bit. */
+int vam_variance_mask_params(const double* prs, const int* n_levels, int n_batch, int levels_stride, int n_pix, int C,
+                             vam_layer_params* table_host);
+int vam_variance_masks_per_image(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch,
+                                 int n_slice, int n_pix, int C, const vam_layer_params* table_dev, int max_levels,
+                                 float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
+                                 long mask_level_stride, float* thr_out, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
