@@ -12,7 +12,11 @@ across ranks (independent units, no data-path collective): weak scaling, whole-j
 ``python -m torch.distributed.run``, before anything here touches the GPU) and relays rank 0's line; under an
 external ``torch.distributed.run`` (RANK / WORLD_SIZE set) it is one of the ranks.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run does only what the headline needs: set up, warm up, time the steps, write ``--dump-outputs`` if asked, and
+print ONE JSON line (rank 0) with the driver's contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``,
+``dtype``, ``ms_per_step``) and the run's configuration; its ``roofline`` is null.  Everything else the benchmark measures
+or checks takes runs of its own and sits behind ``--full`` (off by default; ``--no-cpu-baseline`` / ``--no-bf16`` /
+``--no-train`` drop single legs of a ``--full`` run).  With ``--full`` the line also carries
   roofline      dominant kernel (conv_igemm_kernel) measured live with HIP events on the launch stream: algorithmic
                 FLOP / summed launch time.  Default arithmetic: every fp32 operand split exactly into three bf16 terms,
                 six partial products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -> ceiling 2500 / 6 = 416.7
@@ -21,6 +25,10 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
                 40 % target names) and ``roofline.classes`` the per-class split (ms, TF/s per step).
   cpu_baseline  the CPU oracle (port of the reference's math, ATen CPU ops) on a bounded sample, all host cores this
                 process may use, median of 5 runs after 2 warm-ups
+  bf16          the same steps with bf16 storage of the large g_a / g_s feature maps, timed the same way and compared with
+                the fp32 result (``--dtype bf16`` makes that storage the headline instead; ``vs_fp32`` is then its distance
+                to the fp32 path)
+  train         one first_train step and one REM fine-tune step (BASELINE configs[3] / [4]) on this GPU's share
 
 ``--dump-outputs DIR`` writes what the last timed step returned (rank 0) as DIR/<name>.npy (``dump_outputs``); weights and
 inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -224,12 +232,16 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 (default, the headline and every parity claim) or bf16: BASELINE configs[2] storage mode — g_a / g_s "
                          "feature maps >= 64x64 stored in bf16, bf16-rounded weights there, fp32 accumulation; its distance to "
-                         "the fp32 path (mask XOR, dPSNR, dbpp) is measured and printed in the line")
+                         "the fp32 path (mask XOR, dPSNR, dbpp) is measured and printed in the line by a --full run")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the secondary bf16-storage measurement of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks: the HIP-event roofline "
+                         "of the convolution launches, the bf16-storage leg (or, with --dtype bf16, the comparison with the fp32 "
+                         "path), the training legs and the CPU baseline.  Off by default: a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--no-bf16", action="store_true", help="skip the secondary bf16-storage measurement of a --full run")
     ap.add_argument("--no-train", action="store_true",
-                    help="skip the secondary training measurements of the default run (BASELINE configs[3] / [4]: first_train and "
+                    help="skip the secondary training measurements of a --full run (BASELINE configs[3] / [4]: first_train and "
                          "REM fine-tune steps on this GPU's share of the batch)")
     ap.add_argument("--dry", action="store_true",
                     help="rehearse rank setup / sharding / aggregation without touching a GPU (CPU test of the N>1 entry)")
@@ -310,7 +322,7 @@ def main():
 
     # ---- roofline of the dominant kernel, measured live with HIP events (eager replay, same plan)
     roof = None
-    if rank == 0:
+    if rank == 0 and a.full:
         net.use_graph = False
         ops.prof_reset()
         ops.prof_enable(True)
@@ -382,7 +394,7 @@ def main():
                                "flop_per_step": gfl / psteps}
 
     vs_fp32 = None
-    if rank == 0 and net32 is not None:
+    if rank == 0 and a.full and net32 is not None:
         with torch.no_grad():
             o32 = net32.forward_single_quality(x, q, clone=True)
             o16 = net.forward_single_quality(x, q, clone=True)
@@ -396,7 +408,7 @@ def main():
     # ---- secondary: the SAME steps under the bf16-storage configuration (BASELINE configs[2]'s arithmetic), timed the same
     # way on rank 0 of a 1-GPU run and compared with the fp32 result just measured.  The headline stays fp32.
     bf16_rec = None
-    if rank == 0 and world == 1 and a.dtype == "f32" and not a.no_bf16:
+    if rank == 0 and a.full and world == 1 and a.dtype == "f32" and not a.no_bf16:
         import copy
         net16 = copy.deepcopy(net)
         net16.storage = "bf16"
@@ -423,7 +435,7 @@ def main():
     # ---- secondary: the training configurations (BASELINE configs[3] first_train, configs[4] REM fine-tune) on this GPU's share
     # of their batches, 5 timed steps each, so that the driver's one line carries them too.  The headline is unchanged.
     train_rec = None
-    if rank == 0 and world == 1 and a.dtype == "f32" and not a.no_train and (B, H, W) == (32, 256, 256):
+    if rank == 0 and a.full and world == 1 and a.dtype == "f32" and not a.no_train and (B, H, W) == (32, 256, 256):
         train_rec = train_legs(dev, dist, forced)
     if rank == 0:
         bpp = -out["log2_likelihood_sum"].sum().item() / (B * H * W)
@@ -451,7 +463,7 @@ def main():
         line["retired_graphs"] = ops.retired_graphs()      # executable graphs kept alive instead of destroyed (ops.Graph docstring)
         if forced:
             line["collectives"] = "forced (1-rank nccl group: barrier + max-over-ranks all-reduce issued on RCCL)"
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, H, W, q)
         print(json.dumps(line), flush=True)
     if dist is not None:

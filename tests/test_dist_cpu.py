@@ -152,6 +152,27 @@ def test_bench_entry_launches_its_own_ranks():
     assert abs(rec["value"] - 2 * 32 * 65536 * 4 / 1e6 / (rec["ms_per_step"] * 4e-3)) / rec["value"] < 1e-3
 
 
+def test_bench_full_option_is_off_by_default():
+    """`bench.py --full` exists and is off by default: a plain run times the headline only, the secondary legs (roofline,
+    bf16, train, cpu_baseline) need the option.  --dry: the option parses and the one-line contract holds either way."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    h = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], env=env, capture_output=True, text=True, timeout=300)
+    assert h.returncode == 0 and "--full" in h.stdout, h.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dry", "--full"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(rec) and rec["steps"] == 2
+
+
 def test_bench_dump_outputs(tmp_path):
     """`bench.py --dump-outputs DIR`: one .npy per tensor of the result (nested keys joined), float32 / float64 only, the
     whole set inside the byte budget, small tensors whole, large ones as the same seeded sample in every run."""
