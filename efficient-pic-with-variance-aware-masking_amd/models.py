@@ -12,6 +12,7 @@ models/pic.py:25-666, models/rem_pic.py:8-422.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -377,14 +378,17 @@ class VarianceMaskingPIC(CompressionModel):
             out["x_hat"] = _FsqTrainFn.apply(plan, out["x_hat"], self.use_graph, *plan.train_params)
         return out
 
-    # ---- rate sweep: many qualities from one front end
+    # ---- sweep, per-image qualities, rate and coded-size control (DESIGN sections 9f, 9h-9j): the drivers are control.py's
+    def _batch_shareable(self) -> bool:
+        """Can images at different qualities share one plan?  REM models (a per-quality REM and checkpoint), bf16 storage
+        and VAMPIC_CONV=f16x2 (their bits depend on how the launches are batched) loop over single images instead."""
+        return not isinstance(self, VarianceMaskingPICREM) and getattr(self, "storage", "fp32") == "fp32" and not ops.f16x2_mode()
+
     def _sweep_eligible(self) -> bool:
         """With all_scalable no quality reaches the front end (g_a, hyperprior, base slices, progressive (mu, sigma)
-        chain): the sweep computes it once.  REM models (a per-quality REM refines (mu, sigma)), all_scalable=False (the
-        chain reads the decoded slices of each quality), bf16 storage and VAMPIC_CONV=f16x2 (their bits depend on how the
-        launches are batched) run one forward_single_quality per quality instead."""
-        return (self.all_scalable and not isinstance(self, VarianceMaskingPICREM) and getattr(self, "storage", "fp32") == "fp32"
-                and not ops.f16x2_mode())
+        chain): the sweep computes it once.  all_scalable=False (the chain reads the decoded slices of each quality) and
+        the models that cannot share a batch (:meth:`_batch_shareable`) run one forward_single_quality per quality instead."""
+        return self.all_scalable and self._batch_shareable()
 
     def _sweep_plan(self, x) -> "_SweepPlan":
         B, H, W = _check_input(x)
@@ -392,256 +396,41 @@ class VarianceMaskingPIC(CompressionModel):
                                  self._weights_sig())
 
     def _sweep(self, x, qualities, mask_pol, emit, per_image: bool = False):
-        """Run the sweep over ``qualities`` and hand each result to ``emit(i0, i1, sweep_plan, tail, ks)`` while its buffers
-        hold it (the next group overwrites them): images i0..i1 of x; ``tail`` None = the base reconstruction (the entries
-        ks of ``qualities`` equal to 0), else a _SweepTail whose level g is quality ``qualities[ks[g]]``.  ``emit`` runs on
-        the caller's stream, ordered after the group and before the next one.  ``per_image``: every entry of ``qualities``
-        is a row of B qualities, one per image; the base is emitted for the rows that hold a 0 anywhere, a tail level for
-        the rows that hold a positive quality anywhere (a 0 inside such a row masks everything out: the caller takes that
-        image from the base)."""
-        mask_pol = self._mask_policy(mask_pol)
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        if per_image:
-            lv = [k for k, row in enumerate(qualities) if any(q != 0 for q in row)]
-            zeros = [k for k, row in enumerate(qualities) if any(q == 0 for q in row)]
-        else:
-            lv = [k for k, q in enumerate(qualities) if q != 0]
-            zeros = [k for k, q in enumerate(qualities) if q == 0]
-        B, _, H, W = x.shape
-        for i0, i1, groups in sweep_groups(len(lv), B, H, W):
-            xb = x[i0:i1].detach()
-            sw = self._sweep_plan(xb)
-            sw.front(xb, self.use_graph)
-            if zeros:
-                sw.base(self.use_graph)
-                emit(i0, i1, sw, None, zeros)
-            for l0, l1 in groups:
-                ks = lv[l0:l1]
-                if per_image:
-                    t = sw.tail_per_image([[float(_mask_quality(mask_pol, q)) for q in qualities[k][i0:i1]] for k in ks],
-                                          self.use_graph)
-                else:
-                    t = sw.tail([float(_mask_quality(mask_pol, qualities[k])) for k in ks], self.use_graph)
-                emit(i0, i1, sw, t, ks)
+        return control._sweep(self, x, qualities, mask_pol, emit, per_image)
 
     def forward_qualities(self, x, qualities, mask_pol=None):
         """One ``forward_single_quality(x, q, mask_pol, training=False)`` result dict per quality of the list, in list
         order (same keys, shapes and — log2_likelihood_sum up to its float64 summation order — bits; cloned tensors).
         Eligible models (:meth:`_sweep_eligible`) run the front end once for the whole list and the per-quality tail
         batched over the levels; the others loop."""
-        qualities = list(qualities)
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if not self._sweep_eligible():
-            return [self.forward_single_quality(x, q, mask_pol, training=False) for q in qualities]
-        parts: List[list] = [[] for _ in qualities]
-        self._sweep(x, qualities, mask_pol, self._sweep_dicts(parts))
-        return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
-
-    def _sweep_dicts(self, parts: List[list]):
-        """An ``emit`` for :meth:`_sweep` that appends to ``parts[k]`` the result dict of entry k for each sub-batch."""
-        d = self.division_dimension[0]
-
-        def emit(i0, i1, sw, t, ks):
-            fp = sw.fp
-            nchw = lambda v: v.torch_nchw().clone()
-            for g, k in enumerate(ks):
-                if t is None:                                           # pic.py:558: the base reconstruction
-                    yh = nchw(fp.y_base)
-                    parts[k].append({"x_hat": fp.x_hat.clone(),
-                                     "likelihoods": {"y": nchw(fp.lik.window(0, d)), "z": nchw(fp.z_lik)},
-                                     "log2_likelihood_sum": fp.log2sum.clone(),
-                                     "y_hat": yh, "y_base": yh, "y_prog": yh, "mu": nchw(fp.mu_b), "std": nchw(fp.std_b),
-                                     "mu_base": nchw(fp.mu_b), "std_base": nchw(fp.std_b), "mu_prog": [], "std_prog": []})
-                    continue
-                ls = fp.log2sum.clone()
-                ls[0] += t.log2sum[g]
-                yh = nchw(t.level(t.y_prog, g))
-                parts[k].append({"x_hat": t.x_hat[g * t.B:(g + 1) * t.B].clone(),
-                                 "likelihoods": {"y": torch.cat([fp.lik.window(0, d).torch_nchw(),
-                                                                 t.level(t.lik, g).torch_nchw()], 1),
-                                                 "z": nchw(fp.z_lik)},
-                                 "log2_likelihood_sum": ls,
-                                 "y_hat": yh, "y_base": nchw(fp.y_base), "y_prog": yh, "mu_base": nchw(fp.mu_b),
-                                 "mu": nchw(fp.mu_p), "std_base": nchw(fp.std_b), "std": nchw(fp.std_p),
-                                 "mask": nchw(t.level(t.mask, g))})
-        return emit
-
-    # ---- per-image qualities in one batch (DESIGN section 9j)
-    def _batch_shareable(self) -> bool:
-        """Can images at different qualities share one plan?  REM models (a per-quality REM and checkpoint), bf16 storage
-        and VAMPIC_CONV=f16x2 (their bits depend on how the launches are batched) loop over single images instead."""
-        return (not isinstance(self, VarianceMaskingPICREM) and getattr(self, "storage", "fp32") == "fp32"
-                and not ops.f16x2_mode())
-
-    @staticmethod
-    def _quality_vector(x, qualities, what, allow_zero: bool) -> List[float]:
-        qs = [float(q) for q in (qualities.tolist() if torch.is_tensor(qualities) else list(qualities))]
-        if len(qs) != x.shape[0]:
-            raise ValueError(f"{what}: one quality per image, got {len(qs)} for a batch of {x.shape[0]}")
-        bad = [q for q in qs if not q >= 0]
-        if bad:
-            raise ValueError(f"{what}: qualities must be >= 0 (and not NaN), got {bad[0]}")
-        zero = [b for b, q in enumerate(qs) if q == 0]
-        if zero and not allow_zero:
-            raise ValueError(f"{what}: quality 0 runs the base plan (other transforms): split the batch, e.g. "
-                             f"forward_single_quality(x[zero], 0) for zero = {zero} and {what} for the rest")
-        return qs
+        return control.forward_qualities(self, x, qualities, mask_pol)
 
     def forward_per_image(self, x, qualities, mask_pol=None):
         """``forward_single_quality(x[b:b+1], qualities[b], mask_pol, training=False)`` for every image of the batch in ONE
         plan run: the same dict, image b's tensors bit-identical (log2_likelihood_sum up to its float64 summation order).
         ``qualities``: B numbers > 0.  The variance masks read each image's quality from a device table, so the plan keeps
         one hipGraph whatever the qualities.  Models that cannot share a batch (:meth:`_batch_shareable`) loop."""
-        qs = self._quality_vector(x, qualities, "forward_per_image", allow_zero=False)
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if not self._batch_shareable():
-            return _cat_outputs([self.forward_single_quality(x[b:b + 1], q, mask_pol, training=False) for b, q in enumerate(qs)])
-        mask_pol = self._mask_policy(mask_pol)
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        nb = _max_images_per_plan(x)
-        outs = []
-        for i in range(0, x.shape[0], nb):
-            xb = x[i:i + nb].detach()
-            plan = self._plan(xb, base_only=False, per_image=True)
-            outs.append(plan.execute_per_image(xb, [float(_mask_quality(mask_pol, q)) for q in qs[i:i + nb]], self.use_graph, True))
-        return outs[0] if len(outs) == 1 else _cat_outputs(outs)
-
-    @staticmethod
-    def _quality_rows(x, Q, what) -> List[List[float]]:
-        Qt = torch.as_tensor(Q, dtype=torch.float64).cpu()
-        if Qt.dim() == 1:
-            Qt = Qt.unsqueeze(0)
-        if Qt.dim() != 2 or Qt.shape[1] != x.shape[0]:
-            raise ValueError(f"{what}: Q is [T, {x.shape[0]}] (or one row of {x.shape[0]}), got shape {tuple(Qt.shape)}")
-        if not bool((Qt >= 0).all()):
-            raise ValueError(f"{what}: qualities must be >= 0 (and not NaN)")
-        return Qt.tolist()
+        return control.forward_per_image(self, x, qualities, mask_pol)
 
     def forward_qualities_per_image(self, x, Q, mask_pol=None):
         """One result dict per row of ``Q`` [T, B] (a [B] vector: T = 1), shaped like :meth:`forward_qualities`' results, with
         image b of row t at quality Q[t][b].  A row is all zero (the base dict) or all positive.  Eligible models
         (:meth:`_sweep_eligible`) run one front end per sub-batch and the per-image tails in sweep_groups' groups; the
         others run :meth:`forward_per_image` per positive row."""
-        rows = self._quality_rows(x, Q, "forward_qualities_per_image")
-        for t, row in enumerate(rows):
-            if any(q == 0 for q in row) and any(q != 0 for q in row):
-                raise ValueError(f"forward_qualities_per_image: row {t} mixes quality 0 (the base plan) with positive "
-                                 "qualities; a row is all zero or all positive")
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if not self._sweep_eligible():
-            return [self.forward_single_quality(x, 0, mask_pol, training=False) if row[0] == 0 else
-                    self.forward_per_image(x, row, mask_pol) for row in rows]
-        parts: List[list] = [[] for _ in rows]
-        self._sweep(x, rows, mask_pol, self._sweep_dicts(parts), per_image=True)
-        return [p_[0] if len(p_) == 1 else _cat_outputs(p_) for p_ in parts]
+        return control.forward_qualities_per_image(self, x, Q, mask_pol)
 
     def compress_per_image(self, x, qualities, mask_pol=None):
         """``compress(x[b:b+1], qualities[b], mask_pol)`` for every image, as a list of B dicts {"strings", "shape",
         "quality"} whose strings and shape are exactly that call's.  The images at quality 0 run the base symbols plan as
         one sub-batch, the others the per-image symbols plan (one graph whatever the qualities); all streams are coded by
         the threaded stream coder (bitstream.encode_streams).  Models that cannot share a batch loop over compress."""
-        from . import bitstream as bs
-        qs = self._quality_vector(x, qualities, "compress_per_image", allow_zero=True)
-        if not self._batch_shareable():
-            items = []
-            for b, q in enumerate(qs):
-                out = self.compress(x[b:b + 1], q, mask_pol)
-                items.append({"strings": out["strings"], "shape": out["shape"], "quality": q})
-            return items
-        mask_pol = self._mask_policy(mask_pol)
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        if self.gaussian_conditional.scale_table.numel() == 0:
-            raise ValueError("empty scale table: call model.update() before compress()")
-        tg, te = bs.Tables.of(self.gaussian_conditional), bs.Tables.of(self.entropy_bottleneck)
-        C, nb = self.dim_chunk, _max_images_per_plan(x)
-        y_jobs, z_jobs, where = [], [], []                  # where: (image, number of y streams) per image, in job order
-        with torch.no_grad():
-            for base_only, ids in ((True, [b for b, q in enumerate(qs) if q == 0]), (False, [b for b, q in enumerate(qs) if q != 0])):
-                for i in range(0, len(ids), nb):
-                    sub = ids[i:i + nb]
-                    xb = x[sub].detach().contiguous()
-                    plan = self._plan(xb, base_only=base_only, symbols=True, per_image=not base_only)
-                    if base_only:
-                        plan.execute(xb, 0.0, None, self.use_graph, False)
-                    else:
-                        plan.execute_per_image(xb, [float(_mask_quality(mask_pol, qs[b])) for b in sub], self.use_graph, False)
-                    sym = plan.sym.buf.cpu().numpy()           # [b,h,w,C_lat] int32 (synchronises)
-                    idx = plan.idx.buf.cpu().numpy()
-                    zs = plan.z_sym.buf.cpu().numpy()
-                    zi = np.broadcast_to(np.arange(self.N, dtype=np.int32)[:, None, None], (self.N,) + zs.shape[1:3])
-                    n_sl = self.ns0 if base_only else self.ns1
-                    for k, b in enumerate(sub):                 # stream order: [C, h, w] per image, as compress flattens
-                        for s_ in range(n_sl):
-                            ch = slice(s_ * C, (s_ + 1) * C)
-                            y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
-                        z_jobs.append((zs[k].transpose(2, 0, 1), zi))
-                        where.append((b, n_sl))
-        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
-        items: List[Optional[dict]] = [None] * len(qs)
-        shape = (x.shape[2] // 64, x.shape[3] // 64)
-        o = 0
-        for k, (b, n_sl) in enumerate(where):
-            items[b] = {"strings": [[[s_] for s_ in ys[o:o + n_sl]], [zstr[k]]], "shape": shape, "quality": qs[b]}
-            o += n_sl
-        return items
+        return control.compress_per_image(self, x, qualities, mask_pol)
 
     def decompress_per_image(self, items, mask_pol=None):
         """{"x_hat": [B, 3, H, W]} from the list :meth:`compress_per_image` returns (same ``shape`` everywhere), in order:
         image b is what ``decompress(strings_b, shape, quality_b)`` returns.  Zeros and positives are sub-batched as in
         :meth:`compress_per_image`; the per-slice masks of the positives read each image's quality from a device table."""
-        items = list(items)
-        if not items:
-            raise ValueError("decompress_per_image: no items")
-        shape = tuple(int(v) for v in items[0]["shape"])
-        if any(tuple(int(v) for v in it["shape"]) != shape for it in items):
-            raise ValueError("decompress_per_image: all items must have the same shape; decode other shapes in a call of their own")
-        qs = [float(it["quality"]) for it in items]
-        if any(not q >= 0 for q in qs):
-            raise ValueError("decompress_per_image: qualities must be >= 0 (and not NaN)")
-        if not self._batch_shareable():
-            return {"x_hat": torch.cat([self.decompress(it["strings"], shape, q, mask_pol)["x_hat"] for it, q in zip(items, qs)], 0)}
-        mask_pol = self._mask_policy(mask_pol)
-        L.require_gpu()
-        self._check_config()
-        dev = self.entropy_bottleneck.quantiles.device
-        hz, wz = shape
-        nb = max(1, MAX_PLAN_PIXELS // (hz * wz * 64 * 64))
-        x_hat = torch.empty((len(items), 3, hz * 64, wz * 64), dtype=torch.float32, device=dev)
-        for base_only, ids in ((True, [b for b, q in enumerate(qs) if q == 0]), (False, [b for b, q in enumerate(qs) if q != 0])):
-            n_sl = self.ns0 if base_only else self.ns1
-            for i in range(0, len(ids), nb):
-                sub = ids[i:i + nb]
-                for b in sub:
-                    if len(items[b]["strings"][0]) < n_sl or len(items[b]["strings"][1]) != 1:
-                        raise ValueError(f"decompress_per_image: item {b}: expected {n_sl} slice streams and one z stream of one image")
-                strings = [[[items[b]["strings"][0][s_][0] for b in sub] for s_ in range(n_sl)], [items[b]["strings"][1][0] for b in sub]]
-                if base_only:
-                    x_hat[sub] = self.decompress(strings, shape, 0, mask_pol)["x_hat"]
-                    continue
-
-                def build(B=len(sub)):
-                    if ops.f16x2_mode():
-                        raise NotImplementedError(F16X2_REFUSAL)
-                    return _DecPlan(self, B, hz, wz, False, None, dev, per_image=True)
-                dp = self._cached_plan(self._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image"), build, self._weights_sig())
-                x_hat[sub] = dp.decode(strings, [float(_mask_quality(mask_pol, qs[b])) for b in sub], None)
-        return {"x_hat": x_hat}
-
-    def _per_image_budget(self, x, target, what) -> torch.Tensor:
-        """[1, B] float64 budgets from a scalar or B values."""
-        t = torch.as_tensor(target, dtype=torch.float64).cpu().reshape(-1)
-        B = x.shape[0]
-        if t.numel() == 1:
-            t = t.repeat(B)
-        if t.numel() != B:
-            raise ValueError(f"{what}: one budget, or one per image ({B}), got {t.numel()}")
-        return t.reshape(1, B)
+        return control.decompress_per_image(self, items, mask_pol)
 
     def compress_to_bytes(self, x, target_bytes, q_tol=1e-3, mask_pol=None):
         """Compress every image to its own byte budget (``target_bytes``: a number or B numbers): :meth:`qualities_for_bytes`,
@@ -649,33 +438,13 @@ class VarianceMaskingPIC(CompressionModel):
         bool [B], "bytes_hi": float64 [B] (the guaranteed upper size)}.  Where ``reached``, the item's strings weigh at most
         the budget (they are the strings of compress(x[b:b+1], q_b): the guarantee of qualities_for_bytes); elsewhere the
         item is the base (quality 0)."""
-        sol = self.qualities_for_bytes(x, self._per_image_budget(x, target_bytes, "compress_to_bytes"), q_tol, mask_pol)
-        q = sol["quality"][0]
-        return {"items": self.compress_per_image(x, q.tolist(), mask_pol), "quality": q, "reached": sol["reached"][0],
-                "bytes_hi": sol["bytes"][0]}
+        return control.compress_to(self, x, target_bytes, q_tol, mask_pol, control.BYTES, "bytes_hi")
 
     def compress_to_bpp(self, x, target_bpp, q_tol=1e-3, mask_pol=None):
         """Compress every image to its own estimated-rate budget (``target_bpp``: a number or B numbers):
         :meth:`qualities_for_bpp`, then :meth:`compress_per_image`.  Returns {"items", "quality" [B], "reached" [B], "bpp" [B]
         (the estimated bpp at that quality; the coded size is not bounded by it)}."""
-        sol = self.qualities_for_bpp(x, self._per_image_budget(x, target_bpp, "compress_to_bpp"), q_tol, mask_pol)
-        q = sol["quality"][0]
-        return {"items": self.compress_per_image(x, q.tolist(), mask_pol), "quality": q, "reached": sol["reached"][0],
-                "bpp": sol["bpp"][0]}
-
-    # ---- rate control: the rate of many qualities without the per-quality tail (DESIGN section 9h)
-    _REM_RATE_REFUSAL = ("rate control on REM models: the rate at a quality q needs the checkpoint representation of q's "
-                         "check level (the REM refines (mu, sigma) per level), so neither one front end nor one layer pass "
-                         "gives the curve; call forward_single_quality(x, q, checkpoint_ref=...) per quality")
-
-    def _rate_loop(self, x, qualities, mask_pol) -> torch.Tensor:
-        """[len(qualities), 2, B] from one forward_single_quality per quality (models that are not _sweep_eligible)."""
-        if not len(qualities):
-            return torch.zeros((0, 2, x.shape[0]), dtype=torch.float64, device=x.device)
-        return torch.stack([self.forward_single_quality(x, q, mask_pol, training=False)["log2_likelihood_sum"] for q in qualities])
-
-    def _rate_result(self, ls: torch.Tensor, x) -> Dict[str, torch.Tensor]:
-        return {"log2_likelihood_sum": ls, "bpp": -ls.sum(1) / float(x.shape[2] * x.shape[3])}
+        return control.compress_to(self, x, target_bpp, q_tol, mask_pol, control.BPP, "bpp")
 
     def rate_curve(self, x, qualities, mask_pol=None):
         """The estimated rate of every image of ``x`` at every quality of the list (any order, repeats allowed, any count):
@@ -684,34 +453,7 @@ class VarianceMaskingPIC(CompressionModel):
         (:meth:`_sweep_eligible`) run the front end once per sub-batch and, per group of up to VAM_MAX_LAYER_LEVELS distinct
         qualities, one vam_variance_layers and one vam_gauss_layer_bits launch: no masks, no LRP stacks, no g_s.  The
         others loop over forward_single_quality; REM models are refused."""
-        qualities = [float(q) for q in qualities]
-        if isinstance(self, VarianceMaskingPICREM):
-            raise NotImplementedError(self._REM_RATE_REFUSAL)
-        mask_pol = self._mask_policy(mask_pol)
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        if not self._sweep_eligible():
-            with torch.no_grad():
-                return self._rate_result(self._rate_loop(x, qualities, mask_pol), x)
-        prs = [float(_mask_quality(mask_pol, q)) for q in qualities]
-        levels = sorted({p_ for p_ in prs if p_ != 0})
-        col = {p_: j for j, p_ in enumerate(levels)}
-        B, _, H, W = x.shape
-        out = torch.zeros((len(prs), 2, B), dtype=torch.float64, device=x.device)
-        idx = torch.tensor([col[p_] for p_ in prs if p_ != 0], dtype=torch.long, device=x.device)
-        rows = torch.tensor([k for k, p_ in enumerate(prs) if p_ != 0], dtype=torch.long, device=x.device)
-        with torch.no_grad():
-            for i0, i1, _ in sweep_groups(0, B, H, W):
-                xb = x[i0:i1].detach()
-                sw = self._sweep_plan(xb)
-                sw.front(xb, self.use_graph)
-                out[:, :, i0:i1] = sw.fp.log2sum                       # q == 0: the base-only sums (the sweep's zeros branch)
-                prog = [sw.rate(levels[l0:l0 + L.VAM_MAX_LAYER_LEVELS], self.use_graph)
-                        for l0 in range(0, len(levels), L.VAM_MAX_LAYER_LEVELS)]
-                if prog:
-                    out[rows, 0, i0:i1] += torch.cat(prog, 1).t()[idx]
-        return self._rate_result(out, x)
+        return control.rate_curve(self, x, qualities, mask_pol)
 
     def qualities_for_bpp(self, x, target_bpp, q_tol=1e-3, mask_pol=None):
         """The largest quality whose estimated rate fits a budget, per image: ``target_bpp`` a float, T floats or a [T, B]
@@ -721,79 +463,7 @@ class VarianceMaskingPIC(CompressionModel):
         Eligible models run the front end once per sub-batch and refine a bracket per (target, image) on grids of
         RATE_GRID points (:func:`rate_search`): a pass is vam_variance_layers + vam_gauss_layer_bits on the buffers the
         front end left in place and one host synchronisation.  The others bisect over forward_single_quality."""
-        if isinstance(self, VarianceMaskingPICREM):
-            raise NotImplementedError(self._REM_RATE_REFUSAL)
-        mask_pol = self._mask_policy(mask_pol)
-        if mask_pol != "point-based-std":
-            raise ValueError(f"qualities_for_bpp searches the point-based-std curve; the {mask_pol!r} curve has two values "
-                             "(q == 0 and q != 0): read them from rate_curve(x, [0, 10])")
-        if not q_tol > 0:
-            raise ValueError(f"q_tol must be > 0, got {q_tol}")
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        B, _, H, W = x.shape
-        tg = torch.as_tensor(target_bpp, dtype=torch.float64).cpu().numpy()
-        if tg.ndim == 0:
-            tg = tg.reshape(1)
-        if tg.ndim == 1:
-            tg = np.repeat(tg[:, None], B, axis=1)
-        if tg.ndim != 2 or tg.shape[1] != B:
-            raise ValueError(f"target_bpp: a float, T floats or a [T, {B}] tensor, got shape {tuple(tg.shape)}")
-        hw = float(H * W)
-        quality, bpp, reached = (np.zeros(tg.shape), np.zeros(tg.shape), np.zeros(tg.shape, dtype=bool))
-        with torch.no_grad():
-            if not self._sweep_eligible():
-                def curve(q, need):                        # one forward_single_quality per (image, quality) asked for
-                    out = np.zeros(q.shape)
-                    for b in range(B):
-                        qs = np.unique(q[:, b][need[:, b]])
-                        if qs.size:
-                            ls = self._rate_loop(x[b:b + 1], qs.tolist(), mask_pol)
-                            val = dict(zip(qs.tolist(), (-ls.sum(1)[:, 0] / hw).tolist()))
-                            out[:, b][need[:, b]] = [val[v] for v in q[:, b][need[:, b]].tolist()]
-                    return out
-                bpp0 = (-self._rate_loop(x, [0.0], mask_pol)[0].sum(0) / hw).cpu().numpy()
-                quality, bpp, reached = rate_search(curve, bpp0, tg, q_tol, n_grid=2)
-            else:
-                for i0, i1, _ in sweep_groups(0, B, H, W):
-                    xb = x[i0:i1].detach()
-                    sw = self._sweep_plan(xb)
-                    sw.front(xb, self.use_graph)
-                    base = sw.fp.log2sum.clone()                      # [2, b]: y (base slices) and z
-                    bpp0 = (-base.sum(0) / hw).cpu().numpy()
-                    curve = lambda q, need, sw=sw, base=base: sw.rate_points(q, need, base, self.use_graph) / -hw
-                    quality[:, i0:i1], bpp[:, i0:i1], reached[:, i0:i1] = rate_search(curve, bpp0, tg[:, i0:i1], q_tol)
-        return {"quality": torch.from_numpy(quality), "bpp": torch.from_numpy(bpp), "reached": torch.from_numpy(reached)}
-
-    # ---- coded-size control: the bytes of compress(x, q) without masks, tails or the coder (DESIGN section 9i)
-    _REM_SIZE_REFUSAL = ("coded-size control on REM models: the symbols and indexes at a quality q depend on the checkpoint "
-                         "representation of q's check level (the REM refines (mu, sigma) per level), so neither one front end "
-                         "nor one layer pass prices them; call compress(x, q, checkpoint_rep=...) per quality")
-
-    def _compress_size(self, xb, q, mask_pol):
-        """(bytes, table cost in bits) of the strings of the real ``compress(xb, q)`` for ONE image, the cost priced on the
-        host from that plan's own symbol and index buffers (models that are not _sweep_eligible)."""
-        from . import bitstream as bs
-        out = self.compress(xb, q, mask_pol)
-        nbytes = sum(len(s_) for part in out["strings"][0] for s_ in part) + sum(len(s_) for s_ in out["strings"][1])
-        plan = self._plan(xb, base_only=q <= 0, rem_idx=None, symbols=True)
-        tg, te = bs.Tables.of(self.gaussian_conditional), bs.Tables.of(self.entropy_bottleneck)
-        zs = plan.z_sym.buf.cpu().numpy()
-        bits = bs.price(plan.sym.buf.cpu().numpy(), plan.idx.buf.cpu().numpy(), tg).sum() + \
-            bs.price(zs, np.arange(self.N)[None, None, None, :], te).sum()
-        return nbytes, float(bits)
-
-    def _size_prepare(self, x, mask_pol, what):
-        if isinstance(self, VarianceMaskingPICREM):
-            raise NotImplementedError(self._REM_SIZE_REFUSAL)
-        mask_pol = self._mask_policy(mask_pol)
-        Ly._no_autograd(x)
-        L.require_gpu()
-        self._check_config()
-        if self.gaussian_conditional.scale_table.numel() == 0:
-            raise ValueError(f"empty scale table: call model.update() before {what}()")
-        return mask_pol
+        return control.solve(self, x, target_bpp, q_tol, mask_pol, control.BPP)
 
     def coded_size_curve(self, x, qualities, mask_pol=None):
         """The size of the strings of ``compress(x[b:b+1], q)`` — z, the base slices and, for q > 0, the progressive slices —
@@ -803,37 +473,7 @@ class VarianceMaskingPIC(CompressionModel):
         models (:meth:`_sweep_eligible`) run the front end once per sub-batch, price z and the base slices once, and per
         group of up to VAM_MAX_LAYER_LEVELS distinct qualities run one vam_variance_layers and one vam_coded_layer_bits
         launch.  The others loop over the real compress (bytes_lo == bytes_hi == the actual size); REM models are refused."""
-        qualities = [float(q) for q in qualities]
-        mask_pol = self._size_prepare(x, mask_pol, "coded_size_curve")
-        B, _, H, W = x.shape
-        lo, hi = np.zeros((len(qualities), B), dtype=np.int64), np.zeros((len(qualities), B), dtype=np.int64)
-        bits = np.zeros((len(qualities), B))
-        with torch.no_grad():
-            if not self._sweep_eligible():
-                for b in range(B):
-                    seen: Dict[float, tuple] = {}
-                    for k, q in enumerate(qualities):
-                        if q not in seen:
-                            seen[q] = self._compress_size(x[b:b + 1], q, mask_pol)
-                        lo[k, b] = hi[k, b] = seen[q][0]
-                        bits[k, b] = seen[q][1]
-            else:
-                prs = [float(_mask_quality(mask_pol, q)) for q in qualities]
-                levels = sorted({p_ for p_ in prs if p_ != 0})
-                col = {p_: j for j, p_ in enumerate(levels)}
-                G = L.VAM_MAX_LAYER_LEVELS
-                for i0, i1, _ in sweep_groups(0, B, H, W):
-                    xb = x[i0:i1].detach()
-                    sw = self._sweep_plan(xb)
-                    sw.front(xb, self.use_graph)
-                    sz = sw.size_front(self.use_graph)
-                    prog = [sw.size(levels[l0:l0 + G], self.use_graph) for l0 in range(0, len(levels), G)]
-                    base = sz.base_sizes()                                  # (lo, hi, bits), each [b]
-                    pl = sz.level_sizes(prog, [min(G, len(levels) - l0) for l0 in range(0, len(levels), G)])   # each [b, n_levels]
-                    for k, p_ in enumerate(prs):
-                        for dst, b0, pv in zip((lo, hi, bits), base, pl):
-                            dst[k, i0:i1] = b0 if p_ == 0 else b0 + pv[:, col[p_]]
-        return {"bytes_lo": torch.from_numpy(lo), "bytes_hi": torch.from_numpy(hi), "bits": torch.from_numpy(bits)}
+        return control.coded_size_curve(self, x, qualities, mask_pol)
 
     def qualities_for_bytes(self, x, target_bytes, q_tol=1e-3, mask_pol=None):
         """The largest quality whose coded size fits a byte budget, per image: ``target_bytes`` a number, T numbers or a
@@ -843,43 +483,7 @@ class VarianceMaskingPIC(CompressionModel):
         decrease in q);  q* = 0 with reached = False when even the base exceeds t.  :func:`rate_search` over bytes_hi:
         one front end per sub-batch; the first pass is the batched size tail, every later pass one
         vam_variance_layers_per_image and one vam_coded_layer_bits launch for the sub-batch and one synchronisation."""
-        mask_pol = self.mask_policy if mask_pol is None else mask_pol
-        if not isinstance(self, VarianceMaskingPICREM) and self._mask_policy(mask_pol) != "point-based-std":
-            raise ValueError(f"qualities_for_bytes searches the point-based-std curve; the {mask_pol!r} curve has two values "
-                             "(q == 0 and q != 0): read them from coded_size_curve(x, [0, 10])")
-        mask_pol = self._size_prepare(x, mask_pol, "qualities_for_bytes")
-        if not q_tol > 0:
-            raise ValueError(f"q_tol must be > 0, got {q_tol}")
-        B, _, H, W = x.shape
-        tg = torch.as_tensor(target_bytes, dtype=torch.float64).cpu().numpy()
-        if tg.ndim == 0:
-            tg = tg.reshape(1)
-        if tg.ndim == 1:
-            tg = np.repeat(tg[:, None], B, axis=1)
-        if tg.ndim != 2 or tg.shape[1] != B:
-            raise ValueError(f"target_bytes: a number, T numbers or a [T, {B}] tensor, got shape {tuple(tg.shape)}")
-        quality, size, reached = (np.zeros(tg.shape), np.zeros(tg.shape), np.zeros(tg.shape, dtype=bool))
-        with torch.no_grad():
-            if not self._sweep_eligible():
-                def curve(q, need):                        # one real compress per (image, quality) asked for
-                    out = np.zeros(q.shape)
-                    for b in range(B):
-                        qs = np.unique(q[:, b][need[:, b]])
-                        val = {v: self._compress_size(x[b:b + 1], v, mask_pol)[0] for v in qs.tolist()}
-                        out[:, b][need[:, b]] = [val[v] for v in q[:, b][need[:, b]].tolist()]
-                    return out
-                size0 = np.array([self._compress_size(x[b:b + 1], 0.0, mask_pol)[0] for b in range(B)], dtype=np.float64)
-                quality, size, reached = rate_search(curve, size0, tg, q_tol, n_grid=2)
-            else:
-                for i0, i1, _ in sweep_groups(0, B, H, W):
-                    xb = x[i0:i1].detach()
-                    sw = self._sweep_plan(xb)
-                    sw.front(xb, self.use_graph)
-                    sz = sw.size_front(self.use_graph)
-                    size0 = sz.base_sizes()[1].astype(np.float64)
-                    curve = lambda q, need, sw=sw: sw.size_points(q, need, self.use_graph)
-                    quality[:, i0:i1], size[:, i0:i1], reached[:, i0:i1] = rate_search(curve, size0, tg[:, i0:i1], q_tol)
-        return {"quality": torch.from_numpy(quality), "bytes": torch.from_numpy(size), "reached": torch.from_numpy(reached)}
+        return control.solve(self, x, target_bytes, q_tol, mask_pol, control.BYTES)
 
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),
@@ -992,7 +596,7 @@ class VarianceMaskingPIC(CompressionModel):
         if real_compress:
             from . import bitstream as bs
             if plan.idx is None:
-                raise ValueError("empty scale table: call model.update() before compress()")
+                raise ValueError(EMPTY_SCALE_TABLE.format("compress"))
             tg, te = bs.Tables.of(self.gaussian_conditional), bs.Tables.of(self.entropy_bottleneck)
             sym = plan.sym.buf.cpu().numpy()           # [B,h,w,C_lat] int32 (synchronises)
             idx = plan.idx.buf.cpu().numpy()
@@ -1229,6 +833,8 @@ def _mask_quality(mask_pol, q):
     """The quality the variance mask is computed at (channel_mask.py:152-153: two-levels is all ones unless pr == 0)."""
     return 10 if (mask_pol == "two-levels" and q != 0) else q
 
+
+EMPTY_SCALE_TABLE = "empty scale table: call model.update() before {}()"
 
 F16X2_REFUSAL = ("the fp16x2 arithmetic (VAMPIC_CONV=f16x2) is an evaluation-forward configuration: its results depend, in "
                  "the last bits, on the power-of-two scale of each launch (batch composition, plan structure), so the "
@@ -1768,91 +1374,6 @@ class _FsqPlan:
         return out
 
 
-def sweep_groups(n_levels: int, B: int, H: int, W: int) -> List[tuple]:
-    """How a rate sweep over ``n_levels`` qualities (q != 0) of B images of HxW runs: [(i0, i1, [(l0, l1), ...]), ...].
-    Images are split into sub-batches of at most one plan's worth (``_max_images_per_plan``), as forward_single_quality
-    splits them; the levels of a sub-batch of b images run in groups of at most min(VAM_MAX_MASK_LEVELS, nb // b) levels,
-    so that a group's level batch (levels * b images) fits one plan and its masks one vam_variance_mask_levels launch."""
-    nb = max(1, MAX_PLAN_PIXELS // (H * W))
-    out = []
-    for i0 in range(0, B, nb):
-        b = min(nb, B - i0)
-        g = max(1, min(L.VAM_MAX_MASK_LEVELS, nb // b))
-        out.append((i0, i0 + b, [(l0, min(l0 + g, n_levels)) for l0 in range(0, n_levels, g)]))
-    return out
-
-
-RATE_GRID = 32          # grid points of one refinement pass of qualities_for_bpp (= VAM_MAX_LAYER_LEVELS: one launch)
-
-
-def rate_search_passes(q_tol: float, n_grid: int = RATE_GRID) -> int:
-    """Passes after which a bracket that starts as [0, 10] and shrinks by ``n_grid`` per pass is no wider than q_tol."""
-    n, w = 0, 10.0
-    while w > q_tol:
-        w /= n_grid
-        n += 1
-    return n
-
-
-def rate_search_grid(lo, hi, n_grid: int = RATE_GRID):
-    """[..., n_grid] ascending points that split each bracket (lo, hi] evenly; the last one is hi itself."""
-    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
-    f = np.arange(1, n_grid + 1, dtype=np.float64) / n_grid
-    g = lo[..., None] + (hi - lo)[..., None] * f
-    g[..., -1] = hi
-    return g
-
-
-def rate_search_step(grid_q, grid_bpp, targets):
-    """One refinement of the bracket arithmetic of qualities_for_bpp, on host arrays: ``grid_q`` [..., G] ascending
-    qualities whose FIRST point is the bracket's lower end, ``grid_bpp`` [..., G] the (non-decreasing) rate there,
-    ``targets`` [...].  Returns (lo, bpp_lo, hi, bpp_hi, reached): lo = the largest grid point whose rate is within the
-    target (reached False, and lo = the first point, when not even that one is), hi = the grid point after lo (lo itself
-    when lo is the last one: the budget covers the whole grid)."""
-    q, r = np.asarray(grid_q, dtype=np.float64), np.asarray(grid_bpp, dtype=np.float64)
-    t = np.asarray(targets, dtype=np.float64)
-    ok = r <= t[..., None]
-    G = q.shape[-1]
-    # the LAST point within budget (a non-decreasing curve makes `ok` a prefix; taking the last keeps bpp(lo) <= t anyway)
-    last = G - 1 - np.argmax(ok[..., ::-1], axis=-1)
-    reached = ok.any(axis=-1)
-    i_lo = np.where(reached, last, 0)
-    i_hi = np.minimum(i_lo + 1, G - 1)
-    i_hi = np.where(reached, i_hi, 0)
-    take = lambda a, i: np.take_along_axis(a, i[..., None], axis=-1)[..., 0]
-    return take(q, i_lo), take(r, i_lo), take(q, i_hi), take(r, i_hi), reached
-
-
-def rate_search(curve, bpp0, targets, q_tol: float, n_grid: int = RATE_GRID):
-    """Successive refinement for qualities_for_bpp on host arrays, no model and no GPU of its own.  ``curve(q, need)``
-    returns the rate at the qualities q [T, B, n] (entries outside ``need`` [T, B, n] are not read), non-decreasing in q
-    per image; ``bpp0`` [B] the rate at q = 0; ``targets`` [T, B].  Pass 1 evaluates n_grid points of (0, 10]; later passes
-    the n_grid - 1 interior points of each (target, image)'s bracket (both ends are known), so the bracket shrinks by
-    n_grid per pass and rate_search_passes(q_tol, n_grid) passes end it.  Returns (quality, bpp, reached), each [T, B]."""
-    t = np.asarray(targets, dtype=np.float64)
-    T, B = t.shape
-    lo = np.zeros((T, B))
-    r_lo = np.broadcast_to(np.asarray(bpp0, dtype=np.float64), (T, B)).copy()
-    hi, r_hi = np.full((T, B), 10.0), np.full((T, B), np.inf)
-    reached = r_lo <= t
-    active = reached.copy()                                    # brackets still open
-    for p in range(rate_search_passes(q_tol, n_grid)):
-        if not active.any():
-            break
-        pts = rate_search_grid(lo, hi, n_grid)                 # [T, B, n]; from pass 2 on the last point (hi) is known
-        need = np.broadcast_to(active[..., None], pts.shape).copy()
-        if p > 0:
-            need[..., -1] = False
-        r = np.where(need, curve(pts, need), r_hi[..., None])
-        gq = np.concatenate([lo[..., None], pts], axis=-1)
-        gr = np.concatenate([r_lo[..., None], r], axis=-1)
-        n_lo, n_rlo, n_hi, n_rhi, _ = rate_search_step(gq, gr, t)
-        lo, r_lo = np.where(active, n_lo, lo), np.where(active, n_rlo, r_lo)
-        hi, r_hi = np.where(active, n_hi, hi), np.where(active, n_rhi, r_hi)
-        active &= hi > lo                                      # lo == hi: the budget covers q = 10
-    return np.where(reached, lo, 0.0), r_lo, reached
-
-
 class _RateTail:
     """The rate-only tail of a _SweepPlan's front end for ``n_levels`` sorted distinct qualities > 0: one
     vam_variance_layers launch on the progressive sigma gives every element the first level whose mask holds it, one
@@ -1930,8 +1451,7 @@ class _SizeTail:
         P.call(lambda: ops.coded_symbol_bits(fp.z_sym, None, None, 1, self.te, m.N, self.z_bits, self.z_cnt), "z prices (size)")
         P.call(lambda: ops.coded_layer_bits(fp.y.window(0, d), fp.mu_b, fp.std_b, None, 1, self.table, self.tg, self.C,
                                             self.b_bits, self.b_cnt), "base prices (size)")
-        self.tails: Dict[int, tuple] = {}                # n_levels -> (plan, acc)
-        self.prs: tuple = ()
+        self.tails: Dict[int, SimpleNamespace] = {}      # n_levels -> what make_tail returns
         self.tg = self.te = None
         self._base = None
 
@@ -1955,17 +1475,16 @@ class _SizeTail:
         self.runner.replay(("front",), self.front_plan.run, use_graph)
         self._base = None
 
-    def _tail(self, n_levels: int):
-        t = self.tails.get(n_levels)
-        if t is None:
-            assert 1 <= n_levels <= L.VAM_MAX_LAYER_LEVELS
-            acc = torch.zeros((2, self.B, self.ns, n_levels + 1), dtype=torch.float64, device=self.dev)
-            P = E.Plan(self.dev)
-            P.keep += [acc]
-            P.set_class("lrp_prog")
-            P.call(lambda: ops.memset_zero(acc))
-            P.call(lambda: self.launch(self.prs, acc), "layers + coded layer bits (size)")
-            t = self.tails[n_levels] = (P, acc)
+    def make_tail(self, n_levels: int) -> SimpleNamespace:
+        """The tail of ``n_levels`` sorted distinct qualities > 0, shaped like a _RateTail (``prs``, ``plan``, ``runner``: this
+        object's, one hipGraph per list); ``acc``: its bins [2, B, ns, n_levels + 1]."""
+        assert 1 <= n_levels <= L.VAM_MAX_LAYER_LEVELS
+        acc = torch.zeros((2, self.B, self.ns, n_levels + 1), dtype=torch.float64, device=self.dev)
+        t = SimpleNamespace(prs=(0.0,) * n_levels, plan=E.Plan(self.dev), runner=self.runner, acc=acc)
+        t.plan.keep += [acc]
+        t.plan.set_class("lrp_prog")
+        t.plan.call(lambda: ops.memset_zero(acc))
+        t.plan.call(lambda: self.launch(t.prs, acc), "layers + coded layer bits (size)")
         return t
 
     def launch(self, prs, acc: torch.Tensor, per_image: bool = False):
@@ -1978,14 +1497,6 @@ class _SizeTail:
             ops.variance_layers(pa["std"], prs, self.layer, n_slice=self.ns)                  # pic.py:621-622, all levels
         ops.coded_layer_bits(pa["y_top"], pa["mu"], pa["std"], self.layer, acc.shape[-1] - 1, self.table, self.tg, self.C,
                              acc[0], acc[1].view(torch.int64), y2=pa["y_sub"])
-
-    def levels(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
-        """A clone of the bins [2, B, ns, len(prs) + 1] of the sorted distinct qualities ``prs`` (> 0); one plan per list
-        length and one hipGraph per list, as the rate tails."""
-        P, acc = self._tail(len(prs))
-        self.prs = tuple(float(p_) for p_ in prs)
-        self.runner.replay(self.prs, P.run, use_graph)
-        return acc.clone()
 
     # ---- host arithmetic on the bins
     def base_sizes(self):
@@ -2013,7 +1524,7 @@ class _SizeTail:
 
     def level_sizes(self, accs: Sequence[torch.Tensor], ns_levels: Sequence[int]):
         """(bytes_lo, bytes_hi, bits), each [B, total levels]: the progressive strings of compress at every level of the
-        groups' bins (what :meth:`levels` returned).  One host synchronisation."""
+        groups' bins (what _SweepPlan.size returned).  One host synchronisation."""
         from . import bitstream as bs
         lo, hi, bits = [], [], []
         for acc, n in zip([a.cpu().numpy() for a in accs], ns_levels):
@@ -2135,22 +1646,26 @@ class _SweepPlan:
         with self.runner.on_stream():
             self.runner.replay(("base",), self.p_base.run, use_graph)
 
-    def tail(self, prs: Sequence[float], use_graph: bool) -> _SweepTail:
-        t = self.tails.get(len(prs))
+    def _tail(self, tails: dict, n: int, make, prs: Optional[Sequence[float]] = None, use_graph: bool = False):
+        """The tail of ``n`` levels kept in ``tails`` (``make(n)`` at first use); with ``prs`` set to those qualities and
+        replayed on the plan's stream: one plan per list length, one hipGraph per list."""
+        t = tails.get(n)
         if t is None:
-            t = self.tails[len(prs)] = _SweepTail(self.fp, len(prs))
-        t.prs = tuple(float(p_) for p_ in prs)
-        with self.runner.on_stream():
-            t.runner.replay(t.prs, t.plan.run, use_graph)
+            t = tails[n] = make(n)
+        if prs is not None:
+            t.prs = tuple(float(p_) for p_ in prs)
+            with self.runner.on_stream():
+                t.runner.replay(t.prs, t.plan.run, use_graph)
         return t
+
+    def tail(self, prs: Sequence[float], use_graph: bool) -> _SweepTail:
+        return self._tail(self.tails, len(prs), lambda n: _SweepTail(self.fp, n), prs, use_graph)
 
     def tail_per_image(self, Q_group: Sequence[Sequence[float]], use_graph: bool) -> _SweepTail:
         """:meth:`tail` with level g of image b at mask quality ``Q_group[g][b]``."""
         n = len(Q_group)
         assert all(len(row) == self.B for row in Q_group)
-        t = self.pi_tails.get(n)
-        if t is None:
-            t = self.pi_tails[n] = _SweepTail(self.fp, n, per_image=True)
+        t = self._tail(self.pi_tails, n, lambda n_: _SweepTail(self.fp, n_, per_image=True))
         sg = self.fp.sweep_parts["std"]
         table = ops.mask_table([[float(Q_group[g][b]) for g in range(n)] for b in range(self.B)], sg.H * sg.W, self.m.dim_chunk)
         with self.runner.on_stream():
@@ -2158,19 +1673,12 @@ class _SweepPlan:
             t.runner.replay(("per_image",), t.plan.run, use_graph)
         return t
 
-    def _rate_tail(self, n_levels: int) -> _RateTail:
-        t = self.rate_tails.get(n_levels)
-        if t is None:
-            t = self.rate_tails[n_levels] = _RateTail(self.fp, n_levels)
-        return t
+    def rate_tail(self, n_levels: int, prs: Optional[Sequence[float]] = None, use_graph: bool = False) -> _RateTail:
+        return self._tail(self.rate_tails, n_levels, lambda n: _RateTail(self.fp, n), prs, use_graph)
 
     def rate(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
-        """[B, len(prs)] float64: the progressive log2 sums at the sorted distinct qualities ``prs`` (> 0), one plan per
-        list length and one hipGraph per list, as the sweep's tails."""
-        t = self._rate_tail(len(prs))
-        t.prs = tuple(float(p_) for p_ in prs)
-        with self.runner.on_stream():
-            t.runner.replay(t.prs, t.plan.run, use_graph)
+        """[B, len(prs)] float64: the progressive log2 sums at the sorted distinct qualities ``prs`` (> 0)."""
+        t = self.rate_tail(len(prs), prs, use_graph)
         return t.level_sums(t.acc, len(prs))
 
     # ---- coded sizes (DESIGN section 9i)
@@ -2184,8 +1692,7 @@ class _SweepPlan:
 
     def size(self, prs: Sequence[float], use_graph: bool) -> torch.Tensor:
         """The bins [2, B, ns, len(prs) + 1] of the sorted distinct qualities ``prs`` (> 0) (after :meth:`size_front`)."""
-        with self.runner.on_stream():
-            return self.size_tail.levels(prs, use_graph)
+        return self._tail(self.size_tail.tails, len(prs), self.size_tail.make_tail, prs, use_graph).acc.clone()
 
     def size_eager(self, prs: Sequence[float]) -> np.ndarray:
         """Host bins [2, B, ns, len(prs) + 1] of a non-decreasing list that is asked for once (no graph); synchronises."""
@@ -2194,92 +1701,6 @@ class _SweepPlan:
         with self.runner.on_stream():
             st.launch([float(p_) for p_ in prs], acc)
         return acc.cpu().numpy()
-
-    def size_points(self, q, need, use_graph: bool):
-        """qualities_for_bytes' curve: bytes_hi of compress at the qualities q [T, B, n] (> 0) wanted by ``need``, as a host
-        array of q's shape; one host synchronisation.  When all images ask for the same points (the first pass) the batched
-        tail runs (and its graph); else every image has its own sorted distinct points and, VAM_MAX_LAYER_LEVELS at a
-        time, ONE vam_variance_layers_per_image and one vam_coded_layer_bits launch serve the whole sub-batch, eagerly (the
-        points of a pass are never asked for again)."""
-        T, B, _ = q.shape
-        G = L.VAM_MAX_LAYER_LEVELS
-        st = self.size_tail
-        pts, inv = [], []
-        for b in range(B):
-            u, iv = np.unique(q[:, b][need[:, b]], return_inverse=True)
-            pts.append(u)
-            inv.append(iv)
-        out = np.zeros(q.shape)
-        base_hi = st.base_sizes()[1]
-        most = max(u.size for u in pts)
-        if not most:
-            return out
-        if all(u.size == pts[0].size and np.array_equal(u, pts[0]) for u in pts):
-            chunks = [(l0, min(G, most - l0)) for l0 in range(0, most, G)]
-            accs = [self.size(pts[0][l0:l0 + n].tolist(), use_graph) for l0, n in chunks]
-            hi = st.level_sizes(accs, [n for _, n in chunks])[1]             # [B, n_points]
-            for b in range(B):
-                out[:, b][need[:, b]] = (base_hi[b] + hi[b])[inv[b]]
-            return out
-        from . import bitstream as bs
-        accs = []
-        with self.runner.on_stream():
-            for l0 in range(0, most, G):
-                acc = torch.zeros((2, B, st.ns, G + 1), dtype=torch.float64, device=st.dev)
-                # an image with no point left in this chunk gets the list [0]: no element in any layer, its row is not read
-                st.launch([u[l0:l0 + G].tolist() or [0.0] for u in pts], acc, per_image=True)
-                accs.append(acc)
-        host = [a.cpu().numpy() for a in accs]
-        for b in range(B):
-            vals = np.zeros(pts[b].size)
-            for c, l0 in enumerate(range(0, pts[b].size, G)):
-                n = min(G, pts[b].size - l0)
-                # a list of n < G levels leaves its no-layer elements in slot G: only the first n slots are read
-                S = st.stream_bits(host[c][:, b], n, st.c_out)            # [ns, n]
-                vals[l0:l0 + n] = bs.stream_bytes(S, st.n_y)[1].sum(0)
-            out[:, b][need[:, b]] = (base_hi[b] + vals)[inv[b]]
-        return out
-
-    def rate_points(self, q, need, base: torch.Tensor, use_graph: bool):
-        """qualities_for_bpp's curve: the total log2 sums (y + z) at the qualities q [T, B, n] (> 0) wanted by ``need``, as
-        a host array of q's shape; one host synchronisation.  Every image has its own points: when all images ask for the
-        same ones (the first pass) the batched tail runs, else the two kernels run per image (n_batch = 1 at the image's
-        offset) with the image's sorted distinct points, VAM_MAX_LAYER_LEVELS at a time, eagerly: the points of a pass are
-        never asked for again, so a graph of them would only be captured and dropped."""
-        T, B, _ = q.shape
-        G = L.VAM_MAX_LAYER_LEVELS
-        pts, inv = [], []
-        for b in range(B):
-            u, iv = np.unique(q[:, b][need[:, b]], return_inverse=True)
-            pts.append(u)
-            inv.append(iv)
-        out = np.zeros(q.shape)
-        tot = base.sum(0)                                                  # [B]
-        if all(u.size == pts[0].size and np.array_equal(u, pts[0]) for u in pts):
-            if not pts[0].size:
-                return out
-            sums = torch.cat([self.rate(pts[0][l0:l0 + G].tolist(), use_graph) for l0 in range(0, pts[0].size, G)], 1)
-            vals = (sums + tot[:, None]).cpu().numpy()                     # [B, n_points]
-            for b in range(B):
-                out[:, b][need[:, b]] = vals[b][inv[b]]
-            return out
-        jobs = [(b, l0, min(G, pts[b].size - l0)) for b in range(B) for l0 in range(0, pts[b].size, G)]
-        if not jobs:
-            return out
-        t = self._rate_tail(G)
-        acc = torch.zeros((2, len(jobs), G + 1), dtype=torch.float64, device=base.device)     # a row per launch; unused slots stay 0
-        with self.runner.on_stream():
-            for j, (b, l0, n) in enumerate(jobs):
-                t.launch(pts[b][l0:l0 + n].tolist(), acc[:, j], b)
-        # a launch of n < G levels leaves its no-layer count in slot n: it only reaches the levels >= n, which are not read
-        sums = t.level_sums(acc, G) + tot[[b for b, _, _ in jobs]][:, None]
-        host = sums.cpu().numpy()                                          # [jobs, G]
-        vals = [np.zeros(u.size) for u in pts]
-        for j, (b, l0, n) in enumerate(jobs):
-            vals[b][l0:l0 + n] = host[j, :n]
-        for b in range(B):
-            out[:, b][need[:, b]] = vals[b][inv[b]]
-        return out
 
     def close(self):
         self.fp.close()
@@ -2533,3 +1954,7 @@ def get_model(args, device):
     else:
         raise NotImplementedError
     return net.to(device)
+
+
+from . import control                                                                                   # noqa: E402
+from .control import RATE_GRID, rate_search, rate_search_grid, rate_search_passes, rate_search_step, sweep_groups   # noqa: E402,F401

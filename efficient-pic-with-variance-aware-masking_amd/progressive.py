@@ -232,24 +232,16 @@ def container_sizes(model, x, q_list: Sequence[float] = Q_LIST) -> List[dict]:
     for every group of streams.  One front end per sub-batch, one vam_variance_layers and one vam_coded_layer_bits
     launch; a layer's stream costs its elements' exact table prices plus the price of symbol 0 in table 0 for every other
     element.  The refusals are encode_batch's."""
-    from . import _lib as L
     from . import bitstream as bs
-    from .models import sweep_groups
+    from . import control
     _check_variant(model)
     _check_batched(model)
     qs = check_q_list(q_list)
     m = model
-    B, _, H, W = x.shape
     out: List[dict] = []
     with torch.no_grad():
-        L.require_gpu()
-        m._check_config()
-        if m.gaussian_conditional.scale_table.numel() == 0:
-            raise ValueError("empty scale table: call model.update() before container_sizes()")
-        for i0, i1, _ in sweep_groups(0, B, H, W):
-            xb = x[i0:i1].detach()
-            sw = m._sweep_plan(xb)
-            sw.front(xb, m.use_graph)
+        control._prepare(m, what="container_sizes", need_tables=True, policy=False)
+        for i0, i1, sw in control._fronts(m, x):
             st = sw.size_front(m.use_graph)
             acc = sw.size(qs, m.use_graph).cpu().numpy()
             st.base_sizes()
@@ -273,7 +265,7 @@ def solve_q_list_for_bytes(layer_hi, fixed_hi: float, target_bytes: Sequence[flo
     (the bracket shrinks by n_grid per pass, as rate_search's).  A target that does not even admit the empty layer (or lies
     below the base) is dropped, and so is every target after the mask is full (q = 10).  Returns (qualities, the targets
     kept, the upper size up to each level)."""
-    from .models import rate_search_grid, rate_search_passes, rate_search_step
+    from .control import rate_search_grid, rate_search_passes, rate_search_step
     qs, kept, sizes = [], [], []
     q_prev, used = 0.0, float(fixed_hi)
     for t in sorted(float(t_) for t_ in target_bytes):
@@ -309,19 +301,15 @@ def q_list_for_bytes(model, x, target_bytes: Sequence[float], q_tol: float = 1e-
     kept, one per level."""
     from . import _lib as L
     from . import bitstream as bs
+    from . import control
     if x.shape[0] != 1:
         raise ValueError(f"q_list_for_bytes resolves one image's list (the qualities differ between images), got a batch of {x.shape[0]}")
     _check_variant(model)
     _check_batched(model)
     m = model
     with torch.no_grad():
-        L.require_gpu()
-        m._check_config()
-        if m.gaussian_conditional.scale_table.numel() == 0:
-            raise ValueError("empty scale table: call model.update() before q_list_for_bytes()")
-        xb = x.detach()
-        sw = m._sweep_plan(xb)
-        sw.front(xb, m.use_graph)
+        control._prepare(m, what="q_list_for_bytes", need_tables=True, policy=False)
+        _, _, sw = next(control._fronts(m, x))                                    # one image: one sub-batch
         st = sw.size_front(m.use_graph)
         fixed_hi = float(st.base_sizes()[1][0])
 
@@ -379,6 +367,7 @@ def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
     from . import _lib as L
     from . import bitstream as bs
     from . import ops
+    from .models import EMPTY_SCALE_TABLE
     _check_variant(model)
     _check_batched(model)
     qs = check_q_list(q_list)
@@ -390,7 +379,7 @@ def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
         m._check_config()
         plan = m._plan(x, base_only=False, symbols=True)
         if plan.idx is None:
-            raise ValueError("empty scale table: call model.update() before encode_batch()")
+            raise ValueError(EMPTY_SCALE_TABLE.format("encode_batch"))
         plan.execute(x, 10.0, None, m.use_graph, False)
         layer = torch.empty((B, H // 16, W // 16, d), dtype=torch.uint8, device=x.device)
         ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)              # functions_encode.py:168-196's delta masks
@@ -438,10 +427,8 @@ class ProgressiveDecoder:
                                  f"{shape} / {q0} and {tuple(c['shape'])} / {list(c['q_list'])}; decode them separately")
         self.q_list = check_q_list(q0)
         self.m, self.containers, self.B = model, cs, len(cs)
-        from . import _lib as L
-        from .models import sweep_groups
-        L.require_gpu()
-        model._check_config()
+        from .control import _prepare, sweep_groups
+        _prepare(model, policy=False)
         hz, wz = int(shape[0]), int(shape[1])
         self.H, self.W = 64 * hz, 64 * wz
         if len(sweep_groups(1, self.B, self.H, self.W)) > 1:
@@ -478,7 +465,7 @@ class ProgressiveDecoder:
 
     def decode_levels(self, ks: Sequence[int]) -> List[dict]:
         """{"x_hat", "y_hat"} of the batch for every level of ``ks``, the levels > 0 through the batched tail."""
-        from .models import sweep_groups
+        from .control import sweep_groups
         ks = [int(k) for k in ks]
         if not ks or min(ks) < 0:
             raise ValueError(f"levels must be >= 0, got {ks}")

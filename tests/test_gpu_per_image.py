@@ -5,6 +5,7 @@ decompress_per_image / compress_to_bytes / rd_at_qualities against the single-im
 import argparse
 import copy
 import ctypes
+import sys
 
 import numpy as np
 import pytest
@@ -194,6 +195,23 @@ def test_compress_and_decompress_per_image():
     assert len(plan.runner.graphs) == 1
     with pytest.raises(ValueError, match="same shape"):
         net.decompress_per_image([items[0], dict(items[1], shape=(2, 2))])
+
+
+def test_bitstream_pair_sub_batches_by_the_plan_size(monkeypatch):
+    net = _net()
+    x = _x(3, 128, 128)
+    qs = [0, 2.5, 0.7]
+    with torch.no_grad():
+        items = net.compress_per_image(x, qs)
+        dec = net.decompress_per_image(items)["x_hat"]
+        monkeypatch.setattr(sys.modules["vampic.models"], "MAX_PLAN_PIXELS", 128 * 128)      # one image per plan
+        items1 = net.compress_per_image(x, qs)
+        dec1 = net.decompress_per_image(items1)["x_hat"]
+    assert any(k[0] == 1 and k[-1] == "per_image" for k in net._dec_plans)   # the patched run decoded the positives one by one
+    for a, b in zip(items, items1):
+        assert a["strings"] == b["strings"] and tuple(a["shape"]) == tuple(b["shape"]) and a["quality"] == b["quality"]
+    assert [it["quality"] for it in items1] == [0.0, 2.5, 0.7]
+    assert tuple(dec.shape) == tuple(x.shape) and torch.equal(dec, dec1)
 
 
 def _total(item):
