@@ -1,4 +1,4 @@
-"""Host-side drivers over the plans of ``models.py``: the quality sweep, rate control (9h), coded-size
+"""Host-side drivers over the plans of ``plans.py``: the quality sweep, rate control (9h), coded-size
 control (9i) and per-image qualities (9j).  The public methods of ``VarianceMaskingPIC`` delegate here (their docstrings
 are the contracts); a function validates, splits the batch into sub-batches of one plan's worth, replays the plans and
 does the host arithmetic.  ``models.MAX_PLAN_PIXELS`` is read through the module at call time, never bound by name."""
@@ -14,6 +14,7 @@ from . import _lib as L
 from . import layers as Ly
 from . import models as M
 from . import ops
+from .plans import _DecPlan
 
 _REM_RATE_REFUSAL = ("rate control on REM models: the rate at a quality q needs the checkpoint representation of q's "
                      "check level (the REM refines (mu, sigma) per level), so neither one front end nor one layer pass "
@@ -300,7 +301,7 @@ def decompress_per_image(model, items, mask_pol=None):
         def build(B=len(sub)):
             if ops.f16x2_mode():
                 raise NotImplementedError(M.F16X2_REFUSAL)
-            return M._DecPlan(model, B, hz, wz, False, None, dev, per_image=True)
+            return _DecPlan(model, B, hz, wz, False, None, dev, per_image=True)
         dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image"), build, model._weights_sig())
         x_hat[sub] = dp.decode(strings, _mask_qualities(mask_pol, [qs[b] for b in sub]), None)
     return {"x_hat": x_hat}

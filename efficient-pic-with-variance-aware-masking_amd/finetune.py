@@ -274,7 +274,7 @@ class ScalableRateDistortionLoss(nn.Module):
 
 def clip_grad_norm_(model, max_norm: float):
     """``torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)`` (training/step.py:98) — as ONE reduction when the
-    gradients of all parameters are views of the first-stage plan's flat buffer (models._FullTrainFn.backward hands them
+    gradients of all parameters are views of the first-stage plan's flat buffer (plans._FullTrainFn.backward hands them
     out that way; padding between tensors is zero), instead of a walk over 1065 tensors.  Anything else (a frozen
     subset, gradients from another source such as the aux loss, accumulated gradients) takes torch's own routine."""
     plans = [p for k, p in getattr(model, "_plans", {}).items() if k[0] == "full_train" and getattr(p, "handout", None) is not None]

@@ -1,7 +1,7 @@
 """Taped training pieces shared by every training plan: weight packs refreshed in place, taped conv stacks and
 their backward, the flat gradient buffer, and the taped synthesis transform of ``--training_type refine_gs`` (reference
 train.py:150-157,216-218 — everything frozen except ``g_s[1]``; loss = DistortionLoss, training/loss.py:126-187).  The
-REM fine-tune (models._FsqPlan with ``train=True``), refine_gs with or without ``--lrp`` (models._FsqPlan with
+REM fine-tune (plans._FsqPlan with ``train=True``), refine_gs with or without ``--lrp`` (plans._FsqPlan with
 ``train_gs``) and the first-stage plan (full_train.FullTrainPlan) all build on them.
 
 Forward: the same kernels as the eval lowering (engine.lower_g_s), but every tensor the backward needs is kept ("tape"):
