@@ -170,6 +170,8 @@ _SIGNATURES = {
     "vam_variance_mask_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vam_variance_masks_per_image": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_variance_mask_map": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_coded_layer_bits": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_int, C.c_void_p, C.c_int, C.POINTER(VamCoderTables), C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "vam_coded_symbol_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

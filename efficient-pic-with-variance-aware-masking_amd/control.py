@@ -1,5 +1,5 @@
 """Host-side drivers over the plans of ``plans.py``: the quality sweep, rate control (9h), coded-size
-control (9i) and per-image qualities (9j).  The public methods of ``VarianceMaskingPIC`` delegate here (their docstrings
+control (9i), per-image qualities (9j) and quality maps (9k).  The public methods of ``VarianceMaskingPIC`` delegate here (their docstrings
 are the contracts); a function validates, splits the batch into sub-batches of one plan's worth, replays the plans and
 does the host arithmetic.  ``models.MAX_PLAN_PIXELS`` is read through the module at call time, never bound by name."""
 from __future__ import annotations
@@ -584,3 +584,237 @@ BYTES = _Metric(
     lambda sw: (sw.size_front(sw.m.use_graph).base_sizes()[1].astype(np.float64), None), size_points,
     lambda model, xs, q, mask_pol: np.array([_compress_size(model, xs[b:b + 1], q, mask_pol)[0] for b in range(xs.shape[0])],
                                             dtype=np.float64))
+
+
+# ----------------------------------------------------------------------------- quality maps
+MAP_FLOOR_LEVELS = 8        # distinct values of a floor map per image (quality_map_for_bpp)
+MAP_GRID = 24               # grid points of one refinement pass: floor levels + grid points fit VAM_MAX_LAYER_LEVELS, one launch
+_REM_MAP_REFUSAL = ("quality maps on REM models: a REM and its checkpoint representation belong to ONE quality (the REM refines "
+                    "(mu, sigma) per check level), so the positions of one image cannot be at different qualities")
+_SHARE_MAP_REFUSAL = ("quality maps with {}: the bits of this configuration depend on how the launches are batched "
+                      "(VarianceMaskingPIC._batch_shareable), so a map cannot be stated as 'each position as at its own "
+                      "quality'; run the map in the default fp32 storage and bf16x3 arithmetic")
+
+
+def quality_map_levels(x_shape, qmap, mask_pol):
+    """Validate a quality map for images of ``x_shape`` [B, 3, H, W] and split it into the kernel's two inputs.  ``qmap``:
+    [B, H/16, W/16] (the latent grid), entries >= 0; ``two-levels`` maps every non-zero entry to 10 (_mask_quality).
+    Returns (levels, index): per image the sorted distinct mask qualities (float64 array, at most VAM_MAX_LAYER_LEVELS) and
+    the uint8 array [B, H/16, W/16] of each position's index in its image's list.  Pure host code."""
+    B, H, W = int(x_shape[0]), int(x_shape[2]), int(x_shape[3])
+    want = (B, H // 16, W // 16)
+    try:
+        qm = torch.as_tensor(qmap).detach().to("cpu", torch.float64).numpy()
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"quality map: expected a tensor of shape [B, H/16, W/16] = {list(want)} (the latent grid), got {type(qmap).__name__}") from e
+    if tuple(qm.shape) != want:
+        raise ValueError(f"quality map: expected shape [B, H/16, W/16] = {list(want)} (the latent grid of images {H}x{W}), "
+                         f"got {list(qm.shape)}")
+    if np.isnan(qm).any():
+        raise ValueError("quality map: qualities must be >= 0 (and not NaN), got NaN")
+    if (qm < 0).any():
+        raise ValueError(f"quality map: qualities must be >= 0 (and not NaN), got {float(qm.min())}")
+    if mask_pol == "two-levels":
+        qm = np.where(qm != 0, 10.0, 0.0)
+    levels, index = [], np.zeros(want, dtype=np.uint8)
+    for b in range(B):
+        u, inv = np.unique(qm[b], return_inverse=True)
+        if u.size > L.VAM_MAX_LAYER_LEVELS:
+            raise ValueError(f"quality map: image {b} holds {u.size} distinct qualities, the limit is {L.VAM_MAX_LAYER_LEVELS} "
+                             "(VAM_MAX_LAYER_LEVELS: the levels of one mask launch)")
+        levels.append(u.astype(np.float64))
+        index[b] = inv.reshape(want[1:]).astype(np.uint8)
+    return levels, index
+
+
+def _map_prepare(model, x, qmap, mask_pol, what, need_tables=False):
+    """What every quality-map driver does before GPU work: (mask policy, levels, index).  The map is validated first, then
+    the models that cannot run one are refused, then :func:`_prepare`."""
+    mask_pol = model._mask_policy(mask_pol)
+    M._check_input(x)
+    levels, index = quality_map_levels(x.shape, qmap, mask_pol)
+    _map_refuse(model)
+    _prepare(model, x, mask_pol, what, need_tables)
+    return mask_pol, levels, index
+
+
+def _map_refuse(model):
+    if isinstance(model, M.VarianceMaskingPICREM):
+        raise NotImplementedError(_REM_MAP_REFUSAL)
+    if getattr(model, "storage", "fp32") != "fp32":
+        raise NotImplementedError(_SHARE_MAP_REFUSAL.format(f"{model.storage} storage"))
+    if ops.f16x2_mode():
+        raise NotImplementedError(_SHARE_MAP_REFUSAL.format("VAMPIC_CONV=f16x2"))
+
+
+def forward_quality_map(model, x, qmap, mask_pol=None):
+    mask_pol, levels, index = _map_prepare(model, x, qmap, mask_pol, "forward_quality_map")
+    nb = M._max_images_per_plan(x)
+    outs = []
+    for i in range(0, x.shape[0], nb):
+        xb = x[i:i + nb].detach()
+        plan = model._plan(xb, base_only=False, quality_map=True)
+        outs.append(plan.execute_quality_map(xb, levels[i:i + nb], index[i:i + nb], model.use_graph, True))
+    return outs[0] if len(outs) == 1 else M._cat_outputs(outs)
+
+
+def compress_quality_map(model, x, qmap, mask_pol=None):
+    from . import bitstream as bs
+    mask_pol, levels, index = _map_prepare(model, x, qmap, mask_pol, "compress", need_tables=True)
+    tg, te = bs.Tables.of(model.gaussian_conditional), bs.Tables.of(model.entropy_bottleneck)
+    C, n_sl, nb = model.dim_chunk, model.ns1, M._max_images_per_plan(x)
+    y_jobs, z_jobs = [], []
+    with torch.no_grad():
+        for i in range(0, x.shape[0], nb):
+            xb = x[i:i + nb].detach().contiguous()
+            plan = model._plan(xb, base_only=False, symbols=True, quality_map=True)
+            plan.execute_quality_map(xb, levels[i:i + nb], index[i:i + nb], model.use_graph, False)
+            sym = plan.sym.buf.cpu().numpy()           # [b,h,w,C_lat] int32 (synchronises)
+            idx = plan.idx.buf.cpu().numpy()
+            zs = plan.z_sym.buf.cpu().numpy()
+            zi = np.broadcast_to(np.arange(model.N, dtype=np.int32)[:, None, None], (model.N,) + zs.shape[1:3])
+            for k in range(xb.shape[0]):                # stream order: [C, h, w] per image, as compress flattens
+                for s_ in range(n_sl):
+                    ch = slice(s_ * C, (s_ + 1) * C)
+                    y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
+                z_jobs.append((zs[k].transpose(2, 0, 1), zi))
+    ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+    shape = (x.shape[2] // 64, x.shape[3] // 64)
+    return [{"strings": [[[s_] for s_ in ys[b * n_sl:(b + 1) * n_sl]], [zstr[b]]], "shape": shape,
+             "quality_map": {"levels": [float(q) for q in levels[b]], "index": index[b].copy()},
+             "side_bytes": 8 * len(levels[b]) + index[b].size} for b in range(x.shape[0])]
+
+
+def _item_map(item, b: int, h: int, w: int):
+    """(levels, index) of one item of compress_quality_map, checked against the latent grid [h, w]."""
+    try:
+        qm = item["quality_map"]
+        lv = np.asarray(qm["levels"], dtype=np.float64).reshape(-1)
+        ix = np.asarray(qm["index"])
+    except (KeyError, TypeError) as e:
+        raise ValueError(f"decompress_quality_map: item {b} has no quality_map {{'levels', 'index'}}") from e
+    if not 1 <= lv.size <= L.VAM_MAX_LAYER_LEVELS or not (lv >= 0).all() or (np.diff(lv) < 0).any():
+        raise ValueError(f"decompress_quality_map: item {b}: levels are 1..{L.VAM_MAX_LAYER_LEVELS} non-decreasing qualities >= 0")
+    if ix.dtype != np.uint8 or tuple(ix.shape) != (h, w):
+        raise ValueError(f"decompress_quality_map: item {b}: index is a uint8 array of shape [{h}, {w}] (the latent grid), "
+                         f"got {ix.dtype} {list(ix.shape)}")
+    if int(ix.max()) >= lv.size:
+        raise ValueError(f"decompress_quality_map: item {b}: index {int(ix.max())} names no level of a list of {lv.size}")
+    return lv, ix
+
+
+def decompress_quality_map(model, items, mask_pol=None):
+    items = list(items)
+    if not items:
+        raise ValueError("decompress_quality_map: no items")
+    shape = tuple(int(v) for v in items[0]["shape"])
+    if any(tuple(int(v) for v in it["shape"]) != shape for it in items):
+        raise ValueError("decompress_quality_map: all items must have the same shape; decode other shapes in a call of their own")
+    hz, wz = shape
+    maps = [_item_map(it, b, 4 * hz, 4 * wz) for b, it in enumerate(items)]
+    _map_refuse(model)
+    _prepare(model, None, mask_pol)
+    dev = model.entropy_bottleneck.quantiles.device
+    n_sl = model.ns1
+    for b, it in enumerate(items):
+        if len(it["strings"][0]) < n_sl or len(it["strings"][1]) != 1:
+            raise ValueError(f"decompress_quality_map: item {b}: expected {n_sl} slice streams and one z stream of one image")
+    x_hat = torch.empty((len(items), 3, hz * 64, wz * 64), dtype=torch.float32, device=dev)
+    nb = max(1, M.MAX_PLAN_PIXELS // (hz * wz * 64 * 64))
+    for i in range(0, len(items), nb):
+        sub = list(range(i, min(i + nb, len(items))))
+        strings = [[[items[b]["strings"][0][s_][0] for b in sub] for s_ in range(n_sl)], [items[b]["strings"][1][0] for b in sub]]
+
+        def build(B=len(sub)):
+            if ops.f16x2_mode():
+                raise NotImplementedError(M.F16X2_REFUSAL)
+            return _DecPlan(model, B, hz, wz, False, None, dev, quality_map=True)
+        dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "quality_map"), build, model._weights_sig())
+        x_hat[sub] = dp.decode(strings, None, None, quality_map=([maps[b][0] for b in sub], np.stack([maps[b][1] for b in sub])))
+    return {"x_hat": x_hat}
+
+
+def _map_pixel_values(sw, levels):
+    """[b, h * w, n] float64 on the device, on the front end that has just run: the progressive log2 sum of every latent
+    pixel at every level of its image's sorted list (n = the longest list; columns beyond an image's list are not
+    meaningful).  One vam_variance_layers_per_image and one vam_gauss_layer_bits (pix_per_item = 1) launch."""
+    t = sw.rate_tail(L.VAM_MAX_LAYER_LEVELS)
+    with sw.runner.on_stream():
+        return t.map_values(t.map_bins([[float(q) for q in row] for row in levels]))
+
+
+def quality_map_rate(model, x, qmap, mask_pol=None):
+    mask_pol, levels, index = _map_prepare(model, x, qmap, mask_pol, "quality_map_rate")
+    with torch.no_grad():
+        if not model.all_scalable:
+            return _rate_result(model.forward_quality_map(x, qmap, mask_pol)["log2_likelihood_sum"], x)
+        out = torch.zeros((2, x.shape[0]), dtype=torch.float64, device=x.device)
+        for i0, i1, sw in _fronts(model, x):
+            V = _map_pixel_values(sw, levels[i0:i1])                                     # [b, hw, n]
+            k = torch.from_numpy(index[i0:i1].reshape(i1 - i0, -1).astype(np.int64)).to(x.device)
+            out[:, i0:i1] = sw.fp.log2sum
+            out[0, i0:i1] += V.gather(2, k.unsqueeze(-1))[..., 0].sum(1)
+    return _rate_result(out, x)
+
+
+def _floor_points(sw, base, levels, index, pts):
+    """The bpp of the maps max(floor, q) for the points q = ``pts[b]`` (a sorted distinct array per image, any length) of the
+    floor map (``levels``, ``index`` of :func:`quality_map_levels`), on the front end that has just run: a list of arrays.
+    MAP_GRID points at a time: image b's list is floor levels | points, at most VAM_MAX_LAYER_LEVELS, so a chunk is one
+    vam_variance_layers_per_image and one vam_gauss_layer_bits launch for the sub-batch; one host synchronisation."""
+    B, dev = len(levels), base.device
+    tot = base.sum(0)                                                            # [B]
+    fidx = torch.from_numpy(index.reshape(B, -1).astype(np.int64)).to(dev)       # [B, hw]
+    parts = []
+    with torch.no_grad():
+        for l0 in range(0, max(u.size for u in pts), MAP_GRID):
+            chunk = [u[l0:l0 + MAP_GRID] for u in pts]
+            lists = [np.union1d(lv, c) for lv, c in zip(levels, chunk)]          # sorted distinct
+            V = _map_pixel_values(sw, lists)                                     # [B, hw, n]
+            G = max(c.size for c in chunk)
+            # where the floor's levels and the points sit in each image's list; an image with fewer points repeats its first level
+            f_at = [np.searchsorted(ls, lv) for ls, lv in zip(lists, levels)]
+            p_at = np.zeros((B, G), dtype=np.int64)
+            for b, (ls, c) in enumerate(zip(lists, chunk)):
+                p_at[b, :c.size] = np.searchsorted(ls, c)
+            fk = torch.stack([torch.from_numpy(f_at[b].astype(np.int64)).to(dev)[fidx[b]] for b in range(B)])   # [B, hw]
+            K = torch.maximum(fk.unsqueeze(1), torch.from_numpy(p_at).to(dev).unsqueeze(2))                      # [B, G, hw]
+            parts.append(V.transpose(1, 2).gather(1, K).sum(2) + tot[:, None])   # max(floor, q) is a level of the list: the larger index
+    host = torch.cat(parts, 1).cpu().numpy() / -float(sw.H * sw.W)
+    return [host[b, :u.size] for b, u in enumerate(pts)]
+
+
+def quality_map_for_bpp(model, x, floor_map, target_bpp, q_tol=1e-3, mask_pol=None):
+    what = "quality_map_for_bpp"
+    mask_pol = model._mask_policy(mask_pol)
+    M._check_input(x)
+    levels, index = quality_map_levels(x.shape, floor_map, mask_pol)
+    many = [(b, lv.size) for b, lv in enumerate(levels) if lv.size > MAP_FLOOR_LEVELS]
+    if many:
+        raise ValueError(f"{what}: the floor map of image {many[0][0]} holds {many[0][1]} distinct qualities, the limit is "
+                         f"{MAP_FLOOR_LEVELS} (they share one launch's {L.VAM_MAX_LAYER_LEVELS} levels with {MAP_GRID} grid points)")
+    if mask_pol != "point-based-std":
+        raise ValueError(f"{what} searches the point-based-std curve; the {mask_pol!r} curve has two values "
+                         "(q == 0 and q != 0): read them from quality_map_rate")
+    if not q_tol > 0:
+        raise ValueError(f"q_tol must be > 0, got {q_tol}")
+    _map_refuse(model)
+    if not model.all_scalable:
+        raise NotImplementedError(f"{what} on all_scalable=False: the progressive (mu, sigma) chain reads the decoded slices, so "
+                                  "the rate of a map needs a whole forward; search over forward_quality_map yourself")
+    _prepare(model, x, mask_pol, what)
+    B = x.shape[0]
+    tg = _targets(target_bpp, B, "target_bpp", "float")
+    quality, value, reached = (np.zeros(tg.shape), np.zeros(tg.shape), np.zeros(tg.shape, dtype=bool))
+    with torch.no_grad():
+        for i0, i1, sw in _fronts(model, x):
+            base = sw.fp.log2sum.clone()
+            lv, ix = levels[i0:i1], index[i0:i1]
+            own = lambda pts, sw=sw, base=base, lv=lv, ix=ix: _floor_points(sw, base, lv, ix, pts)
+            same = lambda points, own=own, n=i1 - i0: own([points] * n)
+            curve = lambda q, need, same=same, own=own: _points(q, need, same, own)
+            bpp0 = np.array([v[0] for v in own([np.zeros(1)] * (i1 - i0))])
+            quality[:, i0:i1], value[:, i0:i1], reached[:, i0:i1] = rate_search(curve, bpp0, tg[:, i0:i1], q_tol, n_grid=MAP_GRID)
+    floor = np.stack([lv[ix_.astype(np.int64)] for lv, ix_ in zip(levels, index)])          # [B, h, w]
+    return {"quality": torch.from_numpy(quality), "bpp": torch.from_numpy(value), "reached": torch.from_numpy(reached),
+            "quality_map": torch.from_numpy(np.maximum(floor[None], quality[:, :, None, None]))}

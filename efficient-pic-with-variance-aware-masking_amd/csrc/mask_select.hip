@@ -218,7 +218,18 @@ struct MaskImageMaskArgs : MaskImageArgs {
   int max_levels;
 };
 
-// the per-level fields of the three argument kinds of variance_mask_levels_kernel
+// vam_variance_mask_map: MaskImageArgs' table and thresholds (LAYERS = true: they stay in LDS), and in place of the layer
+// ids ONE float mask in which pixel p of image b takes level level_map[b * map_batch_stride + p] of that image's list
+// (mask_* then describe the float mask, as in MaskArgs; layer stays NULL)
+struct MaskMapArgs : MaskImageArgs {
+  float* mask;
+  const uint8_t* level_map;
+  long map_batch_stride;
+};
+template <class Args> struct lv_is_map { static constexpr bool value = false; };
+template <> struct lv_is_map<MaskMapArgs> { static constexpr bool value = true; };
+
+// the per-level fields of the argument kinds of variance_mask_levels_kernel
 __device__ __forceinline__ int lv_count(const MaskLevelsArgs& a, int) { return a.n_levels; }
 __device__ __forceinline__ int lv_any_select(const MaskLevelsArgs& a, int) { return a.any_select; }
 __device__ __forceinline__ int lv_mode(const MaskLevelsArgs& a, int, int lv) { return a.mode[lv]; }
@@ -252,6 +263,7 @@ __device__ __forceinline__ long lv_stride(const MaskImageMaskArgs& a) { return a
 // Args: MaskLevelsArgs (one quality list in the kernel arguments) or MaskImageArgs (vam_variance_layers_per_image: image
 // b's record of a device table) or MaskImageMaskArgs (vam_variance_masks_per_image: that record, float masks per level);
 // the per-level fields are read through the lv_* accessors above, so the first kind compiles to the accesses it always made.
+// MaskMapArgs (vam_variance_mask_map, LAYERS = true) replaces the last pass: one float mask, each pixel at its own level.
 template <int MAXV, bool LAYERS, class Args = MaskLevelsArgs>
 __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const Args a) {
   __shared__ unsigned hist[256];
@@ -411,8 +423,43 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const Args a
   }
   if (!LAYERS) return;
 
-  // ---- layer assignment: layer <= k  <=>  mask_k == 1 (the masks of a non-decreasing quality list are nested)
   __syncthreads();
+  if constexpr (lv_is_map<Args>::value) {
+    // ---- quality map: pixel p keeps x >= the threshold of ITS level (all one / all zero for the levels without one;
+    // zero for a map entry beyond the image's list)
+    __shared__ int sh_md[VAM_MAX_LAYER_LEVELS];
+    const int n_lv = lv_count(a, b);
+    if (tid < VAM_MAX_LAYER_LEVELS) sh_md[tid] = tid < n_lv ? lv_mode(a, b, tid) : 1;
+    __syncthreads();
+    float* const mdst = a.mask + b * a.mask_batch_stride + j * a.mask_slice_stride;
+    const uint8_t* const lmap = a.level_map + b * a.map_batch_stride;
+    auto put = [&](int i, float4 v) {
+      const int p = i / a.C4;
+      const int lv = (int)lmap[p];
+      const int md = lv < VAM_MAX_LAYER_LEVELS ? sh_md[lv] : 1;
+      float4 o;
+      if (md != 0) {
+        const float c = md == 2 ? 1.f : 0.f;
+        o = make_float4(c, c, c, c);
+      } else {
+        const float thr = sh_thr[lv];
+        o = make_float4(v.x >= thr ? 1.f : 0.f, v.y >= thr ? 1.f : 0.f, v.z >= thr ? 1.f : 0.f, v.w >= thr ? 1.f : 0.f);
+      }
+      *reinterpret_cast<float4*>(mdst + (long)p * a.ld_mask + (i - p * a.C4) * 4) = o;
+    };
+    if (MAXV > 0) {
+#pragma unroll
+      for (int r = 0; r < MAXV; ++r) {
+        int i = tid + r * 1024;
+        if (i < nvec) put(i, reg[r]);
+      }
+    } else {
+      for (int i = tid; i < nvec; i += 1024) put(i, *reinterpret_cast<const float4*>(vec_ptr(i)));
+    }
+    return;
+  }
+
+  // ---- layer assignment: layer <= k  <=>  mask_k == 1 (the masks of a non-decreasing quality list are nested)
   uint8_t* const ldst = a.layer + b * a.mask_batch_stride + j * a.mask_slice_stride;
   auto layer_of = [&](float x) -> unsigned {
     for (int lv = 0; lv < lv_count(a, b); ++lv) {
@@ -683,4 +730,35 @@ extern "C" int vam_variance_masks_per_image(const float* sigma, int ld, long bat
   else
     hipLaunchKernelGGL((variance_mask_levels_kernel<0, false, MaskImageMaskArgs>), dim3(segs), dim3(1024), 0, s, a);
   return check_launch("variance_masks_per_image_kernel");
+}
+
+extern "C" int vam_variance_mask_map(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice,
+                                     int n_pix, int C, const vam_layer_params* table_dev, const uint8_t* level_map,
+                                     long map_batch_stride, float* mask_out, int ld_mask, long mask_batch_stride,
+                                     long mask_slice_stride, float* thr_out, void* stream) {
+  VAM_REQUIRE(sigma && table_dev && level_map && mask_out && n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "vam_variance_mask_map: bad arguments");
+  VAM_REQUIRE(C % 4 == 0 && ld % 4 == 0 && ld_mask % 4 == 0 && batch_stride % 4 == 0 && slice_stride % 4 == 0 && mask_batch_stride % 4 == 0 && mask_slice_stride % 4 == 0, "vam_variance_mask_map: C and strides must be multiples of 4");
+  VAM_REQUIRE((((uintptr_t)sigma) & 15) == 0 && (((uintptr_t)mask_out) & 15) == 0 && (((uintptr_t)table_dev) & 3) == 0,
+              "vam_variance_mask_map: 16-byte alignment (table: 4-byte)");
+  VAM_REQUIRE(ld >= C && ld_mask >= C, "vam_variance_mask_map: pixel stride < C");
+  VAM_REQUIRE(map_batch_stride >= n_pix, "vam_variance_mask_map: map_batch_stride %ld < n_pix %d", map_batch_stride, n_pix);
+  const long n = (long)n_pix * C;
+  VAM_REQUIRE(n <= 16000000L, "vam_variance_mask: segment of %ld elements exceeds torch.quantile's 16M limit", n);
+  MaskMapArgs a;
+  a.sigma = sigma; a.thr = thr_out; a.layer = nullptr; a.table = table_dev;
+  a.batch_stride = batch_stride; a.slice_stride = slice_stride;
+  a.mask_batch_stride = mask_batch_stride; a.mask_slice_stride = mask_slice_stride;
+  a.ld = ld; a.ld_mask = ld_mask; a.n_slice = n_slice; a.n_pix = n_pix; a.C4 = C / 4;
+  a.mask = mask_out; a.level_map = level_map; a.map_batch_stride = map_batch_stride;
+  const int segs = n_batch * n_slice;
+  const int nvec = n_pix * (C / 4);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(VAM_FAM_MASK, s, 0, 8.0 * (double)n * segs);
+  if (nvec <= 4 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<4, true, MaskMapArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else if (nvec <= 16 * 1024)
+    hipLaunchKernelGGL((variance_mask_levels_kernel<16, true, MaskMapArgs>), dim3(segs), dim3(1024), 0, s, a);
+  else
+    hipLaunchKernelGGL((variance_mask_levels_kernel<0, true, MaskMapArgs>), dim3(segs), dim3(1024), 0, s, a);
+  return check_launch("variance_mask_map_kernel");
 }

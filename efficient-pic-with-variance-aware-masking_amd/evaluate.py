@@ -163,6 +163,67 @@ def rd_at_qualities(model, x: torch.Tensor, Q):
     return -vals[0] / hw, -10.0 * torch.log10(vals[1] / (x[0].numel()))
 
 
+# ----------------------------------------------------------------------------- quality maps
+def latent_quality_map(pixel_map) -> torch.Tensor:
+    """A quality map on the latent grid from one on the pixels: [B, H, W] or [B, 1, H, W] -> float64 [B, H/16, W/16], the
+    MAXIMUM over each 16 x 16 block, so a block that touches a region gets the region's quality."""
+    pm = torch.as_tensor(pixel_map).detach().to("cpu", torch.float64)
+    if pm.dim() == 4 and pm.shape[1] == 1:
+        pm = pm[:, 0]
+    if pm.dim() != 3 or pm.shape[1] % 16 or pm.shape[2] % 16:
+        raise ValueError(f"pixel map: [B, H, W] or [B, 1, H, W] with H, W multiples of 16, got shape {list(pm.shape)}")
+    B, H, W = pm.shape
+    return pm.reshape(B, H // 16, 16, W // 16, 16).amax(dim=(2, 4))
+
+
+def quality_map_from_boxes(B: int, H: int, W: int, background: float, boxes) -> torch.Tensor:
+    """The latent quality map [B, H/16, W/16] of images H x W at quality ``background`` with pixel boxes
+    ``(b, y0, x0, y1, x1, q)`` (rows y0..y1-1, columns x0..x1-1 of image b at quality q; later boxes win where boxes
+    overlap).  The pixel map goes through :func:`latent_quality_map`."""
+    pm = torch.full((B, H, W), float(background), dtype=torch.float64)
+    for b, y0, x0, y1, x1, q in boxes:
+        if not (0 <= b < B and 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W):
+            raise ValueError(f"box {(b, y0, x0, y1, x1, q)} lies outside {B} images of {H}x{W}")
+        pm[b, y0:y1, x0:x1] = float(q)
+    return latent_quality_map(pm)
+
+
+def rd_quality_map(model, x: torch.Tensor, qmap, region=None):
+    """Rate and distortion of ``forward_quality_map(x, qmap)`` per image: {"bpp", "psnr"} float64 [B] host tensors
+    (:func:`estimated_bpp` and :func:`compute_psnr` applied to each image on its own) and, with a boolean pixel ``region``
+    [B, H, W] or [B, 1, H, W], {"psnr_in", "psnr_out"}: compute_psnr's definition on the pixels inside and outside the region
+    (NaN for an image whose set is empty)."""
+    dev = next(model.parameters()).device
+    x = x.to(dev).contiguous()
+    B, _, H, W = x.shape
+    with torch.no_grad():
+        out = model.forward_quality_map(x, qmap)
+        x_hat = out["x_hat"].contiguous()
+        sets = [None]
+        if region is not None:
+            r = torch.as_tensor(region).to(dev)
+            r = (r[:, 0] if r.dim() == 4 else r).bool()
+            if tuple(r.shape) != (B, H, W):
+                raise ValueError(f"region: a boolean [B, H, W] or [B, 1, H, W] for images {[B, H, W]}, got {list(r.shape)}")
+            sets += [r, ~r]
+        sq = torch.zeros((len(sets), B), dtype=torch.float64, device=dev)
+        n = torch.full((len(sets), B), float(x[0].numel()), dtype=torch.float64, device=dev)
+        for k, r in enumerate(sets):
+            if r is None:
+                ops.sqdiff_sum_levels(x, x_hat, sq[k:k + 1])
+            else:                                      # outside the set both tensors are 0: only its pixels are summed
+                m = r.unsqueeze(1).to(x.dtype)
+                ops.sqdiff_sum_levels((x * m).contiguous(), (x_hat * m).contiguous(), sq[k:k + 1])
+                n[k] = 3.0 * r.flatten(1).sum(1).double()
+        vals = torch.cat([out["log2_likelihood_sum"].sum(0, keepdim=True), sq, n]).cpu()
+    ns = len(sets)
+    psnr = -10.0 * torch.log10(vals[1:1 + ns] / vals[1 + ns:])
+    res = {"bpp": -vals[0] / (H * W), "psnr": psnr[0]}
+    if region is not None:
+        res.update({"psnr_in": psnr[1], "psnr_out": psnr[2]})
+    return res
+
+
 def rd_at_rates(model, x: torch.Tensor, target_bpps):
     """Rate and distortion at target rates: the qualities are resolved once for the batch (VarianceMaskingPIC.
     qualities_for_bpp: per image the largest quality whose estimated rate fits each target), then every image is

@@ -296,11 +296,12 @@ class VarianceMaskingPIC(CompressionModel):
 
     def _plan(self, x, base_only: bool, rem_idx: Optional[int] = None, symbols: bool = False,
               train: bool = False, own_ck: bool = False, train_gs: bool = False, train_lrp: bool = False,
-              per_image: bool = False) -> "_FsqPlan":
+              per_image: bool = False, quality_map: bool = False) -> "_FsqPlan":
         B, H, W = _check_input(x)
         key = (B, H, W, base_only, rem_idx, str(x.device)) + ((True,) if symbols else ()) + (("train",) if train else ()) + \
             (("own_ck",) if own_ck else ()) + (("train_gs",) if train_gs else ()) + (("train_lrp",) if train_lrp else ()) + \
-            (("bf16",) if getattr(self, "storage", "fp32") == "bf16" else ()) + (("per_image",) if per_image else ())
+            (("bf16",) if getattr(self, "storage", "fp32") == "bf16" else ()) + (("per_image",) if per_image else ()) + \
+            (("quality_map",) if quality_map else ())
         if getattr(self, "storage", "fp32") == "bf16" and (train or symbols):
             raise NotImplementedError("bf16 storage is an inference configuration (forward_single_quality): training and "
                                       "the bitstream path run in fp32")
@@ -310,7 +311,8 @@ class VarianceMaskingPIC(CompressionModel):
         trained = ([self._decoder_in_use(base_only)] if train_gs else []) + ([self.lrp_transforms_prog] if train_lrp else [])
         return self._cached_plan(self._plans, key,
                                  lambda: _FsqPlan(self, B, H, W, base_only, rem_idx, x.device, symbols=symbols, train=train,
-                                                  own_ck=own_ck, train_gs=train_gs, train_lrp=train_lrp, per_image=per_image),
+                                                  own_ck=own_ck, train_gs=train_gs, train_lrp=train_lrp, per_image=per_image,
+                                                  quality_map=quality_map),
                                  self._weights_sig(trained), None if train else rem_idx)
 
     def _decoder_in_use(self, base_only: bool):
@@ -376,7 +378,7 @@ class VarianceMaskingPIC(CompressionModel):
             out["x_hat"] = _FsqTrainFn.apply(plan, out["x_hat"], self.use_graph, *plan.train_params)
         return out
 
-    # ---- sweep, per-image qualities, rate and coded-size control (DESIGN sections 9f, 9h-9j): the drivers are control.py's
+    # ---- sweep, per-image qualities, rate and coded-size control, quality maps (DESIGN sections 9f, 9h-9k): the drivers are control.py's
     def _batch_shareable(self) -> bool:
         """Can images at different qualities share one plan?  REM models (a per-quality REM and checkpoint), bf16 storage
         and VAMPIC_CONV=f16x2 (their bits depend on how the launches are batched) loop over single images instead."""
@@ -482,6 +484,54 @@ class VarianceMaskingPIC(CompressionModel):
         one front end per sub-batch; the first pass is the batched size tail, every later pass one
         vam_variance_layers_per_image and one vam_coded_layer_bits launch for the sub-batch and one synchronisation."""
         return control.solve(self, x, target_bytes, q_tol, mask_pol, control.BYTES)
+
+    # ---- quality maps: region-of-interest coding (DESIGN section 9k)
+    def forward_quality_map(self, x, qmap, mask_pol=None):
+        """``forward_single_quality(..., training=False)``'s dict for a quality that varies INSIDE the images: ``qmap``
+        [B, H/16, W/16] (the latent grid; :func:`evaluate.latent_quality_map` makes one from a pixel map), entries >= 0, at
+        most VAM_MAX_LAYER_LEVELS distinct values per image.  For every slice j, latent position p and channel c the mask is
+        the one ``forward_single_quality(x[b:b+1], qmap[b, p])`` computes there, bit for bit; with all_scalable so are
+        ``likelihoods["y"]``, ``mu`` and ``std`` (they do not depend on the other positions' qualities), while ``y_hat`` and
+        ``x_hat`` mix the positions through the LRP stacks and g_s.  A 0 masks that position out of the progressive half; it
+        does NOT select the base plan, even for a map that is 0 everywhere: g_s[1] still reconstructs.  ``two-levels`` maps
+        every non-zero entry to 10.  One plan run per sub-batch of one plan's worth; table and map are graph inputs, so a
+        plan keeps ONE hipGraph whatever the maps.  Refused (NotImplementedError): REM models (a REM and its checkpoint
+        belong to one quality), bf16 storage and VAMPIC_CONV=f16x2 (:meth:`_batch_shareable`)."""
+        return control.forward_quality_map(self, x, qmap, mask_pol)
+
+    def compress_quality_map(self, x, qmap, mask_pol=None):
+        """The bitstreams of :meth:`forward_quality_map`: one item per image, {"strings": [[one stream per slice], [z]] in the
+        stream order of :meth:`compress_per_image` (always ns1 slice streams: a map never selects the base plan), "shape",
+        "quality_map": {"levels": the image's sorted distinct mask qualities as float64, "index": uint8 ndarray [h, w] of each
+        position's index in them}, "side_bytes": 8 * len(levels) + h * w}.  The map is carried raw (no entropy coding of the
+        map); the decoder needs it to rebuild the masks.  An item whose map is constant q > 0 has the strings of
+        ``compress_per_image`` at q.  Refusals as :meth:`forward_quality_map`."""
+        return control.compress_quality_map(self, x, qmap, mask_pol)
+
+    def decompress_quality_map(self, items, mask_pol=None):
+        """{"x_hat": [B, 3, H, W]} from items of :meth:`compress_quality_map` (one ``shape`` per call): bit-identical to
+        :meth:`forward_quality_map`'s ``x_hat``.  The stored float64 levels are used as they are (``mask_pol`` was applied
+        by the encoder)."""
+        return control.decompress_quality_map(self, items, mask_pol)
+
+    def quality_map_rate(self, x, qmap, mask_pol=None):
+        """The estimated rate of a map without masks, LRP stacks or g_s: {"log2_likelihood_sum": float64 [2, B] (what
+        :meth:`forward_quality_map` returns, to its float64 summation order), "bpp": float64 [B]}.  all_scalable models run
+        the sweep plan's front end, one vam_variance_layers_per_image on each image's levels and one vam_gauss_layer_bits
+        with one bin row per latent position: a position at level index k holds the elements of layers <= k at their
+        in-mask likelihood, every other element counts log2 L(0, 0).  The others call :meth:`forward_quality_map`."""
+        return control.quality_map_rate(self, x, qmap, mask_pol)
+
+    def quality_map_for_bpp(self, x, floor_map, target_bpp, q_tol=1e-3, mask_pol=None):
+        """Spend a rate budget around a region of interest: per image b and target t the largest uniform quality q* in
+        [0, 10] such that the map max(floor_map, q*) stays within t (a region of interest is a floor map with q_roi inside and
+        0 outside; at most 8 distinct values per image).  ``target_bpp``: a float, T floats or [T, B].  Returns {"quality",
+        "bpp", "reached": [T, B], "quality_map": float64 [T, B, h, w] = max(floor_map, q*)} on the host with, for
+        bpp_b(q) = quality_map_rate(max(floor_map, q)):  bpp_b(q*) <= t;  q* = 10 or bpp_b(min(10, q* + q_tol)) > t;  q* = 0 and
+        reached = False when the floor map alone exceeds t.  :func:`rate_search` on grids of 24 points: a pass is one
+        vam_variance_layers_per_image (floor levels and grid points in one list) and one vam_gauss_layer_bits.
+        point-based-std only (ValueError otherwise, as :meth:`qualities_for_bpp`); all_scalable=False is refused."""
+        return control.quality_map_for_bpp(self, x, floor_map, target_bpp, q_tol, mask_pol)
 
     def forward(self, x, quality=None, mask_pol=None, training=True, noise=None):
         """models/pic.py:301-491: the base pass plus one progressive pass per requested quality (default [0, 10]),

@@ -598,6 +598,42 @@ def variance_masks_per_image(sigma: View, table_dev: torch.Tensor, mask: View, n
             "vam_variance_masks_per_image")
 
 
+def layer_table(prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int) -> np.ndarray:
+    """The host bytes (uint8, one L.VamLayerParams record per image) of the table :func:`variance_mask_map` (and
+    vam_variance_layers_per_image) reads: image b's non-decreasing qualities ``prs_per_image[b]`` (1..L.VAM_MAX_LAYER_LEVELS)
+    for segments of ``n_pix`` pixels x ``C_`` channels.  Host arithmetic only (vam_variance_layer_params)."""
+    lists = [[float(p_) for p_ in row] for row in prs_per_image]
+    B = len(lists)
+    width = max([len(r) for r in lists] + [1])
+    flat = (C.c_double * (width * max(B, 1)))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
+    nl = (C.c_int * max(B, 1))(*[len(r) for r in lists])
+    table = np.zeros(B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
+    L.check(L.load().vam_variance_layer_params(flat, nl, B, width, n_pix, C_, table.ctypes.data), "vam_variance_layer_params")
+    return table
+
+
+def variance_mask_map(sigma: View, table_dev: torch.Tensor, level_map: torch.Tensor, mask: View, n_slice: int = 1,
+                      thr: Optional[torch.Tensor] = None):
+    """ONE mask in which every latent pixel takes its own quality: image b's sorted quality list is
+    record b of ``table_dev`` (the bytes of :func:`layer_table` on the device), ``level_map`` uint8 [B, H * W] (or
+    [B, H, W]) the index of each pixel's quality in it.  At the pixels of level k the mask is bit-identical to
+    :func:`variance_mask` on that image alone at that quality; an index beyond the image's list writes 0.  ``thr``
+    [L.VAM_MAX_LAYER_LEVELS, B * n_slice]: level k of image b at [k, b * n_slice + j] for k < the image's count.  Table and
+    map are device buffers, so the call can be captured and the captured graph serves every map."""
+    slice_C = sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C == mask.C and (sigma.B, sigma.H, sigma.W) == (mask.B, mask.H, mask.W)
+    hw = sigma.H * sigma.W
+    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
+        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
+    assert level_map.dtype == torch.uint8 and level_map.is_contiguous() and level_map.device == sigma.buf.device and \
+        level_map.numel() == sigma.B * hw, (level_map.dtype, tuple(level_map.shape), sigma.B, hw)
+    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= L.VAM_MAX_LAYER_LEVELS * sigma.B * n_slice)
+    L.check(L.load().vam_variance_mask_map(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
+                                           table_dev.data_ptr(), level_map.data_ptr(), hw, mask.ptr, mask.ld, hw * mask.ld,
+                                           slice_C, thr.data_ptr() if thr is not None else None, stream_ptr()),
+            "vam_variance_mask_map")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""
@@ -665,15 +701,21 @@ def gauss_levels_decode(sym: "IView", layer: torch.Tensor, mu: View, ks: Sequenc
 
 
 def gauss_layer_bits(y: View, mu: View, sigma: View, layer: torch.Tensor, n_levels: int, bits: torch.Tensor,
-                     count: torch.Tensor, *, y2: Optional[View] = None, ld_layer: Optional[int] = None):
+                     count: torch.Tensor, *, y2: Optional[View] = None, ld_layer: Optional[int] = None,
+                     pix_per_item: Optional[int] = None):
     """Rate-only tail (rate control): per image the fp64 sum of log2 of the IN-mask likelihood — the float
     :func:`gauss_levels_eval` gets for an element inside a mask — and the element count, binned by the layer ids of
     :func:`variance_layers`: ``bits`` float64 / ``count`` int64 [B, n_levels + 1], slot ``n_levels`` for L.LAYER_NONE.
     Both accumulate: clear them first (:func:`memset_zero`); one image may use the head of a longer row.  ``layer`` uint8 with pixel stride ``ld_layer`` (default:
-    contiguous [B, H, W, y.C])."""
+    contiguous [B, H, W, y.C]).  ``pix_per_item`` (default: a whole image): the bins are kept per ``pix_per_item``
+    consecutive pixels instead, [B * H * W / pix_per_item, n_levels + 1] (1: per latent pixel, the quality-map rate)."""
     B = y.B
+    if pix_per_item is not None and pix_per_item != y.H * y.W:
+        assert pix_per_item >= 1 and y.n_pix % pix_per_item == 0, (pix_per_item, y.n_pix)
+        B = y.n_pix // pix_per_item                                  # items
+    pix_per_item = y.H * y.W if pix_per_item is None else pix_per_item
     if ld_layer is None:
-        assert layer.is_contiguous() and tuple(layer.shape) == (B, y.H, y.W, y.C)
+        assert layer.is_contiguous() and tuple(layer.shape) == (y.B, y.H, y.W, y.C)
         ld_layer = y.C
     assert layer.dtype == torch.uint8 and mu.C == sigma.C == y.C and (y2 is None or y2.C == y.C)
     for t, dt in ((bits, torch.float64), (count, torch.int64)):
@@ -681,7 +723,7 @@ def gauss_layer_bits(y: View, mu: View, sigma: View, layer: torch.Tensor, n_leve
         assert t.numel() == B * (n_levels + 1) or (B == 1 and t.numel() > n_levels), (tuple(t.shape), B, n_levels)
     def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
     L.check(L.load().vam_gauss_layer_bits(*p(y), *p(y2), *p(mu), *p(sigma), layer.data_ptr(), ld_layer, n_levels,
-                                          bits.data_ptr(), count.data_ptr(), y.H * y.W, y.n_pix, y.C, stream_ptr()),
+                                          bits.data_ptr(), count.data_ptr(), pix_per_item, y.n_pix, y.C, stream_ptr()),
             "vam_gauss_layer_bits")
 
 

@@ -113,10 +113,14 @@ class _FullTrainFn(torch.autograd.Function):
                                    for o, p, n in zip(plan.offsets, plan.params, need))
 
 
-def _vmask(qtable, q, sigma, mask, n_slice, thr=None):
+def _vmask(qtable, q, sigma, mask, n_slice, thr=None, level_map=None):
     """The variance masks of ``n_slice`` slices at the scalar quality ``q`` or, with ``qtable`` (per-image plans), at each
-    image's own, read from the plan's device table — one level, the same segments, so the same bits per image."""
-    if qtable is not None:
+    image's own, read from the plan's device table — one level, the same segments, so the same bits per image.  With
+    ``level_map`` (quality-map plans) the table holds each image's sorted list and every latent pixel
+    takes the level the map names: still one launch and one mask."""
+    if level_map is not None:
+        ops.variance_mask_map(sigma, qtable, level_map, mask, n_slice=n_slice, thr=thr)
+    elif qtable is not None:
         ops.variance_masks_per_image(sigma, qtable, mask, n_slice=n_slice, thr=thr)
     else:
         ops.variance_mask(sigma, q, mask, n_slice=n_slice, thr=thr)
@@ -126,6 +130,14 @@ def _fill_mask_table(qtable: torch.Tensor, rows: Sequence[Sequence[float]], n_pi
     """Refill a per-image plan's table with image b's mask qualities ``rows[b]``: on the current stream, before the replay
     and outside the capture, so the qualities are inputs of the plan's ONE graph."""
     qtable.copy_(torch.from_numpy(ops.mask_table([[float(q) for q in row] for row in rows], n_pix, C)))
+
+
+def _fill_quality_map(qtable: torch.Tensor, level_map: torch.Tensor, levels: Sequence[Sequence[float]], index, n_pix: int, C: int):
+    """Refill a quality-map plan's two graph inputs: image b's sorted qualities ``levels[b]`` (ops.layer_table) and the uint8
+    index map ``index`` [B, h, w] (host).  On the current stream, before the replay and outside the capture."""
+    idx = torch.from_numpy(np.ascontiguousarray(index, dtype=np.uint8)).view(level_map.shape)
+    qtable.copy_(torch.from_numpy(ops.layer_table([[float(q) for q in row] for row in levels], n_pix, C)))
+    level_map.copy_(idx)
 
 
 def _load_checkpoint(ck: ops.View, checkpoint: torch.Tensor):
@@ -239,12 +251,15 @@ class _FsqPlan:
     """``forward_single_quality`` for one (B,H,W) lowered to libvampic launches."""
 
     def __init__(self, m, B, H, W, base_only, rem_idx, device, symbols=False, train=False,
-                 own_ck=False, train_gs=False, train_lrp=False, sweep=False, per_image=False):
+                 own_ck=False, train_gs=False, train_lrp=False, sweep=False, per_image=False, quality_map=False):
         assert not sweep or (m.all_scalable and not base_only and rem_idx is None and not (symbols or train))
         # per_image: the variance masks read each image's quality from a device table (DESIGN section 9j)
         assert not per_image or not (sweep or base_only or train or own_ck or rem_idx is not None)
-        self.per_image = per_image
-        self.qtable = _mask_table_buffer(B, device) if per_image else None
+        # quality_map: every latent pixel takes its own level of its image's sorted list (DESIGN section 9k)
+        assert not quality_map or not (per_image or sweep or base_only or train or own_ck or rem_idx is not None)
+        self.per_image, self.quality_map = per_image, quality_map
+        self.qtable = _mask_table_buffer(B, device) if per_image or quality_map else None
+        self.level_map = torch.zeros((B, (H // 16) * (W // 16)), dtype=torch.uint8, device=device) if quality_map else None
         self.m, self.B, self.H, self.W = m, B, H, W
         self.train_gs = train_gs    # the synthesis transform in use is being trained (refine_gs): taped g_s + backward plan
         self.train_lrp = train_lrp  # ... and the progressive LRP stacks with it (refine_gs --lrp)
@@ -279,8 +294,9 @@ class _FsqPlan:
         self.y_top = self.y.window(d, d)
         self.y_sub = self.y.window(0, d) if m.delta_encode else None                        # pic.py:583-584
         # the masks' thresholds — not collected by the per-slice launches of the sequential schedule
-        self.thr = torch.empty((B * ns,), **f32) if m.all_scalable and not sweep else None
-        plan.keep.append(self.thr)
+        # (a quality-map plan: one row per level of the longest list)
+        self.thr = torch.empty(((L.VAM_MAX_LAYER_LEVELS if quality_map else 1) * B * ns,), **f32) if m.all_scalable and not sweep else None
+        plan.keep += [self.thr, self.level_map]
         if not m.all_scalable:
             # pic.py:586-587: the (mu, sigma) stacks of progressive slice j read the DECODED progressive slices j-sp..j-1,
             # so mask, quantisation and LRP of a slice must finish before the next slice's stacks start — one slice at a
@@ -432,7 +448,7 @@ class _FsqPlan:
         y_top, mu_f, std_f, mask = sl(self.y_top, j0, n), sl(self.mu_f, j0, n), sl(self.std_f, j0, n), sl(self.mask, j0, n)
         y_sub = sl(self.y_sub, j0, n) if self.y_sub is not None else None
         lik = sl(self.lik, ns + j0, n)
-        plan.call(lambda: _vmask(self.qtable, self.pr, std_f, mask, n, self.thr))                       # pic.py:621-622
+        plan.call(lambda: _vmask(self.qtable, self.pr, std_f, mask, n, self.thr, self.level_map))      # pic.py:621-622
         plan.call(lambda: ops.gauss_tail(y_top, mu_f, std_f, y2=y_sub, mask=mask, yhat=sl(rq, j0, n), lik=lik, log2sum=ls_y,
                                          sym=sl(self.sym, ns + j0, n) if self.symbols else None))      # pic.py:625-629
         if self.train:
@@ -550,6 +566,18 @@ class _FsqPlan:
             self.runner.replay(("per_image",), self.plan.run, use_graph)
         return self._outputs(clone)
 
+    def execute_quality_map(self, x, levels: Sequence[Sequence[float]], index, use_graph, clone=True):
+        """:meth:`execute` of a quality_map plan: latent pixel p of image b at mask quality ``levels[b][index[b, p]]``
+        (``levels[b]`` sorted, ``index`` uint8 [B, h, w] on the host).  Table and map are refilled on the runner's stream
+        before the replay, outside the capture: they are inputs of the plan's ONE graph."""
+        assert self.quality_map and len(levels) == self.B
+        self.generation += 1
+        with self.runner.on_stream():
+            self.x_in.copy_(x)
+            _fill_quality_map(self.qtable, self.level_map, levels, index, (self.H // 16) * (self.W // 16), self.m.dim_chunk)
+            self.runner.replay(("quality_map",), self.plan.run, use_graph)
+        return self._outputs(clone)
+
     def _outputs(self, clone):
         fin = (lambda t: t.clone()) if clone else (lambda t: t)
         nchw = lambda v: fin(v.torch_nchw())
@@ -599,6 +627,26 @@ class _RateTail:
         ops.variance_layers(img(pa["std"]), prs, layer, n_slice=self.ns)                      # pic.py:621-622, all levels
         ops.gauss_layer_bits(img(pa["y_top"]), img(pa["mu"]), img(pa["std"]), layer, len(prs), acc[0], acc[1].view(torch.int64),
                              y2=None if pa["y_sub"] is None else img(pa["y_sub"]))
+
+    def map_bins(self, levels: Sequence[Sequence[float]]) -> torch.Tensor:
+        """The bins of a quality map's rate, eagerly: one vam_variance_layers_per_image on image b's sorted
+        list ``levels[b]`` and one vam_gauss_layer_bits at pix_per_item = 1.  Returns [2, B, h * w, n + 1] (n = the longest
+        list): per latent pixel the float64 sums and (as int64) the counts by level, slot n = no level."""
+        pa, sg = self.parts, self.parts["std"]
+        n = max(len(r) for r in levels)
+        acc = torch.zeros((2, sg.B, sg.H * sg.W, n + 1), dtype=torch.float64, device=sg.buf.device)
+        ops.variance_layers_per_image(pa["std"], levels, self.layer, n_slice=self.ns)
+        ops.gauss_layer_bits(pa["y_top"], pa["mu"], pa["std"], self.layer, n, acc[0], acc[1].view(torch.int64), y2=pa["y_sub"],
+                             pix_per_item=1)
+        return acc
+
+    def map_values(self, acc: torch.Tensor) -> torch.Tensor:
+        """[B, h * w, n] from :meth:`map_bins`: the progressive log2 sum of each latent pixel were it at level k — the
+        elements of layers <= k at their in-mask likelihood, every other element at log2 L(0, 0)."""
+        n = acc.shape[-1] - 1
+        bits, count = acc[0], acc[1].view(torch.int64)
+        total = count.sum(-1, keepdim=True)
+        return bits[..., :n].cumsum(-1) + (total - count[..., :n].cumsum(-1)).double() * self.outside
 
     def level_sums(self, acc: torch.Tensor, n_levels: int) -> torch.Tensor:
         """[..., n_levels] progressive log2 sums from ``acc`` [2, ..., >= n_levels + 1]: level k holds the elements of layers
@@ -901,12 +949,15 @@ class _DecPlan:
     kernel's K order is canonical, so mu / sigma / masks / indexes are bit-identical to the
     encoder's although the launches are grouped differently."""
 
-    def __init__(self, m, B, hz, wz, base_only, rem_idx, device, per_image: bool = False):
-        """``per_image``: the per-slice masks read each image's quality from ``qtable`` (decode_per_image refills it)."""
-        assert not per_image or not (base_only or rem_idx is not None)
+    def __init__(self, m, B, hz, wz, base_only, rem_idx, device, per_image: bool = False, quality_map: bool = False):
+        """``per_image``: the per-slice masks read each image's quality from ``qtable`` (decode_per_image refills it);
+        ``quality_map``: each latent pixel's from ``qtable`` and ``level_map``."""
+        assert not (per_image or quality_map) or not (base_only or rem_idx is not None)
+        assert not (per_image and quality_map)
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
-        self.per_image = per_image
-        self.qtable = _mask_table_buffer(B, device) if per_image else None
+        self.per_image, self.quality_map = per_image, quality_map
+        self.qtable = _mask_table_buffer(B, device) if per_image or quality_map else None
+        self.level_map = torch.zeros((B, 16 * hz * wz), dtype=torch.uint8, device=device) if quality_map else None
         self.device = torch.device(device)
         self.pr = 0.0
         self.runner = E.Runner(device, cap=32)           # stream ordering; _ProgDecPlan's ("base",) graph
@@ -959,7 +1010,7 @@ class _DecPlan:
             ms = sc.lower_prog_params(Pa, j)
             if self.rem_idx is not None:
                 sc.lower_rem(Pa, self, [j])
-            Pa.call(lambda j=j: _vmask(self.qtable, self.pr, sl(sc.std_f, j), sl(sc.mask, j), 1))                  # pic.py:942
+            Pa.call(lambda j=j: _vmask(self.qtable, self.pr, sl(sc.std_f, j), sl(sc.mask, j), 1, level_map=self.level_map))   # pic.py:942
             Pa.call(lambda j=j: ops.build_indexes(sl(sc.std_f, j), table, mask=sl(sc.mask, j), out=sl(self.idx_p, j)))  # :945
             Pb.call(lambda j=j: ops.dequantize(sl(self.sym_p, j), sl(sc.mu_f, j), sl(sc.rq, j)))                  # :948
             sc.lower_prog_lrp(Pb, [j], sc.heads, [ms], sc.rq, sc.yb, sc.yp)
@@ -997,11 +1048,17 @@ class _DecPlan:
             self._decode_slice(strings[i], self.sc.sl(idx, i), self.sc.sl(sym, i), tg, self.m.dim_chunk)
             Pb.run()
 
-    def decode(self, strings, pr, checkpoint_rep):
-        """``pr``: the mask quality, or (per_image plans) one per image."""
+    def decode(self, strings, pr, checkpoint_rep, quality_map=None):
+        """``pr``: the mask quality, or (per_image plans) one per image; ``quality_map`` (quality_map plans): (levels per
+        image, uint8 index map [B, h, w] on the host), and ``pr`` is not read."""
         from . import bitstream as bs
         m = self.m
-        if self.per_image:
+        if self.quality_map:
+            levels, index = quality_map
+            assert len(levels) == self.B
+            with self.runner.on_stream():
+                _fill_quality_map(self.qtable, self.level_map, levels, index, self.h * self.w, m.dim_chunk)
+        elif self.per_image:
             assert len(pr) == self.B
             with self.runner.on_stream():
                 _fill_mask_table(self.qtable, [[p_] for p_ in pr], self.h * self.w, m.dim_chunk)

@@ -318,6 +318,22 @@ int vam_variance_masks_per_image(const float* sigma, int ld, long batch_stride, 
                                  int n_slice, int n_pix, int C, const vam_layer_params* table_dev, int max_levels,
                                  float* mask_out, int ld_mask, long mask_batch_stride, long mask_slice_stride,
                                  long mask_level_stride, float* thr_out, void* stream);
+/* Quality maps (VarianceMaskingPIC.forward_quality_map): ONE float mask in which every latent pixel
+ * takes its own quality.  table_dev: the records of vam_variance_layer_params (image b's non-decreasing list of
+ * 1..VAM_MAX_LAYER_LEVELS qualities); level_map[b * map_batch_stride + p] (uint8, p < n_pix): the index of pixel p's
+ * quality in image b's list.  The kernel of vam_variance_layers_per_image selects every level's threshold once per
+ * segment, then writes, for every slice j, pixel p and channel c,
+ *   mask_out[b, j, p, c] = vam_variance_mask(sigma of image b alone, prs[b][level_map[b, p]])[j, p, c]
+ * bit for bit (float 0/1, the layout and strides of vam_variance_mask): all zero where the quality is 0, all one where
+ * it is >= 10 (even in a segment that holds a NaN), zero in a NaN segment wherever the level needs the threshold.  A map
+ * entry >= the image's n_levels writes 0 at that pixel; a record whose n_levels is outside 1..VAM_MAX_LAYER_LEVELS makes
+ * the kernel write 0 for the whole image.  Level k's thresholds land at thr_out[k * n_batch * n_slice + b * n_slice + j]
+ * for k < n_levels[b], as vam_variance_layers_per_image writes them.  Table and map are device buffers: the call can be
+ * captured, and the captured graph serves every map. */
+int vam_variance_mask_map(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice,
+                          int n_pix, int C, const vam_layer_params* table_dev, const uint8_t* level_map,
+                          long map_batch_stride, float* mask_out, int ld_mask, long mask_batch_stride,
+                          long mask_slice_stride, float* thr_out, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
