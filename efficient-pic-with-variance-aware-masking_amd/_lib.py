@@ -199,6 +199,7 @@ _SIGNATURES = {
     "vam_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vam_conv_wgrad_group": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vam_conv_wgrad_plan": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vam_conv_wgrad_route": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vam_conv_wgrad_lds_grid": (C.c_int, [C.c_int, C.c_int]),
     "vam_colsum_workspace": (C.c_size_t, [C.c_long, C.c_int]),
     "vam_colsum": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

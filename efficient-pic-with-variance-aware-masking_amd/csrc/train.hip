@@ -27,6 +27,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // the caller-owned workspace [S][N][C][taps] (+ [S][N] for the bias); wgrad_reduce_kernel adds the S partials in split
 // order.  Deterministic either way: no float atomics.
 constexpr int WG_WAVES = 8, WG_BATCH = 16;   // MFMAs per batch; each covers 2 pixels
+constexpr int WG_STEP = 16;                  // pixels of one bf16 MFMA step (v_mfma_f32_32x32x16_bf16)
+constexpr int WG_SPLIT = 1;                  // SPLIT of the bf16-pipe instantiations the host launches (steps per loop iteration)
 
 
 struct WgradArgs {
@@ -125,12 +127,12 @@ __global__ __launch_bounds__(WG_WAVES * 64) void wgrad_kernel(const WgradArgs ar
     };
     const __amdgpu_buffer_rsrc_t r_dy = desc(dy), r_x = desc(x);
     const unsigned OOB = 0x80000000u;
-    for (long pb = p_begin + (long)wid * (16 * NH); pb < p_end; pb += (long)WG_WAVES * 16 * NH) {
+    for (long pb = p_begin + (long)wid * (WG_STEP * NH); pb < p_end; pb += (long)WG_WAVES * WG_STEP * NH) {
       float af[NH][TN][8], bf[NH][TC][8];
 #pragma unroll
       for (int hf = 0; hf < NH; ++hf) {
         // this lane's 8 pixels of the step: pb + 16 hf + 8 lh + j; position of the first by division, the rest by carry
-        const long pf = pb + 16 * hf + 8 * lh;
+        const long pf = pb + WG_STEP * hf + 8 * lh;
         int bi = (int)(pf / HW);
         const int r0 = (int)(pf - (long)bi * HW);
         int oy = r0 / W, ox = r0 - oy * W;
@@ -487,6 +489,7 @@ bool wgrad2_eligible(const vam_wgrad& p);
 bool wgrad2_grid(int H, int W);
 int wgrad2_splits(const vam_wgrad& p);
 int wgrad2_launch_class(const vam_wgrad* probs, int n, hipStream_t stream);
+void wgrad2_route(const vam_wgrad& p, int out[5]);     // wn, wc, tn, tc, kp of wgrad2_tile(p)
 
 static inline unsigned sgrid(long n, int block) {
   long g = (n + block - 1) / block;
@@ -523,6 +526,12 @@ static bool wg_split_on() {             // VAMPIC_WGRAD=f32: the fp32-pipe loop 
   return wg_split != 0;
 }
 
+// the bf16-pipe loops address dY and x with 32-bit byte offsets: tensors of 2 GiB and more take the fp32-pipe loop
+static bool wg_small(const vam_wgrad& p) {
+  const double px = (double)p.B * (p.stride == 2 ? (double)p.Hx * p.Wx : (double)p.H * p.W);
+  return !((double)p.B * p.H * p.W * p.ld_dy * 4.0 >= 2147483648.0 || px * p.ld_x * 4.0 >= 2147483648.0);
+}
+
 static int wgrad_splits(const vam_wgrad& p) {
   if (wgrad2_eligible(p)) return wgrad2_splits(p);
   // enough blocks to fill the chip (4 blocks of 8 waves per CU x 256 CUs, twice over), at least 2048 pixels per split
@@ -544,6 +553,26 @@ int vam_conv_wgrad_plan(const vam_wgrad* p, size_t* workspace_bytes) {
   const int s = wgrad_splits(*p);
   if (workspace_bytes) *workspace_bytes = s > 1 ? (size_t)s * ((size_t)p->N * p->C * p->kh * p->kw + p->N) * sizeof(float) : 0;
   return s;
+}
+
+// Which kernel a problem launched ALONE takes, by the functions the launch itself asks (host arithmetic only, no GPU):
+// out = {kernel (0 register-gather wgrad_kernel, 1 LDS-tiled wgrad2_kernel), pipe (0 fp32, 1 bf16x3), wn, wc, tn, tc, kp,
+// plane input}.  Gather kernel: wn = wc = 0, tn x tc = its 32 x 32 blocks per workgroup, kp = pixels per loop step.
+int vam_conv_wgrad_route(const vam_wgrad* p, int out[8]) {
+  if (!p || !out || p->B <= 0 || p->H <= 0 || p->W <= 0 || p->C <= 0 || p->N <= 0 || p->kh <= 0) return 1;
+  const bool use_split = wg_split_on() && wg_small(*p);
+  const bool lds = use_split && wgrad2_eligible(*p);
+  out[0] = lds ? 1 : 0;
+  out[1] = use_split ? 1 : 0;
+  if (lds) {
+    wgrad2_route(*p, out + 2);
+  } else {
+    out[2] = out[3] = 0;
+    wgrad_tile(*p, &out[4], &out[5]);
+    out[6] = use_split ? WG_STEP * WG_SPLIT : 2 * WG_BATCH;       // the loop strides of wgrad_kernel<.., WG_SPLIT> / <.., 0>
+  }
+  out[7] = (p->flags & VAM_WGRAD_X_P3) ? 1 : 0;
+  return 0;
 }
 
 int vam_conv_wgrad_group(const vam_wgrad* probs, int n_probs, void* stream) {
@@ -571,8 +600,7 @@ int vam_conv_wgrad_group(const vam_wgrad* probs, int n_probs, void* stream) {
       max_red = tot > max_red ? tot : max_red;
     }
     flops += 2.0 * p.B * p.H * p.W * (double)p.C * p.N * p.kh * p.kw;
-    const double px = (double)p.B * (p.stride == 2 ? (double)p.Hx * p.Wx : (double)p.H * p.W);
-    if ((double)p.B * p.H * p.W * p.ld_dy * 4.0 >= 2147483648.0 || px * p.ld_x * 4.0 >= 2147483648.0) small = false;
+    if (!wg_small(p)) small = false;
   }
   const bool use_split = wg_split_on() && small;
   WgradArgs wa;
@@ -611,7 +639,7 @@ int vam_conv_wgrad_group(const vam_wgrad* probs, int n_probs, void* stream) {
     }
 #define VAM_WG(TN_, TC_) \
     if (tn == TN_ && tc == TC_) {                                                                                                      \
-      if (use_split) hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, 1>), dim3(max_blocks, n_sub), dim3(WG_WAVES * 64), 0, (hipStream_t)stream, sub); \
+      if (use_split) hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, WG_SPLIT>), dim3(max_blocks, n_sub), dim3(WG_WAVES * 64), 0, (hipStream_t)stream, sub); \
       else hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, 0>), dim3(max_blocks, n_sub), dim3(WG_WAVES * 64), 0, (hipStream_t)stream, sub);           \
     }
     VAM_WG(1, 1) VAM_WG(2, 1) VAM_WG(1, 2) VAM_WG(2, 2) VAM_WG(3, 1) VAM_WG(3, 2)

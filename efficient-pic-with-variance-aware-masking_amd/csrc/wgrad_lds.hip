@@ -427,6 +427,11 @@ W2Tile wgrad2_tile(const vam_wgrad& p) {
   return t;
 }
 
+void wgrad2_route(const vam_wgrad& p, int out[5]) {
+  const W2Tile t = wgrad2_tile(p);
+  out[0] = t.wn; out[1] = t.wc; out[2] = t.tn; out[3] = t.tc; out[4] = t.kp;
+}
+
 int wgrad2_splits(const vam_wgrad& p) {
   // Pixel splits of ONE problem.  A workgroup slot is a CU x (workgroups that fit its LDS); with `per` tiles (kernel rows x
   // n tiles x c tiles) and S splits the launch runs ceil(per S / slots) rounds of ceil(chunks / S) chunks each.  Pick the S

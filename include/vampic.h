@@ -502,6 +502,10 @@ typedef struct vam_wgrad {
 int vam_conv_wgrad_lds_grid(int H, int W);
 /* Suggested number of pixel splits for a problem (>= 1) and the workspace it needs (0 bytes when 1). */
 int vam_conv_wgrad_plan(const vam_wgrad* problem, size_t* workspace_bytes);
+/* Which kernel instantiation a problem launched alone takes (host arithmetic, no GPU needed; returns 0, or 1 on bad
+ * arguments): out = {kernel (0 register-gather, 1 LDS-tiled), pipe (0 fp32, 1 bf16x3), waves wn, wc (0, 0: gather kernel),
+ * 32x32 blocks tn, tc, pixels per step kp, plane input}. */
+int vam_conv_wgrad_route(const vam_wgrad* problem, int out[8]);
 int vam_conv_wgrad_group(const vam_wgrad* problems, int n_problems, void* stream);
 int vam_conv_wgrad(const float* x, int ld_x, const float* dy, int ld_dy, int B, int H, int W, int kh, int kw,
                    int C, int N, float* dw_oihw, float* db, int cin_total, int c_off, void* stream);

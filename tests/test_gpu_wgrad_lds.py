@@ -1,7 +1,9 @@
-"""The LDS-tiled weight-gradient kernel (csrc/wgrad_lds.hip, round 4): k3 / k5 layers on grids of width 16 / 32 / 64k,
-stride 1 and 2, against autograd of F.conv2d (fp32 CPU; tolerance 2e-5 of the max: different summation order), against
-the register-gather kernel it replaces (VAMPIC_WGRAD_LDS=0 in a child process is not needed: shapes the new kernel
-declines — width 8, 1x1 — still take the old one inside the same launch group), and bit-reproducible."""
+"""The LDS-tiled weight-gradient kernel (csrc/wgrad_lds.hip, round 4): k1 / k3 / k5 layers on grids of width 16 / 32 / 64k,
+stride 1 and 2, against autograd of F.conv2d (fp32 CPU; tolerance 2e-5 of the max: different summation order), beside
+the register-gather kernel (VAMPIC_WGRAD_LDS=0 in a child process is not needed here: shapes the new kernel declines —
+width 8, channel counts that are no multiple of 4, fewer than 16 input or 32 output channels — still take the old one
+inside the same launch group; 1x1 layers on the supported grids take the new kernel since wgrad2_eligible accepts
+kh == 1), and bit-reproducible.  The float64 contract with elementwise bounds is tests/test_gpu_wgrad_contract.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -67,8 +69,8 @@ def test_lds_wgrad_matches_autograd(k, stride, segs, n, hw, B):
 
 
 def test_mixed_group_routes_each_problem_to_its_kernel():
-    """One grouped launch holding a k3 problem on a 16 x 16 grid (LDS-tiled kernel), one on an 8 x 8 grid and a 1x1 layer
-    (register-gather kernel): every problem gets its own result."""
+    """One grouped launch holding a k3 and a 1x1 problem on a 16 x 16 grid (LDS-tiled kernel) and a k3 and a 1x1 problem on
+    an 8 x 8 grid (register-gather kernel): every problem gets its own result."""
     out = []
     probs = []
     for (k, hw, c, n) in [(3, (16, 16), 64, 64), (3, (8, 8), 64, 64), (1, (16, 16), 96, 192), (1, (8, 8), 96, 192)]:
