@@ -196,6 +196,14 @@ _SIGNATURES = {
     "vam_eb_forward_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_void_p]),
     "vam_ssim_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_avgpool2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vam_msssim_partial_doubles": (C.c_long, [C.c_int] * 3),
+    "vam_msssim_partial_offset": (C.c_long, [C.c_int] * 4),
+    "vam_msssim_fwd_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    "vam_msssim_pool2": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "vam_msssim_combine": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 5),
+    "vam_msssim_bwd_level": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_float, C.c_float, C.c_int]
+                             + [C.c_void_p] * 5),
     "vam_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vam_conv_wgrad_group": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vam_conv_wgrad_plan": (C.c_int, [C.c_void_p, C.c_void_p]),

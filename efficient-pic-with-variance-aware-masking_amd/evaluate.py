@@ -455,3 +455,15 @@ def compute_msssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 1.0) ->
             x, y, H, W = nx, ny, Ho, Wo
     w = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64, device=x.device).reshape(-1, 1)
     return float(torch.prod(torch.stack(vals, 0) ** w, dim=0).mean())
+
+
+def msssim_per_image(a: torch.Tensor, b: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """MS-SSIM of each image of ``b`` against ``a`` ([B,C,H,W] CUDA tensors): [B] float64, the mean over channels, from the
+    LDS-tiled forward of the training loss (ops.msssim_forward, csrc/msssim.hip) — deterministic, no host synchronisation.
+    The function of :func:`compute_msssim` (whose mean over the batch it reproduces up to summation order); a plane with a
+    non-positive level mean counts as 0."""
+    from . import _lib as L
+    L.require_gpu()
+    ops._msssim_check(a, b)
+    val, _, _ = ops.msssim_forward(a.detach().float().contiguous(), b.detach().float().contiguous(), data_range)
+    return val

@@ -153,14 +153,38 @@ def train_one_epoch(model, criterion, train_dataloader: Iterable[torch.Tensor], 
     return counter, tot["loss"] / n, tot["bpp_loss"] / n, tot["mse_loss"] / n, tot["bpp_scalable"] / n
 
 
+METRICS = ("mse", "ms-ssim")
+
+
+def _check_metric(metric: str) -> str:
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    return metric
+
+
+def _msssim_per_level(x_hat: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """MS-SSIM of every level of ``x_hat`` ([L,B,3,H,W], or [B,3,H,W] for a single-quality output) against ``target``
+    [B,3,H,W], as one call of ops.ms_ssim on L*B images: [L], the mean over the images of a level.  Differentiable in
+    ``x_hat`` (HIP forward and backward, csrc/msssim.hip)."""
+    from . import ops
+    xh = x_hat if x_hat.dim() == 5 else x_hat.unsqueeze(0)
+    n_lvl, n_img = xh.shape[0], xh.shape[1]
+    tgt = target.detach().unsqueeze(0).expand(n_lvl, *target.shape).reshape(n_lvl * n_img, *target.shape[1:])
+    return ops.ms_ssim(tgt, xh.reshape(n_lvl * n_img, *xh.shape[2:])).view(n_lvl, n_img).mean(dim=1)
+
+
 # ============================================================================= decoder refinement (--training_type refine_gs)
 class DistortionLoss(nn.Module):
     """training/loss.py:126-187: loss = weight * lmbda * mse(x, x_hat); the rates are reported only (and, like the
-    reference's, computed from whatever likelihoods the forward returned)."""
+    reference's, computed from whatever likelihoods the forward returned).
 
-    def __init__(self, weight=255 ** 2, device="cuda"):
+    ``metric="ms-ssim"`` (beyond the reference): loss = msssim_weight * mean_l(lmbda * (1 - msssim_l)) with
+    ``out["ms_ssim_loss"]`` the per-level MS-SSIM (ops.ms_ssim); ``out["mse_loss"]`` stays, detached and reported only."""
+
+    def __init__(self, weight=255 ** 2, device="cuda", metric="mse", msssim_weight=1.0):
         super().__init__()
         self.weight, self.device = weight, device
+        self.metric, self.msssim_weight = _check_metric(metric), msssim_weight
 
     def forward(self, output, target, lmbda=1e-2):
         n_img, _, H, W = target.size()
@@ -168,13 +192,18 @@ class DistortionLoss(nn.Module):
         tgt = target
         if n_rec != 1 and n_rec != n_img:
             tgt = target.unsqueeze(0).repeat(n_rec, 1, 1, 1, 1)
-        out = {"mse_loss": torch.nn.functional.mse_loss(tgt, output["x_hat"])}
+        x_hat = output["x_hat"].detach() if self.metric == "ms-ssim" else output["x_hat"]
+        out = {"mse_loss": torch.nn.functional.mse_loss(tgt, x_hat)}
         den = -math.log(2) * n_img * H * W
         lik = output["likelihoods"]
         out["bpp_hype"] = torch.log(lik["z"].detach()).sum() / den
         out["bpp_base"] = torch.log(lik["y"].detach().squeeze(0)).sum() / den
         out["bpp_scalable"] = out["bpp_base"] * 0.0
         out["bpp_loss"] = out["bpp_scalable"] + out["bpp_base"] + n_rec * out["bpp_hype"]
+        if self.metric == "ms-ssim":
+            out["ms_ssim_loss"] = _msssim_per_level(output["x_hat"], target)
+            out["loss"] = self.msssim_weight * (lmbda * (1.0 - out["ms_ssim_loss"])).mean()
+            return out
         out["loss"] = self.weight * (lmbda * out["mse_loss"]).mean()
         return out
 
@@ -242,13 +271,18 @@ class ScalableRateDistortionLoss(nn.Module):
     """training/loss.py:6-66: loss = bpp_scalable + bpp_base + n_rec * bpp_hype + weight * mean(lmbda * mse per level).
     Kept with the reference's own accounting: "y_prog" holds the base slices' likelihoods again, so the base rate enters
     twice; ``n_rec`` = x_hat.shape[0] — the number of levels for the stacked output of ``forward``, the
-    number of images for a single-quality output."""
+    number of images for a single-quality output.
 
-    def __init__(self, weight=255 ** 2, lmbda_list=(0.005, 0.05), device="cuda"):
+    ``metric="ms-ssim"`` (beyond the reference): the distortion of a level is 1 - mean_b ms_ssim and
+    loss = bpp_loss + msssim_weight * mean_l(lmbda_l * (1 - msssim_l)); ``out["ms_ssim_loss"]`` is the per-level MS-SSIM
+    (CompressAI's key), ``out["mse_loss"]`` stays, detached and reported only (the epoch loops read it)."""
+
+    def __init__(self, weight=255 ** 2, lmbda_list=(0.005, 0.05), device="cuda", metric="mse", msssim_weight=1.0):
         super().__init__()
         self.scalable_levels = len(lmbda_list)
         self.lmbda = torch.tensor(list(lmbda_list), dtype=torch.float32).to(device)
         self.weight, self.device = weight, device
+        self.metric, self.msssim_weight = _check_metric(metric), msssim_weight
 
     def forward(self, output, target, lmbda=None):
         n_img, _, H, W = target.size()
@@ -257,7 +291,8 @@ class ScalableRateDistortionLoss(nn.Module):
         if n_rec != 1 and n_rec != n_img:
             tgt = tgt.repeat(n_rec, 1, 1, 1, 1)
         lm = self.lmbda if lmbda is None else torch.tensor([lmbda], dtype=torch.float32).to(self.device)
-        out = {"mse_loss": ((tgt - output["x_hat"]) ** 2).mean(dim=(1, 2, 3, 4))}       # one value per level
+        x_hat = output["x_hat"].detach() if self.metric == "ms-ssim" else output["x_hat"]
+        out = {"mse_loss": ((tgt - x_hat) ** 2).mean(dim=(1, 2, 3, 4))}       # one value per level
         den = -math.log(2) * n_img * H * W
         lik = output["likelihoods"]
         out["bpp_hype"] = torch.log(lik["z"]).sum() / den
@@ -268,6 +303,10 @@ class ScalableRateDistortionLoss(nn.Module):
             out["bpp_base"] = torch.log(lik["y"].squeeze(0)).sum() / den
             out["bpp_scalable"] = torch.log(lik["y"]).sum() / den * 0.0
         out["bpp_loss"] = out["bpp_scalable"] + out["bpp_base"] + n_rec * out["bpp_hype"]
+        if self.metric == "ms-ssim":
+            out["ms_ssim_loss"] = _msssim_per_level(output["x_hat"], target)
+            out["loss"] = out["bpp_loss"] + self.msssim_weight * (lm * (1.0 - out["ms_ssim_loss"])).mean()
+            return out
         out["loss"] = out["bpp_loss"] + self.weight * (lm * out["mse_loss"]).mean()
         return out
 
@@ -358,9 +397,10 @@ class RateDistortionLoss(ScalableRateDistortionLoss):
     """training/loss.py:67-124: ScalableRateDistortionLoss's arithmetic with the Lagrangian passed per call.  The reference
     never sets ``self.lmbda`` (:95-96), so calling it without ``lmbda`` fails there too."""
 
-    def __init__(self, weight=255 ** 2, device="cuda"):
+    def __init__(self, weight=255 ** 2, device="cuda", metric="mse", msssim_weight=1.0):
         nn.Module.__init__(self)
         self.weight, self.device = weight, device
+        self.metric, self.msssim_weight = _check_metric(metric), msssim_weight
 
     def forward(self, output, target, lmbda=None):
         if lmbda is None:

@@ -1261,3 +1261,119 @@ def prof_read():
         L.check(lib.vam_prof_read(fam, C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
         out[name] = {"ms": ms.value, "launches": n.value, "flops": fl.value, "bytes": by.value}
     return out
+
+
+# ------------------------------------------------------------------ differentiable MS-SSIM (csrc/msssim.hip)
+_MS_WINDOWS: dict = {}
+
+
+def _msssim_window(device) -> torch.Tensor:
+    """The 11-tap Gaussian (sigma 1.5) in float32, as pytorch_msssim builds it; one device copy per device."""
+    key = str(device)
+    if key not in _MS_WINDOWS:
+        coords = torch.arange(11, dtype=torch.float32) - 5
+        g = torch.exp(-(coords ** 2) / (2 * 1.5 ** 2))
+        _MS_WINDOWS[key] = (g / g.sum()).to(device)
+    return _MS_WINDOWS[key]
+
+
+def _msssim_check(x: torch.Tensor, y: torch.Tensor):
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"expected two [B,C,H,W] tensors of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not (x.is_cuda and y.is_cuda):
+        raise ValueError("ms_ssim runs on the GPU only: both tensors must be CUDA tensors (there is no CPU fallback)")
+    if min(x.shape[2:]) <= (11 - 1) * 2 ** 4:
+        raise ValueError("image too small for 5 scales with an 11-tap window (smaller side must exceed 160)")
+
+
+def msssim_forward(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, keep_pyramid: bool = False):
+    """The forward of :func:`ms_ssim` on contiguous fp32 [B,C,H,W] CUDA tensors: 5 level launches, 4 pool launches and the
+    combine launch on the current stream, no host synchronisation.  Returns (val [B] float64, val32 [B] float32, state);
+    ``state`` holds what the backward needs (the pooled pyramids and the upstream factors) when ``keep_pyramid``."""
+    lib = L.load()
+    B, C_, H, W = x.shape
+    planes = B * C_
+    win = _msssim_window(x.device)
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    n_part = lib.vam_msssim_partial_doubles(planes, H, W)
+    if n_part <= 0:
+        raise ValueError("image too small for 5 scales with an 11-tap window (smaller side must exceed 160)")
+    partial = torch.empty(n_part, dtype=torch.float64, device=x.device)
+    st = stream_ptr()
+    pyramid = []
+    xl, yl, h, w = x, y, H, W
+    for lvl in range(5):
+        off = lib.vam_msssim_partial_offset(planes, H, W, lvl)
+        L.check(lib.vam_msssim_fwd_level(xl.data_ptr(), yl.data_ptr(), planes, h, w, win.data_ptr(), c1, c2, int(lvl == 4),
+                                         partial.data_ptr() + 8 * off, st), "vam_msssim_fwd_level")
+        pyramid.append((xl, yl, h, w))
+        if lvl < 4:
+            ho, wo = (h + 2 * (h % 2) - 2) // 2 + 1, (w + 2 * (w % 2) - 2) // 2 + 1
+            nx = torch.empty((planes, ho, wo), dtype=torch.float32, device=x.device)
+            ny = torch.empty_like(nx)
+            L.check(lib.vam_msssim_pool2(xl.data_ptr(), yl.data_ptr(), nx.data_ptr(), ny.data_ptr(), planes, h, w, st),
+                    "vam_msssim_pool2")
+            xl, yl, h, w = nx, ny, ho, wo
+    means = torch.empty((5, planes), dtype=torch.float64, device=x.device)
+    dvdm = torch.empty_like(means)
+    val = torch.empty(B, dtype=torch.float64, device=x.device)
+    val32 = torch.empty(B, dtype=torch.float32, device=x.device)
+    L.check(lib.vam_msssim_combine(partial.data_ptr(), B, C_, H, W, means.data_ptr(), dvdm.data_ptr(), val.data_ptr(),
+                                   val32.data_ptr(), st), "vam_msssim_combine")
+    state = (pyramid, dvdm, (c1, c2), (B, C_)) if keep_pyramid else None
+    return val, val32, state
+
+
+def msssim_backward(state, gout: torch.Tensor) -> torch.Tensor:
+    """d(sum_b gout[b] * ms_ssim[b]) / dy from the state of :func:`msssim_forward`: 5 launches, coarse to fine."""
+    lib = L.load()
+    pyramid, dvdm, (c1, c2), (B, C_) = state
+    win = _msssim_window(dvdm.device)
+    gout = gout.detach().to(torch.float32).contiguous()
+    st = stream_ptr()
+    g_coarse = None
+    for lvl in range(4, -1, -1):
+        xl, yl, h, w = pyramid[lvl]
+        g = torch.empty((B * C_, h, w), dtype=torch.float32, device=dvdm.device)
+        L.check(lib.vam_msssim_bwd_level(xl.data_ptr(), yl.data_ptr(), B, C_, h, w, win.data_ptr(), c1, c2, int(lvl == 4),
+                                         dvdm[lvl].data_ptr(), gout.data_ptr(), None if g_coarse is None else g_coarse.data_ptr(),
+                                         g.data_ptr(), st), "vam_msssim_bwd_level")
+        g_coarse = g
+    return g_coarse.view(B, C_, *g_coarse.shape[1:])
+
+
+class _MsSsimFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, data_range):
+        xc, yc = x.detach().float().contiguous(), y.detach().float().contiguous()
+        _, val32, state = msssim_forward(xc, yc, data_range, keep_pyramid=ctx.needs_input_grad[1])
+        ctx.state = state
+        ctx.y_dtype = y.dtype
+        return val32
+
+    @staticmethod
+    def backward(ctx, gout):
+        if ctx.state is None:
+            raise RuntimeError("ms_ssim: backward called twice (the saved pyramid is released after the first call)")
+        g = msssim_backward(ctx.state, gout)
+        ctx.state = None
+        return None, g.to(ctx.y_dtype), None
+
+
+def ms_ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """MS-SSIM of each image of ``y`` against the target ``x``: [B,C,H,W] CUDA tensors -> [B] float32, the mean over channels
+    of V = prod_l relu(m_l)^w_l (11-tap Gaussian, sigma 1.5, 5 scales, pytorch_msssim 0.2.1's published algorithm as restated
+    in oracle/msssim_oracle.py).  Differentiable in ``y`` only (the reconstruction); raises if ``x`` requires grad.  HIP
+    kernels of csrc/msssim.hip on the current stream, no host synchronisation, no atomics: forward and backward replay bit
+    for bit.
+
+    Contract at the relu: an (image, channel) plane with any level mean m_l <= 0 has value 0 and gradient exactly 0 —
+    pytorch_msssim's expression (relu(m)^w differentiated at the kink) can give NaN gradients there.
+
+    Raises ValueError for mismatched shapes, non-CUDA tensors or a smaller side <= 160, and VamError without a GPU: there
+    is no CPU fallback."""
+    L.require_gpu()
+    _msssim_check(x, y)
+    if x.requires_grad:
+        raise ValueError("ms_ssim is differentiable in its second argument (the reconstruction) only: x requires grad")
+    return _MsSsimFn.apply(x, y, float(data_range))

@@ -469,6 +469,36 @@ int vam_ssim_level(const float* x, const float* y, int planes, int H, int W, con
  * [planes][(H+2ph-2)/2+1][(W+2pw-2)/2+1]. */
 int vam_avgpool2(const float* x, float* out, int planes, int H, int W, int pad_h, int pad_w, void* stream);
 
+/* ------------------------------------------------------------------ differentiable MS-SSIM distortion */
+/* The training loss 1 - MS-SSIM: the function of oracle/msssim_oracle.py per plane = (image, channel), V = prod_l
+ * relu(m_l)^w_l, with the gradient with respect to y (the reconstruction).  Planes are contiguous HxW fp32 (NCHW); the
+ * smaller side must exceed 160.  Every launch goes to `stream`, nothing synchronises, and no reduction uses atomics: a
+ * replay gives the same bits.  A plane with any m_l <= 0 has V = 0 and gradient exactly 0 (pytorch_msssim's expression can give NaN there).
+ *
+ * Scratch: one double per forward workgroup, levels concatenated, [plane][tile] within a level.
+ * vam_msssim_partial_doubles: size of the scratch for `planes` HxW planes (0: too small an image);
+ * vam_msssim_partial_offset: first double of `level` (0..4) in it (-1: bad arguments). */
+long vam_msssim_partial_doubles(int planes, int H, int W);
+long vam_msssim_partial_offset(int planes, int H, int W, int level);
+/* One level's forward on its HxW planes: 11-tap window `win11` (device), cs map (last = 0) or ssim map (last = 1) summed
+ * per workgroup in double into partial[plane * tiles + tile] (partial = scratch + vam_msssim_partial_offset(level)). */
+int vam_msssim_fwd_level(const float* x, const float* y, int planes, int H, int W, const float* win11, float c1, float c2,
+                         int last, double* partial, void* stream);
+/* avg_pool2d(kernel 2, padding = size % 2, zeros counted) of x and y in one launch: outputs [planes][Ho][Wo] with
+ * Ho = (H + 2 (H % 2) - 2) / 2 + 1. */
+int vam_msssim_pool2(const float* x, const float* y, float* x_out, float* y_out, int planes, int H, int W, void* stream);
+/* From the scratch of the five levels of B images x C channels of H x W (level 0): means[l * B*C + plane] = m_l,
+ * dvdm[l * B*C + plane] = w_l V / m_l (0 for a plane with any m_l <= 0), val[b] = mean_c V (double), val32[b] the same
+ * in float.  Partials are summed in a fixed order. */
+int vam_msssim_combine(const double* partial, int B, int C, int H, int W, double* means, double* dvdm, double* val, float* val32,
+                       void* stream);
+/* One level's backward, coarse to fine: g[plane][H][W] = d(sum_b gout[b] * val[b]) / dy at this level's HxW planes,
+ * x and y this level's (pooled) planes, dvdm this level's row of vam_msssim_combine's output, gout [B] floats, g_coarse
+ * the gradient already computed at the next coarser level ([planes][Hc][Wc], NULL at the last level; gathered through
+ * the pool as g += g_coarse((iy + H % 2) / 2, (ix + W % 2) / 2) / 4). */
+int vam_msssim_bwd_level(const float* x, const float* y, int B, int C, int H, int W, const float* win11, float c1, float c2, int last,
+                         const double* dvdm, const float* gout, const float* g_coarse, float* g, void* stream);
+
 /* ------------------------------------------------------------------ REM fine-tune backward (configs[4]) */
 /* Weight (and bias) gradient of a stride-1, pad k/2 convolution (autograd's conv backward-weight for
  * layers/rem.py:40-49):  dw[n][c_off + c][ty][tx] = sum_p dy[p][n] * x[pix(p)+(ty-k/2, tx-k/2)][c]  in OIHW with
