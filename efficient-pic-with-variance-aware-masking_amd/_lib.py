@@ -43,6 +43,7 @@ VAM_MAX_TAIL_GROUP = 8
 VAM_MAX_LAYER_LEVELS = 32       # include/vampic.h: qualities of one vam_variance_layers launch
 VAM_RANS_MAX_THREADS = 16       # include/vampic.h: host threads of one vam_rans_*_streams call
 LAYER_NONE = 0xFF               # vam_variance_layers: the element is in no layer
+VAM_MAX_RANK_ELEMENTS = 1 << 18  # include/vampic.h: the largest segment vam_variance_rank sorts
 
 
 class VamRansStream(C.Structure):
@@ -235,6 +236,19 @@ _SIGNATURES = {
                                           C.c_int]),
     "vam_rans_decode_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_int]),
+    "vam_rans_decode_prefix_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_int, C.c_void_p]),
+    "vam_rans_prefix_bytes": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_variance_rank_workspace": (C.c_size_t, [C.c_int] * 4),
+    "vam_variance_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vam_rank_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vam_rank_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p]),
+    "vam_rank_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vam_graph_begin": (C.c_int, [C.c_void_p]),
     "vam_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "vam_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -123,6 +123,42 @@ def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = No
                                              coder_threads() if threads is None else int(threads)), "vam_rans_decode_streams")
 
 
+# ---------------------------------------------------------------- byte prefixes of a stream
+def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> List[int]:
+    """Tolerant decode of many stream PREFIXES in one vam_rans_decode_prefix_streams call.  ``jobs``: (the first L >= 0
+    bytes of a stream, the indexes of the whole stream, out); ``out`` is a writable C-contiguous int32 array of the indexes'
+    size.  Per job the number of leading symbols the bytes decode (written to out[:count]; the rest of ``out`` is left
+    untouched): L < 8 gives 0, a symbol whose renormalisation word or bypass nibbles are incomplete is not counted."""
+    keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
+    for k, j in enumerate(jobs):
+        src = np.frombuffer(j[0], dtype=np.uint8)
+        i, o = _i32(j[1]), j[2]
+        assert o.dtype == np.int32 and o.flags.c_contiguous and o.flags.writeable and o.size == i.size
+        keep.append((src, i))
+        arr[k] = L.VamRansStream(None, o.ctypes.data, i.ctypes.data, None, i.size, 0, 0, src.ctypes.data if src.size else None,
+                                 src.size, src.size)
+    counts = np.zeros(max(len(jobs), 1), dtype=np.int64)
+    L.check(L.load().vam_rans_decode_prefix_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                                    t.offsets.ctypes.data, t.cdf.shape[0],
+                                                    coder_threads() if threads is None else int(threads), counts.ctypes.data),
+            "vam_rans_decode_prefix_streams")
+    return [int(c) for c in counts[:len(jobs)]]
+
+
+def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables) -> List[int]:
+    """Per element count of the sorted list ``counts``: the smallest byte length (a multiple of 4) from which
+    :func:`decode_prefix_streams` yields at least that many symbols of ``stream`` (0 for a count of 0).  One decoding pass."""
+    src = np.frombuffer(stream, dtype=np.uint8)
+    i = _i32(indexes)
+    want = np.ascontiguousarray([int(c) for c in counts], dtype=np.int64)
+    out = np.zeros(max(want.size, 1), dtype=np.int64)
+    L.check(L.load().vam_rans_prefix_bytes(src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size,
+                                           t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data, t.offsets.ctypes.data,
+                                           t.cdf.shape[0], want.ctypes.data if want.size else None, want.size, out.ctypes.data),
+            "vam_rans_prefix_bytes")
+    return [int(b) for b in out[:want.size]]
+
+
 # ---------------------------------------------------------------- coded-size pricing (DESIGN section 9i)
 LOG2E = 1.4426950408889634
 MAX_BYPASS = 8            # raw nibbles of one out-of-range value (a 32-bit raw value; csrc/rans.cpp)

@@ -251,6 +251,87 @@ int decode_one(const uint8_t* in, long n_bytes, const int32_t* indexes, const ui
   return VAM_OK;
 }
 
+// Tolerant prefix decode (embedded streams).  The decoder reads the words of a stream front to back
+// and symbol i depends only on the words consumed up to it, so the first floor(n_bytes / 4) words of a stream decode its
+// leading symbols.  A symbol counts when its whole step fits the prefix: the table symbol, its renormalisation word and
+// every bypass nibble with theirs (what decode_one needs before it writes the symbol).  Returns the number of leading
+// symbols (< 0 on bad arguments); out (may be NULL) receives them, the rest of out is left untouched.  marks (may be
+// NULL): n_marks sorted symbol counts; mark_bytes[m] = the bytes consumed when marks[m] symbols were complete (0 for a
+// count of 0) = the shortest prefix, in whole words, that still decodes that many; marks the prefix does not reach stay
+// at -1.
+long decode_prefix_one(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                       const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out, const long* marks,
+                       int n_marks, long* mark_bytes) {
+  if ((!in && n_bytes > 0) || (!indexes && n > 0) || !cdfs || !cdf_sizes || !offsets || n < 0 || n_bytes < 0 || n_cdfs < 1 ||
+      n_marks < 0 || (n_marks > 0 && (!marks || !mark_bytes))) {
+    set_error("vam_rans_decode_prefix: bad arguments (prefix of %ld bytes)", n_bytes);
+    return VAM_EINVAL;
+  }
+  int m = 0;
+  for (int q = 0; q < n_marks; ++q) {
+    if (marks[q] < 0 || (q > 0 && marks[q] < marks[q - 1])) {
+      set_error("vam_rans_prefix_bytes: counts must be >= 0 and sorted, got %ld at %d", marks[q], q);
+      return VAM_EINVAL;
+    }
+    mark_bytes[q] = -1;
+  }
+  while (m < n_marks && marks[m] == 0) mark_bytes[m++] = 0;
+  if (n_bytes < 8) return 0;
+  std::vector<uint32_t> words((size_t)n_bytes / 4);
+  std::memcpy(words.data(), in, words.size() * 4);
+  const uint32_t* p = words.data();
+  const uint32_t* end = p + words.size();
+  uint64_t x = (uint64_t)p[0] | ((uint64_t)p[1] << 32);
+  p += 2;
+  long count = 0;
+  for (long i = 0; i < n; ++i) {
+    const int ci = indexes[i];
+    if (ci < 0 || ci >= n_cdfs) {
+      set_error("vam_rans_decode_prefix: index %d out of range at %ld", ci, i);
+      return VAM_EINVAL;
+    }
+    const int32_t* cdf = cdfs + (long)ci * cdf_stride;
+    const int sz = cdf_sizes[ci];
+    const int max_value = sz - 2;
+    if (max_value < 0 || max_value + 1 >= cdf_stride) {
+      set_error("vam_rans_decode_prefix: cdf size %d invalid for table %d", sz, ci);
+      return VAM_EINVAL;
+    }
+    const uint32_t cum = (uint32_t)(x & ((1u << kPrecision) - 1));
+    int s = 0;
+    while (s + 1 < sz && (uint32_t)cdf[s + 1] <= cum) ++s;
+    const uint32_t start = (uint32_t)cdf[s], freq = (uint32_t)(cdf[s + 1] - cdf[s]);
+    x = (uint64_t)freq * (x >> kPrecision) + cum - start;
+    if (x < kRansL) {
+      if (p >= end) break;
+      x = (x << 32) | *p++;
+    }
+    bool ok = true;
+    int32_t value = s;
+    if (value == max_value) {
+      int32_t val = (int32_t)dec_get_bits(x, p, end, kBypassBits, ok);
+      int32_t n_bypass = val;
+      while (ok && val == (int32_t)kMaxBypass) {
+        val = (int32_t)dec_get_bits(x, p, end, kBypassBits, ok);
+        n_bypass += val;
+      }
+      uint32_t raw = 0;
+      for (int j = 0; ok && j < n_bypass; ++j) {
+        const uint32_t nib = dec_get_bits(x, p, end, kBypassBits, ok);
+        if (j < 32 / kBypassBits) raw |= nib << (j * kBypassBits);
+      }
+      value = (int32_t)(raw >> 1);
+      if (raw & 1) value = -value - 1;
+      else value += max_value;
+    }
+    if (!ok) break;
+    if (out) out[i] = value + offsets[ci];
+    count = i + 1;
+    while (m < n_marks && marks[m] <= count) mark_bytes[m++] = (long)(p - words.data()) * 4;
+  }
+  return count;
+}
+
 // Runs job(i) for i in [0, n_jobs) on min(n_threads, n_jobs) threads (the caller's thread included).  Jobs write
 // disjoint memory.  The first failure (lowest job index) becomes this thread's vam_last_error.
 template <class F>
@@ -322,6 +403,38 @@ int vam_rans_decode_streams(vam_rans_stream* streams, int n_streams, const int32
     return decode_one(s.bytes, s.n_bytes, s.indexes, s.layer, s.sel, s.n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
                       s.symbols_out);
   });
+}
+
+int vam_rans_decode_prefix_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs, int cdf_stride,
+                                   const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int n_threads,
+                                   long* counts_out) {
+  if (n_streams > 0 && (!streams || !counts_out)) {
+    set_error("vam_rans_decode_prefix_streams: bad arguments");
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, "vam_rans_decode_prefix_streams", [&](int i) -> long {
+    const vam_rans_stream& s = streams[i];
+    if (s.layer) {
+      set_error("vam_rans_decode_prefix_streams: an embedded stream carries no layer selection");
+      return VAM_EINVAL;
+    }
+    return counts_out[i] = decode_prefix_one(s.bytes, s.n_bytes, s.indexes, s.n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                                             s.symbols_out, nullptr, 0, nullptr);
+  });
+}
+
+int vam_rans_prefix_bytes(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                          const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, const long* counts, int n_counts,
+                          long* bytes_out) {
+  const long got = decode_prefix_one(in, n_bytes, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, nullptr, counts,
+                                     n_counts, bytes_out);
+  if (got < 0) return (int)got;
+  for (int q = 0; q < n_counts; ++q)
+    if (bytes_out[q] < 0) {
+      set_error("vam_rans_prefix_bytes: %ld symbols asked for, the %ld bytes given decode %ld of %ld", counts[q], n_bytes, got, n);
+      return VAM_EINVAL;
+    }
+  return VAM_OK;
 }
 
 }  // extern "C"

@@ -363,6 +363,52 @@ def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float
     return rows
 
 
+def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float]):
+    """:func:`progressive_rd`'s printout for the embedded format (embedded.encode_batch / EmbeddedDecoder, DESIGN section
+    9m): images of one shape are padded and coded as one batch, ONCE and without a quality list of their own; the base and
+    then every quality of ``qualities`` (any values >= 0, marked or not) is decoded from the same streams.  Returns one
+    dict per level, the base first: q, bpp (8 * the bytes a receiver needs for that quality — z, the base and the shortest
+    prefix of every slice — / pixels of the ORIGINAL image), psnr (of the cropped decode), enc_s and dec_s (seconds per
+    image: the encode once, the decode of that level), each the mean over the images, plus "bpp_all" / "psnr_all"."""
+    from . import embedded as EB
+    images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
+    levels = [0.0] + [float(q) for q in qualities]
+    rows = [{"q": q, "bpp_all": [None] * len(images), "psnr_all": [None] * len(images), "enc_s": 0.0, "dec_s": 0.0}
+            for q in levels]
+    by_shape = {}
+    for i, x in enumerate(images):
+        by_shape.setdefault(tuple(x.shape[1:]), []).append(i)
+    with torch.no_grad():
+        for ids in by_shape.values():
+            xs = torch.cat([images[i] for i in ids], 0)
+            xp, unpad = pad_image(xs)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            containers = EB.encode_batch(model, xp)
+            t1 = time.perf_counter()
+            dec = EB.EmbeddedDecoder(model, containers)
+            for k, q in enumerate(levels):
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                out = dec.decode_qualities([q])[0]
+                torch.cuda.synchronize()
+                t3 = time.perf_counter()
+                x_hat = torch.nn.functional.pad(out["x_hat"], unpad)
+                bits = dec.bits(q)
+                rows[k]["enc_s"] += (t1 - t0)
+                rows[k]["dec_s"] += (t3 - t2) if k else (t3 - t1)       # the base includes the base and prefix decode
+                for n, i in enumerate(ids):
+                    x = images[i]
+                    rows[k]["bpp_all"][i] = bits[n] / (x.shape[0] * x.shape[2] * x.shape[3])
+                    rows[k]["psnr_all"][i] = compute_psnr(x, x_hat[n:n + 1])
+    for r in rows:
+        r["bpp"] = sum(r["bpp_all"]) / len(images)
+        r["psnr"] = sum(r["psnr_all"]) / len(images)
+        r["enc_s"] /= len(images)
+        r["dec_s"] /= len(images)
+    return rows
+
+
 def valid_epoch(epoch: int, test_dataloader: Iterable[torch.Tensor], criterion, model, pr_list: Sequence[float] = (0.05,),
                 rems: Optional[Sequence[float]] = None):
     """training/step.py:136-202 (without wandb): mean criterion loss over batches x qualities — what drives the

@@ -22,7 +22,7 @@ from . import _lib as L
 from . import layers as Ly
 from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, get_scale_table
-from .plans import _DecPlan, _FsqPlan, _FsqTrainFn, _FullTrainFn, _ProgDecPlan, _SweepPlan, _version_sig
+from .plans import _DecPlan, _EmbDecPlan, _FsqPlan, _FsqTrainFn, _FullTrainFn, _ProgDecPlan, _SweepPlan, _version_sig
 
 
 # ----------------------------------------------------------------------------- builders
@@ -691,6 +691,13 @@ class VarianceMaskingPIC(CompressionModel):
         dev = self.entropy_bottleneck.quantiles.device
         return self._cached_plan(self._dec_plans, ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev)),
                                  lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev), self._weights_sig())
+
+    def _emb_dec_plan(self, B, hz, wz) -> "_EmbDecPlan":
+        """The plans of embedded.EmbeddedDecoder for one (B, z-shape), cached beside decompress's: the cuts are graph
+        inputs, so no quality list is part of the key."""
+        dev = self.entropy_bottleneck.quantiles.device
+        return self._cached_plan(self._dec_plans, ("emb", B, hz, wz, str(dev)),
+                                 lambda: _EmbDecPlan(self, B, hz, wz, dev), self._weights_sig())
 
 
 class VarianceMaskingPICREM(VarianceMaskingPIC):

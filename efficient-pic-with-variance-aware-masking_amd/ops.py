@@ -634,6 +634,81 @@ def variance_mask_map(sigma: View, table_dev: torch.Tensor, level_map: torch.Ten
             "vam_variance_mask_map")
 
 
+# --------------------------------------------------------------------------- rank order (embedded streams)
+def rank_workspace(sigma: View, n_slice: int, device=None) -> Optional[torch.Tensor]:
+    """The workspace :func:`variance_rank` needs for the segments of ``sigma`` (None when they fit LDS).  Raises for
+    segments above L.VAM_MAX_RANK_ELEMENTS elements."""
+    slice_C = sigma.C // n_slice
+    n = L.load().vam_variance_rank_workspace(sigma.B, n_slice, sigma.H * sigma.W, slice_C)
+    if sigma.H * sigma.W * slice_C > L.VAM_MAX_RANK_ELEMENTS:
+        raise ValueError(f"rank order: segments of {sigma.H * sigma.W * slice_C} elements exceed {L.VAM_MAX_RANK_ELEMENTS}")
+    return torch.empty((n // 8,), dtype=torch.int64, device=device or sigma.buf.device) if n else None
+
+
+def variance_rank(sigma: View, perm: torch.Tensor, n_slice: int = 1, workspace: Optional[torch.Tensor] = None):
+    """``perm`` int32 [B, n_slice, n] (n = slice_C * H * W) gets, per (image, slice) segment of ``sigma``, the permutation
+    that sorts it by descending sigma: numpy.argsort(-s, kind="stable") with s flattened in the canonical [C, H, W] order
+    of a stream.  ``workspace``: :func:`rank_workspace` (segments above 8192 elements).  No allocation: capturable."""
+    slice_C = sigma.C // n_slice
+    hw = sigma.H * sigma.W
+    assert slice_C * n_slice == sigma.C
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == sigma.B * n_slice * hw * slice_C
+    assert workspace is None or (workspace.dtype == torch.int64 and workspace.is_contiguous())
+    L.check(L.load().vam_variance_rank(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, perm.data_ptr(),
+                                       workspace.data_ptr() if workspace is not None else None,
+                                       8 * workspace.numel() if workspace is not None else 0, stream_ptr()), "vam_variance_rank")
+
+
+def _rank_view(v: "IView", n_slice: int, slice_C: int):
+    assert v.buf.dtype == torch.int32 and v.buf.is_contiguous() and v.C == n_slice * slice_C, (v.C, n_slice, slice_C)
+    return v.ptr, v.ld
+
+
+def rank_gather(perm: torch.Tensor, n_slice: int, a: "IView", out_a: torch.Tensor, b: Optional["IView"] = None,
+                out_b: Optional[torch.Tensor] = None):
+    """out[b, j, r] = view[b, y, x, j * C + c] for the element perm[b, j, r] = c * H * W + y * W + x: one or two int32 views
+    (symbols and table indexes) into rank order in one launch."""
+    B, H, W = a.buf.shape[:3]
+    slice_C = a.C // n_slice
+    n = H * W * slice_C
+    for o in (out_a, out_b):
+        assert o is None or (o.dtype == torch.int32 and o.is_contiguous() and o.numel() == B * n_slice * n)
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == B * n_slice * n
+    assert (b is None) == (out_b is None) and (b is None or tuple(b.buf.shape[:3]) == (B, H, W))
+    pa, la = _rank_view(a, n_slice, slice_C)
+    pb, lb = _rank_view(b, n_slice, slice_C) if b is not None else (None, 0)
+    L.check(L.load().vam_rank_gather(pa, la, pb, lb, perm.data_ptr(), B, n_slice, H * W, slice_C, out_a.data_ptr(),
+                                     out_b.data_ptr() if out_b is not None else None, stream_ptr()), "vam_rank_gather")
+
+
+def rank_counts(layer: torch.Tensor, perm: torch.Tensor, n_slice: int, n_levels: int, count: torch.Tensor):
+    """count int32 [n_levels, B, n_slice] = #(layer id <= g) per segment, for the uint8 ids of :func:`variance_layers`
+    ([B, H, W, n_slice * C]): how long a prefix of the rank order quality g keeps."""
+    B, H, W, Ct = layer.shape
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and Ct % n_slice == 0
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == B * H * W * Ct
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= n_levels * B * n_slice
+    L.check(L.load().vam_rank_counts(layer.data_ptr(), Ct, perm.data_ptr(), B, n_slice, H * W, Ct // n_slice, n_levels,
+                                     count.data_ptr(), stream_ptr()), "vam_rank_counts")
+
+
+def rank_scatter(ranked: torch.Tensor, perm: torch.Tensor, count: torch.Tensor, n_levels: int, n_slice: int, sym: "IView",
+                 level_id: torch.Tensor):
+    """The inverse of :func:`rank_gather` for a decoder: ``sym`` gets ranked[r] at the element perm[r] where
+    r < count[n_levels - 1] (0 elsewhere), ``level_id`` uint8 [B, H, W, n_slice * C] the smallest g with r < count[g]
+    (L.LAYER_NONE if none).  ``count`` int32 [n_levels, B, n_slice] on the device, non-decreasing in g."""
+    B, H, W = sym.buf.shape[:3]
+    slice_C = sym.C // n_slice
+    n = H * W * slice_C
+    ps, ls = _rank_view(sym, n_slice, slice_C)
+    assert ranked.dtype == torch.int32 and ranked.is_contiguous() and ranked.numel() == B * n_slice * n
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == B * n_slice * n
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == n_levels * B * n_slice and count.is_cuda
+    assert level_id.dtype == torch.uint8 and level_id.is_contiguous() and tuple(level_id.shape) == (B, H, W, sym.C)
+    L.check(L.load().vam_rank_scatter(ranked.data_ptr(), perm.data_ptr(), count.data_ptr(), n_levels, B, n_slice, H * W, slice_C,
+                                      ps, ls, level_id.data_ptr(), sym.C, stream_ptr()), "vam_rank_scatter")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

@@ -1,6 +1,6 @@
 """The plans that lower the models of ``models.py`` to libvampic launches — ``forward_single_quality`` (:class:`_FsqPlan`), the
 quality sweeps with their rate and coded-size tails (:class:`_SweepPlan`), ``decompress`` (:class:`_DecPlan`), the progressive
-container decoder (:class:`_ProgDecPlan`) — and the autograd functions of the training plans.  A plan takes the model as an
+container decoder (:class:`_ProgDecPlan`), the embedded-stream decoder (:class:`_EmbDecPlan`) — and the autograd functions of the training plans.  A plan takes the model as an
 argument; nothing here imports ``models``.  How a slice is lowered is written once, in :class:`_SliceChain`: encoder, sweep
 and decoder have to agree on it bit for bit, or a bitstream does not decode (models/pic.py:497-967, rem_pic.py:229-818).
 """
@@ -1135,3 +1135,68 @@ class _ProgDecPlan(_DecPlan):
         super().close()
         for t in self.tails.values():
             t.close()
+
+
+class _EmbDecPlan(_ProgDecPlan):
+    """embedded.EmbeddedDecoder for one (B, z-shape) (all_scalable): _ProgDecPlan with the rank order
+    of the chain's sigma (vam_variance_rank) where the parent assigns container layers, and the unmasked table indexes in
+    that order for the host's prefix decode.  It owns ``perm``, the ranked symbols, one count table per group size and the
+    layer-id buffer that turns a caller's qualities into counts on the device (vam_variance_layers on the same sigma, then
+    vam_rank_counts: count = #(layer id <= k) per segment).  A tail is vam_rank_scatter — the ranked symbols below each
+    level's count back to the NHWC view, with the level ids in ``layer`` — and then the parent's _SweepTail in decode mode
+    with the fixed cut-offs 0 .. G-1.  The count table is a graph input, copied before the replay on the runner's stream
+    and outside any capture, so the plan keeps ONE hipGraph per group size whatever the cuts."""
+
+    def __init__(self, m, B, hz, wz, device):
+        super().__init__(m, B, hz, wz, (), device)
+        self.counts: Dict[int, torch.Tensor] = {}          # group size -> int32 [G, B, ns], the tails' graph input
+
+    def _lower_progressive(self):
+        m, sc, B, h, w, device = self.m, self.sc, self.B, self.h, self.w, self.device
+        d, ns, mu_p, std_p = m.division_dimension[0], m.ns0, sc.mu_p, sc.std_p
+        n = m.dim_chunk * h * w
+        E.lower_g_s(self.p_syn, [m.g_s[0] if m.multiple_decoder else m.g_s], [sc.yb], [self.x_hat])       # level 0
+        P = self.p_chain = E.Plan(device)
+        sc.lower_param_chain(P)
+        self.layer = torch.full((B, h, w, d), L.LAYER_NONE, dtype=torch.uint8, device=device)    # the tails' level ids
+        self.qlayer = torch.empty((B, h, w, d), dtype=torch.uint8, device=device)                # a quality list's layers
+        self.idx_l, self.sym = ops.new_iview(B, h, w, d, device), ops.new_iview(B, h, w, d, device)
+        self.perm = torch.empty((B, ns, n), dtype=torch.int32, device=device)
+        self.ranked = torch.zeros((B, ns, n), dtype=torch.int32, device=device)                  # decoded symbols, rank order
+        self.idx_r = torch.empty((B, ns, n), dtype=torch.int32, device=device)                   # table indexes, rank order
+        self.rank_ws = ops.rank_workspace(std_p, ns, device)
+        P.keep += [self.layer, self.qlayer, self.idx_l.buf, self.sym.buf, self.perm, self.ranked, self.idx_r, self.rank_ws]
+        P.call(lambda: ops.variance_rank(std_p, self.perm, n_slice=ns, workspace=self.rank_ws), "rank order")
+        P.call(lambda: ops.build_indexes(std_p, m.gaussian_conditional.scale_table, out=self.idx_l))   # functions_decode.py:179-180
+        P.call(lambda: ops.rank_gather(self.perm, ns, self.idx_l, self.idx_r), "indexes in rank order")
+        self.sweep_parts = dict(heads=sc.heads, yb=sc.yb, mu=mu_p, std=std_p, mu_tot=sc.mu_tot, sym=self.sym, layer=self.layer,
+                                g_s=m.g_s[1] if m.multiple_decoder else m.g_s)
+
+    def quality_counts(self, qs: Sequence[float]) -> torch.Tensor:
+        """int32 [len(qs), B, ns] on the device: how many leading elements of every segment's rank order the mask of each
+        quality of the non-decreasing list ``qs`` (up to L.VAM_MAX_LAYER_LEVELS) keeps, from the decoder's own sigma."""
+        ns = self.m.ns0
+        count = torch.empty((len(qs), self.B, ns), dtype=torch.int32, device=self.device)
+        with self.runner.on_stream():
+            ops.variance_layers(self.sc.std_p, [float(q) for q in qs], self.qlayer, n_slice=ns)
+            ops.rank_counts(self.qlayer, self.perm, ns, len(qs), count)
+        return count
+
+    def tail_counts(self, count, use_graph: bool) -> _SweepTail:
+        """The tail of G = count.shape[0] levels, level g keeping the first count[g, b, j] ranked elements of every segment
+        (int32 [G, B, ns], host or device, non-decreasing in g)."""
+        G = int(count.shape[0])
+        t = self.tails.get(G)
+        if t is None:
+            t = self.tails[G] = _SweepTail(self, G, decode=True)
+            t.ks = tuple(range(G))
+            self.counts[G] = torch.zeros((G, self.B, self.m.ns0), dtype=torch.int32, device=self.device)
+        table = self.counts[G]
+
+        def run():
+            ops.rank_scatter(self.ranked, self.perm, table, G, self.m.ns0, self.sym, self.layer)
+            t.plan.run()
+        with self.runner.on_stream():
+            table.copy_(torch.as_tensor(count, dtype=torch.int32).reshape(table.shape))
+            t.runner.replay(("counts",), run, use_graph)
+        return t

@@ -335,6 +335,36 @@ int vam_variance_mask_map(const float* sigma, int ld, long batch_stride, long sl
                           long map_batch_stride, float* mask_out, int ld_mask, long mask_batch_stride,
                           long mask_slice_stride, float* thr_out, void* stream);
 
+/* ------------------------------------------------------------------ rank order (embedded streams) */
+/* Embedded streams (vampic.embedded).  A segment is one (image, slice) of the NHWC window that
+ * vam_variance_layers reads (segment s = b*n_slice + j at sigma + b*batch_stride + j*slice_stride, n = n_pix * C elements,
+ * element (p, c) at p*ld + c); its elements carry the canonical index e = c * n_pix + p, the [C, h, w] order of a stream.
+ * vam_variance_rank writes perm_out[s][0 .. n) (int32), the permutation that sorts the segment by descending sigma:
+ *   perm[s] == numpy.argsort(-sigma_s, kind="stable")   with sigma_s flattened in canonical order,
+ * i.e. equal values by ascending e, -0.0 == +0.0, +inf first, NaN last (the NaNs again by e).  The variance mask of every
+ * quality is a prefix of this order.  Segments of up to 8192 elements are sorted in LDS in one launch; larger ones (up to
+ * 2^18 elements, anything above is VAM_EINVAL and launches nothing) in several passes through `workspace`, whose size
+ * vam_variance_rank_workspace gives (0 when none is needed).  No allocation, no atomics: the call can be captured. */
+size_t vam_variance_rank_workspace(int n_batch, int n_slice, int n_pix, int C);
+int vam_variance_rank(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice, int n_pix,
+                      int C, int32_t* perm_out, void* workspace, size_t workspace_bytes, void* stream);
+/* out[s][r] = in[b, p, j*C + c] for e = c * n_pix + p = perm[s][r]: one or two contiguous int32 NHWC views (pixel strides
+ * ld0 / ld1 >= n_slice * C, n_batch * n_pix pixels; in1 / out1 may be NULL) into rank order in one launch. */
+int vam_rank_gather(const int32_t* in0, int ld0, const int32_t* in1, int ld1, const int32_t* perm, int n_batch, int n_slice,
+                    int n_pix, int C, int32_t* out0, int32_t* out1, void* stream);
+/* count_out[g][s] = #(layer id <= g) of segment s for the uint8 ids of vam_variance_layers (pixel stride ld_layer) and
+ * g < n_levels <= VAM_MAX_LAYER_LEVELS: the length of the prefix of perm[s] that quality g's mask keeps.  The ids never
+ * decrease along the rank order, so this is one binary search per (segment, level). */
+int vam_rank_counts(const uint8_t* layer, int ld_layer, const int32_t* perm, int n_batch, int n_slice, int n_pix, int C,
+                    int n_levels, int32_t* count_out, void* stream);
+/* The decoder's inverse: ranked[s][r] int32, perm, and a device table count[g][s] (int32, non-decreasing in g,
+ * 1 <= n_levels <= VAM_MAX_MASK_LEVELS).  For e = perm[s][r]:  sym_out[e] = ranked[r] if r < count[n_levels-1][s] else 0,
+ * id_out[e] (uint8) = the smallest g with r < count[g][s], 0xFF if there is none, both in the NHWC layout of the views
+ * above: what vam_gauss_levels_decode reads with ks = 0 .. n_levels-1.  The table is read on the device, so one captured
+ * launch serves every cut. */
+int vam_rank_scatter(const int32_t* ranked, const int32_t* perm, const int32_t* count, int n_levels, int n_batch, int n_slice,
+                     int n_pix, int C, int32_t* sym_out, int ld_sym, uint8_t* id_out, int ld_id, void* stream);
+
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
  *  base  (mask == NULL):  v = round(y-mu);           lik = L(|(v+mu)-mu|, sigma);        yhat = v+mu
@@ -691,6 +721,23 @@ int vam_rans_encode_streams(vam_rans_stream* streams, int n_streams, const int32
                             const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int n_threads);
 int vam_rans_decode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
                             const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int n_threads);
+
+/* Embedded streams (vampic.embedded): a stream is decodable from any byte prefix, because the decoder
+ * reads its words front to back and symbol i depends only on the words consumed up to it.
+ * vam_rans_decode_prefix_streams: per stream (bytes = the first n_bytes >= 0 bytes of a stream of n symbols, any length;
+ * layer must be NULL) decode as many leading symbols as the floor(n_bytes / 4) whole words allow, write them to
+ * symbols_out[0 .. count) (the rest is left untouched; symbols_out may be NULL) and the count to counts_out[i].  Fewer
+ * than 8 bytes give 0; a symbol whose renormalisation word or bypass nibbles are incomplete is not counted.  Threaded as
+ * vam_rans_decode_streams.
+ * vam_rans_prefix_bytes: for n_counts sorted symbol counts, bytes_out[q] = the smallest byte length (a multiple of 4)
+ * from which the tolerant decoder yields at least counts[q] symbols (0 for a count of 0): one decoding pass that notes
+ * the read pointer.  A count the given bytes do not reach is VAM_EINVAL. */
+int vam_rans_decode_prefix_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
+                                   const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int n_threads,
+                                   long* counts_out);
+int vam_rans_prefix_bytes(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                          int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                          const long* counts, int n_counts, long* bytes_out);
 
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);

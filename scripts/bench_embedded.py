@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Embedded streams (embedded.encode_batch / EmbeddedDecoder) against the layered container
+(progressive.encode_batch / ProgressiveDecoder, section 9g) on one GPU, same model, same inputs, hipGraph on, at section
+9g's two inputs.  Each case is warmed, then the two formats alternate (layered, embedded, layered, ...), each phase timed
+from a device synchronisation to the next; medians are reported.  "encode" is the container of every image, "decode" the
+base and every quality of the list for every image.  The host coder's share of each phase (the bitstream calls, wall time
+on the calling thread) is reported beside it, and the bytes per image: the embedded streams at full length against the
+layered container's progressive streams.  x_hat of every level must be identical between the two formats (asserted); no
+time is asserted.  Prints one JSON line.
+
+    python scripts/bench_embedded.py [--warmup 1] [--reps 3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+DEMO_Q = [0.01, 0.05, 0.1, 0.25, 0.5, 0.6, 0.7, 0.8, 0.9, 1, 2, 3, 4, 4.5, 10]       # reference test/parser.py:20
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    from bench import build_model
+    import vampic
+    from vampic import bitstream as bs, embedded as EB, progressive as P
+    dev = torch.device("cuda:0")
+    net, _ = build_model(dev)
+    net.update()
+    coder = [0.0]
+
+    def timed(fn):
+        def run(*args, **kw):
+            t0 = time.perf_counter()
+            try:
+                return fn(*args, **kw)
+            finally:
+                coder[0] += time.perf_counter() - t0
+        return run
+    for name in ("encode", "decode", "encode_streams", "decode_streams", "decode_prefix_streams"):
+        setattr(bs, name, timed(getattr(bs, name)))
+    EB._map_threads = timed(EB._map_threads)     # prefix_bytes runs on worker threads: timed around the map
+
+    def layered_enc(x, qs):
+        return P.encode_batch(net, x, qs)[0]
+
+    def layered_dec(cs, qs):
+        return [o["x_hat"] for o in P.ProgressiveDecoder(net, cs).decode_levels(list(range(len(qs) + 1)))]
+
+    def embedded_enc(x, qs):
+        return EB.encode_batch(net, x, qs)
+
+    def embedded_dec(cs, qs):
+        return [o["x_hat"] for o in EB.EmbeddedDecoder(net, cs).decode_qualities([0.0] + list(qs))]
+
+    res = {"metric": "embedded streams vs layered container (ms, median)", "device": torch.cuda.get_device_name(0),
+           "coder_threads": bs.coder_threads(), "warmup": a.warmup, "reps": a.reps, "cases": {}}
+    for case, B, H, W, qs in (("1x512x768/15", 1, 512, 768, DEMO_Q), ("8x256x256/14", 8, 256, 256, P.Q_LIST)):
+        x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
+        paths = {"layered": (layered_enc, layered_dec), "embedded": (embedded_enc, embedded_dec)}
+        t = {f"{p}_{ph}": [] for p in paths for ph in ("enc", "enc_coder", "dec", "dec_coder")}
+        size = {}
+        with torch.no_grad():
+            for rep in range(a.warmup + a.reps):
+                last = {}
+                for p, (enc, dec) in paths.items():
+                    torch.cuda.synchronize()
+                    coder[0] = 0.0
+                    t0 = time.perf_counter()
+                    cs = enc(x, qs)
+                    torch.cuda.synchronize()
+                    t1, c1 = time.perf_counter(), coder[0]
+                    coder[0] = 0.0
+                    last[p] = dec(cs, qs)
+                    torch.cuda.synchronize()
+                    t2, c2 = time.perf_counter(), coder[0]
+                    if rep >= a.warmup:
+                        for k, v in (("enc", t1 - t0), ("enc_coder", c1), ("dec", t2 - t1), ("dec_coder", c2)):
+                            t[f"{p}_{k}"].append(1e3 * v)
+                    if p == "layered":
+                        size[p] = sum(len(s) for c in cs for layer in c["progressive"] for s in layer) / B
+                    else:
+                        size[p] = sum(len(s) for c in cs for s in c["embedded"]) / B
+                for k, (u, v) in enumerate(zip(last["layered"], last["embedded"])):
+                    assert torch.equal(u, v), f"{case}: x_hat of level {k} differs between the formats"
+        med = {k: round(statistics.median(v), 1) for k, v in t.items()}
+        med.update(levels=len(qs), encode_ratio=round(med["embedded_enc"] / med["layered_enc"], 3),
+                   decode_ratio=round(med["embedded_dec"] / med["layered_dec"], 3), x_hat_identical=True,
+                   layered_progressive_bytes_per_image=round(size["layered"], 1),
+                   embedded_bytes_per_image=round(size["embedded"], 1),
+                   bytes_ratio=round(size["embedded"] / size["layered"], 4))
+        res["cases"][case] = med
+        net._drop_plans()
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
