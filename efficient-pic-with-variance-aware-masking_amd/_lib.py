@@ -64,6 +64,12 @@ class VamCoderTables(C.Structure):
     _fields_ = [("cost", C.c_void_p), ("sizes", C.c_void_p), ("offsets", C.c_void_p), ("n_cdfs", C.c_int32), ("stride", C.c_int32)]
 
 
+class VamRansTables(C.Structure):
+    """vam_rans_tables: the coder's tables on the device for the device coder (bitstream.DeviceCoderTables)."""
+    _fields_ = [("cdf", C.c_void_p), ("sizes", C.c_void_p), ("offsets", C.c_void_p), ("n_cdfs", C.c_int32), ("stride", C.c_int32),
+                ("packed", C.c_void_p), ("packed_start", C.c_void_p), ("packed_entries", C.c_int32), ("pad_", C.c_int32)]
+
+
 class VamWgrad(C.Structure):
     _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
                 ("ld_x", C.c_int), ("ld_dy", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -240,6 +246,19 @@ _SIGNATURES = {
                                                  C.c_int, C.c_int, C.c_void_p]),
     "vam_rans_prefix_bytes": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_rans_core_encode": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_long, C.c_void_p, C.c_int]),
+    "vam_rans_core_decode": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_int]),
+    "vam_rans_core_encode_nhwc": (C.c_long, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_long]),
+    "vam_rans_core_decode_nhwc": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_rans_lds_table_bytes": (C.c_int, []),
+    "vam_rans_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.POINTER(VamRansTables), C.c_void_p,
+                                         C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vam_rans_pack_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),
+    "vam_rans_decode_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.POINTER(VamRansTables), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_variance_rank_workspace": (C.c_size_t, [C.c_int] * 4),
     "vam_variance_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -259,6 +259,197 @@ class DeviceTables:
         return d
 
 
+# ---------------------------------------------------------------- the coder on the device
+STATUS_TEXT = {1: "bitstream truncated", 2: "index out of range", 3: "cdf size invalid for its table",
+               4: "output buffer too small", 5: "zero-frequency symbol (cdf table not normalised)",
+               6: "bad arguments (a stream is at least 8 bytes, in whole words)"}
+
+
+def pack_tables(t: Tables):
+    """The tables ragged as 16-bit values for the decoder's LDS copy: table k is its entries 0 .. sizes[k]-2 at starts[k],
+    the terminal 65536 implied; the total is padded to a multiple of 8 entries (16-byte loads).  None when a table does
+    not start at 0, increase strictly and end at 65536 within its row: the decoder then reads the int32 tables."""
+    sizes = t.sizes.astype(np.int64)
+    if (sizes < 2).any() or (sizes > t.cdf.shape[1]).any():
+        return None
+    rows = [t.cdf[k, :sizes[k]].astype(np.int64) for k in range(t.cdf.shape[0])]
+    if any(r[0] != 0 or r[-1] != 65536 or (np.diff(r) <= 0).any() for r in rows):
+        return None
+    starts = np.concatenate([[0], np.cumsum(sizes - 1)]).astype(np.int64)
+    packed = np.zeros((int(starts[-1]) + 7) // 8 * 8, dtype=np.uint16)
+    for k, r in enumerate(rows):
+        packed[starts[k]:starts[k + 1]] = r[:-1]
+    return packed, starts[:-1].astype(np.int32)
+
+
+@dataclass
+class DeviceCoderTables:
+    """The device coder's companion of :class:`Tables`, next to :class:`DeviceTables` and keyed like it: the int32 CDFs,
+    sizes and offsets on the device (the encoder's look-ups, the decoder's fallback) and the packed 16-bit form with
+    per-table start offsets, kept when it fits the LDS a workgroup may use (``lds_bytes`` of ``lds_limit``)."""
+    host: Tables
+    cdf: torch.Tensor
+    sizes: torch.Tensor
+    offsets: torch.Tensor
+    packed: Optional[torch.Tensor]     # int16 storage of the uint16 values
+    starts: Optional[torch.Tensor]
+    lds_bytes: int                     # the packed tables' size (0: not packable)
+    lds_limit: int
+    struct: "L.VamRansTables"
+    key: tuple = ()
+
+    def __deepcopy__(self, memo):
+        return None           # device pointers of THIS model: a copied model builds its own at its first use
+
+    @staticmethod
+    def build(t: Tables, device, key=()) -> "DeviceCoderTables":
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        with torch.cuda.device(device):
+            limit = L.load().vam_rans_lds_table_bytes()
+        if limit < 0:
+            L.check(limit, "vam_rans_lds_table_bytes")
+        pk = pack_tables(t)
+        lds = 2 * pk[0].size if pk is not None else 0
+        fits = pk is not None and lds <= limit
+        d = DeviceCoderTables(t, dev(t.cdf), dev(t.sizes), dev(t.offsets), dev(pk[0].view(np.int16)) if fits else None,
+                              dev(pk[1]) if fits else None, lds, limit, None, key)
+        d.struct = L.VamRansTables(d.cdf.data_ptr(), d.sizes.data_ptr(), d.offsets.data_ptr(), t.cdf.shape[0], t.cdf.shape[1],
+                                   d.packed.data_ptr() if fits else None, d.starts.data_ptr() if fits else None,
+                                   pk[0].size if fits else 0, 0)
+        return d
+
+    @staticmethod
+    def of(model, device) -> "DeviceCoderTables":
+        t = Tables.of(model)
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (model._tables_key, str(device))
+        d = getattr(model, "_device_coder_tables", None)
+        if d is None or d.key != key:
+            d = DeviceCoderTables.build(t, device, key)
+            object.__setattr__(model, "_device_coder_tables", d)
+        return d
+
+
+def _geometry(sym_view, idx_view, n_slices: int, C_: int, layer):
+    buf = sym_view.buf
+    B, h, w, ld = (int(v) for v in buf.shape)
+    if buf.dtype != torch.int32 or not buf.is_contiguous() or sym_view.c0 + n_slices * C_ > ld:
+        raise ValueError(f"device coder: symbols are a contiguous int32 [B,h,w,ld] buffer holding {n_slices} x {C_} channels from {sym_view.c0}")
+    if idx_view is not None and (idx_view.buf.dtype != torch.int32 or tuple(idx_view.buf.shape) != tuple(buf.shape)
+                                 or idx_view.c0 != sym_view.c0 or not idx_view.buf.is_contiguous()):
+        raise ValueError("device coder: the index window must have the geometry of the symbol window")
+    if layer is not None and (layer.dtype != torch.uint8 or tuple(layer.shape) != tuple(buf.shape) or not layer.is_contiguous()):
+        raise ValueError("device coder: the layer ids must be a uint8 buffer of the symbols' shape")
+    return B, h, w, ld
+
+
+def raise_status(status: np.ndarray, B: int, what: str):
+    """VamError for the first stream with a non-zero status; stream id = slice * B + image."""
+    bad = np.flatnonzero(status)
+    if bad.size:
+        k, st = int(bad[0]), int(status[bad[0]])
+        raise L.VamError(f"{what}: stream (image {k % B}, slice {k // B}): {STATUS_TEXT.get(st, f'status {st}')}"
+                         + (f" ({bad.size} streams failed)" if bad.size > 1 else ""))
+
+
+def encode_streams_device(sym_view, idx_view, n_slices: int, C_: int, tables: DeviceCoderTables, layer=None,
+                          sel: int = 0) -> List[List[bytes]]:
+    """All B * n_slices streams of an int32 NHWC window in one vam_rans_encode_device launch on the current stream, packed by
+    vam_rans_pack_device, then two device-to-host copies: the lengths with the status codes, and the coded bytes.
+    ``idx_view`` None: table index = channel (the z streams).  Returns ``[slice][image]``; each stream's bytes equal
+    :func:`encode`'s on the window's [C, h, w] transpose."""
+    from . import ops
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
+    ns, cap = B * n_slices, 2 * C_ * h * w + 16            # 8 n + 64 bytes per stream, the host coder's budget
+    dev = sym_view.buf.device
+    regions = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    packed = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    meta = torch.empty((2, ns), dtype=torch.int32, device=dev)          # lengths in words, status
+    offs = torch.empty(ns + 1, dtype=torch.int64, device=dev)
+    lib, st = L.load(), ops.stream_ptr()
+    L.check(lib.vam_rans_encode_device(sym_view.buf.data_ptr(), idx_view.buf.data_ptr() if idx_view is not None else None,
+                                       layer.data_ptr() if layer is not None else None, int(sel), B, h, w, ld, sym_view.c0, C_,
+                                       n_slices, C.byref(tables.struct), regions.data_ptr(), cap, meta[0].data_ptr(),
+                                       meta[1].data_ptr(), st), "vam_rans_encode_device")
+    L.check(lib.vam_rans_pack_device(regions.data_ptr(), cap, meta[0].data_ptr(), ns, packed.data_ptr(), ns * cap,
+                                     offs.data_ptr(), st), "vam_rans_pack_device")
+    m = meta.cpu().numpy()
+    raise_status(m[1], B, "vam_rans_encode_device")
+    off = np.concatenate([[0], np.cumsum(m[0].astype(np.int64))]) * 4
+    data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
+    return [[data[off[s * B + b]:off[s * B + b + 1]].tobytes() for b in range(B)] for s in range(n_slices)]
+
+
+@dataclass
+class DeviceStreams:
+    """Byte strings on the device: one uint8 buffer [offsets int64 | lengths int32 | the strings, each at a multiple of 4],
+    uploaded in one host-to-device copy; ``status`` receives one code per string."""
+    buf: torch.Tensor
+    n: int
+    status: torch.Tensor       # int32 [n]
+
+    @property
+    def offsets_ptr(self): return self.buf.data_ptr()
+    @property
+    def lengths_ptr(self): return self.buf.data_ptr() + 8 * self.n
+    @property
+    def bytes_ptr(self): return self.buf.data_ptr() + 8 * self.n + 4 * (self.n + self.n % 2)
+
+
+def upload_streams(strings: Sequence[bytes], device) -> DeviceStreams:
+    n = len(strings)
+    lens = np.array([len(s_) for s_ in strings], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
+    head = 8 * n + 4 * (n + n % 2)
+    host = np.zeros(head + int(off[-1]) + 4, dtype=np.uint8)
+    host[:8 * n].view(np.int64)[:] = off[:-1]
+    host[8 * n:8 * n + 4 * n].view(np.int32)[:] = lens
+    for k, s_ in enumerate(strings):
+        host[head + off[k]:head + off[k] + lens[k]] = np.frombuffer(s_, dtype=np.uint8)
+    return DeviceStreams(torch.from_numpy(host).to(device), n, torch.zeros(max(n, 1), dtype=torch.int32, device=device))
+
+
+def decode_uploaded(up: DeviceStreams, first: int, idx_view, sym_view, n_slices: int, C_: int, tables: DeviceCoderTables,
+                    layer=None, sel: int = 0):
+    """One vam_rans_decode_device launch on the current stream: the B * n_slices strings of ``up`` from ``first`` on
+    (string first + slice * B + image) into the window of ``sym_view``.  No synchronisation."""
+    from . import ops
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
+    if first < 0 or first + B * n_slices > up.n:
+        raise ValueError(f"device coder: strings {first} .. {first + B * n_slices} of {up.n} uploaded")
+    L.check(L.load().vam_rans_decode_device(up.bytes_ptr, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                            idx_view.buf.data_ptr() if idx_view is not None else None,
+                                            layer.data_ptr() if layer is not None else None, int(sel), B, h, w, ld, sym_view.c0, C_,
+                                            n_slices, C.byref(tables.struct), sym_view.buf.data_ptr(),
+                                            up.status.data_ptr() + 4 * first, ops.stream_ptr()), "vam_rans_decode_device")
+
+
+def decode_streams_device(strings: Sequence[Sequence[bytes]], idx_view, sym_view, n_slices: int, C_: int,
+                          tables: DeviceCoderTables, layer=None, sel: int = 0) -> DeviceStreams:
+    """``strings[slice][image]`` uploaded in one host-to-device copy and decoded by one launch into the window of
+    ``sym_view``, on the current stream.  Returns without synchronising; :func:`check_status` reads the codes later."""
+    B = int(sym_view.buf.shape[0])
+    if len(strings) != n_slices or any(len(row) != B for row in strings):
+        raise ValueError(f"device coder: expected {n_slices} slices x {B} images of strings")
+    up = upload_streams([s_ for row in strings for s_ in row], sym_view.buf.device)
+    decode_uploaded(up, 0, idx_view, sym_view, n_slices, C_, tables, layer, sel)
+    return up
+
+
+def check_status(up: DeviceStreams, B: int, what: str = "vam_rans_decode_device", name=None):
+    """Reads the status codes of ``up`` (synchronises) and raises VamError naming the first failed stream.  ``name(k)``
+    words string k; the default is stream id = slice * B + image."""
+    st = up.status[:up.n].cpu().numpy()
+    if name is None:
+        return raise_status(st, B, what)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        k = int(bad[0])
+        raise L.VamError(f"{what}: {name(k)}: {STATUS_TEXT.get(int(st[k]), f'status {int(st[k])}')}")
+
+
 def sigma0_index(scale_table) -> int:
     """The table index build_indexes gives sigma = 0 (the 0.11 bound applies), in float32 as the kernel compares."""
     tb = np.asarray(torch.as_tensor(scale_table).detach().cpu().numpy(), dtype=np.float32)

@@ -239,10 +239,12 @@ def compress_per_image(model, x, qualities, mask_pol=None):
     if not model._batch_shareable():
         outs = ((q, model.compress(x[b:b + 1], q, mask_pol)) for b, q in enumerate(qs))
         return [{"strings": out["strings"], "shape": out["shape"], "quality": q} for q, out in outs]
+    coder = model._coder()
     mask_pol = _prepare(model, x, mask_pol, "compress", need_tables=True)
     tg, te = bs.Tables.of(model.gaussian_conditional), bs.Tables.of(model.entropy_bottleneck)
     C = model.dim_chunk
     y_jobs, z_jobs, where = [], [], []                  # where: (image, number of y streams) per image, in job order
+    ys, zstr = [], []                                   # the device coder's strings, in the same order
     with torch.no_grad():
         for base_only, sub in _quality_sub_batches(qs, M._max_images_per_plan(x)):
             xb = x[sub].detach().contiguous()
@@ -251,18 +253,26 @@ def compress_per_image(model, x, qualities, mask_pol=None):
                 plan.execute(xb, 0.0, None, model.use_graph, False)
             else:
                 plan.execute_per_image(xb, _mask_qualities(mask_pol, [qs[b] for b in sub]), model.use_graph, False)
+            n_sl = model.ns0 if base_only else model.ns1
+            if coder == "device":                       # one launch per sub-batch for y, one for z
+                y_dev, z_dev = model._encode_plan_device(plan, n_sl)
+                for k, b in enumerate(sub):
+                    ys += [y_dev[s_][k] for s_ in range(n_sl)]
+                    zstr.append(z_dev[k])
+                    where.append((b, n_sl))
+                continue
             sym = plan.sym.buf.cpu().numpy()           # [b,h,w,C_lat] int32 (synchronises)
             idx = plan.idx.buf.cpu().numpy()
             zs = plan.z_sym.buf.cpu().numpy()
             zi = np.broadcast_to(np.arange(model.N, dtype=np.int32)[:, None, None], (model.N,) + zs.shape[1:3])
-            n_sl = model.ns0 if base_only else model.ns1
             for k, b in enumerate(sub):                 # stream order: [C, h, w] per image, as compress flattens
                 for s_ in range(n_sl):
                     ch = slice(s_ * C, (s_ + 1) * C)
                     y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
                 z_jobs.append((zs[k].transpose(2, 0, 1), zi))
                 where.append((b, n_sl))
-    ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+    if coder == "host":
+        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
     items: List[Optional[dict]] = [None] * len(qs)
     shape = (x.shape[2] // 64, x.shape[3] // 64)
     o = 0
@@ -282,6 +292,7 @@ def decompress_per_image(model, items, mask_pol=None):
     qs = [float(it["quality"]) for it in items]
     if any(not q >= 0 for q in qs):
         raise ValueError("decompress_per_image: qualities must be >= 0 (and not NaN)")
+    coder = model._coder()
     if not model._batch_shareable():
         return {"x_hat": torch.cat([model.decompress(it["strings"], shape, q, mask_pol)["x_hat"] for it, q in zip(items, qs)], 0)}
     mask_pol = _prepare(model, None, mask_pol)
@@ -301,8 +312,9 @@ def decompress_per_image(model, items, mask_pol=None):
         def build(B=len(sub)):
             if ops.f16x2_mode():
                 raise NotImplementedError(M.F16X2_REFUSAL)
-            return _DecPlan(model, B, hz, wz, False, None, dev, per_image=True)
-        dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image"), build, model._weights_sig())
+            return _DecPlan(model, B, hz, wz, False, None, dev, per_image=True, coder=coder)
+        dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image")
+                                + ((coder,) if coder != "host" else ()), build, model._weights_sig())
         x_hat[sub] = dp.decode(strings, _mask_qualities(mask_pol, [qs[b] for b in sub]), None)
     return {"x_hat": x_hat}
 
@@ -660,15 +672,23 @@ def forward_quality_map(model, x, qmap, mask_pol=None):
 
 def compress_quality_map(model, x, qmap, mask_pol=None):
     from . import bitstream as bs
+    coder = model._coder()
     mask_pol, levels, index = _map_prepare(model, x, qmap, mask_pol, "compress", need_tables=True)
     tg, te = bs.Tables.of(model.gaussian_conditional), bs.Tables.of(model.entropy_bottleneck)
     C, n_sl, nb = model.dim_chunk, model.ns1, M._max_images_per_plan(x)
     y_jobs, z_jobs = [], []
+    ys, zstr = [], []                                   # the device coder's strings, in the same order
     with torch.no_grad():
         for i in range(0, x.shape[0], nb):
             xb = x[i:i + nb].detach().contiguous()
             plan = model._plan(xb, base_only=False, symbols=True, quality_map=True)
             plan.execute_quality_map(xb, levels[i:i + nb], index[i:i + nb], model.use_graph, False)
+            if coder == "device":                       # one launch per sub-batch for y, one for z
+                y_dev, z_dev = model._encode_plan_device(plan, n_sl)
+                for k in range(xb.shape[0]):
+                    ys += [y_dev[s_][k] for s_ in range(n_sl)]
+                    zstr.append(z_dev[k])
+                continue
             sym = plan.sym.buf.cpu().numpy()           # [b,h,w,C_lat] int32 (synchronises)
             idx = plan.idx.buf.cpu().numpy()
             zs = plan.z_sym.buf.cpu().numpy()
@@ -678,7 +698,8 @@ def compress_quality_map(model, x, qmap, mask_pol=None):
                     ch = slice(s_ * C, (s_ + 1) * C)
                     y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
                 z_jobs.append((zs[k].transpose(2, 0, 1), zi))
-    ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+    if coder == "host":
+        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
     shape = (x.shape[2] // 64, x.shape[3] // 64)
     return [{"strings": [[[s_] for s_ in ys[b * n_sl:(b + 1) * n_sl]], [zstr[b]]], "shape": shape,
              "quality_map": {"levels": [float(q) for q in levels[b]], "index": index[b].copy()},
@@ -712,6 +733,7 @@ def decompress_quality_map(model, items, mask_pol=None):
         raise ValueError("decompress_quality_map: all items must have the same shape; decode other shapes in a call of their own")
     hz, wz = shape
     maps = [_item_map(it, b, 4 * hz, 4 * wz) for b, it in enumerate(items)]
+    coder = model._coder()
     _map_refuse(model)
     _prepare(model, None, mask_pol)
     dev = model.entropy_bottleneck.quantiles.device
@@ -728,8 +750,9 @@ def decompress_quality_map(model, items, mask_pol=None):
         def build(B=len(sub)):
             if ops.f16x2_mode():
                 raise NotImplementedError(M.F16X2_REFUSAL)
-            return _DecPlan(model, B, hz, wz, False, None, dev, quality_map=True)
-        dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "quality_map"), build, model._weights_sig())
+            return _DecPlan(model, B, hz, wz, False, None, dev, quality_map=True, coder=coder)
+        dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "quality_map")
+                                + ((coder,) if coder != "host" else ()), build, model._weights_sig())
         x_hat[sub] = dp.decode(strings, None, None, quality_map=([maps[b][0] for b in sub], np.stack([maps[b][1] for b in sub])))
     return {"x_hat": x_hat}
 

@@ -1,0 +1,292 @@
+// The rANS coder of rans.cpp as one core for host and device: the same wire format — 64-bit state,
+// 32-bit renormalisation words, 16-bit precision, 4-bit bypass nibbles (count nibbles, then up to 8 raw nibbles), the
+// final state as two words — restated so that one stream is coded without an expansion buffer and decoded without
+// trusting its input.  rans.cpp is the yardstick: tests/test_rans_core_cpu.py holds this header to its bytes.
+//
+// Layers:   steps     enc_put / enc_put_bits / enc_element, dec_init / dec_bits / dec_element: one symbol's state update;
+//                     the device kernels (rans_device.hip) call these between their parallel staging phases
+//           streams   encode_stream / decode_stream: one whole stream on one thread (host exports, sanitizer program)
+// Addressing goes through a functor (Flat, Nhwc), the symbol search through another (CdfSearch here, the wave-wide
+// search of rans_device.hip), so the steps never see a pointer they could walk off.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define VAM_RANS_HD __host__ __device__ inline
+#else
+#define VAM_RANS_HD inline
+#endif
+
+namespace vam_rans {
+
+constexpr int kPrecision = 16;
+constexpr int kBypassBits = 4;
+constexpr uint32_t kMaxBypass = (1u << kBypassBits) - 1;
+constexpr int kMaxRawNibbles = 32 / kBypassBits;
+constexpr uint64_t kRansL = 1ull << 31;
+
+// Per-stream status codes (0 = ok); bitstream.py words them like the host coder's errors.
+enum Status : int32_t {
+  kOk = 0,
+  kTruncated = 1,      // decode: a word was needed past the end of the stream
+  kBadIndex = 2,       // a table index outside [0, n_cdfs)
+  kBadTable = 3,       // a cdf_sizes entry the coder refuses, or a table that is not increasing where it was read
+  kOverflow = 4,       // encode: the output region is too small
+  kZeroFreq = 5,       // encode: zero-frequency symbol (cdf table not normalised)
+  kBadStream = 6       // decode: fewer than 8 bytes, not whole words, or misaligned
+};
+
+// ---------------------------------------------------------------- addressing
+// Stream element i -> offset into a buffer, and the channel it belongs to (the table index when there is no index buffer).
+struct Flat {
+  VAM_RANS_HD long off(long i) const { return i; }
+  VAM_RANS_HD int chan(long) const { return 0; }
+};
+// An NHWC window: element i = (c * h + y) * w + x of one image reads buf[(y * w + x) * ld + c], buf pointing at the
+// image's first pixel and the window's first channel.  That is the [C, h, w] order the host coder gets after transpose.
+struct Nhwc {
+  long hw, ld;
+  VAM_RANS_HD long off(long i) const { const long c = i / hw; return (i - c * hw) * ld + c; }
+  VAM_RANS_HD int chan(long i) const { return (int)(i / hw); }
+};
+
+// ---------------------------------------------------------------- encode steps
+// Exact x / f and x % f for f < 2^16 from m = floor((2^32 - 1) / f), one multiply-high and one correction per 32-bit
+// step: m = 2^32 / f - e with 0 <= e <= 1, so floor(t * m / 2^32) lies in (t / f - 2, t / f]: it is q or q - 1.
+VAM_RANS_HD uint32_t reciprocal(uint32_t f) { return 0xFFFFFFFFu / (f ? f : 1u); }
+
+VAM_RANS_HD uint32_t div_step(uint32_t t, uint32_t f, uint32_t m, uint32_t& r) {
+  uint32_t q = (uint32_t)(((uint64_t)t * m) >> 32);
+  r = t - q * f;
+  if (r >= f) { ++q; r -= f; }
+  return q;
+}
+
+struct Enc {
+  uint64_t x;
+  uint32_t* p;         // next word is stored at --p
+  uint32_t* lo;        // the region is [lo, end)
+  int32_t status;
+  bool writer;         // device: every lane of the wave carries the state, one lane stores
+};
+
+VAM_RANS_HD void enc_init(Enc& e, uint32_t* lo, uint32_t* end, bool writer = true) {
+  e.x = kRansL; e.p = end; e.lo = lo; e.status = kOk; e.writer = writer;
+}
+
+VAM_RANS_HD void enc_flush_word(Enc& e) {
+  if (e.p <= e.lo) { e.status = kOverflow; return; }
+  --e.p;
+  if (e.writer) *e.p = (uint32_t)e.x;
+  e.x >>= 32;
+}
+
+// enc_put of rans.cpp: x = ((x / freq) << 16) + x % freq + start.  After renormalisation x < freq * 2^47, so the high
+// word is below freq * 2^15 and the quotient comes from three 32-bit steps (high word, then 16 bits at a time).
+VAM_RANS_HD void enc_put(Enc& e, uint32_t start, uint32_t freq, uint32_t rcp) {
+  if (e.x >= ((uint64_t)freq << (31 - kPrecision + 32))) enc_flush_word(e);
+  if (e.status) return;
+  const uint32_t hi = (uint32_t)(e.x >> 32), lw = (uint32_t)e.x;
+  uint32_t r;
+  const uint64_t q0 = div_step(hi, freq, rcp, r);
+  const uint64_t q1 = div_step((r << 16) | (lw >> 16), freq, rcp, r);
+  const uint64_t q2 = div_step((r << 16) | (lw & 0xFFFFu), freq, rcp, r);
+  e.x = (((q0 << 32) | (q1 << 16) | q2) << kPrecision) + r + start;
+}
+
+VAM_RANS_HD void enc_put_bits(Enc& e, uint32_t val) {
+  if (e.x >= (1ull << (31 - kPrecision + 32 + kPrecision - kBypassBits))) enc_flush_word(e);
+  if (e.status) return;
+  e.x = (e.x << kBypassBits) | val;
+}
+
+// One element, looked up: the table symbol and, when it is the escape, the raw value behind it.
+struct Put {
+  uint32_t start_freq;  // start | freq << 16 (both < 2^16)
+  uint32_t rcp;
+  uint32_t raw;
+  int32_t n_bypass;     // -1: no escape
+};
+
+// The look-ups of encode_one for one element (value already masked by the layer selection).  Returns a status.
+VAM_RANS_HD int32_t classify(int32_t symbol, int ci, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                             const int32_t* offsets, int n_cdfs, Put& u) {
+  u.start_freq = 0; u.rcp = 0; u.raw = 0; u.n_bypass = -1;
+  if (ci < 0 || ci >= n_cdfs) return kBadIndex;
+  const int32_t* cdf = cdfs + (long)ci * cdf_stride;
+  const int max_value = cdf_sizes[ci] - 2;
+  if (max_value < 0 || max_value + 1 >= cdf_stride) return kBadTable;
+  int64_t value = (int64_t)symbol - offsets[ci];
+  uint32_t raw = 0;
+  if (value < 0) {
+    raw = (uint32_t)(-2 * value - 1);
+    value = max_value;
+  } else if (value >= max_value) {
+    raw = (uint32_t)(2 * (value - max_value));
+    value = max_value;
+  }
+  const uint32_t start = (uint16_t)cdf[value], freq = (uint16_t)(cdf[value + 1] - cdf[value]);
+  if (freq == 0) return kZeroFreq;
+  u.start_freq = start | (freq << 16);
+  u.rcp = reciprocal(freq);
+  if (value == max_value) {
+    int nb = 0;
+    while (nb < kMaxRawNibbles && (raw >> (nb * kBypassBits)) != 0) ++nb;
+    u.raw = raw;
+    u.n_bypass = nb;
+  }
+  return kOk;
+}
+
+// The puts of one element in reverse: raw nibbles n_bypass-1 .. 0, the count nibbles backwards, then the table symbol
+// (the decoder reads symbol, count, raw nibbles 0 .. n_bypass-1).
+VAM_RANS_HD void enc_element(Enc& e, const Put& u) {
+  if (u.n_bypass >= 0) {
+    for (int j = u.n_bypass - 1; j >= 0; --j) enc_put_bits(e, (u.raw >> (j * kBypassBits)) & kMaxBypass);
+    enc_put_bits(e, (uint32_t)u.n_bypass % kMaxBypass);                  // forward: [15] * (n / 15), then n % 15
+    for (int k = u.n_bypass / (int)kMaxBypass; k > 0; --k) enc_put_bits(e, kMaxBypass);
+  }
+  enc_put(e, u.start_freq & 0xFFFFu, u.start_freq >> 16, u.rcp);
+}
+
+// The final state as two words; returns the stream length in words (the stream is the region's tail).
+VAM_RANS_HD long enc_finish(Enc& e, uint32_t* end) {
+  if (e.status) return 0;
+  if (e.p - e.lo < 2) { e.status = kOverflow; return 0; }
+  e.p -= 2;
+  if (e.writer) { e.p[0] = (uint32_t)e.x; e.p[1] = (uint32_t)(e.x >> 32); }
+  return (long)(end - e.p);
+}
+
+// One stream on one thread.  sym / idx / layer are addressed through A; idx == NULL means "index = channel".
+// Words are written backwards from region + cap_words; *n_words receives the length, the stream is the tail.
+template <class A>
+VAM_RANS_HD int32_t encode_stream(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at,
+                                  const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                  int n_cdfs, uint32_t* region, long cap_words, long* n_words) {
+  *n_words = 0;
+  Enc e;
+  enc_init(e, region, region + cap_words);
+  for (long i = n - 1; i >= 0; --i) {
+    const long o = at.off(i);
+    const bool keep = !layer || layer[o] == sel;
+    const int ci = keep ? (idx ? idx[o] : at.chan(i)) : 0;
+    Put u;
+    const int32_t st = classify(keep ? sym[o] : 0, ci, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, u);
+    if (st) return st;
+    enc_element(e, u);
+    if (e.status) return e.status;
+  }
+  *n_words = enc_finish(e, region + cap_words);
+  return e.status;
+}
+
+// ---------------------------------------------------------------- decode steps
+struct Dec {
+  uint64_t x;
+  const uint32_t* p;
+  const uint32_t* end;
+  int32_t status;
+};
+
+VAM_RANS_HD void dec_init(Dec& d, const uint32_t* words, long n_bytes) {
+  d.x = 0; d.p = d.end = words; d.status = kOk;
+  if (!words || n_bytes < 8 || (n_bytes & 3) || ((uintptr_t)words & 3)) { d.status = kBadStream; return; }
+  d.end = words + n_bytes / 4;
+  d.x = (uint64_t)words[0] | ((uint64_t)words[1] << 32);
+  d.p = words + 2;
+}
+
+VAM_RANS_HD void dec_renorm(Dec& d) {
+  if (d.x < kRansL) {
+    if (d.p >= d.end) { d.status = kTruncated; return; }
+    d.x = (d.x << 32) | *d.p++;
+  }
+}
+
+VAM_RANS_HD uint32_t dec_bits(Dec& d) {
+  const uint32_t val = (uint32_t)(d.x & kMaxBypass);
+  d.x >>= kBypassBits;
+  dec_renorm(d);
+  return val;
+}
+
+// One element of a table with `sz` entries.  find(cum, start, freq) returns the host's scan result s = the number of
+// entries 1 .. sz-1 that are <= cum (at most sz - 2), and that entry's start and frequency.  Returns the value relative
+// to the table's offset; d.status != 0 afterwards means the element is incomplete and the value is not to be used.
+template <class F>
+VAM_RANS_HD int32_t dec_element(Dec& d, const F& find, int sz) {
+  const uint32_t cum = (uint32_t)(d.x & ((1u << kPrecision) - 1));
+  uint32_t start, freq;
+  const int s = find(cum, start, freq);
+  if (freq == 0 || freq > (1u << kPrecision) || start > cum) { d.status = kBadTable; return 0; }
+  d.x = (uint64_t)freq * (d.x >> kPrecision) + cum - start;
+  dec_renorm(d);
+  if (d.status) return 0;
+  const int max_value = sz - 2;
+  if (s != max_value) return s;
+  uint32_t val = dec_bits(d);
+  uint32_t n_bypass = val;
+  while (!d.status && val == kMaxBypass) {        // every nibble eats 4 bits of the stream: bounded by its length
+    val = dec_bits(d);
+    n_bypass += val;
+  }
+  uint32_t raw = 0;
+  for (uint32_t j = 0; !d.status && j < n_bypass; ++j) {
+    const uint32_t nib = dec_bits(d);
+    if (j < (uint32_t)kMaxRawNibbles) raw |= nib << (j * kBypassBits);
+  }
+  if (d.status) return 0;
+  const uint32_t half = raw >> 1;                 // unsigned: a corrupt stream may not overflow an int
+  return (int32_t)((raw & 1) ? ~half : half + (uint32_t)max_value);
+}
+
+// The host's linear scan as a binary search over an int32 table: entries 1 .. sz-1 are increasing on every table the
+// coder accepts, so the count of entries <= cum is the scan's stopping point.
+struct CdfSearch {
+  const int32_t* cdf;
+  int sz;
+  VAM_RANS_HD int operator()(uint32_t cum, uint32_t& start, uint32_t& freq) const {
+    int lo = 0, hi = sz - 1;                      // s in [lo, hi]: cdf[1 .. lo] <= cum
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((uint32_t)cdf[mid] <= cum) lo = mid; else hi = mid - 1;
+    }
+    if (lo > sz - 2) lo = sz - 2;                 // only on a table without its terminal 65536: stay inside it
+    start = (uint32_t)cdf[lo];
+    freq = (uint32_t)cdf[lo + 1] - start;
+    return lo;
+  }
+};
+
+// One stream on one thread; idx == NULL means "index = channel".  Only elements with layer[i] == sel are written.
+// After a failure every remaining selected element is written as 0.
+template <class A>
+VAM_RANS_HD int32_t decode_stream(const uint32_t* words, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel,
+                                  long n, const A& at, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                  const int32_t* offsets, int n_cdfs, int32_t* out) {
+  Dec d;
+  dec_init(d, words, n_bytes);
+  for (long i = 0; i < n; ++i) {
+    const long o = at.off(i);
+    const bool keep = !layer || layer[o] == sel;
+    int32_t value = 0;
+    if (!d.status) {
+      const int ci = keep ? (idx ? idx[o] : at.chan(i)) : 0;
+      if (ci < 0 || ci >= n_cdfs) d.status = kBadIndex;
+      else {
+        const int sz = cdf_sizes[ci];
+        if (sz - 2 < 0 || sz - 1 >= cdf_stride) d.status = kBadTable;
+        else {
+          const int32_t v = dec_element(d, CdfSearch{cdfs + (long)ci * cdf_stride, sz}, sz);
+          if (!d.status) value = (int32_t)((uint32_t)v + (uint32_t)offsets[ci]);
+        }
+      }
+    }
+    if (keep) out[o] = value;
+  }
+  return d.status;
+}
+
+}  // namespace vam_rans

@@ -1,0 +1,350 @@
+// The rANS coder on the device: rans_core.h's steps driven by one wave per stream.
+//
+// A stream is an (image, slice) pair of an NHWC int32 window; stream id = slice * B + image.  What is parallel: all
+// streams of a launch, and inside a stream everything that does not depend on the coder state — addressing, the layer
+// selection, the index / size / offset / start / frequency look-ups and the escape classification, staged 64 elements
+// at a time, one per lane.  What is serial: the state update, which every lane of the wave carries redundantly (the
+// values are wave-uniform), so a staged record is fetched with v_readlane and the decoder's symbol search is a wave-wide
+// compare (one ballot per 64 table entries) instead of a scan.  One lane stores.  Plain C++ only.
+#include "common.h"
+#include "rans_core.h"
+#include <cstring>
+
+using namespace vam;
+namespace R = vam_rans;
+
+namespace {
+
+constexpr int kWave = 64;
+
+__device__ __forceinline__ int lane_get(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+struct Geometry {
+  int B, h, w, ld, c0, C, n_slices;
+};
+
+struct EncArgs {
+  const int32_t* sym;
+  const int32_t* idx;
+  const uint8_t* layer;
+  int sel;
+  Geometry g;
+  vam_rans_tables t;
+  uint32_t* out;
+  long cap;
+  int32_t* lengths;
+  int32_t* status;
+};
+
+__global__ __launch_bounds__(kWave) void rans_encode_kernel(EncArgs a) {
+  const int sid = blockIdx.x, lane = threadIdx.x;
+  const int s = sid / a.g.B, b = sid - s * a.g.B;
+  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
+  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  const R::Nhwc at{hw, a.g.ld};
+  uint32_t* region = a.out + (long)sid * a.cap;
+  R::Enc e;
+  R::enc_init(e, region, region + a.cap, lane == 0);
+  int fail = 0;
+  for (long base = (n - 1) / kWave * kWave; base >= 0 && n > 0; base -= kWave) {
+    const long i = base + lane;
+    R::Put u{0, 0, 0, -1};
+    int st = 0;
+    if (i < n) {                                      // staging: one element per lane
+      const long o = img + at.off(i);
+      const bool keep = !a.layer || a.layer[o] == a.sel;
+      const int ci = keep ? (a.idx ? a.idx[o] : at.chan(i)) : 0;
+      st = R::classify(keep ? a.sym[o] : 0, ci, a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+    }
+    const unsigned long long bad = __ballot(st != 0);
+    if (bad) {                                        // the element nearest the stream's end decides, as good as any
+      fail = lane_get(st, 63 - __clzll(bad));
+      break;
+    }
+    const int cnt = (int)(n - base < kWave ? n - base : kWave);
+    for (int k = cnt - 1; k >= 0; --k) {              // serial: wave-uniform state, records by v_readlane
+      const R::Put uk{(uint32_t)lane_get((int)u.start_freq, k), (uint32_t)lane_get((int)u.rcp, k),
+                      (uint32_t)lane_get((int)u.raw, k), lane_get(u.n_bypass, k)};
+      R::enc_element(e, uk);
+    }
+    fail = uniform(e.status);
+    if (fail) break;
+  }
+  long words = 0;
+  if (!fail) {
+    words = R::enc_finish(e, region + a.cap);
+    fail = uniform(e.status);
+  }
+  if (lane == 0) {
+    a.lengths[sid] = fail ? 0 : (int32_t)words;
+    a.status[sid] = fail;
+  }
+}
+
+// offsets[s] = sum of lengths[0 .. s), offsets[n] = the total; stream s's tail words go to packed + offsets[s].
+__global__ __launch_bounds__(256) void rans_pack_kernel(const uint32_t* regions, long cap, const int32_t* lengths, int n_streams,
+                                                        uint32_t* packed, long packed_cap, int64_t* offsets) {
+  __shared__ long part[256];
+  const int sid = blockIdx.x, t = threadIdx.x;
+  long sum = 0;
+  for (int j = t; j < sid; j += 256) sum += lengths[j];
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (t < d) part[t] += part[t + d];
+    __syncthreads();
+  }
+  const long off = part[0], len = lengths[sid];
+  if (t == 0) {
+    offsets[sid] = off;
+    if (sid == n_streams - 1) offsets[n_streams] = off + (len > 0 ? len : 0);
+  }
+  if (len <= 0 || len > cap || off + len > packed_cap) return;
+  const uint32_t* src = regions + (long)sid * cap + (cap - len);
+  for (long j = t; j < len; j += 256) packed[off + j] = src[j];
+}
+
+// The decoder's symbol search across the wave: entries e[1 .. n_ent] of an increasing table, 64 at a time.  Above 64
+// entries the lanes first sample every step-th one to find the bucket.  Returns what the host's linear scan returns.
+template <class E>
+struct WaveSearch {
+  const E* e;          // e[0] = the table's first entry
+  int sz;              // cdf_sizes of the table
+  bool implied_last;   // packed tables: entry sz-1 is not stored, it is 65536
+  __device__ int operator()(uint32_t cum, uint32_t& start, uint32_t& freq) const {
+    const int lane = threadIdx.x;
+    int lo = 0, len = implied_last ? sz - 2 : sz - 1;        // searchable entries e[1 + lo .. 1 + lo + len)
+    while (len > kWave) {
+      const int step = (len + kWave - 1) / kWave;
+      const int pos = lo + (lane + 1) * step - 1;
+      const bool le = pos < lo + len && (uint32_t)e[1 + pos] <= cum;
+      const int full = __popcll(__ballot(le));                 // buckets that lie wholly at or below cum
+      const int end = lo + len;
+      lo += full * step;
+      len = end - lo < step ? (end - lo > 0 ? end - lo : 0) : step;
+    }
+    const bool le = lane < len && (uint32_t)e[1 + lo + lane] <= cum;
+    int s = lo + __popcll(__ballot(le));
+    if (s > sz - 2) s = sz - 2;
+    start = (uint32_t)e[s];
+    freq = (implied_last && s == sz - 2 ? (1u << R::kPrecision) : (uint32_t)e[s + 1]) - start;
+    return s;
+  }
+};
+
+struct DecArgs {
+  const uint8_t* bytes;
+  const int64_t* byte_offsets;
+  const int32_t* byte_lengths;
+  const int32_t* idx;
+  const uint8_t* layer;
+  int sel;
+  Geometry g;
+  vam_rans_tables t;
+  int32_t* out;
+  int32_t* status;
+};
+
+template <bool kPacked>
+__global__ __launch_bounds__(kWave) void rans_decode_kernel(DecArgs a) {
+  extern __shared__ uint4 lds_raw[];
+  const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds_raw);
+  const int sid = blockIdx.x, lane = threadIdx.x;
+  if (kPacked) {                                              // the ragged 16-bit tables into LDS, 16 bytes per lane and step
+    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
+    for (int j = lane; j < a.t.packed_entries / 8; j += kWave) lds_raw[j] = src[j];
+    __syncthreads();
+  }
+  const int s = sid / a.g.B, b = sid - s * a.g.B;
+  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
+  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  const R::Nhwc at{hw, a.g.ld};
+  R::Dec d;
+  const int64_t boff = a.byte_offsets[sid];
+  R::dec_init(d, (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff), a.byte_lengths[sid]);
+  int fail = uniform(d.status);
+  for (long base = 0; base < n; base += kWave) {
+    const long i = base + lane;
+    bool keep = false;
+    long o = 0;
+    int st = 0, sz = 2, offv = 0, t0 = 0;
+    if (i < n) {                                              // staging: one element per lane
+      o = img + at.off(i);
+      keep = !a.layer || a.layer[o] == a.sel;
+      const int ci = keep ? (a.idx ? a.idx[o] : at.chan(i)) : 0;
+      if (ci < 0 || ci >= a.t.n_cdfs) st = R::kBadIndex;
+      else {
+        sz = a.t.sizes[ci];
+        if (sz - 2 < 0 || sz - 1 >= a.t.stride) st = R::kBadTable;
+        else {
+          offv = a.t.offsets[ci];
+          t0 = kPacked ? a.t.packed_start[ci] : ci * a.t.stride;
+        }
+      }
+    }
+    int32_t mine = 0;
+    bool have = false;
+    const int cnt = (int)(n - base < kWave ? n - base : kWave);
+    for (int k = 0; k < cnt && !fail; ++k) {                  // serial: wave-uniform state, records by v_readlane
+      fail = lane_get(st, k);
+      if (fail) break;
+      const int szk = lane_get(sz, k), tk = lane_get(t0, k);
+      int32_t v;
+      if (kPacked) v = R::dec_element(d, WaveSearch<uint16_t>{tab + tk, szk, true}, szk);
+      else v = R::dec_element(d, WaveSearch<int32_t>{a.t.cdf + tk, szk, false}, szk);
+      fail = uniform(d.status);
+      if (fail) break;
+      if (lane == k) { mine = v; have = true; }
+    }
+    if (keep) a.out[o] = have ? (int32_t)((uint32_t)mine + (uint32_t)offv) : 0;   // after a failure: zeros
+  }
+  if (lane == 0) a.status[sid] = fail;
+}
+
+int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices) {
+  VAM_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && n_slices > 0 && c0 >= 0, "%s: B, h, w, C, n_slices must be > 0 and c0 >= 0", what);
+  VAM_REQUIRE((long)c0 + (long)C * n_slices <= ld, "%s: window [%d, %ld) does not fit ld = %d", what, c0, (long)c0 + (long)C * n_slices, ld);
+  VAM_REQUIRE((long)h * w * C <= (1l << 28) && (long)B * n_slices <= (1l << 20), "%s: stream of %ld symbols or %ld streams is too large", what,
+              (long)h * w * C, (long)B * n_slices);
+  return VAM_OK;
+}
+
+int check_tables(const char* what, const vam_rans_tables* t) {
+  VAM_REQUIRE(t && t->cdf && t->sizes && t->offsets && t->n_cdfs > 0 && t->stride >= 2, "%s: tables need cdf, sizes, offsets, n_cdfs > 0, stride >= 2", what);
+  VAM_REQUIRE((long)t->n_cdfs * t->stride < (1l << 31), "%s: tables too large", what);
+  VAM_REQUIRE(!t->packed || (t->packed_start && t->packed_entries > 0 && t->packed_entries % 8 == 0),
+              "%s: packed tables need their start offsets and a multiple of 8 entries", what);
+  return VAM_OK;
+}
+
+const char* status_text(int st) {
+  switch (st) {
+    case R::kTruncated: return "bitstream truncated";
+    case R::kBadIndex: return "index out of range";
+    case R::kBadTable: return "cdf size invalid";
+    case R::kOverflow: return "output buffer too small";
+    case R::kZeroFreq: return "zero-frequency symbol (cdf table not normalised)";
+    case R::kBadStream: return "bad arguments (a stream is at least 8 bytes, in whole words)";
+    default: return "unknown status";
+  }
+}
+
+template <class A>
+long core_encode(const char* what, const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at,
+                 const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out,
+                 long out_cap) {
+  std::vector<uint32_t> region((size_t)(2 * n + 16));       // 8 n + 64 bytes, the host coder's budget
+  long words = 0;
+  const int32_t st = R::encode_stream(sym, idx, layer, sel, n, at, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, region.data(),
+                                      (long)region.size(), &words);
+  VAM_REQUIRE(st == 0, "%s: %s", what, status_text(st));
+  VAM_REQUIRE(words * 4 <= out_cap, "%s: output buffer too small (%ld > %ld)", what, words * 4, out_cap);
+  std::memcpy(out, region.data() + region.size() - words, (size_t)words * 4);
+  return words * 4;
+}
+
+template <class A>
+int core_decode(const uint8_t* in, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at,
+                const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out) {
+  std::vector<uint32_t> words((size_t)(n_bytes / 4));       // aligned copy of the whole words
+  if (!words.empty()) std::memcpy(words.data(), in, words.size() * 4);
+  return R::decode_stream(words.empty() ? nullptr : words.data(), n_bytes, idx, layer, sel, n, at, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+long vam_rans_core_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                          const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap,
+                          const uint8_t* layer, int sel) {
+  VAM_REQUIRE(symbols && indexes && cdfs && cdf_sizes && offsets && out && n >= 0 && n <= (1l << 28) && n_cdfs >= 1,
+              "vam_rans_core_encode: bad arguments");
+  return core_encode("vam_rans_core_encode", symbols, indexes, layer, sel, n, R::Flat{}, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                     out, out_cap);
+}
+
+int vam_rans_core_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                         const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out, const uint8_t* layer, int sel) {
+  VAM_REQUIRE((in || n_bytes == 0) && indexes && cdfs && cdf_sizes && offsets && out && n >= 0 && n_bytes >= 0 && n_cdfs >= 1,
+              "vam_rans_core_decode: bad arguments");
+  return core_decode(in, n_bytes, indexes, layer, sel, n, R::Flat{}, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out);
+}
+
+long vam_rans_core_encode_nhwc(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int image, int h, int w, int ld,
+                               int c0, int C, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                               int n_cdfs, uint8_t* out, long out_cap) {
+  VAM_REQUIRE(sym && cdfs && cdf_sizes && offsets && out && n_cdfs >= 1 && image >= 0, "vam_rans_core_encode_nhwc: bad arguments");
+  if (int rc = check_geometry("vam_rans_core_encode_nhwc", 1, h, w, ld, c0, C, 1)) return rc;
+  const long hw = (long)h * w, img = (long)image * hw * ld + c0;
+  return core_encode("vam_rans_core_encode_nhwc", sym + img, idx ? idx + img : nullptr, layer ? layer + img : nullptr, sel, hw * C,
+                     R::Nhwc{hw, ld}, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out, out_cap);
+}
+
+int vam_rans_core_decode_nhwc(const uint8_t* in, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel, int image, int h,
+                              int w, int ld, int c0, int C, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                              const int32_t* offsets, int n_cdfs, int32_t* sym_out) {
+  VAM_REQUIRE((in || n_bytes == 0) && cdfs && cdf_sizes && offsets && sym_out && n_bytes >= 0 && n_cdfs >= 1 && image >= 0,
+              "vam_rans_core_decode_nhwc: bad arguments");
+  if (int rc = check_geometry("vam_rans_core_decode_nhwc", 1, h, w, ld, c0, C, 1)) return rc;
+  const long hw = (long)h * w, img = (long)image * hw * ld + c0;
+  return core_decode(in, n_bytes, idx ? idx + img : nullptr, layer ? layer + img : nullptr, sel, hw * C, R::Nhwc{hw, ld}, cdfs,
+                     cdf_stride, cdf_sizes, offsets, n_cdfs, sym_out + img);
+}
+
+int vam_rans_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0,
+                           int C, int n_slices, const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words,
+                           int32_t* lengths, int32_t* status, void* stream) {
+  VAM_REQUIRE(sym && out_words && lengths && status, "vam_rans_encode_device: need sym, out_words, lengths, status");
+  if (int rc = check_geometry("vam_rans_encode_device", B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables("vam_rans_encode_device", tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "vam_rans_encode_device: a region is 2 .. 2^31 words, got %ld", out_cap_words);
+  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, *tables, out_words, out_cap_words, lengths, status};
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_encode_kernel, dim3(B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_encode_kernel");
+}
+
+int vam_rans_pack_device(const uint32_t* regions, long cap_words, const int32_t* lengths, int n_streams, uint32_t* packed,
+                         long packed_cap_words, int64_t* offsets, void* stream) {
+  VAM_REQUIRE(regions && lengths && packed && offsets && n_streams > 0 && cap_words >= 2 && packed_cap_words >= 0,
+              "vam_rans_pack_device: bad arguments");
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_pack_kernel, dim3(n_streams), dim3(256), 0, (hipStream_t)stream, regions, cap_words, lengths, n_streams,
+                     packed, packed_cap_words, offsets);
+  return check_launch("rans_pack_kernel");
+}
+
+int vam_rans_lds_table_bytes(void) {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+    set_error("vam_rans_lds_table_bytes: no HIP device");
+    return VAM_ENOGPU;
+  }
+  return v;
+}
+
+int vam_rans_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                           const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
+                           const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status, "vam_rans_decode_device: need bytes, offsets, lengths, sym_out, status");
+  if (int rc = check_geometry("vam_rans_decode_device", B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables("vam_rans_decode_device", tables)) return rc;
+  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, *tables, sym_out, status};
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "vam_rans_decode_device: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_decode_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(rans_decode_kernel<true>, dim3(B * n_slices), dim3(kWave), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rans_decode_kernel<false>, dim3(B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_decode_kernel");
+}
+
+}  // extern "C"

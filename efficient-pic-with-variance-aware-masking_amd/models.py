@@ -155,6 +155,9 @@ class VarianceMaskingPIC(CompressionModel):
         # stored in bf16 and multiplied by bf16-rounded weights (fp32 accumulation); the entropy-parameter stacks, the
         # variance mask and the likelihoods stay fp32.  Differences to the fp32 path are MEASURED (bench.py --dtype bf16).
         self.storage = "fp32"
+        # "host" (default): the rANS coder of csrc/rans.cpp; "device": the same wire format coded and decoded by the kernels
+        # of csrc/rans_device.hip.  Read at each compress / decompress call.
+        self.coder = "host"
 
     # ---- reference helpers kept for the harness
     def freeze_all(self):
@@ -625,11 +628,29 @@ class VarianceMaskingPIC(CompressionModel):
     def _rem_choice(self, quality, checkpoint_rep):
         return None                                    # no REM in the plain model
 
+    def _coder(self) -> str:
+        if self.coder not in ("host", "device"):
+            raise ValueError(f"model.coder is 'host' or 'device', got {self.coder!r}")
+        return self.coder
+
+    def _encode_plan_device(self, plan, n_sl: int):
+        """The streams of an executed symbol plan from the device coder: (y strings [slice][image], z strings [image]).  One
+        launch for the n_sl * B slice streams straight from the plan's NHWC symbol and index views, one for the B z streams
+        (no index buffer: table index = channel)."""
+        from . import bitstream as bs
+        dev = plan.sym.buf.device
+        tg = bs.DeviceCoderTables.of(self.gaussian_conditional, dev)
+        te = bs.DeviceCoderTables.of(self.entropy_bottleneck, dev)
+        ys = bs.encode_streams_device(plan.sym, plan.idx, n_sl, self.dim_chunk, tg)
+        zs = bs.encode_streams_device(plan.z_sym, None, 1, self.N, te)
+        return ys, zs[0]
+
     def compress(self, x, quality=0.0, mask_pol=None, checkpoint_rep=None, real_compress=True):
         """One rANS stream per (slice, image) for y and per image for z.  The latents, entropy
         parameters, masks, symbols and table indexes come from the fused HIP plan; only the
         bit-serial coder runs on the host (as in the reference, entropy_models.py:231-239)."""
         mask_pol = self._mask_policy(mask_pol)
+        coder = self._coder()
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
@@ -641,7 +662,11 @@ class VarianceMaskingPIC(CompressionModel):
         B, C = plan.B, self.dim_chunk
         n_sl = self.ns0 if base_only else self.ns1
         y_strings: List[List[bytes]] = []
-        if real_compress:
+        if real_compress and coder == "device":
+            if plan.idx is None:
+                raise ValueError(EMPTY_SCALE_TABLE.format("compress"))
+            y_strings, z_strings = self._encode_plan_device(plan, n_sl)
+        elif real_compress:
             from . import bitstream as bs
             if plan.idx is None:
                 raise ValueError(EMPTY_SCALE_TABLE.format("compress"))
@@ -671,6 +696,7 @@ class VarianceMaskingPIC(CompressionModel):
         """models/pic.py:838-967: z -> hyper-synthesis -> slice by slice (entropy parameters on the
         GPU, rANS decode on the host, LRP on the GPU) -> g_s."""
         mask_pol = self._mask_policy(mask_pol)
+        coder = self._coder()
         L.require_gpu()
         self._check_config()
         dev = self.entropy_bottleneck.quantiles.device
@@ -682,8 +708,9 @@ class VarianceMaskingPIC(CompressionModel):
         def build():
             if ops.f16x2_mode():
                 raise NotImplementedError(F16X2_REFUSAL)
-            return _DecPlan(self, B, hz, wz, base_only, rem_idx, dev)
-        dp = self._cached_plan(self._dec_plans, (B, hz, wz, base_only, rem_idx, str(dev)), build, self._weights_sig(), rem_idx)
+            return _DecPlan(self, B, hz, wz, base_only, rem_idx, dev, coder=coder)
+        dp = self._cached_plan(self._dec_plans, (B, hz, wz, base_only, rem_idx, str(dev)) + ((coder,) if coder != "host" else ()),
+                               build, self._weights_sig(), rem_idx)
         return {"x_hat": dp.decode(strings, _mask_quality(mask_pol, quality), checkpoint_rep if rem_idx is not None else None)}
 
     def _prog_dec_plan(self, B, hz, wz, q_list) -> "_ProgDecPlan":

@@ -949,12 +949,16 @@ class _DecPlan:
     kernel's K order is canonical, so mu / sigma / masks / indexes are bit-identical to the
     encoder's although the launches are grouped differently."""
 
-    def __init__(self, m, B, hz, wz, base_only, rem_idx, device, per_image: bool = False, quality_map: bool = False):
+    def __init__(self, m, B, hz, wz, base_only, rem_idx, device, per_image: bool = False, quality_map: bool = False,
+                 coder: str = "host"):
         """``per_image``: the per-slice masks read each image's quality from ``qtable`` (decode_per_image refills it);
-        ``quality_map``: each latent pixel's from ``qtable`` and ``level_map``."""
+        ``quality_map``: each latent pixel's from ``qtable`` and ``level_map``.  ``coder`` "device"
+        (DESIGN section 9n): every string is uploaded once at the start of :meth:`decode`, a slice's cut is one
+        vam_rans_decode_device launch on the runner's stream, and the status codes are read once after g_s."""
         assert not (per_image or quality_map) or not (base_only or rem_idx is not None)
         assert not (per_image and quality_map)
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
+        self.coder, self.up, self.up_at = coder, None, 0
         self.per_image, self.quality_map = per_image, quality_map
         self.qtable = _mask_table_buffer(B, device) if per_image or quality_map else None
         self.level_map = torch.zeros((B, 16 * hz * wz), dtype=torch.uint8, device=device) if quality_map else None
@@ -1020,6 +1024,10 @@ class _DecPlan:
     def _decode_slice(self, strings, idx_view: ops.IView, sym_view: ops.IView, tables, C):
         """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window)."""
         from . import bitstream as bs
+        if self.coder == "device":       # the B strings of this slice are the next B uploaded ones: one launch, no round trip
+            bs.decode_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, bs.DeviceCoderTables.of(self.m.gaussian_conditional, self.device))
+            self.up_at += self.B
+            return
         B, h, w = self.B, idx_view.buf.shape[1], idx_view.buf.shape[2]
         self.runner.stream.synchronize()
         idx = idx_view.buf[..., idx_view.c0:idx_view.c0 + C].cpu().numpy()          # [B,h,w,C]
@@ -1034,10 +1042,14 @@ class _DecPlan:
         stream."""
         from . import bitstream as bs
         m = self.m
-        zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
-        zs = np.stack([bs.decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
-                       for b in range(self.B)])
-        self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
+        if self.coder == "device":       # z: the first B uploaded strings, table index = channel
+            bs.decode_uploaded(self.up, 0, None, self.z_sym, 1, m.N, bs.DeviceCoderTables.of(m.entropy_bottleneck, self.device))
+            self.up_at = self.B
+        else:
+            zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
+            zs = np.stack([bs.decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
+                           for b in range(self.B)])
+            self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
         self.p_hyper.run()
         self._run_slices(self.p_base, y_strings, self.idx_b, self.sym_b, tg)
 
@@ -1069,14 +1081,23 @@ class _DecPlan:
         if len(y_strings) < n_need or len(z_strings) != self.B:
             raise ValueError(f"expected {n_need} slice streams x {self.B} images, got {len(y_strings)} x {len(z_strings)}")
         tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
+        if self.coder == "device" and any(len(row) != self.B for row in y_strings[:n_need]):
+            raise ValueError(f"expected {self.B} strings per slice")
         with self.runner.on_stream():
+            if self.coder == "device":   # one upload: z first, then the slices in decoding order
+                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings[:n_need] for s_ in row], self.device)
             if checkpoint_rep is not None:
                 _load_checkpoint(self.ck, checkpoint_rep)
             self._decode_base(y_strings, z_strings, tg, te)
             if not self.base_only:
                 self._run_slices(self.p_prog, y_strings[m.ns0:], self.idx_p, self.sym_p, tg)
             self.p_syn.run()
-        return self.x_hat.clone()
+        x_hat = self.x_hat.clone()
+        if self.coder == "device":       # the one read of the status codes: string k is z of image k, then slice-major
+            up, self.up, B = self.up, None, self.B
+            bs.check_status(up, B, "decompress", lambda k: f"z stream (image {k})" if k < B else
+                            f"stream (image {k % B}, slice {k // B - 1})")
+        return x_hat
 
     def close(self):
         self.runner.close()

@@ -739,6 +739,66 @@ int vam_rans_prefix_bytes(const uint8_t* in_host, long n_bytes, const int32_t* i
                           int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
                           const long* counts, int n_counts, long* bytes_out);
 
+/* ------------------------------------------------------------------ device rANS coder */
+/* The coder above restated as one core for host and device (csrc/rans_core.h): the same wire format, so host-coded and
+ * device-coded streams are interchangeable byte for byte.
+ * vam_rans_core_encode / _decode (HOST pointers): vam_rans_encode / vam_rans_decode through the core, plus the layer
+ * selection of vam_rans_stream.  encode returns the length in bytes (< 0 on error); decode returns 0, a positive
+ * per-stream status (1 bitstream truncated, 2 index out of range, 3 cdf size invalid, 6 stream shorter than 8 bytes or
+ * not in whole words) or VAM_EINVAL for bad arguments.  It never reads outside the stream; after a failure every
+ * remaining selected symbol is written as 0.
+ * The _nhwc variants code one image's channel window of an int32 buffer [.., h, w, ld] in place: stream element
+ * (c * h + y) * w + x reads buf[((image * h + y) * w + x) * ld + c0 + c], the [C, h, w] order the flat calls get after a
+ * transpose.  idx == NULL means "table index = channel c" (the z streams).  layer, when given, has the geometry of sym. */
+long vam_rans_core_encode(const int32_t* symbols_host, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                          int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                          uint8_t* out_host, long out_capacity, const uint8_t* layer_host, int sel);
+int vam_rans_core_decode(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                         int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                         int32_t* symbols_out_host, const uint8_t* layer_host, int sel);
+long vam_rans_core_encode_nhwc(const int32_t* sym_host, const int32_t* idx_host, const uint8_t* layer_host, int sel, int image,
+                               int h, int w, int ld, int c0, int C, const int32_t* cdfs_host, int cdf_stride,
+                               const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, uint8_t* out_host,
+                               long out_capacity);
+int vam_rans_core_decode_nhwc(const uint8_t* in_host, long n_bytes, const int32_t* idx_host, const uint8_t* layer_host, int sel,
+                              int image, int h, int w, int ld, int c0, int C, const int32_t* cdfs_host, int cdf_stride,
+                              const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int32_t* sym_out_host);
+
+/* The coder's tables on the device (bitstream.DeviceCoderTables).  packed (may be NULL): the tables ragged as 16-bit
+ * values for the decoder's LDS copy — table k is its entries 0 .. sizes[k]-2 at packed_start[k], the terminal 65536
+ * implied; packed_entries is the total, padded to a multiple of 8.  Only tables that start at 0, increase strictly and
+ * end at 65536 may be packed.  Without it the decoder reads the int32 tables from global memory. */
+typedef struct vam_rans_tables {
+  const int32_t* cdf;          /* [n_cdfs][stride] */
+  const int32_t* sizes;        /* [n_cdfs] */
+  const int32_t* offsets;      /* [n_cdfs] */
+  int32_t n_cdfs, stride;
+  const uint16_t* packed;
+  const int32_t* packed_start; /* [n_cdfs] */
+  int32_t packed_entries, pad_;
+} vam_rans_tables;
+/* The LDS bytes a workgroup may use on the current device: packed tables above it do not fit. */
+int vam_rans_lds_table_bytes(void);
+
+/* DEVICE pointers from here.  A stream is an (image, slice) pair: slice s covers the channels [c0 + s*C, c0 + (s+1)*C)
+ * of the int32 NHWC buffers [B, h, w, ld], element order as in the _nhwc calls above; stream id = s * B + image.
+ * vam_rans_encode_device: one launch codes all B * n_slices streams.  Stream id's words are written backwards from the
+ * end of its region out_words + id * out_cap_words (2 * C*h*w + 16 words is the host coder's budget); lengths[id] = its
+ * length in words, the stream being the region's tail, and status[id] = 0 or a status as above (4 output region too
+ * small, 5 zero-frequency symbol; the length is then 0).
+ * vam_rans_pack_device: offsets[id] = lengths[0] + .. + lengths[id-1] (offsets[n_streams] = the total) and every stream's
+ * words copied to packed + offsets[id], so the host fetches the lengths and the coded bytes only.
+ * vam_rans_decode_device: stream id is the byte_lengths[id] bytes at bytes + byte_offsets[id] (offsets are multiples of
+ * 4); its symbols go straight into the window of sym_out, status[id] as above.  No read leaves a stream's bytes. */
+int vam_rans_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld,
+                           int c0, int C, int n_slices, const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words,
+                           int32_t* lengths, int32_t* status, void* stream);
+int vam_rans_pack_device(const uint32_t* regions, long cap_words, const int32_t* lengths, int n_streams, uint32_t* packed,
+                         long packed_cap_words, int64_t* offsets, void* stream);
+int vam_rans_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                           const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
+                           const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
 int vam_graph_end(void* stream, void** graph_exec_out);
