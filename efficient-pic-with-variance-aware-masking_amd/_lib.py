@@ -42,6 +42,7 @@ VAM_MAX_MASK_LEVELS = 8         # include/vampic.h: levels of one vam_variance_m
 VAM_MAX_TAIL_GROUP = 8
 VAM_MAX_LAYER_LEVELS = 32       # include/vampic.h: qualities of one vam_variance_layers launch
 VAM_RANS_MAX_THREADS = 16       # include/vampic.h: host threads of one vam_rans_*_streams call
+VAM_RANS_MAX_LANES = 64         # include/vampic.h: lanes of a lane-split stream (a power of two in 1 .. 64)
 LAYER_NONE = 0xFF               # vam_variance_layers: the element is in no layer
 VAM_MAX_RANK_ELEMENTS = 1 << 18  # include/vampic.h: the largest segment vam_variance_rank sorts
 
@@ -259,6 +260,18 @@ _SIGNATURES = {
                                          C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_rans_pack_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),
     "vam_rans_decode_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.POINTER(VamRansTables), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vam_rans_lanes_encode": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vam_rans_lanes_decode": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vam_rans_lanes_encode_nhwc": (C.c_long, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
+    "vam_rans_lanes_decode_nhwc": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_rans_lanes_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.POINTER(VamRansTables), C.c_void_p,
+                                               C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vam_rans_lanes_decode_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 9 + [C.POINTER(VamRansTables), C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     "vam_variance_rank_workspace": (C.c_size_t, [C.c_int] * 4),
     "vam_variance_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

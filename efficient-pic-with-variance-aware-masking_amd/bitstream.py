@@ -67,6 +67,56 @@ def decode(stream: bytes, indexes: np.ndarray, t: Tables) -> np.ndarray:
     return out
 
 
+# ---------------------------------------------------------------- lane-split streams
+def check_lanes(lanes) -> int:
+    """``lanes`` as an int: a power of two in 1 .. 64, anything else is a ValueError."""
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or not 1 <= lanes <= L.VAM_RANS_MAX_LANES \
+            or lanes & (lanes - 1):
+        raise ValueError(f"lanes is a power of two in 1 .. {L.VAM_RANS_MAX_LANES}, got {lanes!r}")
+    return int(lanes)
+
+
+def lanes_capacity(n: int, lanes: int) -> int:
+    """Bytes that hold any lane-split string of n elements: the header and 8 m + 64 bytes per lane of m = ceil(n / K)."""
+    return 4 * lanes + lanes * (8 * (-(-n // lanes)) + 64)
+
+
+def encode_lanes(symbols: np.ndarray, indexes: np.ndarray, t: Tables, lanes: int, layer=None, sel: int = 0) -> bytes:
+    """One stream as ``lanes`` = K independent lanes (vam_rans_lanes_encode): K uint32 lane lengths in words, then lane j =
+    :func:`encode` of the elements j, j + K, ...  K = 1 is :func:`encode`'s string, with no header.  K is not stored in
+    the string: the decoder must be given the same value, like the quality and the shape."""
+    K = check_lanes(lanes)
+    s, i, ly = _i32(symbols), _i32(indexes), _layer(layer)
+    assert s.size == i.size and (ly is None or ly.size == s.size)
+    buf = np.empty(lanes_capacity(s.size, K), dtype=np.uint8)
+    n = L.load().vam_rans_lanes_encode(s.ctypes.data, i.ctypes.data, s.size, t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                       t.offsets.ctypes.data, t.cdf.shape[0], buf.ctypes.data, buf.size,
+                                       ly.ctypes.data if ly is not None else None, int(sel), K, None)
+    if n < 0:
+        L.check(int(n), "vam_rans_lanes_encode")
+    return buf[:n].tobytes()
+
+
+def decode_lanes(stream: bytes, indexes: np.ndarray, t: Tables, lanes: int, layer=None, sel: int = 0, out=None) -> np.ndarray:
+    """The symbols of a string of :func:`encode_lanes` with the same ``lanes`` (a wrong value gives a VamError or wrong
+    symbols: it is not stored).  VamError names the lowest-numbered failing lane.  With a layer array only
+    out[layer == sel] is written (``out``: an int32 array of the indexes' size, zeros when not given)."""
+    K = check_lanes(lanes)
+    i, ly = _i32(indexes), _layer(layer)
+    out = np.zeros(i.size, dtype=np.int32) if out is None else out
+    assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == i.size and (ly is None or ly.size == i.size)
+    src = np.frombuffer(stream, dtype=np.uint8)
+    status = np.zeros(K, dtype=np.int32)
+    st = L.load().vam_rans_lanes_decode(src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size, t.cdf.ctypes.data,
+                                        t.cdf.shape[1], t.sizes.ctypes.data, t.offsets.ctypes.data, t.cdf.shape[0], out.ctypes.data,
+                                        ly.ctypes.data if ly is not None else None, int(sel), K, status.ctypes.data)
+    if st < 0:
+        L.check(int(st), "vam_rans_lanes_decode")
+    if st:
+        raise L.VamError(f"vam_rans_lanes_decode: lane {int(np.flatnonzero(status)[0])}: {status_text(int(st), K)}")
+    return out
+
+
 def coder_threads(requested: Optional[int] = None) -> int:
     """Host threads for the stream coder: at most L.VAM_RANS_MAX_THREADS and the CPUs this process may run on."""
     n = min(L.VAM_RANS_MAX_THREADS, len(os.sched_getaffinity(0)))
@@ -265,6 +315,13 @@ STATUS_TEXT = {1: "bitstream truncated", 2: "index out of range", 3: "cdf size i
                6: "bad arguments (a stream is at least 8 bytes, in whole words)"}
 
 
+def status_text(st: int, lanes: int = 1) -> str:
+    """The words for a status code; for a lane-split string code 6 is the header check's refusal."""
+    if st == 6 and lanes > 1:
+        return f"bad stream (the header of {lanes} lane lengths does not match the string)"
+    return STATUS_TEXT.get(st, f"status {st}")
+
+
 def pack_tables(t: Tables):
     """The tables ragged as 16-bit values for the decoder's LDS copy: table k is its entries 0 .. sizes[k]-2 at starts[k],
     the terminal 65536 implied; the total is padded to a multiple of 8 entries (16-byte loads).  None when a table does
@@ -345,23 +402,32 @@ def _geometry(sym_view, idx_view, n_slices: int, C_: int, layer):
     return B, h, w, ld
 
 
-def raise_status(status: np.ndarray, B: int, what: str):
-    """VamError for the first stream with a non-zero status; stream id = slice * B + image."""
+def raise_status(status: np.ndarray, B: int, what: str, lanes: int = 1):
+    """VamError for the first stream with a non-zero status; stream id = slice * B + image.  ``lanes`` > 1: one code per
+    (stream, lane), and the message names the stream's lowest-numbered failing lane too."""
     bad = np.flatnonzero(status)
     if bad.size:
-        k, st = int(bad[0]), int(status[bad[0]])
-        raise L.VamError(f"{what}: stream (image {k % B}, slice {k // B}): {STATUS_TEXT.get(st, f'status {st}')}"
-                         + (f" ({bad.size} streams failed)" if bad.size > 1 else ""))
+        k, st = int(bad[0]) // lanes, int(status[bad[0]])
+        n_bad = np.unique(bad // lanes).size
+        raise L.VamError(f"{what}: stream (image {k % B}, slice {k // B})" + (f", lane {int(bad[0]) % lanes}" if lanes > 1 else "")
+                         + f": {status_text(st, lanes)}" + (f" ({n_bad} streams failed)" if n_bad > 1 else ""))
 
 
 def encode_streams_device(sym_view, idx_view, n_slices: int, C_: int, tables: DeviceCoderTables, layer=None,
-                          sel: int = 0) -> List[List[bytes]]:
+                          sel: int = 0, lanes: int = 1, lane_kernels: Optional[bool] = None) -> List[List[bytes]]:
     """All B * n_slices streams of an int32 NHWC window in one vam_rans_encode_device launch on the current stream, packed by
     vam_rans_pack_device, then two device-to-host copies: the lengths with the status codes, and the coded bytes.
     ``idx_view`` None: table index = channel (the z streams).  Returns ``[slice][image]``; each stream's bytes equal
-    :func:`encode`'s on the window's [C, h, w] transpose."""
+    :func:`encode`'s on the window's [C, h, w] transpose.
+
+    ``lanes`` = K > 1: one vam_rans_lanes_encode_device launch, one thread per (stream, lane), packed
+    over the K * B * n_slices lane regions; each string equals :func:`encode_lanes`'s.  K is not stored in the strings.
+    ``lane_kernels``: run the per-lane kernel also at K = 1 (the same bytes; None: only for K > 1)."""
     from . import ops
+    K = check_lanes(lanes)
     B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
+    if K > 1 if lane_kernels is None else lane_kernels:
+        return _encode_lanes_device(sym_view, idx_view, n_slices, C_, tables, layer, sel, K, B, h, w, ld)
     ns, cap = B * n_slices, 2 * C_ * h * w + 16            # 8 n + 64 bytes per stream, the host coder's budget
     dev = sym_view.buf.device
     regions = torch.empty(ns * cap, dtype=torch.int32, device=dev)
@@ -382,13 +448,41 @@ def encode_streams_device(sym_view, idx_view, n_slices: int, C_: int, tables: De
     return [[data[off[s * B + b]:off[s * B + b + 1]].tobytes() for b in range(B)] for s in range(n_slices)]
 
 
+def _encode_lanes_device(sym_view, idx_view, n_slices, C_, tables, layer, sel, K, B, h, w, ld) -> List[List[bytes]]:
+    """encode_streams_device with one thread per (stream, lane): the pack over the lane regions leaves every stream's lanes
+    back to back, and the lengths it scanned are the headers."""
+    from . import ops
+    n = C_ * h * w
+    ns, cap = B * n_slices, 2 * (-(-n // K)) + 16          # 8 m + 64 bytes per lane of m = ceil(n / K) elements
+    dev = sym_view.buf.device
+    regions = torch.empty(ns * K * cap, dtype=torch.int32, device=dev)
+    packed = torch.empty(ns * K * cap, dtype=torch.int32, device=dev)
+    meta = torch.empty((2, ns * K), dtype=torch.int32, device=dev)      # per (stream, lane): length in words, status
+    offs = torch.empty(ns * K + 1, dtype=torch.int64, device=dev)
+    lib, st = L.load(), ops.stream_ptr()
+    L.check(lib.vam_rans_lanes_encode_device(sym_view.buf.data_ptr(), idx_view.buf.data_ptr() if idx_view is not None else None,
+                                             layer.data_ptr() if layer is not None else None, int(sel), B, h, w, ld, sym_view.c0,
+                                             C_, n_slices, K, C.byref(tables.struct), regions.data_ptr(), cap, meta[0].data_ptr(),
+                                             meta[1].data_ptr(), st), "vam_rans_lanes_encode_device")
+    L.check(lib.vam_rans_pack_device(regions.data_ptr(), cap, meta[0].data_ptr(), ns * K, packed.data_ptr(), ns * K * cap,
+                                     offs.data_ptr(), st), "vam_rans_pack_device")
+    m = meta.cpu().numpy()
+    raise_status(m[1], B, "vam_rans_lanes_encode_device", K)
+    lens = m[0].reshape(ns, K)
+    off = np.concatenate([[0], np.cumsum(lens.sum(1).astype(np.int64))]) * 4      # the streams' bodies, back to back
+    data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
+    head = (lambda k: b"") if K == 1 else (lambda k: lens[k].astype("<u4").tobytes())
+    return [[head(s * B + b) + data[off[s * B + b]:off[s * B + b + 1]].tobytes() for b in range(B)] for s in range(n_slices)]
+
+
 @dataclass
 class DeviceStreams:
     """Byte strings on the device: one uint8 buffer [offsets int64 | lengths int32 | the strings, each at a multiple of 4],
-    uploaded in one host-to-device copy; ``status`` receives one code per string."""
+    uploaded in one host-to-device copy; ``status`` receives one code per (string, lane)."""
     buf: torch.Tensor
     n: int
-    status: torch.Tensor       # int32 [n]
+    status: torch.Tensor       # int32 [n * lanes]
+    lanes: int = 1
 
     @property
     def offsets_ptr(self): return self.buf.data_ptr()
@@ -398,7 +492,8 @@ class DeviceStreams:
     def bytes_ptr(self): return self.buf.data_ptr() + 8 * self.n + 4 * (self.n + self.n % 2)
 
 
-def upload_streams(strings: Sequence[bytes], device) -> DeviceStreams:
+def upload_streams(strings: Sequence[bytes], device, lanes: int = 1) -> DeviceStreams:
+    lanes = check_lanes(lanes)
     n = len(strings)
     lens = np.array([len(s_) for s_ in strings], dtype=np.int64)
     off = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
@@ -408,17 +503,31 @@ def upload_streams(strings: Sequence[bytes], device) -> DeviceStreams:
     host[8 * n:8 * n + 4 * n].view(np.int32)[:] = lens
     for k, s_ in enumerate(strings):
         host[head + off[k]:head + off[k] + lens[k]] = np.frombuffer(s_, dtype=np.uint8)
-    return DeviceStreams(torch.from_numpy(host).to(device), n, torch.zeros(max(n, 1), dtype=torch.int32, device=device))
+    return DeviceStreams(torch.from_numpy(host).to(device), n, torch.zeros(max(n, 1) * lanes, dtype=torch.int32, device=device), lanes)
 
 
 def decode_uploaded(up: DeviceStreams, first: int, idx_view, sym_view, n_slices: int, C_: int, tables: DeviceCoderTables,
-                    layer=None, sel: int = 0):
+                    layer=None, sel: int = 0, lanes: int = 1, lane_kernels: Optional[bool] = None):
     """One vam_rans_decode_device launch on the current stream: the B * n_slices strings of ``up`` from ``first`` on
-    (string first + slice * B + image) into the window of ``sym_view``.  No synchronisation."""
+    (string first + slice * B + image) into the window of ``sym_view``.  No synchronisation.  ``lanes`` = K > 1: the
+    strings are lane-split (:func:`encode_lanes`) and ``up`` was uploaded with the same K; one
+    vam_rans_lanes_decode_device launch, one thread and one status code per (string, lane).  ``lane_kernels``: run the
+    per-lane kernel also at K = 1 (None: only for K > 1)."""
     from . import ops
+    K = check_lanes(lanes)
     B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
     if first < 0 or first + B * n_slices > up.n:
         raise ValueError(f"device coder: strings {first} .. {first + B * n_slices} of {up.n} uploaded")
+    if K != up.lanes:
+        raise ValueError(f"device coder: strings uploaded for {up.lanes} lanes, decode asked for {K}")
+    if K > 1 if lane_kernels is None else lane_kernels:
+        L.check(L.load().vam_rans_lanes_decode_device(up.bytes_ptr, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                                      idx_view.buf.data_ptr() if idx_view is not None else None,
+                                                      layer.data_ptr() if layer is not None else None, int(sel), B, h, w, ld,
+                                                      sym_view.c0, C_, n_slices, K, C.byref(tables.struct), sym_view.buf.data_ptr(),
+                                                      up.status.data_ptr() + 4 * first * K, ops.stream_ptr()),
+                "vam_rans_lanes_decode_device")
+        return
     L.check(L.load().vam_rans_decode_device(up.bytes_ptr, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
                                             idx_view.buf.data_ptr() if idx_view is not None else None,
                                             layer.data_ptr() if layer is not None else None, int(sel), B, h, w, ld, sym_view.c0, C_,
@@ -427,27 +536,34 @@ def decode_uploaded(up: DeviceStreams, first: int, idx_view, sym_view, n_slices:
 
 
 def decode_streams_device(strings: Sequence[Sequence[bytes]], idx_view, sym_view, n_slices: int, C_: int,
-                          tables: DeviceCoderTables, layer=None, sel: int = 0) -> DeviceStreams:
+                          tables: DeviceCoderTables, layer=None, sel: int = 0, lanes: int = 1,
+                          lane_kernels: Optional[bool] = None) -> DeviceStreams:
     """``strings[slice][image]`` uploaded in one host-to-device copy and decoded by one launch into the window of
-    ``sym_view``, on the current stream.  Returns without synchronising; :func:`check_status` reads the codes later."""
+    ``sym_view``, on the current stream.  Returns without synchronising; :func:`check_status` reads the codes later.
+    ``lanes`` / ``lane_kernels``: as in :func:`decode_uploaded`."""
     B = int(sym_view.buf.shape[0])
     if len(strings) != n_slices or any(len(row) != B for row in strings):
         raise ValueError(f"device coder: expected {n_slices} slices x {B} images of strings")
-    up = upload_streams([s_ for row in strings for s_ in row], sym_view.buf.device)
-    decode_uploaded(up, 0, idx_view, sym_view, n_slices, C_, tables, layer, sel)
+    up = upload_streams([s_ for row in strings for s_ in row], sym_view.buf.device, lanes)
+    decode_uploaded(up, 0, idx_view, sym_view, n_slices, C_, tables, layer, sel, lanes, lane_kernels)
     return up
 
 
-def check_status(up: DeviceStreams, B: int, what: str = "vam_rans_decode_device", name=None):
-    """Reads the status codes of ``up`` (synchronises) and raises VamError naming the first failed stream.  ``name(k)``
-    words string k; the default is stream id = slice * B + image."""
-    st = up.status[:up.n].cpu().numpy()
+def check_status(up: DeviceStreams, B: int, what: str = "vam_rans_decode_device", name=None, lanes: Optional[int] = None):
+    """Reads the status codes of ``up`` (synchronises) and raises VamError naming the first failed stream, and with
+    ``lanes`` > 1 (None: what ``up`` was uploaded for) its lowest-numbered failing lane.  ``name(k)`` words string k; the
+    default is stream id = slice * B + image."""
+    K = up.lanes if lanes is None else check_lanes(lanes)
+    if K != up.lanes:
+        raise ValueError(f"device coder: strings uploaded for {up.lanes} lanes, status asked for {K}")
+    st = up.status[:up.n * K].cpu().numpy()
     if name is None:
-        return raise_status(st, B, what)
+        return raise_status(st, B, what, K)
     bad = np.flatnonzero(st)
     if bad.size:
         k = int(bad[0])
-        raise L.VamError(f"{what}: {name(k)}: {STATUS_TEXT.get(int(st[k]), f'status {int(st[k])}')}")
+        raise L.VamError(f"{what}: {name(k // K)}" + (f", lane {k % K}" if K > 1 else "")
+                         + f": {status_text(int(st[k]), K)}")
 
 
 def sigma0_index(scale_table) -> int:

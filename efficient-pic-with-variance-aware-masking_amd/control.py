@@ -233,13 +233,19 @@ def forward_qualities_per_image(model, x, Q, mask_pol=None):
     return _swept(model, x, rows, mask_pol, per_image=True)
 
 
+def _encode_jobs(jobs, t, lanes: int):
+    """The host coder's strings of (symbols, indexes) jobs: the threaded stream coder, or lane-split strings one by one."""
+    from . import bitstream as bs
+    return bs.encode_streams(jobs, t) if lanes == 1 else [bs.encode_lanes(s_, i_, t, lanes) for s_, i_ in jobs]
+
+
 def compress_per_image(model, x, qualities, mask_pol=None):
     from . import bitstream as bs
     qs = _quality_vector(x, qualities, "compress_per_image", allow_zero=True)
     if not model._batch_shareable():
         outs = ((q, model.compress(x[b:b + 1], q, mask_pol)) for b, q in enumerate(qs))
         return [{"strings": out["strings"], "shape": out["shape"], "quality": q} for q, out in outs]
-    coder = model._coder()
+    coder, lanes = model._coder(), model._coder_lanes()
     mask_pol = _prepare(model, x, mask_pol, "compress", need_tables=True)
     tg, te = bs.Tables.of(model.gaussian_conditional), bs.Tables.of(model.entropy_bottleneck)
     C = model.dim_chunk
@@ -255,7 +261,7 @@ def compress_per_image(model, x, qualities, mask_pol=None):
                 plan.execute_per_image(xb, _mask_qualities(mask_pol, [qs[b] for b in sub]), model.use_graph, False)
             n_sl = model.ns0 if base_only else model.ns1
             if coder == "device":                       # one launch per sub-batch for y, one for z
-                y_dev, z_dev = model._encode_plan_device(plan, n_sl)
+                y_dev, z_dev = model._encode_plan_device(plan, n_sl, lanes)
                 for k, b in enumerate(sub):
                     ys += [y_dev[s_][k] for s_ in range(n_sl)]
                     zstr.append(z_dev[k])
@@ -272,7 +278,7 @@ def compress_per_image(model, x, qualities, mask_pol=None):
                 z_jobs.append((zs[k].transpose(2, 0, 1), zi))
                 where.append((b, n_sl))
     if coder == "host":
-        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+        ys, zstr = _encode_jobs(y_jobs, tg, lanes), _encode_jobs(z_jobs, te, lanes)
     items: List[Optional[dict]] = [None] * len(qs)
     shape = (x.shape[2] // 64, x.shape[3] // 64)
     o = 0
@@ -292,7 +298,7 @@ def decompress_per_image(model, items, mask_pol=None):
     qs = [float(it["quality"]) for it in items]
     if any(not q >= 0 for q in qs):
         raise ValueError("decompress_per_image: qualities must be >= 0 (and not NaN)")
-    coder = model._coder()
+    coder, lanes = model._coder(), model._coder_lanes()
     if not model._batch_shareable():
         return {"x_hat": torch.cat([model.decompress(it["strings"], shape, q, mask_pol)["x_hat"] for it, q in zip(items, qs)], 0)}
     mask_pol = _prepare(model, None, mask_pol)
@@ -315,7 +321,7 @@ def decompress_per_image(model, items, mask_pol=None):
             return _DecPlan(model, B, hz, wz, False, None, dev, per_image=True, coder=coder)
         dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "per_image")
                                 + ((coder,) if coder != "host" else ()), build, model._weights_sig())
-        x_hat[sub] = dp.decode(strings, _mask_qualities(mask_pol, [qs[b] for b in sub]), None)
+        x_hat[sub] = dp.decode(strings, _mask_qualities(mask_pol, [qs[b] for b in sub]), None, lanes=lanes)
     return {"x_hat": x_hat}
 
 
@@ -672,7 +678,7 @@ def forward_quality_map(model, x, qmap, mask_pol=None):
 
 def compress_quality_map(model, x, qmap, mask_pol=None):
     from . import bitstream as bs
-    coder = model._coder()
+    coder, lanes = model._coder(), model._coder_lanes()
     mask_pol, levels, index = _map_prepare(model, x, qmap, mask_pol, "compress", need_tables=True)
     tg, te = bs.Tables.of(model.gaussian_conditional), bs.Tables.of(model.entropy_bottleneck)
     C, n_sl, nb = model.dim_chunk, model.ns1, M._max_images_per_plan(x)
@@ -684,7 +690,7 @@ def compress_quality_map(model, x, qmap, mask_pol=None):
             plan = model._plan(xb, base_only=False, symbols=True, quality_map=True)
             plan.execute_quality_map(xb, levels[i:i + nb], index[i:i + nb], model.use_graph, False)
             if coder == "device":                       # one launch per sub-batch for y, one for z
-                y_dev, z_dev = model._encode_plan_device(plan, n_sl)
+                y_dev, z_dev = model._encode_plan_device(plan, n_sl, lanes)
                 for k in range(xb.shape[0]):
                     ys += [y_dev[s_][k] for s_ in range(n_sl)]
                     zstr.append(z_dev[k])
@@ -699,7 +705,7 @@ def compress_quality_map(model, x, qmap, mask_pol=None):
                     y_jobs.append((sym[k, :, :, ch].transpose(2, 0, 1), idx[k, :, :, ch].transpose(2, 0, 1)))
                 z_jobs.append((zs[k].transpose(2, 0, 1), zi))
     if coder == "host":
-        ys, zstr = bs.encode_streams(y_jobs, tg), bs.encode_streams(z_jobs, te)
+        ys, zstr = _encode_jobs(y_jobs, tg, lanes), _encode_jobs(z_jobs, te, lanes)
     shape = (x.shape[2] // 64, x.shape[3] // 64)
     return [{"strings": [[[s_] for s_ in ys[b * n_sl:(b + 1) * n_sl]], [zstr[b]]], "shape": shape,
              "quality_map": {"levels": [float(q) for q in levels[b]], "index": index[b].copy()},
@@ -733,7 +739,7 @@ def decompress_quality_map(model, items, mask_pol=None):
         raise ValueError("decompress_quality_map: all items must have the same shape; decode other shapes in a call of their own")
     hz, wz = shape
     maps = [_item_map(it, b, 4 * hz, 4 * wz) for b, it in enumerate(items)]
-    coder = model._coder()
+    coder, lanes = model._coder(), model._coder_lanes()
     _map_refuse(model)
     _prepare(model, None, mask_pol)
     dev = model.entropy_bottleneck.quantiles.device
@@ -753,7 +759,8 @@ def decompress_quality_map(model, items, mask_pol=None):
             return _DecPlan(model, B, hz, wz, False, None, dev, quality_map=True, coder=coder)
         dp = model._cached_plan(model._dec_plans, (len(sub), hz, wz, False, None, str(dev), "quality_map")
                                 + ((coder,) if coder != "host" else ()), build, model._weights_sig())
-        x_hat[sub] = dp.decode(strings, None, None, quality_map=([maps[b][0] for b in sub], np.stack([maps[b][1] for b in sub])))
+        x_hat[sub] = dp.decode(strings, None, None, quality_map=([maps[b][0] for b in sub], np.stack([maps[b][1] for b in sub])),
+                               lanes=lanes)
     return {"x_hat": x_hat}
 
 

@@ -6,7 +6,9 @@
 // Layers:   steps     enc_put / enc_put_bits / enc_element, dec_init / dec_bits / dec_element: one symbol's state update;
 //                     the device kernels (rans_device.hip) call these between their parallel staging phases
 //           streams   encode_stream / decode_stream: one whole stream on one thread (host exports, sanitizer program)
-// Addressing goes through a functor (Flat, Nhwc), the symbol search through another (CdfSearch here, the wave-wide
+//           lanes     a stream as K independent lanes, each a stream of its own: the header check,
+//                     lane_encode / lane_decode for one thread per lane, lanes_*_stream for all lanes on one thread
+// Addressing goes through a functor (Flat, Nhwc), the symbol search through another (TableSearch here, the wave-wide
 // search of rans_device.hip), so the steps never see a pointer they could walk off.
 #pragma once
 #include <cstdint>
@@ -242,32 +244,44 @@ VAM_RANS_HD int32_t dec_element(Dec& d, const F& find, int sz) {
   return (int32_t)((raw & 1) ? ~half : half + (uint32_t)max_value);
 }
 
-// The host's linear scan as a binary search over an int32 table: entries 1 .. sz-1 are increasing on every table the
-// coder accepts, so the count of entries <= cum is the scan's stopping point.
-struct CdfSearch {
-  const int32_t* cdf;
+// The host's linear scan as a binary search: entries 1 .. sz-1 are increasing on every table the coder accepts, so the
+// count of entries <= cum is the scan's stopping point.  E = int32_t reads a row of the [n_cdfs][stride] tables;
+// E = uint16_t with implied_last reads a packed table, whose entry sz-1 is not stored: it is 65536, above every cum.
+template <class E>
+struct TableSearch {
+  const E* cdf;
   int sz;
+  bool implied_last;
   VAM_RANS_HD int operator()(uint32_t cum, uint32_t& start, uint32_t& freq) const {
-    int lo = 0, hi = sz - 1;                      // s in [lo, hi]: cdf[1 .. lo] <= cum
+    int lo = 0, hi = implied_last ? sz - 2 : sz - 1;  // s in [lo, hi]: cdf[1 .. lo] <= cum
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
       if ((uint32_t)cdf[mid] <= cum) lo = mid; else hi = mid - 1;
     }
     if (lo > sz - 2) lo = sz - 2;                 // only on a table without its terminal 65536: stay inside it
     start = (uint32_t)cdf[lo];
-    freq = (uint32_t)cdf[lo + 1] - start;
+    freq = (implied_last && lo == sz - 2 ? (1u << kPrecision) : (uint32_t)cdf[lo + 1]) - start;
     return lo;
   }
 };
 
-// One stream on one thread; idx == NULL means "index = channel".  Only elements with layer[i] == sel are written.
-// After a failure every remaining selected element is written as 0.
-template <class A>
-VAM_RANS_HD int32_t decode_stream(const uint32_t* words, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel,
-                                  long n, const A& at, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
-                                  const int32_t* offsets, int n_cdfs, int32_t* out) {
-  Dec d;
-  dec_init(d, words, n_bytes);
+// Where table ci lives: the int32 rows, or the packed 16-bit tables at their start offsets (rans_device.hip's LDS copy).
+struct Int32Rows {
+  const int32_t* cdfs;
+  int stride;
+  VAM_RANS_HD TableSearch<int32_t> operator()(int ci, int sz) const { return {cdfs + (long)ci * stride, sz, false}; }
+};
+struct PackedRows {
+  const uint16_t* packed;
+  const int32_t* starts;
+  VAM_RANS_HD TableSearch<uint16_t> operator()(int ci, int sz) const { return {packed + starts[ci], sz, true}; }
+};
+
+// The n elements of a stream whose state is initialised (or refused: d.status) in d.  Only elements with layer == sel
+// are written; after a failure every remaining selected element is written as 0.
+template <class A, class T>
+VAM_RANS_HD int32_t decode_elements(Dec& d, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at, const T& rows,
+                                    int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out) {
   for (long i = 0; i < n; ++i) {
     const long o = at.off(i);
     const bool keep = !layer || layer[o] == sel;
@@ -279,7 +293,7 @@ VAM_RANS_HD int32_t decode_stream(const uint32_t* words, long n_bytes, const int
         const int sz = cdf_sizes[ci];
         if (sz - 2 < 0 || sz - 1 >= cdf_stride) d.status = kBadTable;
         else {
-          const int32_t v = dec_element(d, CdfSearch{cdfs + (long)ci * cdf_stride, sz}, sz);
+          const int32_t v = dec_element(d, rows(ci, sz), sz);
           if (!d.status) value = (int32_t)((uint32_t)v + (uint32_t)offsets[ci]);
         }
       }
@@ -287,6 +301,110 @@ VAM_RANS_HD int32_t decode_stream(const uint32_t* words, long n_bytes, const int
     if (keep) out[o] = value;
   }
   return d.status;
+}
+
+// One stream on one thread; idx == NULL means "index = channel".
+template <class A>
+VAM_RANS_HD int32_t decode_stream(const uint32_t* words, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel,
+                                  long n, const A& at, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                  const int32_t* offsets, int n_cdfs, int32_t* out) {
+  Dec d;
+  dec_init(d, words, n_bytes);
+  return decode_elements(d, idx, layer, sel, n, at, Int32Rows{cdfs, cdf_stride}, cdf_stride, cdf_sizes, offsets, n_cdfs, out);
+}
+
+// ---------------------------------------------------------------- lane-split streams
+// A stream of n elements as K independent lanes, K a power of two in 1 .. 64: lane j is the stream above of the
+// elements j, j + K, j + 2K, ...  K == 1 is that stream itself, with no header.  For K > 1 the string is K uint32 lane
+// lengths in words (each >= 2), then the lanes' words back to back: 4 K + 4 sum(L_j) bytes, exactly.  K is not stored.
+constexpr int kMaxLanes = 64;
+
+VAM_RANS_HD bool lanes_valid(int K) { return K >= 1 && K <= kMaxLanes && (K & (K - 1)) == 0; }
+VAM_RANS_HD long lane_elements(long n, int j, int K) { return n > j ? (n - j + K - 1) / K : 0; }
+// Words a lane's region needs: 8 m + 64 bytes for the m = ceil(n / K) elements of the longest lane, the host's budget.
+VAM_RANS_HD long lane_cap_words(long n, int K) { return 2 * ((n + K - 1) / K) + 16; }
+
+// Element i of lane j is element j + i K of the stream.
+template <class A>
+struct Lane {
+  A at;
+  long j, K;
+  VAM_RANS_HD long off(long i) const { return at.off(j + i * K); }
+  VAM_RANS_HD int chan(long i) const { return at.chan(j + i * K); }
+};
+
+// The header check: lane `lane` of the string is the n_words words from word `first` on.  kBadStream for a string
+// that is misaligned, not whole words or shorter than its header, for a lane shorter than a final state, and for
+// lengths that do not add up to the string's; the sums are 64-bit, so no header wraps them.  K == 1 has no header:
+// dec_init checks that string itself.
+VAM_RANS_HD int32_t lanes_header(const uint32_t* words, long n_bytes, int K, int lane, long& first, long& n_words) {
+  first = 0; n_words = 0;
+  if (!lanes_valid(K) || lane < 0 || lane >= K) return kBadStream;
+  if (K == 1) { n_words = n_bytes / 4; return kOk; }
+  if (!words || ((uintptr_t)words & 3) || n_bytes < 4l * K || (n_bytes & 3)) return kBadStream;
+  uint64_t total = (uint64_t)K, before = (uint64_t)K;
+  for (int j = 0; j < K; ++j) {
+    const uint32_t len = words[j];
+    if (len < 2) return kBadStream;
+    total += len;
+    if (j < lane) before += len;
+  }
+  if (total != (uint64_t)(n_bytes / 4)) return kBadStream;
+  first = (long)before; n_words = (long)words[lane];
+  return kOk;
+}
+
+// One lane of a string: its own state, word pointer and end.  T finds the tables (Int32Rows, PackedRows).
+template <class A, class T>
+VAM_RANS_HD int32_t lane_decode(const uint32_t* words, long n_bytes, int K, int lane, const int32_t* idx, const uint8_t* layer,
+                                int sel, long n, const A& at, const T& rows, int cdf_stride, const int32_t* cdf_sizes,
+                                const int32_t* offsets, int n_cdfs, int32_t* out) {
+  long first, n_words;
+  Dec d;
+  const int32_t st = lanes_header(words, n_bytes, K, lane, first, n_words);
+  if (st) { d.x = 0; d.p = d.end = words; d.status = st; }
+  else dec_init(d, words + first, K == 1 ? n_bytes : 4 * n_words);
+  return decode_elements(d, idx, layer, sel, lane_elements(n, lane, K), Lane<A>{at, lane, K}, rows, cdf_stride, cdf_sizes, offsets,
+                         n_cdfs, out);
+}
+
+// One lane into its own region of cap_words words (the lane is the region's tail).
+template <class A>
+VAM_RANS_HD int32_t lane_encode(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at, int K,
+                                int lane, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                int n_cdfs, uint32_t* region, long cap_words, long* n_words) {
+  return encode_stream(sym, idx, layer, sel, lane_elements(n, lane, K), Lane<A>{at, lane, K}, cdfs, cdf_stride, cdf_sizes, offsets,
+                       n_cdfs, region, cap_words, n_words);
+}
+
+// All lanes of one stream on one thread.  Lane j is coded into regions + j * cap_words; lane_words[j] and lane_status[j]
+// receive its length and status.  Returns the status of the lowest-numbered failing lane.
+template <class A>
+VAM_RANS_HD int32_t lanes_encode_stream(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at,
+                                        int K, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                        int n_cdfs, uint32_t* regions, long cap_words, long* lane_words, int32_t* lane_status) {
+  int32_t first_bad = kOk;
+  for (int j = 0; j < K; ++j) {
+    lane_status[j] = lane_encode(sym, idx, layer, sel, n, at, K, j, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                                 regions + (long)j * cap_words, cap_words, lane_words + j);
+    if (lane_status[j] && !first_bad) first_bad = lane_status[j];
+  }
+  return first_bad;
+}
+
+// A failing lane zeroes its own elements from the failure on; the other lanes are still decoded.  A refused header
+// fails every lane, so every selected element is 0.  Returns the status of the lowest-numbered failing lane.
+template <class A>
+VAM_RANS_HD int32_t lanes_decode_stream(const uint32_t* words, long n_bytes, int K, const int32_t* idx, const uint8_t* layer, int sel,
+                                        long n, const A& at, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                        const int32_t* offsets, int n_cdfs, int32_t* out, int32_t* lane_status) {
+  int32_t first_bad = kOk;
+  for (int j = 0; j < K; ++j) {
+    lane_status[j] = lane_decode(words, n_bytes, K, j, idx, layer, sel, n, at, Int32Rows{cdfs, cdf_stride}, cdf_stride, cdf_sizes,
+                                 offsets, n_cdfs, out);
+    if (lane_status[j] && !first_bad) first_bad = lane_status[j];
+  }
+  return first_bad;
 }
 
 }  // namespace vam_rans

@@ -6,6 +6,8 @@
 // at a time, one per lane.  What is serial: the state update, which every lane of the wave carries redundantly (the
 // values are wave-uniform), so a staged record is fetched with v_readlane and the decoder's symbol search is a wave-wide
 // compare (one ballot per 64 table entries) instead of a scan.  One lane stores.  Plain C++ only.
+//
+// Lane-split streams turn that around: one thread per (stream, lane), see the second half.
 #include "common.h"
 #include "rans_core.h"
 #include <cstring>
@@ -202,6 +204,86 @@ __global__ __launch_bounds__(kWave) void rans_decode_kernel(DecArgs a) {
   if (lane == 0) a.status[sid] = fail;
 }
 
+// ---------------------------------------------------------------- lane-split streams
+// One thread per (stream, lane): thread id = stream id * K + lane, so 64 / K streams share a wave and a wave is full for
+// every K.  Nothing crosses a lane: each thread runs rans_core.h's lane_encode / lane_decode on its own state, its own
+// words and its own elements (stream elements lane, lane + K, ...), and is its own writer.
+struct LaneEncArgs {
+  const int32_t* sym;
+  const int32_t* idx;
+  const uint8_t* layer;
+  int sel;
+  Geometry g;
+  int K;
+  vam_rans_tables t;
+  uint32_t* out;
+  long cap;
+  int32_t* lengths;
+  int32_t* status;
+};
+
+__global__ __launch_bounds__(kWave) void rans_lanes_encode_kernel(LaneEncArgs a) {
+  const int gid = blockIdx.x * kWave + threadIdx.x;
+  if (gid >= a.g.B * a.g.n_slices * a.K) return;
+  const int sid = gid / a.K, lane = gid - sid * a.K;
+  const int s = sid / a.g.B, b = sid - s * a.g.B;
+  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
+  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  long words = 0;
+  const int32_t st = R::lane_encode(a.sym + img, a.idx ? a.idx + img : nullptr, a.layer ? a.layer + img : nullptr, a.sel, n,
+                                    R::Nhwc{hw, a.g.ld}, a.K, lane, a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs,
+                                    a.out + (long)gid * a.cap, a.cap, &words);
+  a.lengths[gid] = st ? 0 : (int32_t)words;
+  a.status[gid] = st;
+}
+
+// 256 threads share one LDS copy of the packed tables (54 KB for the Gaussian tables: two workgroups, eight waves, per
+// CU); every thread of the workgroup copies, also those past the last lane.  The symbol search is a per-thread binary
+// search (rans_core.h's TableSearch) over the LDS copy, or over the int32 tables in global memory.
+constexpr int kLaneBlock = 256;
+
+struct LaneDecArgs {
+  const uint8_t* bytes;
+  const int64_t* byte_offsets;
+  const int32_t* byte_lengths;
+  const int32_t* idx;
+  const uint8_t* layer;
+  int sel;
+  Geometry g;
+  int K;
+  vam_rans_tables t;
+  int32_t* out;
+  int32_t* status;
+};
+
+template <bool kPacked>
+__global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecArgs a) {
+  extern __shared__ uint4 lds_raw[];
+  if (kPacked) {
+    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
+    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
+    __syncthreads();
+  }
+  const int gid = blockIdx.x * kLaneBlock + threadIdx.x;
+  if (gid >= a.g.B * a.g.n_slices * a.K) return;
+  const int sid = gid / a.K, lane = gid - sid * a.K;
+  const int s = sid / a.g.B, b = sid - s * a.g.B;
+  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
+  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  const int64_t boff = a.byte_offsets[sid];
+  const uint32_t* words = (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff);
+  const int32_t* idx = a.idx ? a.idx + img : nullptr;
+  const uint8_t* layer = a.layer ? a.layer + img : nullptr;
+  const R::Nhwc at{hw, a.g.ld};
+  if (kPacked)
+    a.status[gid] = R::lane_decode(words, a.byte_lengths[sid], a.K, lane, idx, layer, a.sel, n, at,
+                                   R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}, a.t.stride, a.t.sizes,
+                                   a.t.offsets, a.t.n_cdfs, a.out + img);
+  else
+    a.status[gid] = R::lane_decode(words, a.byte_lengths[sid], a.K, lane, idx, layer, a.sel, n, at, R::Int32Rows{a.t.cdf, a.t.stride},
+                                   a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, a.out + img);
+}
+
 int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices) {
   VAM_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && n_slices > 0 && c0 >= 0, "%s: B, h, w, C, n_slices must be > 0 and c0 >= 0", what);
   VAM_REQUIRE((long)c0 + (long)C * n_slices <= ld, "%s: window [%d, %ld) does not fit ld = %d", what, c0, (long)c0 + (long)C * n_slices, ld);
@@ -250,6 +332,51 @@ int core_decode(const uint8_t* in, long n_bytes, const int32_t* idx, const uint8
   std::vector<uint32_t> words((size_t)(n_bytes / 4));       // aligned copy of the whole words
   if (!words.empty()) std::memcpy(words.data(), in, words.size() * 4);
   return R::decode_stream(words.empty() ? nullptr : words.data(), n_bytes, idx, layer, sel, n, at, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out);
+}
+
+template <class A>
+long core_lanes_encode(const char* what, const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, long n, const A& at,
+                       int K, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs,
+                       uint8_t* out, long out_cap, int32_t* lane_status) {
+  VAM_REQUIRE(R::lanes_valid(K), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, K);
+  const long cap = R::lane_cap_words(n, K);
+  std::vector<uint32_t> regions((size_t)(cap * K));
+  long words[R::kMaxLanes];
+  int32_t status[R::kMaxLanes];
+  const int32_t st = R::lanes_encode_stream(sym, idx, layer, sel, n, at, K, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, regions.data(),
+                                            cap, words, status);
+  if (lane_status) std::memcpy(lane_status, status, sizeof(int32_t) * (size_t)K);
+  if (st) {
+    int bad = 0;
+    while (!status[bad]) ++bad;
+    VAM_REQUIRE(false, "%s: lane %d: %s", what, bad, status_text(st));
+  }
+  long total = K > 1 ? K : 0;                                // K == 1: the stream itself, no header
+  for (int j = 0; j < K; ++j) total += words[j];
+  VAM_REQUIRE(total * 4 <= out_cap, "%s: output buffer too small (%ld > %ld)", what, total * 4, out_cap);
+  uint8_t* p = out;
+  if (K > 1)
+    for (int j = 0; j < K; ++j, p += 4) {
+      const uint32_t len = (uint32_t)words[j];
+      std::memcpy(p, &len, 4);
+    }
+  for (int j = 0; j < K; p += words[j] * 4, ++j)
+    std::memcpy(p, regions.data() + (size_t)(j + 1) * cap - words[j], (size_t)words[j] * 4);
+  return total * 4;
+}
+
+template <class A>
+int core_lanes_decode(const char* what, const uint8_t* in, long n_bytes, int K, const int32_t* idx, const uint8_t* layer, int sel,
+                      long n, const A& at, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                      int n_cdfs, int32_t* out, int32_t* lane_status) {
+  VAM_REQUIRE(R::lanes_valid(K), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, K);
+  std::vector<uint32_t> words((size_t)(n_bytes / 4));       // aligned copy of the whole words
+  if (!words.empty()) std::memcpy(words.data(), in, words.size() * 4);
+  int32_t status[R::kMaxLanes];
+  const int32_t st = R::lanes_decode_stream(words.empty() ? nullptr : words.data(), n_bytes, K, idx, layer, sel, n, at, cdfs, cdf_stride,
+                                            cdf_sizes, offsets, n_cdfs, out, status);
+  if (lane_status) std::memcpy(lane_status, status, sizeof(int32_t) * (size_t)K);
+  return st;
 }
 
 }  // namespace
@@ -345,6 +472,87 @@ int vam_rans_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, co
     hipLaunchKernelGGL(rans_decode_kernel<false>, dim3(B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
   }
   return check_launch("rans_decode_kernel");
+}
+
+long vam_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                           const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap,
+                           const uint8_t* layer, int sel, int lanes, int32_t* lane_status) {
+  VAM_REQUIRE(symbols && indexes && cdfs && cdf_sizes && offsets && out && n >= 0 && n <= (1l << 28) && n_cdfs >= 1,
+              "vam_rans_lanes_encode: bad arguments");
+  return core_lanes_encode("vam_rans_lanes_encode", symbols, indexes, layer, sel, n, R::Flat{}, lanes, cdfs, cdf_stride, cdf_sizes,
+                           offsets, n_cdfs, out, out_cap, lane_status);
+}
+
+int vam_rans_lanes_decode(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                          const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int32_t* out, const uint8_t* layer, int sel,
+                          int lanes, int32_t* lane_status) {
+  VAM_REQUIRE((in || n_bytes == 0) && indexes && cdfs && cdf_sizes && offsets && out && n >= 0 && n_bytes >= 0 && n_cdfs >= 1,
+              "vam_rans_lanes_decode: bad arguments");
+  return core_lanes_decode("vam_rans_lanes_decode", in, n_bytes, lanes, indexes, layer, sel, n, R::Flat{}, cdfs, cdf_stride, cdf_sizes,
+                           offsets, n_cdfs, out, lane_status);
+}
+
+long vam_rans_lanes_encode_nhwc(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int image, int h, int w, int ld,
+                                int c0, int C, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                                int n_cdfs, uint8_t* out, long out_cap, int lanes, int32_t* lane_status) {
+  VAM_REQUIRE(sym && cdfs && cdf_sizes && offsets && out && n_cdfs >= 1 && image >= 0, "vam_rans_lanes_encode_nhwc: bad arguments");
+  if (int rc = check_geometry("vam_rans_lanes_encode_nhwc", 1, h, w, ld, c0, C, 1)) return rc;
+  const long hw = (long)h * w, img = (long)image * hw * ld + c0;
+  return core_lanes_encode("vam_rans_lanes_encode_nhwc", sym + img, idx ? idx + img : nullptr, layer ? layer + img : nullptr, sel,
+                           hw * C, R::Nhwc{hw, ld}, lanes, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out, out_cap, lane_status);
+}
+
+int vam_rans_lanes_decode_nhwc(const uint8_t* in, long n_bytes, const int32_t* idx, const uint8_t* layer, int sel, int image, int h,
+                               int w, int ld, int c0, int C, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                               const int32_t* offsets, int n_cdfs, int32_t* sym_out, int lanes, int32_t* lane_status) {
+  VAM_REQUIRE((in || n_bytes == 0) && cdfs && cdf_sizes && offsets && sym_out && n_bytes >= 0 && n_cdfs >= 1 && image >= 0,
+              "vam_rans_lanes_decode_nhwc: bad arguments");
+  if (int rc = check_geometry("vam_rans_lanes_decode_nhwc", 1, h, w, ld, c0, C, 1)) return rc;
+  const long hw = (long)h * w, img = (long)image * hw * ld + c0;
+  return core_lanes_decode("vam_rans_lanes_decode_nhwc", in, n_bytes, lanes, idx ? idx + img : nullptr, layer ? layer + img : nullptr,
+                           sel, hw * C, R::Nhwc{hw, ld}, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, sym_out + img, lane_status);
+}
+
+int vam_rans_lanes_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld,
+                                 int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                                 long out_cap_words, int32_t* lengths, int32_t* status, void* stream) {
+  VAM_REQUIRE(sym && out_words && lengths && status, "vam_rans_lanes_encode_device: need sym, out_words, lengths, status");
+  VAM_REQUIRE(R::lanes_valid(lanes), "vam_rans_lanes_encode_device: lanes is a power of two in 1 .. %d, got %d", R::kMaxLanes, lanes);
+  if (int rc = check_geometry("vam_rans_lanes_encode_device", B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables("vam_rans_lanes_encode_device", tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "vam_rans_lanes_encode_device: a region is 2 .. 2^31 words, got %ld",
+              out_cap_words);
+  LaneEncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, lanes, *tables, out_words, out_cap_words, lengths, status};
+  const int threads = B * n_slices * lanes;                 // at most 2^20 streams of 64 lanes
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_lanes_encode_kernel");
+}
+
+int vam_rans_lanes_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                                 const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices, int lanes,
+                                 const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status,
+              "vam_rans_lanes_decode_device: need bytes, offsets, lengths, sym_out, status");
+  VAM_REQUIRE(R::lanes_valid(lanes), "vam_rans_lanes_decode_device: lanes is a power of two in 1 .. %d, got %d", R::kMaxLanes, lanes);
+  if (int rc = check_geometry("vam_rans_lanes_decode_device", B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables("vam_rans_lanes_decode_device", tables)) return rc;
+  LaneDecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, lanes, *tables, sym_out, status};
+  const int blocks = (B * n_slices * lanes + kLaneBlock - 1) / kLaneBlock;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "vam_rans_lanes_decode_device: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", lds,
+                limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_lanes_decode_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(rans_lanes_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rans_lanes_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_lanes_decode_kernel");
 }
 
 }  // extern "C"

@@ -158,6 +158,11 @@ class VarianceMaskingPIC(CompressionModel):
         # "host" (default): the rANS coder of csrc/rans.cpp; "device": the same wire format coded and decoded by the kernels
         # of csrc/rans_device.hip.  Read at each compress / decompress call.
         self.coder = "host"
+        # Lanes per stream of compress / decompress and their per-image and quality-map siblings, on both coders (DESIGN
+        # section 9o): a power of two in 1 .. 64, read at each call.  1 (default) is the wire format of rans.cpp; K > 1 splits
+        # every y and z stream into K independent lanes behind a header of K lengths, about 12 K bytes more per stream.  The
+        # value is NOT stored in the strings: the decoder must be set to the encoder's, like the quality and the shape.
+        self.coder_lanes = 1
 
     # ---- reference helpers kept for the harness
     def freeze_all(self):
@@ -441,6 +446,7 @@ class VarianceMaskingPIC(CompressionModel):
         bool [B], "bytes_hi": float64 [B] (the guaranteed upper size)}.  Where ``reached``, the item's strings weigh at most
         the budget (they are the strings of compress(x[b:b+1], q_b): the guarantee of qualities_for_bytes); elsewhere the
         item is the base (quality 0)."""
+        self._refuse_lanes_for_sizes("compress_to_bytes")
         return control.compress_to(self, x, target_bytes, q_tol, mask_pol, control.BYTES, "bytes_hi")
 
     def compress_to_bpp(self, x, target_bpp, q_tol=1e-3, mask_pol=None):
@@ -476,6 +482,7 @@ class VarianceMaskingPIC(CompressionModel):
         models (:meth:`_sweep_eligible`) run the front end once per sub-batch, price z and the base slices once, and per
         group of up to VAM_MAX_LAYER_LEVELS distinct qualities run one vam_variance_layers and one vam_coded_layer_bits
         launch.  The others loop over the real compress (bytes_lo == bytes_hi == the actual size); REM models are refused."""
+        self._refuse_lanes_for_sizes("coded_size_curve")
         return control.coded_size_curve(self, x, qualities, mask_pol)
 
     def qualities_for_bytes(self, x, target_bytes, q_tol=1e-3, mask_pol=None):
@@ -486,6 +493,7 @@ class VarianceMaskingPIC(CompressionModel):
         decrease in q);  q* = 0 with reached = False when even the base exceeds t.  :func:`rate_search` over bytes_hi:
         one front end per sub-batch; the first pass is the batched size tail, every later pass one
         vam_variance_layers_per_image and one vam_coded_layer_bits launch for the sub-batch and one synchronisation."""
+        self._refuse_lanes_for_sizes("qualities_for_bytes")
         return control.solve(self, x, target_bytes, q_tol, mask_pol, control.BYTES)
 
     # ---- quality maps: region-of-interest coding (DESIGN section 9k)
@@ -633,24 +641,39 @@ class VarianceMaskingPIC(CompressionModel):
             raise ValueError(f"model.coder is 'host' or 'device', got {self.coder!r}")
         return self.coder
 
-    def _encode_plan_device(self, plan, n_sl: int):
+    def _coder_lanes(self) -> int:
+        from . import bitstream as bs
+        try:
+            return bs.check_lanes(self.coder_lanes)
+        except ValueError:
+            raise ValueError(f"model.coder_lanes is a power of two in 1 .. 64, got {self.coder_lanes!r}") from None
+
+    def _refuse_lanes_for_sizes(self, what: str):
+        """The coded-size functions bracket the bytes of coder_lanes = 1 strings: refuse to answer for any other setting."""
+        if self._coder_lanes() != 1:
+            raise ValueError(f"{what} brackets the bytes of model.coder_lanes = 1 strings; with coder_lanes = {self.coder_lanes} "
+                             "every stream carries a header and one final state per lane, and the bracket no longer holds")
+
+    def _encode_plan_device(self, plan, n_sl: int, lanes: int = 1):
         """The streams of an executed symbol plan from the device coder: (y strings [slice][image], z strings [image]).  One
         launch for the n_sl * B slice streams straight from the plan's NHWC symbol and index views, one for the B z streams
-        (no index buffer: table index = channel)."""
+        (no index buffer: table index = channel).  ``lanes``: model.coder_lanes, for both."""
         from . import bitstream as bs
         dev = plan.sym.buf.device
         tg = bs.DeviceCoderTables.of(self.gaussian_conditional, dev)
         te = bs.DeviceCoderTables.of(self.entropy_bottleneck, dev)
-        ys = bs.encode_streams_device(plan.sym, plan.idx, n_sl, self.dim_chunk, tg)
-        zs = bs.encode_streams_device(plan.z_sym, None, 1, self.N, te)
+        ys = bs.encode_streams_device(plan.sym, plan.idx, n_sl, self.dim_chunk, tg, lanes=lanes)
+        zs = bs.encode_streams_device(plan.z_sym, None, 1, self.N, te, lanes=lanes)
         return ys, zs[0]
 
     def compress(self, x, quality=0.0, mask_pol=None, checkpoint_rep=None, real_compress=True):
         """One rANS stream per (slice, image) for y and per image for z.  The latents, entropy
         parameters, masks, symbols and table indexes come from the fused HIP plan; only the
-        bit-serial coder runs on the host (as in the reference, entropy_models.py:231-239)."""
+        bit-serial coder runs on the host (as in the reference, entropy_models.py:231-239).
+        ``model.coder_lanes`` = K > 1 splits every stream into K lanes; K is not stored in the strings,
+        so :meth:`decompress` must run with the same value, as with the same quality and shape."""
         mask_pol = self._mask_policy(mask_pol)
-        coder = self._coder()
+        coder, lanes = self._coder(), self._coder_lanes()
         Ly._no_autograd(x)
         L.require_gpu()
         self._check_config()
@@ -665,7 +688,7 @@ class VarianceMaskingPIC(CompressionModel):
         if real_compress and coder == "device":
             if plan.idx is None:
                 raise ValueError(EMPTY_SCALE_TABLE.format("compress"))
-            y_strings, z_strings = self._encode_plan_device(plan, n_sl)
+            y_strings, z_strings = self._encode_plan_device(plan, n_sl, lanes)
         elif real_compress:
             from . import bitstream as bs
             if plan.idx is None:
@@ -674,12 +697,13 @@ class VarianceMaskingPIC(CompressionModel):
             sym = plan.sym.buf.cpu().numpy()           # [B,h,w,C_lat] int32 (synchronises)
             idx = plan.idx.buf.cpu().numpy()
             zs = plan.z_sym.buf.cpu().numpy()
+            enc = bs.encode if lanes == 1 else (lambda s_, i_, t_: bs.encode_lanes(s_, i_, t_, lanes))
             for i in range(n_sl):                       # stream order: [C, h, w] per image, as the reference flattens
                 sl = slice(i * C, (i + 1) * C)
-                y_strings.append([bs.encode(sym[b, :, :, sl].transpose(2, 0, 1), idx[b, :, :, sl].transpose(2, 0, 1), tg)
+                y_strings.append([enc(sym[b, :, :, sl].transpose(2, 0, 1), idx[b, :, :, sl].transpose(2, 0, 1), tg)
                                   for b in range(B)])
             zi = torch.arange(self.N, dtype=torch.int32).numpy()[:, None, None]
-            z_strings = [bs.encode(zs[b].transpose(2, 0, 1), np.broadcast_to(zi, (self.N,) + zs.shape[1:3]), te)
+            z_strings = [enc(zs[b].transpose(2, 0, 1), np.broadcast_to(zi, (self.N,) + zs.shape[1:3]), te)
                          for b in range(B)]
         else:                                           # rem_pic.py:498-500,594-597: the quantised tensors instead of bytes
             sy = plan.sym.buf.permute(0, 3, 1, 2)
@@ -694,9 +718,10 @@ class VarianceMaskingPIC(CompressionModel):
 
     def decompress(self, strings, shape, quality, mask_pol=None, checkpoint_rep=None):
         """models/pic.py:838-967: z -> hyper-synthesis -> slice by slice (entropy parameters on the
-        GPU, rANS decode on the host, LRP on the GPU) -> g_s."""
+        GPU, rANS decode on the host, LRP on the GPU) -> g_s.  ``model.coder_lanes`` must be what it was for
+        :meth:`compress`: the strings do not store it, and a wrong value gives a VamError or a wrong image."""
         mask_pol = self._mask_policy(mask_pol)
-        coder = self._coder()
+        coder, lanes = self._coder(), self._coder_lanes()
         L.require_gpu()
         self._check_config()
         dev = self.entropy_bottleneck.quantiles.device
@@ -711,7 +736,8 @@ class VarianceMaskingPIC(CompressionModel):
             return _DecPlan(self, B, hz, wz, base_only, rem_idx, dev, coder=coder)
         dp = self._cached_plan(self._dec_plans, (B, hz, wz, base_only, rem_idx, str(dev)) + ((coder,) if coder != "host" else ()),
                                build, self._weights_sig(), rem_idx)
-        return {"x_hat": dp.decode(strings, _mask_quality(mask_pol, quality), checkpoint_rep if rem_idx is not None else None)}
+        return {"x_hat": dp.decode(strings, _mask_quality(mask_pol, quality), checkpoint_rep if rem_idx is not None else None,
+                                   lanes=lanes)}
 
     def _prog_dec_plan(self, B, hz, wz, q_list) -> "_ProgDecPlan":
         """The plans of progressive.ProgressiveDecoder for one (B, z-shape, quality list), cached beside decompress's."""

@@ -959,6 +959,7 @@ class _DecPlan:
         assert not (per_image and quality_map)
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
         self.coder, self.up, self.up_at = coder, None, 0
+        self.lanes = 1                                   # lanes per stream: decode() sets it per call
         self.per_image, self.quality_map = per_image, quality_map
         self.qtable = _mask_table_buffer(B, device) if per_image or quality_map else None
         self.level_map = torch.zeros((B, 16 * hz * wz), dtype=torch.uint8, device=device) if quality_map else None
@@ -1025,7 +1026,8 @@ class _DecPlan:
         """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window)."""
         from . import bitstream as bs
         if self.coder == "device":       # the B strings of this slice are the next B uploaded ones: one launch, no round trip
-            bs.decode_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, bs.DeviceCoderTables.of(self.m.gaussian_conditional, self.device))
+            bs.decode_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, bs.DeviceCoderTables.of(self.m.gaussian_conditional, self.device),
+                               lanes=self.lanes)
             self.up_at += self.B
             return
         B, h, w = self.B, idx_view.buf.shape[1], idx_view.buf.shape[2]
@@ -1033,9 +1035,13 @@ class _DecPlan:
         idx = idx_view.buf[..., idx_view.c0:idx_view.c0 + C].cpu().numpy()          # [B,h,w,C]
         out = np.empty((B, h, w, C), dtype=np.int32)
         for b in range(B):
-            dec = bs.decode(strings[b], idx[b].transpose(2, 0, 1), tables)           # stream order [C,h,w]
+            dec = self._host_decode(strings[b], idx[b].transpose(2, 0, 1), tables)   # stream order [C,h,w]
             out[b] = dec.reshape(C, h, w).transpose(1, 2, 0)
         sym_view.buf[..., sym_view.c0:sym_view.c0 + C].copy_(torch.from_numpy(out).to(self.device))
+
+    def _host_decode(self, string, idx, tables):
+        from . import bitstream as bs
+        return bs.decode(string, idx, tables) if self.lanes == 1 else bs.decode_lanes(string, idx, tables, self.lanes)
 
     def _decode_base(self, y_strings, z_strings, tg, te):
         """z (host decode) -> hyper-synthesis -> base slices, each slice's symbols decoded on the host; on the runner's
@@ -1043,11 +1049,12 @@ class _DecPlan:
         from . import bitstream as bs
         m = self.m
         if self.coder == "device":       # z: the first B uploaded strings, table index = channel
-            bs.decode_uploaded(self.up, 0, None, self.z_sym, 1, m.N, bs.DeviceCoderTables.of(m.entropy_bottleneck, self.device))
+            bs.decode_uploaded(self.up, 0, None, self.z_sym, 1, m.N, bs.DeviceCoderTables.of(m.entropy_bottleneck, self.device),
+                               lanes=self.lanes)
             self.up_at = self.B
         else:
             zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
-            zs = np.stack([bs.decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
+            zs = np.stack([self._host_decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
                            for b in range(self.B)])
             self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
         self.p_hyper.run()
@@ -1060,11 +1067,13 @@ class _DecPlan:
             self._decode_slice(strings[i], self.sc.sl(idx, i), self.sc.sl(sym, i), tg, self.m.dim_chunk)
             Pb.run()
 
-    def decode(self, strings, pr, checkpoint_rep, quality_map=None):
+    def decode(self, strings, pr, checkpoint_rep, quality_map=None, lanes: int = 1):
         """``pr``: the mask quality, or (per_image plans) one per image; ``quality_map`` (quality_map plans): (levels per
-        image, uint8 index map [B, h, w] on the host), and ``pr`` is not read."""
+        image, uint8 index map [B, h, w] on the host), and ``pr`` is not read.  ``lanes``: the lanes per stream of every y
+        and z string (model.coder_lanes at this call); nothing of the plan depends on it."""
         from . import bitstream as bs
         m = self.m
+        self.lanes = bs.check_lanes(lanes)
         if self.quality_map:
             levels, index = quality_map
             assert len(levels) == self.B
@@ -1085,7 +1094,7 @@ class _DecPlan:
             raise ValueError(f"expected {self.B} strings per slice")
         with self.runner.on_stream():
             if self.coder == "device":   # one upload: z first, then the slices in decoding order
-                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings[:n_need] for s_ in row], self.device)
+                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings[:n_need] for s_ in row], self.device, self.lanes)
             if checkpoint_rep is not None:
                 _load_checkpoint(self.ck, checkpoint_rep)
             self._decode_base(y_strings, z_strings, tg, te)

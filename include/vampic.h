@@ -799,6 +799,46 @@ int vam_rans_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, co
                            const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
                            const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ lane-split streams */
+/* A stream of n elements as `lanes` = K independent lanes, K a power of two in 1 .. VAM_RANS_MAX_LANES: lane j is the
+ * stream above of the elements j, j + K, j + 2K, ... (an empty lane is the 8 bytes of the initial state).  K = 1 is the
+ * existing wire format byte for byte, with no header.  For K > 1 the string is K little-endian uint32 lane lengths in
+ * 32-bit words (each >= 2), then the lanes' words back to back: 4 K + 4 sum(L_j) bytes exactly.  K is not stored in the
+ * string: both sides share it, like the quality and the shape.
+ * vam_rans_lanes_encode / _decode[_nhwc] (HOST pointers) mirror vam_rans_core_encode / _decode[_nhwc] with `lanes` and
+ * lane_status (NULL or K int32: the status of every lane).  A buffer of 4 K + K * (8 * ceil(n / K) + 64) bytes holds any
+ * string.  decode returns the status of the lowest-numbered failing lane: a string shorter than 4 K bytes, an L_j < 2 or
+ * lengths that do not add up to the string's length (64-bit sums) are status 6 for every lane, and every selected symbol
+ * is written as 0; a lane that fails on its own zeroes its symbols from the failure on, the other lanes are decoded. */
+#define VAM_RANS_MAX_LANES 64
+long vam_rans_lanes_encode(const int32_t* symbols_host, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                           int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                           uint8_t* out_host, long out_capacity, const uint8_t* layer_host, int sel, int lanes,
+                           int32_t* lane_status_host);
+int vam_rans_lanes_decode(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                          int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                          int32_t* symbols_out_host, const uint8_t* layer_host, int sel, int lanes, int32_t* lane_status_host);
+long vam_rans_lanes_encode_nhwc(const int32_t* sym_host, const int32_t* idx_host, const uint8_t* layer_host, int sel, int image,
+                                int h, int w, int ld, int c0, int C, const int32_t* cdfs_host, int cdf_stride,
+                                const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, uint8_t* out_host,
+                                long out_capacity, int lanes, int32_t* lane_status_host);
+int vam_rans_lanes_decode_nhwc(const uint8_t* in_host, long n_bytes, const int32_t* idx_host, const uint8_t* layer_host, int sel,
+                               int image, int h, int w, int ld, int c0, int C, const int32_t* cdfs_host, int cdf_stride,
+                               const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int32_t* sym_out_host,
+                               int lanes, int32_t* lane_status_host);
+/* DEVICE pointers.  One thread per (stream, lane); lane id = stream id * lanes + lane.
+ * vam_rans_lanes_encode_device: lane id's words are written backwards from the end of its region out_words + id *
+ * out_cap_words (2 * ceil(C*h*w / lanes) + 16 words is the budget); lengths[id] and status[id] are per lane, so
+ * vam_rans_pack_device over the B * n_slices * lanes regions gives the streams' bodies back to back and lengths is the
+ * headers.  vam_rans_lanes_decode_device: stream id is byte_lengths[id] bytes at bytes + byte_offsets[id] as above;
+ * status has B * n_slices * lanes entries.  No read leaves a stream's bytes, no write the window. */
+int vam_rans_lanes_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld,
+                                 int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                                 long out_cap_words, int32_t* lengths, int32_t* status, void* stream);
+int vam_rans_lanes_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                                 const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices, int lanes,
+                                 const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
 int vam_graph_end(void* stream, void** graph_exec_out);
