@@ -131,11 +131,26 @@ def _layer(a) -> Optional[np.ndarray]:
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
 
 
-def encode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> List[bytes]:
+def _lane_jobs(fn, jobs, threads: Optional[int]):
+    """``fn(job)`` for every job on :func:`coder_threads` host threads (the library calls release the GIL), in job order."""
+    from concurrent.futures import ThreadPoolExecutor
+    n = coder_threads(threads)
+    if n == 1 or len(jobs) <= 1:
+        return [fn(j) for j in jobs]
+    with ThreadPoolExecutor(max_workers=n) as pool:
+        return list(pool.map(fn, jobs))
+
+
+def encode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None, lanes: int = 1) -> List[bytes]:
     """Many independent streams in one vam_rans_encode_streams call.  ``jobs``: (symbols, indexes) or (symbols, indexes,
     layer, sel) per stream; with a layer array only the elements with layer == sel are coded (the others as 0 / table 0).
     Each stream's bytes equal :func:`encode`'s on the same (masked) inputs.  ``threads`` is passed on as given (the library
-    clamps it to L.VAM_RANS_MAX_THREADS); None = :func:`coder_threads`."""
+    clamps it to L.VAM_RANS_MAX_THREADS); None = :func:`coder_threads`.  ``lanes`` = K > 1: every job
+    is :func:`encode_lanes`'s string, the jobs spread over the same number of host threads."""
+    K = check_lanes(lanes)
+    if K > 1:
+        return _lane_jobs(lambda j: encode_lanes(j[0], j[1], t, K, j[2] if len(j) > 2 else None, int(j[3]) if len(j) > 2 else 0),
+                          list(jobs), threads)
     keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
     caps = []
     for j in jobs:
@@ -155,10 +170,16 @@ def encode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = No
     return [out[int(off[k]):int(off[k]) + arr[k].n_bytes].tobytes() for k in range(len(jobs))]
 
 
-def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> None:
+def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None, lanes: int = 1) -> None:
     """Decode many streams in one vam_rans_decode_streams call.  ``jobs``: (stream bytes, indexes, out) or (stream bytes,
     indexes, out, layer, sel); ``out`` is a writable C-contiguous int32 array of the indexes' size.  With a layer array only
-    out[layer == sel] is written, so the layers of a container can fill one array."""
+    out[layer == sel] is written, so the layers of a container can fill one array.  ``lanes`` = K > 1: every job is a
+    string of :func:`encode_lanes`, decoded by :func:`decode_lanes` on the same number of host threads."""
+    K = check_lanes(lanes)
+    if K > 1:
+        _lane_jobs(lambda j: decode_lanes(j[0], j[1], t, K, j[3] if len(j) > 3 else None, int(j[4]) if len(j) > 3 else 0, out=j[2]),
+                   list(jobs), threads)
+        return
     keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
     for k, j in enumerate(jobs):
         src = np.frombuffer(j[0], dtype=np.uint8)
@@ -564,6 +585,122 @@ def check_status(up: DeviceStreams, B: int, what: str = "vam_rans_decode_device"
         k = int(bad[0])
         raise L.VamError(f"{what}: {name(k // K)}" + (f", lane {k % K}" if K > 1 else "")
                          + f": {status_text(int(st[k]), K)}")
+
+
+# ---------------------------------------------------------------- layered launches: a container's layers
+LAYER_SCRATCH_BYTES = 1 << 30     # default bound of encode_layers_device's device scratch: regions plus packed buffer
+
+
+def layer_groups(n_levels: int, level_bytes: int, max_scratch_bytes: Optional[int] = None) -> List[Tuple[int, int]]:
+    """The consecutive level ranges [k0, k1) that :func:`encode_layers_device` codes per launch: as many levels as keep
+    ``(k1 - k0) * level_bytes`` (one level's regions plus its share of the packed buffer) within ``max_scratch_bytes``
+    (None: LAYER_SCRATCH_BYTES), at least one level per group whatever the bound.  Covers 0 .. n_levels in order."""
+    if n_levels < 1 or level_bytes < 1:
+        raise ValueError(f"layer_groups: n_levels and level_bytes must be >= 1, got {n_levels} and {level_bytes}")
+    budget = LAYER_SCRATCH_BYTES if max_scratch_bytes is None else int(max_scratch_bytes)
+    per = max(1, budget // int(level_bytes))
+    return [(k0, min(k0 + per, n_levels)) for k0 in range(0, n_levels, per)]
+
+
+def layer_status_message(status: np.ndarray, B: int, n_slices: int, what: str, lanes: int = 1, first_level: int = 0) -> Optional[str]:
+    """The words for the first non-zero code of a layered launch, None when every stream is fine.  One code per (stream,
+    lane), stream id = (k * n_slices + slice) * B + image; the level is printed as ``first_level`` + k."""
+    bad = np.flatnonzero(status)
+    if not bad.size:
+        return None
+    k, st = int(bad[0]) // lanes, int(status[bad[0]])
+    n_bad = np.unique(bad // lanes).size
+    return (f"{what}: stream (image {k % B}, level {first_level + k // (B * n_slices)}, slice {k // B % n_slices})"
+            + (f", lane {int(bad[0]) % lanes}" if lanes > 1 else "") + f": {status_text(st, lanes)}"
+            + (f" ({n_bad} streams failed)" if n_bad > 1 else ""))
+
+
+def _check_layers(layer, sel0: int, n_sel: int):
+    if layer is None:
+        raise ValueError("device coder: a layered launch needs the layer ids")
+    if sel0 < 0 or n_sel < 1 or sel0 + n_sel > 256:
+        raise ValueError(f"device coder: selectors [{sel0}, {sel0 + n_sel}) outside the layer ids 0 .. 255")
+
+
+def encode_layers_device(sym_view, idx_view, layer, n_levels: int, n_slices: int, C_: int, tables: DeviceCoderTables,
+                         lanes: int = 1, sel0: int = 0, max_scratch_bytes: Optional[int] = None,
+                         first_level: Optional[int] = None) -> List[List[List[bytes]]]:
+    """The layers ``sel0 .. sel0 + n_levels - 1`` of an int32 NHWC window, all n_levels * n_slices * B streams of a group
+    of levels in ONE vam_rans_layers_encode_device launch on the current stream.  Returns ``[level][slice][image]``; string
+    (k, s, b) is what :func:`encode_streams_device` gives with ``sel = sel0 + k``: the elements with layer == sel0 + k, every
+    other one as symbol 0 in table 0.  ``lanes`` = K > 1: lane-split strings, one thread per (stream, lane).
+
+    A stream's region is the host budget, 8 n + 64 bytes (per lane 8 ceil(n / K) + 64), and the packed buffer is as large
+    again, so n_levels levels need n_levels times the scratch of one :func:`encode_streams_device` call.  It is bounded:
+    the levels are coded in the groups of :func:`layer_groups` under ``max_scratch_bytes`` (None: LAYER_SCRATCH_BYTES), each
+    group one encode launch, one pack, one read of lengths + status and one read of the bytes.  ``first_level``: the number
+    an error message prints for level 0 (None: sel0)."""
+    from . import ops
+    K = check_lanes(lanes)
+    n_levels, sel0 = int(n_levels), int(sel0)
+    _check_layers(layer, sel0, n_levels)
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
+    n = C_ * h * w
+    per, cap = B * n_slices, 2 * (-(-n // K)) + 16
+    dev = sym_view.buf.device
+    lib, st = L.load(), ops.stream_ptr()
+    out: List[List[List[bytes]]] = []
+    for k0, k1 in layer_groups(n_levels, 2 * 4 * per * K * cap, max_scratch_bytes):
+        ns = (k1 - k0) * per
+        regions = torch.empty(ns * K * cap, dtype=torch.int32, device=dev)
+        packed = torch.empty(ns * K * cap, dtype=torch.int32, device=dev)
+        meta = torch.empty((2, ns * K), dtype=torch.int32, device=dev)      # per (stream, lane): length in words, status
+        offs = torch.empty(ns * K + 1, dtype=torch.int64, device=dev)
+        L.check(lib.vam_rans_layers_encode_device(sym_view.buf.data_ptr(), idx_view.buf.data_ptr() if idx_view is not None else None,
+                                                  layer.data_ptr(), sel0 + k0, k1 - k0, B, h, w, ld, sym_view.c0, C_, n_slices, K,
+                                                  C.byref(tables.struct), regions.data_ptr(), cap, meta[0].data_ptr(),
+                                                  meta[1].data_ptr(), st), "vam_rans_layers_encode_device")
+        L.check(lib.vam_rans_pack_device(regions.data_ptr(), cap, meta[0].data_ptr(), ns * K, packed.data_ptr(), ns * K * cap,
+                                         offs.data_ptr(), st), "vam_rans_pack_device")
+        m = meta.cpu().numpy()
+        msg = layer_status_message(m[1], B, n_slices, "vam_rans_layers_encode_device", K,
+                                   (sel0 if first_level is None else first_level) + k0)
+        if msg:
+            raise L.VamError(msg)
+        lens = m[0].reshape(ns, K)
+        off = np.concatenate([[0], np.cumsum(lens.sum(1).astype(np.int64))]) * 4      # the streams' bodies, back to back
+        data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
+        head = (lambda i: b"") if K == 1 else (lambda i: lens[i].astype("<u4").tobytes())
+        for k in range(k1 - k0):
+            out.append([[head(i) + data[off[i]:off[i + 1]].tobytes() for i in range((k * n_slices + s) * B, (k * n_slices + s + 1) * B)]
+                        for s in range(n_slices)])
+    return out
+
+
+def decode_layers_uploaded(up: DeviceStreams, first: int, idx_view, sym_view, layer, sel0: int, n_sel: int, n_slices: int, C_: int,
+                           tables: DeviceCoderTables, lanes: int = 1):
+    """One vam_rans_layers_decode_device launch on the current stream, no synchronisation: the n_sel * n_slices * B strings
+    of ``up`` from ``first`` on (string first + (k * n_slices + slice) * B + image is layer sel0 + k) into the ONE window of
+    ``sym_view``.  Every level writes only the elements of its own layer; elements of other layers keep what they hold.
+    The status codes go to ``up.status`` (one per (string, lane)); :func:`check_layer_status` reads them later."""
+    from . import ops
+    K = check_lanes(lanes)
+    sel0, n_sel = int(sel0), int(n_sel)
+    _check_layers(layer, sel0, n_sel)
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, layer)
+    count = n_sel * n_slices * B
+    if first < 0 or first + count > up.n:
+        raise ValueError(f"device coder: strings {first} .. {first + count} of {up.n} uploaded")
+    if K != up.lanes:
+        raise ValueError(f"device coder: strings uploaded for {up.lanes} lanes, decode asked for {K}")
+    L.check(L.load().vam_rans_layers_decode_device(up.bytes_ptr, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                                   idx_view.buf.data_ptr() if idx_view is not None else None, layer.data_ptr(),
+                                                   sel0, n_sel, B, h, w, ld, sym_view.c0, C_, n_slices, K, C.byref(tables.struct),
+                                                   sym_view.buf.data_ptr(), up.status.data_ptr() + 4 * first * K, ops.stream_ptr()),
+            "vam_rans_layers_decode_device")
+
+
+def check_layer_status(up: DeviceStreams, B: int, n_slices: int, what: str = "vam_rans_layers_decode_device", first_level: int = 0):
+    """Reads the status codes of an upload that holds only the strings of one layered launch (synchronises) and raises
+    VamError naming image, level, slice and, for lane-split strings, the lowest-numbered failing lane."""
+    msg = layer_status_message(up.status[:up.n * up.lanes].cpu().numpy(), B, n_slices, what, up.lanes, first_level)
+    if msg:
+        raise L.VamError(msg)
 
 
 def sigma0_index(scale_table) -> int:

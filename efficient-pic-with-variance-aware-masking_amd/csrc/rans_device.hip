@@ -8,6 +8,10 @@
 // compare (one ballot per 64 table entries) instead of a scan.  One lane stores.  Plain C++ only.
 //
 // Lane-split streams turn that around: one thread per (stream, lane), see the second half.
+//
+// Layered launches: every kernel takes n_sel consecutive layer selectors sel .. sel + n_sel - 1 over the
+// same window; stream id = (k * n_slices + slice) * B + image codes / decodes the elements of layer sel + k.  The
+// single-selector entry points are n_sel = 1.
 #include "common.h"
 #include "rans_core.h"
 #include <cstring>
@@ -24,6 +28,7 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 
 struct Geometry {
   int B, h, w, ld, c0, C, n_slices;
+  int n_sel;           // layer selectors of the launch; the level is the slowest dimension of the stream id
 };
 
 struct EncArgs {
@@ -40,12 +45,13 @@ struct EncArgs {
 };
 
 __global__ __launch_bounds__(kWave) void rans_encode_kernel(EncArgs a) {
-  const int sid = blockIdx.x, lane = threadIdx.x;
-  const int s = sid / a.g.B, b = sid - s * a.g.B;
+  const int gid = blockIdx.x, lane = threadIdx.x;
+  const int per = a.g.B * a.g.n_slices, lvl = gid / per, sid = gid - lvl * per;
+  const int s = sid / a.g.B, b = sid - s * a.g.B, sel = a.sel + lvl;
   const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
   const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
   const R::Nhwc at{hw, a.g.ld};
-  uint32_t* region = a.out + (long)sid * a.cap;
+  uint32_t* region = a.out + (long)gid * a.cap;
   R::Enc e;
   R::enc_init(e, region, region + a.cap, lane == 0);
   int fail = 0;
@@ -55,7 +61,7 @@ __global__ __launch_bounds__(kWave) void rans_encode_kernel(EncArgs a) {
     int st = 0;
     if (i < n) {                                      // staging: one element per lane
       const long o = img + at.off(i);
-      const bool keep = !a.layer || a.layer[o] == a.sel;
+      const bool keep = !a.layer || a.layer[o] == sel;
       const int ci = keep ? (a.idx ? a.idx[o] : at.chan(i)) : 0;
       st = R::classify(keep ? a.sym[o] : 0, ci, a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
     }
@@ -79,32 +85,68 @@ __global__ __launch_bounds__(kWave) void rans_encode_kernel(EncArgs a) {
     fail = uniform(e.status);
   }
   if (lane == 0) {
-    a.lengths[sid] = fail ? 0 : (int32_t)words;
-    a.status[sid] = fail;
+    a.lengths[gid] = fail ? 0 : (int32_t)words;
+    a.status[gid] = fail;
   }
 }
 
-// offsets[s] = sum of lengths[0 .. s), offsets[n] = the total; stream s's tail words go to packed + offsets[s].
-__global__ __launch_bounds__(256) void rans_pack_kernel(const uint32_t* regions, long cap, const int32_t* lengths, int n_streams,
-                                                        uint32_t* packed, long packed_cap, int64_t* offsets) {
-  __shared__ long part[256];
-  const int sid = blockIdx.x, t = threadIdx.x;
-  long sum = 0;
-  for (int j = t; j < sid; j += 256) sum += lengths[j];
-  part[t] = sum;
+// offsets[s] = sum of lengths[0 .. s), offsets[n] = the total; stream s's tail words go to packed + offsets[s].  A scan in
+// two levels, with offsets itself as the workspace: (1) every block of 256 regions scans its own lengths, offsets[i + 1] =
+// the inclusive sum inside i's block, so offsets[256 (j + 1)] (offsets[n] for the last block) is block j's total; (2) one
+// workgroup turns those totals into running sums in place, which is their final value; (3) region i adds its block's base
+// offsets[i - i % 256] and copies.  Nothing in (3) writes an entry another workgroup of (3) reads: bases are multiples of 256.
+constexpr int kPackBlock = 256;
+
+__global__ __launch_bounds__(kPackBlock) void rans_pack_local_kernel(const int32_t* lengths, int n, int64_t* offsets) {
+  __shared__ long part[kPackBlock];
+  const int t = threadIdx.x, i = blockIdx.x * kPackBlock + t;
+  part[t] = i < n ? lengths[i] : 0;
   __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if (t < d) part[t] += part[t + d];
+  for (int d = 1; d < kPackBlock; d <<= 1) {
+    const long add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
     __syncthreads();
   }
-  const long off = part[0], len = lengths[sid];
+  if (i < n) offsets[i + 1] = part[t];
+  if (i == 0) offsets[0] = 0;
+}
+
+// Block totals -> running sums, in place.  Thread t takes the blocks [t * per, (t + 1) * per).
+__global__ __launch_bounds__(kPackBlock) void rans_pack_blocks_kernel(int n, int64_t* offsets) {
+  __shared__ long part[kPackBlock];
+  const int t = threadIdx.x, n_blocks = (n + kPackBlock - 1) / kPackBlock, per = (n_blocks + kPackBlock - 1) / kPackBlock;
+  const int j0 = t * per < n_blocks ? t * per : n_blocks, j1 = j0 + per < n_blocks ? j0 + per : n_blocks;
+  auto total_at = [&](int j) -> long { const long e = (long)(j + 1) * kPackBlock; return e < n ? e : n; };
+  long sum = 0;
+  for (int j = j0; j < j1; ++j) sum += offsets[total_at(j)];
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < kPackBlock; d <<= 1) {
+    const long add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  long run = part[t] - sum;                                    // the total of every block before j0
+  for (int j = j0; j < j1; ++j) {
+    run += offsets[total_at(j)];
+    offsets[total_at(j)] = run;
+  }
+}
+
+__global__ __launch_bounds__(kPackBlock) void rans_pack_kernel(const uint32_t* regions, long cap, const int32_t* lengths, int n_streams,
+                                                               uint32_t* packed, long packed_cap, int64_t* offsets) {
+  const int sid = blockIdx.x, t = threadIdx.x, in_block = sid % kPackBlock;
+  const long off = in_block ? offsets[sid - in_block] + offsets[sid] : offsets[sid], len = lengths[sid];
+  __syncthreads();                                            // every thread has read offsets[sid] before it is replaced
   if (t == 0) {
-    offsets[sid] = off;
+    if (in_block) offsets[sid] = off;
     if (sid == n_streams - 1) offsets[n_streams] = off + (len > 0 ? len : 0);
   }
   if (len <= 0 || len > cap || off + len > packed_cap) return;
   const uint32_t* src = regions + (long)sid * cap + (cap - len);
-  for (long j = t; j < len; j += 256) packed[off + j] = src[j];
+  for (long j = t; j < len; j += kPackBlock) packed[off + j] = src[j];
 }
 
 // The decoder's symbol search across the wave: entries e[1 .. n_ent] of an increasing table, 64 at a time.  Above 64
@@ -115,7 +157,7 @@ struct WaveSearch {
   int sz;              // cdf_sizes of the table
   bool implied_last;   // packed tables: entry sz-1 is not stored, it is 65536
   __device__ int operator()(uint32_t cum, uint32_t& start, uint32_t& freq) const {
-    const int lane = threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
     int lo = 0, len = implied_last ? sz - 2 : sz - 1;        // searchable entries e[1 + lo .. 1 + lo + len)
     while (len > kWave) {
       const int step = (len + kWave - 1) / kWave;
@@ -148,23 +190,29 @@ struct DecArgs {
   int32_t* status;
 };
 
-template <bool kPacked>
-__global__ __launch_bounds__(kWave) void rans_decode_kernel(DecArgs a) {
+// kWaves streams per workgroup, one wave each, share one LDS copy of the packed tables (the layered launches: 8 waves;
+// the single-selector entry point: 1).  A wave whose stream id is past the end leaves after the barrier.
+template <bool kPacked, int kWaves>
+__global__ __launch_bounds__(kWave * kWaves) void rans_decode_kernel(DecArgs a) {
   extern __shared__ uint4 lds_raw[];
   const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds_raw);
-  const int sid = blockIdx.x, lane = threadIdx.x;
+  const int lane = threadIdx.x & (kWave - 1);
   if (kPacked) {                                              // the ragged 16-bit tables into LDS, 16 bytes per lane and step
     const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
-    for (int j = lane; j < a.t.packed_entries / 8; j += kWave) lds_raw[j] = src[j];
+    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kWave * kWaves) lds_raw[j] = src[j];
     __syncthreads();
   }
+  const int per = a.g.B * a.g.n_slices;
+  const int gid = blockIdx.x * kWaves + uniform((int)threadIdx.x / kWave);
+  if (gid >= per * a.g.n_sel) return;
+  const int lvl = gid / per, sid = gid - lvl * per, sel = a.sel + lvl;
   const int s = sid / a.g.B, b = sid - s * a.g.B;
   const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
   const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
   const R::Nhwc at{hw, a.g.ld};
   R::Dec d;
-  const int64_t boff = a.byte_offsets[sid];
-  R::dec_init(d, (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff), a.byte_lengths[sid]);
+  const int64_t boff = a.byte_offsets[gid];
+  R::dec_init(d, (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff), a.byte_lengths[gid]);
   int fail = uniform(d.status);
   for (long base = 0; base < n; base += kWave) {
     const long i = base + lane;
@@ -173,7 +221,7 @@ __global__ __launch_bounds__(kWave) void rans_decode_kernel(DecArgs a) {
     int st = 0, sz = 2, offv = 0, t0 = 0;
     if (i < n) {                                              // staging: one element per lane
       o = img + at.off(i);
-      keep = !a.layer || a.layer[o] == a.sel;
+      keep = !a.layer || a.layer[o] == sel;
       const int ci = keep ? (a.idx ? a.idx[o] : at.chan(i)) : 0;
       if (ci < 0 || ci >= a.t.n_cdfs) st = R::kBadIndex;
       else {
@@ -201,7 +249,7 @@ __global__ __launch_bounds__(kWave) void rans_decode_kernel(DecArgs a) {
     }
     if (keep) a.out[o] = have ? (int32_t)((uint32_t)mine + (uint32_t)offv) : 0;   // after a failure: zeros
   }
-  if (lane == 0) a.status[sid] = fail;
+  if (lane == 0) a.status[gid] = fail;
 }
 
 // ---------------------------------------------------------------- lane-split streams
@@ -223,14 +271,15 @@ struct LaneEncArgs {
 };
 
 __global__ __launch_bounds__(kWave) void rans_lanes_encode_kernel(LaneEncArgs a) {
-  const int gid = blockIdx.x * kWave + threadIdx.x;
-  if (gid >= a.g.B * a.g.n_slices * a.K) return;
-  const int sid = gid / a.K, lane = gid - sid * a.K;
+  const int gid = blockIdx.x * kWave + threadIdx.x, per = a.g.B * a.g.n_slices;
+  if (gid >= per * a.g.n_sel * a.K) return;
+  const int str = gid / a.K, lane = gid - str * a.K;          // str = (level * n_slices + slice) * B + image
+  const int lvl = str / per, sid = str - lvl * per;
   const int s = sid / a.g.B, b = sid - s * a.g.B;
   const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
   const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
   long words = 0;
-  const int32_t st = R::lane_encode(a.sym + img, a.idx ? a.idx + img : nullptr, a.layer ? a.layer + img : nullptr, a.sel, n,
+  const int32_t st = R::lane_encode(a.sym + img, a.idx ? a.idx + img : nullptr, a.layer ? a.layer + img : nullptr, a.sel + lvl, n,
                                     R::Nhwc{hw, a.g.ld}, a.K, lane, a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs,
                                     a.out + (long)gid * a.cap, a.cap, &words);
   a.lengths[gid] = st ? 0 : (int32_t)words;
@@ -264,31 +313,33 @@ __global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecAr
     for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
     __syncthreads();
   }
-  const int gid = blockIdx.x * kLaneBlock + threadIdx.x;
-  if (gid >= a.g.B * a.g.n_slices * a.K) return;
-  const int sid = gid / a.K, lane = gid - sid * a.K;
+  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, per = a.g.B * a.g.n_slices;
+  if (gid >= per * a.g.n_sel * a.K) return;
+  const int str = gid / a.K, lane = gid - str * a.K;          // str = (level * n_slices + slice) * B + image
+  const int lvl = str / per, sid = str - lvl * per, sel = a.sel + lvl;
   const int s = sid / a.g.B, b = sid - s * a.g.B;
   const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
   const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
-  const int64_t boff = a.byte_offsets[sid];
+  const int64_t boff = a.byte_offsets[str];
   const uint32_t* words = (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff);
   const int32_t* idx = a.idx ? a.idx + img : nullptr;
   const uint8_t* layer = a.layer ? a.layer + img : nullptr;
   const R::Nhwc at{hw, a.g.ld};
   if (kPacked)
-    a.status[gid] = R::lane_decode(words, a.byte_lengths[sid], a.K, lane, idx, layer, a.sel, n, at,
+    a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, idx, layer, sel, n, at,
                                    R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}, a.t.stride, a.t.sizes,
                                    a.t.offsets, a.t.n_cdfs, a.out + img);
   else
-    a.status[gid] = R::lane_decode(words, a.byte_lengths[sid], a.K, lane, idx, layer, a.sel, n, at, R::Int32Rows{a.t.cdf, a.t.stride},
+    a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, idx, layer, sel, n, at, R::Int32Rows{a.t.cdf, a.t.stride},
                                    a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, a.out + img);
 }
 
-int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices) {
+int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices, int n_sel = 1) {
   VAM_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && n_slices > 0 && c0 >= 0, "%s: B, h, w, C, n_slices must be > 0 and c0 >= 0", what);
   VAM_REQUIRE((long)c0 + (long)C * n_slices <= ld, "%s: window [%d, %ld) does not fit ld = %d", what, c0, (long)c0 + (long)C * n_slices, ld);
-  VAM_REQUIRE((long)h * w * C <= (1l << 28) && (long)B * n_slices <= (1l << 20), "%s: stream of %ld symbols or %ld streams is too large", what,
-              (long)h * w * C, (long)B * n_slices);
+  VAM_REQUIRE(n_sel > 0, "%s: n_sel must be > 0, got %d", what, n_sel);
+  VAM_REQUIRE((long)h * w * C <= (1l << 28) && (long)n_sel * B * n_slices <= (1l << 20), "%s: stream of %ld symbols or %ld streams is too large",
+              what, (long)h * w * C, (long)n_sel * B * n_slices);
   return VAM_OK;
 }
 
@@ -379,6 +430,93 @@ int core_lanes_decode(const char* what, const uint8_t* in, long n_bytes, int K, 
   return st;
 }
 
+// ---------------------------------------------------------------- launches, shared by the single-selector and the layered entry points
+int launch_encode(const char* what, const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int n_sel, int B, int h, int w,
+                  int ld, int c0, int C, int n_slices, const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words,
+                  int32_t* lengths, int32_t* status, void* stream) {
+  VAM_REQUIRE(sym && out_words && lengths && status, "%s: need sym, out_words, lengths, status", what);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "%s: a region is 2 .. 2^31 words, got %ld", what, out_cap_words);
+  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, *tables, out_words, out_cap_words, lengths, status};
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_encode_kernel, dim3(n_sel * B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_encode_kernel");
+}
+
+template <int kWaves>
+int launch_decode(const char* what, const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                  const uint8_t* layer, int sel, int n_sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
+                  const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status, "%s: need bytes, offsets, lengths, sym_out, status", what);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, *tables, sym_out, status};
+  const int blocks = (n_sel * B * n_slices + kWaves - 1) / kWaves;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_decode_kernel<true, kWaves>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((rans_decode_kernel<true, kWaves>), dim3(blocks), dim3(kWave * kWaves), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL((rans_decode_kernel<false, kWaves>), dim3(blocks), dim3(kWave * kWaves), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_decode_kernel");
+}
+
+int launch_lanes_encode(const char* what, const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int n_sel, int B, int h,
+                        int w, int ld, int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                        long out_cap_words, int32_t* lengths, int32_t* status, void* stream) {
+  VAM_REQUIRE(sym && out_words && lengths && status, "%s: need sym, out_words, lengths, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "%s: a region is 2 .. 2^31 words, got %ld", what, out_cap_words);
+  LaneEncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, out_words, out_cap_words, lengths, status};
+  const int threads = n_sel * B * n_slices * lanes;         // at most 2^20 streams of 64 lanes
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_lanes_encode_kernel");
+}
+
+int launch_lanes_decode(const char* what, const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                        const uint8_t* layer, int sel, int n_sel, int B, int h, int w, int ld, int c0, int C, int n_slices, int lanes,
+                        const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status, "%s: need bytes, offsets, lengths, sym_out, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  LaneDecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, sym_out, status};
+  const int blocks = (n_sel * B * n_slices * lanes + kLaneBlock - 1) / kLaneBlock;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_lanes_decode_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(rans_lanes_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rans_lanes_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_lanes_decode_kernel");
+}
+
+// The layered launches select by layer id: a uint8, so the selectors stay within 0 .. 255.
+int check_layers(const char* what, const uint8_t* layer, int sel0, int n_sel) {
+  VAM_REQUIRE(layer, "%s: need the layer ids", what);
+  VAM_REQUIRE(sel0 >= 0 && n_sel > 0 && (long)sel0 + n_sel <= 256, "%s: selectors [%d, %ld) outside the layer ids 0 .. 255", what, sel0,
+              (long)sel0 + n_sel);
+  return VAM_OK;
+}
+
+constexpr int kLayerWaves = 8;       // streams per workgroup of the layered K = 1 decode
+
 }  // namespace
 
 extern "C" {
@@ -423,22 +561,20 @@ int vam_rans_core_decode_nhwc(const uint8_t* in, long n_bytes, const int32_t* id
 int vam_rans_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0,
                            int C, int n_slices, const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words,
                            int32_t* lengths, int32_t* status, void* stream) {
-  VAM_REQUIRE(sym && out_words && lengths && status, "vam_rans_encode_device: need sym, out_words, lengths, status");
-  if (int rc = check_geometry("vam_rans_encode_device", B, h, w, ld, c0, C, n_slices)) return rc;
-  if (int rc = check_tables("vam_rans_encode_device", tables)) return rc;
-  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "vam_rans_encode_device: a region is 2 .. 2^31 words, got %ld", out_cap_words);
-  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, *tables, out_words, out_cap_words, lengths, status};
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  hipLaunchKernelGGL(rans_encode_kernel, dim3(B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
-  return check_launch("rans_encode_kernel");
+  return launch_encode("vam_rans_encode_device", sym, idx, layer, sel, 1, B, h, w, ld, c0, C, n_slices, tables, out_words, out_cap_words,
+                       lengths, status, stream);
 }
 
 int vam_rans_pack_device(const uint32_t* regions, long cap_words, const int32_t* lengths, int n_streams, uint32_t* packed,
                          long packed_cap_words, int64_t* offsets, void* stream) {
   VAM_REQUIRE(regions && lengths && packed && offsets && n_streams > 0 && cap_words >= 2 && packed_cap_words >= 0,
               "vam_rans_pack_device: bad arguments");
+  const int n_blocks = (n_streams + kPackBlock - 1) / kPackBlock;
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  hipLaunchKernelGGL(rans_pack_kernel, dim3(n_streams), dim3(256), 0, (hipStream_t)stream, regions, cap_words, lengths, n_streams,
+  hipLaunchKernelGGL(rans_pack_local_kernel, dim3(n_blocks), dim3(kPackBlock), 0, (hipStream_t)stream, lengths, n_streams, offsets);
+  if (n_blocks > 1)
+    hipLaunchKernelGGL(rans_pack_blocks_kernel, dim3(1), dim3(kPackBlock), 0, (hipStream_t)stream, n_streams, offsets);
+  hipLaunchKernelGGL(rans_pack_kernel, dim3(n_streams), dim3(kPackBlock), 0, (hipStream_t)stream, regions, cap_words, lengths, n_streams,
                      packed, packed_cap_words, offsets);
   return check_launch("rans_pack_kernel");
 }
@@ -455,23 +591,8 @@ int vam_rans_lds_table_bytes(void) {
 int vam_rans_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
                            const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
                            const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
-  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status, "vam_rans_decode_device: need bytes, offsets, lengths, sym_out, status");
-  if (int rc = check_geometry("vam_rans_decode_device", B, h, w, ld, c0, C, n_slices)) return rc;
-  if (int rc = check_tables("vam_rans_decode_device", tables)) return rc;
-  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, *tables, sym_out, status};
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "vam_rans_decode_device: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_decode_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(rans_decode_kernel<true>, dim3(B * n_slices), dim3(kWave), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(rans_decode_kernel<false>, dim3(B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_decode_kernel");
+  return launch_decode<1>("vam_rans_decode_device", bytes, byte_offsets, byte_lengths, idx, layer, sel, 1, B, h, w, ld, c0, C, n_slices,
+                          tables, sym_out, status, stream);
 }
 
 long vam_rans_lanes_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
@@ -516,43 +637,42 @@ int vam_rans_lanes_decode_nhwc(const uint8_t* in, long n_bytes, const int32_t* i
 int vam_rans_lanes_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int B, int h, int w, int ld,
                                  int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
                                  long out_cap_words, int32_t* lengths, int32_t* status, void* stream) {
-  VAM_REQUIRE(sym && out_words && lengths && status, "vam_rans_lanes_encode_device: need sym, out_words, lengths, status");
-  VAM_REQUIRE(R::lanes_valid(lanes), "vam_rans_lanes_encode_device: lanes is a power of two in 1 .. %d, got %d", R::kMaxLanes, lanes);
-  if (int rc = check_geometry("vam_rans_lanes_encode_device", B, h, w, ld, c0, C, n_slices)) return rc;
-  if (int rc = check_tables("vam_rans_lanes_encode_device", tables)) return rc;
-  VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "vam_rans_lanes_encode_device: a region is 2 .. 2^31 words, got %ld",
-              out_cap_words);
-  LaneEncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, lanes, *tables, out_words, out_cap_words, lengths, status};
-  const int threads = B * n_slices * lanes;                 // at most 2^20 streams of 64 lanes
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
-  return check_launch("rans_lanes_encode_kernel");
+  return launch_lanes_encode("vam_rans_lanes_encode_device", sym, idx, layer, sel, 1, B, h, w, ld, c0, C, n_slices, lanes, tables, out_words,
+                             out_cap_words, lengths, status, stream);
 }
 
 int vam_rans_lanes_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
                                  const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices, int lanes,
                                  const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
-  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status,
-              "vam_rans_lanes_decode_device: need bytes, offsets, lengths, sym_out, status");
-  VAM_REQUIRE(R::lanes_valid(lanes), "vam_rans_lanes_decode_device: lanes is a power of two in 1 .. %d, got %d", R::kMaxLanes, lanes);
-  if (int rc = check_geometry("vam_rans_lanes_decode_device", B, h, w, ld, c0, C, n_slices)) return rc;
-  if (int rc = check_tables("vam_rans_lanes_decode_device", tables)) return rc;
-  LaneDecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices}, lanes, *tables, sym_out, status};
-  const int blocks = (B * n_slices * lanes + kLaneBlock - 1) / kLaneBlock;
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "vam_rans_lanes_decode_device: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", lds,
-                limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_lanes_decode_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(rans_lanes_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(rans_lanes_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_lanes_decode_kernel");
+  return launch_lanes_decode("vam_rans_lanes_decode_device", bytes, byte_offsets, byte_lengths, idx, layer, sel, 1, B, h, w, ld, c0, C,
+                             n_slices, lanes, tables, sym_out, status, stream);
+}
+
+// ---------------------------------------------------------------- layered launches
+int vam_rans_layers_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel0, int n_sel, int B, int h, int w,
+                                  int ld, int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                                  long out_cap_words, int32_t* lengths, int32_t* status, void* stream) {
+  const char* what = "vam_rans_layers_encode_device";
+  if (int rc = check_layers(what, layer, sel0, n_sel)) return rc;
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (lanes == 1)
+    return launch_encode(what, sym, idx, layer, sel0, n_sel, B, h, w, ld, c0, C, n_slices, tables, out_words, out_cap_words, lengths, status,
+                         stream);
+  return launch_lanes_encode(what, sym, idx, layer, sel0, n_sel, B, h, w, ld, c0, C, n_slices, lanes, tables, out_words, out_cap_words,
+                             lengths, status, stream);
+}
+
+int vam_rans_layers_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                                  const uint8_t* layer, int sel0, int n_sel, int B, int h, int w, int ld, int c0, int C, int n_slices,
+                                  int lanes, const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream) {
+  const char* what = "vam_rans_layers_decode_device";
+  if (int rc = check_layers(what, layer, sel0, n_sel)) return rc;
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (lanes == 1)
+    return launch_decode<kLayerWaves>(what, bytes, byte_offsets, byte_lengths, idx, layer, sel0, n_sel, B, h, w, ld, c0, C, n_slices, tables,
+                                      sym_out, status, stream);
+  return launch_lanes_decode(what, bytes, byte_offsets, byte_lengths, idx, layer, sel0, n_sel, B, h, w, ld, c0, C, n_slices, lanes, tables,
+                             sym_out, status, stream);
 }
 
 }  // extern "C"

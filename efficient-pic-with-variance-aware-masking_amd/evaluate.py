@@ -318,13 +318,14 @@ def compress_with_ac(model, images: Iterable[torch.Tensor], pr_list: Sequence[fl
     return avg(bpp), avg(psnr), avg(t_enc), avg(t_dec)
 
 
-def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float]):
+def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float], coder: Optional[str] = None, lanes: int = 1):
     """The demo's progressive printout (reference demo.py with src/test/functions_encode.py / functions_decode.py) for a
     list of images on the batched container (progressive.encode_batch / ProgressiveDecoder): images of one shape are
     padded as :func:`compress_with_ac` pads them and coded as one batch; every level 0..len(q_list) is decoded.  Returns
     one dict per level: q (0 for the base), bpp (8 * the container's bytes up to the level / pixels of the ORIGINAL image),
     psnr (of the cropped decode), enc_s and dec_s (seconds per image: the encode once, the decode of that level), each
-    the mean over the images, plus the per-image "bpp_all" / "psnr_all"."""
+    the mean over the images, plus the per-image "bpp_all" / "psnr_all".  ``coder`` (None: model.coder) and ``lanes`` go to
+    encode_batch and the decoder as given."""
     from . import progressive as P
     images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
     nl = len(q_list) + 1
@@ -339,9 +340,9 @@ def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float
             xp, unpad = pad_image(xs)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            containers, _ = P.encode_batch(model, xp, q_list)
+            containers, _ = P.encode_batch(model, xp, q_list, coder=coder, lanes=lanes)
             t1 = time.perf_counter()
-            dec = P.ProgressiveDecoder(model, containers)
+            dec = P.ProgressiveDecoder(model, containers, coder=coder)
             for k in range(nl):
                 torch.cuda.synchronize()
                 t2 = time.perf_counter()

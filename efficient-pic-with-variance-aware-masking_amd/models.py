@@ -739,11 +739,12 @@ class VarianceMaskingPIC(CompressionModel):
         return {"x_hat": dp.decode(strings, _mask_quality(mask_pol, quality), checkpoint_rep if rem_idx is not None else None,
                                    lanes=lanes)}
 
-    def _prog_dec_plan(self, B, hz, wz, q_list) -> "_ProgDecPlan":
-        """The plans of progressive.ProgressiveDecoder for one (B, z-shape, quality list), cached beside decompress's."""
+    def _prog_dec_plan(self, B, hz, wz, q_list, coder: str = "host") -> "_ProgDecPlan":
+        """The plans of progressive.ProgressiveDecoder for one (B, z-shape, quality list, coder), cached beside decompress's."""
         dev = self.entropy_bottleneck.quantiles.device
-        return self._cached_plan(self._dec_plans, ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev)),
-                                 lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev), self._weights_sig())
+        return self._cached_plan(self._dec_plans, ("prog", B, hz, wz, tuple(float(q) for q in q_list), str(dev))
+                                 + ((coder,) if coder != "host" else ()),
+                                 lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev, coder=coder), self._weights_sig())
 
     def _emb_dec_plan(self, B, hz, wz) -> "_EmbDecPlan":
         """The plans of embedded.EmbeddedDecoder for one (B, z-shape), cached beside decompress's: the cuts are graph

@@ -1120,9 +1120,11 @@ class _ProgDecPlan(_DecPlan):
     (src/test/utils.py:35-54, functions_decode.py:186-203).  ``sweep_parts`` feeds _SweepTail in decode mode: level g is
     the decoded symbols of the layers <= ks[g], + mu, then the LRP stacks and g_s[1]; ``p_syn`` is level 0 (g_s[0])."""
 
-    def __init__(self, m, B, hz, wz, q_list, device):
+    def __init__(self, m, B, hz, wz, q_list, device, coder: str = "host"):
+        """``coder`` "device" (DESIGN section 9p): z and the base slices are decoded by the device coder as in _DecPlan, and
+        the decoder hands the layers to ``sym`` with one layered launch per level request."""
         self.q_list = tuple(float(q) for q in q_list)      # before super().__init__: it runs _lower_progressive, which reads it
-        super().__init__(m, B, hz, wz, False, None, device)
+        super().__init__(m, B, hz, wz, False, None, device, coder=coder)
         self.tails: Dict[int, _SweepTail] = {}
         self.owner = None                   # the ProgressiveDecoder whose base and chain the buffers hold
 
@@ -1140,13 +1142,22 @@ class _ProgDecPlan(_DecPlan):
         self.sweep_parts = dict(heads=sc.heads, yb=sc.yb, mu=mu_p, std=std_p, mu_tot=sc.mu_tot, sym=self.sym, layer=self.layer,
                                 g_s=m.g_s[1] if m.multiple_decoder else m.g_s)
 
-    def front(self, y_strings, z_strings):
-        """Base slices (host round trips) and the progressive chain, layer ids and indexes of every image."""
+    def front(self, y_strings, z_strings, lanes: int = 1):
+        """Base slices (host round trips) and the progressive chain, layer ids and indexes of every image.  ``lanes``: the
+        lanes per stream of every string.  Device coder: z and the base go up in one copy, no round trip follows, the
+        symbol window is zeroed, and the upload is returned for the caller to read its status codes later (host: None)."""
         from . import bitstream as bs
         tg, te = bs.Tables.of(self.m.gaussian_conditional), bs.Tables.of(self.m.entropy_bottleneck)
+        self.lanes = bs.check_lanes(lanes)
         with self.runner.on_stream():
+            if self.coder == "device":
+                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings for s_ in row], self.device, self.lanes)
             self._decode_base(y_strings, z_strings, tg, te)
             self.p_chain.run()
+            if self.coder == "device":
+                self.sym.buf.zero_()
+        up, self.up = self.up, None
+        return up
 
     def base(self, use_graph: bool):
         with self.runner.on_stream():

@@ -231,7 +231,8 @@ def container_sizes(model, x, q_list: Sequence[float] = Q_LIST) -> List[dict]:
     {"z": [lo, hi], "base": [lo, hi], "progressive": [[lo, hi] per layer]} in bytes, with lo <= actual <= hi guaranteed
     for every group of streams.  One front end per sub-batch, one vam_variance_layers and one vam_coded_layer_bits
     launch; a layer's stream costs its elements' exact table prices plus the price of symbol 0 in table 0 for every other
-    element.  The refusals are encode_batch's."""
+    element.  The refusals are encode_batch's.  The brackets describe K = 1 containers, from either coder; a lane-split
+    container (``encode_batch(..., lanes=K)``) adds a header and K - 1 final states to every stream."""
     from . import bitstream as bs
     from . import control
     _check_variant(model)
@@ -298,7 +299,7 @@ def q_list_for_bytes(model, x, target_bytes: Sequence[float], q_tol: float = 1e-
     quality level by level (:func:`solve_q_list_for_bytes`): a layer's size depends on the previous cut, and every layer
     adds its own stream overheads.  Targets below the base (z + base slices) are dropped.  One front end; every
     refinement pass is one vam_variance_layers and one vam_coded_layer_bits launch.  ``return_targets``: also the targets
-    kept, one per level."""
+    kept, one per level.  The guarantee describes K = 1 containers (``lanes=1``, from either coder), not lane-split ones."""
     from . import _lib as L
     from . import bitstream as bs
     from . import control
@@ -358,12 +359,62 @@ def _check_batched(model):
                                   f"use {_EAGER}")
 
 
-def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
+def _check_coder(model, coder) -> str:
+    """``coder`` None reads model.coder; anything but "host" / "device" is a ValueError."""
+    if coder is None:
+        return model._coder()
+    if coder not in ("host", "device"):
+        raise ValueError(f"coder is 'host' or 'device' (None: model.coder), got {coder!r}")
+    return coder
+
+
+def check_containers(containers):
+    """(shape, q_list, lanes) shared by a batch of containers for one :class:`ProgressiveDecoder`: every container must have
+    the same shape, quality list and ``"lanes"`` value (a container without the key is K = 1).  Host arithmetic only."""
+    from . import bitstream as bs
+    cs = list(containers)
+    if not cs:
+        raise ValueError("ProgressiveDecoder: no containers")
+    shape, q0 = tuple(cs[0]["shape"]), [float(q) for q in cs[0]["q_list"]]
+    for c in cs[1:]:
+        if tuple(c["shape"]) != shape or [float(q) for q in c["q_list"]] != q0:
+            raise ValueError("ProgressiveDecoder: every container must have the same shape and q_list, got "
+                             f"{shape} / {q0} and {tuple(c['shape'])} / {list(c['q_list'])}; decode them separately")
+    lanes = [bs.check_lanes(c.get("lanes", 1)) for c in cs]
+    if any(k != lanes[0] for k in lanes):
+        raise ValueError(f"ProgressiveDecoder: every container must have the same lanes per stream, got {sorted(set(lanes))}; "
+                         "decode them separately")
+    return shape, check_q_list(q0), lanes[0]
+
+
+def _encode_batch_device(m, plan, layer, n_levels: int, lanes: int):
+    """z, the base slices and all layers from the device coder: (z [image], base [slice][image], layers
+    [level][slice][image]).  The progressive window of the plan's symbols and indexes is copied on the device into buffers
+    of the layer ids' geometry; nothing but lengths, status codes and coded bytes comes to the host."""
+    from . import bitstream as bs
+    from . import ops
+    d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
+    dev = plan.sym.buf.device
+    tg, te = bs.DeviceCoderTables.of(m.gaussian_conditional, dev), bs.DeviceCoderTables.of(m.entropy_bottleneck, dev)
+    z_str = bs.encode_streams_device(plan.z_sym, None, 1, m.N, te, lanes=lanes)[0]
+    base = bs.encode_streams_device(plan.sym, plan.idx, ns, C, tg, lanes=lanes)
+    win = lambda v: ops.IView(v.buf[..., v.c0 + d:v.c0 + 2 * d].contiguous(), 0, d)
+    prog = bs.encode_layers_device(win(plan.sym), win(plan.idx), layer, n_levels, ns, C, tg, lanes=lanes, first_level=1)
+    return z_str, base, prog
+
+
+def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None, *, coder: Optional[str] = None, lanes: int = 1):
     """:func:`encode` for a batch x [B,3,H,W] (H, W multiples of 64, as for ``compress``) on the fused plans: the
     ``compress(x, 10)`` plan (symbols round(r - mu), unmasked indexes), then vam_variance_layers on its sigma assigns every
-    element its layer.  The symbols, indexes, layer ids and z symbols go to the host once; z, the base slices and the
-    layers are coded by the threaded stream coder.  Returns (containers, bits): per image the container of :func:`encode`
-    and [bits_z, bits_base, bits_per_layer]."""
+    element its layer.  Returns (containers, bits): per image the container of :func:`encode` and [bits_z, bits_base,
+    bits_per_layer].
+
+    ``coder`` (None: ``model.coder``): "host" brings the symbols, indexes, layer ids and z symbols to the host once and codes
+    z, the base slices and the layers with the threaded stream coder; "device"  codes z and the base
+    slices with one launch each and ALL layers with one more, and fetches lengths, status codes and coded bytes only.  The
+    containers are the same byte for byte.  ``lanes`` = K > 1 splits every stream into K lanes on either
+    coder; such a container carries ``"lanes": K`` (a K = 1 container has no such key) and is read from the argument only,
+    never from ``model.coder_lanes``."""
     from . import _lib as L
     from . import bitstream as bs
     from . import ops
@@ -371,6 +422,7 @@ def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
     _check_variant(model)
     _check_batched(model)
     qs = check_q_list(q_list)
+    coder, K = _check_coder(model, coder), bs.check_lanes(lanes)
     m = model
     B, _, H, W = x.shape
     d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
@@ -383,21 +435,27 @@ def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
         plan.execute(x, 10.0, None, m.use_graph, False)
         layer = torch.empty((B, H // 16, W // 16, d), dtype=torch.uint8, device=x.device)
         ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)              # functions_encode.py:168-196's delta masks
-        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
-        sym, idx, lay, zs = nchw(plan.sym.buf), nchw(plan.idx.buf), nchw(layer), nchw(plan.z_sym.buf)
-    tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
-    zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
-    z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te)
-    sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
-    jobs = [(sl(sym, b, i), sl(idx, b, i)) for i in range(ns) for b in range(B)]
-    jobs += [(sl(sym, b, ns + j), sl(idx, b, ns + j), sl(lay, b, j), k) for k in range(len(qs)) for j in range(ns) for b in range(B)]
-    y_str = bs.encode_streams(jobs, tg)
-    base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
-    prog = [[y_str[(ns + k * ns + j) * B:(ns + k * ns + j + 1) * B] for j in range(ns)] for k in range(len(qs))]
+        if coder == "device":
+            z_str, base, prog = _encode_batch_device(m, plan, layer, len(qs), K)
+        else:
+            nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+            sym, idx, lay, zs = nchw(plan.sym.buf), nchw(plan.idx.buf), nchw(layer), nchw(plan.z_sym.buf)
+    if coder == "host":
+        tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
+        zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
+        z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te, lanes=K)
+        sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
+        jobs = [(sl(sym, b, i), sl(idx, b, i)) for i in range(ns) for b in range(B)]
+        jobs += [(sl(sym, b, ns + j), sl(idx, b, ns + j), sl(lay, b, j), k) for k in range(len(qs)) for j in range(ns) for b in range(B)]
+        y_str = bs.encode_streams(jobs, tg, lanes=K)
+        base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
+        prog = [[y_str[(ns + k * ns + j) * B:(ns + k * ns + j + 1) * B] for j in range(ns)] for k in range(len(qs))]
     containers, bits = [], []
     for b in range(B):
         c = {"q_list": list(q_list), "shape": (H // 64, W // 64), "z": [z_str[b]], "base": [[base[i][b]] for i in range(ns)],
              "progressive": [[prog[k][j][b] for j in range(ns)] for k in range(len(qs))]}
+        if K > 1:
+            c["lanes"] = K
         containers.append(c)
         bits.append(container_bits(c))
     if save_path is not None:
@@ -409,23 +467,22 @@ def encode_batch(model, x, q_list: Sequence[float] = Q_LIST, save_path=None):
 
 
 class ProgressiveDecoder:
-    """Decodes the levels of a batch of containers (all of one shape and quality list) on the fused plans.  Level 0 is
-    the base, level k (1 <= k <= len(q_list)) quality q_list[k-1]; each equals ``forward_single_quality(x, q)`` bit for bit.
-    The base slices and the progressive (mu, sigma) chain run once; a layer's streams are entropy-decoded only the first
-    time a level needs them (:attr:`layers_decoded`)."""
+    """Decodes the levels of a batch of containers (all of one shape, quality list and lanes per stream) on the fused plans.
+    Level 0 is the base, level k (1 <= k <= len(q_list)) quality q_list[k-1]; each equals ``forward_single_quality(x, q)``
+    bit for bit.  The base slices and the progressive (mu, sigma) chain run once; a layer's streams are entropy-decoded
+    only the first time a level needs them (:attr:`layers_decoded`).
 
-    def __init__(self, model, containers):
+    ``coder`` (None: ``model.coder``): "host" decodes on the host's thread pool and copies the symbols up at each level
+    request; "device"  uploads z and the base in one copy, and for a level request the strings of the
+    layers it still needs in one more, decoded by ONE launch into the plan's symbol window; the status codes are read once
+    per :meth:`decode_levels`, after the tail.  Either reads the other's containers."""
+
+    def __init__(self, model, containers, coder: Optional[str] = None):
         _check_variant(model)
         _check_batched(model)
         cs = list(containers)
-        if not cs:
-            raise ValueError("ProgressiveDecoder: no containers")
-        shape, q0 = tuple(cs[0]["shape"]), [float(q) for q in cs[0]["q_list"]]
-        for c in cs[1:]:
-            if tuple(c["shape"]) != shape or [float(q) for q in c["q_list"]] != q0:
-                raise ValueError("ProgressiveDecoder: every container must have the same shape and q_list, got "
-                                 f"{shape} / {q0} and {tuple(c['shape'])} / {list(c['q_list'])}; decode them separately")
-        self.q_list = check_q_list(q0)
+        shape, self.q_list, self.lanes = check_containers(cs)
+        self.coder = _check_coder(model, coder)
         self.m, self.containers, self.B = model, cs, len(cs)
         from .control import _prepare, sweep_groups
         _prepare(model, policy=False)
@@ -434,17 +491,22 @@ class ProgressiveDecoder:
         if len(sweep_groups(1, self.B, self.H, self.W)) > 1:
             raise NotImplementedError(f"ProgressiveDecoder: {self.B} images of {self.H}x{self.W} exceed one plan; decode "
                                       "the containers in smaller batches")
-        self.dp = model._prog_dec_plan(self.B, hz, wz, self.q_list)
-        d, ns, C = model.division_dimension[0], model.ns0, model.dim_chunk
+        self.dp = model._prog_dec_plan(self.B, hz, wz, self.q_list, self.coder)
+        self._pending = []                   # device coder: (upload, first level or None for z + base) not yet checked
         self._front()
-        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
-        self.idx, self.layer = nchw(self.dp.idx_l.buf), nchw(self.dp.layer)
-        self.sym = np.zeros(self.idx.shape, dtype=np.int32)          # [B, d, h, w]: the layers decoded so far
+        if self.coder == "device":           # this decoder's own copy of the layers decoded so far, on the device
+            self.sym = torch.zeros_like(self.dp.sym.buf)
+        else:
+            nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+            self.idx, self.layer = nchw(self.dp.idx_l.buf), nchw(self.dp.layer)
+            self.sym = np.zeros(self.idx.shape, dtype=np.int32)          # [B, d, h, w]: the layers decoded so far
         self.layers_decoded = 0
 
     def _front(self):
         cs, ns = self.containers, self.m.ns0
-        self.dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
+        up = self.dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs], self.lanes)
+        if up is not None:
+            self._pending.append((up, None))
         self.dp.owner = self
 
     def _need(self, k: int):
@@ -452,16 +514,53 @@ class ProgressiveDecoder:
         from . import bitstream as bs
         if not 0 <= k <= len(self.q_list):
             raise ValueError(f"level {k} outside 0..{len(self.q_list)}")
-        if self.dp.owner is not self:                    # another decoder ran on the same plans since
+        restore = self.dp.owner is not self
+        if restore:                                      # another decoder ran on the same plans since
             self._front()
         C, ns = self.m.dim_chunk, self.m.ns0
+        if self.coder == "device":
+            return self._need_device(k, restore)
         if k > self.layers_decoded:
             sl = lambda a, b, j: a[b, j * C:(j + 1) * C]
             jobs = [(c["progressive"][kk][j], sl(self.idx, b, j), sl(self.sym, b, j), sl(self.layer, b, j), kk)
                     for kk in range(self.layers_decoded, k) for j in range(ns) for b, c in enumerate(self.containers)]
-            bs.decode_streams(jobs, bs.Tables.of(self.m.gaussian_conditional))
+            bs.decode_streams(jobs, bs.Tables.of(self.m.gaussian_conditional), lanes=self.lanes)
             self.layers_decoded = k
         self.dp.sym.buf.copy_(torch.from_numpy(self.sym).to(self.dp.device).permute(0, 2, 3, 1))
+
+    def _need_device(self, k: int, restore: bool):
+        """The plan's symbol window holds this decoder's layers: restored from its own copy after another decoder used the
+        plans, then the layers [layers_decoded, k) in one upload and one launch.  No synchronisation."""
+        from . import bitstream as bs
+        dp, k0 = self.dp, self.layers_decoded
+        with dp.runner.on_stream():
+            if restore:
+                dp.sym.buf.copy_(self.sym)
+            if k > k0:
+                strings = [c["progressive"][kk][j] for kk in range(k0, k) for j in range(self.m.ns0) for c in self.containers]
+                up = bs.upload_streams(strings, dp.device, self.lanes)
+                bs.decode_layers_uploaded(up, 0, dp.idx_l, dp.sym, dp.layer, k0, k - k0, self.m.ns0, self.m.dim_chunk,
+                                          bs.DeviceCoderTables.of(self.m.gaussian_conditional, dp.device), self.lanes)
+                self.sym.copy_(dp.sym.buf)
+                self._pending.append((up, k0 + 1))
+                self.layers_decoded = k
+
+    def _check_pending(self):
+        """The one read of the device coder's status codes.  After a failure the decoder starts over at its next call."""
+        from . import bitstream as bs
+        pending, self._pending, B = self._pending, [], self.B
+        try:
+            for up, first_level in pending:
+                if first_level is None:      # string k is z of image k, then the base slices slice-major
+                    bs.check_status(up, B, "ProgressiveDecoder", lambda k: f"z stream (image {k})" if k < B else
+                                    f"base stream (image {k % B}, slice {k // B - 1})")
+                else:
+                    bs.check_layer_status(up, B, self.m.ns0, "ProgressiveDecoder", first_level)
+        except Exception:
+            self.layers_decoded = 0
+            self.sym.zero_()
+            self.dp.owner = None
+            raise
 
     def decode_levels(self, ks: Sequence[int]) -> List[dict]:
         """{"x_hat", "y_hat"} of the batch for every level of ``ks``, the levels > 0 through the batched tail."""
@@ -486,6 +585,8 @@ class ProgressiveDecoder:
                     for i, g in enumerate(gs):
                         out[g] = {"x_hat": t.x_hat[i * self.B:(i + 1) * self.B].clone(),
                                   "y_hat": t.level(t.y_prog, i).torch_nchw().clone()}
+            if self._pending:
+                self._check_pending()
         return out
 
     def decode(self, k: int) -> dict:

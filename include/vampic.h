@@ -839,6 +839,24 @@ int vam_rans_lanes_decode_device(const uint8_t* bytes, const int64_t* byte_offse
                                  const uint8_t* layer, int sel, int B, int h, int w, int ld, int c0, int C, int n_slices, int lanes,
                                  const vam_rans_tables* tables, int32_t* sym_out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ layered launches */
+/* DEVICE pointers.  The device pairs above with a level dimension: one launch covers the n_sel consecutive layer selectors
+ * sel0 .. sel0 + n_sel - 1 (layer ids are uint8: sel0 + n_sel <= 256; layer must not be NULL) over one window.  Stream id =
+ * (k * n_slices + slice) * B + image, and stream (k, slice, image) is exactly what the single-selector call gives for
+ * sel = sel0 + k: the elements with layer == sel0 + k, every other element as symbol 0 in table 0.  lanes = 1: one wave per
+ * stream (vam_rans_encode_device / _decode_device's form); lanes = K > 1: one thread per (stream, lane), regions, lengths
+ * and status per (stream, lane) as in the lanes calls.  n_sel * B * n_slices is at most 2^20.
+ * vam_rans_layers_decode_device: all levels write into the same window, each only the elements of its own layer, so the
+ * writes are disjoint; elements whose layer id is outside [sel0, sel0 + n_sel) are not touched.  With lanes = 1 eight
+ * streams, one wave each, share a workgroup and its LDS copy of the packed tables. */
+int vam_rans_layers_encode_device(const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel0, int n_sel, int B, int h,
+                                  int w, int ld, int c0, int C, int n_slices, int lanes, const vam_rans_tables* tables,
+                                  uint32_t* out_words, long out_cap_words, int32_t* lengths, int32_t* status, void* stream);
+int vam_rans_layers_decode_device(const uint8_t* bytes, const int64_t* byte_offsets, const int32_t* byte_lengths, const int32_t* idx,
+                                  const uint8_t* layer, int sel0, int n_sel, int B, int h, int w, int ld, int c0, int C,
+                                  int n_slices, int lanes, const vam_rans_tables* tables, int32_t* sym_out, int32_t* status,
+                                  void* stream);
+
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
 int vam_graph_end(void* stream, void** graph_exec_out);
