@@ -276,6 +276,22 @@ _SIGNATURES = {
                                                 C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_rans_layers_decode_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 10 + [C.POINTER(VamRansTables), C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "vam_rans_interleaved_encode": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_long, C.c_int]),
+    "vam_rans_interleaved_encode_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_int]),
+    "vam_rans_interleaved_decode_prefix": (C.c_long, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vam_rans_interleaved_decode_prefix_streams": (C.c_int, [C.POINTER(VamRansStream), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vam_rans_interleaved_prefix_bytes": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_rans_interleaved_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.POINTER(VamRansTables),
+                                                     C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_void_p]),
+    "vam_rans_interleaved_decode_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long,
+                                                     C.c_int, C.POINTER(VamRansTables), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     "vam_variance_rank_workspace": (C.c_size_t, [C.c_int] * 4),
     "vam_variance_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

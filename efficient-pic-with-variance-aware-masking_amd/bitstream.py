@@ -195,11 +195,48 @@ def decode_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = No
 
 
 # ---------------------------------------------------------------- byte prefixes of a stream
-def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None) -> List[int]:
+def interleaved_capacity(n: int, lanes: int) -> int:
+    """Bytes that hold any interleaved string of n elements: the K states and two words per element, with the host's slack."""
+    return 8 * n + 8 * lanes + 64
+
+
+def encode_interleaved(symbols: np.ndarray, indexes: np.ndarray, t: Tables, lanes: int) -> bytes:
+    """One stream on ``lanes`` = K INTERLEAVED lanes (vam_rans_interleaved_encode): element i belongs to
+    lane i % K, the K coder states share one word stream whose words lie in the order the decoder reads them, and the K
+    final states stand in front.  Any byte prefix decodes a prefix of the elements (:func:`decode_prefix_streams`);
+    K = 1 is :func:`encode`'s string.  K is not stored in the string."""
+    return encode_interleaved_streams([(symbols, indexes)], t, lanes=lanes)[0]
+
+
+def encode_interleaved_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None, lanes: int = 1) -> List[bytes]:
+    """Many (symbols, indexes) streams as :func:`encode_interleaved` strings in one vam_rans_interleaved_encode_streams call,
+    threaded as :func:`encode_streams`."""
+    K = check_lanes(lanes)
+    keep, arr, caps = [], (L.VamRansStream * max(len(jobs), 1))(), []
+    for j in jobs:
+        s, i = _i32(j[0]), _i32(j[1])
+        assert s.size == i.size
+        caps.append(interleaved_capacity(s.size, K))
+        keep.append((s, i))
+    out = np.empty(sum(caps), dtype=np.uint8)
+    off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    for k, (s, i) in enumerate(keep):
+        arr[k] = L.VamRansStream(s.ctypes.data, None, i.ctypes.data, None, s.size, 0, 0, out.ctypes.data + int(off[k]), caps[k], 0)
+    L.check(L.load().vam_rans_interleaved_encode_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                                         t.offsets.ctypes.data, t.cdf.shape[0], K,
+                                                         coder_threads() if threads is None else int(threads)),
+            "vam_rans_interleaved_encode_streams")
+    return [out[int(off[k]):int(off[k]) + arr[k].n_bytes].tobytes() for k in range(len(jobs))]
+
+
+def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[int] = None, lanes: int = 1) -> List[int]:
     """Tolerant decode of many stream PREFIXES in one vam_rans_decode_prefix_streams call.  ``jobs``: (the first L >= 0
     bytes of a stream, the indexes of the whole stream, out); ``out`` is a writable C-contiguous int32 array of the indexes'
     size.  Per job the number of leading symbols the bytes decode (written to out[:count]; the rest of ``out`` is left
-    untouched): L < 8 gives 0, a symbol whose renormalisation word or bypass nibbles are incomplete is not counted."""
+    untouched): L < 8 gives 0, a symbol whose renormalisation word or bypass nibbles are incomplete is not counted.
+    ``lanes`` = K > 1: the strings are :func:`encode_interleaved`'s (vam_rans_interleaved_decode_prefix_streams): fewer than
+    8 K bytes give 0, and the count is g K + the lowest lane of the last group whose element is incomplete."""
+    K = check_lanes(lanes)
     keep, arr = [], (L.VamRansStream * max(len(jobs), 1))()
     for k, j in enumerate(jobs):
         src = np.frombuffer(j[0], dtype=np.uint8)
@@ -209,24 +246,36 @@ def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[in
         arr[k] = L.VamRansStream(None, o.ctypes.data, i.ctypes.data, None, i.size, 0, 0, src.ctypes.data if src.size else None,
                                  src.size, src.size)
     counts = np.zeros(max(len(jobs), 1), dtype=np.int64)
+    n_threads = coder_threads() if threads is None else int(threads)
+    if K > 1:
+        L.check(L.load().vam_rans_interleaved_decode_prefix_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1],
+                                                                    t.sizes.ctypes.data, t.offsets.ctypes.data, t.cdf.shape[0], K,
+                                                                    n_threads, counts.ctypes.data),
+                "vam_rans_interleaved_decode_prefix_streams")
+        return [int(c) for c in counts[:len(jobs)]]
     L.check(L.load().vam_rans_decode_prefix_streams(arr, len(jobs), t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
-                                                    t.offsets.ctypes.data, t.cdf.shape[0],
-                                                    coder_threads() if threads is None else int(threads), counts.ctypes.data),
+                                                    t.offsets.ctypes.data, t.cdf.shape[0], n_threads, counts.ctypes.data),
             "vam_rans_decode_prefix_streams")
     return [int(c) for c in counts[:len(jobs)]]
 
 
-def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables) -> List[int]:
+def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables, lanes: int = 1) -> List[int]:
     """Per element count of the sorted list ``counts``: the smallest byte length (a multiple of 4) from which
-    :func:`decode_prefix_streams` yields at least that many symbols of ``stream`` (0 for a count of 0).  One decoding pass."""
+    :func:`decode_prefix_streams` yields at least that many symbols of ``stream`` (0 for a count of 0).  One decoding pass.
+    ``lanes`` = K > 1: of an :func:`encode_interleaved` string — 4 x the read position after the last word that any of the
+    first ``count`` elements reads, 8 K when they read none."""
+    K = check_lanes(lanes)
     src = np.frombuffer(stream, dtype=np.uint8)
     i = _i32(indexes)
     want = np.ascontiguousarray([int(c) for c in counts], dtype=np.int64)
     out = np.zeros(max(want.size, 1), dtype=np.int64)
-    L.check(L.load().vam_rans_prefix_bytes(src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size,
-                                           t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data, t.offsets.ctypes.data,
-                                           t.cdf.shape[0], want.ctypes.data if want.size else None, want.size, out.ctypes.data),
-            "vam_rans_prefix_bytes")
+    head = (src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size, t.cdf.ctypes.data, t.cdf.shape[1],
+            t.sizes.ctypes.data, t.offsets.ctypes.data, t.cdf.shape[0])
+    tail = (want.ctypes.data if want.size else None, want.size, out.ctypes.data)
+    if K > 1:
+        L.check(L.load().vam_rans_interleaved_prefix_bytes(*head, K, *tail), "vam_rans_interleaved_prefix_bytes")
+    else:
+        L.check(L.load().vam_rans_prefix_bytes(*head, *tail), "vam_rans_prefix_bytes")
     return [int(b) for b in out[:want.size]]
 
 
@@ -701,6 +750,71 @@ def check_layer_status(up: DeviceStreams, B: int, n_slices: int, what: str = "va
     msg = layer_status_message(up.status[:up.n * up.lanes].cpu().numpy(), B, n_slices, what, up.lanes, first_level)
     if msg:
         raise L.VamError(msg)
+
+
+# ---------------------------------------------------------------- embedded streams on the device coder
+def encode_embedded_device(r_sym: torch.Tensor, r_idx: torch.Tensor, tables: DeviceCoderTables, lanes: int = 1,
+                           count: Optional[torch.Tensor] = None) -> Tuple[List[bytes], np.ndarray]:
+    """The flat ranked buffers ``r_sym`` / ``r_idx`` (contiguous int32 [..., n] on the device, every leading index one
+    stream) as :func:`encode_interleaved` strings (K = 1: :func:`encode`'s) in ONE vam_rans_interleaved_encode_device launch
+    on the current stream, packed by vam_rans_pack_device; then one copy of lengths, status codes and marks and one of the
+    coded bytes.  ``count``: int32 [L, ...streams] on the device, non-decreasing in L; the second result is then
+    :func:`prefix_bytes` of every count, int64 [L, n_streams], taken from the encoder's own word positions (None: [0, n_streams])."""
+    from . import ops
+    K = check_lanes(lanes)
+    for a in (r_sym, r_idx):
+        if a.dtype != torch.int32 or not a.is_contiguous() or a.dim() < 1 or tuple(a.shape) != tuple(r_sym.shape) or not a.is_cuda:
+            raise ValueError("device coder: the ranked symbols and indexes are contiguous int32 device buffers of one shape")
+    n = int(r_sym.shape[-1])
+    ns = int(np.prod(r_sym.shape[:-1]))
+    n_marks = 0 if count is None else int(count.shape[0])
+    if count is not None and (count.dtype != torch.int32 or not count.is_contiguous() or count.numel() != n_marks * ns):
+        raise ValueError(f"device coder: count is a contiguous int32 [L, {ns}] buffer")
+    cap = 2 * n + 2 * K + 16
+    dev = r_sym.device
+    regions = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    packed = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    meta = torch.empty((2 + n_marks, ns), dtype=torch.int32, device=dev)          # lengths in words, status, the marks' bytes
+    offs = torch.empty(ns + 1, dtype=torch.int64, device=dev)
+    lib, st = L.load(), ops.stream_ptr()
+    L.check(lib.vam_rans_interleaved_encode_device(r_sym.data_ptr(), r_idx.data_ptr(), ns, n, K, C.byref(tables.struct),
+                                                   regions.data_ptr(), cap, meta[0].data_ptr(), meta[1].data_ptr(),
+                                                   count.data_ptr() if n_marks else None, n_marks,
+                                                   meta[2].data_ptr() if n_marks else None, st), "vam_rans_interleaved_encode_device")
+    L.check(lib.vam_rans_pack_device(regions.data_ptr(), cap, meta[0].data_ptr(), ns, packed.data_ptr(), ns * cap,
+                                     offs.data_ptr(), st), "vam_rans_pack_device")
+    m = meta.cpu().numpy()
+    bad = np.flatnonzero(m[1])
+    if bad.size:
+        raise L.VamError(f"vam_rans_interleaved_encode_device: embedded stream {int(bad[0])}: {status_text(int(m[1][bad[0]]))}"
+                         + (f" ({bad.size} streams failed)" if bad.size > 1 else ""))
+    off = np.concatenate([[0], np.cumsum(m[0].astype(np.int64))]) * 4
+    data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
+    return [data[off[k]:off[k + 1]].tobytes() for k in range(ns)], m[2:].astype(np.int64)
+
+
+def decode_embedded_uploaded(up: DeviceStreams, first: int, r_idx: torch.Tensor, ranked: torch.Tensor, tables: DeviceCoderTables,
+                             lanes: int, meta: torch.Tensor):
+    """One vam_rans_interleaved_decode_device launch on the current stream, no synchronisation: the strings of ``up`` from
+    ``first`` on, one per stream of the flat buffers ``r_idx`` / ``ranked`` (contiguous int32 [..., n]), each the first bytes
+    of an :func:`encode_interleaved` string of ``lanes`` = K, decoded tolerantly.  ``ranked`` receives the decoded elements
+    and 0 beyond them; ``meta`` (int32 [2, n_streams] on the device) the available counts and the status codes."""
+    from . import ops
+    K = check_lanes(lanes)
+    for a in (r_idx, ranked):
+        if a.dtype != torch.int32 or not a.is_contiguous() or tuple(a.shape) != tuple(r_idx.shape):
+            raise ValueError("device coder: the ranked symbols and indexes are contiguous int32 device buffers of one shape")
+    n = int(r_idx.shape[-1])
+    ns = int(np.prod(r_idx.shape[:-1]))
+    if first < 0 or first + ns > up.n:
+        raise ValueError(f"device coder: strings {first} .. {first + ns} of {up.n} uploaded")
+    if meta.dtype != torch.int32 or tuple(meta.shape) != (2, ns) or not meta.is_contiguous():
+        raise ValueError(f"device coder: meta is a contiguous int32 [2, {ns}] buffer")
+    total = up.buf.numel() - (up.bytes_ptr - up.buf.data_ptr())
+    L.check(L.load().vam_rans_interleaved_decode_device(up.bytes_ptr, total, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                                        r_idx.data_ptr(), ns, n, K, C.byref(tables.struct), ranked.data_ptr(),
+                                                        meta[0].data_ptr(), meta[1].data_ptr(), ops.stream_ptr()),
+            "vam_rans_interleaved_decode_device")
 
 
 def sigma0_index(scale_table) -> int:

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/vampic.h"
+#include "rans_core.h"
 
 namespace vam {
 void set_error(const char* fmt, ...);
@@ -432,6 +433,152 @@ int vam_rans_prefix_bytes(const uint8_t* in, long n_bytes, const int32_t* indexe
   for (int q = 0; q < n_counts; ++q)
     if (bytes_out[q] < 0) {
       set_error("vam_rans_prefix_bytes: %ld symbols asked for, the %ld bytes given decode %ld of %ld", counts[q], n_bytes, got, n);
+      return VAM_EINVAL;
+    }
+  return VAM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- interleaved lanes (rans_core.h)
+// The host exports of the interleaved format drive rans_core.h's one-thread functions; K = 1 gives the strings, counts
+// and byte marks of the functions above.
+namespace {
+
+namespace R = vam_rans;
+
+const char* ilv_status_text(int st) {
+  switch (st) {
+    case R::kBadIndex: return "index out of range";
+    case R::kBadTable: return "cdf size invalid";
+    case R::kOverflow: return "output buffer too small";
+    case R::kZeroFreq: return "zero-frequency symbol (cdf table not normalised)";
+    case R::kBadStream: return "bad arguments (lanes is a power of two in 1 .. 64, the string word-aligned)";
+    default: return "unknown status";
+  }
+}
+
+long ilv_encode_one(const char* what, const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                    const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap, int lanes) {
+  if (!symbols || !indexes || !cdfs || !cdf_sizes || !offsets || !out || n < 0 || n > (1l << 28) || n_cdfs < 1) {
+    set_error("%s: bad arguments", what);
+    return VAM_EINVAL;
+  }
+  if (!R::lanes_valid(lanes)) {
+    set_error("%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+    return VAM_EINVAL;
+  }
+  std::vector<uint32_t> region((size_t)R::interleaved_cap_words(n, lanes));
+  long words = 0;
+  const int32_t st = R::interleaved_encode(symbols, indexes, n, R::Flat{}, lanes, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                                           region.data(), (long)region.size(), &words);
+  if (st) {
+    set_error("%s: %s", what, ilv_status_text(st));
+    return VAM_EINVAL;
+  }
+  if (words * 4 > out_cap) {
+    set_error("%s: output buffer too small (%ld > %ld)", what, words * 4, out_cap);
+    return VAM_EINVAL;
+  }
+  std::memcpy(out, region.data() + region.size() - words, (size_t)words * 4);
+  return words * 4;
+}
+
+// Returns the count (< 0: bad arguments, or a status when status_out is NULL).
+long ilv_decode_one(const char* what, const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
+                    int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes, int32_t* out,
+                    int32_t* status_out, const long* marks, int n_marks, long* mark_bytes) {
+  if (status_out) *status_out = 0;
+  if ((!in && n_bytes > 0) || (!indexes && n > 0) || !cdfs || !cdf_sizes || !offsets || n < 0 || n_bytes < 0 || n_cdfs < 1 ||
+      n_marks < 0 || (n_marks > 0 && (!marks || !mark_bytes))) {
+    set_error("%s: bad arguments (prefix of %ld bytes)", what, n_bytes);
+    return VAM_EINVAL;
+  }
+  if (!R::lanes_valid(lanes)) {
+    set_error("%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+    return VAM_EINVAL;
+  }
+  for (int q = 0; q < n_marks; ++q)
+    if (marks[q] < 0 || (q > 0 && marks[q] < marks[q - 1])) {
+      set_error("%s: counts must be >= 0 and sorted, got %ld at %d", what, marks[q], q);
+      return VAM_EINVAL;
+    }
+  std::vector<uint32_t> words((size_t)n_bytes / 4);         // aligned copy of the whole words
+  if (!words.empty()) std::memcpy(words.data(), in, words.size() * 4);
+  long available = 0;
+  const int32_t st = R::interleaved_decode(words.empty() ? nullptr : words.data(), (long)words.size() * 4, lanes, indexes, n, R::Flat{},
+                                           R::Int32Rows{cdfs, cdf_stride}, cdf_stride, cdf_sizes, offsets, n_cdfs, out, &available,
+                                           marks, n_marks, mark_bytes);
+  if (status_out) *status_out = st;
+  else if (st) {
+    set_error("%s: %s after %ld symbols", what, ilv_status_text(st), available);
+    return VAM_EINVAL;
+  }
+  return available;
+}
+
+}  // namespace
+
+extern "C" {
+
+long vam_rans_interleaved_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                                 const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap, int lanes) {
+  return ilv_encode_one("vam_rans_interleaved_encode", symbols, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, out, out_cap,
+                        lanes);
+}
+
+int vam_rans_interleaved_encode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs, int cdf_stride,
+                                        const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes, int n_threads) {
+  if (n_streams > 0 && !streams) {
+    set_error("vam_rans_interleaved_encode_streams: bad arguments");
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, "vam_rans_interleaved_encode_streams", [&](int i) -> long {
+    vam_rans_stream& s = streams[i];
+    if (s.layer) {
+      set_error("vam_rans_interleaved_encode_streams: an embedded stream carries no layer selection");
+      return s.n_bytes = VAM_EINVAL;
+    }
+    return s.n_bytes = ilv_encode_one("vam_rans_interleaved_encode", s.symbols, s.indexes, s.n, cdfs, cdf_stride, cdf_sizes, offsets,
+                                      n_cdfs, s.bytes, s.capacity, lanes);
+  });
+}
+
+long vam_rans_interleaved_decode_prefix(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
+                                        int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes,
+                                        int32_t* out, int32_t* status_out) {
+  return ilv_decode_one("vam_rans_interleaved_decode_prefix", in, n_bytes, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs,
+                        lanes, out, status_out, nullptr, 0, nullptr);
+}
+
+int vam_rans_interleaved_decode_prefix_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs, int cdf_stride,
+                                               const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes, int n_threads,
+                                               long* counts_out) {
+  if (n_streams > 0 && (!streams || !counts_out)) {
+    set_error("vam_rans_interleaved_decode_prefix_streams: bad arguments");
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, "vam_rans_interleaved_decode_prefix_streams", [&](int i) -> long {
+    const vam_rans_stream& s = streams[i];
+    if (s.layer) {
+      set_error("vam_rans_interleaved_decode_prefix_streams: an embedded stream carries no layer selection");
+      return VAM_EINVAL;
+    }
+    return counts_out[i] = ilv_decode_one("vam_rans_interleaved_decode_prefix", s.bytes, s.n_bytes, s.indexes, s.n, cdfs, cdf_stride,
+                                          cdf_sizes, offsets, n_cdfs, lanes, s.symbols_out, nullptr, nullptr, 0, nullptr);
+  });
+}
+
+int vam_rans_interleaved_prefix_bytes(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
+                                      int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes,
+                                      const long* counts, int n_counts, long* bytes_out) {
+  const long got = ilv_decode_one("vam_rans_interleaved_prefix_bytes", in, n_bytes, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets,
+                                  n_cdfs, lanes, nullptr, nullptr, counts, n_counts, bytes_out);
+  if (got < 0) return (int)got;
+  for (int q = 0; q < n_counts; ++q)
+    if (bytes_out[q] < 0) {
+      set_error("vam_rans_interleaved_prefix_bytes: %ld symbols asked for, the %ld bytes given decode %ld of %ld", counts[q], n_bytes,
+                got, n);
       return VAM_EINVAL;
     }
   return VAM_OK;

@@ -407,4 +407,198 @@ VAM_RANS_HD int32_t lanes_decode_stream(const uint32_t* words, long n_bytes, int
   return first_bad;
 }
 
+// ---------------------------------------------------------------- interleaved lanes
+// A stream of n elements on K interleaved lanes, K as above: element i belongs to lane i % K and group i / K, and the K
+// coder states share ONE word stream.  The string is the K final states in lane order (two words each, as enc_finish
+// writes one), then the renormalisation words in the order the decoder reads them: groups ascending; inside a group the
+// rounds t = 0, 1, ..; in round t every lane that still has a get t updates its state, then the lanes whose state fell
+// below 2^31 take one word each in ascending lane order.  Get 0 of an element is the table symbol, the count nibbles and
+// the raw nibbles follow when it is the escape (dec_element's order).  The encoder is the mirror: groups, rounds and lanes
+// descending, words stored backwards.  So a prefix of the words decodes a prefix of the elements, and K == 1 is the
+// stream above byte for byte.
+//
+// The steps here split an element into its gets / puts so that a driver can renormalise between them: the host drivers
+// below run all lanes on one thread, rans_device.hip runs one thread per lane and finds a lane's word by a wave ballot.
+
+// Put t of an element, numbered like the decoder's gets: 0 = the table symbol, 1 .. = the count nibbles ([15] * (n / 15),
+// then n % 15), then the raw nibbles 0 .. n_bypass - 1.  An element has put_gets(u) <= kMaxGets of them.
+constexpr int kMaxGets = 2 + kMaxRawNibbles;                // classify gives n_bypass <= 8: one count nibble
+VAM_RANS_HD int put_gets(const Put& u) { return u.n_bypass < 0 ? 1 : 2 + u.n_bypass / (int)kMaxBypass + u.n_bypass; }
+
+VAM_RANS_HD uint32_t put_nibble(const Put& u, int t) {
+  const int nc = u.n_bypass / (int)kMaxBypass + 1;          // count nibbles
+  if (t < nc) return kMaxBypass;
+  if (t == nc) return (uint32_t)u.n_bypass % kMaxBypass;
+  return (u.raw >> ((t - nc - 1) * kBypassBits)) & kMaxBypass;
+}
+
+// Whether put t flushes a word first: the bounds of enc_put and enc_put_bits.
+VAM_RANS_HD bool put_flushes(const Enc& e, const Put& u, int t) {
+  return t == 0 ? e.x >= ((uint64_t)(u.start_freq >> 16) << (31 - kPrecision + 32))
+                : e.x >= (1ull << (31 - kPrecision + 32 + kPrecision - kBypassBits));
+}
+
+VAM_RANS_HD void enc_put_step(Enc& e, const Put& u, int t) {
+  if (t == 0) enc_put(e, u.start_freq & 0xFFFFu, u.start_freq >> 16, u.rcp);
+  else enc_put_bits(e, put_nibble(u, t));
+}
+
+// Words that hold any string: the K states and at most two words per element (16 + 4 * 9 bits), with the host's slack.
+VAM_RANS_HD long interleaved_cap_words(long n, int K) { return 2 * n + 2 * K + 16; }
+
+// All lanes on one thread.  Words are written backwards from region + cap_words; the string is the region's tail.
+template <class A>
+VAM_RANS_HD int32_t interleaved_encode(const int32_t* sym, const int32_t* idx, long n, const A& at, int K, const int32_t* cdfs,
+                                       int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs,
+                                       uint32_t* region, long cap_words, long* n_words) {
+  *n_words = 0;
+  if (!lanes_valid(K) || n < 0) return kBadStream;
+  Enc e;
+  enc_init(e, region, region + cap_words);
+  uint64_t xs[kMaxLanes];
+  Put us[kMaxLanes];
+  for (int l = 0; l < K; ++l) xs[l] = kRansL;
+  for (long g = (n + K - 1) / K - 1; g >= 0; --g) {
+    const int m = (int)(n - g * K < K ? n - g * K : K);      // lanes with an element in this group
+    int rounds = 0;
+    for (int l = 0; l < m; ++l) {
+      const long o = at.off(g * K + l);
+      const int32_t st = classify(sym[o], idx ? idx[o] : at.chan(g * K + l), cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, us[l]);
+      if (st) return st;
+      if (put_gets(us[l]) > rounds) rounds = put_gets(us[l]);
+    }
+    for (int t = rounds - 1; t >= 0; --t)
+      for (int l = m - 1; l >= 0; --l) {
+        if (put_gets(us[l]) <= t) continue;
+        e.x = xs[l];
+        enc_put_step(e, us[l], t);
+        if (e.status) return e.status;
+        xs[l] = e.x;
+      }
+  }
+  if (e.p - e.lo < 2l * K) return kOverflow;
+  e.p -= 2l * K;
+  for (int l = 0; l < K; ++l) { e.p[2 * l] = (uint32_t)xs[l]; e.p[2 * l + 1] = (uint32_t)(xs[l] >> 32); }
+  *n_words = (long)(region + cap_words - e.p);
+  return kOk;
+}
+
+// One lane's element in flight: dec_element cut into its gets.  get_step does one get's state update (dec_element's
+// arithmetic) and says whether a renormalisation word is due; the driver supplies it (x = x << 32 | word) or fails the lane.
+enum GetPhase : int32_t { kGetSymbol = 0, kGetCount = 1, kGetRaw = 2, kGetDone = 3 };
+struct Get {
+  uint64_t x;
+  uint32_t n_bypass, raw, j;
+  int32_t value;       // relative to the table's offset; valid once phase == kGetDone with status == 0
+  int32_t phase;
+  int32_t status;
+};
+
+template <class F>
+VAM_RANS_HD bool get_step(Get& g, const F& find, int sz) {
+  const int max_value = sz - 2;
+  if (g.phase == kGetSymbol) {
+    const uint32_t cum = (uint32_t)(g.x & ((1u << kPrecision) - 1));
+    uint32_t start, freq;
+    const int s = find(cum, start, freq);
+    if (freq == 0 || freq > (1u << kPrecision) || start > cum) { g.status = kBadTable; g.phase = kGetDone; return false; }
+    g.x = (uint64_t)freq * (g.x >> kPrecision) + cum - start;
+    g.value = s;
+    g.n_bypass = 0; g.raw = 0; g.j = 0;
+    g.phase = s != max_value ? kGetDone : kGetCount;
+  } else {
+    const uint32_t nib = (uint32_t)(g.x & kMaxBypass);
+    g.x >>= kBypassBits;
+    if (g.phase == kGetCount) {
+      g.n_bypass += nib;
+      if (nib != kMaxBypass) g.phase = g.n_bypass ? kGetRaw : kGetDone;
+    } else {
+      if (g.j < (uint32_t)kMaxRawNibbles) g.raw |= nib << (g.j * kBypassBits);
+      if (++g.j >= g.n_bypass) g.phase = kGetDone;
+    }
+    if (g.phase == kGetDone) {
+      const uint32_t half = g.raw >> 1;                      // unsigned: a corrupt stream may not overflow an int
+      g.value = (int32_t)((g.raw & 1) ? ~half : half + (uint32_t)max_value);
+    }
+  }
+  return g.x < kRansL;
+}
+
+// Tolerant prefix decode, all lanes on one thread: `words` are the first floor(n_bytes / 4) words of a string.  With fewer
+// than 2 K words nothing decodes.  A lane that needs a word past the prefix fails, and so does every later request; the
+// other lanes of that group finish the gets that need no word, and decoding ends with that group:
+// *available = g K + the lowest failed lane of group g (n when no lane failed).  out (may be NULL) receives the elements
+// below *available, the rest of it is left untouched.  A bad index or table fails its lane the same way and is the status
+// returned (that of the lowest such lane of the last group); running out of words is no error.
+// marks (may be NULL): n_marks sorted counts; mark_bytes[m] = 4 * the read position after the last word any of the
+// elements 0 .. marks[m] - 1 reads (8 K when they read none, 0 for a count of 0), -1 for a count beyond *available.
+template <class A, class T>
+VAM_RANS_HD int32_t interleaved_decode(const uint32_t* words, long n_bytes, int K, const int32_t* idx, long n, const A& at,
+                                       const T& rows, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs,
+                                       int32_t* out, long* available, const long* marks, int n_marks, long* mark_bytes) {
+  *available = 0;
+  int mk = 0;
+  for (int q = 0; q < n_marks; ++q) mark_bytes[q] = -1;
+  while (mk < n_marks && marks[mk] <= 0) mark_bytes[mk++] = 0;
+  if (!lanes_valid(K) || n < 0 || n_bytes < 0) return kBadStream;
+  const long W = n_bytes / 4;
+  if (W > 0 && (!words || ((uintptr_t)words & 3))) return kBadStream;
+  if (W < 2l * K) return kOk;
+  using Find = decltype(rows(0, 2));
+  Get gs[kMaxLanes];
+  for (int l = 0; l < K; ++l) gs[l].x = (uint64_t)words[2 * l] | ((uint64_t)words[2 * l + 1] << 32);
+  long pos = 2l * K, reach = 2l * K;                        // next word; read position after the last word of the elements so far
+  for (long g = 0; g * K < n; ++g) {
+    const int m = (int)(n - g * K < K ? n - g * K : K);
+    Find find[kMaxLanes];
+    int sz[kMaxLanes], ci[kMaxLanes];
+    long last[kMaxLanes];
+    bool active[kMaxLanes], failed[kMaxLanes], need[kMaxLanes];
+    int n_active = 0;
+    for (int l = 0; l < m; ++l) {
+      Get& t = gs[l];
+      t.status = kOk; t.phase = kGetSymbol; t.value = 0;
+      last[l] = 0; failed[l] = false; sz[l] = 2;
+      ci[l] = idx ? idx[at.off(g * K + l)] : at.chan(g * K + l);
+      if (ci[l] < 0 || ci[l] >= n_cdfs) t.status = kBadIndex;
+      else {
+        sz[l] = cdf_sizes[ci[l]];
+        if (sz[l] - 2 < 0 || sz[l] - 1 >= cdf_stride) t.status = kBadTable;
+      }
+      find[l] = rows(t.status ? 0 : ci[l], t.status ? 2 : sz[l]);
+      failed[l] = t.status != 0;
+      active[l] = !failed[l];
+      n_active += active[l];
+    }
+    while (n_active > 0) {                                    // one round: the updates, then the words in lane order
+      for (int l = 0; l < m; ++l) {
+        need[l] = active[l] && get_step(gs[l], find[l], sz[l]);
+        if (active[l] && gs[l].status) { failed[l] = true; need[l] = false; }
+      }
+      for (int l = 0; l < m; ++l) {
+        if (!active[l]) continue;
+        if (need[l]) {
+          if (pos < W) { gs[l].x = (gs[l].x << 32) | words[pos]; last[l] = ++pos; }
+          else failed[l] = true;
+        }
+        if (failed[l] || gs[l].phase == kGetDone) { active[l] = false; --n_active; }
+      }
+    }
+    int first = 0;
+    while (first < m && !failed[first]) ++first;
+    for (int l = 0; l < first; ++l) {
+      if (out) out[at.off(g * K + l)] = (int32_t)((uint32_t)gs[l].value + (uint32_t)offsets[ci[l]]);
+      if (last[l] > reach) reach = last[l];
+      while (mk < n_marks && marks[mk] <= g * K + l + 1) mark_bytes[mk++] = 4 * reach;
+    }
+    *available = g * K + first;
+    if (first < m) {
+      for (int l = first; l < m; ++l)
+        if (gs[l].status) return gs[l].status;
+      return kOk;
+    }
+  }
+  return kOk;
+}
+
 }  // namespace vam_rans

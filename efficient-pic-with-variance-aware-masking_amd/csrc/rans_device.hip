@@ -15,6 +15,7 @@
 #include "common.h"
 #include "rans_core.h"
 #include <cstring>
+#include <type_traits>
 
 using namespace vam;
 namespace R = vam_rans;
@@ -332,6 +333,204 @@ __global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecAr
   else
     a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, idx, layer, sel, n, at, R::Int32Rows{a.t.cdf, a.t.stride},
                                    a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, a.out + img);
+}
+
+// ---------------------------------------------------------------- interleaved lanes
+// One thread per (stream, lane) as above, thread id = stream id * K + lane, but the K lanes of a stream share ONE word
+// stream: in every round the lanes that flush (encode) or fetch (decode) are a ballot, a stream's K bits of it are cut out
+// with the stream's first wave lane (`shift`), and a lane's word position is the stream's position plus the popcount of the
+// flushing / fetching lanes above (encode: words are stored backwards) or below it (decode).  Every lane of a stream
+// carries the stream's position itself, so nothing but the ballot crosses a lane.  All streams of a launch have the same
+// n, so the group loop is wave-uniform; the rounds of a group run until no lane of the wave has a put / get left.
+// No thread leaves early: a lane past the last stream stays, inactive, so that the wave stays converged at the ballots.
+struct IlvEncArgs {
+  const int32_t* sym;
+  const int32_t* idx;
+  int n_streams;
+  long n;
+  int K;
+  vam_rans_tables t;
+  uint32_t* out;
+  long cap;
+  int32_t* lengths;
+  int32_t* status;
+  const int32_t* counts;     // [n_marks][n_streams], non-decreasing in the mark
+  int n_marks;
+  int32_t* mark_bytes;       // [n_marks][n_streams]
+};
+
+__global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncArgs a) {
+  typedef unsigned long long u64;
+  const int tid = threadIdx.x, gid = blockIdx.x * kWave + tid, K = a.K;
+  const int str = gid / K, lane = gid - str * K, shift = tid - lane;
+  const bool valid = str < a.n_streams;
+  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
+  const u64 above = kmask & ~((2ull << lane) - 1);           // the stream's lanes above this one
+  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  uint32_t* region = a.out + (long)(valid ? str : 0) * a.cap;
+  uint32_t* top = region + a.cap;                            // the stream's next word goes below top
+  R::Enc e;
+  R::enc_init(e, region, top);
+  long emitted = 0;                                          // words of the stream so far
+  int m_hi = valid ? a.n_marks : 0;                          // marks 0 .. m_hi - 1 have seen no flush of theirs yet
+  long c_top = m_hi > 0 ? a.counts[(long)(m_hi - 1) * a.n_streams + str] : 0;
+  int32_t st = 0;
+  bool alive = valid;
+  for (long g = (n + K - 1) / K - 1; g >= 0; --g) {
+    const long i = g * K + lane;
+    R::Put u{0, 0, 0, -1};
+    int gets = 0;
+    if (alive && i < n) {
+      st = R::classify(a.sym[base + i], a.idx[base + i], a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+      gets = st ? 0 : R::put_gets(u);
+    }
+    if ((__ballot(st != 0) >> shift) & kmask) alive = false;
+    if (!alive) gets = 0;
+    for (int t = R::kMaxGets - 1; t >= 0; --t) {
+      const bool act = gets > t;
+      if (!__ballot(act)) continue;
+      const bool fl = act && R::put_flushes(e, u, t);
+      const u64 sub = (__ballot(fl) >> shift) & kmask;
+      while (m_hi > 0 && sub) {                               // the first flush on behalf of an element below a mark's count
+        const long c = c_top > 0 ? c_top : 0, gq = c / K;
+        const u64 mine = g < gq ? sub : g == gq ? sub & ((1ull << (int)(c - gq * K)) - 1) : 0;
+        if (!mine) break;
+        const int hi = 63 - __clzll(mine);                    // descending lanes: the highest flushes first
+        if (lane == 0) a.mark_bytes[(long)(m_hi - 1) * a.n_streams + str] = (int32_t)(emitted + __popcll(sub & ~((2ull << hi) - 1)));
+        --m_hi;
+        c_top = m_hi > 0 ? a.counts[(long)(m_hi - 1) * a.n_streams + str] : 0;
+      }
+      if (fl) e.p = top - __popcll(sub & above);              // enc_flush_word stores at --p
+      if (act) R::enc_put_step(e, u, t);
+      top -= __popcll(sub);
+      emitted += __popcll(sub);
+    }
+    if ((__ballot(e.status != 0) >> shift) & kmask) alive = false;
+  }
+  const int32_t own = st ? st : e.status;
+  const u64 bad = (__ballot(own != 0) >> shift) & kmask;
+  int32_t sst = __shfl(own, bad ? shift + __ffsll(bad) - 1 : shift);     // the stream's status: its lowest failing lane's
+  if (!bad) sst = 0;
+  long words = 0;
+  if (valid && !sst) {
+    if (top - region < 2l * K) sst = R::kOverflow;
+    else {
+      uint32_t* s = top - 2l * K;
+      s[2 * lane] = (uint32_t)e.x;
+      s[2 * lane + 1] = (uint32_t)(e.x >> 32);
+      words = (long)(region + a.cap - s);
+    }
+  }
+  if (valid && lane == 0) {
+    a.lengths[str] = sst ? 0 : (int32_t)words;
+    a.status[str] = sst;
+    for (int m = 0; m < a.n_marks; ++m) {                     // words before the mark's first flush -> the prefix's bytes
+      const long at = (long)m * a.n_streams + str;
+      if (sst) a.mark_bytes[at] = 0;
+      else if (m < m_hi) a.mark_bytes[at] = a.counts[at] > 0 ? 8 * K : 0;
+      else a.mark_bytes[at] = (int32_t)(4 * (words - a.mark_bytes[at]));
+    }
+  }
+}
+
+struct IlvDecArgs {
+  const uint8_t* bytes;
+  long bytes_total;
+  const int64_t* byte_offsets;
+  const int32_t* byte_lengths;
+  const int32_t* idx;
+  int n_streams;
+  long n;
+  int K;
+  vam_rans_tables t;
+  int32_t* out;
+  int32_t* available;
+  int32_t* status;
+};
+
+template <bool kPacked>
+__global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(IlvDecArgs a) {
+  typedef unsigned long long u64;
+  using Find = R::TableSearch<typename std::conditional<kPacked, uint16_t, int32_t>::type>;
+  extern __shared__ uint4 lds_raw[];
+  if (kPacked) {
+    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
+    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
+    __syncthreads();
+  }
+  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, K = a.K;
+  const int str = gid / K, lane = gid - str * K, shift = (int)(threadIdx.x & (kWave - 1)) - lane;
+  const bool valid = str < a.n_streams;
+  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
+  const u64 below = (1ull << lane) - 1;
+  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  const uint32_t* words = nullptr;
+  long W = 0;
+  int32_t sst = 0;
+  if (valid) {
+    const int64_t boff = a.byte_offsets[str];
+    const long len = a.byte_lengths[str];
+    if (boff < 0 || (boff & 3) || len < 0 || boff > a.bytes_total || len > a.bytes_total - boff) sst = R::kBadStream;
+    else { words = reinterpret_cast<const uint32_t*>(a.bytes + boff); W = len / 4; }
+  }
+  bool alive = valid && !sst && W >= 2l * K;
+  long avail = alive ? n : 0, pos = 2l * K;
+  R::Get gt{0, 0, 0, 0, 0, R::kGetDone, 0};
+  if (alive) gt.x = (uint64_t)words[2 * lane] | ((uint64_t)words[2 * lane + 1] << 32);
+  for (long g = 0; g * K < n; ++g) {
+    const long i = g * K + lane;
+    const bool has = valid && i < n, was_alive = alive;
+    int32_t lst = 0;                                          // what failed this lane, when it is an error
+    int sz = 2, offv = 0;
+    Find find{nullptr, 2, kPacked};
+    bool act = false, failed = false;
+    if (alive && has) {
+      const int ci = a.idx[base + i];
+      if (ci < 0 || ci >= a.t.n_cdfs) lst = R::kBadIndex;
+      else {
+        sz = a.t.sizes[ci];
+        if (sz - 2 < 0 || sz - 1 >= a.t.stride) lst = R::kBadTable;
+        else {
+          offv = a.t.offsets[ci];
+          if constexpr (kPacked) find = R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}(ci, sz);
+          else find = R::Int32Rows{a.t.cdf, a.t.stride}(ci, sz);
+        }
+      }
+      failed = lst != 0;
+      act = !failed;
+      gt.phase = R::kGetSymbol;
+      gt.status = 0;
+      gt.value = 0;
+    }
+    while (__ballot(act)) {                                   // one round: the updates, then the words in lane order
+      bool need = false;
+      if (act) {
+        need = R::get_step(gt, find, sz);
+        if (gt.status) { lst = gt.status; failed = true; need = false; }
+      }
+      const u64 sub = (__ballot(need) >> shift) & kmask;
+      if (need) {
+        const long p = pos + __popcll(sub & below);
+        if (p < W) gt.x = (gt.x << 32) | words[p];
+        else failed = true;                                   // past the prefix: so is every later request
+      }
+      pos += __popcll(sub);
+      if (failed || gt.phase == R::kGetDone) act = false;
+    }
+    const u64 fsub = (__ballot(failed) >> shift) & kmask, esub = (__ballot(lst != 0) >> shift) & kmask;
+    const int first = fsub ? __ffsll(fsub) - 1 : K;
+    const int32_t err = __shfl(lst, esub ? shift + __ffsll(esub) - 1 : shift);
+    if (has) a.out[base + i] = was_alive && lane < first ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+    if (was_alive && fsub) {
+      alive = false;
+      avail = g * K + first;
+      sst = esub ? err : 0;
+    }
+  }
+  if (valid && lane == 0) {
+    a.available[str] = (int32_t)avail;
+    a.status[str] = sst;
+  }
 }
 
 int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices, int n_sel = 1) {
@@ -673,6 +872,54 @@ int vam_rans_layers_decode_device(const uint8_t* bytes, const int64_t* byte_offs
                                       sym_out, status, stream);
   return launch_lanes_decode(what, bytes, byte_offsets, byte_lengths, idx, layer, sel0, n_sel, B, h, w, ld, c0, C, n_slices, lanes, tables,
                              sym_out, status, stream);
+}
+
+// ---------------------------------------------------------------- interleaved lanes
+int vam_rans_interleaved_encode_device(const int32_t* sym, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words, int32_t* lengths,
+                                       int32_t* status, const int32_t* counts, int n_marks, int32_t* mark_bytes, void* stream) {
+  const char* what = "vam_rans_interleaved_encode_device";
+  VAM_REQUIRE(sym && idx && out_words && lengths && status, "%s: need sym, idx, out_words, lengths, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
+              what, n_streams, n);
+  VAM_REQUIRE(n_marks >= 0 && n_marks <= 4096 && (n_marks == 0 || (counts && mark_bytes)), "%s: marks need counts and mark_bytes", what);
+  if (int rc = check_tables(what, tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2l * lanes && out_cap_words < (1l << 31), "%s: a region is 2 * lanes .. 2^31 words, got %ld", what,
+              out_cap_words);
+  IlvEncArgs a{sym, idx, n_streams, n, lanes, *tables, out_words, out_cap_words, lengths, status, counts, n_marks, mark_bytes};
+  const int threads = n_streams * lanes;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_interleaved_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_interleaved_encode_kernel");
+}
+
+int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                       const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, int32_t* sym_out, int32_t* available, int32_t* status,
+                                       void* stream) {
+  const char* what = "vam_rans_interleaved_decode_device";
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && idx && sym_out && available && status && bytes_total >= 0 &&
+              ((uintptr_t)bytes & 3) == 0, "%s: need word-aligned bytes, offsets, lengths, idx, sym_out, available, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
+              what, n_streams, n);
+  if (int rc = check_tables(what, tables)) return rc;
+  IlvDecArgs a{bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, available, status};
+  const int blocks = (n_streams * lanes + kLaneBlock - 1) / kLaneBlock;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_decode_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(rans_interleaved_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rans_interleaved_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_interleaved_decode_kernel");
 }
 
 }  // extern "C"

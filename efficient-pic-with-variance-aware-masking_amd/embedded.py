@@ -19,6 +19,11 @@ alone.  Container of one image::
 z and the base slices are the layered container's, byte for byte.  The marks give, for each listed quality, the element
 count of every slice (the project's own masks: vam_variance_layers on the same sigma) and the exact byte length that
 decodes it (bitstream.prefix_bytes).  :func:`truncate` needs neither the model nor a GPU.
+
+``lanes`` = K > 1 codes every embedded stream on K interleaved lanes (bitstream.encode_interleaved):
+K coder states share one word stream in the decoder's reading order, so a wave decodes K elements per step and a byte
+prefix is still a rank prefix.  Such a container carries ``"format": "embedded-2"`` and ``"lanes": K``; z and the base
+slices stay the K = 1 strings.  ``coder="device"`` keeps symbols and indexes on the device on both sides.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ from . import progressive as P
 from .progressive import Q_LIST
 
 FORMAT = "embedded-1"
+FORMAT_LANES = "embedded-2"          # embedded streams on K > 1 interleaved lanes; carries "lanes": K
 _LAYERED = "the layered container (progressive.encode_batch / ProgressiveDecoder)"
 
 
@@ -67,19 +73,26 @@ def container_bytes(c) -> List[int]:
     return [sum(len(s) for s in c["z"]), sum(len(s[0]) for s in c["base"]), sum(len(s) for s in c["embedded"])]
 
 
-def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None) -> List[dict]:
+def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, coder: Optional[str] = None, lanes: int = 1) -> List[dict]:
     """Embedded containers of a batch x [B,3,H,W] (H, W multiples of 64, as for ``compress``) on the fused plans: the
     ``compress(x, 10)`` plan (symbols round(r - mu), unmasked indexes), vam_variance_rank on its progressive sigma, then
-    vam_rank_gather writes symbols and indexes of every segment in rank order; only these two arrays (and z and the base
-    slices, coded as :func:`progressive.encode_batch` codes them) go to the host.  Each progressive slice becomes ONE
+    vam_rank_gather writes symbols and indexes of every segment in rank order.  Each progressive slice becomes ONE
     stream; ``marks`` (1..32 non-decreasing qualities) are looked up for the receiver's convenience, they do not limit
-    where a stream may be cut."""
+    where a stream may be cut.
+
+    ``coder`` (None: ``model.coder``): "host" brings the ranked symbols and indexes (and z and the base slices, coded as
+    :func:`progressive.encode_batch` codes them) to the host and codes them on its threads; "device" 
+    codes z and the base slices with the device coder's launches and ALL embedded streams with one more, which also gives
+    the marks' bytes, and fetches lengths, status codes, marks and coded bytes only.  The containers are the same byte for
+    byte.  ``lanes`` = K > 1: the embedded streams on K interleaved lanes, format ``"embedded-2"`` with ``"lanes": K``; read
+    from the argument only, never from ``model.coder_lanes``.  K = 1 is format ``"embedded-1"`` with no new key."""
     from . import _lib as L
     from . import bitstream as bs
     from . import ops
     from .models import EMPTY_SCALE_TABLE
     _check_model(model)
     qs = P.check_q_list(marks)
+    coder, K = P._check_coder(model, coder), bs.check_lanes(lanes)
     m = model
     B, _, H, W = x.shape
     d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
@@ -102,25 +115,44 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None) -> L
         ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)               # the masks of the marks, as every plan builds them
         count = torch.empty((len(qs), B, ns), dtype=torch.int32, device=dev)
         ops.rank_counts(layer, perm, ns, len(qs), count)
-        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
-        sym_b, idx_b, zs = nchw(plan.sym.buf[..., :d]), nchw(plan.idx.buf[..., :d]), nchw(plan.z_sym.buf)
-        r_sym, r_idx, count = r_sym.cpu().numpy(), r_idx.cpu().numpy(), count.cpu().numpy().astype(np.int64)
-    tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
-    zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
-    z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te)
-    sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
-    jobs = [(sl(sym_b, b, i), sl(idx_b, b, i)) for i in range(ns) for b in range(B)]
-    jobs += [(r_sym[b, j], r_idx[b, j]) for j in range(ns) for b in range(B)]
-    y_str = bs.encode_streams(jobs, tg)
-    emb = lambda b, j: y_str[(ns + j) * B + b]
-    cuts = _map_threads(lambda bj: bs.prefix_bytes(emb(*bj), r_idx[bj[0], bj[1]], count[:, bj[0], bj[1]].tolist(), tg),
-                        [(b, j) for b in range(B) for j in range(ns)])
+        if coder == "device":
+            tg, te = bs.DeviceCoderTables.of(m.gaussian_conditional, dev), bs.DeviceCoderTables.of(m.entropy_bottleneck, dev)
+            z_str = bs.encode_streams_device(plan.z_sym, None, 1, m.N, te)[0]
+            base = bs.encode_streams_device(plan.sym, plan.idx, ns, C, tg)                      # [slice][image]
+            emb_str, cut = bs.encode_embedded_device(r_sym, r_idx, tg, K, count)                # stream b * ns + j
+            cuts = cut.reshape(len(qs), B, ns)
+            count = count.cpu().numpy().astype(np.int64)
+        else:
+            nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+            sym_b, idx_b, zs = nchw(plan.sym.buf[..., :d]), nchw(plan.idx.buf[..., :d]), nchw(plan.z_sym.buf)
+            r_sym, r_idx, count = r_sym.cpu().numpy(), r_idx.cpu().numpy(), count.cpu().numpy().astype(np.int64)
+    if coder == "host":
+        tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
+        zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
+        z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te)
+        sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
+        jobs = [(sl(sym_b, b, i), sl(idx_b, b, i)) for i in range(ns) for b in range(B)]
+        e_jobs = [(r_sym[b, j], r_idx[b, j]) for b in range(B) for j in range(ns)]
+        if K == 1:                                                                              # one call, as ever
+            y_str = bs.encode_streams(jobs + e_jobs, tg)
+            emb_str = y_str[ns * B:]
+        else:
+            y_str = bs.encode_streams(jobs, tg)
+            emb_str = bs.encode_interleaved_streams(e_jobs, tg, lanes=K)
+        base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
+        got = _map_threads(lambda bj: bs.prefix_bytes(emb_str[bj[0] * ns + bj[1]], r_idx[bj[0], bj[1]],
+                                                      count[:, bj[0], bj[1]].tolist(), tg, lanes=K),
+                           [(b, j) for b in range(B) for j in range(ns)])
+        cuts = np.asarray(got, dtype=np.int64).reshape(B, ns, len(qs)).transpose(2, 0, 1)
     containers = []
     for b in range(B):
-        containers.append({"format": FORMAT, "shape": (H // 64, W // 64), "z": [z_str[b]],
-                           "base": [[y_str[i * B + b]] for i in range(ns)], "embedded": [emb(b, j) for j in range(ns)],
-                           "marks": {"q": list(qs), "count": [[int(count[k, b, j]) for j in range(ns)] for k in range(len(qs))],
-                                     "bytes": [[int(cuts[b * ns + j][k]) for j in range(ns)] for k in range(len(qs))]}})
+        c = {"format": FORMAT if K == 1 else FORMAT_LANES, "shape": (H // 64, W // 64), "z": [z_str[b]],
+             "base": [[base[i][b]] for i in range(ns)], "embedded": [emb_str[b * ns + j] for j in range(ns)],
+             "marks": {"q": list(qs), "count": [[int(count[k, b, j]) for j in range(ns)] for k in range(len(qs))],
+                       "bytes": [[int(cuts[k, b, j]) for j in range(ns)] for k in range(len(qs))]}}
+        if K > 1:
+            c["lanes"] = K
+        containers.append(c)
     if save_path is not None:
         os.makedirs(save_path, exist_ok=True)
         for b, c in enumerate(containers):
@@ -129,10 +161,18 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None) -> L
     return containers
 
 
-def _check_container(c):
-    if not isinstance(c, dict) or c.get("format") != FORMAT:
-        raise ValueError(f"not an embedded container (format {FORMAT!r}): got "
+def _check_container(c) -> int:
+    """The lanes per embedded stream of container ``c``: 1 for ``"embedded-1"``, its ``"lanes"`` for ``"embedded-2"``."""
+    from . import bitstream as bs
+    if not isinstance(c, dict) or c.get("format") not in (FORMAT, FORMAT_LANES):
+        raise ValueError(f"not an embedded container (format {FORMAT!r} or {FORMAT_LANES!r}): got "
                          f"{c.get('format') if isinstance(c, dict) else type(c).__name__!r}")
+    if c["format"] == FORMAT:
+        return 1
+    K = bs.check_lanes(c.get("lanes"))
+    if K == 1:
+        raise ValueError(f"an {FORMAT_LANES!r} container carries lanes > 1; one lane is format {FORMAT!r}")
+    return K
 
 
 def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = None,
@@ -178,15 +218,25 @@ class EmbeddedDecoder:
     """Decodes a batch of embedded containers of one shape, whole or truncated, each image cut at its own place.  The base
     slices and the progressive (mu, sigma) chain run once, the rank order comes from the decoder's own sigma, and the
     embedded streams are prefix-decoded once (bitstream.decode_prefix_streams): :meth:`available` says how many leading
-    elements of every slice are present.  A decoded quality equals ``forward_single_quality(x, q)`` bit for bit."""
+    elements of every slice are present.  A decoded quality equals ``forward_single_quality(x, q)`` bit for bit.
 
-    def __init__(self, model, containers):
+    The lanes per embedded stream are read from the containers (``"embedded-2"``: their ``"lanes"``); a batch that mixes
+    them is refused.  ``coder`` (None: ``model.coder``): "host" prefix-decodes on the host's threads from a host copy of
+    the ranked indexes; "device"  decodes z and the base slices with the device coder, uploads the
+    embedded strings once and prefix-decodes them with ONE launch into the plan's ranked symbols; the counts come back
+    with the status codes in one read, and the ranked indexes stay on the device unless :meth:`bits` asks for them.
+    Either coder reads either coder's containers."""
+
+    def __init__(self, model, containers, coder: Optional[str] = None):
         _check_model(model)
         cs = list(containers)
         if not cs:
             raise ValueError("EmbeddedDecoder: no containers")
-        for c in cs:
-            _check_container(c)
+        lanes = [_check_container(c) for c in cs]
+        if any(k != lanes[0] for k in lanes):
+            raise ValueError(f"EmbeddedDecoder: every container must have the same lanes per embedded stream, got "
+                             f"{sorted(set(lanes))}; decode them separately")
+        self.lanes, self.coder = lanes[0], P._check_coder(model, coder)
         shape = tuple(cs[0]["shape"])
         for c in cs[1:]:
             if tuple(c["shape"]) != shape:
@@ -201,24 +251,60 @@ class EmbeddedDecoder:
         ns = model.ns0
         if any(len(c["embedded"]) != ns or len(c["base"]) != ns for c in cs):
             raise ValueError(f"EmbeddedDecoder: a container of this model has {ns} base and {ns} embedded streams")
-        self.dp = model._emb_dec_plan(self.B, hz, wz)
+        self.dp = model._emb_dec_plan(self.B, hz, wz, self.coder)
         self._avail: Optional[np.ndarray] = None
+        self.idx_r: Optional[np.ndarray] = None             # host copy of the ranked indexes (device coder: only for bits())
         with torch.no_grad():
             self._front()
 
     def _front(self):
         from . import bitstream as bs
         cs, ns, dp = self.containers, self.m.ns0, self.dp
-        dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
+        up = dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
         dp.owner = self
+        if self.coder == "device":
+            return self._front_device(up)
         if self._avail is None:                             # the host's one pass over the embedded streams
             self.idx_r = dp.idx_r.cpu().numpy()             # [B, ns, n]
             self.ranked = np.zeros(self.idx_r.shape, dtype=np.int32)
             jobs = [(c["embedded"][j], self.idx_r[b, j], self.ranked[b, j]) for b, c in enumerate(cs) for j in range(ns)]
-            got = bs.decode_prefix_streams(jobs, bs.Tables.of(self.m.gaussian_conditional))
+            got = bs.decode_prefix_streams(jobs, bs.Tables.of(self.m.gaussian_conditional), lanes=self.lanes)
             self._avail = np.asarray(got, dtype=np.int64).reshape(self.B, ns)
         with dp.runner.on_stream():
             dp.ranked.copy_(torch.from_numpy(self.ranked))
+
+    def _front_device(self, up):
+        """The embedded strings go up once and ONE launch prefix-decodes them from the plan's ranked indexes into its ranked
+        symbols; this decoder keeps its own copy of them for when another decoder has used the plans since."""
+        from . import _lib as L
+        from . import bitstream as bs
+        cs, ns, dp, B = self.containers, self.m.ns0, self.dp, self.B
+        with dp.runner.on_stream():
+            if self._avail is None:
+                emb = bs.upload_streams([c["embedded"][j] for c in cs for j in range(ns)], dp.device)
+                meta = torch.empty((2, B * ns), dtype=torch.int32, device=dp.device)
+                bs.decode_embedded_uploaded(emb, 0, dp.idx_r, dp.ranked, bs.DeviceCoderTables.of(self.m.gaussian_conditional, dp.device),
+                                            self.lanes, meta)
+                self.ranked = dp.ranked.clone()
+                got = meta.cpu().numpy()                    # the one read: available counts and status codes
+            else:
+                dp.ranked.copy_(self.ranked)
+                got = None
+            bs.check_status(up, B, "EmbeddedDecoder", lambda k: f"z stream (image {k})" if k < B else
+                            f"base stream (image {k % B}, slice {k // B - 1})")
+        if got is not None:
+            bad = np.flatnonzero(got[1])
+            if bad.size:
+                k = int(bad[0])
+                raise L.VamError(f"EmbeddedDecoder: embedded stream (image {k // ns}, slice {k % ns}): "
+                                 f"{bs.status_text(int(got[1][k]))}")
+            self._avail = got[0].astype(np.int64).reshape(B, ns)
+
+    def _idx_r(self) -> np.ndarray:
+        if self.idx_r is None:
+            self._own()
+            self.idx_r = self.dp.idx_r.cpu().numpy()
+        return self.idx_r
 
     def _own(self):
         if self.dp.owner is not self:                       # another decoder ran on the same plans since
@@ -299,7 +385,8 @@ class EmbeddedDecoder:
             count = self._counts([q]).cpu().numpy()
         self._check_present([q], count)
         tg = bs.Tables.of(self.m.gaussian_conditional)
-        cut = _map_threads(lambda bj: bs.prefix_bytes(self.containers[bj[0]]["embedded"][bj[1]], self.idx_r[bj[0], bj[1]],
-                                                      [int(count[0, bj[0], bj[1]])], tg)[0],
+        idx_r = self._idx_r()
+        cut = _map_threads(lambda bj: bs.prefix_bytes(self.containers[bj[0]]["embedded"][bj[1]], idx_r[bj[0], bj[1]],
+                                                      [int(count[0, bj[0], bj[1]])], tg, lanes=self.lanes)[0],
                            [(b, j) for b in range(self.B) for j in range(ns)])
         return [fixed[b] + 8.0 * sum(cut[b * ns:(b + 1) * ns]) for b in range(self.B)]

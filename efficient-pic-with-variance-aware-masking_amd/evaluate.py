@@ -364,13 +364,14 @@ def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float
     return rows
 
 
-def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float]):
+def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float], coder=None, lanes: int = 1):
     """:func:`progressive_rd`'s printout for the embedded format (embedded.encode_batch / EmbeddedDecoder, DESIGN section
     9m): images of one shape are padded and coded as one batch, ONCE and without a quality list of their own; the base and
     then every quality of ``qualities`` (any values >= 0, marked or not) is decoded from the same streams.  Returns one
     dict per level, the base first: q, bpp (8 * the bytes a receiver needs for that quality — z, the base and the shortest
     prefix of every slice — / pixels of the ORIGINAL image), psnr (of the cropped decode), enc_s and dec_s (seconds per
-    image: the encode once, the decode of that level), each the mean over the images, plus "bpp_all" / "psnr_all"."""
+    image: the encode once, the decode of that level), each the mean over the images, plus "bpp_all" / "psnr_all".
+    ``coder`` and ``lanes`` are passed on to embedded.encode_batch, ``coder`` to the decoder too."""
     from . import embedded as EB
     images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
     levels = [0.0] + [float(q) for q in qualities]
@@ -385,9 +386,9 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
             xp, unpad = pad_image(xs)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            containers = EB.encode_batch(model, xp)
+            containers = EB.encode_batch(model, xp, coder=coder, lanes=lanes)
             t1 = time.perf_counter()
-            dec = EB.EmbeddedDecoder(model, containers)
+            dec = EB.EmbeddedDecoder(model, containers, coder=coder)
             for k, q in enumerate(levels):
                 torch.cuda.synchronize()
                 t2 = time.perf_counter()

@@ -746,12 +746,12 @@ class VarianceMaskingPIC(CompressionModel):
                                  + ((coder,) if coder != "host" else ()),
                                  lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev, coder=coder), self._weights_sig())
 
-    def _emb_dec_plan(self, B, hz, wz) -> "_EmbDecPlan":
-        """The plans of embedded.EmbeddedDecoder for one (B, z-shape), cached beside decompress's: the cuts are graph
+    def _emb_dec_plan(self, B, hz, wz, coder: str = "host") -> "_EmbDecPlan":
+        """The plans of embedded.EmbeddedDecoder for one (B, z-shape, coder), cached beside decompress's: the cuts are graph
         inputs, so no quality list is part of the key."""
         dev = self.entropy_bottleneck.quantiles.device
-        return self._cached_plan(self._dec_plans, ("emb", B, hz, wz, str(dev)),
-                                 lambda: _EmbDecPlan(self, B, hz, wz, dev), self._weights_sig())
+        return self._cached_plan(self._dec_plans, ("emb", B, hz, wz, str(dev)) + ((coder,) if coder != "host" else ()),
+                                 lambda: _EmbDecPlan(self, B, hz, wz, dev, coder=coder), self._weights_sig())
 
 
 class VarianceMaskingPICREM(VarianceMaskingPIC):

@@ -1188,8 +1188,10 @@ class _EmbDecPlan(_ProgDecPlan):
     with the fixed cut-offs 0 .. G-1.  The count table is a graph input, copied before the replay on the runner's stream
     and outside any capture, so the plan keeps ONE hipGraph per group size whatever the cuts."""
 
-    def __init__(self, m, B, hz, wz, device):
-        super().__init__(m, B, hz, wz, (), device)
+    def __init__(self, m, B, hz, wz, device, coder: str = "host"):
+        """``coder`` "device" (DESIGN section 9q): z and the base slices are decoded by the device coder as in _ProgDecPlan,
+        and the decoder prefix-decodes the embedded strings from ``idx_r`` into ``ranked`` with one launch."""
+        super().__init__(m, B, hz, wz, (), device, coder=coder)
         self.counts: Dict[int, torch.Tensor] = {}          # group size -> int32 [G, B, ns], the tails' graph input
 
     def _lower_progressive(self):

@@ -857,6 +857,59 @@ int vam_rans_layers_decode_device(const uint8_t* bytes, const int64_t* byte_offs
                                   int n_slices, int lanes, const vam_rans_tables* tables, int32_t* sym_out, int32_t* status,
                                   void* stream);
 
+/* ------------------------------------------------------------------ interleaved lanes */
+/* A stream of n elements on `lanes` = K interleaved lanes, K as above: element i belongs to lane i % K and group i / K, and
+ * the K coder states share ONE word stream.  The string is the K final states in lane order (two little-endian words each,
+ * low then high; a lane without elements holds 2^31), then the renormalisation words in the order the decoder reads them:
+ * groups ascending, inside a group rounds t = 0, 1, ..: every lane that still has a get t (0 the table symbol, then the
+ * count and raw nibbles of an escape) updates its state, then the lanes whose state fell below 2^31 take one word each in
+ * ascending lane order.  A byte prefix therefore decodes a rank prefix, and K = 1 is the existing wire format byte for
+ * byte.  A buffer of 8 n + 8 K + 64 bytes holds any string.  K is not stored in the string.
+ * HOST pointers.  vam_rans_interleaved_encode[_streams]: vam_rans_encode[_streams] for this format (layer must be NULL).
+ * vam_rans_interleaved_decode_prefix[_streams]: the tolerant decode of the first n_bytes >= 0 bytes (floor(n_bytes / 4)
+ * words; fewer than 2 K decode nothing).  A lane that needs a word the prefix does not hold fails, as does every later
+ * request; the other lanes of that group finish the gets that need no word and decoding ends with that group: the count
+ * is g K + the lowest failed lane.  symbols_out[0 .. count) is written, the rest left untouched.  The single-stream call
+ * returns the count and, in status_out, 0 or the status (2 index out of range, 3 cdf size invalid) that ended the stream;
+ * with status_out NULL, and in the _streams call, such a status is VAM_EINVAL.
+ * vam_rans_interleaved_prefix_bytes: bytes_out[q] = 4 * the read position after the last word that any of the elements
+ * 0 .. counts[q] - 1 reads (8 K when they read none, 0 for a count of 0): the smallest prefix that decodes counts[q]. */
+long vam_rans_interleaved_encode(const int32_t* symbols_host, const int32_t* indexes_host, long n, const int32_t* cdfs_host,
+                                 int cdf_stride, const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs,
+                                 uint8_t* out_host, long out_capacity, int lanes);
+int vam_rans_interleaved_encode_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
+                                        const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int lanes,
+                                        int n_threads);
+long vam_rans_interleaved_decode_prefix(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n,
+                                        const int32_t* cdfs_host, int cdf_stride, const int32_t* cdf_sizes_host,
+                                        const int32_t* offsets_host, int n_cdfs, int lanes, int32_t* symbols_out_host,
+                                        int32_t* status_out);
+int vam_rans_interleaved_decode_prefix_streams(vam_rans_stream* streams, int n_streams, const int32_t* cdfs_host, int cdf_stride,
+                                               const int32_t* cdf_sizes_host, const int32_t* offsets_host, int n_cdfs, int lanes,
+                                               int n_threads, long* counts_out);
+int vam_rans_interleaved_prefix_bytes(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n,
+                                      const int32_t* cdfs_host, int cdf_stride, const int32_t* cdf_sizes_host,
+                                      const int32_t* offsets_host, int n_cdfs, int lanes, const long* counts, int n_counts,
+                                      long* bytes_out);
+/* DEVICE pointers.  n_streams streams of n elements each, flat: stream s reads sym / idx [s * n, (s + 1) * n) (the ranked
+ * buffers of vam_rank_gather).  One thread per (stream, lane); 64 / K streams share a wave, a lane finds its word by a
+ * prefix popcount of the wave's ballot.
+ * vam_rans_interleaved_encode_device: regions, lengths and status as in vam_rans_encode_device (2 n + 2 K + 16 words hold
+ * any string); vam_rans_pack_device packs them.  counts (may be NULL with n_marks = 0): int32 [n_marks][n_streams], for
+ * every stream non-decreasing in the mark; mark_bytes [n_marks][n_streams] receives vam_rans_interleaved_prefix_bytes of
+ * each count, taken from the encoder's own word positions (0 for a stream that failed).
+ * vam_rans_interleaved_decode_device: stream s is the first byte_lengths[s] >= 0 bytes of a string at bytes +
+ * byte_offsets[s] (a multiple of 4, inside [0, bytes_total)), decoded tolerantly: sym_out[s * n + i] for i < available[s],
+ * 0 for every other element; status[s] = 0, 2, 3 or 6 (a refused offset or length: nothing is read).  No read leaves a
+ * stream's bytes, no write the n_streams * n elements. */
+int vam_rans_interleaved_encode_device(const int32_t* sym, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, uint32_t* out_words, long out_cap_words, int32_t* lengths,
+                                       int32_t* status, const int32_t* counts, int n_marks, int32_t* mark_bytes, void* stream);
+int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                       const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, int32_t* sym_out, int32_t* available, int32_t* status,
+                                       void* stream);
+
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
 int vam_graph_end(void* stream, void** graph_exec_out);

@@ -3,12 +3,17 @@
 (progressive.encode_batch / ProgressiveDecoder, section 9g) on one GPU, same model, same inputs, hipGraph on, at section
 9g's two inputs.  Each case is warmed, then the two formats alternate (layered, embedded, layered, ...), each phase timed
 from a device synchronisation to the next; medians are reported.  "encode" is the container of every image, "decode" the
-base and every quality of the list for every image.  The host coder's share of each phase (the bitstream calls, wall time
-on the calling thread) is reported beside it, and the bytes per image: the embedded streams at full length against the
+base and every quality of the list for every image.  The coder's share of each phase (host: the bitstream calls, wall time
+on the calling thread; device: HIP events around the device coder's calls, the embedded launches also on their own) is
+reported beside it, and the bytes per image: the embedded streams at full length against the
 layered container's progressive streams.  x_hat of every level must be identical between the two formats (asserted); no
 time is asserted.  Prints one JSON line.
 
-    python scripts/bench_embedded.py [--warmup 1] [--reps 3]
+``--coder`` and ``--lanes`` add one embedded cell per (coder, lanes per embedded stream) to the same
+alternation: encode ms, decode ms and bytes per image under "cells", next to the host K = 1 cell of the same run, which is
+the "embedded" path above.  x_hat of every level is asserted identical for every cell.
+
+    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64]
 """
 import argparse
 import json
@@ -29,6 +34,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--coder", nargs="+", default=["host"], choices=["host", "device"])
+    ap.add_argument("--lanes", nargs="+", type=int, default=[1])
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -49,6 +56,28 @@ def main():
     for name in ("encode", "decode", "encode_streams", "decode_streams", "decode_prefix_streams"):
         setattr(bs, name, timed(getattr(bs, name)))
     EB._map_threads = timed(EB._map_threads)     # prefix_bytes runs on worker threads: timed around the map
+    events = {"coder": [], "emb": []}            # device coder: HIP events around its calls, read after the phase's synchronise
+
+    def evented(fn, *keys):
+        def run(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            try:
+                return fn(*args, **kw)
+            finally:
+                e1.record()
+                for k in keys:
+                    events[k].append((e0, e1))
+        return run
+    for name in ("encode_streams_device", "decode_uploaded"):
+        setattr(bs, name, evented(getattr(bs, name), "coder"))
+    for name in ("encode_embedded_device", "decode_embedded_uploaded"):
+        setattr(bs, name, evented(getattr(bs, name), "coder", "emb"))
+
+    def drain(key):
+        ms = sum(e0.elapsed_time(e1) for e0, e1 in events[key])
+        events[key].clear()
+        return ms
 
     def layered_enc(x, qs):
         return P.encode_batch(net, x, qs)[0]
@@ -62,12 +91,18 @@ def main():
     def embedded_dec(cs, qs):
         return [o["x_hat"] for o in EB.EmbeddedDecoder(net, cs).decode_qualities([0.0] + list(qs))]
 
+    def cell(coder_, K):
+        return (lambda x, qs: EB.encode_batch(net, x, qs, coder=coder_, lanes=K),
+                lambda cs, qs: [o["x_hat"] for o in EB.EmbeddedDecoder(net, cs, coder=coder_).decode_qualities([0.0] + list(qs))])
+
+    cells = [(c, K) for c in a.coder for K in a.lanes if (c, K) != ("host", 1)]
     res = {"metric": "embedded streams vs layered container (ms, median)", "device": torch.cuda.get_device_name(0),
            "coder_threads": bs.coder_threads(), "warmup": a.warmup, "reps": a.reps, "cases": {}}
     for case, B, H, W, qs in (("1x512x768/15", 1, 512, 768, DEMO_Q), ("8x256x256/14", 8, 256, 256, P.Q_LIST)):
         x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
         paths = {"layered": (layered_enc, layered_dec), "embedded": (embedded_enc, embedded_dec)}
-        t = {f"{p}_{ph}": [] for p in paths for ph in ("enc", "enc_coder", "dec", "dec_coder")}
+        paths.update({f"embedded_{c}_k{K}": cell(c, K) for c, K in cells})
+        t = {f"{p}_{ph}": [] for p in paths for ph in ("enc", "enc_coder", "dec", "dec_coder", "enc_emb_dev", "dec_emb_dev")}
         size = {}
         with torch.no_grad():
             for rep in range(a.warmup + a.reps):
@@ -78,26 +113,35 @@ def main():
                     t0 = time.perf_counter()
                     cs = enc(x, qs)
                     torch.cuda.synchronize()
-                    t1, c1 = time.perf_counter(), coder[0]
+                    m1 = drain("emb")
+                    t1, c1 = time.perf_counter(), coder[0] + 1e-3 * drain("coder")
                     coder[0] = 0.0
                     last[p] = dec(cs, qs)
                     torch.cuda.synchronize()
-                    t2, c2 = time.perf_counter(), coder[0]
+                    m2 = drain("emb")
+                    t2, c2 = time.perf_counter(), coder[0] + 1e-3 * drain("coder")
                     if rep >= a.warmup:
-                        for k, v in (("enc", t1 - t0), ("enc_coder", c1), ("dec", t2 - t1), ("dec_coder", c2)):
+                        for k, v in (("enc", t1 - t0), ("enc_coder", c1), ("dec", t2 - t1), ("dec_coder", c2),
+                                     ("enc_emb_dev", 1e-3 * m1), ("dec_emb_dev", 1e-3 * m2)):
                             t[f"{p}_{k}"].append(1e3 * v)
                     if p == "layered":
                         size[p] = sum(len(s) for c in cs for layer in c["progressive"] for s in layer) / B
                     else:
                         size[p] = sum(len(s) for c in cs for s in c["embedded"]) / B
-                for k, (u, v) in enumerate(zip(last["layered"], last["embedded"])):
-                    assert torch.equal(u, v), f"{case}: x_hat of level {k} differs between the formats"
+                for p in paths:
+                    for k, (u, v) in enumerate(zip(last["layered"], last[p])):
+                        assert torch.equal(u, v), f"{case}: x_hat of level {k} differs between layered and {p}"
         med = {k: round(statistics.median(v), 1) for k, v in t.items()}
         med.update(levels=len(qs), encode_ratio=round(med["embedded_enc"] / med["layered_enc"], 3),
                    decode_ratio=round(med["embedded_dec"] / med["layered_dec"], 3), x_hat_identical=True,
                    layered_progressive_bytes_per_image=round(size["layered"], 1),
                    embedded_bytes_per_image=round(size["embedded"], 1),
                    bytes_ratio=round(size["embedded"] / size["layered"], 4))
+        if cells:
+            row = lambda p: {"enc_ms": med[f"{p}_enc"], "enc_coder_ms": med[f"{p}_enc_coder"], "enc_embedded_launch_ms": med[f"{p}_enc_emb_dev"],
+                             "dec_ms": med[f"{p}_dec"], "dec_coder_ms": med[f"{p}_dec_coder"],
+                             "dec_embedded_launch_ms": med[f"{p}_dec_emb_dev"], "bytes_per_image": round(size[p], 1)}
+            med["cells"] = {"host_k1": row("embedded"), **{f"{c}_k{K}": row(f"embedded_{c}_k{K}") for c, K in cells}}
         res["cases"][case] = med
         net._drop_plans()
         torch.cuda.empty_cache()
