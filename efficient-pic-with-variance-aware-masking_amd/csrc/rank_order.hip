@@ -14,6 +14,12 @@
 //               steps j >= 8192 as one global compare-exchange launch each (rank_global_step_kernel) and its steps
 //               j <= 4096 in LDS again (rank_chunk_kernel<false>); the last stage writes the permutation.
 // No allocation and no atomics; every launch is capturable.
+//
+// Scheduled streams: vam_stage_ids turns the layer ids of vam_variance_layers_per_image and a
+// schedule's per-image stage maps into a stage id per element, and vam_variance_rank_staged sorts with that id as the
+// major key,
+//     key = (stage << 56) | (~ordered_bits(sigma) << 24) | e,      e < 2^18 in the low 24 bits,
+// through the same network, chunks, workspace and passes (the STAGED template flag of the key build and the final write).
 #include "common.h"
 #include <cstdint>
 
@@ -28,15 +34,16 @@ constexpr u64 kRankSentinel = ~0ull;
 
 struct RankArgs {
   const float* sigma;
+  const uint8_t* stage;   // STAGED: the ids of vam_stage_ids, pixel stride ld_stage, slice j at channel j * C
   u64* ws;
   int32_t* perm;
   long batch_stride, slice_stride;
-  int ld, n_slice, n_pix, C, n, np, ch;
+  int ld, ld_stage, n_slice, n_pix, C, n, np, ch;
   int k;       // rank_chunk_kernel<false> / rank_global_step_kernel: the stage
   int j;       // rank_global_step_kernel: the step
 };
 
-__device__ __forceinline__ u64 rank_key(float s, unsigned e) {
+__device__ __forceinline__ unsigned rank_sigma_bits(float s) {
   unsigned u = __float_as_uint(s);
   unsigned d;
   if (s != s) {
@@ -45,7 +52,15 @@ __device__ __forceinline__ u64 rank_key(float s, unsigned e) {
     if (u == 0x80000000u) u = 0u;                         // -0.0 == +0.0
     d = ~(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u));   // descending in sigma
   }
-  return ((u64)d << 32) | e;
+  return d;
+}
+
+__device__ __forceinline__ u64 rank_key(float s, unsigned e) { return ((u64)rank_sigma_bits(s) << 32) | e; }
+
+// The scheduled key: e < 2^18 (kRankMaxN) leaves the low 24 bits to it; stage 0xFF with a NaN still lies below the
+// all-ones sentinel because e never reaches 0xFFFFFF.
+__device__ __forceinline__ u64 rank_key_staged(unsigned stage, float s, unsigned e) {
+  return ((u64)stage << 56) | ((u64)rank_sigma_bits(s) << 24) | e;
 }
 
 // One compare-exchange step of the network on an LDS chunk whose first key has global index `base`.
@@ -66,7 +81,8 @@ __device__ __forceinline__ void lds_step(u64* keys, int ch, int base, int k, int
 // FIRST: build the keys of chunk blockIdx.x of segment blockIdx.y from sigma and run the stages k = 2 .. ch.
 // else:  load the chunk from the workspace and run the steps j = ch/2 .. 1 of stage a.k.
 // The chunk goes to the permutation when the network is complete (stage np done), else back to the workspace.
-template <bool FIRST>
+// STAGED: the stage id is the major key and e sits in the low 24 bits (vam_variance_rank_staged).
+template <bool FIRST, bool STAGED>
 __global__ __launch_bounds__(kRankThreads) void rank_chunk_kernel(const RankArgs a) {
   extern __shared__ u64 keys[];
   const int seg = blockIdx.y;
@@ -75,12 +91,15 @@ __global__ __launch_bounds__(kRankThreads) void rank_chunk_kernel(const RankArgs
   if (FIRST) {
     const int b = seg / a.n_slice, jj = seg - b * a.n_slice;
     const float* src = a.sigma + b * a.batch_stride + jj * a.slice_stride;
+    const uint8_t* sid = STAGED ? a.stage + (long)b * a.n_pix * a.ld_stage + jj * a.C : nullptr;
     for (int t = threadIdx.x; t < a.ch; t += kRankThreads) {
       const int g = base + t;                              // memory order (pixel, channel): coalesced over the window
       u64 key = kRankSentinel;
       if (g < a.n) {
         const int p = g / a.C, c = g - p * a.C;
-        key = rank_key(src[(long)p * a.ld + c], (unsigned)(c * a.n_pix + p));
+        const unsigned e = (unsigned)(c * a.n_pix + p);
+        const float s = src[(long)p * a.ld + c];
+        key = STAGED ? rank_key_staged(sid[(long)p * a.ld_stage + c], s, e) : rank_key(s, e);
       }
       keys[t] = key;
     }
@@ -96,7 +115,8 @@ __global__ __launch_bounds__(kRankThreads) void rank_chunk_kernel(const RankArgs
   if (done) {
     int32_t* out = a.perm + (long)seg * a.n;
     for (int t = threadIdx.x; t < a.ch; t += kRankThreads)
-      if (base + t < a.n) out[base + t] = (int32_t)(unsigned)keys[t];     // the sentinels sit behind every real key
+      if (base + t < a.n)                                                 // the sentinels sit behind every real key
+        out[base + t] = STAGED ? (int32_t)((unsigned)keys[t] & 0xFFFFFFu) : (int32_t)(unsigned)keys[t];
   } else {
     for (int t = threadIdx.x; t < a.ch; t += kRankThreads) ws[t] = keys[t];
   }
@@ -194,6 +214,36 @@ __global__ __launch_bounds__(256) void rank_counts_kernel(const CountArgs a) {
   a.count[g * a.n_seg + seg] = lo;
 }
 
+struct StageArgs {
+  const uint8_t* layer;
+  const uint8_t* stage_map;  // [n_batch][VAM_MAX_LAYER_LEVELS][n_pix]
+  const int32_t* n_stages;   // [n_batch]
+  uint8_t* out;
+  long total;                // n_batch * n_pix * Ct
+  int ld_layer, ld_out, n_pix, Ct;
+};
+
+// stage(e) = the first stage whose map index at e's pixel reaches e's layer id (layer[e] <= k  <=>  mask_k[e] == 1), 0xFF
+// when none does.  Stage count and maps come from device memory, so one captured launch serves every schedule.
+__global__ __launch_bounds__(256) void stage_ids_kernel(const StageArgs a) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.total) return;
+  const long pix = t / a.Ct;                                 // b * n_pix + p
+  const int ch = (int)(t - pix * a.Ct);
+  const int b = (int)(pix / a.n_pix), p = (int)(pix - (long)b * a.n_pix);
+  const int l = a.layer[pix * a.ld_layer + ch];
+  int ns = a.n_stages[b];
+  if (ns < 1 || ns > VAM_MAX_LAYER_LEVELS) ns = 0;
+  const uint8_t* map = a.stage_map + (long)b * VAM_MAX_LAYER_LEVELS * a.n_pix + p;
+  int id = 0xFF;
+  for (int k = 0; k < ns; ++k)
+    if (map[(long)k * a.n_pix] >= l) {
+      id = k;
+      break;
+    }
+  a.out[pix * a.ld_out + ch] = (uint8_t)id;
+}
+
 int rank_shape(const char* what, int n_batch, int n_slice, int n_pix, int C, long* n_out) {
   VAM_REQUIRE(n_batch > 0 && n_slice > 0 && n_pix > 0 && C > 0, "%s: need n_batch, n_slice, n_pix, C > 0", what);
   VAM_REQUIRE((long)n_batch * n_slice <= 65535, "%s: %ld segments exceed one launch (65535)", what, (long)n_batch * n_slice);
@@ -208,6 +258,44 @@ int rank_np(long n) {
   int np = 2;
   while (np < n) np <<= 1;
   return np;
+}
+
+// vam_variance_rank (STAGED = false) and vam_variance_rank_staged: one network, one launch sequence.
+template <bool STAGED>
+int rank_launch(const char* what, const float* sigma, int ld, long batch_stride, long slice_stride, const uint8_t* stage,
+                int ld_stage, int n_batch, int n_slice, int n_pix, int C, int32_t* perm_out, void* workspace,
+                size_t workspace_bytes, void* stream) {
+  long n;
+  if (int rc = rank_shape(what, n_batch, n_slice, n_pix, C, &n)) return rc;
+  VAM_REQUIRE(sigma && perm_out && ld >= C, "%s: need sigma, perm_out and ld >= C", what);
+  const int np_ = rank_np(n);
+  const size_t need = np_ > kRankChunk ? (size_t)n_batch * n_slice * np_ * sizeof(u64) : 0;
+  VAM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0),
+              "%s: segments of %ld elements need an 8-byte aligned workspace of %zu bytes "
+              "(vam_variance_rank_workspace), got %zu", what, n, need, workspace_bytes);
+  RankArgs a;
+  a.sigma = sigma; a.stage = stage; a.ws = need ? (u64*)workspace : nullptr; a.perm = perm_out;
+  a.batch_stride = batch_stride; a.slice_stride = slice_stride;
+  a.ld = ld; a.ld_stage = ld_stage; a.n_slice = n_slice; a.n_pix = n_pix; a.C = C; a.n = (int)n;
+  a.np = rank_np(n); a.ch = a.np < kRankChunk ? a.np : kRankChunk;
+  a.k = 0; a.j = 0;
+  const int n_seg = n_batch * n_slice, chunks = a.np / a.ch;
+  const size_t lds = (size_t)a.ch * sizeof(u64);
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(VAM_FAM_MASK, s, 0, (double)n_seg * n * 8.0);
+  hipLaunchKernelGGL((rank_chunk_kernel<true, STAGED>), dim3(chunks, n_seg), dim3(kRankThreads), lds, s, a);
+  if (int rc = check_launch("rank_chunk_kernel<true>")) return rc;
+  for (int k = 2 * kRankChunk; k <= a.np && chunks > 1; k <<= 1) {
+    a.k = k;
+    for (int j = k >> 1; j >= kRankChunk; j >>= 1) {
+      a.j = j;
+      hipLaunchKernelGGL(rank_global_step_kernel, dim3(cdiv(a.np >> 1, 256), n_seg), dim3(256), 0, s, a);
+      if (int rc = check_launch("rank_global_step_kernel")) return rc;
+    }
+    hipLaunchKernelGGL((rank_chunk_kernel<false, STAGED>), dim3(chunks, n_seg), dim3(kRankThreads), lds, s, a);
+    if (int rc = check_launch("rank_chunk_kernel<false>")) return rc;
+  }
+  return VAM_OK;
 }
 
 }  // namespace
@@ -226,36 +314,31 @@ size_t vam_variance_rank_workspace(int n_batch, int n_slice, int n_pix, int C) {
 
 int vam_variance_rank(const float* sigma, int ld, long batch_stride, long slice_stride, int n_batch, int n_slice, int n_pix,
                       int C, int32_t* perm_out, void* workspace, size_t workspace_bytes, void* stream) {
-  long n;
-  if (int rc = rank_shape("vam_variance_rank", n_batch, n_slice, n_pix, C, &n)) return rc;
-  VAM_REQUIRE(sigma && perm_out && ld >= C, "vam_variance_rank: need sigma, perm_out and ld >= C");
-  const size_t need = vam_variance_rank_workspace(n_batch, n_slice, n_pix, C);
-  VAM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0),
-              "vam_variance_rank: segments of %ld elements need an 8-byte aligned workspace of %zu bytes "
-              "(vam_variance_rank_workspace), got %zu", n, need, workspace_bytes);
-  RankArgs a;
-  a.sigma = sigma; a.ws = need ? (u64*)workspace : nullptr; a.perm = perm_out;
-  a.batch_stride = batch_stride; a.slice_stride = slice_stride;
-  a.ld = ld; a.n_slice = n_slice; a.n_pix = n_pix; a.C = C; a.n = (int)n;
-  a.np = rank_np(n); a.ch = a.np < kRankChunk ? a.np : kRankChunk;
-  a.k = 0; a.j = 0;
-  const int n_seg = n_batch * n_slice, chunks = a.np / a.ch;
-  const size_t lds = (size_t)a.ch * sizeof(u64);
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(VAM_FAM_MASK, s, 0, (double)n_seg * n * 8.0);
-  hipLaunchKernelGGL(rank_chunk_kernel<true>, dim3(chunks, n_seg), dim3(kRankThreads), lds, s, a);
-  if (int rc = check_launch("rank_chunk_kernel<true>")) return rc;
-  for (int k = 2 * kRankChunk; k <= a.np && chunks > 1; k <<= 1) {
-    a.k = k;
-    for (int j = k >> 1; j >= kRankChunk; j >>= 1) {
-      a.j = j;
-      hipLaunchKernelGGL(rank_global_step_kernel, dim3(cdiv(a.np >> 1, 256), n_seg), dim3(256), 0, s, a);
-      if (int rc = check_launch("rank_global_step_kernel")) return rc;
-    }
-    hipLaunchKernelGGL(rank_chunk_kernel<false>, dim3(chunks, n_seg), dim3(kRankThreads), lds, s, a);
-    if (int rc = check_launch("rank_chunk_kernel<false>")) return rc;
-  }
-  return VAM_OK;
+  return rank_launch<false>("vam_variance_rank", sigma, ld, batch_stride, slice_stride, nullptr, 0, n_batch, n_slice, n_pix, C,
+                            perm_out, workspace, workspace_bytes, stream);
+}
+
+int vam_variance_rank_staged(const float* sigma, int ld, long batch_stride, long slice_stride, const uint8_t* stage,
+                             int ld_stage, int n_batch, int n_slice, int n_pix, int C, int32_t* perm_out, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  VAM_REQUIRE(stage && ld_stage >= n_slice * C, "vam_variance_rank_staged: need stage and ld_stage >= n_slice * C");
+  return rank_launch<true>("vam_variance_rank_staged", sigma, ld, batch_stride, slice_stride, stage, ld_stage, n_batch, n_slice,
+                           n_pix, C, perm_out, workspace, workspace_bytes, stream);
+}
+
+int vam_stage_ids(const uint8_t* layer, int ld_layer, const uint8_t* stage_map, const int32_t* n_stages, int n_batch, int n_pix,
+                  int C_total, uint8_t* stage_out, int ld_out, void* stream) {
+  VAM_REQUIRE(layer && stage_map && n_stages && stage_out, "vam_stage_ids: need layer, stage_map, n_stages and stage_out");
+  VAM_REQUIRE(n_batch > 0 && n_pix > 0 && C_total > 0 && ld_layer >= C_total && ld_out >= C_total,
+              "vam_stage_ids: need n_batch, n_pix, C_total > 0 and pixel strides >= C_total");
+  StageArgs a;
+  a.layer = layer; a.stage_map = stage_map; a.n_stages = n_stages; a.out = stage_out;
+  a.total = (long)n_batch * n_pix * C_total;
+  a.ld_layer = ld_layer; a.ld_out = ld_out; a.n_pix = n_pix; a.Ct = C_total;
+  VAM_REQUIRE(a.total <= (long)INT32_MAX * 256, "vam_stage_ids: %ld elements exceed one launch", a.total);
+  ProfScope ps(VAM_FAM_MASK, (hipStream_t)stream, 0, (double)a.total * 2.0);
+  hipLaunchKernelGGL(stage_ids_kernel, dim3((unsigned)cdiv(a.total, 256L)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("stage_ids_kernel");
 }
 
 int vam_rank_gather(const int32_t* in0, int ld0, const int32_t* in1, int ld1, const int32_t* perm, int n_batch, int n_slice,

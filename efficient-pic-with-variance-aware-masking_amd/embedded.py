@@ -24,6 +24,15 @@ decodes it (bitstream.prefix_bytes).  :func:`truncate` needs neither the model n
 K coder states share one word stream in the decoder's reading order, so a wave decodes K elements per step and a byte
 prefix is still a rank prefix.  Such a container carries ``"format": "embedded-2"`` and ``"lanes": K``; z and the base
 slices stay the K = 1 strings.  ``coder="device"`` keeps symbols and indexes on the device on both sides.
+
+A **schedule**  gives a region of interest the front of every stream: L quality maps
+S[0] <= ... <= S[L-1] on the latent grid.  The masks of a pointwise non-decreasing sequence of maps are nested, so they are
+prefixes of ONE ordering: ascending stage (the first map whose mask holds the element), within a stage descending sigma.
+Both sides build it on the device from their own sigma and the schedule the container carries (vam_stage_ids,
+vam_variance_rank_staged); a stream cut at stage k's mark reproduces ``forward_quality_map(x, S[k])``, any other cut is a
+rank prefix, and the whole stream is still ``forward_single_quality(x, 10)``.  Such a container carries
+``"format": "embedded-3"``, always ``"lanes"``, ``"schedule": {"levels", "index"}`` with its raw ``"side_bytes"``, and marks
+by ``"stage"`` instead of ``"q"``.
 """
 from __future__ import annotations
 
@@ -41,6 +50,7 @@ from .progressive import Q_LIST
 
 FORMAT = "embedded-1"
 FORMAT_LANES = "embedded-2"          # embedded streams on K > 1 interleaved lanes; carries "lanes": K
+FORMAT_SCHEDULED = "embedded-3"      # scheduled rank order; carries "lanes": K >= 1, "schedule" and "side_bytes"
 _LAYERED = "the layered container (progressive.encode_batch / ProgressiveDecoder)"
 
 
@@ -73,7 +83,99 @@ def container_bytes(c) -> List[int]:
     return [sum(len(s) for s in c["z"]), sum(len(s[0]) for s in c["base"]), sum(len(s) for s in c["embedded"])]
 
 
-def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, coder: Optional[str] = None, lanes: int = 1) -> List[dict]:
+def schedule_buffers(B: int, n_pix: int, device):
+    """The three device inputs of a scheduled rank order for B images of n_pix latent positions: the layer-parameter table
+    (ops.layer_table), the stage index maps uint8 [B, VAM_MAX_LAYER_LEVELS, n_pix] and the stage counts int32 [B]."""
+    import ctypes
+    from . import _lib as L
+    return (torch.zeros((B * ctypes.sizeof(L.VamLayerParams),), dtype=torch.uint8, device=device),
+            torch.zeros((B, L.VAM_MAX_LAYER_LEVELS, n_pix), dtype=torch.uint8, device=device),
+            torch.zeros((B,), dtype=torch.int32, device=device))
+
+
+def fill_schedule(table, stage_map, n_stages, levels, index, n_pix: int, C: int):
+    """Refill :func:`schedule_buffers` from :func:`check_schedule`'s (levels, index [B, L, h, w]) on the current stream: host
+    arithmetic and three copies, outside any capture."""
+    from . import ops
+    B, n_st = index.shape[:2]
+    maps = np.zeros(tuple(stage_map.shape), dtype=np.uint8)
+    maps[:, :n_st] = np.asarray(index, dtype=np.uint8).reshape(B, n_st, n_pix)
+    table.copy_(torch.from_numpy(ops.layer_table([[float(q) for q in row] for row in levels], n_pix, C)))
+    stage_map.copy_(torch.from_numpy(maps))
+    n_stages.copy_(torch.full((B,), n_st, dtype=torch.int32))
+
+
+def check_schedule(schedule, B: int, h: int, w: int):
+    """Validate a schedule for B images of latent grid h x w and split it into the kernels' inputs.  ``schedule``: L maps
+    [B, h, w] (a sequence of them or one [L, B, h, w] array), 1 <= L <= VAM_MAX_LAYER_LEVELS, every entry finite and >= 0
+    and, at every position, non-decreasing from one stage to the next.  Returns (levels, index): per image the sorted
+    distinct values over all stages (float64 array, at most VAM_MAX_LAYER_LEVELS) and the uint8 array [B, L, h, w] of each
+    stage's index into its image's list.  Pure host code; ValueError names what is wrong."""
+    from . import _lib as L
+    from .control import quality_map_levels
+    G = L.VAM_MAX_LAYER_LEVELS
+    want = (int(B), int(h), int(w))
+    try:
+        stages = list(schedule)
+    except TypeError as e:
+        raise ValueError(f"schedule: expected a sequence of quality maps [B, H/16, W/16] = {list(want)}, got "
+                         f"{type(schedule).__name__}") from e
+    if not 1 <= len(stages) <= G:
+        raise ValueError(f"schedule: 1..{G} stages, got {len(stages)}")
+    maps = []
+    for k, m in enumerate(stages):
+        try:                                                # a stage is a quality map: shape, NaN and sign as section 9k checks them
+            lv, ix = quality_map_levels((want[0], 3, 16 * want[1], 16 * want[2]), m, None)
+        except ValueError as e:
+            raise ValueError(f"schedule: stage {k}: {e}") from e
+        maps.append(np.stack([lv[b][ix[b]] for b in range(want[0])]))
+        if np.isinf(maps[-1]).any():
+            raise ValueError(f"schedule: stage {k}: qualities must be finite, got inf")
+    S = np.stack(maps)                                      # [L, B, h, w]
+    down = np.argwhere(S[1:] < S[:-1])
+    if len(down):
+        k, b, y, x = (int(v) for v in down[0])
+        raise ValueError(f"schedule: image {b}, position ({y}, {x}): stage {k + 1} lowers the quality from {S[k, b, y, x]} to "
+                         f"{S[k + 1, b, y, x]}; a schedule never decreases from one stage to the next")
+    levels, index = [], np.zeros((want[0], len(maps)) + want[1:], dtype=np.uint8)
+    for b in range(want[0]):
+        u, inv = np.unique(S[:, b], return_inverse=True)
+        if u.size > G:
+            raise ValueError(f"schedule: image {b} holds {u.size} distinct qualities over its stages, the limit is {G} "
+                             "(VAM_MAX_LAYER_LEVELS: the levels of one mask launch)")
+        levels.append(u.astype(np.float64))
+        index[b] = inv.reshape((len(maps),) + want[1:]).astype(np.uint8)
+    return levels, index
+
+
+def _schedule_of(cs):
+    """(levels, index [B, L, h, w]) of a batch of scheduled containers, checked against the containers' own shape."""
+    from . import _lib as L
+    levels, index = [], []
+    for b, c in enumerate(cs):
+        sc = c.get("schedule")
+        if not isinstance(sc, dict) or "levels" not in sc or "index" not in sc:
+            raise ValueError(f"EmbeddedDecoder: container {b} is {FORMAT_SCHEDULED!r} and carries no schedule")
+        lv = np.asarray(sc["levels"], dtype=np.float64).reshape(-1)
+        ix = np.asarray(sc["index"])
+        h, w = 4 * int(c["shape"][0]), 4 * int(c["shape"][1])
+        if ix.dtype != np.uint8 or ix.ndim != 3 or tuple(ix.shape[1:]) != (h, w) or not 1 <= ix.shape[0] <= L.VAM_MAX_LAYER_LEVELS:
+            raise ValueError(f"EmbeddedDecoder: container {b}: the schedule's index is uint8 [1..{L.VAM_MAX_LAYER_LEVELS}, {h}, {w}], "
+                             f"got {ix.dtype} {list(ix.shape)}")
+        if not 1 <= lv.size <= L.VAM_MAX_LAYER_LEVELS or not np.all(np.isfinite(lv)) or (lv < 0).any() or (np.diff(lv) <= 0).any() \
+                or int(ix.max()) >= lv.size or (np.diff(ix.astype(np.int16), axis=0) < 0).any():
+            raise ValueError(f"EmbeddedDecoder: container {b}: not a schedule (1..{L.VAM_MAX_LAYER_LEVELS} increasing finite levels "
+                             ">= 0, indexes into them that never decrease from stage to stage)")
+        levels.append(lv)
+        index.append(ix)
+    if any(ix.shape[0] != index[0].shape[0] for ix in index):
+        raise ValueError(f"EmbeddedDecoder: every container must have the same number of stages, got "
+                         f"{sorted({int(ix.shape[0]) for ix in index})}; decode them separately")
+    return levels, np.stack(index)
+
+
+def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=None, coder: Optional[str] = None, lanes: int = 1,
+                 schedule=None) -> List[dict]:
     """Embedded containers of a batch x [B,3,H,W] (H, W multiples of 64, as for ``compress``) on the fused plans: the
     ``compress(x, 10)`` plan (symbols round(r - mu), unmasked indexes), vam_variance_rank on its progressive sigma, then
     vam_rank_gather writes symbols and indexes of every segment in rank order.  Each progressive slice becomes ONE
@@ -85,16 +187,28 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, code
     codes z and the base slices with the device coder's launches and ALL embedded streams with one more, which also gives
     the marks' bytes, and fetches lengths, status codes, marks and coded bytes only.  The containers are the same byte for
     byte.  ``lanes`` = K > 1: the embedded streams on K interleaved lanes, format ``"embedded-2"`` with ``"lanes": K``; read
-    from the argument only, never from ``model.coder_lanes``.  K = 1 is format ``"embedded-1"`` with no new key."""
+    from the argument only, never from ``model.coder_lanes``.  K = 1 is format ``"embedded-1"`` with no new key.
+
+    ``schedule`` (exclusive with ``marks``): L quality maps [B, H/16, W/16], non-decreasing from stage to
+    stage (:func:`check_schedule`).  The streams are coded in the scheduled rank order — vam_variance_layers_per_image on the
+    schedule's levels, vam_stage_ids, vam_variance_rank_staged — and marked per stage (vam_rank_counts on the stage ids);
+    the coders are unchanged.  Format ``"embedded-3"``: ``"lanes"`` always, ``"schedule"`` and its raw ``"side_bytes"``,
+    ``"marks": {"stage", "count", "bytes"}``; z and the base slices are byte for byte as before."""
     from . import _lib as L
     from . import bitstream as bs
     from . import ops
     from .models import EMPTY_SCALE_TABLE
     _check_model(model)
-    qs = P.check_q_list(marks)
+    if schedule is not None and marks is not None:
+        raise ValueError("embedded.encode_batch: give marks or schedule, not both (a scheduled container is marked per stage)")
+    B, _, H, W = x.shape
+    if schedule is not None:
+        levels, index = check_schedule(schedule, B, H // 16, W // 16)         # on the host, before any GPU work
+        qs = list(range(index.shape[1]))
+    else:
+        qs = P.check_q_list(Q_LIST if marks is None else marks)
     coder, K = P._check_coder(model, coder), bs.check_lanes(lanes)
     m = model
-    B, _, H, W = x.shape
     d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
     with torch.no_grad():
         L.require_gpu()
@@ -108,11 +222,21 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, code
         n = C * h * w
         dev = x.device
         perm = torch.empty((B, ns, n), dtype=torch.int32, device=dev)
-        ops.variance_rank(plan.std_p, perm, n_slice=ns, workspace=ops.rank_workspace(plan.std_p, ns, dev))
+        layer = torch.empty((B, h, w, d), dtype=torch.uint8, device=dev)
+        if schedule is not None:
+            table, stage_map, n_stages = schedule_buffers(B, h * w, dev)
+            fill_schedule(table, stage_map, n_stages, levels, index, h * w, C)
+            stage = torch.empty_like(layer)
+            ops.variance_layers_table(plan.std_p, table, layer, n_slice=ns)
+            ops.stage_ids(layer, stage_map, n_stages, stage)
+            ops.variance_rank_staged(plan.std_p, stage, perm, n_slice=ns, workspace=ops.rank_workspace(plan.std_p, ns, dev))
+            layer = stage                                                    # the marks count stage ids
+        else:
+            ops.variance_rank(plan.std_p, perm, n_slice=ns, workspace=ops.rank_workspace(plan.std_p, ns, dev))
         r_sym, r_idx = torch.empty_like(perm), torch.empty_like(perm)
         ops.rank_gather(perm, ns, plan.sym.window(d, d), r_sym, plan.idx.window(d, d), r_idx)
-        layer = torch.empty((B, h, w, d), dtype=torch.uint8, device=dev)
-        ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)               # the masks of the marks, as every plan builds them
+        if schedule is None:
+            ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)           # the masks of the marks, as every plan builds them
         count = torch.empty((len(qs), B, ns), dtype=torch.int32, device=dev)
         ops.rank_counts(layer, perm, ns, len(qs), count)
         if coder == "device":
@@ -152,6 +276,11 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, code
                        "bytes": [[int(cuts[k, b, j]) for j in range(ns)] for k in range(len(qs))]}}
         if K > 1:
             c["lanes"] = K
+        if schedule is not None:
+            c["format"], c["lanes"] = FORMAT_SCHEDULED, K
+            c["marks"]["stage"] = c["marks"].pop("q")
+            c["schedule"] = {"levels": [float(v) for v in levels[b]], "index": index[b].copy()}
+            c["side_bytes"] = 8 * len(levels[b]) + int(index[b].size)     # carried raw, as a quality map is (section 9k)
         containers.append(c)
     if save_path is not None:
         os.makedirs(save_path, exist_ok=True)
@@ -162,34 +291,56 @@ def encode_batch(model, x, marks: Sequence[float] = Q_LIST, save_path=None, code
 
 
 def _check_container(c) -> int:
-    """The lanes per embedded stream of container ``c``: 1 for ``"embedded-1"``, its ``"lanes"`` for ``"embedded-2"``."""
+    """The lanes per embedded stream of container ``c``: 1 for ``"embedded-1"``, its ``"lanes"`` for ``"embedded-2"`` and
+    ``"embedded-3"`` (which carries the key for K = 1 too)."""
     from . import bitstream as bs
-    if not isinstance(c, dict) or c.get("format") not in (FORMAT, FORMAT_LANES):
-        raise ValueError(f"not an embedded container (format {FORMAT!r} or {FORMAT_LANES!r}): got "
+    if not isinstance(c, dict) or c.get("format") not in (FORMAT, FORMAT_LANES, FORMAT_SCHEDULED):
+        raise ValueError(f"not an embedded container (format {FORMAT!r}, {FORMAT_LANES!r} or {FORMAT_SCHEDULED!r}): got "
                          f"{c.get('format') if isinstance(c, dict) else type(c).__name__!r}")
     if c["format"] == FORMAT:
         return 1
     K = bs.check_lanes(c.get("lanes"))
+    if c["format"] == FORMAT_SCHEDULED:
+        if not isinstance(c.get("schedule"), dict) or "side_bytes" not in c or "stage" not in c.get("marks", ()):
+            raise ValueError(f"not an embedded container: format {FORMAT_SCHEDULED!r} carries \"schedule\", \"side_bytes\" and marks "
+                             "by \"stage\", this one lacks them")
+        return K
     if K == 1:
         raise ValueError(f"an {FORMAT_LANES!r} container carries lanes > 1; one lane is format {FORMAT!r}")
     return K
 
 
 def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = None,
-             slice_bytes: Optional[Sequence[int]] = None) -> dict:
+             slice_bytes: Optional[Sequence[int]] = None, stage: Optional[int] = None) -> dict:
     """A copy of ``container`` with its embedded streams cut, on the host alone (what a server or a transmitter does).
     Exactly one of: ``q`` — a marked quality: every slice is cut at that mark's bytes; ``max_bytes`` — the largest mark
     whose z + base + embedded total fits (the base alone when no mark fits, ValueError when not even the base does);
-    ``slice_bytes`` — one explicit length per slice, any byte count (a length beyond what the slice holds keeps it whole)."""
+    ``slice_bytes`` — one explicit length per slice, any byte count (a length beyond what the slice holds keeps it whole);
+    ``stage`` — a stage of a scheduled container (``"embedded-3"``), which is marked by stage and refuses ``q``; its
+    ``max_bytes`` counts the schedule's ``side_bytes`` with z and the base."""
     _check_container(container)
-    if sum(a is not None for a in (q, max_bytes, slice_bytes)) != 1:
-        raise ValueError("truncate: give exactly one of q, max_bytes and slice_bytes")
+    if sum(a is not None for a in (q, max_bytes, slice_bytes, stage)) != 1:
+        raise ValueError("truncate: give exactly one of q, stage, max_bytes and slice_bytes")
     emb, marks = container["embedded"], container["marks"]
     ns = len(emb)
+    scheduled = container["format"] == FORMAT_SCHEDULED
+    if q is not None and scheduled:
+        raise ValueError(f"truncate: a scheduled container ({FORMAT_SCHEDULED!r}) is marked by stage, a uniform quality is no "
+                         "prefix of its order; cut it with stage=")
+    if stage is not None:
+        if not scheduled:
+            raise ValueError(f"truncate: stage= cuts a scheduled container ({FORMAT_SCHEDULED!r}), this one is "
+                             f"{container['format']!r}; cut it with q=")
+        ks = [k for k, st in enumerate(marks["stage"]) if int(st) == int(stage)] if int(stage) == stage else []
+        if not ks:
+            raise ValueError(f"truncate: stage {stage} is not marked in this container (stages {list(marks['stage'])})")
+        q, row = f"stage {int(stage)}", marks["bytes"][ks[0]]
     if slice_bytes is not None:
         cut = [int(v) for v in slice_bytes]
         if len(cut) != ns or min(cut) < 0:
             raise ValueError(f"truncate: slice_bytes takes {ns} lengths >= 0, got {list(slice_bytes)}")
+    elif stage is not None:
+        cut = [int(v) for v in row]
     elif q is not None:
         ks = [k for k, mq in enumerate(marks["q"]) if float(mq) == float(q)]
         if not ks:
@@ -197,9 +348,10 @@ def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = No
                              "lengths with slice_bytes, or decode the quality from a longer prefix")
         cut = [int(v) for v in marks["bytes"][ks[0]]]
     else:
-        fixed = sum(container_bytes(container)[:2])
+        fixed = sum(container_bytes(container)[:2]) + (int(container["side_bytes"]) if scheduled else 0)
         if fixed > max_bytes:
-            raise ValueError(f"truncate: z and the base slices take {fixed} bytes, more than max_bytes = {max_bytes}")
+            raise ValueError(f"truncate: z and the base slices{' and the schedule' if scheduled else ''} take {fixed} bytes, "
+                             f"more than max_bytes = {max_bytes}")
         cut = [0] * ns
         for row in marks["bytes"]:                         # non-decreasing with the quality
             if fixed + sum(int(v) for v in row) <= max_bytes and all(int(v) <= len(s) for v, s in zip(row, emb)):
@@ -207,7 +359,8 @@ def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = No
     if q is not None:
         short = [j for j in range(ns) if cut[j] > len(emb[j])]
         if short:
-            raise ValueError(f"truncate: slice {short[0]} holds {len(emb[short[0]])} bytes, the mark of quality {q} needs "
+            raise ValueError(f"truncate: slice {short[0]} holds {len(emb[short[0]])} bytes, the mark of "
+                             f"{q if stage is not None else f'quality {q}'} needs "
                              f"{cut[short[0]]}: the container was already cut below it")
     out = dict(container)
     out["embedded"] = [bytes(s[:b]) for s, b in zip(emb, cut)]
@@ -225,7 +378,12 @@ class EmbeddedDecoder:
     the ranked indexes; "device"  decodes z and the base slices with the device coder, uploads the
     embedded strings once and prefix-decodes them with ONE launch into the plan's ranked symbols; the counts come back
     with the status codes in one read, and the ranked indexes stay on the device unless :meth:`bits` asks for them.
-    Either coder reads either coder's containers."""
+    Either coder reads either coder's containers.
+
+    Scheduled containers (``"embedded-3"``) bring their schedule: the plan rebuilds the scheduled rank
+    order from its own sigma, :meth:`decode` and :meth:`available` work unchanged, :meth:`decode_stages` decodes stages, and
+    :meth:`decode_qualities` and :meth:`bits` are refused — a uniform quality is no prefix of a scheduled order.  A batch
+    mixes neither scheduled with plain containers nor different stage counts."""
 
     def __init__(self, model, containers, coder: Optional[str] = None):
         _check_model(model)
@@ -237,6 +395,11 @@ class EmbeddedDecoder:
             raise ValueError(f"EmbeddedDecoder: every container must have the same lanes per embedded stream, got "
                              f"{sorted(set(lanes))}; decode them separately")
         self.lanes, self.coder = lanes[0], P._check_coder(model, coder)
+        sched = [c["format"] == FORMAT_SCHEDULED for c in cs]
+        if any(sched) and not all(sched):
+            raise ValueError(f"EmbeddedDecoder: a batch holds scheduled ({FORMAT_SCHEDULED!r}) or plain containers, not both "
+                             "(their rank orders differ); decode them separately")
+        self.scheduled = sched[0]
         shape = tuple(cs[0]["shape"])
         for c in cs[1:]:
             if tuple(c["shape"]) != shape:
@@ -251,7 +414,10 @@ class EmbeddedDecoder:
         ns = model.ns0
         if any(len(c["embedded"]) != ns or len(c["base"]) != ns for c in cs):
             raise ValueError(f"EmbeddedDecoder: a container of this model has {ns} base and {ns} embedded streams")
-        self.dp = model._emb_dec_plan(self.B, hz, wz, self.coder)
+        self.schedule = _schedule_of(cs) if self.scheduled else None      # (levels, index [B, L, h, w])
+        self.n_stages = int(self.schedule[1].shape[1]) if self.scheduled else 0
+        self.dp = model._emb_dec_plan(self.B, hz, wz, self.coder, scheduled=self.scheduled)
+        self._stage_count = None                            # (device, host) int [L, B, ns]: #(stage id <= k) per segment
         self._avail: Optional[np.ndarray] = None
         self.idx_r: Optional[np.ndarray] = None             # host copy of the ranked indexes (device coder: only for bits())
         with torch.no_grad():
@@ -260,6 +426,9 @@ class EmbeddedDecoder:
     def _front(self):
         from . import bitstream as bs
         cs, ns, dp = self.containers, self.m.ns0, self.dp
+        if self.scheduled:
+            dp.fill_schedule(*self.schedule)                # before the chain that reads it, on the same stream
+            self._stage_count = None
         up = dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
         dp.owner = self
         if self.coder == "device":
@@ -340,11 +509,52 @@ class EmbeddedDecoder:
                 raise ValueError(f"EmbeddedDecoder: quality {q} needs {int(count[k, b, j])} elements of slice {j} of image {b}, "
                                  f"its container holds {int(self._avail[b, j])}")
 
+    def _refuse_scheduled(self, what: str):
+        if self.scheduled:
+            raise ValueError(f"EmbeddedDecoder.{what}: these containers are scheduled ({FORMAT_SCHEDULED!r}); a uniform quality is "
+                             "no prefix of a scheduled rank order, decode stages with decode_stages")
+
+    def decode_stages(self, ks: Sequence[int]) -> List[dict]:
+        """{"x_hat", "y_hat"} of the batch per stage of ``ks`` (any stages 0 .. L-1 in any order) of a scheduled decoder:
+        stage k equals ``forward_quality_map(x, S[k])`` bit for bit.  The counts come from the decoder's own sigma and the
+        containers' schedule (vam_rank_counts on the stage ids); ValueError when a container holds too little for a stage."""
+        from .control import sweep_groups
+        if not self.scheduled:
+            raise ValueError("EmbeddedDecoder.decode_stages: these containers carry no schedule; decode qualities with "
+                             "decode_qualities")
+        ks = list(ks)
+        if not ks or any(isinstance(k, bool) or int(k) != k or not 0 <= int(k) < self.n_stages for k in ks):
+            raise ValueError(f"stages must be integers in 0..{self.n_stages - 1}, got {ks}")
+        ks = [int(k) for k in ks]
+        with torch.no_grad():
+            self._own()
+            dp, use_graph = self.dp, self.m.use_graph
+            if self._stage_count is None:
+                count = dp.stage_counts(self.n_stages)
+                self._stage_count = (count, count.cpu().numpy())
+            count, host = self._stage_count
+            for k in sorted(set(ks)):
+                short = np.argwhere(host[k] > self._avail)
+                if len(short):
+                    b, j = (int(v) for v in short[0])
+                    raise ValueError(f"EmbeddedDecoder: stage {k} needs {int(host[k, b, j])} elements of slice {j} of image {b}, "
+                                     f"its container holds {int(self._avail[b, j])}")
+            out: List[Optional[dict]] = [None] * len(ks)
+            pos = sorted(range(len(ks)), key=lambda g: ks[g])              # the counts never decrease with the stage
+            count = count[[ks[g] for g in pos]].contiguous()
+            for _, _, groups in sweep_groups(len(pos), self.B, self.H, self.W):
+                for l0, l1 in groups:
+                    t = dp.tail_counts(count[l0:l1], use_graph)
+                    for i, g in enumerate(pos[l0:l1]):
+                        out[g] = self._result(t, i)
+        return out
+
     def decode_qualities(self, qs: Sequence[float]) -> List[dict]:
         """{"x_hat", "y_hat"} of the batch per quality of ``qs`` (any qualities >= 0 in any order, marked or not; 0 is the
         base, g_s[0] on y_hat_base).  The counts come from the decoder's own sigma; ValueError when a container holds too
         little for one of them."""
         from .control import sweep_groups
+        self._refuse_scheduled("decode_qualities")
         qs = [float(q) for q in qs]
         if not qs or any(not (q >= 0.0) or math.isinf(q) for q in qs):
             raise ValueError(f"qualities must be finite and >= 0, got {qs}")
@@ -373,6 +583,7 @@ class EmbeddedDecoder:
         """Each image's bits up to quality ``q``: z, the base and, per slice, the shortest prefix that decodes the elements
         of that quality's mask (0 = the base alone)."""
         from . import bitstream as bs
+        self._refuse_scheduled("bits")
         q = float(q)
         if not (q >= 0.0) or math.isinf(q):
             raise ValueError(f"qualities must be finite and >= 0, got {q}")

@@ -188,6 +188,33 @@ def quality_map_from_boxes(B: int, H: int, W: int, background: float, boxes) -> 
     return latent_quality_map(pm)
 
 
+def _region_sets(region, B: int, H: int, W: int, dev):
+    """[None] (all pixels) and, with a boolean pixel ``region`` [B, H, W] or [B, 1, H, W], the region and its complement."""
+    if region is None:
+        return [None]
+    r = torch.as_tensor(region).to(dev)
+    r = (r[:, 0] if r.dim() == 4 else r).bool()
+    if tuple(r.shape) != (B, H, W):
+        raise ValueError(f"region: a boolean [B, H, W] or [B, 1, H, W] for images {[B, H, W]}, got {list(r.shape)}")
+    return [None, r, ~r]
+
+
+def _sqdiff_sets(x, x_hat, sets):
+    """(sq, n) float64 [len(sets), B] on the device: per image the squared error summed over each pixel set of
+    :func:`_region_sets` and the number of values in it (compute_psnr's two terms)."""
+    B = x.shape[0]
+    sq = torch.zeros((len(sets), B), dtype=torch.float64, device=x.device)
+    n = torch.full((len(sets), B), float(x[0].numel()), dtype=torch.float64, device=x.device)
+    for k, r in enumerate(sets):
+        if r is None:
+            ops.sqdiff_sum_levels(x, x_hat, sq[k:k + 1])
+        else:                                      # outside the set both tensors are 0: only its pixels are summed
+            m = r.unsqueeze(1).to(x.dtype)
+            ops.sqdiff_sum_levels((x * m).contiguous(), (x_hat * m).contiguous(), sq[k:k + 1])
+            n[k] = 3.0 * r.flatten(1).sum(1).double()
+    return sq, n
+
+
 def rd_quality_map(model, x: torch.Tensor, qmap, region=None):
     """Rate and distortion of ``forward_quality_map(x, qmap)`` per image: {"bpp", "psnr"} float64 [B] host tensors
     (:func:`estimated_bpp` and :func:`compute_psnr` applied to each image on its own) and, with a boolean pixel ``region``
@@ -199,22 +226,8 @@ def rd_quality_map(model, x: torch.Tensor, qmap, region=None):
     with torch.no_grad():
         out = model.forward_quality_map(x, qmap)
         x_hat = out["x_hat"].contiguous()
-        sets = [None]
-        if region is not None:
-            r = torch.as_tensor(region).to(dev)
-            r = (r[:, 0] if r.dim() == 4 else r).bool()
-            if tuple(r.shape) != (B, H, W):
-                raise ValueError(f"region: a boolean [B, H, W] or [B, 1, H, W] for images {[B, H, W]}, got {list(r.shape)}")
-            sets += [r, ~r]
-        sq = torch.zeros((len(sets), B), dtype=torch.float64, device=dev)
-        n = torch.full((len(sets), B), float(x[0].numel()), dtype=torch.float64, device=dev)
-        for k, r in enumerate(sets):
-            if r is None:
-                ops.sqdiff_sum_levels(x, x_hat, sq[k:k + 1])
-            else:                                      # outside the set both tensors are 0: only its pixels are summed
-                m = r.unsqueeze(1).to(x.dtype)
-                ops.sqdiff_sum_levels((x * m).contiguous(), (x_hat * m).contiguous(), sq[k:k + 1])
-                n[k] = 3.0 * r.flatten(1).sum(1).double()
+        sets = _region_sets(region, B, H, W, dev)
+        sq, n = _sqdiff_sets(x, x_hat, sets)
         vals = torch.cat([out["log2_likelihood_sum"].sum(0, keepdim=True), sq, n]).cpu()
     ns = len(sets)
     psnr = -10.0 * torch.log10(vals[1:1 + ns] / vals[1 + ns:])
@@ -408,6 +421,49 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
         r["psnr"] = sum(r["psnr_all"]) / len(images)
         r["enc_s"] /= len(images)
         r["dec_s"] /= len(images)
+    return rows
+
+
+def roi_schedule(B: int, H: int, W: int, boxes, roi_qualities: Sequence[float], background_qualities: Sequence[float]):
+    """A region-of-interest schedule for embedded.encode_batch(schedule=...): a list of latent quality
+    maps [B, H/16, W/16].  ``boxes``: pixel boxes ``(b, y0, x0, y1, x1)`` of the region.  First the region climbs through
+    ``roi_qualities`` over the background at ``background_qualities[0]``, then the background climbs through the rest of
+    ``background_qualities`` under the region at ``roi_qualities[-1]``.  Both lists non-decreasing; a stage at which the
+    background would pass the region is refused by embedded.check_schedule's monotonicity (the block-maximum rule of
+    :func:`latent_quality_map` gives a block that touches the region the larger of the two)."""
+    rq, bq = [float(q) for q in roi_qualities], [float(q) for q in background_qualities]
+    if not rq or not bq:
+        raise ValueError("roi_schedule: roi_qualities and background_qualities need at least one quality each")
+    stages = [(r, bq[0]) for r in rq] + [(rq[-1], g) for g in bq[1:]]
+    return [quality_map_from_boxes(B, H, W, g, [tuple(box[:5]) + (r,) for box in boxes]) for r, g in stages]
+
+
+def embedded_roi_rd(model, images: torch.Tensor, schedule, region, coder=None, lanes: int = 1):
+    """Rate and distortion per stage of a scheduled embedded stream: ``images`` [B, 3, H, W] (H, W
+    multiples of 64) are coded ONCE with embedded.encode_batch(schedule=...), and every stage is decoded from the same
+    containers.  One dict per stage: "stage", "bytes" (per image: z, the base, the schedule's side bytes and the stage's
+    mark of every slice — what a receiver needs for it), "bpp" (8 * bytes / pixels), and "psnr", "psnr_in", "psnr_out"
+    (float64 [B] host tensors; :func:`rd_quality_map`'s definition on all pixels and on the pixels inside and outside the
+    boolean pixel ``region`` [B, H, W] or [B, 1, H, W])."""
+    from . import embedded as EB
+    dev = next(model.parameters()).device
+    x = images.to(dev).contiguous()
+    B, _, H, W = x.shape
+    sets = _region_sets(region, B, H, W, dev)
+    if len(sets) != 3:
+        raise ValueError("embedded_roi_rd: region is a boolean [B, H, W] or [B, 1, H, W]")
+    rows = []
+    with torch.no_grad():
+        containers = EB.encode_batch(model, x, schedule=schedule, coder=coder, lanes=lanes)
+        dec = EB.EmbeddedDecoder(model, containers, coder=coder)
+        for k in range(dec.n_stages):
+            x_hat = dec.decode_stages([k])[0]["x_hat"].contiguous()
+            sq, n = _sqdiff_sets(x, x_hat, sets)
+            psnr = (-10.0 * torch.log10(sq / n)).cpu()
+            nbytes = [sum(EB.container_bytes(c)[:2]) + int(c["side_bytes"]) + sum(int(v) for v in c["marks"]["bytes"][k])
+                      for c in containers]
+            rows.append({"stage": k, "bytes": nbytes, "bpp": [8.0 * v / (H * W) for v in nbytes],
+                         "psnr": psnr[0], "psnr_in": psnr[1], "psnr_out": psnr[2]})
     return rows
 
 

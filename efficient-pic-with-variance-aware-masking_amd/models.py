@@ -746,12 +746,14 @@ class VarianceMaskingPIC(CompressionModel):
                                  + ((coder,) if coder != "host" else ()),
                                  lambda: _ProgDecPlan(self, B, hz, wz, q_list, dev, coder=coder), self._weights_sig())
 
-    def _emb_dec_plan(self, B, hz, wz, coder: str = "host") -> "_EmbDecPlan":
+    def _emb_dec_plan(self, B, hz, wz, coder: str = "host", scheduled: bool = False) -> "_EmbDecPlan":
         """The plans of embedded.EmbeddedDecoder for one (B, z-shape, coder), cached beside decompress's: the cuts are graph
-        inputs, so no quality list is part of the key."""
+        inputs, so no quality list is part of the key.  ``scheduled`` (DESIGN section 9r): the plan of scheduled containers;
+        the key says so and carries no schedule, which is an input of the plan's device buffers."""
         dev = self.entropy_bottleneck.quantiles.device
-        return self._cached_plan(self._dec_plans, ("emb", B, hz, wz, str(dev)) + ((coder,) if coder != "host" else ()),
-                                 lambda: _EmbDecPlan(self, B, hz, wz, dev, coder=coder), self._weights_sig())
+        return self._cached_plan(self._dec_plans, ("emb", B, hz, wz, str(dev)) + ((coder,) if coder != "host" else ())
+                                 + (("scheduled",) if scheduled else ()),
+                                 lambda: _EmbDecPlan(self, B, hz, wz, dev, coder=coder, scheduled=scheduled), self._weights_sig())
 
 
 class VarianceMaskingPICREM(VarianceMaskingPIC):

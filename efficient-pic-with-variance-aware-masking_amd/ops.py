@@ -549,11 +549,8 @@ def variance_layers_per_image(sigma: View, prs: Sequence[Sequence[float]], layer
     nl = (C.c_int * sigma.B)(*[len(r) for r in lists])
     table = np.zeros(sigma.B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
     L.check(L.load().vam_variance_layer_params(flat, nl, sigma.B, width, hw, slice_C, table.ctypes.data), "vam_variance_layer_params")
-    dev = torch.from_numpy(table).to(sigma.buf.device)
-    L.check(L.load().vam_variance_layers_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
-                                                   dev.data_ptr(), layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
-                                                   thr.data_ptr() if thr is not None else None, stream_ptr()),
-            "vam_variance_layers_per_image")        # `dev` returns to the allocator of this same stream
+    variance_layers_table(sigma, torch.from_numpy(table).to(sigma.buf.device), layer, n_slice=n_slice, thr=thr, thr_levels=width)
+    # the device copy of the table returns to the allocator of this same stream
 
 
 def mask_table(prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int) -> np.ndarray:
@@ -657,6 +654,60 @@ def variance_rank(sigma: View, perm: torch.Tensor, n_slice: int = 1, workspace: 
     L.check(L.load().vam_variance_rank(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, perm.data_ptr(),
                                        workspace.data_ptr() if workspace is not None else None,
                                        8 * workspace.numel() if workspace is not None else 0, stream_ptr()), "vam_variance_rank")
+
+
+def variance_layers_table(sigma: View, table_dev: torch.Tensor, layer: torch.Tensor, n_slice: int = 1,
+                          thr: Optional[torch.Tensor] = None, thr_levels: int = L.VAM_MAX_LAYER_LEVELS):
+    """:func:`variance_layers_per_image` with image b's list read from record b of ``table_dev`` (the bytes of
+    :func:`layer_table` on the device): no host arithmetic and no copy, so the call can be captured and the captured
+    launch serves every table content.  ``thr`` holds ``thr_levels`` rows, at least the longest list of the table."""
+    slice_C = sigma.C // n_slice
+    hw = sigma.H * sigma.W
+    assert slice_C * n_slice == sigma.C
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
+    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
+        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
+    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= thr_levels * sigma.B * n_slice)
+    L.check(L.load().vam_variance_layers_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
+                                                   table_dev.data_ptr(), layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
+                                                   thr.data_ptr() if thr is not None else None, stream_ptr()),
+            "vam_variance_layers_per_image")
+
+
+def stage_ids(layer: torch.Tensor, stage_map: torch.Tensor, n_stages: torch.Tensor, stage: torch.Tensor):
+    """Scheduled embedded streams: ``stage`` uint8 [B, H, W, Ct] gets, for the layer ids ``layer`` of
+    :func:`variance_layers_per_image` (same shape), the first stage k < n_stages[b] whose index map reaches the id,
+    ``stage_map[b, k, p] >= layer[e]``, L.LAYER_NONE when none does or when n_stages[b] is outside
+    1..L.VAM_MAX_LAYER_LEVELS.  ``stage_map`` uint8 [B, L.VAM_MAX_LAYER_LEVELS, H * W] and ``n_stages`` int32 [B] are device
+    buffers, so the call can be captured and the captured launch serves every schedule."""
+    B, H, W, Ct = layer.shape
+    dev = layer.device
+    assert layer.dtype == torch.uint8 and layer.is_contiguous() and layer.is_cuda
+    assert stage.dtype == torch.uint8 and stage.is_contiguous() and stage.shape == layer.shape and stage.device == dev
+    assert stage_map.dtype == torch.uint8 and stage_map.is_contiguous() and stage_map.device == dev and \
+        stage_map.numel() == B * L.VAM_MAX_LAYER_LEVELS * H * W, (tuple(stage_map.shape), B, H, W)
+    assert n_stages.dtype == torch.int32 and n_stages.is_contiguous() and n_stages.device == dev and n_stages.numel() == B
+    L.check(L.load().vam_stage_ids(layer.data_ptr(), Ct, stage_map.data_ptr(), n_stages.data_ptr(), B, H * W, Ct,
+                                   stage.data_ptr(), Ct, stream_ptr()), "vam_stage_ids")
+
+
+def variance_rank_staged(sigma: View, stage: torch.Tensor, perm: torch.Tensor, n_slice: int = 1,
+                         workspace: Optional[torch.Tensor] = None):
+    """:func:`variance_rank` with the ids of :func:`stage_ids` (uint8 [B, H, W, sigma.C]) as the major key: ascending
+    stage, within a stage descending sigma with :func:`variance_rank`'s ties.  With o = numpy.argsort(-s, kind="stable"),
+    ``perm`` = o[numpy.argsort(stage[o], kind="stable")].  Same workspace (:func:`rank_workspace`); capturable."""
+    slice_C = sigma.C // n_slice
+    hw = sigma.H * sigma.W
+    assert slice_C * n_slice == sigma.C
+    assert stage.dtype == torch.uint8 and stage.is_contiguous() and tuple(stage.shape) == (sigma.B, sigma.H, sigma.W, sigma.C) \
+        and stage.device == sigma.buf.device
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == sigma.B * n_slice * hw * slice_C
+    assert workspace is None or (workspace.dtype == torch.int64 and workspace.is_contiguous())
+    L.check(L.load().vam_variance_rank_staged(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, stage.data_ptr(), sigma.C, sigma.B,
+                                              n_slice, hw, slice_C, perm.data_ptr(),
+                                              workspace.data_ptr() if workspace is not None else None,
+                                              8 * workspace.numel() if workspace is not None else 0, stream_ptr()),
+            "vam_variance_rank_staged")
 
 
 def _rank_view(v: "IView", n_slice: int, slice_C: int):

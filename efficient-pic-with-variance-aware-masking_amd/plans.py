@@ -1186,11 +1186,17 @@ class _EmbDecPlan(_ProgDecPlan):
     vam_rank_counts: count = #(layer id <= k) per segment).  A tail is vam_rank_scatter — the ranked symbols below each
     level's count back to the NHWC view, with the level ids in ``layer`` — and then the parent's _SweepTail in decode mode
     with the fixed cut-offs 0 .. G-1.  The count table is a graph input, copied before the replay on the runner's stream
-    and outside any capture, so the plan keeps ONE hipGraph per group size whatever the cuts."""
+    and outside any capture, so the plan keeps ONE hipGraph per group size whatever the cuts.
 
-    def __init__(self, m, B, hz, wz, device, coder: str = "host"):
+    ``scheduled``: the rank order is the scheduled one — vam_variance_layers_per_image on the schedule's
+    levels, vam_stage_ids, vam_variance_rank_staged — from three device buffers (embedded.schedule_buffers) that
+    :meth:`fill_schedule` refills on the runner's stream before the chain runs and outside any capture.  The tails read
+    ``perm`` and counts only, so they, and their one graph per group size, are the plain plan's whatever the schedule."""
+
+    def __init__(self, m, B, hz, wz, device, coder: str = "host", scheduled: bool = False):
         """``coder`` "device" (DESIGN section 9q): z and the base slices are decoded by the device coder as in _ProgDecPlan,
         and the decoder prefix-decodes the embedded strings from ``idx_r`` into ``ranked`` with one launch."""
+        self.scheduled = bool(scheduled)                   # before super().__init__: it runs _lower_progressive, which reads it
         super().__init__(m, B, hz, wz, (), device, coder=coder)
         self.counts: Dict[int, torch.Tensor] = {}          # group size -> int32 [G, B, ns], the tails' graph input
 
@@ -1209,7 +1215,17 @@ class _EmbDecPlan(_ProgDecPlan):
         self.idx_r = torch.empty((B, ns, n), dtype=torch.int32, device=device)                   # table indexes, rank order
         self.rank_ws = ops.rank_workspace(std_p, ns, device)
         P.keep += [self.layer, self.qlayer, self.idx_l.buf, self.sym.buf, self.perm, self.ranked, self.idx_r, self.rank_ws]
-        P.call(lambda: ops.variance_rank(std_p, self.perm, n_slice=ns, workspace=self.rank_ws), "rank order")
+        if self.scheduled:
+            from .embedded import schedule_buffers
+            self.sched_table, self.stage_map, self.n_stages = schedule_buffers(B, h * w, device)
+            self.stage = torch.empty((B, h, w, d), dtype=torch.uint8, device=device)             # stage id of every element
+            P.keep += [self.sched_table, self.stage_map, self.n_stages, self.stage]
+            P.call(lambda: ops.variance_layers_table(std_p, self.sched_table, self.qlayer, n_slice=ns), "schedule layers")
+            P.call(lambda: ops.stage_ids(self.qlayer, self.stage_map, self.n_stages, self.stage), "stage ids")
+            P.call(lambda: ops.variance_rank_staged(std_p, self.stage, self.perm, n_slice=ns, workspace=self.rank_ws),
+                   "scheduled rank order")
+        else:
+            P.call(lambda: ops.variance_rank(std_p, self.perm, n_slice=ns, workspace=self.rank_ws), "rank order")
         P.call(lambda: ops.build_indexes(std_p, m.gaussian_conditional.scale_table, out=self.idx_l))   # functions_decode.py:179-180
         P.call(lambda: ops.rank_gather(self.perm, ns, self.idx_l, self.idx_r), "indexes in rank order")
         self.sweep_parts = dict(heads=sc.heads, yb=sc.yb, mu=mu_p, std=std_p, mu_tot=sc.mu_tot, sym=self.sym, layer=self.layer,
@@ -1223,6 +1239,23 @@ class _EmbDecPlan(_ProgDecPlan):
         with self.runner.on_stream():
             ops.variance_layers(self.sc.std_p, [float(q) for q in qs], self.qlayer, n_slice=ns)
             ops.rank_counts(self.qlayer, self.perm, ns, len(qs), count)
+        return count
+
+    def fill_schedule(self, levels, index):
+        """Refill the scheduled plan's inputs from embedded.check_schedule's (levels, index [B, L, h, w]): on the runner's
+        stream, before :meth:`front` runs the chain that reads them, outside any capture."""
+        from .embedded import fill_schedule
+        assert self.scheduled and len(levels) == self.B
+        with self.runner.on_stream():
+            fill_schedule(self.sched_table, self.stage_map, self.n_stages, levels, index, self.h * self.w, self.m.dim_chunk)
+
+    def stage_counts(self, n_stages: int) -> torch.Tensor:
+        """int32 [n_stages, B, ns] on the device: #(stage id <= k) per segment, the prefix of the scheduled order that
+        stage k's map keeps."""
+        ns = self.m.ns0
+        count = torch.empty((n_stages, self.B, ns), dtype=torch.int32, device=self.device)
+        with self.runner.on_stream():
+            ops.rank_counts(self.stage, self.perm, ns, n_stages, count)
         return count
 
     def tail_counts(self, count, use_graph: bool) -> _SweepTail:

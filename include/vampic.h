@@ -364,6 +364,25 @@ int vam_rank_counts(const uint8_t* layer, int ld_layer, const int32_t* perm, int
  * launch serves every cut. */
 int vam_rank_scatter(const int32_t* ranked, const int32_t* perm, const int32_t* count, int n_levels, int n_batch, int n_slice,
                      int n_pix, int C, int32_t* sym_out, int ld_sym, uint8_t* id_out, int ld_id, void* stream);
+/* Scheduled embedded streams.  A schedule is 1..VAM_MAX_LAYER_LEVELS quality maps per image that never
+ * decrease from stage to stage at any pixel; image b's sorted distinct values are the list of its vam_layer_params record
+ * and stage_map[b][k][p] (uint8, [n_batch][VAM_MAX_LAYER_LEVELS][n_pix]) is the index of stage k's quality at pixel p in
+ * that list.  For the layer ids of vam_variance_layers_per_image on that table (uint8, n_batch * n_pix pixels of C_total
+ * channels, pixel stride ld_layer) vam_stage_ids writes, in the same layout (pixel stride ld_out),
+ *   stage_out[e] = min{k < n_stages[b] : stage_map[b][k][p] >= layer[e]},  0xFF when there is none,
+ * so that  stage[e] <= k  <=>  vam_variance_mask_map of stage k's map holds e.  n_stages (int32 [n_batch]) and the maps
+ * are read on the device: one captured launch serves every schedule.  An image whose n_stages is outside
+ * 1..VAM_MAX_LAYER_LEVELS gets 0xFF everywhere.
+ * vam_variance_rank_staged is vam_variance_rank with that id (slice j's channels at j*C, pixel stride ld_stage) as the
+ * major key: ascending stage, within a stage vam_variance_rank's order,
+ *   o = numpy.argsort(-sigma_s, kind="stable");  perm[s] == o[numpy.argsort(stage_s[o], kind="stable")].
+ * Same network, chunks, workspace (vam_variance_rank_workspace) and passes.  The ids never decrease along this order, so
+ * vam_rank_counts on them gives #(stage <= k), and vam_rank_gather / vam_rank_scatter take the permutation as it is. */
+int vam_stage_ids(const uint8_t* layer, int ld_layer, const uint8_t* stage_map, const int32_t* n_stages, int n_batch, int n_pix,
+                  int C_total, uint8_t* stage_out, int ld_out, void* stream);
+int vam_variance_rank_staged(const float* sigma, int ld, long batch_stride, long slice_stride, const uint8_t* stage,
+                             int ld_stage, int n_batch, int n_slice, int n_pix, int C, int32_t* perm_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).

@@ -13,7 +13,13 @@ time is asserted.  Prints one JSON line.
 alternation: encode ms, decode ms and bytes per image under "cells", next to the host K = 1 cell of the same run, which is
 the "embedded" path above.  x_hat of every level is asserted identical for every cell.
 
-    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64]
+``--schedule roi`` measures scheduled streams instead: a centre box climbs through 3 stages to
+q = 10 over background 0, then the background climbs through 3 stages.  Per (coder, lanes) cell the scheduled encode and the
+decode of all 6 stages alternate with the plain embedded encode and the decode of as many marks, same run, same inputs;
+before timing, x_hat of every stage is asserted identical to ``forward_quality_map`` of that stage's map.  The plain cells
+are the same calls the default mode times.
+
+    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64] [--schedule roi]
 """
 import argparse
 import json
@@ -27,7 +33,59 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+ROI_Q, BACKGROUND_Q = [1, 4, 10], [0, 0.5, 2, 5]          # --schedule roi: 3 region stages, then 3 background stages
+PLAIN_MARKS = [0.5, 1, 2, 4, 5, 10]                        # as many marks for the plain path of the same run
 DEMO_Q = [0.01, 0.05, 0.1, 0.25, 0.5, 0.6, 0.7, 0.8, 0.9, 1, 2, 3, 4, 4.5, 10]       # reference test/parser.py:20
+
+
+def schedule_main(a, net, dev):
+    """--schedule roi: scheduled against plain embedded streams, interleaved; prints one JSON line."""
+    import vampic
+    from vampic import bitstream as bs, embedded as EB, evaluate as EV
+    res = {"metric": "scheduled vs plain embedded streams (ms, median)", "device": torch.cuda.get_device_name(0),
+           "coder_threads": bs.coder_threads(), "warmup": a.warmup, "reps": a.reps, "stages": len(ROI_Q) + len(BACKGROUND_Q) - 1,
+           "cases": {}}
+    for case, B, H, W in (("1x512x768", 1, 512, 768), ("8x256x256", 8, 256, 256)):
+        x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
+        S = EV.roi_schedule(B, H, W, [(b, H // 4, W // 4, 3 * H // 4, 3 * W // 4) for b in range(B)], ROI_Q, BACKGROUND_Q)
+        ks = list(range(len(S)))
+        assert len(S) == len(PLAIN_MARKS)
+        cells = {}
+        for c in a.coder:
+            for K in a.lanes:
+                cells[f"plain_{c}_k{K}"] = (lambda c=c, K=K: EB.encode_batch(net, x, PLAIN_MARKS, coder=c, lanes=K),
+                                            lambda cs, c=c: EB.EmbeddedDecoder(net, cs, coder=c).decode_qualities(PLAIN_MARKS))
+                cells[f"scheduled_{c}_k{K}"] = (lambda c=c, K=K: EB.encode_batch(net, x, schedule=S, coder=c, lanes=K),
+                                                lambda cs, c=c: EB.EmbeddedDecoder(net, cs, coder=c).decode_stages(ks))
+        t = {f"{p}_{ph}": [] for p in cells for ph in ("enc", "dec")}
+        size = {}
+        with torch.no_grad():
+            want = [net.forward_quality_map(x, m)["x_hat"] for m in S]
+            for p, (enc, dec) in cells.items():                                  # equality before any timing
+                if p.startswith("scheduled"):
+                    for k, (o, w_) in enumerate(zip(dec(enc()), want)):
+                        assert torch.equal(o["x_hat"], w_), f"{case}: {p}: x_hat of stage {k} differs from forward_quality_map"
+            for rep in range(a.warmup + a.reps):
+                for p, (enc, dec) in cells.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    cs = enc()
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    dec(cs)
+                    torch.cuda.synchronize()
+                    t2 = time.perf_counter()
+                    if rep >= a.warmup:
+                        t[f"{p}_enc"].append(1e3 * (t1 - t0))
+                        t[f"{p}_dec"].append(1e3 * (t2 - t1))
+                    size[p] = sum(len(s_) for c_ in cs for s_ in c_["embedded"]) / B
+        med = {k: round(statistics.median(v), 1) for k, v in t.items()}
+        med.update(x_hat_identical_to_forward_quality_map=True, side_bytes_per_image=cs[0].get("side_bytes"),
+                   embedded_bytes_per_image={p: round(v, 1) for p, v in size.items()})
+        res["cases"][case] = med
+        net._drop_plans()
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
 
 
 def main():
@@ -36,6 +94,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--coder", nargs="+", default=["host"], choices=["host", "device"])
     ap.add_argument("--lanes", nargs="+", type=int, default=[1])
+    ap.add_argument("--schedule", choices=["roi"], default=None)
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -43,6 +102,8 @@ def main():
     dev = torch.device("cuda:0")
     net, _ = build_model(dev)
     net.update()
+    if a.schedule:
+        return schedule_main(a, net, dev)
     coder = [0.0]
 
     def timed(fn):
