@@ -53,6 +53,11 @@ class VamRansStream(C.Structure):
                 ("n_bytes", C.c_long)]
 
 
+class VamRansCheckpoint(C.Structure):
+    """vam_rans_checkpoint: a resumable stream's decoder at the start of a group."""
+    _fields_ = [("done", C.c_long), ("pos", C.c_long), ("states", C.c_void_p)]
+
+
 class VamLayerParams(C.Structure):
     """vam_layer_params: one image's record of the device table of vam_variance_layers_per_image."""
     _fields_ = [("n_levels", C.c_int32), ("any_select", C.c_int32), ("k_lo", C.c_int32 * VAM_MAX_LAYER_LEVELS),
@@ -292,6 +297,13 @@ _SIGNATURES = {
     "vam_rans_interleaved_decode_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long,
                                                      C.c_int, C.POINTER(VamRansTables), C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]),
+    "vam_rans_interleaved_resume": (C.c_long, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(VamRansCheckpoint), C.c_void_p]),
+    "vam_rans_interleaved_resume_streams": (C.c_int, [C.POINTER(VamRansStream), C.POINTER(VamRansCheckpoint), C.c_int, C.c_void_p,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                      C.c_void_p]),
+    "vam_rans_interleaved_resume_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long,
+                                                     C.c_int, C.POINTER(VamRansTables)] + [C.c_void_p] * 7),
     "vam_variance_rank_workspace": (C.c_size_t, [C.c_int] * 4),
     "vam_variance_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -259,6 +259,63 @@ def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[in
     return [int(c) for c in counts[:len(jobs)]]
 
 
+@dataclass
+class Checkpoints:
+    """The checkpoints of ``n`` resumable streams on K lanes: per stream the decoder at the start of a
+    group — ``done`` elements before it, ``pos`` the next word of the whole string, ``states`` [n, K] the lane states.  On the
+    host numpy arrays (uint64, int64, int64), on the device tensors (int64 holding the uint64 bits, int32, int32)."""
+    states: object
+    done: object
+    pos: object
+
+    @staticmethod
+    def fresh(n_streams: int, lanes: int, device=None) -> "Checkpoints":
+        K = check_lanes(lanes)
+        if device is None:
+            return Checkpoints(np.zeros((n_streams, K), dtype=np.uint64), np.zeros(n_streams, dtype=np.int64),
+                               np.zeros(n_streams, dtype=np.int64))
+        return Checkpoints(torch.zeros((n_streams, K), dtype=torch.int64, device=device),
+                           torch.zeros(n_streams, dtype=torch.int32, device=device),
+                           torch.zeros(n_streams, dtype=torch.int32, device=device))
+
+
+def resume_prefix_streams(jobs: Sequence[Tuple], t: Tables, checkpoints: Checkpoints, threads: Optional[int] = None, lanes: int = 1,
+                          status: Optional[np.ndarray] = None) -> List[int]:
+    """:func:`decode_prefix_streams` continued from ``checkpoints`` (host arrays, one row per job, updated in place) in one
+    vam_rans_interleaved_resume_streams call.  ``jobs``: (the bytes of the string FROM BYTE 4 * pos ON, the indexes of the
+    whole stream, out); out[done_in:count] is written, nothing else.  Per job the count :func:`decode_prefix_streams` gives
+    on everything received so far.  The bytes beyond the last whole word are not consumed: send them again, in front of what
+    follows.  ``status`` (int32, one per job) receives the status codes; a non-zero one raises VamError all the same."""
+    K = check_lanes(lanes)
+    ck = checkpoints
+    nj = len(jobs)
+    if not (isinstance(ck.states, np.ndarray) and ck.states.dtype == np.uint64 and ck.states.shape == (nj, K)
+            and ck.states.flags.c_contiguous and all(isinstance(a, np.ndarray) and a.dtype == np.int64 and a.shape == (nj,)
+                                                     for a in (ck.done, ck.pos))):
+        raise ValueError(f"resume_prefix_streams: host checkpoints of {nj} streams on {K} lanes (Checkpoints.fresh)")
+    keep, arr, cks = [], (L.VamRansStream * max(nj, 1))(), (L.VamRansCheckpoint * max(nj, 1))()
+    for k, j in enumerate(jobs):
+        src = np.frombuffer(j[0], dtype=np.uint8)
+        i, o = _i32(j[1]), j[2]
+        assert o.dtype == np.int32 and o.flags.c_contiguous and o.flags.writeable and o.size == i.size
+        keep.append((src, i))
+        arr[k] = L.VamRansStream(None, o.ctypes.data, i.ctypes.data, None, i.size, 0, 0, src.ctypes.data if src.size else None,
+                                 src.size, src.size)
+        cks[k] = L.VamRansCheckpoint(int(ck.done[k]), int(ck.pos[k]), ck.states.ctypes.data + 8 * K * k)
+    counts = np.zeros(max(nj, 1), dtype=np.int64)
+    st = np.zeros(max(nj, 1), dtype=np.int32)
+    rc = L.load().vam_rans_interleaved_resume_streams(arr, cks, nj, t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data,
+                                                      t.offsets.ctypes.data, t.cdf.shape[0], K,
+                                                      coder_threads() if threads is None else int(threads), counts.ctypes.data,
+                                                      st.ctypes.data)
+    for k in range(nj):
+        ck.done[k], ck.pos[k] = cks[k].done, cks[k].pos
+    if status is not None:
+        status[:nj] = st[:nj]
+    L.check(rc, "vam_rans_interleaved_resume_streams")
+    return [int(c) for c in counts[:nj]]
+
+
 def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables, lanes: int = 1) -> List[int]:
     """Per element count of the sorted list ``counts``: the smallest byte length (a multiple of 4) from which
     :func:`decode_prefix_streams` yields at least that many symbols of ``stream`` (0 for a count of 0).  One decoding pass.
@@ -815,6 +872,39 @@ def decode_embedded_uploaded(up: DeviceStreams, first: int, r_idx: torch.Tensor,
                                                         r_idx.data_ptr(), ns, n, K, C.byref(tables.struct), ranked.data_ptr(),
                                                         meta[0].data_ptr(), meta[1].data_ptr(), ops.stream_ptr()),
             "vam_rans_interleaved_decode_device")
+
+
+def resume_embedded_uploaded(up: DeviceStreams, first: int, r_idx: torch.Tensor, ranked: torch.Tensor, tables: DeviceCoderTables,
+                             lanes: int, checkpoints: Checkpoints, meta: torch.Tensor):
+    """:func:`decode_embedded_uploaded` continued from ``checkpoints`` (device tensors, updated by the kernel): ONE
+    vam_rans_interleaved_resume_device launch on the current stream, no synchronisation.  String k of ``up`` (from ``first``
+    on) holds stream k FROM BYTE 4 * pos[k] ON.  ``ranked`` receives the elements done_in <= i < available of every stream and
+    keeps what it holds elsewhere; ``meta`` (int32 [3, n_streams] on the device) the available counts, the status codes and
+    the new ``pos``, which is all the host needs to cut the next upload."""
+    from . import ops
+    K = check_lanes(lanes)
+    for a in (r_idx, ranked):
+        if a.dtype != torch.int32 or not a.is_contiguous() or tuple(a.shape) != tuple(r_idx.shape):
+            raise ValueError("device coder: the ranked symbols and indexes are contiguous int32 device buffers of one shape")
+    n = int(r_idx.shape[-1])
+    ns = int(np.prod(r_idx.shape[:-1]))
+    if first < 0 or first + ns > up.n:
+        raise ValueError(f"device coder: strings {first} .. {first + ns} of {up.n} uploaded")
+    if meta.dtype != torch.int32 or tuple(meta.shape) != (3, ns) or not meta.is_contiguous():
+        raise ValueError(f"device coder: meta is a contiguous int32 [3, {ns}] buffer")
+    ck = checkpoints
+    if not (torch.is_tensor(ck.states) and ck.states.dtype == torch.int64 and tuple(ck.states.shape) == (ns, K)
+            and ck.states.is_contiguous() and all(torch.is_tensor(a) and a.dtype == torch.int32 and tuple(a.shape) == (ns,)
+                                                  and a.is_contiguous() for a in (ck.done, ck.pos))):
+        raise ValueError(f"device coder: device checkpoints of {ns} streams on {K} lanes (Checkpoints.fresh)")
+    total = up.buf.numel() - (up.bytes_ptr - up.buf.data_ptr())
+    L.check(L.load().vam_rans_interleaved_resume_device(up.bytes_ptr, total, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                                        r_idx.data_ptr(), ns, n, K, C.byref(tables.struct), ranked.data_ptr(),
+                                                        ck.states.data_ptr(), ck.done.data_ptr(), ck.pos.data_ptr(),
+                                                        meta[0].data_ptr(), meta[1].data_ptr(), ops.stream_ptr()),
+            "vam_rans_interleaved_resume_device")
+    if ck.pos.data_ptr() != meta[2].data_ptr():               # a decoder keeps pos in meta itself
+        meta[2].copy_(ck.pos)
 
 
 def sigma0_index(scale_table) -> int:

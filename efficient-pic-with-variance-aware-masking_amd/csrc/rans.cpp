@@ -517,9 +517,88 @@ long ilv_decode_one(const char* what, const uint8_t* in, long n_bytes, const int
   return available;
 }
 
+// The resumable decode of one stream: `in` holds the string from byte 4 * ck->pos on.  Returns the count
+// (< 0: refused by message, nothing written); *status_out receives the status that ended the stream.
+long ilv_resume_one(const char* what, const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs,
+                    int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes, int32_t* out,
+                    vam_rans_checkpoint* ck, int32_t* status_out) {
+  if (n_bytes < 0 || n < 0) {
+    set_error("%s: bad arguments (%ld bytes for %ld symbols)", what, n_bytes, n);
+    return VAM_EINVAL;
+  }
+  if ((!in && n_bytes > 0) || (!indexes && n > 0) || !cdfs || !cdf_sizes || !offsets || n_cdfs < 1 || !ck || !ck->states) {
+    set_error("%s: bad arguments (need the bytes, indexes, tables and a checkpoint with its states)", what);
+    return VAM_EINVAL;
+  }
+  if (!R::lanes_valid(lanes)) {
+    set_error("%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+    return VAM_EINVAL;
+  }
+  if ((uintptr_t)ck->states & 7) {
+    set_error("%s: the checkpoint's states are 64-bit words, the pointer is misaligned", what);
+    return VAM_EINVAL;
+  }
+  if (!R::checkpoint_valid(ck->done, ck->pos, n, lanes)) {
+    set_error("%s: impossible checkpoint (done = %ld, pos = %ld for %ld symbols on %d lanes: done is a multiple of lanes or n, "
+              "and pos >= 2 * lanes once done > 0)", what, ck->done, ck->pos, n, lanes);
+    return VAM_EINVAL;
+  }
+  std::vector<uint32_t> words((size_t)n_bytes / 4);         // aligned copy of the whole words
+  if (!words.empty()) std::memcpy(words.data(), in, words.size() * 4);
+  long available = 0, done = ck->done, pos = ck->pos;
+  const int32_t st = R::interleaved_resume(words.empty() ? nullptr : words.data(), (long)words.size() * 4, lanes, indexes, n, R::Flat{},
+                                           R::Int32Rows{cdfs, cdf_stride}, cdf_stride, cdf_sizes, offsets, n_cdfs, out, &available,
+                                           &done, &pos, ck->states);
+  ck->done = done;
+  ck->pos = pos;
+  *status_out = st;
+  return available;
+}
+
 }  // namespace
 
 extern "C" {
+
+long vam_rans_interleaved_resume(const uint8_t* in, long n_bytes, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
+                                 const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes, int32_t* out,
+                                 vam_rans_checkpoint* checkpoint, int32_t* status_out) {
+  const char* what = "vam_rans_interleaved_resume";
+  int32_t st = 0;
+  const long got = ilv_resume_one(what, in, n_bytes, indexes, n, cdfs, cdf_stride, cdf_sizes, offsets, n_cdfs, lanes, out, checkpoint, &st);
+  if (got < 0) return got;
+  if (status_out) *status_out = st;
+  else if (st) {
+    set_error("%s: %s after %ld symbols", what, ilv_status_text(st), got);
+    return VAM_EINVAL;
+  }
+  return got;
+}
+
+int vam_rans_interleaved_resume_streams(vam_rans_stream* streams, vam_rans_checkpoint* checkpoints, int n_streams, const int32_t* cdfs,
+                                        int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, int lanes,
+                                        int n_threads, long* counts_out, int32_t* status_out) {
+  const char* what = "vam_rans_interleaved_resume_streams";
+  if (n_streams > 0 && (!streams || !checkpoints || !counts_out || !status_out)) {
+    set_error("%s: bad arguments", what);
+    return VAM_EINVAL;
+  }
+  return run_jobs(n_streams, n_threads, what, [&](int i) -> long {
+    const vam_rans_stream& s = streams[i];
+    if (s.layer) {
+      set_error("%s: an embedded stream carries no layer selection", what);
+      return VAM_EINVAL;
+    }
+    const long got = ilv_resume_one("vam_rans_interleaved_resume", s.bytes, s.n_bytes, s.indexes, s.n, cdfs, cdf_stride, cdf_sizes,
+                                    offsets, n_cdfs, lanes, s.symbols_out, checkpoints + i, status_out + i);
+    if (got < 0) return got;
+    counts_out[i] = got;
+    if (status_out[i]) {
+      set_error("vam_rans_interleaved_resume: %s after %ld symbols", ilv_status_text(status_out[i]), got);
+      return VAM_EINVAL;
+    }
+    return got;
+  });
+}
 
 long vam_rans_interleaved_encode(const int32_t* symbols, const int32_t* indexes, long n, const int32_t* cdfs, int cdf_stride,
                                  const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs, uint8_t* out, long out_cap, int lanes) {

@@ -8,6 +8,8 @@
 //           streams   encode_stream / decode_stream: one whole stream on one thread (host exports, sanitizer program)
 //           lanes     a stream as K independent lanes, each a stream of its own: the header check,
 //                     lane_encode / lane_decode for one thread per lane, lanes_*_stream for all lanes on one thread
+//           interleaved  K lanes on ONE word stream: interleaved_encode / _decode, and the decode from a
+//                     checkpoint at a group boundary, interleaved_resume
 // Addressing goes through a functor (Flat, Nhwc), the symbol search through another (TableSearch here, the wave-wide
 // search of rans_device.hip), so the steps never see a pointer they could walk off.
 #pragma once
@@ -524,6 +526,56 @@ VAM_RANS_HD bool get_step(Get& g, const F& find, int sz) {
   return g.x < kRansL;
 }
 
+// One group of the tolerant decode, all lanes on one thread: the m lanes of group g run their gets from the states in gs,
+// taking words from position pos on.  The string's word p is words[p - first_word] and it holds the words below W.  Returns
+// the lowest failed lane (m when none failed); status = that of the lowest lane from there on that failed with one, kOk when
+// the group only ran out of words.  ci and last (m entries each) receive the lanes' table indexes and the read position
+// after each lane's last word (0: it read none).
+template <class A, class T>
+VAM_RANS_HD int interleaved_group(const uint32_t* words, long first_word, long W, int K, long g, int m, const int32_t* idx, const A& at,
+                                  const T& rows, int cdf_stride, const int32_t* cdf_sizes, int n_cdfs, Get* gs, long& pos, int* ci,
+                                  long* last, int32_t& status) {
+  using Find = decltype(rows(0, 2));
+  Find find[kMaxLanes];
+  int sz[kMaxLanes];
+  bool active[kMaxLanes], failed[kMaxLanes], need[kMaxLanes];
+  int n_active = 0;
+  for (int l = 0; l < m; ++l) {
+    Get& t = gs[l];
+    t.status = kOk; t.phase = kGetSymbol; t.value = 0;
+    last[l] = 0; failed[l] = false; sz[l] = 2;
+    ci[l] = idx ? idx[at.off(g * K + l)] : at.chan(g * K + l);
+    if (ci[l] < 0 || ci[l] >= n_cdfs) t.status = kBadIndex;
+    else {
+      sz[l] = cdf_sizes[ci[l]];
+      if (sz[l] - 2 < 0 || sz[l] - 1 >= cdf_stride) t.status = kBadTable;
+    }
+    find[l] = rows(t.status ? 0 : ci[l], t.status ? 2 : sz[l]);
+    failed[l] = t.status != 0;
+    active[l] = !failed[l];
+    n_active += active[l];
+  }
+  while (n_active > 0) {                                      // one round: the updates, then the words in lane order
+    for (int l = 0; l < m; ++l) {
+      need[l] = active[l] && get_step(gs[l], find[l], sz[l]);
+      if (active[l] && gs[l].status) { failed[l] = true; need[l] = false; }
+    }
+    for (int l = 0; l < m; ++l) {
+      if (!active[l]) continue;
+      if (need[l]) {
+        if (pos < W) { gs[l].x = (gs[l].x << 32) | words[pos - first_word]; last[l] = ++pos; }
+        else failed[l] = true;
+      }
+      if (failed[l] || gs[l].phase == kGetDone) { active[l] = false; --n_active; }
+    }
+  }
+  int first = 0;
+  while (first < m && !failed[first]) ++first;
+  status = kOk;
+  for (int l = first; l < m && !status; ++l) status = gs[l].status;
+  return first;
+}
+
 // Tolerant prefix decode, all lanes on one thread: `words` are the first floor(n_bytes / 4) words of a string.  With fewer
 // than 2 K words nothing decodes.  A lane that needs a word past the prefix fails, and so does every later request; the
 // other lanes of that group finish the gets that need no word, and decoding ends with that group:
@@ -544,60 +596,82 @@ VAM_RANS_HD int32_t interleaved_decode(const uint32_t* words, long n_bytes, int 
   const long W = n_bytes / 4;
   if (W > 0 && (!words || ((uintptr_t)words & 3))) return kBadStream;
   if (W < 2l * K) return kOk;
-  using Find = decltype(rows(0, 2));
   Get gs[kMaxLanes];
   for (int l = 0; l < K; ++l) gs[l].x = (uint64_t)words[2 * l] | ((uint64_t)words[2 * l + 1] << 32);
   long pos = 2l * K, reach = 2l * K;                        // next word; read position after the last word of the elements so far
   for (long g = 0; g * K < n; ++g) {
     const int m = (int)(n - g * K < K ? n - g * K : K);
-    Find find[kMaxLanes];
-    int sz[kMaxLanes], ci[kMaxLanes];
+    int ci[kMaxLanes];
     long last[kMaxLanes];
-    bool active[kMaxLanes], failed[kMaxLanes], need[kMaxLanes];
-    int n_active = 0;
-    for (int l = 0; l < m; ++l) {
-      Get& t = gs[l];
-      t.status = kOk; t.phase = kGetSymbol; t.value = 0;
-      last[l] = 0; failed[l] = false; sz[l] = 2;
-      ci[l] = idx ? idx[at.off(g * K + l)] : at.chan(g * K + l);
-      if (ci[l] < 0 || ci[l] >= n_cdfs) t.status = kBadIndex;
-      else {
-        sz[l] = cdf_sizes[ci[l]];
-        if (sz[l] - 2 < 0 || sz[l] - 1 >= cdf_stride) t.status = kBadTable;
-      }
-      find[l] = rows(t.status ? 0 : ci[l], t.status ? 2 : sz[l]);
-      failed[l] = t.status != 0;
-      active[l] = !failed[l];
-      n_active += active[l];
-    }
-    while (n_active > 0) {                                    // one round: the updates, then the words in lane order
-      for (int l = 0; l < m; ++l) {
-        need[l] = active[l] && get_step(gs[l], find[l], sz[l]);
-        if (active[l] && gs[l].status) { failed[l] = true; need[l] = false; }
-      }
-      for (int l = 0; l < m; ++l) {
-        if (!active[l]) continue;
-        if (need[l]) {
-          if (pos < W) { gs[l].x = (gs[l].x << 32) | words[pos]; last[l] = ++pos; }
-          else failed[l] = true;
-        }
-        if (failed[l] || gs[l].phase == kGetDone) { active[l] = false; --n_active; }
-      }
-    }
-    int first = 0;
-    while (first < m && !failed[first]) ++first;
+    int32_t status;
+    const int first = interleaved_group(words, 0, W, K, g, m, idx, at, rows, cdf_stride, cdf_sizes, n_cdfs, gs, pos, ci, last, status);
     for (int l = 0; l < first; ++l) {
       if (out) out[at.off(g * K + l)] = (int32_t)((uint32_t)gs[l].value + (uint32_t)offsets[ci[l]]);
       if (last[l] > reach) reach = last[l];
       while (mk < n_marks && marks[mk] <= g * K + l + 1) mark_bytes[mk++] = 4 * reach;
     }
     *available = g * K + first;
+    if (first < m) return status;
+  }
+  return kOk;
+}
+
+// ---------------------------------------------------------------- resumable decode
+// The checkpoint of a stream is the decoder at the start of a group: `done` elements lie before that group (a multiple of
+// K, or n once the stream is finished), `pos` is the index in the whole string of the next word to read, and states holds
+// the K lane states there.  done = 0, pos = 0 is the fresh checkpoint: its states are read from the string's first 2 K words.
+VAM_RANS_HD bool checkpoint_valid(long done, long pos, long n, int K) {
+  return done >= 0 && done <= n && (done == n || done % K == 0) && pos >= 0 && (done == 0 || pos >= 2l * K);
+}
+
+// interleaved_decode from a checkpoint: `words` are the string's whole words FROM WORD pos ON, n_bytes their bytes, so the
+// string is known up to the absolute word count W = pos + floor(n_bytes / 4).  Decoding proceeds as interleaved_decode's
+// does from group done / K and writes out[i] (out may be NULL) for done_in <= i < *available only.  When a lane of group g
+// fails, for want of a word or with a status, the checkpoint becomes the start of that group: done = g K, pos and states
+// as they were when it began; a complete stream gets done = n and reads and writes nothing on later calls.  With a fresh
+// checkpoint and W < 2 K nothing decodes and the checkpoint stays fresh.  For successive prefixes of one string,
+// *available, the elements below it and the status returned equal interleaved_decode's on the whole prefix: a group that
+// completed read only words the shorter prefix held.  The status is recomputed on every call.  An impossible checkpoint
+// is kBadStream, with nothing read or written.
+template <class A, class T>
+VAM_RANS_HD int32_t interleaved_resume(const uint32_t* words, long n_bytes, int K, const int32_t* idx, long n, const A& at,
+                                       const T& rows, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int n_cdfs,
+                                       int32_t* out, long* available, long* done, long* pos, uint64_t* states) {
+  *available = 0;
+  if (!lanes_valid(K) || n < 0 || n_bytes < 0 || !checkpoint_valid(*done, *pos, n, K)) return kBadStream;
+  if (*done == n) { *available = n; return kOk; }
+  const long first_word = *pos, W = first_word + n_bytes / 4;
+  if (W > first_word && (!words || ((uintptr_t)words & 3))) return kBadStream;
+  Get gs[kMaxLanes];
+  long p = first_word;
+  if (*done == 0 && *pos == 0) {
+    if (W < 2l * K) return kOk;
+    for (int l = 0; l < K; ++l) gs[l].x = (uint64_t)words[2 * l] | ((uint64_t)words[2 * l + 1] << 32);
+    p = 2l * K;
+  } else {
+    for (int l = 0; l < K; ++l) gs[l].x = states[l];
+  }
+  for (long g = *done / K; g * K < n; ++g) {
+    const int m = (int)(n - g * K < K ? n - g * K : K);
+    int ci[kMaxLanes];
+    long last[kMaxLanes];
+    uint64_t begin[kMaxLanes];
+    const long p_begin = p;
+    for (int l = 0; l < K; ++l) begin[l] = gs[l].x;
+    int32_t status;
+    const int first = interleaved_group(words, first_word, W, K, g, m, idx, at, rows, cdf_stride, cdf_sizes, n_cdfs, gs, p, ci, last,
+                                        status);
+    for (int l = 0; l < first; ++l)
+      if (out) out[at.off(g * K + l)] = (int32_t)((uint32_t)gs[l].value + (uint32_t)offsets[ci[l]]);
+    *available = g * K + first;
     if (first < m) {
-      for (int l = first; l < m; ++l)
-        if (gs[l].status) return gs[l].status;
-      return kOk;
+      for (int l = 0; l < K; ++l) states[l] = begin[l];
+      *done = g * K; *pos = p_begin;
+      return status;
     }
   }
+  for (int l = 0; l < K; ++l) states[l] = gs[l].x;
+  *done = n; *pos = p;
   return kOk;
 }
 

@@ -533,6 +533,149 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
   }
 }
 
+// ---------------------------------------------------------------- resumable decode
+// The kernel above from a checkpoint (rans_core.h's interleaved_resume), same geometry.  The streams of a launch stand at
+// different groups, so every stream counts its own group g and the loop runs while any stream of the wave still decodes:
+// that test is a ballot, wave-uniform, and so are the rounds inside, where the lanes of a stream that has ended take no
+// part.  A wave therefore leaves after the groups its bytes reach, not after n / K.  Every lane carries the state and the
+// word position it had when the current group began; they are what a failing group leaves as the checkpoint.
+struct IlvResArgs {
+  const uint8_t* bytes;
+  long bytes_total;
+  const int64_t* byte_offsets;
+  const int32_t* byte_lengths;
+  const int32_t* idx;
+  int n_streams;
+  long n;
+  int K;
+  vam_rans_tables t;
+  int32_t* out;
+  uint64_t* states;          // [n_streams][K]
+  int32_t* done;             // [n_streams]
+  int32_t* pos;              // [n_streams]: the uploaded bytes of stream s begin at the string's word pos[s]
+  int32_t* available;
+  int32_t* status;
+};
+
+template <bool kPacked>
+__global__ __launch_bounds__(kLaneBlock) void rans_interleaved_resume_kernel(IlvResArgs a) {
+  typedef unsigned long long u64;
+  using Find = R::TableSearch<typename std::conditional<kPacked, uint16_t, int32_t>::type>;
+  extern __shared__ uint4 lds_raw[];
+  if (kPacked) {
+    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
+    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
+    __syncthreads();
+  }
+  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, K = a.K;
+  const int str = gid / K, lane = gid - str * K, shift = (int)(threadIdx.x & (kWave - 1)) - lane;
+  const bool valid = str < a.n_streams;
+  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
+  const u64 below = (1ull << lane) - 1;
+  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  const uint32_t* words = nullptr;                            // the string's word p is words[p - first_word]
+  long W = 0, pos = 0, first_word = 0, g = 0;
+  int32_t sst = 0;
+  bool alive = false;
+  long avail = 0;
+  R::Get gt{0, 0, 0, 0, 0, R::kGetDone, 0};
+  if (valid) {
+    const int64_t boff = a.byte_offsets[str];
+    const long len = a.byte_lengths[str], done = a.done[str];
+    pos = a.pos[str];
+    if (boff < 0 || (boff & 3) || len < 0 || boff > a.bytes_total || len > a.bytes_total - boff || !R::checkpoint_valid(done, pos, n, K))
+      sst = R::kBadStream;
+    else if (done == n) avail = n;                            // finished: nothing is read or written
+    else {
+      words = reinterpret_cast<const uint32_t*>(a.bytes + boff);
+      first_word = pos;
+      W = pos + len / 4;
+      g = done / K;
+      if (done == 0 && pos == 0) {                            // fresh: the states stand in front of the string
+        if (W >= 2l * K) {
+          alive = true;
+          gt.x = (uint64_t)words[2 * lane] | ((uint64_t)words[2 * lane + 1] << 32);
+          pos = 2l * K;
+        }
+      } else {
+        alive = true;
+        gt.x = a.states[(long)str * K + lane];
+      }
+    }
+  }
+  const bool ran = alive;
+  uint64_t ck_x = gt.x;                                       // the checkpoint this lane will leave
+  long ck_pos = pos, ck_done = 0;
+  while (__ballot(alive)) {
+    const long i = g * K + lane;
+    const bool has = alive && i < n;
+    if (alive) { ck_x = gt.x; ck_pos = pos; ck_done = g * K; }
+    int32_t lst = 0;                                          // what failed this lane, when it is an error
+    int sz = 2, offv = 0;
+    Find find{nullptr, 2, kPacked};
+    bool act = false, failed = false;
+    if (has) {
+      const int ci = a.idx[base + i];
+      if (ci < 0 || ci >= a.t.n_cdfs) lst = R::kBadIndex;
+      else {
+        sz = a.t.sizes[ci];
+        if (sz - 2 < 0 || sz - 1 >= a.t.stride) lst = R::kBadTable;
+        else {
+          offv = a.t.offsets[ci];
+          if constexpr (kPacked) find = R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}(ci, sz);
+          else find = R::Int32Rows{a.t.cdf, a.t.stride}(ci, sz);
+        }
+      }
+      failed = lst != 0;
+      act = !failed;
+      gt.phase = R::kGetSymbol;
+      gt.status = 0;
+      gt.value = 0;
+    }
+    while (__ballot(act)) {                                   // one round: the updates, then the words in lane order
+      bool need = false;
+      if (act) {
+        need = R::get_step(gt, find, sz);
+        if (gt.status) { lst = gt.status; failed = true; need = false; }
+      }
+      const u64 sub = (__ballot(need) >> shift) & kmask;
+      if (need) {
+        const long p = pos + __popcll(sub & below);
+        if (p < W) gt.x = (gt.x << 32) | words[p - first_word];
+        else failed = true;                                   // past the bytes held: so is every later request
+      }
+      pos += __popcll(sub);
+      if (failed || gt.phase == R::kGetDone) act = false;
+    }
+    const u64 fsub = (__ballot(failed) >> shift) & kmask, esub = (__ballot(lst != 0) >> shift) & kmask;
+    const int first = fsub ? __ffsll(fsub) - 1 : K;
+    const int32_t err = __shfl(lst, esub ? shift + __ffsll(esub) - 1 : shift);
+    if (has && lane < first) a.out[base + i] = (int32_t)((uint32_t)gt.value + (uint32_t)offv);
+    if (alive) {
+      if (fsub) {                                             // the group failed: its start is the checkpoint
+        alive = false;
+        avail = g * K + first;
+        sst = esub ? err : 0;
+      } else if ((++g) * K >= n) {                            // the stream is complete
+        alive = false;
+        avail = n;
+        ck_x = gt.x; ck_pos = pos; ck_done = n;
+      }
+    }
+  }
+  if (ran) {
+    a.states[(long)str * K + lane] = ck_x;
+    if (lane == 0) {
+      a.done[str] = (int32_t)ck_done;
+      a.pos[str] = (int32_t)ck_pos;
+    }
+  }
+  if (valid && lane == 0) {
+    a.available[str] = (int32_t)avail;
+    a.status[str] = sst;
+  }
+}
+
 int check_geometry(const char* what, int B, int h, int w, int ld, int c0, int C, int n_slices, int n_sel = 1) {
   VAM_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0 && n_slices > 0 && c0 >= 0, "%s: B, h, w, C, n_slices must be > 0 and c0 >= 0", what);
   VAM_REQUIRE((long)c0 + (long)C * n_slices <= ld, "%s: window [%d, %ld) does not fit ld = %d", what, c0, (long)c0 + (long)C * n_slices, ld);
@@ -920,6 +1063,37 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
     hipLaunchKernelGGL(rans_interleaved_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
   }
   return check_launch("rans_interleaved_decode_kernel");
+}
+
+// ---------------------------------------------------------------- resumable decode
+int vam_rans_interleaved_resume_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                       const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, int32_t* sym_out, uint64_t* states, int32_t* done, int32_t* pos,
+                                       int32_t* available, int32_t* status, void* stream) {
+  const char* what = "vam_rans_interleaved_resume_device";
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && idx && sym_out && available && status && bytes_total >= 0 &&
+              ((uintptr_t)bytes & 3) == 0, "%s: need word-aligned bytes, offsets, lengths, idx, sym_out, available, status", what);
+  VAM_REQUIRE(states && done && pos && ((uintptr_t)states & 7) == 0, "%s: need the checkpoints: 64-bit aligned states, done, pos", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
+              what, n_streams, n);
+  if (int rc = check_tables(what, tables)) return rc;
+  IlvResArgs a{bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, states, done, pos, available,
+               status};
+  const int blocks = (n_streams * lanes + kLaneBlock - 1) / kLaneBlock;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_resume_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(rans_interleaved_resume_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rans_interleaved_resume_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_interleaved_resume_kernel");
 }
 
 }  // extern "C"

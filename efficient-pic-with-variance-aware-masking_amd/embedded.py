@@ -33,6 +33,11 @@ vam_variance_rank_staged); a stream cut at stage k's mark reproduces ``forward_q
 rank prefix, and the whole stream is still ``forward_single_quality(x, 10)``.  Such a container carries
 ``"format": "embedded-3"``, always ``"lanes"``, ``"schedule": {"levels", "index"}`` with its raw ``"side_bytes"``, and marks
 by ``"stage"`` instead of ``"q"``.
+
+A **resumable** decoder is a receiver whose bytes keep arriving: ``EmbeddedDecoder(..., resumable=True)``
+keeps a checkpoint per stream at a group boundary (bitstream.Checkpoints), :meth:`EmbeddedDecoder.extend` takes the bytes
+that follow — :func:`delta` cuts them on the transmitter's side — and only the new elements are entropy-decoded.  The
+format is unchanged, and after every ``extend`` the decoder equals a fresh one on the concatenated containers bit for bit.
 """
 from __future__ import annotations
 
@@ -367,6 +372,42 @@ def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = No
     return out
 
 
+def _same(a, b) -> bool:
+    """Equality of container entries: dicts and sequences entry by entry (a list equals a tuple), arrays by value."""
+    if isinstance(a, dict) and isinstance(b, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return np.array_equal(np.asarray(a), np.asarray(b))
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return a == b
+
+
+def delta(longer, shorter) -> List[bytes]:
+    """Per slice, the bytes of ``longer`` that follow ``shorter``: what a transmitter sends to a receiver that holds
+    ``shorter`` (:meth:`EmbeddedDecoder.extend`).  On the host alone, like :func:`truncate`.  ``shorter`` must be a cut of
+    ``longer`` — the same format, shape, lanes, z, base and schedule, every embedded string a prefix of ``longer``'s —;
+    ValueError names the slice that is not."""
+    Ka, Kb = _check_container(longer), _check_container(shorter)
+    for key, what in (("format", "format"), ("shape", "shape"), ("z", "z stream"), ("base", "base slices"), ("schedule", "schedule")):
+        if (key in longer) != (key in shorter) or not _same(longer.get(key), shorter.get(key)):
+            if key == "base" and len(longer["base"]) == len(shorter["base"]):
+                j = [_same(a, b) for a, b in zip(longer["base"], shorter["base"])].index(False)
+                raise ValueError(f"delta: the base stream of slice {j} differs: the shorter container is no cut of the longer one")
+            raise ValueError(f"delta: the containers differ in their {what}: the shorter one is no cut of the longer one")
+    if Ka != Kb:
+        raise ValueError(f"delta: the containers differ in their lanes ({Kb} and {Ka}): the shorter one is no cut of the longer one")
+    ea, eb = longer["embedded"], shorter["embedded"]
+    if len(ea) != len(eb):
+        raise ValueError(f"delta: the containers hold {len(eb)} and {len(ea)} slices: the shorter one is no cut of the longer one")
+    out = []
+    for j, (a, b) in enumerate(zip(ea, eb)):
+        if len(b) > len(a) or bytes(a[:len(b)]) != bytes(b):
+            raise ValueError(f"delta: slice {j}: the shorter container's {len(b)} bytes are no prefix of the longer one's {len(a)}")
+        out.append(bytes(a[len(b):]))
+    return out
+
+
 class EmbeddedDecoder:
     """Decodes a batch of embedded containers of one shape, whole or truncated, each image cut at its own place.  The base
     slices and the progressive (mu, sigma) chain run once, the rank order comes from the decoder's own sigma, and the
@@ -383,9 +424,14 @@ class EmbeddedDecoder:
     Scheduled containers (``"embedded-3"``) bring their schedule: the plan rebuilds the scheduled rank
     order from its own sigma, :meth:`decode` and :meth:`available` work unchanged, :meth:`decode_stages` decodes stages, and
     :meth:`decode_qualities` and :meth:`bits` are refused — a uniform quality is no prefix of a scheduled order.  A batch
-    mixes neither scheduled with plain containers nor different stage counts."""
+    mixes neither scheduled with plain containers nor different stage counts.
 
-    def __init__(self, model, containers, coder: Optional[str] = None):
+    ``resumable=True`` makes the decoder a receiver whose bytes keep arriving: the prefix decode goes
+    through the resume path from fresh checkpoints, which the decoder owns next to its ranked symbols (device tensors on the
+    device coder, numpy arrays on the host coder), and :meth:`extend` hands it the bytes that follow and decodes only the
+    new elements.  With the default nothing changes."""
+
+    def __init__(self, model, containers, coder: Optional[str] = None, resumable: bool = False):
         _check_model(model)
         cs = list(containers)
         if not cs:
@@ -419,6 +465,10 @@ class EmbeddedDecoder:
         self.dp = model._emb_dec_plan(self.B, hz, wz, self.coder, scheduled=self.scheduled)
         self._stage_count = None                            # (device, host) int [L, B, ns]: #(stage id <= k) per segment
         self._avail: Optional[np.ndarray] = None
+        self.resumable = bool(resumable)
+        self._ck = None                                     # resumable: bitstream.Checkpoints of the B * ns embedded streams
+        self._pos = np.zeros(self.B * ns, dtype=np.int64)   # resumable: the host's copy of every stream's word position
+        self.extend_bytes = 0                               # payload bytes the last extend handed to the coder
         self.idx_r: Optional[np.ndarray] = None             # host copy of the ranked indexes (device coder: only for bits())
         with torch.no_grad():
             self._front()
@@ -436,9 +486,13 @@ class EmbeddedDecoder:
         if self._avail is None:                             # the host's one pass over the embedded streams
             self.idx_r = dp.idx_r.cpu().numpy()             # [B, ns, n]
             self.ranked = np.zeros(self.idx_r.shape, dtype=np.int32)
-            jobs = [(c["embedded"][j], self.idx_r[b, j], self.ranked[b, j]) for b, c in enumerate(cs) for j in range(ns)]
-            got = bs.decode_prefix_streams(jobs, bs.Tables.of(self.m.gaussian_conditional), lanes=self.lanes)
-            self._avail = np.asarray(got, dtype=np.int64).reshape(self.B, ns)
+            if self.resumable:
+                self._ck = bs.Checkpoints.fresh(self.B * ns, self.lanes)
+                self._resume_host()
+            else:
+                jobs = [(c["embedded"][j], self.idx_r[b, j], self.ranked[b, j]) for b, c in enumerate(cs) for j in range(ns)]
+                got = bs.decode_prefix_streams(jobs, bs.Tables.of(self.m.gaussian_conditional), lanes=self.lanes)
+                self._avail = np.asarray(got, dtype=np.int64).reshape(self.B, ns)
         with dp.runner.on_stream():
             dp.ranked.copy_(torch.from_numpy(self.ranked))
 
@@ -449,7 +503,13 @@ class EmbeddedDecoder:
         from . import bitstream as bs
         cs, ns, dp, B = self.containers, self.m.ns0, self.dp, self.B
         with dp.runner.on_stream():
-            if self._avail is None:
+            if self._avail is None and self.resumable:
+                self._ck = bs.Checkpoints.fresh(B * ns, self.lanes, dp.device)
+                self._meta = torch.zeros((3, B * ns), dtype=torch.int32, device=dp.device)
+                self._ck.pos = self._meta[2]                # the kernel's pos comes back with the one read of meta
+                self.ranked = torch.zeros_like(dp.ranked)
+                got = self._resume_device()
+            elif self._avail is None:
                 emb = bs.upload_streams([c["embedded"][j] for c in cs for j in range(ns)], dp.device)
                 meta = torch.empty((2, B * ns), dtype=torch.int32, device=dp.device)
                 bs.decode_embedded_uploaded(emb, 0, dp.idx_r, dp.ranked, bs.DeviceCoderTables.of(self.m.gaussian_conditional, dp.device),
@@ -468,6 +528,93 @@ class EmbeddedDecoder:
                 raise L.VamError(f"EmbeddedDecoder: embedded stream (image {k // ns}, slice {k % ns}): "
                                  f"{bs.status_text(int(got[1][k]))}")
             self._avail = got[0].astype(np.int64).reshape(B, ns)
+
+    def _tails(self) -> List[bytes]:
+        """Per embedded stream (image-major) the bytes its container holds from byte 4 * pos on."""
+        ns = self.m.ns0
+        return [c["embedded"][j][4 * int(self._pos[b * ns + j]):] for b, c in enumerate(self.containers) for j in range(ns)]
+
+    def _raise_status(self, status: np.ndarray):
+        from . import _lib as L
+        from . import bitstream as bs
+        bad = np.flatnonzero(status)
+        if bad.size:
+            k, ns = int(bad[0]), self.m.ns0
+            raise L.VamError(f"EmbeddedDecoder: embedded stream (image {k // ns}, slice {k % ns}): "
+                             f"{bs.status_text(int(status[k]))}")
+
+    def _resume_host(self):
+        """The resume call on the thread pool, every stream from its bytes at 4 * pos, into the host's ranked symbols."""
+        from . import _lib as L
+        from . import bitstream as bs
+        ns, tails = self.m.ns0, self._tails()
+        jobs = [(tails[k], self.idx_r[k // ns, k % ns], self.ranked[k // ns, k % ns]) for k in range(self.B * ns)]
+        status = np.zeros(self.B * ns, dtype=np.int32)
+        self.extend_bytes = sum(len(t) for t in tails)
+        try:
+            got = bs.resume_prefix_streams(jobs, bs.Tables.of(self.m.gaussian_conditional), self._ck, lanes=self.lanes, status=status)
+        except L.VamError:
+            self._pos[:] = self._ck.pos
+            self._raise_status(status)
+            raise
+        self._pos[:] = self._ck.pos
+        self._avail = np.asarray(got, dtype=np.int64).reshape(self.B, ns)
+
+    def _resume_device(self) -> np.ndarray:
+        """ONE upload of every stream's bytes from 4 * pos on, ONE launch into the decoder's own ranked symbols, ONE read of
+        meta (available, status, pos); then the plan's ranked symbols are refreshed on the device.  Returns meta."""
+        from . import bitstream as bs
+        dp, tails = self.dp, self._tails()
+        self.extend_bytes = sum(len(t) for t in tails)
+        up = bs.upload_streams(tails, dp.device)
+        bs.resume_embedded_uploaded(up, 0, dp.idx_r, self.ranked, bs.DeviceCoderTables.of(self.m.gaussian_conditional, dp.device),
+                                    self.lanes, self._ck, self._meta)
+        dp.ranked.copy_(self.ranked)
+        got = self._meta.cpu().numpy()
+        self._pos[:] = got[2]
+        return got
+
+    def extend(self, more) -> np.ndarray:
+        """Hand a resumable decoder the bytes that follow what it holds: ``more`` has one entry per container, each a
+        sequence of ns ``bytes`` objects (``b""`` allowed), e.g. :func:`delta`'s.  Only the elements the new bytes reach are
+        entropy-decoded, from each stream's checkpoint.  Returns the new :meth:`available`.  Afterwards the decoder is
+        indistinguishable from a fresh one on the concatenated containers, which ``self.containers`` then holds.
+        Host coder: the resume call on the thread pool, then the device copy of the ranked symbols is refreshed.  Device
+        coder: one host-to-device copy of every stream's bytes from its last whole decoded group on, one launch, one read of
+        (available, status, pos); no symbols or indexes cross to the host.  ``self.extend_bytes``: the payload bytes handed to
+        the coder."""
+        ns = self.m.ns0
+        if not self.resumable:
+            raise ValueError("EmbeddedDecoder.extend: this decoder keeps no checkpoints; build it with resumable=True")
+        try:
+            more = [list(row) for row in more]
+        except TypeError as e:
+            raise ValueError(f"EmbeddedDecoder.extend: expected {self.B} sequences of {ns} bytes objects") from e
+        if len(more) != self.B or any(len(row) != ns for row in more):
+            raise ValueError(f"EmbeddedDecoder.extend: expected {self.B} entries of {ns} slices each, got "
+                             f"{[len(row) for row in more]}")
+        for b, row in enumerate(more):
+            for j, s in enumerate(row):
+                if not isinstance(s, (bytes, bytearray, memoryview)):
+                    raise ValueError(f"EmbeddedDecoder.extend: image {b}, slice {j}: expected bytes, got {type(s).__name__}")
+        cs = []
+        for c, row in zip(self.containers, more):
+            c = dict(c)
+            c["embedded"] = [bytes(old) + bytes(s) for old, s in zip(c["embedded"], row)]
+            cs.append(c)
+        with torch.no_grad():
+            self._own()
+            self.containers = cs
+            if self.coder == "device":
+                with self.dp.runner.on_stream():
+                    got = self._resume_device()
+                self._raise_status(got[1])
+                self._avail = got[0].astype(np.int64).reshape(self.B, ns)
+            else:
+                self._resume_host()
+                with self.dp.runner.on_stream():
+                    self.dp.ranked.copy_(torch.from_numpy(self.ranked))
+        return self.available()
 
     def _idx_r(self) -> np.ndarray:
         if self.idx_r is None:

@@ -929,6 +929,49 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
                                        const vam_rans_tables* tables, int32_t* sym_out, int32_t* available, int32_t* status,
                                        void* stream);
 
+/* ------------------------------------------------------------------ resumable embedded decode */
+/* The format above, unchanged, decoded in steps as the bytes arrive.  The CHECKPOINT of a stream is the decoder at the
+ * start of a group: `done` elements lie before that group (a multiple of K, or n once the stream is finished), `pos` is the
+ * index, in the whole string, of the next word to read, and states holds the K lane states (uint64) there.  The fresh
+ * checkpoint is done = 0, pos = 0: its states are read from the string's first 2 K words (with fewer nothing decodes and it
+ * stays fresh).
+ * A resume call is handed the bytes of the string FROM BYTE 4 * pos ON and nothing before; the whole words among them extend
+ * to an absolute word count W.  It decodes exactly as the tolerant decode does from group done / K, writes
+ * symbols_out[i] for done_in <= i < count and no other element, and returns the count and the status.  If a lane of group g
+ * failed, for want of a word or with a status, the checkpoint becomes the start of that group (done = g K, pos and states as
+ * they were when it began); a complete stream gets done = n and later calls read and write nothing.  For successive
+ * prefixes L1 <= L2 <= .. of one string, count, symbols and status after the call for Lk equal
+ * vam_rans_interleaved_decode_prefix on the first Lk bytes; the status is recomputed on every call.  The Lk mod 4 trailing
+ * bytes belong to no word yet: the caller keeps them and sends them again.
+ * HOST pointers.  vam_rans_interleaved_resume: one stream; status_out as in vam_rans_interleaved_decode_prefix.
+ * vam_rans_interleaved_resume_streams: streams[i] as vam_rans_interleaved_decode_prefix_streams reads it, bytes / n_bytes
+ * being the string from byte 4 * checkpoints[i].pos on; counts_out and status_out receive one entry per stream, and a
+ * status of 2 or 3 is VAM_EINVAL.  Refused by message, with nothing written: invalid lanes, n < 0, a negative length,
+ * misaligned states, or an impossible checkpoint (done neither a multiple of K nor n, done > n, pos < 2 K while done > 0). */
+typedef struct vam_rans_checkpoint {
+  long done;                  /* elements before the checkpointed group */
+  long pos;                   /* next word of the whole string */
+  uint64_t* states;           /* K lane states */
+} vam_rans_checkpoint;
+long vam_rans_interleaved_resume(const uint8_t* in_host, long n_bytes, const int32_t* indexes_host, long n,
+                                 const int32_t* cdfs_host, int cdf_stride, const int32_t* cdf_sizes_host,
+                                 const int32_t* offsets_host, int n_cdfs, int lanes, int32_t* symbols_out_host,
+                                 vam_rans_checkpoint* checkpoint, int32_t* status_out);
+int vam_rans_interleaved_resume_streams(vam_rans_stream* streams, vam_rans_checkpoint* checkpoints, int n_streams,
+                                        const int32_t* cdfs_host, int cdf_stride, const int32_t* cdf_sizes_host,
+                                        const int32_t* offsets_host, int n_cdfs, int lanes, int n_threads, long* counts_out,
+                                        int32_t* status_out);
+/* DEVICE pointers.  vam_rans_interleaved_resume_device: the geometry of vam_rans_interleaved_decode_device, one thread per
+ * (stream, lane).  The checkpoints are states [n_streams][lanes] (uint64), done [n_streams] and pos [n_streams] (int32), all
+ * in and out; the uploaded bytes of stream s (byte_lengths[s] at bytes + byte_offsets[s]) begin at the string's word pos[s].
+ * sym_out[s * n + i] is written for done_in <= i < available[s] only; status[s] = 0, 2, 3, or 6 for a refused offset, length
+ * or checkpoint, and a refused stream is neither read nor written.  A wave leaves as soon as none of its streams is still
+ * decoding.  No read leaves a stream's uploaded bytes, no write its n elements or its K states. */
+int vam_rans_interleaved_resume_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                       const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
+                                       const vam_rans_tables* tables, int32_t* sym_out, uint64_t* states, int32_t* done,
+                                       int32_t* pos, int32_t* available, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ graphs / timing */
 int vam_graph_begin(void* stream);
 int vam_graph_end(void* stream, void** graph_exec_out);

@@ -19,7 +19,14 @@ decode of all 6 stages alternate with the plain embedded encode and the decode o
 before timing, x_hat of every stage is asserted identical to ``forward_quality_map`` of that stage's map.  The plain cells
 are the same calls the default mode times.
 
-    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64] [--schedule roi]
+``--resume S`` measures a receiver whose bytes keep arriving: every container is received in S equal
+byte steps.  Per (coder, lanes) cell, (a) a fresh EmbeddedDecoder on the prefix of every step, the only way without
+checkpoints, alternates with (b) ONE resumable decoder and ``extend`` per step, same run, same containers; each step ends
+with ``decode()``.  Per step and in total: the wall time and the entropy-decode share of the embedded streams (host: the
+bitstream call, wall time; device: HIP events around the launch).  x_hat of every step is asserted identical
+between (a) and (b); no time is asserted.
+
+    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64] [--schedule roi | --resume S]
 """
 import argparse
 import json
@@ -88,6 +95,90 @@ def schedule_main(a, net, dev):
     print(json.dumps(res))
 
 
+def resume_main(a, net, dev):
+    """--resume S: a fresh decoder per step against one resumable decoder and extend, interleaved; prints one JSON line."""
+    import vampic
+    from vampic import bitstream as bs, embedded as EB
+    S = a.resume
+    share = {"host": 0.0, "events": []}
+
+    def timed(fn):
+        def run(*args, **kw):
+            t0 = time.perf_counter()
+            try:
+                return fn(*args, **kw)
+            finally:
+                share["host"] += time.perf_counter() - t0
+        return run
+
+    def evented(fn):
+        def run(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            try:
+                return fn(*args, **kw)
+            finally:
+                e1.record()
+                share["events"].append((e0, e1))
+        return run
+    for name in ("decode_prefix_streams", "resume_prefix_streams"):
+        setattr(bs, name, timed(getattr(bs, name)))
+    for name in ("decode_embedded_uploaded", "resume_embedded_uploaded"):
+        setattr(bs, name, evented(getattr(bs, name)))
+
+    def drain():
+        ms = 1e3 * share["host"] + sum(e0.elapsed_time(e1) for e0, e1 in share["events"])
+        share["host"] = 0.0
+        share["events"].clear()
+        return ms
+
+    res = {"metric": "receiving a container in steps: fresh decoder per step (a) vs extend (b) (ms, median)",
+           "device": torch.cuda.get_device_name(0), "coder_threads": bs.coder_threads(), "warmup": a.warmup, "reps": a.reps,
+           "steps": S, "cases": {}}
+    for case, B, H, W in (("1x512x768", 1, 512, 768), ("8x256x256", 8, 256, 256)):
+        x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
+        out = {}
+        with torch.no_grad():
+            for c in a.coder:
+                for K in a.lanes:
+                    cs = EB.encode_batch(net, x, coder=c, lanes=K)
+                    prefixes = [[EB.truncate(c_, slice_bytes=[len(s_) * i // S for s_ in c_["embedded"]]) for c_ in cs]
+                                for i in range(1, S + 1)]
+                    more = [None] + [[EB.delta(now, held) for now, held in zip(prefixes[i], prefixes[i - 1])] for i in range(1, S)]
+                    t = {k: [[] for _ in range(S)] for k in ("fresh_ms", "fresh_coder_ms", "extend_ms", "extend_coder_ms")}
+                    for r in range(a.warmup + a.reps):
+                        hats = {}
+                        for path in ("fresh", "extend"):
+                            dec = None
+                            for i in range(S):
+                                torch.cuda.synchronize()
+                                drain()
+                                t0 = time.perf_counter()
+                                if path == "fresh":
+                                    dec = EB.EmbeddedDecoder(net, prefixes[i], coder=c)
+                                elif i == 0:
+                                    dec = EB.EmbeddedDecoder(net, prefixes[0], coder=c, resumable=True)
+                                else:
+                                    dec.extend(more[i])
+                                x_hat = dec.decode()["x_hat"]
+                                torch.cuda.synchronize()
+                                ms = 1e3 * (time.perf_counter() - t0)
+                                if r >= a.warmup:
+                                    t[f"{path}_ms"][i].append(ms)
+                                    t[f"{path}_coder_ms"][i].append(drain())
+                                hats[path, i] = x_hat
+                        for i in range(S):
+                            assert torch.equal(hats["fresh", i], hats["extend", i]), f"{case}: {c} K={K}: x_hat of step {i} differs"
+                    med = {k: [round(statistics.median(v), 2) for v in rows] for k, rows in t.items()}
+                    med.update({f"{k}_total": round(sum(v), 2) for k, v in list(med.items())})
+                    med.update(x_hat_identical=True, bytes_per_image=round(sum(len(s_) for c_ in cs for s_ in c_["embedded"]) / B, 1))
+                    out[f"{c}_k{K}"] = med
+        res["cases"][case] = out
+        net._drop_plans()
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=1)
@@ -95,6 +186,7 @@ def main():
     ap.add_argument("--coder", nargs="+", default=["host"], choices=["host", "device"])
     ap.add_argument("--lanes", nargs="+", type=int, default=[1])
     ap.add_argument("--schedule", choices=["roi"], default=None)
+    ap.add_argument("--resume", type=int, default=None, metavar="S")
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -102,8 +194,14 @@ def main():
     dev = torch.device("cuda:0")
     net, _ = build_model(dev)
     net.update()
+    if a.schedule and a.resume:
+        ap.error("--schedule and --resume measure different things: give one")
     if a.schedule:
         return schedule_main(a, net, dev)
+    if a.resume is not None:
+        if a.resume < 2:
+            ap.error("--resume takes S >= 2 steps")
+        return resume_main(a, net, dev)
     coder = [0.0]
 
     def timed(fn):
