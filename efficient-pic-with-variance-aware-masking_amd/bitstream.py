@@ -259,6 +259,34 @@ def decode_prefix_streams(jobs: Sequence[Tuple], t: Tables, threads: Optional[in
     return [int(c) for c in counts[:len(jobs)]]
 
 
+def decode_interleaved_counted(stream: bytes, indexes, t: Tables, lanes: int) -> Tuple[np.ndarray, int, int]:
+    """The tolerant decode of one :func:`encode_interleaved` string with its verdict (vam_rans_interleaved_decode_prefix):
+    (symbols, count, status) — ``symbols[:count]`` are decoded, the rest is 0, and ``status`` is 0 or the code (2 index out
+    of range, 3 cdf size invalid) that ended the stream.  Running out of bytes is no status: the count says it."""
+    K = check_lanes(lanes)
+    src = np.frombuffer(stream, dtype=np.uint8)
+    i = _i32(indexes)
+    out = np.zeros(i.size, dtype=np.int32)
+    st = C.c_int32(0)
+    n = L.load().vam_rans_interleaved_decode_prefix(src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size,
+                                                    t.cdf.ctypes.data, t.cdf.shape[1], t.sizes.ctypes.data, t.offsets.ctypes.data,
+                                                    t.cdf.shape[0], K, out.ctypes.data, C.byref(st))
+    if n < 0:
+        L.check(int(n), "vam_rans_interleaved_decode_prefix")
+    return out, int(n), int(st.value)
+
+
+def decode_interleaved_strict(stream: bytes, indexes, t: Tables, lanes: int, what: str = "stream") -> np.ndarray:
+    """The symbols of an :func:`encode_interleaved` string that is needed WHOLE (z and the base slices of an ``"embedded-4"``
+    container): :func:`decode_interleaved_counted` with count == n required.  ValueError names ``what``
+    and gives :func:`status_text`: the status that ended the stream, or 1 (truncated) for a string that ends early."""
+    out, count, st = decode_interleaved_counted(stream, indexes, t, lanes)
+    if st or count != out.size:
+        raise ValueError(f"{what}: {status_text(st if st else 1)} ({count} of {out.size} elements decode from {len(stream)} bytes "
+                         f"on {lanes} lanes)")
+    return out
+
+
 @dataclass
 class Checkpoints:
     """The checkpoints of ``n`` resumable streams on K lanes: per stream the decoder at the start of a
@@ -905,6 +933,55 @@ def resume_embedded_uploaded(up: DeviceStreams, first: int, r_idx: torch.Tensor,
             "vam_rans_interleaved_resume_device")
     if ck.pos.data_ptr() != meta[2].data_ptr():               # a decoder keeps pos in meta itself
         meta[2].copy_(ck.pos)
+
+
+# ---------------------------------------------------------------- an interleaved base
+def encode_window_interleaved_device(sym_view, idx_view, n_slices: int, C_: int, tables: DeviceCoderTables, lanes: int) -> List[List[bytes]]:
+    """:func:`encode_streams_device` with every string an :func:`encode_interleaved` string of ``lanes`` = K: all
+    B * n_slices streams of an int32 NHWC window in ONE vam_rans_interleaved_encode_nhwc_device launch on the current stream,
+    one thread per (stream, lane), packed by vam_rans_pack_device; then the two device-to-host copies.  ``idx_view`` None:
+    table index = channel (the z streams).  Returns ``[slice][image]``; at K = 1 the bytes are encode_streams_device's."""
+    from . import ops
+    K = check_lanes(lanes)
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, None)
+    ns, cap = B * n_slices, 2 * C_ * h * w + 2 * K + 16
+    dev = sym_view.buf.device
+    regions = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    packed = torch.empty(ns * cap, dtype=torch.int32, device=dev)
+    meta = torch.empty((2, ns), dtype=torch.int32, device=dev)          # lengths in words, status
+    offs = torch.empty(ns + 1, dtype=torch.int64, device=dev)
+    lib, st = L.load(), ops.stream_ptr()
+    L.check(lib.vam_rans_interleaved_encode_nhwc_device(sym_view.buf.data_ptr(), idx_view.buf.data_ptr() if idx_view is not None else None,
+                                                        B, h, w, ld, sym_view.c0, C_, n_slices, K, C.byref(tables.struct),
+                                                        regions.data_ptr(), cap, meta[0].data_ptr(), meta[1].data_ptr(), st),
+            "vam_rans_interleaved_encode_nhwc_device")
+    L.check(lib.vam_rans_pack_device(regions.data_ptr(), cap, meta[0].data_ptr(), ns, packed.data_ptr(), ns * cap,
+                                     offs.data_ptr(), st), "vam_rans_pack_device")
+    m = meta.cpu().numpy()
+    raise_status(m[1], B, "vam_rans_interleaved_encode_nhwc_device")
+    off = np.concatenate([[0], np.cumsum(m[0].astype(np.int64))]) * 4
+    data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
+    return [[data[off[s * B + b]:off[s * B + b + 1]].tobytes() for b in range(B)] for s in range(n_slices)]
+
+
+def decode_window_interleaved_uploaded(up: DeviceStreams, first: int, idx_view, sym_view, n_slices: int, C_: int,
+                                       tables: DeviceCoderTables, lanes: int):
+    """:func:`decode_uploaded` for :func:`encode_interleaved` strings of ``lanes`` = K: one
+    vam_rans_interleaved_decode_nhwc_device launch on the current stream, no synchronisation.  The decode is STRICT: a string
+    that ends before its stream does gets status 1.  ``up`` is an upload for one lane: one status code per string."""
+    from . import ops
+    K = check_lanes(lanes)
+    B, h, w, ld = _geometry(sym_view, idx_view, n_slices, C_, None)
+    if first < 0 or first + B * n_slices > up.n:
+        raise ValueError(f"device coder: strings {first} .. {first + B * n_slices} of {up.n} uploaded")
+    if up.lanes != 1:
+        raise ValueError(f"device coder: interleaved strings have one status code each, these were uploaded for {up.lanes} lanes")
+    total = up.buf.numel() - (up.bytes_ptr - up.buf.data_ptr())
+    L.check(L.load().vam_rans_interleaved_decode_nhwc_device(up.bytes_ptr, total, up.offsets_ptr + 8 * first, up.lengths_ptr + 4 * first,
+                                                             idx_view.buf.data_ptr() if idx_view is not None else None, B, h, w, ld,
+                                                             sym_view.c0, C_, n_slices, K, C.byref(tables.struct),
+                                                             sym_view.buf.data_ptr(), up.status.data_ptr() + 4 * first,
+                                                             ops.stream_ptr()), "vam_rans_interleaved_decode_nhwc_device")
 
 
 def sigma0_index(scale_table) -> int:

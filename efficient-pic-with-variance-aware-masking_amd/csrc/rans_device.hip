@@ -343,7 +343,32 @@ __global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecAr
 // carries the stream's position itself, so nothing but the ballot crosses a lane.  All streams of a launch have the same
 // n, so the group loop is wave-uniform; the rounds of a group run until no lane of the wave has a put / get left.
 // No thread leaves early: a lane past the last stream stays, inactive, so that the wave stays converged at the ballots.
-struct IlvEncArgs {
+//
+// Where a stream's elements lie is a base of the argument structs: FlatRows, the ranked buffers of the
+// embedded streams, or NhwcWindow, the (image, slice) windows of the first half of this file, for z and the base slices
+// of an "embedded-4" container.  The group body is the same; what a window adds is compiled only for it (kWindow).
+struct FlatRows {                                            // stream s = elements [s * n, (s + 1) * n) in place, idx given
+  static constexpr bool kWindow = false;
+  __device__ long origin(int) const { return 0; }
+  __device__ long off(long i) const { return i; }
+  __device__ int chan(long) const { return 0; }
+};
+struct NhwcWindow {                                          // stream s * B + image = channels [c0 + s C, c0 + (s + 1) C) of an image
+  static constexpr bool kWindow = true;
+  int B, hw, ld, c0, C;
+  __device__ long origin(int str) const {
+    const int s = str / B, b = str - s * B;
+    return (long)b * hw * ld + c0 + (long)s * C;
+  }
+  __device__ long off(long i) const {                        // n <= 2^28: 32-bit division
+    const uint32_t c = (uint32_t)i / (uint32_t)hw;
+    return (long)((uint32_t)i - c * (uint32_t)hw) * ld + c;
+  }
+  __device__ int chan(long i) const { return (int)((uint32_t)i / (uint32_t)hw); }
+};
+
+template <class A>
+struct IlvEncArgs : A {
   const int32_t* sym;
   const int32_t* idx;
   int n_streams;
@@ -359,14 +384,15 @@ struct IlvEncArgs {
   int32_t* mark_bytes;       // [n_marks][n_streams]
 };
 
-__global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncArgs a) {
+template <class A>
+__global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncArgs<A> a) {
   typedef unsigned long long u64;
   const int tid = threadIdx.x, gid = blockIdx.x * kWave + tid, K = a.K;
   const int str = gid / K, lane = gid - str * K, shift = tid - lane;
   const bool valid = str < a.n_streams;
   const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
   const u64 above = kmask & ~((2ull << lane) - 1);           // the stream's lanes above this one
-  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  const long n = a.n, base = A::kWindow ? a.origin(valid ? str : 0) : (long)(valid ? str : 0) * n;
   uint32_t* region = a.out + (long)(valid ? str : 0) * a.cap;
   uint32_t* top = region + a.cap;                            // the stream's next word goes below top
   R::Enc e;
@@ -381,7 +407,12 @@ __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncAr
     R::Put u{0, 0, 0, -1};
     int gets = 0;
     if (alive && i < n) {
-      st = R::classify(a.sym[base + i], a.idx[base + i], a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+      if constexpr (A::kWindow) {
+        const long o = base + a.off(i);
+        st = R::classify(a.sym[o], a.idx ? a.idx[o] : a.chan(i), a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+      } else {
+        st = R::classify(a.sym[base + i], a.idx[base + i], a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+      }
       gets = st ? 0 : R::put_gets(u);
     }
     if ((__ballot(st != 0) >> shift) & kmask) alive = false;
@@ -433,7 +464,8 @@ __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncAr
   }
 }
 
-struct IlvDecArgs {
+template <class A>
+struct IlvDecArgs : A {
   const uint8_t* bytes;
   long bytes_total;
   const int64_t* byte_offsets;
@@ -448,8 +480,11 @@ struct IlvDecArgs {
   int32_t* status;
 };
 
-template <bool kPacked>
-__global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(IlvDecArgs a) {
+// A window is decoded STRICTLY: the base of a container is needed whole.  A stream whose words end early gets kTruncated,
+// its elements from the failing group on are written as 0, and a refused stream (kBadStream) is neither read nor written;
+// there are no available counts.
+template <bool kPacked, class A>
+__global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(IlvDecArgs<A> a) {
   typedef unsigned long long u64;
   using Find = R::TableSearch<typename std::conditional<kPacked, uint16_t, int32_t>::type>;
   extern __shared__ uint4 lds_raw[];
@@ -463,7 +498,7 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
   const bool valid = str < a.n_streams;
   const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
   const u64 below = (1ull << lane) - 1;
-  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  const long n = a.n, base = A::kWindow ? a.origin(valid ? str : 0) : (long)(valid ? str : 0) * n;
   const uint32_t* words = nullptr;
   long W = 0;
   int32_t sst = 0;
@@ -474,6 +509,11 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
     else { words = reinterpret_cast<const uint32_t*>(a.bytes + boff); W = len / 4; }
   }
   bool alive = valid && !sst && W >= 2l * K;
+  bool refused = false;
+  if constexpr (A::kWindow) {
+    refused = sst != 0;
+    if (valid && !sst && !alive) sst = R::kTruncated;         // not even the states
+  }
   long avail = alive ? n : 0, pos = 2l * K;
   R::Get gt{0, 0, 0, 0, 0, R::kGetDone, 0};
   if (alive) gt.x = (uint64_t)words[2 * lane] | ((uint64_t)words[2 * lane + 1] << 32);
@@ -485,7 +525,9 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
     Find find{nullptr, 2, kPacked};
     bool act = false, failed = false;
     if (alive && has) {
-      const int ci = a.idx[base + i];
+      int ci;
+      if constexpr (A::kWindow) ci = a.idx ? a.idx[base + a.off(i)] : a.chan(i);
+      else ci = a.idx[base + i];
       if (ci < 0 || ci >= a.t.n_cdfs) lst = R::kBadIndex;
       else {
         sz = a.t.sizes[ci];
@@ -520,15 +562,20 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
     const u64 fsub = (__ballot(failed) >> shift) & kmask, esub = (__ballot(lst != 0) >> shift) & kmask;
     const int first = fsub ? __ffsll(fsub) - 1 : K;
     const int32_t err = __shfl(lst, esub ? shift + __ffsll(esub) - 1 : shift);
-    if (has) a.out[base + i] = was_alive && lane < first ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+    if constexpr (A::kWindow) {                               // strict: a failing group is zeros as a whole
+      if (has && !refused) a.out[base + a.off(i)] = was_alive && !fsub ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+    } else {
+      if (has) a.out[base + i] = was_alive && lane < first ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+    }
     if (was_alive && fsub) {
       alive = false;
       avail = g * K + first;
-      sst = esub ? err : 0;
+      if constexpr (A::kWindow) sst = esub ? err : (int32_t)R::kTruncated;
+      else sst = esub ? err : 0;
     }
   }
   if (valid && lane == 0) {
-    a.available[str] = (int32_t)avail;
+    if constexpr (!A::kWindow) a.available[str] = (int32_t)avail;
     a.status[str] = sst;
   }
 }
@@ -859,6 +906,24 @@ int check_layers(const char* what, const uint8_t* layer, int sel0, int n_sel) {
 
 constexpr int kLayerWaves = 8;       // streams per workgroup of the layered K = 1 decode
 
+template <class A>
+int launch_interleaved_decode(const char* what, const IlvDecArgs<A>& a, const vam_rans_tables* tables, void* stream) {
+  const int blocks = (a.n_streams * a.K + kLaneBlock - 1) / kLaneBlock;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (tables->packed) {
+    const int lds = tables->packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_decode_kernel<true, A>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((rans_interleaved_decode_kernel<true, A>), dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL((rans_interleaved_decode_kernel<false, A>), dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
+  }
+  return check_launch("rans_interleaved_decode_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1030,10 +1095,10 @@ int vam_rans_interleaved_encode_device(const int32_t* sym, const int32_t* idx, i
   if (int rc = check_tables(what, tables)) return rc;
   VAM_REQUIRE(out_cap_words >= 2l * lanes && out_cap_words < (1l << 31), "%s: a region is 2 * lanes .. 2^31 words, got %ld", what,
               out_cap_words);
-  IlvEncArgs a{sym, idx, n_streams, n, lanes, *tables, out_words, out_cap_words, lengths, status, counts, n_marks, mark_bytes};
+  IlvEncArgs<FlatRows> a{{}, sym, idx, n_streams, n, lanes, *tables, out_words, out_cap_words, lengths, status, counts, n_marks, mark_bytes};
   const int threads = n_streams * lanes;
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  hipLaunchKernelGGL(rans_interleaved_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(rans_interleaved_encode_kernel<FlatRows>, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
   return check_launch("rans_interleaved_encode_kernel");
 }
 
@@ -1048,21 +1113,43 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
   VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
               what, n_streams, n);
   if (int rc = check_tables(what, tables)) return rc;
-  IlvDecArgs a{bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, available, status};
-  const int blocks = (n_streams * lanes + kLaneBlock - 1) / kLaneBlock;
+  IlvDecArgs<FlatRows> a{{}, bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, available, status};
+  return launch_interleaved_decode(what, a, tables, stream);
+}
+
+// The window forms: z and the base slices of an "embedded-4" container.
+int vam_rans_interleaved_encode_nhwc_device(const int32_t* sym, const int32_t* idx, int B, int h, int w, int ld, int c0, int C,
+                                            int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                                            long out_cap_words, int32_t* lengths, int32_t* status, void* stream) {
+  const char* what = "vam_rans_interleaved_encode_nhwc_device";
+  VAM_REQUIRE(sym && out_words && lengths && status, "%s: need sym, out_words, lengths, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  VAM_REQUIRE(out_cap_words >= 2l * lanes && out_cap_words < (1l << 31), "%s: a region is 2 * lanes .. 2^31 words, got %ld", what,
+              out_cap_words);
+  const int n_streams = B * n_slices;                       // at most 2^20, each of at most 2^28 elements
+  IlvEncArgs<NhwcWindow> a{{B, h * w, ld, c0, C}, sym, idx, n_streams, (long)h * w * C, lanes, *tables, out_words, out_cap_words,
+                           lengths, status, nullptr, 0, nullptr};
+  const int threads = n_streams * lanes;
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_decode_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(rans_interleaved_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(rans_interleaved_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_interleaved_decode_kernel");
+  hipLaunchKernelGGL(rans_interleaved_encode_kernel<NhwcWindow>, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_interleaved_encode_kernel");
+}
+
+int vam_rans_interleaved_decode_nhwc_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                            const int32_t* byte_lengths, const int32_t* idx, int B, int h, int w, int ld, int c0,
+                                            int C, int n_slices, int lanes, const vam_rans_tables* tables, int32_t* sym_out,
+                                            int32_t* status, void* stream) {
+  const char* what = "vam_rans_interleaved_decode_nhwc_device";
+  VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status && bytes_total >= 0 && ((uintptr_t)bytes & 3) == 0,
+              "%s: need word-aligned bytes, offsets, lengths, sym_out, status", what);
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices)) return rc;
+  if (int rc = check_tables(what, tables)) return rc;
+  IlvDecArgs<NhwcWindow> a{{B, h * w, ld, c0, C}, bytes, bytes_total, byte_offsets, byte_lengths, idx, B * n_slices, (long)h * w * C,
+                           lanes, *tables, sym_out, nullptr, status};
+  return launch_interleaved_decode(what, a, tables, stream);
 }
 
 // ---------------------------------------------------------------- resumable decode

@@ -38,6 +38,12 @@ A **resumable** decoder is a receiver whose bytes keep arriv
 keeps a checkpoint per stream at a group boundary (bitstream.Checkpoints), :meth:`EmbeddedDecoder.extend` takes the bytes
 that follow — :func:`delta` cuts them on the transmitter's side — and only the new elements are entropy-decoded.  The
 format is unchanged, and after every ``extend`` the decoder equals a fresh one on the concatenated containers bit for bit.
+
+``base_lanes`` = Kb > 1 codes z and the base slices, too, as interleaved strings, on Kb lanes, so that
+the device coder decodes them with one thread per lane instead of one wave per string.  Such a container carries
+``"format": "embedded-4"``, always ``"lanes"`` and ``"base_lanes": Kb``; it is scheduled exactly when it carries
+``"schedule"`` (then also ``"side_bytes"`` and marks by ``"stage"``).  Embedded streams, marks, counts and mark bytes are
+those of ``base_lanes=1``.  z and the base are needed whole: a string that ends early is a ValueError at the decoder.
 """
 from __future__ import annotations
 
@@ -56,6 +62,8 @@ from .progressive import Q_LIST
 FORMAT = "embedded-1"
 FORMAT_LANES = "embedded-2"          # embedded streams on K > 1 interleaved lanes; carries "lanes": K
 FORMAT_SCHEDULED = "embedded-3"      # scheduled rank order; carries "lanes": K >= 1, "schedule" and "side_bytes"
+FORMAT_BASE_LANES = "embedded-4"     # z and the base on Kb > 1 interleaved lanes; carries "lanes": K >= 1, "base_lanes": Kb
+_FORMATS = (FORMAT, FORMAT_LANES, FORMAT_SCHEDULED, FORMAT_BASE_LANES)
 _LAYERED = "the layered container (progressive.encode_batch / ProgressiveDecoder)"
 
 
@@ -160,7 +168,7 @@ def _schedule_of(cs):
     for b, c in enumerate(cs):
         sc = c.get("schedule")
         if not isinstance(sc, dict) or "levels" not in sc or "index" not in sc:
-            raise ValueError(f"EmbeddedDecoder: container {b} is {FORMAT_SCHEDULED!r} and carries no schedule")
+            raise ValueError(f"EmbeddedDecoder: container {b} is scheduled ({c.get('format')!r}) and carries no schedule")
         lv = np.asarray(sc["levels"], dtype=np.float64).reshape(-1)
         ix = np.asarray(sc["index"])
         h, w = 4 * int(c["shape"][0]), 4 * int(c["shape"][1])
@@ -180,7 +188,7 @@ def _schedule_of(cs):
 
 
 def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=None, coder: Optional[str] = None, lanes: int = 1,
-                 schedule=None) -> List[dict]:
+                 schedule=None, base_lanes: int = 1) -> List[dict]:
     """Embedded containers of a batch x [B,3,H,W] (H, W multiples of 64, as for ``compress``) on the fused plans: the
     ``compress(x, 10)`` plan (symbols round(r - mu), unmasked indexes), vam_variance_rank on its progressive sigma, then
     vam_rank_gather writes symbols and indexes of every segment in rank order.  Each progressive slice becomes ONE
@@ -198,7 +206,13 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
     stage (:func:`check_schedule`).  The streams are coded in the scheduled rank order — vam_variance_layers_per_image on the
     schedule's levels, vam_stage_ids, vam_variance_rank_staged — and marked per stage (vam_rank_counts on the stage ids);
     the coders are unchanged.  Format ``"embedded-3"``: ``"lanes"`` always, ``"schedule"`` and its raw ``"side_bytes"``,
-    ``"marks": {"stage", "count", "bytes"}``; z and the base slices are byte for byte as before."""
+    ``"marks": {"stage", "count", "bytes"}``; z and the base slices are byte for byte as before.
+
+    ``base_lanes`` = Kb > 1 (read from the argument only, like ``lanes``): z and every base slice as an
+    interleaved string on Kb lanes of the same elements in the same order (bitstream.encode_interleaved_streams; on the
+    device one vam_rans_interleaved_encode_nhwc_device launch for z and one for all base slices).  Format ``"embedded-4"``
+    with ``"lanes"`` always and ``"base_lanes": Kb``, scheduled exactly when it carries ``"schedule"``; everything else in
+    the container is what ``base_lanes=1`` gives.  Kb = 1 changes nothing."""
     from . import _lib as L
     from . import bitstream as bs
     from . import ops
@@ -212,7 +226,7 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
         qs = list(range(index.shape[1]))
     else:
         qs = P.check_q_list(Q_LIST if marks is None else marks)
-    coder, K = P._check_coder(model, coder), bs.check_lanes(lanes)
+    coder, K, Kb = P._check_coder(model, coder), bs.check_lanes(lanes), bs.check_lanes(base_lanes)
     m = model
     d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
     with torch.no_grad():
@@ -246,8 +260,12 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
         ops.rank_counts(layer, perm, ns, len(qs), count)
         if coder == "device":
             tg, te = bs.DeviceCoderTables.of(m.gaussian_conditional, dev), bs.DeviceCoderTables.of(m.entropy_bottleneck, dev)
-            z_str = bs.encode_streams_device(plan.z_sym, None, 1, m.N, te)[0]
-            base = bs.encode_streams_device(plan.sym, plan.idx, ns, C, tg)                      # [slice][image]
+            if Kb > 1:
+                z_str = bs.encode_window_interleaved_device(plan.z_sym, None, 1, m.N, te, Kb)[0]
+                base = bs.encode_window_interleaved_device(plan.sym, plan.idx, ns, C, tg, Kb)   # [slice][image]
+            else:
+                z_str = bs.encode_streams_device(plan.z_sym, None, 1, m.N, te)[0]
+                base = bs.encode_streams_device(plan.sym, plan.idx, ns, C, tg)                  # [slice][image]
             emb_str, cut = bs.encode_embedded_device(r_sym, r_idx, tg, K, count)                # stream b * ns + j
             cuts = cut.reshape(len(qs), B, ns)
             count = count.cpu().numpy().astype(np.int64)
@@ -258,16 +276,17 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
     if coder == "host":
         tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
         zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
-        z_str = bs.encode_streams([(zs[b], zi) for b in range(B)], te)
+        z_jobs = [(zs[b], zi) for b in range(B)]
+        z_str = bs.encode_streams(z_jobs, te) if Kb == 1 else bs.encode_interleaved_streams(z_jobs, te, lanes=Kb)
         sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
         jobs = [(sl(sym_b, b, i), sl(idx_b, b, i)) for i in range(ns) for b in range(B)]
         e_jobs = [(r_sym[b, j], r_idx[b, j]) for b in range(B) for j in range(ns)]
-        if K == 1:                                                                              # one call, as ever
+        if K == 1 and Kb == 1:                                                                  # one call, as ever
             y_str = bs.encode_streams(jobs + e_jobs, tg)
             emb_str = y_str[ns * B:]
         else:
-            y_str = bs.encode_streams(jobs, tg)
-            emb_str = bs.encode_interleaved_streams(e_jobs, tg, lanes=K)
+            y_str = bs.encode_streams(jobs, tg) if Kb == 1 else bs.encode_interleaved_streams(jobs, tg, lanes=Kb)
+            emb_str = bs.encode_streams(e_jobs, tg) if K == 1 else bs.encode_interleaved_streams(e_jobs, tg, lanes=K)
         base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
         got = _map_threads(lambda bj: bs.prefix_bytes(emb_str[bj[0] * ns + bj[1]], r_idx[bj[0], bj[1]],
                                                       count[:, bj[0], bj[1]].tolist(), tg, lanes=K),
@@ -286,6 +305,8 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
             c["marks"]["stage"] = c["marks"].pop("q")
             c["schedule"] = {"levels": [float(v) for v in levels[b]], "index": index[b].copy()}
             c["side_bytes"] = 8 * len(levels[b]) + int(index[b].size)     # carried raw, as a quality map is (section 9k)
+        if Kb > 1:
+            c["format"], c["lanes"], c["base_lanes"] = FORMAT_BASE_LANES, K, Kb
         containers.append(c)
     if save_path is not None:
         os.makedirs(save_path, exist_ok=True)
@@ -295,20 +316,46 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
     return containers
 
 
+def _scheduled(c) -> bool:
+    """Whether a checked container is in a scheduled rank order: ``"embedded-3"``, or ``"embedded-4"`` with a schedule."""
+    return c["format"] == FORMAT_SCHEDULED or (c["format"] == FORMAT_BASE_LANES and "schedule" in c)
+
+
+def _base_lanes(c) -> int:
+    """The lanes of z and the base strings of a checked container: its ``"base_lanes"`` for ``"embedded-4"``, otherwise 1."""
+    return int(c["base_lanes"]) if c["format"] == FORMAT_BASE_LANES else 1
+
+
 def _check_container(c) -> int:
-    """The lanes per embedded stream of container ``c``: 1 for ``"embedded-1"``, its ``"lanes"`` for ``"embedded-2"`` and
-    ``"embedded-3"`` (which carries the key for K = 1 too)."""
+    """The lanes per embedded stream of container ``c``: 1 for ``"embedded-1"``, its ``"lanes"`` for ``"embedded-2"``,
+    ``"embedded-3"`` and ``"embedded-4"`` (which carry the key for K = 1 too).  An ``"embedded-4"`` container also carries
+    ``"base_lanes"`` > 1 (:func:`_base_lanes`) and is scheduled exactly when it carries ``"schedule"`` (:func:`_scheduled`)."""
     from . import bitstream as bs
-    if not isinstance(c, dict) or c.get("format") not in (FORMAT, FORMAT_LANES, FORMAT_SCHEDULED):
-        raise ValueError(f"not an embedded container (format {FORMAT!r}, {FORMAT_LANES!r} or {FORMAT_SCHEDULED!r}): got "
-                         f"{c.get('format') if isinstance(c, dict) else type(c).__name__!r}")
+    if not isinstance(c, dict) or c.get("format") not in _FORMATS:
+        raise ValueError(f"not an embedded container (format {FORMAT!r}, {FORMAT_LANES!r}, {FORMAT_SCHEDULED!r} or "
+                         f"{FORMAT_BASE_LANES!r}): got {c.get('format') if isinstance(c, dict) else type(c).__name__!r}")
     if c["format"] == FORMAT:
         return 1
     K = bs.check_lanes(c.get("lanes"))
-    if c["format"] == FORMAT_SCHEDULED:
+    if c["format"] == FORMAT_BASE_LANES:
+        if "base_lanes" not in c:
+            raise ValueError(f"not an embedded container: format {FORMAT_BASE_LANES!r} carries \"base_lanes\", this one lacks it")
+        try:
+            Kb = bs.check_lanes(c["base_lanes"])
+        except ValueError as e:
+            raise ValueError(f"not an embedded container: format {FORMAT_BASE_LANES!r}: base_lanes: {e}") from e
+        if Kb == 1:
+            raise ValueError(f"an {FORMAT_BASE_LANES!r} container carries base_lanes > 1; \"base_lanes\": 1 is format {FORMAT!r}, "
+                             f"{FORMAT_LANES!r} or {FORMAT_SCHEDULED!r}")
+        if "schedule" not in c:
+            if "q" not in c.get("marks", ()):
+                raise ValueError(f"not an embedded container: an unscheduled {FORMAT_BASE_LANES!r} container carries marks by \"q\", "
+                                 "this one lacks them")
+            return K
+    if _scheduled(c):
         if not isinstance(c.get("schedule"), dict) or "side_bytes" not in c or "stage" not in c.get("marks", ()):
-            raise ValueError(f"not an embedded container: format {FORMAT_SCHEDULED!r} carries \"schedule\", \"side_bytes\" and marks "
-                             "by \"stage\", this one lacks them")
+            raise ValueError(f"not an embedded container: a scheduled {c['format']!r} container carries \"schedule\", \"side_bytes\" "
+                             "and marks by \"stage\", this one lacks them")
         return K
     if K == 1:
         raise ValueError(f"an {FORMAT_LANES!r} container carries lanes > 1; one lane is format {FORMAT!r}")
@@ -321,21 +368,22 @@ def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = No
     Exactly one of: ``q`` — a marked quality: every slice is cut at that mark's bytes; ``max_bytes`` — the largest mark
     whose z + base + embedded total fits (the base alone when no mark fits, ValueError when not even the base does);
     ``slice_bytes`` — one explicit length per slice, any byte count (a length beyond what the slice holds keeps it whole);
-    ``stage`` — a stage of a scheduled container (``"embedded-3"``), which is marked by stage and refuses ``q``; its
-    ``max_bytes`` counts the schedule's ``side_bytes`` with z and the base."""
+    ``stage`` — a stage of a scheduled container (``"embedded-3"``, or ``"embedded-4"`` with a schedule), which is marked by
+    stage and refuses ``q``; its ``max_bytes`` counts the schedule's ``side_bytes`` with z and the base.  ``"lanes"``,
+    ``"base_lanes"`` and the schedule go through untouched."""
     _check_container(container)
     if sum(a is not None for a in (q, max_bytes, slice_bytes, stage)) != 1:
         raise ValueError("truncate: give exactly one of q, stage, max_bytes and slice_bytes")
     emb, marks = container["embedded"], container["marks"]
     ns = len(emb)
-    scheduled = container["format"] == FORMAT_SCHEDULED
+    scheduled = _scheduled(container)
     if q is not None and scheduled:
-        raise ValueError(f"truncate: a scheduled container ({FORMAT_SCHEDULED!r}) is marked by stage, a uniform quality is no "
+        raise ValueError(f"truncate: a scheduled container ({container['format']!r}) is marked by stage, a uniform quality is no "
                          "prefix of its order; cut it with stage=")
     if stage is not None:
         if not scheduled:
-            raise ValueError(f"truncate: stage= cuts a scheduled container ({FORMAT_SCHEDULED!r}), this one is "
-                             f"{container['format']!r}; cut it with q=")
+            raise ValueError(f"truncate: stage= cuts a scheduled container ({FORMAT_SCHEDULED!r}, or {FORMAT_BASE_LANES!r} with a "
+                             f"schedule), this one is {container['format']!r} without one; cut it with q=")
         ks = [k for k, st in enumerate(marks["stage"]) if int(st) == int(stage)] if int(stage) == stage else []
         if not ks:
             raise ValueError(f"truncate: stage {stage} is not marked in this container (stages {list(marks['stage'])})")
@@ -397,6 +445,9 @@ def delta(longer, shorter) -> List[bytes]:
             raise ValueError(f"delta: the containers differ in their {what}: the shorter one is no cut of the longer one")
     if Ka != Kb:
         raise ValueError(f"delta: the containers differ in their lanes ({Kb} and {Ka}): the shorter one is no cut of the longer one")
+    if _base_lanes(longer) != _base_lanes(shorter):
+        raise ValueError(f"delta: the containers differ in their base_lanes ({_base_lanes(shorter)} and {_base_lanes(longer)}): "
+                         "the shorter one is no cut of the longer one")
     ea, eb = longer["embedded"], shorter["embedded"]
     if len(ea) != len(eb):
         raise ValueError(f"delta: the containers hold {len(eb)} and {len(ea)} slices: the shorter one is no cut of the longer one")
@@ -415,7 +466,10 @@ class EmbeddedDecoder:
     elements of every slice are present.  A decoded quality equals ``forward_single_quality(x, q)`` bit for bit.
 
     The lanes per embedded stream are read from the containers (``"embedded-2"``: their ``"lanes"``); a batch that mixes
-    them is refused.  ``coder`` (None: ``model.coder``): "host" prefix-decodes on the host's threads from a host copy of
+    them is refused.  So are the lanes of z and the base (``"embedded-4"``: their ``"base_lanes"``; 1
+    without the key): those strings are needed whole, and one that decodes fewer than its elements, or fails with a status,
+    is a ValueError naming the image and "z" or the slice — from the tolerant decode on the host coder, from status 1 of
+    vam_rans_interleaved_decode_nhwc_device on the device.  ``coder`` (None: ``model.coder``): "host" prefix-decodes on the host's threads from a host copy of
     the ranked indexes; "device"  decodes z and the base slices with the device coder, uploads the
     embedded strings once and prefix-decodes them with ONE launch into the plan's ranked symbols; the counts come back
     with the status codes in one read, and the ranked indexes stay on the device unless :meth:`bits` asks for them.
@@ -441,10 +495,15 @@ class EmbeddedDecoder:
             raise ValueError(f"EmbeddedDecoder: every container must have the same lanes per embedded stream, got "
                              f"{sorted(set(lanes))}; decode them separately")
         self.lanes, self.coder = lanes[0], P._check_coder(model, coder)
-        sched = [c["format"] == FORMAT_SCHEDULED for c in cs]
+        base_lanes = [_base_lanes(c) for c in cs]
+        if any(k != base_lanes[0] for k in base_lanes):
+            raise ValueError(f"EmbeddedDecoder: every container must have the same base_lanes (the lanes of z and the base slices; "
+                             f"1 without the key), got {sorted(set(base_lanes))}; decode them separately")
+        self.base_lanes = base_lanes[0]
+        sched = [_scheduled(c) for c in cs]
         if any(sched) and not all(sched):
-            raise ValueError(f"EmbeddedDecoder: a batch holds scheduled ({FORMAT_SCHEDULED!r}) or plain containers, not both "
-                             "(their rank orders differ); decode them separately")
+            raise ValueError(f"EmbeddedDecoder: a batch holds scheduled ({FORMAT_SCHEDULED!r}, or {FORMAT_BASE_LANES!r} with a "
+                             "schedule) or plain containers, not both (their rank orders differ); decode them separately")
         self.scheduled = sched[0]
         shape = tuple(cs[0]["shape"])
         for c in cs[1:]:
@@ -479,7 +538,8 @@ class EmbeddedDecoder:
         if self.scheduled:
             dp.fill_schedule(*self.schedule)                # before the chain that reads it, on the same stream
             self._stage_count = None
-        up = dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs])
+        up = dp.front([[c["base"][i][0] for c in cs] for i in range(ns)], [c["z"][0] for c in cs], lanes=self.base_lanes,
+                      interleaved=self.base_lanes > 1)
         dp.owner = self
         if self.coder == "device":
             return self._front_device(up)
@@ -519,8 +579,13 @@ class EmbeddedDecoder:
             else:
                 dp.ranked.copy_(self.ranked)
                 got = None
-            bs.check_status(up, B, "EmbeddedDecoder", lambda k: f"z stream (image {k})" if k < B else
-                            f"base stream (image {k % B}, slice {k // B - 1})")
+            try:
+                bs.check_status(up, B, "EmbeddedDecoder", lambda k: f"z stream (image {k})" if k < B else
+                                f"base stream (image {k % B}, slice {k // B - 1})")
+            except L.VamError as e:
+                if self.base_lanes == 1:
+                    raise
+                raise ValueError(f"{e} (z and the base of an {FORMAT_BASE_LANES!r} container are needed whole)") from e
         if got is not None:
             bad = np.flatnonzero(got[1])
             if bad.size:
@@ -658,7 +723,7 @@ class EmbeddedDecoder:
 
     def _refuse_scheduled(self, what: str):
         if self.scheduled:
-            raise ValueError(f"EmbeddedDecoder.{what}: these containers are scheduled ({FORMAT_SCHEDULED!r}); a uniform quality is "
+            raise ValueError(f"EmbeddedDecoder.{what}: these containers are scheduled ({self.containers[0]['format']!r}); a uniform quality is "
                              "no prefix of a scheduled rank order, decode stages with decode_stages")
 
     def decode_stages(self, ks: Sequence[int]) -> List[dict]:

@@ -377,14 +377,15 @@ def progressive_rd(model, images: Sequence[torch.Tensor], q_list: Sequence[float
     return rows
 
 
-def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float], coder=None, lanes: int = 1):
+def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float], coder=None, lanes: int = 1, base_lanes: int = 1):
     """:func:`progressive_rd`'s printout for the embedded format (embedded.encode_batch / EmbeddedDecoder, DESIGN section
     9m): images of one shape are padded and coded as one batch, ONCE and without a quality list of their own; the base and
     then every quality of ``qualities`` (any values >= 0, marked or not) is decoded from the same streams.  Returns one
     dict per level, the base first: q, bpp (8 * the bytes a receiver needs for that quality — z, the base and the shortest
     prefix of every slice — / pixels of the ORIGINAL image), psnr (of the cropped decode), enc_s and dec_s (seconds per
     image: the encode once, the decode of that level), each the mean over the images, plus "bpp_all" / "psnr_all".
-    ``coder`` and ``lanes`` are passed on to embedded.encode_batch, ``coder`` to the decoder too."""
+    ``coder``, ``lanes`` and ``base_lanes`` are passed on to embedded.encode_batch, ``coder`` to the decoder too (DESIGN sections
+    9q and 9t)."""
     from . import embedded as EB
     images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
     levels = [0.0] + [float(q) for q in qualities]
@@ -399,7 +400,7 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
             xp, unpad = pad_image(xs)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            containers = EB.encode_batch(model, xp, coder=coder, lanes=lanes)
+            containers = EB.encode_batch(model, xp, coder=coder, lanes=lanes, base_lanes=base_lanes)
             t1 = time.perf_counter()
             dec = EB.EmbeddedDecoder(model, containers, coder=coder)
             for k, q in enumerate(levels):
@@ -438,13 +439,13 @@ def roi_schedule(B: int, H: int, W: int, boxes, roi_qualities: Sequence[float], 
     return [quality_map_from_boxes(B, H, W, g, [tuple(box[:5]) + (r,) for box in boxes]) for r, g in stages]
 
 
-def embedded_roi_rd(model, images: torch.Tensor, schedule, region, coder=None, lanes: int = 1):
+def embedded_roi_rd(model, images: torch.Tensor, schedule, region, coder=None, lanes: int = 1, base_lanes: int = 1):
     """Rate and distortion per stage of a scheduled embedded stream: ``images`` [B, 3, H, W] (H, W
     multiples of 64) are coded ONCE with embedded.encode_batch(schedule=...), and every stage is decoded from the same
     containers.  One dict per stage: "stage", "bytes" (per image: z, the base, the schedule's side bytes and the stage's
     mark of every slice — what a receiver needs for it), "bpp" (8 * bytes / pixels), and "psnr", "psnr_in", "psnr_out"
     (float64 [B] host tensors; :func:`rd_quality_map`'s definition on all pixels and on the pixels inside and outside the
-    boolean pixel ``region`` [B, H, W] or [B, 1, H, W])."""
+    boolean pixel ``region`` [B, H, W] or [B, 1, H, W]).  ``coder``, ``lanes`` and ``base_lanes`` go to encode_batch."""
     from . import embedded as EB
     dev = next(model.parameters()).device
     x = images.to(dev).contiguous()
@@ -454,7 +455,7 @@ def embedded_roi_rd(model, images: torch.Tensor, schedule, region, coder=None, l
         raise ValueError("embedded_roi_rd: region is a boolean [B, H, W] or [B, 1, H, W]")
     rows = []
     with torch.no_grad():
-        containers = EB.encode_batch(model, x, schedule=schedule, coder=coder, lanes=lanes)
+        containers = EB.encode_batch(model, x, schedule=schedule, coder=coder, lanes=lanes, base_lanes=base_lanes)
         dec = EB.EmbeddedDecoder(model, containers, coder=coder)
         for k in range(dec.n_stages):
             x_hat = dec.decode_stages([k])[0]["x_hat"].contiguous()

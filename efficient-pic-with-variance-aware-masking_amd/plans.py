@@ -960,6 +960,7 @@ class _DecPlan:
         self.m, self.B, self.base_only, self.rem_idx = m, B, base_only, rem_idx
         self.coder, self.up, self.up_at = coder, None, 0
         self.lanes = 1                                   # lanes per stream: decode() sets it per call
+        self.interleaved = False                         # the lanes share one word stream: front() sets it
         self.per_image, self.quality_map = per_image, quality_map
         self.qtable = _mask_table_buffer(B, device) if per_image or quality_map else None
         self.level_map = torch.zeros((B, 16 * hz * wz), dtype=torch.uint8, device=device) if quality_map else None
@@ -1022,12 +1023,16 @@ class _DecPlan:
             self.p_prog.append((Pa, Pb))
         E.lower_g_s(self.p_syn, [m.g_s[1] if m.multiple_decoder else m.g_s], [sc.yp], [self.x_hat])
 
-    def _decode_slice(self, strings, idx_view: ops.IView, sym_view: ops.IView, tables, C):
-        """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window)."""
+    def _decode_slice(self, strings, idx_view: ops.IView, sym_view: ops.IView, tables, C, name: str = "slice"):
+        """indexes GPU -> host, rANS decode per image, symbols host -> GPU (NHWC window).  ``name`` words the slice in the
+        refusal of an interleaved string."""
         from . import bitstream as bs
         if self.coder == "device":       # the B strings of this slice are the next B uploaded ones: one launch, no round trip
-            bs.decode_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, bs.DeviceCoderTables.of(self.m.gaussian_conditional, self.device),
-                               lanes=self.lanes)
+            tg = bs.DeviceCoderTables.of(self.m.gaussian_conditional, self.device)
+            if self.interleaved:
+                bs.decode_window_interleaved_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, tg, self.lanes)
+            else:
+                bs.decode_uploaded(self.up, self.up_at, idx_view, sym_view, 1, C, tg, lanes=self.lanes)
             self.up_at += self.B
             return
         B, h, w = self.B, idx_view.buf.shape[1], idx_view.buf.shape[2]
@@ -1035,12 +1040,14 @@ class _DecPlan:
         idx = idx_view.buf[..., idx_view.c0:idx_view.c0 + C].cpu().numpy()          # [B,h,w,C]
         out = np.empty((B, h, w, C), dtype=np.int32)
         for b in range(B):
-            dec = self._host_decode(strings[b], idx[b].transpose(2, 0, 1), tables)   # stream order [C,h,w]
+            dec = self._host_decode(strings[b], idx[b].transpose(2, 0, 1), tables, f"base stream (image {b}, {name})")   # stream order [C,h,w]
             out[b] = dec.reshape(C, h, w).transpose(1, 2, 0)
         sym_view.buf[..., sym_view.c0:sym_view.c0 + C].copy_(torch.from_numpy(out).to(self.device))
 
-    def _host_decode(self, string, idx, tables):
+    def _host_decode(self, string, idx, tables, what: str = "stream"):
         from . import bitstream as bs
+        if self.interleaved:             # the tolerant decode, the whole stream required
+            return bs.decode_interleaved_strict(string, idx, tables, self.lanes, what)
         return bs.decode(string, idx, tables) if self.lanes == 1 else bs.decode_lanes(string, idx, tables, self.lanes)
 
     def _decode_base(self, y_strings, z_strings, tg, te):
@@ -1049,12 +1056,15 @@ class _DecPlan:
         from . import bitstream as bs
         m = self.m
         if self.coder == "device":       # z: the first B uploaded strings, table index = channel
-            bs.decode_uploaded(self.up, 0, None, self.z_sym, 1, m.N, bs.DeviceCoderTables.of(m.entropy_bottleneck, self.device),
-                               lanes=self.lanes)
+            tz = bs.DeviceCoderTables.of(m.entropy_bottleneck, self.device)
+            if self.interleaved:
+                bs.decode_window_interleaved_uploaded(self.up, 0, None, self.z_sym, 1, m.N, tz, self.lanes)
+            else:
+                bs.decode_uploaded(self.up, 0, None, self.z_sym, 1, m.N, tz, lanes=self.lanes)
             self.up_at = self.B
         else:
             zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], (m.N, self.hz, self.wz))
-            zs = np.stack([self._host_decode(z_strings[b], zi, te).reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
+            zs = np.stack([self._host_decode(z_strings[b], zi, te, f"z stream (image {b})").reshape(m.N, self.hz, self.wz).transpose(1, 2, 0)
                            for b in range(self.B)])
             self.z_sym.buf.copy_(torch.from_numpy(zs).to(self.device))
         self.p_hyper.run()
@@ -1064,7 +1074,7 @@ class _DecPlan:
         """Slice by slice: entropy parameters and indexes, the host's rANS decode, then dequantisation and LRP."""
         for i, (Pa, Pb) in enumerate(pairs):
             Pa.run()
-            self._decode_slice(strings[i], self.sc.sl(idx, i), self.sc.sl(sym, i), tg, self.m.dim_chunk)
+            self._decode_slice(strings[i], self.sc.sl(idx, i), self.sc.sl(sym, i), tg, self.m.dim_chunk, f"slice {i}")
             Pb.run()
 
     def decode(self, strings, pr, checkpoint_rep, quality_map=None, lanes: int = 1):
@@ -1142,16 +1152,20 @@ class _ProgDecPlan(_DecPlan):
         self.sweep_parts = dict(heads=sc.heads, yb=sc.yb, mu=mu_p, std=std_p, mu_tot=sc.mu_tot, sym=self.sym, layer=self.layer,
                                 g_s=m.g_s[1] if m.multiple_decoder else m.g_s)
 
-    def front(self, y_strings, z_strings, lanes: int = 1):
+    def front(self, y_strings, z_strings, lanes: int = 1, interleaved: bool = False):
         """Base slices (host round trips) and the progressive chain, layer ids and indexes of every image.  ``lanes``: the
-        lanes per stream of every string.  Device coder: z and the base go up in one copy, no round trip follows, the
-        symbol window is zeroed, and the upload is returned for the caller to read its status codes later (host: None)."""
+        lanes per stream of every string; ``interleaved``: they share one word stream (bitstream.encode_interleaved, DESIGN
+        section 9t) and every string is needed whole — ValueError on the host coder, status 1 on the device — where the
+        default is the lane-split string of section 9o.  Device coder: z and the base go up in one copy, no round trip
+        follows, the symbol window is zeroed, and the upload is returned for the caller to read its status codes later
+        (host: None)."""
         from . import bitstream as bs
         tg, te = bs.Tables.of(self.m.gaussian_conditional), bs.Tables.of(self.m.entropy_bottleneck)
-        self.lanes = bs.check_lanes(lanes)
+        self.lanes, self.interleaved = bs.check_lanes(lanes), bool(interleaved)
         with self.runner.on_stream():
-            if self.coder == "device":
-                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings for s_ in row], self.device, self.lanes)
+            if self.coder == "device":            # an interleaved string has one status code, whatever its lanes
+                self.up = bs.upload_streams(list(z_strings) + [s_ for row in y_strings for s_ in row], self.device,
+                                            1 if self.interleaved else self.lanes)
             self._decode_base(y_strings, z_strings, tg, te)
             self.p_chain.run()
             if self.coder == "device":

@@ -928,6 +928,23 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
                                        const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
                                        const vam_rans_tables* tables, int32_t* sym_out, int32_t* available, int32_t* status,
                                        void* stream);
+/* The same strings over the stream geometry of vam_rans_encode_device / vam_rans_decode_device: a stream
+ * is an (image, slice) pair over the channels [c0 + s C, c0 + (s + 1) C) of int32 NHWC buffers [B, h, w, ld], stream id =
+ * s * B + image, n = C h w, element i = channel i / (h w) at pixel i % (h w); idx NULL: the table index is the channel.
+ * Thread geometry as above: one thread per (stream, lane).  These code z and the base slices of an "embedded-4" container.
+ * vam_rans_interleaved_encode_nhwc_device: regions (2 n + 2 K + 16 words hold any string), lengths and status as in
+ * vam_rans_interleaved_encode_device, no marks; the strings equal vam_rans_interleaved_encode of the same elements, and at
+ * K = 1 vam_rans_encode_device's.
+ * vam_rans_interleaved_decode_nhwc_device: STRICT, the whole stream is needed.  status[s] = 0 and every element written;
+ * 1 the words end early, 2 / 3 a bad index / table: the elements from the failing group on are written as 0; 6 a refused
+ * offset or length: nothing is read or written.  No read leaves a stream's bytes, no write its own channel window. */
+int vam_rans_interleaved_encode_nhwc_device(const int32_t* sym, const int32_t* idx, int B, int h, int w, int ld, int c0, int C,
+                                            int n_slices, int lanes, const vam_rans_tables* tables, uint32_t* out_words,
+                                            long out_cap_words, int32_t* lengths, int32_t* status, void* stream);
+int vam_rans_interleaved_decode_nhwc_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,
+                                            const int32_t* byte_lengths, const int32_t* idx, int B, int h, int w, int ld, int c0,
+                                            int C, int n_slices, int lanes, const vam_rans_tables* tables, int32_t* sym_out,
+                                            int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ resumable embedded decode */
 /* The format above, unchanged, decoded in steps as the bytes arrive.  The CHECKPOINT of a stream is the decoder at the

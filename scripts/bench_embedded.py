@@ -26,7 +26,18 @@ with ``decode()``.  Per step and in total: the wall time and the entropy-decode 
 bitstream call, wall time; device: HIP events around the launch).  x_hat of every step is asserted identical
 between (a) and (b); no time is asserted.
 
-    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64] [--schedule roi | --resume S]
+``--base-lanes 1 8 64`` measures z and the base slices as interleaved strings on Kb lanes
+(``encode_batch(..., base_lanes=Kb)``, format "embedded-4") next to today's K = 1 strings.  One cell per (coder, lanes, Kb),
+the cells alternating on one build at the two inputs above: encode and decode wall time (decode = the decoder, the base and
+every mark), the coder's share (host: the bitstream calls, wall time; device: HIP events around the device coder's calls),
+within it the z + base part (device: events around those launches alone; host decode: the wall time of the strict / K = 1
+string decodes; host encode: not separable where one call codes base and embedded streams), and the bytes of z + base per
+image.  In the same run the layered container's device front end — ``progressive`` with ``coder="device"`` and ``lanes`` =
+Kb, a LANE-SPLIT base (section 9o) — is timed at every Kb, which puts the two lane formats side by side.  x_hat of every
+level is asserted identical across all cells; no time is asserted.
+
+    python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64]
+                                     [--schedule roi | --resume S | --base-lanes 1 8 64]
 """
 import argparse
 import json
@@ -179,6 +190,100 @@ def resume_main(a, net, dev):
     print(json.dumps(res))
 
 
+def base_lanes_main(a, net, dev):
+    """--base-lanes: an interleaved base on Kb lanes against the K = 1 base, cells interleaved; prints one JSON line."""
+    import vampic
+    from vampic import bitstream as bs, embedded as EB, progressive as P
+    acc = {"host": 0.0, "host_zb": 0.0, "coder": [], "zb": []}
+
+    def timed(fn, *keys):
+        def run(*args, **kw):
+            t0 = time.perf_counter()
+            try:
+                return fn(*args, **kw)
+            finally:
+                for k in keys:
+                    acc[k] += time.perf_counter() - t0
+        return run
+
+    def evented(fn, *keys):
+        def run(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            try:
+                return fn(*args, **kw)
+            finally:
+                e1.record()
+                for k in keys:
+                    acc[k].append((e0, e1))
+        return run
+    for name in ("encode_streams", "encode_interleaved_streams", "decode_prefix_streams"):
+        setattr(bs, name, timed(getattr(bs, name), "host"))
+    for name in ("decode", "decode_interleaved_strict"):                         # the host decoder's z and base strings
+        setattr(bs, name, timed(getattr(bs, name), "host", "host_zb"))
+    EB._map_threads = timed(EB._map_threads, "host")
+    for name in ("encode_streams_device", "encode_window_interleaved_device", "decode_uploaded", "decode_window_interleaved_uploaded"):
+        setattr(bs, name, evented(getattr(bs, name), "coder", "zb"))             # the device coder's z and base launches
+    for name in ("encode_embedded_device", "decode_embedded_uploaded", "encode_layers_device"):
+        setattr(bs, name, evented(getattr(bs, name), "coder"))
+
+    def drain():
+        """(coder ms, z + base ms) since the last call; after a synchronise."""
+        out = (1e3 * acc["host"] + sum(e0.elapsed_time(e1) for e0, e1 in acc["coder"]),
+               1e3 * acc["host_zb"] + sum(e0.elapsed_time(e1) for e0, e1 in acc["zb"]))
+        acc["host"] = acc["host_zb"] = 0.0
+        acc["coder"].clear()
+        acc["zb"].clear()
+        return out
+
+    res = {"metric": "embedded containers: interleaved base on Kb lanes vs the K = 1 base (ms, median)",
+           "device": torch.cuda.get_device_name(0), "coder_threads": bs.coder_threads(), "warmup": a.warmup, "reps": a.reps, "cases": {}}
+    for case, B, H, W, qs in (("1x512x768/15", 1, 512, 768, DEMO_Q), ("8x256x256/14", 8, 256, 256, P.Q_LIST)):
+        x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
+        cells = {f"{c}_k{K}_b{Kb}": (lambda c=c, K=K, Kb=Kb: EB.encode_batch(net, x, qs, coder=c, lanes=K, base_lanes=Kb),
+                                     lambda cs, c=c: [o["x_hat"] for o in EB.EmbeddedDecoder(net, cs, coder=c).decode_qualities([0.0] + list(qs))])
+                 for c in a.coder for K in a.lanes for Kb in a.base_lanes}
+        front = {f"layered_device_lanes{Kb}": (lambda Kb=Kb: P.encode_batch(net, x, qs, coder="device", lanes=Kb)[0],
+                                                lambda cs: [P.ProgressiveDecoder(net, cs, coder="device").decode_levels([0])[0]["x_hat"]])
+                 for Kb in a.base_lanes}
+        keys = ("enc", "enc_coder", "enc_zbase", "dec", "dec_coder", "dec_zbase")
+        t = {f"{p}_{k}": [] for p in list(cells) + list(front) for k in keys}
+        size = {}
+        with torch.no_grad():
+            for r in range(a.warmup + a.reps):
+                last = {}
+                for p, (enc, dec) in list(cells.items()) + list(front.items()):
+                    torch.cuda.synchronize()
+                    drain()
+                    t0 = time.perf_counter()
+                    cs = enc()
+                    torch.cuda.synchronize()
+                    t1, (c1, z1) = time.perf_counter(), drain()
+                    last[p] = dec(cs)
+                    torch.cuda.synchronize()
+                    t2, (c2, z2) = time.perf_counter(), drain()
+                    if r >= a.warmup:
+                        for k, v in zip(keys, (1e3 * (t1 - t0), c1, z1, 1e3 * (t2 - t1), c2, z2)):
+                            t[f"{p}_{k}"].append(v)
+                    size[p] = sum(sum(len(s_) for s_ in c_["z"]) + sum(len(s_[0]) for s_ in c_["base"]) for c_ in cs) / B
+                first = last[next(iter(cells))]
+                for p in cells:
+                    for k, (u, v) in enumerate(zip(first, last[p])):
+                        assert torch.equal(u, v), f"{case}: x_hat of level {k} differs between {next(iter(cells))} and {p}"
+                for p in front:                                                  # the layered container's level 0 is the base
+                    assert torch.equal(first[0], last[p][0]), f"{case}: the base x_hat differs between the embedded cells and {p}"
+        med = {k: round(statistics.median(v), 1) for k, v in t.items()}
+        row = lambda p: dict({k + "_ms": med[f"{p}_{k}"] for k in keys}, z_base_bytes_per_image=round(size[p], 1))
+        out = {"levels": len(qs), "x_hat_identical": True, "cells": {p: row(p) for p in cells}, "layered_front": {p: row(p) for p in front}}
+        for p, v in out["cells"].items():
+            if p.startswith("host"):
+                v["enc_zbase_ms"] = None                                         # one host call codes base and embedded streams
+        res["cases"][case] = out
+        net._drop_plans()
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=1)
@@ -187,6 +292,7 @@ def main():
     ap.add_argument("--lanes", nargs="+", type=int, default=[1])
     ap.add_argument("--schedule", choices=["roi"], default=None)
     ap.add_argument("--resume", type=int, default=None, metavar="S")
+    ap.add_argument("--base-lanes", nargs="+", type=int, default=None, metavar="Kb")
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -194,8 +300,10 @@ def main():
     dev = torch.device("cuda:0")
     net, _ = build_model(dev)
     net.update()
-    if a.schedule and a.resume:
-        ap.error("--schedule and --resume measure different things: give one")
+    if sum(v is not None for v in (a.schedule, a.resume, a.base_lanes)) > 1:
+        ap.error("--schedule, --resume and --base-lanes measure different things: give one")
+    if a.base_lanes is not None:
+        return base_lanes_main(a, net, dev)
     if a.schedule:
         return schedule_main(a, net, dev)
     if a.resume is not None:
