@@ -44,12 +44,20 @@ the device coder decodes them with one thread per lane instead of one wave per s
 ``"format": "embedded-4"``, always ``"lanes"`` and ``"base_lanes": Kb``; it is scheduled exactly when it carries
 ``"schedule"`` (then also ``"side_bytes"`` and marks by ``"stage"``).  Embedded streams, marks, counts and mark bytes are
 those of ``base_lanes=1``.  z and the base are needed whole: a string that ends early is a ValueError at the decoder.
+
+A **codestream**  is one container as ONE byte string whose every prefix decodes: a preamble, a
+little-endian header with a CRC-32, z and the base whole, then the embedded streams in rounds, one round per mark, every
+slice's bytes between two marks in slice order.  :func:`to_bytes` writes it, :func:`need_bytes`, :func:`layout` and
+:func:`from_bytes` read it on the host alone, and :class:`StreamDecoder` is a receiver that is fed raw chunks: it turns
+them into :meth:`EmbeddedDecoder.extend` calls by the header's arithmetic.  The containers and their coders are unchanged.
 """
 from __future__ import annotations
 
 import math
 import os
 import pickle
+import struct
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
@@ -459,6 +467,319 @@ def delta(longer, shorter) -> List[bytes]:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ codestreams (section 9u)
+STREAM_MAGIC = b"VAMe"
+STREAM_VERSION = 1
+_PREAMBLE = struct.Struct("<4sHHII")       # magic, version, reserved (0), bytes of the header, CRC-32 of the header
+PREAMBLE_BYTES = _PREAMBLE.size            # 16
+_FIXED = struct.Struct("<BBBBHHHHI")       # format digit, flags, lanes, base_lanes, shape[0], shape[1], ns, L, bytes of z
+_FLAG_SCHEDULED = 1
+_MAX_HEADER = 1 << 24                      # far above any header: 32 marks of 65535 slices stay below it
+
+
+def _format_of(K: int, Kb: int, scheduled: bool) -> str:
+    """The format name encode_batch gives a container of these lanes, base lanes and order."""
+    return FORMAT_BASE_LANES if Kb > 1 else FORMAT_SCHEDULED if scheduled else FORMAT_LANES if K > 1 else FORMAT
+
+
+def _u32_table(rows, L: int, ns: int, what: str) -> np.ndarray:
+    try:
+        a = np.asarray(rows, dtype=np.int64)
+    except (TypeError, ValueError, OverflowError) as e:
+        raise ValueError(f"to_bytes: the marks' {what} are integers [{L}][{ns}]") from e
+    if a.shape != (L, ns) or (a < 0).any() or (a >= 1 << 32).any():
+        raise ValueError(f"to_bytes: the marks' {what} are integers [{L}][{ns}] in 0 .. 2^32 - 1, got shape {list(a.shape)}")
+    return a
+
+
+def to_bytes(container) -> bytes:
+    """One UNCUT container of any embedded format as one codestream: preamble, header, z, the ns base
+    strings, then the embedded streams in rounds — round k holds, slice by slice, the bytes between mark k - 1 and mark k,
+    a last round what follows the last mark.  Every prefix of the result from :func:`need_bytes` on is a container
+    (:func:`from_bytes`), and ``from_bytes(to_bytes(c))`` equals ``c`` entry by entry.  Host only.  ValueError for a cut
+    container (an embedded string shorter than its last mark's bytes) and for one the format cannot carry."""
+    K = _check_container(container)
+    c = container
+    Kb, scheduled = _base_lanes(c), _scheduled(c)
+    if _format_of(K, Kb, scheduled) != c["format"]:
+        raise ValueError(f"to_bytes: lanes {K}, base_lanes {Kb}{', a schedule' if scheduled else ''} are format "
+                         f"{_format_of(K, Kb, scheduled)!r}, this container says {c['format']!r}")
+    keys = {"format", "shape", "z", "base", "embedded", "marks"} | ({"lanes"} if c["format"] != FORMAT else set()) \
+        | ({"base_lanes"} if Kb > 1 else set()) | ({"schedule", "side_bytes"} if scheduled else set())
+    if set(c) != keys:
+        raise ValueError(f"to_bytes: an {c['format']!r} container{' with a schedule' if scheduled else ''} has the keys "
+                         f"{sorted(keys)}, this one has {sorted(c, key=str)}")
+    try:
+        s0, s1 = (int(v) for v in c["shape"])
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"to_bytes: shape is (H / 64, W / 64), got {c['shape']!r}") from e
+    if tuple(c["shape"]) != (s0, s1) or not (1 <= s0 <= 0xFFFF and 1 <= s1 <= 0xFFFF):
+        raise ValueError(f"to_bytes: shape is (H / 64, W / 64) with entries in 1 .. 65535, got {c['shape']!r}")
+    isb = lambda s: isinstance(s, (bytes, bytearray, memoryview))
+    emb, z, base = c["embedded"], c["z"], c["base"]
+    if not isinstance(emb, (list, tuple)) or not 1 <= len(emb) <= 0xFFFF or not all(isb(s) for s in emb):
+        raise ValueError("to_bytes: \"embedded\" is a list of 1 .. 65535 bytes objects")
+    ns = len(emb)
+    if not isinstance(z, (list, tuple)) or len(z) != 1 or not isb(z[0]):
+        raise ValueError("to_bytes: \"z\" is a list of one bytes object")
+    if not isinstance(base, (list, tuple)) or len(base) != ns or not all(isinstance(s, (list, tuple)) and len(s) == 1 and isb(s[0])
+                                                                          for s in base):
+        raise ValueError(f"to_bytes: \"base\" is a list of {ns} lists of one bytes object each")
+    lens = np.asarray([len(z[0])] + [len(s[0]) for s in base] + [len(s) for s in emb], dtype=np.int64)
+    if (lens >= 1 << 32).any():
+        raise ValueError("to_bytes: a string of 2^32 bytes or more does not fit the header's length fields")
+    marks = c["marks"]
+    by = "stage" if scheduled else "q"
+    if not isinstance(marks, dict) or set(marks) != {by, "count", "bytes"}:
+        raise ValueError(f"to_bytes: the marks of this container are a dict of \"{by}\", \"count\" and \"bytes\"")
+    try:
+        vals = [int(v) if scheduled else float(v) for v in marks[by]]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"to_bytes: the marks' \"{by}\" is a list of numbers") from e
+    L = len(vals)
+    if not 1 <= L <= 0xFFFF or (scheduled and (vals != list(marks[by]) or min(vals) < 0 or max(vals) >= 1 << 32)):
+        raise ValueError(f"to_bytes: 1 .. 65535 marks{', stages as integers in 0 .. 2^32 - 1' if scheduled else ''}, got {marks[by]!r}")
+    count, cut = _u32_table(marks["count"], L, ns, "counts"), _u32_table(marks["bytes"], L, ns, "bytes")
+    down = np.argwhere(np.diff(cut, axis=0) < 0)
+    if len(down):
+        raise ValueError(f"to_bytes: slice {int(down[0][1])}: the bytes of mark {int(down[0][0]) + 1} lie below those of the mark "
+                         "before; marks never decrease")
+    short = np.flatnonzero(cut[-1] > lens[1 + ns:])
+    if short.size:
+        j = int(short[0])
+        raise ValueError(f"to_bytes: slice {j} holds {int(lens[1 + ns + j])} bytes, its last mark needs {int(cut[-1, j])}: the "
+                         "container was cut; a codestream is made from the uncut container and cut as bytes")
+    parts = [_FIXED.pack(_FORMATS.index(c["format"]) + 1, _FLAG_SCHEDULED if scheduled else 0, K, Kb, s0, s1, ns, L, int(lens[0])),
+             lens[1:].astype("<u4").tobytes(), np.asarray(vals, dtype="<u4" if scheduled else "<f8").tobytes(),
+             count.astype("<u4").tobytes(), cut.astype("<u4").tobytes()]
+    if scheduled:
+        sc = c["schedule"]
+        try:
+            lv, ix = np.asarray(sc["levels"], dtype=np.float64).reshape(-1), np.asarray(sc["index"])
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError("to_bytes: the schedule is {\"levels\": floats, \"index\": uint8 [stages, H / 16, W / 16]}") from e
+        if ix.dtype != np.uint8 or ix.ndim != 3 or ix.shape[1:] != (4 * s0, 4 * s1) or not 1 <= ix.shape[0] <= 0xFFFF \
+                or not 1 <= lv.size <= 0xFFFF:
+            raise ValueError(f"to_bytes: the schedule's index is uint8 [stages, {4 * s0}, {4 * s1}] beside 1 .. 65535 levels, got "
+                             f"{ix.dtype} {list(ix.shape)} and {lv.size} levels")
+        if c["side_bytes"] != 8 * lv.size + ix.size:
+            raise ValueError(f"to_bytes: side_bytes is 8 per level and 1 per index entry, {8 * lv.size + ix.size}, got {c['side_bytes']!r}")
+        parts += [struct.pack("<HH", lv.size, ix.shape[0]), lv.astype("<f8").tobytes(), np.ascontiguousarray(ix).tobytes()]
+    hlen = sum(len(p) for p in parts) + 8
+    if hlen > _MAX_HEADER:
+        raise ValueError(f"to_bytes: the header would take {hlen} bytes, the limit is {_MAX_HEADER}")
+    parts.append(struct.pack("<Q", PREAMBLE_BYTES + hlen + int(lens.sum())))
+    header = b"".join(parts)
+    out = [_seal(header), bytes(z[0])] + [bytes(s[0]) for s in base]
+    edge = np.concatenate([np.zeros((1, ns), dtype=np.int64), cut, lens[None, 1 + ns:]])
+    out += [bytes(emb[j][int(edge[k, j]):int(edge[k + 1, j])]) for k in range(L + 1) for j in range(ns)]
+    return b"".join(out)
+
+
+def _seal(header: bytes) -> bytes:
+    """The preamble of ``header`` and the header: magic, version, its length and its CRC-32."""
+    return _PREAMBLE.pack(STREAM_MAGIC, STREAM_VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF) + header
+
+
+class _Stream:
+    """A parsed codestream header: the fields, and the byte arithmetic of the body that follows from them."""
+
+    def __init__(self, d, what: str):
+        """Parses ``d`` (a memoryview that holds at least the header, as :func:`_header_end` says).  ValueError names what
+        is wrong; nothing beyond the stated header length is read."""
+        from . import bitstream as bs
+        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
+        end = PREAMBLE_BYTES + hlen
+        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
+            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        self.header_end, at = end, PREAMBLE_BYTES
+
+        def take(dtype, n):
+            nonlocal at
+            size = n * np.dtype(dtype).itemsize
+            if at + size > end:
+                raise ValueError(f"{what}: the header's fields need more than its stated {hlen} bytes: it contradicts itself")
+            a = np.frombuffer(d, dtype=dtype, count=n, offset=at)
+            at += size
+            return a
+        digit, flags, K, Kb, s0, s1, ns, L, z_len = _FIXED.unpack_from(d, at)      # hlen >= _FIXED.size + 8 (_header_end)
+        at += _FIXED.size
+        if not 1 <= digit <= len(_FORMATS) or flags & ~_FLAG_SCHEDULED:
+            raise ValueError(f"{what}: format digit {digit} and flags {flags:#x}: not a header of version {STREAM_VERSION}")
+        self.format, self.scheduled = _FORMATS[digit - 1], bool(flags & _FLAG_SCHEDULED)
+        for name, v in (("lanes", K), ("base_lanes", Kb)):
+            try:
+                bs.check_lanes(v)
+            except ValueError as e:
+                raise ValueError(f"{what}: the header's {name}: {e}") from e
+        if _format_of(K, Kb, self.scheduled) != self.format:
+            raise ValueError(f"{what}: the header contradicts itself: lanes {K}, base_lanes {Kb}"
+                             f"{', scheduled' if self.scheduled else ''} are format {_format_of(K, Kb, self.scheduled)!r}, it says "
+                             f"{self.format!r}")
+        if not (s0 and s1 and ns and L):
+            raise ValueError(f"{what}: the header contradicts itself: shape ({s0}, {s1}), {ns} slices and {L} marks, none may be 0")
+        self.lanes, self.base_lanes, self.shape, self.ns, self.L = K, Kb, (s0, s1), ns, L
+        lens = take("<u4", 2 * ns).astype(np.int64)
+        self.z_len, self.base_len, self.emb_len = z_len, lens[:ns], lens[ns:]
+        self.values = [int(v) for v in take("<u4", L)] if self.scheduled else [float(v) for v in take("<f8", L)]
+        self.count = take("<u4", L * ns).astype(np.int64).reshape(L, ns)
+        self.cut = take("<u4", L * ns).astype(np.int64).reshape(L, ns)
+        self.schedule = None
+        if self.scheduled:
+            n_lv, n_st = (int(v) for v in take("<u2", 2))
+            if not (n_lv and n_st):
+                raise ValueError(f"{what}: the header contradicts itself: a schedule of {n_lv} levels and {n_st} stages, none may be 0")
+            lv = take("<f8", n_lv)
+            self.schedule = {"levels": [float(v) for v in lv], "index": take("u1", n_st * 16 * s0 * s1).reshape(n_st, 4 * s0, 4 * s1).copy()}
+            self.side_bytes = 8 * n_lv + n_st * 16 * s0 * s1
+        self.total = int(take("<u8", 1)[0])
+        if at != end:
+            raise ValueError(f"{what}: the header's fields take {at - PREAMBLE_BYTES} of its stated {hlen} bytes: it contradicts itself")
+        down = np.argwhere(np.diff(self.cut, axis=0) < 0)
+        if len(down):
+            k, j = int(down[0][0]) + 1, int(down[0][1])
+            raise ValueError(f"{what}: the header contradicts itself: slice {j}: the bytes of mark {k}, {int(self.cut[k, j])}, lie "
+                             f"below those of mark {k - 1}, {int(self.cut[k - 1, j])}")
+        beyond = np.flatnonzero(self.cut[-1] > self.emb_len)
+        if beyond.size:
+            j = int(beyond[0])
+            raise ValueError(f"{what}: the header contradicts itself: slice {j}: its last mark, {int(self.cut[-1, j])} bytes, lies "
+                             f"beyond its stream's length, {int(self.emb_len[j])}")
+        self.base_end = end + z_len + int(self.base_len.sum())
+        if self.base_end + int(self.emb_len.sum()) != self.total:
+            raise ValueError(f"{what}: the header contradicts itself: its lengths add up to {self.base_end + int(self.emb_len.sum())} "
+                             f"bytes, it states a total of {self.total}")
+        # the body: piece (k, j) = bytes edge[k][j] : edge[k + 1][j] of stream j, pieces in round-major order from base_end on
+        self.edge = np.concatenate([np.zeros((1, ns), dtype=np.int64), self.cut, self.emb_len[None]])
+        self.size = np.diff(self.edge, axis=0)                                   # [L + 1, ns]
+        ends = np.cumsum(self.size.reshape(-1))
+        self.start = (ends - self.size.reshape(-1)).reshape(L + 1, ns)           # offset of every piece in the body
+        self.round_end = [self.base_end + int(v) for v in ends.reshape(L + 1, ns)[:L, -1]]
+
+    def marks(self) -> dict:
+        return {"stage" if self.scheduled else "q": list(self.values), "count": [[int(v) for v in row] for row in self.count],
+                "bytes": [[int(v) for v in row] for row in self.cut]}
+
+    def slice_lengths(self, n: int) -> np.ndarray:
+        """int64 [ns]: the bytes of every embedded stream that the first ``n`` >= base_end bytes of the codestream hold."""
+        return np.clip(n - self.base_end - self.start, 0, self.size).sum(0)
+
+    def slices(self, d, lo, hi) -> List[bytes]:
+        """Per slice j, bytes lo[j] : hi[j] of embedded stream j, gathered from the codestream ``d`` (which must hold them)."""
+        out = []
+        for j in range(self.ns):
+            a, b, parts = int(lo[j]), int(hi[j]), []
+            for k in range(self.L + 1) if a < b else ():
+                s, e = int(self.edge[k, j]), int(self.edge[k + 1, j])
+                u, v = max(s, a), min(e, b)
+                if u < v:
+                    off = self.base_end + int(self.start[k, j]) - s
+                    parts.append(d[off + u:off + v])
+            out.append(b"".join(parts))
+        return out
+
+    def same_batch(self, o) -> Optional[str]:
+        """What keeps this image and ``o`` out of one decoder, or None."""
+        for name, a, b in (("shape", self.shape, o.shape), ("lanes", self.lanes, o.lanes), ("base_lanes", self.base_lanes, o.base_lanes),
+                           ("slice count", self.ns, o.ns)):
+            if a != b:
+                return f"its {name} is {a}, the others' {b}"
+        if self.scheduled != o.scheduled:
+            return "it is " + ("scheduled, the others are plain" if self.scheduled else "plain, the others are scheduled")
+        if self.scheduled and self.schedule["index"].shape[0] != o.schedule["index"].shape[0]:
+            return f"it has {self.schedule['index'].shape[0]} stages, the others {o.schedule['index'].shape[0]}"
+        return None
+
+
+def _view(data, what: str):
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError(f"{what}: a codestream is a bytes-like object, got {type(data).__name__}")
+    d = memoryview(data)
+    return d if d.format == "B" and d.ndim == 1 and d.contiguous else memoryview(bytes(d))
+
+
+def _header_end(d, what: str) -> Optional[int]:
+    """The byte at which the header of ``d`` ends, read from its preamble; None while the preamble is incomplete.  A wrong
+    magic, version or header length is a ValueError."""
+    if len(d) < PREAMBLE_BYTES:
+        return None
+    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
+    if magic != STREAM_MAGIC:
+        raise ValueError(f"{what}: not an embedded codestream: it begins with {bytes(magic)!r}, not with the magic {STREAM_MAGIC!r}")
+    if version != STREAM_VERSION or reserved:
+        raise ValueError(f"{what}: codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this reader knows "
+                         f"version {STREAM_VERSION}")
+    if not _FIXED.size + 8 <= hlen <= _MAX_HEADER:
+        raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 8} .. {_MAX_HEADER}")
+    return PREAMBLE_BYTES + hlen
+
+
+def _parse(data, what: str):
+    """(view, parsed header) of a codestream that holds its whole header; too few bytes are a ValueError with the need."""
+    d = _view(data, what)
+    end = _header_end(d, what)
+    if end is None or len(d) < end:
+        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
+                         "before it can be read")
+    return d, _Stream(d, what)
+
+
+def need_bytes(data) -> int:
+    """The smallest length from which :func:`from_bytes` succeeds on this codestream, as far as ``data`` (any prefix of it)
+    tells: the preamble's size while that is incomplete, the header's end while the header is, then the end of the base.
+    A damaged preamble or header is a ValueError."""
+    d = _view(data, "need_bytes")
+    end = _header_end(d, "need_bytes")
+    if end is None:
+        return PREAMBLE_BYTES
+    return end if len(d) < end else _Stream(d, "need_bytes").base_end
+
+
+def layout(data) -> dict:
+    """Where a codestream may be cut, from its header alone (``data``: any prefix that holds the header): ``header_end``,
+    ``base_end`` (the least a decoder needs), ``round_end[k]`` (the prefix that is ``truncate`` at mark k), ``total``, and the
+    ``marks``, ``lanes``, ``base_lanes``, ``shape``, ``format``, ``ns`` and ``scheduled`` of the container."""
+    _, s = _parse(data, "layout")
+    return {"header_end": s.header_end, "base_end": s.base_end, "round_end": list(s.round_end), "total": s.total, "marks": s.marks(),
+            "lanes": s.lanes, "base_lanes": s.base_lanes, "shape": s.shape, "format": s.format, "ns": s.ns, "scheduled": s.scheduled}
+
+
+def _container_of(s: "_Stream", d, n: int) -> dict:
+    """The container that the first ``n`` bytes of codestream ``d`` hold (base_end <= n <= total, checked by the caller)."""
+    at, strings = s.header_end, []
+    for ln in [s.z_len] + [int(v) for v in s.base_len]:
+        strings.append(bytes(d[at:at + ln]))
+        at += ln
+    c = {"format": s.format, "shape": s.shape, "z": [strings[0]], "base": [[b] for b in strings[1:]],
+         "embedded": s.slices(d, np.zeros(s.ns, dtype=np.int64), s.slice_lengths(n)), "marks": s.marks()}
+    if s.format != FORMAT:
+        c["lanes"] = s.lanes
+    if s.scheduled:
+        c["schedule"], c["side_bytes"] = {"levels": list(s.schedule["levels"]), "index": s.schedule["index"].copy()}, s.side_bytes
+    if s.base_lanes > 1:
+        c["base_lanes"] = s.base_lanes
+    return c
+
+
+def _check_length(s: "_Stream", n: int, what: str):
+    if n < s.base_end:
+        raise ValueError(f"{what}: {n} bytes end before z and the base do: {s.base_end} bytes are needed, they are decoded whole")
+    if n > s.total:
+        raise ValueError(f"{what}: {n} bytes, the header states a total of {s.total}: {n - s.total} bytes follow the codestream")
+
+
+def from_bytes(data) -> dict:
+    """The container that ``data`` holds: any prefix of a codestream of :func:`need_bytes` bytes or more.  Its embedded
+    strings are prefixes of the original's and their lengths sum to ``len(data) - base_end`` — every byte received is used:
+    a prefix that ends inside round k gives the earlier slices round k, the later ones round k - 1, and cuts one slice in
+    mid-piece, which the tolerant decoder accepts.  The whole codestream gives the container it was made from, entry by
+    entry.  Host only; the decoder trusts nothing: a wrong magic or version, a CRC mismatch, a header that contradicts
+    itself, bytes beyond the total and too few bytes (with the number needed) are each a ValueError."""
+    d, s = _parse(data, "from_bytes")
+    _check_length(s, len(d), "from_bytes")
+    return _container_of(s, d, len(d))
+
+
 class EmbeddedDecoder:
     """Decodes a batch of embedded containers of one shape, whole or truncated, each image cut at its own place.  The base
     slices and the progressive (mu, sigma) chain run once, the rank order comes from the decoder's own sigma, and the
@@ -813,3 +1134,125 @@ class EmbeddedDecoder:
                                                       [int(count[0, bj[0], bj[1]])], tg, lanes=self.lanes)[0],
                            [(b, j) for b in range(self.B) for j in range(ns)])
         return [fixed[b] + 8.0 * sum(cut[b * ns:(b + 1) * ns]) for b in range(self.B)]
+
+
+class StreamDecoder:
+    """A receiver of codestreams: ``n_images`` images of one batch, each arriving as raw bytes in chunks
+    that may end anywhere — inside the header, inside a word.  :meth:`feed` keeps every image's bytes and parses its header
+    as soon as it is complete; when ALL images hold z and the base whole it builds one
+    ``EmbeddedDecoder(model, [from_bytes(...)], coder, resumable=True)``, and from then on every feed turns the new bytes into
+    per-slice deltas by the header's arithmetic (no transmitter-side :func:`delta`) and calls
+    :meth:`EmbeddedDecoder.extend`: nothing is entropy-decoded twice.  After any sequence of feeds :meth:`decode`,
+    :meth:`available` and the inner decoder equal, bit for bit, a fresh ``EmbeddedDecoder`` on ``from_bytes`` of everything
+    fed so far, on both coders.  The images must agree in shape, lanes, base_lanes, schedule-or-not and stage count; the one
+    that does not is refused, by its number, at the feed that completes its header.  A refused feed changes nothing: it is
+    checked as a whole before anything is kept, and when the feed that completes z and the base makes ``EmbeddedDecoder``
+    raise (a damaged base string, a coder status) its bytes are dropped again, so the decoder stays not ready and says so.
+    Only :meth:`EmbeddedDecoder.extend` of a ready decoder keeps the bytes it was handed when it raises a coder status, as it
+    does on its own."""
+
+    def __init__(self, model, n_images: int, coder: Optional[str] = None):
+        _check_model(model)
+        if isinstance(n_images, bool) or not isinstance(n_images, (int, np.integer)) or n_images < 1:
+            raise ValueError(f"StreamDecoder: n_images is an integer >= 1, got {n_images!r}")
+        self.m, self.B, self.coder = model, int(n_images), P._check_coder(model, coder)
+        self._buf = [bytearray() for _ in range(self.B)]
+        self._hdr: List[Optional[_Stream]] = [None] * self.B
+        self._held: List[Optional[np.ndarray]] = [None] * self.B      # per image the bytes of every slice the inner decoder holds
+        self.decoder: Optional[EmbeddedDecoder] = None
+        self.extend_bytes = 0                               # payload bytes the last feed handed to the coder
+
+    @property
+    def ready(self) -> bool:
+        """Whether every image held z and the base at the last feed: there is a picture to decode."""
+        return self.decoder is not None
+
+    def need(self) -> List[int]:
+        """Per image the bytes it still lacks before the first picture, as far as its bytes tell (:func:`need_bytes`)."""
+        return [max(0, (h.base_end if h is not None else need_bytes(bytes(b))) - len(b)) for h, b in zip(self._hdr, self._buf)]
+
+    def feed(self, chunks) -> Optional[np.ndarray]:
+        """``chunks``: one bytes-like object per image, ``b""`` allowed, each the bytes that follow what the image was fed
+        before.  Returns :meth:`available`, or None while an image still lacks part of its header, z or base."""
+        try:
+            chunks = list(chunks)
+        except TypeError as e:
+            raise ValueError(f"StreamDecoder.feed: expected {self.B} bytes-like objects, one per image") from e
+        if len(chunks) != self.B:
+            raise ValueError(f"StreamDecoder.feed: expected {self.B} chunks, one per image, got {len(chunks)}")
+        for b, ch in enumerate(chunks):
+            if not isinstance(ch, (bytes, bytearray, memoryview)):
+                raise ValueError(f"StreamDecoder.feed: image {b}: expected bytes, got {type(ch).__name__}")
+        chunks = [_view(ch, "StreamDecoder.feed") for ch in chunks]             # bytes, whatever the item size of a memoryview
+        hdr, before = list(self._hdr), (list(self._hdr), [len(buf) for buf in self._buf])
+        for b, ch in enumerate(chunks):                     # everything is checked before anything is kept
+            if hdr[b] is None:
+                d = memoryview(bytes(self._buf[b]) + bytes(ch))
+                end = _header_end(d, f"StreamDecoder.feed: image {b}")
+                if end is not None and len(d) >= end:
+                    hdr[b] = _Stream(d, f"StreamDecoder.feed: image {b}")
+                    if hdr[b].ns != self.m.ns0:
+                        raise ValueError(f"StreamDecoder.feed: image {b}: its codestream holds {hdr[b].ns} slices, a container of this "
+                                         f"model has {self.m.ns0}")
+                    other = next((h for a, h in enumerate(hdr) if h is not None and a != b), None)
+                    why = hdr[b].same_batch(other) if other is not None else None
+                    if why:
+                        raise ValueError(f"StreamDecoder.feed: image {b} does not belong to this batch: {why}; decode it separately")
+            if hdr[b] is not None and len(self._buf[b]) + len(ch) > hdr[b].total:
+                raise ValueError(f"StreamDecoder.feed: image {b}: {len(self._buf[b]) + len(ch)} bytes, its header states a total of "
+                                 f"{hdr[b].total}: bytes follow the codestream")
+        self._hdr = hdr
+        for buf, ch in zip(self._buf, chunks):
+            buf += ch
+        self.extend_bytes = 0
+        if any(h is None or len(buf) < h.base_end for h, buf in zip(hdr, self._buf)):
+            return None
+        now = [h.slice_lengths(len(buf)) for h, buf in zip(hdr, self._buf)]
+        if self.decoder is None:
+            views = [memoryview(buf) for buf in self._buf]
+            try:
+                cs = [_container_of(h, d, len(d)) for h, d in zip(hdr, views)]
+            finally:
+                for d in views:
+                    d.release()
+            try:
+                self.decoder = EmbeddedDecoder(self.m, cs, self.coder, resumable=True)
+            except Exception:                               # a damaged z or base, a coder status: this feed is not kept either
+                self._hdr = before[0]
+                for buf, n in zip(self._buf, before[1]):
+                    del buf[n:]
+                raise
+            self._held = now
+            self.extend_bytes = self.decoder.extend_bytes
+        elif any((a != b).any() for a, b in zip(now, self._held)):
+            views = [memoryview(buf) for buf in self._buf]
+            try:
+                more = [h.slices(d, lo, hi) for h, d, lo, hi in zip(hdr, views, self._held, now)]
+            finally:
+                for d in views:
+                    d.release()
+            self._held = now                                # extend keeps the bytes even when it raises a coder status
+            self.decoder.extend(more)
+            self.extend_bytes = self.decoder.extend_bytes
+        return self.available()
+
+    def available(self) -> Optional[np.ndarray]:
+        """int [B][ns] as :meth:`EmbeddedDecoder.available`; None while not ready."""
+        return self.decoder.available() if self.ready else None
+
+    def _inner(self, what: str) -> "EmbeddedDecoder":
+        if not self.ready:
+            need = self.need()
+            b = next((k for k, v in enumerate(need) if v), 0)
+            raise ValueError(f"StreamDecoder.{what}: nothing to decode yet: image {b} lacks {need[b]} bytes of its header, z "
+                             "and base")
+        return self.decoder
+
+    def decode(self) -> dict:
+        return self._inner("decode").decode()
+
+    def decode_stages(self, ks: Sequence[int]) -> List[dict]:
+        return self._inner("decode_stages").decode_stages(ks)
+
+    def decode_qualities(self, qs: Sequence[float]) -> List[dict]:
+        return self._inner("decode_qualities").decode_qualities(qs)

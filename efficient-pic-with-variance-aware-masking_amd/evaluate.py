@@ -425,6 +425,52 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
     return rows
 
 
+def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
+                       base_lanes: int = 1):
+    """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE
+    shape are padded and coded as one batch, once; every image's codestream is cut at ``data[:n]`` for each n of
+    ``byte_budgets`` (ascending; every n at least the largest ``need_bytes`` of the batch, a ValueError says which is not)
+    and ONE embedded.StreamDecoder is fed from budget to budget.  One dict per budget, with a list per image: "budget",
+    "bytes" (min(n, the image's total): all of them are decoded), "bpp" (8 * bytes / pixels of the original image), "psnr"
+    (of the cropped decode) and "available" (decoded elements); beside them what ``truncate(container, max_bytes=n)`` makes
+    of the same n — "truncate_bytes" (z, base and the embedded bytes of the largest mark that fits; it counts no header),
+    "unused" (n - truncate_bytes, the slack a mark leaves) and "truncate_psnr" — and "header_bytes" of the codestream."""
+    from . import embedded as EB
+    images = [x if x.dim() == 4 else x.unsqueeze(0) for x in images]
+    budgets = [int(n) for n in byte_budgets]
+    if not budgets or any(b < a for a, b in zip(budgets, budgets[1:])):
+        raise ValueError(f"embedded_stream_rd: byte_budgets are one or more byte counts in ascending order, got {list(byte_budgets)}")
+    if len({tuple(x.shape[1:]) for x in images}) != 1 or any(x.shape[0] != 1 for x in images):
+        raise ValueError("embedded_stream_rd: the images of one call are single images of one shape")
+    rows = []
+    with torch.no_grad():
+        xp, unpad = pad_image(torch.cat(images, 0))
+        cs = EB.encode_batch(model, xp, coder=coder, lanes=lanes, base_lanes=base_lanes)
+        data = [EB.to_bytes(c) for c in cs]
+        lay = [EB.layout(d) for d in data]
+        need = max(v["base_end"] for v in lay)
+        if budgets[0] < need:
+            raise ValueError(f"embedded_stream_rd: a budget of {budgets[0]} bytes decodes nothing: {need} bytes are needed for header, "
+                             "z and base")
+        pixels = [x.shape[2] * x.shape[3] for x in images]
+        psnr = lambda out: [compute_psnr(x, torch.nn.functional.pad(out["x_hat"], unpad)[i:i + 1]) for i, x in enumerate(images)]
+        dec, sent, marked = EB.StreamDecoder(model, len(images), coder=coder), [0] * len(images), {}
+        for n in budgets:
+            upto = [min(n, v["total"]) for v in lay]
+            avail = dec.feed([d[a:b] for d, a, b in zip(data, sent, upto)])
+            sent = upto
+            row = {"budget": n, "bytes": upto, "bpp": [8.0 * b / p for b, p in zip(upto, pixels)], "psnr": psnr(dec.decode()),
+                   "available": [int(v) for v in avail.sum(1)], "header_bytes": [v["header_end"] for v in lay]}
+            cut = [EB.truncate(c, max_bytes=n) for c in cs]
+            key = tuple(len(s) for c in cut for s in c["embedded"])
+            if key not in marked:                           # budgets that buy the same marks share one decode
+                marked[key] = psnr(EB.EmbeddedDecoder(model, cut, coder=coder).decode())
+            row.update(truncate_bytes=[sum(EB.container_bytes(c)) for c in cut], truncate_psnr=marked[key])
+            row["unused"] = [n - v for v in row["truncate_bytes"]]
+            rows.append(row)
+    return rows
+
+
 def roi_schedule(B: int, H: int, W: int, boxes, roi_qualities: Sequence[float], background_qualities: Sequence[float]):
     """A region-of-interest schedule for embedded.encode_batch(schedule=...): a list of latent quality
     maps [B, H/16, W/16].  ``boxes``: pixel boxes ``(b, y0, x0, y1, x1)`` of the region.  First the region climbs through

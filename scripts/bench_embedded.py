@@ -36,8 +36,15 @@ image.  In the same run the layered container's device front end — ``progressi
 Kb, a LANE-SPLIT base (section 9o) — is timed at every Kb, which puts the two lane formats side by side.  x_hat of every
 level is asserted identical across all cells; no time is asserted.
 
+``--stream S`` measures the same receiver fed one byte string per image: every codestream
+(``embedded.to_bytes``) is cut into S steps, the first up to an S-th of its body, the others an S-th of the body each.  Per
+(coder, lanes) cell three paths alternate on the same prefixes: (a) a fresh EmbeddedDecoder on ``from_bytes`` of every
+prefix, (b) one resumable decoder with ``delta`` + ``extend``, (c) one ``StreamDecoder`` and ``feed`` of the raw bytes; each
+step ends with ``decode()``.  (c) - (b) per step is what the framing costs a receiver.  x_hat of every step is asserted
+identical across the three; no time is asserted.
+
     python scripts/bench_embedded.py [--warmup 1] [--reps 3] [--coder host device] [--lanes 1 8 64]
-                                     [--schedule roi | --resume S | --base-lanes 1 8 64]
+                                     [--schedule roi | --resume S | --stream S | --base-lanes 1 8 64]
 """
 import argparse
 import json
@@ -190,6 +197,69 @@ def resume_main(a, net, dev):
     print(json.dumps(res))
 
 
+def stream_main(a, net, dev):
+    """--stream S: every image's codestream received in S byte steps; fresh decoder per step (a), delta + extend (b) and
+    StreamDecoder.feed of the raw bytes (c) on the same prefixes, interleaved; prints one JSON line."""
+    import vampic
+    from vampic import bitstream as bs, embedded as EB
+    S = a.stream
+    res = {"metric": "receiving a codestream in steps: fresh decoder per step (a) vs delta + extend (b) vs StreamDecoder.feed (c) "
+                     "(ms, median)", "device": torch.cuda.get_device_name(0), "coder_threads": bs.coder_threads(), "warmup": a.warmup,
+           "reps": a.reps, "steps": S, "cases": {}}
+    for case, B, H, W in (("1x512x768", 1, 512, 768), ("8x256x256", 8, 256, 256)):
+        x = vampic.synth.synth_image(B, H, W, seed=0).to(dev)
+        out = {}
+        with torch.no_grad():
+            for c in a.coder:
+                for K in a.lanes:
+                    cs = EB.encode_batch(net, x, coder=c, lanes=K)
+                    data = [EB.to_bytes(c_) for c_ in cs]
+                    lay = [EB.layout(d) for d in data]
+                    cuts = [[v["base_end"] + (v["total"] - v["base_end"]) * i // S for v in lay] for i in range(1, S + 1)]
+                    t0 = time.perf_counter()
+                    prefixes = [[EB.from_bytes(d[:n]) for d, n in zip(data, row)] for row in cuts]
+                    demux_ms = 1e3 * (time.perf_counter() - t0) / S
+                    more = [None] + [[EB.delta(now, held) for now, held in zip(prefixes[i], prefixes[i - 1])] for i in range(1, S)]
+                    chunks = [[d[(cuts[i - 1][b] if i else 0):cuts[i][b]] for b, d in enumerate(data)] for i in range(S)]
+                    t = {f"{p}_ms": [[] for _ in range(S)] for p in ("fresh", "extend", "feed")}
+                    for r in range(a.warmup + a.reps):
+                        hats = {}
+                        for path in ("fresh", "extend", "feed"):
+                            dec = None
+                            for i in range(S):
+                                torch.cuda.synchronize()
+                                t0 = time.perf_counter()
+                                if path == "fresh":
+                                    dec = EB.EmbeddedDecoder(net, prefixes[i], coder=c)
+                                elif path == "extend":
+                                    if i == 0:
+                                        dec = EB.EmbeddedDecoder(net, prefixes[0], coder=c, resumable=True)
+                                    else:
+                                        dec.extend(more[i])
+                                else:
+                                    dec = EB.StreamDecoder(net, B, coder=c) if i == 0 else dec
+                                    dec.feed(chunks[i])
+                                x_hat = dec.decode()["x_hat"]
+                                torch.cuda.synchronize()
+                                if r >= a.warmup:
+                                    t[f"{path}_ms"][i].append(1e3 * (time.perf_counter() - t0))
+                                hats[path, i] = x_hat
+                        for i in range(S):
+                            assert torch.equal(hats["fresh", i], hats["extend", i]) and torch.equal(hats["fresh", i], hats["feed", i]), \
+                                f"{case}: {c} K={K}: x_hat of step {i} differs"
+                    med = {k: [round(statistics.median(v), 2) for v in rows] for k, rows in t.items()}
+                    med.update({f"{k}_total": round(sum(v), 2) for k, v in list(med.items())})
+                    med.update(x_hat_identical=True, from_bytes_ms_per_prefix=round(demux_ms, 3), header_bytes=lay[0]["header_end"],
+                               stream_bytes_per_image=round(sum(len(d) for d in data) / B, 1),
+                               feed_minus_extend_ms_per_step=round((med["feed_ms_total"] - med["feed_ms"][0]
+                                                                    - med["extend_ms_total"] + med["extend_ms"][0]) / (S - 1), 3))
+                    out[f"{c}_k{K}"] = med
+        res["cases"][case] = out
+        net._drop_plans()
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
 def base_lanes_main(a, net, dev):
     """--base-lanes: an interleaved base on Kb lanes against the K = 1 base, cells interleaved; prints one JSON line."""
     import vampic
@@ -293,6 +363,7 @@ def main():
     ap.add_argument("--schedule", choices=["roi"], default=None)
     ap.add_argument("--resume", type=int, default=None, metavar="S")
     ap.add_argument("--base-lanes", nargs="+", type=int, default=None, metavar="Kb")
+    ap.add_argument("--stream", type=int, default=None, metavar="S")
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -300,8 +371,12 @@ def main():
     dev = torch.device("cuda:0")
     net, _ = build_model(dev)
     net.update()
-    if sum(v is not None for v in (a.schedule, a.resume, a.base_lanes)) > 1:
-        ap.error("--schedule, --resume and --base-lanes measure different things: give one")
+    if sum(v is not None for v in (a.schedule, a.resume, a.base_lanes, a.stream)) > 1:
+        ap.error("--schedule, --resume, --stream and --base-lanes measure different things: give one")
+    if a.stream is not None:
+        if a.stream < 2:
+            ap.error("--stream takes S >= 2 steps")
+        return stream_main(a, net, dev)
     if a.base_lanes is not None:
         return base_lanes_main(a, net, dev)
     if a.schedule:
