@@ -321,6 +321,10 @@ _SIGNATURES = {
                                   C.c_void_p]),
     "vam_rank_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_tile_extract": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "vam_tile_blend": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vam_graph_begin": (C.c_int, [C.c_void_p]),
     "vam_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "vam_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,0 +1,259 @@
+// Tiled pictures (vampic.tiled): cutting overlapping tiles out of a picture of any size and blending
+// decoded tiles back into a window of it.
+//
+// Geometry (one definition for the host, these kernels and tests/tiled_ref.py): tiles of th x tw, overlap V with
+// 2 V <= min(th, tw), strides Sy = th - V and Sx = tw - V, grid R = max(1, ceil((H - V) / Sy)) by C likewise; tile (r, c)
+// covers rows [r Sy, r Sy + th) and columns [c Sx, c Sx + tw).  At most two tiles overlap along an axis.
+//
+//   tile_extract_kernel   tile pixel (y, x) = image[:, clamp(r Sy + y, 0, H - 1), clamp(c Sx + x, 0, W - 1)]: the edge is
+//                         replicated.  One launch serves a list of (r, c); a thread moves four pixels of a row.
+//   tile_blend_kernel     output-centric: a thread owns four consecutive pixels of one row of the window and all three
+//                         channels.  Along an axis the pixel P lies in tile t1 = min(n - 1, P / S) at l1 = P - t1 S and, when
+//                         t1 > 0 and l1 < V, in tile t1 - 1 too (the band): there t1 takes w_hi[l1] and t1 - 1 takes w_lo[l1]
+//                         from the host's tables, elsewhere the one tile has weight 1.  The pixel is the sum, over its tiles in
+//                         ascending r and within that ascending c, of (wy * wx) * v, every product and add one fp32
+//                         operation (__fmul_rn / __fadd_rn never contract), starting from the first term: outside the bands
+//                         it is the tile's value bit for bit.  No atomics, no division of floats, a fixed order.
+// Both move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
+// scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
+#include "common.h"
+#include <cstdint>
+
+namespace vam {
+namespace {
+
+constexpr int kTileMaxSide = 1 << 24;       // picture sides: every pixel index stays far inside a long
+
+struct TileGeom {
+  int H, W, th, tw, V, Sy, Sx, R, C;
+};
+
+int tile_geometry(const char* who, int H, int W, int th, int tw, int V, TileGeom* g) {
+  VAM_REQUIRE(H >= 1 && W >= 1 && H <= kTileMaxSide && W <= kTileMaxSide, "%s: a picture of %d x %d: sides are 1 .. %d", who, H, W,
+              kTileMaxSide);
+  VAM_REQUIRE(th >= 1 && tw >= 1 && th <= 65536 && tw <= 65536, "%s: tiles of %d x %d: sides are 1 .. 65536", who, th, tw);
+  VAM_REQUIRE(V >= 0 && 2 * (long)V <= (th < tw ? th : tw), "%s: overlap %d: need 0 <= 2 * overlap <= min(%d, %d)", who, V, th, tw);
+  g->H = H; g->W = W; g->th = th; g->tw = tw; g->V = V;
+  g->Sy = th - V; g->Sx = tw - V;
+  g->R = H - V > 0 ? (int)cdiv(H - V, g->Sy) : 1;
+  g->C = W - V > 0 ? (int)cdiv(W - V, g->Sx) : 1;
+  return VAM_OK;
+}
+
+struct ExtractArgs {
+  const float* image;
+  const int32_t* coords;
+  float* out;
+  TileGeom g;
+};
+
+__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+__global__ __launch_bounds__(256) void tile_extract_kernel(const ExtractArgs a) {
+  const TileGeom& g = a.g;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= g.tw || y >= g.th) return;
+  const int i = blockIdx.z;
+  const int r = a.coords[2 * i], c = a.coords[2 * i + 1];
+  if ((unsigned)r >= (unsigned)g.R || (unsigned)c >= (unsigned)g.C) return;      // not a tile of this grid: write nothing
+  const int nv = min(4, g.tw - x);
+  const int Y = min(r * g.Sy + y, g.H - 1), X = c * g.Sx + x;
+  const long plane = (long)g.H * g.W;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float* src = a.image + ch * plane + (long)Y * g.W;
+    float* dst = a.out + (((long)i * 3 + ch) * g.th + y) * g.tw + x;
+    float v[4];
+    if (X + 3 < g.W && aligned16(src + X)) {
+      const float4 q = *reinterpret_cast<const float4*>(src + X);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = src[min(X + k, g.W - 1)];
+    }
+    if (nv == 4 && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) dst[k] = v[k];
+    }
+  }
+}
+
+struct BlendArgs {
+  const float* tiles;
+  const int32_t* slot;
+  const float* w_lo;
+  const float* w_hi;
+  float* out_f;
+  uint8_t* out_u8;
+  int32_t* status;
+  TileGeom g;
+  int n, y0, x0, h, w;
+};
+
+// Where pixel P lies along an axis of n tiles with stride S: in tile t1 at l1, and when `two` in tile t1 - 1 at l1 + S.
+struct Axis {
+  int t1, l1;
+  bool two;
+};
+
+__device__ __forceinline__ Axis tile_axis(int P, int S, int V, int n) {
+  Axis a;
+  a.t1 = min(n - 1, P / S);
+  a.l1 = P - a.t1 * S;
+  a.two = a.t1 > 0 && a.l1 < V;
+  return a;
+}
+
+// NW pixels from column X on that share their column tiles (NW = 1: any pixel): acc[ch][k] by the rule above.
+template <int NW>
+__device__ __forceinline__ void blend_run(const BlendArgs& a, const Axis ay, const Axis ax, float (&acc)[3][4], int k0) {
+  const TileGeom& g = a.g;
+  bool started = false;
+#pragma unroll
+  for (int ry = 0; ry < 2; ++ry) {
+    if (!ry && !ay.two) continue;
+    const float wy = !ay.two ? 1.0f : ry ? a.w_hi[ay.l1] : a.w_lo[ay.l1];
+    const int r = ay.t1 - 1 + ry, ly = ay.l1 + (ry ? 0 : g.Sy);
+#pragma unroll
+    for (int cx = 0; cx < 2; ++cx) {
+      if (!cx && !ax.two) continue;
+      const int c = ax.t1 - 1 + cx, lx = ax.l1 + (cx ? 0 : g.Sx);
+      const int s = a.slot[r * g.C + c];
+      if ((unsigned)s >= (unsigned)a.n) {                  // the host checks beforehand: a guard, every writer stores the same 1
+        *a.status = 1;
+        continue;
+      }
+      float w[NW];
+#pragma unroll
+      for (int k = 0; k < NW; ++k) {
+        const float wx = !ax.two ? 1.0f : cx ? a.w_hi[ax.l1 + k] : a.w_lo[ax.l1 + k];
+        w[k] = __fmul_rn(wy, wx);
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float* p = a.tiles + (((long)s * 3 + ch) * g.th + ly) * g.tw + lx;
+        float v[4];
+        if (NW == 4 && aligned16(p)) {
+          const float4 q = *reinterpret_cast<const float4*>(p);
+          v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < NW; ++k) v[k] = p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+          const float t = __fmul_rn(w[k], v[k]);
+          acc[ch][k0 + k] = started ? __fadd_rn(acc[ch][k0 + k], t) : t;
+        }
+      }
+      started = true;
+    }
+  }
+  if (!started) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+      for (int k = 0; k < NW; ++k) acc[ch][k0 + k] = 0.0f;
+  }
+}
+
+__device__ __forceinline__ unsigned tile_u8(float v) { return (unsigned)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
+
+__global__ __launch_bounds__(256) void tile_blend_kernel(const BlendArgs a) {
+  const TileGeom& g = a.g;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= a.w || y >= a.h) return;
+  const int nv = min(4, a.w - x);
+  const int X = a.x0 + x;
+  const Axis ay = tile_axis(a.y0 + y, g.Sy, g.V, g.R);
+  const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
+  float acc[3][4];
+  bool run = false;
+  if (nv == 4) {
+    const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
+    run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;         // t1 never decreases and `two` only ends within a tile
+  }
+  if (run) {
+    blend_run<4>(a, ay, ax0, acc, 0);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < nv) blend_run<1>(a, ay, tile_axis(X + k, g.Sx, g.V, g.C), acc, k);
+  }
+  const long at = (long)y * a.w + x;
+  if (a.out_u8) {
+    uint8_t* dst = a.out_u8 + 3 * at;
+    unsigned b[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) b[3 * k + ch] = k < nv ? tile_u8(acc[ch][k]) : 0u;
+    if (nv == 4 && ((uintptr_t)dst & 3) == 0) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        reinterpret_cast<uint32_t*>(dst)[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j)
+        if (j < 3 * nv) dst[j] = (uint8_t)b[j];
+    }
+    return;
+  }
+  const long plane = (long)a.h * a.w;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float* dst = a.out_f + ch * plane + at;
+    if (nv == 4 && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) dst[k] = acc[ch][k];
+    }
+  }
+}
+
+}  // namespace
+}  // namespace vam
+
+using namespace vam;
+
+extern "C" {
+
+int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
+                     void* stream) {
+  ExtractArgs a;
+  if (int rc = tile_geometry("vam_tile_extract", H, W, th, tw, V, &a.g)) return rc;
+  VAM_REQUIRE(image && coords && out, "vam_tile_extract: need image, coords and out");
+  VAM_REQUIRE(n >= 1 && n <= 65535, "vam_tile_extract: 1 .. 65535 tiles per launch, got %d", n);
+  VAM_REQUIRE(cdiv(th, 4) <= 65535u, "vam_tile_extract: tiles of %d rows exceed one launch", th);
+  a.image = image; a.coords = coords; a.out = out;
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)n * th * tw * 24.0);
+  hipLaunchKernelGGL(tile_extract_kernel, dim3(cdiv(cdiv(tw, 4), 64), cdiv(th, 4), n), dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("tile_extract_kernel");
+}
+
+int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
+                   int tw, int V, int y0, int x0, int h, int w, void* out, int out_u8, int32_t* status, void* stream) {
+  BlendArgs a;
+  if (int rc = tile_geometry("vam_tile_blend", H, W, th, tw, V, &a.g)) return rc;
+  VAM_REQUIRE(tiles && slot && out && status, "vam_tile_blend: need tiles, slot, out and status");
+  VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_blend: an overlap of %d needs the two ramp tables", V);
+  VAM_REQUIRE(n >= 1, "vam_tile_blend: a buffer of %d tiles", n);
+  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && h <= H - y0 && w <= W - x0,
+              "vam_tile_blend: the window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", y0, x0, h, w, H, W);
+  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_blend: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
+  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_blend: a window of %d rows exceeds one launch", h);
+  a.tiles = tiles; a.slot = slot; a.w_lo = w_lo; a.w_hi = w_hi; a.status = status;
+  a.out_f = out_u8 ? nullptr : (float*)out;
+  a.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
+  a.n = n; a.y0 = y0; a.x0 = x0; a.h = h; a.w = w;
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
+  hipLaunchKernelGGL(tile_blend_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("tile_blend_kernel");
+}
+
+}  // extern "C"

@@ -425,6 +425,38 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
     return rows
 
 
+def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int = 256, overlap: int = 32, coder=None, lanes: int = 1,
+             base_lanes: int = 1, group: Optional[int] = None):
+    """:func:`embedded_rd` for ONE picture of any size coded in tiles (tiled.encode / PictureDecoder): the
+    picture, fp32 [3, H, W] or [1, 3, H, W], is coded ONCE with ``qualities`` (non-decreasing, as marks) as its marks, and
+    mark k is decoded from ``data[:round_end[k]]``, the prefix that holds every tile at exactly that mark.  One dict per
+    quality: q, bytes (``round_end[k]``: picture header, every tile's head and the rounds up to k), bpp (8 * bytes / (H W),
+    the true size), psnr against the original (:func:`compute_psnr`; nothing is padded or cropped), enc_s (the one encode) and
+    dec_s (parsing that prefix and decoding the whole picture at q).  Quality q keeps a quantile PER TILE, so these rows are
+    not those of the untiled forward; and nothing here measures the seams."""
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    qs = [float(q) for q in qualities]
+    rows = []
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        data = TL.encode(model, x, tile=tile, overlap=overlap, marks=qs, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        ends = TL.layout(data)["round_end"]
+        for k, q in enumerate(qs):
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            x_hat = TL.PictureDecoder(model, data[:ends[k]], coder=coder, group=group).decode(q=q)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            rows.append({"q": q, "bytes": int(ends[k]), "bpp": 8.0 * ends[k] / (H * W), "psnr": compute_psnr(x, x_hat.unsqueeze(0)),
+                         "enc_s": t1 - t0, "dec_s": t3 - t2})
+    return rows
+
+
 def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
                        base_lanes: int = 1):
     """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE

@@ -760,6 +760,43 @@ def rank_scatter(ranked: torch.Tensor, perm: torch.Tensor, count: torch.Tensor, 
                                       ps, ls, level_id.data_ptr(), sym.C, stream_ptr()), "vam_rank_scatter")
 
 
+def tile_extract(image: torch.Tensor, coords: torch.Tensor, out: torch.Tensor, overlap: int):
+    """out[i, :, y, x] = image[:, min(r * Sy + y, H - 1), min(c * Sx + x, W - 1)] for (r, c) = coords[i]: the tiles of a
+    picture ``image`` fp32 [3, H, W], edge replicated, ``coords`` int32 [n, 2] on the device, ``out`` fp32
+    [n, 3, th, tw], strides Sy = th - overlap and Sx = tw - overlap.  One launch; capturable."""
+    assert image.dtype == torch.float32 and image.is_contiguous() and image.dim() == 3 and image.shape[0] == 3 and image.is_cuda
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[1] == 3 and out.device == image.device
+    n, _, th, tw = out.shape
+    assert coords.dtype == torch.int32 and coords.is_contiguous() and tuple(coords.shape) == (n, 2) and coords.device == image.device
+    L.check(L.load().vam_tile_extract(image.data_ptr(), image.shape[1], image.shape[2], th, tw, int(overlap), coords.data_ptr(), n,
+                                      out.data_ptr(), stream_ptr()), "vam_tile_extract")
+
+
+def tile_blend(tiles: torch.Tensor, slot: torch.Tensor, w_lo: Optional[torch.Tensor], w_hi: Optional[torch.Tensor], H: int, W: int,
+               overlap: int, window: Sequence[int], out: torch.Tensor, status: torch.Tensor):
+    """The window (y0, x0, h, w) of a picture of H x W blended from decoded tiles: ``tiles`` fp32
+    [n, 3, th, tw], ``slot`` int32 [R, C] (index into ``tiles``, -1: absent), the ramps ``w_lo`` / ``w_hi`` fp32 [overlap]
+    (None for overlap 0).  ``out``: fp32 [3, h, w], or uint8 [h, w, 3] as rint(clamp(v, 0, 1) * 255).  ``status`` int32 [1],
+    cleared by the caller, becomes 1 when a pixel needs an absent tile.  One launch; capturable."""
+    y0, x0, h, w = (int(v) for v in window)
+    assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.is_cuda
+    n, _, th, tw = tiles.shape
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and slot.device == tiles.device
+    if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):       # the grid the library derives; anything else it refuses
+        grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
+        assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
+    for t in (w_lo, w_hi):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == tiles.device)
+    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == tiles.device
+    assert out.is_contiguous() and out.device == tiles.device
+    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, h, w)) or (out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3)), \
+        (out.dtype, tuple(out.shape), (h, w))
+    rc = L.load().vam_tile_blend(tiles.data_ptr(), n, slot.data_ptr(), w_lo.data_ptr() if w_lo is not None else None,
+                                 w_hi.data_ptr() if w_hi is not None else None, int(H), int(W), th, tw, int(overlap), y0, x0, h, w,
+                                 out.data_ptr(), int(out.dtype == torch.uint8), status.data_ptr(), stream_ptr())
+    L.check(rc, "vam_tile_blend")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

@@ -1,0 +1,508 @@
+"""Tiled picture codestreams: a picture of ANY size as overlapping tiles, each tile an embedded
+codestream of its own (embedded.to_bytes, section 9u), all of them in one byte string that is decodable by window.
+
+Geometry, one definition for the host, the kernels of ``csrc/tiles.hip`` and ``tests/tiled_ref.py`` (:func:`grid`): tiles of
+``th x tw`` with ``th = min(tile, ceil64(H))``, ``tw = min(tile, ceil64(W))``, an overlap ``V <= min(th, tw) / 2``, strides
+``Sy = th - V`` and ``Sx = tw - V``, a grid of ``R = max(1, ceil((H - V) / Sy))`` by ``C`` likewise; tile (r, c) covers rows
+``[r Sy, r Sy + th)`` and columns ``[c Sx, c Sx + tw)``, the picture's edge replicated beyond it (vam_tile_extract).  At most
+two tiles overlap along an axis.  In the band that tiles r and r + 1 share, row ``(r + 1) Sy + t`` takes
+``w_hi[t] = float32((t + 0.5) / V)`` of tile r + 1 and ``w_lo[t] = float32(1) - w_hi[t]`` of tile r (:func:`ramps`); an output
+pixel is the sum over its tiles, ascending r and within that ascending c, of ``(wy * wx) * v`` in fp32 (vam_tile_blend):
+outside the bands the picture IS the tile's decode, bit for bit.
+
+The codestream: ``embedded._PREAMBLE`` with magic ``b"VAMp"``, a little-endian header (u32 H, W; u16 th / 64, tw / 64, V, R, C,
+n_rounds; a u32 table [R C][1 + n_rounds]; u64 total) under a CRC-32, then the body: the **heads** of all tiles in raster
+order, then round 0 of all tiles, round 1, ...  A tile's head is its own embedded codestream up to its ``base_end``, its round
+pieces are the differences of its ``round_end`` and a last piece up to its ``total``: head and pieces concatenated are exactly
+``embedded.to_bytes`` of the tile, nothing is re-framed.  A head of 0 bytes marks an absent tile.  From :func:`need_bytes` on
+every prefix decodes the whole picture; ``data[:round_end[k]]`` holds every tile exactly at mark k; :func:`extract` cuts a
+stream down to a window and a number of rounds on the host alone, and what it returns is again a picture codestream.
+
+:func:`encode` and :class:`PictureDecoder` run the tiles, a group at a time, through ``embedded.encode_batch`` and
+``embedded.EmbeddedDecoder`` unchanged: an image codes and decodes bit for bit the same alone or in a batch, so neither the
+bytes nor the pixels depend on the grouping.  Quality q keeps a quantile PER TILE: a tiled picture at q is not the untiled
+forward at q.  Out of scope: schedules (``embedded-3``), incremental feeding, rate allocation between tiles and a tile cache
+across ``decode`` calls.
+"""
+from __future__ import annotations
+
+import struct
+import zlib
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import embedded as EB
+
+MAGIC = b"VAMp"
+VERSION = 1
+_PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
+PREAMBLE_BYTES = EB.PREAMBLE_BYTES
+_FIXED = struct.Struct("<IIHHHHHH")        # H, W, th / 64, tw / 64, V, R, C, n_rounds
+_MAX_HEADER = EB._MAX_HEADER
+MAX_SIDE = 1 << 24                         # csrc/tiles.hip: the largest picture side
+MAX_GROUP = 32
+
+
+# ------------------------------------------------------------------------------------------------------------- geometry
+def _int(v, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{what} is an integer, got {v!r}")
+    return int(v)
+
+
+def _geometry(H: int, W: int, th: int, tw: int, V: int, what: str) -> dict:
+    """The grid of th x tw tiles with overlap V over a picture of H x W."""
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"{what}: a picture of {H} x {W}: sides are 1 .. {MAX_SIDE}")
+    if not 0 <= V <= min(th, tw) // 2:
+        raise ValueError(f"{what}: overlap {V}: tiles of {th} x {tw} take 0 <= overlap <= {min(th, tw) // 2} (half a tile: at most two "
+                         "tiles overlap along an axis)")
+    Sy, Sx = th - V, tw - V
+    R, C = max(1, -(-(H - V) // Sy)), max(1, -(-(W - V) // Sx))
+    if R > 0xFFFF or C > 0xFFFF:
+        raise ValueError(f"{what}: a grid of {R} x {C} tiles; the format carries up to 65535 along an axis, use larger tiles")
+    return {"H": H, "W": W, "th": th, "tw": tw, "V": V, "Sy": Sy, "Sx": Sx, "R": R, "C": C}
+
+
+def grid(H: int, W: int, tile: int = 256, overlap: int = 32) -> dict:
+    """The geometry of a picture of H x W at ``tile`` (a multiple of 64 in 64 .. 1024) and ``overlap``: a dict of H, W, th,
+    tw, V, Sy, Sx, R, C (module docstring) and ``tile``.  ValueError names what is out of range."""
+    H, W, T, V = _int(H, "grid: H"), _int(W, "grid: W"), _int(tile, "grid: tile"), _int(overlap, "grid: overlap")
+    if T % 64 or not 64 <= T <= 1024:
+        raise ValueError(f"grid: tile is a multiple of 64 in 64 .. 1024, got {T}")
+    c64 = lambda n: -(-n // 64) * 64
+    g = _geometry(H, W, min(T, c64(max(H, 1))), min(T, c64(max(W, 1))), V, "grid")
+    g["tile"] = T
+    return g
+
+
+def ramps(V: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(w_lo, w_hi) float32 [V]: ``w_hi[t] = float32((t + 0.5) / V)`` from float64, rounded once, ``w_lo = float32(1) - w_hi``
+    in float32.  The kernel reads these tables and divides nothing."""
+    w_hi = ((np.arange(V, dtype=np.float64) + 0.5) / max(V, 1)).astype(np.float32)
+    return np.float32(1) - w_hi, w_hi
+
+
+def _window(g: dict, window, what: str) -> Tuple[int, int, int, int]:
+    if window is None:
+        return 0, 0, g["H"], g["W"]
+    try:
+        y0, x0, h, w = (_int(v, f"{what}: a window entry") for v in window)
+    except TypeError as e:
+        raise ValueError(f"{what}: a window is (y0, x0, h, w), got {window!r}") from e
+    if not (y0 >= 0 and x0 >= 0 and h >= 1 and w >= 1 and y0 + h <= g["H"] and x0 + w <= g["W"]):
+        raise ValueError(f"{what}: the window (y0 {y0}, x0 {x0}, h {h}, w {w}) does not lie inside the {g['H']} x {g['W']} picture")
+    return y0, x0, h, w
+
+
+def tiles_for(layout: dict, window=None) -> List[Tuple[int, int]]:
+    """The (r, c), in raster order, of the tiles whose extent meets ``window`` = (y0, x0, h, w) (None: the picture): exactly
+    the tiles a blend of that window reads, band neighbours included.  ``layout``: :func:`layout`'s or :func:`grid`'s dict."""
+    g = layout
+    y0, x0, h, w = _window(g, window, "tiles_for")
+    rows = [r for r in range(g["R"]) if r * g["Sy"] < y0 + h and r * g["Sy"] + g["th"] > y0]
+    cols = [c for c in range(g["C"]) if c * g["Sx"] < x0 + w and c * g["Sx"] + g["tw"] > x0]
+    return [(r, c) for r in rows for c in cols]
+
+
+# ----------------------------------------------------------------------------------------------------------- codestream
+class _Picture:
+    """A parsed picture header and the byte arithmetic of the body that follows from it."""
+
+    def __init__(self, d, what: str):
+        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
+        end = PREAMBLE_BYTES + hlen
+        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
+            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        H, W, th, tw, V, R, C, nr = _FIXED.unpack_from(d, PREAMBLE_BYTES)
+        if not (1 <= th <= 16 and 1 <= tw <= 16):
+            raise ValueError(f"{what}: the header contradicts itself: tiles of {64 * th} x {64 * tw}, sides are 64 .. 1024")
+        g = _geometry(H, W, 64 * th, 64 * tw, V, what)
+        if (g["R"], g["C"]) != (R, C) or any(grid(H, W, 64 * max(th, tw), V)[k] != g[k] for k in ("th", "tw")):
+            raise ValueError(f"{what}: the header contradicts itself: {H} x {W} in tiles of {64 * th} x {64 * tw} with overlap {V} "
+                             f"is no grid of {R} x {C}")
+        if hlen != _FIXED.size + 4 * R * C * (1 + nr) + 8:
+            raise ValueError(f"{what}: the header contradicts itself: {R} x {C} tiles of {nr} rounds take "
+                             f"{_FIXED.size + 4 * R * C * (1 + nr) + 8} bytes, it states {hlen}")
+        self.g, self.nr, self.header_end = g, nr, end
+        self.table = np.frombuffer(d, dtype="<u4", count=R * C * (1 + nr), offset=PREAMBLE_BYTES + _FIXED.size) \
+            .astype(np.int64).reshape(R * C, 1 + nr)
+        self.total = int(np.frombuffer(d, dtype="<u8", count=1, offset=end - 8)[0])
+        self.present = self.table[:, 0] > 0
+        bad = np.flatnonzero(~self.present & (self.table[:, 1:].sum(1) > 0))
+        if bad.size:
+            raise ValueError(f"{what}: the header contradicts itself: tile {self.rc(int(bad[0]))} is absent (a head of 0 bytes) and "
+                             "has round pieces")
+        if not self.present.any():
+            raise ValueError(f"{what}: the header holds no tile: every head has 0 bytes")
+        if end + int(self.table.sum()) != self.total:
+            raise ValueError(f"{what}: the header contradicts itself: its table adds up to {end + int(self.table.sum())} bytes, it "
+                             f"states a total of {self.total}")
+        # the body: segment (k, i) = column k of tile i (k = 0: the head, k >= 1: round k - 1), column-major from header_end on
+        self.size = np.ascontiguousarray(self.table.T)                           # [1 + nr, R C]
+        ends = np.cumsum(self.size.reshape(-1)).reshape(1 + nr, R * C)
+        self.off = end + ends - self.size
+        self.need = end + int(self.size[0].sum())
+        self.round_end = [end + int(v) for v in ends[1:, -1]]
+
+    def rc(self, i: int) -> Tuple[int, int]:
+        return i // self.g["C"], i % self.g["C"]
+
+    def index(self, r, c, what: str) -> int:
+        r, c = _int(r, f"{what}: r"), _int(c, f"{what}: c")
+        if not (0 <= r < self.g["R"] and 0 <= c < self.g["C"]):
+            raise ValueError(f"{what}: tile ({r}, {c}) is outside the grid of {self.g['R']} x {self.g['C']}")
+        return r * self.g["C"] + c
+
+    def held(self, n: int) -> np.ndarray:
+        """int64 [1 + nr, R C]: the bytes of every segment that the first ``n`` bytes of the codestream hold."""
+        return np.clip(n - self.off, 0, self.size)
+
+    def stream(self, d, i: int) -> bytes:
+        """Tile i's embedded codestream as far as ``d`` holds it."""
+        n = len(d)
+        return b"".join(bytes(d[int(o):min(int(o + s), n)]) for o, s in zip(self.off[:, i], self.size[:, i]) if s and o < n)
+
+
+def _header_end(d, what: str) -> Optional[int]:
+    if len(d) < PREAMBLE_BYTES:
+        return None
+    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
+    if magic != MAGIC:
+        raise ValueError(f"{what}: not a picture codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
+    if version != VERSION or reserved:
+        raise ValueError(f"{what}: picture codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
+                         f"reader knows version {VERSION}")
+    if not _FIXED.size + 4 + 8 <= hlen <= _MAX_HEADER:
+        raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 12} .. {_MAX_HEADER}")
+    return PREAMBLE_BYTES + hlen
+
+
+def _parse(data, what: str):
+    """(view, parsed header) of a picture codestream, or a prefix of one, that holds its whole header."""
+    d = EB._view(data, what)
+    end = _header_end(d, what)
+    if end is None or len(d) < end:
+        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
+                         "before it can be read")
+    s = _Picture(d, what)
+    if len(d) > s.total:
+        raise ValueError(f"{what}: {len(d)} bytes, the header states a total of {s.total}: {len(d) - s.total} bytes follow the "
+                         "codestream")
+    return d, s
+
+
+def _tile_layout(stream, g: dict, rc, what: str) -> dict:
+    """embedded.layout of one tile's head or codestream, with this format's refusals."""
+    try:
+        lay = EB.layout(stream)
+    except ValueError as e:
+        raise ValueError(f"{what}: tile {rc}: {e}") from e
+    if lay["scheduled"]:
+        raise ValueError(f"{what}: tile {rc} is scheduled ({lay['format']!r}); a picture codestream carries no schedules")
+    if tuple(lay["shape"]) != (g["th"] // 64, g["tw"] // 64):
+        raise ValueError(f"{what}: tile {rc} is an image of {64 * lay['shape'][0]} x {64 * lay['shape'][1]}, the tiles of this picture "
+                         f"are {g['th']} x {g['tw']}")
+    lay["marks"] = [float(q) for q in lay["marks"]["q"]]                  # the marked qualities; counts and bytes are a tile's own
+    return lay
+
+
+_ALIKE = ("marks", "lanes", "base_lanes", "ns")
+
+
+def _unlike(lay: dict, first: dict, rc, rc0, what: str):
+    for key in _ALIKE:
+        if not EB._same(lay[key], first[key]):
+            raise ValueError(f"{what}: tile {rc} and tile {rc0} differ in their {key}: all tiles of a picture carry the same "
+                             "marks, lanes and base_lanes")
+
+
+def _pieces(lay: dict) -> List[int]:
+    """[bytes of the head, of round 0, ..., of the last piece] of a tile with embedded.layout ``lay``."""
+    edges = [0, lay["base_end"]] + list(lay["round_end"]) + [lay["total"]]
+    return [b - a for a, b in zip(edges, edges[1:])]
+
+
+def _tile_meta(d, s: _Picture, what: str) -> Optional[dict]:
+    """Reads the head of every present tile that ``d`` holds whole and checks it against the table: the head ends at the
+    tile's base_end, the round pieces are those of its marks, no schedule, the picture's tile shape, and all tiles alike.
+    Returns the first one's embedded.layout, None when ``d`` holds no head yet."""
+    first, rc0 = None, None
+    for i in (int(v) for v in np.flatnonzero(s.present)):
+        off, size = int(s.off[0, i]), int(s.size[0, i])
+        if off + size > len(d):
+            break
+        lay = _tile_layout(d[off:off + size], s.g, s.rc(i), what)
+        want = _pieces(lay)
+        if s.nr > len(want) - 1 or [int(v) for v in s.table[i]] != want[:1 + s.nr]:
+            raise ValueError(f"{what}: the header contradicts tile {s.rc(i)}: its table row {[int(v) for v in s.table[i]]} is not the "
+                             f"head and the first {s.nr} round pieces of the tile's own codestream, {want}")
+        if first is None:
+            first, rc0 = lay, s.rc(i)
+        else:
+            _unlike(lay, first, s.rc(i), rc0, what)
+    return first
+
+
+def _assemble(g: dict, table: np.ndarray, get) -> bytes:
+    """The picture codestream of ``table`` int64 [R C, 1 + nr]; ``get(i, k)`` gives the bytes of column k of tile i."""
+    nr = table.shape[1] - 1
+    if (table >= 1 << 32).any():
+        raise ValueError("a head or round piece of 2^32 bytes or more does not fit the header's table")
+    hlen = _FIXED.size + 4 * table.size + 8
+    if hlen > _MAX_HEADER:
+        raise ValueError(f"the header would take {hlen} bytes, the limit is {_MAX_HEADER}; use larger tiles")
+    if nr > 0xFFFF:
+        raise ValueError(f"{nr} rounds; the format carries up to 65535")
+    header = _FIXED.pack(g["H"], g["W"], g["th"] // 64, g["tw"] // 64, g["V"], g["R"], g["C"], nr) + table.astype("<u4").tobytes() \
+        + struct.pack("<Q", PREAMBLE_BYTES + hlen + int(table.sum()))
+    out = [_PREAMBLE.pack(MAGIC, VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
+    out += [get(i, k) for k in range(1 + nr) for i in range(table.shape[0]) if table[i, k]]
+    return b"".join(out)
+
+
+def pack(H: int, W: int, tile: int, overlap: int, tile_streams) -> bytes:
+    """The picture codestream of R C whole tile codestreams (``embedded.to_bytes``), given in raster order as one flat
+    sequence or as [R][C]; None marks an absent tile.  Pure framing on the host.  ValueError for a wrong count, a cut or
+    scheduled tile, a tile of another shape and tiles that differ in marks, lanes or base_lanes."""
+    g = grid(H, W, tile, overlap)
+    try:
+        streams = list(tile_streams)
+    except TypeError as e:
+        raise ValueError(f"pack: tile_streams is a sequence of {g['R'] * g['C']} codestreams") from e
+    if len(streams) == g["R"] and all(isinstance(row, (list, tuple)) for row in streams):
+        streams = [s for row in streams for s in row]
+    if len(streams) != g["R"] * g["C"]:
+        raise ValueError(f"pack: a {H} x {W} picture at tile {tile}, overlap {overlap} has {g['R']} x {g['C']} = {g['R'] * g['C']} tiles, "
+                         f"got {len(streams)} codestreams")
+    rows, views, first, rc0 = [], [], None, None
+    for i, s in enumerate(streams):
+        rc = (i // g["C"], i % g["C"])
+        if s is None:
+            rows.append(None)
+            views.append(None)
+            continue
+        v = EB._view(s, f"pack: tile {rc}")
+        lay = _tile_layout(v, g, rc, "pack")
+        if len(v) != lay["total"]:
+            raise ValueError(f"pack: tile {rc}: {len(v)} bytes, its header states a total of {lay['total']}: a picture is packed from "
+                             "whole tile codestreams and cut as bytes")
+        if first is None:
+            first, rc0 = lay, rc
+        else:
+            _unlike(lay, first, rc, rc0, "pack")
+        rows.append(_pieces(lay))
+        views.append(v)
+    if first is None:
+        raise ValueError("pack: no tile: every entry is None")
+    width = 2 + len(first["round_end"])
+    table = np.asarray([row if row is not None else [0] * width for row in rows], dtype=np.int64)
+    edges = np.concatenate([np.zeros((len(rows), 1), dtype=np.int64), np.cumsum(table, axis=1)], axis=1)
+    try:
+        return _assemble(g, table, lambda i, k: bytes(views[i][int(edges[i, k]):int(edges[i, k + 1])]))
+    except ValueError as e:
+        raise ValueError(f"pack: {e}") from e
+
+
+def need_bytes(data) -> int:
+    """The smallest length from which the whole picture decodes, as far as ``data`` (any prefix) tells: the preamble's size
+    while that is incomplete, the header's end while the header is, then the end of the last head."""
+    d = EB._view(data, "need_bytes")
+    end = _header_end(d, "need_bytes")
+    if end is None:
+        return PREAMBLE_BYTES
+    return end if len(d) < end else _parse(d, "need_bytes")[1].need
+
+
+def layout(data) -> dict:
+    """Where a picture codestream may be cut, from its header (``data``: any prefix that holds it): the geometry of
+    :func:`grid` (H, W, th, tw, V, Sy, Sx, R, C), ``header_end``, ``need_bytes``, ``n_rounds``, ``total``,
+    ``present[r][c]``, ``head[r][c]`` = (offset, length), ``piece[k][r][c]`` = (offset, length) and ``round_end[k]`` for
+    k < n_rounds: ``data[:round_end[k]]`` holds every present tile exactly at its mark k (a whole stream has one round more
+    than marks, and its last ``round_end`` is ``total``).  ``marks``, ``lanes``, ``base_lanes``, ``ns`` and ``format`` are
+    those of the tiles, read from the heads that ``data`` holds whole (all checked against the table and each other); None
+    while it holds none."""
+    d, s = _parse(data, "layout")
+    g, meta = s.g, _tile_meta(d, s, "layout")
+    R, C = g["R"], g["C"]
+    seg = lambda k: [[(int(s.off[k, r * C + c]), int(s.size[k, r * C + c])) for c in range(C)] for r in range(R)]
+    out = dict(g)
+    out.update({"header_end": s.header_end, "need_bytes": s.need, "n_rounds": s.nr, "total": s.total,
+                "present": [[bool(s.present[r * C + c]) for c in range(C)] for r in range(R)],
+                "head": seg(0), "piece": [seg(1 + k) for k in range(s.nr)], "round_end": list(s.round_end)})
+    for key in _ALIKE + ("format",):
+        out[key] = meta[key] if meta is not None else None
+    return out
+
+
+def tile_stream(data, r: int, c: int) -> bytes:
+    """Tile (r, c)'s embedded codestream as far as ``data`` (a picture codestream or any prefix that holds the header) holds
+    it: its head and round pieces, concatenated.  The result may end anywhere, also inside a piece; from the tile's head on
+    ``embedded.from_bytes`` accepts it.  ValueError for an absent tile."""
+    d, s = _parse(data, "tile_stream")
+    i = s.index(r, c, "tile_stream")
+    if not s.present[i]:
+        raise ValueError(f"tile_stream: tile ({r}, {c}) is absent from this codestream")
+    return s.stream(d, i)
+
+
+def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
+    """A shorter picture codestream of the same picture: only the tiles ``tiles_for(window)`` (None: those present) and only
+    the first ``rounds`` rounds (None: all it has).  What a server does to crop and to cut the quality, without the model.
+    ``data`` must hold what is kept.  ``extract(data)`` is ``data``; an extract of an extract is an extract.  ValueError
+    names a wanted tile that ``data`` lacks."""
+    d, s = _parse(data, "extract")
+    _tile_meta(d, s, "extract")
+    nr = s.nr if rounds is None else _int(rounds, "extract: rounds")
+    if not 0 <= nr <= s.nr:
+        raise ValueError(f"extract: rounds is 0 .. {s.nr} (the rounds this codestream holds), got {nr}")
+    keep = np.zeros_like(s.present)
+    if window is None:
+        keep[:] = s.present
+    else:
+        for r, c in tiles_for(s.g, _window(s.g, window, "extract")):
+            i = r * s.g["C"] + c
+            if not s.present[i]:
+                raise ValueError(f"extract: the window {tuple(window)} needs tile ({r}, {c}), which is absent from this codestream")
+            keep[i] = True
+    table = np.where(keep[:, None], s.table[:, :1 + nr], 0)
+    short = np.argwhere((s.held(len(d))[:1 + nr].T < table))
+    if len(short):
+        i, k = (int(v) for v in short[0])
+        raise ValueError(f"extract: {len(d)} bytes end before {'the head' if k == 0 else f'round {k - 1}'} of tile {s.rc(i)} does; "
+                         "a codestream is extracted from bytes that hold what is kept")
+    return _assemble(s.g, table, lambda i, k: bytes(d[int(s.off[k, i]):int(s.off[k, i] + s.size[k, i])]))
+
+
+# ---------------------------------------------------------------------------------------------------- encoder and decoder
+def _default_group(th: int, tw: int) -> int:
+    """The most tiles of th x tw that control.sweep_groups keeps in one plan, at most MAX_GROUP."""
+    from .control import sweep_groups
+    n = 1
+    while n < MAX_GROUP and len(sweep_groups(1, n + 1, th, tw)) == 1:
+        n += 1
+    return n
+
+
+def _check_group(group, th: int, tw: int, what: str) -> int:
+    if group is None:
+        return _default_group(th, tw)
+    group = _int(group, f"{what}: group")
+    if group < 1:
+        raise ValueError(f"{what}: group is the tiles per batch, >= 1, got {group}")
+    return group
+
+
+def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Sequence[float]] = None, coder: Optional[str] = None,
+           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None) -> bytes:
+    """The picture codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device, any H, W >= 1: the tiles are cut
+    ``group`` at a time (vam_tile_extract, one launch per group), each group goes through ``embedded.encode_batch`` (``marks``,
+    ``coder``, ``lanes`` and ``base_lanes`` are its) and ``embedded.to_bytes``, and :func:`pack` frames them.  ``group``: the
+    tiles per batch, by default the most that one plan holds, at most 32; the bytes do not depend on it."""
+    import torch
+    from . import ops
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() not in (3, 4) \
+            or tuple(image.shape[:-2]) not in ((3,), (1, 3)):
+        raise ValueError("tiled.encode: image is an fp32 tensor [3, H, W] or [1, 3, H, W], got "
+                         f"{tuple(image.shape) if isinstance(image, torch.Tensor) else type(image).__name__}")
+    H, W = (int(v) for v in image.shape[-2:])
+    g = grid(H, W, tile, overlap)
+    group = _check_group(group, g["th"], g["tw"], "tiled.encode")
+    EB._check_model(model)
+    img = image.detach().reshape(3, H, W).contiguous()
+    coords = [(r, c) for r in range(g["R"]) for c in range(g["C"])]
+    streams: List[bytes] = []
+    with torch.no_grad():
+        for i0 in range(0, len(coords), group):
+            part = coords[i0:i0 + group]
+            x = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
+            ops.tile_extract(img, torch.tensor(part, dtype=torch.int32).to(img.device), x, g["V"])
+            cs = EB.encode_batch(model, x, marks=marks, coder=coder, lanes=lanes, base_lanes=base_lanes)
+            streams += [EB.to_bytes(c) for c in cs]
+    return pack(H, W, tile, overlap, streams)
+
+
+class PictureDecoder:
+    """Decodes a picture codestream by window.  ``data``: any prefix of at least :func:`need_bytes`, or an :func:`extract`.
+    ``shape``: the true (H, W); ``grid``: the geometry; ``rounds``: int [R, C], the complete rounds ``data`` holds of every
+    tile, -1 where the tile is absent.  Every :meth:`decode` decodes the tiles of its window afresh, ``group`` at a time
+    through ``embedded.EmbeddedDecoder`` (``coder`` is its), and blends them with one vam_tile_blend launch."""
+
+    def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
+        from . import progressive as P
+        EB._check_model(model)
+        d, s = _parse(data, "PictureDecoder")
+        if len(d) < s.need:
+            raise ValueError(f"PictureDecoder: {len(d)} bytes end before the heads of the tiles do: {s.need} bytes are needed, every "
+                             "tile's z and base are decoded whole")
+        self.meta = _tile_meta(d, s, "PictureDecoder")
+        self.m, self.coder, self._d, self._s = model, P._check_coder(model, coder), bytes(d), s
+        self.grid, self.shape = dict(s.g), (s.g["H"], s.g["W"])
+        self.group = _check_group(group, s.g["th"], s.g["tw"], "PictureDecoder")
+        whole = (s.held(len(d))[1:] == s.size[1:])                               # [nr, R C]: a piece of 0 bytes is whole
+        done = np.cumprod(whole, axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
+        self.rounds = np.where(s.present, done, -1).astype(np.int64).reshape(s.g["R"], s.g["C"])
+        self.last_tiles: List[Tuple[int, int]] = []
+        self._ramps = None
+
+    def _blend_inputs(self, device):
+        import torch
+        if self._ramps is None or self._ramps[0].device != device:
+            self._ramps = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ramps(self.grid["V"]))
+        return self._ramps
+
+    def _decode_tiles(self, containers, q):
+        dec = EB.EmbeddedDecoder(self.m, containers, coder=self.coder)
+        return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
+
+    def decode(self, window=None, q: Optional[float] = None, dtype=None):
+        """The window (y0, x0, h, w) of the picture (None: all of it): fp32 [3, h, w], or uint8 [h, w, 3] for
+        ``dtype=torch.uint8`` (round half to even of clamp(v, 0, 1) * 255, as evaluate.write_image).  ``q`` = None: from
+        everything ``data`` holds of every tile (``EmbeddedDecoder.decode``); a quality: ``decode_qualities([q])``, every tile
+        at its own quantile.  Only ``tiles_for(window)`` are decoded (``last_tiles``).  ValueError names the tile (r, c) that
+        the window needs and the codestream lacks, or whose bytes end before ``q``."""
+        import torch
+        from . import _lib as L
+        from . import ops
+        g, s = self.grid, self._s
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
+        y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
+        tiles = tiles_for(g, (y0, x0, h, w))
+        for r, c in tiles:
+            if not s.present[r * g["C"] + c]:
+                raise ValueError(f"PictureDecoder.decode: the window ({y0}, {x0}, {h}, {w}) needs tile ({r}, {c}), which is absent "
+                                 "from this codestream")
+        buf = None
+        with torch.no_grad():
+            for i0 in range(0, len(tiles), self.group):
+                part = tiles[i0:i0 + self.group]
+                cs = [EB.from_bytes(s.stream(self._d, r * g["C"] + c)) for r, c in part]
+                try:
+                    x_hat = self._decode_tiles(cs, q)
+                except ValueError:
+                    for rc, c1 in zip(part, cs):            # a tile decodes alone as in its group: find the one that is refused
+                        try:
+                            self._decode_tiles([c1], q)
+                        except ValueError as e:
+                            raise ValueError(f"PictureDecoder.decode: tile {rc}: {e}") from e
+                    raise
+                if buf is None:
+                    buf = torch.empty((len(tiles), 3, g["th"], g["tw"]), dtype=torch.float32, device=x_hat.device)
+                buf[i0:i0 + len(part)].copy_(x_hat)
+            dev = buf.device
+            slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
+            for i, (r, c) in enumerate(tiles):
+                slot[r, c] = i
+            w_lo, w_hi = self._blend_inputs(dev)
+            status = torch.zeros((1,), dtype=torch.int32, device=dev)
+            out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
+                else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+            ops.tile_blend(buf, torch.from_numpy(slot).to(dev), w_lo if g["V"] else None, w_hi if g["V"] else None, g["H"], g["W"],
+                           g["V"], (y0, x0, h, w), out, status)
+            if int(status.item()):
+                raise L.VamError("PictureDecoder.decode: vam_tile_blend met an absent tile inside the window")
+        self.last_tiles = tiles
+        return out

@@ -384,6 +384,26 @@ int vam_variance_rank_staged(const float* sigma, int ld, long batch_stride, long
                              int ld_stage, int n_batch, int n_slice, int n_pix, int C, int32_t* perm_out, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ tiled pictures */
+/* Tiled pictures (vampic.tiled).  A picture of H x W (any sizes >= 1) is covered by tiles of th x tw with
+ * overlap V, 0 <= 2 V <= min(th, tw): strides Sy = th - V and Sx = tw - V, grid R = max(1, ceil((H - V) / Sy)) by
+ * C = max(1, ceil((W - V) / Sx)), tile (r, c) over rows [r Sy, r Sy + th) and columns [c Sx, c Sx + tw).  Both calls derive
+ * R and C from (H, W, th, tw, V); a geometry outside these bounds is VAM_EINVAL and launches nothing.
+ * vam_tile_extract: image fp32 [3, H, W], coords int32 [n][2] = (r, c) on the device, out fp32 [n, 3, th, tw] with
+ *   out[i, :, y, x] = image[:, min(r Sy + y, H - 1), min(c Sx + x, W - 1)]      (the edge is replicated);
+ * an (r, c) outside the grid leaves its tile unwritten.  One launch for the whole list.
+ * vam_tile_blend: tiles fp32 [n, 3, th, tw], slot int32 [R][C] (index into tiles, -1: absent), the ramps w_lo / w_hi fp32 [V]
+ * (NULL allowed for V = 0), a window y0, x0, h, w inside the picture.  Along an axis pixel P lies in tile
+ * t1 = min(n_tiles - 1, P / S) at l1 = P - t1 S with weight 1, or, when t1 > 0 and l1 < V, in t1 with w_hi[l1] and in t1 - 1
+ * with w_lo[l1].  out = sum over the pixel's tiles, ascending r and within that ascending c, of (wy * wx) * v, every product
+ * and add one fp32 operation, the sum starting from its first term: fp32 [3, h, w] (out_u8 = 0) or uint8 [h, w, 3]
+ * (out_u8 = 1) as rintf(clamp(v, 0, 1) * 255).  A pixel that needs an absent tile (a slot outside 0 .. n - 1) sets
+ * *status = 1 and skips that term; the caller clears status.  No atomics, no allocation: both calls can be captured. */
+int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
+                     void* stream);
+int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
+                   int tw, int V, int y0, int x0, int h, int w, void* out, int out_u8, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
  *  base  (mask == NULL):  v = round(y-mu);           lik = L(|(v+mu)-mu|, sigma);        yhat = v+mu
