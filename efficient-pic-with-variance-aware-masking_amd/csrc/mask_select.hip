@@ -12,6 +12,7 @@
 // lane, coalesced over the NHWC channel window) and stay in registers for every pass, so HBM
 // traffic is the algorithmic 4 B read + 4 B written per element.  Histograms live in LDS.
 #include "common.h"
+#include "quantile.h"
 #include <cmath>
 #include <cstring>
 
@@ -27,15 +28,6 @@ struct MaskArgs {
   float w;
   int mode;  // 0 = quantile, 1 = all zero (pr == 0), 2 = all one (pr >= 10)
 };
-
-__device__ __forceinline__ unsigned f2key(float f) {
-  unsigned u = __float_as_uint(f);
-  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-  unsigned u = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-  return __uint_as_float(u);
-}
 
 // MAXV = float4 per thread kept in registers (0 = stream from memory every pass)
 template <int MAXV>
@@ -159,8 +151,7 @@ __global__ __launch_bounds__(1024) void variance_mask_kernel(const MaskArgs a) {
     key_hi = (sh_cnt > (unsigned)a.k_lo + 1u) ? key_lo : sh_min;
   }
   const float lo_v = key2f(key_lo), hi_v = key2f(key_hi);
-  const float d = hi_v - lo_v;
-  float thr = (a.w < 0.5f) ? __builtin_fmaf(a.w, d, lo_v) : __builtin_fmaf(a.w - 1.0f, d, hi_v);
+  float thr = quantile_lerp(a.w, lo_v, hi_v);
   if (sh_nan) thr = __uint_as_float(0x7FC00000u);
   if (tid == 0 && a.thr) a.thr[seg] = thr;
 
@@ -394,8 +385,7 @@ __global__ __launch_bounds__(1024) void variance_mask_levels_kernel(const Args a
       key_hi = (sh_cnt > (unsigned)k_lo + 1u) ? key_lo : sh_min;
     }
     const float lo_v = key2f(key_lo), hi_v = key2f(key_hi);
-    const float d = hi_v - lo_v;
-    float thr = (w < 0.5f) ? __builtin_fmaf(w, d, lo_v) : __builtin_fmaf(w - 1.0f, d, hi_v);
+    float thr = quantile_lerp(w, lo_v, hi_v);
     if (sh_nan) thr = __uint_as_float(0x7FC00000u);
     if (tid == 0 && thr_out) thr_out[seg] = thr;
     if (LAYERS) {
@@ -537,26 +527,7 @@ extern "C" int vam_variance_mask(const float* sigma, int ld, long batch_stride, 
 
 // rank / weight of torch.quantile for one pr (the host arithmetic of channel_mask.py:138-139)
 static int mask_level_params(MaskLevelsArgs& a, int lv, double pr, long n) {
-  VAM_REQUIRE(pr >= 0.0 && pr == pr, "vam_variance_mask: pr must be >= 0");
-  a.k_lo[lv] = a.k_hi[lv] = 0; a.w[lv] = 0.f;
-  if (pr >= 10.0) a.mode[lv] = 2;             // channel_mask.py:133-134
-  else if (pr == 0.0) a.mode[lv] = 1;         // :135-136
-  else {
-    a.mode[lv] = 0;
-    const double q_keep = pr * 0.1;            // python float arithmetic of :138-139
-    // volatile: each step must round to fp32 exactly like ATen's tensor ops; a host-side
-    // contraction of (qt*(n-1)) - lo into one fma changes w in the 5th digit and the
-    // threshold by an ulp (caught by tests/golden thresholds).
-    volatile float qt = (float)(1.0 - q_keep);       // scalar_tensor(q, float32)
-    volatile float last = (float)(n - 1);
-    volatile float rank = qt * last;                 // fp32 multiply (q * last_index)
-    const float lo = floorf(rank);
-    a.k_lo[lv] = (int)lo;
-    a.k_hi[lv] = (int)ceilf(rank);
-    a.w[lv] = rank - lo;
-    VAM_REQUIRE(a.k_lo[lv] >= 0 && a.k_hi[lv] < n, "vam_variance_mask: rank out of range");
-  }
-  return 0;
+  return quantile_level(pr, n, &a.k_lo[lv], &a.k_hi[lv], &a.w[lv], &a.mode[lv]);
 }
 
 // layer_out != NULL: vam_variance_layers (mask_* then describe the uint8 layer array)

@@ -21,6 +21,7 @@
 //     key = (stage << 56) | (~ordered_bits(sigma) << 24) | e,      e < 2^18 in the low 24 bits,
 // through the same network, chunks, workspace and passes (the STAGED template flag of the key build and the final write).
 #include "common.h"
+#include "quantile.h"
 #include <cstdint>
 
 namespace vam {
@@ -42,18 +43,6 @@ struct RankArgs {
   int k;       // rank_chunk_kernel<false> / rank_global_step_kernel: the stage
   int j;       // rank_global_step_kernel: the step
 };
-
-__device__ __forceinline__ unsigned rank_sigma_bits(float s) {
-  unsigned u = __float_as_uint(s);
-  unsigned d;
-  if (s != s) {
-    d = 0xFFFFFFFFu;                                      // every NaN: behind -inf (whose d is 0xFF800000)
-  } else {
-    if (u == 0x80000000u) u = 0u;                         // -0.0 == +0.0
-    d = ~(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u));   // descending in sigma
-  }
-  return d;
-}
 
 __device__ __forceinline__ u64 rank_key(float s, unsigned e) { return ((u64)rank_sigma_bits(s) << 32) | e; }
 

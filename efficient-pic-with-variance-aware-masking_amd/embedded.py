@@ -220,11 +220,12 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
     interleaved string on Kb lanes of the same elements in the same order (bitstream.encode_interleaved_streams; on the
     device one vam_rans_interleaved_encode_nhwc_device launch for z and one for all base slices).  Format ``"embedded-4"``
     with ``"lanes"`` always and ``"base_lanes": Kb``, scheduled exactly when it carries ``"schedule"``; everything else in
-    the container is what ``base_lanes=1`` gives.  Kb = 1 changes nothing."""
-    from . import _lib as L
+    the container is what ``base_lanes=1`` gives.  Kb = 1 changes nothing.
+
+    The work is two passes, :func:`_encode_front` (everything but the marks' bytes) and :func:`_encode_finish` (the marks'
+    bytes from the marks' counts), so that a caller can supply the counts later (tiled pictures); this
+    function runs them back to back with the batch's own counts."""
     from . import bitstream as bs
-    from . import ops
-    from .models import EMPTY_SCALE_TABLE
     _check_model(model)
     if schedule is not None and marks is not None:
         raise ValueError("embedded.encode_batch: give marks or schedule, not both (a scheduled container is marked per stage)")
@@ -235,8 +236,34 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
     else:
         qs = P.check_q_list(Q_LIST if marks is None else marks)
     coder, K, Kb = P._check_coder(model, coder), bs.check_lanes(lanes), bs.check_lanes(base_lanes)
+    st = _encode_front(model, x, qs, coder, K, Kb, None if schedule is None else (levels, index))
+    containers = _encode_finish(st)
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+        for b, c in enumerate(containers):
+            with open(os.path.join(save_path, "embedded.pkl" if B == 1 else f"embedded_{b}.pkl"), "wb") as f:
+                pickle.dump(c, f)
+    return containers
+
+
+def _encode_front(model, x, qs, coder: str, K: int, Kb: int, schedule=None) -> dict:
+    """The first pass of :func:`encode_batch` on checked arguments, everything that does not depend on the marks' counts: the
+    network (once), the rank order, the gather into rank order, the batch's own counts, and the coding of z and the base; on
+    the host coder also of the embedded strings.  Returns the state :func:`_encode_finish` turns into containers, now or
+    later and with the batch's own counts or a caller's (``tiled.encode(allocation="picture")``).
+
+    What the state keeps per image between the passes: the coded z, base (and, host coder, embedded) strings; the ranked
+    table indexes int32 [ns, n]; on the device coder also the ranked symbols int32 [ns, n], both on the device; the own counts
+    int32 [L, ns].  ``perm`` (int32 [B, ns, n]) and ``std_p`` (the plan's sigma view) are valid only until the model's next
+    plan runs: a caller that pools keys (ops.pool_keys) does so at once and drops them."""
+    from . import _lib as L
+    from . import bitstream as bs
+    from . import ops
+    from .models import EMPTY_SCALE_TABLE
+    B, _, H, W = x.shape
     m = model
     d, C, ns = m.division_dimension[0], m.dim_chunk, m.ns0
+    st = {"m": m, "B": B, "H": H, "W": W, "qs": list(qs), "coder": coder, "K": K, "Kb": Kb, "schedule": schedule}
     with torch.no_grad():
         L.require_gpu()
         m._check_config()
@@ -251,6 +278,7 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
         perm = torch.empty((B, ns, n), dtype=torch.int32, device=dev)
         layer = torch.empty((B, h, w, d), dtype=torch.uint8, device=dev)
         if schedule is not None:
+            levels, index = schedule
             table, stage_map, n_stages = schedule_buffers(B, h * w, dev)
             fill_schedule(table, stage_map, n_stages, levels, index, h * w, C)
             stage = torch.empty_like(layer)
@@ -266,6 +294,7 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
             ops.variance_layers(plan.std_p, qs, layer, n_slice=ns)           # the masks of the marks, as every plan builds them
         count = torch.empty((len(qs), B, ns), dtype=torch.int32, device=dev)
         ops.rank_counts(layer, perm, ns, len(qs), count)
+        st.update(perm=perm, std_p=plan.std_p, count=count)
         if coder == "device":
             tg, te = bs.DeviceCoderTables.of(m.gaussian_conditional, dev), bs.DeviceCoderTables.of(m.entropy_bottleneck, dev)
             if Kb > 1:
@@ -274,32 +303,52 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
             else:
                 z_str = bs.encode_streams_device(plan.z_sym, None, 1, m.N, te)[0]
                 base = bs.encode_streams_device(plan.sym, plan.idx, ns, C, tg)                  # [slice][image]
-            emb_str, cut = bs.encode_embedded_device(r_sym, r_idx, tg, K, count)                # stream b * ns + j
-            cuts = cut.reshape(len(qs), B, ns)
-            count = count.cpu().numpy().astype(np.int64)
-        else:
-            nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
-            sym_b, idx_b, zs = nchw(plan.sym.buf[..., :d]), nchw(plan.idx.buf[..., :d]), nchw(plan.z_sym.buf)
-            r_sym, r_idx, count = r_sym.cpu().numpy(), r_idx.cpu().numpy(), count.cpu().numpy().astype(np.int64)
-    if coder == "host":
-        tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
-        zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
-        z_jobs = [(zs[b], zi) for b in range(B)]
-        z_str = bs.encode_streams(z_jobs, te) if Kb == 1 else bs.encode_interleaved_streams(z_jobs, te, lanes=Kb)
-        sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
-        jobs = [(sl(sym_b, b, i), sl(idx_b, b, i)) for i in range(ns) for b in range(B)]
-        e_jobs = [(r_sym[b, j], r_idx[b, j]) for b in range(B) for j in range(ns)]
-        if K == 1 and Kb == 1:                                                                  # one call, as ever
-            y_str = bs.encode_streams(jobs + e_jobs, tg)
-            emb_str = y_str[ns * B:]
-        else:
-            y_str = bs.encode_streams(jobs, tg) if Kb == 1 else bs.encode_interleaved_streams(jobs, tg, lanes=Kb)
-            emb_str = bs.encode_streams(e_jobs, tg) if K == 1 else bs.encode_interleaved_streams(e_jobs, tg, lanes=K)
-        base = [y_str[i * B:(i + 1) * B] for i in range(ns)]
+            st.update(z_str=z_str, base=base, r_sym=r_sym, r_idx=r_idx)
+            return st
+        nchw = lambda t: t.permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        sym_b, idx_b, zs = nchw(plan.sym.buf[..., :d]), nchw(plan.idx.buf[..., :d]), nchw(plan.z_sym.buf)
+        r_sym, r_idx = r_sym.cpu().numpy(), r_idx.cpu().numpy()
+    tg, te = bs.Tables.of(m.gaussian_conditional), bs.Tables.of(m.entropy_bottleneck)
+    zi = np.broadcast_to(np.arange(m.N, dtype=np.int32)[:, None, None], zs.shape[1:])
+    z_jobs = [(zs[b], zi) for b in range(B)]
+    z_str = bs.encode_streams(z_jobs, te) if Kb == 1 else bs.encode_interleaved_streams(z_jobs, te, lanes=Kb)
+    sl = lambda a, b, i: a[b, i * C:(i + 1) * C]
+    jobs = [(sl(sym_b, b, i), sl(idx_b, b, i)) for i in range(ns) for b in range(B)]
+    e_jobs = [(r_sym[b, j], r_idx[b, j]) for b in range(B) for j in range(ns)]
+    if K == 1 and Kb == 1:                                                                  # one call, as ever
+        y_str = bs.encode_streams(jobs + e_jobs, tg)
+        emb_str = y_str[ns * B:]
+    else:
+        y_str = bs.encode_streams(jobs, tg) if Kb == 1 else bs.encode_interleaved_streams(jobs, tg, lanes=Kb)
+        emb_str = bs.encode_streams(e_jobs, tg) if K == 1 else bs.encode_interleaved_streams(e_jobs, tg, lanes=K)
+    st.update(z_str=z_str, base=[y_str[i * B:(i + 1) * B] for i in range(ns)], emb_str=emb_str, r_idx=r_idx)
+    return st
+
+
+def _encode_finish(st: dict, count=None) -> List[dict]:
+    """The second pass of :func:`encode_batch`: the marks' bytes from the marks' counts — bitstream.prefix_bytes on the host
+    coder, the device encode launch (which also codes the embedded strings) on the device coder — and the containers.
+    ``count``: int32 [L, B, ns], a device tensor or an array, non-decreasing in L and at most n; None: the batch's own."""
+    from . import bitstream as bs
+    m, B, H, W, qs, K, Kb, schedule = (st[k] for k in ("m", "B", "H", "W", "qs", "K", "Kb", "schedule"))
+    ns = m.ns0
+    count = st["count"] if count is None else count
+    if st["coder"] == "device":
+        dev = st["r_sym"].device
+        count = torch.as_tensor(count, dtype=torch.int32).to(dev).contiguous()
+        with torch.no_grad():
+            emb_str, cut = bs.encode_embedded_device(st["r_sym"], st["r_idx"], bs.DeviceCoderTables.of(m.gaussian_conditional, dev),
+                                                     K, count)                                  # stream b * ns + j
+        cuts = cut.reshape(len(qs), B, ns)
+        count = count.cpu().numpy().astype(np.int64)
+    else:
+        count = (count.cpu().numpy() if isinstance(count, torch.Tensor) else np.asarray(count)).astype(np.int64)
+        emb_str, r_idx, tg = st["emb_str"], st["r_idx"], bs.Tables.of(m.gaussian_conditional)
         got = _map_threads(lambda bj: bs.prefix_bytes(emb_str[bj[0] * ns + bj[1]], r_idx[bj[0], bj[1]],
                                                       count[:, bj[0], bj[1]].tolist(), tg, lanes=K),
                            [(b, j) for b in range(B) for j in range(ns)])
         cuts = np.asarray(got, dtype=np.int64).reshape(B, ns, len(qs)).transpose(2, 0, 1)
+    z_str, base = st["z_str"], st["base"]
     containers = []
     for b in range(B):
         c = {"format": FORMAT if K == 1 else FORMAT_LANES, "shape": (H // 64, W // 64), "z": [z_str[b]],
@@ -309,6 +358,7 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
         if K > 1:
             c["lanes"] = K
         if schedule is not None:
+            levels, index = schedule
             c["format"], c["lanes"] = FORMAT_SCHEDULED, K
             c["marks"]["stage"] = c["marks"].pop("q")
             c["schedule"] = {"levels": [float(v) for v in levels[b]], "index": index[b].copy()}
@@ -316,11 +366,6 @@ def encode_batch(model, x, marks: Optional[Sequence[float]] = None, save_path=No
         if Kb > 1:
             c["format"], c["lanes"], c["base_lanes"] = FORMAT_BASE_LANES, K, Kb
         containers.append(c)
-    if save_path is not None:
-        os.makedirs(save_path, exist_ok=True)
-        for b, c in enumerate(containers):
-            with open(os.path.join(save_path, "embedded.pkl" if B == 1 else f"embedded_{b}.pkl"), "wb") as f:
-                pickle.dump(c, f)
     return containers
 
 
@@ -1078,6 +1123,40 @@ class EmbeddedDecoder:
             for _, _, groups in sweep_groups(len(pos), self.B, self.H, self.W):
                 for l0, l1 in groups:
                     t = dp.tail_counts(count[l0:l1], use_graph)
+                    for i, g in enumerate(pos[l0:l1]):
+                        out[g] = self._result(t, i)
+        return out
+
+    def decode_marks(self, ks: Sequence[int]) -> List[dict]:
+        """{"x_hat", "y_hat"} of the batch per mark of ``ks`` (any marks 0 .. L-1 in any order), every slice at the element
+        count the container's OWN mark states (``marks["count"][k]``), not at a count derived from the decoder's sigma.  On an
+        ordinary container mark k equals ``decode_qualities([q_k])`` bit for bit, on a scheduled one ``decode_stages([k])``;
+        the marks of a tile of a picture with picture-wide marks state the picture's counts, which no
+        quality of the tile alone gives.  ValueError when a container holds too little for a mark."""
+        from .control import sweep_groups
+        ks = list(ks)
+        rows = [np.asarray(c["marks"]["count"], dtype=np.int64).reshape(-1, self.m.ns0) for c in self.containers]
+        n_marks = min(r.shape[0] for r in rows)
+        if not ks or any(isinstance(k, bool) or int(k) != k or not 0 <= int(k) < n_marks for k in ks):
+            raise ValueError(f"marks must be integers in 0..{n_marks - 1} (the marks every container carries), got {ks}")
+        ks = [int(k) for k in ks]
+        pos = sorted(range(len(ks)), key=lambda g: ks[g])                  # a container's counts never decrease with the mark
+        host = np.stack([np.stack([r[ks[g]] for r in rows]) for g in pos])  # [len(ks), B, ns]
+        if (np.diff(host, axis=0) < 0).any() or (host < 0).any():
+            raise ValueError("EmbeddedDecoder.decode_marks: a container's mark counts decrease with the mark or are negative")
+        for i, g in enumerate(pos):
+            short = np.argwhere(host[i] > self._avail)
+            if len(short):
+                b, j = (int(v) for v in short[0])
+                raise ValueError(f"EmbeddedDecoder: mark {ks[g]} needs {int(host[i, b, j])} elements of slice {j} of image {b}, "
+                                 f"its container holds {int(self._avail[b, j])}")
+        with torch.no_grad():
+            self._own()
+            out: List[Optional[dict]] = [None] * len(ks)
+            count = host.astype(np.int32)
+            for _, _, groups in sweep_groups(len(pos), self.B, self.H, self.W):
+                for l0, l1 in groups:
+                    t = self.dp.tail_counts(count[l0:l1], self.m.use_graph)
                     for i, g in enumerate(pos[l0:l1]):
                         out[g] = self._result(t, i)
         return out

@@ -426,14 +426,21 @@ def embedded_rd(model, images: Sequence[torch.Tensor], qualities: Sequence[float
 
 
 def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int = 256, overlap: int = 32, coder=None, lanes: int = 1,
-             base_lanes: int = 1, group: Optional[int] = None):
+             base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile"):
     """:func:`embedded_rd` for ONE picture of any size coded in tiles (tiled.encode / PictureDecoder): the
     picture, fp32 [3, H, W] or [1, 3, H, W], is coded ONCE with ``qualities`` (non-decreasing, as marks) as its marks, and
     mark k is decoded from ``data[:round_end[k]]``, the prefix that holds every tile at exactly that mark.  One dict per
     quality: q, bytes (``round_end[k]``: picture header, every tile's head and the rounds up to k), bpp (8 * bytes / (H W),
     the true size), psnr against the original (:func:`compute_psnr`; nothing is padded or cropped), enc_s (the one encode) and
     dec_s (parsing that prefix and decoding the whole picture at q).  Quality q keeps a quantile PER TILE, so these rows are
-    not those of the untiled forward; and nothing here measures the seams."""
+    not those of the untiled forward; and nothing here measures the seams.
+
+    ``allocation`` = "picture" (DESIGN section 9w): the marks are picture-wide (``tiled.encode(allocation="picture")``) and mark
+    k is decoded with ``decode(mark=k)``.  Every row also carries ``allocation`` and ``kept_min`` / ``kept_max``: the smallest
+    and largest fraction of its progressive elements that a tile keeps at that mark, from the counts in the tiles' heads —
+    the spread that a picture-wide threshold opens between flat and busy tiles."""
+    import numpy as np
+    from . import embedded as EB
     from . import tiled as TL
     x = image if image.dim() == 4 else image.unsqueeze(0)
     H, W = int(x.shape[2]), int(x.shape[3])
@@ -442,18 +449,25 @@ def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int =
     with torch.no_grad():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        data = TL.encode(model, x, tile=tile, overlap=overlap, marks=qs, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group)
+        data = TL.encode(model, x, tile=tile, overlap=overlap, marks=qs, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group,
+                         allocation=allocation)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        ends = TL.layout(data)["round_end"]
+        lay = TL.layout(data)
+        ends = lay["round_end"]
+        heads = [data[o:o + n] for row in lay["head"] for o, n in row if n]
+        count = np.asarray([EB.layout(h)["marks"]["count"] for h in heads], dtype=np.float64)            # [tiles, marks, ns]
+        kept = count.sum(-1) / (lay["ns"] * model.dim_chunk * (lay["th"] // 16) * (lay["tw"] // 16))    # [tiles, marks]
         for k, q in enumerate(qs):
             torch.cuda.synchronize()
             t2 = time.perf_counter()
-            x_hat = TL.PictureDecoder(model, data[:ends[k]], coder=coder, group=group).decode(q=q)
+            dec = TL.PictureDecoder(model, data[:ends[k]], coder=coder, group=group)
+            x_hat = dec.decode(mark=k) if allocation == "picture" else dec.decode(q=q)
             torch.cuda.synchronize()
             t3 = time.perf_counter()
             rows.append({"q": q, "bytes": int(ends[k]), "bpp": 8.0 * ends[k] / (H * W), "psnr": compute_psnr(x, x_hat.unsqueeze(0)),
-                         "enc_s": t1 - t0, "dec_s": t3 - t2})
+                         "enc_s": t1 - t0, "dec_s": t3 - t2, "allocation": allocation, "kept_min": float(kept[:, k].min()),
+                         "kept_max": float(kept[:, k].max())})
     return rows
 
 

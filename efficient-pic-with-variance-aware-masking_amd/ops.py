@@ -760,6 +760,49 @@ def rank_scatter(ranked: torch.Tensor, perm: torch.Tensor, count: torch.Tensor, 
                                       ps, ls, level_id.data_ptr(), sym.C, stream_ptr()), "vam_rank_scatter")
 
 
+# ------------------------------------------------------------- pooled selection (picture-wide marks)
+def _pool_keys_shape(keys: torch.Tensor):
+    assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.dim() == 3 and keys.is_cuda, (keys.dtype, tuple(keys.shape))
+    return tuple(int(v) for v in keys.shape)
+
+
+def pool_keys(sigma: View, perm: torch.Tensor, keys: torch.Tensor, t0: int = 0, n_slice: int = 1):
+    """Rows ``[t0, t0 + sigma.B)`` of ``keys`` (the bits of uint32 in an int32 tensor [T, n_slice, n]) get every (tile, slice)
+    segment of ``sigma`` in the rank order ``perm`` (:func:`variance_rank` on the same view) as order-preserving keys that
+    ascend as sigma descends; -0.0 == +0.0 and every NaN is the key 0xFFFFFFFF, last.  One launch; capturable."""
+    T, ns, n = _pool_keys_shape(keys)
+    slice_C = sigma.C // n_slice
+    hw = sigma.H * sigma.W
+    assert slice_C * n_slice == sigma.C and ns == n_slice and n == hw * slice_C, (sigma.C, n_slice, ns, n, hw)
+    assert 0 <= t0 and t0 + sigma.B <= T, (t0, sigma.B, T)
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() == sigma.B * n_slice * n
+    assert keys.device == sigma.buf.device == perm.device
+    L.check(L.load().vam_pool_keys(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, perm.data_ptr(), sigma.B, n_slice, hw, slice_C,
+                                   keys.data_ptr(), int(t0), T, stream_ptr()), "vam_pool_keys")
+
+
+def pooled_select(keys: torch.Tensor, prs: Sequence[float], thr: torch.Tensor):
+    """``thr`` fp32 [len(prs), n_slice] gets, per slice j, ``torch.quantile(pool_j, float32(1 - 0.1 q))`` of the pool of all
+    T * n sigmas behind ``keys[:, j]`` (:func:`pool_keys`; every row sorted) for the non-decreasing qualities ``prs`` > 0 (up
+    to L.VAM_MAX_LAYER_LEVELS), bit for bit; -inf for q >= 10, NaN when the pool holds one.  One launch; capturable."""
+    T, ns, n = _pool_keys_shape(keys)
+    prs = [float(p_) for p_ in prs]
+    assert thr.dtype == torch.float32 and thr.is_contiguous() and tuple(thr.shape) == (len(prs), ns) and thr.device == keys.device
+    arr = (C.c_double * max(len(prs), 1))(*prs)
+    L.check(L.load().vam_pooled_select(keys.data_ptr(), T, ns, n, arr, len(prs), thr.data_ptr(), stream_ptr()), "vam_pooled_select")
+
+
+def threshold_counts(keys: torch.Tensor, thr: torch.Tensor, count: torch.Tensor):
+    """``count`` int32 [L, T, n_slice] = how many keys of row (t, j) of ``keys`` hold a sigma >= ``thr[k, j]`` (fp32
+    [L, n_slice] on the device), compared as floats; a threshold of -inf counts the whole row.  One launch; capturable."""
+    T, ns, n = _pool_keys_shape(keys)
+    assert thr.dtype == torch.float32 and thr.is_contiguous() and thr.dim() == 2 and thr.shape[1] == ns and thr.device == keys.device
+    nl = int(thr.shape[0])
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (nl, T, ns) and count.device == keys.device
+    L.check(L.load().vam_threshold_counts(keys.data_ptr(), T, ns, n, thr.data_ptr(), nl, count.data_ptr(), stream_ptr()),
+            "vam_threshold_counts")
+
+
 def tile_extract(image: torch.Tensor, coords: torch.Tensor, out: torch.Tensor, overlap: int):
     """out[i, :, y, x] = image[:, min(r * Sy + y, H - 1), min(c * Sx + x, W - 1)] for (r, c) = coords[i]: the tiles of a
     picture ``image`` fp32 [3, H, W], edge replicated, ``coords`` int32 [n, 2] on the device, ``out`` fp32

@@ -20,9 +20,16 @@ stream down to a window and a number of rounds on the host alone, and what it re
 
 :func:`encode` and :class:`PictureDecoder` run the tiles, a group at a time, through ``embedded.encode_batch`` and
 ``embedded.EmbeddedDecoder`` unchanged: an image codes and decodes bit for bit the same alone or in a batch, so neither the
-bytes nor the pixels depend on the grouping.  Quality q keeps a quantile PER TILE: a tiled picture at q is not the untiled
-forward at q.  Out of scope: schedules (``embedded-3``), incremental feeding, rate allocation between tiles and a tile cache
-across ``decode`` calls.
+bytes nor the pixels depend on the grouping.  By default (``allocation="tile"``) quality q keeps a quantile PER TILE: a
+tiled picture at q is not the untiled forward at q.  Out of scope: schedules (``embedded-3``), incremental feeding and a tile
+cache across ``decode`` calls.
+
+Picture-wide marks: ``encode(..., allocation="picture")`` takes, per mark and slice, ONE sigma threshold
+over the pool of all tiles' sigmas (``torch.quantile`` of the pool, bit for bit; ``csrc/pooled_select.hip``) and marks every
+tile with the count of its elements at or above it.  Such a stream has a version-2 header: the version-1 fields and table,
+then u16 allocation (1), n_marks, ns, reserved (0) and the thresholds float32 [n_marks][ns], then the u64 total, under the same
+CRC.  Tile heads stay ordinary embedded headers.  ``PictureDecoder.decode(mark=k)`` decodes every tile at its header's counts
+of mark k and, on a version-2 stream, checks them against the thresholds on its own sigma.
 """
 from __future__ import annotations
 
@@ -35,13 +42,18 @@ import numpy as np
 from . import embedded as EB
 
 MAGIC = b"VAMp"
-VERSION = 1
+VERSION = 1                                # allocation="tile": every tile marks its own quantiles
+VERSION_POOLED = 2                         # allocation="picture" (DESIGN section 9w): the header also carries the picture's thresholds
+ALLOCATIONS = ("tile", "picture")
+_ALLOC_PICTURE = 1                         # the one allocation value a version-2 header may state
 _PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
 PREAMBLE_BYTES = EB.PREAMBLE_BYTES
 _FIXED = struct.Struct("<IIHHHHHH")        # H, W, th / 64, tw / 64, V, R, C, n_rounds
+_POOLED = struct.Struct("<HHHH")           # version 2, after the table: allocation, n_marks, ns, reserved (0); then f32 [n_marks][ns]
 _MAX_HEADER = EB._MAX_HEADER
 MAX_SIDE = 1 << 24                         # csrc/tiles.hip: the largest picture side
 MAX_GROUP = 32
+MAX_POOL = 16000000                        # csrc/pooled_select.hip: torch.quantile's largest input
 
 
 # ------------------------------------------------------------------------------------------------------------- geometry
@@ -111,7 +123,7 @@ class _Picture:
     """A parsed picture header and the byte arithmetic of the body that follows from it."""
 
     def __init__(self, d, what: str):
-        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
+        version, _, hlen, crc = _PREAMBLE.unpack_from(d, 0)[1:]
         end = PREAMBLE_BYTES + hlen
         if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
             raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
@@ -122,9 +134,35 @@ class _Picture:
         if (g["R"], g["C"]) != (R, C) or any(grid(H, W, 64 * max(th, tw), V)[k] != g[k] for k in ("th", "tw")):
             raise ValueError(f"{what}: the header contradicts itself: {H} x {W} in tiles of {64 * th} x {64 * tw} with overlap {V} "
                              f"is no grid of {R} x {C}")
-        if hlen != _FIXED.size + 4 * R * C * (1 + nr) + 8:
+        table_end = _FIXED.size + 4 * R * C * (1 + nr)
+        self.version, self.thresholds = version, None
+        if version == VERSION_POOLED:
+            # every refusal of the extension names the version: a version-1 header read as version 2 says so
+            v2 = f"{what}: picture codestream version {VERSION_POOLED}: the header contradicts itself"
+            if hlen < table_end + _POOLED.size + 8:
+                raise ValueError(f"{v2}: {R} x {C} tiles of {nr} rounds and the allocation fields take at least "
+                                 f"{table_end + _POOLED.size + 8} bytes, it states {hlen}")
+            alloc, nm, ns, zero = _POOLED.unpack_from(d, PREAMBLE_BYTES + table_end)
+            if hlen != table_end + _POOLED.size + 4 * nm * ns + 8:
+                raise ValueError(f"{v2}: {R} x {C} tiles of {nr} rounds and thresholds of {nm} marks x {ns} slices take "
+                                 f"{table_end + _POOLED.size + 4 * nm * ns + 8} bytes, it states {hlen}")
+            if alloc != _ALLOC_PICTURE or zero:
+                raise ValueError(f"{v2}: allocation {alloc} (reserved field {zero}); this reader knows allocation {_ALLOC_PICTURE}, "
+                                 "picture-wide marks")
+            if nm < 1 or ns < 1:
+                raise ValueError(f"{v2}: thresholds of {nm} marks x {ns} slices")
+            thr = np.frombuffer(d, dtype="<f4", count=nm * ns, offset=PREAMBLE_BYTES + table_end + _POOLED.size) \
+                .astype(np.float32).reshape(nm, ns)
+            with np.errstate(invalid="ignore"):
+                up = np.argwhere(thr[1:] > thr[:-1])
+            if len(up):
+                k, j = (int(v) for v in up[0])
+                raise ValueError(f"{v2}: the threshold of slice {j} rises from mark {k} ({thr[k, j]}) to mark {k + 1} ({thr[k + 1, j]}): "
+                                 "a higher quality never keeps less")
+            self.thresholds = thr
+        elif hlen != table_end + 8:
             raise ValueError(f"{what}: the header contradicts itself: {R} x {C} tiles of {nr} rounds take "
-                             f"{_FIXED.size + 4 * R * C * (1 + nr) + 8} bytes, it states {hlen}")
+                             f"{table_end + 8} bytes, it states {hlen}")
         self.g, self.nr, self.header_end = g, nr, end
         self.table = np.frombuffer(d, dtype="<u4", count=R * C * (1 + nr), offset=PREAMBLE_BYTES + _FIXED.size) \
             .astype(np.int64).reshape(R * C, 1 + nr)
@@ -171,9 +209,9 @@ def _header_end(d, what: str) -> Optional[int]:
     magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
     if magic != MAGIC:
         raise ValueError(f"{what}: not a picture codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
-    if version != VERSION or reserved:
+    if version not in (VERSION, VERSION_POOLED) or reserved:
         raise ValueError(f"{what}: picture codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
-                         f"reader knows version {VERSION}")
+                         f"reader knows versions {VERSION} and {VERSION_POOLED}")
     if not _FIXED.size + 4 + 8 <= hlen <= _MAX_HEADER:
         raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 12} .. {_MAX_HEADER}")
     return PREAMBLE_BYTES + hlen
@@ -240,32 +278,44 @@ def _tile_meta(d, s: _Picture, what: str) -> Optional[dict]:
                              f"head and the first {s.nr} round pieces of the tile's own codestream, {want}")
         if first is None:
             first, rc0 = lay, s.rc(i)
+            if s.thresholds is not None and tuple(s.thresholds.shape) != (len(lay["marks"]), lay["ns"]):
+                raise ValueError(f"{what}: the header contradicts tile {rc0}: thresholds of {s.thresholds.shape[0]} marks x "
+                                 f"{s.thresholds.shape[1]} slices, the tile carries {len(lay['marks'])} marks of {lay['ns']} slices")
         else:
             _unlike(lay, first, s.rc(i), rc0, what)
     return first
 
 
-def _assemble(g: dict, table: np.ndarray, get) -> bytes:
-    """The picture codestream of ``table`` int64 [R C, 1 + nr]; ``get(i, k)`` gives the bytes of column k of tile i."""
+def _assemble(g: dict, table: np.ndarray, get, thresholds: Optional[np.ndarray] = None) -> bytes:
+    """The picture codestream of ``table`` int64 [R C, 1 + nr]; ``get(i, k)`` gives the bytes of column k of tile i.
+    ``thresholds`` fp32 [n_marks][ns]: a version-2 header that carries them (picture-wide marks)."""
     nr = table.shape[1] - 1
+    ext = b""
+    if thresholds is not None:
+        thr = np.ascontiguousarray(thresholds, dtype="<f4")
+        if thr.ndim != 2 or not (1 <= thr.shape[0] <= 0xFFFF and 1 <= thr.shape[1] <= 0xFFFF):
+            raise ValueError(f"thresholds are float32 [n_marks][ns], got {list(thr.shape)}")
+        ext = _POOLED.pack(_ALLOC_PICTURE, thr.shape[0], thr.shape[1], 0) + thr.tobytes()
     if (table >= 1 << 32).any():
         raise ValueError("a head or round piece of 2^32 bytes or more does not fit the header's table")
-    hlen = _FIXED.size + 4 * table.size + 8
+    hlen = _FIXED.size + 4 * table.size + len(ext) + 8
     if hlen > _MAX_HEADER:
         raise ValueError(f"the header would take {hlen} bytes, the limit is {_MAX_HEADER}; use larger tiles")
     if nr > 0xFFFF:
         raise ValueError(f"{nr} rounds; the format carries up to 65535")
     header = _FIXED.pack(g["H"], g["W"], g["th"] // 64, g["tw"] // 64, g["V"], g["R"], g["C"], nr) + table.astype("<u4").tobytes() \
-        + struct.pack("<Q", PREAMBLE_BYTES + hlen + int(table.sum()))
-    out = [_PREAMBLE.pack(MAGIC, VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
+        + ext + struct.pack("<Q", PREAMBLE_BYTES + hlen + int(table.sum()))
+    out = [_PREAMBLE.pack(MAGIC, VERSION_POOLED if ext else VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
     out += [get(i, k) for k in range(1 + nr) for i in range(table.shape[0]) if table[i, k]]
     return b"".join(out)
 
 
-def pack(H: int, W: int, tile: int, overlap: int, tile_streams) -> bytes:
+def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None) -> bytes:
     """The picture codestream of R C whole tile codestreams (``embedded.to_bytes``), given in raster order as one flat
     sequence or as [R][C]; None marks an absent tile.  Pure framing on the host.  ValueError for a wrong count, a cut or
-    scheduled tile, a tile of another shape and tiles that differ in marks, lanes or base_lanes."""
+    scheduled tile, a tile of another shape and tiles that differ in marks, lanes or base_lanes.  ``thresholds`` fp32
+    [n_marks][ns]: the picture-wide thresholds behind the tiles' marks, one row per mark, never rising
+    with the mark; the header is then version 2 and carries them.  None: version 1, byte for byte as ever."""
     g = grid(H, W, tile, overlap)
     try:
         streams = list(tile_streams)
@@ -299,8 +349,16 @@ def pack(H: int, W: int, tile: int, overlap: int, tile_streams) -> bytes:
     width = 2 + len(first["round_end"])
     table = np.asarray([row if row is not None else [0] * width for row in rows], dtype=np.int64)
     edges = np.concatenate([np.zeros((len(rows), 1), dtype=np.int64), np.cumsum(table, axis=1)], axis=1)
+    if thresholds is not None:
+        thresholds = np.asarray(thresholds, dtype=np.float32)
+        if tuple(thresholds.shape) != (len(first["marks"]), first["ns"]):
+            raise ValueError(f"pack: thresholds are float32 [{len(first['marks'])} marks][{first['ns']} slices], got "
+                             f"{list(thresholds.shape)}")
+        with np.errstate(invalid="ignore"):
+            if (thresholds[1:] > thresholds[:-1]).any():
+                raise ValueError("pack: a threshold rises with the mark: a higher quality never keeps less")
     try:
-        return _assemble(g, table, lambda i, k: bytes(views[i][int(edges[i, k]):int(edges[i, k + 1])]))
+        return _assemble(g, table, lambda i, k: bytes(views[i][int(edges[i, k]):int(edges[i, k + 1])]), thresholds)
     except ValueError as e:
         raise ValueError(f"pack: {e}") from e
 
@@ -322,7 +380,8 @@ def layout(data) -> dict:
     k < n_rounds: ``data[:round_end[k]]`` holds every present tile exactly at its mark k (a whole stream has one round more
     than marks, and its last ``round_end`` is ``total``).  ``marks``, ``lanes``, ``base_lanes``, ``ns`` and ``format`` are
     those of the tiles, read from the heads that ``data`` holds whole (all checked against the table and each other); None
-    while it holds none."""
+    while it holds none.  ``allocation``: "tile" (version 1) or "picture" (version 2), and then
+    ``thresholds`` float32 [marks][ns], the picture-wide sigma thresholds behind the tiles' marks (None for "tile")."""
     d, s = _parse(data, "layout")
     g, meta = s.g, _tile_meta(d, s, "layout")
     R, C = g["R"], g["C"]
@@ -333,6 +392,8 @@ def layout(data) -> dict:
                 "head": seg(0), "piece": [seg(1 + k) for k in range(s.nr)], "round_end": list(s.round_end)})
     for key in _ALIKE + ("format",):
         out[key] = meta[key] if meta is not None else None
+    out["allocation"] = ALLOCATIONS[s.version == VERSION_POOLED]
+    out["thresholds"] = None if s.thresholds is None else s.thresholds.copy()
     return out
 
 
@@ -351,7 +412,8 @@ def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
     """A shorter picture codestream of the same picture: only the tiles ``tiles_for(window)`` (None: those present) and only
     the first ``rounds`` rounds (None: all it has).  What a server does to crop and to cut the quality, without the model.
     ``data`` must hold what is kept.  ``extract(data)`` is ``data``; an extract of an extract is an extract.  ValueError
-    names a wanted tile that ``data`` lacks."""
+    names a wanted tile that ``data`` lacks.  An extract keeps the version, and a version-2 stream its thresholds: the pool
+    is the picture's, not the window's."""
     d, s = _parse(data, "extract")
     _tile_meta(d, s, "extract")
     nr = s.nr if rounds is None else _int(rounds, "extract: rounds")
@@ -372,7 +434,7 @@ def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
         i, k = (int(v) for v in short[0])
         raise ValueError(f"extract: {len(d)} bytes end before {'the head' if k == 0 else f'round {k - 1}'} of tile {s.rc(i)} does; "
                          "a codestream is extracted from bytes that hold what is kept")
-    return _assemble(s.g, table, lambda i, k: bytes(d[int(s.off[k, i]):int(s.off[k, i] + s.size[k, i])]))
+    return _assemble(s.g, table, lambda i, k: bytes(d[int(s.off[k, i]):int(s.off[k, i] + s.size[k, i])]), s.thresholds)
 
 
 # ---------------------------------------------------------------------------------------------------- encoder and decoder
@@ -395,13 +457,22 @@ def _check_group(group, th: int, tw: int, what: str) -> int:
 
 
 def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Sequence[float]] = None, coder: Optional[str] = None,
-           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None) -> bytes:
+           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile") -> bytes:
     """The picture codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device, any H, W >= 1: the tiles are cut
     ``group`` at a time (vam_tile_extract, one launch per group), each group goes through ``embedded.encode_batch`` (``marks``,
     ``coder``, ``lanes`` and ``base_lanes`` are its) and ``embedded.to_bytes``, and :func:`pack` frames them.  ``group``: the
-    tiles per batch, by default the most that one plan holds, at most 32; the bytes do not depend on it."""
+    tiles per batch, by default the most that one plan holds, at most 32; the bytes do not depend on it.
+
+    ``allocation`` = "tile" (the default, version-1 bytes as ever): every tile marks its own quantiles.  "picture" (DESIGN
+    section 9w): the marks are picture-wide.  Pass 1 runs every group's network, rank order and gather once
+    (``embedded._encode_front``) and writes its sigmas, in rank order, as keys into one buffer [T, ns, n] (vam_pool_keys); one
+    vam_pooled_select gives, per mark and slice, ``torch.quantile`` of the pool of ALL tiles' sigmas, one vam_threshold_counts
+    every tile's counts; pass 2 (``embedded._encode_finish``) marks the tiles with them.  The tile heads stay ordinary
+    embedded headers; the picture header is version 2 and carries the thresholds.  Marks are qualities > 0."""
     import torch
     from . import ops
+    if allocation not in ALLOCATIONS:
+        raise ValueError(f"tiled.encode: allocation is one of {ALLOCATIONS}, got {allocation!r}")
     if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() not in (3, 4) \
             or tuple(image.shape[:-2]) not in ((3,), (1, 3)):
         raise ValueError("tiled.encode: image is an fp32 tensor [3, H, W] or [1, 3, H, W], got "
@@ -413,14 +484,44 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     img = image.detach().reshape(3, H, W).contiguous()
     coords = [(r, c) for r in range(g["R"]) for c in range(g["C"])]
     streams: List[bytes] = []
+
+    def cut(i0):
+        part = coords[i0:i0 + group]
+        x = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
+        ops.tile_extract(img, torch.tensor(part, dtype=torch.int32).to(img.device), x, g["V"])
+        return x
+    if allocation == "tile":
+        with torch.no_grad():
+            for i0 in range(0, len(coords), group):
+                cs = EB.encode_batch(model, cut(i0), marks=marks, coder=coder, lanes=lanes, base_lanes=base_lanes)
+                streams += [EB.to_bytes(c) for c in cs]
+        return pack(H, W, tile, overlap, streams)
+    from . import bitstream as bs
+    from . import progressive as P
+    qs = P.check_q_list(EB.Q_LIST if marks is None else marks)
+    if qs[0] <= 0:
+        raise ValueError(f"tiled.encode: a picture-wide mark is a quality > 0, got {qs}")
+    coder, K, Kb = P._check_coder(model, coder), bs.check_lanes(lanes), bs.check_lanes(base_lanes)
+    T, ns, n = len(coords), model.ns0, model.dim_chunk * (g["th"] // 16) * (g["tw"] // 16)
+    if T * n > MAX_POOL:
+        raise ValueError(f"tiled.encode: the pool of a slice holds {T} tiles x {n} = {T * n} sigmas, torch.quantile and "
+                         f"vam_pooled_select take up to {MAX_POOL}; use allocation='tile'")
     with torch.no_grad():
-        for i0 in range(0, len(coords), group):
-            part = coords[i0:i0 + group]
-            x = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
-            ops.tile_extract(img, torch.tensor(part, dtype=torch.int32).to(img.device), x, g["V"])
-            cs = EB.encode_batch(model, x, marks=marks, coder=coder, lanes=lanes, base_lanes=base_lanes)
+        keys = torch.empty((T, ns, n), dtype=torch.int32, device=img.device)      # the bits of uint32 keys
+        passes = []
+        for i0 in range(0, T, group):                                             # pass 1: the network runs once per tile
+            st = EB._encode_front(model, cut(i0), qs, coder, K, Kb)
+            ops.pool_keys(st.pop("std_p"), st.pop("perm"), keys, t0=i0, n_slice=ns)
+            passes.append((i0, st))
+        thr = torch.empty((len(qs), ns), dtype=torch.float32, device=img.device)
+        count = torch.empty((len(qs), T, ns), dtype=torch.int32, device=img.device)
+        ops.pooled_select(keys, qs, thr)
+        ops.threshold_counts(keys, thr, count)
+        for i0, st in passes:                                                     # pass 2: the marks' bytes from the picture's counts
+            cs = EB._encode_finish(st, count[:, i0:i0 + st["B"]].contiguous())
             streams += [EB.to_bytes(c) for c in cs]
-    return pack(H, W, tile, overlap, streams)
+        thr = thr.cpu().numpy()
+    return pack(H, W, tile, overlap, streams, thresholds=thr)
 
 
 class PictureDecoder:
@@ -452,16 +553,68 @@ class PictureDecoder:
             self._ramps = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ramps(self.grid["V"]))
         return self._ramps
 
-    def _decode_tiles(self, containers, q):
+    def _decode_tiles(self, containers, q, mark=None, part=None):
         dec = EB.EmbeddedDecoder(self.m, containers, coder=self.coder)
-        return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
+        if mark is None:
+            return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
+        x_hat = dec.decode_marks([mark])[0]["x_hat"]
+        if self._s.thresholds is not None:
+            self._check_pooled(dec, containers, part)
+        return x_hat
 
-    def decode(self, window=None, q: Optional[float] = None, dtype=None):
+    def _check_pooled(self, dec, containers, part):
+        """A version-2 header's thresholds against the tiles' marks: the decoder's OWN sigma, in its own rank order
+        (vam_pool_keys), counted against the header's thresholds (vam_threshold_counts), must give the counts the tiles'
+        marks state, for every mark."""
+        import torch
+        from . import ops
+        dp, ns = dec.dp, self.m.ns0
+        thr = np.ascontiguousarray(self._s.thresholds, dtype=np.float32)
+        with torch.no_grad():
+            dec._own()
+            with dp.runner.on_stream():
+                keys = torch.empty((dp.B, ns, dp.perm.shape[2]), dtype=torch.int32, device=dp.device)
+                count = torch.empty((thr.shape[0], dp.B, ns), dtype=torch.int32, device=dp.device)
+                ops.pool_keys(dp.sc.std_p, dp.perm, keys, t0=0, n_slice=ns)
+                ops.threshold_counts(keys, torch.from_numpy(thr).to(dp.device), count)
+                got = count.cpu().numpy()
+        want = np.stack([np.asarray(c["marks"]["count"], dtype=np.int64).reshape(-1, ns) for c in containers], axis=1)
+        bad = np.argwhere(got != want) if got.shape == want.shape else np.zeros((1, 3), dtype=np.int64)
+        if len(bad):
+            k, b, j = (int(v) for v in bad[0])
+            raise ValueError(f"tile {part[b] if part is not None else b}, mark {k}, slice {j}: the header's picture-wide threshold "
+                             f"{thr[k, j]} keeps {int(got[k, b, j])} elements of this tile's sigma, the tile's mark states "
+                             f"{int(want[k, b, j])}: thresholds and tiles are not of one picture")
+
+    def _mark_of(self, q, mark) -> Optional[int]:
+        """The mark a ``decode`` call means: ``mark`` itself, or, on a version-2 stream, the mark whose quality ``q`` is."""
+        marks = self.meta["marks"]
+        if mark is not None:
+            if q is not None:
+                raise ValueError("PictureDecoder.decode: give q or mark, not both")
+            mark = _int(mark, "PictureDecoder.decode: mark")
+            if not 0 <= mark < len(marks):
+                raise ValueError(f"PictureDecoder.decode: mark is 0 .. {len(marks) - 1} (the marks {marks}), got {mark}")
+            return mark
+        if q is None or self._s.thresholds is None:
+            return None
+        if float(q) not in marks:
+            raise ValueError(f"PictureDecoder.decode: quality {q} is not marked; this picture's marks are picture-wide (allocation "
+                             f"'picture') and a picture-wide quality exists only where the encoder pooled: the marks are {marks}")
+        return marks.index(float(q))
+
+    def decode(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, dtype=None):
         """The window (y0, x0, h, w) of the picture (None: all of it): fp32 [3, h, w], or uint8 [h, w, 3] for
         ``dtype=torch.uint8`` (round half to even of clamp(v, 0, 1) * 255, as evaluate.write_image).  ``q`` = None: from
         everything ``data`` holds of every tile (``EmbeddedDecoder.decode``); a quality: ``decode_qualities([q])``, every tile
         at its own quantile.  Only ``tiles_for(window)`` are decoded (``last_tiles``).  ValueError names the tile (r, c) that
-        the window needs and the codestream lacks, or whose bytes end before ``q``."""
+        the window needs and the codestream lacks, or whose bytes end before ``q``.
+
+        ``mark`` = k (exclusive with ``q``): every tile at the counts its own header states for mark k
+        (``EmbeddedDecoder.decode_marks``), for both versions.  On a version-2 stream (picture-wide marks)
+        every decoded tile is also checked: its own sigma against the header's thresholds must reproduce its marks' counts,
+        else a ValueError names tile, mark and slice; and ``q`` is accepted only when it is a marked quality and then means
+        that mark: any other q is a ValueError that lists the marks."""
         import torch
         from . import _lib as L
         from . import ops
@@ -469,6 +622,7 @@ class PictureDecoder:
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
+        mark = self._mark_of(q, mark)
         y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
         tiles = tiles_for(g, (y0, x0, h, w))
         for r, c in tiles:
@@ -481,11 +635,11 @@ class PictureDecoder:
                 part = tiles[i0:i0 + self.group]
                 cs = [EB.from_bytes(s.stream(self._d, r * g["C"] + c)) for r, c in part]
                 try:
-                    x_hat = self._decode_tiles(cs, q)
+                    x_hat = self._decode_tiles(cs, q, mark, part)
                 except ValueError:
                     for rc, c1 in zip(part, cs):            # a tile decodes alone as in its group: find the one that is refused
                         try:
-                            self._decode_tiles([c1], q)
+                            self._decode_tiles([c1], q, mark, [rc])
                         except ValueError as e:
                             raise ValueError(f"PictureDecoder.decode: tile {rc}: {e}") from e
                     raise

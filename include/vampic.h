@@ -384,6 +384,27 @@ int vam_variance_rank_staged(const float* sigma, int ld, long batch_stride, long
                              int ld_stage, int n_batch, int n_slice, int n_pix, int C, int32_t* perm_out, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ pooled selection (picture-wide marks) */
+/* Picture-wide quality marks of tiled pictures (vampic.tiled).  The pool of slice j is the multiset of
+ * the T * n sigmas of slice j of all T tiles of a picture; quality q's threshold is torch.quantile(pool_j, float32(1 - 0.1 q))
+ * with vam_variance_mask's arithmetic at N = T * n, bit for bit.  keys is uint32 [T][n_slice][n] on the device.
+ * vam_pool_keys: for the n_batch tiles of the window vam_variance_rank read (same sigma, strides and perm), row
+ *   (t0 + b, j) gets the segment's sigmas in rank order as keys that ascend as sigma descends, with vam_variance_rank's
+ *   canonicalisation: -0.0 == +0.0, every NaN the key 0xFFFFFFFF, last.  An entry of perm outside [0, n) writes that key.
+ * vam_pooled_select: thr_out[k][j] (fp32 [n_levels][n_slice]) for the non-decreasing qualities prs[k] > 0, 1 <= n_levels <=
+ *   VAM_MAX_LAYER_LEVELS.  Every row of keys must be sorted (vam_pool_keys of a rank order is).  q >= 10 stores -inf; a NaN
+ *   anywhere in pool_j stores NaN.  One workgroup per (slice, level) descends the 32 key bits; nothing waits across
+ *   workgroups.  A pool above 16 000 000 elements is VAM_EINVAL, as torch.quantile refuses it.
+ * vam_threshold_counts: count_out[k][t][j] (int32 [n_levels][T][n_slice]) = #{r : sigma(keys[t][j][r]) >= thr[k][j]}, compared
+ *   as floats (a NaN threshold counts 0); a threshold of -inf counts n.  thr is read on the device.
+ * No allocation, no atomics: all three can be captured.  Bad arguments are VAM_EINVAL and launch nothing. */
+int vam_pool_keys(const float* sigma, int ld, long batch_stride, long slice_stride, const int32_t* perm, int n_batch,
+                  int n_slice, int n_pix, int C, uint32_t* keys, int t0, int T, void* stream);
+int vam_pooled_select(const uint32_t* keys, int T, int n_slice, int n, const double* prs, int n_levels, float* thr_out,
+                      void* stream);
+int vam_threshold_counts(const uint32_t* keys, int T, int n_slice, int n, const float* thr, int n_levels, int32_t* count_out,
+                         void* stream);
+
 /* ------------------------------------------------------------------ tiled pictures */
 /* Tiled pictures (vampic.tiled).  A picture of H x W (any sizes >= 1) is covered by tiles of th x tw with
  * overlap V, 0 <= 2 V <= min(th, tw): strides Sy = th - V and Sx = tw - V, grid R = max(1, ceil((H - V) / Sy)) by

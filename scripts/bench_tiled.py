@@ -11,10 +11,16 @@ synchronisation to the next and the median of the repetitions is reported:
   and in percent of the total; and, for the picture's top-left 1024 x 2048, the largest single image the rank order takes,
   the same numbers beside ``embedded.encode_batch`` of that crop as ONE image (its header, z and base against its total).
 
+``--allocation tile picture`` adds ``"allocations"``: per allocation the encode time, the stream's size,
+the picture header's bytes and, per mark, the smallest and largest fraction of its progressive elements a tile keeps; and for
+"picture" the three kernels of csrc/pooled_select.hip alone on the picture's own key buffer (HIP events over 50 launches;
+vam_pool_keys for the last group of tiles beside a ``copy_`` of the rows it writes), and ``decode(mark=k)`` of the picture-wide
+stream beside ``decode(q=q_k)`` of the per-tile one for the middle mark.  Without the flag the line is what it always was.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
-                                  [--coder host|device] [--lanes 1] [--base-lanes 1]
+                                  [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
 """
 import argparse
 import json
@@ -63,6 +69,60 @@ def overhead(data, TL):
             "overhead_pct": round(100.0 * lay["need_bytes"] / lay["total"], 3)}
 
 
+def kept_spread(data, net, TL, EB):
+    """Per mark (min, max) over the tiles of the fraction of a tile's progressive elements its mark keeps."""
+    import numpy as np
+    lay = TL.layout(data)
+    count = np.asarray([EB.layout(data[o:o + n])["marks"]["count"] for row in lay["head"] for o, n in row if n], dtype=np.float64)
+    kept = count.sum(-1) / (lay["ns"] * net.dim_chunk * (lay["th"] // 16) * (lay["tw"] // 16))
+    return [[round(float(kept[:, k].min()), 4), round(float(kept[:, k].max()), 4)] for k in range(kept.shape[1])]
+
+
+def allocations(a, net, x, g, kw, TL, EB, ops):
+    """The ``--allocation`` section: see the module docstring."""
+    from vampic import bitstream as bs, progressive as P
+    out, streams = {"marks": [float(q) for q in EB.Q_LIST]}, {}
+    for name in a.allocation:
+        ms, data = wall_ms(lambda: TL.encode(net, x, allocation=name, **kw), a.warmup, a.reps)
+        streams[name] = data
+        lay = TL.layout(data)
+        out[name] = {"encode_ms": round(ms, 2), "total_bytes": lay["total"], "header_bytes": lay["header_end"],
+                     "kept_min_max": kept_spread(data, net, TL, EB)}
+    if "picture" not in streams:
+        return out
+    dev, qs, ns = x.device, [float(q) for q in EB.Q_LIST], net.ns0
+    coords = TL.tiles_for(g)
+    T, n, group = len(coords), net.dim_chunk * (g["th"] // 16) * (g["tw"] // 16), TL._default_group(g["th"], g["tw"])
+    keys = torch.empty((T, ns, n), dtype=torch.int32, device=dev)
+    coder, K, Kb = P._check_coder(net, a.coder), bs.check_lanes(a.lanes), bs.check_lanes(a.base_lanes)
+    for i0 in range(0, T, group):                                  # the picture's own keys, as tiled.encode's first pass builds them
+        part = coords[i0:i0 + group]
+        t = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=dev)
+        ops.tile_extract(x, torch.tensor(part, dtype=torch.int32).to(dev), t, g["V"])
+        st = EB._encode_front(net, t, qs, coder, K, Kb)
+        ops.pool_keys(st["std_p"], st["perm"], keys, t0=i0, n_slice=ns)
+    rows, like = keys[i0:i0 + len(part)], torch.empty_like(keys[i0:i0 + len(part)])
+    thr = torch.empty((len(qs), ns), dtype=torch.float32, device=dev)
+    count = torch.empty((len(qs), T, ns), dtype=torch.int32, device=dev)
+    out["kernels"] = {
+        "pool": [T, ns, n], "pool_keys_tiles": len(part),
+        "pool_keys_us": round(event_us(lambda: ops.pool_keys(st["std_p"], st["perm"], keys, t0=i0, n_slice=ns)), 2),
+        "pool_keys_copy_us": round(event_us(lambda: like.copy_(rows)), 2), "pool_keys_out_bytes": rows.numel() * 4,
+        "pooled_select_us": round(event_us(lambda: ops.pooled_select(keys, qs, thr)), 2),
+        "threshold_counts_us": round(event_us(lambda: ops.threshold_counts(keys, thr, count)), 2)}
+    out["v2_header_extra_bytes"] = TL.layout(streams["picture"])["header_end"] - (
+        TL.layout(streams["tile"])["header_end"] if "tile" in streams else
+        TL.layout(streams["picture"])["header_end"] - 8 - 4 * len(qs) * ns)
+    k = len(qs) // 2
+    dp = TL.PictureDecoder(net, streams["picture"], coder=a.coder)
+    out["decode_mark"] = {"mark": k, "q": qs[k], "picture_mark_ms": round(wall_ms(lambda: dp.decode(mark=k), a.warmup, a.reps)[0], 2)}
+    if "tile" in streams:
+        dt = TL.PictureDecoder(net, streams["tile"], coder=a.coder)
+        out["decode_mark"]["tile_q_ms"] = round(wall_ms(lambda: dt.decode(q=qs[k]), a.warmup, a.reps)[0], 2)
+        out["decode_mark"]["tile_mark_ms"] = round(wall_ms(lambda: dt.decode(mark=k), a.warmup, a.reps)[0], 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -74,6 +134,7 @@ def main():
     ap.add_argument("--coder", default="host", choices=["host", "device"])
     ap.add_argument("--lanes", type=int, default=1)
     ap.add_argument("--base-lanes", type=int, default=1)
+    ap.add_argument("--allocation", nargs="+", default=None, choices=["tile", "picture"])
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -127,6 +188,8 @@ def main():
             one = EB.layout(EB.to_bytes(EB.encode_batch(net, crop_x[None], coder=a.coder, lanes=a.lanes, base_lanes=a.base_lanes)[0]))
             res["crop"]["one_image"] = {"head_bytes": one["base_end"], "total_bytes": one["total"],
                                         "overhead_pct": round(100.0 * one["base_end"] / one["total"], 3)}
+        if a.allocation:
+            res["allocations"] = allocations(a, net, x, g, kw, TL, EB, ops)
     for k in ("encode_ms", "decode_full_ms", "decode_window_ms"):
         res[k] = round(res[k], 2)
     print(json.dumps(res))
