@@ -268,16 +268,39 @@ struct TableSearch {
 };
 
 // Where table ci lives: the int32 rows, or the packed 16-bit tables at their start offsets (rans_device.hip's LDS copy).
+// none() is the row of no table: what a refused index is given, never searched.
 struct Int32Rows {
   const int32_t* cdfs;
   int stride;
   VAM_RANS_HD TableSearch<int32_t> operator()(int ci, int sz) const { return {cdfs + (long)ci * stride, sz, false}; }
+  VAM_RANS_HD TableSearch<int32_t> none() const { return {nullptr, 2, false}; }
 };
 struct PackedRows {
   const uint16_t* packed;
   const int32_t* starts;
   VAM_RANS_HD TableSearch<uint16_t> operator()(int ci, int sz) const { return {packed + starts[ci], sz, true}; }
+  VAM_RANS_HD TableSearch<uint16_t> none() const { return {nullptr, 2, true}; }
 };
+
+// The one check of a table index: table ci of `rows` with its size, or the status that refuses it (kBadIndex, kBadTable)
+// with the row of no table and the smallest size, so that a caller may carry the row on without a branch.  The nested
+// form, one assignment in the innermost branch, is what keeps the device kernels' registers where they were.
+template <class F>
+struct TableRow {
+  int32_t status;
+  int sz;
+  F row;
+};
+template <class T>
+VAM_RANS_HD auto table_row(const T& rows, int ci, int cdf_stride, const int32_t* cdf_sizes, int n_cdfs) -> TableRow<decltype(rows(0, 2))> {
+  TableRow<decltype(rows(0, 2))> t{kBadIndex, 2, rows.none()};
+  if (ci >= 0 && ci < n_cdfs) {
+    const int sz = cdf_sizes[ci];
+    if (sz - 2 < 0 || sz - 1 >= cdf_stride) t.status = kBadTable;
+    else t = {kOk, sz, rows(ci, sz)};
+  }
+  return t;
+}
 
 // The n elements of a stream whose state is initialised (or refused: d.status) in d.  Only elements with layer == sel
 // are written; after a failure every remaining selected element is written as 0.
@@ -290,14 +313,11 @@ VAM_RANS_HD int32_t decode_elements(Dec& d, const int32_t* idx, const uint8_t* l
     int32_t value = 0;
     if (!d.status) {
       const int ci = keep ? (idx ? idx[o] : at.chan(i)) : 0;
-      if (ci < 0 || ci >= n_cdfs) d.status = kBadIndex;
-      else {
-        const int sz = cdf_sizes[ci];
-        if (sz - 2 < 0 || sz - 1 >= cdf_stride) d.status = kBadTable;
-        else {
-          const int32_t v = dec_element(d, rows(ci, sz), sz);
-          if (!d.status) value = (int32_t)((uint32_t)v + (uint32_t)offsets[ci]);
-        }
+      const auto t = table_row(rows, ci, cdf_stride, cdf_sizes, n_cdfs);
+      d.status = t.status;
+      if (!d.status) {
+        const int32_t v = dec_element(d, t.row, t.sz);
+        if (!d.status) value = (int32_t)((uint32_t)v + (uint32_t)offsets[ci]);
       }
     }
     if (keep) out[o] = value;
@@ -543,14 +563,10 @@ VAM_RANS_HD int interleaved_group(const uint32_t* words, long first_word, long W
   for (int l = 0; l < m; ++l) {
     Get& t = gs[l];
     t.status = kOk; t.phase = kGetSymbol; t.value = 0;
-    last[l] = 0; failed[l] = false; sz[l] = 2;
+    last[l] = 0;
     ci[l] = idx ? idx[at.off(g * K + l)] : at.chan(g * K + l);
-    if (ci[l] < 0 || ci[l] >= n_cdfs) t.status = kBadIndex;
-    else {
-      sz[l] = cdf_sizes[ci[l]];
-      if (sz[l] - 2 < 0 || sz[l] - 1 >= cdf_stride) t.status = kBadTable;
-    }
-    find[l] = rows(t.status ? 0 : ci[l], t.status ? 2 : sz[l]);
+    const auto row = table_row(rows, ci[l], cdf_stride, cdf_sizes, n_cdfs);
+    t.status = row.status; sz[l] = row.sz; find[l] = row.row;
     failed[l] = t.status != 0;
     active[l] = !failed[l];
     n_active += active[l];

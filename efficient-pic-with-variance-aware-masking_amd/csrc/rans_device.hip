@@ -15,7 +15,6 @@
 #include "common.h"
 #include "rans_core.h"
 #include <cstring>
-#include <type_traits>
 
 using namespace vam;
 namespace R = vam_rans;
@@ -30,14 +29,25 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 struct Geometry {
   int B, h, w, ld, c0, C, n_slices;
   int n_sel;           // layer selectors of the launch; the level is the slowest dimension of the stream id
+  __device__ int streams() const { return B * n_slices * n_sel; }
+  __device__ long hw() const { return (long)h * w; }
+  // Stream str = (level * n_slices + slice) * B + image: its level, and where its (image, slice) window begins.
+  __device__ long origin(int str, int& lvl) const {
+    const int per = B * n_slices;
+    lvl = str / per;
+    const int sid = str - lvl * per, s = sid / B, b = sid - s * B;
+    return (long)b * hw() * ld + c0 + (long)s * C;
+  }
 };
 
+// The arguments of the four kernels over a window; K is the lanes of a stream, which the wave-per-stream kernels ignore.
 struct EncArgs {
   const int32_t* sym;
   const int32_t* idx;
   const uint8_t* layer;
   int sel;
   Geometry g;
+  int K;
   vam_rans_tables t;
   uint32_t* out;
   long cap;
@@ -47,10 +57,9 @@ struct EncArgs {
 
 __global__ __launch_bounds__(kWave) void rans_encode_kernel(EncArgs a) {
   const int gid = blockIdx.x, lane = threadIdx.x;
-  const int per = a.g.B * a.g.n_slices, lvl = gid / per, sid = gid - lvl * per;
-  const int s = sid / a.g.B, b = sid - s * a.g.B, sel = a.sel + lvl;
-  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
-  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  int lvl;
+  const long img = a.g.origin(gid, lvl), hw = a.g.hw(), n = hw * a.g.C;
+  const int sel = a.sel + lvl;
   const R::Nhwc at{hw, a.g.ld};
   uint32_t* region = a.out + (long)gid * a.cap;
   R::Enc e;
@@ -178,6 +187,57 @@ struct WaveSearch {
   }
 };
 
+// The decode kernels' tables.  Packed: every thread of the workgroup (kThreads of them, also those with no stream) copies
+// the ragged 16-bit tables into LDS, 16 bytes per thread and step, and waits at the barrier; the LDS copy is what returns.
+// Otherwise the tables are read as int32 rows from global memory and nothing is copied.
+template <bool kPacked, int kThreads>
+__device__ __forceinline__ const uint16_t* stage_tables(const vam_rans_tables& t) {
+  extern __shared__ uint4 lds_raw[];
+  if (kPacked) {
+    const uint4* src = reinterpret_cast<const uint4*>(t.packed);
+    for (int j = threadIdx.x; j < t.packed_entries / 8; j += kThreads) lds_raw[j] = src[j];
+    __syncthreads();
+  }
+  return reinterpret_cast<const uint16_t*>(lds_raw);
+}
+
+// The rows a thread of its own searches (rans_core.h's TableSearch): in the LDS copy, or in the int32 tables.
+template <bool kPacked>
+__device__ __forceinline__ auto table_rows(const uint16_t* tab, const vam_rans_tables& t) {
+  if constexpr (kPacked) return R::PackedRows{tab, t.packed_start};
+  else return R::Int32Rows{t.cdf, t.stride};
+}
+
+// Where a row begins for the wave-wide search: an offset into the LDS copy, or into the int32 tables.
+template <bool kPacked>
+struct RowStarts {
+  const int32_t* starts;
+  int stride;
+  __device__ int operator()(int ci, int) const { return kPacked ? starts[ci] : ci * stride; }
+  __device__ int none() const { return 0; }
+};
+
+// What a kernel stages per element: the row of T and the table's offset, read side by side so that neither load waits for
+// the other.
+template <class T>
+struct Staged {
+  T rows;
+  const int32_t* offsets;
+  struct Row {
+    decltype(T{}(0, 2)) where;   // T's row: a TableSearch, or the row's start
+    int offv;
+  };
+  __device__ Row operator()(int ci, int sz) const { return {rows(ci, sz), offsets[ci]}; }
+  __device__ Row none() const { return {rows.none(), 0}; }
+};
+template <class T>
+__device__ __forceinline__ Staged<T> staged(const T& rows, const vam_rans_tables& t) { return {rows, t.offsets}; }
+
+// A stream's bytes lie inside the launch's: a whole-word offset and a length within [0, total].
+__device__ __forceinline__ bool span_ok(int64_t boff, long len, long total) {
+  return boff >= 0 && !(boff & 3) && len >= 0 && boff <= total && len <= total - boff;
+}
+
 struct DecArgs {
   const uint8_t* bytes;
   const int64_t* byte_offsets;
@@ -186,6 +246,7 @@ struct DecArgs {
   const uint8_t* layer;
   int sel;
   Geometry g;
+  int K;
   vam_rans_tables t;
   int32_t* out;
   int32_t* status;
@@ -195,21 +256,13 @@ struct DecArgs {
 // the single-selector entry point: 1).  A wave whose stream id is past the end leaves after the barrier.
 template <bool kPacked, int kWaves>
 __global__ __launch_bounds__(kWave * kWaves) void rans_decode_kernel(DecArgs a) {
-  extern __shared__ uint4 lds_raw[];
-  const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds_raw);
+  const uint16_t* tab = stage_tables<kPacked, kWave * kWaves>(a.t);
   const int lane = threadIdx.x & (kWave - 1);
-  if (kPacked) {                                              // the ragged 16-bit tables into LDS, 16 bytes per lane and step
-    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
-    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kWave * kWaves) lds_raw[j] = src[j];
-    __syncthreads();
-  }
-  const int per = a.g.B * a.g.n_slices;
   const int gid = blockIdx.x * kWaves + uniform((int)threadIdx.x / kWave);
-  if (gid >= per * a.g.n_sel) return;
-  const int lvl = gid / per, sid = gid - lvl * per, sel = a.sel + lvl;
-  const int s = sid / a.g.B, b = sid - s * a.g.B;
-  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
-  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+  if (gid >= a.g.streams()) return;
+  int lvl;
+  const long img = a.g.origin(gid, lvl), hw = a.g.hw(), n = hw * a.g.C;
+  const int sel = a.sel + lvl;
   const R::Nhwc at{hw, a.g.ld};
   R::Dec d;
   const int64_t boff = a.byte_offsets[gid];
@@ -224,15 +277,8 @@ __global__ __launch_bounds__(kWave * kWaves) void rans_decode_kernel(DecArgs a) 
       o = img + at.off(i);
       keep = !a.layer || a.layer[o] == sel;
       const int ci = keep ? (a.idx ? a.idx[o] : at.chan(i)) : 0;
-      if (ci < 0 || ci >= a.t.n_cdfs) st = R::kBadIndex;
-      else {
-        sz = a.t.sizes[ci];
-        if (sz - 2 < 0 || sz - 1 >= a.t.stride) st = R::kBadTable;
-        else {
-          offv = a.t.offsets[ci];
-          t0 = kPacked ? a.t.packed_start[ci] : ci * a.t.stride;
-        }
-      }
+      const auto t = R::table_row(staged(RowStarts<kPacked>{a.t.packed_start, a.t.stride}, a.t), ci, a.t.stride, a.t.sizes, a.t.n_cdfs);
+      st = t.status; sz = t.sz; t0 = t.row.where; offv = t.row.offv;
     }
     int32_t mine = 0;
     bool have = false;
@@ -257,28 +303,12 @@ __global__ __launch_bounds__(kWave * kWaves) void rans_decode_kernel(DecArgs a) 
 // One thread per (stream, lane): thread id = stream id * K + lane, so 64 / K streams share a wave and a wave is full for
 // every K.  Nothing crosses a lane: each thread runs rans_core.h's lane_encode / lane_decode on its own state, its own
 // words and its own elements (stream elements lane, lane + K, ...), and is its own writer.
-struct LaneEncArgs {
-  const int32_t* sym;
-  const int32_t* idx;
-  const uint8_t* layer;
-  int sel;
-  Geometry g;
-  int K;
-  vam_rans_tables t;
-  uint32_t* out;
-  long cap;
-  int32_t* lengths;
-  int32_t* status;
-};
-
-__global__ __launch_bounds__(kWave) void rans_lanes_encode_kernel(LaneEncArgs a) {
-  const int gid = blockIdx.x * kWave + threadIdx.x, per = a.g.B * a.g.n_slices;
-  if (gid >= per * a.g.n_sel * a.K) return;
-  const int str = gid / a.K, lane = gid - str * a.K;          // str = (level * n_slices + slice) * B + image
-  const int lvl = str / per, sid = str - lvl * per;
-  const int s = sid / a.g.B, b = sid - s * a.g.B;
-  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
-  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+__global__ __launch_bounds__(kWave) void rans_lanes_encode_kernel(EncArgs a) {
+  const int gid = blockIdx.x * kWave + threadIdx.x;
+  if (gid >= a.g.streams() * a.K) return;
+  const int str = gid / a.K, lane = gid - str * a.K;
+  int lvl;
+  const long img = a.g.origin(str, lvl), hw = a.g.hw(), n = hw * a.g.C;
   long words = 0;
   const int32_t st = R::lane_encode(a.sym + img, a.idx ? a.idx + img : nullptr, a.layer ? a.layer + img : nullptr, a.sel + lvl, n,
                                     R::Nhwc{hw, a.g.ld}, a.K, lane, a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs,
@@ -288,57 +318,29 @@ __global__ __launch_bounds__(kWave) void rans_lanes_encode_kernel(LaneEncArgs a)
 }
 
 // 256 threads share one LDS copy of the packed tables (54 KB for the Gaussian tables: two workgroups, eight waves, per
-// CU); every thread of the workgroup copies, also those past the last lane.  The symbol search is a per-thread binary
-// search (rans_core.h's TableSearch) over the LDS copy, or over the int32 tables in global memory.
+// CU); stage_tables has every thread of the workgroup copy, also those past the last lane.  The symbol search is a
+// per-thread binary search (table_rows: rans_core.h's TableSearch) over the LDS copy, or over the int32 tables in global memory.
 constexpr int kLaneBlock = 256;
 
-struct LaneDecArgs {
-  const uint8_t* bytes;
-  const int64_t* byte_offsets;
-  const int32_t* byte_lengths;
-  const int32_t* idx;
-  const uint8_t* layer;
-  int sel;
-  Geometry g;
-  int K;
-  vam_rans_tables t;
-  int32_t* out;
-  int32_t* status;
-};
-
 template <bool kPacked>
-__global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecArgs a) {
-  extern __shared__ uint4 lds_raw[];
-  if (kPacked) {
-    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
-    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
-    __syncthreads();
-  }
-  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, per = a.g.B * a.g.n_slices;
-  if (gid >= per * a.g.n_sel * a.K) return;
-  const int str = gid / a.K, lane = gid - str * a.K;          // str = (level * n_slices + slice) * B + image
-  const int lvl = str / per, sid = str - lvl * per, sel = a.sel + lvl;
-  const int s = sid / a.g.B, b = sid - s * a.g.B;
-  const long hw = (long)a.g.h * a.g.w, n = hw * a.g.C;
-  const long img = (long)b * hw * a.g.ld + a.g.c0 + (long)s * a.g.C;
+__global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(DecArgs a) {
+  const uint16_t* tab = stage_tables<kPacked, kLaneBlock>(a.t);
+  const int gid = blockIdx.x * kLaneBlock + threadIdx.x;
+  if (gid >= a.g.streams() * a.K) return;
+  const int str = gid / a.K, lane = gid - str * a.K;
+  int lvl;
+  const long img = a.g.origin(str, lvl), hw = a.g.hw(), n = hw * a.g.C;
   const int64_t boff = a.byte_offsets[str];
   const uint32_t* words = (boff & 3) ? nullptr : reinterpret_cast<const uint32_t*>(a.bytes + boff);
-  const int32_t* idx = a.idx ? a.idx + img : nullptr;
-  const uint8_t* layer = a.layer ? a.layer + img : nullptr;
-  const R::Nhwc at{hw, a.g.ld};
-  if (kPacked)
-    a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, idx, layer, sel, n, at,
-                                   R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}, a.t.stride, a.t.sizes,
-                                   a.t.offsets, a.t.n_cdfs, a.out + img);
-  else
-    a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, idx, layer, sel, n, at, R::Int32Rows{a.t.cdf, a.t.stride},
-                                   a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, a.out + img);
+  a.status[gid] = R::lane_decode(words, a.byte_lengths[str], a.K, lane, a.idx ? a.idx + img : nullptr, a.layer ? a.layer + img : nullptr,
+                                 a.sel + lvl, n, R::Nhwc{hw, a.g.ld}, table_rows<kPacked>(tab, a.t), a.t.stride, a.t.sizes, a.t.offsets,
+                                 a.t.n_cdfs, a.out + img);
 }
 
 // ---------------------------------------------------------------- interleaved lanes
 // One thread per (stream, lane) as above, thread id = stream id * K + lane, but the K lanes of a stream share ONE word
 // stream: in every round the lanes that flush (encode) or fetch (decode) are a ballot, a stream's K bits of it are cut out
-// with the stream's first wave lane (`shift`), and a lane's word position is the stream's position plus the popcount of the
+// with the stream's first wave lane (StreamLanes), and a lane's word position is the stream's position plus the popcount of the
 // flushing / fetching lanes above (encode: words are stored backwards) or below it (decode).  Every lane of a stream
 // carries the stream's position itself, so nothing but the ballot crosses a lane.  All streams of a launch have the same
 // n, so the group loop is wave-uniform; the rounds of a group run until no lane of the wave has a put / get left.
@@ -346,7 +348,8 @@ __global__ __launch_bounds__(kLaneBlock) void rans_lanes_decode_kernel(LaneDecAr
 //
 // Where a stream's elements lie is a base of the argument structs: FlatRows, the ranked buffers of the
 // embedded streams, or NhwcWindow, the (image, slice) windows of the first half of this file, for z and the base slices
-// of an "embedded-4" container.  The group body is the same; what a window adds is compiled only for it (kWindow).
+// of an "embedded-4" container.  What a window adds is compiled only for it (kWindow); the decoder's group step is one
+// function, wave_group, for both forms and for the resume kernel.
 struct FlatRows {                                            // stream s = elements [s * n, (s + 1) * n) in place, idx given
   static constexpr bool kWindow = false;
   __device__ long origin(int) const { return 0; }
@@ -365,6 +368,18 @@ struct NhwcWindow {                                          // stream s * B + i
     return (long)((uint32_t)i - c * (uint32_t)hw) * ld + c;
   }
   __device__ int chan(long i) const { return (int)((uint32_t)i / (uint32_t)hw); }
+};
+
+typedef unsigned long long u64;
+
+// Thread gid of a launch as lane `lane` of stream `str`, and that stream's part of a wave ballot.
+struct StreamLanes {
+  int K, str, lane, shift;   // shift: the wave lane of the stream's lane 0
+  u64 kmask, below, above;   // the stream's lanes; those below and above this one
+  __device__ StreamLanes(int gid, int K_)
+      : K(K_), str(gid / K_), lane(gid - str * K_), shift((int)(threadIdx.x & (kWave - 1)) - lane),
+        kmask(K_ == kWave ? ~0ull : (1ull << K_) - 1), below((1ull << lane) - 1), above(kmask & ~((2ull << lane) - 1)) {}
+  __device__ u64 mine(u64 ballot) const { return (ballot >> shift) & kmask; }
 };
 
 template <class A>
@@ -386,12 +401,9 @@ struct IlvEncArgs : A {
 
 template <class A>
 __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncArgs<A> a) {
-  typedef unsigned long long u64;
-  const int tid = threadIdx.x, gid = blockIdx.x * kWave + tid, K = a.K;
-  const int str = gid / K, lane = gid - str * K, shift = tid - lane;
+  const StreamLanes L(blockIdx.x * kWave + threadIdx.x, a.K);
+  const int K = L.K, str = L.str, lane = L.lane;
   const bool valid = str < a.n_streams;
-  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
-  const u64 above = kmask & ~((2ull << lane) - 1);           // the stream's lanes above this one
   const long n = a.n, base = A::kWindow ? a.origin(valid ? str : 0) : (long)(valid ? str : 0) * n;
   uint32_t* region = a.out + (long)(valid ? str : 0) * a.cap;
   uint32_t* top = region + a.cap;                            // the stream's next word goes below top
@@ -415,13 +427,13 @@ __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncAr
       }
       gets = st ? 0 : R::put_gets(u);
     }
-    if ((__ballot(st != 0) >> shift) & kmask) alive = false;
+    if (L.mine(__ballot(st != 0))) alive = false;
     if (!alive) gets = 0;
     for (int t = R::kMaxGets - 1; t >= 0; --t) {
       const bool act = gets > t;
       if (!__ballot(act)) continue;
       const bool fl = act && R::put_flushes(e, u, t);
-      const u64 sub = (__ballot(fl) >> shift) & kmask;
+      const u64 sub = L.mine(__ballot(fl));
       while (m_hi > 0 && sub) {                               // the first flush on behalf of an element below a mark's count
         const long c = c_top > 0 ? c_top : 0, gq = c / K;
         const u64 mine = g < gq ? sub : g == gq ? sub & ((1ull << (int)(c - gq * K)) - 1) : 0;
@@ -431,16 +443,16 @@ __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncAr
         --m_hi;
         c_top = m_hi > 0 ? a.counts[(long)(m_hi - 1) * a.n_streams + str] : 0;
       }
-      if (fl) e.p = top - __popcll(sub & above);              // enc_flush_word stores at --p
+      if (fl) e.p = top - __popcll(sub & L.above);            // enc_flush_word stores at --p
       if (act) R::enc_put_step(e, u, t);
       top -= __popcll(sub);
       emitted += __popcll(sub);
     }
-    if ((__ballot(e.status != 0) >> shift) & kmask) alive = false;
+    if (L.mine(__ballot(e.status != 0))) alive = false;
   }
   const int32_t own = st ? st : e.status;
-  const u64 bad = (__ballot(own != 0) >> shift) & kmask;
-  int32_t sst = __shfl(own, bad ? shift + __ffsll(bad) - 1 : shift);     // the stream's status: its lowest failing lane's
+  const u64 bad = L.mine(__ballot(own != 0));
+  int32_t sst = __shfl(own, bad ? L.shift + __ffsll(bad) - 1 : L.shift);    // the stream's status: its lowest failing lane's
   if (!bad) sst = 0;
   long words = 0;
   if (valid && !sst) {
@@ -480,24 +492,57 @@ struct IlvDecArgs : A {
   int32_t* status;
 };
 
-// A window is decoded STRICTLY: the base of a container is needed whole.  A stream whose words end early gets kTruncated,
-// its elements from the failing group on are written as 0, and a refused stream (kBadStream) is neither read nor written;
-// there are no available counts.
+// One group of the tolerant decode on the wave, the counterpart of rans_core.h's interleaved_group: a lane that `has` an
+// element runs its gets on the staged row t (a refused row fails the lane at once) from the state in gt, and in every
+// round the lanes that need a word take the stream's words from `pos` on in lane order.  The string's word p is
+// words[p - first_word] and it holds the words below W; a request past them fails the lane.  The rounds are wave-uniform:
+// every lane of the wave calls this together, the lanes without an element take no part but stay at the ballots.
+// What comes back is the stream's: the lanes that failed and those that failed with a status (bits of the stream), the
+// lowest failed lane (K when none) and the status of the lowest lane that has one.
+struct GroupEnd {
+  u64 fsub, esub;
+  int first;
+  int32_t err;
+};
+
+template <class S>
+__device__ __forceinline__ GroupEnd wave_group(const StreamLanes& L, bool has, const R::TableRow<S>& t, R::Get& gt, long& pos,
+                                               const uint32_t* words, long first_word, long W) {
+  int32_t lst = t.status;                                     // what failed this lane, when it is an error
+  bool failed = lst != 0, act = has && !failed;
+  if (has) {
+    gt.phase = R::kGetSymbol;
+    gt.status = 0;
+    gt.value = 0;
+  }
+  while (__ballot(act)) {                                     // one round: the updates, then the words in lane order
+    bool need = false;
+    if (act) {
+      need = R::get_step(gt, t.row.where, t.sz);
+      if (gt.status) { lst = gt.status; failed = true; need = false; }
+    }
+    const u64 sub = L.mine(__ballot(need));
+    if (need) {
+      const long p = pos + __popcll(sub & L.below);
+      if (p < W) gt.x = (gt.x << 32) | words[p - first_word];
+      else failed = true;                                     // past the words held: so is every later request
+    }
+    pos += __popcll(sub);
+    if (failed || gt.phase == R::kGetDone) act = false;
+  }
+  const u64 fsub = L.mine(__ballot(failed)), esub = L.mine(__ballot(lst != 0));
+  return {fsub, esub, fsub ? __ffsll(fsub) - 1 : L.K, __shfl(lst, esub ? L.shift + __ffsll(esub) - 1 : L.shift)};
+}
+
+// The flat form is tolerant (rans_core.h's interleaved_decode).  A window is decoded STRICTLY: the base of a container is
+// needed whole.  A stream whose words end early gets kTruncated, its elements from the failing group on are written as 0,
+// and a refused stream (kBadStream) is neither read nor written; there are no available counts.
 template <bool kPacked, class A>
 __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(IlvDecArgs<A> a) {
-  typedef unsigned long long u64;
-  using Find = R::TableSearch<typename std::conditional<kPacked, uint16_t, int32_t>::type>;
-  extern __shared__ uint4 lds_raw[];
-  if (kPacked) {
-    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
-    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
-    __syncthreads();
-  }
-  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, K = a.K;
-  const int str = gid / K, lane = gid - str * K, shift = (int)(threadIdx.x & (kWave - 1)) - lane;
+  const auto rows = staged(table_rows<kPacked>(stage_tables<kPacked, kLaneBlock>(a.t), a.t), a.t);
+  const StreamLanes L(blockIdx.x * kLaneBlock + threadIdx.x, a.K);
+  const int K = L.K, str = L.str, lane = L.lane;
   const bool valid = str < a.n_streams;
-  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
-  const u64 below = (1ull << lane) - 1;
   const long n = a.n, base = A::kWindow ? a.origin(valid ? str : 0) : (long)(valid ? str : 0) * n;
   const uint32_t* words = nullptr;
   long W = 0;
@@ -505,7 +550,7 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
   if (valid) {
     const int64_t boff = a.byte_offsets[str];
     const long len = a.byte_lengths[str];
-    if (boff < 0 || (boff & 3) || len < 0 || boff > a.bytes_total || len > a.bytes_total - boff) sst = R::kBadStream;
+    if (!span_ok(boff, len, a.bytes_total)) sst = R::kBadStream;
     else { words = reinterpret_cast<const uint32_t*>(a.bytes + boff); W = len / 4; }
   }
   bool alive = valid && !sst && W >= 2l * K;
@@ -520,58 +565,24 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
   for (long g = 0; g * K < n; ++g) {
     const long i = g * K + lane;
     const bool has = valid && i < n, was_alive = alive;
-    int32_t lst = 0;                                          // what failed this lane, when it is an error
-    int sz = 2, offv = 0;
-    Find find{nullptr, 2, kPacked};
-    bool act = false, failed = false;
+    R::TableRow<decltype(rows.none())> t{R::kOk, 2, rows.none()};
     if (alive && has) {
       int ci;
       if constexpr (A::kWindow) ci = a.idx ? a.idx[base + a.off(i)] : a.chan(i);
       else ci = a.idx[base + i];
-      if (ci < 0 || ci >= a.t.n_cdfs) lst = R::kBadIndex;
-      else {
-        sz = a.t.sizes[ci];
-        if (sz - 2 < 0 || sz - 1 >= a.t.stride) lst = R::kBadTable;
-        else {
-          offv = a.t.offsets[ci];
-          if constexpr (kPacked) find = R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}(ci, sz);
-          else find = R::Int32Rows{a.t.cdf, a.t.stride}(ci, sz);
-        }
-      }
-      failed = lst != 0;
-      act = !failed;
-      gt.phase = R::kGetSymbol;
-      gt.status = 0;
-      gt.value = 0;
+      t = R::table_row(rows, ci, a.t.stride, a.t.sizes, a.t.n_cdfs);
     }
-    while (__ballot(act)) {                                   // one round: the updates, then the words in lane order
-      bool need = false;
-      if (act) {
-        need = R::get_step(gt, find, sz);
-        if (gt.status) { lst = gt.status; failed = true; need = false; }
-      }
-      const u64 sub = (__ballot(need) >> shift) & kmask;
-      if (need) {
-        const long p = pos + __popcll(sub & below);
-        if (p < W) gt.x = (gt.x << 32) | words[p];
-        else failed = true;                                   // past the prefix: so is every later request
-      }
-      pos += __popcll(sub);
-      if (failed || gt.phase == R::kGetDone) act = false;
-    }
-    const u64 fsub = (__ballot(failed) >> shift) & kmask, esub = (__ballot(lst != 0) >> shift) & kmask;
-    const int first = fsub ? __ffsll(fsub) - 1 : K;
-    const int32_t err = __shfl(lst, esub ? shift + __ffsll(esub) - 1 : shift);
+    const GroupEnd e = wave_group(L, alive && has, t, gt, pos, words, 0, W);
     if constexpr (A::kWindow) {                               // strict: a failing group is zeros as a whole
-      if (has && !refused) a.out[base + a.off(i)] = was_alive && !fsub ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+      if (has && !refused) a.out[base + a.off(i)] = was_alive && !e.fsub ? (int32_t)((uint32_t)gt.value + (uint32_t)t.row.offv) : 0;
     } else {
-      if (has) a.out[base + i] = was_alive && lane < first ? (int32_t)((uint32_t)gt.value + (uint32_t)offv) : 0;
+      if (has) a.out[base + i] = was_alive && lane < e.first ? (int32_t)((uint32_t)gt.value + (uint32_t)t.row.offv) : 0;
     }
-    if (was_alive && fsub) {
+    if (was_alive && e.fsub) {
       alive = false;
-      avail = g * K + first;
-      if constexpr (A::kWindow) sst = esub ? err : (int32_t)R::kTruncated;
-      else sst = esub ? err : 0;
+      avail = g * K + e.first;
+      if constexpr (A::kWindow) sst = e.esub ? e.err : (int32_t)R::kTruncated;
+      else sst = e.esub ? e.err : 0;
     }
   }
   if (valid && lane == 0) {
@@ -581,7 +592,8 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_decode_kernel(Ilv
 }
 
 // ---------------------------------------------------------------- resumable decode
-// The kernel above from a checkpoint (rans_core.h's interleaved_resume), same geometry.  The streams of a launch stand at
+// The flat decode from a checkpoint (rans_core.h's interleaved_resume): the same geometry and, through wave_group, the same
+// group step as the kernel above, with a policy of its own around it.  The streams of a launch stand at
 // different groups, so every stream counts its own group g and the loop runs while any stream of the wave still decodes:
 // that test is a ballot, wave-uniform, and so are the rounds inside, where the lanes of a stream that has ended take no
 // part.  A wave therefore leaves after the groups its bytes reach, not after n / K.  Every lane carries the state and the
@@ -606,19 +618,10 @@ struct IlvResArgs {
 
 template <bool kPacked>
 __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_resume_kernel(IlvResArgs a) {
-  typedef unsigned long long u64;
-  using Find = R::TableSearch<typename std::conditional<kPacked, uint16_t, int32_t>::type>;
-  extern __shared__ uint4 lds_raw[];
-  if (kPacked) {
-    const uint4* src = reinterpret_cast<const uint4*>(a.t.packed);
-    for (int j = threadIdx.x; j < a.t.packed_entries / 8; j += kLaneBlock) lds_raw[j] = src[j];
-    __syncthreads();
-  }
-  const int gid = blockIdx.x * kLaneBlock + threadIdx.x, K = a.K;
-  const int str = gid / K, lane = gid - str * K, shift = (int)(threadIdx.x & (kWave - 1)) - lane;
+  const auto rows = staged(table_rows<kPacked>(stage_tables<kPacked, kLaneBlock>(a.t), a.t), a.t);
+  const StreamLanes L(blockIdx.x * kLaneBlock + threadIdx.x, a.K);
+  const int K = L.K, str = L.str, lane = L.lane;
   const bool valid = str < a.n_streams;
-  const u64 kmask = K == kWave ? ~0ull : (1ull << K) - 1;
-  const u64 below = (1ull << lane) - 1;
   const long n = a.n, base = (long)(valid ? str : 0) * n;
   const uint32_t* words = nullptr;                            // the string's word p is words[p - first_word]
   long W = 0, pos = 0, first_word = 0, g = 0;
@@ -630,8 +633,7 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_resume_kernel(Ilv
     const int64_t boff = a.byte_offsets[str];
     const long len = a.byte_lengths[str], done = a.done[str];
     pos = a.pos[str];
-    if (boff < 0 || (boff & 3) || len < 0 || boff > a.bytes_total || len > a.bytes_total - boff || !R::checkpoint_valid(done, pos, n, K))
-      sst = R::kBadStream;
+    if (!span_ok(boff, len, a.bytes_total) || !R::checkpoint_valid(done, pos, n, K)) sst = R::kBadStream;
     else if (done == n) avail = n;                            // finished: nothing is read or written
     else {
       words = reinterpret_cast<const uint32_t*>(a.bytes + boff);
@@ -657,52 +659,15 @@ __global__ __launch_bounds__(kLaneBlock) void rans_interleaved_resume_kernel(Ilv
     const long i = g * K + lane;
     const bool has = alive && i < n;
     if (alive) { ck_x = gt.x; ck_pos = pos; ck_done = g * K; }
-    int32_t lst = 0;                                          // what failed this lane, when it is an error
-    int sz = 2, offv = 0;
-    Find find{nullptr, 2, kPacked};
-    bool act = false, failed = false;
-    if (has) {
-      const int ci = a.idx[base + i];
-      if (ci < 0 || ci >= a.t.n_cdfs) lst = R::kBadIndex;
-      else {
-        sz = a.t.sizes[ci];
-        if (sz - 2 < 0 || sz - 1 >= a.t.stride) lst = R::kBadTable;
-        else {
-          offv = a.t.offsets[ci];
-          if constexpr (kPacked) find = R::PackedRows{reinterpret_cast<const uint16_t*>(lds_raw), a.t.packed_start}(ci, sz);
-          else find = R::Int32Rows{a.t.cdf, a.t.stride}(ci, sz);
-        }
-      }
-      failed = lst != 0;
-      act = !failed;
-      gt.phase = R::kGetSymbol;
-      gt.status = 0;
-      gt.value = 0;
-    }
-    while (__ballot(act)) {                                   // one round: the updates, then the words in lane order
-      bool need = false;
-      if (act) {
-        need = R::get_step(gt, find, sz);
-        if (gt.status) { lst = gt.status; failed = true; need = false; }
-      }
-      const u64 sub = (__ballot(need) >> shift) & kmask;
-      if (need) {
-        const long p = pos + __popcll(sub & below);
-        if (p < W) gt.x = (gt.x << 32) | words[p - first_word];
-        else failed = true;                                   // past the bytes held: so is every later request
-      }
-      pos += __popcll(sub);
-      if (failed || gt.phase == R::kGetDone) act = false;
-    }
-    const u64 fsub = (__ballot(failed) >> shift) & kmask, esub = (__ballot(lst != 0) >> shift) & kmask;
-    const int first = fsub ? __ffsll(fsub) - 1 : K;
-    const int32_t err = __shfl(lst, esub ? shift + __ffsll(esub) - 1 : shift);
-    if (has && lane < first) a.out[base + i] = (int32_t)((uint32_t)gt.value + (uint32_t)offv);
+    R::TableRow<decltype(rows.none())> t{R::kOk, 2, rows.none()};
+    if (has) t = R::table_row(rows, a.idx[base + i], a.t.stride, a.t.sizes, a.t.n_cdfs);
+    const GroupEnd e = wave_group(L, has, t, gt, pos, words, first_word, W);
+    if (has && lane < e.first) a.out[base + i] = (int32_t)((uint32_t)gt.value + (uint32_t)t.row.offv);
     if (alive) {
-      if (fsub) {                                             // the group failed: its start is the checkpoint
+      if (e.fsub) {                                           // the group failed: its start is the checkpoint
         alive = false;
-        avail = g * K + first;
-        sst = esub ? err : 0;
+        avail = g * K + e.first;
+        sst = e.esub ? e.err : 0;
       } else if ((++g) * K >= n) {                            // the stream is complete
         alive = false;
         avail = n;
@@ -827,10 +792,29 @@ int launch_encode(const char* what, const int32_t* sym, const int32_t* idx, cons
   if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
   VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "%s: a region is 2 .. 2^31 words, got %ld", what, out_cap_words);
-  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, *tables, out_words, out_cap_words, lengths, status};
+  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, 1, *tables, out_words, out_cap_words, lengths, status};
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
   hipLaunchKernelGGL(rans_encode_kernel, dim3(n_sel * B * n_slices), dim3(kWave), 0, (hipStream_t)stream, a);
   return check_launch("rans_encode_kernel");
+}
+
+// The launch of a decode kernel: its <true> form with the packed tables a.t in LDS (refused when a workgroup may not have
+// that much), its <false> form over the int32 tables otherwise.  `kernel` is the name a failed launch is reported under.
+template <class Args>
+int launch_with_tables(const char* what, const char* kernel, void (*packed)(Args), void (*plain)(Args), int blocks, int threads,
+                       const Args& a, void* stream) {
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  if (a.t.packed) {
+    const int lds = a.t.packed_entries * 2;
+    const int limit = vam_rans_lds_table_bytes();
+    if (limit < 0) return limit;
+    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
+    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(packed), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(packed, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(plain, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, a);
+  }
+  return check_launch(kernel);
 }
 
 template <int kWaves>
@@ -840,21 +824,9 @@ int launch_decode(const char* what, const uint8_t* bytes, const int64_t* byte_of
   VAM_REQUIRE(bytes && byte_offsets && byte_lengths && sym_out && status, "%s: need bytes, offsets, lengths, sym_out, status", what);
   if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
-  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, *tables, sym_out, status};
-  const int blocks = (n_sel * B * n_slices + kWaves - 1) / kWaves;
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_decode_kernel<true, kWaves>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((rans_decode_kernel<true, kWaves>), dim3(blocks), dim3(kWave * kWaves), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL((rans_decode_kernel<false, kWaves>), dim3(blocks), dim3(kWave * kWaves), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_decode_kernel");
+  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, 1, *tables, sym_out, status};
+  return launch_with_tables(what, "rans_decode_kernel", rans_decode_kernel<true, kWaves>, rans_decode_kernel<false, kWaves>,
+                            (n_sel * B * n_slices + kWaves - 1) / kWaves, kWave * kWaves, a, stream);
 }
 
 int launch_lanes_encode(const char* what, const int32_t* sym, const int32_t* idx, const uint8_t* layer, int sel, int n_sel, int B, int h,
@@ -865,7 +837,7 @@ int launch_lanes_encode(const char* what, const int32_t* sym, const int32_t* idx
   if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
   VAM_REQUIRE(out_cap_words >= 2 && out_cap_words < (1l << 31), "%s: a region is 2 .. 2^31 words, got %ld", what, out_cap_words);
-  LaneEncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, out_words, out_cap_words, lengths, status};
+  EncArgs a{sym, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, out_words, out_cap_words, lengths, status};
   const int threads = n_sel * B * n_slices * lanes;         // at most 2^20 streams of 64 lanes
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
   hipLaunchKernelGGL(rans_lanes_encode_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
@@ -879,21 +851,9 @@ int launch_lanes_decode(const char* what, const uint8_t* bytes, const int64_t* b
   VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
   if (int rc = check_geometry(what, B, h, w, ld, c0, C, n_slices, n_sel)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
-  LaneDecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, sym_out, status};
-  const int blocks = (n_sel * B * n_slices * lanes + kLaneBlock - 1) / kLaneBlock;
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_lanes_decode_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(rans_lanes_decode_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(rans_lanes_decode_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_lanes_decode_kernel");
+  DecArgs a{bytes, byte_offsets, byte_lengths, idx, layer, sel, {B, h, w, ld, c0, C, n_slices, n_sel}, lanes, *tables, sym_out, status};
+  return launch_with_tables(what, "rans_lanes_decode_kernel", rans_lanes_decode_kernel<true>, rans_lanes_decode_kernel<false>,
+                            (n_sel * B * n_slices * lanes + kLaneBlock - 1) / kLaneBlock, kLaneBlock, a, stream);
 }
 
 // The layered launches select by layer id: a uint8, so the selectors stay within 0 .. 255.
@@ -907,21 +867,17 @@ int check_layers(const char* what, const uint8_t* layer, int sel0, int n_sel) {
 constexpr int kLayerWaves = 8;       // streams per workgroup of the layered K = 1 decode
 
 template <class A>
-int launch_interleaved_decode(const char* what, const IlvDecArgs<A>& a, const vam_rans_tables* tables, void* stream) {
-  const int blocks = (a.n_streams * a.K + kLaneBlock - 1) / kLaneBlock;
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_decode_kernel<true, A>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((rans_interleaved_decode_kernel<true, A>), dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL((rans_interleaved_decode_kernel<false, A>), dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_interleaved_decode_kernel");
+int launch_interleaved_decode(const char* what, const IlvDecArgs<A>& a, void* stream) {
+  return launch_with_tables(what, "rans_interleaved_decode_kernel", rans_interleaved_decode_kernel<true, A>,
+                            rans_interleaved_decode_kernel<false, A>, (a.n_streams * a.K + kLaneBlock - 1) / kLaneBlock, kLaneBlock, a, stream);
+}
+
+// What the flat interleaved entry points refuse alike: the lanes of a stream, and the streams and symbols of a launch.
+int check_streams(const char* what, int lanes, int n_streams, long n) {
+  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
+  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
+              what, n_streams, n);
+  return VAM_OK;
 }
 
 }  // namespace
@@ -1088,9 +1044,7 @@ int vam_rans_interleaved_encode_device(const int32_t* sym, const int32_t* idx, i
                                        int32_t* status, const int32_t* counts, int n_marks, int32_t* mark_bytes, void* stream) {
   const char* what = "vam_rans_interleaved_encode_device";
   VAM_REQUIRE(sym && idx && out_words && lengths && status, "%s: need sym, idx, out_words, lengths, status", what);
-  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
-  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
-              what, n_streams, n);
+  if (int rc = check_streams(what, lanes, n_streams, n)) return rc;
   VAM_REQUIRE(n_marks >= 0 && n_marks <= 4096 && (n_marks == 0 || (counts && mark_bytes)), "%s: marks need counts and mark_bytes", what);
   if (int rc = check_tables(what, tables)) return rc;
   VAM_REQUIRE(out_cap_words >= 2l * lanes && out_cap_words < (1l << 31), "%s: a region is 2 * lanes .. 2^31 words, got %ld", what,
@@ -1109,12 +1063,10 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
   const char* what = "vam_rans_interleaved_decode_device";
   VAM_REQUIRE(bytes && byte_offsets && byte_lengths && idx && sym_out && available && status && bytes_total >= 0 &&
               ((uintptr_t)bytes & 3) == 0, "%s: need word-aligned bytes, offsets, lengths, idx, sym_out, available, status", what);
-  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
-  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
-              what, n_streams, n);
+  if (int rc = check_streams(what, lanes, n_streams, n)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
   IlvDecArgs<FlatRows> a{{}, bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, available, status};
-  return launch_interleaved_decode(what, a, tables, stream);
+  return launch_interleaved_decode(what, a, stream);
 }
 
 // The window forms: z and the base slices of an "embedded-4" container.
@@ -1149,7 +1101,7 @@ int vam_rans_interleaved_decode_nhwc_device(const uint8_t* bytes, long bytes_tot
   if (int rc = check_tables(what, tables)) return rc;
   IlvDecArgs<NhwcWindow> a{{B, h * w, ld, c0, C}, bytes, bytes_total, byte_offsets, byte_lengths, idx, B * n_slices, (long)h * w * C,
                            lanes, *tables, sym_out, nullptr, status};
-  return launch_interleaved_decode(what, a, tables, stream);
+  return launch_interleaved_decode(what, a, stream);
 }
 
 // ---------------------------------------------------------------- resumable decode
@@ -1161,26 +1113,12 @@ int vam_rans_interleaved_resume_device(const uint8_t* bytes, long bytes_total, c
   VAM_REQUIRE(bytes && byte_offsets && byte_lengths && idx && sym_out && available && status && bytes_total >= 0 &&
               ((uintptr_t)bytes & 3) == 0, "%s: need word-aligned bytes, offsets, lengths, idx, sym_out, available, status", what);
   VAM_REQUIRE(states && done && pos && ((uintptr_t)states & 7) == 0, "%s: need the checkpoints: 64-bit aligned states, done, pos", what);
-  VAM_REQUIRE(R::lanes_valid(lanes), "%s: lanes is a power of two in 1 .. %d, got %d", what, R::kMaxLanes, lanes);
-  VAM_REQUIRE(n_streams > 0 && n_streams <= (1 << 20) && n >= 0 && n <= (1l << 28), "%s: 1 .. 2^20 streams of 0 .. 2^28 symbols, got %d of %ld",
-              what, n_streams, n);
+  if (int rc = check_streams(what, lanes, n_streams, n)) return rc;
   if (int rc = check_tables(what, tables)) return rc;
   IlvResArgs a{bytes, bytes_total, byte_offsets, byte_lengths, idx, n_streams, n, lanes, *tables, sym_out, states, done, pos, available,
                status};
-  const int blocks = (n_streams * lanes + kLaneBlock - 1) / kLaneBlock;
-  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
-  if (tables->packed) {
-    const int lds = tables->packed_entries * 2;
-    const int limit = vam_rans_lds_table_bytes();
-    if (limit < 0) return limit;
-    VAM_REQUIRE(lds <= limit, "%s: packed tables of %d bytes exceed the %d bytes of LDS a workgroup may use", what, lds, limit);
-    VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&rans_interleaved_resume_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(rans_interleaved_resume_kernel<true>, dim3(blocks), dim3(kLaneBlock), lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(rans_interleaved_resume_kernel<false>, dim3(blocks), dim3(kLaneBlock), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("rans_interleaved_resume_kernel");
+  return launch_with_tables(what, "rans_interleaved_resume_kernel", rans_interleaved_resume_kernel<true>,
+                            rans_interleaved_resume_kernel<false>, (n_streams * lanes + kLaneBlock - 1) / kLaneBlock, kLaneBlock, a, stream);
 }
 
 }  // extern "C"
