@@ -14,7 +14,13 @@
 //                         ascending r and within that ascending c, of (wy * wx) * v, every product and add one fp32
 //                         operation (__fmul_rn / __fadd_rn never contract), starting from the first term: outside the bands
 //                         it is the tile's value bit for bit.  No atomics, no division of floats, a fixed order.
-// Both move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
+//   tile_schedule_kernel  a picture-wide schedule, fp32 [L, H, W] at pixel resolution, brought down onto the latent grids of a
+//                         list of tiles: out[i, k, a, b] = max over y, x in [0, 16) of
+//                         maps[k, min(r Sy + 16 a + y, H - 1), min(c Sx + 16 b + x, W - 1)], the block maximum of
+//                         evaluate.latent_quality_map composed with the extract kernel's edge replication.  One wave per
+//                         output cell: lane l reads the four pixels 4 (l & 3) .. of row l >> 2 and the 64 partial results are
+//                         reduced with wave-64 shuffles.  A NaN anywhere in the block gives NaN (fmaxf alone would drop it).
+// All move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
 // scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
 #include "common.h"
 #include <cstdint>
@@ -79,6 +85,44 @@ __global__ __launch_bounds__(256) void tile_extract_kernel(const ExtractArgs a) 
         if (k < nv) dst[k] = v[k];
     }
   }
+}
+
+struct ScheduleArgs {
+  const float* maps;
+  const int32_t* coords;
+  float* out;
+  TileGeom g;
+  int L, ch, cw;                            // stages, latent rows and columns of a tile (th / 16, tw / 16)
+};
+
+// Block (64, 4): wave threadIdx.y owns cell (a, b) = (blockIdx.y, 4 blockIdx.x + threadIdx.y) of tile i at stage k, where
+// blockIdx.z = i L + k.  Everything that decides a return is uniform over the wave, so the shuffles run with all 64 lanes.
+__global__ __launch_bounds__(256) void tile_schedule_kernel(const ScheduleArgs s) {
+  const TileGeom& g = s.g;
+  const int a = blockIdx.y, b = 4 * blockIdx.x + threadIdx.y;
+  if (b >= s.cw) return;
+  const int i = blockIdx.z / s.L, k = blockIdx.z - i * s.L;
+  const int r = s.coords[2 * i], c = s.coords[2 * i + 1];
+  if ((unsigned)r >= (unsigned)g.R || (unsigned)c >= (unsigned)g.C) return;      // not a tile of this grid: write nothing
+  const int lane = threadIdx.x;
+  const int Y = min(r * g.Sy + 16 * a + (lane >> 2), g.H - 1), X = c * g.Sx + 16 * b + 4 * (lane & 3);
+  const float* src = s.maps + ((long)k * g.H + Y) * g.W;
+  float v[4];
+  if (X + 3 < g.W && aligned16(src + X)) {
+    const float4 q = *reinterpret_cast<const float4*>(src + X);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = src[min(X + j, g.W - 1)];
+  }
+  float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+  int bad = (v[0] != v[0]) | (v[1] != v[1]) | (v[2] != v[2]) | (v[3] != v[3]);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    m = fmaxf(m, __shfl_xor(m, d, 64));
+    bad |= __shfl_xor(bad, d, 64);
+  }
+  if (lane == 0) s.out[(((long)i * s.L + k) * s.ch + a) * s.cw + b] = bad ? __int_as_float(0x7FC00000) : m;
 }
 
 struct BlendArgs {
@@ -234,6 +278,25 @@ int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, co
   ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)n * th * tw * 24.0);
   hipLaunchKernelGGL(tile_extract_kernel, dim3(cdiv(cdiv(tw, 4), 64), cdiv(th, 4), n), dim3(64, 4), 0, (hipStream_t)stream, a);
   return check_launch("tile_extract_kernel");
+}
+
+int vam_tile_schedule(const float* maps, int L, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
+                      void* stream) {
+  ScheduleArgs a;
+  if (int rc = tile_geometry("vam_tile_schedule", H, W, th, tw, V, &a.g)) return rc;
+  VAM_REQUIRE(th % 16 == 0 && tw % 16 == 0, "vam_tile_schedule: tiles of %d x %d: a latent cell is 16 x 16 pixels, sides are multiples of 16",
+              th, tw);
+  VAM_REQUIRE(L >= 1 && L <= VAM_MAX_LAYER_LEVELS, "vam_tile_schedule: 1 .. %d stages, got %d", VAM_MAX_LAYER_LEVELS, L);
+  VAM_REQUIRE(maps && coords && out, "vam_tile_schedule: need maps, coords and out");
+  VAM_REQUIRE(n >= 1 && (long)n * L <= 65535, "vam_tile_schedule: 1 .. %d tiles per launch at %d stages, got %d", 65535 / L, L, n);
+  a.maps = maps; a.coords = coords; a.out = out;
+  a.L = L; a.ch = th / 16; a.cw = tw / 16;
+  const dim3 grid(cdiv(a.cw, 4), a.ch, n * L);
+  VAM_REQUIRE((double)grid.x * grid.y * grid.z * 256.0 < 4294967296.0, "vam_tile_schedule: %d tiles of %d x %d at %d stages exceed one launch",
+              n, th, tw, L);
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)n * L * th * tw * 4.0 * (1.0 + 1.0 / 256.0));
+  hipLaunchKernelGGL(tile_schedule_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("tile_schedule_kernel");
 }
 
 int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,

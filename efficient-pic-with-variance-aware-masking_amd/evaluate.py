@@ -560,6 +560,67 @@ def embedded_roi_rd(model, images: torch.Tensor, schedule, region, coder=None, l
     return rows
 
 
+def picture_roi_schedule(H: int, W: int, boxes, roi_qualities: Sequence[float], background_qualities: Sequence[float], device):
+    """:func:`roi_schedule`'s stage ladder as a PICTURE-wide schedule for ``tiled.encode(schedule=)``: fp32
+    [L, H, W] on ``device``, at pixel resolution, any H and W.  ``boxes``: pixel boxes ``(y0, x0, y1, x1)`` of the region
+    (rows y0..y1-1, columns x0..x1-1).  First the region climbs through ``roi_qualities`` over the background at
+    ``background_qualities[0]``, then the background climbs through the rest of ``background_qualities`` under the region at
+    ``roi_qualities[-1]``; L = len(roi_qualities) + len(background_qualities) - 1.  Built with torch fills on the device."""
+    rq, bq = [float(q) for q in roi_qualities], [float(q) for q in background_qualities]
+    if not rq or not bq:
+        raise ValueError("picture_roi_schedule: roi_qualities and background_qualities need at least one quality each")
+    boxes = [tuple(int(v) for v in box[:4]) for box in boxes]
+    for y0, x0, y1, x1 in boxes:
+        if not (0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W):
+            raise ValueError(f"picture_roi_schedule: box {(y0, x0, y1, x1)} lies outside the picture of {H}x{W}")
+    stages = [(r, bq[0]) for r in rq] + [(rq[-1], g) for g in bq[1:]]
+    S = torch.empty((len(stages), H, W), dtype=torch.float32, device=device)
+    for k, (r, g) in enumerate(stages):
+        S[k].fill_(g)
+        for y0, x0, y1, x1 in boxes:
+            S[k, y0:y1, x0:x1].fill_(r)
+    return S
+
+
+def tiled_roi_rd(model, image: torch.Tensor, schedule, region, tile: int = 256, overlap: int = 32, coder=None, lanes: int = 1,
+                 base_lanes: int = 1, group: Optional[int] = None):
+    """:func:`embedded_roi_rd` for ONE picture of any size coded in scheduled tiles (tiled.encode(schedule=) /
+    PictureDecoder.decode(stage=)): the picture, fp32 [3, H, W] or [1, 3, H, W], is coded ONCE with the
+    picture-wide ``schedule`` fp32 [L, H, W], and stage k is decoded from ``data[:round_end[k]]``, the prefix that holds every
+    tile exactly at that stage.  One dict per stage: "stage", "bytes" (``round_end[k]``: picture header, every tile's head —
+    its schedule included — and the rounds up to k), "bpp" (8 * bytes / (H W), the true size), and "psnr", "psnr_in",
+    "psnr_out": :func:`compute_psnr`'s definition on all pixels and on the pixels inside and outside the boolean pixel
+    ``region`` [H, W] (NaN for an empty set); "enc_s" (the one encode) and "dec_s"."""
+    from . import tiled as TL
+    x = (image if image.dim() == 4 else image.unsqueeze(0)).contiguous()
+    H, W = int(x.shape[2]), int(x.shape[3])
+    r = torch.as_tensor(region)
+    if r.dim() != 2 or tuple(r.shape) != (H, W):
+        raise ValueError(f"tiled_roi_rd: region is a boolean [H, W] = {[H, W]}, got {list(r.shape)}")
+    sets = _region_sets(r.unsqueeze(0), 1, H, W, x.device)
+    rows = []
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        data = TL.encode(model, x, tile=tile, overlap=overlap, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group,
+                         schedule=schedule)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        lay = TL.layout(data)
+        for k in range(lay["stages"]):
+            end = lay["round_end"][k]
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            x_hat = TL.PictureDecoder(model, data[:end], coder=coder, group=group).decode(stage=k)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            sq, n = _sqdiff_sets(x, x_hat.unsqueeze(0).contiguous(), sets)
+            psnr = (-10.0 * torch.log10(sq / n)).cpu()
+            rows.append({"stage": k, "bytes": int(end), "bpp": 8.0 * end / (H * W), "psnr": float(psnr[0, 0]),
+                         "psnr_in": float(psnr[1, 0]), "psnr_out": float(psnr[2, 0]), "enc_s": t1 - t0, "dec_s": t3 - t2})
+    return rows
+
+
 def valid_epoch(epoch: int, test_dataloader: Iterable[torch.Tensor], criterion, model, pr_list: Sequence[float] = (0.05,),
                 rems: Optional[Sequence[float]] = None):
     """training/step.py:136-202 (without wandb): mean criterion loss over batches x qualities — what drives the

@@ -815,6 +815,21 @@ def tile_extract(image: torch.Tensor, coords: torch.Tensor, out: torch.Tensor, o
                                       out.data_ptr(), stream_ptr()), "vam_tile_extract")
 
 
+def tile_schedule(maps: torch.Tensor, coords: torch.Tensor, out: torch.Tensor, th: int, tw: int, overlap: int):
+    """out[i, k, a, b] = the maximum over the 16 x 16 pixels of latent cell (a, b) of tile (r, c) = coords[i] of
+    ``maps[k, min(r * Sy + y, H - 1), min(c * Sx + x, W - 1)]``: a picture-wide schedule ``maps`` fp32 [L, H, W] at pixel
+    resolution brought down onto the tiles' latent grids, the block maximum of
+    evaluate.latent_quality_map over :func:`tile_extract`'s replicated edge; a NaN in a block gives NaN.  ``coords`` int32
+    [n, 2] on the device, ``out`` fp32 [n, L, th / 16, tw / 16].  One launch; capturable."""
+    assert maps.dtype == torch.float32 and maps.is_contiguous() and maps.dim() == 3 and maps.is_cuda
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.device == maps.device
+    n, nl = int(out.shape[0]), int(maps.shape[0])
+    assert tuple(out.shape) == (n, nl, th // 16, tw // 16), (tuple(out.shape), (n, nl, th // 16, tw // 16))
+    assert coords.dtype == torch.int32 and coords.is_contiguous() and tuple(coords.shape) == (n, 2) and coords.device == maps.device
+    L.check(L.load().vam_tile_schedule(maps.data_ptr(), nl, maps.shape[1], maps.shape[2], int(th), int(tw), int(overlap),
+                                       coords.data_ptr(), n, out.data_ptr(), stream_ptr()), "vam_tile_schedule")
+
+
 def tile_blend(tiles: torch.Tensor, slot: torch.Tensor, w_lo: Optional[torch.Tensor], w_hi: Optional[torch.Tensor], H: int, W: int,
                overlap: int, window: Sequence[int], out: torch.Tensor, status: torch.Tensor):
     """The window (y0, x0, h, w) of a picture of H x W blended from decoded tiles: ``tiles`` fp32

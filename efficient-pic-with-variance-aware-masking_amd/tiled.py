@@ -21,8 +21,8 @@ stream down to a window and a number of rounds on the host alone, and what it re
 :func:`encode` and :class:`PictureDecoder` run the tiles, a group at a time, through ``embedded.encode_batch`` and
 ``embedded.EmbeddedDecoder`` unchanged: an image codes and decodes bit for bit the same alone or in a batch, so neither the
 bytes nor the pixels depend on the grouping.  By default (``allocation="tile"``) quality q keeps a quantile PER TILE: a
-tiled picture at q is not the untiled forward at q.  Out of scope: schedules (``embedded-3``), incremental feeding and a tile
-cache across ``decode`` calls.
+tiled picture at q is not the untiled forward at q.  Out of scope: incremental feeding and a tile cache across ``decode``
+calls.
 
 Picture-wide marks: ``encode(..., allocation="picture")`` takes, per mark and slice, ONE sigma threshold
 over the pool of all tiles' sigmas (``torch.quantile`` of the pool, bit for bit; ``csrc/pooled_select.hip``) and marks every
@@ -30,6 +30,17 @@ tile with the count of its elements at or above it.  Such a stream has a version
 then u16 allocation (1), n_marks, ns, reserved (0) and the thresholds float32 [n_marks][ns], then the u64 total, under the same
 CRC.  Tile heads stay ordinary embedded headers.  ``PictureDecoder.decode(mark=k)`` decodes every tile at its header's counts
 of mark k and, on a version-2 stream, checks them against the thresholds on its own sigma.
+
+Scheduled pictures: ``encode(..., schedule=S)`` with ``S`` fp32 [L, H, W], L quality maps at PIXEL
+resolution that never decrease from stage to stage, codes a region of interest first in every prefix.  A tile's schedule is
+``S_tile[k][a][b] = max over y, x in [0, 16) of S[k][min(r Sy + 16 a + y, H - 1)][min(c Sx + 16 b + x, W - 1)]``
+(vam_tile_schedule): ``evaluate.latent_quality_map``'s block maximum over vam_tile_extract's replicated edge.  Every tile is a
+scheduled embedded codestream of L stages (``embedded.encode_batch(schedule=)``) that carries its own schedule in its head.
+Such a stream has a version-3 header: the version-1 fields and table, then u16 kind (1: scheduled), u16 n_stages, u32
+reserved (0), then the u64 total, under the same CRC; its rounds are stages: ``data[:round_end[k]]`` and
+``extract(data, rounds=k + 1)`` hold every tile exactly at stage k, and ``PictureDecoder.decode(stage=k)`` is the blend of
+``forward_quality_map(tile, S_tile[k])``.  Out of scope: a schedule together with ``allocation="picture"``, reassembling the
+picture-level schedule at the receiver, incremental feeding and a tile cache.
 """
 from __future__ import annotations
 
@@ -44,12 +55,15 @@ from . import embedded as EB
 MAGIC = b"VAMp"
 VERSION = 1                                # allocation="tile": every tile marks its own quantiles
 VERSION_POOLED = 2                         # allocation="picture" (DESIGN section 9w): the header also carries the picture's thresholds
+VERSION_SCHEDULED = 3                      # schedule=S: every tile is scheduled, the rounds are stages
 ALLOCATIONS = ("tile", "picture")
 _ALLOC_PICTURE = 1                         # the one allocation value a version-2 header may state
 _PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
 PREAMBLE_BYTES = EB.PREAMBLE_BYTES
 _FIXED = struct.Struct("<IIHHHHHH")        # H, W, th / 64, tw / 64, V, R, C, n_rounds
 _POOLED = struct.Struct("<HHHH")           # version 2, after the table: allocation, n_marks, ns, reserved (0); then f32 [n_marks][ns]
+_SCHED = struct.Struct("<HHI")             # version 3, after the table: kind (1: scheduled), n_stages, reserved (0)
+_KIND_SCHEDULED = 1                        # the one kind a version-3 header may state
 _MAX_HEADER = EB._MAX_HEADER
 MAX_SIDE = 1 << 24                         # csrc/tiles.hip: the largest picture side
 MAX_GROUP = 32
@@ -135,8 +149,20 @@ class _Picture:
             raise ValueError(f"{what}: the header contradicts itself: {H} x {W} in tiles of {64 * th} x {64 * tw} with overlap {V} "
                              f"is no grid of {R} x {C}")
         table_end = _FIXED.size + 4 * R * C * (1 + nr)
-        self.version, self.thresholds = version, None
-        if version == VERSION_POOLED:
+        self.version, self.thresholds, self.stages = version, None, 0
+        if version == VERSION_SCHEDULED:
+            v3 = f"{what}: picture codestream version {VERSION_SCHEDULED}: the header contradicts itself"
+            if hlen != table_end + _SCHED.size + 8:
+                raise ValueError(f"{v3}: {R} x {C} tiles of {nr} rounds and the schedule fields take "
+                                 f"{table_end + _SCHED.size + 8} bytes, it states {hlen}")
+            kind, n_st, zero = _SCHED.unpack_from(d, PREAMBLE_BYTES + table_end)
+            if kind != _KIND_SCHEDULED or zero:
+                raise ValueError(f"{v3}: kind {kind} (reserved field {zero}); this reader knows kind {_KIND_SCHEDULED}, scheduled "
+                                 "tiles whose rounds are stages")
+            if n_st < 1 or nr > n_st + 1:               # a whole stream has one round more than stages: what follows the last stage
+                raise ValueError(f"{v3}: {n_st} stages and {nr} rounds: a picture of L >= 1 stages holds at most L + 1 rounds")
+            self.stages = n_st
+        elif version == VERSION_POOLED:
             # every refusal of the extension names the version: a version-1 header read as version 2 says so
             v2 = f"{what}: picture codestream version {VERSION_POOLED}: the header contradicts itself"
             if hlen < table_end + _POOLED.size + 8:
@@ -209,9 +235,9 @@ def _header_end(d, what: str) -> Optional[int]:
     magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
     if magic != MAGIC:
         raise ValueError(f"{what}: not a picture codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
-    if version not in (VERSION, VERSION_POOLED) or reserved:
+    if version not in (VERSION, VERSION_POOLED, VERSION_SCHEDULED) or reserved:
         raise ValueError(f"{what}: picture codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
-                         f"reader knows versions {VERSION} and {VERSION_POOLED}")
+                         f"reader knows versions {VERSION}, {VERSION_POOLED} and {VERSION_SCHEDULED}")
     if not _FIXED.size + 4 + 8 <= hlen <= _MAX_HEADER:
         raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 12} .. {_MAX_HEADER}")
     return PREAMBLE_BYTES + hlen
@@ -231,18 +257,27 @@ def _parse(data, what: str):
     return d, s
 
 
-def _tile_layout(stream, g: dict, rc, what: str) -> dict:
-    """embedded.layout of one tile's head or codestream, with this format's refusals."""
+def _tile_layout(stream, g: dict, rc, what: str, stages: int = 0) -> dict:
+    """embedded.layout of one tile's head or codestream, with this format's refusals.  ``stages`` = L > 0: the tiles of a
+    scheduled picture (version 3), scheduled codestreams marked by the stages 0 .. L - 1; 0: plain tiles."""
     try:
         lay = EB.layout(stream)
     except ValueError as e:
         raise ValueError(f"{what}: tile {rc}: {e}") from e
-    if lay["scheduled"]:
-        raise ValueError(f"{what}: tile {rc} is scheduled ({lay['format']!r}); a picture codestream carries no schedules")
+    if not stages:
+        if lay["scheduled"]:
+            raise ValueError(f"{what}: tile {rc} is scheduled ({lay['format']!r}); a picture codestream carries no schedules")
+    elif not lay["scheduled"]:
+        raise ValueError(f"{what}: tile {rc} is plain ({lay['format']!r}); a scheduled picture codestream (version "
+                         f"{VERSION_SCHEDULED}) of {stages} stages carries scheduled tiles only")
+    elif [int(v) for v in lay["marks"]["stage"]] != list(range(stages)):
+        raise ValueError(f"{what}: tile {rc} is marked at the stages {[int(v) for v in lay['marks']['stage']]}; the tiles of this "
+                         f"picture have {stages} stages and are marked at {list(range(stages))}")
     if tuple(lay["shape"]) != (g["th"] // 64, g["tw"] // 64):
         raise ValueError(f"{what}: tile {rc} is an image of {64 * lay['shape'][0]} x {64 * lay['shape'][1]}, the tiles of this picture "
                          f"are {g['th']} x {g['tw']}")
-    lay["marks"] = [float(q) for q in lay["marks"]["q"]]                  # the marked qualities; counts and bytes are a tile's own
+    # the marked qualities, or the stages of a scheduled tile; counts and bytes are a tile's own
+    lay["marks"] = [int(v) for v in lay["marks"]["stage"]] if stages else [float(q) for q in lay["marks"]["q"]]
     return lay
 
 
@@ -271,7 +306,7 @@ def _tile_meta(d, s: _Picture, what: str) -> Optional[dict]:
         off, size = int(s.off[0, i]), int(s.size[0, i])
         if off + size > len(d):
             break
-        lay = _tile_layout(d[off:off + size], s.g, s.rc(i), what)
+        lay = _tile_layout(d[off:off + size], s.g, s.rc(i), what, s.stages)
         want = _pieces(lay)
         if s.nr > len(want) - 1 or [int(v) for v in s.table[i]] != want[:1 + s.nr]:
             raise ValueError(f"{what}: the header contradicts tile {s.rc(i)}: its table row {[int(v) for v in s.table[i]]} is not the "
@@ -286,12 +321,18 @@ def _tile_meta(d, s: _Picture, what: str) -> Optional[dict]:
     return first
 
 
-def _assemble(g: dict, table: np.ndarray, get, thresholds: Optional[np.ndarray] = None) -> bytes:
+def _assemble(g: dict, table: np.ndarray, get, thresholds: Optional[np.ndarray] = None, stages: int = 0) -> bytes:
     """The picture codestream of ``table`` int64 [R C, 1 + nr]; ``get(i, k)`` gives the bytes of column k of tile i.
-    ``thresholds`` fp32 [n_marks][ns]: a version-2 header that carries them (picture-wide marks)."""
+    ``thresholds`` fp32 [n_marks][ns]: a version-2 header that carries them (picture-wide marks).  ``stages`` = L > 0: a
+    version-3 header that states them (scheduled tiles)."""
     nr = table.shape[1] - 1
-    ext = b""
-    if thresholds is not None:
+    ext, version = b"", VERSION
+    if stages:
+        if not 1 <= stages <= 0xFFFF or nr > stages + 1:
+            raise ValueError(f"{stages} stages and {nr} rounds: a picture of L stages, 1 .. 65535, holds at most L + 1 rounds")
+        ext, version = _SCHED.pack(_KIND_SCHEDULED, stages, 0), VERSION_SCHEDULED
+    elif thresholds is not None:
+        version = VERSION_POOLED
         thr = np.ascontiguousarray(thresholds, dtype="<f4")
         if thr.ndim != 2 or not (1 <= thr.shape[0] <= 0xFFFF and 1 <= thr.shape[1] <= 0xFFFF):
             raise ValueError(f"thresholds are float32 [n_marks][ns], got {list(thr.shape)}")
@@ -305,17 +346,29 @@ def _assemble(g: dict, table: np.ndarray, get, thresholds: Optional[np.ndarray] 
         raise ValueError(f"{nr} rounds; the format carries up to 65535")
     header = _FIXED.pack(g["H"], g["W"], g["th"] // 64, g["tw"] // 64, g["V"], g["R"], g["C"], nr) + table.astype("<u4").tobytes() \
         + ext + struct.pack("<Q", PREAMBLE_BYTES + hlen + int(table.sum()))
-    out = [_PREAMBLE.pack(MAGIC, VERSION_POOLED if ext else VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
+    out = [_PREAMBLE.pack(MAGIC, version, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
     out += [get(i, k) for k in range(1 + nr) for i in range(table.shape[0]) if table[i, k]]
     return b"".join(out)
 
 
-def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None) -> bytes:
+def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None, stages: Optional[int] = None) -> bytes:
     """The picture codestream of R C whole tile codestreams (``embedded.to_bytes``), given in raster order as one flat
     sequence or as [R][C]; None marks an absent tile.  Pure framing on the host.  ValueError for a wrong count, a cut or
     scheduled tile, a tile of another shape and tiles that differ in marks, lanes or base_lanes.  ``thresholds`` fp32
     [n_marks][ns]: the picture-wide thresholds behind the tiles' marks, one row per mark, never rising
-    with the mark; the header is then version 2 and carries them.  None: version 1, byte for byte as ever."""
+    with the mark; the header is then version 2 and carries them.  None: version 1, byte for byte as ever.
+
+    ``stages`` = L (exclusive with ``thresholds``): every present tile is a SCHEDULED embedded codestream
+    of exactly L stages, marked at the stages 0 .. L - 1; a plain tile and another stage count are ValueErrors naming the
+    tile.  The header is then version 3 and states L; the heads are the tiles' own and carry their schedules.  None:
+    nothing changes, and a scheduled tile is refused."""
+    if stages is not None:
+        stages = _int(stages, "pack: stages")
+        if not 1 <= stages <= 0xFFFF:
+            raise ValueError(f"pack: stages is 1 .. 65535, got {stages}")
+        if thresholds is not None:
+            raise ValueError("pack: give thresholds or stages, not both: picture-wide marks (version 2) are marks of plain tiles, a "
+                             "scheduled picture (version 3) is marked by stage")
     g = grid(H, W, tile, overlap)
     try:
         streams = list(tile_streams)
@@ -334,7 +387,7 @@ def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None)
             views.append(None)
             continue
         v = EB._view(s, f"pack: tile {rc}")
-        lay = _tile_layout(v, g, rc, "pack")
+        lay = _tile_layout(v, g, rc, "pack", stages or 0)
         if len(v) != lay["total"]:
             raise ValueError(f"pack: tile {rc}: {len(v)} bytes, its header states a total of {lay['total']}: a picture is packed from "
                              "whole tile codestreams and cut as bytes")
@@ -358,7 +411,7 @@ def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None)
             if (thresholds[1:] > thresholds[:-1]).any():
                 raise ValueError("pack: a threshold rises with the mark: a higher quality never keeps less")
     try:
-        return _assemble(g, table, lambda i, k: bytes(views[i][int(edges[i, k]):int(edges[i, k + 1])]), thresholds)
+        return _assemble(g, table, lambda i, k: bytes(views[i][int(edges[i, k]):int(edges[i, k + 1])]), thresholds, stages or 0)
     except ValueError as e:
         raise ValueError(f"pack: {e}") from e
 
@@ -381,7 +434,9 @@ def layout(data) -> dict:
     than marks, and its last ``round_end`` is ``total``).  ``marks``, ``lanes``, ``base_lanes``, ``ns`` and ``format`` are
     those of the tiles, read from the heads that ``data`` holds whole (all checked against the table and each other); None
     while it holds none.  ``allocation``: "tile" (version 1) or "picture" (version 2), and then
-    ``thresholds`` float32 [marks][ns], the picture-wide sigma thresholds behind the tiles' marks (None for "tile")."""
+    ``thresholds`` float32 [marks][ns], the picture-wide sigma thresholds behind the tiles' marks (None for "tile").
+    ``scheduled`` and ``stages``: True and L for a version-3 stream, whose tiles are scheduled, whose
+    rounds are stages and whose ``marks`` is the stage list [0 .. L - 1]; False and 0 otherwise."""
     d, s = _parse(data, "layout")
     g, meta = s.g, _tile_meta(d, s, "layout")
     R, C = g["R"], g["C"]
@@ -394,6 +449,7 @@ def layout(data) -> dict:
         out[key] = meta[key] if meta is not None else None
     out["allocation"] = ALLOCATIONS[s.version == VERSION_POOLED]
     out["thresholds"] = None if s.thresholds is None else s.thresholds.copy()
+    out["scheduled"], out["stages"] = s.stages > 0, s.stages
     return out
 
 
@@ -413,7 +469,8 @@ def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
     the first ``rounds`` rounds (None: all it has).  What a server does to crop and to cut the quality, without the model.
     ``data`` must hold what is kept.  ``extract(data)`` is ``data``; an extract of an extract is an extract.  ValueError
     names a wanted tile that ``data`` lacks.  An extract keeps the version, and a version-2 stream its thresholds: the pool
-    is the picture's, not the window's."""
+    is the picture's, not the window's; a version-3 stream keeps its n_stages, and ``rounds=k + 1`` holds every kept tile
+    exactly at stage k."""
     d, s = _parse(data, "extract")
     _tile_meta(d, s, "extract")
     nr = s.nr if rounds is None else _int(rounds, "extract: rounds")
@@ -434,7 +491,7 @@ def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
         i, k = (int(v) for v in short[0])
         raise ValueError(f"extract: {len(d)} bytes end before {'the head' if k == 0 else f'round {k - 1}'} of tile {s.rc(i)} does; "
                          "a codestream is extracted from bytes that hold what is kept")
-    return _assemble(s.g, table, lambda i, k: bytes(d[int(s.off[k, i]):int(s.off[k, i] + s.size[k, i])]), s.thresholds)
+    return _assemble(s.g, table, lambda i, k: bytes(d[int(s.off[k, i]):int(s.off[k, i] + s.size[k, i])]), s.thresholds, s.stages)
 
 
 # ---------------------------------------------------------------------------------------------------- encoder and decoder
@@ -456,8 +513,48 @@ def _check_group(group, th: int, tw: int, what: str) -> int:
     return group
 
 
+def _check_picture_schedule(schedule, H: int, W: int, device):
+    """A picture-wide schedule for a picture of H x W on ``device``: an fp32 tensor [L, H, W] there,
+    1 <= L <= VAM_MAX_LAYER_LEVELS, every entry finite and >= 0, never decreasing from stage to stage at any pixel.  Shape,
+    dtype, device and L are checked on the host; the values with a few reductions on the device and ONE read.  Returns the
+    contiguous tensor; ValueError names the stage and the pixel of the first violation."""
+    import torch
+    from . import _lib as L
+    G = L.VAM_MAX_LAYER_LEVELS
+    if not isinstance(schedule, torch.Tensor) or schedule.dtype != torch.float32 or schedule.dim() != 3 \
+            or tuple(schedule.shape[1:]) != (H, W):
+        got = f"{schedule.dtype} {list(schedule.shape)}" if isinstance(schedule, torch.Tensor) else type(schedule).__name__
+        raise ValueError(f"tiled.encode: schedule is an fp32 tensor [L, H, W] = [1..{G}, {H}, {W}], L quality maps at pixel "
+                         f"resolution, got {got}")
+    if schedule.device != device:
+        raise ValueError(f"tiled.encode: schedule lies on {schedule.device}, the image on {device}: a picture-wide schedule is "
+                         "read on the image's device")
+    n_st = int(schedule.shape[0])
+    if not 1 <= n_st <= G:
+        raise ValueError(f"tiled.encode: schedule: 1..{G} stages, got {n_st}")
+    S = schedule.detach().contiguous()
+    with torch.no_grad():
+        flat = S.reshape(-1)
+        bad = (~torch.isfinite(flat)) | (flat < 0)
+        down = (S[1:] < S[:-1]).reshape(-1) if n_st > 1 else torch.zeros((1,), dtype=torch.bool, device=device)
+        at_bad, at_down = bad.to(torch.uint8).argmax(), down.to(torch.uint8).argmax()      # the first violation of each kind
+        lo = flat[at_down] if n_st > 1 else flat[0]
+        hi = flat[at_down + H * W] if n_st > 1 else flat[0]
+        got = torch.stack([bad[at_bad].double(), at_bad.double(), flat[at_bad].double(), down[at_down].double(), at_down.double(),
+                           lo.double(), hi.double()]).cpu().numpy()
+    where = lambda i: (int(i) // (H * W), (int(i) % (H * W)) // W, int(i) % W)
+    if got[0]:
+        k, y, x = where(got[1])
+        raise ValueError(f"tiled.encode: schedule: stage {k}, pixel ({y}, {x}): qualities are finite and >= 0, got {float(got[2])}")
+    if got[3]:
+        k, y, x = where(got[4])
+        raise ValueError(f"tiled.encode: schedule: pixel ({y}, {x}): stage {k + 1} lowers the quality from {float(got[5])} to "
+                         f"{float(got[6])}; a schedule never decreases from one stage to the next")
+    return S
+
+
 def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Sequence[float]] = None, coder: Optional[str] = None,
-           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile") -> bytes:
+           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile", schedule=None) -> bytes:
     """The picture codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device, any H, W >= 1: the tiles are cut
     ``group`` at a time (vam_tile_extract, one launch per group), each group goes through ``embedded.encode_batch`` (``marks``,
     ``coder``, ``lanes`` and ``base_lanes`` are its) and ``embedded.to_bytes``, and :func:`pack` frames them.  ``group``: the
@@ -468,11 +565,24 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     (``embedded._encode_front``) and writes its sigmas, in rank order, as keys into one buffer [T, ns, n] (vam_pool_keys); one
     vam_pooled_select gives, per mark and slice, ``torch.quantile`` of the pool of ALL tiles' sigmas, one vam_threshold_counts
     every tile's counts; pass 2 (``embedded._encode_finish``) marks the tiles with them.  The tile heads stay ordinary
-    embedded headers; the picture header is version 2 and carries the thresholds.  Marks are qualities > 0."""
+    embedded headers; the picture header is version 2 and carries the thresholds.  Marks are qualities > 0.
+
+    ``schedule`` (exclusive with ``marks`` and with ``allocation="picture"``): a picture-wide schedule,
+    fp32 [L, H, W] on the image's device, 1 <= L <= 32 quality maps at PIXEL resolution, every entry finite and >= 0 and
+    never decreasing from stage to stage (checked on the device up front; a violation names stage and pixel).  Per group one
+    vam_tile_extract, one vam_tile_schedule (the block maximum of every latent cell over the tile's replicated pixels), one
+    copy of that small result to the host and ``embedded.encode_batch(schedule=)`` unchanged; the picture header is
+    version 3 and its rounds are stages.  A tile whose schedule holds more than 32 distinct qualities is
+    ``embedded.check_schedule``'s error, naming the tile (r, c)."""
     import torch
     from . import ops
     if allocation not in ALLOCATIONS:
         raise ValueError(f"tiled.encode: allocation is one of {ALLOCATIONS}, got {allocation!r}")
+    if schedule is not None and marks is not None:
+        raise ValueError("tiled.encode: give marks or schedule, not both (a scheduled picture is marked per stage)")
+    if schedule is not None and allocation != "tile":
+        raise ValueError(f"tiled.encode: a schedule goes with allocation='tile', not with {allocation!r}: picture-wide marks are "
+                         "marks of plain tiles")
     if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() not in (3, 4) \
             or tuple(image.shape[:-2]) not in ((3,), (1, 3)):
         raise ValueError("tiled.encode: image is an fp32 tensor [3, H, W] or [1, 3, H, W], got "
@@ -485,11 +595,33 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     coords = [(r, c) for r in range(g["R"]) for c in range(g["C"])]
     streams: List[bytes] = []
 
-    def cut(i0):
+    def cut(i0, with_coords=False):
         part = coords[i0:i0 + group]
+        cd = torch.tensor(part, dtype=torch.int32).to(img.device)
         x = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=img.device)
-        ops.tile_extract(img, torch.tensor(part, dtype=torch.int32).to(img.device), x, g["V"])
-        return x
+        ops.tile_extract(img, cd, x, g["V"])
+        return (x, cd) if with_coords else x
+    if schedule is not None:
+        S = _check_picture_schedule(schedule, H, W, img.device)
+        n_st, h, w = int(S.shape[0]), g["th"] // 16, g["tw"] // 16
+        with torch.no_grad():
+            for i0 in range(0, len(coords), group):
+                x, cd = cut(i0, True)
+                st = torch.empty((x.shape[0], n_st, h, w), dtype=torch.float32, device=img.device)
+                ops.tile_schedule(S, cd, st, g["th"], g["tw"], g["V"])
+                st = st.cpu().numpy()
+                stage_maps = [st[:, k] for k in range(n_st)]
+                try:
+                    cs = EB.encode_batch(model, x, schedule=stage_maps, coder=coder, lanes=lanes, base_lanes=base_lanes)
+                except ValueError:
+                    for b, rc in enumerate(coords[i0:i0 + group]):     # a tile's schedule is checked alone as in its group
+                        try:
+                            EB.check_schedule([m[b:b + 1] for m in stage_maps], 1, h, w)
+                        except ValueError as e:
+                            raise ValueError(f"tiled.encode: tile {rc}: {e}") from e
+                    raise
+                streams += [EB.to_bytes(c) for c in cs]
+        return pack(H, W, tile, overlap, streams, stages=n_st)
     if allocation == "tile":
         with torch.no_grad():
             for i0 in range(0, len(coords), group):
@@ -527,7 +659,8 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
 class PictureDecoder:
     """Decodes a picture codestream by window.  ``data``: any prefix of at least :func:`need_bytes`, or an :func:`extract`.
     ``shape``: the true (H, W); ``grid``: the geometry; ``rounds``: int [R, C], the complete rounds ``data`` holds of every
-    tile, -1 where the tile is absent.  Every :meth:`decode` decodes the tiles of its window afresh, ``group`` at a time
+    tile, -1 where the tile is absent; ``scheduled`` and ``stages``: whether the picture is scheduled and
+    its L, else False and 0.  Every :meth:`decode` decodes the tiles of its window afresh, ``group`` at a time
     through ``embedded.EmbeddedDecoder`` (``coder`` is its), and blends them with one vam_tile_blend launch."""
 
     def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
@@ -540,6 +673,7 @@ class PictureDecoder:
         self.meta = _tile_meta(d, s, "PictureDecoder")
         self.m, self.coder, self._d, self._s = model, P._check_coder(model, coder), bytes(d), s
         self.grid, self.shape = dict(s.g), (s.g["H"], s.g["W"])
+        self.scheduled, self.stages = s.stages > 0, s.stages                     # version 3: rounds are stages
         self.group = _check_group(group, s.g["th"], s.g["tw"], "PictureDecoder")
         whole = (s.held(len(d))[1:] == s.size[1:])                               # [nr, R C]: a piece of 0 bytes is whole
         done = np.cumprod(whole, axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
@@ -553,8 +687,10 @@ class PictureDecoder:
             self._ramps = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ramps(self.grid["V"]))
         return self._ramps
 
-    def _decode_tiles(self, containers, q, mark=None, part=None):
+    def _decode_tiles(self, containers, q, mark=None, part=None, stage=None):
         dec = EB.EmbeddedDecoder(self.m, containers, coder=self.coder)
+        if stage is not None:
+            return dec.decode_stages([stage])[0]["x_hat"]
         if mark is None:
             return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
         x_hat = dec.decode_marks([mark])[0]["x_hat"]
@@ -603,7 +739,24 @@ class PictureDecoder:
                              f"'picture') and a picture-wide quality exists only where the encoder pooled: the marks are {marks}")
         return marks.index(float(q))
 
-    def decode(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, dtype=None):
+    def _stage_of(self, q, mark, stage) -> Optional[int]:
+        """The stage a ``decode`` call means, checked against what this picture is."""
+        if stage is None:
+            if q is not None and self.scheduled:
+                raise ValueError(f"PictureDecoder.decode: this picture is scheduled ({self.stages} stages): a uniform quality is no "
+                                 f"prefix of a scheduled rank order, decode a stage with stage=0 .. {self.stages - 1}")
+            return None
+        if q is not None or mark is not None:
+            raise ValueError("PictureDecoder.decode: give stage alone, not with q or mark")
+        if not self.scheduled:
+            raise ValueError("PictureDecoder.decode: stage= decodes a scheduled picture (tiled.encode(schedule=)); this picture "
+                             "carries no schedule, decode a quality with q or a mark with mark")
+        stage = _int(stage, "PictureDecoder.decode: stage")
+        if not 0 <= stage < self.stages:
+            raise ValueError(f"PictureDecoder.decode: stage is 0 .. {self.stages - 1}, got {stage}")
+        return stage
+
+    def decode(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
         """The window (y0, x0, h, w) of the picture (None: all of it): fp32 [3, h, w], or uint8 [h, w, 3] for
         ``dtype=torch.uint8`` (round half to even of clamp(v, 0, 1) * 255, as evaluate.write_image).  ``q`` = None: from
         everything ``data`` holds of every tile (``EmbeddedDecoder.decode``); a quality: ``decode_qualities([q])``, every tile
@@ -614,7 +767,12 @@ class PictureDecoder:
         (``EmbeddedDecoder.decode_marks``), for both versions.  On a version-2 stream (picture-wide marks)
         every decoded tile is also checked: its own sigma against the header's thresholds must reproduce its marks' counts,
         else a ValueError names tile, mark and slice; and ``q`` is accepted only when it is a marked quality and then means
-        that mark: any other q is a ValueError that lists the marks."""
+        that mark: any other q is a ValueError that lists the marks.
+
+        ``stage`` = k (exclusive with ``q`` and ``mark``; scheduled pictures): every tile at stage k of its
+        own schedule (``EmbeddedDecoder.decode_stages([k])``), the blend of ``forward_quality_map(tile, S_tile[k])``; a tile
+        whose bytes end before stage k is named.  On a scheduled picture ``mark=k`` gives the same pixels and ``q`` is a
+        ValueError that points here; on a plain picture ``stage`` is a ValueError."""
         import torch
         from . import _lib as L
         from . import ops
@@ -622,6 +780,7 @@ class PictureDecoder:
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
+        stage = self._stage_of(q, mark, stage)
         mark = self._mark_of(q, mark)
         y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
         tiles = tiles_for(g, (y0, x0, h, w))
@@ -635,11 +794,11 @@ class PictureDecoder:
                 part = tiles[i0:i0 + self.group]
                 cs = [EB.from_bytes(s.stream(self._d, r * g["C"] + c)) for r, c in part]
                 try:
-                    x_hat = self._decode_tiles(cs, q, mark, part)
+                    x_hat = self._decode_tiles(cs, q, mark, part, stage)
                 except ValueError:
                     for rc, c1 in zip(part, cs):            # a tile decodes alone as in its group: find the one that is refused
                         try:
-                            self._decode_tiles([c1], q, mark, [rc])
+                            self._decode_tiles([c1], q, mark, [rc], stage)
                         except ValueError as e:
                             raise ValueError(f"PictureDecoder.decode: tile {rc}: {e}") from e
                     raise

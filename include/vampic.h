@@ -419,11 +419,18 @@ int vam_threshold_counts(const uint32_t* keys, int T, int n_slice, int n, const 
  * with w_lo[l1].  out = sum over the pixel's tiles, ascending r and within that ascending c, of (wy * wx) * v, every product
  * and add one fp32 operation, the sum starting from its first term: fp32 [3, h, w] (out_u8 = 0) or uint8 [h, w, 3]
  * (out_u8 = 1) as rintf(clamp(v, 0, 1) * 255).  A pixel that needs an absent tile (a slot outside 0 .. n - 1) sets
- * *status = 1 and skips that term; the caller clears status.  No atomics, no allocation: both calls can be captured. */
+ * *status = 1 and skips that term; the caller clears status.  No atomics, no allocation: both calls can be captured.
+ * vam_tile_schedule: maps fp32 [L, H, W], a picture-wide schedule of 1 <= L <= VAM_MAX_LAYER_LEVELS quality
+ * maps at pixel resolution, the coords of vam_tile_extract, th and tw multiples of 16, out fp32 [n, L, th / 16, tw / 16] with
+ *   out[i, k, a, b] = max over y, x in [0, 16) of maps[k, min(r Sy + 16 a + y, H - 1), min(c Sx + 16 b + x, W - 1)]:
+ * the block maximum of a latent cell over the tile's replicated pixels; a NaN anywhere in the block gives NaN.  An (r, c)
+ * outside the grid leaves its rows unwritten.  n L <= 65535 per launch.  No atomics, no allocation, capturable. */
 int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
                      void* stream);
 int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
                    int tw, int V, int y0, int x0, int h, int w, void* out, int out_u8, int32_t* status, void* stream);
+int vam_tile_schedule(const float* maps, int L, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
+                      void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).

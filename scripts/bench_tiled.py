@@ -17,10 +17,18 @@ the picture header's bytes and, per mark, the smallest and largest fraction of i
 vam_pool_keys for the last group of tiles beside a ``copy_`` of the rows it writes), and ``decode(mark=k)`` of the picture-wide
 stream beside ``decode(q=q_k)`` of the per-tile one for the middle mark.  Without the flag the line is what it always was.
 
+``--schedule roi`` adds ``"scheduled"``: the picture coded with a picture-wide schedule of five stages
+(``evaluate.picture_roi_schedule``: the box of the 512 x 512 window climbs through 0.5, 2.5, 5 over a background at 0.05, then the
+background through 0.5, 2.5) — the encode time beside the unscheduled ``encode_ms`` of the same run, ``decode(stage=k)`` for
+every stage beside ``decode(mark=k)`` of the unscheduled stream, vam_tile_schedule alone for all tiles in one launch (HIP events
+over 50 launches) beside a ``copy_`` of as many bytes as it reads, the bytes of every stage (``round_end``) and the share of
+every stage's round that lies in the tiles the box touches.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
+                                  [--schedule roi]
 """
 import argparse
 import json
@@ -123,6 +131,46 @@ def allocations(a, net, x, g, kw, TL, EB, ops):
     return out
 
 
+ROI_QUALITIES, BACKGROUND_QUALITIES = (0.5, 2.5, 5.0), (0.05, 0.5, 2.5)
+
+
+def scheduled(a, net, x, g, kw, plain, window, TL, EV, ops):
+    """The ``--schedule roi`` section: see the module docstring.  ``plain``: the unscheduled stream of the same run."""
+    H, W = g["H"], g["W"]
+    y0, x0, h, w = window
+    S = EV.picture_roi_schedule(H, W, [(y0, x0, y0 + h, x0 + w)], ROI_QUALITIES, BACKGROUND_QUALITIES, x.device)
+    n_st = int(S.shape[0])
+    ms, data = wall_ms(lambda: TL.encode(net, x, schedule=S, **kw), a.warmup, a.reps)
+    lay = TL.layout(data)
+    box_tiles = TL.tiles_for(g, window)
+    out = {"box": [y0, x0, y0 + h, x0 + w], "roi_qualities": list(ROI_QUALITIES), "background_qualities": list(BACKGROUND_QUALITIES),
+           "stages": n_st, "encode_ms": round(ms, 2), "total_bytes": lay["total"], "header_bytes": lay["header_end"],
+           "head_bytes": lay["need_bytes"] - lay["header_end"], "box_tiles": len(box_tiles), "round_end": lay["round_end"][:n_st]}
+    share = []
+    for k in range(n_st):
+        size = lay["piece"][k]
+        total = sum(n for row in size for _, n in row)
+        share.append({"round_bytes": total, "box_tiles_pct": round(100.0 * sum(size[r][c][1] for r, c in box_tiles) / max(total, 1), 2)})
+    out["rounds"] = share
+    dec = TL.PictureDecoder(net, data, coder=a.coder)
+    out["decode_stage_ms"] = [round(wall_ms(lambda: dec.decode(stage=k), a.warmup, a.reps)[0], 2) for k in range(n_st)]
+    dp = TL.PictureDecoder(net, plain, coder=a.coder)
+    marks = TL.layout(plain)["marks"]
+    out["decode_plain_mark_ms"] = {str(k): round(wall_ms(lambda: dp.decode(mark=k), a.warmup, a.reps)[0], 2)
+                                   for k in sorted({min(2, len(marks) - 1), len(marks) // 2})}
+    out["plain_marks"] = marks
+    coords = TL.tiles_for(g)
+    cd = torch.tensor(coords, dtype=torch.int32).to(x.device)
+    st = torch.empty((len(coords), n_st, g["th"] // 16, g["tw"] // 16), dtype=torch.float32, device=x.device)
+    src = torch.empty((len(coords) * n_st * g["th"] * g["tw"],), dtype=torch.float32, device=x.device)
+    dst = torch.empty_like(src)
+    out["tile_schedule_us"] = round(event_us(lambda: ops.tile_schedule(S, cd, st, g["th"], g["tw"], g["V"])), 2)
+    out["tile_schedule_copy_us"] = round(event_us(lambda: dst.copy_(src)), 2)
+    out["tile_schedule_in_bytes"], out["tile_schedule_out_bytes"] = src.numel() * 4, st.numel() * 4
+    out["schedule_bytes"] = S.numel() * 4
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -135,6 +183,7 @@ def main():
     ap.add_argument("--lanes", type=int, default=1)
     ap.add_argument("--base-lanes", type=int, default=1)
     ap.add_argument("--allocation", nargs="+", default=None, choices=["tile", "picture"])
+    ap.add_argument("--schedule", default=None, choices=["roi"])
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -190,6 +239,8 @@ def main():
                                         "overhead_pct": round(100.0 * one["base_end"] / one["total"], 3)}
         if a.allocation:
             res["allocations"] = allocations(a, net, x, g, kw, TL, EB, ops)
+        if a.schedule:
+            res["scheduled"] = scheduled(a, net, x, g, kw, data, window, TL, EV, ops)
     for k in ("encode_ms", "decode_full_ms", "decode_window_ms"):
         res[k] = round(res[k], 2)
     print(json.dumps(res))
