@@ -20,6 +20,10 @@
 //                         evaluate.latent_quality_map composed with the extract kernel's edge replication.  One wave per
 //                         output cell: lane l reads the four pixels 4 (l & 3) .. of row l >> 2 and the 64 partial results are
 //                         reduced with wave-64 shuffles.  A NaN anywhere in the block gives NaN (fmaxf alone would drop it).
+//   tile_refresh_kernel   tile_blend_kernel over a box of a persistent canvas: a pixel is computed and
+//                         stored only when one of its tiles is marked in `dirty` [R][C]; the value is blend_run's, so it is
+//                         tile_blend_kernel's bit for bit.  A pixel without a dirty tile is not written and its slots are not
+//                         read.  The output has the canvas's pitch; wide stores need all four pixels written.
 // All move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
 // scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
 #include "common.h"
@@ -260,6 +264,90 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const BlendArgs a) {
   }
 }
 
+struct RefreshArgs {
+  BlendArgs b;                              // tiles, slot, ramps, status, geometry; y0, x0, h, w: the box to visit
+  const int32_t* dirty;
+  int cy0, cx0, ch, cw;                     // the canvas's window in the picture: out has its pitch
+};
+
+// Whether one of the 1, 2 or 4 tiles of a pixel at (ay, ax) is dirty.  Reads `dirty` only, never a slot.
+__device__ __forceinline__ bool tiles_dirty(const int32_t* dirty, int C, const Axis ay, const Axis ax) {
+  const int32_t* row = dirty + ay.t1 * C + ax.t1;
+  bool d = row[0] != 0;
+  if (ax.two) d |= row[-1] != 0;
+  if (ay.two) {
+    d |= row[-C] != 0;
+    if (ax.two) d |= row[-C - 1] != 0;
+  }
+  return d;
+}
+
+// tile_blend_kernel's thread layout over the box: a thread owns four consecutive pixels of one row.  Bit k of `wr` says that
+// pixel k has a dirty tile and is written; a pixel without one is neither computed nor stored, and its slots are not read.
+__global__ __launch_bounds__(256) void tile_refresh_kernel(const RefreshArgs a) {
+  const BlendArgs& b = a.b;
+  const TileGeom& g = b.g;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= b.w || y >= b.h) return;
+  const int nv = min(4, b.w - x);
+  const int X = b.x0 + x, Y = b.y0 + y;
+  const Axis ay = tile_axis(Y, g.Sy, g.V, g.R);
+  const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
+  float acc[3][4];
+  unsigned wr = 0;
+  bool run = false;
+  if (nv == 4) {
+    const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
+    run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;         // one tile set for the four: one decision
+  }
+  if (run) {
+    if (!tiles_dirty(a.dirty, g.C, ay, ax0)) return;
+    blend_run<4>(b, ay, ax0, acc, 0);
+    wr = 15u;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k >= nv) continue;
+      const Axis ax = tile_axis(X + k, g.Sx, g.V, g.C);
+      if (!tiles_dirty(a.dirty, g.C, ay, ax)) continue;
+      blend_run<1>(b, ay, ax, acc, k);
+      wr |= 1u << k;
+    }
+    if (!wr) return;
+  }
+  const long at = (long)(Y - a.cy0) * a.cw + (X - a.cx0);
+  if (b.out_u8) {
+    uint8_t* dst = b.out_u8 + 3 * at;
+    unsigned v[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = (wr >> k) & 1u ? tile_u8(acc[ch][k]) : 0u;
+    if (wr == 15u && ((uintptr_t)dst & 3) == 0) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        reinterpret_cast<uint32_t*>(dst)[j] = v[4 * j] | (v[4 * j + 1] << 8) | (v[4 * j + 2] << 16) | (v[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j)
+        if ((wr >> (j / 3)) & 1u) dst[j] = (uint8_t)v[j];
+    }
+    return;
+  }
+  const long plane = (long)a.ch * a.cw;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float* dst = b.out_f + ch * plane + at;
+    if (wr == 15u && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((wr >> k) & 1u) dst[k] = acc[ch][k];
+    }
+  }
+}
+
 }  // namespace
 }  // namespace vam
 
@@ -317,6 +405,33 @@ int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* 
   ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
   hipLaunchKernelGGL(tile_blend_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
   return check_launch("tile_blend_kernel");
+}
+
+int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32_t* dirty, const float* w_lo, const float* w_hi,
+                     int H, int W, int th, int tw, int V, int cy0, int cx0, int ch, int cw, int y0, int x0, int h, int w, void* out,
+                     int out_u8, int32_t* status, void* stream) {
+  RefreshArgs a;
+  BlendArgs& b = a.b;
+  if (int rc = tile_geometry("vam_tile_refresh", H, W, th, tw, V, &b.g)) return rc;
+  VAM_REQUIRE(tiles && slot && dirty && out && status, "vam_tile_refresh: need tiles, slot, dirty, out and status");
+  VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_refresh: an overlap of %d needs the two ramp tables", V);
+  VAM_REQUIRE(n >= 1, "vam_tile_refresh: a buffer of %d tiles", n);
+  VAM_REQUIRE(cy0 >= 0 && cx0 >= 0 && ch >= 1 && cw >= 1 && ch <= H - cy0 && cw <= W - cx0,
+              "vam_tile_refresh: the canvas window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", cy0, cx0, ch,
+              cw, H, W);
+  VAM_REQUIRE(y0 >= cy0 && x0 >= cx0 && h >= 1 && w >= 1 && h <= cy0 + ch - y0 && w <= cx0 + cw - x0,
+              "vam_tile_refresh: the box (y0 %d, x0 %d, h %d, w %d) does not lie inside the canvas window (y0 %d, x0 %d, h %d, w %d)",
+              y0, x0, h, w, cy0, cx0, ch, cw);
+  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_refresh: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
+  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_refresh: a box of %d rows exceeds one launch", h);
+  b.tiles = tiles; b.slot = slot; b.w_lo = w_lo; b.w_hi = w_hi; b.status = status;
+  b.out_f = out_u8 ? nullptr : (float*)out;
+  b.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
+  b.n = n; b.y0 = y0; b.x0 = x0; b.h = h; b.w = w;
+  a.dirty = dirty; a.cy0 = cy0; a.cx0 = cx0; a.ch = ch; a.cw = cw;
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
+  hipLaunchKernelGGL(tile_refresh_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("tile_refresh_kernel");
 }
 
 }  // extern "C"

@@ -471,6 +471,46 @@ def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int =
     return rows
 
 
+def tiled_stream_rd(model, image: torch.Tensor, cuts: Optional[Sequence[int]] = None, window=None, tile: int = 256, overlap: int = 32,
+                    marks: Optional[Sequence[float]] = None, coder=None, lanes: int = 1, base_lanes: int = 1,
+                    group: Optional[int] = None, allocation: str = "tile", schedule=None, cache_tiles: Optional[int] = None):
+    """Rate and distortion of ONE picture codestream as a receiver sees it arrive (tiled.PictureStream):
+    the picture is coded once (``tiled.encode`` with the encode options given), then ONE ``PictureStream`` is fed up to each
+    byte position of ``cuts`` (ascending, from ``need_bytes`` on; None: ``need_bytes`` and every ``round_end``) and
+    ``view(window)`` is taken after each feed.  One dict per cut: bytes, bpp (8 * bytes / (H W)), psnr of the view against
+    the same window of the picture, ``tiles`` (the tiles of the window) and ``decoded`` (those that ran the network for this
+    cut: the tiles whose own bytes grew since the cut before), and dec_s (the feed and the view).  ``cache_tiles`` defaults to
+    the tiles of the window."""
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    rows = []
+    with torch.no_grad():
+        data = TL.encode(model, x, tile=tile, overlap=overlap, marks=marks, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group,
+                         allocation=allocation, schedule=schedule)
+        lay = TL.layout(data)
+        cuts = sorted({lay["need_bytes"], *lay["round_end"]}) if cuts is None else [int(n) for n in cuts]
+        if any(b < a for a, b in zip(cuts, cuts[1:])) or (cuts and not lay["need_bytes"] <= cuts[0]) or (cuts and cuts[-1] > len(data)):
+            raise ValueError(f"tiled_stream_rd: cuts are ascending byte positions in {lay['need_bytes']} (need_bytes) .. {len(data)}, "
+                             f"got {cuts}")
+        y0, x0, h, w = TL._window(lay, window, "tiled_stream_rd")
+        want = x[:, :, y0:y0 + h, x0:x0 + w]
+        n_tiles = len(TL.tiles_for(lay, (y0, x0, h, w)))
+        stream = TL.PictureStream(model, coder=coder, group=group, cache_tiles=max(n_tiles, 1) if cache_tiles is None else cache_tiles)
+        at = 0
+        for n in cuts:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stream.feed(data[at:n])
+            x_hat = stream.view((y0, x0, h, w))
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            at = n
+            rows.append({"bytes": n, "bpp": 8.0 * n / (H * W), "psnr": compute_psnr(want, x_hat.unsqueeze(0)),
+                         "decoded": len(stream.last_decoded), "tiles": len(stream.last_tiles), "dec_s": t1 - t0})
+    return rows
+
+
 def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
                        base_lanes: int = 1):
     """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE

@@ -855,6 +855,35 @@ def tile_blend(tiles: torch.Tensor, slot: torch.Tensor, w_lo: Optional[torch.Ten
     L.check(rc, "vam_tile_blend")
 
 
+def tile_refresh(tiles: torch.Tensor, slot: torch.Tensor, dirty: torch.Tensor, w_lo: Optional[torch.Tensor], w_hi: Optional[torch.Tensor],
+                 H: int, W: int, overlap: int, window: Sequence[int], box: Sequence[int], out: torch.Tensor, status: torch.Tensor):
+    """:func:`tile_blend` restricted to what changed: ``out`` is a persistent canvas of ``window`` =
+    (cy0, cx0, ch, cw), fp32 [3, ch, cw] or uint8 [ch, cw, 3]; ``dirty`` int32 [R, C] marks tiles, ``box`` = (y0, x0, h, w) in
+    picture coordinates is the part of the window to visit.  A pixel of the box with a dirty tile gets tile_blend's value, bit
+    for bit (all its tiles must be present, else ``status`` becomes 1); any other pixel is not written, and the slots of its
+    tiles are not read.  One launch; capturable."""
+    cy0, cx0, ch, cw = (int(v) for v in window)
+    y0, x0, h, w = (int(v) for v in box)
+    assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.is_cuda
+    n, _, th, tw = tiles.shape
+    for t in (slot, dirty):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.device == tiles.device
+    assert slot.shape == dirty.shape
+    if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):       # the grid the library derives; anything else it refuses
+        grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
+        assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
+    for t in (w_lo, w_hi):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == tiles.device)
+    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == tiles.device
+    assert out.is_contiguous() and out.device == tiles.device
+    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, ch, cw)) or (out.dtype == torch.uint8 and tuple(out.shape) == (ch, cw, 3)), \
+        (out.dtype, tuple(out.shape), (ch, cw))
+    rc = L.load().vam_tile_refresh(tiles.data_ptr(), n, slot.data_ptr(), dirty.data_ptr(), w_lo.data_ptr() if w_lo is not None else None,
+                                   w_hi.data_ptr() if w_hi is not None else None, int(H), int(W), th, tw, int(overlap), cy0, cx0, ch, cw,
+                                   y0, x0, h, w, out.data_ptr(), int(out.dtype == torch.uint8), status.data_ptr(), stream_ptr())
+    L.check(rc, "vam_tile_refresh")
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

@@ -21,8 +21,7 @@ stream down to a window and a number of rounds on the host alone, and what it re
 :func:`encode` and :class:`PictureDecoder` run the tiles, a group at a time, through ``embedded.encode_batch`` and
 ``embedded.EmbeddedDecoder`` unchanged: an image codes and decodes bit for bit the same alone or in a batch, so neither the
 bytes nor the pixels depend on the grouping.  By default (``allocation="tile"``) quality q keeps a quantile PER TILE: a
-tiled picture at q is not the untiled forward at q.  Out of scope: incremental feeding and a tile cache across ``decode``
-calls.
+tiled picture at q is not the untiled forward at q.
 
 Picture-wide marks: ``encode(..., allocation="picture")`` takes, per mark and slice, ONE sigma threshold
 over the pool of all tiles' sigmas (``torch.quantile`` of the pool, bit for bit; ``csrc/pooled_select.hip``) and marks every
@@ -39,8 +38,16 @@ scheduled embedded codestream of L stages (``embedded.encode_batch(schedule=)``)
 Such a stream has a version-3 header: the version-1 fields and table, then u16 kind (1: scheduled), u16 n_stages, u32
 reserved (0), then the u64 total, under the same CRC; its rounds are stages: ``data[:round_end[k]]`` and
 ``extract(data, rounds=k + 1)`` hold every tile exactly at stage k, and ``PictureDecoder.decode(stage=k)`` is the blend of
-``forward_quality_map(tile, S_tile[k])``.  Out of scope: a schedule together with ``allocation="picture"``, reassembling the
-picture-level schedule at the receiver, incremental feeding and a tile cache.
+``forward_quality_map(tile, S_tile[k])``.  Out of scope: a schedule together with ``allocation="picture"`` and reassembling
+the picture-level schedule at the receiver.
+
+The receiver: :class:`PictureStream` is fed the bytes as they arrive, in chunks that end anywhere
+(:class:`PictureFeed`, the byte bookkeeping, needs neither a model nor a GPU), and keeps decoded tiles in a device pool across
+calls: ``view(window, q | mark | stage)`` equals a fresh ``PictureDecoder(everything fed so far).decode(...)`` bit for bit
+and runs through the network only the tiles of the window whose own bytes grew since they were decoded, or that were never
+decoded at that level.  A :class:`Canvas` is a persistent output that ``refresh()`` re-blends only where such tiles
+contribute (vam_tile_refresh).  Out of scope: per-tile entropy resumption (a resumable ``EmbeddedDecoder`` kept per tile
+group), decoding tiles before all heads have arrived, and a priority order for stale tiles.
 """
 from __future__ import annotations
 
@@ -656,6 +663,112 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     return pack(H, W, tile, overlap, streams, thresholds=thr)
 
 
+def _ramps_on(have, V: int, device):
+    """The blend ramps of overlap V as tensors on ``device``; ``have``: what an earlier call returned, or None."""
+    import torch
+    if have is None or have[0].device != device:
+        have = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ramps(V))
+    return have
+
+
+def _check_pooled(model, thresholds, dec, containers, part):
+    """A version-2 header's thresholds against the tiles' marks: the decoder's OWN sigma, in its own rank order
+    (vam_pool_keys), counted against the header's thresholds (vam_threshold_counts), must give the counts the tiles'
+    marks state, for every mark."""
+    import torch
+    from . import ops
+    dp, ns = dec.dp, model.ns0
+    thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+    with torch.no_grad():
+        dec._own()
+        with dp.runner.on_stream():
+            keys = torch.empty((dp.B, ns, dp.perm.shape[2]), dtype=torch.int32, device=dp.device)
+            count = torch.empty((thr.shape[0], dp.B, ns), dtype=torch.int32, device=dp.device)
+            ops.pool_keys(dp.sc.std_p, dp.perm, keys, t0=0, n_slice=ns)
+            ops.threshold_counts(keys, torch.from_numpy(thr).to(dp.device), count)
+            got = count.cpu().numpy()
+    want = np.stack([np.asarray(c["marks"]["count"], dtype=np.int64).reshape(-1, ns) for c in containers], axis=1)
+    bad = np.argwhere(got != want) if got.shape == want.shape else np.zeros((1, 3), dtype=np.int64)
+    if len(bad):
+        k, b, j = (int(v) for v in bad[0])
+        raise ValueError(f"tile {part[b] if part is not None else b}, mark {k}, slice {j}: the header's picture-wide threshold "
+                         f"{thr[k, j]} keeps {int(got[k, b, j])} elements of this tile's sigma, the tile's mark states "
+                         f"{int(want[k, b, j])}: thresholds and tiles are not of one picture")
+
+
+def _decode_tiles(model, coder, thresholds, containers, q, mark=None, part=None, stage=None):
+    """x_hat of one group of tile containers through a fresh ``embedded.EmbeddedDecoder``: from everything they hold, at a
+    quality, at a mark (checked against ``thresholds`` when the picture carries them) or at a stage."""
+    dec = EB.EmbeddedDecoder(model, containers, coder=coder)
+    if stage is not None:
+        return dec.decode_stages([stage])[0]["x_hat"]
+    if mark is None:
+        return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
+    x_hat = dec.decode_marks([mark])[0]["x_hat"]
+    if thresholds is not None:
+        _check_pooled(model, thresholds, dec, containers, part)
+    return x_hat
+
+
+def _mark_of(what: str, marks, thresholds, q, mark) -> Optional[int]:
+    """The mark a decode call means: ``mark`` itself, or, on a version-2 stream, the mark whose quality ``q`` is."""
+    if mark is not None:
+        if q is not None:
+            raise ValueError(f"{what}: give q or mark, not both")
+        mark = _int(mark, f"{what}: mark")
+        if not 0 <= mark < len(marks):
+            raise ValueError(f"{what}: mark is 0 .. {len(marks) - 1} (the marks {marks}), got {mark}")
+        return mark
+    if q is None or thresholds is None:
+        return None
+    if float(q) not in marks:
+        raise ValueError(f"{what}: quality {q} is not marked; this picture's marks are picture-wide (allocation "
+                         f"'picture') and a picture-wide quality exists only where the encoder pooled: the marks are {marks}")
+    return marks.index(float(q))
+
+
+def _stage_of(what: str, scheduled: bool, stages: int, q, mark, stage) -> Optional[int]:
+    """The stage a decode call means, checked against what the picture is."""
+    if stage is None:
+        if q is not None and scheduled:
+            raise ValueError(f"{what}: this picture is scheduled ({stages} stages): a uniform quality is no "
+                             f"prefix of a scheduled rank order, decode a stage with stage=0 .. {stages - 1}")
+        return None
+    if q is not None or mark is not None:
+        raise ValueError(f"{what}: give stage alone, not with q or mark")
+    if not scheduled:
+        raise ValueError(f"{what}: stage= decodes a scheduled picture (tiled.encode(schedule=)); this picture "
+                         "carries no schedule, decode a quality with q or a mark with mark")
+    stage = _int(stage, f"{what}: stage")
+    if not 0 <= stage < stages:
+        raise ValueError(f"{what}: stage is 0 .. {stages - 1}, got {stage}")
+    return stage
+
+
+def _decode_window(what: str, model, coder, thresholds, tiles, stream_of, group: int, g: dict, q, mark, stage):
+    """fp32 [len(tiles), 3, th, tw] on the model's device: the tiles (r, c) of ``tiles``, ``group`` at a time through
+    :func:`_decode_tiles`; ``stream_of(r, c)`` gives a tile's bytes.  When a group is refused its tiles are tried alone, and
+    the ValueError names the one that is."""
+    import torch
+    buf = None
+    for i0 in range(0, len(tiles), group):
+        part = tiles[i0:i0 + group]
+        cs = [EB.from_bytes(stream_of(r, c)) for r, c in part]
+        try:
+            x_hat = _decode_tiles(model, coder, thresholds, cs, q, mark, part, stage)
+        except ValueError:
+            for rc, c1 in zip(part, cs):            # a tile decodes alone as in its group: find the one that is refused
+                try:
+                    _decode_tiles(model, coder, thresholds, [c1], q, mark, [rc], stage)
+                except ValueError as e:
+                    raise ValueError(f"{what}: tile {rc}: {e}") from e
+            raise
+        if buf is None:
+            buf = torch.empty((len(tiles), 3, g["th"], g["tw"]), dtype=torch.float32, device=x_hat.device)
+        buf[i0:i0 + len(part)].copy_(x_hat)
+    return buf
+
+
 class PictureDecoder:
     """Decodes a picture codestream by window.  ``data``: any prefix of at least :func:`need_bytes`, or an :func:`extract`.
     ``shape``: the true (H, W); ``grid``: the geometry; ``rounds``: int [R, C], the complete rounds ``data`` holds of every
@@ -681,81 +794,6 @@ class PictureDecoder:
         self.last_tiles: List[Tuple[int, int]] = []
         self._ramps = None
 
-    def _blend_inputs(self, device):
-        import torch
-        if self._ramps is None or self._ramps[0].device != device:
-            self._ramps = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ramps(self.grid["V"]))
-        return self._ramps
-
-    def _decode_tiles(self, containers, q, mark=None, part=None, stage=None):
-        dec = EB.EmbeddedDecoder(self.m, containers, coder=self.coder)
-        if stage is not None:
-            return dec.decode_stages([stage])[0]["x_hat"]
-        if mark is None:
-            return (dec.decode() if q is None else dec.decode_qualities([q])[0])["x_hat"]
-        x_hat = dec.decode_marks([mark])[0]["x_hat"]
-        if self._s.thresholds is not None:
-            self._check_pooled(dec, containers, part)
-        return x_hat
-
-    def _check_pooled(self, dec, containers, part):
-        """A version-2 header's thresholds against the tiles' marks: the decoder's OWN sigma, in its own rank order
-        (vam_pool_keys), counted against the header's thresholds (vam_threshold_counts), must give the counts the tiles'
-        marks state, for every mark."""
-        import torch
-        from . import ops
-        dp, ns = dec.dp, self.m.ns0
-        thr = np.ascontiguousarray(self._s.thresholds, dtype=np.float32)
-        with torch.no_grad():
-            dec._own()
-            with dp.runner.on_stream():
-                keys = torch.empty((dp.B, ns, dp.perm.shape[2]), dtype=torch.int32, device=dp.device)
-                count = torch.empty((thr.shape[0], dp.B, ns), dtype=torch.int32, device=dp.device)
-                ops.pool_keys(dp.sc.std_p, dp.perm, keys, t0=0, n_slice=ns)
-                ops.threshold_counts(keys, torch.from_numpy(thr).to(dp.device), count)
-                got = count.cpu().numpy()
-        want = np.stack([np.asarray(c["marks"]["count"], dtype=np.int64).reshape(-1, ns) for c in containers], axis=1)
-        bad = np.argwhere(got != want) if got.shape == want.shape else np.zeros((1, 3), dtype=np.int64)
-        if len(bad):
-            k, b, j = (int(v) for v in bad[0])
-            raise ValueError(f"tile {part[b] if part is not None else b}, mark {k}, slice {j}: the header's picture-wide threshold "
-                             f"{thr[k, j]} keeps {int(got[k, b, j])} elements of this tile's sigma, the tile's mark states "
-                             f"{int(want[k, b, j])}: thresholds and tiles are not of one picture")
-
-    def _mark_of(self, q, mark) -> Optional[int]:
-        """The mark a ``decode`` call means: ``mark`` itself, or, on a version-2 stream, the mark whose quality ``q`` is."""
-        marks = self.meta["marks"]
-        if mark is not None:
-            if q is not None:
-                raise ValueError("PictureDecoder.decode: give q or mark, not both")
-            mark = _int(mark, "PictureDecoder.decode: mark")
-            if not 0 <= mark < len(marks):
-                raise ValueError(f"PictureDecoder.decode: mark is 0 .. {len(marks) - 1} (the marks {marks}), got {mark}")
-            return mark
-        if q is None or self._s.thresholds is None:
-            return None
-        if float(q) not in marks:
-            raise ValueError(f"PictureDecoder.decode: quality {q} is not marked; this picture's marks are picture-wide (allocation "
-                             f"'picture') and a picture-wide quality exists only where the encoder pooled: the marks are {marks}")
-        return marks.index(float(q))
-
-    def _stage_of(self, q, mark, stage) -> Optional[int]:
-        """The stage a ``decode`` call means, checked against what this picture is."""
-        if stage is None:
-            if q is not None and self.scheduled:
-                raise ValueError(f"PictureDecoder.decode: this picture is scheduled ({self.stages} stages): a uniform quality is no "
-                                 f"prefix of a scheduled rank order, decode a stage with stage=0 .. {self.stages - 1}")
-            return None
-        if q is not None or mark is not None:
-            raise ValueError("PictureDecoder.decode: give stage alone, not with q or mark")
-        if not self.scheduled:
-            raise ValueError("PictureDecoder.decode: stage= decodes a scheduled picture (tiled.encode(schedule=)); this picture "
-                             "carries no schedule, decode a quality with q or a mark with mark")
-        stage = _int(stage, "PictureDecoder.decode: stage")
-        if not 0 <= stage < self.stages:
-            raise ValueError(f"PictureDecoder.decode: stage is 0 .. {self.stages - 1}, got {stage}")
-        return stage
-
     def decode(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
         """The window (y0, x0, h, w) of the picture (None: all of it): fp32 [3, h, w], or uint8 [h, w, 3] for
         ``dtype=torch.uint8`` (round half to even of clamp(v, 0, 1) * 255, as evaluate.write_image).  ``q`` = None: from
@@ -780,36 +818,22 @@ class PictureDecoder:
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
-        stage = self._stage_of(q, mark, stage)
-        mark = self._mark_of(q, mark)
+        stage = _stage_of("PictureDecoder.decode", self.scheduled, self.stages, q, mark, stage)
+        mark = _mark_of("PictureDecoder.decode", self.meta["marks"], s.thresholds, q, mark)
         y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
         tiles = tiles_for(g, (y0, x0, h, w))
         for r, c in tiles:
             if not s.present[r * g["C"] + c]:
                 raise ValueError(f"PictureDecoder.decode: the window ({y0}, {x0}, {h}, {w}) needs tile ({r}, {c}), which is absent "
                                  "from this codestream")
-        buf = None
         with torch.no_grad():
-            for i0 in range(0, len(tiles), self.group):
-                part = tiles[i0:i0 + self.group]
-                cs = [EB.from_bytes(s.stream(self._d, r * g["C"] + c)) for r, c in part]
-                try:
-                    x_hat = self._decode_tiles(cs, q, mark, part, stage)
-                except ValueError:
-                    for rc, c1 in zip(part, cs):            # a tile decodes alone as in its group: find the one that is refused
-                        try:
-                            self._decode_tiles([c1], q, mark, [rc], stage)
-                        except ValueError as e:
-                            raise ValueError(f"PictureDecoder.decode: tile {rc}: {e}") from e
-                    raise
-                if buf is None:
-                    buf = torch.empty((len(tiles), 3, g["th"], g["tw"]), dtype=torch.float32, device=x_hat.device)
-                buf[i0:i0 + len(part)].copy_(x_hat)
+            buf = _decode_window("PictureDecoder.decode", self.m, self.coder, s.thresholds, tiles,
+                                 lambda r, c: s.stream(self._d, r * g["C"] + c), self.group, g, q, mark, stage)
             dev = buf.device
             slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
             for i, (r, c) in enumerate(tiles):
                 slot[r, c] = i
-            w_lo, w_hi = self._blend_inputs(dev)
+            self._ramps = w_lo, w_hi = _ramps_on(self._ramps, g["V"], dev)
             status = torch.zeros((1,), dtype=torch.int32, device=dev)
             out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
                 else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
@@ -819,3 +843,346 @@ class PictureDecoder:
                 raise L.VamError("PictureDecoder.decode: vam_tile_blend met an absent tile inside the window")
         self.last_tiles = tiles
         return out
+
+
+# ------------------------------------------------------------------------------------- the receiver
+class PictureFeed:
+    """The byte bookkeeping of a receiver: a picture codestream, whole or an :func:`extract`, of any
+    header version, arriving in chunks that may end anywhere.  Host arithmetic only: it needs no model and no GPU.
+    :class:`PictureStream` owns one and adds the decoder.
+
+    ``ready``: whether the bytes reach :func:`need_bytes` (every present tile's head).  ``need()``: the bytes still missing
+    before that, as far as the bytes tell.  Once the header is complete (it is parsed once, by the parser of
+    :func:`layout`): ``shape``, ``grid``, ``scheduled``, ``stages``; ``meta``: the tiles' own layout as far as heads are
+    whole (``PictureDecoder.meta`` once ready); and once ready ``rounds`` (``PictureDecoder.rounds``) and ``held`` int [R, C],
+    the bytes present of each tile's own codestream, -1 where the tile is absent.  ``fed_tiles``: the (r, c), in raster
+    order, whose held bytes grew in the last feed.  ``data``: everything fed so far."""
+
+    def __init__(self, what: str = "PictureFeed"):
+        self._what = what
+        self._buf = bytearray()
+        self._s: Optional[_Picture] = None
+        self._heads = 0                                     # the whole heads that were checked against the table
+        self._per_tile = None                               # int64 [R C]: bytes of every tile's stream, absent tiles 0
+        self.meta: Optional[dict] = None
+        self.fed_tiles: List[Tuple[int, int]] = []
+
+    @property
+    def data(self) -> bytes:
+        return bytes(self._buf)
+
+    def __len__(self) -> int:
+        return len(self._buf)
+
+    @property
+    def ready(self) -> bool:
+        return self._s is not None and len(self._buf) >= self._s.need
+
+    def need(self) -> int:
+        if self._s is not None:
+            return max(0, self._s.need - len(self._buf))
+        end = _header_end(self._buf, self._what) if len(self._buf) >= PREAMBLE_BYTES else None
+        return (PREAMBLE_BYTES if end is None else end) - len(self._buf)
+
+    def _header(self, name: str):
+        if self._s is None:
+            raise ValueError(f"{self._what}.{name}: the header is not complete yet: {self.need()} bytes are missing")
+        return self._s
+
+    @property
+    def grid(self) -> dict:
+        return dict(self._header("grid").g)
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        g = self._header("shape").g
+        return g["H"], g["W"]
+
+    @property
+    def stages(self) -> int:
+        return self._header("stages").stages
+
+    @property
+    def scheduled(self) -> bool:
+        return self._header("scheduled").stages > 0
+
+    @property
+    def held(self) -> Optional[np.ndarray]:
+        if not self.ready:
+            return None
+        s = self._s
+        return np.where(s.present, self._per_tile, -1).reshape(s.g["R"], s.g["C"])
+
+    @property
+    def rounds(self) -> Optional[np.ndarray]:
+        if not self.ready:
+            return None
+        s = self._s
+        whole = (s.held(len(self._buf))[1:] == s.size[1:])                       # as PictureDecoder: a piece of 0 bytes is whole
+        done = np.cumprod(whole, axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
+        return np.where(s.present, done, -1).astype(np.int64).reshape(s.g["R"], s.g["C"])
+
+    def tile_bytes(self, r: int, c: int) -> bytes:
+        """Tile (r, c)'s embedded codestream as far as the fed bytes hold it (:func:`tile_stream`)."""
+        s = self._header("tile_bytes")
+        return s.stream(self._buf, s.index(r, c, f"{self._what}.tile_bytes"))
+
+    def feed(self, chunk) -> Optional[np.ndarray]:
+        """``chunk``: the bytes that follow what was fed before, ``b""`` allowed.  Returns ``rounds`` once ready, else None.
+        The feed is checked as a whole before anything is kept: a damaged or contradicting header, a tile head that
+        contradicts the table or the other tiles, bytes beyond the header's total and a non-bytes argument are ValueErrors
+        that leave the receiver as it was."""
+        what = f"{self._what}.feed"
+        if not isinstance(chunk, (bytes, bytearray, memoryview)):
+            raise ValueError(f"{what}: expected bytes, got {type(chunk).__name__}")
+        chunk = bytes(EB._view(chunk, what))
+        s, heads, meta, n = self._s, self._heads, self.meta, len(self._buf) + len(chunk)
+        if s is None or heads < int(s.present.sum()):                             # the header or a head may complete: look at the bytes
+            d = memoryview(bytes(self._buf) + chunk)
+            if s is None:
+                end = _header_end(d, what)
+                if end is not None and n >= end:
+                    s = _Picture(d, what)
+            if s is not None:
+                whole = int((s.present & (s.off[0] + s.size[0] <= n)).sum())
+                if whole != heads:
+                    meta, heads = _tile_meta(d, s, what), whole
+        if s is not None and n > s.total:
+            raise ValueError(f"{what}: {n} bytes, the header states a total of {s.total}: {n - s.total} bytes follow the codestream")
+        self._buf += chunk
+        self._s, self._heads, self.meta = s, heads, meta
+        self.fed_tiles = []
+        if s is not None:
+            per_tile = s.held(n).sum(0)
+            before = self._per_tile if self._per_tile is not None else np.zeros_like(per_tile)
+            self.fed_tiles = [s.rc(int(i)) for i in np.flatnonzero(per_tile > before)]
+            self._per_tile = per_tile
+        return self.rounds
+
+
+class PictureStream:
+    """A receiver of one picture codestream that is fed bytes and caches decoded tiles.
+
+    :meth:`feed` takes the bytes that follow what was fed before (:class:`PictureFeed`, which it owns as ``feed_state``; its
+    attributes ``ready``, ``need()``, ``shape``, ``grid``, ``scheduled``, ``stages``, ``meta``, ``rounds``, ``held`` and
+    ``fed_tiles`` are this object's, too).  After any sequence of feeds and views, ``view(window, q, mark, stage, dtype)``
+    equals, bit for bit, ``PictureDecoder(model, everything fed so far, coder, group).decode(window, q, mark, stage, dtype)``
+    and raises that call's ValueErrors, but it runs through the network only the tiles it has not cached: an image decodes
+    bit for bit the same alone or in a batch (DESIGN sections 9r, 9v), so a tile decoded earlier, in another group, holds
+    the pixels a fresh decode would give.
+
+    The cache is a device pool fp32 [cache_tiles, 3, th, tw], allocated at the first view on the model's device: 12 th tw
+    bytes per tile.  Default ``cache_tiles``: the most tiles a 1024 x 1024 window can meet at the stream's geometry, at least
+    ``group``; at 256 x 256 tiles with overlap 32 that is 36 tiles, 27 MiB.  An entry is (tile, key, generation).  With q, mark
+    and stage all None the key is ("held", the bytes held of that tile): the tile is stale exactly when its own bytes grew,
+    and a round piece of 0 bytes leaves it fresh.  With a level the key is ("q", q), ("mark", k) or ("stage", k): a tile's
+    pixels at a level do not depend on later bytes, so such an entry never goes stale.  Keys of one tile coexist.  Eviction
+    is least recently used and never takes a tile of the current call; a window of more tiles than ``cache_tiles`` is a
+    ValueError before any GPU work.  A decode that raises leaves the cache as it was.  ``last_tiles``: the tiles of the last
+    view's window; ``last_decoded``: those that ran the network; ``decoded_total``: the running count.  :meth:`drop` empties
+    the cache."""
+
+    def __init__(self, model, coder: Optional[str] = None, group: Optional[int] = None, cache_tiles: Optional[int] = None):
+        from . import progressive as P
+        EB._check_model(model)
+        self.m, self.coder = model, P._check_coder(model, coder)
+        self._group_arg = None if group is None else _check_group(group, 64, 64, "PictureStream")
+        if cache_tiles is not None:
+            cache_tiles = _int(cache_tiles, "PictureStream: cache_tiles")
+            if cache_tiles < 1:
+                raise ValueError(f"PictureStream: cache_tiles is the tiles the cache holds, >= 1, got {cache_tiles}")
+        self._cache_arg = cache_tiles
+        self.feed_state = PictureFeed("PictureStream")
+        self.group: Optional[int] = None
+        self.cache_tiles: Optional[int] = None
+        self.last_tiles: List[Tuple[int, int]] = []
+        self.last_decoded: List[Tuple[int, int]] = []
+        self.decoded_total = 0
+        self._pool = None
+        self._ramps = None
+        self._entries = {}                                  # (tile index, key) -> [slot, generation], least recently used first
+        self._free: List[int] = []
+        self._held_key = {}                                 # tile index -> the ("held", n) key it is cached under
+        self._generation = 0
+
+    # ------------------------------------------------------------------------------------------------------ the bytes
+    ready = property(lambda self: self.feed_state.ready)
+    shape = property(lambda self: self.feed_state.shape)
+    grid = property(lambda self: self.feed_state.grid)
+    scheduled = property(lambda self: self.feed_state.scheduled)
+    stages = property(lambda self: self.feed_state.stages)
+    meta = property(lambda self: self.feed_state.meta)
+    rounds = property(lambda self: self.feed_state.rounds)
+    held = property(lambda self: self.feed_state.held)
+    fed_tiles = property(lambda self: self.feed_state.fed_tiles)
+    data = property(lambda self: self.feed_state.data)
+
+    def need(self) -> int:
+        return self.feed_state.need()
+
+    def feed(self, chunk) -> Optional[np.ndarray]:
+        """:meth:`PictureFeed.feed`: host arithmetic only, it touches no GPU and no cache entry (a stale tile is found by
+        its key at the next view)."""
+        out = self.feed_state.feed(chunk)
+        if self.group is None and self.feed_state._s is not None:
+            g = self.feed_state._s.g
+            self.group = self._group_arg if self._group_arg is not None else _default_group(g["th"], g["tw"])
+            span = lambda n, t, S, N: min(N, (min(1024, n) + t - 2) // S + 1)     # the most tiles a span of 1024 meets along an axis
+            self.cache_tiles = self._cache_arg if self._cache_arg is not None else \
+                max(self.group, span(g["H"], g["th"], g["Sy"], g["R"]) * span(g["W"], g["tw"], g["Sx"], g["C"]))
+        return out
+
+    # ------------------------------------------------------------------------------------------------------ the cache
+    def drop(self):
+        """Empties the cache; the pool stays allocated."""
+        self._entries, self._held_key = {}, {}
+        self._free = list(range(self.cache_tiles)) if self._pool is not None else []
+
+    def _update(self, what: str, window, q, mark, stage):
+        """Brings the tiles of ``window`` into the cache at the level (q, mark, stage).  Returns (window, its tiles, the level
+        key or None, slot int32 [R, C], generation int64 [R, C]); both tables are -1 outside the window's tiles."""
+        import torch
+        fs = self.feed_state
+        if not fs.ready:
+            raise ValueError(f"{what}: nothing to decode yet: {fs.need()} bytes are missing before every tile's head is whole")
+        s, g = fs._s, fs._s.g
+        stage = _stage_of(what, s.stages > 0, s.stages, q, mark, stage)
+        mark = _mark_of(what, fs.meta["marks"], s.thresholds, q, mark)
+        y0, x0, h, w = _window(g, window, what)
+        tiles = tiles_for(g, (y0, x0, h, w))
+        for r, c in tiles:
+            if not s.present[r * g["C"] + c]:
+                raise ValueError(f"{what}: the window ({y0}, {x0}, {h}, {w}) needs tile ({r}, {c}), which is absent "
+                                 "from this codestream")
+        if len(tiles) > self.cache_tiles:
+            raise ValueError(f"{what}: the window ({y0}, {x0}, {h}, {w}) needs {len(tiles)} tiles, the cache holds {self.cache_tiles}: "
+                             "give PictureStream a larger cache_tiles or view a smaller window")
+        level = ("stage", stage) if stage is not None else ("mark", mark) if mark is not None else ("q", float(q)) if q is not None \
+            else None
+        index = [r * g["C"] + c for r, c in tiles]
+        keys = [(i, level if level is not None else ("held", int(fs._per_tile[i]))) for i in index]
+        missing = [(rc, k) for rc, k in zip(tiles, keys) if k not in self._entries]
+        if missing:
+            part = [rc for rc, _ in missing]
+            with torch.no_grad():                           # everything is decoded before the cache changes
+                fresh = _decode_window(what, self.m, self.coder, s.thresholds, part, fs.tile_bytes, self.group, g, q, mark, stage)
+                if self._pool is None:
+                    self._pool = torch.empty((self.cache_tiles, 3, g["th"], g["tw"]), dtype=torch.float32, device=fresh.device)
+                    self._free = list(range(self.cache_tiles))
+                slots = []
+                for _, k in missing:
+                    if level is None and self._held_key.get(k[0]) in self._entries:       # the tile's bytes grew: its entry is stale
+                        self._free.append(self._entries.pop(self._held_key[k[0]])[0])
+                    if not self._free:
+                        now = set(keys)
+                        old = next(e for e in self._entries if e not in now)              # the least recently used, never a tile of this call
+                        if self._held_key.get(old[0]) == old:
+                            del self._held_key[old[0]]
+                        self._free.append(self._entries.pop(old)[0])
+                    self._generation += 1
+                    slots.append(self._free.pop())
+                    self._entries[k] = [slots[-1], self._generation]
+                    if level is None:
+                        self._held_key[k[0]] = k
+                self._pool.index_copy_(0, torch.tensor(slots, dtype=torch.int64, device=fresh.device), fresh)
+        slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
+        gen = np.full((g["R"], g["C"]), -1, dtype=np.int64)
+        for (r, c), k in zip(tiles, keys):
+            e = self._entries.pop(k)
+            self._entries[k] = e                            # the most recently used last
+            slot[r, c], gen[r, c] = e
+        self.last_tiles, self.last_decoded = tiles, [rc for rc, _ in missing]
+        self.decoded_total += len(missing)
+        return (y0, x0, h, w), tiles, level, slot, gen
+
+    def _blend_inputs(self):
+        g = self.feed_state._s.g
+        self._ramps = _ramps_on(self._ramps, g["V"], self._pool.device)
+        return self._ramps if g["V"] else (None, None)
+
+    def view(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
+        """``PictureDecoder(model, everything fed so far).decode(window, q, mark, stage, dtype)``, bit for bit, with its
+        ValueErrors under the prefix ``PictureStream.view:``; only the tiles of the window that are not cached at that level
+        run the network (``last_decoded``).  Before ``ready`` a ValueError states ``need()``."""
+        import torch
+        from . import _lib as L
+        from . import ops
+        what = "PictureStream.view"
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        (y0, x0, h, w), _, _, slot, _ = self._update(what, window, q, mark, stage)
+        g, dev = self.feed_state._s.g, self._pool.device
+        with torch.no_grad():
+            w_lo, w_hi = self._blend_inputs()
+            status = torch.zeros((1,), dtype=torch.int32, device=dev)
+            out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
+                else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+            ops.tile_blend(self._pool, torch.from_numpy(slot).to(dev), w_lo, w_hi, g["H"], g["W"], g["V"], (y0, x0, h, w), out, status)
+            if int(status.item()):
+                raise L.VamError(f"{what}: vam_tile_blend met an absent tile inside the window")
+        return out
+
+    def canvas(self, window=None, dtype=None) -> "Canvas":
+        """A persistent output of ``window`` (None: the picture) that :meth:`Canvas.refresh` keeps equal to :meth:`view`."""
+        return Canvas(self, window, dtype)
+
+
+class Canvas:
+    """A persistent output tensor of one window of a :class:`PictureStream`: ``out`` is fp32 [3, h, w], or
+    uint8 [h, w, 3] for ``dtype=torch.uint8``, on the model's device.  Per tile of the grid it remembers the generation of the
+    cache entry it last blended from, and the level (q, mark or stage) of its last :meth:`refresh`."""
+
+    def __init__(self, stream: PictureStream, window=None, dtype=None):
+        import torch
+        what = "PictureStream.canvas"
+        fs = stream.feed_state
+        if fs._s is None:
+            raise ValueError(f"{what}: the header is not complete yet: {fs.need()} bytes are missing")
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        g = fs._s.g
+        self.stream, self.window, self.dtype = stream, _window(g, window, what), dtype
+        dev, (_, _, h, w) = next(stream.m.parameters()).device, self.window
+        self.out = torch.zeros((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
+            else torch.zeros((h, w, 3), dtype=torch.uint8, device=dev)
+        self._gen = np.full((g["R"], g["C"]), -1, dtype=np.int64)
+        self._level = None
+
+    def refresh(self, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None):
+        """Brings the window's tiles up to date through the cache, as :meth:`PictureStream.view` does, and re-blends, with one
+        vam_tile_refresh launch, only the pixels that a dirty tile contributes to: a tile is dirty when its cache entry is
+        not the one this canvas last blended from, and every tile of the window is when the level changed.  Returns the box
+        (y0, x0, h, w), in picture coordinates, that was visited: the bounding box of the dirty tiles' extents inside the
+        window; None when nothing was dirty, and then nothing is launched.  Afterwards ``out`` equals
+        ``view(window, q, mark, stage, dtype)`` of the same moment, bit for bit."""
+        import torch
+        from . import _lib as L
+        from . import ops
+        what = "Canvas.refresh"
+        st = self.stream
+        (cy0, cx0, ch, cw), tiles, level, slot, gen = st._update(what, self.window, q, mark, stage)
+        g, dev = st.feed_state._s.g, st._pool.device
+        if level != self._level:
+            self._gen[:] = -1
+        dirty = np.zeros(gen.shape, dtype=np.int32)
+        for r, c in tiles:
+            dirty[r, c] = gen[r, c] != self._gen[r, c]
+        if not dirty.any():
+            return None
+        rows, cols = np.flatnonzero(dirty.any(1)), np.flatnonzero(dirty.any(0))
+        y0, y1 = max(cy0, int(rows[0]) * g["Sy"]), min(cy0 + ch, int(rows[-1]) * g["Sy"] + g["th"])
+        x0, x1 = max(cx0, int(cols[0]) * g["Sx"]), min(cx0 + cw, int(cols[-1]) * g["Sx"] + g["tw"])
+        box = (y0, x0, y1 - y0, x1 - x0)
+        with torch.no_grad():
+            w_lo, w_hi = st._blend_inputs()
+            status = torch.zeros((1,), dtype=torch.int32, device=dev)
+            ops.tile_refresh(st._pool, torch.from_numpy(slot).to(dev), torch.from_numpy(dirty).to(dev), w_lo, w_hi, g["H"], g["W"],
+                             g["V"], (cy0, cx0, ch, cw), box, self.out, status)
+            if int(status.item()):
+                raise L.VamError(f"{what}: vam_tile_refresh met an absent tile inside the window")
+        for r, c in tiles:
+            self._gen[r, c] = gen[r, c]
+        self._level = level
+        return box

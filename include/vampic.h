@@ -424,13 +424,24 @@ int vam_threshold_counts(const uint32_t* keys, int T, int n_slice, int n, const 
  * maps at pixel resolution, the coords of vam_tile_extract, th and tw multiples of 16, out fp32 [n, L, th / 16, tw / 16] with
  *   out[i, k, a, b] = max over y, x in [0, 16) of maps[k, min(r Sy + 16 a + y, H - 1), min(c Sx + 16 b + x, W - 1)]:
  * the block maximum of a latent cell over the tile's replicated pixels; a NaN anywhere in the block gives NaN.  An (r, c)
- * outside the grid leaves its rows unwritten.  n L <= 65535 per launch.  No atomics, no allocation, capturable. */
+ * outside the grid leaves its rows unwritten.  n L <= 65535 per launch.  No atomics, no allocation, capturable.
+ * vam_tile_refresh: vam_tile_blend restricted to what changed.  out is a persistent canvas of the window
+ * cy0, cx0, ch, cw of the picture: fp32 [3, ch, cw] (out_u8 = 0) or uint8 [ch, cw, 3] (out_u8 = 1).  dirty int32 [R][C] on the
+ * device marks tiles (non-zero: dirty); y0, x0, h, w, in picture coordinates, is the box to visit inside the canvas window.  Per
+ * pixel of the box: when none of its 1, 2 or 4 tiles is dirty it is not written and its tiles' slots are not read (they may
+ * be absent); otherwise all of its tiles must be present (else *status = 1, as vam_tile_blend) and it gets vam_tile_blend's
+ * value, bit for bit.  Pixels outside the box are never touched.  A canvas window outside the picture, a box outside the
+ * canvas window and a box of more than 4 * 65535 rows are VAM_EINVAL and launch nothing.  No atomics, no allocation,
+ * capturable. */
 int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
                      void* stream);
 int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
                    int tw, int V, int y0, int x0, int h, int w, void* out, int out_u8, int32_t* status, void* stream);
 int vam_tile_schedule(const float* maps, int L, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
                       void* stream);
+int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32_t* dirty, const float* w_lo, const float* w_hi,
+                     int H, int W, int th, int tw, int V, int cy0, int cx0, int ch, int cw, int y0, int x0, int h, int w, void* out,
+                     int out_u8, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).

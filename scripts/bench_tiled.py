@@ -24,11 +24,21 @@ every stage beside ``decode(mark=k)`` of the unscheduled stream, vam_tile_schedu
 over 50 launches) beside a ``copy_`` of as many bytes as it reads, the bytes of every stage (``round_end``) and the share of
 every stage's round that lies in the tiles the box touches.
 
+``--stream`` adds ``"receiver"``: the stream is fed to a ``tiled.PictureStream`` round by round (the heads,
+then every ``round_end``); after each feed ``Canvas.refresh()`` of the whole picture and, on a second receiver, of the 512 x 512
+window is timed beside a fresh ``PictureDecoder(prefix).decode(window)`` of the same bytes in the same process (whose code
+path is that of the commit before the receiver); every run starts a new receiver, and the median, the smallest and the largest
+of the runs are reported with the tiles that ran the network.  With ``--schedule roi`` the scheduled stream is fed, too.  It
+also times vam_tile_refresh alone (HIP events over 50 launches, five times: median, min, max) for a box of one dirty tile, of
+nine and of all, beside vam_tile_blend of the same box.  ``--pan`` adds ``"pan"``: on the whole stream a 512 x 512 window moves by
+one tile stride at a time along the middle row of the picture and then down its middle column; per step ``view`` beside a
+fresh ``decode`` of that window, and the tiles ``view`` decoded.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
-                                  [--schedule roi]
+                                  [--schedule roi] [--stream] [--pan]
 """
 import argparse
 import json
@@ -171,6 +181,106 @@ def scheduled(a, net, x, g, kw, plain, window, TL, EV, ops):
     return out
 
 
+def spread(times):
+    return [round(statistics.median(times), 3), round(min(times), 3), round(max(times), 3)]
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0), out
+
+
+def receiver(a, net, g, data, window, TL):
+    """One stream of the ``--stream`` section: [median, min, max] ms over ``reps`` runs per feed, each run on new receivers."""
+    lay = TL.layout(data)
+    cuts = sorted({lay["need_bytes"], *lay["round_end"]})
+    n_tiles = g["R"] * g["C"]
+    keys = ("refresh_full_ms", "fresh_full_ms", "refresh_window_ms", "fresh_window_ms")
+    times = [{k: [] for k in keys} for _ in cuts]
+    decoded = [None] * len(cuts)
+    for run in range(a.warmup + a.reps):
+        full, part = (TL.PictureStream(net, coder=a.coder, cache_tiles=n_tiles) for _ in range(2))
+        at, canvases = 0, None
+        for i, n in enumerate(cuts):
+            for st in (full, part):
+                st.feed(data[at:n])
+            at = n
+            if canvases is None:
+                canvases = (full.canvas(), part.canvas(window))
+            fresh = TL.PictureDecoder(net, data[:n], coder=a.coder)
+            row = {"refresh_full_ms": timed(canvases[0].refresh)[0], "fresh_full_ms": timed(fresh.decode)[0],
+                   "refresh_window_ms": timed(canvases[1].refresh)[0], "fresh_window_ms": timed(lambda: fresh.decode(window))[0]}
+            decoded[i] = [len(full.last_decoded), len(part.last_decoded)]
+            if run == a.warmup + a.reps - 1:                       # what was timed is what a fresh decode gives
+                assert torch.equal(canvases[0].out, fresh.decode()) and torch.equal(canvases[1].out, fresh.decode(window))
+            if run >= a.warmup:
+                for k in keys:
+                    times[i][k].append(row[k])
+    return {"tiles": [n_tiles, len(TL.tiles_for(g, window))], "runs": a.reps,
+            "feeds": [dict({"bytes": n, "decoded_full": decoded[i][0], "decoded_window": decoded[i][1]},
+                           **{k: spread(times[i][k]) for k in keys}) for i, n in enumerate(cuts)]}
+
+
+def refresh_kernel(g, dev, TL, ops):
+    """vam_tile_refresh alone beside vam_tile_blend of the same box: one dirty tile, nine, all; fp32 and uint8."""
+    H, W, R, C = g["H"], g["W"], g["R"], g["C"]
+    n = R * C
+    tiles = torch.rand((n, 3, g["th"], g["tw"]), dtype=torch.float32, device=dev)
+    slot = torch.arange(n, dtype=torch.int32, device=dev).view(R, C)
+    w_lo, w_hi = (torch.from_numpy(t).to(dev) if g["V"] else None for t in TL.ramps(g["V"]))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    r0, c0 = R // 2, C // 2
+    cases = {"one_tile": (r0, r0 + 1, c0, c0 + 1), "nine_tiles": (max(r0 - 1, 0), min(r0 + 2, R), max(c0 - 1, 0), min(c0 + 2, C)),
+             "all_tiles": (0, R, 0, C)}
+    out = {}
+    for name, (ra, rb, ca, cb) in cases.items():
+        dirty = torch.zeros((R, C), dtype=torch.int32)
+        dirty[ra:rb, ca:cb] = 1
+        dirty = dirty.to(dev)
+        y0, y1 = ra * g["Sy"], min(H, (rb - 1) * g["Sy"] + g["th"])
+        x0, x1 = ca * g["Sx"], min(W, (cb - 1) * g["Sx"] + g["tw"])
+        box = (y0, x0, y1 - y0, x1 - x0)
+        row = {"box": list(box), "dirty_tiles": (rb - ra) * (cb - ca)}
+        for kind, canvas, crop in (("f32", torch.zeros((3, H, W), dtype=torch.float32, device=dev), torch.empty((3, box[2], box[3]), dtype=torch.float32, device=dev)),
+                                   ("u8", torch.zeros((H, W, 3), dtype=torch.uint8, device=dev), torch.empty((box[2], box[3], 3), dtype=torch.uint8, device=dev))):
+            row[f"refresh_{kind}_us"] = spread([event_us(lambda: ops.tile_refresh(tiles, slot, dirty, w_lo, w_hi, H, W, g["V"], (0, 0, H, W), box,
+                                                                                   canvas, status)) for _ in range(5)])
+            row[f"blend_{kind}_us"] = spread([event_us(lambda: ops.tile_blend(tiles, slot, w_lo, w_hi, H, W, g["V"], box, crop, status))
+                                              for _ in range(5)])
+        out[name] = row
+    assert int(status.item()) == 0
+    return out
+
+
+def pan(a, net, g, data, TL):
+    """The ``--pan`` section: see the module docstring."""
+    H, W = g["H"], g["W"]
+    h, w = min(512, H), min(512, W)
+    ym, xm = (H - h) // 2, (W - w) // 2
+    path = [(ym, x0, h, w) for x0 in range(0, W - w + 1, g["Sx"])] + [(y0, xm, h, w) for y0 in range(0, H - h + 1, g["Sy"])]
+    fresh = TL.PictureDecoder(net, data, coder=a.coder)
+    times = [{"view_ms": [], "fresh_ms": []} for _ in path]
+    decoded = [0] * len(path)
+    for run in range(a.warmup + a.reps):
+        st = TL.PictureStream(net, coder=a.coder)
+        st.feed(data)
+        for i, win in enumerate(path):
+            tv, got = timed(lambda: st.view(win))
+            decoded[i] = len(st.last_decoded)
+            tf, want = timed(lambda: fresh.decode(win))
+            assert torch.equal(got, want)
+            if run >= a.warmup:
+                times[i]["view_ms"].append(tv)
+                times[i]["fresh_ms"].append(tf)
+    steps = [{"window": list(win), "tiles": len(TL.tiles_for(g, win)), "decoded": decoded[i], "view_ms": spread(times[i]["view_ms"]),
+              "fresh_ms": spread(times[i]["fresh_ms"])} for i, win in enumerate(path)]
+    return {"runs": a.reps, "cache_tiles": st.cache_tiles, "steps": steps,
+            "sum_view_ms": round(sum(s_["view_ms"][0] for s_ in steps), 2), "sum_fresh_ms": round(sum(s_["fresh_ms"][0] for s_ in steps), 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -184,6 +294,8 @@ def main():
     ap.add_argument("--base-lanes", type=int, default=1)
     ap.add_argument("--allocation", nargs="+", default=None, choices=["tile", "picture"])
     ap.add_argument("--schedule", default=None, choices=["roi"])
+    ap.add_argument("--stream", action="store_true")
+    ap.add_argument("--pan", action="store_true")
     a = ap.parse_args()
     from bench import build_model
     import vampic
@@ -241,6 +353,14 @@ def main():
             res["allocations"] = allocations(a, net, x, g, kw, TL, EB, ops)
         if a.schedule:
             res["scheduled"] = scheduled(a, net, x, g, kw, data, window, TL, EV, ops)
+        if a.stream:
+            res["receiver"] = {"plain": receiver(a, net, g, data, window, TL), "refresh_kernel": refresh_kernel(g, dev, TL, ops)}
+            if a.schedule:
+                y0, x0, h, w = window
+                S = EV.picture_roi_schedule(H, W, [(y0, x0, y0 + h, x0 + w)], ROI_QUALITIES, BACKGROUND_QUALITIES, dev)
+                res["receiver"]["roi"] = receiver(a, net, g, TL.encode(net, x, schedule=S, **kw), window, TL)
+        if a.pan:
+            res["pan"] = pan(a, net, g, data, TL)
     for k in ("encode_ms", "decode_full_ms", "decode_window_ms"):
         res[k] = round(res[k], 2)
     print(json.dumps(res))
