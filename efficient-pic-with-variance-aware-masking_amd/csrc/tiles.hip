@@ -24,6 +24,10 @@
 //                         stored only when one of its tiles is marked in `dirty` [R][C]; the value is blend_run's, so it is
 //                         tile_blend_kernel's bit for bit.  A pixel without a dirty tile is not written and its slots are not
 //                         read.  The output has the canvas's pitch; wide stores need all four pixels written.
+//   picture_halve_kernel  the next level of a resolution pyramid: fp32 [C, Hs, Ws] to [C, ceil(Hs / 2),
+//                         ceil(Ws / 2)], out[c][y][x] = ((s[2y][2x] + s[2y][x1]) + (s[y1][2x] + s[y1][x1])) * 0.25f with
+//                         y1 = min(2y + 1, Hs - 1), x1 = min(2x + 1, Ws - 1), every add and the multiply one fp32 operation;
+//                         mode 1 takes the maximum of the four instead (schedules), a NaN among them giving NaN.
 // All move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
 // scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
 #include "common.h"
@@ -348,6 +352,67 @@ __global__ __launch_bounds__(256) void tile_refresh_kernel(const RefreshArgs a) 
   }
 }
 
+struct HalveArgs {
+  const float* src;
+  float* dst;
+  int C, Hs, Ws, Hd, Wd, mode, gy;          // gy: row blocks along grid.y; grid.z = C * (splits of the row blocks)
+};
+
+// One 2 x 2 block of the level below: rows a b over c d.  The mean is three adds and one multiply that
+// nothing can contract; the maximum keeps the first of two equal operands.  Which NaN comes out is pinned: the quiet one.
+__device__ __forceinline__ float halve_one(float a, float b, float c, float d, int mode) {
+  float r;
+  if (mode) {
+    const float m0 = a >= b ? a : b, m1 = c >= d ? c : d;
+    r = m0 >= m1 ? m0 : m1;
+    if ((a != a) | (b != b) | (c != c) | (d != d)) r = __int_as_float(0x7FC00000);
+  } else {
+    r = __fmul_rn(__fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d)), 0.25f);
+    if (r != r) r = __int_as_float(0x7FC00000);
+  }
+  return r;
+}
+
+// Block (64, 4): a thread owns four consecutive pixels of one row of the level above, a wave 256 of them: it reads 2 KiB of
+// each of the two source rows in 16-byte loads and stores 1 KiB.  The wide path needs all eight source columns inside the row
+// and both addresses 16-byte aligned (an odd Ws or a base 4 bytes off puts rows off the boundary); otherwise the pixels are
+// read one by one with the clamped column.  A clamped last ROW is the same row twice on either path.
+__global__ __launch_bounds__(256) void picture_halve_kernel(const HalveArgs a) {
+  const int ch = blockIdx.z % a.C;
+  const long yb = (long)(blockIdx.z / a.C) * a.gy + blockIdx.y;
+  const long y = yb * 4 + threadIdx.y;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x);
+  if (x >= a.Wd || y >= a.Hd) return;
+  const int nv = min(4, a.Wd - x);
+  const long Y0 = 2 * y, Y1 = min(2 * y + 1, (long)a.Hs - 1);
+  const float* r0 = a.src + ((long)ch * a.Hs + Y0) * a.Ws;
+  const float* r1 = a.src + ((long)ch * a.Hs + Y1) * a.Ws;
+  float* dst = a.dst + ((long)ch * a.Hd + y) * a.Wd + x;
+  const int X = 2 * x;
+  float v[4];
+  if (X + 7 < a.Ws && aligned16(r0 + X) && aligned16(r1 + X)) {
+    const float4 t0 = *reinterpret_cast<const float4*>(r0 + X), t1 = *reinterpret_cast<const float4*>(r0 + X + 4);
+    const float4 b0 = *reinterpret_cast<const float4*>(r1 + X), b1 = *reinterpret_cast<const float4*>(r1 + X + 4);
+    v[0] = halve_one(t0.x, t0.y, b0.x, b0.y, a.mode);
+    v[1] = halve_one(t0.z, t0.w, b0.z, b0.w, a.mode);
+    v[2] = halve_one(t1.x, t1.y, b1.x, b1.y, a.mode);
+    v[3] = halve_one(t1.z, t1.w, b1.z, b1.w, a.mode);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int xa = min(X + 2 * k, a.Ws - 1), xb = min(X + 2 * k + 1, a.Ws - 1);      // k >= nv: clamped reads, never stored
+      v[k] = halve_one(r0[xa], r0[xb], r1[xa], r1[xb], a.mode);
+    }
+  }
+  if (nv == 4 && aligned16(dst)) {
+    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < nv) dst[k] = v[k];
+  }
+}
+
 }  // namespace
 }  // namespace vam
 
@@ -432,6 +497,25 @@ int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32
   ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
   hipLaunchKernelGGL(tile_refresh_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
   return check_launch("tile_refresh_kernel");
+}
+
+int vam_picture_halve(const float* src, int C, int Hs, int Ws, float* dst, int mode, void* stream) {
+  VAM_REQUIRE(src && dst, "vam_picture_halve: need src and dst");
+  VAM_REQUIRE(C >= 1 && C <= VAM_MAX_LAYER_LEVELS, "vam_picture_halve: 1 .. %d planes, got %d", VAM_MAX_LAYER_LEVELS, C);
+  VAM_REQUIRE(Hs >= 1 && Ws >= 1 && Hs <= kTileMaxSide && Ws <= kTileMaxSide, "vam_picture_halve: a picture of %d x %d: sides are 1 .. %d",
+              Hs, Ws, kTileMaxSide);
+  VAM_REQUIRE(mode == 0 || mode == 1, "vam_picture_halve: mode is 0 (mean) or 1 (max), got %d", mode);
+  HalveArgs a;
+  a.src = src; a.dst = dst; a.C = C; a.Hs = Hs; a.Ws = Ws; a.mode = mode;
+  a.Hd = (Hs + 1) / 2; a.Wd = (Ws + 1) / 2;
+  const unsigned row_blocks = cdiv(a.Hd, 4), kMaxY = 32768;                     // up to 2^21: over grid.y and grid.z
+  a.gy = (int)(row_blocks < kMaxY ? row_blocks : kMaxY);
+  const dim3 grid(cdiv(cdiv(a.Wd, 4), 64), a.gy, C * cdiv(row_blocks, a.gy));
+  VAM_REQUIRE((double)grid.x * grid.y * grid.z * 256.0 < 4294967296.0, "vam_picture_halve: %d planes of %d x %d exceed one launch", C,
+              Hs, Ws);
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, 4.0 * C * ((double)Hs * Ws + (double)a.Hd * a.Wd));
+  hipLaunchKernelGGL(picture_halve_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("picture_halve_kernel");
 }
 
 }  // extern "C"

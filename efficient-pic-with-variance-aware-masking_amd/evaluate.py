@@ -511,6 +511,51 @@ def tiled_stream_rd(model, image: torch.Tensor, cuts: Optional[Sequence[int]] = 
     return rows
 
 
+def pyramid_rd(model, image: torch.Tensor, qualities: Sequence[float], levels: Optional[int] = None, tile: int = 256, overlap: int = 32,
+               coder=None, lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None):
+    """:func:`tiled_rd` for a resolution pyramid (pyramid.encode / PyramidDecoder): the picture is coded
+    ONCE with ``qualities`` (non-decreasing, as marks) as the marks of every level.  One dict per level and quality: level,
+    shape (H_k, W_k), q, bytes (the pyramid header plus that level's own ``round_end`` for the mark: the prefix of that level's
+    codestream that holds every tile exactly at the mark, sent alone), bpp (8 * bytes / (H W) over the
+    TRUE level-0 size), psnr of the level's decode against the REDUCED original (``ops.picture_halve`` of the picture, k
+    times), enc_s (the one encode of all levels), dec_s (parsing that prefix of the level and decoding it whole at q) and
+    total_over_level0: the pyramid's total bytes over level 0's alone."""
+    from . import ops
+    from . import pyramid as PY
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    qs = [float(q) for q in qualities]
+    rows = []
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        data = PY.encode(model, x, levels=levels, tile=tile, overlap=overlap, marks=qs, coder=coder, lanes=lanes, base_lanes=base_lanes,
+                         group=group)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        lay = PY.layout(data)
+        ratio = lay["total"] / lay["levels"][0]["length"]
+        want = x[0].contiguous()
+        for lv in lay["levels"]:
+            k = lv["level"]
+            if k:
+                want = ops.picture_halve(want)
+            stream = PY.level_stream(data, k)
+            for j, q in enumerate(qs):
+                end = lv["layout"]["round_end"][j]
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                x_hat = TL.PictureDecoder(model, stream[:end], coder=coder, group=group).decode(q=q)
+                torch.cuda.synchronize()
+                t3 = time.perf_counter()
+                n = lay["header_end"] + int(end)
+                rows.append({"level": k, "shape": tuple(lv["shape"]), "q": q, "bytes": n, "bpp": 8.0 * n / (H * W),
+                             "psnr": compute_psnr(want.unsqueeze(0), x_hat.unsqueeze(0)), "enc_s": t1 - t0, "dec_s": t3 - t2,
+                             "total_over_level0": ratio})
+    return rows
+
+
 def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
                        base_lanes: int = 1):
     """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE

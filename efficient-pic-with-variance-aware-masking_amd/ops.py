@@ -884,6 +884,29 @@ def tile_refresh(tiles: torch.Tensor, slot: torch.Tensor, dirty: torch.Tensor, w
     L.check(rc, "vam_tile_refresh")
 
 
+HALVE_MODES = ("mean", "max")
+
+
+def picture_halve(src: torch.Tensor, mode: str = "mean", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The next level of a resolution pyramid: ``src`` fp32 [C, Hs, Ws], contiguous, 1 <= C <= 32, to fp32
+    [C, ceil(Hs / 2), ceil(Ws / 2)].  ``mode`` = "mean": ``((s[2y][2x] + s[2y][x1]) + (s[y1][2x] + s[y1][x1])) * 0.25`` with
+    ``y1 = min(2y + 1, Hs - 1)``, ``x1 = min(2x + 1, Ws - 1)``, every operation one fp32 operation in this order; "max": the
+    maximum of the four (schedules), a NaN among them giving NaN.  ``out``: where to write it (allocated when None).  One
+    launch (vam_picture_halve); capturable when ``out`` is given."""
+    if mode not in HALVE_MODES:
+        raise ValueError(f"picture_halve: mode is one of {HALVE_MODES}, got {mode!r}")
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3 and src.is_cuda
+    C_, Hs, Ws = (int(v) for v in src.shape)
+    shape = (C_, (Hs + 1) // 2, (Ws + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == src.device, \
+        (out.dtype, tuple(out.shape), shape)
+    L.check(L.load().vam_picture_halve(src.data_ptr(), C_, Hs, Ws, out.data_ptr(), HALVE_MODES.index(mode), stream_ptr()),
+            "vam_picture_halve")
+    return out
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

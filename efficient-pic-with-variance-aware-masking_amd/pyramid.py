@@ -1,0 +1,602 @@
+"""Resolution pyramids of tiled pictures: the picture at halved resolutions as well, coarsest first, so
+that the first bytes are a thumbnail and a zoomed-out view decodes a small picture instead of every tile of the large one.
+
+The definition, one rule for ``csrc/tiles.hip`` (vam_picture_halve), this module and ``tests/pyramid_ref.py``: level 0 is the
+picture, fp32 [3, H, W]; level k >= 1 has ``H_k = ceil(H_{k-1} / 2)`` rows and ``W_k = ceil(W_{k-1} / 2)`` columns
+(``H_k = ceil(H / 2^k)``), and with ``y1 = min(2y + 1, H_{k-1} - 1)``, ``x1 = min(2x + 1, W_{k-1} - 1)``
+
+    P_k[c][y][x] = ((P_{k-1}[c][2y][2x] + P_{k-1}[c][2y][x1]) + (P_{k-1}[c][y1][2x] + P_{k-1}[c][y1][x1])) * 0.25f
+
+every add and the multiply one fp32 operation in this order, the edge replicated at every level.  A schedule (section 9x) is
+reduced alongside with the maximum of the four.  Pixel (y, x) of level k stands for the level-0 rows ``[y 2^k, (y + 1) 2^k)``
+and the columns likewise, clipped to the picture; :func:`window_at` gives the smallest level-k window that covers a level-0
+window.
+
+The codestream: ``embedded._PREAMBLE`` with magic ``b"VAMy"`` (version 1, reserved 0, bytes of the header, CRC-32 of the
+header), a little-endian header (u32 H, W; u16 n_levels; u16 reserved (0); n_levels x u64 ``bytes_k`` for k = 0 .. n - 1, 0: the
+level is absent; u64 total), then the body: the level codestreams, COARSEST FIRST (k = n - 1 down to 0), each exactly the bytes
+``tiled.encode`` gives for that level's picture; nothing is re-framed.  From :func:`need_bytes` on every prefix decodes a
+whole picture at some resolution.  Everything but :func:`encode`, :class:`PyramidDecoder`, and the views of
+:class:`PyramidStream` is host arithmetic and needs neither a model nor a GPU.
+
+Out of scope: scales that are no power of two and resampling; showing an upsampled coarser level where a finer one has not
+arrived; interleaving rounds across levels; coding a level as a residual of the coarser one; entropy-coded headers.
+"""
+from __future__ import annotations
+
+import struct
+import zlib
+from typing import List, Optional, Sequence, Tuple
+
+from . import embedded as EB
+from . import tiled as TL
+
+MAGIC = b"VAMy"
+VERSION = 1
+MAX_LEVELS = 16
+_PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
+PREAMBLE_BYTES = EB.PREAMBLE_BYTES
+_FIXED = struct.Struct("<IIHH")            # H, W, n_levels, reserved (0); then u64 bytes_k [n_levels] and the u64 total
+_ALIKE = ("V", "allocation", "stages", "marks", "lanes", "base_lanes", "ns")
+
+
+# ------------------------------------------------------------------------------------------------------------- geometry
+def level_shapes(H: int, W: int, n_levels: int) -> List[Tuple[int, int]]:
+    """[(H_k, W_k)] for k = 0 .. n_levels - 1: ``H_k = ceil(H / 2^k)``."""
+    return [(-(-H // (1 << k)), -(-W // (1 << k))) for k in range(n_levels)]
+
+
+def _check_levels(H: int, W: int, n: int, what: str) -> List[Tuple[int, int]]:
+    if not (1 <= H <= TL.MAX_SIDE and 1 <= W <= TL.MAX_SIDE):
+        raise ValueError(f"{what}: a picture of {H} x {W}: sides are 1 .. {TL.MAX_SIDE}")
+    if not 1 <= n <= MAX_LEVELS:
+        raise ValueError(f"{what}: levels is 1 .. {MAX_LEVELS}, got {n}")
+    shapes = level_shapes(H, W, n)
+    if n >= 2 and shapes[n - 2] == (1, 1):
+        k = shapes.index((1, 1))
+        raise ValueError(f"{what}: {n} levels of a {H} x {W} picture: level {k} is 1 x 1 already and level {k + 1} would repeat it; "
+                         f"at most {k + 1} levels")
+    return shapes
+
+
+def default_levels(H: int, W: int, tile: int = 256) -> int:
+    """Levels until a level fits one tile (``H_k <= tile and W_k <= tile``): at least 1, at most 16."""
+    n = 1
+    while n < MAX_LEVELS and not (-(-H // (1 << (n - 1))) <= tile and -(-W // (1 << (n - 1))) <= tile):
+        n += 1
+    return n
+
+
+def window_at(window, k: int, H: int, W: int) -> Tuple[int, int, int, int]:
+    """The smallest window (y0, x0, h, w) of level k that covers the level-0 window ``window`` of an H x W picture (None:
+    the picture): rows ``y0 >> k`` .. ``min(H_k, ceil((y0 + h) / 2^k))``, columns likewise."""
+    k = TL._int(k, "window_at: k")
+    if not 0 <= k < 32:
+        raise ValueError(f"window_at: k is a level, 0 .. 31, got {k}")
+    y0, x0, h, w = TL._window({"H": H, "W": W}, window, "window_at")
+    Hk, Wk = level_shapes(H, W, k + 1)[k]
+    ya, xa = y0 >> k, x0 >> k
+    return ya, xa, min(Hk, -(-(y0 + h) // (1 << k))) - ya, min(Wk, -(-(x0 + w) // (1 << k))) - xa
+
+
+def best_level(window, out_hw, H: int, W: int, n_levels: int) -> int:
+    """The coarsest level of ``n_levels`` whose window covering ``window`` (level-0 coordinates; None: the picture) has at
+    least ``out_hw`` = (rows, columns) in both directions: the level to decode for a viewport of that size.  0 when not
+    even level 0 has."""
+    oh, ow = (TL._int(v, "best_level: out_hw") for v in out_hw)
+    n = TL._int(n_levels, "best_level: n_levels")
+    if oh < 1 or ow < 1 or n < 1:
+        raise ValueError(f"best_level: out_hw is (rows, columns) >= 1 and n_levels >= 1, got {tuple(out_hw)} and {n}")
+    best = 0
+    for k in range(n):                                                          # the covering window never grows with k
+        _, _, h, w = window_at(window, k, H, W)
+        if h >= oh and w >= ow:
+            best = k
+    return best
+
+
+# ----------------------------------------------------------------------------------------------------------- codestream
+def _header_end(d, what: str) -> Optional[int]:
+    if len(d) < PREAMBLE_BYTES:
+        return None
+    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
+    if magic != MAGIC:
+        raise ValueError(f"{what}: not a pyramid codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
+    if version != VERSION or reserved:
+        raise ValueError(f"{what}: pyramid codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
+                         f"reader knows version {VERSION}")
+    if not _FIXED.size + 16 <= hlen <= _FIXED.size + 8 * MAX_LEVELS + 8 or (hlen - _FIXED.size) % 8:
+        raise ValueError(f"{what}: a header of {hlen} bytes: the header of n = 1 .. {MAX_LEVELS} levels takes {_FIXED.size + 8} + 8 n")
+    return PREAMBLE_BYTES + hlen
+
+
+class _Pyramid:
+    """A parsed pyramid header and the byte arithmetic of the body that follows from it."""
+
+    def __init__(self, d, what: str):
+        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
+        end = PREAMBLE_BYTES + hlen
+        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
+            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        H, W, n, zero = _FIXED.unpack_from(d, PREAMBLE_BYTES)
+        if zero:
+            raise ValueError(f"{what}: the header's reserved field is {zero}, this reader knows 0")
+        if hlen != _FIXED.size + 8 * n + 8:
+            raise ValueError(f"{what}: the header contradicts itself: {n} levels take {_FIXED.size + 8 * n + 8} bytes, it states {hlen}")
+        self.shapes = _check_levels(H, W, n, what)
+        self.H, self.W, self.n, self.header_end = H, W, n, end
+        sizes = struct.unpack_from(f"<{n + 1}Q", d, PREAMBLE_BYTES + _FIXED.size)
+        self.size, self.total = [int(v) for v in sizes[:n]], int(sizes[n])
+        if not any(self.size):
+            raise ValueError(f"{what}: the header holds no level: every level has 0 bytes")
+        if end + sum(self.size) != self.total:
+            raise ValueError(f"{what}: the header contradicts itself: its levels add up to {end + sum(self.size)} bytes, it states a "
+                             f"total of {self.total}")
+        self.off, at = [0] * n, end
+        for k in reversed(range(n)):                                            # the body: coarsest first
+            self.off[k] = at
+            at += self.size[k]
+        self.order = [k for k in reversed(range(n)) if self.size[k]]            # the present levels in the order of the body
+
+    def held(self, n: int, k: int) -> int:
+        """The bytes of level k that the first ``n`` bytes of the codestream hold."""
+        return min(max(n - self.off[k], 0), self.size[k])
+
+    def level(self, k, what: str) -> int:
+        k = TL._int(k, f"{what}: level")
+        if not 0 <= k < self.n:
+            raise ValueError(f"{what}: level is 0 .. {self.n - 1}, got {k}")
+        return k
+
+
+def _parse(data, what: str):
+    """(view, parsed header) of a pyramid codestream, or a prefix of one, that holds its whole header."""
+    d = EB._view(data, what)
+    end = _header_end(d, what)
+    if end is None or len(d) < end:
+        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
+                         "before it can be read")
+    p = _Pyramid(d, what)
+    if len(d) > p.total:
+        raise ValueError(f"{what}: {len(d)} bytes, the header states a total of {p.total}: {len(d) - p.total} bytes follow the "
+                         "codestream")
+    return d, p
+
+
+def _facts(g: dict, total: int, allocation: str, stages: int, meta: Optional[dict]) -> dict:
+    """What the levels of one pyramid are checked on: a level's geometry and total, and, once a tile head is held, what its
+    tiles carry."""
+    f = {key: g[key] for key in ("H", "W", "th", "tw", "V")}
+    f.update({"total": total, "allocation": allocation, "stages": stages})
+    for key in ("marks", "lanes", "base_lanes", "ns"):
+        f[key] = None if meta is None else meta[key]
+    return f
+
+
+def _check_facts(p: _Pyramid, facts: dict, what: str):
+    """``facts``: level -> :func:`_facts` of every level whose own header is held.  Each level against the pyramid's header,
+    then the levels against each other: one overlap, one tile size, one allocation and stage count, and tiles that carry
+    the same marks, lanes and base_lanes."""
+    for k, f in facts.items():
+        if (f["H"], f["W"]) != p.shapes[k]:
+            raise ValueError(f"{what}: level {k} holds a picture of {f['H']} x {f['W']}; level {k} of a {p.H} x {p.W} picture is "
+                             f"{p.shapes[k][0]} x {p.shapes[k][1]}")
+        if f["total"] != p.size[k]:
+            raise ValueError(f"{what}: the header contradicts level {k}: it states {p.size[k]} bytes, the level's own header a total "
+                             f"of {f['total']}")
+    ks = sorted(facts)
+    if len(ks) < 2:
+        return
+    for k in ks[1:]:
+        a, b = facts[ks[0]], facts[k]
+        for key in _ALIKE:
+            if a[key] is not None and b[key] is not None and not EB._same(a[key], b[key]):
+                name = {"V": "overlap", "stages": "stages (scheduled or not)"}.get(key, key)
+                raise ValueError(f"{what}: level {k} and level {ks[0]} differ in their {name} ({b[key]!r} against {a[key]!r}): all "
+                                 "levels of a pyramid are coded with the same tile geometry, marks and lanes")
+    c64 = lambda v: -(-v // 64) * 64
+    for axis, side in (("th", "H"), ("tw", "W")):                               # th = min(tile, ceil64(H_k)) for ONE tile
+        cut = {k: f[axis] for k, f in facts.items() if f[axis] < c64(f[side])}  # levels that state the tile exactly
+        least = max(f[axis] for f in facts.values())
+        if len(set(cut.values())) > 1 or (cut and least > min(cut.values())):
+            raise ValueError(f"{what}: the levels differ in their tile size: tiles of {[facts[k][axis] for k in ks]} along "
+                             f"{side} at the levels {ks} are not min(tile, the level's side rounded up to 64) for one tile")
+
+
+def _level_layout(d, p: _Pyramid, k: int, what: str) -> Optional[dict]:
+    """``tiled.layout`` of what ``d`` holds of level k; None while it does not hold that level's own header."""
+    held = p.held(len(d), k)
+    part = d[p.off[k]:p.off[k] + held]
+    try:
+        end = TL._header_end(part, what)
+        return TL.layout(part) if end is not None and held >= end else None
+    except ValueError as e:
+        raise ValueError(f"{what}: level {k}: {e}") from e
+
+
+def _layouts(d, p: _Pyramid, what: str) -> List[Optional[dict]]:
+    """Every level's :func:`_level_layout`, checked against the header and against each other."""
+    lays = [_level_layout(d, p, k, what) if p.size[k] else None for k in range(p.n)]
+    _check_facts(p, {k: _facts(lay, lay["total"], lay["allocation"], lay["stages"], lay if lay["marks"] is not None else None)
+                     for k, lay in enumerate(lays) if lay is not None}, what)
+    return lays
+
+
+def _assemble(H: int, W: int, streams: Sequence[Optional[bytes]]) -> bytes:
+    """The pyramid codestream of the level codestreams ``streams[k]`` (None or empty: level k is absent)."""
+    n = len(streams)
+    size = [len(s) if s else 0 for s in streams]
+    hlen = _FIXED.size + 8 * n + 8
+    header = _FIXED.pack(H, W, n, 0) + struct.pack(f"<{n + 1}Q", *size, PREAMBLE_BYTES + hlen + sum(size))
+    out = [_PREAMBLE.pack(MAGIC, VERSION, 0, hlen, zlib.crc32(header) & 0xFFFFFFFF), header]
+    out += [bytes(streams[k]) for k in reversed(range(n)) if size[k]]
+    return b"".join(out)
+
+
+def pack(H: int, W: int, level_streams) -> bytes:
+    """The pyramid codestream of an H x W picture from its whole level codestreams (``tiled.encode`` of every level's
+    picture), ``level_streams[k]`` for level k, None for an absent level.  Pure framing on the host; ValueError for what
+    :func:`layout` would refuse."""
+    try:
+        streams = [None if s is None else bytes(EB._view(s, "pack")) for s in level_streams]
+    except TypeError as e:
+        raise ValueError("pack: level_streams is a sequence of picture codestreams") from e
+    _check_levels(TL._int(H, "pack: H"), TL._int(W, "pack: W"), len(streams), "pack")
+    if not any(streams):
+        raise ValueError("pack: no level: every entry is None")
+    data = _assemble(H, W, streams)
+    d, p = _parse(data, "pack")
+    for k, lay in enumerate(_layouts(d, p, "pack")):
+        if streams[k] and lay is None:
+            raise ValueError(f"pack: level {k}: {len(streams[k])} bytes do not hold a picture header")
+    return data
+
+
+def need_bytes(data) -> int:
+    """The smallest length from which a whole picture decodes at some resolution, as far as ``data`` (any prefix) tells:
+    the preamble's size while that is incomplete, the header's end while the header is, then the header plus
+    ``tiled.need_bytes`` of the coarsest present level."""
+    d = EB._view(data, "need_bytes")
+    end = _header_end(d, "need_bytes")
+    if end is None:
+        return PREAMBLE_BYTES
+    if len(d) < end:
+        return end
+    d, p = _parse(d, "need_bytes")
+    k = p.order[0]
+    try:
+        return end + TL.need_bytes(d[end:end + p.held(len(d), k)])
+    except ValueError as e:
+        raise ValueError(f"need_bytes: level {k}: {e}") from e
+
+
+def layout(data) -> dict:
+    """Where a pyramid codestream may be cut, from its header (``data``: any prefix that holds it): ``H``, ``W``,
+    ``n_levels``, ``header_end``, ``need_bytes``, ``total``, ``ready_levels`` and ``levels``: per level k a dict of ``level``,
+    ``shape`` = (H_k, W_k), ``present``, ``offset`` and ``length`` of its codestream in the whole pyramid, ``held`` (the bytes
+    of it that ``data`` holds), ``ready`` (it holds the level's own ``tiled.need_bytes``: the level decodes) and ``layout``:
+    ``tiled.layout`` of what is held, None while the level's own header is not.  Every held level header is checked against
+    this header and against the other levels."""
+    d, p = _parse(data, "layout")
+    lays = _layouts(d, p, "layout")
+    levels = []
+    for k in range(p.n):
+        held = p.held(len(d), k)
+        levels.append({"level": k, "shape": p.shapes[k], "present": p.size[k] > 0, "offset": p.off[k], "length": p.size[k], "held": held,
+                       "ready": lays[k] is not None and held >= lays[k]["need_bytes"], "layout": lays[k]})
+    first = levels[p.order[0]]
+    need = p.header_end + (TL.need_bytes(d[first["offset"]:first["offset"] + first["held"]]))
+    return {"H": p.H, "W": p.W, "n_levels": p.n, "header_end": p.header_end, "need_bytes": need, "total": p.total,
+            "ready_levels": [lv["level"] for lv in levels if lv["ready"]], "levels": levels}
+
+
+def level_stream(data, k: int) -> bytes:
+    """Level k's picture codestream as far as ``data`` (a pyramid codestream or any prefix that holds the header) holds it;
+    it may end anywhere.  ValueError for an absent level."""
+    d, p = _parse(data, "level_stream")
+    k = p.level(k, "level_stream")
+    if not p.size[k]:
+        raise ValueError(f"level_stream: level {k} is absent from this codestream; it holds the levels {sorted(p.order)}")
+    return bytes(d[p.off[k]:p.off[k] + p.held(len(d), k)])
+
+
+def extract(data, levels: Optional[Sequence[int]] = None, window=None, rounds: Optional[int] = None) -> bytes:
+    """A shorter pyramid codestream of the same picture: only the levels ``levels`` (None: those present), of each only
+    the tiles that ``window``, given in LEVEL-0 coordinates, needs at that level (``tiled.extract`` with
+    :func:`window_at`; None: those present) and only the first ``rounds`` rounds (None: all).  What a server does to send one
+    resolution, a crop, a lower quality, without the model.  ``data`` must hold what is kept.  ``extract(data)`` is ``data``;
+    an extract of an extract is an extract.  ValueError names a wanted level that ``data`` lacks."""
+    d, p = _parse(data, "extract")
+    _layouts(d, p, "extract")
+    if levels is None:
+        keep = sorted(p.order)
+    else:
+        try:
+            keep = sorted({p.level(k, "extract") for k in levels})
+        except TypeError as e:
+            raise ValueError(f"extract: levels is a sequence of levels, got {levels!r}") from e
+        if not keep:
+            raise ValueError("extract: levels is empty: a pyramid holds at least one level")
+    if window is not None:
+        window = TL._window({"H": p.H, "W": p.W}, window, "extract")
+    streams: List[Optional[bytes]] = [None] * p.n
+    for k in keep:
+        if not p.size[k]:
+            raise ValueError(f"extract: level {k} is absent from this codestream; it holds the levels {sorted(p.order)}")
+        part = d[p.off[k]:p.off[k] + p.held(len(d), k)]
+        try:
+            streams[k] = TL.extract(part, None if window is None else window_at(window, k, p.H, p.W), rounds)
+        except ValueError as e:
+            raise ValueError(f"extract: level {k}: {e}") from e
+    return _assemble(p.H, p.W, streams)
+
+
+# ---------------------------------------------------------------------------------------------------- encoder and decoder
+def encode(model, image, levels: Optional[int] = None, tile: int = 256, overlap: int = 32, **tiled_kwargs) -> bytes:
+    """The pyramid codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device.  ``levels`` = None: levels until a
+    level fits one tile (:func:`default_levels`); an explicit count is 1 .. 16 and is refused when a level would repeat a
+    1 x 1 picture.  The level pictures are made on the device, one vam_picture_halve launch each (``ops.picture_halve``), and
+    every level goes through ``tiled.encode`` UNCHANGED with ``tile``, ``overlap`` and ``tiled_kwargs`` (``marks``, ``coder``,
+    ``lanes``, ``base_lanes``, ``group``, ``allocation``): ``level_stream(data, k)`` is ``tiled.encode`` of level k's picture byte
+    for byte, level 0's is ``tiled.encode(model, image, ...)``.  ``schedule`` = S, fp32 [L, H, W], is reduced
+    alongside with ``ops.picture_halve(mode="max")``, which keeps it finite, >= 0, never decreasing by stage and adds no
+    value: level k is coded with its reduced schedule."""
+    import torch
+    from . import ops
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() not in (3, 4) \
+            or tuple(image.shape[:-2]) not in ((3,), (1, 3)):
+        raise ValueError("pyramid.encode: image is an fp32 tensor [3, H, W] or [1, 3, H, W], got "
+                         f"{tuple(image.shape) if isinstance(image, torch.Tensor) else type(image).__name__}")
+    H, W = (int(v) for v in image.shape[-2:])
+    T = TL.grid(H, W, tile, overlap)["tile"]
+    n = default_levels(H, W, T) if levels is None else TL._int(levels, "pyramid.encode: levels")
+    shapes = _check_levels(H, W, n, "pyramid.encode")
+    schedule = tiled_kwargs.pop("schedule", None)
+    pic = image.detach().reshape(3, H, W).contiguous()
+    streams = []
+    with torch.no_grad():
+        for k in range(n):
+            if k:                                                               # level 0 went through tiled.encode's own checks
+                pic = ops.picture_halve(pic)
+                schedule = None if schedule is None else ops.picture_halve(schedule, "max")
+                assert tuple(pic.shape[1:]) == shapes[k]
+            try:
+                streams.append(TL.encode(model, pic, tile=tile, overlap=overlap, schedule=schedule, **tiled_kwargs))
+            except ValueError as e:
+                if not k:
+                    raise
+                raise ValueError(f"pyramid.encode: level {k} ({shapes[k][0]} x {shapes[k][1]}): {e}") from e
+            if k == 0 and schedule is not None:
+                schedule = schedule.detach().contiguous()
+    return _assemble(H, W, streams)
+
+
+def _not_ready(what: str, k: int, present: bool, ready: List[int]) -> ValueError:
+    why = "its bytes end before the heads of its tiles do" if present else "it is absent from this codestream"
+    return ValueError(f"{what}: level {k} does not decode: {why}; the ready levels are {ready}")
+
+
+class PyramidDecoder:
+    """Decodes a pyramid codestream by level and window.  ``data``: any prefix of at least :func:`need_bytes`, or an
+    :func:`extract`.  ``shape``: the true (H, W) of level 0; ``levels``: n_levels; ``shapes``: [(H_k, W_k)]; ``ready``: per level,
+    whether ``data`` holds enough of it to decode.  A level's ``tiled.PictureDecoder`` is made when it is first decoded."""
+
+    def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
+        EB._check_model(model)
+        lay = layout(data)
+        self.m, self.coder, self.group, self._d = model, coder, group, bytes(EB._view(data, "PyramidDecoder"))
+        self.shape, self.levels, self.shapes = (lay["H"], lay["W"]), lay["n_levels"], [lv["shape"] for lv in lay["levels"]]
+        self.ready = [lv["ready"] for lv in lay["levels"]]
+        self._present = [lv["present"] for lv in lay["levels"]]
+        if not any(self.ready):
+            raise ValueError(f"PyramidDecoder: {len(self._d)} bytes end before any level decodes: {lay['need_bytes']} bytes are "
+                             "needed for the coarsest level's tile heads")
+        self._dec = {}
+        self.last_tiles: List[Tuple[int, int]] = []
+
+    def decoder(self, level: int = 0) -> "TL.PictureDecoder":
+        """The ``tiled.PictureDecoder`` of ``level`` on ``level_stream(data, level)``."""
+        k = TL._int(level, "PyramidDecoder.decode: level")
+        if not 0 <= k < self.levels:
+            raise ValueError(f"PyramidDecoder.decode: level is 0 .. {self.levels - 1}, got {k}")
+        if not self.ready[k]:
+            raise _not_ready("PyramidDecoder.decode", k, self._present[k], [j for j in range(self.levels) if self.ready[j]])
+        if k not in self._dec:
+            self._dec[k] = TL.PictureDecoder(self.m, level_stream(self._d, k), coder=self.coder, group=self.group)
+        return self._dec[k]
+
+    def decode(self, window=None, level: int = 0, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None,
+               dtype=None):
+        """``tiled.PictureDecoder(model, level_stream(data, level)).decode(window, q, mark, stage, dtype)``, bit for bit and
+        error for error: ``window`` is in the coordinates of ``level`` (:func:`window_at` maps a level-0 window).  A level that
+        is absent or not ready is a ValueError that names it and the ready levels."""
+        dec = self.decoder(level)
+        out = dec.decode(window, q=q, mark=mark, stage=stage, dtype=dtype)
+        self.last_tiles = dec.last_tiles
+        return out
+
+
+# --------------------------------------------------------------------------------------------------------- the receiver
+class PyramidFeed:
+    """The byte bookkeeping of a pyramid's receiver: a pyramid codestream, whole or an :func:`extract`, arriving in chunks
+    that may end anywhere, the header included.  Once the header is complete it owns one receiver per present level
+    (``receivers[k]``, None for an absent level; by default a ``tiled.PictureFeed``: host arithmetic only) and routes the
+    bytes to them in the order of the body.  ``make(k)`` builds level k's receiver: anything with ``tiled.PictureFeed``'s
+    interface, or that owns one as ``feed_state``.
+
+    ``ready``: a level decodes; ``ready_levels``; ``need()``: the bytes still missing before the first level does;
+    ``shape``, ``levels``, ``shapes`` once the header is complete; ``fed_levels``: the levels that the last feed gave bytes to;
+    ``data``: everything fed so far."""
+
+    def __init__(self, what: str = "PyramidFeed", make=None):
+        self._what = what
+        self._make = make if make is not None else (lambda k: TL.PictureFeed(f"{what} level {k}"))
+        self._head = bytearray()                            # the bytes up to the header's end
+        self._p: Optional[_Pyramid] = None
+        self._n = 0
+        self.receivers: List = []
+        self.fed_levels: List[int] = []
+
+    @staticmethod
+    def _state(r) -> "TL.PictureFeed":
+        return getattr(r, "feed_state", r)
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def data(self) -> bytes:
+        return bytes(self._head) + b"".join(self._state(self.receivers[k]).data for k in (self._p.order if self._p else []))
+
+    def _header(self, name: str) -> _Pyramid:
+        if self._p is None:
+            raise ValueError(f"{self._what}.{name}: the header is not complete yet: {self.need()} bytes are missing")
+        return self._p
+
+    shape = property(lambda self: (self._header("shape").H, self._header("shape").W))
+    levels = property(lambda self: self._header("levels").n)
+    shapes = property(lambda self: list(self._header("shapes").shapes))
+
+    @property
+    def ready_levels(self) -> List[int]:
+        return [k for k, r in enumerate(self.receivers) if r is not None and self._state(r).ready]
+
+    @property
+    def ready(self) -> bool:
+        return bool(self.ready_levels)
+
+    def need(self) -> int:
+        if self._p is not None:
+            return 0 if self.ready else self._state(self.receivers[self._p.order[0]]).need()
+        end = _header_end(self._head, self._what) if len(self._head) >= PREAMBLE_BYTES else None
+        return (PREAMBLE_BYTES if end is None else end) - len(self._head)
+
+    def _facts(self) -> dict:
+        out = {}
+        for k, r in enumerate(self.receivers):
+            s = None if r is None else self._state(r)._s
+            if s is not None:
+                out[k] = _facts(s.g, s.total, TL.ALLOCATIONS[s.version == TL.VERSION_POOLED], s.stages, self._state(r).meta)
+        return out
+
+    def feed(self, chunk) -> List[int]:
+        """``chunk``: the bytes that follow what was fed before, ``b""`` allowed.  Returns ``ready_levels``.  The feed is
+        checked as a whole before anything is kept: a damaged or contradicting header, a level that contradicts the header or
+        the other levels, what ``tiled.PictureFeed.feed`` refuses of a level's own bytes, bytes beyond the header's total
+        and a non-bytes argument are ValueErrors that leave the receiver, and every level's, as it was."""
+        what = f"{self._what}.feed"
+        if not isinstance(chunk, (bytes, bytearray, memoryview)):
+            raise ValueError(f"{what}: expected bytes, got {type(chunk).__name__}")
+        chunk = bytes(EB._view(chunk, what))
+        before = (len(self._head), self._p, self._n, self.receivers, self.fed_levels,
+                  [None if r is None else self._state(r)._mark() for r in self.receivers])
+        try:
+            self._route(chunk, what)
+        except ValueError:
+            n_head, self._p, self._n, self.receivers, self.fed_levels, marks = before
+            del self._head[n_head:]
+            for r, m in zip(self.receivers, marks):
+                if r is not None:
+                    self._state(r)._rewind(m)
+                    if hasattr(r, "_rewound"):
+                        r._rewound()
+            raise
+        return self.ready_levels
+
+    def _route(self, chunk: bytes, what: str):
+        at, fed = 0, []
+        if self._p is None:
+            end = _header_end(self._head + chunk[:PREAMBLE_BYTES], what)       # refuses a wrong preamble as soon as it is whole
+            take = len(chunk) if end is None else min(len(chunk), end - len(self._head))
+            self._head += chunk[:take]
+            at = take
+            if end is None or len(self._head) < end:
+                self._n += take
+                return
+            p = _Pyramid(self._head, what)
+            self._p, self.receivers = p, [self._make(k) if p.size[k] else None for k in range(p.n)]
+        p = self._p
+        n = self._n + len(chunk)
+        if n > p.total:
+            raise ValueError(f"{what}: {n} bytes, the header states a total of {p.total}: {n - p.total} bytes follow the codestream")
+        pos = self._n + at                                                      # where chunk[at:] begins in the codestream
+        for k in p.order:
+            a, b = max(pos, p.off[k]), min(n, p.off[k] + p.size[k])
+            if a < b:
+                try:
+                    self.receivers[k].feed(chunk[at + a - pos:at + b - pos])
+                except ValueError as e:
+                    raise ValueError(f"{what}: level {k}: {e}") from e
+                fed.append(k)
+        if fed:
+            _check_facts(p, self._facts(), what)
+        self._n, self.fed_levels = n, fed
+
+
+class PyramidStream:
+    """A receiver of one pyramid codestream: one ``tiled.PictureStream`` per level (``streams[k]``, None
+    for an absent level), created when the header is complete, each with its own tile cache of ``cache_tiles`` tiles
+    (None: ``PictureStream``'s default for that level's geometry).  :meth:`feed` takes chunks that end anywhere
+    (:class:`PyramidFeed`, which it owns as ``feed_state``; ``ready``, ``ready_levels``, ``need()``, ``shape``, ``levels``,
+    ``shapes``, ``fed_levels`` and ``data`` are this object's, too).  After any sequence of feeds, ``view(window, level, ...)``
+    equals a fresh ``PyramidDecoder(everything fed so far).decode(window, level, ...)`` bit for bit while only the tiles that
+    level has not cached run the network.  ``last_tiles`` / ``last_decoded``: those of the level viewed last."""
+
+    def __init__(self, model, coder: Optional[str] = None, group: Optional[int] = None, cache_tiles: Optional[int] = None):
+        TL.PictureStream(model, coder=coder, group=group, cache_tiles=cache_tiles)      # its checks of the arguments, now and not at the header
+        self.feed_state = PyramidFeed("PyramidStream", lambda k: _LevelStream(model, coder=coder, group=group, cache_tiles=cache_tiles))
+        self.last_tiles: List[Tuple[int, int]] = []
+        self.last_decoded: List[Tuple[int, int]] = []
+
+    ready = property(lambda self: self.feed_state.ready)
+    ready_levels = property(lambda self: self.feed_state.ready_levels)
+    shape = property(lambda self: self.feed_state.shape)
+    levels = property(lambda self: self.feed_state.levels)
+    shapes = property(lambda self: self.feed_state.shapes)
+    fed_levels = property(lambda self: self.feed_state.fed_levels)
+    data = property(lambda self: self.feed_state.data)
+    streams = property(lambda self: list(self.feed_state.receivers))
+
+    def need(self) -> int:
+        return self.feed_state.need()
+
+    def feed(self, chunk) -> List[int]:
+        """:meth:`PyramidFeed.feed`: host arithmetic only; it touches no GPU and no cache entry."""
+        return self.feed_state.feed(chunk)
+
+    def _level(self, what: str, level) -> "TL.PictureStream":
+        fs = self.feed_state
+        if fs._p is None:
+            raise ValueError(f"{what}: nothing to decode yet: the header is not complete, {fs.need()} bytes are missing")
+        k = fs._p.level(level, what)
+        if k not in fs.ready_levels:
+            raise _not_ready(what, k, fs._p.size[k] > 0, fs.ready_levels)
+        return fs.receivers[k]
+
+    def view(self, window=None, level: int = 0, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None,
+             dtype=None):
+        """``streams[level].view(window, q, mark, stage, dtype)``: the window is in the coordinates of ``level``.  A level that
+        is absent or not ready is a ValueError that names it and the ready levels."""
+        st = self._level("PyramidStream.view", level)
+        out = st.view(window, q=q, mark=mark, stage=stage, dtype=dtype)
+        self.last_tiles, self.last_decoded = st.last_tiles, st.last_decoded
+        return out
+
+    def canvas(self, window=None, level: int = 0, dtype=None) -> "TL.Canvas":
+        """``streams[level].canvas(window, dtype)``: a persistent output of that level that ``refresh()`` keeps equal to
+        :meth:`view` (vam_tile_refresh)."""
+        fs = self.feed_state
+        if fs._p is None:
+            raise ValueError(f"PyramidStream.canvas: the header is not complete yet: {fs.need()} bytes are missing")
+        k = fs._p.level(level, "PyramidStream.canvas")
+        if fs.receivers[k] is None:
+            raise _not_ready("PyramidStream.canvas", k, False, fs.ready_levels)
+        return fs.receivers[k].canvas(window, dtype)
+
+
+class _LevelStream(TL.PictureStream):
+    """A level's ``tiled.PictureStream``; when the pyramid refuses a chunk its bytes are taken back."""
+
+    def _rewound(self):
+        if self.feed_state._s is None:                      # the level's header went with the chunk: its geometry is open again
+            self.group = self.cache_tiles = None

@@ -959,6 +959,15 @@ class PictureFeed:
             self._per_tile = per_tile
         return self.rounds
 
+    def _mark(self):
+        """What :meth:`_rewind` needs to undo the feeds that follow: vampic.pyramid feeds one receiver per level and refuses
+        a chunk as a whole."""
+        return len(self._buf), self._s, self._heads, self._per_tile, self.meta, self.fed_tiles
+
+    def _rewind(self, mark):
+        n, self._s, self._heads, self._per_tile, self.meta, self.fed_tiles = mark
+        del self._buf[n:]
+
 
 class PictureStream:
     """A receiver of one picture codestream that is fed bytes and caches decoded tiles.

@@ -443,6 +443,23 @@ int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32
                      int H, int W, int th, int tw, int V, int cy0, int cx0, int ch, int cw, int y0, int x0, int h, int w, void* out,
                      int out_u8, int32_t* status, void* stream);
 
+/* Resolution pyramids (vampic.pyramid).  Level 0 is the picture; level k >= 1 has
+ * H_k = ceil(H_{k-1} / 2) rows and W_k = ceil(W_{k-1} / 2) columns.  vam_picture_halve makes one level from the one below:
+ * src fp32 [C, Hs, Ws] contiguous, dst fp32 [C, ceil(Hs / 2), ceil(Ws / 2)], 1 <= C <= VAM_MAX_LAYER_LEVELS (3 for a picture,
+ * L for a schedule), 1 <= Hs, Ws <= 2^24.  With y1 = min(2y + 1, Hs - 1) and x1 = min(2x + 1, Ws - 1) (the edge is replicated)
+ *   mode 0 (mean): dst[c][y][x] = ((src[c][2y][2x] + src[c][2y][x1]) + (src[c][y1][2x] + src[c][y1][x1])) * 0.25f,
+ *                  every add and the multiply one fp32 operation, in exactly this order; nothing is contracted;
+ *   mode 1 (max):  dst[c][y][x] = max(max(src[c][2y][2x], src[c][2y][x1]), max(src[c][y1][2x], src[c][y1][x1])), where
+ *                  max(p, q) is p when p >= q and q otherwise (of +0 and -0 the first), and a NaN among the four gives NaN,
+ *                  as vam_tile_schedule's block maximum does.
+ * NaN and +-inf propagate as the arithmetic gives them; a NaN result is stored as the quiet NaN 0x7FC00000 (which NaN
+ * inf - inf makes differs between processors, so its bits are pinned).  The value does not depend on the path a lane takes
+ * (16-byte loads where all eight source columns lie inside the row and both row addresses are 16-byte aligned, single loads
+ * with the clamped column otherwise).  One launch per level, rows split over two grid dimensions; no atomics, no allocation:
+ * it can be captured.  Null pointers, C outside 1 .. VAM_MAX_LAYER_LEVELS, a side outside 1 .. 2^24, a mode other than 0
+ * or 1 and a problem of 2^32 threads or more are VAM_EINVAL and launch nothing. */
+int vam_picture_halve(const float* src, int C, int Hs, int Ws, float* dst, int mode, void* stream);
+
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
  *  base  (mask == NULL):  v = round(y-mu);           lik = L(|(v+mu)-mu|, sigma);        yhat = v+mu

@@ -34,11 +34,19 @@ nine and of all, beside vam_tile_blend of the same box.  ``--pan`` adds ``"pan"`
 one tile stride at a time along the middle row of the picture and then down its middle column; per step ``view`` beside a
 fresh ``decode`` of that window, and the tiles ``view`` decoded.
 
+``--pyramid`` adds ``"pyramid"``: ``pyramid.encode`` of the picture (default levels) beside ``encode_ms``, the
+``tiled.encode`` of the same run, whose code this section's commit did not touch, and beside the figure DESIGN section 9y
+recorded for it; the pyramid's total bytes over level 0's; ``PyramidDecoder.decode(level=k)`` of the WHOLE picture at every level
+(level 0 is the full decode); a new ``PyramidStream`` that is fed ``need_bytes`` only, timed from the feed to the first
+whole-picture view (the coarsest level), beside a new ``tiled.PictureStream`` fed level 0's ``need_bytes`` and viewed whole;
+and vam_picture_halve alone on the picture, both modes (HIP events over 50 launches, five times: median, min, max), beside a
+``copy_`` of as many bytes as it READS.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
-                                  [--schedule roi] [--stream] [--pan]
+                                  [--schedule roi] [--stream] [--pan] [--pyramid]
 """
 import argparse
 import json
@@ -281,6 +289,61 @@ def pan(a, net, g, data, TL):
             "sum_view_ms": round(sum(s_["view_ms"][0] for s_ in steps), 2), "sum_fresh_ms": round(sum(s_["fresh_ms"][0] for s_ in steps), 2)}
 
 
+PARENT_TILED_ENCODE_MS = 266.5             # DESIGN section 9y's recorded tiled.encode of this picture, the commit before 9z
+
+
+def pyramid(a, net, x, g, kw, TL, PY, ops):
+    """The ``--pyramid`` section: see the module docstring."""
+    H, W = g["H"], g["W"]
+    ms, data = wall_ms(lambda: PY.encode(net, x, **kw), a.warmup, a.reps)
+    lay = PY.layout(data)
+    n = lay["n_levels"]
+    out = {"levels": n, "encode_ms": round(ms, 2), "parent_recorded_tiled_encode_ms": PARENT_TILED_ENCODE_MS, "runs": a.reps,
+           "header_bytes": lay["header_end"], "need_bytes": lay["need_bytes"], "total_bytes": lay["total"],
+           "level0_bytes": lay["levels"][0]["length"], "total_over_level0": round(lay["total"] / lay["levels"][0]["length"], 4),
+           "viewport_512x768_level": PY.best_level(None, (512, 768), H, W, n)}
+    dec = PY.PyramidDecoder(net, data, coder=a.coder)
+    rows = []
+    for lv in lay["levels"]:
+        k = lv["level"]
+        times, got = [], None
+        for i in range(a.warmup + a.reps):
+            t, got = timed(lambda: dec.decode(level=k))
+            if i >= a.warmup:
+                times.append(t)
+        assert tuple(got.shape[1:]) == tuple(lv["shape"])
+        if k:                                                      # what was timed is the level's own picture decode
+            assert torch.equal(got, TL.PictureDecoder(net, PY.level_stream(data, k), coder=a.coder).decode())
+        rows.append({"level": k, "shape": list(lv["shape"]), "tiles": lv["layout"]["R"] * lv["layout"]["C"], "bytes": lv["length"],
+                     "need_bytes": lv["layout"]["need_bytes"], "decode_whole_ms": spread(times)})
+    out["per_level"] = rows
+    first, plain = [], []
+    level0 = PY.level_stream(data, 0)
+    need0 = TL.need_bytes(level0)
+    for i in range(a.warmup + a.reps):
+        def thumbnail():
+            st = PY.PyramidStream(net, coder=a.coder)
+            st.feed(data[:lay["need_bytes"]])
+            return st.view(level=n - 1)
+
+        def heads():
+            st = TL.PictureStream(net, coder=a.coder, cache_tiles=g["R"] * g["C"])
+            st.feed(level0[:need0])
+            return st.view()
+        t, _ = timed(thumbnail)
+        u, _ = timed(heads)
+        if i >= a.warmup:
+            first.append(t)
+            plain.append(u)
+    out["first_view"] = {"pyramid_bytes": lay["need_bytes"], "pyramid_ms": spread(first), "level0_need_bytes": need0, "level0_ms": spread(plain)}
+    dst, like = torch.empty((3, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device), torch.empty_like(x)
+    out["halve_kernel"] = {"in_bytes": x.numel() * 4, "out_bytes": dst.numel() * 4,
+                           "mean_us": spread([event_us(lambda: ops.picture_halve(x, "mean", out=dst)) for _ in range(5)]),
+                           "max_us": spread([event_us(lambda: ops.picture_halve(x, "max", out=dst)) for _ in range(5)]),
+                           "copy_in_bytes_us": spread([event_us(lambda: like.copy_(x)) for _ in range(5)])}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -296,10 +359,11 @@ def main():
     ap.add_argument("--schedule", default=None, choices=["roi"])
     ap.add_argument("--stream", action="store_true")
     ap.add_argument("--pan", action="store_true")
+    ap.add_argument("--pyramid", action="store_true")
     a = ap.parse_args()
     from bench import build_model
     import vampic
-    from vampic import embedded as EB, evaluate as EV, ops, tiled as TL
+    from vampic import embedded as EB, evaluate as EV, ops, pyramid as PY, tiled as TL
     dev = torch.device("cuda:0")
     net, _ = build_model(dev)
     net.update()
@@ -361,6 +425,8 @@ def main():
                 res["receiver"]["roi"] = receiver(a, net, g, TL.encode(net, x, schedule=S, **kw), window, TL)
         if a.pan:
             res["pan"] = pan(a, net, g, data, TL)
+        if a.pyramid:
+            res["pyramid"] = pyramid(a, net, x, g, kw, TL, PY, ops)
     for k in ("encode_ms", "decode_full_ms", "decode_window_ms"):
         res[k] = round(res[k], 2)
     print(json.dumps(res))
