@@ -333,6 +333,8 @@ _SIGNATURES = {
                                     C.c_void_p]),
     "vam_tile_refresh": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 13
                          + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vam_tile_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] + [C.c_int] * 7
+                         + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vam_picture_halve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vam_graph_begin": (C.c_int, [C.c_void_p]),
     "vam_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -28,6 +28,14 @@
 //                         ceil(Ws / 2)], out[c][y][x] = ((s[2y][2x] + s[2y][x1]) + (s[y1][2x] + s[y1][x1])) * 0.25f with
 //                         y1 = min(2y + 1, Hs - 1), x1 = min(2x + 1, Ws - 1), every add and the multiply one fp32 operation;
 //                         mode 1 takes the maximum of the four instead (schedules), a NaN among them giving NaN.
+//   tile_compose_kernel   tile_blend_kernel over a window of pyramid level k whose tiles have not all arrived (DESIGN section
+//                         9za): a pixel all of whose 1, 2 or 4 tiles have a slot >= 0 is sharp and gets blend_run's value,
+//                         tile_blend_kernel's bit for bit; any other pixel reads none of its tiles and is the bilinear upsample
+//                         by 2^d of `below`, a window of level j = k + d.  Along an axis, output coordinate P has
+//                         n = 2 P + 1 - 2^d, a = n >> (d + 1) (the floor, also for n < 0), f = (n - a 2^(d+1)) / 2^(d+1), exact
+//                         and never 0, and the sources clamp(a) and clamp(a + 1) in 0 .. N_j - 1; with lerp(p, q, f) =
+//                         p + f * (q - p), three fp32 operations that nothing contracts, the value is
+//                         lerp(lerp(s[r0][c0], s[r0][c1], fx), lerp(s[r1][c0], s[r1][c1], fx), fy).  The switch is hard.
 // All move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
 // scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
 #include "common.h"
@@ -268,6 +276,135 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const BlendArgs a) {
   }
 }
 
+// tile_blend_kernel's stores: the first nv of a thread's four pixels into row y from column x on of the window's output, fp32
+// [3, h, w] planes or uint8 [h, w, 3], wide where all four are written and the address is aligned.
+__device__ __forceinline__ void store_pixels(const BlendArgs& a, int y, int x, int nv, const float (&acc)[3][4]) {
+  const long at = (long)y * a.w + x;
+  if (a.out_u8) {
+    uint8_t* dst = a.out_u8 + 3 * at;
+    unsigned b[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) b[3 * k + ch] = k < nv ? tile_u8(acc[ch][k]) : 0u;
+    if (nv == 4 && ((uintptr_t)dst & 3) == 0) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        reinterpret_cast<uint32_t*>(dst)[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j)
+        if (j < 3 * nv) dst[j] = (uint8_t)b[j];
+    }
+    return;
+  }
+  const long plane = (long)a.h * a.w;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float* dst = a.out_f + ch * plane + at;
+    if (nv == 4 && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) dst[k] = acc[ch][k];
+    }
+  }
+}
+
+struct ComposeArgs {
+  BlendArgs b;                              // slot == nullptr: no tiles, and then the geometry is not looked at
+  const float* below;                       // fp32 [3, hb, wb]: the window (by0, bx0, hb, wb) of the level-j picture
+  int by0, bx0, hb, wb, Hj, Wj, d;
+  float inv;                                // 2^-(d + 1)
+};
+
+// Whether all of the 1, 2 or 4 tiles of a pixel at (ay, ax) have a slot >= 0.
+__device__ __forceinline__ bool tiles_there(const int32_t* slot, int C, const Axis ay, const Axis ax) {
+  const int32_t* row = slot + ay.t1 * C + ax.t1;
+  bool t = row[0] >= 0;
+  if (ax.two) t &= row[-1] >= 0;
+  if (ay.two) {
+    t &= row[-C] >= 0;
+    if (ax.two) t &= row[-C - 1] >= 0;
+  }
+  return t;
+}
+
+// Where coordinate P of level k reads level j = k + d along an axis of N source pixels: the two sources, as offsets into a
+// window that begins at o, and the weight of the second.
+struct Up {
+  int i0, i1;
+  float f;
+};
+
+__device__ __forceinline__ Up up_axis(int P, int d, float inv, int N, int o) {
+  const int n = 2 * P + 1 - (1 << d);
+  const int a = n >> (d + 1);                              // arithmetic: the floor for n < 0 as well
+  Up u;
+  u.f = (float)(n - a * (2 << d)) * inv;                   // an odd integer below 2^16 times a power of two: exact
+  u.i0 = min(max(a, 0), N - 1) - o;
+  u.i1 = min(max(a + 1, 0), N - 1) - o;
+  return u;
+}
+
+__device__ __forceinline__ float lerp_rn(float p, float q, float f) { return __fadd_rn(p, __fmul_rn(f, __fsub_rn(q, p))); }
+
+// tile_blend_kernel's thread layout.  Bit k of `sharp` says that pixel k has all its tiles and holds blend_run's value; the
+// others are read from `below`, a quarter of the output's size or less, one value at a time: neighbouring lanes share them.
+__global__ __launch_bounds__(256) void tile_compose_kernel(const ComposeArgs a) {
+  const BlendArgs& b = a.b;
+  const TileGeom& g = b.g;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= b.w || y >= b.h) return;
+  const int nv = min(4, b.w - x);
+  const int X = b.x0 + x, Y = b.y0 + y;
+  float acc[3][4];
+  unsigned sharp = 0;
+  if (b.slot) {
+    const Axis ay = tile_axis(Y, g.Sy, g.V, g.R);
+    const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
+    bool run = false;
+    if (nv == 4) {
+      const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
+      run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;       // one tile set for the four: one decision
+    }
+    if (run) {
+      if (tiles_there(b.slot, g.C, ay, ax0)) {
+        blend_run<4>(b, ay, ax0, acc, 0);
+        sharp = 15u;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k >= nv) continue;
+        const Axis ax = tile_axis(X + k, g.Sx, g.V, g.C);
+        if (!tiles_there(b.slot, g.C, ay, ax)) continue;
+        blend_run<1>(b, ay, ax, acc, k);
+        sharp |= 1u << k;
+      }
+    }
+  }
+  if (sharp != 15u) {
+    const Up uy = up_axis(Y, a.d, a.inv, a.Hj, a.by0);
+    const long plane = (long)a.hb * a.wb;
+    const float* r0 = a.below + (long)uy.i0 * a.wb;
+    const float* r1 = a.below + (long)uy.i1 * a.wb;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k >= nv || ((sharp >> k) & 1u)) continue;
+      const Up ux = up_axis(X + k, a.d, a.inv, a.Wj, a.bx0);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float* s0 = r0 + ch * plane;
+        const float* s1 = r1 + ch * plane;
+        acc[ch][k] = lerp_rn(lerp_rn(s0[ux.i0], s0[ux.i1], ux.f), lerp_rn(s1[ux.i0], s1[ux.i1], ux.f), uy.f);
+      }
+    }
+  }
+  store_pixels(b, y, x, nv, acc);
+}
+
 struct RefreshArgs {
   BlendArgs b;                              // tiles, slot, ramps, status, geometry; y0, x0, h, w: the box to visit
   const int32_t* dirty;
@@ -470,6 +607,53 @@ int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* 
   ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
   hipLaunchKernelGGL(tile_blend_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
   return check_launch("tile_blend_kernel");
+}
+
+int vam_tile_compose(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
+                     int tw, int V, int y0, int x0, int h, int w, const float* below, int by0, int bx0, int hb, int wb, int Hj, int Wj,
+                     int d, void* out, int out_u8, int32_t* status, void* stream) {
+  ComposeArgs a = {};
+  BlendArgs& b = a.b;
+  const bool none = !slot && n == 0;                                            // no tiles: th, tw and V are not looked at
+  if (none) {
+    VAM_REQUIRE(H >= 1 && W >= 1 && H <= kTileMaxSide && W <= kTileMaxSide, "vam_tile_compose: a picture of %d x %d: sides are 1 .. %d", H,
+                W, kTileMaxSide);
+  } else {
+    if (int rc = tile_geometry("vam_tile_compose", H, W, th, tw, V, &b.g)) return rc;
+    VAM_REQUIRE(tiles && slot && status, "vam_tile_compose: need tiles, slot and status (or slot = NULL and n = 0: no tiles)");
+    VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_compose: an overlap of %d needs the two ramp tables", V);
+    VAM_REQUIRE(n >= 1, "vam_tile_compose: a buffer of %d tiles", n);
+  }
+  VAM_REQUIRE(below && out, "vam_tile_compose: need below and out");
+  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && h <= H - y0 && w <= W - x0,
+              "vam_tile_compose: the window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", y0, x0, h, w, H, W);
+  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_compose: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
+  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_compose: a window of %d rows exceeds one launch", h);
+  VAM_REQUIRE(d >= 1 && d <= 15, "vam_tile_compose: d is 1 .. 15 (the level below is 2^d times coarser), got %d", d);
+  const int scale = 1 << d;
+  VAM_REQUIRE(Hj == (H + scale - 1) / scale && Wj == (W + scale - 1) / scale,
+              "vam_tile_compose: a level of %d x %d below a %d x %d picture at d = %d: it is ceil(H / 2^d) x ceil(W / 2^d) = %d x %d", Hj, Wj,
+              H, W, d, (H + scale - 1) / scale, (W + scale - 1) / scale);
+  VAM_REQUIRE(by0 >= 0 && bx0 >= 0 && hb >= 1 && wb >= 1 && hb <= Hj - by0 && wb <= Wj - bx0,
+              "vam_tile_compose: the window of below (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d level", by0, bx0, hb, wb,
+              Hj, Wj);
+  // the sources of the window: clamp(a(first)) .. clamp(a(last) + 1) along each axis, a(P) = floor((2 P + 1 - 2^d) / 2^(d+1))
+  auto lo = [&](int P, int N) { const int v = (2 * P + 1 - scale) >> (d + 1); return v < 0 ? 0 : v > N - 1 ? N - 1 : v; };
+  auto hi = [&](int P, int N) { const int v = ((2 * P + 1 - scale) >> (d + 1)) + 1; return v < 0 ? 0 : v > N - 1 ? N - 1 : v; };
+  const int sy0 = lo(y0, Hj), sy1 = hi(y0 + h - 1, Hj), sx0 = lo(x0, Wj), sx1 = hi(x0 + w - 1, Wj);
+  VAM_REQUIRE(by0 <= sy0 && sy1 < by0 + hb && bx0 <= sx0 && sx1 < bx0 + wb,
+              "vam_tile_compose: the window of below (y0 %d, x0 %d, h %d, w %d) does not cover the source window (y0 %d, x0 %d, h %d, w %d) "
+              "of the window (y0 %d, x0 %d, h %d, w %d) at d = %d",
+              by0, bx0, hb, wb, sy0, sx0, sy1 - sy0 + 1, sx1 - sx0 + 1, y0, x0, h, w, d);
+  b.tiles = tiles; b.slot = slot; b.w_lo = w_lo; b.w_hi = w_hi; b.status = status;
+  b.out_f = out_u8 ? nullptr : (float*)out;
+  b.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
+  b.n = n; b.y0 = y0; b.x0 = x0; b.h = h; b.w = w;
+  a.below = below; a.by0 = by0; a.bx0 = bx0; a.hb = hb; a.wb = wb; a.Hj = Hj; a.Wj = Wj; a.d = d;
+  a.inv = 1.0f / (float)(2 << d);
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0) + 12.0 * hb * wb);
+  hipLaunchKernelGGL(tile_compose_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("tile_compose_kernel");
 }
 
 int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32_t* dirty, const float* w_lo, const float* w_hi,

@@ -556,6 +556,51 @@ def pyramid_rd(model, image: torch.Tensor, qualities: Sequence[float], levels: O
     return rows
 
 
+def pyramid_fill_rd(model, image: torch.Tensor, cuts: Sequence[int], levels: Optional[int] = None, tile: int = 256, overlap: int = 32,
+                    marks: Optional[Sequence[float]] = None, coder=None, lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None,
+                    cache_tiles: Optional[int] = None):
+    """Bytes received against the quality of the FILLED level-0 view (``PyramidStream.view(fill=True)``):
+    the picture is coded once as a pyramid, and one receiver is fed from cut to cut (``cuts``: byte counts in ascending order,
+    each at least ``pyramid.need_bytes`` of the stream, those beyond its total meaning all of it).  One dict per cut: bytes,
+    bpp (8 * bytes / (H W)), psnr of the filled level-0 view against the picture, sharp (the share of level-0 pixels all of
+    whose tiles have arrived), chain (per level of the view, finest first: (level, tiles composed sharp, tiles that ran the
+    network), as counts) and dec_s (feeding the bytes and the view).  ``cache_tiles`` defaults to every tile of a level."""
+    import numpy as np
+    from . import pyramid as PY
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    cuts = [int(n) for n in cuts]
+    if not cuts or any(b < a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError(f"pyramid_fill_rd: cuts are one or more byte counts in ascending order, got {list(cuts)}")
+    rows = []
+    with torch.no_grad():
+        data = PY.encode(model, x, levels=levels, tile=tile, overlap=overlap, marks=marks, coder=coder, lanes=lanes, base_lanes=base_lanes,
+                         group=group)
+        need = PY.need_bytes(data)
+        if cuts[0] < need:
+            raise ValueError(f"pyramid_fill_rd: a cut of {cuts[0]} bytes: nothing decodes before need_bytes = {need}")
+        g = TL.grid(H, W, tile, overlap)
+        stream = PY.PyramidStream(model, coder=coder, group=group, cache_tiles=g["R"] * g["C"] if cache_tiles is None else cache_tiles)
+        want = x[:1].contiguous()
+        for n in (min(n, len(data)) for n in cuts):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stream.feed(data[len(stream.data):n])
+            x_hat = stream.view(level=0, fill=True)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            ready = stream.streams[0].tile_ready
+            sharp = np.zeros((H, W), dtype=bool)
+            if ready is not None:
+                sharp[:] = True
+                for r, c in zip(*np.nonzero(~ready)):          # a tile that has not arrived takes its whole extent with it
+                    sharp[r * g["Sy"]:r * g["Sy"] + g["th"], c * g["Sx"]:c * g["Sx"] + g["tw"]] = False
+            rows.append({"bytes": n, "bpp": 8.0 * n / (H * W), "psnr": compute_psnr(want, x_hat.unsqueeze(0)), "sharp": float(sharp.mean()),
+                         "chain": [(k, len(a), len(b)) for k, a, b in stream.last_chain], "dec_s": t1 - t0})
+    return rows
+
+
 def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
                        base_lanes: int = 1):
     """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE

@@ -884,6 +884,43 @@ def tile_refresh(tiles: torch.Tensor, slot: torch.Tensor, dirty: torch.Tensor, w
     L.check(rc, "vam_tile_refresh")
 
 
+def tile_compose(tiles: Optional[torch.Tensor], slot: Optional[torch.Tensor], w_lo: Optional[torch.Tensor], w_hi: Optional[torch.Tensor],
+                 H: int, W: int, overlap: int, window: Sequence[int], below: torch.Tensor, below_window: Sequence[int], shift: int,
+                 out: torch.Tensor, status: Optional[torch.Tensor]):
+    """:func:`tile_blend` of a window of a pyramid level whose tiles have not all arrived: a tile is
+    available when its ``slot`` is >= 0; a pixel all of whose tiles are available gets tile_blend's value, bit for bit; any
+    other pixel reads none of its tiles and is the bilinear upsample by 2^``shift`` (1 .. 15) of ``below``, fp32 [3, hb, wb]:
+    the window ``below_window`` = (by0, bx0, hb, wb) of the level ``shift`` levels coarser, ceil(H / 2^shift) x
+    ceil(W / 2^shift), which must cover ``pyramid.source_window(window, shift, ...)``.  ``tiles`` and ``slot`` None: no tiles,
+    every pixel comes from ``below`` (``overlap``, the ramps and ``status`` are then ignored).  One launch; capturable."""
+    y0, x0, h, w = (int(v) for v in window)
+    by0, bx0, hb, wb = (int(v) for v in below_window)
+    d = int(shift)
+    assert below.dtype == torch.float32 and below.is_contiguous() and tuple(below.shape) == (3, hb, wb) and below.is_cuda, \
+        (below.dtype, tuple(below.shape), (hb, wb))
+    assert (tiles is None) == (slot is None)
+    n = th = tw = 0
+    if tiles is not None:
+        assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.device == below.device
+        n, _, th, tw = tiles.shape
+        assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and slot.device == below.device
+        if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):   # the grid the library derives; anything else it refuses
+            grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
+            assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
+        for t in (w_lo, w_hi):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == below.device)
+        assert status is not None and status.dtype == torch.int32 and status.numel() == 1 and status.device == below.device
+    assert out.is_contiguous() and out.device == below.device
+    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, h, w)) or (out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3)), \
+        (out.dtype, tuple(out.shape), (h, w))
+    Hj, Wj = (-(-int(v) // (1 << d)) for v in (H, W)) if 1 <= d <= 15 else (0, 0)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    rc = L.load().vam_tile_compose(ptr(tiles), n, ptr(slot), ptr(w_lo), ptr(w_hi), int(H), int(W), th, tw, int(overlap), y0, x0, h, w,
+                                   below.data_ptr(), by0, bx0, hb, wb, Hj, Wj, d, out.data_ptr(), int(out.dtype == torch.uint8),
+                                   ptr(status), stream_ptr())
+    L.check(rc, "vam_tile_compose")
+
+
 HALVE_MODES = ("mean", "max")
 
 

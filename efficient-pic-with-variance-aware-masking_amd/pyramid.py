@@ -19,8 +19,22 @@ level is absent; u64 total), then the body: the level codestreams, COARSEST FIRS
 whole picture at some resolution.  Everything but :func:`encode`, :class:`PyramidDecoder`, and the views of
 :class:`PyramidStream` is host arithmetic and needs neither a model nor a GPU.
 
-Out of scope: scales that are no power of two and resampling; showing an upsampled coarser level where a finer one has not
-arrived; interleaving rounds across levels; coding a level as a residual of the coarser one; entropy-coded headers.
+Filled views: ``PyramidDecoder.decode(..., fill=True)`` and ``PyramidStream.view(..., fill=True)`` always
+give a whole picture at the level asked for: sharp where that level's tiles have arrived, filled from the next coarser level,
+upsampled, where they have not.  One rule for ``csrc/tiles.hip`` (vam_tile_compose), this module and ``tests/fill_ref.py``:
+upsampling by 2^d from level j = k + d has half-pixel centres; for row Y of level k, ``n = 2 Y + 1 - 2^d``, ``a = floor(n /
+2^(d+1))``, ``f_y = float(n - a 2^(d+1)) / 2^(d+1)`` (exact in fp32, never 0 or 1), the source rows ``r0 = clamp(a, 0, H_j - 1)``
+and ``r1 = clamp(a + 1, 0, H_j - 1)``, the columns likewise, and with ``lerp(p, q, f) = p + f * (q - p)`` (three fp32 operations)
+the value is ``lerp(lerp(s[r0][c0], s[r0][c1], f_x), lerp(s[r1][c0], s[r1][c1], f_x), f_y)``.  A level is USABLE when it is present
+and the bytes hold its own picture header whole; a tile is AVAILABLE when its head is whole (at ``mark`` / ``stage`` m: and its
+rounds 0 .. m).  ``F_k(window)`` composes level k's available tiles over the upsample of ``F_j(source_window(window))``, j the
+smallest usable level above k; a level that is not usable contributes no tiles; the coarsest usable level has nothing below
+it, and there a tile that is not available is a ValueError.  A pixel is sharp exactly when every tile the blend sums there is
+available, and the switch is hard.
+
+Out of scope: scales that are no power of two and resampling; feathering the seam between sharp and filled pixels; ``q=`` with
+``fill``; a filled ``Canvas``; interleaving rounds across levels; coding a level as a residual of the coarser one;
+entropy-coded headers.
 """
 from __future__ import annotations
 
@@ -93,6 +107,30 @@ def best_level(window, out_hw, H: int, W: int, n_levels: int) -> int:
         if h >= oh and w >= ow:
             best = k
     return best
+
+
+def source_window(window, d: int, Hj: int, Wj: int) -> Tuple[int, int, int, int]:
+    """The window (y0, x0, h, w) of level j = k + d, a picture of Hj x Wj, that upsampling by 2^d reads for the level-k
+    window ``window``: rows ``clamp(a(y0))`` .. ``clamp(a(y0 + h - 1) + 1)`` with ``a(Y) = floor((2 Y + 1 - 2^d) / 2^(d+1))`` and the
+    clamp to 0 .. Hj - 1, columns likewise (module docstring).  Host arithmetic only."""
+    d, Hj, Wj = TL._int(d, "source_window: d"), TL._int(Hj, "source_window: Hj"), TL._int(Wj, "source_window: Wj")
+    if not 1 <= d <= 15:
+        raise ValueError(f"source_window: d is 1 .. 15 (the levels between the two pictures), got {d}")
+    if Hj < 1 or Wj < 1:
+        raise ValueError(f"source_window: the coarser level is a picture of at least 1 x 1, got {Hj} x {Wj}")
+    try:
+        entries = list(window)
+    except TypeError:
+        entries = []
+    if len(entries) != 4:
+        raise ValueError(f"source_window: a window is (y0, x0, h, w), got {window!r}")
+    y0, x0, h, w = (TL._int(v, "source_window: a window entry") for v in entries)
+    if y0 < 0 or x0 < 0 or h < 1 or w < 1:
+        raise ValueError(f"source_window: a window is (y0, x0, h, w) with y0, x0 >= 0 and h, w >= 1, got {(y0, x0, h, w)}")
+    a = lambda P: (2 * P + 1 - (1 << d)) >> (d + 1)         # Python's shift floors negative numbers too
+    cl = lambda v, n: min(max(v, 0), n - 1)
+    ya, yb, xa, xb = cl(a(y0), Hj), cl(a(y0 + h - 1) + 1, Hj), cl(a(x0), Wj), cl(a(x0 + w - 1) + 1, Wj)
+    return ya, xa, yb - ya + 1, xb - xa + 1
 
 
 # ----------------------------------------------------------------------------------------------------------- codestream
@@ -376,10 +414,57 @@ def _not_ready(what: str, k: int, present: bool, ready: List[int]) -> ValueError
     return ValueError(f"{what}: level {k} does not decode: {why}; the ready levels are {ready}")
 
 
+def _fill(what: str, shapes, usable: List[int], composer, window, k: int, q, mark, stage, dtype, missing: int):
+    """``F_k(window)`` of the module docstring and its chain, finest to coarsest: [(level, the tiles composed sharp, those that
+    ran the network)].  ``usable``: the usable levels, ascending; ``composer(j)``: level j's ``tiled.PictureDecoder`` or
+    ``tiled.PictureStream``; ``missing``: the bytes still missing before the first level decodes.  A level whose window is
+    all available is not filled: it is the blend, and the chain ends there.  Intermediate pictures are fp32 [3, h, w]."""
+    import torch
+    from . import ops
+    if q is not None:
+        raise ValueError(f"{what}: q does not go with fill=True: whether a tile's bytes reach a quality is only known by decoding it; "
+                         "give mark, stage or neither")
+    window = TL._window({"H": shapes[k][0], "W": shapes[k][1]}, window, what)
+    chain: List = []
+
+    def level(j: int, win, out_dtype):
+        above = [i for i in usable if i > j]
+        obj = composer(j) if j in usable else None
+        if obj is None and not above:
+            raise ValueError(f"{what}: nothing to fill level {j} from: no level from {j} up holds its picture header"
+                             + (f"; {missing} bytes are missing before the coarsest level decodes" if missing else ""))
+        at = len(chain)
+        chain.append(None)
+        try:
+            if obj is not None and (not above or len(obj.available(win, mark, stage)) == len(TL.tiles_for(obj.grid, win))):
+                out = obj.compose(win, None, None, 0, mark=mark, stage=stage, dtype=out_dtype)       # nothing to fill: the blend
+            else:
+                d = above[0] - j
+                source = source_window(win, d, *shapes[above[0]])
+                below = level(above[0], source, None)
+                if obj is not None:
+                    out = obj.compose(win, below, source, d, mark=mark, stage=stage, dtype=out_dtype)
+                else:                                       # no tiles: the pure upsample, one launch
+                    out = torch.empty((3,) + win[2:], dtype=torch.float32, device=below.device) if out_dtype in (None, torch.float32) \
+                        else torch.empty(win[2:] + (3,), dtype=torch.uint8, device=below.device)
+                    ops.tile_compose(None, None, None, None, shapes[j][0], shapes[j][1], 0, win, below, source, d, out, None)
+        except ValueError as e:
+            raise (e if str(e).startswith(f"{what}: ") else ValueError(f"{what}: level {j}: {e}")) from e
+        chain[at] = (j, [], []) if obj is None else (j, list(obj.last_tiles), list(obj.last_decoded))
+        return out
+
+    if dtype not in (None, torch.float32, torch.uint8):
+        raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+    return level(k, window, dtype), chain
+
+
 class PyramidDecoder:
     """Decodes a pyramid codestream by level and window.  ``data``: any prefix of at least :func:`need_bytes`, or an
     :func:`extract`.  ``shape``: the true (H, W) of level 0; ``levels``: n_levels; ``shapes``: [(H_k, W_k)]; ``ready``: per level,
-    whether ``data`` holds enough of it to decode.  A level's ``tiled.PictureDecoder`` is made when it is first decoded."""
+    whether ``data`` holds enough of it to decode; ``usable``: whether it holds the level's own picture header, so that
+    ``decode(fill=True)`` takes the level's available tiles.  A level's ``tiled.PictureDecoder`` is made when it is first
+    decoded.  ``last_chain``: what the last decode composed, finest level first: [(level, the tiles composed sharp, the tiles
+    that ran the network)]."""
 
     def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
         EB._check_model(model)
@@ -388,11 +473,14 @@ class PyramidDecoder:
         self.shape, self.levels, self.shapes = (lay["H"], lay["W"]), lay["n_levels"], [lv["shape"] for lv in lay["levels"]]
         self.ready = [lv["ready"] for lv in lay["levels"]]
         self._present = [lv["present"] for lv in lay["levels"]]
+        self.usable = [lv["layout"] is not None for lv in lay["levels"]]
         if not any(self.ready):
             raise ValueError(f"PyramidDecoder: {len(self._d)} bytes end before any level decodes: {lay['need_bytes']} bytes are "
                              "needed for the coarsest level's tile heads")
         self._dec = {}
+        self._partial = {}                                  # the decoders of usable levels that are not ready (fill=True)
         self.last_tiles: List[Tuple[int, int]] = []
+        self.last_chain: List[Tuple[int, List[Tuple[int, int]], List[Tuple[int, int]]]] = []
 
     def decoder(self, level: int = 0) -> "TL.PictureDecoder":
         """The ``tiled.PictureDecoder`` of ``level`` on ``level_stream(data, level)``."""
@@ -405,14 +493,35 @@ class PyramidDecoder:
             self._dec[k] = TL.PictureDecoder(self.m, level_stream(self._d, k), coder=self.coder, group=self.group)
         return self._dec[k]
 
+    def _composer(self, k: int) -> "TL.PictureDecoder":
+        if self.ready[k]:
+            return self.decoder(k)
+        if k not in self._partial:
+            self._partial[k] = TL.PictureDecoder(self.m, level_stream(self._d, k), coder=self.coder, group=self.group, partial=True)
+        return self._partial[k]
+
     def decode(self, window=None, level: int = 0, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None,
-               dtype=None):
+               dtype=None, fill: bool = False):
         """``tiled.PictureDecoder(model, level_stream(data, level)).decode(window, q, mark, stage, dtype)``, bit for bit and
         error for error: ``window`` is in the coordinates of ``level`` (:func:`window_at` maps a level-0 window).  A level that
-        is absent or not ready is a ValueError that names it and the ready levels."""
-        dec = self.decoder(level)
-        out = dec.decode(window, q=q, mark=mark, stage=stage, dtype=dtype)
-        self.last_tiles = dec.last_tiles
+        is absent or not ready is a ValueError that names it and the ready levels.
+
+        ``fill=True`` (with ``mark``, ``stage`` or neither, never ``q``): always the whole window at
+        ``level``, for any level 0 .. n - 1: sharp where the level's tiles are available, elsewhere the upsample of the same
+        view of the next coarser usable level, down the chain (module docstring).  Once every tile of the window is
+        available it is the call without ``fill``, bit for bit.  ``last_chain`` records what was composed."""
+        if not fill:
+            dec = self.decoder(level)
+            out = dec.decode(window, q=q, mark=mark, stage=stage, dtype=dtype)
+            self.last_tiles, self.last_chain = dec.last_tiles, [(int(level), list(dec.last_tiles), list(dec.last_tiles))]
+            return out
+        what = "PyramidDecoder.decode"
+        k = TL._int(level, f"{what}: level")
+        if not 0 <= k < self.levels:
+            raise ValueError(f"{what}: level is 0 .. {self.levels - 1}, got {k}")
+        out, chain = _fill(what, self.shapes, [j for j in range(self.levels) if self.usable[j]], self._composer, window, k, q, mark, stage,
+                           dtype, 0)
+        self.last_tiles, self.last_chain = chain[0][1], chain
         return out
 
 
@@ -547,6 +656,7 @@ class PyramidStream:
         self.feed_state = PyramidFeed("PyramidStream", lambda k: _LevelStream(model, coder=coder, group=group, cache_tiles=cache_tiles))
         self.last_tiles: List[Tuple[int, int]] = []
         self.last_decoded: List[Tuple[int, int]] = []
+        self.last_chain: List[Tuple[int, List[Tuple[int, int]], List[Tuple[int, int]]]] = []
 
     ready = property(lambda self: self.feed_state.ready)
     ready_levels = property(lambda self: self.feed_state.ready_levels)
@@ -574,12 +684,29 @@ class PyramidStream:
         return fs.receivers[k]
 
     def view(self, window=None, level: int = 0, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None,
-             dtype=None):
+             dtype=None, fill: bool = False):
         """``streams[level].view(window, q, mark, stage, dtype)``: the window is in the coordinates of ``level``.  A level that
-        is absent or not ready is a ValueError that names it and the ready levels."""
-        st = self._level("PyramidStream.view", level)
-        out = st.view(window, q=q, mark=mark, stage=stage, dtype=dtype)
-        self.last_tiles, self.last_decoded = st.last_tiles, st.last_decoded
+        is absent or not ready is a ValueError that names it and the ready levels.
+
+        ``fill=True``: a fresh ``PyramidDecoder(everything fed so far).decode(window, level, mark=, stage=,
+        dtype=, fill=True)``, bit for bit, from the moment the coarsest level decodes: tiles turn sharp one by one as their
+        heads come in, and only the tiles a level has not cached run the network (``last_chain``: finest level first,
+        (level, the tiles composed sharp, the tiles that ran the network); ``last_tiles`` / ``last_decoded``: those of
+        ``level``).  Before that a ValueError states the bytes still missing."""
+        what = "PyramidStream.view"
+        if not fill:
+            st = self._level(what, level)
+            out = st.view(window, q=q, mark=mark, stage=stage, dtype=dtype)
+            self.last_tiles, self.last_decoded = st.last_tiles, st.last_decoded
+            self.last_chain = [(int(level), list(st.last_tiles), list(st.last_decoded))]
+            return out
+        fs = self.feed_state
+        if fs._p is None:
+            raise ValueError(f"{what}: nothing to decode yet: the header is not complete, {fs.need()} bytes are missing")
+        k = fs._p.level(level, what)
+        usable = [j for j, r in enumerate(fs.receivers) if r is not None and r.feed_state._s is not None]
+        out, chain = _fill(what, fs._p.shapes, usable, lambda j: fs.receivers[j], window, k, q, mark, stage, dtype, fs.need())
+        self.last_tiles, self.last_decoded, self.last_chain = chain[0][1], chain[0][2], chain
         return out
 
     def canvas(self, window=None, level: int = 0, dtype=None) -> "TL.Canvas":

@@ -47,7 +47,14 @@ calls: ``view(window, q | mark | stage)`` equals a fresh ``PictureDecoder(everyt
 and runs through the network only the tiles of the window whose own bytes grew since they were decoded, or that were never
 decoded at that level.  A :class:`Canvas` is a persistent output that ``refresh()`` re-blends only where such tiles
 contribute (vam_tile_refresh).  Out of scope: per-tile entropy resumption (a resumable ``EmbeddedDecoder`` kept per tile
-group), decoding tiles before all heads have arrived, and a priority order for stale tiles.
+group) and a priority order for stale tiles.
+
+Tiles before all heads have arrived: a tile is AVAILABLE when it is present and the bytes held hold its
+head whole (``PictureFeed.tile_ready`` / ``tile_rounds``, ``PictureDecoder(partial=True)``); at ``mark=m`` or ``stage=m`` it
+must hold the rounds 0 .. m whole as well.  ``compose(window, below, below_window, shift)`` of :class:`PictureDecoder` and
+:class:`PictureStream` decodes the available tiles of the window only and, with one vam_tile_compose launch, gives the
+blend where all tiles of a pixel are available and elsewhere the upsample of ``below``, a window of the same picture 2^shift
+times coarser (``vampic.pyramid`` chains the levels).
 """
 from __future__ import annotations
 
@@ -769,18 +776,87 @@ def _decode_window(what: str, model, coder, thresholds, tiles, stream_of, group:
     return buf
 
 
+def _tile_rounds(s: _Picture, n: int) -> np.ndarray:
+    """int64 [R, C]: the complete rounds that the first ``n`` bytes of the codestream hold of every tile (a piece of 0 bytes
+    is whole), -1 where the tile is absent or its head is not whole."""
+    held = s.held(n)
+    done = np.cumprod(held[1:] == s.size[1:], axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
+    return np.where(s.present & (held[0] == s.size[0]), done, -1).astype(np.int64).reshape(s.g["R"], s.g["C"])
+
+
+def _available(rounds: np.ndarray, tiles, level: Optional[int]) -> List[Tuple[int, int]]:
+    """Those of ``tiles`` whose head is whole and, at mark or stage ``level``, whose rounds 0 .. level are."""
+    least = 0 if level is None else level + 1
+    return [(r, c) for r, c in tiles if rounds[r, c] >= least]
+
+
+def _not_available(what: str, s: _Picture, window, rc, missing: int, level: Optional[int], rounds: np.ndarray) -> ValueError:
+    """The error of a window that needs tile ``rc`` where nothing coarser stands in for it."""
+    y0, x0, h, w = window
+    if not s.present[rc[0] * s.g["C"] + rc[1]]:
+        why = "which is absent from this codestream"
+    elif rounds[rc] < 0:
+        why = f"whose head has not arrived: {missing} bytes are missing before every tile's head is whole"
+    else:
+        why = f"which holds {int(rounds[rc])} whole rounds, {level + 1} are needed"
+    return ValueError(f"{what}: the window ({y0}, {x0}, {h}, {w}) needs tile ({rc[0]}, {rc[1]}), {why}, and there is no coarser "
+                      "level to fill it from")
+
+
+def _compose_out(what: str, g: dict, window, buf, slot: Optional[np.ndarray], ramps_on, below, below_window, shift, dtype):
+    """The output of one ``compose``: ``buf`` fp32 [n, 3, th, tw] and ``slot`` int32 [R, C] (both None: no tile is
+    available); ``below`` None: every tile of the window is available and the result is vam_tile_blend's.  ``ramps_on(dev)``
+    gives the blend ramps there."""
+    import torch
+    from . import _lib as L
+    from . import ops
+    y0, x0, h, w = window
+    if below is not None:
+        if not isinstance(below, torch.Tensor) or below.dtype != torch.float32 or below.dim() != 3 or below.shape[0] != 3 or not below.is_cuda:
+            raise ValueError(f"{what}: below is an fp32 tensor [3, hb, wb] on the device, got "
+                             f"{(below.dtype, tuple(below.shape)) if isinstance(below, torch.Tensor) else type(below).__name__}")
+        shift = _int(shift, f"{what}: shift")
+        if not 1 <= shift <= 15:
+            raise ValueError(f"{what}: shift is 1 .. 15 (below is 2^shift times coarser), got {shift}")
+        lower = {"H": -(-g["H"] // (1 << shift)), "W": -(-g["W"] // (1 << shift))}
+        below_window = _window(lower, below_window, f"{what}: below_window")
+        if tuple(below.shape[1:]) != below_window[2:]:
+            raise ValueError(f"{what}: below is {tuple(below.shape)}, its window {below_window} takes [3, {below_window[2]}, {below_window[3]}]")
+        if buf is not None and buf.device != below.device:
+            raise ValueError(f"{what}: below lies on {below.device}, the tiles on {buf.device}")
+    dev = buf.device if buf is not None else below.device
+    with torch.no_grad():
+        w_lo, w_hi = ramps_on(dev) if buf is not None and g["V"] else (None, None)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
+            else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        slot_dev = None if slot is None else torch.from_numpy(slot).to(dev)
+        if below is None:
+            ops.tile_blend(buf, slot_dev, w_lo, w_hi, g["H"], g["W"], g["V"], window, out, status)
+        else:
+            ops.tile_compose(buf, slot_dev, w_lo, w_hi, g["H"], g["W"], g["V"], window, below.detach().contiguous(), below_window, shift,
+                             out, status)
+        if int(status.item()):
+            raise L.VamError(f"{what}: the kernel met a slot beyond the tile buffer inside the window")
+    return out
+
+
 class PictureDecoder:
     """Decodes a picture codestream by window.  ``data``: any prefix of at least :func:`need_bytes`, or an :func:`extract`.
     ``shape``: the true (H, W); ``grid``: the geometry; ``rounds``: int [R, C], the complete rounds ``data`` holds of every
     tile, -1 where the tile is absent; ``scheduled`` and ``stages``: whether the picture is scheduled and
     its L, else False and 0.  Every :meth:`decode` decodes the tiles of its window afresh, ``group`` at a time
-    through ``embedded.EmbeddedDecoder`` (``coder`` is its), and blends them with one vam_tile_blend launch."""
+    through ``embedded.EmbeddedDecoder`` (``coder`` is its), and blends them with one vam_tile_blend launch.
 
-    def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
+    ``partial=True``: any prefix that holds the header is accepted; ``rounds`` is then -1 also for a tile
+    whose head is not whole, ``meta`` is None while no head is, and :meth:`decode` names such a tile when its window needs
+    it.  :meth:`compose` fills what is not available from a coarser picture."""
+
+    def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None, partial: bool = False):
         from . import progressive as P
         EB._check_model(model)
         d, s = _parse(data, "PictureDecoder")
-        if len(d) < s.need:
+        if not partial and len(d) < s.need:
             raise ValueError(f"PictureDecoder: {len(d)} bytes end before the heads of the tiles do: {s.need} bytes are needed, every "
                              "tile's z and base are decoded whole")
         self.meta = _tile_meta(d, s, "PictureDecoder")
@@ -788,11 +864,61 @@ class PictureDecoder:
         self.grid, self.shape = dict(s.g), (s.g["H"], s.g["W"])
         self.scheduled, self.stages = s.stages > 0, s.stages                     # version 3: rounds are stages
         self.group = _check_group(group, s.g["th"], s.g["tw"], "PictureDecoder")
-        whole = (s.held(len(d))[1:] == s.size[1:])                               # [nr, R C]: a piece of 0 bytes is whole
-        done = np.cumprod(whole, axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
-        self.rounds = np.where(s.present, done, -1).astype(np.int64).reshape(s.g["R"], s.g["C"])
+        self.rounds = _tile_rounds(s, len(d))                                    # from need_bytes on every present tile's head is whole
+        self.partial = bool(partial)
         self.last_tiles: List[Tuple[int, int]] = []
+        self.last_decoded: List[Tuple[int, int]] = []
         self._ramps = None
+
+    def _ramps_at(self, dev):
+        self._ramps = _ramps_on(self._ramps, self.grid["V"], dev)
+        return self._ramps
+
+    def _level(self, what: str, mark, stage) -> Tuple[Optional[int], Optional[int]]:
+        """(mark, stage) of a call without q, checked as :meth:`decode` checks them; before any head is whole the marks are
+        not known, and no tile is available anyway."""
+        stage = _stage_of(what, self.scheduled, self.stages, None, mark, stage)
+        return (None if self.meta is None else _mark_of(what, self.meta["marks"], self._s.thresholds, None, mark)), stage
+
+    def available(self, window=None, mark: Optional[int] = None, stage: Optional[int] = None) -> List[Tuple[int, int]]:
+        """Those of ``tiles_for(window)`` that are available: present, the head whole and, at ``mark`` or ``stage`` m, the
+        rounds 0 .. m whole."""
+        mark, stage = self._level("PictureDecoder.available", mark, stage)
+        tiles = tiles_for(self.grid, _window(self.grid, window, "PictureDecoder.available"))
+        return _available(self.rounds, tiles, stage if stage is not None else mark)
+
+    def compose(self, window, below, below_window, shift, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
+        """The window like :meth:`decode` (everything held, a ``mark`` or a ``stage``; no ``q``: whether a tile's bytes reach
+        a quality is only known by decoding it), from the AVAILABLE tiles alone (:meth:`available`; ``last_tiles``, which are
+        also ``last_decoded``): a pixel all of whose tiles are available is :meth:`decode`'s, bit for bit; any other is the
+        upsample by 2^``shift`` of ``below``, fp32 [3, hb, wb] on the device, the window ``below_window`` of the same picture
+        ``shift`` levels coarser, which must cover ``pyramid.source_window(window, shift, ...)``.  One vam_tile_compose launch.
+        ``below`` = None: nothing stands in, and a tile that is not available is a ValueError that names it."""
+        import torch
+        what = "PictureDecoder.compose"
+        g, s = self.grid, self._s
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        mark, stage = self._level(what, mark, stage)
+        level = stage if stage is not None else mark
+        window = _window(g, window, what)
+        wanted = tiles_for(g, window)
+        tiles = _available(self.rounds, wanted, level)
+        if below is None and len(tiles) < len(wanted):
+            rc = next(rc for rc in wanted if rc not in tiles)
+            raise _not_available(what, s, window, rc, max(0, s.need - len(self._d)), level, self.rounds)
+        buf = slot = None
+        if tiles:
+            with torch.no_grad():
+                buf = _decode_window(what, self.m, self.coder, s.thresholds, tiles, lambda r, c: s.stream(self._d, r * g["C"] + c),
+                                     self.group, g, None, mark, stage)
+            slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
+            for i, (r, c) in enumerate(tiles):
+                slot[r, c] = i
+        out = _compose_out(what, g, window, buf, slot, self._ramps_at, below, below_window, shift, dtype)
+        self.last_tiles = self.last_decoded = tiles
+        return out
 
     def decode(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
         """The window (y0, x0, h, w) of the picture (None: all of it): fp32 [3, h, w], or uint8 [h, w, 3] for
@@ -818,8 +944,15 @@ class PictureDecoder:
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
+        if self.partial and len(self._d) < s.need:          # a prefix that ends inside the heads: the tiles the window needs must be whole
+            win = _window(g, window, "PictureDecoder.decode")
+            for r, c in tiles_for(g, win):
+                if s.present[r * g["C"] + c] and self.rounds[r, c] < 0:
+                    raise ValueError(f"PictureDecoder.decode: the window {win} needs tile ({r}, {c}), whose head has not arrived: "
+                                     f"{s.need - len(self._d)} bytes are missing before every tile's head is whole")
         stage = _stage_of("PictureDecoder.decode", self.scheduled, self.stages, q, mark, stage)
-        mark = _mark_of("PictureDecoder.decode", self.meta["marks"], s.thresholds, q, mark)
+        if self.meta is not None:                           # None: a partial prefix without a whole head, whose tiles are refused below
+            mark = _mark_of("PictureDecoder.decode", self.meta["marks"], s.thresholds, q, mark)
         y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
         tiles = tiles_for(g, (y0, x0, h, w))
         for r, c in tiles:
@@ -855,8 +988,9 @@ class PictureFeed:
     before that, as far as the bytes tell.  Once the header is complete (it is parsed once, by the parser of
     :func:`layout`): ``shape``, ``grid``, ``scheduled``, ``stages``; ``meta``: the tiles' own layout as far as heads are
     whole (``PictureDecoder.meta`` once ready); and once ready ``rounds`` (``PictureDecoder.rounds``) and ``held`` int [R, C],
-    the bytes present of each tile's own codestream, -1 where the tile is absent.  ``fed_tiles``: the (r, c), in raster
-    order, whose held bytes grew in the last feed.  ``data``: everything fed so far."""
+    the bytes present of each tile's own codestream, -1 where the tile is absent.  Per tile, from the header on:
+    ``tile_ready`` bool [R, C] and ``tile_rounds`` int [R, C].  ``fed_tiles``: the (r, c), in raster order, whose held bytes
+    grew in the last feed.  ``data``: everything fed so far."""
 
     def __init__(self, what: str = "PictureFeed"):
         self._what = what
@@ -921,6 +1055,18 @@ class PictureFeed:
         whole = (s.held(len(self._buf))[1:] == s.size[1:])                       # as PictureDecoder: a piece of 0 bytes is whole
         done = np.cumprod(whole, axis=0).sum(0) if s.nr else np.zeros(s.present.size, dtype=np.int64)
         return np.where(s.present, done, -1).astype(np.int64).reshape(s.g["R"], s.g["C"])
+
+    @property
+    def tile_rounds(self) -> Optional[np.ndarray]:
+        """int [R, C] once the header is complete (None before): the complete rounds held of every tile, -1 where the tile
+        is absent or its head is not whole yet.  Once ``ready`` it is ``rounds``."""
+        return None if self._s is None else _tile_rounds(self._s, len(self._buf))
+
+    @property
+    def tile_ready(self) -> Optional[np.ndarray]:
+        """bool [R, C] once the header is complete (None before): the tile is present and its head is whole in the bytes
+        held, so it decodes."""
+        return None if self._s is None else self.tile_rounds >= 0
 
     def tile_bytes(self, r: int, c: int) -> bytes:
         """Tile (r, c)'s embedded codestream as far as the fed bytes hold it (:func:`tile_stream`)."""
@@ -1023,6 +1169,8 @@ class PictureStream:
     meta = property(lambda self: self.feed_state.meta)
     rounds = property(lambda self: self.feed_state.rounds)
     held = property(lambda self: self.feed_state.held)
+    tile_ready = property(lambda self: self.feed_state.tile_ready)
+    tile_rounds = property(lambda self: self.feed_state.tile_rounds)
     fed_tiles = property(lambda self: self.feed_state.fed_tiles)
     data = property(lambda self: self.feed_state.data)
 
@@ -1047,18 +1195,28 @@ class PictureStream:
         self._entries, self._held_key = {}, {}
         self._free = list(range(self.cache_tiles)) if self._pool is not None else []
 
-    def _update(self, what: str, window, q, mark, stage):
+    def _update(self, what: str, window, q, mark, stage, below=False):
         """Brings the tiles of ``window`` into the cache at the level (q, mark, stage).  Returns (window, its tiles, the level
-        key or None, slot int32 [R, C], generation int64 [R, C]); both tables are -1 outside the window's tiles."""
+        key or None, slot int32 [R, C], generation int64 [R, C]); both tables are -1 outside the window's tiles.  ``below``
+        (:meth:`compose`; None: nothing stands in): the header suffices, and its tiles are the AVAILABLE ones of the window."""
         import torch
         fs = self.feed_state
-        if not fs.ready:
+        partial = below is not False
+        if partial and fs._s is None:
+            raise ValueError(f"{what}: nothing to decode yet: the header is not complete, {fs.need()} bytes are missing")
+        if not partial and not fs.ready:
             raise ValueError(f"{what}: nothing to decode yet: {fs.need()} bytes are missing before every tile's head is whole")
         s, g = fs._s, fs._s.g
         stage = _stage_of(what, s.stages > 0, s.stages, q, mark, stage)
-        mark = _mark_of(what, fs.meta["marks"], s.thresholds, q, mark)
+        if fs.meta is not None:                             # None: no head is whole yet (compose), and no tile is available
+            mark = _mark_of(what, fs.meta["marks"], s.thresholds, q, mark)
         y0, x0, h, w = _window(g, window, what)
         tiles = tiles_for(g, (y0, x0, h, w))
+        if partial:
+            rounds, wanted, m = fs.tile_rounds, tiles, stage if stage is not None else mark
+            tiles = _available(rounds, wanted, m)
+            if below is None and len(tiles) < len(wanted):
+                raise _not_available(what, s, (y0, x0, h, w), next(rc for rc in wanted if rc not in tiles), fs.need(), m, rounds)
         for r, c in tiles:
             if not s.present[r * g["C"] + c]:
                 raise ValueError(f"{what}: the window ({y0}, {x0}, {h}, {w}) needs tile ({r}, {c}), which is absent "
@@ -1131,6 +1289,33 @@ class PictureStream:
             if int(status.item()):
                 raise L.VamError(f"{what}: vam_tile_blend met an absent tile inside the window")
         return out
+
+    def available(self, window=None, mark: Optional[int] = None, stage: Optional[int] = None) -> List[Tuple[int, int]]:
+        """``PictureDecoder(model, everything fed so far, partial=True).available(window, mark, stage)``; [] before the header
+        is complete."""
+        fs, what = self.feed_state, "PictureStream.available"
+        if fs._s is None:
+            return []
+        s = fs._s
+        stage = _stage_of(what, s.stages > 0, s.stages, None, mark, stage)
+        if fs.meta is not None:
+            mark = _mark_of(what, fs.meta["marks"], s.thresholds, None, mark)
+        return _available(fs.tile_rounds, tiles_for(s.g, _window(s.g, window, what)), stage if stage is not None else mark)
+
+    def compose(self, window, below, below_window, shift, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
+        """``PictureDecoder(model, everything fed so far, partial=True).compose(...)``, bit for bit, from
+        the header on: the available tiles of the window come from the cache (``last_tiles``), only those not cached at that
+        level run the network (``last_decoded``), and one vam_tile_compose launch fills the rest from ``below``.  The cache's
+        keys, eviction and ``cache_tiles`` refusal are :meth:`view`'s."""
+        import torch
+        what = "PictureStream.compose"
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        window, tiles, _, slot, _ = self._update(what, window, None, mark, stage, below)
+        g = self.feed_state._s.g
+        ramps_at = lambda dev: self._blend_inputs()
+        return _compose_out(what, g, window, self._pool if tiles else None, slot if tiles else None, ramps_at, below, below_window, shift, dtype)
 
     def canvas(self, window=None, dtype=None) -> "Canvas":
         """A persistent output of ``window`` (None: the picture) that :meth:`Canvas.refresh` keeps equal to :meth:`view`."""

@@ -432,7 +432,25 @@ int vam_threshold_counts(const uint32_t* keys, int T, int n_slice, int n, const 
  * be absent); otherwise all of its tiles must be present (else *status = 1, as vam_tile_blend) and it gets vam_tile_blend's
  * value, bit for bit.  Pixels outside the box are never touched.  A canvas window outside the picture, a box outside the
  * canvas window and a box of more than 4 * 65535 rows are VAM_EINVAL and launch nothing.  No atomics, no allocation,
- * capturable. */
+ * capturable.
+ * vam_tile_compose: vam_tile_blend of a window of pyramid level k whose tiles have not all arrived.  A
+ * tile is available when its slot is >= 0; a pixel is sharp exactly when every tile vam_tile_blend would sum there (1, 2 or 4)
+ * is available, and it gets vam_tile_blend's value, bit for bit (an available slot >= n sets *status = 1 and skips the term,
+ * as there).  Any other pixel reads none of its tiles and is the upsample of `below`, fp32 [3, hb, wb]: the window by0, bx0, hb,
+ * wb of the picture of level j = k + d, Hj x Wj with Hj = ceil(H / 2^d), Wj = ceil(W / 2^d), 1 <= d <= 15.  For row Y:
+ * n = 2 Y + 1 - 2^d, a = floor(n / 2^(d+1)), fy = float(n - a 2^(d+1)) / 2^(d+1) (exact, never 0 or 1), the source rows
+ * r0 = clamp(a, 0, Hj - 1) and r1 = clamp(a + 1, 0, Hj - 1); columns likewise; with lerp(p, q, f) = p + f * (q - p), a subtract,
+ * a multiply and an add in fp32 that nothing contracts,
+ *   out = lerp(lerp(s[r0][c0], s[r0][c1], fx), lerp(s[r1][c0], s[r1][c1], fx), fy):
+ * a constant stays constant bit for bit, the replicated edge is exact.  Only finite inputs are specified.  The switch between
+ * sharp and filled pixels is hard.  slot = NULL with n = 0 means no tiles: every pixel comes from below; tiles, the ramps, th,
+ * tw, V and status are then not looked at.  The value does not depend on the path a lane takes.  VAM_EINVAL, nothing launched:
+ * a null below or out, d outside 1 .. 15, an Hj or Wj that is not ceil(. / 2^d), a window of below that does not lie inside
+ * the level or does not cover the window's sources (rows clamp(a(y0)) .. clamp(a(y0 + h - 1) + 1), columns likewise), and
+ * everything vam_tile_blend refuses.  No atomics, no allocation, capturable. */
+int vam_tile_compose(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
+                     int tw, int V, int y0, int x0, int h, int w, const float* below, int by0, int bx0, int hb, int wb, int Hj, int Wj,
+                     int d, void* out, int out_u8, int32_t* status, void* stream);
 int vam_tile_extract(const float* image, int H, int W, int th, int tw, int V, const int32_t* coords, int n, float* out,
                      void* stream);
 int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,

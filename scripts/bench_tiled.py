@@ -42,11 +42,18 @@ whole-picture view (the coarsest level), beside a new ``tiled.PictureStream`` fe
 and vam_picture_halve alone on the picture, both modes (HIP events over 50 launches, five times: median, min, max), beside a
 ``copy_`` of as many bytes as it READS.
 
+``--pyramid --fill`` adds ``"fill"`` to it: vam_tile_compose alone on a 512 x 768 window in the middle of
+the picture, fp32 and uint8, at d = 1 and d = 3 with all tiles, half of them (a checkerboard) and none available, beside
+vam_tile_blend of that window and a device ``copy_`` of as many bytes as it writes -- each a few microseconds, so 200 launches
+are captured into one graph and its replays are timed by HIP events (five times: median, min, max): events around single
+launches would time the host's enqueue; and the first picture at level-0 resolution: a new ``PyramidStream`` fed ``need_bytes`` and viewed with
+``fill=True``, beside a new one fed up to the last of level 0's heads and viewed without: bytes and wall time of each.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
-                                  [--schedule roi] [--stream] [--pan] [--pyramid]
+                                  [--schedule roi] [--stream] [--pan] [--pyramid [--fill]]
 """
 import argparse
 import json
@@ -86,6 +93,27 @@ def event_us(fn, iters=50):
     e1.record()
     torch.cuda.synchronize()
     return 1e3 * e0.elapsed_time(e1) / iters
+
+
+def graph_us(fn, iters=200, replays=5):
+    """Microseconds per call of ``fn`` with the host out of the way: ``iters`` calls captured into one graph, which is
+    replayed ``replays`` times between two HIP events after one replay of warm-up.  For kernels of a few microseconds, where
+    ``event_us`` would measure how fast the host enqueues."""
+    fn()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(iters):
+            fn()
+    graph.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(replays):
+        graph.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / (iters * replays)
 
 
 def overhead(data, TL):
@@ -341,7 +369,58 @@ def pyramid(a, net, x, g, kw, TL, PY, ops):
                            "mean_us": spread([event_us(lambda: ops.picture_halve(x, "mean", out=dst)) for _ in range(5)]),
                            "max_us": spread([event_us(lambda: ops.picture_halve(x, "max", out=dst)) for _ in range(5)]),
                            "copy_in_bytes_us": spread([event_us(lambda: like.copy_(x)) for _ in range(5)])}
+    if a.fill:
+        out["fill"] = fill(a, net, data, lay, g, TL, PY, ops)
     return out
+
+
+def fill(a, net, data, lay, g, TL, PY, ops):
+    """The ``--fill`` section: see the module docstring."""
+    H, W, R, C, dev = g["H"], g["W"], g["R"], g["C"], next(net.parameters()).device
+    h, w = min(512, H), min(768, W)
+    win = ((H - h) // 2, (W - w) // 2, h, w)
+    tiles = torch.rand((R * C, 3, g["th"], g["tw"]), dtype=torch.float32, device=dev)
+    every = torch.arange(R * C, dtype=torch.int32).view(R, C)
+    half = torch.where((torch.arange(R)[:, None] + torch.arange(C)[None, :]) % 2 == 0, every, torch.full_like(every, -1)).to(dev)
+    every = every.to(dev)
+    w_lo, w_hi = (torch.from_numpy(t).to(dev) if g["V"] else None for t in TL.ramps(g["V"]))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    kernel = {"window": list(win), "window_tiles": len(TL.tiles_for(g, win)), "timing": "200 launches in one graph, 5 replays, 5 times"}
+    for kind, dst in (("f32", torch.empty((3, h, w), dtype=torch.float32, device=dev)), ("u8", torch.empty((h, w, 3), dtype=torch.uint8, device=dev))):
+        src = torch.empty_like(dst)
+        kernel[f"out_{kind}_bytes"] = dst.numel() * dst.element_size()
+        kernel[f"copy_{kind}_us"] = spread([graph_us(lambda: dst.copy_(src)) for _ in range(5)])
+        kernel[f"blend_{kind}_us"] = spread([graph_us(lambda: ops.tile_blend(tiles, every, w_lo, w_hi, H, W, g["V"], win, dst, status))
+                                             for _ in range(5)])
+        for d in (1, 3):
+            Hj, Wj = -(-H // (1 << d)), -(-W // (1 << d))
+            bwin = PY.source_window(win, d, Hj, Wj)
+            below = torch.rand((3,) + bwin[2:], dtype=torch.float32, device=dev)
+            for name, slot in (("all", every), ("half", half), ("none", None)):
+                kernel[f"compose_{kind}_d{d}_{name}_us"] = spread([graph_us(lambda: ops.tile_compose(
+                    None if slot is None else tiles, slot, w_lo, w_hi, H, W, g["V"], win, below, bwin, d, dst, status)) for _ in range(5)])
+    assert int(status.item()) == 0
+    heads0 = lay["levels"][0]["offset"] + lay["levels"][0]["layout"]["need_bytes"]
+    filled, plain, chain = [], [], None
+    for i in range(a.warmup + a.reps):
+        def first_filled():
+            st = PY.PyramidStream(net, coder=a.coder)
+            st.feed(data[:lay["need_bytes"]])
+            return st, st.view(level=0, fill=True)
+
+        def first_plain():
+            st = PY.PyramidStream(net, coder=a.coder, cache_tiles=R * C)
+            st.feed(data[:heads0])
+            return st.view(level=0)
+        t, (st, got) = timed(first_filled)
+        chain = [(k, len(s_), len(n_)) for k, s_, n_ in st.last_chain]
+        assert tuple(got.shape) == (3, H, W)
+        u, _ = timed(first_plain)
+        if i >= a.warmup:
+            filled.append(t)
+            plain.append(u)
+    return {"kernel": kernel, "first_level0_picture": {"fill_bytes": lay["need_bytes"], "fill_ms": spread(filled), "fill_chain": chain,
+                                                        "plain_bytes": heads0, "plain_ms": spread(plain)}}
 
 
 def main():
@@ -360,7 +439,10 @@ def main():
     ap.add_argument("--stream", action="store_true")
     ap.add_argument("--pan", action="store_true")
     ap.add_argument("--pyramid", action="store_true")
+    ap.add_argument("--fill", action="store_true")
     a = ap.parse_args()
+    if a.fill and not a.pyramid:
+        ap.error("--fill is a part of --pyramid")
     from bench import build_model
     import vampic
     from vampic import embedded as EB, evaluate as EV, ops, pyramid as PY, tiled as TL
