@@ -57,7 +57,6 @@ import math
 import os
 import pickle
 import struct
-import zlib
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence
 
@@ -65,6 +64,7 @@ import numpy as np
 import torch
 
 from . import progressive as P
+from .framing import MAX_HEADER, PREAMBLE_BYTES, Frame, check_total, chunk_view, same as _same, view as _view
 from .progressive import Q_LIST
 
 FORMAT = "embedded-1"
@@ -473,17 +473,6 @@ def truncate(container, q: Optional[float] = None, max_bytes: Optional[int] = No
     return out
 
 
-def _same(a, b) -> bool:
-    """Equality of container entries: dicts and sequences entry by entry (a list equals a tuple), arrays by value."""
-    if isinstance(a, dict) and isinstance(b, dict):
-        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
-    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
-        return np.array_equal(np.asarray(a), np.asarray(b))
-    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
-        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
-    return a == b
-
-
 def delta(longer, shorter) -> List[bytes]:
     """Per slice, the bytes of ``longer`` that follow ``shorter``: what a transmitter sends to a receiver that holds
     ``shorter`` (:meth:`EmbeddedDecoder.extend`).  On the host alone, like :func:`truncate`.  ``shorter`` must be a cut of
@@ -515,11 +504,11 @@ def delta(longer, shorter) -> List[bytes]:
 # ------------------------------------------------------------------------------------------------ codestreams (section 9u)
 STREAM_MAGIC = b"VAMe"
 STREAM_VERSION = 1
-_PREAMBLE = struct.Struct("<4sHHII")       # magic, version, reserved (0), bytes of the header, CRC-32 of the header
-PREAMBLE_BYTES = _PREAMBLE.size            # 16
 _FIXED = struct.Struct("<BBBBHHHHI")       # format digit, flags, lanes, base_lanes, shape[0], shape[1], ns, L, bytes of z
 _FLAG_SCHEDULED = 1
-_MAX_HEADER = 1 << 24                      # far above any header: 32 marks of 65535 slices stay below it
+FRAME = Frame(STREAM_MAGIC, "an embedded codestream", "codestream", (STREAM_VERSION,), range(_FIXED.size + 8, MAX_HEADER + 1),
+              f"a header takes {_FIXED.size + 8} .. {MAX_HEADER}")
+_seal = FRAME.seal                         # the preamble of a header and the header
 
 
 def _format_of(K: int, Kb: int, scheduled: bool) -> str:
@@ -611,8 +600,8 @@ def to_bytes(container) -> bytes:
             raise ValueError(f"to_bytes: side_bytes is 8 per level and 1 per index entry, {8 * lv.size + ix.size}, got {c['side_bytes']!r}")
         parts += [struct.pack("<HH", lv.size, ix.shape[0]), lv.astype("<f8").tobytes(), np.ascontiguousarray(ix).tobytes()]
     hlen = sum(len(p) for p in parts) + 8
-    if hlen > _MAX_HEADER:
-        raise ValueError(f"to_bytes: the header would take {hlen} bytes, the limit is {_MAX_HEADER}")
+    if hlen > MAX_HEADER:
+        raise ValueError(f"to_bytes: the header would take {hlen} bytes, the limit is {MAX_HEADER}")
     parts.append(struct.pack("<Q", PREAMBLE_BYTES + hlen + int(lens.sum())))
     header = b"".join(parts)
     out = [_seal(header), bytes(z[0])] + [bytes(s[0]) for s in base]
@@ -621,22 +610,14 @@ def to_bytes(container) -> bytes:
     return b"".join(out)
 
 
-def _seal(header: bytes) -> bytes:
-    """The preamble of ``header`` and the header: magic, version, its length and its CRC-32."""
-    return _PREAMBLE.pack(STREAM_MAGIC, STREAM_VERSION, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF) + header
-
-
 class _Stream:
     """A parsed codestream header: the fields, and the byte arithmetic of the body that follows from them."""
 
     def __init__(self, d, what: str):
-        """Parses ``d`` (a memoryview that holds at least the header, as :func:`_header_end` says).  ValueError names what
+        """Parses ``d`` (bytes that hold at least the header, or ``FRAME.open`` says what is needed).  ValueError names what
         is wrong; nothing beyond the stated header length is read."""
         from . import bitstream as bs
-        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
-        end = PREAMBLE_BYTES + hlen
-        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
-            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        d, _, hlen, end = FRAME.open(d, what)
         self.header_end, at = end, PREAMBLE_BYTES
 
         def take(dtype, n):
@@ -736,36 +717,9 @@ class _Stream:
         return None
 
 
-def _view(data, what: str):
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise ValueError(f"{what}: a codestream is a bytes-like object, got {type(data).__name__}")
-    d = memoryview(data)
-    return d if d.format == "B" and d.ndim == 1 and d.contiguous else memoryview(bytes(d))
-
-
-def _header_end(d, what: str) -> Optional[int]:
-    """The byte at which the header of ``d`` ends, read from its preamble; None while the preamble is incomplete.  A wrong
-    magic, version or header length is a ValueError."""
-    if len(d) < PREAMBLE_BYTES:
-        return None
-    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
-    if magic != STREAM_MAGIC:
-        raise ValueError(f"{what}: not an embedded codestream: it begins with {bytes(magic)!r}, not with the magic {STREAM_MAGIC!r}")
-    if version != STREAM_VERSION or reserved:
-        raise ValueError(f"{what}: codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this reader knows "
-                         f"version {STREAM_VERSION}")
-    if not _FIXED.size + 8 <= hlen <= _MAX_HEADER:
-        raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 8} .. {_MAX_HEADER}")
-    return PREAMBLE_BYTES + hlen
-
-
 def _parse(data, what: str):
     """(view, parsed header) of a codestream that holds its whole header; too few bytes are a ValueError with the need."""
     d = _view(data, what)
-    end = _header_end(d, what)
-    if end is None or len(d) < end:
-        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
-                         "before it can be read")
     return d, _Stream(d, what)
 
 
@@ -774,9 +728,7 @@ def need_bytes(data) -> int:
     tells: the preamble's size while that is incomplete, the header's end while the header is, then the end of the base.
     A damaged preamble or header is a ValueError."""
     d = _view(data, "need_bytes")
-    end = _header_end(d, "need_bytes")
-    if end is None:
-        return PREAMBLE_BYTES
+    end = FRAME.need_header(d, "need_bytes")
     return end if len(d) < end else _Stream(d, "need_bytes").base_end
 
 
@@ -809,8 +761,7 @@ def _container_of(s: "_Stream", d, n: int) -> dict:
 def _check_length(s: "_Stream", n: int, what: str):
     if n < s.base_end:
         raise ValueError(f"{what}: {n} bytes end before z and the base do: {s.base_end} bytes are needed, they are decoded whole")
-    if n > s.total:
-        raise ValueError(f"{what}: {n} bytes, the header states a total of {s.total}: {n - s.total} bytes follow the codestream")
+    check_total(n, s.total, what)
 
 
 def from_bytes(data) -> dict:
@@ -1259,16 +1210,12 @@ class StreamDecoder:
             raise ValueError(f"StreamDecoder.feed: expected {self.B} bytes-like objects, one per image") from e
         if len(chunks) != self.B:
             raise ValueError(f"StreamDecoder.feed: expected {self.B} chunks, one per image, got {len(chunks)}")
-        for b, ch in enumerate(chunks):
-            if not isinstance(ch, (bytes, bytearray, memoryview)):
-                raise ValueError(f"StreamDecoder.feed: image {b}: expected bytes, got {type(ch).__name__}")
-        chunks = [_view(ch, "StreamDecoder.feed") for ch in chunks]             # bytes, whatever the item size of a memoryview
+        chunks = [chunk_view(ch, f"StreamDecoder.feed: image {b}") for b, ch in enumerate(chunks)]
         hdr, before = list(self._hdr), (list(self._hdr), [len(buf) for buf in self._buf])
         for b, ch in enumerate(chunks):                     # everything is checked before anything is kept
             if hdr[b] is None:
                 d = memoryview(bytes(self._buf[b]) + bytes(ch))
-                end = _header_end(d, f"StreamDecoder.feed: image {b}")
-                if end is not None and len(d) >= end:
+                if FRAME.whole(d, f"StreamDecoder.feed: image {b}"):
                     hdr[b] = _Stream(d, f"StreamDecoder.feed: image {b}")
                     if hdr[b].ns != self.m.ns0:
                         raise ValueError(f"StreamDecoder.feed: image {b}: its codestream holds {hdr[b].ns} slices, a container of this "
@@ -1277,9 +1224,8 @@ class StreamDecoder:
                     why = hdr[b].same_batch(other) if other is not None else None
                     if why:
                         raise ValueError(f"StreamDecoder.feed: image {b} does not belong to this batch: {why}; decode it separately")
-            if hdr[b] is not None and len(self._buf[b]) + len(ch) > hdr[b].total:
-                raise ValueError(f"StreamDecoder.feed: image {b}: {len(self._buf[b]) + len(ch)} bytes, its header states a total of "
-                                 f"{hdr[b].total}: bytes follow the codestream")
+            if hdr[b] is not None:
+                check_total(len(self._buf[b]) + len(ch), hdr[b].total, f"StreamDecoder.feed: image {b}", per_image=True)
         self._hdr = hdr
         for buf, ch in zip(self._buf, chunks):
             buf += ch

@@ -12,7 +12,7 @@ reduced alongside with the maximum of the four.  Pixel (y, x) of level k stands 
 and the columns likewise, clipped to the picture; :func:`window_at` gives the smallest level-k window that covers a level-0
 window.
 
-The codestream: ``embedded._PREAMBLE`` with magic ``b"VAMy"`` (version 1, reserved 0, bytes of the header, CRC-32 of the
+The codestream: ``framing.PREAMBLE`` with magic ``b"VAMy"`` (version 1, reserved 0, bytes of the header, CRC-32 of the
 header), a little-endian header (u32 H, W; u16 n_levels; u16 reserved (0); n_levels x u64 ``bytes_k`` for k = 0 .. n - 1, 0: the
 level is absent; u64 total), then the body: the level codestreams, COARSEST FIRST (k = n - 1 down to 0), each exactly the bytes
 ``tiled.encode`` gives for that level's picture; nothing is re-framed.  From :func:`need_bytes` on every prefix decodes a
@@ -39,18 +39,18 @@ entropy-coded headers.
 from __future__ import annotations
 
 import struct
-import zlib
 from typing import List, Optional, Sequence, Tuple
 
 from . import embedded as EB
 from . import tiled as TL
+from .framing import PREAMBLE_BYTES, Frame, as_int, check_total, chunk_view, same, view
 
 MAGIC = b"VAMy"
 VERSION = 1
 MAX_LEVELS = 16
-_PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
-PREAMBLE_BYTES = EB.PREAMBLE_BYTES
 _FIXED = struct.Struct("<IIHH")            # H, W, n_levels, reserved (0); then u64 bytes_k [n_levels] and the u64 total
+FRAME = Frame(MAGIC, "a pyramid codestream", "pyramid codestream", (VERSION,), range(_FIXED.size + 16, _FIXED.size + 8 * MAX_LEVELS + 9, 8),
+              f"the header of n = 1 .. {MAX_LEVELS} levels takes {_FIXED.size + 8} + 8 n")
 _ALIKE = ("V", "allocation", "stages", "marks", "lanes", "base_lanes", "ns")
 
 
@@ -84,7 +84,7 @@ def default_levels(H: int, W: int, tile: int = 256) -> int:
 def window_at(window, k: int, H: int, W: int) -> Tuple[int, int, int, int]:
     """The smallest window (y0, x0, h, w) of level k that covers the level-0 window ``window`` of an H x W picture (None:
     the picture): rows ``y0 >> k`` .. ``min(H_k, ceil((y0 + h) / 2^k))``, columns likewise."""
-    k = TL._int(k, "window_at: k")
+    k = as_int(k, "window_at: k")
     if not 0 <= k < 32:
         raise ValueError(f"window_at: k is a level, 0 .. 31, got {k}")
     y0, x0, h, w = TL._window({"H": H, "W": W}, window, "window_at")
@@ -97,8 +97,8 @@ def best_level(window, out_hw, H: int, W: int, n_levels: int) -> int:
     """The coarsest level of ``n_levels`` whose window covering ``window`` (level-0 coordinates; None: the picture) has at
     least ``out_hw`` = (rows, columns) in both directions: the level to decode for a viewport of that size.  0 when not
     even level 0 has."""
-    oh, ow = (TL._int(v, "best_level: out_hw") for v in out_hw)
-    n = TL._int(n_levels, "best_level: n_levels")
+    oh, ow = (as_int(v, "best_level: out_hw") for v in out_hw)
+    n = as_int(n_levels, "best_level: n_levels")
     if oh < 1 or ow < 1 or n < 1:
         raise ValueError(f"best_level: out_hw is (rows, columns) >= 1 and n_levels >= 1, got {tuple(out_hw)} and {n}")
     best = 0
@@ -113,7 +113,7 @@ def source_window(window, d: int, Hj: int, Wj: int) -> Tuple[int, int, int, int]
     """The window (y0, x0, h, w) of level j = k + d, a picture of Hj x Wj, that upsampling by 2^d reads for the level-k
     window ``window``: rows ``clamp(a(y0))`` .. ``clamp(a(y0 + h - 1) + 1)`` with ``a(Y) = floor((2 Y + 1 - 2^d) / 2^(d+1))`` and the
     clamp to 0 .. Hj - 1, columns likewise (module docstring).  Host arithmetic only."""
-    d, Hj, Wj = TL._int(d, "source_window: d"), TL._int(Hj, "source_window: Hj"), TL._int(Wj, "source_window: Wj")
+    d, Hj, Wj = as_int(d, "source_window: d"), as_int(Hj, "source_window: Hj"), as_int(Wj, "source_window: Wj")
     if not 1 <= d <= 15:
         raise ValueError(f"source_window: d is 1 .. 15 (the levels between the two pictures), got {d}")
     if Hj < 1 or Wj < 1:
@@ -124,7 +124,7 @@ def source_window(window, d: int, Hj: int, Wj: int) -> Tuple[int, int, int, int]
         entries = []
     if len(entries) != 4:
         raise ValueError(f"source_window: a window is (y0, x0, h, w), got {window!r}")
-    y0, x0, h, w = (TL._int(v, "source_window: a window entry") for v in entries)
+    y0, x0, h, w = (as_int(v, "source_window: a window entry") for v in entries)
     if y0 < 0 or x0 < 0 or h < 1 or w < 1:
         raise ValueError(f"source_window: a window is (y0, x0, h, w) with y0, x0 >= 0 and h, w >= 1, got {(y0, x0, h, w)}")
     a = lambda P: (2 * P + 1 - (1 << d)) >> (d + 1)         # Python's shift floors negative numbers too
@@ -134,28 +134,11 @@ def source_window(window, d: int, Hj: int, Wj: int) -> Tuple[int, int, int, int]
 
 
 # ----------------------------------------------------------------------------------------------------------- codestream
-def _header_end(d, what: str) -> Optional[int]:
-    if len(d) < PREAMBLE_BYTES:
-        return None
-    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
-    if magic != MAGIC:
-        raise ValueError(f"{what}: not a pyramid codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
-    if version != VERSION or reserved:
-        raise ValueError(f"{what}: pyramid codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
-                         f"reader knows version {VERSION}")
-    if not _FIXED.size + 16 <= hlen <= _FIXED.size + 8 * MAX_LEVELS + 8 or (hlen - _FIXED.size) % 8:
-        raise ValueError(f"{what}: a header of {hlen} bytes: the header of n = 1 .. {MAX_LEVELS} levels takes {_FIXED.size + 8} + 8 n")
-    return PREAMBLE_BYTES + hlen
-
-
 class _Pyramid:
     """A parsed pyramid header and the byte arithmetic of the body that follows from it."""
 
     def __init__(self, d, what: str):
-        hlen, crc = _PREAMBLE.unpack_from(d, 0)[3:]
-        end = PREAMBLE_BYTES + hlen
-        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
-            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        d, _, hlen, end = FRAME.open(d, what)
         H, W, n, zero = _FIXED.unpack_from(d, PREAMBLE_BYTES)
         if zero:
             raise ValueError(f"{what}: the header's reserved field is {zero}, this reader knows 0")
@@ -181,7 +164,7 @@ class _Pyramid:
         return min(max(n - self.off[k], 0), self.size[k])
 
     def level(self, k, what: str) -> int:
-        k = TL._int(k, f"{what}: level")
+        k = as_int(k, f"{what}: level")
         if not 0 <= k < self.n:
             raise ValueError(f"{what}: level is 0 .. {self.n - 1}, got {k}")
         return k
@@ -189,23 +172,16 @@ class _Pyramid:
 
 def _parse(data, what: str):
     """(view, parsed header) of a pyramid codestream, or a prefix of one, that holds its whole header."""
-    d = EB._view(data, what)
-    end = _header_end(d, what)
-    if end is None or len(d) < end:
-        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
-                         "before it can be read")
+    d = view(data, what)
     p = _Pyramid(d, what)
-    if len(d) > p.total:
-        raise ValueError(f"{what}: {len(d)} bytes, the header states a total of {p.total}: {len(d) - p.total} bytes follow the "
-                         "codestream")
+    check_total(len(d), p.total, what)
     return d, p
 
 
-def _facts(g: dict, total: int, allocation: str, stages: int, meta: Optional[dict]) -> dict:
-    """What the levels of one pyramid are checked on: a level's geometry and total, and, once a tile head is held, what its
-    tiles carry."""
-    f = {key: g[key] for key in ("H", "W", "th", "tw", "V")}
-    f.update({"total": total, "allocation": allocation, "stages": stages})
+def _facts(g: dict, meta: Optional[dict]) -> dict:
+    """What the levels of one pyramid are checked on: a level's geometry, total, allocation and stages (``g``:
+    ``tiled.layout``'s dict or ``tiled.PictureFeed.facts``), and, once a tile head is held, what its tiles carry."""
+    f = {key: g[key] for key in ("H", "W", "th", "tw", "V", "total", "allocation", "stages")}
     for key in ("marks", "lanes", "base_lanes", "ns"):
         f[key] = None if meta is None else meta[key]
     return f
@@ -228,7 +204,7 @@ def _check_facts(p: _Pyramid, facts: dict, what: str):
     for k in ks[1:]:
         a, b = facts[ks[0]], facts[k]
         for key in _ALIKE:
-            if a[key] is not None and b[key] is not None and not EB._same(a[key], b[key]):
+            if a[key] is not None and b[key] is not None and not same(a[key], b[key]):
                 name = {"V": "overlap", "stages": "stages (scheduled or not)"}.get(key, key)
                 raise ValueError(f"{what}: level {k} and level {ks[0]} differ in their {name} ({b[key]!r} against {a[key]!r}): all "
                                  "levels of a pyramid are coded with the same tile geometry, marks and lanes")
@@ -246,8 +222,7 @@ def _level_layout(d, p: _Pyramid, k: int, what: str) -> Optional[dict]:
     held = p.held(len(d), k)
     part = d[p.off[k]:p.off[k] + held]
     try:
-        end = TL._header_end(part, what)
-        return TL.layout(part) if end is not None and held >= end else None
+        return TL.layout(part) if TL.FRAME.whole(part, what) else None
     except ValueError as e:
         raise ValueError(f"{what}: level {k}: {e}") from e
 
@@ -255,8 +230,7 @@ def _level_layout(d, p: _Pyramid, k: int, what: str) -> Optional[dict]:
 def _layouts(d, p: _Pyramid, what: str) -> List[Optional[dict]]:
     """Every level's :func:`_level_layout`, checked against the header and against each other."""
     lays = [_level_layout(d, p, k, what) if p.size[k] else None for k in range(p.n)]
-    _check_facts(p, {k: _facts(lay, lay["total"], lay["allocation"], lay["stages"], lay if lay["marks"] is not None else None)
-                     for k, lay in enumerate(lays) if lay is not None}, what)
+    _check_facts(p, {k: _facts(lay, lay if lay["marks"] is not None else None) for k, lay in enumerate(lays) if lay is not None}, what)
     return lays
 
 
@@ -266,7 +240,7 @@ def _assemble(H: int, W: int, streams: Sequence[Optional[bytes]]) -> bytes:
     size = [len(s) if s else 0 for s in streams]
     hlen = _FIXED.size + 8 * n + 8
     header = _FIXED.pack(H, W, n, 0) + struct.pack(f"<{n + 1}Q", *size, PREAMBLE_BYTES + hlen + sum(size))
-    out = [_PREAMBLE.pack(MAGIC, VERSION, 0, hlen, zlib.crc32(header) & 0xFFFFFFFF), header]
+    out = [FRAME.seal(header)]
     out += [bytes(streams[k]) for k in reversed(range(n)) if size[k]]
     return b"".join(out)
 
@@ -276,10 +250,10 @@ def pack(H: int, W: int, level_streams) -> bytes:
     picture), ``level_streams[k]`` for level k, None for an absent level.  Pure framing on the host; ValueError for what
     :func:`layout` would refuse."""
     try:
-        streams = [None if s is None else bytes(EB._view(s, "pack")) for s in level_streams]
+        streams = [None if s is None else bytes(view(s, "pack")) for s in level_streams]
     except TypeError as e:
         raise ValueError("pack: level_streams is a sequence of picture codestreams") from e
-    _check_levels(TL._int(H, "pack: H"), TL._int(W, "pack: W"), len(streams), "pack")
+    _check_levels(as_int(H, "pack: H"), as_int(W, "pack: W"), len(streams), "pack")
     if not any(streams):
         raise ValueError("pack: no level: every entry is None")
     data = _assemble(H, W, streams)
@@ -294,10 +268,8 @@ def need_bytes(data) -> int:
     """The smallest length from which a whole picture decodes at some resolution, as far as ``data`` (any prefix) tells:
     the preamble's size while that is incomplete, the header's end while the header is, then the header plus
     ``tiled.need_bytes`` of the coarsest present level."""
-    d = EB._view(data, "need_bytes")
-    end = _header_end(d, "need_bytes")
-    if end is None:
-        return PREAMBLE_BYTES
+    d = view(data, "need_bytes")
+    end = FRAME.need_header(d, "need_bytes")
     if len(d) < end:
         return end
     d, p = _parse(d, "need_bytes")
@@ -387,7 +359,7 @@ def encode(model, image, levels: Optional[int] = None, tile: int = 256, overlap:
                          f"{tuple(image.shape) if isinstance(image, torch.Tensor) else type(image).__name__}")
     H, W = (int(v) for v in image.shape[-2:])
     T = TL.grid(H, W, tile, overlap)["tile"]
-    n = default_levels(H, W, T) if levels is None else TL._int(levels, "pyramid.encode: levels")
+    n = default_levels(H, W, T) if levels is None else as_int(levels, "pyramid.encode: levels")
     shapes = _check_levels(H, W, n, "pyramid.encode")
     schedule = tiled_kwargs.pop("schedule", None)
     pic = image.detach().reshape(3, H, W).contiguous()
@@ -469,7 +441,7 @@ class PyramidDecoder:
     def __init__(self, model, data, coder: Optional[str] = None, group: Optional[int] = None):
         EB._check_model(model)
         lay = layout(data)
-        self.m, self.coder, self.group, self._d = model, coder, group, bytes(EB._view(data, "PyramidDecoder"))
+        self.m, self.coder, self.group, self._d = model, coder, group, bytes(view(data, "PyramidDecoder"))
         self.shape, self.levels, self.shapes = (lay["H"], lay["W"]), lay["n_levels"], [lv["shape"] for lv in lay["levels"]]
         self.ready = [lv["ready"] for lv in lay["levels"]]
         self._present = [lv["present"] for lv in lay["levels"]]
@@ -484,7 +456,7 @@ class PyramidDecoder:
 
     def decoder(self, level: int = 0) -> "TL.PictureDecoder":
         """The ``tiled.PictureDecoder`` of ``level`` on ``level_stream(data, level)``."""
-        k = TL._int(level, "PyramidDecoder.decode: level")
+        k = as_int(level, "PyramidDecoder.decode: level")
         if not 0 <= k < self.levels:
             raise ValueError(f"PyramidDecoder.decode: level is 0 .. {self.levels - 1}, got {k}")
         if not self.ready[k]:
@@ -516,7 +488,7 @@ class PyramidDecoder:
             self.last_tiles, self.last_chain = dec.last_tiles, [(int(level), list(dec.last_tiles), list(dec.last_tiles))]
             return out
         what = "PyramidDecoder.decode"
-        k = TL._int(level, f"{what}: level")
+        k = as_int(level, f"{what}: level")
         if not 0 <= k < self.levels:
             raise ValueError(f"{what}: level is 0 .. {self.levels - 1}, got {k}")
         out, chain = _fill(what, self.shapes, [j for j in range(self.levels) if self.usable[j]], self._composer, window, k, q, mark, stage,
@@ -530,8 +502,8 @@ class PyramidFeed:
     """The byte bookkeeping of a pyramid's receiver: a pyramid codestream, whole or an :func:`extract`, arriving in chunks
     that may end anywhere, the header included.  Once the header is complete it owns one receiver per present level
     (``receivers[k]``, None for an absent level; by default a ``tiled.PictureFeed``: host arithmetic only) and routes the
-    bytes to them in the order of the body.  ``make(k)`` builds level k's receiver: anything with ``tiled.PictureFeed``'s
-    interface, or that owns one as ``feed_state``.
+    bytes to them in the order of the body.  ``make(k)`` builds level k's receiver: a ``tiled.PictureFeed`` or anything with
+    its ``feed``, ``mark`` / ``rewind``, ``ready``, ``need()``, ``data``, ``facts`` and ``meta``, as ``tiled.PictureStream``.
 
     ``ready``: a level decodes; ``ready_levels``; ``need()``: the bytes still missing before the first level does;
     ``shape``, ``levels``, ``shapes`` once the header is complete; ``fed_levels``: the levels that the last feed gave bytes to;
@@ -546,16 +518,12 @@ class PyramidFeed:
         self.receivers: List = []
         self.fed_levels: List[int] = []
 
-    @staticmethod
-    def _state(r) -> "TL.PictureFeed":
-        return getattr(r, "feed_state", r)
-
     def __len__(self) -> int:
         return self._n
 
     @property
     def data(self) -> bytes:
-        return bytes(self._head) + b"".join(self._state(self.receivers[k]).data for k in (self._p.order if self._p else []))
+        return bytes(self._head) + b"".join(self.receivers[k].data for k in (self._p.order if self._p else []))
 
     def _header(self, name: str) -> _Pyramid:
         if self._p is None:
@@ -568,7 +536,7 @@ class PyramidFeed:
 
     @property
     def ready_levels(self) -> List[int]:
-        return [k for k, r in enumerate(self.receivers) if r is not None and self._state(r).ready]
+        return [k for k, r in enumerate(self.receivers) if r is not None and r.ready]
 
     @property
     def ready(self) -> bool:
@@ -576,16 +544,15 @@ class PyramidFeed:
 
     def need(self) -> int:
         if self._p is not None:
-            return 0 if self.ready else self._state(self.receivers[self._p.order[0]]).need()
-        end = _header_end(self._head, self._what) if len(self._head) >= PREAMBLE_BYTES else None
-        return (PREAMBLE_BYTES if end is None else end) - len(self._head)
+            return 0 if self.ready else self.receivers[self._p.order[0]].need()
+        return FRAME.need_header(self._head, self._what) - len(self._head)
 
     def _facts(self) -> dict:
         out = {}
         for k, r in enumerate(self.receivers):
-            s = None if r is None else self._state(r)._s
-            if s is not None:
-                out[k] = _facts(s.g, s.total, TL.ALLOCATIONS[s.version == TL.VERSION_POOLED], s.stages, self._state(r).meta)
+            g = None if r is None else r.facts
+            if g is not None:
+                out[k] = _facts(g, r.meta)
         return out
 
     def feed(self, chunk) -> List[int]:
@@ -594,11 +561,9 @@ class PyramidFeed:
         the other levels, what ``tiled.PictureFeed.feed`` refuses of a level's own bytes, bytes beyond the header's total
         and a non-bytes argument are ValueErrors that leave the receiver, and every level's, as it was."""
         what = f"{self._what}.feed"
-        if not isinstance(chunk, (bytes, bytearray, memoryview)):
-            raise ValueError(f"{what}: expected bytes, got {type(chunk).__name__}")
-        chunk = bytes(EB._view(chunk, what))
+        chunk = bytes(chunk_view(chunk, what))
         before = (len(self._head), self._p, self._n, self.receivers, self.fed_levels,
-                  [None if r is None else self._state(r)._mark() for r in self.receivers])
+                  [None if r is None else r.mark() for r in self.receivers])
         try:
             self._route(chunk, what)
         except ValueError:
@@ -606,28 +571,25 @@ class PyramidFeed:
             del self._head[n_head:]
             for r, m in zip(self.receivers, marks):
                 if r is not None:
-                    self._state(r)._rewind(m)
-                    if hasattr(r, "_rewound"):
-                        r._rewound()
+                    r.rewind(m)
             raise
         return self.ready_levels
 
     def _route(self, chunk: bytes, what: str):
         at, fed = 0, []
         if self._p is None:
-            end = _header_end(self._head + chunk[:PREAMBLE_BYTES], what)       # refuses a wrong preamble as soon as it is whole
+            end = FRAME.header_end(self._head + chunk[:PREAMBLE_BYTES], what)  # refuses a wrong preamble as soon as it is whole
             take = len(chunk) if end is None else min(len(chunk), end - len(self._head))
             self._head += chunk[:take]
             at = take
             if end is None or len(self._head) < end:
                 self._n += take
                 return
-            p = _Pyramid(self._head, what)
+            p = _Pyramid(bytes(self._head), what)                               # a copy: a view of it would pin the buffer's size
             self._p, self.receivers = p, [self._make(k) if p.size[k] else None for k in range(p.n)]
         p = self._p
         n = self._n + len(chunk)
-        if n > p.total:
-            raise ValueError(f"{what}: {n} bytes, the header states a total of {p.total}: {n - p.total} bytes follow the codestream")
+        check_total(n, p.total, what)
         pos = self._n + at                                                      # where chunk[at:] begins in the codestream
         for k in p.order:
             a, b = max(pos, p.off[k]), min(n, p.off[k] + p.size[k])
@@ -653,7 +615,7 @@ class PyramidStream:
 
     def __init__(self, model, coder: Optional[str] = None, group: Optional[int] = None, cache_tiles: Optional[int] = None):
         TL.PictureStream(model, coder=coder, group=group, cache_tiles=cache_tiles)      # its checks of the arguments, now and not at the header
-        self.feed_state = PyramidFeed("PyramidStream", lambda k: _LevelStream(model, coder=coder, group=group, cache_tiles=cache_tiles))
+        self.feed_state = PyramidFeed("PyramidStream", lambda k: TL.PictureStream(model, coder=coder, group=group, cache_tiles=cache_tiles))
         self.last_tiles: List[Tuple[int, int]] = []
         self.last_decoded: List[Tuple[int, int]] = []
         self.last_chain: List[Tuple[int, List[Tuple[int, int]], List[Tuple[int, int]]]] = []
@@ -704,7 +666,7 @@ class PyramidStream:
         if fs._p is None:
             raise ValueError(f"{what}: nothing to decode yet: the header is not complete, {fs.need()} bytes are missing")
         k = fs._p.level(level, what)
-        usable = [j for j, r in enumerate(fs.receivers) if r is not None and r.feed_state._s is not None]
+        usable = [j for j, r in enumerate(fs.receivers) if r is not None and r.facts is not None]
         out, chain = _fill(what, fs._p.shapes, usable, lambda j: fs.receivers[j], window, k, q, mark, stage, dtype, fs.need())
         self.last_tiles, self.last_decoded, self.last_chain = chain[0][1], chain[0][2], chain
         return out
@@ -719,11 +681,3 @@ class PyramidStream:
         if fs.receivers[k] is None:
             raise _not_ready("PyramidStream.canvas", k, False, fs.ready_levels)
         return fs.receivers[k].canvas(window, dtype)
-
-
-class _LevelStream(TL.PictureStream):
-    """A level's ``tiled.PictureStream``; when the pyramid refuses a chunk its bytes are taken back."""
-
-    def _rewound(self):
-        if self.feed_state._s is None:                      # the level's header went with the chunk: its geometry is open again
-            self.group = self.cache_tiles = None

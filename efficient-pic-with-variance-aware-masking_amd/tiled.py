@@ -10,7 +10,7 @@ two tiles overlap along an axis.  In the band that tiles r and r + 1 share, row 
 pixel is the sum over its tiles, ascending r and within that ascending c, of ``(wy * wx) * v`` in fp32 (vam_tile_blend):
 outside the bands the picture IS the tile's decode, bit for bit.
 
-The codestream: ``embedded._PREAMBLE`` with magic ``b"VAMp"``, a little-endian header (u32 H, W; u16 th / 64, tw / 64, V, R, C,
+The codestream: ``framing.PREAMBLE`` with magic ``b"VAMp"``, a little-endian header (u32 H, W; u16 th / 64, tw / 64, V, R, C,
 n_rounds; a u32 table [R C][1 + n_rounds]; u64 total) under a CRC-32, then the body: the **heads** of all tiles in raster
 order, then round 0 of all tiles, round 1, ...  A tile's head is its own embedded codestream up to its ``base_end``, its round
 pieces are the differences of its ``round_end`` and a last piece up to its ``total``: head and pieces concatenated are exactly
@@ -59,12 +59,12 @@ times coarser (``vampic.pyramid`` chains the levels).
 from __future__ import annotations
 
 import struct
-import zlib
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import embedded as EB
+from .framing import MAX_HEADER, PREAMBLE as _PREAMBLE, PREAMBLE_BYTES, Frame, as_int as _int, check_total, chunk_view, same, view
 
 MAGIC = b"VAMp"
 VERSION = 1                                # allocation="tile": every tile marks its own quantiles
@@ -72,25 +72,19 @@ VERSION_POOLED = 2                         # allocation="picture" (DESIGN sectio
 VERSION_SCHEDULED = 3                      # schedule=S: every tile is scheduled, the rounds are stages
 ALLOCATIONS = ("tile", "picture")
 _ALLOC_PICTURE = 1                         # the one allocation value a version-2 header may state
-_PREAMBLE = EB._PREAMBLE                   # magic, version, reserved (0), bytes of the header, CRC-32 of the header
-PREAMBLE_BYTES = EB.PREAMBLE_BYTES
 _FIXED = struct.Struct("<IIHHHHHH")        # H, W, th / 64, tw / 64, V, R, C, n_rounds
 _POOLED = struct.Struct("<HHHH")           # version 2, after the table: allocation, n_marks, ns, reserved (0); then f32 [n_marks][ns]
 _SCHED = struct.Struct("<HHI")             # version 3, after the table: kind (1: scheduled), n_stages, reserved (0)
 _KIND_SCHEDULED = 1                        # the one kind a version-3 header may state
-_MAX_HEADER = EB._MAX_HEADER
+FRAME = Frame(MAGIC, "a picture codestream", "picture codestream", (VERSION, VERSION_POOLED, VERSION_SCHEDULED),
+              range(_FIXED.size + 12, MAX_HEADER + 1), f"a header takes {_FIXED.size + 12} .. {MAX_HEADER}")
+_header_end = FRAME.header_end             # None while the preamble is incomplete, else where the header ends (tests read it and _PREAMBLE)
 MAX_SIDE = 1 << 24                         # csrc/tiles.hip: the largest picture side
 MAX_GROUP = 32
 MAX_POOL = 16000000                        # csrc/pooled_select.hip: torch.quantile's largest input
 
 
 # ------------------------------------------------------------------------------------------------------------- geometry
-def _int(v, what: str) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f"{what} is an integer, got {v!r}")
-    return int(v)
-
-
 def _geometry(H: int, W: int, th: int, tw: int, V: int, what: str) -> dict:
     """The grid of th x tw tiles with overlap V over a picture of H x W."""
     if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
@@ -151,10 +145,7 @@ class _Picture:
     """A parsed picture header and the byte arithmetic of the body that follows from it."""
 
     def __init__(self, d, what: str):
-        version, _, hlen, crc = _PREAMBLE.unpack_from(d, 0)[1:]
-        end = PREAMBLE_BYTES + hlen
-        if zlib.crc32(d[PREAMBLE_BYTES:end]) & 0xFFFFFFFF != crc:
-            raise ValueError(f"{what}: the header's CRC-32 does not match: the first {end} bytes are damaged")
+        d, version, hlen, end = FRAME.open(d, what)
         H, W, th, tw, V, R, C, nr = _FIXED.unpack_from(d, PREAMBLE_BYTES)
         if not (1 <= th <= 16 and 1 <= tw <= 16):
             raise ValueError(f"{what}: the header contradicts itself: tiles of {64 * th} x {64 * tw}, sides are 64 .. 1024")
@@ -243,31 +234,11 @@ class _Picture:
         return b"".join(bytes(d[int(o):min(int(o + s), n)]) for o, s in zip(self.off[:, i], self.size[:, i]) if s and o < n)
 
 
-def _header_end(d, what: str) -> Optional[int]:
-    if len(d) < PREAMBLE_BYTES:
-        return None
-    magic, version, reserved, hlen, _ = _PREAMBLE.unpack_from(d, 0)
-    if magic != MAGIC:
-        raise ValueError(f"{what}: not a picture codestream: it begins with {bytes(magic)!r}, not with the magic {MAGIC!r}")
-    if version not in (VERSION, VERSION_POOLED, VERSION_SCHEDULED) or reserved:
-        raise ValueError(f"{what}: picture codestream version {version}{f' (reserved field {reserved})' if reserved else ''}; this "
-                         f"reader knows versions {VERSION}, {VERSION_POOLED} and {VERSION_SCHEDULED}")
-    if not _FIXED.size + 4 + 8 <= hlen <= _MAX_HEADER:
-        raise ValueError(f"{what}: a header of {hlen} bytes: a header takes {_FIXED.size + 12} .. {_MAX_HEADER}")
-    return PREAMBLE_BYTES + hlen
-
-
 def _parse(data, what: str):
     """(view, parsed header) of a picture codestream, or a prefix of one, that holds its whole header."""
-    d = EB._view(data, what)
-    end = _header_end(d, what)
-    if end is None or len(d) < end:
-        raise ValueError(f"{what}: {len(d)} bytes do not hold the header: {PREAMBLE_BYTES if end is None else end} bytes are needed "
-                         "before it can be read")
+    d = view(data, what)
     s = _Picture(d, what)
-    if len(d) > s.total:
-        raise ValueError(f"{what}: {len(d)} bytes, the header states a total of {s.total}: {len(d) - s.total} bytes follow the "
-                         "codestream")
+    check_total(len(d), s.total, what)
     return d, s
 
 
@@ -300,7 +271,7 @@ _ALIKE = ("marks", "lanes", "base_lanes", "ns")
 
 def _unlike(lay: dict, first: dict, rc, rc0, what: str):
     for key in _ALIKE:
-        if not EB._same(lay[key], first[key]):
+        if not same(lay[key], first[key]):
             raise ValueError(f"{what}: tile {rc} and tile {rc0} differ in their {key}: all tiles of a picture carry the same "
                              "marks, lanes and base_lanes")
 
@@ -354,13 +325,13 @@ def _assemble(g: dict, table: np.ndarray, get, thresholds: Optional[np.ndarray] 
     if (table >= 1 << 32).any():
         raise ValueError("a head or round piece of 2^32 bytes or more does not fit the header's table")
     hlen = _FIXED.size + 4 * table.size + len(ext) + 8
-    if hlen > _MAX_HEADER:
-        raise ValueError(f"the header would take {hlen} bytes, the limit is {_MAX_HEADER}; use larger tiles")
+    if hlen > MAX_HEADER:
+        raise ValueError(f"the header would take {hlen} bytes, the limit is {MAX_HEADER}; use larger tiles")
     if nr > 0xFFFF:
         raise ValueError(f"{nr} rounds; the format carries up to 65535")
     header = _FIXED.pack(g["H"], g["W"], g["th"] // 64, g["tw"] // 64, g["V"], g["R"], g["C"], nr) + table.astype("<u4").tobytes() \
         + ext + struct.pack("<Q", PREAMBLE_BYTES + hlen + int(table.sum()))
-    out = [_PREAMBLE.pack(MAGIC, version, 0, len(header), zlib.crc32(header) & 0xFFFFFFFF), header]
+    out = [FRAME.seal(header, version)]
     out += [get(i, k) for k in range(1 + nr) for i in range(table.shape[0]) if table[i, k]]
     return b"".join(out)
 
@@ -400,7 +371,7 @@ def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None,
             rows.append(None)
             views.append(None)
             continue
-        v = EB._view(s, f"pack: tile {rc}")
+        v = view(s, f"pack: tile {rc}")
         lay = _tile_layout(v, g, rc, "pack", stages or 0)
         if len(v) != lay["total"]:
             raise ValueError(f"pack: tile {rc}: {len(v)} bytes, its header states a total of {lay['total']}: a picture is packed from "
@@ -433,10 +404,8 @@ def pack(H: int, W: int, tile: int, overlap: int, tile_streams, thresholds=None,
 def need_bytes(data) -> int:
     """The smallest length from which the whole picture decodes, as far as ``data`` (any prefix) tells: the preamble's size
     while that is incomplete, the header's end while the header is, then the end of the last head."""
-    d = EB._view(data, "need_bytes")
-    end = _header_end(d, "need_bytes")
-    if end is None:
-        return PREAMBLE_BYTES
+    d = view(data, "need_bytes")
+    end = FRAME.need_header(d, "need_bytes")
     return end if len(d) < end else _parse(d, "need_bytes")[1].need
 
 
@@ -990,7 +959,8 @@ class PictureFeed:
     whole (``PictureDecoder.meta`` once ready); and once ready ``rounds`` (``PictureDecoder.rounds``) and ``held`` int [R, C],
     the bytes present of each tile's own codestream, -1 where the tile is absent.  Per tile, from the header on:
     ``tile_ready`` bool [R, C] and ``tile_rounds`` int [R, C].  ``fed_tiles``: the (r, c), in raster order, whose held bytes
-    grew in the last feed.  ``data``: everything fed so far."""
+    grew in the last feed.  ``data``: everything fed so far.  ``facts``, ``mark()`` and ``rewind(mark)``: what
+    ``pyramid.PyramidFeed`` asks of a level's receiver besides."""
 
     def __init__(self, what: str = "PictureFeed"):
         self._what = what
@@ -1015,8 +985,7 @@ class PictureFeed:
     def need(self) -> int:
         if self._s is not None:
             return max(0, self._s.need - len(self._buf))
-        end = _header_end(self._buf, self._what) if len(self._buf) >= PREAMBLE_BYTES else None
-        return (PREAMBLE_BYTES if end is None else end) - len(self._buf)
+        return FRAME.need_header(self._buf, self._what) - len(self._buf)
 
     def _header(self, name: str):
         if self._s is None:
@@ -1079,22 +1048,18 @@ class PictureFeed:
         contradicts the table or the other tiles, bytes beyond the header's total and a non-bytes argument are ValueErrors
         that leave the receiver as it was."""
         what = f"{self._what}.feed"
-        if not isinstance(chunk, (bytes, bytearray, memoryview)):
-            raise ValueError(f"{what}: expected bytes, got {type(chunk).__name__}")
-        chunk = bytes(EB._view(chunk, what))
+        chunk = bytes(chunk_view(chunk, what))
         s, heads, meta, n = self._s, self._heads, self.meta, len(self._buf) + len(chunk)
         if s is None or heads < int(s.present.sum()):                             # the header or a head may complete: look at the bytes
             d = memoryview(bytes(self._buf) + chunk)
-            if s is None:
-                end = _header_end(d, what)
-                if end is not None and n >= end:
-                    s = _Picture(d, what)
+            if s is None and FRAME.whole(d, what):
+                s = _Picture(d, what)
             if s is not None:
                 whole = int((s.present & (s.off[0] + s.size[0] <= n)).sum())
                 if whole != heads:
                     meta, heads = _tile_meta(d, s, what), whole
-        if s is not None and n > s.total:
-            raise ValueError(f"{what}: {n} bytes, the header states a total of {s.total}: {n - s.total} bytes follow the codestream")
+        if s is not None:
+            check_total(n, s.total, what)
         self._buf += chunk
         self._s, self._heads, self.meta = s, heads, meta
         self.fed_tiles = []
@@ -1105,12 +1070,19 @@ class PictureFeed:
             self._per_tile = per_tile
         return self.rounds
 
-    def _mark(self):
-        """What :meth:`_rewind` needs to undo the feeds that follow: vampic.pyramid feeds one receiver per level and refuses
+    @property
+    def facts(self) -> Optional[dict]:
+        """Once the header is complete (None before): the geometry of :func:`grid` with ``total``, ``allocation`` and
+        ``stages`` as :func:`layout` names them; with ``meta``, what vampic.pyramid checks its levels on."""
+        s = self._s
+        return None if s is None else dict(s.g, total=s.total, allocation=ALLOCATIONS[s.version == VERSION_POOLED], stages=s.stages)
+
+    def mark(self):
+        """What :meth:`rewind` needs to undo the feeds that follow: vampic.pyramid feeds one receiver per level and refuses
         a chunk as a whole."""
         return len(self._buf), self._s, self._heads, self._per_tile, self.meta, self.fed_tiles
 
-    def _rewind(self, mark):
+    def rewind(self, mark):
         n, self._s, self._heads, self._per_tile, self.meta, self.fed_tiles = mark
         del self._buf[n:]
 
@@ -1173,9 +1145,19 @@ class PictureStream:
     tile_rounds = property(lambda self: self.feed_state.tile_rounds)
     fed_tiles = property(lambda self: self.feed_state.fed_tiles)
     data = property(lambda self: self.feed_state.data)
+    facts = property(lambda self: self.feed_state.facts)
 
     def need(self) -> int:
         return self.feed_state.need()
+
+    def mark(self):
+        return self.feed_state.mark()
+
+    def rewind(self, mark):
+        """:meth:`PictureFeed.rewind`; when the header went with the bytes, the stream's geometry is open again."""
+        self.feed_state.rewind(mark)
+        if self.feed_state._s is None:
+            self.group = self.cache_tiles = None
 
     def feed(self, chunk) -> Optional[np.ndarray]:
         """:meth:`PictureFeed.feed`: host arithmetic only, it touches no GPU and no cache entry (a stale tile is found by
