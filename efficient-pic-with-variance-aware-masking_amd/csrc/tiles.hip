@@ -13,24 +13,26 @@
 //                         from the host's tables, elsewhere the one tile has weight 1.  The pixel is the sum, over its tiles in
 //                         ascending r and within that ascending c, of (wy * wx) * v, every product and add one fp32
 //                         operation (__fmul_rn / __fadd_rn never contract), starting from the first term: outside the bands
-//                         it is the tile's value bit for bit.  No atomics, no division of floats, a fixed order.
+//                         it is the tile's value bit for bit.  No atomics, no division of floats, a fixed order.  This
+//                         kernel, tile_refresh_kernel and tile_compose_kernel are the three modes of ONE skeleton,
+//                         window_pixels<Mode>: thread layout, run decision, blend_run and store_pixels are written once.
 //   tile_schedule_kernel  a picture-wide schedule, fp32 [L, H, W] at pixel resolution, brought down onto the latent grids of a
 //                         list of tiles: out[i, k, a, b] = max over y, x in [0, 16) of
 //                         maps[k, min(r Sy + 16 a + y, H - 1), min(c Sx + 16 b + x, W - 1)], the block maximum of
 //                         evaluate.latent_quality_map composed with the extract kernel's edge replication.  One wave per
 //                         output cell: lane l reads the four pixels 4 (l & 3) .. of row l >> 2 and the 64 partial results are
 //                         reduced with wave-64 shuffles.  A NaN anywhere in the block gives NaN (fmaxf alone would drop it).
-//   tile_refresh_kernel   tile_blend_kernel over a box of a persistent canvas: a pixel is computed and
-//                         stored only when one of its tiles is marked in `dirty` [R][C]; the value is blend_run's, so it is
-//                         tile_blend_kernel's bit for bit.  A pixel without a dirty tile is not written and its slots are not
-//                         read.  The output has the canvas's pitch; wide stores need all four pixels written.
+//   tile_refresh_kernel   the skeleton over a box of a persistent canvas: a pixel is computed and stored
+//                         only when one of its tiles is marked in `dirty` [R][C]; the value is tile_blend_kernel's.  A pixel
+//                         without a dirty tile is not written and its slots are not read.  The output has the canvas's
+//                         pitch; wide stores need all four pixels written.
 //   picture_halve_kernel  the next level of a resolution pyramid: fp32 [C, Hs, Ws] to [C, ceil(Hs / 2),
 //                         ceil(Ws / 2)], out[c][y][x] = ((s[2y][2x] + s[2y][x1]) + (s[y1][2x] + s[y1][x1])) * 0.25f with
 //                         y1 = min(2y + 1, Hs - 1), x1 = min(2x + 1, Ws - 1), every add and the multiply one fp32 operation;
 //                         mode 1 takes the maximum of the four instead (schedules), a NaN among them giving NaN.
-//   tile_compose_kernel   tile_blend_kernel over a window of pyramid level k whose tiles have not all arrived (DESIGN section
-//                         9za): a pixel all of whose 1, 2 or 4 tiles have a slot >= 0 is sharp and gets blend_run's value,
-//                         tile_blend_kernel's bit for bit; any other pixel reads none of its tiles and is the bilinear upsample
+//   tile_compose_kernel   the skeleton over a window of pyramid level k whose tiles have not all arrived (DESIGN section
+//                         9za): a pixel all of whose 1, 2 or 4 tiles have a slot >= 0 is sharp and gets
+//                         tile_blend_kernel's value; any other pixel reads none of its tiles and is the bilinear upsample
 //                         by 2^d of `below`, a window of level j = k + d.  Along an axis, output coordinate P has
 //                         n = 2 P + 1 - 2^d, a = n >> (d + 1) (the floor, also for n < 0), f = (n - a 2^(d+1)) / 2^(d+1), exact
 //                         and never 0, and the sources clamp(a) and clamp(a + 1) in 0 .. N_j - 1; with lerp(p, q, f) =
@@ -150,7 +152,20 @@ struct BlendArgs {
   uint8_t* out_u8;
   int32_t* status;
   TileGeom g;
-  int n, y0, x0, h, w;
+  int n, y0, x0, h, w;                      // the tile buffer's size; the window (refresh: the box) to visit
+};
+
+struct RefreshArgs {
+  BlendArgs b;
+  const int32_t* dirty;                     // int32 [R][C]
+  int cy0, cx0, ch, cw;                     // the canvas's window in the picture: out has its pitch
+};
+
+struct ComposeArgs {
+  BlendArgs b;                              // slot == nullptr: no tiles, and then the geometry is not looked at
+  const float* below;                       // fp32 [3, hb, wb]: the window (by0, bx0, hb, wb) of the level-j picture
+  int by0, bx0, hb, wb, Hj, Wj, d;
+  float inv;                                // 2^-(d + 1)
 };
 
 // Where pixel P lies along an axis of n tiles with stride S: in tile t1 at l1, and when `two` in tile t1 - 1 at l1 + S.
@@ -222,113 +237,66 @@ __device__ __forceinline__ void blend_run(const BlendArgs& a, const Axis ay, con
 
 __device__ __forceinline__ unsigned tile_u8(float v) { return (unsigned)rintf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
 
-__global__ __launch_bounds__(256) void tile_blend_kernel(const BlendArgs a) {
-  const TileGeom& g = a.g;
-  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
-  if (x >= a.w || y >= a.h) return;
-  const int nv = min(4, a.w - x);
-  const int X = a.x0 + x;
-  const Axis ay = tile_axis(a.y0 + y, g.Sy, g.V, g.R);
-  const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
-  float acc[3][4];
-  bool run = false;
-  if (nv == 4) {
-    const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
-    run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;         // t1 never decreases and `two` only ends within a tile
-  }
-  if (run) {
-    blend_run<4>(a, ay, ax0, acc, 0);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < nv) blend_run<1>(a, ay, tile_axis(X + k, g.Sx, g.V, g.C), acc, k);
-  }
-  const long at = (long)y * a.w + x;
+// A thread's four pixels into element `at` on of a row of out, fp32 planes `plane` elements apart or uint8 triples.  Pixel k
+// is written where k < nv (PREFIX: a thread that writes its first nv pixels; the compiler folds these compares) or where bit
+// k of `mask` is set; wide where all four are written and the address is aligned (4 bytes for the uint8 triple).
+template <bool PREFIX>
+__device__ __forceinline__ void store_pixels(const BlendArgs& a, long at, long plane, int nv, unsigned mask, const float (&acc)[3][4]) {
+  auto on = [&](int k) { return PREFIX ? k < nv : ((mask >> k) & 1u) != 0; };
+  const bool all = PREFIX ? nv == 4 : mask == 15u;
   if (a.out_u8) {
     uint8_t* dst = a.out_u8 + 3 * at;
     unsigned b[12];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) b[3 * k + ch] = k < nv ? tile_u8(acc[ch][k]) : 0u;
-    if (nv == 4 && ((uintptr_t)dst & 3) == 0) {
+      for (int ch = 0; ch < 3; ++ch) b[3 * k + ch] = on(k) ? tile_u8(acc[ch][k]) : 0u;
+    if (all && ((uintptr_t)dst & 3) == 0) {
 #pragma unroll
       for (int j = 0; j < 3; ++j)
         reinterpret_cast<uint32_t*>(dst)[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
     } else {
 #pragma unroll
       for (int j = 0; j < 12; ++j)
-        if (j < 3 * nv) dst[j] = (uint8_t)b[j];
+        if (on(j / 3)) dst[j] = (uint8_t)b[j];
     }
     return;
   }
-  const long plane = (long)a.h * a.w;
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
     float* dst = a.out_f + ch * plane + at;
-    if (nv == 4 && aligned16(dst)) {
+    if (all && aligned16(dst)) {
       *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (k < nv) dst[k] = acc[ch][k];
+        if (on(k)) dst[k] = acc[ch][k];
     }
   }
 }
 
-// tile_blend_kernel's stores: the first nv of a thread's four pixels into row y from column x on of the window's output, fp32
-// [3, h, w] planes or uint8 [h, w, 3], wide where all four are written and the address is aligned.
-__device__ __forceinline__ void store_pixels(const BlendArgs& a, int y, int x, int nv, const float (&acc)[3][4]) {
-  const long at = (long)y * a.w + x;
-  if (a.out_u8) {
-    uint8_t* dst = a.out_u8 + 3 * at;
-    unsigned b[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) b[3 * k + ch] = k < nv ? tile_u8(acc[ch][k]) : 0u;
-    if (nv == 4 && ((uintptr_t)dst & 3) == 0) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        reinterpret_cast<uint32_t*>(dst)[j] = b[4 * j] | (b[4 * j + 1] << 8) | (b[4 * j + 2] << 16) | (b[4 * j + 3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 12; ++j)
-        if (j < 3 * nv) dst[j] = (uint8_t)b[j];
-    }
-    return;
-  }
-  const long plane = (long)a.h * a.w;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    float* dst = a.out_f + ch * plane + at;
-    if (nv == 4 && aligned16(dst)) {
-      *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < nv) dst[k] = acc[ch][k];
-    }
-  }
-}
-
-struct ComposeArgs {
-  BlendArgs b;                              // slot == nullptr: no tiles, and then the geometry is not looked at
-  const float* below;                       // fp32 [3, hb, wb]: the window (by0, bx0, hb, wb) of the level-j picture
-  int by0, bx0, hb, wb, Hj, Wj, d;
-  float inv;                                // 2^-(d + 1)
-};
-
-// Whether all of the 1, 2 or 4 tiles of a pixel at (ay, ax) have a slot >= 0.
-__device__ __forceinline__ bool tiles_there(const int32_t* slot, int C, const Axis ay, const Axis ax) {
-  const int32_t* row = slot + ay.t1 * C + ax.t1;
-  bool t = row[0] >= 0;
-  if (ax.two) t &= row[-1] >= 0;
+// Whether one of the 1, 2 or 4 entries of `table` [R][C] that belong to the tiles of a pixel at (ay, ax) passes `test`.
+template <class Test>
+__device__ __forceinline__ bool any_tile(const int32_t* table, int C, const Axis ay, const Axis ax, Test test) {
+  const int32_t* row = table + ay.t1 * C + ax.t1;
+  bool t = test(row[0]);
+  if (ax.two) t |= test(row[-1]);
   if (ay.two) {
-    t &= row[-C] >= 0;
-    if (ax.two) t &= row[-C - 1] >= 0;
+    t |= test(row[-C]);
+    if (ax.two) t |= test(row[-C - 1]);
   }
   return t;
+}
+
+enum class Mode { Blend, Refresh, Compose };
+
+// Whether a pixel at (ay, ax) gets blend_run's value.  Blend: always.  Refresh: when one of its tiles is dirty; this reads
+// `dirty` only, never a slot.  Compose: when all of its tiles have a slot >= 0.
+template <Mode M, class Args>
+__device__ __forceinline__ bool blended(const BlendArgs& a, const Args& e, const Axis ay, const Axis ax) {
+  if constexpr (M == Mode::Refresh) return any_tile(e.dirty, a.g.C, ay, ax, [](int32_t d) { return d != 0; });
+  if constexpr (M == Mode::Compose) return !any_tile(a.slot, a.g.C, ay, ax, [](int32_t s) { return s < 0; });
+  return true;
 }
 
 // Where coordinate P of level k reads level j = k + d along an axis of N source pixels: the two sources, as offsets into a
@@ -350,28 +318,33 @@ __device__ __forceinline__ Up up_axis(int P, int d, float inv, int N, int o) {
 
 __device__ __forceinline__ float lerp_rn(float p, float q, float f) { return __fadd_rn(p, __fmul_rn(f, __fsub_rn(q, p))); }
 
-// tile_blend_kernel's thread layout.  Bit k of `sharp` says that pixel k has all its tiles and holds blend_run's value; the
-// others are read from `below`, a quarter of the output's size or less, one value at a time: neighbouring lanes share them.
-__global__ __launch_bounds__(256) void tile_compose_kernel(const ComposeArgs a) {
-  const BlendArgs& b = a.b;
-  const TileGeom& g = b.g;
+// The three window kernels.  A thread owns four consecutive pixels of one row of the window (refresh: the box) and all three
+// channels.  Where the four share one tile set, one decision (blended) and blend_run<4> serve them; otherwise a decision and
+// blend_run<1> per pixel.  Bit k of `sharp` says that pixel k holds blend_run's value.  A pixel that does not: refresh
+// neither computes nor stores it, and its slots are not read; compose (also all pixels when slot == nullptr: no tiles, the
+// geometry is not looked at) reads none of its tiles and takes the bilinear upsample of `below`, a quarter of the output's
+// size or less, one value at a time: neighbouring lanes share them.
+// `a`: what the three share; `e`: the mode's own arguments (blend: `a` again).
+template <Mode M, class Args>
+__device__ __forceinline__ void window_pixels(const BlendArgs& a, const Args& e) {
+  const TileGeom& g = a.g;
   const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
-  if (x >= b.w || y >= b.h) return;
-  const int nv = min(4, b.w - x);
-  const int X = b.x0 + x, Y = b.y0 + y;
+  if (x >= a.w || y >= a.h) return;
+  const int nv = min(4, a.w - x);
+  const int X = a.x0 + x, Y = a.y0 + y;
   float acc[3][4];
   unsigned sharp = 0;
-  if (b.slot) {
+  if (M != Mode::Compose || a.slot) {
     const Axis ay = tile_axis(Y, g.Sy, g.V, g.R);
     const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
     bool run = false;
     if (nv == 4) {
       const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
-      run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;       // one tile set for the four: one decision
+      run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;       // t1 never decreases and `two` only ends within a tile
     }
     if (run) {
-      if (tiles_there(b.slot, g.C, ay, ax0)) {
-        blend_run<4>(b, ay, ax0, acc, 0);
+      if (blended<M>(a, e, ay, ax0)) {
+        blend_run<4>(a, ay, ax0, acc, 0);
         sharp = 15u;
       }
     } else {
@@ -379,115 +352,41 @@ __global__ __launch_bounds__(256) void tile_compose_kernel(const ComposeArgs a) 
       for (int k = 0; k < 4; ++k) {
         if (k >= nv) continue;
         const Axis ax = tile_axis(X + k, g.Sx, g.V, g.C);
-        if (!tiles_there(b.slot, g.C, ay, ax)) continue;
-        blend_run<1>(b, ay, ax, acc, k);
+        if (!blended<M>(a, e, ay, ax)) continue;
+        blend_run<1>(a, ay, ax, acc, k);
         sharp |= 1u << k;
       }
     }
   }
-  if (sharp != 15u) {
-    const Up uy = up_axis(Y, a.d, a.inv, a.Hj, a.by0);
-    const long plane = (long)a.hb * a.wb;
-    const float* r0 = a.below + (long)uy.i0 * a.wb;
-    const float* r1 = a.below + (long)uy.i1 * a.wb;
+  if constexpr (M == Mode::Refresh) {
+    if (sharp) store_pixels<false>(a, (long)(Y - e.cy0) * e.cw + (X - e.cx0), (long)e.ch * e.cw, nv, sharp, acc);
+    return;
+  }
+  if constexpr (M == Mode::Compose) {
+    if (sharp != 15u) {
+      const Up uy = up_axis(Y, e.d, e.inv, e.Hj, e.by0);
+      const long plane = (long)e.hb * e.wb;
+      const float* r0 = e.below + (long)uy.i0 * e.wb;
+      const float* r1 = e.below + (long)uy.i1 * e.wb;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k >= nv || ((sharp >> k) & 1u)) continue;
-      const Up ux = up_axis(X + k, a.d, a.inv, a.Wj, a.bx0);
+      for (int k = 0; k < 4; ++k) {
+        if (k >= nv || ((sharp >> k) & 1u)) continue;
+        const Up ux = up_axis(X + k, e.d, e.inv, e.Wj, e.bx0);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float* s0 = r0 + ch * plane;
-        const float* s1 = r1 + ch * plane;
-        acc[ch][k] = lerp_rn(lerp_rn(s0[ux.i0], s0[ux.i1], ux.f), lerp_rn(s1[ux.i0], s1[ux.i1], ux.f), uy.f);
+        for (int ch = 0; ch < 3; ++ch) {
+          const float* s0 = r0 + ch * plane;
+          const float* s1 = r1 + ch * plane;
+          acc[ch][k] = lerp_rn(lerp_rn(s0[ux.i0], s0[ux.i1], ux.f), lerp_rn(s1[ux.i0], s1[ux.i1], ux.f), uy.f);
+        }
       }
     }
   }
-  store_pixels(b, y, x, nv, acc);
+  store_pixels<true>(a, (long)y * a.w + x, (long)a.h * a.w, nv, 0u, acc);
 }
 
-struct RefreshArgs {
-  BlendArgs b;                              // tiles, slot, ramps, status, geometry; y0, x0, h, w: the box to visit
-  const int32_t* dirty;
-  int cy0, cx0, ch, cw;                     // the canvas's window in the picture: out has its pitch
-};
-
-// Whether one of the 1, 2 or 4 tiles of a pixel at (ay, ax) is dirty.  Reads `dirty` only, never a slot.
-__device__ __forceinline__ bool tiles_dirty(const int32_t* dirty, int C, const Axis ay, const Axis ax) {
-  const int32_t* row = dirty + ay.t1 * C + ax.t1;
-  bool d = row[0] != 0;
-  if (ax.two) d |= row[-1] != 0;
-  if (ay.two) {
-    d |= row[-C] != 0;
-    if (ax.two) d |= row[-C - 1] != 0;
-  }
-  return d;
-}
-
-// tile_blend_kernel's thread layout over the box: a thread owns four consecutive pixels of one row.  Bit k of `wr` says that
-// pixel k has a dirty tile and is written; a pixel without one is neither computed nor stored, and its slots are not read.
-__global__ __launch_bounds__(256) void tile_refresh_kernel(const RefreshArgs a) {
-  const BlendArgs& b = a.b;
-  const TileGeom& g = b.g;
-  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
-  if (x >= b.w || y >= b.h) return;
-  const int nv = min(4, b.w - x);
-  const int X = b.x0 + x, Y = b.y0 + y;
-  const Axis ay = tile_axis(Y, g.Sy, g.V, g.R);
-  const Axis ax0 = tile_axis(X, g.Sx, g.V, g.C);
-  float acc[3][4];
-  unsigned wr = 0;
-  bool run = false;
-  if (nv == 4) {
-    const Axis ax3 = tile_axis(X + 3, g.Sx, g.V, g.C);
-    run = ax3.t1 == ax0.t1 && ax3.two == ax0.two;         // one tile set for the four: one decision
-  }
-  if (run) {
-    if (!tiles_dirty(a.dirty, g.C, ay, ax0)) return;
-    blend_run<4>(b, ay, ax0, acc, 0);
-    wr = 15u;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k >= nv) continue;
-      const Axis ax = tile_axis(X + k, g.Sx, g.V, g.C);
-      if (!tiles_dirty(a.dirty, g.C, ay, ax)) continue;
-      blend_run<1>(b, ay, ax, acc, k);
-      wr |= 1u << k;
-    }
-    if (!wr) return;
-  }
-  const long at = (long)(Y - a.cy0) * a.cw + (X - a.cx0);
-  if (b.out_u8) {
-    uint8_t* dst = b.out_u8 + 3 * at;
-    unsigned v[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) v[3 * k + ch] = (wr >> k) & 1u ? tile_u8(acc[ch][k]) : 0u;
-    if (wr == 15u && ((uintptr_t)dst & 3) == 0) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        reinterpret_cast<uint32_t*>(dst)[j] = v[4 * j] | (v[4 * j + 1] << 8) | (v[4 * j + 2] << 16) | (v[4 * j + 3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 12; ++j)
-        if ((wr >> (j / 3)) & 1u) dst[j] = (uint8_t)v[j];
-    }
-    return;
-  }
-  const long plane = (long)a.ch * a.cw;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    float* dst = b.out_f + ch * plane + at;
-    if (wr == 15u && aligned16(dst)) {
-      *reinterpret_cast<float4*>(dst) = make_float4(acc[ch][0], acc[ch][1], acc[ch][2], acc[ch][3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if ((wr >> k) & 1u) dst[k] = acc[ch][k];
-    }
-  }
-}
+__global__ __launch_bounds__(256) void tile_blend_kernel(const BlendArgs a) { window_pixels<Mode::Blend>(a, a); }
+__global__ __launch_bounds__(256) void tile_refresh_kernel(const RefreshArgs a) { window_pixels<Mode::Refresh>(a.b, a); }
+__global__ __launch_bounds__(256) void tile_compose_kernel(const ComposeArgs a) { window_pixels<Mode::Compose>(a.b, a); }
 
 struct HalveArgs {
   const float* src;
@@ -550,6 +449,50 @@ __global__ __launch_bounds__(256) void picture_halve_kernel(const HalveArgs a) {
   }
 }
 
+// The checks and the arguments that vam_tile_blend, vam_tile_refresh and vam_tile_compose share, in three steps that an entry
+// point puts its own checks between.  First the tiles: the geometry, the pointers (`have`: whether the entry point's are
+// there, `need`: their names), the ramps and n; `none`: compose without tiles, where th, tw and V are not looked at.
+int window_tiles(const char* who, BlendArgs* a, bool none, bool have, const char* need, const float* tiles, int n, const int32_t* slot,
+                 const float* w_lo, const float* w_hi, int32_t* status, int H, int W, int th, int tw, int V) {
+  if (none) {
+    VAM_REQUIRE(H >= 1 && W >= 1 && H <= kTileMaxSide && W <= kTileMaxSide, "%s: a picture of %d x %d: sides are 1 .. %d", who, H, W,
+                kTileMaxSide);
+  } else {
+    if (int rc = tile_geometry(who, H, W, th, tw, V, &a->g)) return rc;
+    VAM_REQUIRE(have, "%s: need %s", who, need);
+    VAM_REQUIRE(V == 0 || (w_lo && w_hi), "%s: an overlap of %d needs the two ramp tables", who, V);
+    VAM_REQUIRE(n >= 1, "%s: a buffer of %d tiles", who, n);
+  }
+  a->tiles = tiles; a->slot = slot; a->w_lo = w_lo; a->w_hi = w_hi; a->status = status; a->n = n;
+  return VAM_OK;
+}
+
+// Then the window of the picture that out holds (`noun`: what the entry point calls it), which is also the one to visit
+// until the entry point says otherwise.
+int window_inside(const char* who, const char* noun, BlendArgs* a, int y0, int x0, int h, int w, int H, int W) {
+  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && h <= H - y0 && w <= W - x0,
+              "%s: the %s (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", who, noun, y0, x0, h, w, H, W);
+  a->y0 = y0; a->x0 = x0; a->h = h; a->w = w;
+  return VAM_OK;
+}
+
+// Last the output and the a->h rows to visit (`noun`: what the entry point calls the pixels to visit).
+int window_out(const char* who, const char* noun, BlendArgs* a, void* out, int out_u8) {
+  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "%s: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", who, out_u8);
+  VAM_REQUIRE(cdiv(a->h, 4) <= 65535u, "%s: a %s of %d rows exceeds one launch", who, noun, a->h);
+  a->out_f = out_u8 ? nullptr : (float*)out;
+  a->out_u8 = out_u8 ? (uint8_t*)out : nullptr;
+  return VAM_OK;
+}
+
+// The launch of a window kernel over the a.h x a.w pixels to visit; `more`: the bytes it moves beside its output.
+template <class Args>
+int window_launch(void (*kernel)(Args), const char* name, const Args& args, const BlendArgs& a, double more, void* stream) {
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)a.h * a.w * (a.out_u8 ? 15.0 : 24.0) + more);
+  hipLaunchKernelGGL(kernel, dim3(cdiv(cdiv(a.w, 4), 64), cdiv(a.h, 4)), dim3(64, 4), 0, (hipStream_t)stream, args);
+  return check_launch(name);
+}
+
 }  // namespace
 }  // namespace vam
 
@@ -591,44 +534,29 @@ int vam_tile_schedule(const float* maps, int L, int H, int W, int th, int tw, in
 
 int vam_tile_blend(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
                    int tw, int V, int y0, int x0, int h, int w, void* out, int out_u8, int32_t* status, void* stream) {
-  BlendArgs a;
-  if (int rc = tile_geometry("vam_tile_blend", H, W, th, tw, V, &a.g)) return rc;
-  VAM_REQUIRE(tiles && slot && out && status, "vam_tile_blend: need tiles, slot, out and status");
-  VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_blend: an overlap of %d needs the two ramp tables", V);
-  VAM_REQUIRE(n >= 1, "vam_tile_blend: a buffer of %d tiles", n);
-  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && h <= H - y0 && w <= W - x0,
-              "vam_tile_blend: the window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", y0, x0, h, w, H, W);
-  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_blend: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
-  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_blend: a window of %d rows exceeds one launch", h);
-  a.tiles = tiles; a.slot = slot; a.w_lo = w_lo; a.w_hi = w_hi; a.status = status;
-  a.out_f = out_u8 ? nullptr : (float*)out;
-  a.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
-  a.n = n; a.y0 = y0; a.x0 = x0; a.h = h; a.w = w;
-  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
-  hipLaunchKernelGGL(tile_blend_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
-  return check_launch("tile_blend_kernel");
+  const char* who = "vam_tile_blend";
+  BlendArgs a = {};
+  if (int rc = window_tiles(who, &a, false, tiles && slot && out && status, "tiles, slot, out and status", tiles, n, slot, w_lo, w_hi,
+                            status, H, W, th, tw, V))
+    return rc;
+  if (int rc = window_inside(who, "window", &a, y0, x0, h, w, H, W)) return rc;
+  if (int rc = window_out(who, "window", &a, out, out_u8)) return rc;
+  return window_launch(tile_blend_kernel, "tile_blend_kernel", a, a, 0.0, stream);
 }
 
 int vam_tile_compose(const float* tiles, int n, const int32_t* slot, const float* w_lo, const float* w_hi, int H, int W, int th,
                      int tw, int V, int y0, int x0, int h, int w, const float* below, int by0, int bx0, int hb, int wb, int Hj, int Wj,
                      int d, void* out, int out_u8, int32_t* status, void* stream) {
+  const char* who = "vam_tile_compose";
   ComposeArgs a = {};
   BlendArgs& b = a.b;
   const bool none = !slot && n == 0;                                            // no tiles: th, tw and V are not looked at
-  if (none) {
-    VAM_REQUIRE(H >= 1 && W >= 1 && H <= kTileMaxSide && W <= kTileMaxSide, "vam_tile_compose: a picture of %d x %d: sides are 1 .. %d", H,
-                W, kTileMaxSide);
-  } else {
-    if (int rc = tile_geometry("vam_tile_compose", H, W, th, tw, V, &b.g)) return rc;
-    VAM_REQUIRE(tiles && slot && status, "vam_tile_compose: need tiles, slot and status (or slot = NULL and n = 0: no tiles)");
-    VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_compose: an overlap of %d needs the two ramp tables", V);
-    VAM_REQUIRE(n >= 1, "vam_tile_compose: a buffer of %d tiles", n);
-  }
+  if (int rc = window_tiles(who, &b, none, tiles && slot && status, "tiles, slot and status (or slot = NULL and n = 0: no tiles)", tiles, n,
+                            slot, w_lo, w_hi, status, H, W, th, tw, V))
+    return rc;
   VAM_REQUIRE(below && out, "vam_tile_compose: need below and out");
-  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && h <= H - y0 && w <= W - x0,
-              "vam_tile_compose: the window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", y0, x0, h, w, H, W);
-  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_compose: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
-  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_compose: a window of %d rows exceeds one launch", h);
+  if (int rc = window_inside(who, "window", &b, y0, x0, h, w, H, W)) return rc;
+  if (int rc = window_out(who, "window", &b, out, out_u8)) return rc;
   VAM_REQUIRE(d >= 1 && d <= 15, "vam_tile_compose: d is 1 .. 15 (the level below is 2^d times coarser), got %d", d);
   const int scale = 1 << d;
   VAM_REQUIRE(Hj == (H + scale - 1) / scale && Wj == (W + scale - 1) / scale,
@@ -645,42 +573,28 @@ int vam_tile_compose(const float* tiles, int n, const int32_t* slot, const float
               "vam_tile_compose: the window of below (y0 %d, x0 %d, h %d, w %d) does not cover the source window (y0 %d, x0 %d, h %d, w %d) "
               "of the window (y0 %d, x0 %d, h %d, w %d) at d = %d",
               by0, bx0, hb, wb, sy0, sx0, sy1 - sy0 + 1, sx1 - sx0 + 1, y0, x0, h, w, d);
-  b.tiles = tiles; b.slot = slot; b.w_lo = w_lo; b.w_hi = w_hi; b.status = status;
-  b.out_f = out_u8 ? nullptr : (float*)out;
-  b.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
-  b.n = n; b.y0 = y0; b.x0 = x0; b.h = h; b.w = w;
   a.below = below; a.by0 = by0; a.bx0 = bx0; a.hb = hb; a.wb = wb; a.Hj = Hj; a.Wj = Wj; a.d = d;
   a.inv = 1.0f / (float)(2 << d);
-  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0) + 12.0 * hb * wb);
-  hipLaunchKernelGGL(tile_compose_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
-  return check_launch("tile_compose_kernel");
+  return window_launch(tile_compose_kernel, "tile_compose_kernel", a, b, 12.0 * hb * wb, stream);
 }
 
 int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32_t* dirty, const float* w_lo, const float* w_hi,
                      int H, int W, int th, int tw, int V, int cy0, int cx0, int ch, int cw, int y0, int x0, int h, int w, void* out,
                      int out_u8, int32_t* status, void* stream) {
-  RefreshArgs a;
+  const char* who = "vam_tile_refresh";
+  RefreshArgs a = {};
   BlendArgs& b = a.b;
-  if (int rc = tile_geometry("vam_tile_refresh", H, W, th, tw, V, &b.g)) return rc;
-  VAM_REQUIRE(tiles && slot && dirty && out && status, "vam_tile_refresh: need tiles, slot, dirty, out and status");
-  VAM_REQUIRE(V == 0 || (w_lo && w_hi), "vam_tile_refresh: an overlap of %d needs the two ramp tables", V);
-  VAM_REQUIRE(n >= 1, "vam_tile_refresh: a buffer of %d tiles", n);
-  VAM_REQUIRE(cy0 >= 0 && cx0 >= 0 && ch >= 1 && cw >= 1 && ch <= H - cy0 && cw <= W - cx0,
-              "vam_tile_refresh: the canvas window (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d picture", cy0, cx0, ch,
-              cw, H, W);
+  if (int rc = window_tiles(who, &b, false, tiles && slot && dirty && out && status, "tiles, slot, dirty, out and status", tiles, n, slot, w_lo,
+                            w_hi, status, H, W, th, tw, V))
+    return rc;
+  if (int rc = window_inside(who, "canvas window", &b, cy0, cx0, ch, cw, H, W)) return rc;
   VAM_REQUIRE(y0 >= cy0 && x0 >= cx0 && h >= 1 && w >= 1 && h <= cy0 + ch - y0 && w <= cx0 + cw - x0,
               "vam_tile_refresh: the box (y0 %d, x0 %d, h %d, w %d) does not lie inside the canvas window (y0 %d, x0 %d, h %d, w %d)",
               y0, x0, h, w, cy0, cx0, ch, cw);
-  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_tile_refresh: out_u8 is 0 (fp32 [3, h, w]) or 1 (uint8 [h, w, 3]), got %d", out_u8);
-  VAM_REQUIRE(cdiv(h, 4) <= 65535u, "vam_tile_refresh: a box of %d rows exceeds one launch", h);
-  b.tiles = tiles; b.slot = slot; b.w_lo = w_lo; b.w_hi = w_hi; b.status = status;
-  b.out_f = out_u8 ? nullptr : (float*)out;
-  b.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
-  b.n = n; b.y0 = y0; b.x0 = x0; b.h = h; b.w = w;
   a.dirty = dirty; a.cy0 = cy0; a.cx0 = cx0; a.ch = ch; a.cw = cw;
-  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, (double)h * w * (out_u8 ? 15.0 : 24.0));
-  hipLaunchKernelGGL(tile_refresh_kernel, dim3(cdiv(cdiv(w, 4), 64), cdiv(h, 4)), dim3(64, 4), 0, (hipStream_t)stream, a);
-  return check_launch("tile_refresh_kernel");
+  b.y0 = y0; b.x0 = x0; b.h = h; b.w = w;
+  if (int rc = window_out(who, "box", &b, out, out_u8)) return rc;
+  return window_launch(tile_refresh_kernel, "tile_refresh_kernel", a, b, 0.0, stream);
 }
 
 int vam_picture_halve(const float* src, int C, int Hs, int Ws, float* dst, int mode, void* stream) {

@@ -830,6 +830,29 @@ def tile_schedule(maps: torch.Tensor, coords: torch.Tensor, out: torch.Tensor, t
                                        coords.data_ptr(), n, out.data_ptr(), stream_ptr()), "vam_tile_schedule")
 
 
+def _check_tiles(tiles, slot, w_lo, w_hi, H, W, overlap, hw, out, status, device=None):
+    """The asserts that :func:`tile_blend`, :func:`tile_refresh` and :func:`tile_compose` share: ``tiles``, ``slot`` (against
+    the grid the library derives), the ramps and ``status`` (all on ``device``, by default wherever ``tiles`` lies) and ``out``,
+    which holds a window of ``hw`` = (h, w).  ``tiles`` None (compose without tiles): ``out`` alone.  Returns (n, th, tw)."""
+    n = th = tw = 0
+    if tiles is not None:
+        assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3
+        assert tiles.is_cuda if device is None else tiles.device == device
+        device = tiles.device
+        n, _, th, tw = tiles.shape
+        assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and slot.device == device
+        if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):   # the grid the library derives; anything else it refuses
+            grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
+            assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
+        for t in (w_lo, w_hi):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == device)
+        assert status is not None and status.dtype == torch.int32 and status.numel() == 1 and status.device == device
+    assert out.is_contiguous() and out.device == device
+    assert (out.dtype == torch.float32 and tuple(out.shape) == (3,) + hw) or (out.dtype == torch.uint8 and tuple(out.shape) == hw + (3,)), \
+        (out.dtype, tuple(out.shape), hw)
+    return n, th, tw
+
+
 def tile_blend(tiles: torch.Tensor, slot: torch.Tensor, w_lo: Optional[torch.Tensor], w_hi: Optional[torch.Tensor], H: int, W: int,
                overlap: int, window: Sequence[int], out: torch.Tensor, status: torch.Tensor):
     """The window (y0, x0, h, w) of a picture of H x W blended from decoded tiles: ``tiles`` fp32
@@ -837,18 +860,7 @@ def tile_blend(tiles: torch.Tensor, slot: torch.Tensor, w_lo: Optional[torch.Ten
     (None for overlap 0).  ``out``: fp32 [3, h, w], or uint8 [h, w, 3] as rint(clamp(v, 0, 1) * 255).  ``status`` int32 [1],
     cleared by the caller, becomes 1 when a pixel needs an absent tile.  One launch; capturable."""
     y0, x0, h, w = (int(v) for v in window)
-    assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.is_cuda
-    n, _, th, tw = tiles.shape
-    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and slot.device == tiles.device
-    if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):       # the grid the library derives; anything else it refuses
-        grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
-        assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
-    for t in (w_lo, w_hi):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == tiles.device)
-    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == tiles.device
-    assert out.is_contiguous() and out.device == tiles.device
-    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, h, w)) or (out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3)), \
-        (out.dtype, tuple(out.shape), (h, w))
+    n, th, tw = _check_tiles(tiles, slot, w_lo, w_hi, H, W, overlap, (h, w), out, status)
     rc = L.load().vam_tile_blend(tiles.data_ptr(), n, slot.data_ptr(), w_lo.data_ptr() if w_lo is not None else None,
                                  w_hi.data_ptr() if w_hi is not None else None, int(H), int(W), th, tw, int(overlap), y0, x0, h, w,
                                  out.data_ptr(), int(out.dtype == torch.uint8), status.data_ptr(), stream_ptr())
@@ -864,20 +876,8 @@ def tile_refresh(tiles: torch.Tensor, slot: torch.Tensor, dirty: torch.Tensor, w
     tiles are not read.  One launch; capturable."""
     cy0, cx0, ch, cw = (int(v) for v in window)
     y0, x0, h, w = (int(v) for v in box)
-    assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.is_cuda
-    n, _, th, tw = tiles.shape
-    for t in (slot, dirty):
-        assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.device == tiles.device
-    assert slot.shape == dirty.shape
-    if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):       # the grid the library derives; anything else it refuses
-        grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
-        assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
-    for t in (w_lo, w_hi):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == tiles.device)
-    assert status.dtype == torch.int32 and status.numel() == 1 and status.device == tiles.device
-    assert out.is_contiguous() and out.device == tiles.device
-    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, ch, cw)) or (out.dtype == torch.uint8 and tuple(out.shape) == (ch, cw, 3)), \
-        (out.dtype, tuple(out.shape), (ch, cw))
+    n, th, tw = _check_tiles(tiles, slot, w_lo, w_hi, H, W, overlap, (ch, cw), out, status)
+    assert dirty.dtype == torch.int32 and dirty.is_contiguous() and dirty.shape == slot.shape and dirty.device == tiles.device
     rc = L.load().vam_tile_refresh(tiles.data_ptr(), n, slot.data_ptr(), dirty.data_ptr(), w_lo.data_ptr() if w_lo is not None else None,
                                    w_hi.data_ptr() if w_hi is not None else None, int(H), int(W), th, tw, int(overlap), cy0, cx0, ch, cw,
                                    y0, x0, h, w, out.data_ptr(), int(out.dtype == torch.uint8), status.data_ptr(), stream_ptr())
@@ -899,20 +899,7 @@ def tile_compose(tiles: Optional[torch.Tensor], slot: Optional[torch.Tensor], w_
     assert below.dtype == torch.float32 and below.is_contiguous() and tuple(below.shape) == (3, hb, wb) and below.is_cuda, \
         (below.dtype, tuple(below.shape), (hb, wb))
     assert (tiles is None) == (slot is None)
-    n = th = tw = 0
-    if tiles is not None:
-        assert tiles.dtype == torch.float32 and tiles.is_contiguous() and tiles.dim() == 4 and tiles.shape[1] == 3 and tiles.device == below.device
-        n, _, th, tw = tiles.shape
-        assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.dim() == 2 and slot.device == below.device
-        if H >= 1 and W >= 1 and 0 <= 2 * overlap <= min(th, tw):   # the grid the library derives; anything else it refuses
-            grid = tuple(max(1, -(-(n_ - overlap) // (t_ - overlap))) for n_, t_ in ((H, th), (W, tw)))
-            assert tuple(slot.shape) == grid, (tuple(slot.shape), grid)
-        for t in (w_lo, w_hi):
-            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == overlap and t.device == below.device)
-        assert status is not None and status.dtype == torch.int32 and status.numel() == 1 and status.device == below.device
-    assert out.is_contiguous() and out.device == below.device
-    assert (out.dtype == torch.float32 and tuple(out.shape) == (3, h, w)) or (out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3)), \
-        (out.dtype, tuple(out.shape), (h, w))
+    n, th, tw = _check_tiles(tiles, slot, w_lo, w_hi, H, W, overlap, (h, w), out, status, below.device)
     Hj, Wj = (-(-int(v) // (1 << d)) for v in (H, W)) if 1 <= d <= 15 else (0, 0)
     ptr = lambda t: t.data_ptr() if t is not None else None
     rc = L.load().vam_tile_compose(ptr(tiles), n, ptr(slot), ptr(w_lo), ptr(w_hi), int(H), int(W), th, tw, int(overlap), y0, x0, h, w,

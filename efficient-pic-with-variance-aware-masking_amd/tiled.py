@@ -647,6 +647,23 @@ def _ramps_on(have, V: int, device):
     return have
 
 
+def _check_dtype(what: str, dtype):
+    """The dtype of an output, torch.float32 when None."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+    return dtype
+
+
+def _slot_table(g: dict, tiles) -> np.ndarray:
+    """int32 [R, C] for a buffer that holds just ``tiles``, in their order: i at the i-th of them, -1 elsewhere."""
+    slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
+    for i, (r, c) in enumerate(tiles):
+        slot[r, c] = i
+    return slot
+
+
 def _check_pooled(model, thresholds, dec, containers, part):
     """A version-2 header's thresholds against the tiles' marks: the decoder's OWN sigma, in its own rank order
     (vam_pool_keys), counted against the header's thresholds (vam_threshold_counts), must give the counts the tiles'
@@ -721,6 +738,13 @@ def _stage_of(what: str, scheduled: bool, stages: int, q, mark, stage) -> Option
     return stage
 
 
+def _level_of(what: str, stages: int, meta: Optional[dict], thresholds, q, mark, stage) -> Tuple[Optional[int], Optional[int]]:
+    """(mark, stage) that a call with (q, mark, stage) means, checked against what the picture is.  ``meta`` None: no head
+    is whole yet, the marks are not known, and no tile is available anyway."""
+    stage = _stage_of(what, stages > 0, stages, q, mark, stage)
+    return (None if meta is None else _mark_of(what, meta["marks"], thresholds, q, mark)), stage
+
+
 def _decode_window(what: str, model, coder, thresholds, tiles, stream_of, group: int, g: dict, q, mark, stage):
     """fp32 [len(tiles), 3, th, tw] on the model's device: the tiles (r, c) of ``tiles``, ``group`` at a time through
     :func:`_decode_tiles`; ``stream_of(r, c)`` gives a tile's bytes.  When a group is refused its tiles are tried alone, and
@@ -772,14 +796,16 @@ def _not_available(what: str, s: _Picture, window, rc, missing: int, level: Opti
                       "level to fill it from")
 
 
-def _compose_out(what: str, g: dict, window, buf, slot: Optional[np.ndarray], ramps_on, below, below_window, shift, dtype):
-    """The output of one ``compose``: ``buf`` fp32 [n, 3, th, tw] and ``slot`` int32 [R, C] (both None: no tile is
-    available); ``below`` None: every tile of the window is available and the result is vam_tile_blend's.  ``ramps_on(dev)``
-    gives the blend ramps there."""
+def _blend_out(what: str, g: dict, window, buf, slot: Optional[np.ndarray], ramps_on, dtype, below=None, below_window=None, shift=None,
+               dirty: Optional[np.ndarray] = None, box=None, out=None):
+    """One launch over ``window`` from ``buf`` fp32 [n, 3, th, tw] and ``slot`` int32 [R, C] (both None: no tile is
+    available); ``ramps_on(dev)`` gives the blend ramps there.  ``dirty`` int32 [R, C]: vam_tile_refresh of ``box`` into
+    ``out``, a canvas of the window, whose dtype holds (``dtype`` is not looked at when ``out`` is given); else ``out`` is new,
+    of ``dtype``, and with ``below`` it is vam_tile_compose's, without (every tile of the window is available)
+    vam_tile_blend's."""
     import torch
     from . import _lib as L
     from . import ops
-    y0, x0, h, w = window
     if below is not None:
         if not isinstance(below, torch.Tensor) or below.dtype != torch.float32 or below.dim() != 3 or below.shape[0] != 3 or not below.is_cuda:
             raise ValueError(f"{what}: below is an fp32 tensor [3, hb, wb] on the device, got "
@@ -797,10 +823,14 @@ def _compose_out(what: str, g: dict, window, buf, slot: Optional[np.ndarray], ra
     with torch.no_grad():
         w_lo, w_hi = ramps_on(dev) if buf is not None and g["V"] else (None, None)
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
-            else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        if out is None:
+            h, w = window[2:]
+            out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
+                else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
         slot_dev = None if slot is None else torch.from_numpy(slot).to(dev)
-        if below is None:
+        if dirty is not None:
+            ops.tile_refresh(buf, slot_dev, torch.from_numpy(dirty).to(dev), w_lo, w_hi, g["H"], g["W"], g["V"], window, box, out, status)
+        elif below is None:
             ops.tile_blend(buf, slot_dev, w_lo, w_hi, g["H"], g["W"], g["V"], window, out, status)
         else:
             ops.tile_compose(buf, slot_dev, w_lo, w_hi, g["H"], g["W"], g["V"], window, below.detach().contiguous(), below_window, shift,
@@ -843,16 +873,13 @@ class PictureDecoder:
         self._ramps = _ramps_on(self._ramps, self.grid["V"], dev)
         return self._ramps
 
-    def _level(self, what: str, mark, stage) -> Tuple[Optional[int], Optional[int]]:
-        """(mark, stage) of a call without q, checked as :meth:`decode` checks them; before any head is whole the marks are
-        not known, and no tile is available anyway."""
-        stage = _stage_of(what, self.scheduled, self.stages, None, mark, stage)
-        return (None if self.meta is None else _mark_of(what, self.meta["marks"], self._s.thresholds, None, mark)), stage
+    def _level(self, what: str, q, mark, stage) -> Tuple[Optional[int], Optional[int]]:
+        return _level_of(what, self.stages, self.meta, self._s.thresholds, q, mark, stage)
 
     def available(self, window=None, mark: Optional[int] = None, stage: Optional[int] = None) -> List[Tuple[int, int]]:
         """Those of ``tiles_for(window)`` that are available: present, the head whole and, at ``mark`` or ``stage`` m, the
         rounds 0 .. m whole."""
-        mark, stage = self._level("PictureDecoder.available", mark, stage)
+        mark, stage = self._level("PictureDecoder.available", None, mark, stage)
         tiles = tiles_for(self.grid, _window(self.grid, window, "PictureDecoder.available"))
         return _available(self.rounds, tiles, stage if stage is not None else mark)
 
@@ -866,10 +893,8 @@ class PictureDecoder:
         import torch
         what = "PictureDecoder.compose"
         g, s = self.grid, self._s
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
-        mark, stage = self._level(what, mark, stage)
+        dtype = _check_dtype(what, dtype)
+        mark, stage = self._level(what, None, mark, stage)
         level = stage if stage is not None else mark
         window = _window(g, window, what)
         wanted = tiles_for(g, window)
@@ -882,10 +907,8 @@ class PictureDecoder:
             with torch.no_grad():
                 buf = _decode_window(what, self.m, self.coder, s.thresholds, tiles, lambda r, c: s.stream(self._d, r * g["C"] + c),
                                      self.group, g, None, mark, stage)
-            slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
-            for i, (r, c) in enumerate(tiles):
-                slot[r, c] = i
-        out = _compose_out(what, g, window, buf, slot, self._ramps_at, below, below_window, shift, dtype)
+            slot = _slot_table(g, tiles)
+        out = _blend_out(what, g, window, buf, slot, self._ramps_at, dtype, below, below_window, shift)
         self.last_tiles = self.last_decoded = tiles
         return out
 
@@ -907,42 +930,26 @@ class PictureDecoder:
         whose bytes end before stage k is named.  On a scheduled picture ``mark=k`` gives the same pixels and ``q`` is a
         ValueError that points here; on a plain picture ``stage`` is a ValueError."""
         import torch
-        from . import _lib as L
-        from . import ops
+        what = "PictureDecoder.decode"
         g, s = self.grid, self._s
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"PictureDecoder.decode: dtype is torch.float32 or torch.uint8, got {dtype}")
+        dtype = _check_dtype(what, dtype)
         if self.partial and len(self._d) < s.need:          # a prefix that ends inside the heads: the tiles the window needs must be whole
             win = _window(g, window, "PictureDecoder.decode")
             for r, c in tiles_for(g, win):
                 if s.present[r * g["C"] + c] and self.rounds[r, c] < 0:
                     raise ValueError(f"PictureDecoder.decode: the window {win} needs tile ({r}, {c}), whose head has not arrived: "
                                      f"{s.need - len(self._d)} bytes are missing before every tile's head is whole")
-        stage = _stage_of("PictureDecoder.decode", self.scheduled, self.stages, q, mark, stage)
-        if self.meta is not None:                           # None: a partial prefix without a whole head, whose tiles are refused below
-            mark = _mark_of("PictureDecoder.decode", self.meta["marks"], s.thresholds, q, mark)
-        y0, x0, h, w = _window(g, window, "PictureDecoder.decode")
+        mark, stage = self._level(what, q, mark, stage)       # no head is whole (a partial prefix): the tiles are refused below
+        y0, x0, h, w = _window(g, window, what)
         tiles = tiles_for(g, (y0, x0, h, w))
         for r, c in tiles:
             if not s.present[r * g["C"] + c]:
                 raise ValueError(f"PictureDecoder.decode: the window ({y0}, {x0}, {h}, {w}) needs tile ({r}, {c}), which is absent "
                                  "from this codestream")
         with torch.no_grad():
-            buf = _decode_window("PictureDecoder.decode", self.m, self.coder, s.thresholds, tiles,
-                                 lambda r, c: s.stream(self._d, r * g["C"] + c), self.group, g, q, mark, stage)
-            dev = buf.device
-            slot = np.full((g["R"], g["C"]), -1, dtype=np.int32)
-            for i, (r, c) in enumerate(tiles):
-                slot[r, c] = i
-            self._ramps = w_lo, w_hi = _ramps_on(self._ramps, g["V"], dev)
-            status = torch.zeros((1,), dtype=torch.int32, device=dev)
-            out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
-                else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-            ops.tile_blend(buf, torch.from_numpy(slot).to(dev), w_lo if g["V"] else None, w_hi if g["V"] else None, g["H"], g["W"],
-                           g["V"], (y0, x0, h, w), out, status)
-            if int(status.item()):
-                raise L.VamError("PictureDecoder.decode: vam_tile_blend met an absent tile inside the window")
+            buf = _decode_window(what, self.m, self.coder, s.thresholds, tiles, lambda r, c: s.stream(self._d, r * g["C"] + c),
+                                 self.group, g, q, mark, stage)
+        out = _blend_out(what, g, (y0, x0, h, w), buf, _slot_table(g, tiles), self._ramps_at, dtype)
         self.last_tiles = tiles
         return out
 
@@ -1189,9 +1196,7 @@ class PictureStream:
         if not partial and not fs.ready:
             raise ValueError(f"{what}: nothing to decode yet: {fs.need()} bytes are missing before every tile's head is whole")
         s, g = fs._s, fs._s.g
-        stage = _stage_of(what, s.stages > 0, s.stages, q, mark, stage)
-        if fs.meta is not None:                             # None: no head is whole yet (compose), and no tile is available
-            mark = _mark_of(what, fs.meta["marks"], s.thresholds, q, mark)
+        mark, stage = _level_of(what, s.stages, fs.meta, s.thresholds, q, mark, stage)
         y0, x0, h, w = _window(g, window, what)
         tiles = tiles_for(g, (y0, x0, h, w))
         if partial:
@@ -1244,33 +1249,18 @@ class PictureStream:
         self.decoded_total += len(missing)
         return (y0, x0, h, w), tiles, level, slot, gen
 
-    def _blend_inputs(self):
-        g = self.feed_state._s.g
-        self._ramps = _ramps_on(self._ramps, g["V"], self._pool.device)
-        return self._ramps if g["V"] else (None, None)
+    def _ramps_at(self, dev):
+        self._ramps = _ramps_on(self._ramps, self.feed_state._s.g["V"], dev)
+        return self._ramps
 
     def view(self, window=None, q: Optional[float] = None, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
         """``PictureDecoder(model, everything fed so far).decode(window, q, mark, stage, dtype)``, bit for bit, with its
         ValueErrors under the prefix ``PictureStream.view:``; only the tiles of the window that are not cached at that level
         run the network (``last_decoded``).  Before ``ready`` a ValueError states ``need()``."""
-        import torch
-        from . import _lib as L
-        from . import ops
         what = "PictureStream.view"
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
-        (y0, x0, h, w), _, _, slot, _ = self._update(what, window, q, mark, stage)
-        g, dev = self.feed_state._s.g, self._pool.device
-        with torch.no_grad():
-            w_lo, w_hi = self._blend_inputs()
-            status = torch.zeros((1,), dtype=torch.int32, device=dev)
-            out = torch.empty((3, h, w), dtype=torch.float32, device=dev) if dtype == torch.float32 \
-                else torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
-            ops.tile_blend(self._pool, torch.from_numpy(slot).to(dev), w_lo, w_hi, g["H"], g["W"], g["V"], (y0, x0, h, w), out, status)
-            if int(status.item()):
-                raise L.VamError(f"{what}: vam_tile_blend met an absent tile inside the window")
-        return out
+        dtype = _check_dtype(what, dtype)
+        window, _, _, slot, _ = self._update(what, window, q, mark, stage)
+        return _blend_out(what, self.feed_state._s.g, window, self._pool, slot, self._ramps_at, dtype)
 
     def available(self, window=None, mark: Optional[int] = None, stage: Optional[int] = None) -> List[Tuple[int, int]]:
         """``PictureDecoder(model, everything fed so far, partial=True).available(window, mark, stage)``; [] before the header
@@ -1279,9 +1269,7 @@ class PictureStream:
         if fs._s is None:
             return []
         s = fs._s
-        stage = _stage_of(what, s.stages > 0, s.stages, None, mark, stage)
-        if fs.meta is not None:
-            mark = _mark_of(what, fs.meta["marks"], s.thresholds, None, mark)
+        mark, stage = _level_of(what, s.stages, fs.meta, s.thresholds, None, mark, stage)
         return _available(fs.tile_rounds, tiles_for(s.g, _window(s.g, window, what)), stage if stage is not None else mark)
 
     def compose(self, window, below, below_window, shift, mark: Optional[int] = None, stage: Optional[int] = None, dtype=None):
@@ -1289,15 +1277,11 @@ class PictureStream:
         the header on: the available tiles of the window come from the cache (``last_tiles``), only those not cached at that
         level run the network (``last_decoded``), and one vam_tile_compose launch fills the rest from ``below``.  The cache's
         keys, eviction and ``cache_tiles`` refusal are :meth:`view`'s."""
-        import torch
         what = "PictureStream.compose"
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        dtype = _check_dtype(what, dtype)
         window, tiles, _, slot, _ = self._update(what, window, None, mark, stage, below)
-        g = self.feed_state._s.g
-        ramps_at = lambda dev: self._blend_inputs()
-        return _compose_out(what, g, window, self._pool if tiles else None, slot if tiles else None, ramps_at, below, below_window, shift, dtype)
+        return _blend_out(what, self.feed_state._s.g, window, self._pool if tiles else None, slot if tiles else None, self._ramps_at, dtype,
+                          below, below_window, shift)
 
     def canvas(self, window=None, dtype=None) -> "Canvas":
         """A persistent output of ``window`` (None: the picture) that :meth:`Canvas.refresh` keeps equal to :meth:`view`."""
@@ -1315,9 +1299,7 @@ class Canvas:
         fs = stream.feed_state
         if fs._s is None:
             raise ValueError(f"{what}: the header is not complete yet: {fs.need()} bytes are missing")
-        dtype = torch.float32 if dtype is None else dtype
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+        dtype = _check_dtype(what, dtype)
         g = fs._s.g
         self.stream, self.window, self.dtype = stream, _window(g, window, what), dtype
         dev, (_, _, h, w) = next(stream.m.parameters()).device, self.window
@@ -1333,13 +1315,10 @@ class Canvas:
         (y0, x0, h, w), in picture coordinates, that was visited: the bounding box of the dirty tiles' extents inside the
         window; None when nothing was dirty, and then nothing is launched.  Afterwards ``out`` equals
         ``view(window, q, mark, stage, dtype)`` of the same moment, bit for bit."""
-        import torch
-        from . import _lib as L
-        from . import ops
         what = "Canvas.refresh"
         st = self.stream
         (cy0, cx0, ch, cw), tiles, level, slot, gen = st._update(what, self.window, q, mark, stage)
-        g, dev = st.feed_state._s.g, st._pool.device
+        g = st.feed_state._s.g
         if level != self._level:
             self._gen[:] = -1
         dirty = np.zeros(gen.shape, dtype=np.int32)
@@ -1351,13 +1330,7 @@ class Canvas:
         y0, y1 = max(cy0, int(rows[0]) * g["Sy"]), min(cy0 + ch, int(rows[-1]) * g["Sy"] + g["th"])
         x0, x1 = max(cx0, int(cols[0]) * g["Sx"]), min(cx0 + cw, int(cols[-1]) * g["Sx"] + g["tw"])
         box = (y0, x0, y1 - y0, x1 - x0)
-        with torch.no_grad():
-            w_lo, w_hi = st._blend_inputs()
-            status = torch.zeros((1,), dtype=torch.int32, device=dev)
-            ops.tile_refresh(st._pool, torch.from_numpy(slot).to(dev), torch.from_numpy(dirty).to(dev), w_lo, w_hi, g["H"], g["W"],
-                             g["V"], (cy0, cx0, ch, cw), box, self.out, status)
-            if int(status.item()):
-                raise L.VamError(f"{what}: vam_tile_refresh met an absent tile inside the window")
+        _blend_out(what, g, self.window, st._pool, slot, st._ramps_at, self.dtype, dirty=dirty, box=box, out=self.out)
         for r, c in tiles:
             self._gen[r, c] = gen[r, c]
         self._level = level
