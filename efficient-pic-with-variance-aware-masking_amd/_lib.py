@@ -336,6 +336,7 @@ _SIGNATURES = {
     "vam_tile_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] + [C.c_int] * 7
                          + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vam_picture_halve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vam_picture_resample": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_int64] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
     "vam_graph_begin": (C.c_int, [C.c_void_p]),
     "vam_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "vam_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),

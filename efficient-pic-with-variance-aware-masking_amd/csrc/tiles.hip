@@ -38,10 +38,20 @@
 //                         and never 0, and the sources clamp(a) and clamp(a + 1) in 0 .. N_j - 1; with lerp(p, q, f) =
 //                         p + f * (q - p), three fp32 operations that nothing contracts, the value is
 //                         lerp(lerp(s[r0][c0], s[r0][c1], fx), lerp(s[r1][c0], s[r1][c1], fx), fy).  The switch is hard.
+//   picture_resample_kernel  a viewport: the rect (y0, x0, h, w) / unit of the picture, read from level k,
+//                         shown in oh x ow pixels at any zoom.  Along an axis, output coordinate P has its centre at n / D of
+//                         level k (pixel i centred at i + 1/2): D = 2^(k+1) oh unit, n = 2 oh y0 + (2 P + 1) h - 2^k oh unit,
+//                         T = max(D, 2 h); the taps are the i with |D i - n| < T, of integer weight u_i = T - |D i - n| and
+//                         fp32 weight float(u_i) / float(sum u), the source clamp(i, 0, N_k - 1).  The value is the sum over
+//                         the row taps of wy * (sum over the column taps of wx * s), ascending, each sum from its first term,
+//                         every operation one fp32 operation.  All of it comes from the viewport's integers in the thread.
+//                         Three kernels, one value: up to 4 taps per axis unrolled with cached reads, the same with the block's
+//                         source box staged in LDS where the column scale is 1.9 .. 2, and a bounded loop up to 32 taps.
 // All move data only: 16-byte loads and stores where the four pixels share their tiles and the addresses are aligned,
 // scalar ones otherwise (a window may start at any column).  They allocate nothing and can be captured.
 #include "common.h"
 #include <cstdint>
+#include <type_traits>
 
 namespace vam {
 namespace {
@@ -449,6 +459,264 @@ __global__ __launch_bounds__(256) void picture_halve_kernel(const HalveArgs a) {
   }
 }
 
+// One axis of a viewport at level k, in units of 1 / D of a level-k pixel: output coordinate P has its
+// centre at n(P) / D with n(P) = n0 + P dn, the tent reaches T = max(D, 2 extent) to either side, the level has N pixels
+// along the axis and src's window begins at o.  Everything is below 2^53: exact in a long and in a double.
+struct ResampleAxis {
+  long D, T, n0, dn;
+  int N, o;
+};
+
+struct ResampleArgs {
+  const float* src;
+  float* out_f;
+  uint8_t* out_u8;
+  ResampleAxis y, x;
+  int C, hs, ws, oh, ow;
+};
+
+// floor(n / D) for D > 0.  The fp64 quotient of two exact operands is within 2^-27 of the true one here (it is below 2^26),
+// so its floor is the true floor or one above it; the remainder, in integers, says which.
+__device__ __forceinline__ long floor_div(long n, long D) {
+  long q = (long)floor((double)n / (double)D);
+  const long r = n - q * D;
+  if (r < 0) --q;
+  else if (r >= D) ++q;
+  return q;
+}
+
+__device__ __forceinline__ long abs_l(long v) { return v < 0 ? -v : v; }
+
+// Level coordinate i, clamped to the level (the edge is replicated), as an offset into a window that begins at o.
+__device__ __forceinline__ int window_index(long i, int N, int o) { return (int)(i < 0 ? 0 : i > N - 1 ? N - 1 : i) - o; }
+
+// The taps of coordinate P where the scale is at most 2 (T <= 2 D): a - 1 .. a + 2 with a = floor(n / D), r = n - a D, at the
+// distances D + r, r, D - r, 2 D - r.  A weight u / S is never 0 (u >= 1, S < 2^46), so w == 0 marks a slot without a tap; such
+// a slot carries the index of tap a, which always is one, so that it may be read all the same: reads need no branch.
+struct Taps4 {
+  int i[4];
+  float w[4];
+};
+
+__device__ __forceinline__ Taps4 taps4(const ResampleAxis& ax, int P) {
+  const long n = ax.n0 + P * ax.dn;
+  const long a = floor_div(n, ax.D), r = n - a * ax.D;
+  const long u[4] = {ax.T - ax.D - r, ax.T - r, ax.T - ax.D + r, ax.T - 2 * ax.D + r};
+  long S = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) S += u[j] > 0 ? u[j] : 0;
+  const float fS = (float)S;
+  Taps4 t;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    t.w[j] = u[j] > 0 ? (float)u[j] / fS : 0.0f;           // two round-to-nearest conversions, one correctly rounded division
+    t.i[j] = window_index(u[j] > 0 ? a - 1 + j : a, ax.N, ax.o);
+  }
+  return t;
+}
+
+// The taps of coordinate P at any scale up to 16: lo .. lo + cnt - 1 (cnt <= 32), tap lo + j at the signed distance e0 + j D.
+struct TapsN {
+  long e0, lo;
+  int cnt;
+  float fS;
+};
+
+__device__ __forceinline__ TapsN tapsN(const ResampleAxis& ax, int P) {
+  const long n = ax.n0 + P * ax.dn;
+  TapsN t;
+  t.lo = floor_div(n - ax.T, ax.D) + 1;                    // the first i with D i - n > -T
+  const long cnt = floor_div(n + ax.T - 1, ax.D) - t.lo + 1;      // up to the last i with D i - n < T
+  t.cnt = (int)(cnt < 32 ? cnt : 32);                      // the bound; the host refuses a scale above 16, which has no more
+  t.e0 = ax.D * t.lo - n;
+  long S = 0;
+  for (int j = 0; j < t.cnt; ++j) S += ax.T - abs_l(t.e0 + j * ax.D);
+  t.fS = (float)S;
+  return t;
+}
+
+__device__ __forceinline__ float tapN_weight(const ResampleAxis& ax, const TapsN& t, int j) {
+  return (float)(ax.T - abs_l(t.e0 + j * ax.D)) / t.fS;
+}
+
+// One plane's four pixels: v[k] = sum over the row taps r of wy_r * (sum over pixel k's column taps c of wx_c * s[r][c]),
+// taps ascending, every sum from its first term, every product and add one fp32 operation.  Pixels past the row's end were
+// given the last column's taps: their reads stay inside and they are never stored.  A wave shares its output row, so the row
+// slots are in scalar registers and an empty one is skipped by the whole wave.  Along the columns the outer slots a - 1 and
+// a + 2 are skipped by the whole launch when the scale is at most 1 (`wide` false: T = D leaves a and a + 1); a slot that is
+// read is read without a branch, so that a row's loads are in flight together, and a select leaves an empty slot out of the
+// sum: the operations performed are those of the taps alone.
+__device__ __forceinline__ void resample_plane(const float* s, int pitch, const Taps4& ty, const Taps4 (&tx)[4], bool wide, float (&v)[4]) {
+  bool started = false;
+#pragma unroll
+  for (int jr = 0; jr < 4; ++jr) {
+    if (ty.w[jr] == 0.0f) continue;
+    const float* row = s + (long)ty.i[jr] * pitch;
+    float q[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      q[k][1] = row[tx[k].i[1]];
+      q[k][2] = row[tx[k].i[2]];
+      if (wide) {
+        q[k][0] = row[tx[k].i[0]];
+        q[k][3] = row[tx[k].i[3]];
+      } else {
+        q[k][0] = q[k][3] = 0.0f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float in = __fmul_rn(tx[k].w[1], q[k][1]);                                // tap a: always there
+      in = tx[k].w[0] != 0.0f ? __fadd_rn(__fmul_rn(tx[k].w[0], q[k][0]), in) : in;
+      in = tx[k].w[2] != 0.0f ? __fadd_rn(in, __fmul_rn(tx[k].w[2], q[k][2])) : in;
+      in = tx[k].w[3] != 0.0f ? __fadd_rn(in, __fmul_rn(tx[k].w[3], q[k][3])) : in;
+      const float t = __fmul_rn(ty.w[jr], in);
+      v[k] = started ? __fadd_rn(v[k], t) : t;
+    }
+    started = true;
+  }
+}
+
+__device__ __forceinline__ void resample_plane(const ResampleArgs& a, const float* s, const TapsN& ty, const TapsN (&tx)[4], float (&v)[4]) {
+  for (int jr = 0; jr < ty.cnt; ++jr) {
+    const float wy = tapN_weight(a.y, ty, jr);
+    const float* row = s + (long)window_index(ty.lo + jr, a.y.N, a.y.o) * a.ws;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float in = 0.0f;
+      for (int jc = 0; jc < tx[k].cnt; ++jc) {
+        const float t = __fmul_rn(tapN_weight(a.x, tx[k], jc), row[window_index(tx[k].lo + jc, a.x.N, a.x.o)]);
+        in = jc ? __fadd_rn(in, t) : t;
+      }
+      const float t = __fmul_rn(wy, in);
+      v[k] = jr ? __fadd_rn(v[k], t) : t;
+    }
+  }
+}
+
+// Block (64, 4): a thread owns four consecutive pixels of one output row and every plane.  It works out the row's taps once
+// and each pixel's column taps once, from the viewport's integers alone (no table comes from the host), then reads src, a
+// window of the level that the host has checked to hold every tap, one value at a time: neighbouring lanes share them.
+// LOOP = false: at most four taps along both axes, held in registers; true: up to 32, their weights recomputed where used.
+// picture_resample_staged_kernel below is LOOP = false with src staged in LDS; the host picks it by the column scale.
+template <bool LOOP>
+__global__ __launch_bounds__(256) void picture_resample_kernel(const ResampleArgs a) {
+  using Taps = typename std::conditional<LOOP, TapsN, Taps4>::type;
+  const int x = 4 * (blockIdx.x * 64 + threadIdx.x), y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= a.ow || y >= a.oh) return;
+  const int nv = min(4, a.ow - x);
+  Taps ty, tx[4];
+  if constexpr (LOOP) {
+    ty = tapsN(a.y, y);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tx[k] = tapsN(a.x, min(x + k, a.ow - 1));
+  } else {
+    ty = taps4(a.y, y);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                          // blockDim.x is the wave: its lanes share y
+      ty.w[j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ty.w[j])));
+      ty.i[j] = __builtin_amdgcn_readfirstlane(ty.i[j]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tx[k] = taps4(a.x, min(x + k, a.ow - 1));
+  }
+  const bool wide = a.x.T > a.x.D;
+  const long plane = (long)a.hs * a.ws, at = (long)y * a.ow + x;
+  auto one = [&](int ch, float (&v)[4]) {
+    if constexpr (LOOP) resample_plane(a, a.src + ch * plane, ty, tx, v);
+    else resample_plane(a.src + ch * plane, a.ws, ty, tx, wide, v);
+  };
+  if (a.out_u8) {                                          // C = 3: the triples need all three planes
+    float acc[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) one(ch, acc[ch]);
+    BlendArgs b = {};
+    b.out_u8 = a.out_u8;
+    store_pixels<true>(b, at, 0, nv, 0u, acc);
+    return;
+  }
+  for (int ch = 0; ch < a.C; ++ch) {
+    float v[4];
+    one(ch, v);
+    float* dst = a.out_f + (long)ch * a.oh * a.ow + at;
+    if (nv == 4 && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) dst[k] = v[k];
+    }
+  }
+}
+
+// The unrolled kernel with the source staged in LDS, for column scales from 1.9 to 2, where a wave's reads of src lie 30 bytes
+// and more apart and the cached reads above cost up to half as much again (below 1.9 staging loses).  The
+// block's 4 x 256 pixels read a box of src of at most 3 * 2 + 4 rows and 255 * 2 + 4 columns: rows floor(n / D) - 1 of its first
+// row .. floor(n / D) + 2 of its last, columns likewise, clamped to the level and cut to the window of src (a slot outside
+// it is empty and carries the index of tap a).  Plane by plane the block copies the box with coalesced reads, waits, and
+// every thread takes its taps from LDS with resample_plane: the same operations on the same values as the kernel above.  A
+// thread past the output's edge takes the edge's taps, keeps to the barriers and stores nothing.
+constexpr int kStageRows = 11, kStagePitch = 520;
+
+__global__ __launch_bounds__(256) void picture_resample_staged_kernel(const ResampleArgs a) {
+  __shared__ float tile[kStageRows * kStagePitch];
+  const int bx = 256 * blockIdx.x, by = 4 * blockIdx.y;
+  const int x = bx + 4 * threadIdx.x, y = by + threadIdx.y;
+  const bool live = x < a.ow && y < a.oh;
+  const int nv = min(4, a.ow - x);
+  auto box = [&](const ResampleAxis& ax, int P0, int P1, int n_win, int* lo, int* hi) {
+    const int l = window_index(floor_div(ax.n0 + P0 * ax.dn, ax.D) - 1, ax.N, ax.o);
+    const int h = window_index(floor_div(ax.n0 + P1 * ax.dn, ax.D) + 2, ax.N, ax.o);
+    *lo = min(max(l, 0), n_win - 1);
+    *hi = min(max(h, 0), n_win - 1);
+  };
+  int rlo, rhi, clo, chi;
+  box(a.y, by, min(by + 3, a.oh - 1), a.hs, &rlo, &rhi);
+  box(a.x, bx, min(bx + 255, a.ow - 1), a.ws, &clo, &chi);
+  const int nr = min(rhi - rlo + 1, kStageRows), nc = min(chi - clo + 1, kStagePitch);
+  Taps4 ty = taps4(a.y, min(y, a.oh - 1)), tx[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ty.w[j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ty.w[j])));
+    ty.i[j] = __builtin_amdgcn_readfirstlane(ty.i[j]);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tx[k] = taps4(a.x, min(x + k, a.ow - 1));
+  const bool wide = a.x.T > a.x.D;
+  const long plane = (long)a.hs * a.ws, at = (long)y * a.ow + x;
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  auto one = [&](int ch, float (&v)[4]) {
+    __syncthreads();
+    const float* s = a.src + ch * plane + (long)rlo * a.ws + clo;
+    for (int r = 0; r < nr; ++r)
+      for (int c = tid; c < nc; c += 256) tile[r * kStagePitch + c] = s[(long)r * a.ws + c];
+    __syncthreads();
+    resample_plane(tile - rlo * kStagePitch - clo, kStagePitch, ty, tx, wide, v);
+  };
+  if (a.out_u8) {
+    float acc[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) one(ch, acc[ch]);
+    BlendArgs b = {};
+    b.out_u8 = a.out_u8;
+    if (live) store_pixels<true>(b, at, 0, nv, 0u, acc);
+    return;
+  }
+  for (int ch = 0; ch < a.C; ++ch) {
+    float v[4];
+    one(ch, v);
+    if (!live) continue;
+    float* dst = a.out_f + (long)ch * a.oh * a.ow + at;
+    if (nv == 4 && aligned16(dst)) {
+      *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < nv) dst[k] = v[k];
+    }
+  }
+}
+
 // The checks and the arguments that vam_tile_blend, vam_tile_refresh and vam_tile_compose share, in three steps that an entry
 // point puts its own checks between.  First the tiles: the geometry, the pointers (`have`: whether the entry point's are
 // there, `need`: their names), the ramps and n; `none`: compose without tiles, where th, tw and V are not looked at.
@@ -614,6 +882,71 @@ int vam_picture_halve(const float* src, int C, int Hs, int Ws, float* dst, int m
   ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0, 4.0 * C * ((double)Hs * Ws + (double)a.Hd * a.Wd));
   hipLaunchKernelGGL(picture_halve_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
   return check_launch("picture_halve_kernel");
+}
+
+int vam_picture_resample(const float* src, int C, int sy0, int sx0, int hs, int ws, int Hk, int Wk, int shift, int64_t y0, int64_t x0,
+                         int64_t h, int64_t w, int unit, int oh, int ow, void* out, int out_u8, void* stream) {
+  VAM_REQUIRE(src && out, "vam_picture_resample: need src and out");
+  VAM_REQUIRE(C >= 1 && C <= VAM_MAX_LAYER_LEVELS, "vam_picture_resample: 1 .. %d planes, got %d", VAM_MAX_LAYER_LEVELS, C);
+  VAM_REQUIRE(out_u8 == 0 || out_u8 == 1, "vam_picture_resample: out_u8 is 0 (fp32 [C, oh, ow]) or 1 (uint8 [oh, ow, 3]), got %d", out_u8);
+  VAM_REQUIRE(!out_u8 || C == 3, "vam_picture_resample: a uint8 output is [oh, ow, 3]: it takes 3 planes, got %d", C);
+  VAM_REQUIRE(unit >= 1 && unit <= 256, "vam_picture_resample: unit is 1 .. 256, got %d", unit);
+  VAM_REQUIRE(oh >= 1 && ow >= 1 && oh <= 65536 && ow <= 65536, "vam_picture_resample: an output of %d x %d: sides are 1 .. 65536", oh, ow);
+  VAM_REQUIRE(shift >= 0 && shift <= 15, "vam_picture_resample: shift is 0 .. 15 (the level), got %d", shift);
+  // the pictures that have this level: sides (N_k - 1) 2^shift + 1 .. N_k 2^shift, and 2^24 at the most
+  VAM_REQUIRE(Hk >= 1 && Wk >= 1 && ((long)(Hk - 1) << shift) < kTileMaxSide && ((long)(Wk - 1) << shift) < kTileMaxSide,
+              "vam_picture_resample: a level of %d x %d at shift %d is ceil(. / 2^shift) of no picture with sides 1 .. %d", Hk, Wk, shift,
+              kTileMaxSide);
+  const long Hmax = ((long)Hk << shift) < kTileMaxSide ? ((long)Hk << shift) : kTileMaxSide;
+  const long Wmax = ((long)Wk << shift) < kTileMaxSide ? ((long)Wk << shift) : kTileMaxSide;
+  VAM_REQUIRE(y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && y0 <= unit * Hmax && h <= unit * Hmax - y0 && x0 <= unit * Wmax && w <= unit * Wmax - x0,
+              "vam_picture_resample: the rect (y0 %lld, x0 %lld, h %lld, w %lld) / %d does not lie inside the %ld x %ld picture of this %d x %d "
+              "level at shift %d", (long long)y0, (long long)x0, (long long)h, (long long)w, unit, Hmax, Wmax, Hk, Wk, shift);
+  VAM_REQUIRE(sy0 >= 0 && sx0 >= 0 && hs >= 1 && ws >= 1 && hs <= Hk - sy0 && ws <= Wk - sx0,
+              "vam_picture_resample: the window of src (y0 %d, x0 %d, h %d, w %d) does not lie inside the %d x %d level", sy0, sx0, hs, ws,
+              Hk, Wk);
+  ResampleArgs a;
+  auto axis = [&](ResampleAxis* ax, long origin, long extent, int o_n, int N, int o) {
+    const long half = ((long)o_n * unit) << shift;          // D / 2: an output pixel's share of the axis at scale 1
+    ax->D = 2 * half;
+    ax->T = ax->D > 2 * extent ? ax->D : 2 * extent;
+    ax->n0 = 2 * o_n * origin + extent - half;
+    ax->dn = 2 * extent;
+    ax->N = N; ax->o = o;
+  };
+  axis(&a.y, y0, h, oh, Hk, sy0);
+  axis(&a.x, x0, w, ow, Wk, sx0);
+  if (a.y.T > 16 * a.y.D || a.x.T > 16 * a.x.D) {           // more than 32 taps: how many levels bring both scales to 16
+    int need = shift;
+    while ((h > 16 * (((long)oh * unit) << need) || w > 16 * (((long)ow * unit) << need)) && need < 40) ++need;
+    set_error("vam_picture_resample: the rect (h %lld, w %lld) / %d into %d x %d at shift %d has a scale of %.4g x %.4g: above 16; a "
+              "pyramid of %d levels has a level (shift %d) that brings it to 16 or below", (long long)h, (long long)w, unit, oh, ow, shift,
+              (double)h / (double)(a.y.D / 2), (double)w / (double)(a.x.D / 2), need + 1, need);
+    return VAM_EINVAL;
+  }
+  // the support window: clamp(first tap of the first output coordinate) .. clamp(last tap of the last one), per axis
+  auto fdiv = [](long n, long D) { return n >= 0 ? n / D : -((-n + D - 1) / D); };
+  auto clampN = [](long v, int N) { return (int)(v < 0 ? 0 : v > N - 1 ? N - 1 : v); };
+  auto first = [&](const ResampleAxis& ax) { return clampN(fdiv(ax.n0 - ax.T, ax.D) + 1, ax.N); };
+  auto last = [&](const ResampleAxis& ax, int o_n) { return clampN(fdiv(ax.n0 + (o_n - 1) * ax.dn + ax.T - 1, ax.D), ax.N); };
+  const int ry0 = first(a.y), ry1 = last(a.y, oh), rx0 = first(a.x), rx1 = last(a.x, ow);
+  VAM_REQUIRE(sy0 <= ry0 && ry1 < sy0 + hs && sx0 <= rx0 && rx1 < sx0 + ws,
+              "vam_picture_resample: the window of src (y0 %d, x0 %d, h %d, w %d) does not cover the support window (y0 %d, x0 %d, h %d, w %d) "
+              "of the rect (y0 %lld, x0 %lld, h %lld, w %lld) / %d into %d x %d at shift %d",
+              sy0, sx0, hs, ws, ry0, rx0, ry1 - ry0 + 1, rx1 - rx0 + 1, (long long)y0, (long long)x0, (long long)h, (long long)w, unit, oh, ow,
+              shift);
+  a.src = src; a.C = C; a.hs = hs; a.ws = ws; a.oh = oh; a.ow = ow;
+  a.out_f = out_u8 ? nullptr : (float*)out;
+  a.out_u8 = out_u8 ? (uint8_t*)out : nullptr;
+  const bool loop = a.y.T > 2 * a.y.D || a.x.T > 2 * a.x.D;  // a scale above 2 has more than four taps
+  const dim3 grid(cdiv(cdiv(ow, 4), 64), cdiv(oh, 4));
+  ProfScope ps(VAM_FAM_MISC, (hipStream_t)stream, 0,
+               (double)C * ((double)oh * ow * (out_u8 ? 1.0 : 4.0) + 4.0 * (ry1 - ry0 + 1) * (double)(rx1 - rx0 + 1)));
+  const bool staged = !loop && 10 * a.x.T >= 19 * a.x.D;     // a column scale of 1.9 .. 2: measured, DESIGN section 9zc
+  if (staged) hipLaunchKernelGGL(picture_resample_staged_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
+  else if (loop) hipLaunchKernelGGL(picture_resample_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(picture_resample_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, a);
+  return check_launch("picture_resample_kernel");
 }
 
 }  // extern "C"

@@ -931,6 +931,41 @@ def picture_halve(src: torch.Tensor, mode: str = "mean", out: Optional[torch.Ten
     return out
 
 
+def picture_resample(src: torch.Tensor, src_window: Sequence[int], level_hw: Sequence[int], shift: int, rect: Sequence[int], unit: int,
+                     out_hw: Sequence[int], out: Optional[torch.Tensor] = None, dtype=None) -> torch.Tensor:
+    """A viewport of a picture at any zoom and pan: the rect (y0, x0, h, w) / ``unit`` of the picture, in
+    level-0 pixels divided by the integer ``unit`` (1 .. 256), resampled from pyramid level ``shift`` (0 .. 15) into ``out_hw``
+    = (oh, ow) pixels with a tent of half-width max(1, scale) level pixels, scale = h / (oh unit 2^shift) at most 16.  ``src``
+    fp32 [C, hs, ws], contiguous, 1 <= C <= 32, is the window ``src_window`` = (sy0, sx0, hs, ws) of the level's picture of
+    ``level_hw`` = (Hk, Wk) and must cover ``pyramid.viewport_window(rect, out_hw, shift, ...)``.  Taps and weights are exact
+    integer arithmetic in the kernel (``pyramid.viewport_taps`` restates them); the value is the sum over the row taps of
+    wy * (the sum over the column taps of wx * s), ascending, every operation one fp32 operation.  ``out``: fp32 [C, oh, ow] or,
+    for C = 3, uint8 [oh, ow, 3] as rint(clamp(v, 0, 1) * 255); allocated in ``dtype`` (torch.float32 when None) when None.
+    One launch (vam_picture_resample), no table is uploaded; capturable when ``out`` is given."""
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3 and src.is_cuda
+    sy0, sx0, hs, ws = (int(v) for v in src_window)
+    assert tuple(src.shape[1:]) == (hs, ws), (tuple(src.shape), (hs, ws))
+    Hk, Wk = (int(v) for v in level_hw)
+    y0, x0, h, w = (int(v) for v in rect)
+    oh, ow = (int(v) for v in out_hw)
+    C_ = int(src.shape[0])
+    if out is None:
+        if dtype not in (None, torch.float32, torch.uint8):
+            raise ValueError(f"picture_resample: dtype is torch.float32 or torch.uint8, got {dtype}")
+        if not (1 <= oh <= 65536 and 1 <= ow <= 65536):
+            raise ValueError(f"picture_resample: an output of {oh} x {ow}: sides are 1 .. 65536")
+        out = torch.empty((oh, ow, C_), dtype=torch.uint8, device=src.device) if dtype == torch.uint8 \
+            else torch.empty((C_, oh, ow), dtype=torch.float32, device=src.device)
+    assert out.is_contiguous() and out.device == src.device
+    assert (out.dtype == torch.float32 and tuple(out.shape) == (C_, oh, ow)) or (out.dtype == torch.uint8 and tuple(out.shape) == (oh, ow, C_)), \
+        (out.dtype, tuple(out.shape), (C_, oh, ow))
+    within = lambda v: v if -2 ** 63 <= v < 2 ** 63 else -1                    # what no int64 holds is outside every picture
+    L.check(L.load().vam_picture_resample(src.data_ptr(), C_, sy0, sx0, hs, ws, Hk, Wk, int(shift), within(y0), within(x0), within(h),
+                                          within(w), int(unit), oh, ow, out.data_ptr(), int(out.dtype == torch.uint8), stream_ptr()),
+            "vam_picture_resample")
+    return out
+
+
 @dataclass
 class IView:
     """int32 NHWC channel window (symbols / table indexes)."""

@@ -32,9 +32,26 @@ smallest usable level above k; a level that is not usable contributes no tiles; 
 it, and there a tile that is not available is a ValueError.  A pixel is sharp exactly when every tile the blend sums there is
 available, and the switch is hard.
 
-Out of scope: scales that are no power of two and resampling; feathering the seam between sharp and filled pixels; ``q=`` with
-``fill``; a filled ``Canvas``; interleaving rounds across levels; coding a level as a residual of the coarser one;
-entropy-coded headers.
+Viewports: ``PyramidDecoder.viewport`` and ``PyramidStream.viewport`` show a rectangle of the picture in
+an output of any size, at any zoom and pan; :func:`extract_viewport` is the server's side.  One rule for ``csrc/tiles.hip``
+(vam_picture_resample), this module and ``tests/resample_ref.py``, all indices and weights exact integer arithmetic: a viewport
+is ``rect = (y0, x0, h, w)`` in level-0 pixels divided by an integer ``unit`` (1 .. 256; above 1 for sub-pixel pans) and
+``out_hw = (oh, ow)``, 1 .. 65536 each, with ``rect / unit`` inside the picture.  Resampled from level k, output row Y has its
+centre at ``n / D`` of level k, pixel i being centred at i + 1/2 on both sides (columns likewise):
+
+    D = 2^(k+1) oh unit      n = 2 oh y0 + (2 Y + 1) h - 2^k oh unit      T = max(D, 2 h)
+
+``T`` is the tent's half-width, max(1, scale) level-k pixels, the scale being ``h / (oh unit 2^k)``.  The taps are the integers i
+with ``|D i - n| < T``, of integer weight ``u_i = T - |D i - n|`` and fp32 weight ``float(u_i) / float(S)``, ``S`` their sum, read
+at ``clamp(i, 0, H_k - 1)``; the value is ``sum_r wy_r * (sum_c wx_c * s[r][c])``, taps ascending, every sum from its first term,
+every multiply and add one fp32 operation.  The level ``k*`` (:func:`viewport_level`) is the largest k below n_levels with
+``2^k oh unit <= h`` and ``2^k ow unit <= w``, 0 when there is none (magnification): the scales are then at least 1 on both axes
+and below 2 on at least one.  A scale above 16 on either axis is refused.  The support window (:func:`viewport_window`) is what
+the taps read of level k.
+
+Out of scope: filters other than the tent and rotation; a persistent resampled ``Canvas``; fusing the resample into the
+blend; feathering the seam between sharp and filled pixels; ``q=`` with ``fill``; a filled ``Canvas``; interleaving rounds
+across levels; coding a level as a residual of the coarser one; entropy-coded headers.
 """
 from __future__ import annotations
 
@@ -131,6 +148,116 @@ def source_window(window, d: int, Hj: int, Wj: int) -> Tuple[int, int, int, int]
     cl = lambda v, n: min(max(v, 0), n - 1)
     ya, yb, xa, xb = cl(a(y0), Hj), cl(a(y0 + h - 1) + 1, Hj), cl(a(x0), Wj), cl(a(x0 + w - 1) + 1, Wj)
     return ya, xa, yb - ya + 1, xb - xa + 1
+
+
+MAX_UNIT, MAX_OUT, MAX_SCALE = 256, 65536, 16
+
+
+def _viewport(what: str, rect, out_hw, H: int, W: int, unit) -> Tuple[int, int, int, int, int, int, int]:
+    """The checked integers (y0, x0, h, w, oh, ow, unit) of a viewport of an H x W picture (``rect`` None: the picture)."""
+    H, W, unit = as_int(H, f"{what}: H"), as_int(W, f"{what}: W"), as_int(unit, f"{what}: unit")
+    if not (1 <= H <= TL.MAX_SIDE and 1 <= W <= TL.MAX_SIDE):
+        raise ValueError(f"{what}: a picture of {H} x {W}: sides are 1 .. {TL.MAX_SIDE}")
+    if not 1 <= unit <= MAX_UNIT:
+        raise ValueError(f"{what}: unit is 1 .. {MAX_UNIT} (rect is in level-0 pixels divided by it), got {unit}")
+    try:
+        entries = list(out_hw)
+    except TypeError:
+        entries = []
+    if len(entries) != 2:
+        raise ValueError(f"{what}: out_hw is (rows, columns), got {out_hw!r}")
+    oh, ow = (as_int(v, f"{what}: out_hw") for v in entries)
+    if not (1 <= oh <= MAX_OUT and 1 <= ow <= MAX_OUT):
+        raise ValueError(f"{what}: out_hw is (rows, columns) of 1 .. {MAX_OUT} each, got {(oh, ow)}")
+    if rect is None:
+        return 0, 0, H * unit, W * unit, oh, ow, unit
+    try:
+        entries = list(rect)
+    except TypeError:
+        entries = []
+    if len(entries) != 4:
+        raise ValueError(f"{what}: a rect is (y0, x0, h, w), got {rect!r}")
+    y0, x0, h, w = (as_int(v, f"{what}: a rect entry") for v in entries)
+    if not (y0 >= 0 and x0 >= 0 and h >= 1 and w >= 1 and y0 + h <= H * unit and x0 + w <= W * unit):
+        raise ValueError(f"{what}: the rect (y0 {y0}, x0 {x0}, h {h}, w {w}) / {unit} does not lie inside the {H} x {W} picture")
+    return y0, x0, h, w, oh, ow, unit
+
+
+def _viewport_k(what: str, k, v) -> int:
+    """Level k for the viewport ``v`` (:func:`_viewport`'s), refused where it is no level or the scale there is above 16."""
+    k = as_int(k, f"{what}: level")
+    if not 0 <= k < MAX_LEVELS:
+        raise ValueError(f"{what}: level is 0 .. {MAX_LEVELS - 1}, got {k}")
+    _, _, h, w, oh, ow, unit = v
+    if h > MAX_SCALE * (oh * unit << k) or w > MAX_SCALE * (ow * unit << k):
+        need = k
+        while h > MAX_SCALE * (oh * unit << need) or w > MAX_SCALE * (ow * unit << need):
+            need += 1
+        raise ValueError(f"{what}: the rect (h {h}, w {w}) / {unit} into {oh} x {ow} at level {k} has a scale of "
+                         f"{h / (oh * unit << k):.4g} x {w / (ow * unit << k):.4g}: above {MAX_SCALE}; level {need}, of a pyramid of "
+                         f"{need + 1} levels, brings it to {MAX_SCALE} or below")
+    return k
+
+
+def _axis(origin: int, extent: int, out: int, k: int, unit: int) -> Tuple[int, int, int, int]:
+    """(D, n of output coordinate 0, the step of n, T) along one axis (module docstring)."""
+    half = out * unit << k
+    return 2 * half, 2 * out * origin + extent - half, 2 * extent, max(2 * half, 2 * extent)
+
+
+def _level_star(v, n_levels: int) -> int:
+    _, _, h, w, oh, ow, unit = v
+    best = 0
+    for k in range(n_levels):
+        if (oh * unit << k) <= h and (ow * unit << k) <= w:
+            best = k
+    return best
+
+
+def viewport_level(rect, out_hw, H: int, W: int, n_levels: int, unit: int = 1) -> int:
+    """``k*``: the level of an ``n_levels`` pyramid of an H x W picture to resample the viewport ``rect`` / ``unit`` into
+    ``out_hw`` from (module docstring): the largest k with ``2^k oh unit <= h`` and ``2^k ow unit <= w``, 0 when there is none.
+    ValueError when the scale at ``k*`` is above 16: the viewport is strongly anisotropic or the pyramid has too few levels."""
+    what = "viewport_level"
+    v = _viewport(what, rect, out_hw, H, W, unit)
+    n = as_int(n_levels, f"{what}: n_levels")
+    _check_levels(H, W, n, what)
+    return _viewport_k(what, _level_star(v, n), v)
+
+
+def viewport_window(rect, out_hw, k: int, H: int, W: int, unit: int = 1) -> Tuple[int, int, int, int]:
+    """The support window (y0, x0, h, w) of level k: what resampling the viewport from level k reads, rows ``clamp(first tap
+    of Y = 0)`` .. ``clamp(last tap of Y = oh - 1)`` with the clamp to 0 .. H_k - 1, columns likewise.  Host arithmetic only."""
+    what = "viewport_window"
+    v = _viewport(what, rect, out_hw, H, W, unit)
+    k = _viewport_k(what, k, v)
+    y0, x0, h, w, oh, ow, unit = v
+    out = []
+    for origin, extent, o_n, N in ((y0, h, oh, -(-H // (1 << k))), (x0, w, ow, -(-W // (1 << k)))):
+        D, n0, dn, T = _axis(origin, extent, o_n, k, unit)
+        cl = lambda i: min(max(i, 0), N - 1)
+        out.append((cl((n0 - T) // D + 1), cl((n0 + (o_n - 1) * dn + T - 1) // D)))
+    (ya, yb), (xa, xb) = out
+    return ya, xa, yb - ya + 1, xb - xa + 1
+
+
+def viewport_taps(rect, out_hw, k: int, H: int, W: int, unit: int = 1, axis: int = 0) -> List[Tuple[int, Tuple[int, ...]]]:
+    """The taps of one axis (0: rows, 1: columns) of the viewport resampled from level k: per output coordinate
+    ``(first, weights)``, the taps being ``first``, ``first + 1``, .. with the integer weights ``u_i`` (module docstring); the
+    fp32 weight is ``float(u_i) / float(sum(weights))`` and the source index ``clamp(i, 0, N_k - 1)``.  For tests and
+    references to compare against; the kernel derives the same numbers itself."""
+    what = "viewport_taps"
+    v = _viewport(what, rect, out_hw, H, W, unit)
+    k = _viewport_k(what, k, v)
+    if axis not in (0, 1):
+        raise ValueError(f"{what}: axis is 0 (rows) or 1 (columns), got {axis!r}")
+    D, n0, dn, T = _axis(v[axis], v[2 + axis], v[4 + axis], k, v[6])
+    taps = []
+    for P in range(v[4 + axis]):
+        n = n0 + P * dn
+        first, last = (n - T) // D + 1, (n + T - 1) // D
+        taps.append((first, tuple(T - abs(D * i - n) for i in range(first, last + 1))))
+    return taps
 
 
 # ----------------------------------------------------------------------------------------------------------- codestream
@@ -341,6 +468,30 @@ def extract(data, levels: Optional[Sequence[int]] = None, window=None, rounds: O
     return _assemble(p.H, p.W, streams)
 
 
+def extract_viewport(data, rect, out_hw, unit: int = 1, rounds: Optional[int] = None, thumbnail: bool = True) -> bytes:
+    """What a server sends for one viewport, without the model: of the pyramid codestream ``data``, level
+    ``k*`` = :func:`viewport_level` cut to the level-0 window that covers its support window (:func:`viewport_window` times
+    ``2^k*``, clipped to the picture) and, with ``thumbnail``, the coarsest present level whole, both with the first ``rounds``
+    rounds (None: all), by :func:`extract`.  ``PyramidDecoder(model, it).viewport(rect, out_hw, unit, fill=thumbnail)`` equals
+    the viewport of ``data`` bit for bit at the same mark.  ValueError when ``data`` lacks level ``k*``."""
+    d, p = _parse(data, "extract_viewport")
+    try:
+        k = viewport_level(rect, out_hw, p.H, p.W, p.n, unit)
+        ya, xa, h, w = viewport_window(rect, out_hw, k, p.H, p.W, unit)
+    except ValueError as e:
+        raise ValueError(f"extract_viewport: {e}") from e
+    y0, x0 = ya << k, xa << k
+    window = (y0, x0, min(p.H, (ya + h) << k) - y0, min(p.W, (xa + w) << k) - x0)
+    if not isinstance(thumbnail, bool):
+        raise ValueError(f"extract_viewport: thumbnail is True or False, got {thumbnail!r}")
+    if not thumbnail or p.order[0] == k:                                        # k* is the coarsest level: the whole of it covers both
+        return extract(d, [k], None if thumbnail else window, rounds)
+    cut, whole = extract(d, [k], window, rounds), extract(d, [p.order[0]], None, rounds)
+    streams: List[Optional[bytes]] = [None] * p.n
+    streams[k], streams[p.order[0]] = level_stream(cut, k), level_stream(whole, p.order[0])
+    return _assemble(p.H, p.W, streams)
+
+
 # ---------------------------------------------------------------------------------------------------- encoder and decoder
 def encode(model, image, levels: Optional[int] = None, tile: int = 256, overlap: int = 32, **tiled_kwargs) -> bytes:
     """The pyramid codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device.  ``levels`` = None: levels until a
@@ -430,6 +581,28 @@ def _fill(what: str, shapes, usable: List[int], composer, window, k: int, q, mar
     return level(k, window, dtype), chain
 
 
+def _viewport_plan(what: str, rect, out_hw, unit, level, dtype, H: int, W: int, n_levels: int):
+    """(rect, out_hw, unit, k, the support window at k) of a viewport call, checked before anything is decoded."""
+    import torch
+    v = _viewport(what, rect, out_hw, H, W, unit)
+    if dtype not in (None, torch.float32, torch.uint8):
+        raise ValueError(f"{what}: dtype is torch.float32 or torch.uint8, got {dtype}")
+    if level is None:
+        k = _viewport_k(what, _level_star(v, n_levels), v)
+    else:
+        k = as_int(level, f"{what}: level")
+        if not 0 <= k < n_levels:
+            raise ValueError(f"{what}: level is 0 .. {n_levels - 1}, got {k}")
+        k = _viewport_k(what, k, v)
+    return v[:4], v[4:6], v[6], k, viewport_window(v[:4], v[4:6], k, H, W, v[6])
+
+
+def _resample(src, window, level_hw, k: int, rect, unit: int, out_hw, dtype):
+    """One vam_picture_resample launch on the fp32 support window ``src`` of level k."""
+    from . import ops
+    return ops.picture_resample(src.detach().contiguous(), window, level_hw, k, rect, unit, out_hw, dtype=dtype)
+
+
 class PyramidDecoder:
     """Decodes a pyramid codestream by level and window.  ``data``: any prefix of at least :func:`need_bytes`, or an
     :func:`extract`.  ``shape``: the true (H, W) of level 0; ``levels``: n_levels; ``shapes``: [(H_k, W_k)]; ``ready``: per level,
@@ -495,6 +668,18 @@ class PyramidDecoder:
                            dtype, 0)
         self.last_tiles, self.last_chain = chain[0][1], chain
         return out
+
+    def viewport(self, rect, out_hw, unit: int = 1, level: Optional[int] = None, q: Optional[float] = None, mark: Optional[int] = None,
+                 stage: Optional[int] = None, dtype=None, fill: bool = False):
+        """The viewport ``rect`` = (y0, x0, h, w) / ``unit`` of the picture (None: the picture) in ``out_hw`` = (oh, ow) pixels, at
+        any zoom and pan: fp32 [3, oh, ow] or, with ``dtype=torch.uint8``, uint8 [oh, ow, 3].  ``level`` None
+        takes :func:`viewport_level`; an explicit level is allowed while the scale there stays at most 16.  The level's support
+        window (:func:`viewport_window`) is ``decode(window, level, q, mark, stage, fill=fill)`` in fp32, with its errors, and
+        one vam_picture_resample launch writes the output: the result is ``tests/resample_ref.py`` on that decode, bit for bit."""
+        what = "PyramidDecoder.viewport"
+        rect, out_hw, unit, k, win = _viewport_plan(what, rect, out_hw, unit, level, dtype, self.shape[0], self.shape[1], self.levels)
+        src = self.decode(win, k, q=q, mark=mark, stage=stage, dtype=None, fill=fill)
+        return _resample(src, win, self.shapes[k], k, rect, unit, out_hw, dtype)
 
 
 # --------------------------------------------------------------------------------------------------------- the receiver
@@ -670,6 +855,20 @@ class PyramidStream:
         out, chain = _fill(what, fs._p.shapes, usable, lambda j: fs.receivers[j], window, k, q, mark, stage, dtype, fs.need())
         self.last_tiles, self.last_decoded, self.last_chain = chain[0][1], chain[0][2], chain
         return out
+
+    def viewport(self, rect, out_hw, unit: int = 1, level: Optional[int] = None, q: Optional[float] = None, mark: Optional[int] = None,
+                 stage: Optional[int] = None, dtype=None, fill: bool = False):
+        """A fresh ``PyramidDecoder(everything fed so far).viewport(rect, out_hw, unit, level, ...)``, bit for bit: the level's
+        support window is :meth:`view`'s, through that level's ``tiled.PictureStream`` and its tile cache (``last_tiles``,
+        ``last_decoded`` and ``last_chain`` are the view's), then one vam_picture_resample launch.  Over cached tiles a pan step
+        is one blend and one resample and runs no network."""
+        what = "PyramidStream.viewport"
+        fs = self.feed_state
+        if fs._p is None:
+            raise ValueError(f"{what}: nothing to decode yet: the header is not complete, {fs.need()} bytes are missing")
+        rect, out_hw, unit, k, win = _viewport_plan(what, rect, out_hw, unit, level, dtype, fs._p.H, fs._p.W, fs._p.n)
+        src = self.view(win, k, q=q, mark=mark, stage=stage, dtype=None, fill=fill)
+        return _resample(src, win, fs._p.shapes[k], k, rect, unit, out_hw, dtype)
 
     def canvas(self, window=None, level: int = 0, dtype=None) -> "TL.Canvas":
         """``streams[level].canvas(window, dtype)``: a persistent output of that level that ``refresh()`` keeps equal to

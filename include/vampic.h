@@ -478,6 +478,31 @@ int vam_tile_refresh(const float* tiles, int n, const int32_t* slot, const int32
  * or 1 and a problem of 2^32 threads or more are VAM_EINVAL and launch nothing. */
 int vam_picture_halve(const float* src, int C, int Hs, int Ws, float* dst, int mode, void* stream);
 
+/* Pyramid viewports (vampic.pyramid): the rect (y0, x0, h, w) / unit of the picture, in level-0 pixels
+ * divided by the integer unit (1 .. 256), resampled from level k = shift (0 .. 15) into oh x ow pixels (1 .. 65536 each), at any
+ * zoom and pan, with a tent filter of half-width max(1, scale) level-k pixels.  src is fp32 [C, hs, ws], the window sy0, sx0, hs,
+ * ws of the level's picture of Hk x Wk; out is fp32 [C, oh, ow] (out_u8 = 0) or, for C = 3, uint8 [oh, ow, 3] by vam_tile_blend's
+ * rule (out_u8 = 1).  Along the rows (the columns likewise, with x0, w, ow, Wk), output row Y has its centre at n / D of level k,
+ * pixel i being centred at i + 1/2 on both sides:
+ *   D = 2^(k+1) oh unit,  n = 2 oh y0 + (2 Y + 1) h - 2^k oh unit,  T = max(D, 2 h);
+ * its taps are the integers i with |D i - n| < T, of integer weight u_i = T - |D i - n| > 0 and fp32 weight
+ * float(u_i) / float(S), S = sum u_i (two round-to-nearest conversions, one correctly rounded division), read at
+ * clamp(i, 0, Hk - 1): the edge is replicated.  The scale is h / (oh unit 2^k); up to 2 there are at most 4 taps, within
+ * floor(n / D) - 1 .. floor(n / D) + 2; up to 16, the limit, at most 32.  The value is
+ *   sum over the row taps r of wy_r * (sum over the column taps c of wx_c * src[r][c]),
+ * taps ascending, each sum starting from its first term, every multiply and add one fp32 operation that nothing contracts.
+ * Only finite inputs are specified.  The kernel derives taps and weights from these integers in the thread: nothing is uploaded
+ * per call.  The value does not depend on the path a lane takes (16-byte stores where aligned, scalar otherwise; at most 4 taps
+ * per axis unrolled, with cached reads or, at column scales of 1.9 .. 2, the source staged in LDS; more in a bounded loop).  The picture is known here through its level: the rect / unit must lie inside
+ * min(Hk 2^k, 2^24) x min(Wk 2^k, 2^24).  src must cover the support window, rows clamp(first tap of Y = 0) ..
+ * clamp(last tap of Y = oh - 1) and columns likewise, so that every index formed lies inside it.  VAM_EINVAL, nothing launched:
+ * a null src or out, C outside 1 .. VAM_MAX_LAYER_LEVELS, out_u8 other than 0 or 1 or 1 with C != 3, unit, oh, ow or shift out
+ * of range, an Hk x Wk that is the level of no picture with sides 1 .. 2^24, a rect outside the picture, a window of src
+ * outside the level or not covering the support window, and a scale above 16 on either axis (the message names the level
+ * that would do).  No atomics, no allocation, capturable. */
+int vam_picture_resample(const float* src, int C, int sy0, int sx0, int hs, int ws, int Hk, int Wk, int shift, int64_t y0, int64_t x0,
+                         int64_t h, int64_t w, int unit, int oh, int ow, void* out, int out_u8, void* stream);
+
 /* ------------------------------------------------------------------ Gaussian conditional */
 /* Fused slice tail (models/pic.py:545-546,625-629; entropy_models.py:620-652).
  *  base  (mask == NULL):  v = round(y-mu);           lik = L(|(v+mu)-mu|, sigma);        yhat = v+mu

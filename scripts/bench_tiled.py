@@ -49,11 +49,17 @@ are captured into one graph and its replays are timed by HIP events (five times:
 launches would time the host's enqueue; and the first picture at level-0 resolution: a new ``PyramidStream`` fed ``need_bytes`` and viewed with
 ``fill=True``, beside a new one fed up to the last of level 0's heads and viewed without: bytes and wall time of each.
 
+``--pyramid --zoom`` adds ``"zoom"`` to it: vam_picture_resample alone into a 512 x 768 viewport from level
+0's support window at the scales 1, 1.5, 2 and 1/3, fp32 and uint8, beside a device ``copy_`` of as many bytes as it writes and
+vam_tile_compose of the same output size, timed as ``--fill`` times its kernels; then ``PyramidDecoder.viewport`` of the whole
+picture beside ``decode`` of the level it picks, a level-0 rect at scale 1.5 beside ``decode`` of its support window, and pan
+steps of that rect on a warm ``PyramidStream``: wall time and the tiles that ran the network.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
-                                  [--schedule roi] [--stream] [--pan] [--pyramid [--fill]]
+                                  [--schedule roi] [--stream] [--pan] [--pyramid [--fill] [--zoom]]
 """
 import argparse
 import json
@@ -371,6 +377,8 @@ def pyramid(a, net, x, g, kw, TL, PY, ops):
                            "copy_in_bytes_us": spread([event_us(lambda: like.copy_(x)) for _ in range(5)])}
     if a.fill:
         out["fill"] = fill(a, net, data, lay, g, TL, PY, ops)
+    if a.zoom:
+        out["zoom"] = zoom(a, net, data, lay, g, TL, PY, ops)
     return out
 
 
@@ -423,6 +431,72 @@ def fill(a, net, data, lay, g, TL, PY, ops):
                                                         "plain_bytes": heads0, "plain_ms": spread(plain)}}
 
 
+def zoom(a, net, data, lay, g, TL, PY, ops):
+    """The ``--zoom`` section: see the module docstring."""
+    H, W, R, C, dev = g["H"], g["W"], g["R"], g["C"], next(net.parameters()).device
+    oh, ow = min(512, H), min(768, W)
+    picture = torch.rand((3, H, W), dtype=torch.float32, device=dev)
+    kernel = {"out_hw": [oh, ow], "timing": "200 launches in one graph, 5 replays, 5 times"}
+    views = {}
+    for name, num, den in (("1", 1, 1), ("1.5", 3, 2), ("2", 2, 1), ("1/3", 1, 3)):
+        unit = den                                                              # the rect in 1 / den pixels: h = oh num exactly
+        h, w = oh * num, ow * num
+        rect = ((H * unit - h) // 2 | 1, (W * unit - w) // 2 | 1, h, w)
+        win = PY.viewport_window(rect, (oh, ow), 0, H, W, unit)
+        views[name] = (rect, unit, win, picture[:, win[0]:win[0] + win[2], win[1]:win[1] + win[3]].contiguous())
+        kernel[f"scale_{name}"] = {"rect": list(rect), "unit": unit, "support_window": list(win),
+                                   "taps": [max(len(u) for _, u in PY.viewport_taps(rect, (oh, ow), 0, H, W, unit, ax)) for ax in (0, 1)]}
+    tiles = torch.rand((R * C, 3, g["th"], g["tw"]), dtype=torch.float32, device=dev)
+    every = torch.arange(R * C, dtype=torch.int32, device=dev).view(R, C)
+    w_lo, w_hi = (torch.from_numpy(t).to(dev) if g["V"] else None for t in TL.ramps(g["V"]))
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    cwin = ((H - oh) // 2, (W - ow) // 2, oh, ow)
+    bwin = PY.source_window(cwin, 1, -(-H // 2), -(-W // 2))
+    below = torch.rand((3,) + bwin[2:], dtype=torch.float32, device=dev)
+    for kind, dst in (("f32", torch.empty((3, oh, ow), dtype=torch.float32, device=dev)), ("u8", torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev))):
+        like = torch.empty_like(dst)
+        kernel[f"out_{kind}_bytes"] = dst.numel() * dst.element_size()
+        kernel[f"copy_{kind}_us"] = spread([graph_us(lambda: dst.copy_(like)) for _ in range(5)])
+        kernel[f"compose_{kind}_us"] = spread([graph_us(lambda: ops.tile_compose(tiles, every, w_lo, w_hi, H, W, g["V"], cwin, below, bwin, 1, dst, status))
+                                               for _ in range(5)])
+        for name, (rect, unit, win, src) in views.items():
+            kernel[f"scale_{name}"][f"resample_{kind}_us"] = spread([graph_us(lambda: ops.picture_resample(src, win, (H, W), 0, rect, unit, (oh, ow), out=dst))
+                                                                      for _ in range(5)])
+    assert int(status.item()) == 0
+    dec = PY.PyramidDecoder(net, data, coder=a.coder)
+
+    def beside(rect, level):
+        """Wall times of ``dec.viewport`` and of ``dec.decode`` of its support window alone, in turn."""
+        k = PY.viewport_level(rect, (oh, ow), H, W, lay["n_levels"]) if level is None else level
+        win = PY.viewport_window(rect, (oh, ow), k, H, W)
+        tv, td = [], []
+        for i in range(a.warmup + a.reps):
+            t, got = timed(lambda: dec.viewport(rect, (oh, ow), level=level))
+            u, _ = timed(lambda: dec.decode(win, level=k))
+            assert tuple(got.shape) == (3, oh, ow)
+            if i >= a.warmup:
+                tv.append(t)
+                td.append(u)
+        return {"rect": None if rect is None else list(rect), "level": k, "support_window": list(win), "tiles": len(dec.last_tiles),
+                "viewport_ms": spread(tv), "decode_ms": spread(td)}
+
+    rect = ((H - oh * 3 // 2) // 2 | 1, (W - ow * 3 // 2) // 2 | 1, oh * 3 // 2, ow * 3 // 2)
+    end = {"whole_picture": beside(None, None), "level0_scale_1.5": beside(rect, None)}
+    st = PY.PyramidStream(net, coder=a.coder, cache_tiles=R * C)
+    st.feed(data)
+    st.viewport(rect, (oh, ow))                                                 # warm: the rect's tiles are cached
+    steps, ran = [], 0
+    for i in range(a.warmup + 8):
+        pan = (rect[0] + 4 * (i + 1), rect[1] - 6 * (i + 1)) + rect[2:]
+        t, got = timed(lambda: st.viewport(pan, (oh, ow)))
+        ran += len(st.last_decoded)
+        if i >= a.warmup:
+            steps.append(t)
+    assert torch.equal(got, dec.viewport(pan, (oh, ow)))
+    end["pan_step_warm_stream"] = {"steps": len(steps), "tiles_composed": len(st.last_tiles), "tiles_that_ran_the_network": ran, "ms": spread(steps)}
+    return {"kernel": kernel, "end_to_end": end}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -440,9 +514,10 @@ def main():
     ap.add_argument("--pan", action="store_true")
     ap.add_argument("--pyramid", action="store_true")
     ap.add_argument("--fill", action="store_true")
+    ap.add_argument("--zoom", action="store_true")
     a = ap.parse_args()
-    if a.fill and not a.pyramid:
-        ap.error("--fill is a part of --pyramid")
+    if (a.fill or a.zoom) and not a.pyramid:
+        ap.error("--fill and --zoom are parts of --pyramid")
     from bench import build_model
     import vampic
     from vampic import embedded as EB, evaluate as EV, ops, pyramid as PY, tiled as TL
