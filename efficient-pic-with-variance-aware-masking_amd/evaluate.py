@@ -601,6 +601,60 @@ def pyramid_fill_rd(model, image: torch.Tensor, cuts: Sequence[int], levels: Opt
     return rows
 
 
+def session_rd(model, image: torch.Tensor, tour: Sequence[dict], levels: Optional[int] = None, tile: int = 256, overlap: int = 32,
+               marks: Optional[Sequence[float]] = None, coder=None, lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None,
+               allocation: str = "tile", schedule=None, cache_tiles: Optional[int] = None):
+    """Bytes sent against the quality of the viewport along a viewing session (``session.Server`` / ``session.Client``, DESIGN
+    section 9zd): the picture is coded ONCE as a pyramid, and one server and one client follow ``tour``, a list of
+    ``dict(rect, out_hw, unit=1, rounds=None)``.  The session opens with ``Server.open()``, the picture's headers alone, merged
+    before the tour and counted in bytes_total, in no step.  Per step the server's increment for the viewport is merged and
+    the viewport is viewed filled, at the last mark (stage, for a schedule) that ``rounds`` holds whole, from everything held
+    when ``rounds`` is 0.  One dict per step: bytes (this message), bytes_total (all messages so far, the opening one
+    included), bytes_stateless (the length of ``pyramid.extract_viewport`` for the same request), tiles and decoded (of the
+    viewport's level: composed, and run through the network), dec_s (the merge plus the viewport) and psnr against the same
+    viewport of the original: ``ops.picture_halve`` k* times, then ``ops.picture_resample``.  ``cache_tiles`` defaults to every
+    tile of level 0."""
+    from . import ops
+    from . import pyramid as PY
+    from . import session as SS
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    H, W = int(x.shape[2]), int(x.shape[3])
+    rows = []
+    with torch.no_grad():
+        kw = dict(schedule=schedule) if schedule is not None else dict(marks=marks, allocation=allocation)
+        data = PY.encode(model, x, levels=levels, tile=tile, overlap=overlap, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group, **kw)
+        lay = PY.layout(data)
+        n_marks = len(lay["levels"][0]["layout"]["marks"])
+        g = TL.grid(H, W, tile, overlap)
+        server = SS.Server(data)
+        client = SS.Client(model, coder=coder, group=group, cache_tiles=g["R"] * g["C"] if cache_tiles is None else cache_tiles)
+        opening = server.open()
+        client.merge(opening)
+        originals, total = [x[0].contiguous()], len(opening)
+        for step in tour:
+            rect, out_hw, unit, rounds = step["rect"], step["out_hw"], step.get("unit", 1), step.get("rounds")
+            stateless = len(PY.extract_viewport(data, rect, out_hw, unit, rounds))
+            m = n_marks - 1 if rounds is None else min(int(rounds), n_marks) - 1
+            how = {} if m < 0 else {"stage": m} if schedule is not None else {"mark": m}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            message = server.viewport(rect, out_hw, unit, rounds)
+            client.merge(message)
+            x_hat = client.viewport(rect, out_hw, unit, fill=True, **how)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            full, out_hw, unit, k, win = PY._viewport_plan("session_rd", rect, out_hw, unit, None, None, H, W, lay["n_levels"])
+            while len(originals) <= k:
+                originals.append(ops.picture_halve(originals[-1]))
+            y0, x0, h, w = win
+            want = ops.picture_resample(originals[k][:, y0:y0 + h, x0:x0 + w].contiguous(), win, lay["levels"][k]["shape"], k, full, unit, out_hw)
+            total += len(message)
+            rows.append({"bytes": len(message), "bytes_total": total, "bytes_stateless": stateless, "tiles": len(client.last_tiles),
+                         "decoded": len(client.last_decoded), "dec_s": t1 - t0, "psnr": compute_psnr(want.unsqueeze(0), x_hat.unsqueeze(0))})
+    return rows
+
+
 def embedded_stream_rd(model, images: Sequence[torch.Tensor], byte_budgets: Sequence[int], coder=None, lanes: int = 1,
                        base_lanes: int = 1):
     """Rate and distortion of a codestream (embedded.to_bytes) cut at real byte budgets: images of ONE

@@ -1,5 +1,6 @@
-"""The framing that the three codestream formats share: embedded (``VAMe``, ``embedded.py``), tiled
-picture (``VAMp``, ``tiled.py``) and pyramid (``VAMy``, ``pyramid.py``) codestreams all open with one 16-byte preamble, magic,
+"""The framing that the four formats share: embedded (``VAMe``, ``embedded.py``), tiled picture
+(``VAMp``, ``tiled.py``) and pyramid (``VAMy``, ``pyramid.py``) codestreams and a viewing session's increment messages (``VAMi``,
+``session.py``) all open with one 16-byte preamble, magic,
 version, reserved (0), bytes of the header, CRC-32 of the header, then the header and the body.  A :class:`Frame` holds what
 differs between formats as data and refuses a preamble that cannot be trusted with one set of messages; the formats keep
 their own header fields and body arithmetic.  Host only."""

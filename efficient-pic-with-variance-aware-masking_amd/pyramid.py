@@ -49,6 +49,11 @@ every multiply and add one fp32 operation.  The level ``k*`` (:func:`viewport_le
 and below 2 on at least one.  A scale above 16 on either axis is refused.  The support window (:func:`viewport_window`) is what
 the taps read of level k.
 
+Viewing sessions: :func:`extract_viewport` cuts a self-contained stream per viewport and repeats what the
+receiver holds; ``vampic.session`` keeps, on both sides, a ledger of the segments held per tile, and its ``Server.viewport`` /
+``Server.window`` send for the same request (:func:`_viewport_cuts`, :func:`_kept`: one arithmetic) only what the ledger lacks,
+to a ``Client`` that takes bytes by tile and keeps its cache of decoded tiles from viewport to viewport.
+
 Out of scope: filters other than the tent and rotation; a persistent resampled ``Canvas``; fusing the resample into the
 blend; feathering the seam between sharp and filled pixels; ``q=`` with ``fill``; a filled ``Canvas``; interleaving rounds
 across levels; coding a level as a residual of the coarser one; entropy-coded headers.
@@ -445,27 +450,51 @@ def extract(data, levels: Optional[Sequence[int]] = None, window=None, rounds: O
     an extract of an extract is an extract.  ValueError names a wanted level that ``data`` lacks."""
     d, p = _parse(data, "extract")
     _layouts(d, p, "extract")
+    streams: List[Optional[bytes]] = [None] * p.n
+    for k, win in _kept(p, levels, window, "extract"):
+        part = d[p.off[k]:p.off[k] + p.held(len(d), k)]
+        try:
+            streams[k] = TL.extract(part, win, rounds)
+        except ValueError as e:
+            raise ValueError(f"extract: level {k}: {e}") from e
+    return _assemble(p.H, p.W, streams)
+
+
+def _kept(p: _Pyramid, levels, window, what: str) -> List[Tuple[int, Optional[Tuple[int, int, int, int]]]]:
+    """[(level, its window or None: the level whole)], finest first, that :func:`extract` of ``levels`` and the level-0
+    ``window`` keeps of the pyramid ``p``."""
     if levels is None:
         keep = sorted(p.order)
     else:
         try:
-            keep = sorted({p.level(k, "extract") for k in levels})
+            keep = sorted({p.level(k, what) for k in levels})
         except TypeError as e:
-            raise ValueError(f"extract: levels is a sequence of levels, got {levels!r}") from e
+            raise ValueError(f"{what}: levels is a sequence of levels, got {levels!r}") from e
         if not keep:
-            raise ValueError("extract: levels is empty: a pyramid holds at least one level")
+            raise ValueError(f"{what}: levels is empty: a pyramid holds at least one level")
     if window is not None:
-        window = TL._window({"H": p.H, "W": p.W}, window, "extract")
-    streams: List[Optional[bytes]] = [None] * p.n
+        window = TL._window({"H": p.H, "W": p.W}, window, what)
     for k in keep:
         if not p.size[k]:
-            raise ValueError(f"extract: level {k} is absent from this codestream; it holds the levels {sorted(p.order)}")
-        part = d[p.off[k]:p.off[k] + p.held(len(d), k)]
-        try:
-            streams[k] = TL.extract(part, None if window is None else window_at(window, k, p.H, p.W), rounds)
-        except ValueError as e:
-            raise ValueError(f"extract: level {k}: {e}") from e
-    return _assemble(p.H, p.W, streams)
+            raise ValueError(f"{what}: level {k} is absent from this codestream; it holds the levels {sorted(p.order)}")
+    return [(k, None if window is None else window_at(window, k, p.H, p.W)) for k in keep]
+
+
+def _viewport_cuts(p: _Pyramid, rect, out_hw, unit, thumbnail, what: str) -> List[Tuple[List[int], Optional[Tuple[int, int, int, int]]]]:
+    """What :func:`extract_viewport` keeps of the pyramid ``p``: one or two (levels, level-0 window or None) for
+    :func:`extract`, level ``k*`` first."""
+    try:
+        k = viewport_level(rect, out_hw, p.H, p.W, p.n, unit)
+        ya, xa, h, w = viewport_window(rect, out_hw, k, p.H, p.W, unit)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from e
+    y0, x0 = ya << k, xa << k
+    window = (y0, x0, min(p.H, (ya + h) << k) - y0, min(p.W, (xa + w) << k) - x0)
+    if not isinstance(thumbnail, bool):
+        raise ValueError(f"{what}: thumbnail is True or False, got {thumbnail!r}")
+    if not thumbnail or p.order[0] == k:                                        # k* is the coarsest level: the whole of it covers both
+        return [([k], None if thumbnail else window)]
+    return [([k], window), ([p.order[0]], None)]
 
 
 def extract_viewport(data, rect, out_hw, unit: int = 1, rounds: Optional[int] = None, thumbnail: bool = True) -> bytes:
@@ -475,20 +504,12 @@ def extract_viewport(data, rect, out_hw, unit: int = 1, rounds: Optional[int] = 
     rounds (None: all), by :func:`extract`.  ``PyramidDecoder(model, it).viewport(rect, out_hw, unit, fill=thumbnail)`` equals
     the viewport of ``data`` bit for bit at the same mark.  ValueError when ``data`` lacks level ``k*``."""
     d, p = _parse(data, "extract_viewport")
-    try:
-        k = viewport_level(rect, out_hw, p.H, p.W, p.n, unit)
-        ya, xa, h, w = viewport_window(rect, out_hw, k, p.H, p.W, unit)
-    except ValueError as e:
-        raise ValueError(f"extract_viewport: {e}") from e
-    y0, x0 = ya << k, xa << k
-    window = (y0, x0, min(p.H, (ya + h) << k) - y0, min(p.W, (xa + w) << k) - x0)
-    if not isinstance(thumbnail, bool):
-        raise ValueError(f"extract_viewport: thumbnail is True or False, got {thumbnail!r}")
-    if not thumbnail or p.order[0] == k:                                        # k* is the coarsest level: the whole of it covers both
-        return extract(d, [k], None if thumbnail else window, rounds)
-    cut, whole = extract(d, [k], window, rounds), extract(d, [p.order[0]], None, rounds)
+    cuts = _viewport_cuts(p, rect, out_hw, unit, thumbnail, "extract_viewport")
+    if len(cuts) == 1:
+        return extract(d, cuts[0][0], cuts[0][1], rounds)
     streams: List[Optional[bytes]] = [None] * p.n
-    streams[k], streams[p.order[0]] = level_stream(cut, k), level_stream(whole, p.order[0])
+    for levels, window in cuts:
+        streams[levels[0]] = level_stream(extract(d, levels, window, rounds), levels[0])
     return _assemble(p.H, p.W, streams)
 
 

@@ -228,6 +228,10 @@ class _Picture:
         """int64 [1 + nr, R C]: the bytes of every segment that the first ``n`` bytes of the codestream hold."""
         return np.clip(n - self.off, 0, self.size)
 
+    def facts(self) -> dict:
+        """The geometry with ``total``, ``allocation`` and ``stages`` as :func:`layout` names them."""
+        return dict(self.g, total=self.total, allocation=ALLOCATIONS[self.version == VERSION_POOLED], stages=self.stages)
+
     def stream(self, d, i: int) -> bytes:
         """Tile i's embedded codestream as far as ``d`` holds it."""
         n = len(d)
@@ -282,27 +286,36 @@ def _pieces(lay: dict) -> List[int]:
     return [b - a for a, b in zip(edges, edges[1:])]
 
 
+def _check_head(head, s: _Picture, i: int, first: Optional[dict], rc0, what: str) -> dict:
+    """The embedded.layout of tile i's whole head, checked against the table: the head ends at the tile's base_end, the
+    round pieces are those of its marks, plain or scheduled as the picture is, the picture's tile shape; and against
+    ``first``, the layout of tile ``rc0`` (None: this is the first head, and it is checked against the header's thresholds):
+    all tiles alike."""
+    lay = _tile_layout(head, s.g, s.rc(i), what, s.stages)
+    want = _pieces(lay)
+    if s.nr > len(want) - 1 or [int(v) for v in s.table[i]] != want[:1 + s.nr]:
+        raise ValueError(f"{what}: the header contradicts tile {s.rc(i)}: its table row {[int(v) for v in s.table[i]]} is not the "
+                         f"head and the first {s.nr} round pieces of the tile's own codestream, {want}")
+    if first is None:
+        if s.thresholds is not None and tuple(s.thresholds.shape) != (len(lay["marks"]), lay["ns"]):
+            raise ValueError(f"{what}: the header contradicts tile {s.rc(i)}: thresholds of {s.thresholds.shape[0]} marks x "
+                             f"{s.thresholds.shape[1]} slices, the tile carries {len(lay['marks'])} marks of {lay['ns']} slices")
+    else:
+        _unlike(lay, first, s.rc(i), rc0, what)
+    return lay
+
+
 def _tile_meta(d, s: _Picture, what: str) -> Optional[dict]:
-    """Reads the head of every present tile that ``d`` holds whole and checks it against the table: the head ends at the
-    tile's base_end, the round pieces are those of its marks, no schedule, the picture's tile shape, and all tiles alike.
-    Returns the first one's embedded.layout, None when ``d`` holds no head yet."""
+    """Reads the head of every present tile that ``d`` holds whole and checks it (:func:`_check_head`).  Returns the first
+    one's embedded.layout, None when ``d`` holds no head yet."""
     first, rc0 = None, None
     for i in (int(v) for v in np.flatnonzero(s.present)):
         off, size = int(s.off[0, i]), int(s.size[0, i])
         if off + size > len(d):
             break
-        lay = _tile_layout(d[off:off + size], s.g, s.rc(i), what, s.stages)
-        want = _pieces(lay)
-        if s.nr > len(want) - 1 or [int(v) for v in s.table[i]] != want[:1 + s.nr]:
-            raise ValueError(f"{what}: the header contradicts tile {s.rc(i)}: its table row {[int(v) for v in s.table[i]]} is not the "
-                             f"head and the first {s.nr} round pieces of the tile's own codestream, {want}")
+        lay = _check_head(d[off:off + size], s, i, first, rc0, what)
         if first is None:
             first, rc0 = lay, s.rc(i)
-            if s.thresholds is not None and tuple(s.thresholds.shape) != (len(lay["marks"]), lay["ns"]):
-                raise ValueError(f"{what}: the header contradicts tile {rc0}: thresholds of {s.thresholds.shape[0]} marks x "
-                                 f"{s.thresholds.shape[1]} slices, the tile carries {len(lay['marks'])} marks of {lay['ns']} slices")
-        else:
-            _unlike(lay, first, s.rc(i), rc0, what)
     return first
 
 
@@ -447,6 +460,23 @@ def tile_stream(data, r: int, c: int) -> bytes:
     return s.stream(d, i)
 
 
+def _kept(s: _Picture, window, rounds, what: str) -> Tuple[int, np.ndarray]:
+    """(the rounds, bool [R C]: the tiles) that :func:`extract` of ``window`` and ``rounds`` keeps of the picture ``s``."""
+    nr = s.nr if rounds is None else _int(rounds, f"{what}: rounds")
+    if not 0 <= nr <= s.nr:
+        raise ValueError(f"{what}: rounds is 0 .. {s.nr} (the rounds this codestream holds), got {nr}")
+    keep = np.zeros_like(s.present)
+    if window is None:
+        keep[:] = s.present
+    else:
+        for r, c in tiles_for(s.g, _window(s.g, window, what)):
+            i = r * s.g["C"] + c
+            if not s.present[i]:
+                raise ValueError(f"{what}: the window {tuple(window)} needs tile ({r}, {c}), which is absent from this codestream")
+            keep[i] = True
+    return nr, keep
+
+
 def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
     """A shorter picture codestream of the same picture: only the tiles ``tiles_for(window)`` (None: those present) and only
     the first ``rounds`` rounds (None: all it has).  What a server does to crop and to cut the quality, without the model.
@@ -456,18 +486,7 @@ def extract(data, window=None, rounds: Optional[int] = None) -> bytes:
     exactly at stage k."""
     d, s = _parse(data, "extract")
     _tile_meta(d, s, "extract")
-    nr = s.nr if rounds is None else _int(rounds, "extract: rounds")
-    if not 0 <= nr <= s.nr:
-        raise ValueError(f"extract: rounds is 0 .. {s.nr} (the rounds this codestream holds), got {nr}")
-    keep = np.zeros_like(s.present)
-    if window is None:
-        keep[:] = s.present
-    else:
-        for r, c in tiles_for(s.g, _window(s.g, window, "extract")):
-            i = r * s.g["C"] + c
-            if not s.present[i]:
-                raise ValueError(f"extract: the window {tuple(window)} needs tile ({r}, {c}), which is absent from this codestream")
-            keep[i] = True
+    nr, keep = _kept(s, window, rounds, "extract")
     table = np.where(keep[:, None], s.table[:, :1 + nr], 0)
     short = np.argwhere((s.held(len(d))[:1 + nr].T < table))
     if len(short):
@@ -1081,8 +1100,7 @@ class PictureFeed:
     def facts(self) -> Optional[dict]:
         """Once the header is complete (None before): the geometry of :func:`grid` with ``total``, ``allocation`` and
         ``stages`` as :func:`layout` names them; with ``meta``, what vampic.pyramid checks its levels on."""
-        s = self._s
-        return None if s is None else dict(s.g, total=s.total, allocation=ALLOCATIONS[s.version == VERSION_POOLED], stages=s.stages)
+        return None if self._s is None else self._s.facts()
 
     def mark(self):
         """What :meth:`rewind` needs to undo the feeds that follow: vampic.pyramid feeds one receiver per level and refuses
@@ -1116,7 +1134,12 @@ class PictureStream:
     view's window; ``last_decoded``: those that ran the network; ``decoded_total``: the running count.  :meth:`drop` empties
     the cache."""
 
-    def __init__(self, model, coder: Optional[str] = None, group: Optional[int] = None, cache_tiles: Optional[int] = None):
+    def __init__(self, model, coder: Optional[str] = None, group: Optional[int] = None, cache_tiles: Optional[int] = None,
+                 feed_state=None):
+        """``feed_state``: the byte bookkeeping, by default a new :class:`PictureFeed`.  Anything else keeps the bytes its own
+        way (``vampic.session`` holds them by tile) and gives what the cache and the views read of a ``PictureFeed``: ``_s``,
+        ``meta``, ``ready``, ``need()``, ``tile_rounds``, ``_per_tile`` and ``tile_bytes``; it is then filled from outside, not
+        through :meth:`feed`."""
         from . import progressive as P
         EB._check_model(model)
         self.m, self.coder = model, P._check_coder(model, coder)
@@ -1126,7 +1149,7 @@ class PictureStream:
             if cache_tiles < 1:
                 raise ValueError(f"PictureStream: cache_tiles is the tiles the cache holds, >= 1, got {cache_tiles}")
         self._cache_arg = cache_tiles
-        self.feed_state = PictureFeed("PictureStream")
+        self.feed_state = PictureFeed("PictureStream") if feed_state is None else feed_state
         self.group: Optional[int] = None
         self.cache_tiles: Optional[int] = None
         self.last_tiles: List[Tuple[int, int]] = []
@@ -1138,6 +1161,7 @@ class PictureStream:
         self._free: List[int] = []
         self._held_key = {}                                 # tile index -> the ("held", n) key it is cached under
         self._generation = 0
+        self._sized()
 
     # ------------------------------------------------------------------------------------------------------ the bytes
     ready = property(lambda self: self.feed_state.ready)
@@ -1170,13 +1194,17 @@ class PictureStream:
         """:meth:`PictureFeed.feed`: host arithmetic only, it touches no GPU and no cache entry (a stale tile is found by
         its key at the next view)."""
         out = self.feed_state.feed(chunk)
+        self._sized()
+        return out
+
+    def _sized(self):
+        """``group`` and ``cache_tiles`` for the stream's geometry, once the header is complete."""
         if self.group is None and self.feed_state._s is not None:
             g = self.feed_state._s.g
             self.group = self._group_arg if self._group_arg is not None else _default_group(g["th"], g["tw"])
             span = lambda n, t, S, N: min(N, (min(1024, n) + t - 2) // S + 1)     # the most tiles a span of 1024 meets along an axis
             self.cache_tiles = self._cache_arg if self._cache_arg is not None else \
                 max(self.group, span(g["H"], g["th"], g["Sy"], g["R"]) * span(g["W"], g["tw"], g["Sx"], g["C"]))
-        return out
 
     # ------------------------------------------------------------------------------------------------------ the cache
     def drop(self):

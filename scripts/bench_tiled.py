@@ -55,11 +55,19 @@ vam_tile_compose of the same output size, timed as ``--fill`` times its kernels;
 picture beside ``decode`` of the level it picks, a level-0 rect at scale 1.5 beside ``decode`` of its support window, and pan
 steps of that rect on a warm ``PyramidStream``: wall time and the tiles that ran the network.
 
+``--pyramid --session`` adds ``"session"`` to it: one ``session.Server`` and one ``session.Client`` follow a tour
+of 512 x 768 viewports after the session's opening message (``Server.open()``, the headers; ``open_bytes``, in no step and not
+in ``sum_bytes``) -- the whole picture, a zoom to a level-0 rect in the middle, eight pan steps of (+64, -96) pixels, all
+rounds instead of the first two, and a zoom out to the whole picture.  Per step: the bytes of the server's increment beside
+the length of ``pyramid.extract_viewport`` for the same request, the tiles composed and those that ran the network, and the
+wall time of merging the message and viewing the viewport (filled, at the mark the rounds hold) beside a fresh
+``PyramidDecoder`` on the stateless extract showing the same viewport; every run starts a new server and client.
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
-                                  [--schedule roi] [--stream] [--pan] [--pyramid [--fill] [--zoom]]
+                                  [--schedule roi] [--stream] [--pan] [--pyramid [--fill] [--zoom] [--session]]
 """
 import argparse
 import json
@@ -379,6 +387,9 @@ def pyramid(a, net, x, g, kw, TL, PY, ops):
         out["fill"] = fill(a, net, data, lay, g, TL, PY, ops)
     if a.zoom:
         out["zoom"] = zoom(a, net, data, lay, g, TL, PY, ops)
+    if a.session:
+        from vampic import session as SS
+        out["session"] = session(a, net, data, lay, g, PY, SS)
     return out
 
 
@@ -497,6 +508,47 @@ def zoom(a, net, data, lay, g, TL, PY, ops):
     return {"kernel": kernel, "end_to_end": end}
 
 
+def session(a, net, data, lay, g, PY, SS):
+    """The ``--session`` section: see the module docstring."""
+    H, W = g["H"], g["W"]
+    oh, ow = min(512, H), min(768, W)
+    n_marks = len(lay["levels"][0]["layout"]["marks"])
+    low = min(2, n_marks)
+    y0, x0 = (H - oh) // 2, (W - ow) // 2
+    pans = [(min(y0 + 64 * (i + 1), H - oh), max(x0 - 96 * (i + 1), 0), oh, ow) for i in range(8)]
+    tour = [("whole picture", None, low), ("zoom to level 0", (y0, x0, oh, ow), low)] + [(f"pan {i + 1}", rect, low) for i, rect in enumerate(pans)] \
+        + [("all rounds", pans[-1], None), ("zoom out", None, None)]
+    times = [{"session_ms": [], "stateless_ms": []} for _ in tour]
+    rows = [None] * len(tour)
+    for run in range(a.warmup + a.reps):
+        server, client = SS.Server(data), SS.Client(net, coder=a.coder, cache_tiles=g["R"] * g["C"])
+        opening = server.open()                                    # the headers, once, before the first request
+        client.merge(opening)
+        for i, (name, rect, rounds) in enumerate(tour):
+            m = n_marks - 1 if rounds is None else rounds - 1
+            message = server.viewport(rect, (oh, ow), 1, rounds)
+
+            def step():
+                client.merge(message)
+                return client.viewport(rect, (oh, ow), mark=m, fill=True)
+            ts, got = timed(step)
+            rows[i] = {"step": name, "rect": None if rect is None else list(rect), "rounds": rounds, "level": client.last_chain[0][0],
+                       "tiles": len(client.last_tiles), "decoded": sum(len(e[2]) for e in client.last_chain)}
+            stateless = PY.extract_viewport(data, rect, (oh, ow), 1, rounds)
+            tf, want = timed(lambda: PY.PyramidDecoder(net, stateless, coder=a.coder).viewport(rect, (oh, ow), mark=m, fill=True))
+            rows[i].update({"bytes": len(message), "bytes_stateless": len(stateless)})
+            if run == a.warmup + a.reps - 1:                       # what was timed is what the stateless extract shows
+                assert torch.equal(got, want), name
+            if run >= a.warmup:
+                times[i]["session_ms"].append(ts)
+                times[i]["stateless_ms"].append(tf)
+    for row, t in zip(rows, times):
+        row.update({k: spread(v) for k, v in t.items()})
+    return {"runs": a.reps, "out_hw": [oh, ow], "open_bytes": len(opening), "steps": rows, "sum_bytes": sum(r["bytes"] for r in rows),
+            "sum_bytes_stateless": sum(r["bytes_stateless"] for r in rows), "sum_decoded": sum(r["decoded"] for r in rows),
+            "sum_session_ms": round(sum(r["session_ms"][0] for r in rows), 2), "sum_stateless_ms": round(sum(r["stateless_ms"][0] for r in rows), 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--height", type=int, default=2048)
@@ -515,9 +567,10 @@ def main():
     ap.add_argument("--pyramid", action="store_true")
     ap.add_argument("--fill", action="store_true")
     ap.add_argument("--zoom", action="store_true")
+    ap.add_argument("--session", action="store_true")
     a = ap.parse_args()
-    if (a.fill or a.zoom) and not a.pyramid:
-        ap.error("--fill and --zoom are parts of --pyramid")
+    if (a.fill or a.zoom or a.session) and not a.pyramid:
+        ap.error("--fill, --zoom and --session are parts of --pyramid")
     from bench import build_model
     import vampic
     from vampic import embedded as EB, evaluate as EV, ops, pyramid as PY, tiled as TL
