@@ -297,6 +297,8 @@ _SIGNATURES = {
     "vam_rans_interleaved_decode_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long,
                                                      C.c_int, C.POINTER(VamRansTables), C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]),
+    "vam_rans_interleaved_cut_table_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.POINTER(VamRansTables),
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_rans_interleaved_encode_nhwc_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.POINTER(VamRansTables),
                                                           C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vam_rans_interleaved_decode_nhwc_device": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8

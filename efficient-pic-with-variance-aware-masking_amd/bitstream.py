@@ -349,10 +349,14 @@ def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables, lanes
     :func:`decode_prefix_streams` yields at least that many symbols of ``stream`` (0 for a count of 0).  One decoding pass.
     ``lanes`` = K > 1: of an :func:`encode_interleaved` string — 4 x the read position after the last word that any of the
     first ``count`` elements reads, 8 K when they read none."""
+    return [int(b) for b in _prefix_bytes(stream, indexes, np.ascontiguousarray([int(c) for c in counts], dtype=np.int64), t, lanes)]
+
+
+def _prefix_bytes(stream: bytes, indexes, want: np.ndarray, t: Tables, lanes: int) -> np.ndarray:
+    """:func:`prefix_bytes` on arrays: ``want`` contiguous int64 counts, the result int64 of the same length."""
     K = check_lanes(lanes)
     src = np.frombuffer(stream, dtype=np.uint8)
     i = _i32(indexes)
-    want = np.ascontiguousarray([int(c) for c in counts], dtype=np.int64)
     out = np.zeros(max(want.size, 1), dtype=np.int64)
     head = (src.ctypes.data if src.size else None, src.size, i.ctypes.data, i.size, t.cdf.ctypes.data, t.cdf.shape[1],
             t.sizes.ctypes.data, t.offsets.ctypes.data, t.cdf.shape[0])
@@ -361,7 +365,15 @@ def prefix_bytes(stream: bytes, indexes, counts: Sequence[int], t: Tables, lanes
         L.check(L.load().vam_rans_interleaved_prefix_bytes(*head, K, *tail), "vam_rans_interleaved_prefix_bytes")
     else:
         L.check(L.load().vam_rans_prefix_bytes(*head, *tail), "vam_rans_prefix_bytes")
-    return [int(b) for b in out[:want.size]]
+    return out[:want.size]
+
+
+def cut_table(stream: bytes, indexes, t: Tables, lanes: int = 1) -> np.ndarray:
+    """The cut table of one embedded string: int32 [n + 1], entry c = :func:`prefix_bytes` of count c,
+    for every count 0 .. n, from ONE prefix_bytes pass over the string (one decoding pass).  The row never decreases, entry 0 is 0 and
+    entry n is at most ``len(stream)``."""
+    n = _i32(indexes).size
+    return _prefix_bytes(stream, indexes, np.arange(n + 1, dtype=np.int64), t, lanes).astype(np.int32)
 
 
 # ---------------------------------------------------------------- coded-size pricing (DESIGN section 9i)
@@ -876,6 +888,51 @@ def encode_embedded_device(r_sym: torch.Tensor, r_idx: torch.Tensor, tables: Dev
     off = np.concatenate([[0], np.cumsum(m[0].astype(np.int64))]) * 4
     data = packed[:int(off[-1]) // 4].cpu().numpy().view(np.uint8)
     return [data[off[k]:off[k + 1]].tobytes() for k in range(ns)], m[2:].astype(np.int64)
+
+
+def cut_table_launch(r_sym: torch.Tensor, r_idx: torch.Tensor, tables: DeviceCoderTables, lanes: int, cut: torch.Tensor,
+                     status: torch.Tensor):
+    """ONE vam_rans_interleaved_cut_table_device launch on the current stream, no synchronisation and no allocation: the
+    cut tables of the streams of ``r_sym`` / ``r_idx`` (as :func:`encode_embedded_device` takes them) into ``cut``
+    (contiguous int32 [n_streams, n + 1] on the device) and their status codes into ``status`` (int32 [n_streams])."""
+    from . import ops
+    K = check_lanes(lanes)
+    for a in (r_sym, r_idx):
+        if a.dtype != torch.int32 or not a.is_contiguous() or a.dim() < 1 or tuple(a.shape) != tuple(r_sym.shape) or not a.is_cuda:
+            raise ValueError("device coder: the ranked symbols and indexes are contiguous int32 device buffers of one shape")
+    n = int(r_sym.shape[-1])
+    ns = int(np.prod(r_sym.shape[:-1]))
+    if cut.dtype != torch.int32 or not cut.is_contiguous() or cut.numel() != ns * (n + 1) or cut.device != r_sym.device:
+        raise ValueError(f"device coder: cut is a contiguous int32 [{ns}, {n + 1}] device buffer")
+    if status.dtype != torch.int32 or not status.is_contiguous() or status.numel() != ns or status.device != r_sym.device:
+        raise ValueError(f"device coder: status is a contiguous int32 [{ns}] device buffer")
+    L.check(L.load().vam_rans_interleaved_cut_table_device(r_sym.data_ptr(), r_idx.data_ptr(), ns, n, K, C.byref(tables.struct),
+                                                           cut.data_ptr(), status.data_ptr(), ops.stream_ptr()),
+            "vam_rans_interleaved_cut_table_device")
+
+
+def cut_table_device(r_sym: torch.Tensor, r_idx: torch.Tensor, tables: DeviceCoderTables, lanes: int = 1) -> torch.Tensor:
+    """The cut tables of the streams of the flat ranked buffers ``r_sym`` / ``r_idx`` (contiguous int32 [..., n] on the
+    device, every leading index one stream): int32 [n_streams, n + 1] ON THE DEVICE, entry (s, c) =
+    :func:`prefix_bytes` of count c on the string :func:`encode_embedded_device` writes for stream s, from one dry walk of
+    the encoder (:func:`cut_table_launch`) and one read of the status codes.  A stream the encode launch would refuse is
+    raised as that wrapper raises it."""
+    n = int(r_sym.shape[-1]) if r_sym.dim() else 0
+    ns = int(np.prod(r_sym.shape[:-1])) if r_sym.dim() else 0
+    cut = torch.empty((ns, n + 1), dtype=torch.int32, device=r_sym.device)
+    status = torch.empty(ns, dtype=torch.int32, device=r_sym.device)
+    cut_table_launch(r_sym, r_idx, tables, lanes, cut, status)
+    raise_cut_status(status)
+    return cut
+
+
+def raise_cut_status(status: torch.Tensor):
+    """Reads the status codes of :func:`cut_table_launch` (synchronises) and raises VamError naming the first failed stream."""
+    m = status.cpu().numpy().reshape(-1)
+    bad = np.flatnonzero(m)
+    if bad.size:
+        raise L.VamError(f"vam_rans_interleaved_cut_table_device: embedded stream {int(bad[0])}: {status_text(int(m[bad[0]]))}"
+                         + (f" ({bad.size} streams failed)" if bad.size > 1 else ""))
 
 
 def decode_embedded_uploaded(up: DeviceStreams, first: int, r_idx: torch.Tensor, ranked: torch.Tensor, tables: DeviceCoderTables,

@@ -476,6 +476,90 @@ __global__ __launch_bounds__(kWave) void rans_interleaved_encode_kernel(IlvEncAr
   }
 }
 
+// ---------------------------------------------------------------- cut table
+// cut[s][c], 0 <= c <= n: vam_rans_interleaved_prefix_bytes of count c on the string the kernel above writes for stream s,
+// for EVERY count, from one dry walk of the encoder: the same thread geometry, groups and rounds descending, the same
+// ballots, but no word is stored, so there is no region and no overflow.  The decoder reads an element's LAST word where
+// the encoder flushes for it FIRST; with e_i the stream's words before that flush in encoder order (+inf when element i
+// never flushes) and `words` the string's length, the prefix that decodes c elements ends at 4 (words - min over i < c of
+// e_i), or at 8 K when that minimum is +inf.  Inside a group a high lane may flush in a later round than a low one, hence
+// a minimum and not "the last flushing element".
+// Phase 1, the walk: every thread stores e_i (kNoFlush: none) into cut[s][i + 1] for its own elements i = g K + lane.
+// Phase 2: the stream's lanes rewrite their row ascending, K entries at a time, with a prefix minimum over the stream's
+// lanes and a carry.  A thread reads back only entries it stored itself, so nothing but shuffles and ballots crosses a
+// lane and nothing leaves the wave.  A stream that ends with a status gets a row of zeros.  No thread leaves early.
+constexpr int32_t kNoFlush = 0x7fffffff;
+
+struct CutArgs {
+  const int32_t* sym;
+  const int32_t* idx;
+  int n_streams;
+  long n;
+  int K;
+  vam_rans_tables t;
+  int32_t* cut;              // [n_streams][n + 1]
+  int32_t* status;           // [n_streams]
+};
+
+__global__ __launch_bounds__(kWave) void rans_interleaved_cut_table_kernel(CutArgs a) {
+  const StreamLanes L(blockIdx.x * kWave + threadIdx.x, a.K);
+  const int K = L.K, str = L.str, lane = L.lane, wl = (int)(threadIdx.x & (kWave - 1));
+  const bool valid = str < a.n_streams;
+  const long n = a.n, base = (long)(valid ? str : 0) * n;
+  int32_t* row = a.cut + (long)(valid ? str : 0) * (n + 1);
+  R::Enc e;
+  R::enc_init(e, nullptr, nullptr, false);                    // a dry run: the flush below is the state's half of enc_flush_word
+  int32_t emitted = 0;                                        // words of the stream so far: at most 2 n <= 2^29
+  int32_t st = 0;
+  bool alive = valid;
+  for (long g = (n + K - 1) / K - 1; g >= 0; --g) {
+    const long i = g * K + lane;
+    R::Put u{0, 0, 0, -1};
+    int gets = 0;
+    if (alive && i < n) {
+      st = R::classify(a.sym[base + i], a.idx[base + i], a.t.cdf, a.t.stride, a.t.sizes, a.t.offsets, a.t.n_cdfs, u);
+      gets = st ? 0 : R::put_gets(u);
+    }
+    if (L.mine(__ballot(st != 0))) alive = false;
+    if (!alive) gets = 0;
+    int32_t first = kNoFlush;                                 // e_i of this thread's element
+    for (int t = R::kMaxGets - 1; t >= 0; --t) {
+      const bool act = gets > t;
+      if (!__ballot(act)) continue;
+      const bool fl = act && R::put_flushes(e, u, t);
+      const u64 sub = L.mine(__ballot(fl));
+      if (fl) {
+        if (first == kNoFlush) first = emitted + __popcll(sub & L.above);
+        e.x >>= 32;                                           // after it no bound of enc_put / enc_put_bits is reached again
+      }
+      if (act) R::enc_put_step(e, u, t);
+      emitted += __popcll(sub);
+    }
+    if (valid && i < n) row[i + 1] = first;
+  }
+  const u64 bad = L.mine(__ballot(st != 0));
+  int32_t sst = __shfl(st, bad ? L.shift + __ffsll(bad) - 1 : L.shift);     // the stream's status: its lowest failing lane's
+  if (!bad) sst = 0;
+  const int32_t words = emitted + 2 * K;
+  int32_t carry = kNoFlush;                                   // min of e_i over the groups below
+  for (long g = 0; g * K < n; ++g) {
+    const long i = g * K + lane;
+    const bool has = valid && i < n;
+    int32_t v = has && !sst ? row[i + 1] : kNoFlush;
+    for (int d = 1; d < K; d <<= 1) {                         // inclusive prefix minimum over the stream's lanes
+      const int32_t o = __shfl(v, lane >= d ? wl - d : wl);
+      if (lane >= d && o < v) v = o;
+    }
+    if (carry < v) v = carry;
+    carry = __shfl(v, L.shift + K - 1);                       // lanes past n hold kNoFlush: the last lane's is the group's
+    if (has) row[i + 1] = sst ? 0 : v == kNoFlush ? 8 * K : 4 * (words - v);
+  }
+  if (valid && lane == 0) {
+    row[0] = 0;
+    a.status[str] = sst;
+  }
+}
+
 template <class A>
 struct IlvDecArgs : A {
   const uint8_t* bytes;
@@ -1054,6 +1138,20 @@ int vam_rans_interleaved_encode_device(const int32_t* sym, const int32_t* idx, i
   ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
   hipLaunchKernelGGL(rans_interleaved_encode_kernel<FlatRows>, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
   return check_launch("rans_interleaved_encode_kernel");
+}
+
+int vam_rans_interleaved_cut_table_device(const int32_t* sym, const int32_t* idx, int n_streams, long n, int lanes,
+                                          const vam_rans_tables* tables, int32_t* cut, int32_t* status, void* stream) {
+  const char* what = "vam_rans_interleaved_cut_table_device";
+  VAM_REQUIRE(sym && idx && cut && status, "%s: need sym, idx, cut, status", what);
+  VAM_REQUIRE(n >= 1, "%s: a row has n + 1 >= 2 entries, got n = %ld", what, n);
+  if (int rc = check_streams(what, lanes, n_streams, n)) return rc;      // n <= 2^28: n + 1 and every entry fit an int32
+  if (int rc = check_tables(what, tables)) return rc;
+  CutArgs a{sym, idx, n_streams, n, lanes, *tables, cut, status};
+  const int threads = n_streams * lanes;
+  ProfScope prof(VAM_FAM_MISC, (hipStream_t)stream, 0.0, 0.0);
+  hipLaunchKernelGGL(rans_interleaved_cut_table_kernel, dim3((threads + kWave - 1) / kWave), dim3(kWave), 0, (hipStream_t)stream, a);
+  return check_launch("rans_interleaved_cut_table_kernel");
 }
 
 int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, const int64_t* byte_offsets,

@@ -439,13 +439,9 @@ def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int =
     k is decoded with ``decode(mark=k)``.  Every row also carries ``allocation`` and ``kept_min`` / ``kept_max``: the smallest
     and largest fraction of its progressive elements that a tile keeps at that mark, from the counts in the tiles' heads —
     the spread that a picture-wide threshold opens between flat and busy tiles."""
-    import numpy as np
-    from . import embedded as EB
     from . import tiled as TL
     x = image if image.dim() == 4 else image.unsqueeze(0)
-    H, W = int(x.shape[2]), int(x.shape[3])
     qs = [float(q) for q in qualities]
-    rows = []
     with torch.no_grad():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -453,21 +449,54 @@ def tiled_rd(model, image: torch.Tensor, qualities: Sequence[float], tile: int =
                          allocation=allocation)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        lay = TL.layout(data)
-        ends = lay["round_end"]
-        heads = [data[o:o + n] for row in lay["head"] for o, n in row if n]
-        count = np.asarray([EB.layout(h)["marks"]["count"] for h in heads], dtype=np.float64)            # [tiles, marks, ns]
-        kept = count.sum(-1) / (lay["ns"] * model.dim_chunk * (lay["th"] // 16) * (lay["tw"] // 16))    # [tiles, marks]
-        for k, q in enumerate(qs):
-            torch.cuda.synchronize()
-            t2 = time.perf_counter()
-            dec = TL.PictureDecoder(model, data[:ends[k]], coder=coder, group=group)
-            x_hat = dec.decode(mark=k) if allocation == "picture" else dec.decode(q=q)
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
-            rows.append({"q": q, "bytes": int(ends[k]), "bpp": 8.0 * ends[k] / (H * W), "psnr": compute_psnr(x, x_hat.unsqueeze(0)),
-                         "enc_s": t1 - t0, "dec_s": t3 - t2, "allocation": allocation, "kept_min": float(kept[:, k].min()),
-                         "kept_max": float(kept[:, k].max())})
+        return _tiled_rows(model, x, data, qs, coder, group, allocation, t1 - t0)
+
+
+def _tiled_rows(model, x, data, qs, coder, group, allocation: str, enc_s: float):
+    """The rows of :func:`tiled_rd` for the coded picture ``data`` whose marks are ``qs``: mark k decoded from
+    ``data[:round_end[k]]``, and the kept fractions from the counts in the tiles' heads."""
+    import numpy as np
+    from . import embedded as EB
+    from . import tiled as TL
+    H, W = int(x.shape[2]), int(x.shape[3])
+    rows = []
+    lay = TL.layout(data)
+    ends = lay["round_end"]
+    heads = [data[o:o + n] for row in lay["head"] for o, n in row if n]
+    count = np.asarray([EB.layout(h)["marks"]["count"] for h in heads], dtype=np.float64)            # [tiles, marks, ns]
+    kept = count.sum(-1) / (lay["ns"] * model.dim_chunk * (lay["th"] // 16) * (lay["tw"] // 16))    # [tiles, marks]
+    for k, q in enumerate(qs):
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        dec = TL.PictureDecoder(model, data[:ends[k]], coder=coder, group=group)
+        x_hat = dec.decode(mark=k) if allocation == "picture" else dec.decode(q=q)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        rows.append({"q": q, "bytes": int(ends[k]), "bpp": 8.0 * ends[k] / (H * W), "psnr": compute_psnr(x, x_hat.unsqueeze(0)),
+                     "enc_s": enc_s, "dec_s": t3 - t2, "allocation": allocation, "kept_min": float(kept[:, k].min()),
+                     "kept_max": float(kept[:, k].max())})
+    return rows
+
+
+def tiled_rd_at_sizes(model, image: torch.Tensor, budgets, tile: int = 256, overlap: int = 32, coder=None, lanes: int = 1,
+                      q_tol: float = 1e-3, base_lanes: int = 1, group: Optional[int] = None):
+    """:func:`tiled_rd` at byte budgets instead of qualities (``tiled.encode(allocation="picture", max_bytes=budgets)``,
+    DESIGN section 9ze): the picture is coded ONCE with its rounds placed at the budgets, and mark k is decoded from
+    ``data[:round_end[k]]`` with ``decode(mark=k)``.  One dict per budget: tiled_rd's keys, where "q" is the quality the
+    search solved and "bytes" = ``round_end[k]`` <= the budget, and "budget" itself."""
+    from . import tiled as TL
+    x = image if image.dim() == 4 else image.unsqueeze(0)
+    budgets = TL.check_budgets(budgets, "tiled_rd_at_sizes")
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        data = TL.encode(model, x, tile=tile, overlap=overlap, coder=coder, lanes=lanes, base_lanes=base_lanes, group=group,
+                         allocation="picture", max_bytes=budgets, q_tol=q_tol)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        rows = _tiled_rows(model, x, data, [q for q, _ in TL.budget_marks(data)], coder, group, "picture", t1 - t0)
+    for r, N in zip(rows, budgets):
+        r["budget"] = N
     return rows
 
 

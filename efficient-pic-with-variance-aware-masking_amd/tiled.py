@@ -30,6 +30,10 @@ then u16 allocation (1), n_marks, ns, reserved (0) and the thresholds float32 [n
 CRC.  Tile heads stay ordinary embedded headers.  ``PictureDecoder.decode(mark=k)`` decodes every tile at its header's counts
 of mark k and, on a version-2 stream, checks them against the thresholds on its own sigma.
 
+Rounds at byte budgets: ``encode(..., allocation="picture", max_bytes=[N_1 < ... < N_L])`` solves the
+picture-wide quality of every mark so that ``round_end[k] <= N_k`` (:func:`solve_budgets`, on a cut table of every stream's
+bytes for every count); the stream is the version-2 stream of those marks, and :func:`budget_marks` reads them back.
+
 Scheduled pictures: ``encode(..., schedule=S)`` with ``S`` fp32 [L, H, W], L quality maps at PIXEL
 resolution that never decrease from stage to stage, codes a region of interest first in every prefix.  A tile's schedule is
 ``S_tile[k][a][b] = max over y, x in [0, 16) of S[k][min(r Sy + 16 a + y, H - 1)][min(c Sx + 16 b + x, W - 1)]``
@@ -555,8 +559,115 @@ def _check_picture_schedule(schedule, H: int, W: int, device):
     return S
 
 
+MAX_BUDGETS = 32                           # the marks of one container (progressive.check_q_list)
+
+
+def check_budgets(max_bytes, what: str = "tiled.encode") -> List[int]:
+    """``max_bytes`` as the budget list of :func:`encode`: one integer or 1 .. MAX_BUDGETS strictly increasing integers."""
+    if isinstance(max_bytes, (int, np.integer)) and not isinstance(max_bytes, bool):
+        max_bytes = [max_bytes]
+    try:
+        budgets = [_int(v, f"{what}: max_bytes") for v in max_bytes]
+    except TypeError as e:
+        raise ValueError(f"{what}: max_bytes is a byte budget or a list of them, got {type(max_bytes).__name__}") from e
+    if not 1 <= len(budgets) <= MAX_BUDGETS:
+        raise ValueError(f"{what}: max_bytes: 1 .. {MAX_BUDGETS} budgets, got {len(budgets)}")
+    for k in range(1, len(budgets)):
+        if budgets[k] <= budgets[k - 1]:
+            raise ValueError(f"{what}: max_bytes: budget {k}, {budgets[k]} bytes, does not exceed budget {k - 1}, {budgets[k - 1]} "
+                             "bytes: budgets are strictly increasing")
+    return budgets
+
+
+def solve_budgets(sizes, heads_end: int, budgets: Sequence[int], q_tol: float = 1e-3, what: str = "tiled.encode") -> List[float]:
+    """The qualities of a budgeted picture, on the host alone: per budget N_k the largest quality that
+    ``control.rate_search`` reaches at ``q_tol`` whose round ends within N_k; raising it by q_tol (capped at 10) would not
+    fit unless it is 10.  ``sizes(rows)``: ``rows`` is a list of ascending quality lists in (0, 10], each at most
+    ``control.RATE_GRID`` long, and the result holds, row by row, the byte position at which a round marked at each of those
+    qualities ends, heads included; it never decreases with the quality.  ``heads_end``: where the heads end, what a round
+    of nothing costs.  Every budget is solved on its own: the heads do not depend on the qualities.  ValueError names a
+    budget below ``heads_end``, one that holds the heads but not the smallest quality tried (with the bytes that one needs)
+    and two budgets that solve to one quality."""
+    from .control import rate_search
+    budgets = check_budgets(list(budgets), what)
+    if not q_tol > 0:
+        raise ValueError(f"{what}: q_tol must be > 0, got {q_tol}")
+    for k, N in enumerate(budgets):
+        if N < heads_end:
+            raise ValueError(f"{what}: max_bytes: budget {k}, {N} bytes, is below heads_end = {heads_end} bytes: the header, z, the "
+                             "base and the tile heads, which every prefix needs")
+    least = {}                                                   # per budget: the smallest quality tried and the bytes it needs
+
+    def curve(q, need):
+        rows = [k for k in range(len(budgets)) if need[k, 0].any()]
+        got = sizes([[float(v) for v in q[k, 0][need[k, 0]]] for k in rows])
+        out = np.zeros(q.shape)
+        for k, r in zip(rows, got):
+            out[k, 0][need[k, 0]] = np.asarray(r, dtype=np.float64)
+            q0 = float(q[k, 0][need[k, 0]][0])
+            if k not in least or q0 < least[k][0]:
+                least[k] = (q0, int(r[0]))
+        return out
+    quality, _, _ = rate_search(curve, np.asarray([float(heads_end)]), np.asarray(budgets, dtype=np.float64)[:, None], q_tol)
+    qs = [float(v) for v in quality[:, 0]]
+    for k, q in enumerate(qs):
+        if q <= 0:
+            raise ValueError(f"{what}: max_bytes: budget {k}, {budgets[k]} bytes, holds the heads ({heads_end} bytes) but no round: "
+                             f"the smallest quality tried, {least[k][0]:.6g}, needs {least[k][1]} bytes")
+        if k and q <= qs[k - 1]:
+            raise ValueError(f"{what}: max_bytes: budgets {k - 1} and {k}, {budgets[k - 1]} and {budgets[k]} bytes, solve to the same "
+                             f"quality {q:.6g}: the second round would be empty; drop one of them")
+    return qs
+
+
+def budget_marks(data) -> List[Tuple[float, int]]:
+    """What a picture-wide encode marked, and :func:`encode` with ``max_bytes`` solved: ``[(q_k, round_end[k])]`` per mark,
+    the qualities from the tile heads, the round ends from the header's table.  ``data``: any prefix that holds the header
+    and one tile's head.  ValueError for a stream that is not picture-wide (version 2)."""
+    lay = layout(data)
+    if lay["allocation"] != "picture" or lay["marks"] is None:
+        raise ValueError("budget_marks: " + ("these bytes hold no tile's head yet" if lay["allocation"] == "picture" else
+                                             "the marks of this codestream are not picture-wide (allocation='picture')"))
+    return [(float(q), int(e)) for q, e in zip(lay["marks"], lay["round_end"])]
+
+
+def _round_ends(keys, cuts, qs):
+    """int64 [len(qs)] on the device: the bytes of all tiles' embedded streams up to a picture-wide mark at each of the
+    ascending qualities ``qs`` (at most 32), from the pooled keys and the cut table ``cuts`` int32 [T, ns, n + 1]: one
+    vam_pooled_select, one vam_threshold_counts, a gather and a sum.  No synchronisation."""
+    import torch
+    from . import ops
+    T, ns, _ = keys.shape
+    thr = torch.empty((len(qs), ns), dtype=torch.float32, device=keys.device)
+    count = torch.empty((len(qs), T, ns), dtype=torch.int32, device=keys.device)
+    ops.pooled_select(keys, qs, thr)
+    ops.threshold_counts(keys, thr, count)
+    return torch.gather(cuts, 2, count.permute(1, 2, 0).long()).sum(dim=(0, 1), dtype=torch.int64)
+
+
+def _heads_end(H: int, W: int, tile: int, overlap: int, passes, n_marks: int) -> int:
+    """Where the heads of a picture-wide stream of ``n_marks`` marks end, measured on a packed stream: the picture of the
+    front passes' z and base strings with EMPTY embedded strings is nothing but header and heads.  Neither the picture
+    header nor a tile head depends on the values of marks, counts, bytes or thresholds, only on how many there are."""
+    streams = []
+    for _, st in passes:
+        K, Kb, ns = st["K"], st["Kb"], st["m"].ns0
+        zero = [[0] * ns for _ in range(n_marks)]
+        for b in range(st["B"]):                      # the container embedded._encode_finish builds, with nothing embedded
+            c = {"format": EB._format_of(K, Kb, False), "shape": (st["H"] // 64, st["W"] // 64), "z": [st["z_str"][b]],
+                 "base": [[st["base"][i][b]] for i in range(ns)], "embedded": [b""] * ns,
+                 "marks": {"q": [float(k + 1) for k in range(n_marks)], "count": zero, "bytes": zero}}
+            if c["format"] != EB.FORMAT:
+                c["lanes"] = K
+            if Kb > 1:
+                c["base_lanes"] = Kb
+            streams.append(EB.to_bytes(c))
+    return len(pack(H, W, tile, overlap, streams, thresholds=np.zeros((n_marks, passes[0][1]["m"].ns0), dtype=np.float32)))
+
+
 def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Sequence[float]] = None, coder: Optional[str] = None,
-           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile", schedule=None) -> bytes:
+           lanes: int = 1, base_lanes: int = 1, group: Optional[int] = None, allocation: str = "tile", schedule=None,
+           max_bytes=None, q_tol: float = 1e-3) -> bytes:
     """The picture codestream of ``image``, fp32 [3, H, W] or [1, 3, H, W] on the device, any H, W >= 1: the tiles are cut
     ``group`` at a time (vam_tile_extract, one launch per group), each group goes through ``embedded.encode_batch`` (``marks``,
     ``coder``, ``lanes`` and ``base_lanes`` are its) and ``embedded.to_bytes``, and :func:`pack` frames them.  ``group``: the
@@ -569,6 +680,17 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     every tile's counts; pass 2 (``embedded._encode_finish``) marks the tiles with them.  The tile heads stay ordinary
     embedded headers; the picture header is version 2 and carries the thresholds.  Marks are qualities > 0.
 
+    ``max_bytes`` = N or [N_1 < ... < N_L], 1 <= L <= 32 (with ``allocation="picture"`` only, exclusive
+    with ``marks`` and ``schedule``): rounds that end at byte budgets.  The result is an ordinary version-2 stream of L
+    marks whose ``layout(data)["round_end"][k] <= N_k``; mark k's quality is the largest that ``control.rate_search``
+    reaches at ``q_tol`` (:func:`solve_budgets`), and :func:`budget_marks` reads it back.  Pass 1 also fills a cut table int32
+    [T, ns, n + 1] on the device, the bytes of every stream for EVERY count: one vam_rans_interleaved_cut_table_device
+    launch per group on the device coder, ``bitstream.cut_table`` of the coded strings on the host coder.  A candidate
+    quality then costs one vam_pooled_select and one vam_threshold_counts per 32 of them, a gather and a sum; the coder runs
+    once, in pass 2, with the solved counts, and the bytes it marks must equal the table's (checked, not tolerated).
+    ValueError names a budget that is out of order, below the heads, too small for the smallest quality tried, or that
+    solves to its neighbour's quality.
+
     ``schedule`` (exclusive with ``marks`` and with ``allocation="picture"``): a picture-wide schedule,
     fp32 [L, H, W] on the image's device, 1 <= L <= 32 quality maps at PIXEL resolution, every entry finite and >= 0 and
     never decreasing from stage to stage (checked on the device up front; a violation names stage and pixel).  Per group one
@@ -580,6 +702,17 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     from . import ops
     if allocation not in ALLOCATIONS:
         raise ValueError(f"tiled.encode: allocation is one of {ALLOCATIONS}, got {allocation!r}")
+    budgets = None
+    if max_bytes is not None:
+        if marks is not None or schedule is not None:
+            raise ValueError("tiled.encode: give max_bytes or " + ("marks" if marks is not None else "schedule") + ", not both: "
+                             "byte budgets solve the marks' qualities themselves")
+        if allocation != "picture":
+            raise ValueError(f"tiled.encode: max_bytes goes with allocation='picture', not with {allocation!r}: one threshold per "
+                             "slice over all tiles is what spends a budget where the picture is busy")
+        budgets = check_budgets(max_bytes)
+        if not q_tol > 0:
+            raise ValueError(f"tiled.encode: q_tol must be > 0, got {q_tol}")
     if schedule is not None and marks is not None:
         raise ValueError("tiled.encode: give marks or schedule, not both (a scheduled picture is marked per stage)")
     if schedule is not None and allocation != "tile":
@@ -632,6 +765,8 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
         return pack(H, W, tile, overlap, streams)
     from . import bitstream as bs
     from . import progressive as P
+    if budgets is not None:                # placeholders until the search has run: the front pass needs only their number
+        marks = [10.0 * (k + 1) / len(budgets) for k in range(len(budgets))]
     qs = P.check_q_list(EB.Q_LIST if marks is None else marks)
     if qs[0] <= 0:
         raise ValueError(f"tiled.encode: a picture-wide mark is a quality > 0, got {qs}")
@@ -643,19 +778,58 @@ def encode(model, image, tile: int = 256, overlap: int = 32, marks: Optional[Seq
     with torch.no_grad():
         keys = torch.empty((T, ns, n), dtype=torch.int32, device=img.device)      # the bits of uint32 keys
         passes = []
+        cuts = cut_status = None
+        if budgets is not None:                                                   # the cut table: bytes for EVERY count of every stream
+            cuts = torch.empty((T, ns, n + 1), dtype=torch.int32, device=img.device)
+            cut_status = torch.zeros(T * ns, dtype=torch.int32, device=img.device)
+            tg = bs.DeviceCoderTables.of(model.gaussian_conditional, img.device) if coder == "device" \
+                else bs.Tables.of(model.gaussian_conditional)
         for i0 in range(0, T, group):                                             # pass 1: the network runs once per tile
             st = EB._encode_front(model, cut(i0), qs, coder, K, Kb)
             ops.pool_keys(st.pop("std_p"), st.pop("perm"), keys, t0=i0, n_slice=ns)
             passes.append((i0, st))
+            if budgets is None:
+                continue
+            B = st["B"]
+            if coder == "device":                                                 # one dry walk of the encoder, no read-back
+                bs.cut_table_launch(st["r_sym"], st["r_idx"], tg, K, cuts[i0:i0 + B], cut_status[i0 * ns:(i0 + B) * ns])
+            else:                                                                 # one decoding pass per coded string, on the host's threads
+                rows = EB._map_threads(lambda bj, st=st: bs.cut_table(st["emb_str"][bj[0] * ns + bj[1]], st["r_idx"][bj[0], bj[1]], tg, K),
+                                       [(b, j) for b in range(B) for j in range(ns)])
+                cuts[i0:i0 + B].copy_(torch.from_numpy(np.stack(rows).reshape(B, ns, n + 1)))
+        if budgets is not None:
+            bs.raise_cut_status(cut_status)
+            heads_end = _heads_end(H, W, tile, overlap, passes, len(budgets))
+
+            def round_ends(rows):                                                 # per row: 2 launches, a gather, a sum; ONE read-back
+                ends = torch.stack([_round_ends(keys, cuts, row) for row in rows]).cpu().numpy()      # a pass asks rows of one length
+                return [heads_end + e for e in ends]
+            qs = solve_budgets(round_ends, heads_end, budgets, q_tol)
+            for _, st in passes:
+                st["qs"] = list(qs)
         thr = torch.empty((len(qs), ns), dtype=torch.float32, device=img.device)
         count = torch.empty((len(qs), T, ns), dtype=torch.int32, device=img.device)
         ops.pooled_select(keys, qs, thr)
         ops.threshold_counts(keys, thr, count)
+        if budgets is not None:                                                   # what the table says the marks' bytes are
+            want = torch.gather(cuts, 2, count.permute(1, 2, 0).long()).cpu().numpy().astype(np.int64)      # [T, ns, L]
         for i0, st in passes:                                                     # pass 2: the marks' bytes from the picture's counts
             cs = EB._encode_finish(st, count[:, i0:i0 + st["B"]].contiguous())
+            if budgets is not None:
+                for b, c in enumerate(cs):                                        # the coder's own positions: equal, or a bug
+                    got = np.asarray(c["marks"]["bytes"], dtype=np.int64).T
+                    if not np.array_equal(got, want[i0 + b]):
+                        raise AssertionError(f"tiled.encode: tile {coords[i0 + b]}: the coder marks its slices at {got.tolist()} bytes, "
+                                             f"the cut table says {want[i0 + b].tolist()} (slice by mark)")
             streams += [EB.to_bytes(c) for c in cs]
         thr = thr.cpu().numpy()
-    return pack(H, W, tile, overlap, streams, thresholds=thr)
+    data = pack(H, W, tile, overlap, streams, thresholds=thr)
+    if budgets is not None:
+        ends = [int(want[:, :, k].sum()) + heads_end for k in range(len(budgets))]
+        got = layout(data)["round_end"][:len(budgets)]
+        if got != ends or any(e > N for e, N in zip(ends, budgets)):
+            raise AssertionError(f"tiled.encode: the rounds end at {got}, the search placed them at {ends} within the budgets {budgets}")
+    return data
 
 
 def _ramps_on(have, V: int, device):

@@ -1047,6 +1047,17 @@ int vam_rans_interleaved_decode_device(const uint8_t* bytes, long bytes_total, c
                                        const int32_t* byte_lengths, const int32_t* idx, int n_streams, long n, int lanes,
                                        const vam_rans_tables* tables, int32_t* sym_out, int32_t* available, int32_t* status,
                                        void* stream);
+/* The cut table.  vam_rans_interleaved_cut_table_device: for the streams vam_rans_interleaved_encode_device
+ * reads (same sym / idx, n_streams, n >= 1, lanes, tables), cut [n_streams][n + 1] receives, for EVERY count 0 <= c <= n,
+ * cut[s][c] = vam_rans_interleaved_prefix_bytes of count c on the string that launch writes for stream s (K = 1:
+ * vam_rans_prefix_bytes): 0 for c = 0, 8 K while none of the elements 0 .. c - 1 reads a word, else 4 * the read position
+ * after the last word any of them reads.  A row never decreases and cut[s][n] is at most the string's length.  It is a dry
+ * walk of the encoder in the encode launch's thread geometry: no word is written, so there is no region, no lengths and no
+ * status 4.  status[s] = 0, or 2 / 3 / 5 as the encode launch gives them, and then row s is all zeros.  No atomics, no
+ * allocation; capturable.  Null pointers, n < 1, n > 2^28 (so that n + 1 and every entry fit an int32) and an invalid
+ * lanes are VAM_EINVAL with a message, and nothing is launched or written. */
+int vam_rans_interleaved_cut_table_device(const int32_t* sym, const int32_t* idx, int n_streams, long n, int lanes,
+                                          const vam_rans_tables* tables, int32_t* cut, int32_t* status, void* stream);
 /* The same strings over the stream geometry of vam_rans_encode_device / vam_rans_decode_device: a stream
  * is an (image, slice) pair over the channels [c0 + s C, c0 + (s + 1) C) of int32 NHWC buffers [B, h, w, ld], stream id =
  * s * B + image, n = C h w, element i = channel i / (h w) at pixel i % (h w); idx NULL: the table index is the channel.

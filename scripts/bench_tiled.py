@@ -63,11 +63,19 @@ the length of ``pyramid.extract_viewport`` for the same request, the tiles compo
 wall time of merging the message and viewing the viewport (filled, at the mark the rounds hold) beside a fresh
 ``PyramidDecoder`` on the stateless extract showing the same viewport; every run starts a new server and client.
 
+``--budget N [N ...]`` adds ``"budget"``: ``tiled.encode(allocation="picture", max_bytes=[N ...])`` beside
+``encode(allocation="picture", marks=)`` at the qualities it solved, whose code that section's commit did not touch ([median,
+min, max] ms each; the two streams must be identical); ``tiled.solve_budgets`` alone inside such an encode with its passes,
+launches and read-backs; the ``cut`` buffer's size; and vam_rans_interleaved_cut_table_device alone on the last group of tiles
+beside vam_rans_interleaved_encode_device on the same buffers with the solved marks, at 1 and 64 lanes (HIP events over 50
+launches, three times each).
+
 No time is asserted.  Prints one JSON line.
 
     python scripts/bench_tiled.py [--height 2048] [--width 3072] [--tile 256] [--overlap 32] [--warmup 1] [--reps 3]
                                   [--coder host|device] [--lanes 1] [--base-lanes 1] [--allocation tile picture]
                                   [--schedule roi] [--stream] [--pan] [--pyramid [--fill] [--zoom] [--session]]
+                                  [--budget BYTES [BYTES ...]] [--q-tol 1e-3]
 """
 import argparse
 import json
@@ -188,6 +196,83 @@ def allocations(a, net, x, g, kw, TL, EB, ops):
         dt = TL.PictureDecoder(net, streams["tile"], coder=a.coder)
         out["decode_mark"]["tile_q_ms"] = round(wall_ms(lambda: dt.decode(q=qs[k]), a.warmup, a.reps)[0], 2)
         out["decode_mark"]["tile_mark_ms"] = round(wall_ms(lambda: dt.decode(mark=k), a.warmup, a.reps)[0], 2)
+    return out
+
+
+def budget(a, net, x, g, kw, TL, EB, ops):
+    """The ``--budget`` section: see the module docstring."""
+    import ctypes as C
+    from vampic import _lib as L, bitstream as bs, control
+    dev, ns = x.device, net.ns0
+    budgets = [int(v) for v in a.budget]
+
+    def runs(fn):
+        times, out = [], None
+        for i in range(a.warmup + a.reps):
+            ms, out = timed(fn)
+            if i >= a.warmup:
+                times.append(ms)
+        return spread(times), out                                  # [median, min, max]
+    enc = lambda: TL.encode(net, x, allocation="picture", max_bytes=budgets, q_tol=a.q_tol, **kw)
+    t_budget, data = runs(enc)
+    solved = TL.budget_marks(data)
+    qs = [q for q, _ in solved]
+    t_marks, again = runs(lambda: TL.encode(net, x, allocation="picture", marks=qs, **kw))      # the path this section did not touch
+    out = {"budgets": budgets, "q_tol": a.q_tol, "solved": [[q, e] for q, e in solved], "encode_budget_ms": t_budget,
+           "encode_marks_ms": t_marks, "identical": again == data}
+    # the search alone, and what it launches
+    calls, took = {"round_ends": 0, "reads": 0}, []
+    inner, solve = TL._round_ends, TL.solve_budgets
+
+    def counted(*args):
+        calls["round_ends"] += 1
+        return inner(*args)
+
+    def solve_timed(sizes, *args, **kwargs):
+        def sizes_counted(rows):
+            calls["reads"] += 1
+            return sizes(rows)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = solve(sizes_counted, *args, **kwargs)
+        torch.cuda.synchronize()
+        took.append(1e3 * (time.perf_counter() - t0))
+        return r
+    TL._round_ends, TL.solve_budgets = counted, solve_timed
+    try:
+        for _ in range(a.reps):
+            enc()
+    finally:
+        TL._round_ends, TL.solve_budgets = inner, solve
+    out["search"] = {"ms": spread(took), "passes": control.rate_search_passes(a.q_tol), "read_backs": calls["reads"] // a.reps,
+                     "pooled_select_launches": calls["round_ends"] // a.reps, "threshold_counts_launches": calls["round_ends"] // a.reps,
+                     "launches_per_budget": 2 * calls["round_ends"] // a.reps // len(budgets)}
+    # the cut-table launch alone beside the encode launch, on the last group of tiles
+    coords = TL.tiles_for(g)
+    T, n, group = len(coords), net.dim_chunk * (g["th"] // 16) * (g["tw"] // 16), TL._default_group(g["th"], g["tw"])
+    out["cut_buffer"] = {"shape": [T, ns, n + 1], "bytes": 4 * T * ns * (n + 1)}
+    part = coords[-group:]
+    t = torch.empty((len(part), 3, g["th"], g["tw"]), dtype=torch.float32, device=dev)
+    ops.tile_extract(x, torch.tensor(part, dtype=torch.int32).to(dev), t, g["V"])
+    st = EB._encode_front(net, t, qs, "device", 1, 1)
+    r_sym, r_idx = st["r_sym"], st["r_idx"]
+    S = len(part) * ns
+    tg = bs.DeviceCoderTables.of(net.gaussian_conditional, dev)
+    cut, status = torch.empty((S, n + 1), dtype=torch.int32, device=dev), torch.empty(S, dtype=torch.int32, device=dev)
+    count = st["count"].contiguous()
+    lib, stream = L.load(), ops.stream_ptr()
+    out["kernels"] = {"streams": S, "n": n}
+    for K in (1, 64):
+        cap = 2 * n + 2 * K + 16
+        regions = torch.empty(S * cap, dtype=torch.int32, device=dev)
+        meta = torch.empty((2 + len(qs), S), dtype=torch.int32, device=dev)
+        encode = lambda: L.check(lib.vam_rans_interleaved_encode_device(
+            r_sym.data_ptr(), r_idx.data_ptr(), S, n, K, C.byref(tg.struct), regions.data_ptr(), cap, meta[0].data_ptr(), meta[1].data_ptr(),
+            count.data_ptr(), len(qs), meta[2].data_ptr(), stream), "vam_rans_interleaved_encode_device")
+        table = lambda: bs.cut_table_launch(r_sym, r_idx, tg, K, cut, status)
+        out["kernels"][f"lanes_{K}"] = {"cut_table_us": [round(event_us(table), 2) for _ in range(3)],
+                                        "encode_us": [round(event_us(encode), 2) for _ in range(3)]}
+        assert not int(status.abs().sum()) and not int(meta[1].abs().sum())
     return out
 
 
@@ -568,6 +653,8 @@ def main():
     ap.add_argument("--fill", action="store_true")
     ap.add_argument("--zoom", action="store_true")
     ap.add_argument("--session", action="store_true")
+    ap.add_argument("--budget", type=int, nargs="+", default=None, metavar="BYTES")
+    ap.add_argument("--q-tol", type=float, default=1e-3)
     a = ap.parse_args()
     if (a.fill or a.zoom or a.session) and not a.pyramid:
         ap.error("--fill, --zoom and --session are parts of --pyramid")
@@ -625,6 +712,8 @@ def main():
                                         "overhead_pct": round(100.0 * one["base_end"] / one["total"], 3)}
         if a.allocation:
             res["allocations"] = allocations(a, net, x, g, kw, TL, EB, ops)
+        if a.budget:
+            res["budget"] = budget(a, net, x, g, kw, TL, EB, ops)
         if a.schedule:
             res["scheduled"] = scheduled(a, net, x, g, kw, data, window, TL, EV, ops)
         if a.stream:
