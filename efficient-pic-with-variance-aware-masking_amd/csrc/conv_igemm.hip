@@ -32,6 +32,7 @@
 // layers/rem.py:52-66,130-141, models/pic.py:528-551,598-641.
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace vam {
 
@@ -138,6 +139,22 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
   constexpr int NB = (BN + RPP - 1) / RPP;
   constexpr bool A_FULL = (BM % RPP) == 0, B_FULL = (BN % RPP) == 0;
   static_assert(TM >= 1 && TN >= 1 && BM == TM * WGM * 32 && BN == TN * WGN * 32, "tile/wave layout");
+  // Block map of the wave-specialised 128x224 tile.  Its 4 x 7 blocks of 32x32 are not dealt to the four consumer waves
+  // as rows of seven (8 fragments of 32 rows per 7 blocks) but as 2x2 groups: wave w, pair p = w >> 1, side s = w & 1,
+  // holds the A fragments of row blocks 2p, 2p+1 and the B fragments of column blocks 4s .. 4s+2 and 3; it computes
+  // that 2x3 rectangle and block (2p+s, 3) of the column the pair shares: 6 fragments per 7 blocks.  acc[0][j] is
+  // block j of the wave: j < 6 the rectangle row-major, j = 6 the shared column's.  The side is a compile-time value
+  // of the consumer code (two copies behind one wave-uniform branch), so no fragment is ever selected per lane.
+  // 72 instead of 96 fragment registers and 18 instead of 24 operand reads per 42 MFMAs; 196 VGPRs, no scratch, no
+  // scheduling fence ("Tile choice").
+  constexpr bool MAP22 = SPEC && BM == 128 && BN == 224;
+  static_assert(!MAP22 || (WGM == 4 && WGN == 1), "the 2x2 block map is laid out for 4x1 consumer waves");
+  constexpr int NFA = MAP22 ? 2 : TM, NFB = MAP22 ? 4 : TN;                                     // A / B fragments (32 rows each) a wave reads
+  auto blk_a = [](int i, int j, int S) constexpr { return MAP22 ? (j < 6 ? j / 3 : S) : i; };   // A fragment of block (i, j)
+  auto blk_b = [](int j) constexpr { return MAP22 ? (j < 6 ? j % 3 : 3) : j; };                 // B fragment of block (i, j)
+  auto frag_col = [](int f, int S) constexpr { return MAP22 ? (f < 3 ? 4 * S + f : 3) : f; };   // column block of B fragment f, from the wave's first
+  constexpr std::integral_constant<int, 0> side0{};
+  constexpr std::integral_constant<int, 1> side1{};
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sA = smem;                          // [2][BM][LDS_LD]
@@ -186,6 +203,9 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
   const int tid = (SPEC && (int)threadIdx.x >= NTC) ? (int)threadIdx.x - NTC : (int)threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WGN, wn = wid % WGN;
+  const int u_wid = __builtin_amdgcn_readfirstlane(wid);
+  const int w_rb = MAP22 ? (u_wid & ~1) : wm * TM;   // the wave's first row block and column block in the tile
+  const int w_cb = wn * TN;
   const int ld_row = tid / CPR;              // row within a pass
   const int ld_col = (tid % CPR) * LDW;      // float offset within the chunk
 
@@ -600,75 +620,78 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
         if (b_loff[j] >= 0) *reinterpret_cast<u32x4*>(b + b_loff[j]) = rb[j];
       }
     };
-    const int a_row1 = (wm * TM * 32 + l31) * RS;
-    const int b_row1 = (wn * TN * 32 + l31) * RS;
+    const int a_row1 = (w_rb * 32 + l31) * RS;
+    const int b_row1 = (w_cb * 32 + l31) * RS;
     const int rsw = (l31 >> 2) & 3;                  // rows of a wave's 32-row groups differ by multiples of 32
     const int rd1[2] = {((lh ^ rsw) << 2), (((2 + lh) ^ rsw) << 2)};
     const int rsw3 = (l31 >> 1) & 7;
     const int rd3[2][2] = {{((lh ^ rsw3) << 2), (((4 + lh) ^ rsw3) << 2)}, {(((2 + lh) ^ rsw3) << 2), (((6 + lh) ^ rsw3) << 2)}};   // MODE 3: [k-step][plane]
-    auto compute = [&](int buf) {
+    // `side`: the wave's side of the 2x2 block map (MAP22); side0 for every other tile
+    auto compute_s = [&](int buf, auto side) {
+      constexpr int S = decltype(side)::value;
       const float* a = sA1 + buf * BM * RS + a_row1;
       const float* b = sB1 + buf * BN * RS + b_row1;
       if constexpr (F16) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          f16x8 fa[TM][2], fb[TN][2];
+          f16x8 fa[NFA][2], fb[NFB][2];
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
+          for (int i = 0; i < NFA; ++i)
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) fa[i][pl] = *reinterpret_cast<const f16x8*>(a + i * 32 * RS + rd3[ks][pl]);
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
+          for (int j = 0; j < NFB; ++j)
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) fb[j][pl] = *reinterpret_cast<const f16x8*>(b + j * 32 * RS + rd3[ks][pl]);
+            for (int pl = 0; pl < 2; ++pl) fb[j][pl] = *reinterpret_cast<const f16x8*>(b + frag_col(j, S) * 32 * RS + rd3[ks][pl]);
 #pragma unroll
           for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
+              const int ai = blk_a(i, j, S), bj = blk_b(j);
               // fixed order, smallest terms first: (h,l) (l,h) (h,h)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ai][0], fb[bj][1], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ai][1], fb[bj][0], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ai][0], fb[bj][0], acc[i][j], 0, 0, 0);
             }
         }
         return;
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 fa[TM][3], fb[TN][3];
+        bf16x8 fa[NFA][3], fb[NFB][3];
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < NFA; ++i)
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) fa[i][pl] = *reinterpret_cast<const bf16x8*>(a + i * 32 * RS + pl * 16 + rd1[ks]);
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+        for (int j = 0; j < NFB; ++j)
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) fb[j][pl] = *reinterpret_cast<const bf16x8*>(b + j * 32 * RS + pl * 16 + rd1[ks]);
+          for (int pl = 0; pl < 3; ++pl) fb[j][pl] = *reinterpret_cast<const bf16x8*>(b + frag_col(j, S) * 32 * RS + pl * 16 + rd1[ks]);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
+            const int ai = blk_a(i, j, S), bj = blk_b(j);
             // fixed order, smallest terms first: (hi,lo) (lo,hi) (mid,mid) (hi,mid) (mid,hi) (hi,hi)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][0], fb[bj][2], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][2], fb[bj][0], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][1], fb[bj][1], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][0], fb[bj][1], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][1], fb[bj][0], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ai][0], fb[bj][0], acc[i][j], 0, 0, 0);
           }
-        // seven column groups per wave: 112 accumulator + 96 fragment registers; keep hipcc from hoisting the next
-        // sub-step's 96 fragment registers above this one's MFMAs (39 spilled registers otherwise)
-        if constexpr (TN >= 7) __builtin_amdgcn_sched_barrier(0);
       }
     };
+    auto compute = [&](int buf) { compute_s(buf, side0); };
     // MODE 3: take the two scales out of the accumulators (powers of two: exact).  The per-channel factors 2^-s_n sit
     // behind the packed weights ([taps][Kc][Npad] rows of 128 B, then Npad floats).
-    auto unscale = [&]() {
+    auto unscale_s = [&](auto side) {
       if constexpr (F16) {
+        constexpr int S = decltype(side)::value;
         const float* wsc = P.wpack + (size_t)n_taps * u_Kc * u_Npad * 32;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          const int n = n0 + (wn * TN + j) * 32 + l31;
+          const int n = n0 + (w_cb + frag_col(blk_b(j), S)) * 32 + l31;
           const float f = (n < u_Npad ? wsc[n] : 0.f) * a_unscale;
 #pragma unroll
           for (int i = 0; i < TM; ++i)
@@ -677,6 +700,7 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
         }
       }
     };
+    auto unscale = [&]() { unscale_s(side0); };
     if constexpr (SPEC) {
       // chunk c sits in register stage c & 1 between its global loads and its LDS store, and in LDS buffer c & 1
       // afterwards.  Iteration ch: consumers compute from buffer ch & 1 while loaders store chunk ch+1 into the other
@@ -708,27 +732,54 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
         // the next sub-step's fragment reads ahead of each MFMA block and pinned the order with sched_barrier(0) measured
         // 10-25 % SLOWER on every tile — the pinned order keeps the compiler from interleaving reads and MFMAs)
         __syncthreads();
-        for (int ch = 0; ch < n_chunks; ch += 2) {
-          compute(0);
-          __syncthreads();
-          if (ch + 1 >= n_chunks) break;
-          compute(1);
-          __syncthreads();
-        }
-        unscale();
-        // the whole C tile goes to LDS (it fits in the pipeline buffers, which every wave has left behind the last
-        // barrier); C layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-        if (!direct_out) {
-          float* sCf = smem;
+        auto consume = [&](auto side) {
+          constexpr int S = decltype(side)::value;
+          if constexpr (MAP22) {
+            // whole pairs of chunks, then the odd last one.  (The loop below, with its exit in the middle, makes hipcc
+            // carry the accumulators through the second half in other registers than through the first and spill
+            // fragments there: 8 to 12 registers stored and reloaded per pair of chunks on this tile.  The other tiles
+            // fit either way and keep the loop they were measured with.)
+            int ch = 0;
+            for (; ch + 1 < n_chunks; ch += 2) {
+              compute_s(0, side);
+              __syncthreads();
+              compute_s(1, side);
+              __syncthreads();
+            }
+            if (ch < n_chunks) {
+              compute_s(0, side);
+              __syncthreads();
+            }
+          } else {
+            for (int ch = 0; ch < n_chunks; ch += 2) {
+              compute_s(0, side);
+              __syncthreads();
+              if (ch + 1 >= n_chunks) break;
+              compute_s(1, side);
+              __syncthreads();
+            }
+          }
+          unscale_s(side);
+          // the whole C tile goes to LDS (it fits in the pipeline buffers, which every wave has left behind the last
+          // barrier); C layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+          if (!direct_out) {
+            float* sCf = smem;
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
+              for (int j = 0; j < TN; ++j)
 #pragma unroll
-              for (int r = 0; r < 16; ++r) {
-                const int row = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                sCf[row * (BN + 4) + wn * TN * 32 + j * 32 + l31] = acc[i][j][r];
-              }
+                for (int r = 0; r < 16; ++r) {
+                  const int row = (w_rb + blk_a(i, j, S)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                  sCf[row * (BN + 4) + (w_cb + frag_col(blk_b(j), S)) * 32 + l31] = acc[i][j][r];
+                }
+          }
+        };
+        if constexpr (MAP22) {           // one wave-uniform branch around the whole consumer role
+          if (u_wid & 1) consume(side1);
+          else consume(side0);
+        } else {
+          consume(side0);
         }
       }
     } else if constexpr (NBUF == 2) {
@@ -1767,7 +1818,7 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
   const bool m1 = conv_mode() == 1 || conv_mode() == 3 || w16;
   const Cand* cand = m1 ? cands1 : cands;
   const int n_cand = m1 ? 10 : 14;
-  // deep-K launches of the split-operand mode may use the wave-specialised 128x224 tile (4x1 consumer waves of 32 x 224:
+  // deep-K launches of the split-operand mode may use the wave-specialised 128x224 tile (four consumer waves, 2x2 block map:
   // the layers with 224 output channels without padding them to 256); it exists as a specialised block only
   int min_chunks32 = 1 << 30;
   for (int i = 0; i < nprob; ++i) {
