@@ -22,13 +22,22 @@ __device__ __forceinline__ float gauss_lik(float absv, float sigma) {
   return fmaxf(upper - lower, 1e-9f);            // likelihood_lower_bound, :650
 }
 
-// wave-aggregated atomic accumulation of a per-lane double into acc[item]
+// wave-aggregated atomic accumulation of a per-lane double into acc[item].  Called from inside grid-stride loops: the
+// lanes that have left the loop (a launch's last wave, or the last pass) are inactive here.  `__all` votes over the
+// active lanes only; what a shuffle delivers from an inactive lane is not relied upon — a term enters the sum only if
+// its source lane is in `live`.  The active lanes of a grid-stride pass are a prefix of the wave (the index grows with
+// the lane), so lane 0 is active whenever any lane is and holds the wave's sum after the last step.
 __device__ __forceinline__ void wave_accumulate(double v, int item, double* acc) {
   int first = __builtin_amdgcn_readfirstlane(item);
   if (__all(item == first)) {
+    const unsigned long long live = __ballot(1);
+    const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(acc + first, v);
+    for (int o = 32; o > 0; o >>= 1) {
+      const double t = __shfl_down(v, o, 64);
+      if (lane + o < 64 && ((live >> (lane + o)) & 1ull)) v += t;
+    }
+    if (lane == 0) atomicAdd(acc + first, v);
   } else {
     atomicAdd(acc + item, v);
   }

@@ -169,6 +169,7 @@ def test_gauss_likelihood_and_indexes():
     # lik = Phi(a) - Phi(b): two erfc values of magnitude <= 1 whose implementations differ by a
     # few ulp (6e-8 each), so the tolerance is absolute
     err = (lik.cpu() - ref).abs().max().item()
+    # (the bound in bits, the tails and the rounding edges: tests/test_gpu_entropy_contract.py)
     assert err < 3e-7, f"likelihood abs err {err}"
     out2, lik2 = gc(y.cuda(), sg.cuda(), None, training=False)
     assert torch.equal(out2.cpu(), torch.round(y))
@@ -194,6 +195,7 @@ def test_entropy_bottleneck():
     err = (lik.cpu() - lik_ref).abs()
     rel = (err / lik_ref).max().item()
     print(f"EB likelihood: abs err {err.max().item():.3g}, rel err {rel:.3g}, min lik {lik_ref.min().item():.3g}")
+    # (the bound in bits against float64, ties and the 1e-9 decision: tests/test_gpu_entropy_contract.py)
     assert err.max().item() <= 3e-7, f"EB likelihood abs err {err.max().item()}"
     assert rel <= 2e-5, rel                            # measured 6.6e-6 (the fp32 oracle's own: 8e-6)
 
