@@ -127,6 +127,12 @@ class VamConv(C.Structure):
     ]
 
 
+class VamConvChoice(C.Structure):
+    """vam_conv_choice: what vam_conv_plan says vam_conv_group would launch a group of problems with."""
+    _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32), ("spec", C.c_int32), ("blocks", C.c_int32),
+                ("dual", C.c_int32 * VAM_MAX_GROUP), ("staged", C.c_int32 * VAM_MAX_GROUP)]
+
+
 class VamPackJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bias", C.c_int32), ("mode", C.c_int32), ("phase", C.c_int32),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("cin", C.c_int32), ("n", C.c_int32), ("pad_", C.c_int32)]
@@ -159,6 +165,7 @@ _SIGNATURES = {
     "vam_conv_set_mode": (C.c_int, [C.c_int]),
     "vam_conv_get_mode": (C.c_int, []),
     "vam_conv_group": (C.c_int, [C.POINTER(VamConv), C.c_int, C.c_void_p]),
+    "vam_conv_plan": (C.c_int, [C.POINTER(VamConv), C.c_int, C.POINTER(VamConvChoice)]),
     "vam_resunit_struct_size": (C.c_size_t, []),
     "vam_resunit_supported": (C.c_int, [C.c_int] * 3),
     "vam_resunit_group": (C.c_int, [C.POINTER(VamResunit), C.c_int, C.c_void_p]),

@@ -2,6 +2,7 @@
 // HIP-event profiler).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <vector>
@@ -44,6 +45,20 @@ inline int check_launch(const char* what) {
   if (e != hipSuccess) {
     set_error("launch of %s failed: %s", what, hipGetErrorString(e));
     return VAM_EHIP;
+  }
+  return VAM_OK;
+}
+
+// Raise a kernel's dynamic-LDS limit.  The limit is a property of the kernel on ONE device: `done` (the caller's, one per
+// kernel) holds a bit per device, so it is set once per device, whichever thread comes first (a second thread setting it
+// again is harmless); devices beyond the mask set it on every call.
+inline int set_dynamic_lds(const void* kernel, int bytes, std::atomic<unsigned long long>& done) {
+  int dev = 0;
+  VAM_CHECK_HIP(hipGetDevice(&dev));
+  const unsigned long long bit = (unsigned)dev < 64u ? 1ull << dev : 0ull;
+  if (!(done.load(std::memory_order_acquire) & bit)) {
+    VAM_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_release);
   }
   return VAM_OK;
 }

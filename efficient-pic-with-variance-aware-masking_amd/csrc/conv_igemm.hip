@@ -30,8 +30,7 @@
 // Replaces nn.Conv2d / nn.ConvTranspose2d (per sub-pixel phase) / nn.Linear plus the
 // surrounding element-wise ops of reference layers/layers.py:5-86, layers/gdn.py:62-75,
 // layers/rem.py:52-66,130-141, models/pic.py:528-551,598-641.
-#include "common.h"
-#include <cstdlib>
+#include "conv_host.h"
 #include <type_traits>
 
 namespace vam {
@@ -41,43 +40,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-struct ConvP {
-  const float* seg_ptr[VAM_MAX_SEG];
-  int seg_ld[VAM_MAX_SEG];
-  int seg_end[VAM_MAX_SEG];  // cumulative channel end of each segment
-  int n_seg;
-  int H, W, HW;
-  int kh, kw, stride, pad_y, pad_x;
-  int Ho, Wo, HoWo;
-  int P;        // B*Ho*Wo
-  int N, Npad;  // output channels, padded to 32
-  int Cin, Kc, Kc16;  // total input channels, K chunks (of the kernel's BK) per tap, 16-channel packing chunks per tap
-  const float* wpack;
-  const float* bias;
-  float* out;
-  int ldo, Hf, Wf, osy, osx, ooy, oox, Cq, act, flags;
-  const float* pre;
-  const float* mul;
-  const float* post;
-  const float* post2;
-  int ld_pre, ld_mul, ld_post, ld_post2;
-  float* preact;        // optional second output: the value the activation is applied to (bias + pre + conv), fp32, indexed like the output
-  int ld_preact;
-  int tiles_n;
-  const int* in_amax[VAM_MAX_SEG];   // MODE 3: per input segment, a device cell holding the bits of an upper bound of max |x| (nullptr: unused)
-  int* out_amax;        // any mode: if set, the epilogue folds max |stored value| into this cell (integer atomicMax on the float's bits)
-};
-
-constexpr int VAM_CONVI_DUAL = 1 << 29;     // internal ConvP flag: 16-channel input, two taps share one 32-channel K chunk (split-operand mode)
-constexpr int VAM_CONVI_STAGED = 1 << 30;   // internal ConvP flag: tensor extents beyond the direct epilogue's 32-bit window
-
-struct GroupArgs {
-  int nprob;
-  int staged_epilogue;   // 1: every problem takes the LDS-staged epilogue (VAMPIC_EPILOGUE=staged: A/B measurements, bit-identity tests)
-  int tile_start[VAM_MAX_GROUP + 1];
-  ConvP p[VAM_MAX_GROUP];
-};
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
@@ -92,8 +54,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     default: return v;
   }
 }
-
-constexpr int PK = 16;  // packing granularity of the weight buffer along K
 
 // MODE 0: fp32 operands on v_mfma_f32_32x32x2_f32 (exact fp32 fma chain).
 // MODE 1: every fp32 operand is split EXACTLY into three bf16 terms (x = hi + mid + lo, 8 + 8 + 8 mantissa bits) and
@@ -1273,250 +1233,16 @@ __global__ __launch_bounds__(WGM * WGN * 64 * (SPEC ? 2 : 1), SPEC ? ((BM + BN <
   }
   publish();
 }
-
-// ---------------------------------------------------------------- weight packing
-__device__ __forceinline__ float pack_value(const float* __restrict__ src, int mode, int phase, int kh, int kw, int cin,
-                                            int n, int nn, int cc, int ty, int tx) {
-  float v = 0.f;
-  if (nn < n && cc < cin) {
-    if (mode == VAM_PACK_CONV) {
-      v = src[(((size_t)nn * cin + cc) * kh + ty) * kw + tx];
-    } else if (mode == VAM_PACK_PS2) {
-      int cq = n / 4;
-      int ph = nn / cq, c = nn - ph * cq;
-      v = src[(((size_t)(c * 4 + ph) * cin + cc) * kh + ty) * kw + tx];
-    } else if (mode == VAM_PACK_CONV_DGRAD) {
-      // data gradient of a stride-1 conv = correlation of dY with the taps flipped and the channel roles
-      // swapped: here `cin` = forward Cout (channels of dY), `n` = forward Cin; src is the forward OIHW tensor
-      v = src[(((size_t)cc * n + nn) * kh + (kh - 1 - ty)) * kw + (kw - 1 - tx)];
-    } else if (mode == VAM_PACK_GDN || mode == VAM_PACK_GDN_T) {
-      float g = mode == VAM_PACK_GDN ? src[(size_t)nn * cin + cc] : src[(size_t)cc * n + nn];   // _T: gamma transposed
-      const float bound = 3.814697265625e-06f;       // 2^-18 = sqrt(0 + 2^-36)
-      const float ped = 1.4551915228366852e-11f;     // 2^-36
-      g = fmaxf(g, bound);
-      v = g * g - ped;
-    } else if (mode == VAM_PACK_DECONV5S2) {
-      if (phase >= 0) {
-        int py = phase >> 1, px = phase & 1;
-        int dy = ty - (py ? 0 : 1), dx = tx - (px ? 0 : 1);
-        int ky = py + 2 - 2 * dy, kx = px + 2 - 2 * dx;
-        if (ky >= 0 && ky < 5 && kx >= 0 && kx < 5)
-          v = src[(((size_t)cc * n + nn) * 5 + ky) * 5 + kx];
-      } else {
-        int cout = n / 4;
-        int ph = nn / cout, c = nn - ph * cout;
-        int py = ph >> 1, px = ph & 1;
-        int dy = ty - 1, dx = tx - 1;
-        int ky = py + 2 - 2 * dy, kx = px + 2 - 2 * dx;
-        if (ky >= 0 && ky < 5 && kx >= 0 && kx < 5)
-          v = src[(((size_t)cc * cout + c) * 5 + ky) * 5 + kx];
-      }
-    }
-  }
-  return v;
-}
-
-__global__ void pack_weights_kernel(const float* __restrict__ src, float* __restrict__ dst, int mode,
-                                    int phase, int kh, int kw, int cin, int n, int npad, int bk, int kc,
-                                    long total) {
-  long d = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= total) return;
-  int kk = (int)(d % bk);
-  long r = d / bk;
-  int nn = (int)(r % npad);
-  r /= npad;
-  int c_chunk = (int)(r % kc);
-  int tap = (int)(r / kc);
-  int ty = tap / kw, tx = tap % kw;
-  int cc = c_chunk * bk + kk;
-  dst[d] = pack_value(src, mode, phase, kh, kw, cin, n, nn, cc, ty, tx);
-}
-
-// bf16x3 layout: [tap][32-channel chunk][Npad][12 chunks][8 bf16]; chunk (p*4 + g) holds plane p (hi/mid/lo) of
-// channels 8g..8g+7 of the 32-channel chunk.  The three planes sum to the fp32 weight exactly.
-__device__ __forceinline__ void pack_bf3_element(long d, const float* __restrict__ src, unsigned short* __restrict__ dst, int mode,
-                                                 int phase, int kh, int kw, int cin, int n, int npad, int kc32, int dual) {
-  int kk = (int)(d % 32);
-  long r = d / 32;
-  int nn = (int)(r % npad);
-  r /= npad;
-  int c_chunk = (int)(r % kc32);
-  int tap = (int)(r / kc32);
-  int cc = c_chunk * 32 + kk;
-  if (dual) {                                    // 16 input channels: chunk = tap pair, [tap 2c: 16 ch | tap 2c+1: 16 ch]
-    tap = 2 * tap + (kk >> 4);
-    cc = kk & 15;
-  }
-  int ty = tap / kw, tx = tap % kw;
-  const float v = (tap < kh * kw) ? pack_value(src, mode, phase, kh, kw, cin, n, nn, cc, ty, tx) : 0.f;
-  // exact split by truncation (same as the activations' in the kernel): hi + mid + lo == v
-  const unsigned hb = __float_as_uint(v);
-  const float r1 = v - __uint_as_float(hb & 0xFFFF0000u);
-  const unsigned mb = __float_as_uint(r1);
-  const unsigned lb = __float_as_uint(r1 - __uint_as_float(mb & 0xFFFF0000u));
-  const size_t row = (size_t)(d / 32) * 96;                                  // 96 bf16 = 192 B per (chunk, n) row
-  const int g = kk >> 3, e = kk & 7;
-  dst[row + (0 * 4 + g) * 8 + e] = (unsigned short)(hb >> 16);
-  dst[row + (1 * 4 + g) * 8 + e] = (unsigned short)(mb >> 16);
-  dst[row + (2 * 4 + g) * 8 + e] = (unsigned short)(lb >> 16);
-}
-
-__global__ void pack_weights_bf3_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int mode,
-                                        int phase, int kh, int kw, int cin, int n, int npad, int kc32, long total, int dual) {
-  long d = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= total) return;
-  pack_bf3_element(d, src, dst, mode, phase, kh, kw, cin, n, npad, kc32, dual);
-}
-
-// fp16x2 (MODE 3): per output channel n the power of two 2^s_n that maps max |w[n, :]| into [2^14, 2^15); out[n] = 2^-s_n
-// (1 for an all-zero channel).  One block per channel.
-__global__ void wscale_f16x2_kernel(const float* __restrict__ src, float* __restrict__ out, int mode, int phase, int kh, int kw,
-                                    int cin, int n, int npad) {
-  const int nn = blockIdx.x;
-  float m = 0.f;
-  for (int i = threadIdx.x; i < kh * kw * cin; i += blockDim.x) {
-    const int tap = i / cin, cc = i - tap * cin;
-    m = fmaxf(m, fabsf(pack_value(src, mode, phase, kh, kw, cin, n, nn, cc, tap / kw, tap % kw)));
-  }
-  __shared__ float red[256];
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 128; o; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    m = red[0];
-    const int e = (int)((__float_as_uint(m) >> 23) & 0xFFu) - 127;
-    int sh = (m > 0.f && e > -127 && e < 128) ? 14 - e : 0;
-    sh = sh > 126 ? 126 : (sh < -126 ? -126 : sh);
-    out[nn] = __uint_as_float((unsigned)(127 - sh) << 23);
-  }
-  (void)npad;
-}
-
-// fp16x2 layout: [tap][32-channel chunk][Npad][8 chunks][8 fp16]; chunk (p*4 + g) holds plane p (h / l) of channels
-// 8g..8g+7; w 2^s_n = h + l up to 2^-22 |w|.  (dual: as in the bf16x3 layout)
-__global__ void pack_weights_f16x2_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, const float* __restrict__ wsc,
-                                          int mode, int phase, int kh, int kw, int cin, int n, int npad, int kc32, long total, int dual) {
-  long d = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= total) return;
-  int kk = (int)(d % 32);
-  long r = d / 32;
-  int nn = (int)(r % npad);
-  r /= npad;
-  int c_chunk = (int)(r % kc32);
-  int tap = (int)(r / kc32);
-  int cc = c_chunk * 32 + kk;
-  if (dual) {
-    tap = 2 * tap + (kk >> 4);
-    cc = kk & 15;
-  }
-  int ty = tap / kw, tx = tap % kw;
-  const float v = (tap < kh * kw) ? pack_value(src, mode, phase, kh, kw, cin, n, nn, cc, ty, tx) : 0.f;
-  const float vs = v / wsc[nn];                      // 2^-s_n is a power of two: the division is exact
-  const _Float16 h = (_Float16)vs;
-  const _Float16 l = (_Float16)(vs - (float)h);
-  const size_t row = (size_t)(d / 32) * 64;          // 64 fp16 = 128 B per (chunk, n) row
-  const int g = kk >> 3, e = kk & 7;
-  dst[row + (0 * 4 + g) * 8 + e] = __builtin_bit_cast(unsigned short, h);
-  dst[row + (1 * 4 + g) * 8 + e] = __builtin_bit_cast(unsigned short, l);
-}
-
-// max |x| over an NHWC window, folded into *cell (the float's bits; integer atomicMax).  float4 loads, grid-stride.
-struct AbsmaxArgs { const float* ptr[VAM_MAX_SEG]; int C[VAM_MAX_SEG]; int ld[VAM_MAX_SEG]; int n_seg; long n_pix; int* cell; };
-__global__ __launch_bounds__(256) void absmax_kernel(const AbsmaxArgs a) {
-  float m = 0.f;
-  for (int s = 0; s < a.n_seg; ++s) {
-    const int c4 = a.C[s] >> 2;
-    const long total = a.n_pix * c4;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-      const long pix = i / c4;
-      const int c = (int)(i - pix * c4);
-      const float4 v = *reinterpret_cast<const float4*>(a.ptr[s] + pix * a.ld[s] + 4 * c);
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    }
-  }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0 && m > 0.f && __float_as_int(m) > __hip_atomic_load(a.cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMax(a.cell, __float_as_int(m));
-}
-
-// bf16 storage mode: [tap][32-channel chunk][Npad][32 bf16] = 64 B per row, each weight rounded to nearest-even bf16
-__global__ void pack_weights_bf16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int mode,
-                                         int phase, int kh, int kw, int cin, int n, int npad, int kc32, long total) {
-  long d = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= total) return;
-  int kk = (int)(d % 32);
-  long r = d / 32;
-  int nn = (int)(r % npad);
-  r /= npad;
-  int c_chunk = (int)(r % kc32);
-  int tap = (int)(r / kc32);
-  int ty = tap / kw, tx = tap % kw;
-  const float v = pack_value(src, mode, phase, kh, kw, cin, n, nn, c_chunk * 32 + kk, ty, tx);
-  const __bf16 h = (__bf16)v;
-  dst[d] = __builtin_bit_cast(unsigned short, h);
-}
-
-__device__ __forceinline__ void pack_bias_element(int i, const float* __restrict__ src, float* __restrict__ dst, int mode, int n) {
-  float v;
-  if (mode == VAM_PACK_PS2) {
-    int cq = n / 4;
-    int ph = i / cq, c = i - ph * cq;
-    v = src[c * 4 + ph];
-  } else if (mode == VAM_PACK_DECONV5S2) {
-    int cout = n / 4;
-    v = src[i % cout];
-  } else if (mode == VAM_PACK_GDN) {
-    // beta: NonNegativeParametrizer(minimum=1e-6): bound = sqrt(1e-6 + 2^-36) rounded to fp32
-    const float bound = (float)1.0000072759311445e-03;
-    const float ped = 1.4551915228366852e-11f;
-    float b = fmaxf(src[i], bound);
-    v = b * b - ped;
-  } else {
-    v = src[i];
-  }
-  dst[i] = v;
-}
-
-__global__ void pack_bias_kernel(const float* __restrict__ src, float* __restrict__ dst, int mode, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  pack_bias_element(i, src, dst, mode, n);
-}
-
-// Many small repacks as one launch (training: every trained layer is repacked after every optimiser step — 1,250 launches
-// of ~4.5 us per first_train step when issued one by one).  blockIdx.y = job; a job's blocks stride over its elements.
-struct PackJobD {
-  const float* src;
-  void* dst;
-  long total;
-  int kind, mode, phase, kh, kw, cin, n, npad, kc32, dual;
-};
-struct PackGroupArgs {
-  PackJobD j[VAM_MAX_PACK_GROUP];
-};
-__global__ __launch_bounds__(256) void pack_group_kernel(const PackGroupArgs a) {
-  const PackJobD& j = a.j[blockIdx.y];
-  for (long d = (long)blockIdx.x * 256 + threadIdx.x; d < j.total; d += (long)gridDim.x * 256) {
-    if (j.kind == 0) pack_bf3_element(d, j.src, reinterpret_cast<unsigned short*>(j.dst), j.mode, j.phase, j.kh, j.kw, j.cin, j.n, j.npad, j.kc32, j.dual);
-    else pack_bias_element((int)d, j.src, reinterpret_cast<float*>(j.dst), j.mode, j.n);
-  }
-}
-
+// ---------------------------------------------------------------- launch path: lower -> choose_tile -> dispatch
 static int g_force[3] = {0, 0, 0};   // tuning hook: forced BM / BN / BK (0 = automatic)
 static int g_staged = -1;             // tuning / test hook: 1 = staged epilogue everywhere, 0 = automatic, -1 = VAMPIC_EPILOGUE
 static int g_last[3] = {0, 0, 0};   // tile configuration of the most recent launch (diagnostics)
-
-static inline bool dual_tap(int cin, int taps) { return cin == 16 && taps > 1; }   // split-operand mode: see VAM_CONVI_DUAL
 
 static inline int bk_for(int cin) { return (cin % 32 == 0) ? 32 : 16; }   // kernel K step (packing is always 16-granular)
 
 static int g_mode = -1;              // 0 = fp32 MFMA, 1 = bf16x3 MFMA, 3 = fp16x2 MFMA (opt-in); -1 = not chosen yet (VAMPIC_CONV, default bf16x3)
 
-static int conv_mode() {
+int conv_mode() {
   if (g_mode < 0) {
     const char* e = getenv("VAMPIC_CONV");
     g_mode = (e && (e[0] == 'f' || e[0] == 'F')) ? ((e[1] == '1') ? 3 : 0) : 1;      // "f32" -> 0, "f16x2" -> 3
@@ -1524,135 +1250,18 @@ static int conv_mode() {
   return g_mode;
 }
 
-template <int BM, int BN, int BK, int WGM, int WGN, int MODE, int AIN = 0, int SPEC = 0>
-static int launch_cfg(const GroupArgs& ga, int total_tiles, hipStream_t s) {
-  constexpr size_t pipe = MODE == 2 ? (size_t)2 * (BM + BN) * 16 * sizeof(float)
-                          : MODE ? (size_t)((SPEC || BM + BN <= 128) ? 2 : 1) * (BM + BN) * (MODE == 3 ? 32 : 48) * sizeof(float)
-                                 : (size_t)2 * (BM + BN) * BK * sizeof(float);
-  constexpr int crows = SPEC ? BM : WGM * 32;              // rows of C staged through LDS at a time
-  constexpr size_t ctile = (size_t)crows * (BN + 4) * sizeof(float) + (size_t)crows * 2 * sizeof(int);
-  constexpr size_t smem = pipe > ctile ? pipe : ctile;
-  static_assert(smem <= 160 * 1024, "tile does not fit the CU's LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BM, BN, BK, WGM, WGN, MODE, AIN, SPEC>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-  // grid: 8 XCD groups x the largest per-XCD share (see the kernel's tile mapping)
-  int per_xcd = 0;
-  for (int i = 0; i < ga.nprob; ++i) per_xcd += (ga.tile_start[i + 1] - ga.tile_start[i] + 7) / 8;
-  (void)total_tiles;
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WGM, WGN, MODE, AIN, SPEC>), dim3(8 * per_xcd), dim3(WGM * WGN * 64 * (SPEC ? 2 : 1)), smem, s, ga);
-  return check_launch("conv_igemm_kernel");
-}
+// What the tile chooser and the dispatch need to know about a lowered group beyond its problems.
+struct GroupFacts {
+  int mode;                 // conv_mode() of the launch
+  bool w16, in16, in_p3;    // bf16-packed weights (MODE 2), bf16 inputs, bf16x3-plane inputs: the same for every problem
+  int bk;                   // K step the problems were lowered for (fp32 pipe: the chooser may still halve 32 to 16)
+  double flops, bytes;      // algorithmic work and traffic, for ProfScope
+};
 
-}  // namespace vam
-
-using namespace vam;
-
-extern "C" {
-
-int vam_conv_last_tile(int* bm, int* bn, int* bk) {
-  if (bm) *bm = g_last[0];
-  if (bn) *bn = g_last[1];
-  if (bk) *bk = g_last[2];
-  return VAM_OK;
-}
-
-int vam_conv_force_tile(int bm, int bn, int bk) {
-  g_force[0] = bm; g_force[1] = bn; g_force[2] = bk;
-  return VAM_OK;
-}
-
-int vam_conv_force_epilogue(int staged) {
-  g_staged = staged < 0 ? -1 : (staged ? 1 : 0);
-  return VAM_OK;
-}
-
-int vam_conv_set_mode(int mode) {
-  if (mode != 0 && mode != 1 && mode != 3) {
-    set_error("vam_conv_set_mode: mode %d (0 = fp32 MFMA, 1 = bf16x3 MFMA, 3 = fp16x2 MFMA)", mode);
-    return VAM_EINVAL;
-  }
-  g_mode = mode;
-  return VAM_OK;
-}
-
-int vam_conv_get_mode(void) { return conv_mode(); }
-
-size_t vam_conv_wpack_floats(int kh, int kw, int cin, int n) {
-  int npad = (n + 31) / 32 * 32;
-  if (conv_mode() == 1) return (size_t)kh * kw * ((cin + 31) / 32) * npad * 48;   // 96 bf16 per (n, 32-channel chunk)
-  if (conv_mode() == 3) return (size_t)kh * kw * ((cin + 31) / 32) * npad * 32 + npad;   // 64 fp16 per row, then 2^-s_n per channel
-  int bk = PK;
-  int kc = (cin + bk - 1) / bk;
-  return (size_t)kh * kw * kc * npad * bk;
-}
-
-int vam_pack_conv_weights(const float* src, float* dst, int mode, int phase, int kh, int kw, int cin, int n,
-                          void* stream) {
-  VAM_REQUIRE(src && dst && kh > 0 && kw > 0 && cin > 0 && n > 0, "vam_pack_conv_weights: bad arguments");
-  VAM_REQUIRE(mode >= VAM_PACK_CONV && mode <= VAM_PACK_GDN_T, "vam_pack_conv_weights: bad mode %d", mode);
-  if (mode == VAM_PACK_PS2) VAM_REQUIRE(n % 4 == 0, "PS2 pack needs N %% 4 == 0");
-  if (mode == VAM_PACK_DECONV5S2 && phase < 0) VAM_REQUIRE(n % 4 == 0 && kh == 3 && kw == 3, "merged deconv pack needs 3x3, N=4*Cout");
-  if (mode == VAM_PACK_DECONV5S2 && phase >= 0)
-    VAM_REQUIRE(phase < 4 && kh == ((phase >> 1) ? 2 : 3) && kw == ((phase & 1) ? 2 : 3), "deconv phase %d needs kh/kw = 3|2", phase);
-  if (mode == VAM_PACK_GDN || mode == VAM_PACK_GDN_T) VAM_REQUIRE(kh == 1 && kw == 1 && cin == n, "GDN pack is 1x1 and square");
-  int npad = (n + 31) / 32 * 32;
-  if (conv_mode() == 3) {
-    const int kc32 = (cin + 31) / 32;
-    const int dual = dual_tap(cin, kh * kw) ? 1 : 0;
-    const long total1 = dual ? (long)((kh * kw + 1) / 2) * npad * 32 : (long)kh * kw * kc32 * npad * 32;
-    float* wsc = dst + (size_t)kh * kw * kc32 * npad * 32;
-    hipLaunchKernelGGL(wscale_f16x2_kernel, dim3(npad), dim3(256), 0, (hipStream_t)stream, src, wsc, mode, phase, kh, kw, cin, n, npad);
-    hipLaunchKernelGGL(pack_weights_f16x2_kernel, dim3(cdiv(total1, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                       reinterpret_cast<unsigned short*>(dst), wsc, mode, phase, kh, kw, cin, n, npad, kc32, total1, dual);
-    return check_launch("pack_weights_f16x2_kernel");
-  }
-  if (conv_mode() == 1) {
-    const int kc32 = (cin + 31) / 32;
-    const int dual = dual_tap(cin, kh * kw) ? 1 : 0;       // 16-channel inputs: two taps per 32-channel chunk (kernel: VAM_CONVI_DUAL)
-    const long total1 = dual ? (long)((kh * kw + 1) / 2) * npad * 32 : (long)kh * kw * kc32 * npad * 32;
-    hipLaunchKernelGGL(pack_weights_bf3_kernel, dim3(cdiv(total1, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                       reinterpret_cast<unsigned short*>(dst), mode, phase, kh, kw, cin, n, npad, kc32, total1, dual);
-    return check_launch("pack_weights_bf3_kernel");
-  }
-  int bk = PK;
-  int kc = (cin + bk - 1) / bk;
-  long total = (long)kh * kw * kc * npad * bk;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, mode,
-                     phase, kh, kw, cin, n, npad, bk, kc, total);
-  return check_launch("pack_weights_kernel");
-}
-
-size_t vam_conv_wpack_bf16_bytes(int kh, int kw, int cin, int n) {
-  return (size_t)kh * kw * ((cin + 31) / 32) * ((n + 31) / 32 * 32) * 64;
-}
-
-int vam_pack_conv_weights_bf16(const float* src, void* dst, int mode, int phase, int kh, int kw, int cin, int n, void* stream) {
-  VAM_REQUIRE(src && dst && kh > 0 && kw > 0 && cin > 0 && n > 0, "vam_pack_conv_weights_bf16: bad arguments");
-  VAM_REQUIRE(mode >= VAM_PACK_CONV && mode <= VAM_PACK_GDN_T, "vam_pack_conv_weights_bf16: bad mode %d", mode);
-  if (mode == VAM_PACK_PS2) VAM_REQUIRE(n % 4 == 0, "PS2 pack needs N %% 4 == 0");
-  if (mode == VAM_PACK_DECONV5S2 && phase < 0) VAM_REQUIRE(n % 4 == 0 && kh == 3 && kw == 3, "merged deconv pack needs 3x3, N=4*Cout");
-  if (mode == VAM_PACK_DECONV5S2 && phase >= 0)
-    VAM_REQUIRE(phase < 4 && kh == ((phase >> 1) ? 2 : 3) && kw == ((phase & 1) ? 2 : 3), "deconv phase %d needs kh/kw = 3|2", phase);
-  const int npad = (n + 31) / 32 * 32, kc32 = (cin + 31) / 32;
-  const long total = (long)kh * kw * kc32 * npad * 32;
-  hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src,
-                     reinterpret_cast<unsigned short*>(dst), mode, phase, kh, kw, cin, n, npad, kc32, total);
-  return check_launch("pack_weights_bf16_kernel");
-}
-
-int vam_pack_bias(const float* src, float* dst, int mode, int n, void* stream) {
-  VAM_REQUIRE(src && dst && n > 0, "vam_pack_bias: bad arguments");
-  hipLaunchKernelGGL(pack_bias_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, mode, n);
-  return check_launch("pack_bias_kernel");
-}
-
-int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
+// vam_conv -> ConvP: every rule of the problem contract, then the kernel's view of each problem.  tiles_n, tile_start and
+// the final Kc depend on the tile and are dispatch's.
+static int lower(const vam_conv* probs, int nprob, GroupArgs& ga, GroupFacts& gf) {
   VAM_REQUIRE(probs && nprob >= 1 && nprob <= VAM_MAX_GROUP, "vam_conv_group: 1..%d problems", VAM_MAX_GROUP);
-  GroupArgs ga;
   ga.nprob = nprob;
   {
     static int staged_env = -1;
@@ -1662,10 +1271,9 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
     }
     ga.staged_epilogue = g_staged >= 0 ? g_staged : staged_env;
   }
+  const int mode = conv_mode();
   bool in_p3 = false, w16 = false, in16 = false;
   int bk = 0;
-  long max_p = 0;
-  int max_n = 0;
   double flops = 0, bytes = 0;
   for (int i = 0; i < nprob; ++i) {
     const vam_conv& c = probs[i];
@@ -1686,10 +1294,10 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
     if (c_aux16) VAM_REQUIRE(!(c.flags & (VAM_CONV_OUT_NCHW)) && (!(c.flags & VAM_CONV_PS2) || (c.Cq % 4) == 0), "conv[%d]: bf16 epilogue operands need the vector epilogue", i);
     if (i == 0) in_p3 = p3_in;
     VAM_REQUIRE(p3_in == in_p3, "conv group mixes fp32 and bf16x3-plane inputs");
-    if (conv_mode() == 3 && !c_w16)
+    if (mode == 3 && !c_w16)
       for (int sg = 0; sg < c.n_seg; ++sg)
         VAM_REQUIRE(c.in_amax[sg] != nullptr, "conv[%d]: the fp16x2 mode needs in_amax[%d] (max |x| of that input segment: vam_absmax, or its producer's out_amax)", i, sg);
-    if (p3_in || p3_out) VAM_REQUIRE(conv_mode() == 1, "conv[%d]: bf16x3-plane tensors need the split-operand mode", i);
+    if (p3_in || p3_out) VAM_REQUIRE(mode == 1, "conv[%d]: bf16x3-plane tensors need the split-operand mode", i);
     if (p3_in) VAM_REQUIRE(!(c.flags & VAM_CONV_SQUARE_IN), "conv[%d]: SQUARE_IN needs fp32 input", i);
     if (p3_out) VAM_REQUIRE(!(c.flags & (VAM_CONV_PS2 | VAM_CONV_OUT_NCHW)) && c.N % 8 == 0 && c.ldo * 8 >= c.N, "conv[%d]: bf16x3-plane output needs plain NHWC placement, N %% 8 == 0 and ldo (groups) >= N/8", i);
     for (int s = 0; s < VAM_MAX_SEG; ++s) {
@@ -1701,8 +1309,8 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
           VAM_REQUIRE(c.seg[s].ptr && c.seg[s].C > 0 && c.seg[s].C % 8 == 0 && c.seg[s].ld * 8 >= c.seg[s].C, "conv[%d]: bf16x3 segment %d invalid", i, s);
           VAM_REQUIRE((((uintptr_t)c.seg[s].ptr) % 16) == 0, "conv[%d]: segment %d not 16-byte aligned", i, s);
         } else {
-        VAM_REQUIRE(c.seg[s].ptr && c.seg[s].C > 0 && c.seg[s].ld >= c.seg[s].C, "conv[%d]: segment %d invalid", i, s);
-        VAM_REQUIRE((c.seg[s].ld % 4) == 0 && (((uintptr_t)c.seg[s].ptr) % 16) == 0, "conv[%d]: segment %d not 16-byte aligned", i, s);
+          VAM_REQUIRE(c.seg[s].ptr && c.seg[s].C > 0 && c.seg[s].ld >= c.seg[s].C, "conv[%d]: segment %d invalid", i, s);
+          VAM_REQUIRE((c.seg[s].ld % 4) == 0 && (((uintptr_t)c.seg[s].ptr) % 16) == 0, "conv[%d]: segment %d not 16-byte aligned", i, s);
         }
         cin += c.seg[s].C;
         p.seg_ptr[s] = c.seg[s].ptr;
@@ -1714,9 +1322,10 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
         p.seg_end[s] = 1 << 30;
       }
     }
-    const int mode1 = conv_mode() == 1 || conv_mode() == 3 || c_w16;
+    const int mode1 = mode == 1 || mode == 3 || c_w16;
     int pbk = mode1 ? 32 : bk_for(cin);
     VAM_REQUIRE(cin % 16 == 0, "conv[%d]: Cin %d not a multiple of 16", i, cin);
+    // the kernel addresses every input segment with 32-bit byte offsets inside a 2^31-byte window
     for (int sgi = 0; sgi < c.n_seg; ++sgi)
       VAM_REQUIRE((double)c.B * c.H * c.W * c.seg[sgi].ld * (p3_in ? 48.0 : (c_in16 ? 2.0 : 4.0)) < 2147000000.0, "conv[%d]: input window larger than 2 GiB (32-bit buffer offsets)", i);
     VAM_REQUIRE((double)vam_conv_wpack_floats(c.kh, c.kw, cin, c.N) * 4.0 < 2147000000.0, "conv[%d]: packed weights larger than 2 GiB", i);
@@ -1761,18 +1370,14 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
     // 16-channel multi-tap problems: vam_pack_conv_weights lays the weights out two taps per 32-channel chunk in the
     // split-operand mode (dual_tap), and ONLY the dual-tap indexing reads that layout — so every such problem must be one
     // the dual path takes (one fp32 segment); anything else would read dual-packed weights with plain indexing
-    if ((conv_mode() == 1 || conv_mode() == 3) && !c_w16 && dual_tap(cin, c.kh * c.kw)) {
+    if ((mode == 1 || mode == 3) && !c_w16 && dual_tap(cin, c.kh * c.kw)) {
       VAM_REQUIRE(!p3_in && c.n_seg == 1, "conv[%d]: a 16-channel multi-tap problem takes one fp32 input segment (its weights are "
                   "packed two taps per chunk)", i);
       p.flags |= VAM_CONVI_DUAL;
     }
     {
-      // the kernel addresses every input segment with 32-bit byte offsets inside a 2^31-byte window
-      const double in_pix = (double)c.B * c.H * c.W;
-      for (int s = 0; s < c.n_seg; ++s)
-        VAM_REQUIRE(in_pix * c.seg[s].ld * (p3_in ? 48.0 : c_in16 ? 2.0 : 4.0) < 2147483648.0, "conv[%d]: input segment %d spans 2 GiB or more (split the batch)", i, s);
-      // the direct epilogue does the same for the output and the epilogue operands, with 24-bit pixel arithmetic;
-      // anything larger takes the staged epilogue (64-bit addresses)
+      // the direct epilogue addresses the output and the epilogue operands with 32-bit byte offsets too, and with 24-bit
+      // pixel arithmetic; anything larger takes the staged epilogue (64-bit addresses)
       const double out_pix = (double)c.B * c.Hf * c.Wf;
       auto fits = [&](const void* q, int ld) { return !q || (ld < (1 << 24) && out_pix * ld * 4.0 < 2147483648.0); };
       if (!(out_pix < (double)(1 << 22) && fits(c.out, c.ldo) && fits(c.pre.ptr, c.pre.ld) && fits(c.mul.ptr, c.mul.ld) &&
@@ -1792,47 +1397,54 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
     p.post2 = c.post2.ptr; p.ld_post2 = c.post2.ld;
     for (int sg = 0; sg < VAM_MAX_SEG; ++sg) p.in_amax[sg] = sg < c.n_seg ? c.in_amax[sg] : nullptr;
     p.out_amax = c.out_amax;
-    if (P > max_p) max_p = P;
-    if (c.N > max_n) max_n = c.N;
     flops += 2.0 * (double)P * c.N * cin * c.kh * c.kw;
     bytes += 4.0 * ((double)c.B * c.H * c.W * cin + (double)P * c.N + (double)c.kh * c.kw * cin * c.N);
   }
-  // ---- tile choice: one configuration per launch, by a cost score fitted to a sweep of all
-  // (BM,BN,BK) over the model's layer shapes on MI355X (scratch/tune.py; DESIGN.md "Tile choice"):
-  //   score = padded work / real work  x  block-count penalty (fewer than ~4 blocks per CU leaves
-  //   barriers and load latency exposed)  x  tile-shape factor  x  thin-K factor (1x1 layers are
-  //   load-bound: narrow tiles, more blocks in flight).
+  gf.mode = mode; gf.w16 = w16; gf.in16 = in16; gf.in_p3 = in_p3; gf.bk = bk; gf.flops = flops; gf.bytes = bytes;
+  return VAM_OK;
+}
+
+struct TileHooks {
+  int force[3];     // vam_conv_force_tile: BM / BN / BK, 0 = automatic
+  int spec_env;     // VAMPIC_SPEC: 0 / 1 forces one kind of block everywhere, -1 = unset
+};
+struct TileChoice { int bm, bn, bk, spec; };
+
+// ---- tile choice: one configuration per launch, by a cost score fitted to a sweep of all
+// (BM,BN,BK) over the model's layer shapes on MI355X (scratch/tune.py; DESIGN.md "Tile choice"):
+//   score = padded work / real work  x  block-count penalty (fewer than ~4 blocks per CU leaves
+//   barriers and load latency exposed)  x  tile-shape factor  x  thin-K factor (1x1 layers are
+//   load-bound: narrow tiles, more blocks in flight).
+// A pure function of the lowered problems (P, N, Npad, Cin, kh, kw), the group facts and the hooks.
+static TileChoice choose_tile(const GroupArgs& ga, const GroupFacts& gf, const TileHooks& hk) {
   struct Cand { int bm, bn; double shape; };
   static const Cand cands[14] = {{128, 192, 1.0}, {128, 224, 1.04}, {128, 160, 1.04}, {128, 128, 1.06}, {128, 96, 1.04},
                                  {128, 64, 1.10}, {128, 32, 1.35}, {64, 192, 1.05}, {64, 128, 1.04}, {64, 64, 1.05},
                                  {64, 96, 1.12}, {64, 160, 1.35}, {64, 224, 1.6}, {64, 32, 1.5}};
-  int ktot_max = 0;
-  for (int i = 0; i < nprob; ++i) {
-    int kt = ga.p[i].Cin * ga.p[i].kh * ga.p[i].kw;
-    if (kt > ktot_max) ktot_max = kt;
-  }
   // bf16x3 mode: nine configurations (the wave tile needs 12 operand registers per 32 rows / columns and K step), own fit,
   // plus the wave-specialised 128x224 tile (below)
   static const Cand cands1[10] = {{128, 192, 1.0}, {128, 128, 0.974}, {128, 96, 1.021}, {128, 64, 1.035}, {128, 32, 1.35},
                                   {64, 192, 1.05}, {64, 128, 1.019}, {64, 64, 1.05}, {64, 32, 1.363}, {128, 224, 1.0}};
-  const bool m1 = conv_mode() == 1 || conv_mode() == 3 || w16;
+  const int nprob = ga.nprob;
+  const bool split = gf.mode == 1 || gf.mode == 3;     // split-operand arithmetic (unless the weights are bf16-packed)
+  const bool m1 = split || gf.w16;
   const Cand* cand = m1 ? cands1 : cands;
   const int n_cand = m1 ? 10 : 14;
+  // K extent of the group: the largest taps x channels, and the fewest K chunks of 32 channels any problem runs.  (The
+  // specialisation rule below used to count chunks of the problems' own Kc; on the split-operand path, the only one
+  // that reads it, Kc is cdiv(Cin, 32), so the two counts are one.)
+  int ktot_max = 0, min_chunks = 1 << 30;
+  for (int i = 0; i < nprob; ++i) {
+    const int taps = ga.p[i].kh * ga.p[i].kw;
+    if (ga.p[i].Cin * taps > ktot_max) ktot_max = ga.p[i].Cin * taps;
+    const int nc = taps * ((ga.p[i].Cin + 31) / 32);
+    if (nc < min_chunks) min_chunks = nc;
+  }
   // deep-K launches of the split-operand mode may use the wave-specialised 128x224 tile (four consumer waves, 2x2 block map:
   // the layers with 224 output channels without padding them to 256); it exists as a specialised block only
-  int min_chunks32 = 1 << 30;
-  for (int i = 0; i < nprob; ++i) {
-    const int nc = ga.p[i].kh * ga.p[i].kw * ((ga.p[i].Cin + 31) / 32);
-    if (nc < min_chunks32) min_chunks32 = nc;
-  }
-  static int spec_env0 = -2;
-  if (spec_env0 == -2) {
-    const char* e = getenv("VAMPIC_SPEC");
-    spec_env0 = e ? (e[0] == '1' ? 1 : 0) : -1;
-  }
-  const bool wide224_ok = (conv_mode() == 1 || conv_mode() == 3) && !w16 && spec_env0 != 0 && min_chunks32 >= 16;
+  const bool wide224_ok = split && !gf.w16 && hk.spec_env != 0 && min_chunks >= 16;
   const double b512 = m1 ? 1.018 : 1.04, b256 = m1 ? 1.097 : 1.10, k96 = m1 ? 1.084 : 1.1;
-  int bm = 128, best_bn = 128;
+  int bm = 128, best_bn = 128, bk = gf.bk;
   double best_score = -1.0;
   for (int c = 0; c < n_cand; ++c) {
     if (m1 && cand[c].bn == 224 && !wide224_ok) continue;
@@ -1854,156 +1466,186 @@ int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
     double sc = padded / real * bp * cand[c].shape * kp;
     if (best_score < 0 || sc < best_score) { best_score = sc; bm = cand[c].bm; best_bn = cand[c].bn; }
   }
-  if (g_force[0] == 64 || g_force[0] == 128) bm = g_force[0];
-  if (g_force[1] > 0) best_bn = g_force[1];
+  if (hk.force[0] == 64 || hk.force[0] == 128) bm = hk.force[0];
+  if (hk.force[1] > 0) best_bn = hk.force[1];
   // K step 32 halves the barriers per FLOP; the sweep prefers 16 for the 128x192 tile (LDS for
   // three resident blocks per CU) and for thin-K layers.
   // (BN=224 and the two-wave 64x160 tile would spill at BK=32 with two register stages.)
-  if (bk == 32 && (g_force[2] == 16 || best_bn == 224 || (bm == 64 && best_bn == 160) ||
-                   (g_force[2] != 32 && ((bm == 128 && (best_bn == 192 || best_bn == 96)) || ktot_max <= 256)))) {
+  if (bk == 32 && (hk.force[2] == 16 || best_bn == 224 || (bm == 64 && best_bn == 160) ||
+                   (hk.force[2] != 32 && ((bm == 128 && (best_bn == 192 || best_bn == 96)) || ktot_max <= 256))))
     bk = 16;
-    for (int i = 0; i < nprob; ++i) ga.p[i].Kc = ga.p[i].Kc16;
-  }
-  if (conv_mode() == 1 || conv_mode() == 3 || w16) {
+  if (m1) {
     // bf16x3 path: K step is always 32; configurations whose operand fragments would not fit the register file
     // (seven 32-column groups per wave) fall back to their two-tile neighbours
     bk = 32;
-    for (int i = 0; i < nprob; ++i) ga.p[i].Kc = (ga.p[i].Cin + 31) / 32;
     if (best_bn == 224 && !(bm == 128 && wide224_ok)) best_bn = 128;
     if (best_bn == 160) best_bn = (bm == 128) ? 96 : 64;
     if (bm == 64 && best_bn == 96) best_bn = 64;
   }
-  g_last[0] = bm; g_last[1] = best_bn; g_last[2] = bk;
-  int total = 0;
-  for (int i = 0; i < nprob; ++i) {
-    ga.tile_start[i] = total;
-    ga.p[i].tiles_n = cdiv(ga.p[i].Npad, best_bn);
-    total += cdiv(ga.p[i].P, bm) * ga.p[i].tiles_n;
-  }
-  for (int i = nprob; i <= VAM_MAX_GROUP; ++i) ga.tile_start[i] = total;
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(VAM_FAM_CONV, s, flops, bytes);
-  if (w16) {          // bf16 storage mode (MODE 2): one MFMA per block, double-buffered LDS
-#define VAM_CFG2(BM_, BN_, WGM_, WGN_) \
-    if (bm == BM_ && best_bn == BN_) return in16 ? launch_cfg<BM_, BN_, 32, WGM_, WGN_, 2, 1>(ga, total, s) \
-                                                 : launch_cfg<BM_, BN_, 32, WGM_, WGN_, 2, 0>(ga, total, s);
-    VAM_CFG2(128, 32, 4, 1) VAM_CFG2(128, 64, 2, 2) VAM_CFG2(128, 96, 4, 1) VAM_CFG2(128, 128, 2, 2) VAM_CFG2(128, 192, 2, 2)
-    VAM_CFG2(64, 32, 2, 1) VAM_CFG2(64, 64, 2, 2) VAM_CFG2(64, 128, 2, 2) VAM_CFG2(64, 192, 2, 2)
-#undef VAM_CFG2
-    set_error("vam_conv_group: no bf16 kernel configuration for BM=%d BN=%d", bm, best_bn);
-    return VAM_EINVAL;
-  }
-  if (conv_mode() == 1 || conv_mode() == 3) {
-    const bool f16 = conv_mode() == 3;
+  bool spec = false;
+  if (split && !gf.w16) {
     // Wave-specialised blocks where they measured faster (interleaved A/B on one box, scratch/ab_spec.sh): the small
     // tiles of the slice chain (64x32 / 64x64 / 64x128: +12...+32 %) and the large tiles of deep-K layers (128x128,
     // 128x192: +3...+7 %); short-K layers (1x1, the 16-channel first layer) and the 4x1-wave 128x96 tile lose 15-30 %
     // (a longer prologue, one block per CU) and keep the one-role kernel.  VAMPIC_SPEC=0 / 1 forces one kind everywhere.
-    static int spec_env = -2;
-    if (spec_env == -2) {
-      const char* e = getenv("VAMPIC_SPEC");
-      spec_env = e ? (e[0] == '1' ? 1 : 0) : -1;
-    }
-    int min_chunks = 1 << 30;
-    for (int i = 0; i < nprob; ++i) {
-      const int nc = ga.p[i].kh * ga.p[i].kw * ga.p[i].Kc;
-      if (nc < min_chunks) min_chunks = nc;
-    }
     // (128x128: the one-role block at three blocks per CU — 168 registers, launch bounds — measured 3.5 % faster than the
     // specialised one, which is alone on its CU with 96 KB of LDS: 474 vs 491 us on 8x[320->224])
     const bool spec_tile = (bm == 64 && (best_bn == 32 || best_bn == 64 || best_bn == 128)) || (bm == 128 && best_bn == 192);
-    const bool spec = (bm == 128 && best_bn == 224) || (spec_env >= 0 ? (spec_env == 1) : (spec_tile && min_chunks >= 16));
-#define VAM_CFG1(BM_, BN_, WGM_, WGN_) \
-    if (bm == BM_ && best_bn == BN_) {                                                                      \
-      if (f16) return spec ? launch_cfg<BM_, BN_, 32, WGM_, WGN_, 3, 0, 1>(ga, total, s)                    \
-                           : launch_cfg<BM_, BN_, 32, WGM_, WGN_, 3, 0, 0>(ga, total, s);                   \
-      if (spec) return in_p3 ? launch_cfg<BM_, BN_, 32, WGM_, WGN_, 1, 1, 1>(ga, total, s)                  \
-                             : launch_cfg<BM_, BN_, 32, WGM_, WGN_, 1, 0, 1>(ga, total, s);                 \
-      return in_p3 ? launch_cfg<BM_, BN_, 32, WGM_, WGN_, 1, 1, 0>(ga, total, s)                            \
-                   : launch_cfg<BM_, BN_, 32, WGM_, WGN_, 1, 0, 0>(ga, total, s);                           \
-    }
-    VAM_CFG1(128, 32, 4, 1) VAM_CFG1(128, 64, 2, 2) VAM_CFG1(128, 96, 4, 1) VAM_CFG1(128, 128, 2, 2) VAM_CFG1(128, 192, 2, 2)
-    VAM_CFG1(64, 32, 2, 1) VAM_CFG1(64, 64, 2, 2) VAM_CFG1(64, 128, 2, 2) VAM_CFG1(64, 192, 2, 2)
-#undef VAM_CFG1
-    if (bm == 128 && best_bn == 224 && f16) return launch_cfg<128, 224, 32, 4, 1, 3, 0, 1>(ga, total, s);
-    if (bm == 128 && best_bn == 224)
-      return in_p3 ? launch_cfg<128, 224, 32, 4, 1, 1, 1, 1>(ga, total, s) : launch_cfg<128, 224, 32, 4, 1, 1, 0, 1>(ga, total, s);
-    set_error("vam_conv_group: no bf16x3 kernel configuration for BM=%d BN=%d", bm, best_bn);
-    return VAM_EINVAL;
+    spec = (bm == 128 && best_bn == 224) || (hk.spec_env >= 0 ? (hk.spec_env == 1) : (spec_tile && min_chunks >= 16));
   }
-#define VAM_CFG(BM_, BN_, WGM_, WGN_)                                                        \
-  if (bm == BM_ && best_bn == BN_)                                                           \
-    return bk == 32 ? launch_cfg<BM_, BN_, 32, WGM_, WGN_, 0>(ga, total, s) : launch_cfg<BM_, BN_, 16, WGM_, WGN_, 0>(ga, total, s);
-  VAM_CFG(128, 32, 4, 1) VAM_CFG(128, 64, 2, 2) VAM_CFG(128, 96, 4, 1) VAM_CFG(128, 128, 2, 2)
-  VAM_CFG(128, 160, 4, 1) VAM_CFG(128, 192, 2, 2) VAM_CFG(128, 224, 4, 1)
-  VAM_CFG(64, 32, 2, 1) VAM_CFG(64, 64, 2, 2) VAM_CFG(64, 96, 2, 1) VAM_CFG(64, 128, 2, 2)
-  VAM_CFG(64, 160, 2, 1) VAM_CFG(64, 192, 2, 2) VAM_CFG(64, 224, 2, 1)
-#undef VAM_CFG
-  set_error("vam_conv_group: no kernel configuration for BM=%d BN=%d", bm, best_bn);
+  return {bm, best_bn, bk, spec ? 1 : 0};
+}
+
+static TileHooks tile_hooks() {
+  static int spec_env = -2;
+  if (spec_env == -2) {
+    const char* e = getenv("VAMPIC_SPEC");
+    spec_env = e ? (e[0] == '1' ? 1 : 0) : -1;
+  }
+  return {{g_force[0], g_force[1], g_force[2]}, spec_env};
+}
+
+// Cut every problem into tiles of the choice: K chunks per tap, tiles along N, and where each problem's tiles start.
+static void lay_out_tiles(GroupArgs& ga, const TileChoice& t) {
+  int total = 0;
+  for (int i = 0; i < ga.nprob; ++i) {
+    ga.p[i].Kc = (ga.p[i].Cin + t.bk - 1) / t.bk;
+    ga.tile_start[i] = total;
+    ga.p[i].tiles_n = cdiv(ga.p[i].Npad, t.bn);
+    total += cdiv(ga.p[i].P, t.bm) * ga.p[i].tiles_n;
+  }
+  for (int i = ga.nprob; i <= VAM_MAX_GROUP; ++i) ga.tile_start[i] = total;
+}
+
+// grid: 8 XCD groups x the largest per-XCD share (see the kernel's tile mapping)
+static int grid_blocks(const GroupArgs& ga) {
+  int per_xcd = 0;
+  for (int i = 0; i < ga.nprob; ++i) per_xcd += (ga.tile_start[i + 1] - ga.tile_start[i] + 7) / 8;
+  return 8 * per_xcd;
+}
+
+template <int BM, int BN, int BK, int WGM, int WGN, int MODE, int AIN = 0, int SPEC = 0>
+static int launch_cfg(const GroupArgs& ga, hipStream_t s) {
+  constexpr size_t pipe = MODE == 2 ? (size_t)2 * (BM + BN) * 16 * sizeof(float)
+                          : MODE ? (size_t)((SPEC || BM + BN <= 128) ? 2 : 1) * (BM + BN) * (MODE == 3 ? 32 : 48) * sizeof(float)
+                                 : (size_t)2 * (BM + BN) * BK * sizeof(float);
+  constexpr int crows = SPEC ? BM : WGM * 32;              // rows of C staged through LDS at a time
+  constexpr size_t ctile = (size_t)crows * (BN + 4) * sizeof(float) + (size_t)crows * 2 * sizeof(int);
+  constexpr size_t smem = pipe > ctile ? pipe : ctile;
+  static_assert(smem <= 160 * 1024, "tile does not fit the CU's LDS");
+  static std::atomic<unsigned long long> attr_set{0};
+  if (int rc = set_dynamic_lds((const void*)conv_igemm_kernel<BM, BN, BK, WGM, WGN, MODE, AIN, SPEC>, (int)smem, attr_set)) return rc;
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WGM, WGN, MODE, AIN, SPEC>), dim3(grid_blocks(ga)), dim3(WGM * WGN * 64 * (SPEC ? 2 : 1)), smem, s, ga);
+  return check_launch("conv_igemm_kernel");
+}
+
+// Every tile the kernel is built for, with its wave grid: X(BM, BN, WGM, WGN, SET).  SET 0: all three arithmetic families.
+// SET 1: the fp32 pipe, and the split-operand modes as a wave-specialised block only.  SET 2: the fp32 pipe only.
+#define VAM_CONV_TILES(X)                                                                                      \
+  X(128, 32, 4, 1, 0) X(128, 64, 2, 2, 0) X(128, 96, 4, 1, 0) X(128, 128, 2, 2, 0) X(128, 192, 2, 2, 0)       \
+  X(64, 32, 2, 1, 0) X(64, 64, 2, 2, 0) X(64, 128, 2, 2, 0) X(64, 192, 2, 2, 0)                                \
+  X(128, 224, 4, 1, 1)                                                                                         \
+  X(128, 160, 4, 1, 2) X(64, 96, 2, 1, 2) X(64, 160, 2, 1, 2) X(64, 224, 2, 1, 2)
+
+constexpr int NO_KERNEL = -1;
+
+// The instantiations of one tile: bf16 storage (MODE 2) by input type; the split-operand modes (MODE 1 / 3) by block
+// kind and, for bf16x3, input type; the fp32 pipe (MODE 0) at K step 16 and 32.
+template <int BM, int BN, int WGM, int WGN, int SET>
+static int launch_tile(const TileChoice& t, const GroupFacts& gf, const GroupArgs& ga, hipStream_t s) {
+  if (gf.w16) {
+    if constexpr (SET == 0) return gf.in16 ? launch_cfg<BM, BN, 32, WGM, WGN, 2, 1>(ga, s) : launch_cfg<BM, BN, 32, WGM, WGN, 2, 0>(ga, s);
+  } else if (gf.mode == 1 || gf.mode == 3) {
+    if constexpr (SET <= 1) {
+      if (t.spec) return gf.mode == 3 ? launch_cfg<BM, BN, 32, WGM, WGN, 3, 0, 1>(ga, s)
+                         : gf.in_p3   ? launch_cfg<BM, BN, 32, WGM, WGN, 1, 1, 1>(ga, s)
+                                      : launch_cfg<BM, BN, 32, WGM, WGN, 1, 0, 1>(ga, s);
+    }
+    if constexpr (SET == 0) {
+      return gf.mode == 3 ? launch_cfg<BM, BN, 32, WGM, WGN, 3, 0, 0>(ga, s)
+             : gf.in_p3   ? launch_cfg<BM, BN, 32, WGM, WGN, 1, 1, 0>(ga, s)
+                          : launch_cfg<BM, BN, 32, WGM, WGN, 1, 0, 0>(ga, s);
+    }
+  } else {
+    return t.bk == 32 ? launch_cfg<BM, BN, 32, WGM, WGN, 0>(ga, s) : launch_cfg<BM, BN, 16, WGM, WGN, 0>(ga, s);
+  }
+  return NO_KERNEL;
+}
+
+static int dispatch(const TileChoice& t, const GroupFacts& gf, GroupArgs& ga, hipStream_t s) {
+  lay_out_tiles(ga, t);
+  int rc = NO_KERNEL;
+#define VAM_TILE(BM_, BN_, WGM_, WGN_, SET_) \
+  if (t.bm == BM_ && t.bn == BN_) rc = launch_tile<BM_, BN_, WGM_, WGN_, SET_>(t, gf, ga, s);
+  VAM_CONV_TILES(VAM_TILE)
+#undef VAM_TILE
+  if (rc != NO_KERNEL) return rc;
+  if (gf.w16) set_error("vam_conv_group: no bf16 kernel configuration for BM=%d BN=%d", t.bm, t.bn);
+  else if (gf.mode == 1 || gf.mode == 3) set_error("vam_conv_group: no bf16x3 kernel configuration for BM=%d BN=%d", t.bm, t.bn);
+  else set_error("vam_conv_group: no kernel configuration for BM=%d BN=%d", t.bm, t.bn);
   return VAM_EINVAL;
 }
 
-int vam_pack_group(const vam_pack_job* jobs, int n_jobs, void* stream) {
-  VAM_REQUIRE(jobs && n_jobs >= 1, "vam_pack_group: no jobs");
-  if (conv_mode() != 1) {                      // other arithmetic modes: one by one through the ordinary entry points
-    for (int i = 0; i < n_jobs; ++i) {
-      const vam_pack_job& q = jobs[i];
-      int rc = q.bias ? vam_pack_bias(q.src, (float*)q.dst, q.mode, q.n, stream)
-                      : vam_pack_conv_weights(q.src, (float*)q.dst, q.mode, q.phase, q.kh, q.kw, q.cin, q.n, stream);
-      if (rc != VAM_OK) return rc;
-    }
-    return VAM_OK;
-  }
-  for (int i0 = 0; i0 < n_jobs; i0 += VAM_MAX_PACK_GROUP) {
-    const int cnt = n_jobs - i0 < VAM_MAX_PACK_GROUP ? n_jobs - i0 : VAM_MAX_PACK_GROUP;
-    PackGroupArgs a;
-    long max_total = 0;
-    for (int i = 0; i < cnt; ++i) {
-      const vam_pack_job& q = jobs[i0 + i];
-      PackJobD& j = a.j[i];
-      VAM_REQUIRE(q.src && q.dst && q.n > 0, "vam_pack_group: job %d: bad arguments", i0 + i);
-      j.src = q.src; j.dst = q.dst; j.mode = q.mode; j.phase = q.phase; j.kh = q.kh; j.kw = q.kw; j.cin = q.cin; j.n = q.n;
-      if (q.bias) {
-        j.kind = 1; j.total = q.n; j.npad = j.kc32 = j.dual = 0;
-      } else {
-        VAM_REQUIRE(q.kh > 0 && q.kw > 0 && q.cin > 0 && q.mode >= VAM_PACK_CONV && q.mode <= VAM_PACK_GDN_T, "vam_pack_group: job %d: bad geometry / mode", i0 + i);
-        if (q.mode == VAM_PACK_PS2) VAM_REQUIRE(q.n % 4 == 0, "PS2 pack needs N %% 4 == 0");
-        if (q.mode == VAM_PACK_DECONV5S2 && q.phase < 0) VAM_REQUIRE(q.n % 4 == 0 && q.kh == 3 && q.kw == 3, "merged deconv pack needs 3x3, N=4*Cout");
-        if (q.mode == VAM_PACK_DECONV5S2 && q.phase >= 0)
-          VAM_REQUIRE(q.phase < 4 && q.kh == ((q.phase >> 1) ? 2 : 3) && q.kw == ((q.phase & 1) ? 2 : 3), "deconv phase %d needs kh/kw = 3|2", q.phase);
-        if (q.mode == VAM_PACK_GDN || q.mode == VAM_PACK_GDN_T) VAM_REQUIRE(q.kh == 1 && q.kw == 1 && q.cin == q.n, "GDN pack is 1x1 and square");
-        j.kind = 0;
-        j.npad = (q.n + 31) / 32 * 32;
-        j.kc32 = (q.cin + 31) / 32;
-        j.dual = dual_tap(q.cin, q.kh * q.kw) ? 1 : 0;
-        j.total = j.dual ? (long)((q.kh * q.kw + 1) / 2) * j.npad * 32 : (long)q.kh * q.kw * j.kc32 * j.npad * 32;
-      }
-      if (j.total > max_total) max_total = j.total;
-    }
-    long bx = cdiv(max_total, 256 * 4);          // ~4 elements per thread of the largest job
-    if (bx > 512) bx = 512;
-    if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(pack_group_kernel, dim3((unsigned)bx, (unsigned)cnt), dim3(256), 0, (hipStream_t)stream, a);
-    if (int rc = check_launch("pack_group_kernel")) return rc;
-  }
+}  // namespace vam
+
+using namespace vam;
+
+extern "C" {
+
+int vam_conv_last_tile(int* bm, int* bn, int* bk) {
+  if (bm) *bm = g_last[0];
+  if (bn) *bn = g_last[1];
+  if (bk) *bk = g_last[2];
   return VAM_OK;
 }
 
-int vam_absmax(const vam_seg* segs, int n_seg, long n_pix, int32_t* cell, void* stream) {
-  VAM_REQUIRE(segs && n_seg >= 1 && n_seg <= VAM_MAX_SEG && n_pix > 0 && cell, "vam_absmax: bad arguments");
-  AbsmaxArgs a;
-  double work = 0;
-  for (int s = 0; s < n_seg; ++s) {
-    VAM_REQUIRE(segs[s].ptr && segs[s].C > 0 && segs[s].C % 4 == 0 && segs[s].ld % 4 == 0 && (((uintptr_t)segs[s].ptr) & 15) == 0,
-                "vam_absmax: segment %d needs C, ld multiples of 4 and a 16-byte aligned pointer", s);
-    a.ptr[s] = segs[s].ptr; a.C[s] = segs[s].C; a.ld[s] = segs[s].ld;
-    work += (double)n_pix * segs[s].C / 4;
+int vam_conv_force_tile(int bm, int bn, int bk) {
+  g_force[0] = bm; g_force[1] = bn; g_force[2] = bk;
+  return VAM_OK;
+}
+
+int vam_conv_force_epilogue(int staged) {
+  g_staged = staged < 0 ? -1 : (staged ? 1 : 0);
+  return VAM_OK;
+}
+
+int vam_conv_set_mode(int mode) {
+  if (mode != 0 && mode != 1 && mode != 3) {
+    set_error("vam_conv_set_mode: mode %d (0 = fp32 MFMA, 1 = bf16x3 MFMA, 3 = fp16x2 MFMA)", mode);
+    return VAM_EINVAL;
   }
-  a.n_seg = n_seg; a.n_pix = n_pix; a.cell = cell;
-  long blocks = (long)(work / 256 / 8) + 1;            // ~8 float4 per thread
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("absmax_kernel");
+  g_mode = mode;
+  return VAM_OK;
+}
+
+int vam_conv_get_mode(void) { return conv_mode(); }
+
+int vam_conv_group(const vam_conv* probs, int nprob, void* stream) {
+  GroupArgs ga;
+  GroupFacts gf;
+  if (int rc = lower(probs, nprob, ga, gf)) return rc;
+  const TileChoice t = choose_tile(ga, gf, tile_hooks());
+  g_last[0] = t.bm; g_last[1] = t.bn; g_last[2] = t.bk;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(VAM_FAM_CONV, s, gf.flops, gf.bytes);
+  return dispatch(t, gf, ga, s);
+}
+
+int vam_conv_plan(const vam_conv* probs, int nprob, vam_conv_choice* out) {
+  VAM_REQUIRE(out, "vam_conv_plan: null result");
+  GroupArgs ga;
+  GroupFacts gf;
+  if (int rc = lower(probs, nprob, ga, gf)) return rc;
+  const TileChoice t = choose_tile(ga, gf, tile_hooks());
+  lay_out_tiles(ga, t);
+  *out = vam_conv_choice{};
+  out->bm = t.bm; out->bn = t.bn; out->bk = t.bk; out->spec = t.spec;
+  out->blocks = grid_blocks(ga);
+  for (int i = 0; i < nprob; ++i) {
+    out->dual[i] = (ga.p[i].flags & VAM_CONVI_DUAL) ? 1 : 0;
+    out->staged[i] = (ga.p[i].flags & VAM_CONVI_STAGED) ? 1 : 0;
+  }
+  return VAM_OK;
 }
 
 }  // extern "C"

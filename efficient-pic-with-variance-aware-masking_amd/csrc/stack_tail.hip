@@ -363,18 +363,8 @@ extern "C" int vam_stack_tail_group(const vam_stack_tail* probs, int n, void* st
   const int B = probs[0].B, H = probs[0].H, W = probs[0].W;
   VAM_REQUIRE(B >= 1 && W == WW && H >= TR && H % TR == 0, "vam_stack_tail_group: built for latents 16 columns wide, rows a multiple of 4 (got %d x %d)", H, W);
   VAM_REQUIRE((long)B * H * W < (1L << 24), "vam_stack_tail_group: too many pixels");
-  {
-    // the dynamic-LDS limit is a property of the kernel on ONE device: once per device, whichever thread comes first (a second
-    // thread setting it again is harmless); devices beyond the mask set it on every call
-    static std::atomic<unsigned long long> attr_set{0};
-    int dev = 0;
-    VAM_CHECK_HIP(hipGetDevice(&dev));
-    const unsigned long long bit = (unsigned)dev < 64u ? 1ull << dev : 0ull;
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-      VAM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stack_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS));
-      attr_set.fetch_or(bit, std::memory_order_release);
-    }
-  }
+  static std::atomic<unsigned long long> attr_set{0};
+  if (int rc = set_dynamic_lds(reinterpret_cast<const void*>(stack_tail_kernel), TAIL_LDS, attr_set)) return rc;
   for (int i0 = 0; i0 < n; i0 += VAM_MAX_TAIL_GROUP) {
     const int m = n - i0 < VAM_MAX_TAIL_GROUP ? n - i0 : VAM_MAX_TAIL_GROUP;
     TailArgs a;

@@ -195,6 +195,16 @@ int vam_conv_set_mode(int mode);
 int vam_conv_get_mode(void);
 /* Diagnostics: the (BM, BN, BK) the tile heuristic picked for the most recent vam_conv_group launch. */
 int vam_conv_last_tile(int* bm, int* bn, int* bk);
+/* What vam_conv_group would do with these problems, without launching: the contract checks and the tile heuristic only.
+ * Host arithmetic (no GPU needed): pointers are checked for null and alignment, never dereferenced.  Return codes and
+ * vam_last_error texts are vam_conv_group's.  (A forced tile that no kernel is built for is refused at the launch.) */
+typedef struct vam_conv_choice {
+  int32_t bm, bn, bk, spec;            /* the tile vam_conv_group would launch these problems with   */
+  int32_t blocks;                      /* its grid size (8 x the largest per-XCD share)              */
+  int32_t dual[VAM_MAX_GROUP];         /* per problem: two taps per 32-channel chunk                 */
+  int32_t staged[VAM_MAX_GROUP];       /* per problem: forced onto the LDS-staged epilogue           */
+} vam_conv_choice;
+int vam_conv_plan(const vam_conv* problems, int n_problems, vam_conv_choice* out);
 
 /* ------------------------------------------------------------------ fused residual unit */
 /*

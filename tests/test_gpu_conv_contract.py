@@ -1,6 +1,7 @@
 """``vam_conv_group`` against the float64 statement of its contract (tests/conv_contract.py): every corner of the problem
 struct at the smallest shape where it can still go wrong, every tile shape and both epilogues, what a launch owns and
 what it must leave alone.  This file is what a rewrite of the convolution kernel has to keep."""
+import ctypes
 import functools
 import os
 import subprocess
@@ -25,6 +26,18 @@ def _launch(prob):
     torch.cuda.synchronize()
 
 
+AUTO_TILE = {}      # case -> ((BM, BN, BK) vam_conv_last_tile reported after the automatic-tile launch, vam_conv_plan's for the same problem)
+
+
+def _last_and_planned_tile(prob):
+    lib = L.load()
+    bm, bn, bk = (ctypes.c_int() for _ in range(3))
+    lib.vam_conv_last_tile(ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(bk))
+    ch = L.VamConvChoice()
+    L.check(lib.vam_conv_plan((L.VamConv * 1)(prob), 1, ctypes.byref(ch)), "vam_conv_plan")
+    return (bm.value, bn.value, bk.value), (ch.bm, ch.bn, ch.bk)
+
+
 @functools.lru_cache(maxsize=None)
 def _launches(cid):
     """Every variant of one case, launched once and shared by the tests: (built, reference, [(name, out, stray elements of
@@ -40,6 +53,8 @@ def _launches(cid):
         try:
             prob, obuf, pbuf = built.problem()
             _launch(prob)
+            if name == "auto":
+                AUTO_TILE[cid] = _last_and_planned_tile(prob)
         finally:
             lib.vam_conv_force_tile(0, 0, 0)
             lib.vam_conv_force_epilogue(-1)
@@ -53,6 +68,7 @@ def _launches(cid):
 def test_contract_against_float64(cid):
     """out = post2 + post + mul * act(conv(cat(seg...)) + bias + pre) against float64, elementwise.
 
+    * the tile of the automatic launch (``vam_conv_last_tile``) is the one ``vam_conv_plan`` names for the same problem;
     * every tile shape and both epilogues give the same bits, ``out`` and ``preact`` alike;
     * z (ACT_NONE cases without mul / post / post2, and the preact output) within (K + 4) 2^-24 abs_sum, the worst case of
       an fp32 accumulation of exact products in any order: a correct kernel cannot fail it, a wrong tap, segment, pad,
@@ -70,6 +86,8 @@ def test_contract_against_float64(cid):
     from conftest import record_measurement
     case = CC.CASES[cid]
     built, ref, res = _launches(cid)
+    launched, planned = AUTO_TILE[cid]
+    assert planned == launched, f"{cid}: vam_conv_plan says {planned}, the automatic-tile launch took {launched}"
     name0, out0, _, pre0, _ = res[0]
     for name, out, _, pre, _ in res[1:]:
         assert torch.equal(out, out0), f"{cid}: {name} differs from {name0} in {(out != out0).sum().item()} elements of out"
