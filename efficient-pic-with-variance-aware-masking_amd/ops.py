@@ -480,17 +480,48 @@ def win_attention(qkv: View, out: View, table: torch.Tensor, C_: int, heads: int
                                        ws, shift, stream_ptr()), "vam_win_attention")
 
 
+def _segments(sigma: View, n_slice: int, slice_C: Optional[int] = None):
+    """(the eight leading arguments of every variance-mask entry point, slice_C, H * W): ``sigma``'s window as ``n_slice``
+    consecutive slices of ``slice_C`` channels per image, one segment per (image, slice)."""
+    slice_C = slice_C or sigma.C // n_slice
+    assert slice_C * n_slice == sigma.C
+    hw = sigma.H * sigma.W
+    return (sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C), slice_C, hw
+
+
+def _thr_ptr(thr: Optional[torch.Tensor], rows: int, sigma: View, n_slice: int, any_dtype: bool = False):
+    """The pointer of ``thr`` (optional): ``rows`` levels of one fp32 threshold per segment."""
+    assert thr is None or ((any_dtype or thr.dtype == torch.float32) and thr.numel() >= rows * sigma.B * n_slice)
+    return thr.data_ptr() if thr is not None else None
+
+
+def _assert_table(table_dev: torch.Tensor, sigma: View):
+    """``table_dev``: one L.VamLayerParams record per image of ``sigma``, as bytes on its device."""
+    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
+        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
+
+
+def _quality_table(params: str, prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int):
+    """(host bytes of one L.VamLayerParams record per image, the longest list's length) from the library's host
+    arithmetic ``params`` (vam_variance_layer_params / vam_variance_mask_params)."""
+    lists = [[float(p_) for p_ in row] for row in prs_per_image]
+    B = len(lists)
+    width = max([len(r) for r in lists] + [1])
+    flat = (C.c_double * (width * max(B, 1)))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
+    nl = (C.c_int * max(B, 1))(*[len(r) for r in lists])
+    table = np.zeros(B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
+    L.check(getattr(L.load(), params)(flat, nl, B, width, n_pix, C_, table.ctypes.data), params)
+    return table, width
+
+
 def variance_mask(sigma: View, pr: float, mask: View, n_slice: int = 1, slice_C: Optional[int] = None,
                   thr: Optional[torch.Tensor] = None):
     """sigma/mask windows hold n_slice consecutive slices of slice_C channels each; one
     quantile per (batch item, slice)."""
-    slice_C = slice_C or sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C == mask.C
-    hw = sigma.H * sigma.W
-    L.check(L.load().vam_variance_mask(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, float(pr),
-                                       mask.ptr, mask.ld, hw * mask.ld, slice_C,
+    seg, slice_C, hw = _segments(sigma, n_slice, slice_C)
+    assert sigma.C == mask.C
+    L.check(L.load().vam_variance_mask(*seg, float(pr), mask.ptr, mask.ld, hw * mask.ld, slice_C,
                                        thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_mask")
-
 
 
 def variance_mask_levels(sigma: View, prs: Sequence[float], mask: View, n_slice: int = 1, level_stride: Optional[int] = None,
@@ -498,19 +529,17 @@ def variance_mask_levels(sigma: View, prs: Sequence[float], mask: View, n_slice:
     """The masks of several qualities in one launch: level l's mask is ``mask`` shifted by l * ``level_stride`` floats
     (default: the next ``sigma.B`` images, i.e. ``mask`` holds [L * B, H, W, ld]); ``thr`` [L, B * n_slice].  Bit-identical
     to one :func:`variance_mask` per level."""
-    slice_C = sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
+    seg, slice_C, hw = _segments(sigma, n_slice)
+    assert sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
     prs = [float(p_) for p_ in prs]
     nl = len(prs)
-    hw = sigma.H * sigma.W
     if level_stride is None:
         assert mask.B == nl * sigma.B, (mask.B, nl, sigma.B)
         level_stride = sigma.B * hw * mask.ld
-    assert thr is None or thr.numel() >= nl * sigma.B * n_slice
     arr = (C.c_double * max(nl, 1))(*prs)
-    L.check(L.load().vam_variance_mask_levels(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, arr, nl,
-                                              mask.ptr, mask.ld, hw * mask.ld, slice_C, level_stride,
-                                              thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_mask_levels")
+    L.check(L.load().vam_variance_mask_levels(*seg, arr, nl, mask.ptr, mask.ld, hw * mask.ld, slice_C, level_stride,
+                                              _thr_ptr(thr, nl, sigma, n_slice, any_dtype=True), stream_ptr()),
+            "vam_variance_mask_levels")
 
 
 def variance_layers(sigma: View, prs: Sequence[float], layer: torch.Tensor, n_slice: int = 1,
@@ -518,17 +547,13 @@ def variance_layers(sigma: View, prs: Sequence[float], layer: torch.Tensor, n_sl
     """Container layer of every element for the non-decreasing quality list ``prs`` (up to L.VAM_MAX_LAYER_LEVELS, one
     launch): ``layer`` uint8 [B, H, W, sigma.C] gets the first k with ``variance_mask(sigma, prs[k])`` == 1 (L.LAYER_NONE if
     none); ``thr`` [L, B * n_slice] the thresholds as :func:`variance_mask_levels` writes them."""
-    slice_C = sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C
+    seg, slice_C, hw = _segments(sigma, n_slice)
     assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
     prs = [float(p_) for p_ in prs]
     nl = len(prs)
-    hw = sigma.H * sigma.W
-    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= nl * sigma.B * n_slice)
     arr = (C.c_double * max(nl, 1))(*prs)
-    L.check(L.load().vam_variance_layers(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C, arr, nl,
-                                         layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
-                                         thr.data_ptr() if thr is not None else None, stream_ptr()), "vam_variance_layers")
+    L.check(L.load().vam_variance_layers(*seg, arr, nl, layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
+                                         _thr_ptr(thr, nl, sigma, n_slice), stream_ptr()), "vam_variance_layers")
 
 
 def variance_layers_per_image(sigma: View, prs: Sequence[Sequence[float]], layer: torch.Tensor, n_slice: int = 1,
@@ -538,17 +563,10 @@ def variance_layers_per_image(sigma: View, prs: Sequence[Sequence[float]], layer
     byte for byte; ``thr`` [max length, B * n_slice] gets level k of image b at [k, b * n_slice + j] for k < len(prs[b]).
     The per-image ranks and weights are host arithmetic (vam_variance_layer_params); their table is copied to the device
     here, so this call cannot be captured into a graph."""
-    slice_C = sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C and len(prs) == sigma.B
+    seg, slice_C, hw = _segments(sigma, n_slice)
+    assert len(prs) == sigma.B
     assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
-    lists = [[float(p_) for p_ in row] for row in prs]
-    width = max([len(r) for r in lists] + [1])
-    hw = sigma.H * sigma.W
-    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= width * sigma.B * n_slice)
-    flat = (C.c_double * (width * sigma.B))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
-    nl = (C.c_int * sigma.B)(*[len(r) for r in lists])
-    table = np.zeros(sigma.B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
-    L.check(L.load().vam_variance_layer_params(flat, nl, sigma.B, width, hw, slice_C, table.ctypes.data), "vam_variance_layer_params")
+    table, width = _quality_table("vam_variance_layer_params", prs, hw, slice_C)
     variance_layers_table(sigma, torch.from_numpy(table).to(sigma.buf.device), layer, n_slice=n_slice, thr=thr, thr_levels=width)
     # the device copy of the table returns to the allocator of this same stream
 
@@ -557,14 +575,7 @@ def mask_table(prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int) ->
     """The host bytes (uint8, one L.VamLayerParams record per image) of the table :func:`variance_masks_per_image` reads:
     image b's qualities ``prs_per_image[b]`` (1..L.VAM_MAX_MASK_LEVELS, any order, repeats allowed) for segments of
     ``n_pix`` pixels x ``C_`` channels.  Host arithmetic only (vam_variance_mask_params)."""
-    lists = [[float(p_) for p_ in row] for row in prs_per_image]
-    B = len(lists)
-    width = max([len(r) for r in lists] + [1])
-    flat = (C.c_double * (width * max(B, 1)))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
-    nl = (C.c_int * max(B, 1))(*[len(r) for r in lists])
-    table = np.zeros(B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
-    L.check(L.load().vam_variance_mask_params(flat, nl, B, width, n_pix, C_, table.ctypes.data), "vam_variance_mask_params")
-    return table
+    return _quality_table("vam_variance_mask_params", prs_per_image, n_pix, C_)[0]
 
 
 def variance_masks_per_image(sigma: View, table_dev: torch.Tensor, mask: View, n_slice: int = 1,
@@ -575,9 +586,8 @@ def variance_masks_per_image(sigma: View, table_dev: torch.Tensor, mask: View, n
     Level l's mask is ``mask`` shifted by l * ``level_stride`` floats (default: ``mask`` holds [L * B, H, W, ld] and the
     table may hold up to L = mask.B // sigma.B levels per image; with an explicit stride ``max_levels`` says how many
     the buffers hold); ``thr`` [L, B * n_slice].  Bit-identical per (image, level) to :func:`variance_mask` on that image."""
-    slice_C = sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
-    hw = sigma.H * sigma.W
+    seg, slice_C, hw = _segments(sigma, n_slice)
+    assert sigma.C == mask.C and sigma.H == mask.H and sigma.W == mask.W
     if level_stride is None:
         assert mask.B % sigma.B == 0 and mask.B >= sigma.B, (mask.B, sigma.B)
         max_levels = mask.B // sigma.B if max_levels is None else max_levels
@@ -586,12 +596,9 @@ def variance_masks_per_image(sigma: View, table_dev: torch.Tensor, mask: View, n
     assert max_levels is not None and 1 <= max_levels <= L.VAM_MAX_MASK_LEVELS, max_levels
     # the last element the kernel may write lies inside the mask's buffer
     assert level_stride >= 0 and mask.c0 + (max_levels - 1) * level_stride + (sigma.B * hw - 1) * mask.ld + mask.C <= mask.buf.numel()
-    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
-        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
-    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= max_levels * sigma.B * n_slice)
-    L.check(L.load().vam_variance_masks_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
-                                                  table_dev.data_ptr(), max_levels, mask.ptr, mask.ld, hw * mask.ld, slice_C,
-                                                  level_stride, thr.data_ptr() if thr is not None else None, stream_ptr()),
+    _assert_table(table_dev, sigma)
+    L.check(L.load().vam_variance_masks_per_image(*seg, table_dev.data_ptr(), max_levels, mask.ptr, mask.ld, hw * mask.ld, slice_C,
+                                                  level_stride, _thr_ptr(thr, max_levels, sigma, n_slice), stream_ptr()),
             "vam_variance_masks_per_image")
 
 
@@ -599,14 +606,7 @@ def layer_table(prs_per_image: Sequence[Sequence[float]], n_pix: int, C_: int) -
     """The host bytes (uint8, one L.VamLayerParams record per image) of the table :func:`variance_mask_map` (and
     vam_variance_layers_per_image) reads: image b's non-decreasing qualities ``prs_per_image[b]`` (1..L.VAM_MAX_LAYER_LEVELS)
     for segments of ``n_pix`` pixels x ``C_`` channels.  Host arithmetic only (vam_variance_layer_params)."""
-    lists = [[float(p_) for p_ in row] for row in prs_per_image]
-    B = len(lists)
-    width = max([len(r) for r in lists] + [1])
-    flat = (C.c_double * (width * max(B, 1)))(*[v for r in lists for v in r + [0.0] * (width - len(r))])
-    nl = (C.c_int * max(B, 1))(*[len(r) for r in lists])
-    table = np.zeros(B * C.sizeof(L.VamLayerParams), dtype=np.uint8)
-    L.check(L.load().vam_variance_layer_params(flat, nl, B, width, n_pix, C_, table.ctypes.data), "vam_variance_layer_params")
-    return table
+    return _quality_table("vam_variance_layer_params", prs_per_image, n_pix, C_)[0]
 
 
 def variance_mask_map(sigma: View, table_dev: torch.Tensor, level_map: torch.Tensor, mask: View, n_slice: int = 1,
@@ -617,17 +617,13 @@ def variance_mask_map(sigma: View, table_dev: torch.Tensor, level_map: torch.Ten
     :func:`variance_mask` on that image alone at that quality; an index beyond the image's list writes 0.  ``thr``
     [L.VAM_MAX_LAYER_LEVELS, B * n_slice]: level k of image b at [k, b * n_slice + j] for k < the image's count.  Table and
     map are device buffers, so the call can be captured and the captured graph serves every map."""
-    slice_C = sigma.C // n_slice
-    assert slice_C * n_slice == sigma.C == mask.C and (sigma.B, sigma.H, sigma.W) == (mask.B, mask.H, mask.W)
-    hw = sigma.H * sigma.W
-    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
-        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
+    seg, slice_C, hw = _segments(sigma, n_slice)
+    assert sigma.C == mask.C and (sigma.B, sigma.H, sigma.W) == (mask.B, mask.H, mask.W)
+    _assert_table(table_dev, sigma)
     assert level_map.dtype == torch.uint8 and level_map.is_contiguous() and level_map.device == sigma.buf.device and \
         level_map.numel() == sigma.B * hw, (level_map.dtype, tuple(level_map.shape), sigma.B, hw)
-    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= L.VAM_MAX_LAYER_LEVELS * sigma.B * n_slice)
-    L.check(L.load().vam_variance_mask_map(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
-                                           table_dev.data_ptr(), level_map.data_ptr(), hw, mask.ptr, mask.ld, hw * mask.ld,
-                                           slice_C, thr.data_ptr() if thr is not None else None, stream_ptr()),
+    L.check(L.load().vam_variance_mask_map(*seg, table_dev.data_ptr(), level_map.data_ptr(), hw, mask.ptr, mask.ld, hw * mask.ld,
+                                           slice_C, _thr_ptr(thr, L.VAM_MAX_LAYER_LEVELS, sigma, n_slice), stream_ptr()),
             "vam_variance_mask_map")
 
 
@@ -661,16 +657,12 @@ def variance_layers_table(sigma: View, table_dev: torch.Tensor, layer: torch.Ten
     """:func:`variance_layers_per_image` with image b's list read from record b of ``table_dev`` (the bytes of
     :func:`layer_table` on the device): no host arithmetic and no copy, so the call can be captured and the captured
     launch serves every table content.  ``thr`` holds ``thr_levels`` rows, at least the longest list of the table."""
-    slice_C = sigma.C // n_slice
-    hw = sigma.H * sigma.W
-    assert slice_C * n_slice == sigma.C
+    seg, slice_C, hw = _segments(sigma, n_slice)
     assert layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (sigma.B, sigma.H, sigma.W, sigma.C)
-    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.device == sigma.buf.device and \
-        table_dev.numel() >= sigma.B * C.sizeof(L.VamLayerParams)
-    assert thr is None or (thr.dtype == torch.float32 and thr.numel() >= thr_levels * sigma.B * n_slice)
-    L.check(L.load().vam_variance_layers_per_image(sigma.ptr, sigma.ld, hw * sigma.ld, slice_C, sigma.B, n_slice, hw, slice_C,
-                                                   table_dev.data_ptr(), layer.data_ptr(), sigma.C, hw * sigma.C, slice_C,
-                                                   thr.data_ptr() if thr is not None else None, stream_ptr()),
+    _assert_table(table_dev, sigma)
+    L.check(L.load().vam_variance_layers_per_image(*seg, table_dev.data_ptr(), layer.data_ptr(), sigma.C,
+                                                   hw * sigma.C, slice_C,
+                                                   _thr_ptr(thr, thr_levels, sigma, n_slice), stream_ptr()),
             "vam_variance_layers_per_image")
 
 
