@@ -4,10 +4,10 @@
 // -> LatentRateReduction (conv3x3 / LeakyReLU / 1x1 skips, reference layers/rem.py:37-141).
 //   * data gradients of a convolution reuse conv_igemm_kernel with weights repacked by
 //     vam_pack_conv_weights(VAM_PACK_CONV_DGRAD) (channels swapped, taps flipped);
-//   * weight gradients: wgrad_kernel below (GEMM over pixels on the fp32 matrix cores);
-//   * element-wise pieces: LeakyReLU backward, products, and the likelihood's forward (with
-//     additive uniform noise, entropy_models.py:132-138,620-652) and backward (incl. compressai's
-//     LowerBound gradient rule).
+//   * weight gradients: wgrad_kernel below (GEMM over pixels on the fp32 matrix cores), and colsum for the biases;
+//   * element-wise pieces: LeakyReLU backward and products (csrc/elementwise.hip), the likelihood's forward (with
+//     additive uniform noise, entropy_models.py:132-138,620-652) and backward (incl. compressai's LowerBound gradient
+//     rule) in csrc/entropy.hip.
 // These layers are 32-96 channels on a 16x16 latent grid: 0.3 % of the step's FLOPs, so the
 // kernels are written for clarity and determinism (fixed reduction order, no float atomics).
 #include "common.h"
@@ -299,203 +299,12 @@ __global__ void colsum_reduce_kernel(const float* __restrict__ partial, int S, i
   out[n] = v;
 }
 
-__global__ void leaky_bwd_kernel(const float* __restrict__ act, int ld_a, const float* __restrict__ dy, int ld_dy,
-                                 float* __restrict__ dx, int ld_dx, long n_vec, int C4) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (long)gridDim.x * blockDim.x) {
-    long p = i / C4;
-    int c = (int)(i - p * C4) * 4;
-    float4 a = *reinterpret_cast<const float4*>(act + p * ld_a + c);
-    float4 g = *reinterpret_cast<const float4*>(dy + p * ld_dy + c);
-    *reinterpret_cast<float4*>(dx + p * ld_dx + c) =
-        make_float4(g.x * (a.x > 0.f ? 1.f : 0.01f), g.y * (a.y > 0.f ? 1.f : 0.01f), g.z * (a.z > 0.f ? 1.f : 0.01f),
-                    g.w * (a.w > 0.f ? 1.f : 0.01f));
-  }
-}
-
-__global__ void mul_kernel(const float* __restrict__ a, int ld_a, const float* __restrict__ b, int ld_b,
-                           float* __restrict__ out, int ld_out, long n_vec, int C4) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (long)gridDim.x * blockDim.x) {
-    long p = i / C4;
-    int c = (int)(i - p * C4) * 4;
-    float4 x = *reinterpret_cast<const float4*>(a + p * ld_a + c);
-    float4 y = *reinterpret_cast<const float4*>(b + p * ld_b + c);
-    *reinterpret_cast<float4*>(out + p * ld_out + c) = make_float4(x.x * y.x, x.y * y.y, x.z * y.z, x.w * y.w);
-  }
-}
-
-// ---- training-mode Gaussian likelihood (additive-noise quantisation proxy)
-//   v   = ((y - y2) - mu) * m + noise          (progressive: pic.py:437-442 / rem_pic.py:387-390; m, y2 optional)
-//   s   = max(sigma * m, 0.11)                  LowerBound
-//   lik = max(Phi((.5-|v|)/s) - Phi((-.5-|v|)/s), 1e-9)
-struct LikArgs {
-  const float *y, *y2, *mu, *sigma, *mask, *noise, *glik;
-  float *lik, *dmu, *dsigma;
-  int ld_y, ld_y2, ld_mu, ld_sigma, ld_mask, ld_noise, ld_glik, ld_lik, ld_dmu, ld_dsigma, C4;
-  long n_vec;
-};
-
-__device__ __forceinline__ float phi_cdf(float t) { return 0.5f * erfcf(-0.70710678118654752440f * t); }
-__device__ __forceinline__ float phi_pdf(float t) { return 0.3989422804014327f * expf(-0.5f * t * t); }
-
-// one element of the noisy likelihood: d = (y - y2) - mu, m = mask (1 without one), n = noise
-__device__ __forceinline__ float lik_train_fwd(float d, float sg, float m, float n, bool masked) {
-  const float v = masked ? d * m + n : d + n;
-  const float raw_s = masked ? sg * m : sg;
-  const float s = fmaxf(raw_s, 0.11f);
-  const float av = fabsf(v);
-  const float u = (0.5f - av) / s, l = (-0.5f - av) / s;
-  const float lik_raw = phi_cdf(u) - phi_cdf(l);
-  return fmaxf(lik_raw, 1e-9f);
-}
-
-// its backward: (dmu, dsigma) from the incoming gradient g of the bounded likelihood
-__device__ __forceinline__ void lik_train_bwd(float d, float sg, float m, float n, float g, bool masked, float& dmu, float& dsg) {
-  const float v = masked ? d * m + n : d + n;
-  const float raw_s = masked ? sg * m : sg;
-  const float s = fmaxf(raw_s, 0.11f);
-  const float av = fabsf(v);
-  const float u = (0.5f - av) / s, l = (-0.5f - av) / s;
-  const float lik_raw = phi_cdf(u) - phi_cdf(l);
-  // LowerBound backward: pass where x >= bound or the incoming gradient is negative
-  if (!(lik_raw >= 1e-9f || g < 0.f)) g = 0.f;
-  const float pu = phi_pdf(u), pl = phi_pdf(l);
-  const float dlik_dv = (av == 0.f ? 0.f : (v > 0.f ? 1.f : -1.f)) * (pl - pu) / s;      // d|v|/dv * dlik/d|v|
-  float gs = g * (pl * l - pu * u) / s;                                                 // dlik/ds = (-pu*u + pl*l)/s
-  if (!(raw_s >= 0.11f || gs < 0.f)) gs = 0.f;                                          // LowerBound(0.11) rule
-  dmu = -g * dlik_dv * m;              // d/dmu : v = (.. - mu) * m
-  dsg = gs * m;                        // d/dsigma: s = sigma * m
-}
-
-template <bool BWD>
-__global__ void gauss_train_kernel(const LikArgs a) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_vec; i += (long)gridDim.x * blockDim.x) {
-    long p = i / a.C4;
-    int c = (int)(i - p * a.C4) * 4;
-    float4 y4 = *reinterpret_cast<const float4*>(a.y + p * a.ld_y + c);
-    if (a.y2) {
-      float4 t = *reinterpret_cast<const float4*>(a.y2 + p * a.ld_y2 + c);
-      y4.x -= t.x; y4.y -= t.y; y4.z -= t.z; y4.w -= t.w;
-    }
-    const float4 mu4 = *reinterpret_cast<const float4*>(a.mu + p * a.ld_mu + c);
-    const float4 sg4 = *reinterpret_cast<const float4*>(a.sigma + p * a.ld_sigma + c);
-    const float4 nz4 = *reinterpret_cast<const float4*>(a.noise + p * a.ld_noise + c);
-    float4 m4 = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (a.mask) m4 = *reinterpret_cast<const float4*>(a.mask + p * a.ld_mask + c);
-    float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (BWD) g4 = *reinterpret_cast<const float4*>(a.glik + p * a.ld_glik + c);
-    const float yv[4] = {y4.x, y4.y, y4.z, y4.w}, mv[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, sv[4] = {sg4.x, sg4.y, sg4.z, sg4.w};
-    const float nv[4] = {nz4.x, nz4.y, nz4.z, nz4.w}, kv[4] = {m4.x, m4.y, m4.z, m4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
-    float o0[4], o1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float d = yv[k] - mv[k];
-      if (!BWD) o0[k] = lik_train_fwd(d, sv[k], kv[k], nv[k], a.mask != nullptr);
-      else lik_train_bwd(d, sv[k], kv[k], nv[k], gv[k], a.mask != nullptr, o0[k], o1[k]);
-    }
-    if (!BWD) {
-      *reinterpret_cast<float4*>(a.lik + p * a.ld_lik + c) = make_float4(o0[0], o0[1], o0[2], o0[3]);
-    } else {
-      *reinterpret_cast<float4*>(a.dmu + p * a.ld_dmu + c) = make_float4(o0[0], o0[1], o0[2], o0[3]);
-      *reinterpret_cast<float4*>(a.dsigma + p * a.ld_dsigma + c) = make_float4(o1[0], o1[1], o1[2], o1[3]);
-    }
-  }
-}
-
-// ---- the progressive tail of several quality levels over one shared (y, y2, mu, sigma) window (vam_gauss_levels_*).
-// Level l's arrays sit at base + l * <ls> floats.  Per element: the shared operands are read once, each level's mask /
-// noise / gradient once; the arithmetic is that of gauss_tail_kernel (yhat), gauss_train_kernel and the EW_MASK_SPLIT /
-// EW_AXPY launches, in the order the unfused sequence runs them (-ffp-contract=off: no contraction either way).
-struct LevelsArgs {
-  const float *y, *y2, *mu, *sigma, *mask, *noise, *glik, *drq;
-  float *rq, *lik, *gmu, *dsigma, *dyt, *dys;
-  int ld_y, ld_y2, ld_mu, ld_sigma, ld_mask, ld_noise, ld_glik, ld_drq, ld_rq, ld_lik, ld_gmu, ld_dsigma, ld_dyt, ld_dys, C4;
-  long ls_mask, ls_noise, ls_glik, ls_drq, ls_rq, ls_lik;
-  int n_levels;
-  long n_vec;
-};
-
-__device__ __forceinline__ float4 ld4(const float* base, long p, int ld, int c) {
-  return *reinterpret_cast<const float4*>(base + p * ld + c);
-}
-__device__ __forceinline__ void st4(float* base, long p, int ld, int c, const float* v) {
-  *reinterpret_cast<float4*>(base + p * ld + c) = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-template <bool BWD>
-__global__ void gauss_levels_kernel(const LevelsArgs a) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_vec; i += (long)gridDim.x * blockDim.x) {
-    const long p = i / a.C4;
-    const int c = (int)(i - p * a.C4) * 4;
-    float4 y4 = ld4(a.y, p, a.ld_y, c);
-    if (a.y2) {
-      const float4 t = ld4(a.y2, p, a.ld_y2, c);
-      y4.x -= t.x; y4.y -= t.y; y4.z -= t.z; y4.w -= t.w;
-    }
-    const float4 mu4 = ld4(a.mu, p, a.ld_mu, c), sg4 = ld4(a.sigma, p, a.ld_sigma, c);
-    const float yv[4] = {y4.x, y4.y, y4.z, y4.w}, mv[4] = {mu4.x, mu4.y, mu4.z, mu4.w}, sv[4] = {sg4.x, sg4.y, sg4.z, sg4.w};
-    float dv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dv[k] = yv[k] - mv[k];
-    float gacc[4] = {0.f, 0.f, 0.f, 0.f}, sacc[4] = {0.f, 0.f, 0.f, 0.f}, dyt[4], dys[4];
-    if (BWD) {
-      const float4 t = ld4(a.dyt, p, a.ld_dyt, c);
-      dyt[0] = t.x; dyt[1] = t.y; dyt[2] = t.z; dyt[3] = t.w;
-      if (a.dys) {
-        const float4 u = ld4(a.dys, p, a.ld_dys, c);
-        dys[0] = u.x; dys[1] = u.y; dys[2] = u.z; dys[3] = u.w;
-      }
-    }
-    for (int lv = 0; lv < a.n_levels; ++lv) {
-      const float4 m4 = ld4(a.mask + lv * a.ls_mask, p, a.ld_mask, c), n4 = ld4(a.noise + lv * a.ls_noise, p, a.ld_noise, c);
-      const float kv[4] = {m4.x, m4.y, m4.z, m4.w}, nv[4] = {n4.x, n4.y, n4.z, n4.w};
-      if (!BWD) {
-        float rq[4], lk[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          rq[k] = rintf(dv[k]) * kv[k] + mv[k];                               // gauss_tail_kernel: yhat = round(r-mu)*m + mu
-          lk[k] = lik_train_fwd(dv[k], sv[k], kv[k], nv[k], true);
-        }
-        st4(a.rq + lv * a.ls_rq, p, a.ld_rq, c, rq);
-        st4(a.lik + lv * a.ls_lik, p, a.ld_lik, c, lk);
-      } else {
-        const float4 g4 = ld4(a.glik + lv * a.ls_glik, p, a.ld_glik, c), q4 = ld4(a.drq + lv * a.ls_drq, p, a.ld_drq, c);
-        const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float dmu, dsg;
-          lik_train_bwd(dv[k], sv[k], kv[k], nv[k], gv[k], true, dmu, dsg);
-          float dr = qv[k] * kv[k];                   // EW_MASK_SPLIT
-          float g = qv[k] * (1.0f - kv[k]);
-          g = g + 1.0f * dmu;                         // EW_AXPY (G_mu += dmu_lik)
-          dr = dr + (-1.0f) * dmu;                    // EW_AXPY (d_r -= dmu_lik)
-          dyt[k] = dyt[k] + 1.0f * dr;                // EW_AXPY into the two windows of D_y (delta_encode: r = y_top - y_sub)
-          if (a.dys) dys[k] = dys[k] + (-1.0f) * dr;
-          gacc[k] = gacc[k] + 1.0f * g;               // EW_AXPY: the levels' sum, level order
-          sacc[k] = sacc[k] + 1.0f * dsg;
-        }
-      }
-    }
-    if (BWD) {
-      st4(a.gmu, p, a.ld_gmu, c, gacc);
-      st4(a.dsigma, p, a.ld_dsigma, c, sacc);
-      st4(a.dyt, p, a.ld_dyt, c, dyt);
-      if (a.dys) st4(a.dys, p, a.ld_dys, c, dys);
-    }
-  }
-}
-
 // LDS-tiled kernel for the k3 / k5 layers (wgrad_lds.hip)
 bool wgrad2_eligible(const vam_wgrad& p);
 bool wgrad2_grid(int H, int W);
 int wgrad2_splits(const vam_wgrad& p);
 int wgrad2_launch_class(const vam_wgrad* probs, int n, hipStream_t stream);
 void wgrad2_route(const vam_wgrad& p, int out[5]);     // wn, wc, tn, tc, kp of wgrad2_tile(p)
-
-static inline unsigned sgrid(long n, int block) {
-  long g = (n + block - 1) / block;
-  return (unsigned)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-static bool a16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace vam
 
@@ -679,87 +488,6 @@ int vam_colsum(const float* dy, int ld, long n_pix, int N, float* out, float* wo
   if (int rc = check_launch("colsum_kernel")) return rc;
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3(cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, workspace, S, N, out);
   return check_launch("colsum_reduce_kernel");
-}
-
-int vam_leaky_bwd(const float* act, int ld_a, const float* dy, int ld_dy, float* dx, int ld_dx, long n_pix, int C,
-                  void* stream) {
-  VAM_REQUIRE(act && dy && dx && n_pix > 0 && C > 0 && C % 4 == 0 && ld_a % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0 && a16(act) && a16(dy) && a16(dx), "vam_leaky_bwd: bad arguments");
-  long n_vec = n_pix * (C / 4);
-  hipLaunchKernelGGL(leaky_bwd_kernel, dim3(sgrid(n_vec, 256)), dim3(256), 0, (hipStream_t)stream, act, ld_a, dy, ld_dy, dx, ld_dx, n_vec, C / 4);
-  return check_launch("leaky_bwd_kernel");
-}
-
-int vam_mul(const float* a, int ld_a, const float* b, int ld_b, float* out, int ld_out, long n_pix, int C, void* stream) {
-  VAM_REQUIRE(a && b && out && n_pix > 0 && C > 0 && C % 4 == 0 && ld_a % 4 == 0 && ld_b % 4 == 0 && ld_out % 4 == 0 && a16(a) && a16(b) && a16(out), "vam_mul: bad arguments");
-  long n_vec = n_pix * (C / 4);
-  hipLaunchKernelGGL(mul_kernel, dim3(sgrid(n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a, ld_a, b, ld_b, out, ld_out, n_vec, C / 4);
-  return check_launch("mul_kernel");
-}
-
-int vam_gauss_train(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu, const float* sigma,
-                    int ld_sigma, const float* mask, int ld_mask, const float* noise, int ld_noise, const float* grad_lik,
-                    int ld_glik, float* lik, int ld_lik, float* dmu, int ld_dmu, float* dsigma, int ld_dsigma, long n_pix,
-                    int C, void* stream) {
-  VAM_REQUIRE(y && mu && sigma && noise && n_pix > 0 && C > 0 && C % 4 == 0, "vam_gauss_train: bad arguments");
-  const bool bwd = grad_lik != nullptr;
-  VAM_REQUIRE(bwd ? (dmu && dsigma) : (lik != nullptr), "vam_gauss_train: forward needs lik, backward needs dmu and dsigma");
-  LikArgs a;
-  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.mask = mask; a.noise = noise; a.glik = grad_lik;
-  a.lik = lik; a.dmu = dmu; a.dsigma = dsigma;
-  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma; a.ld_mask = ld_mask; a.ld_noise = ld_noise;
-  a.ld_glik = ld_glik; a.ld_lik = ld_lik; a.ld_dmu = ld_dmu; a.ld_dsigma = ld_dsigma;
-  a.C4 = C / 4; a.n_vec = n_pix * (C / 4);
-  VAM_REQUIRE(a16(y) && a16(y2) && a16(mu) && a16(sigma) && a16(mask) && a16(noise) && a16(grad_lik) && a16(lik) && a16(dmu) && a16(dsigma), "vam_gauss_train: alignment");
-  VAM_REQUIRE(ld_y % 4 == 0 && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && ld_noise % 4 == 0 && (!y2 || ld_y2 % 4 == 0) && (!mask || ld_mask % 4 == 0) && (!bwd || (ld_glik % 4 == 0 && ld_dmu % 4 == 0 && ld_dsigma % 4 == 0)) && (bwd || ld_lik % 4 == 0), "vam_gauss_train: strides");
-  ProfScope ps(VAM_FAM_TAIL, (hipStream_t)stream, 0, 4.0 * (double)n_pix * C * 8);
-  if (bwd) hipLaunchKernelGGL((gauss_train_kernel<true>), dim3(sgrid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((gauss_train_kernel<false>), dim3(sgrid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("gauss_train_kernel");
-}
-
-int vam_gauss_levels_fwd(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
-                         const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls,
-                         const float* noise, int ld_noise, long noise_ls, float* rq, int ld_rq, long rq_ls,
-                         float* lik, int ld_lik, long lik_ls, int n_levels, long n_pix, int C, void* stream) {
-  VAM_REQUIRE(y && mu && sigma && mask && noise && rq && lik && n_levels > 0 && n_pix > 0 && C > 0 && C % 4 == 0,
-              "vam_gauss_levels_fwd: bad arguments");
-  auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  VAM_REQUIRE(a16(y) && a16(y2) && a16(mu) && a16(sigma) && a16(mask) && a16(noise) && a16(rq) && a16(lik), "vam_gauss_levels_fwd: alignment");
-  VAM_REQUIRE(ld_y % 4 == 0 && (!y2 || ld_y2 % 4 == 0) && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && ld_mask % 4 == 0 && ld_noise % 4 == 0 &&
-              ld_rq % 4 == 0 && ld_lik % 4 == 0 && mask_ls % 4 == 0 && noise_ls % 4 == 0 && rq_ls % 4 == 0 && lik_ls % 4 == 0,
-              "vam_gauss_levels_fwd: strides");
-  LevelsArgs a{};
-  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.mask = mask; a.noise = noise; a.rq = rq; a.lik = lik;
-  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma; a.ld_mask = ld_mask; a.ld_noise = ld_noise;
-  a.ld_rq = ld_rq; a.ld_lik = ld_lik;
-  a.ls_mask = mask_ls; a.ls_noise = noise_ls; a.ls_rq = rq_ls; a.ls_lik = lik_ls;
-  a.n_levels = n_levels; a.C4 = C / 4; a.n_vec = n_pix * (C / 4);
-  hipLaunchKernelGGL((gauss_levels_kernel<false>), dim3(sgrid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("gauss_levels_kernel");
-}
-
-int vam_gauss_levels_bwd(const float* y, int ld_y, const float* y2, int ld_y2, const float* mu, int ld_mu,
-                         const float* sigma, int ld_sigma, const float* mask, int ld_mask, long mask_ls,
-                         const float* noise, int ld_noise, long noise_ls, const float* grad_lik, int ld_glik, long glik_ls,
-                         const float* d_rq, int ld_drq, long drq_ls, float* gmu, int ld_gmu, float* dsigma, int ld_dsigma,
-                         float* dy_top, int ld_dyt, float* dy_sub, int ld_dys, int n_levels, long n_pix, int C, void* stream) {
-  VAM_REQUIRE(y && mu && sigma && mask && noise && grad_lik && d_rq && gmu && dsigma && dy_top && n_levels > 0 && n_pix > 0 &&
-              C > 0 && C % 4 == 0, "vam_gauss_levels_bwd: bad arguments");
-  auto a16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  VAM_REQUIRE(a16(y) && a16(y2) && a16(mu) && a16(sigma) && a16(mask) && a16(noise) && a16(grad_lik) && a16(d_rq) && a16(gmu) &&
-              a16(dsigma) && a16(dy_top) && a16(dy_sub), "vam_gauss_levels_bwd: alignment");
-  VAM_REQUIRE(ld_y % 4 == 0 && (!y2 || ld_y2 % 4 == 0) && ld_mu % 4 == 0 && ld_sigma % 4 == 0 && ld_mask % 4 == 0 && ld_noise % 4 == 0 &&
-              ld_glik % 4 == 0 && ld_drq % 4 == 0 && ld_gmu % 4 == 0 && ld_dsigma % 4 == 0 && ld_dyt % 4 == 0 && (!dy_sub || ld_dys % 4 == 0) &&
-              mask_ls % 4 == 0 && noise_ls % 4 == 0 && glik_ls % 4 == 0 && drq_ls % 4 == 0, "vam_gauss_levels_bwd: strides");
-  LevelsArgs a{};
-  a.y = y; a.y2 = y2; a.mu = mu; a.sigma = sigma; a.mask = mask; a.noise = noise; a.glik = grad_lik; a.drq = d_rq;
-  a.gmu = gmu; a.dsigma = dsigma; a.dyt = dy_top; a.dys = dy_sub;
-  a.ld_y = ld_y; a.ld_y2 = ld_y2; a.ld_mu = ld_mu; a.ld_sigma = ld_sigma; a.ld_mask = ld_mask; a.ld_noise = ld_noise;
-  a.ld_glik = ld_glik; a.ld_drq = ld_drq; a.ld_gmu = ld_gmu; a.ld_dsigma = ld_dsigma; a.ld_dyt = ld_dyt; a.ld_dys = ld_dys;
-  a.ls_mask = mask_ls; a.ls_noise = noise_ls; a.ls_glik = glik_ls; a.ls_drq = drq_ls;
-  a.n_levels = n_levels; a.C4 = C / 4; a.n_vec = n_pix * (C / 4);
-  hipLaunchKernelGGL((gauss_levels_kernel<true>), dim3(sgrid(a.n_vec, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("gauss_levels_kernel");
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //     window-attention backward (softmax, q/k/v and relative-position-bias gradients).
 // Formulas mirror what autograd derives for layers/layers.py:30-74, layers/gdn.py:62-75, layers/win_attention.py:84-115.
 #include "common.h"
+#include "window.h"
 #include <cstdlib>
 
 namespace vam {
@@ -31,10 +32,11 @@ enum { EW_GELU_FWD = 0, EW_GELU_BWD, EW_GATE_BWD, EW_GDN_APPLY, EW_GDN_BWD_PREP,
 template <int OP>
 __global__ void ew_kernel(const EwArgs a) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_vec; i += (long)gridDim.x * blockDim.x) {
-    const long p = i / a.C4;
-    const int c = (int)(i - p * a.C4) * 4;
-    auto ld4 = [&](int k) { return *reinterpret_cast<const float4*>(a.in[k] + p * a.ld_in[k] + c); };
-    auto st4 = [&](int k, const float* v) { *reinterpret_cast<float4*>(a.out[k] + p * a.ld_out[k] + c) = make_float4(v[0], v[1], v[2], v[3]); };
+    long p;
+    int c;
+    vec_at(i, a.C4, p, c);
+    auto ld4 = [&](int k) { return vam::ld4(a.in[k], p, a.ld_in[k], c); };
+    auto st4 = [&](int k, const float* v) { vam::st4(a.out[k], p, a.ld_out[k], c, v); };
     float4 t0 = ld4(0);
     const float x0[4] = {t0.x, t0.y, t0.z, t0.w};
     float o0[4], o1[4], o2[4];
@@ -510,10 +512,7 @@ __global__ __launch_bounds__(256) void bias_grad_reduce_kernel(const float* __re
   if (threadIdx.x == 0) dtable[r * heads + hg * hpw + h2] = red[0];
 }
 
-static inline unsigned sgrid2(long n, int block) {
-  long g = (n + block - 1) / block;
-  return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
+constexpr int GRID_CAP = 4096;
 
 // several AXPY updates of independent windows in one launch (blockIdx.y = job): what ew_kernel<EW_AXPY> computes, per job
 struct AxpyJob {
@@ -531,16 +530,21 @@ struct AxpyGroupArgs {
 __global__ __launch_bounds__(256) void axpy_group_kernel(const AxpyGroupArgs g) {
   const AxpyJob& J = g.j[blockIdx.y];
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < J.n_vec; v += (long)gridDim.x * 256) {
-    const long p = v / J.C4;
-    const int c = (int)(v - p * J.C4) * 4;
-    const float4 x = *reinterpret_cast<const float4*>(J.a + p * J.lda + c), y = *reinterpret_cast<const float4*>(J.b + p * J.ldb + c);
-    *reinterpret_cast<float4*>(J.o + p * J.ldo + c) = make_float4(x.x + J.coef * y.x, x.y + J.coef * y.y, x.z + J.coef * y.z, x.w + J.coef * y.w);
+    long p;
+    int c;
+    vec_at(v, J.C4, p, c);
+    float x[4], y[4], o[4];
+    ld4(J.a, p, J.lda, c, x);
+    ld4(J.b, p, J.ldb, c, y);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = x[k] + J.coef * y[k];
+    st4(J.o, p, J.ldo, c, o);
   }
 }
 
 template <int OP>
 static int launch_ew(const EwArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((ew_kernel<OP>), dim3(sgrid2(a.n_vec, 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((ew_kernel<OP>), dim3(stream_grid(a.n_vec, 256, GRID_CAP)), dim3(256), 0, s, a);
   return check_launch("ew_kernel");
 }
 
@@ -557,10 +561,13 @@ int vam_train_axpy_group(const vam_ew* jobs, int n, void* stream) {
   for (int i = 0; i < n; ++i) {
     const vam_ew& e = jobs[i];
     VAM_REQUIRE(e.n_pix > 0 && e.C > 0 && e.C % 4 == 0, "vam_train_axpy_group: job %d extent", i);
-    VAM_REQUIRE(e.in[0].ptr && e.in[1].ptr && e.out[0].ptr, "vam_train_axpy_group: job %d needs in0, in1, out0", i);
-    VAM_REQUIRE(e.in[0].ld % 4 == 0 && e.in[1].ld % 4 == 0 && e.out[0].ld % 4 == 0 && e.in[0].ld >= e.C && e.in[1].ld >= e.C && e.out[0].ld >= e.C,
-                "vam_train_axpy_group: job %d row pitches", i);
-    VAM_REQUIRE((((uintptr_t)e.in[0].ptr | (uintptr_t)e.in[1].ptr | (uintptr_t)e.out[0].ptr) & 15) == 0, "vam_train_axpy_group: job %d alignment", i);
+    char job[16];
+    snprintf(job, sizeof job, "job %d ", i);
+    VAM_CHECK_WINDOWS("vam_train_axpy_group", e.C,
+                      {{"in0", e.in[0].ptr, e.in[0].ld, 0, true, 16, true},
+                       {"in1", e.in[1].ptr, e.in[1].ld, 0, true, 16, true},
+                       {"out0", e.out[0].ptr, e.out[0].ld, 0, true, 16, true}},
+                      {"needs in0, in1, out0", "alignment", "row pitches", job});
     AxpyJob& J = g.j[i];
     J.a = e.in[0].ptr; J.b = e.in[1].ptr; J.o = const_cast<float*>(e.out[0].ptr);
     J.lda = e.in[0].ld; J.ldb = e.in[1].ld; J.ldo = e.out[0].ld;
@@ -570,7 +577,7 @@ int vam_train_axpy_group(const vam_ew* jobs, int n, void* stream) {
     most = J.n_vec > most ? J.n_vec : most;
   }
   for (int i = n; i < VAM_MAX_EW_GROUP; ++i) g.j[i] = AxpyJob{nullptr, nullptr, nullptr, 0, 0, 0, 1, 0, 0.f};
-  hipLaunchKernelGGL(axpy_group_kernel, dim3(sgrid2(most, 256), n), dim3(256), 0, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(axpy_group_kernel, dim3(stream_grid(most, 256, GRID_CAP), n), dim3(256), 0, (hipStream_t)stream, g);
   return check_launch("axpy_group_kernel");
 }
 
@@ -580,12 +587,12 @@ int vam_train_elementwise(int op, const vam_ew* e, void* stream) {
   for (int k = 0; k < 4; ++k) {
     a.in[k] = e->in[k].ptr;
     a.ld_in[k] = e->in[k].ld;
-    if (a.in[k]) VAM_REQUIRE(a.ld_in[k] % 4 == 0 && ((uintptr_t)a.in[k] & 15) == 0, "vam_train_elementwise: input %d alignment", k);
+    if (a.in[k]) VAM_REQUIRE(a.ld_in[k] % 4 == 0 && aligned(a.in[k], 16), "vam_train_elementwise: input %d alignment", k);
   }
   for (int k = 0; k < 3; ++k) {
     a.out[k] = const_cast<float*>(e->out[k].ptr);
     a.ld_out[k] = e->out[k].ld;
-    if (a.out[k]) VAM_REQUIRE(a.ld_out[k] % 4 == 0 && ((uintptr_t)a.out[k] & 15) == 0, "vam_train_elementwise: output %d alignment", k);
+    if (a.out[k]) VAM_REQUIRE(a.ld_out[k] % 4 == 0 && aligned(a.out[k], 16), "vam_train_elementwise: output %d alignment", k);
   }
   a.C4 = e->C / 4;
   a.n_vec = e->n_pix * (e->C / 4);

@@ -5,7 +5,7 @@ at the end of this file).
 
 Only the Rate-Enhancement blocks train; every step is
     checkpoint latent at the check level (no grad)  ->  training-mode forward at a sampled quality
-    ->  RateLoss  ->  backward (HIP kernels, csrc/train.hip)  ->  gradient all-reduce (RCCL)  ->  clip  ->  Adam.
+    ->  RateLoss  ->  backward (HIP kernels, csrc/train.hip, csrc/entropy.hip, csrc/elementwise.hip)  ->  gradient all-reduce (RCCL)  ->  clip  ->  Adam.
 Images shard across ranks; the only collective is the all-reduce of the REM gradients
 (15.2 MB per REM in fp32), issued as ONE flat bucket: xGMI rings are per-link bound, one
 large message beats 420 small ones.

@@ -977,18 +977,38 @@ def new_iview(B, H, W, C_, device="cuda") -> IView:
     return IView(torch.empty((B, H, W, C_), dtype=torch.int32, device=device), 0, C_)
 
 
+def _win(v):
+    """(ptr, pixel stride) of a window, or (None, 0) for an absent one."""
+    return (v.ptr, v.ld) if v is not None else (None, 0)
+
+
+def _levels_win(v, n: int, ref: View, ls: Optional[int] = None):
+    """(ptr, pixel stride, level stride in elements) of a per-level operand of ``n`` levels over ``ref``'s window, or
+    (None, 0, 0): by default the levels are consecutive blocks of ``ref.B`` images of ``v``'s buffer; with ``ls`` they are
+    windows of one [B, ...] buffer ``ls`` elements apart."""
+    if v is None:
+        return None, 0, 0
+    nb, ld = v.buf.shape[0], v.buf.shape[3]
+    assert v.C == ref.C and tuple(v.buf.shape[1:3]) == (ref.H, ref.W), (v.C, ref.C, tuple(v.buf.shape))
+    if ls is None:
+        assert nb == n * ref.B, (nb, n, ref.B)
+        ls = ref.B * ref.H * ref.W * ld
+    else:
+        assert nb == ref.B
+    return v.ptr, ld, ls
+
+
 def gauss_tail(y: View, mu: View, sigma: View, *, y2: Optional[View] = None, mask: Optional[View] = None,
                yhat: Optional[View] = None, lik: Optional[View] = None, sym=None,
                log2sum: Optional[torch.Tensor] = None):
     n_pix = y.n_pix
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
     if sym is None:
         sym_ptr, sym_ld = None, 0
     elif isinstance(sym, IView):
         sym_ptr, sym_ld = sym.ptr, sym.ld
     else:
         sym_ptr, sym_ld = sym.data_ptr(), sym.shape[-1]
-    L.check(L.load().vam_gauss_tail(*p(y), *p(y2), *p(mu), *p(sigma), *p(mask), *p(yhat), *p(lik), sym_ptr, sym_ld,
+    L.check(L.load().vam_gauss_tail(*_win(y), *_win(y2), *_win(mu), *_win(sigma), *_win(mask), *_win(yhat), *_win(lik), sym_ptr, sym_ld,
                                     log2sum.data_ptr() if log2sum is not None else None, y.H * y.W, n_pix, y.C,
                                     stream_ptr()), "vam_gauss_tail")
 
@@ -1000,15 +1020,9 @@ def gauss_levels_eval(y: View, mu: View, sigma: View, mask: View, n_levels: int,
     of :func:`gauss_tail`, bit for bit.  ``mask`` / ``yhat`` / ``lik`` / ``sym`` hold the levels as consecutive image
     blocks ([L * B, H, W, ld], level l = images l*B ..); ``log2sum`` [L, B] float64 receives level l's per-image sums."""
     B = y.B
-    def lv(v):
-        if v is None:
-            return None, 0, 0
-        nb, ld = v.buf.shape[0], v.buf.shape[3]
-        assert nb == n_levels * B and tuple(v.buf.shape[1:3]) == (y.H, y.W) and v.C == y.C, (nb, n_levels, B, v.C, y.C)
-        return v.ptr, ld, B * y.H * y.W * ld
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
     assert log2sum is None or (log2sum.dtype == torch.float64 and log2sum.is_contiguous() and log2sum.numel() == n_levels * B)
-    L.check(L.load().vam_gauss_levels_eval(*p(y), *p(y2), *p(mu), *p(sigma), *lv(mask), *lv(yhat), *lv(lik), *lv(sym),
+    L.check(L.load().vam_gauss_levels_eval(*_win(y), *_win(y2), *_win(mu), *_win(sigma), *_levels_win(mask, n_levels, y), *_levels_win(yhat, n_levels, y),
+                                           *_levels_win(lik, n_levels, y), *_levels_win(sym, n_levels, y),
                                            log2sum.data_ptr() if log2sum is not None else None, y.H * y.W, n_levels,
                                            y.n_pix, y.C, stream_ptr()), "vam_gauss_levels_eval")
 
@@ -1045,8 +1059,7 @@ def gauss_layer_bits(y: View, mu: View, sigma: View, layer: torch.Tensor, n_leve
     for t, dt in ((bits, torch.float64), (count, torch.int64)):
         assert t.dtype == dt and t.is_contiguous(), (t.dtype, tuple(t.shape))
         assert t.numel() == B * (n_levels + 1) or (B == 1 and t.numel() > n_levels), (tuple(t.shape), B, n_levels)
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_gauss_layer_bits(*p(y), *p(y2), *p(mu), *p(sigma), layer.data_ptr(), ld_layer, n_levels,
+    L.check(L.load().vam_gauss_layer_bits(*_win(y), *_win(y2), *_win(mu), *_win(sigma), layer.data_ptr(), ld_layer, n_levels,
                                           bits.data_ptr(), count.data_ptr(), pix_per_item, y.n_pix, y.C, stream_ptr()),
             "vam_gauss_layer_bits")
 
@@ -1088,8 +1101,7 @@ def coded_layer_bits(y: View, mu: View, sigma: View, layer: Optional[torch.Tenso
     assert layer is None or (layer.dtype == torch.uint8 and layer.is_contiguous() and tuple(layer.shape) == (B, y.H, y.W, y.C))
     assert scale_table.dtype == torch.float32 and scale_table.is_contiguous() and scale_table.device == y.buf.device
     _coded_bins(bits, count, B * (y.C // max(chans_per_stream, 1)), n_levels)
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_coded_layer_bits(*p(y), *p(y2), *p(mu), *p(sigma), layer.data_ptr() if layer is not None else None, y.C,
+    L.check(L.load().vam_coded_layer_bits(*_win(y), *_win(y2), *_win(mu), *_win(sigma), layer.data_ptr() if layer is not None else None, y.C,
                                           n_levels, scale_table.data_ptr(), scale_table.numel(), C.byref(tables.struct),
                                           chans_per_stream, bits.data_ptr(), count.data_ptr(), y.H * y.W, y.n_pix, y.C,
                                           stream_ptr()), "vam_coded_layer_bits")
@@ -1125,17 +1137,16 @@ def dequantize(sym: IView, mu: Optional[View], out: View):
 
 def eb_forward(z: View, params: torch.Tensor, zhat: Optional[View], lik: Optional[View],
                log2sum: Optional[torch.Tensor] = None, sym: Optional[IView] = None, noise: Optional[View] = None):
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_eb_forward_noise(z.ptr, z.ld, params.data_ptr(), z.C, *p(zhat), *p(lik), *p(sym),
+    L.check(L.load().vam_eb_forward_noise(z.ptr, z.ld, params.data_ptr(), z.C, *_win(zhat), *_win(lik), *_win(sym),
                                           log2sum.data_ptr() if log2sum is not None else None, z.H * z.W, z.n_pix,
-                                          *p(noise), stream_ptr()), "vam_eb_forward")
+                                          *_win(noise), stream_ptr()), "vam_eb_forward")
 
 
 def add(a: View, b: View, out: View):
     L.check(L.load().vam_add(a.ptr, a.ld, b.ptr, b.ld, out.ptr, out.ld, a.n_pix, a.C, stream_ptr()), "vam_add")
 
 
-# ---- REM fine-tune backward pieces (csrc/train.hip)
+# ---- REM fine-tune backward pieces (csrc/train.hip, csrc/elementwise.hip, csrc/entropy.hip)
 def pack_conv_dgrad(weight: torch.Tensor) -> Packed:
     """Weights of the data-gradient conv of a stride-1 ``nn.Conv2d`` (taps flipped, channel roles swapped)."""
     n_out, c_in, kh, kw = weight.shape
@@ -1236,33 +1247,20 @@ def gauss_train(y: View, mu: View, sigma: View, noise: View, *, y2: Optional[Vie
                 lik: Optional[View] = None, grad_lik: Optional[View] = None, dmu: Optional[View] = None,
                 dsigma: Optional[View] = None):
     """Noisy-likelihood forward (``lik``) or backward (``grad_lik`` -> ``dmu``, ``dsigma``)."""
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_gauss_train(*p(y), *p(y2), *p(mu), *p(sigma), *p(mask), *p(noise), *p(grad_lik), *p(lik),
-                                     *p(dmu), *p(dsigma), y.n_pix, y.C, stream_ptr()), "vam_gauss_train")
+    L.check(L.load().vam_gauss_train(*_win(y), *_win(y2), *_win(mu), *_win(sigma), *_win(mask), *_win(noise), *_win(grad_lik), *_win(lik),
+                                     *_win(dmu), *_win(dsigma), y.n_pix, y.C, stream_ptr()), "vam_gauss_train")
 
-
-
-def _level_arg(v: View, n: int, ref: View, ls: Optional[int]):
-    """(ptr, ld, level stride in floats) of a per-level operand: default stride = the next ``ref.B`` images of ``v``."""
-    assert v.C == ref.C and v.H == ref.H and v.W == ref.W
-    if ls is None:
-        assert v.B == n * ref.B, (v.B, n, ref.B)
-        ls = ref.B * ref.H * ref.W * v.ld
-    else:
-        assert v.B == ref.B
-    return v.ptr, v.ld, ls
 
 
 def gauss_levels_fwd(y: View, mu: View, sigma: View, mask: View, noise: View, rq: View, lik: View, n_levels: int, *,
                      y2: Optional[View] = None, noise_ls: Optional[int] = None, lik_ls: Optional[int] = None):
-    """Progressive tail of ``n_levels`` quality levels over one (y, y2, mu, sigma) window (csrc/train.hip): per level
+    """Progressive tail of ``n_levels`` quality levels over one (y, y2, mu, sigma) window (csrc/entropy.hip): per level
     rq = round(r - mu) * m + mu and the noisy likelihood.  ``mask`` / ``rq`` hold the levels as consecutive image blocks
     ([L * B, H, W, ld]); ``noise`` / ``lik`` likewise, or — with ``noise_ls`` / ``lik_ls`` — windows of one [B, ...]
     buffer whose level l starts ``l * ls`` floats further (e.g. consecutive channel blocks)."""
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_gauss_levels_fwd(*p(y), *p(y2), *p(mu), *p(sigma), *_level_arg(mask, n_levels, y, None),
-                                          *_level_arg(noise, n_levels, y, noise_ls), *_level_arg(rq, n_levels, y, None),
-                                          *_level_arg(lik, n_levels, y, lik_ls), n_levels, y.n_pix, y.C, stream_ptr()),
+    L.check(L.load().vam_gauss_levels_fwd(*_win(y), *_win(y2), *_win(mu), *_win(sigma), *_levels_win(mask, n_levels, y, None),
+                                          *_levels_win(noise, n_levels, y, noise_ls), *_levels_win(rq, n_levels, y, None),
+                                          *_levels_win(lik, n_levels, y, lik_ls), n_levels, y.n_pix, y.C, stream_ptr()),
             "vam_gauss_levels_fwd")
 
 
@@ -1272,10 +1270,9 @@ def gauss_levels_bwd(y: View, mu: View, sigma: View, mask: View, noise: View, gr
     """Backward of :func:`gauss_levels_fwd` with the straight-through rounding under each level's mask: writes
     gmu = sum_l (d_rq_l * (1 - m_l) + dmu_l) and dsigma = sum_l dsigma_l, and adds sum_l d_r_l into ``dy_top`` (and its
     negative into ``dy_sub``) in place — level by level, as the unfused launches would."""
-    def p(v): return (v.ptr, v.ld) if v is not None else (None, 0)
-    L.check(L.load().vam_gauss_levels_bwd(*p(y), *p(y2), *p(mu), *p(sigma), *_level_arg(mask, n_levels, y, None),
-                                          *_level_arg(noise, n_levels, y, noise_ls), *_level_arg(grad_lik, n_levels, y, glik_ls),
-                                          *_level_arg(d_rq, n_levels, y, None), *p(gmu), *p(dsigma), *p(dy_top), *p(dy_sub),
+    L.check(L.load().vam_gauss_levels_bwd(*_win(y), *_win(y2), *_win(mu), *_win(sigma), *_levels_win(mask, n_levels, y, None),
+                                          *_levels_win(noise, n_levels, y, noise_ls), *_levels_win(grad_lik, n_levels, y, glik_ls),
+                                          *_levels_win(d_rq, n_levels, y, None), *_win(gmu), *_win(dsigma), *_win(dy_top), *_win(dy_sub),
                                           n_levels, y.n_pix, y.C, stream_ptr()), "vam_gauss_levels_bwd")
 
 

@@ -1,6 +1,6 @@
 """The contract of the inference likelihood and rate kernels in float64.  TEST HELPER (torch and numpy on the CPU).
 
-Kernels (csrc/elementwise.hip): ``gauss_tail_kernel``, ``gauss_levels_eval_kernel``, ``gauss_levels_decode_kernel``,
+Kernels (csrc/entropy.hip): ``gauss_tail_kernel``, ``gauss_levels_eval_kernel``, ``gauss_levels_decode_kernel``,
 ``gauss_layer_bits_kernel``, ``build_indexes_kernel`` and the evaluation path of ``eb_forward_kernel``.
 
 The machinery is the training contract's (tests/train_ew_contract.py): every chain is ONE body in the kernel's order of

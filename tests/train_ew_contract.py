@@ -1,8 +1,8 @@
 """The contract of the training element-wise and likelihood kernels in float64.  TEST HELPER (torch and numpy on the CPU).
 
-Kernels: ``ew_kernel`` / ``axpy_group_kernel`` (csrc/train_gs.hip), ``leaky_bwd`` / ``mul`` / ``gauss_train`` /
-``gauss_levels`` (csrc/train.hip), ``eb_train_bwd`` / ``ps2_unshuffle`` / ``upsample2_zero`` (csrc/train_full.hip) and the
-noisy likelihood of ``eb_forward_kernel`` (csrc/elementwise.hip).
+Kernels: ``ew_kernel`` / ``axpy_group_kernel`` (csrc/train_gs.hip), ``leaky_bwd`` / ``mul`` / ``ps2_unshuffle`` /
+``upsample2_zero`` (csrc/elementwise.hip), ``gauss_train`` / ``gauss_levels`` / ``eb_train_bwd`` and the
+noisy likelihood of ``eb_forward_kernel`` (csrc/entropy.hip).
 
 Every operation is ONE function body written in the kernel's order of operations over a ``Tape``:
   * ``ref64``  the body in float64 (inputs are the fp32 values converted exactly) — the reference;
